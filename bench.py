@@ -13,10 +13,15 @@ Workload - ONE workload at every N (BASELINE.json's metric is the 1 / 2 / 4 / 8-
   BASELINE.json configs[2] (N = 1) = configs[3] per GPU (N > 1): joint CTC/attention (lambda = 0.3) encoder-decoder, bf16,
          32 utterances per GPU, T=500, F=80, V=4232, synthetic N(0,1) features, random-init weights; at N > 1 weak scaling with the
          bucketed RCCL all-reduce overlapped with backward.  --config ctc|joint overrides.
-  Extra keys at N = 1: configs[1] (6-layer encoder + CTC-only: `ctc_ms_per_step`, `ctc_utterances_per_s`), the reference's dropout 0.1
-         recipe on both models, configs[4] per GPU (long-form), training from waveforms - each timed the same way.
+  Extra keys at N = 1 (with --full): configs[1] (6-layer encoder + CTC-only: `ctc_ms_per_step`, `ctc_utterances_per_s`), the reference's
+         dropout 0.1 recipe on both models, configs[4] per GPU (long-form), training from waveforms - each timed the same way.
 
-Extra objects on the JSON line:
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the result line.  --dump-outputs DIR then
+writes what one step of the timed path hands its caller when it starts from the seeded state the timed steps started from (Run.snapshot,
+dump_outputs): same model, engine, streams and kernels as the timed steps, run after them.  Everything else on the line below needs --full
+(--no-kernel-timer / --no-extras / --no-cpu-baseline switch parts of it off again).
+
+Extra objects on the JSON line (with --full):
   roofline      the GEMM family with the most time IN THE STEP (weight-gradient stream live beside the main stream, as in the timed
                 region): algorithmic FLOP / HIP-event time of its launches, against the dense bf16 MFMA peak (2.5 PFLOP/s);
                 `frac_standalone` = the same launches with the overlap off; `roofline_other_gemm_family` = the other family.
@@ -64,6 +69,12 @@ def parse(argv=None):
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra single-GPU measurements (joint model, dropout 0.1)")
     ap.add_argument("--cpu-sample-batch", type=int, default=32)
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the per-kernel / roofline passes, "
+                    "the other single-GPU configurations and the CPU baseline (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, run the timed path once more from the seeded state "
+                    "the timed steps started from and write what it computed as DIR/<name>.npy (float32 / float64): the step's metrics and a "
+                    "fixed, seeded sample of the updated parameters and of the gradients.  The engine keeps its default mode; "
+                    "ASR_DETERMINISTIC=1 makes the files repeat bit for bit (fixed-order reductions, slower)")
     ap.add_argument("--plumbing", action="store_true", help="tests only: form the process group, exchange one tensor, print the line "
                     "skeleton - no GPU work (drives the N-rank launcher on a CPU-only machine)")
     return ap.parse_args(argv)
@@ -219,6 +230,40 @@ class Run:
         for _ in range(n):
             self.last, _ = runner.iterate(self.pack, optimizer=self.opt, is_train=True)
 
+    def _step_state(self):
+        f = self.model._flat
+        return [t for t in (f.p, f.m, f.v, f.lp) if t is not None]
+
+    def snapshot(self):
+        """Copy what a training step changes - flat fp32 parameters, their bf16 copy, Adam moments, the Noam / Adam step counters and
+        learning rates, the dropout step seed - while it still holds the seeded starting state (before the warm-up)."""
+        m, opt = self.model, self.opt
+        m._ensure_engine(self.pack.wave.device)      # the flat buffers exist from the first step on: allocate them now, as that step would
+        self._snap = ([t.clone() for t in self._step_state()], opt._step, opt._rate, getattr(opt.optimizer, "_t", 0),
+                      [g["lr"] for g in opt.optimizer.param_groups], m._step_seed)
+
+    def replay_first_step(self):
+        """One more step of the timed path (same runner, engine, streams and kernels) from the state snapshot() copied.  The last of the
+        W + K timed steps starts from a state the earlier steps reached through fp32 atomics that add in arrival order: from run to run it
+        differs by more than rounding (Adam steps of near-zero gradients change sign, bf16 weight copies round the other way), and so would
+        that step's outputs.  This step's inputs are the same in every run."""
+        torch, m, opt = self.torch, self.model, self.opt
+        bufs, opt._step, opt._rate, t, lrs, m._step_seed = self._snap
+        torch.cuda.synchronize()
+        for dst, src in zip(self._step_state(), bufs):
+            dst.copy_(src)
+        m._flat.version += 1      # the bf16 weights changed: the engine's transposed copies are stale
+        if hasattr(opt.optimizer, "_t"):
+            opt.optimizer._t = t
+        for g, lr in zip(opt.optimizer.param_groups, lrs):
+            g["lr"] = lr
+        if opt._dev is not None:
+            opt._dev[0].fill_(opt._step)      # the device copy of the step counter the fused optimizer reads
+        self._snap = None
+        torch.cuda.synchronize()      # the copies are done before the step's side streams read the weights
+        self.steps(1)
+        torch.cuda.synchronize()
+
     def timed(self, warmup, steps, strict=True):
         """`warmup` untimed steps, then exactly `steps` timed ones between barrier + synchronize.  The caching allocator must not
         grow inside the timed region (a hipMalloc synchronises the device): the engine keeps the operands of its side-stream kernels
@@ -367,6 +412,39 @@ class Run:
         return timer.summary()
 
 
+DUMP_SAMPLE = 1 << 20      # elements of the parameter / gradient sample (4 MB per file)
+DUMP_SEED = 0
+
+
+def dump_outputs(run, out_dir):
+    """What the step of Run.replay_first_step handed its caller, as .npy files under `out_dir`: every metric of `iterate` (loss and,
+    per model, ce / ctc / cer) in float64, and - the model's parameters after the step and the step's gradients, ~40 M elements each -
+    the same fixed, seeded sample of DUMP_SAMPLE positions of both (named_parameters() flattened and concatenated in that order) in
+    float32.  The step's inputs (batch, weights, optimizer state) are the same in every run, so two builds of the project compare output
+    for output; the default engine's fp32 atomics leave differences of rounding between runs."""
+    import numpy as np
+    torch = run.torch
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for k, v in run.last.items():
+        a = v.detach().double().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+        names.append(k)
+    params = [p for _, p in run.model.named_parameters()]
+    offs = np.cumsum([0] + [p.numel() for p in params])
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(offs[-1], size=min(DUMP_SAMPLE, offs[-1]), replace=False))
+    vals, grads = [], []
+    for i, p in enumerate(params):      # gathered parameter by parameter: no copy of the whole model on the device
+        lo, hi = np.searchsorted(idx, offs[i]), np.searchsorted(idx, offs[i + 1])
+        j = torch.from_numpy(idx[lo:hi] - offs[i]).to(p.device)
+        vals.append(p.detach().reshape(-1)[j].float().cpu())
+        grads.append(torch.zeros(hi - lo) if p.grad is None else p.grad.detach().reshape(-1)[j].float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(vals).numpy())
+    np.save(os.path.join(out_dir, "grads_sample.npy"), torch.cat(grads).numpy())
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(names + ['params_sample', 'grads_sample'])}")
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -407,6 +485,7 @@ def main():
     torch.cuda.set_device(dev_idx)
     dev = torch.device("cuda", dev_idx)
     use_dp = world > 1 or os.environ.get("ASR_FORCE_DP") == "1"    # ASR_FORCE_DP: exercise the RCCL path with one rank
+    from asr_chinese_e2e_amd import kernels as K
     if use_dp:
         from asr_chinese_e2e_amd import dist as D
         os.environ["LOCAL_RANK"] = str(dev_idx)
@@ -442,16 +521,24 @@ def main():
         raise SystemExit(3)
 
     log(f"rank {rank}/{world}: {config} model on {dev}, warm-up {args.warmup} steps")
+    if args.dump_outputs:
+        run.snapshot()      # the seeded starting state, before the warm-up
     dt = run.timed(args.warmup, args.steps, strict=(world == 1))      # N > 1 has never run on xGMI: count and report, do not end the run
     alloc_growth = run.alloc_growth
     headline_peak = run.peak_gb
     headline_chunks = run.chunk_ms
     headline_gc = run.gc_passes
     log(f"timed region done: {1e3 * dt / args.steps:.2f} ms/step")
+    if args.dump_outputs:
+        timed_last = run.last
+        run.replay_first_step()      # on every rank: under data parallelism the step's collectives need them all
+        if rank == 0:
+            dump_outputs(run, args.dump_outputs)
+        run.last = timed_last        # final_loss stays the last timed step's
     summary, n_inst = None, min(args.steps, 10)
     lib_gemm_per_step = None
     in_step = None
-    if not args.no_kernel_timer:
+    if args.full and not args.no_kernel_timer:
         summary = run.kernel_pass(n_inst)
         lib_gemm_per_step = run.lib_gemm_calls_per_step
         in_step = run.kernel_pass(n_inst, in_step=True)
@@ -486,7 +573,7 @@ def main():
             log(f"REPLICAS DIVERGED: parameter checksum min {lo!r} max {hi!r} over {world} ranks")
 
     extras = {}
-    if world == 1 and not use_dp and not args.no_extras and rank == 0:
+    if args.full and world == 1 and not use_dp and not args.no_extras and rank == 0:
         # the other single-GPU configurations, timed the same way (shorter).
         # The blocks of the finished Run go back to the caching allocator and the next Run takes them from there: NO
         # torch.cuda.empty_cache() in between.  Round 3 had one, and the driver's numbers for these keys were 12 - 38 % above the
@@ -547,6 +634,7 @@ def main():
             "value": utt, "unit": "utterances/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": step_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "bf16", "data": "synthetic", "ranks_formed": world, "allocator_growth_in_timed_region": alloc_growth,
+            "deterministic": K.deterministic(),      # True only under ASR_DETERMINISTIC=1: fixed-order reductions, not the default step
             "frames_per_s": utt * args.frames, "final_loss": loss,
             "ms_per_step_by_fifth": headline_chunks,      # rank 0's stream events inside the timed region: a stall of the box shows as one outlier
             "config": {"workload": (("configs[3]: data-parallel " if world > 1 else "configs[2]: ") + "joint CTC/attention (lambda=0.3) encoder-decoder" if joint else
@@ -617,7 +705,7 @@ def main():
                                    "in_step_avg_us: a second instrumented pass with both streams live, as in the timed region (includes what a kernel loses to "
                                    "the kernels beside it); bytes / FLOP per launch are the algorithmic figures of SURVEY.md 8(d) / DESIGN.md section 4; "
                                    "hbm_frac against 8 TB/s, mfma_frac against 2.5 PFLOP/s dense bf16")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, config)      # the SAME workload as `value`
             if not args.no_extras:      # and the other model of the extra keys, on a smaller sample
                 other = "joint" if config == "ctc" else "ctc"

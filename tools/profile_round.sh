@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 40 --warmup 10 --no-extras --no-cpu-baseline"      # the headline workload (round 5: the joint model, configs[2])
+ARGS="--steps 40 --warmup 10 --full --no-extras --no-cpu-baseline"      # the headline workload with its kernel-timer passes (round 5: the joint model, configs[2])
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o p --output-format csv -- python3 $R/bench.py $ARGS > $OUT/bench_profiled.json 2> $OUT/trace.err
 echo "trace done"
 # counter passes: on the CTC-only configuration (the same GEMM / attention / LayerNorm kernels at the same shapes; under counter collection the joint
