@@ -235,6 +235,9 @@ class _SpeechTransformer(BaseModel):
             eng.step_seed = self._step_seed
         x = wave if wave.dtype == eng.dtype else wave.to(eng.dtype)
         x = x.contiguous()
+        if input.tgt_for_input is None:      # audio-only batch (inference): no label preprocessing, no decoder pass in forward()
+            self._tgt_len32 = None
+            return eng, x, self._len32_of(input.wave_len, (), ()).contiguous(), None
         tgt = input.tgt_for_input.contiguous()
         # the batch contract hands lengths over as int64 (ai_shell_1.py:75-88): the label preprocessing launch also makes the int32 copies
         lens64 = [t.contiguous() for t in (input.wave_len, input.tgt_len) if t is not None and t.dtype == torch.int64 and t.device == tgt.device]
@@ -253,13 +256,14 @@ class _SpeechTransformer(BaseModel):
         return t.to(torch.int32)
 
     def forward(self, input):
-        """transformer_official.py:68-81 (inference-style forward; no gradients)."""
+        """transformer_official.py:68-81 (inference-style forward; no gradients).  A batch without a transcript (only wave / wave_len)
+        gets the encoder output and the CTC logits; pred / gold need tgt_for_input."""
         eng, x, wave_len, prep = self._prepare(input)
         B, T, _ = x.shape
         enc, _ = eng.encoder_fwd(x, wave_len, self.attn_window)
         pack = Pack()
         pack.add(encoder_out=enc.view(B, T, -1))
-        if self.use_decoder:
+        if self.use_decoder and prep is not None:      # teacher forcing needs the transcript
             cross_len = self._tgt_len32 if self.cross_mask == "ref_compat" else wave_len
             pred, _ = eng.decoder_fwd(prep, enc, cross_len, B, T)
             pack.add(pred=pred.view(B, -1, self.V), gold=prep[1].long())
@@ -381,6 +385,110 @@ class _SpeechTransformer(BaseModel):
         ids, lens = K.ctc_greedy_decode(out.ctc_logits.contiguous(), input.wave_len.to(torch.int32), PAD_ID)
         ids, lens = ids.cpu(), lens.cpu()
         return [ids[b, : int(lens[b])].tolist() for b in range(ids.shape[0])]
+
+    def frame_seconds(self):
+        """Duration of one encoder frame: lfr_n * hop / sample_rate (the low-frame-rate stacking keeps every lfr_n-th 10 ms
+        feature frame; 30 ms with the AISHELL-1 defaults lfr_n = 3, sample_rate = 16000)."""
+        from ..data_handler.processor import HOP
+        return int(getattr(self.config, "lfr_n", 3) or 3) * HOP / float(getattr(self.config, "sample_rate", 16000) or 16000)
+
+    def ctc_align(self, input, labels=None):
+        """CTC forced alignment (Viterbi over the CTC head, asr_ctc_align) of a batch.
+        labels=None aligns the batch's own transcripts (tgt_for_input); otherwise one list of token ids per utterance.
+        Returns per utterance {"score": log-probability of the best path (-inf when the labels do not fit the frames),
+        "tokens": [{"id", "token", "start_frame", "end_frame", "start_s", "end_s", "logp"}]}, where frames count encoder frames,
+        start_s = start_frame * d and end_s = (end_frame + 1) * d with d = frame_seconds(), and logp is the sum of the token's
+        log-probabilities over its frames.  Tokens of an utterance that cannot be aligned carry None for the frames, times and logp."""
+        if not self.use_ctc:
+            raise RuntimeError("this model has no CTC head (config.ctc_weight = 0)")
+        if labels is None:
+            if input.tgt_for_input is None:
+                raise ValueError("ctc_align(labels=None) aligns the batch's transcripts, and this batch has none: pass labels")
+            prep = K.dec_preprocess(input.tgt_for_input.contiguous(), SOS_ID, EOS_ID)
+            lab, lens = prep[2].cpu(), prep[4].cpu().tolist()
+            labels = [lab[b, : lens[b]].tolist() for b in range(lab.shape[0])]
+        return self._align_lists(self._ctc_logits(input), input.wave_len, labels)
+
+    def _ctc_logits(self, input):
+        eng = self._ensure_engine(input.wave.device)
+        was_training = eng.training
+        try:
+            with torch.no_grad():
+                return self.forward(input).ctc_logits
+        finally:
+            eng.training = was_training
+
+    def _align_lists(self, logits, wave_len, labels, alignable=None):
+        """One asr_ctc_align launch for a batch of id lists; entries with alignable[b] False are not aligned (times None)."""
+        B, T, V = logits.shape
+        if len(labels) != B:
+            raise ValueError(f"{len(labels)} label sequences for a batch of {B}")
+        labels = [[int(x) for x in l] for l in labels]
+        ok = [True] * B if alignable is None else list(alignable)
+        for b, l in enumerate(labels):
+            if ok[b] and (len(l) > 255 or any(x < 0 or x >= V for x in l)):
+                raise ValueError(f"utterance {b}: labels must be at most 255 ids in [0, {V})")
+        use = [l if ok[b] else [] for b, l in enumerate(labels)]
+        Lmax = max([len(l) for l in use] + [0])
+        lab = torch.zeros(B, Lmax, dtype=torch.int32)
+        for b, l in enumerate(use):
+            if l:
+                lab[b, : len(l)] = torch.tensor(l, dtype=torch.int32)
+        dev = logits.device
+        lab_len = torch.tensor([len(l) for l in use], dtype=torch.int32)
+        _, spans, tlp, score = K.ctc_align(logits, wave_len.to(torch.int32).contiguous(), lab.to(dev), lab_len.to(dev), blank=PAD_ID,
+                                           ws=self._engine.ws)
+        spans, tlp, score = spans.cpu().tolist(), tlp.cpu().tolist(), score.cpu().tolist()
+        d = self.frame_seconds()
+        id2tok = self.vocab._id2token
+        out = []
+        for b, l in enumerate(labels):
+            timed = ok[b] and score[b] != float("-inf")
+            toks = []
+            for i, x in enumerate(l):
+                st, en = (spans[b][i][0], spans[b][i][1]) if timed else (None, None)
+                toks.append({"id": x, "token": id2tok[x] if 0 <= x < len(id2tok) else None, "start_frame": st, "end_frame": en,
+                             "start_s": st * d if timed else None, "end_s": (en + 1) * d if timed else None,
+                             "logp": tlp[b][i] if timed else None})
+            out.append({"score": score[b] if ok[b] else None, "tokens": toks})
+        return out
+
+    def transcribe(self, input, beam_size=5, ctc_weight=None, timestamps=True):
+        """Audio in, text out, for a batch that needs only wave / wave_len.  The search follows the model's heads: joint model =
+        beam_search(ctc_weight = config.ctc_weight unless given), CTC-only model = ctc_prefix_beam_search, attention-only model =
+        beam_search (no timestamps: they come from the CTC head).  Returns per utterance {"text", "ids", "score", "tokens"}: ids of
+        the best hypothesis without sos / eos, text = their vocabulary tokens joined (pad / sos / eos dropped), score = the search's
+        score, tokens = ctc_align's token list of the hypothesis (one launch for the batch; None when timestamps=False).  A hypothesis
+        the CTC head cannot spell (infeasible for the frames, containing the blank id, longer than 255) keeps its text with None times."""
+        if timestamps and not self.use_ctc:
+            raise ValueError("timestamps come from the CTC head, and this model has none (config.ctc_weight = 0)")
+        if self.use_decoder:
+            w = float(getattr(self.config, "ctc_weight", 0.0)) if ctc_weight is None else float(ctc_weight)
+            hyps = self.beam_search(input, beam_size, 1, ctc_weight=w if self.use_ctc else 0.0)
+        else:
+            hyps = self.ctc_prefix_beam_search(input, beam_size, 1)
+        ids, scores = [], []
+        for h in hyps:
+            if not h:
+                ids.append([])
+                scores.append(float("-inf"))
+                continue
+            seq = list(h[0]["yseq"])
+            if self.use_decoder:
+                seq = seq[1:] if seq and seq[0] == SOS_ID else seq
+                seq = seq[:-1] if seq and seq[-1] == EOS_ID else seq
+            ids.append(seq)
+            scores.append(float(h[0]["score"]))
+        id2tok = self.vocab._id2token
+        out = [{"text": "".join(id2tok[x] for x in seq if x not in (PAD_ID, SOS_ID, EOS_ID)), "ids": seq, "score": sc, "tokens": None}
+               for seq, sc in zip(ids, scores)]
+        if timestamps:
+            V = self.V
+            ok = [len(seq) <= 255 and all(0 <= x < V and x != PAD_ID for x in seq) for seq in ids]
+            al = self._align_lists(self._ctc_logits(input), input.wave_len, ids, alignable=ok)
+            for o, a in zip(out, al):
+                o["tokens"] = a["tokens"]
+        return out
 
     def _ctc_cer(self, logits, wave_len, labels32, lab_len):
         ids, lens = K.ctc_greedy_decode(logits, wave_len, PAD_ID)

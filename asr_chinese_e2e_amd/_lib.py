@@ -82,6 +82,8 @@ SIGNATURES = {
     "asr_sdpa_dropout_mask": (I, [P, I, I, I, I, F, U, P]),
     "asr_ctc_workspace_bytes": (Z, [I, I, I]),
     "asr_ctc_fwd_bwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P, I, P, P, Z, I, P]),
+    "asr_ctc_align_workspace_bytes": (Z, [I, I, I]),
+    "asr_ctc_align": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, Z, I, P]),
     "asr_ctc_greedy_decode": (I, [P, P, P, P, I, I, I, I, I, I, P]),
     "asr_ctc_frame_argmax": (I, [P, P, P, I, I, I, I, I, I, P]),
     "asr_ctc_collapse": (I, [P, P, P, I, I, I, P]),

@@ -647,6 +647,231 @@ __global__ __launch_bounds__(256) void ctc_label_fix_kernel(bf16_t* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------- forced alignment (Viterbi)
+// The best single path through the lattice of kernel 1 (asr_ctc_align): the alpha recursion with max in place of +, one wave per
+// utterance, same layout (entry i = lane + 64 j, interleaved (blank, label) rows), same prefetch and the same power-of-two rescaling by the
+// column maximum (a per-frame factor does not change which predecessor wins).  Every step also writes one back-pointer byte per entry:
+//   bit 0      blank state 2i:   0 = stay, 1 = from Lb[i-1]
+//   bits 1..2  label state 2i+1: 0 = stay, 1 = from Bk[i], 2 = from Lb[i-1] (skip)
+// Ties prefer the state itself, then s-1, then s-2 (strict > below).  The rows (T x W bytes) live in LDS when they fit VIT_LDS_BP,
+// else in the workspace, and the backtrace stages them into LDS VIT_LDS_BP bytes at a time: it is a chain of dependent reads, one per frame,
+// and pays LDS latency per step instead of a global round trip.
+constexpr int VIT_LDS_BP = 64 * 1024;
+
+// Returns ln of the scale taken out (or -inf once every state reached 0); fin_b / fin_l = the final column's Bk[L] and Lb[L-1] (scaled).
+template <int W>
+__device__ __forceinline__ double ctc_viterbi_recursion(const double* __restrict__ y, uint8_t* bp, const int32_t* __restrict__ lab,
+                                                        int Tb, int L, int lane, double& fin_b, double& fin_l) {
+    constexpr int NS = W <= 64 ? 1 : W / 64;
+    constexpr ptrdiff_t RW = 2 * W;
+    int esum = 0;
+    bool dead = false;
+    bool skip[NS];         // the label-to-label transition into Lb[i] exists
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int i = lane + 64 * j;
+        skip[j] = i >= 1 && i < L && lab[i] != lab[i - 1];
+    }
+    const double* yp = y + 2 * lane;
+    uint8_t* op = bp + lane;            // back-pointer row t at op + t * W (row 0 is never written nor read)
+    double bk[NS], lb[NS];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int i = lane + 64 * j;
+        const f64x2 y0 = *(const f64x2*)(yp + 128 * j);
+        bk[j] = i == 0 ? y0[0] : 0.0;
+        lb[j] = i == 0 ? y0[1] : 0.0;
+    }
+    constexpr int CH = 8;
+    constexpr int NB = NS == 1 ? 4 : 2;   // chunk buffers, as ctc_recursion (CH loads + CH byte stores per chunk)
+    const int nsteps = Tb - 1;
+    struct Chunk { f64x2 v[CH][NS]; };
+    Chunk q[NB];
+    auto fetch = [&](Chunk& d, const double* p) {
+#pragma unroll
+        for (int k = 0; k < CH; ++k)
+#pragma unroll
+            for (int j = 0; j < NS; ++j) d.v[k][j] = *(const f64x2*)(p + k * RW + 128 * j);
+    };
+    auto fetch_clamped = [&](Chunk& d, int chunk) {
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            const int step = min(1 + chunk * CH + k, nsteps);
+#pragma unroll
+            for (int j = 0; j < NS; ++j) d.v[k][j] = *(const f64x2*)(yp + (ptrdiff_t)step * RW + 128 * j);
+        }
+    };
+    double sc = 1.0;
+    int e_pending = 0;
+    auto one_step = [&](const f64x2 (&yv)[NS], uint8_t* o, int k) {
+        double yb[NS], yl[NS];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) { yb[j] = yv[j][0]; yl[j] = yv[j][1]; }
+        if ((k & 3) == 1) {
+#pragma unroll
+            for (int j = 0; j < NS; ++j) { yb[j] *= sc; yl[j] *= sc; }
+            esum += e_pending;
+        }
+        double nb[NS], nl[NS];
+        unsigned code[NS];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            double sh = wave_shr1(lb[j]);          // Lb[i-1]
+            if (j > 0) sh = lane == 0 ? lane_bcast(lb[j > 0 ? j - 1 : 0], 63) : sh;
+            const bool fb = sh > bk[j];
+            double ml = lb[j];
+            unsigned cl = 0u;
+            if (bk[j] > ml) { ml = bk[j]; cl = 1u; }
+            if (skip[j] && sh > ml) { ml = sh; cl = 2u; }
+            nb[j] = yb[j] * (fb ? sh : bk[j]);
+            nl[j] = yl[j] * ml;
+            code[j] = (fb ? 1u : 0u) | (cl << 1);
+        }
+#pragma unroll
+        for (int j = 0; j < NS; ++j) { bk[j] = nb[j]; lb[j] = nl[j]; }
+        if ((k & 3) == 3) {      // rescaling: see ctc_recursion
+            unsigned hi = 0u;
+#pragma unroll
+            for (int j = 0; j < NS; ++j) hi = max(hi, max((unsigned)__double2hiint(bk[j]), (unsigned)__double2hiint(lb[j])));
+            hi = wave_max_u32<(W < 64 ? W : 64) - 1>(hi);
+            const bool zero = (hi >> 20) == 0u;
+            e_pending = zero ? 0 : (int)(hi >> 20) - 1023;
+            sc = __hiloint2double((1023 - e_pending) << 20, 0);
+            dead |= zero;
+        }
+#pragma unroll
+        for (int j = 0; j < NS; ++j) o[64 * j] = (uint8_t)code[j];
+    };
+    const int nfull = nsteps / CH;
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < NB - 1; ++i) fetch_clamped(q[i], i);
+    const double* yq = yp + RW;
+    uint8_t* oq = op + W;
+    for (; c + 2 * NB - 1 <= nfull; c += NB) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            fetch(q[(i + NB - 1) % NB], yq + (i + NB - 1) * CH * RW);
+#pragma unroll
+            for (int k = 0; k < CH; ++k) one_step(q[i].v[k], oq + (i * CH + k) * W, k);
+        }
+        yq += NB * CH * RW;
+        oq += NB * CH * W;
+    }
+    for (; c * CH < nsteps; ++c) {
+        fetch_clamped(q[NB - 1], c + NB - 1);
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            if (1 + c * CH + k > nsteps) break;
+            one_step(q[0].v[k], oq + k * W, k);
+        }
+        oq += CH * W;
+#pragma unroll
+        for (int i = 0; i + 1 < NB; ++i) q[i] = q[i + 1];
+    }
+    fin_b = 0.0;
+    fin_l = 0.0;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {      // L is uniform: readlane of the one register that holds each end state
+        if ((L >> 6) == j) fin_b = lane_bcast(bk[j], L & 63);
+        if (L > 0 && ((L - 1) >> 6) == j) fin_l = lane_bcast(lb[j], (L - 1) & 63);
+    }
+    return dead ? -INFINITY : (double)esum * 0.6931471805599453;
+}
+
+// One wave per utterance: recursion, backtrace (state indices into path[]), then one pass over the frames, 64 at a time, that turns
+// states into token ids and fills spans / token_logp (sums of log y over a token's frames by a segmented scan: fixed order).
+template <int W, bool LDS_BP>
+__global__ __launch_bounds__(64) void ctc_viterbi_kernel(const double* __restrict__ lp, uint8_t* __restrict__ bp_ws, const int32_t* __restrict__ in_len,
+                                                         const int32_t* __restrict__ labels, const int32_t* __restrict__ lab_len, int32_t* __restrict__ path,
+                                                         int32_t* __restrict__ spans, float* __restrict__ token_logp, float* __restrict__ score,
+                                                         int T_, int Lmax, int blank) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_bp[];
+    __shared__ double s_fin[3];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int Tb = min(max(in_len[b], 0), T_);
+    const int L = min(max(lab_len[b], 0), Lmax);
+    constexpr size_t RW = 2 * (size_t)W;
+    const double* lpb = lp + (size_t)b * T_ * RW;
+    const int32_t* lab = labels + (size_t)b * Lmax;
+    int32_t* pb = path + (size_t)b * T_;
+    int32_t* spb = spans + (size_t)b * Lmax * 2;
+    float* tlb = token_logp + (size_t)b * Lmax;
+    uint8_t* bpg = bp_ws + (size_t)b * T_ * W;
+    for (int i = lane; i < Lmax; i += 64) {     // overwritten below for the tokens of a feasible alignment
+        spb[2 * i] = -1;
+        spb[2 * i + 1] = -1;
+        tlb[i] = i < L ? -INFINITY : 0.f;
+    }
+    if (Tb > 0 && (W >= 64 || lane < W)) {      // W = 32: half a wave
+        double fb, fl;
+        const double logc = ctc_viterbi_recursion<W>(lpb, LDS_BP ? s_bp : bpg, lab, Tb, L, lane, fb, fl);
+        if (lane == 0) { s_fin[0] = fb; s_fin[1] = fl; s_fin[2] = logc; }
+    }
+    __syncthreads();
+    bool feasible = L == 0;      // Tb = 0
+    int s = 2 * L;
+    if (Tb > 0) {
+        const double fb = s_fin[0], fl = s_fin[1], logc = s_fin[2];
+        s = fb >= fl ? 2 * L : 2 * L - 1;       // ties: end in the blank
+        const double best = fb >= fl ? fb : fl;
+        feasible = best > 0.0 && logc != -INFINITY;
+        if (lane == 0) score[b] = feasible ? (float)(logc + log(best)) : -INFINITY;
+    } else if (lane == 0) {
+        score[b] = feasible ? 0.f : -INFINITY;
+    }
+    if (feasible && Tb > 0) {
+        constexpr int F = VIT_LDS_BP / W;       // frames per staged block of back-pointer rows
+        int t = Tb - 1;
+        for (;;) {
+            const int t0 = LDS_BP ? 0 : max(t - F + 1, 0);
+            if (!LDS_BP) {      // rows t0 .. t of the workspace -> LDS (16-byte pieces; W is a multiple of 16)
+                const int n16 = (t - t0 + 1) * (W / 16);
+                const u32x4* src = (const u32x4*)(bpg + (size_t)t0 * W);
+                for (int k = lane; k < n16; k += 64) ((u32x4*)s_bp)[k] = src[k];
+                __syncthreads();
+            }
+            for (; t >= t0; --t) {
+                if (lane == 0) pb[t] = s;
+                if (t > 0) {
+                    const unsigned cb = s_bp[(size_t)(t - t0) * W + (s >> 1)];
+                    s = max((s & 1) ? s - (int)((cb >> 1) & 3u) : s - (int)(cb & 1u), 0);
+                }
+            }
+            if (t < 0) break;
+            __syncthreads();        // every lane is done with this block before the next one overwrites it
+        }
+    }
+    __syncthreads();
+    double carry = 0.0;     // running log y sum of the token that ends the previous block of frames
+    int s_last = -1;        // state of the last frame of the previous block
+    for (int t0 = 0; t0 < T_; t0 += 64) {
+        const int t = t0 + lane;
+        const int st = t < Tb ? (feasible ? pb[t] : 0) : -1;
+        int nx = __shfl_down(st, 1, 64);
+        if (lane == 63) nx = (feasible && t + 1 < Tb) ? pb[t + 1] : -1;
+        int pv = __shfl_up(st, 1, 64);
+        if (lane == 0) pv = s_last;
+        const bool tok = st > 0 && (st & 1);
+        double v = tok ? log(lpb[(size_t)t * RW + st]) : 0.0;     // the state index is the double's index in the interleaved row
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {      // inclusive scan over runs of one state (a token's frames are contiguous)
+            const double u = __shfl_up(v, o, 64);
+            const int su = __shfl_up(st, o, 64);
+            if (lane >= o && su == st) v += u;
+        }
+        if (tok && st == s_last) v += carry;
+        carry = __shfl(v, 63, 64);
+        s_last = __shfl(st, 63, 64);
+        if (tok) {
+            const int i = st >> 1;
+            if (pv != st) spb[2 * i] = t;
+            if (nx != st) { spb[2 * i + 1] = t; tlb[i] = (float)v; }
+        }
+        if (t < T_) pb[t] = t < Tb ? (tok ? lab[st >> 1] : blank) : -1;
+    }
+}
+
 // ---------------------------------------------------------------------------------- xent
 // (value, index) of the row maximum over the workgroup, first index on ties (torch.argmax): every thread brings the first maximum of its own
 // elements (ascending indices, strict >); `redi` = 8 ints of LDS
@@ -870,5 +1095,62 @@ extern "C" int asr_xent_fwd_bwd(const void* logits, const int32_t* gold, const f
     else { if (argmax_out) XENT(bf16_t, true); else XENT(bf16_t, false); }
 #undef XENT
     ASR_CHECK_LAUNCH("asr_xent_fwd_bwd");
+    return ASR_OK;
+}
+
+// ---------------------------------------------------------------------------------- forced alignment
+// workspace: the lattice of kernel 1 (B T 2W doubles), back-pointer rows (B T W bytes; used when T W > VIT_LDS_BP), lse (B T floats)
+extern "C" size_t asr_ctc_align_workspace_bytes(int B, int T, int Lmax) {
+    if (B <= 0 || T <= 0) return 0;
+    const size_t n = (size_t)B * T, W = (size_t)width_of(Lmax);
+    return n * 2 * W * sizeof(double) + n * W + n * sizeof(float);
+}
+
+extern "C" int asr_ctc_align(const void* logits, const int32_t* in_len, const int32_t* labels, const int32_t* lab_len, int32_t* path,
+                             int32_t* spans, float* token_logp, float* score, int B, int T, int V, int ld, int Lmax, int blank, void* ws,
+                             size_t ws_bytes, int dtype, void* stream) {
+    if (!logits || !in_len || !labels || !lab_len || !path || !spans || !token_logp || !score || !ws) ASR_FAIL(ASR_EINVAL, "asr_ctc_align: null pointer");
+    if (B <= 0 || T <= 0 || V <= 1 || Lmax <= 0 || blank < 0 || blank >= V) ASR_FAIL(ASR_EINVAL, "asr_ctc_align: bad shape B=%d T=%d V=%d Lmax=%d blank=%d", B, T, V, Lmax, blank);
+    if (ld < V || (ld != V && ld % 8)) ASR_FAIL(ASR_EINVAL, "asr_ctc_align: row stride ld=%d (V=%d): V, or a multiple of 8 above it", ld, V);
+    if (Lmax > 255) ASR_FAIL(ASR_EINVAL, "asr_ctc_align: Lmax = %d: label sequences longer than 255 are not supported", Lmax);
+    const size_t need = asr_ctc_align_workspace_bytes(B, T, Lmax);
+    if (ws_bytes < need) ASR_FAIL(ASR_EINVAL, "asr_ctc_align: workspace %zu < %zu", ws_bytes, need);
+    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "asr_ctc_align: dtype %d", dtype);
+    hipStream_t st = (hipStream_t)stream;
+    const int W = width_of(Lmax);
+    double* lp = (double*)ws;
+    uint8_t* bp = (uint8_t*)(lp + (size_t)B * T * 2 * W);
+    float* lse = (float*)(bp + (size_t)B * T * W);
+    const int rows = B * T;
+    int g1 = ceil_div(rows, 4);
+    if (g1 > 4096) g1 = 4096;
+    const int cu_lim = asr_option(ASR_OPT_CU_LIMIT);
+    if (cu_lim > 0 && g1 > 8 * cu_lim) g1 = 8 * cu_lim;
+    // kernel 1 of asr_ctc_fwd_bwd without gradient or path: the logits are read once into the linear-domain lattice
+    const int need_v = ceil_div(V / 8, 64);
+    const bool rows_path = dtype == ASR_BF16 && V % 8 == 0 && ld % 8 == 0 && need_v <= 16 && ((uintptr_t)logits % 16) == 0;
+    if (rows_path) {
+        const int need = need_v;
+#define K1(NV) ctc_lse_gather_rows_kernel<NV, false, false><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank, nullptr, 0.f, nullptr, nullptr)
+        ROWS_DISPATCH(K1);
+#undef K1
+    } else if (dtype == ASR_F32) ctc_lse_gather_kernel<float><<<g1, 256, 0, st>>>((const float*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
+    else ctc_lse_gather_kernel<bf16_t><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
+    const bool lds_bp = (size_t)T * W <= (size_t)VIT_LDS_BP;
+    const size_t lds = lds_bp ? (size_t)T * W : (size_t)VIT_LDS_BP;
+#define VIT(N, M)                                                                                                                        \
+    do {                                                                                                                                 \
+        static bool attr = false;                                                                                                        \
+        if (!attr) { (void)hipFuncSetAttribute((const void*)ctc_viterbi_kernel<N, M>, hipFuncAttributeMaxDynamicSharedMemorySize, VIT_LDS_BP); attr = true; } \
+        ctc_viterbi_kernel<N, M><<<B, 64, lds, st>>>(lp, bp, in_len, labels, lab_len, path, spans, token_logp, score, T, Lmax, blank);  \
+    } while (0)
+#define VIT_W(N) do { if (lds_bp) VIT(N, true); else VIT(N, false); } while (0)
+    if (W == 32) VIT_W(32);
+    else if (W == 64) VIT_W(64);
+    else if (W == 128) VIT_W(128);
+    else VIT_W(256);
+#undef VIT_W
+#undef VIT
+    ASR_CHECK_LAUNCH("asr_ctc_align");
     return ASR_OK;
 }

@@ -310,6 +310,34 @@ def ctc_fwd_bwd(logits, in_len, labels, lab_len, ws, blank=0, grad_scale=1.0, ze
     return nll, dlogits
 
 
+def ctc_align(logits, in_len, labels, lab_len, blank=0, ws=None):
+    """CTC forced alignment (Viterbi, asr_ctc_align): the best single path of each utterance's labels through its frames.
+    logits (B, T, V) f32 / bf16, dense or rows padded as the engine lays them out; in_len (B,), labels (B, Lmax) with every entry
+    (padding included) a class id in [0, V), lab_len (B,): int32 on the device.  Lmax <= 255; Lmax = 0 is allowed.
+    Returns (path (B, T) int32: token id per frame, `blank` on blank frames, -1 past in_len; spans (B, Lmax, 2) int32: first and last
+    frame of each token, -1 past lab_len; token_logp (B, Lmax) f32: sum of log softmax over a token's frames; score (B,) f32:
+    log-probability of the best path, -inf when the labels cannot be aligned in the frames).  Semantics: include/asr_hip.h."""
+    B, T, V = logits.shape
+    ld = _frame_rows(logits)
+    _chk_i32(in_len, labels, lab_len)
+    assert labels.dim() == 2 and labels.shape[0] == B and in_len.numel() == B and lab_len.numel() == B
+    Lmax = labels.shape[1]
+    dev = logits.device
+    lab = labels if Lmax > 0 else torch.zeros(B, 1, dtype=torch.int32, device=dev)     # the entry point takes Lmax >= 1
+    La = lab.shape[1]
+    path = torch.empty(B, T, dtype=torch.int32, device=dev)
+    spans = torch.empty(B, La, 2, dtype=torch.int32, device=dev)
+    token_logp = torch.empty(B, La, dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    nbytes = lib.asr_ctc_align_workspace_bytes(B, T, La)
+    w = ws.get(nbytes) if ws is not None else torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    timed("ctc_align", 0.0, lambda: check(
+        lib.asr_ctc_align(_p(logits), _p(in_len), _p(lab), _p(lab_len), _p(path), _p(spans), _p(token_logp), _p(score), B, T, V, ld, La,
+                          int(blank), _p(w), w.numel(), _dt(logits), _stream()),
+        "asr_ctc_align"), logits.numel() * logits.element_size())
+    return path, spans[:, :Lmax], token_logp[:, :Lmax], score
+
+
 def ctc_greedy_decode(logits, in_len, blank=0):
     """logits (B,T,V) -> (ids (B,T) int32, collapsed and 0-padded; lens (B,) int32)."""
     B, T, V = logits.shape

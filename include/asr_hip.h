@@ -216,6 +216,27 @@ int asr_ctc_fwd_bwd(const void* logits, void* dlogits, const int32_t* in_len,
                     int32_t* best_path, void* ws, size_t ws_bytes, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * CTC forced alignment (Viterbi): the single best path through the same lattice, i.e. the max-product form of
+ * torch.nn.functional.ctc_loss.  Additive to ABI 10 (no version change).  Inputs as asr_ctc_fwd_bwd.
+ * States: the blank-augmented sequence l' (blanks at even s, labels at odd s, S = 2L + 1);
+ *   delta_0(0) = log y_0(blank), delta_0(1) = log y_0(l_1),
+ *   delta_t(s) = log y_t(l'_s) + max(delta_{t-1}(s), delta_{t-1}(s-1), delta_{t-1}(s-2)), the s-2 term only where l'_s is a label
+ *   different from l'_{s-2}; y = softmax of the logits row.  The path ends in 2L or 2L-1 at t = in_len[b] - 1.
+ *   Ties: the predecessor s before s-1 before s-2; at the end 2L before 2L-1.
+ * path: (B, T) int32 token id of the aligned state per frame (`blank` on blank frames, -1 for t >= in_len[b]).
+ * spans: (B, Lmax, 2) int32 first and last frame (inclusive) of each label token, -1 for i >= lab_len[b].
+ * token_logp: (B, Lmax) f32 sum of log y_t(l_i) over the frames of token i (0 for i >= lab_len[b]).
+ * score: (B) f32 log-probability of the best path.
+ * Infeasible utterances (in_len < L + number of adjacent repeats): score = -inf, spans -1, token_logp -inf, path `blank` on the
+ * utterance's frames.  L = 0 aligns every frame to the blank; in_len = 0 gives score 0 when L = 0 (else -inf) and a path of -1.
+ * ws: asr_ctc_align_workspace_bytes(B, T, Lmax) bytes.  Lmax <= 255.
+ */
+size_t asr_ctc_align_workspace_bytes(int B, int T, int Lmax);
+int asr_ctc_align(const void* logits, const int32_t* in_len, const int32_t* labels, const int32_t* lab_len, int32_t* path,
+                  int32_t* spans, float* token_logp, float* score, int B, int T, int V, int ld, int Lmax, int blank, void* ws,
+                  size_t ws_bytes, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Greedy CTC decoding: per-frame argmax over the vocabulary (first index wins ties, as
  * torch.argmax), frames t >= in_len[b] count as blank, then the CTC collapse (merge repeats, drop
  * blanks).  NOT in the reference (no CTC there; its decoder-side search is the Python beam loop

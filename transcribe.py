@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""transcribe.py - audio in, text out: the inference entry point the reference's Predictor/predictor.py was meant to be.
+
+    python transcribe.py --model_name=TransformerOffical --ctc_weight=0.3 --ckpt=ckpt/exp/model.model \
+        --vocab_path=Predictor/vocab.t --wavs=a.wav,b.wav
+
+Model flags are train.py's (same parser, same TrainConfig / ModelConfig merge, same get_model_class), so the flags a model was
+trained with rebuild it.  Inference flags:
+  --ckpt         state dict as BaseModel.save writes it (required; a missing file or missing keys are errors)
+  --vocab_path   the vocabulary the model was trained with (Vocab.save)
+  --wavs         comma-separated 16-bit PCM WAV files, or
+  --manifest     a collector manifest (one JSON object {"wave": path, ...} per line)
+  --beam_size    beam of the search (default 5)
+  --ctc_weight   joint models: weight of the CTC score in the rescoring (default: the model's ctc_weight)
+  --batch_size   utterances per batch (default 16)
+  --timestamps   per-character times from the CTC head (default: on when the model has one)
+Audio goes through load_wav -> AudioParser.parse_batch on the device -> model.transcribe; one JSON line per file is printed:
+{"file", "duration_s", "text", "ids", "score", "tokens": [{"id", "token", "start_frame", "end_frame", "start_s", "end_s", "logp"}]}.
+"""
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from asr_chinese_e2e_amd.data_handler import AudioParser, Vocab, load_wav  # noqa: E402
+from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
+from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
+
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps")
+
+
+def _finite(x):
+    return None if isinstance(x, float) and not math.isfinite(x) else x
+
+
+def load_model(config, vocab, ckpt, device="cuda"):
+    """Model of config.model_name with the checkpoint's weights; a missing file or missing keys raise."""
+    Model, _ = get_model_class(config.model_name)
+    if not ckpt or not os.path.isfile(ckpt):
+        raise SystemExit(f"transcribe.py: checkpoint not found: {ckpt!r}")
+    state = torch.load(ckpt, map_location="cpu", weights_only=True)
+    model = Model(config, vocab)
+    missing, unexpected = model.load_state_dict(state, strict=False)
+    if missing:
+        raise SystemExit(f"transcribe.py: {ckpt} lacks {len(missing)} parameters of {config.model_name} "
+                         f"(model flags differ from the training run?): {missing[:5]}")
+    if unexpected:
+        print(f"transcribe.py: ignoring {len(unexpected)} unexpected keys of {ckpt}: {unexpected[:5]}", file=sys.stderr)
+    return model.to(device).eval()
+
+
+def audio_files(flags):
+    if flags.get("wavs"):
+        w = flags["wavs"]
+        return [p for p in (w if isinstance(w, (list, tuple)) else str(w).split(",")) if p]
+    if flags.get("manifest"):
+        with open(flags["manifest"], encoding="utf-8") as f:
+            return [json.loads(line)["wave"] for line in f if line.strip()]
+    raise SystemExit("transcribe.py: give --wavs=a.wav,b.wav or --manifest=<collector json>")
+
+
+def transcribe(**flags):
+    cli = {k: flags.pop(k) for k in CLI_KEYS if k in flags}
+    ctc_weight = flags.get("ctc_weight")          # model flag and decoding weight: the search uses the model's unless given
+    config = TrainConfig()
+    config.fn_build(flags)
+    Model, ModelConfig = get_model_class(config.model_name)
+    config.fn_combine(ModelConfig())
+    config.fn_build(flags)
+    if not torch.cuda.is_available():
+        raise SystemExit("transcribe.py needs an MI355X: the inference path has no CPU fallback")
+    vocab = Vocab.load(config.vocab_path)
+    model = load_model(config, vocab, cli.get("ckpt"))
+    files = audio_files(cli)
+    parser = AudioParser(sample_rate=config.sample_rate, n_mels=config.n_mels, window_size=config.window_size,
+                         lfr_m=config.lfr_m, lfr_n=config.lfr_n)
+    beam = int(cli.get("beam_size", 5))
+    bs = max(1, int(cli.get("batch_size", 16)))
+    timestamps = bool(cli.get("timestamps", model.use_ctc))
+    for i in range(0, len(files), bs):
+        chunk = files[i:i + bs]
+        waves = []
+        for path in chunk:
+            pcm, sr = load_wav(path)
+            if sr != config.sample_rate:
+                raise SystemExit(f"transcribe.py: {path}: sample rate {sr}, the model expects {config.sample_rate}")
+            waves.append(pcm)
+        S = max(1, max(len(w) for w in waves))
+        wav = np.zeros((len(waves), S), dtype=np.float32)
+        for b, w in enumerate(waves):
+            wav[b, : len(w)] = w
+        wav_len = torch.tensor([len(w) for w in waves], dtype=torch.int32)
+        feats, flen = parser.parse_batch(torch.from_numpy(wav).cuda(), wav_len.cuda())
+        out = model.transcribe(Pack(wave=feats, wave_len=flen), beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps)
+        for path, w, r in zip(chunk, waves, out):
+            dur = len(w) / float(config.sample_rate)
+            for t in r["tokens"] or ():          # the last encoder frame may reach past the end of the audio
+                for k in ("start_s", "end_s"):
+                    if t[k] is not None:
+                        t[k] = min(t[k], dur)
+            line = {"file": path, "duration_s": dur, "text": r["text"], "ids": r["ids"],
+                    "score": _finite(r["score"]), "tokens": r["tokens"]}
+            print(json.dumps(line, ensure_ascii=False), flush=True)
+
+
+if __name__ == "__main__":
+    transcribe(**parse_flags(sys.argv[1:]))
