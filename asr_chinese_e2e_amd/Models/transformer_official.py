@@ -361,13 +361,22 @@ class _SpeechTransformer(BaseModel):
             pack.add(**({"ctc_cer": cer} if self.use_decoder else {"cer": cer}))
         return pack
 
-    def beam_search(self, input, beam_size=5, nbest=1, decode_max_len=0, ctc_weight=0.0):
+    def beam_search(self, input, beam_size=5, nbest=1, decode_max_len=0, ctc_weight=0.0, joint="rescore", ctc_pre_beam=None):
         """Attention-decoder beam search for a batch (Decoder.recognize_beam, transformer_official.py:
         331-434, batched on the GPU with key/value caches): per utterance a list of at most `nbest`
         {'yseq': [sos, ..., eos], 'score': float}.
         ctc_weight > 0 (joint models): the beam's hypotheses are re-ranked by ctc_weight * log p_ctc + (1 - ctc_weight) *
-        log p_att (decode.joint_beam_search; entries then also carry 'att_score' and 'ctc_score')."""
+        log p_att (decode.joint_beam_search; entries then also carry 'att_score' and 'ctc_score').
+        joint="one_pass": CTC prefix scores take part in every step of the search instead (decode.one_pass_beam_search, same result
+        format; needs both heads and 0 < ctc_weight <= 1); ctc_pre_beam = attention candidates per hypothesis (default
+        min(16, int(1.5 * beam_size)), at least beam_size)."""
         from .. import decode
+        if joint not in ("rescore", "one_pass"):
+            raise ValueError(f"joint must be 'rescore' or 'one_pass' (got {joint!r})")
+        if joint == "one_pass":
+            return decode.one_pass_beam_search(self, input, beam_size, nbest, decode_max_len, ctc_weight, ctc_pre_beam)
+        if ctc_pre_beam is not None:
+            raise ValueError("ctc_pre_beam applies to joint='one_pass' only")
         if ctc_weight > 0.0:
             return decode.joint_beam_search(self, input, beam_size, nbest, decode_max_len, ctc_weight)
         return decode.beam_search(self, input, beam_size, nbest, decode_max_len)
@@ -453,18 +462,23 @@ class _SpeechTransformer(BaseModel):
             out.append({"score": score[b] if ok[b] else None, "tokens": toks})
         return out
 
-    def transcribe(self, input, beam_size=5, ctc_weight=None, timestamps=True):
+    def transcribe(self, input, beam_size=5, ctc_weight=None, timestamps=True, joint="rescore"):
         """Audio in, text out, for a batch that needs only wave / wave_len.  The search follows the model's heads: joint model =
         beam_search(ctc_weight = config.ctc_weight unless given), CTC-only model = ctc_prefix_beam_search, attention-only model =
         beam_search (no timestamps: they come from the CTC head).  Returns per utterance {"text", "ids", "score", "tokens"}: ids of
         the best hypothesis without sos / eos, text = their vocabulary tokens joined (pad / sos / eos dropped), score = the search's
         score, tokens = ctc_align's token list of the hypothesis (one launch for the batch; None when timestamps=False).  A hypothesis
-        the CTC head cannot spell (infeasible for the frames, containing the blank id, longer than 255) keeps its text with None times."""
+        the CTC head cannot spell (infeasible for the frames, containing the blank id, longer than 255) keeps its text with None times.
+        joint: the joint model's search, "rescore" (two-pass) or "one_pass" (beam_search(joint=...)); "one_pass" needs both heads."""
+        if joint not in ("rescore", "one_pass"):
+            raise ValueError(f"joint must be 'rescore' or 'one_pass' (got {joint!r})")
+        if joint == "one_pass" and not (self.use_decoder and self.use_ctc):
+            raise RuntimeError("joint='one_pass' needs a model with both the attention decoder and the CTC head")
         if timestamps and not self.use_ctc:
             raise ValueError("timestamps come from the CTC head, and this model has none (config.ctc_weight = 0)")
         if self.use_decoder:
             w = float(getattr(self.config, "ctc_weight", 0.0)) if ctc_weight is None else float(ctc_weight)
-            hyps = self.beam_search(input, beam_size, 1, ctc_weight=w if self.use_ctc else 0.0)
+            hyps = self.beam_search(input, beam_size, 1, ctc_weight=w if self.use_ctc else 0.0, joint=joint)
         else:
             hyps = self.ctc_prefix_beam_search(input, beam_size, 1)
         ids, scores = [], []

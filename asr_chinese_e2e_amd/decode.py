@@ -43,22 +43,67 @@ def beam_search(model, input, beam_size=5, nbest=1, decode_max_len=0, check_ever
         eng.training = was_training
 
 
+class _DecoderSteps:
+    """The batched key/value-cache decoder of the searches: the encoder, the encoder-side K|V of every layer, the two cache copies;
+    logits(i, last_tok) runs decoder step i for all R = B * beam hypotheses, gather(parent, i) reorders the caches by parent."""
+
+    def __init__(self, model, eng, input, beam, decode_max_len):
+        x = input.wave.to(eng.dtype).contiguous()
+        self.wave_len = input.wave_len.to(torch.int32).contiguous()
+        self.B, self.T, _ = x.shape
+        self.dev = x.device
+        self.eng, self.beam = eng, beam
+        hd = eng.H * eng.dk
+        self.enc, _ = eng.encoder_fwd(x, self.wave_len, model.attn_window)            # (B*T, d)
+        self.maxlen = self.wave_len.clone() if decode_max_len == 0 else torch.full_like(self.wave_len, decode_max_len)
+        self.Lcap = int(self.maxlen.max())
+        if self.Lcap > eng.pe.shape[0]:
+            raise ValueError(f"decode length {self.Lcap} exceeds the positional-encoding table ({eng.pe.shape[0]})")
+        self.R = R = self.B * beam
+        # encoder-side keys / values of every layer, once
+        self.cross_kv = [cross.kv.fwd(self.enc) for _, cross, _ in eng.dec]            # (B*T, 2hd)
+        self.caches = [torch.zeros(eng.L, R, self.Lcap, 2 * hd, dtype=eng.dtype, device=self.dev) for _ in range(2)]
+        self.row_bytes = 2 * hd * self.caches[0].element_size()
+        self.cur = 0
+        self.use_sdpa = eng.dk == 64 and eng.dtype == torch.bfloat16 and USE_SDPA
+        self.o_buf = torch.empty(R, hd, dtype=eng.dtype, device=self.dev) if self.use_sdpa else None
+        self.lse_buf = None
+
+    def logits(self, i, last_tok):
+        eng, R, B, T, beam = self.eng, self.R, self.B, self.T, self.beam
+        d, H, dk, Lcap = eng.d, eng.H, eng.dk, self.Lcap
+        hd = H * dk
+        cache = self.caches[self.cur]
+        y = K.embed_pe_fwd(last_tok.reshape(-1), eng.emb32, eng.pe[i:i + 1], d ** -0.5, R, 1, eng.dtype)   # :369-371
+        for l, (slf, cross, ffn) in enumerate(eng.dec):
+            q = slf.q.fwd(y)
+            slf.kv.fwd(y, out=cache[l, :, i, :])                          # this step's key | value straight into the cache
+            kv = cache[l].view(R * Lcap, 2 * hd)
+            o = K.decode_attn(q, kv[:, :hd], kv[:, hd:], H, dk, Lcap, kv_div=1, k_len_uniform=i + 1)
+            y, _, _ = K.add_ln_fwd(slf.fc.fwd(o), y, slf.ln.g, slf.ln.b, None, None, R, 1)
+            q = cross.q.fwd(y)
+            ckv = self.cross_kv[l]
+            if self.use_sdpa:
+                # the beams of an utterance are `beam` query rows against the SAME encoder keys / values: that is the training
+                # attention kernel at Tq = beam (one workgroup per (utterance, head), K / V fetched once for all beams, MFMA) -
+                # 11 us against ~220 us for the one-wave-per-(row, head) decode kernel, which was 48 of the 65 ms of a search
+                o, self.lse_buf = K.sdpa_fwd(q, ckv[:, :hd], ckv[:, hd:], self.wave_len, B, H, beam, T, dk, o=self.o_buf, lse=self.lse_buf)
+            else:
+                o = K.decode_attn(q, ckv[:, :hd], ckv[:, hd:], H, dk, T, kv_div=beam, k_len=self.wave_len, len_div=beam)
+            y, _, _ = K.add_ln_fwd(cross.fc.fwd(o), y, cross.ln.g, cross.ln.b, None, None, R, 1)
+            h = ffn.w1.fwd(y, act=1)
+            y, _, _ = K.add_ln_fwd(ffn.w2.fwd(h), y, ffn.ln.g, ffn.ln.b, None, None, R, 1)
+        return eng.prj.fwd(y)                                             # tied projection, no bias (:379)
+
+    def gather(self, parent, i):
+        K.cache_gather(self.caches[self.cur], self.caches[self.cur ^ 1], parent.reshape(-1), self.eng.L, self.R, self.beam, self.Lcap, i + 1,
+                       self.row_bytes)
+        self.cur ^= 1
+
+
 def _search(model, eng, input, beam, nbest, decode_max_len, check_every):
-    x = input.wave.to(eng.dtype).contiguous()
-    wave_len = input.wave_len.to(torch.int32).contiguous()
-    B, T, _ = x.shape
-    dev = x.device
-    d, H, dk, L, V = eng.d, eng.H, eng.dk, eng.L, eng.V
-    hd = H * dk
-    enc, _ = eng.encoder_fwd(x, wave_len, model.attn_window)            # (B*T, d)
-    maxlen = wave_len.clone() if decode_max_len == 0 else torch.full_like(wave_len, decode_max_len)
-    Lcap = int(maxlen.max())
-    if Lcap > eng.pe.shape[0]:
-        raise ValueError(f"decode length {Lcap} exceeds the positional-encoding table ({eng.pe.shape[0]})")
-    R = B * beam
-    # encoder-side keys / values of every layer, once
-    cross_kv = [cross.kv.fwd(enc) for _, cross, _ in eng.dec]            # (B*T, 2hd)
-    caches = [torch.zeros(L, R, Lcap, 2 * hd, dtype=eng.dtype, device=dev) for _ in range(2)]
+    dec = _DecoderSteps(model, eng, input, beam, decode_max_len)
+    B, Lcap, dev = dec.B, dec.Lcap, dec.dev
     score = torch.zeros(B, beam, dtype=torch.float32, device=dev)
     alive = torch.zeros(B, beam, dtype=torch.int32, device=dev)
     alive[:, 0] = 1                                                       # one hypothesis [sos] per utterance
@@ -69,51 +114,27 @@ def _search(model, eng, input, beam, nbest, decode_max_len, check_every):
     rec_end = torch.zeros_like(rec_tok)
     rec_score = torch.full((Lcap, B, beam), float("-inf"), dtype=torch.float32, device=dev)
     alive_total = torch.zeros(Lcap, dtype=torch.int32, device=dev)
-    row_bytes = 2 * hd * caches[0].element_size()
-    cur = 0
     steps_done = 0
-    use_sdpa = dk == 64 and eng.dtype == torch.bfloat16 and USE_SDPA
-    o_buf = torch.empty(R, hd, dtype=eng.dtype, device=dev) if use_sdpa else None
-    lse_buf = None
     for i in range(Lcap):
-        cache = caches[cur]
-        y = K.embed_pe_fwd(last_tok.reshape(-1), eng.emb32, eng.pe[i:i + 1], d ** -0.5, R, 1, eng.dtype)   # :369-371
-        for l, (slf, cross, ffn) in enumerate(eng.dec):
-            q = slf.q.fwd(y)
-            slf.kv.fwd(y, out=cache[l, :, i, :])                          # this step's key | value straight into the cache
-            kv = cache[l].view(R * Lcap, 2 * hd)
-            o = K.decode_attn(q, kv[:, :hd], kv[:, hd:], H, dk, Lcap, kv_div=1, k_len_uniform=i + 1)
-            y, _, _ = K.add_ln_fwd(slf.fc.fwd(o), y, slf.ln.g, slf.ln.b, None, None, R, 1)
-            q = cross.q.fwd(y)
-            ckv = cross_kv[l]
-            if use_sdpa:
-                # the beams of an utterance are `beam` query rows against the SAME encoder keys / values: that is the training
-                # attention kernel at Tq = beam (one workgroup per (utterance, head), K / V fetched once for all beams, MFMA) -
-                # 11 us against ~220 us for the one-wave-per-(row, head) decode kernel, which was 48 of the 65 ms of a search
-                o, lse_buf = K.sdpa_fwd(q, ckv[:, :hd], ckv[:, hd:], wave_len, B, H, beam, T, dk, o=o_buf, lse=lse_buf)
-            else:
-                o = K.decode_attn(q, ckv[:, :hd], ckv[:, hd:], H, dk, T, kv_div=beam, k_len=wave_len, len_div=beam)
-            y, _, _ = K.add_ln_fwd(cross.fc.fwd(o), y, cross.ln.g, cross.ln.b, None, None, R, 1)
-            h = ffn.w1.fwd(y, act=1)
-            y, _, _ = K.add_ln_fwd(ffn.w2.fwd(h), y, ffn.ln.g, ffn.ln.b, None, None, R, 1)
-        logits = eng.prj.fwd(y)                                           # tied projection, no bias (:379)
+        logits = dec.logits(i, last_tok)
         vals, ids = K.logsoftmax_topk(logits, beam)
-        K.beam_step(vals, ids, score, alive, last_tok, parent, rec_tok, rec_par, rec_end, rec_score, maxlen, alive_total[i:i + 1],
+        K.beam_step(vals, ids, score, alive, last_tok, parent, rec_tok, rec_par, rec_end, rec_score, dec.maxlen, alive_total[i:i + 1],
                     B, beam, i, EOS_ID)
         steps_done = i + 1
         if i + 1 < Lcap:
-            K.cache_gather(caches[cur], caches[cur ^ 1], parent.reshape(-1), L, R, beam, Lcap, i + 1, row_bytes)
-            cur ^= 1
+            dec.gather(parent, i)
         if (i % check_every) == check_every - 1 and int(alive_total[i]) == 0:   # the only host sync of the loop
             break
     return _backtrace(rec_tok[:steps_done].cpu(), rec_par[:steps_done].cpu(), rec_end[:steps_done].cpu(), rec_score[:steps_done].cpu(), B, beam, nbest)
 
 
-def _backtrace(rec_tok, rec_par, rec_end, rec_score, B, beam, nbest):
+def _backtrace(rec_tok, rec_par, rec_end, rec_score, B, beam, nbest, extra=None):
+    """extra: optional {name: (steps, B, beam) tensor} of per-record values that each entry carries under `name`."""
     steps = rec_tok.shape[0]
     # plain nested lists: element access on a tensor costs ~1 us each, and this walk touches ~50 k of them per batch
     # (33 of the 97 ms of a B = 32, beam 5 search before)
     rec_tok, rec_par, rec_end, rec_score = rec_tok.tolist(), rec_par.tolist(), rec_end.tolist(), rec_score.tolist()
+    extra = {k: v.tolist() for k, v in (extra or {}).items()}
     out = []
     for b in range(B):
         ended = []                                           # in the order the reference appends to ended_hyps
@@ -128,9 +149,9 @@ def _backtrace(rec_tok, rec_par, rec_end, rec_score, B, beam, nbest):
                     seq.append(rec_tok[s][b][kk])
                     kk = rec_par[s][b][kk]
                 seq = [SOS_ID] + seq[::-1] + ([EOS_ID] if e == 2 else [])
-                ended.append((rec_score[i][b][k], seq))
+                ended.append((rec_score[i][b][k], seq, {n: v[i][b][k] for n, v in extra.items()}))
         ended = sorted(ended, key=lambda h: h[0], reverse=True)[: min(len(ended), nbest)]
-        out.append([{"yseq": seq, "score": sc} for sc, seq in ended])
+        out.append([{"yseq": seq, "score": sc, **ex} for sc, seq, ex in ended])
     return out
 
 
@@ -251,3 +272,79 @@ def joint_beam_search(model, input, beam_size=5, nbest=1, decode_max_len=0, ctc_
             cands.append(dict(yseq=h["yseq"], att_score=h["score"], ctc_score=ctc, score=ctc_weight * ctc + (1.0 - ctc_weight) * h["score"]))
         out.append(sorted(cands, key=lambda c: c["score"], reverse=True)[:nbest])
     return out
+
+
+# --------------------------------------------------------------------------------------------- one-pass joint CTC / attention search
+def default_pre_beam(beam_size):
+    """Attention candidates per hypothesis of the one-pass search: min(16, int(1.5 * beam)), ESPnet's ratio."""
+    return min(16, int(1.5 * beam_size))
+
+
+def one_pass_beam_search(model, input, beam_size=5, nbest=1, decode_max_len=0, ctc_weight=0.3, pre_beam=None, check_every=8):
+    """One-pass joint decoding (Watanabe et al. 2017, section 3.2 and algorithm 2): CTC shapes the beam while it is built.  At every
+    step each live hypothesis g proposes its `pre_beam` best attention tokens c; each extension h = g + c is scored by
+        (1 - ctc_weight) * log p_att(c | g, x) + ctc_weight * (log psi_ctc(h) - log psi_ctc(g)),
+    psi_ctc the CTC prefix probability over all frames (asr_ctc_prefix_score; for c = eos the full-sequence probability of g);
+    the `beam` best per hypothesis, then the `beam` best of the utterance survive (stable order), -inf extensions are dropped, eos
+    ends a hypothesis, at step maxlen - 1 eos is appended to the rest, no length normalisation.
+    Returns per utterance at most `nbest` dicts {'yseq', 'score', 'att_score', 'ctc_score'}, best first: att_score = the sum of the
+    attention log-probabilities (plain beam_search's score of that yseq), ctc_score = log p_ctc(yseq without sos / eos), score =
+    ctc_weight * ctc_score + (1 - ctc_weight) * att_score.  An utterance whose every extension is -inf gets an empty list."""
+    if beam_size < 1 or beam_size > 8:
+        raise ValueError("beam_size must be in 1..8 (asr_joint_beam_step merges beam*beam <= 64 candidates per wave)")
+    eng = model._ensure_engine(input.wave.device)
+    if not (eng.use_ctc and eng.use_decoder):
+        raise RuntimeError("one-pass joint decoding needs a model with both the attention decoder and the CTC head (0 < config.ctc_weight < 1)")
+    lam = float(ctc_weight)
+    if not 0.0 < lam <= 1.0:
+        raise ValueError(f"one-pass joint decoding needs 0 < ctc_weight <= 1 (got {ctc_weight})")
+    C = default_pre_beam(beam_size) if pre_beam is None else int(pre_beam)
+    if C < beam_size or C > 16 or C > eng.V:
+        raise ValueError(f"pre_beam must be in beam_size..min(16, vocabulary size) (got {C} for beam {beam_size})")
+    was_training, eng.training = eng.training, False
+    try:
+        with torch.no_grad():
+            return _one_pass(model, eng, input, int(beam_size), int(nbest), int(decode_max_len), lam, C, int(check_every))
+    finally:
+        eng.training = was_training
+
+
+def _one_pass(model, eng, input, beam, nbest, decode_max_len, lam, C, check_every):
+    dec = _DecoderSteps(model, eng, input, beam, decode_max_len)
+    B, T, Lcap, R, dev = dec.B, dec.T, dec.Lcap, dec.R, dec.dev
+    # the CTC head over the search's own encoder output, once: log-probabilities transposed to (B, V, T)
+    lpT = K.ctc_prefix_logprobs(eng.ctc_lo.fwd(dec.enc).view(B, T, eng.V))
+    st = [torch.empty(T, R, dtype=torch.float64, device=dev) for _ in range(2)]         # log r^b, log (r^n + r^b) of each hypothesis
+    cand = [torch.empty(T, R * C, dtype=torch.float64, device=dev) for _ in range(2)]   # the same for every (hypothesis, candidate)
+    score = torch.zeros(B, beam, dtype=torch.float32, device=dev)
+    att_score = torch.zeros_like(score)
+    ctc_score = torch.zeros_like(score)
+    alive = torch.zeros(B, beam, dtype=torch.int32, device=dev)
+    alive[:, 0] = 1                                                       # one hypothesis [sos] per utterance
+    last_tok = torch.full((B, beam), SOS_ID, dtype=torch.int32, device=dev)
+    parent = torch.zeros(B, beam, dtype=torch.int32, device=dev)
+    rec_tok = torch.zeros(Lcap, B, beam, dtype=torch.int32, device=dev)
+    rec_par = torch.zeros_like(rec_tok)
+    rec_end = torch.zeros_like(rec_tok)
+    rec_score = torch.full((Lcap, B, beam), float("-inf"), dtype=torch.float32, device=dev)
+    rec_att = torch.full_like(rec_score, float("-inf"))
+    rec_ctc = torch.full_like(rec_score, float("-inf"))
+    alive_total = torch.zeros(Lcap, dtype=torch.int32, device=dev)
+    top = None
+    steps_done = 0
+    for i in range(Lcap):
+        logits = dec.logits(i, last_tok)
+        att_vals, att_ids = K.logsoftmax_topk(logits, C)
+        top = K.ctc_prefix_score(lpT, dec.wave_len, st[0], st[1], ctc_score.view(-1), last_tok.view(-1), alive.view(-1), att_vals, att_ids,
+                                 cand[0], cand[1], beam, i, lam, EOS_ID, BLANK_ID, out=top)
+        K.joint_beam_step(top, score, att_score, ctc_score, alive, last_tok, parent, rec_tok, rec_par, rec_end, rec_score, rec_att, rec_ctc,
+                          dec.maxlen, alive_total[i:i + 1], B, beam, i, EOS_ID, lam)
+        steps_done = i + 1
+        if i + 1 < Lcap:
+            K.ctc_prefix_gather(cand[0], cand[1], st[0], st[1], parent.view(-1), last_tok.view(-1), alive.view(-1), att_ids, dec.wave_len, B, beam)
+            dec.gather(parent, i)
+        if (i % check_every) == check_every - 1 and int(alive_total[i]) == 0:   # the only host sync of the loop
+            break
+    n = steps_done
+    return _backtrace(rec_tok[:n].cpu(), rec_par[:n].cpu(), rec_end[:n].cpu(), rec_score[:n].cpu(), B, beam, nbest,
+                      extra={"att_score": rec_att[:n].cpu(), "ctc_score": rec_ctc[:n].cpu()})

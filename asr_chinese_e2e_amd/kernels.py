@@ -423,6 +423,62 @@ def cache_gather(src, dst, parent, L, R, beam, Lcap, n_pos, row_bytes):
     check(lib.asr_cache_gather(_p(src), _p(dst), _p(parent), L, R, beam, Lcap, int(n_pos), int(row_bytes), _stream()), "asr_cache_gather")
 
 
+def ctc_prefix_logprobs(logits):
+    """log_softmax of the CTC head's frames, transposed (asr_ctc_prefix_logprobs): logits (B, T, V) f32 / bf16, dense or rows padded as
+    the engine lays them out -> (B, V, T) f32, the per-batch input of ctc_prefix_score."""
+    B, T, V = logits.shape
+    ld = _frame_rows(logits)
+    lpT = torch.empty(B, V, T, dtype=torch.float32, device=logits.device)
+    check(lib.asr_ctc_prefix_logprobs(_p(logits), _p(lpT), B, T, V, ld, _dt(logits), _stream()), "asr_ctc_prefix_logprobs")
+    return lpT
+
+
+def ctc_prefix_score(lpT, in_len, st_rb, st_rt, hyp_psi, last_tok, alive, att_vals, att_ids, cand_rb, cand_rt, beam, step, ctc_weight,
+                     eos, blank=0, out=None):
+    """One step of CTC prefix scoring (asr_ctc_prefix_score, include/asr_hip.h): lpT (B, V, T) from ctc_prefix_logprobs; state st_rb /
+    st_rt (T, R) f64, hyp_psi (R) f32, last_tok / alive (R) int32 (R = B * beam; not read at step 0); candidates att_vals / att_ids
+    (R, C); writes the candidates' state into cand_rb / cand_rt (T, R * C) f64.  Returns (vals, ids, att, psi, full), each (R, beam):
+    per hypothesis the `beam` best candidates by joint score."""
+    B, V, T = lpT.shape
+    R, C = att_ids.shape
+    assert R == B * beam and att_vals.shape == (R, C) and lpT.is_contiguous()
+    assert cand_rb.shape == cand_rt.shape == (T, R * C) and cand_rb.dtype == cand_rt.dtype == torch.float64
+    assert step == 0 or (st_rb.shape == st_rt.shape == (T, R) and st_rb.dtype == st_rt.dtype == torch.float64)
+    _chk_f32(lpT, att_vals, hyp_psi)
+    _chk_i32(in_len, last_tok, alive, att_ids)
+    if out is None:
+        dev = lpT.device
+        out = (torch.empty(R, beam, dtype=torch.float32, device=dev), torch.empty(R, beam, dtype=torch.int32, device=dev),
+               torch.empty(R, beam, dtype=torch.float32, device=dev), torch.empty(R, beam, dtype=torch.float32, device=dev),
+               torch.empty(R, beam, dtype=torch.float32, device=dev))
+    vals, ids, att, psi, full = out
+    check(lib.asr_ctc_prefix_score(_p(lpT), _p(in_len), _p(st_rb), _p(st_rt), _p(hyp_psi), _p(last_tok), _p(alive), _p(att_vals), _p(att_ids),
+                                   _p(cand_rb), _p(cand_rt), _p(vals), _p(ids), _p(att), _p(psi), _p(full), B, T, V, int(beam), C, int(step),
+                                   float(ctc_weight), int(eos), int(blank), _stream()), "asr_ctc_prefix_score")
+    return out
+
+
+def ctc_prefix_gather(cand_rb, cand_rt, st_rb, st_rt, parent, last_tok, alive, att_ids, in_len, B, beam):
+    """Every live slot r takes the state of its parent's candidate with token last_tok[r] (asr_ctc_prefix_gather)."""
+    T, R = st_rb.shape
+    C = att_ids.shape[1]
+    assert R == B * beam and cand_rb.shape == cand_rt.shape == (T, R * C) and st_rt.shape == (T, R)
+    _chk_i32(parent, last_tok, alive, att_ids, in_len)
+    check(lib.asr_ctc_prefix_gather(_p(cand_rb), _p(cand_rt), _p(st_rb), _p(st_rt), _p(parent), _p(last_tok), _p(alive), _p(att_ids), _p(in_len),
+                                    B, T, int(beam), C, _stream()), "asr_ctc_prefix_gather")
+
+
+def joint_beam_step(top, score, att_score, ctc_score, alive, last_tok, parent, rec_tok, rec_par, rec_end, rec_score, rec_att, rec_ctc, maxlen,
+                    alive_total, B, beam, step, eos, ctc_weight):
+    """One step of the one-pass joint search (asr_joint_beam_step) on ctc_prefix_score's (vals, ids, att, psi, full)."""
+    vals, ids, att, psi, full = top
+    _chk_f32(vals, att, psi, full, score, att_score, ctc_score, rec_score, rec_att, rec_ctc)
+    _chk_i32(ids, alive, last_tok, parent, rec_tok, rec_par, rec_end, maxlen, alive_total)
+    check(lib.asr_joint_beam_step(_p(vals), _p(ids), _p(att), _p(psi), _p(full), _p(score), _p(att_score), _p(ctc_score), _p(alive), _p(last_tok),
+                                  _p(parent), _p(rec_tok), _p(rec_par), _p(rec_end), _p(rec_score), _p(rec_att), _p(rec_ctc), _p(maxlen),
+                                  _p(alive_total), B, beam, int(step), int(eos), float(ctc_weight), _stream()), "asr_joint_beam_step")
+
+
 def xent_fwd_bwd(logits, gold, n_valid, ignore_index=0, smoothing=0.0, grad_scale=1.0, dlogits=None, want_grad=True,
                  row_nll=None, argmax=None):
     """argmax: optional (M) int32 tensor that receives every row's greedy class (first index of the maximum, ignored rows included)."""

@@ -307,6 +307,45 @@ int asr_beam_step(const float* top_vals, const int32_t* top_ids, float* score, i
 int asr_cache_gather(const void* src, void* dst, const int32_t* parent, int L, int R, int beam,
                      int Lcap, int n_pos, int row_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * CTC prefix scoring for one-pass joint CTC / attention beam search (Watanabe et al. 2017, section 3.2 and algorithm 2).  NOT in
+ * the reference (no CTC there).  Additive to ABI 10 (no version change).  The search (asr_chinese_e2e_amd/decode.py::
+ * one_pass_beam_search) runs, per step, asr_logsoftmax_topk with k = C (the attention candidates), asr_ctc_prefix_score,
+ * asr_joint_beam_step, then asr_ctc_prefix_gather beside asr_cache_gather.  R = B * beam hypotheses, slot r of utterance r / beam.
+ *
+ * asr_ctc_prefix_logprobs: lpT (B, V, T) f32 = log_softmax of each frame of logits ((B, T, V) `dtype`, rows `ld` apart), transposed.
+ * asr_ctc_prefix_score: the state of hypothesis r is st_rb / st_rt (T, R) f64 (frame-major, element [t * R + r]): log r^b_t(g) (paths
+ *   of frames 0..t whose collapse is g and that end in a blank) and log (r^n_t(g) + r^b_t(g)), for t < in_len[b]; hyp_psi (R) f32 =
+ *   log psi(g).  At step 0 every hypothesis is [sos] (r^n = -inf, r^b_t = sum_{tau <= t} log y_tau(blank), psi = 0) and st_rb,
+ *   st_rt, hyp_psi, last_tok are not read (may be NULL).  att_vals / att_ids (R, C): the attention candidates (beam <= C <= 16).
+ *   Per (r, j), c = att_ids[r, j], h = g + c: cand_rb / cand_rt (T, R * C) f64, element [t * R * C + r * C + j], the state of h;
+ *   log psi(h) = logsumexp_t (phi_{t-1} + log y_t(c)) with phi = r^b(g) + [c != last(g)] r^n(g), the t = 0 term only for g = [sos];
+ *   c == eos: psi = log p_ctc(g) = log (r^n + r^b)_{in_len-1}(g); c == blank: -inf; h longer than the frames can spell: -inf.
+ *   Joint score (1 - ctc_weight) * att + ctc_weight * (log psi(h) - log psi(g)), -inf for dead hypotheses (alive[r] == 0).
+ *   Out (R, beam), per hypothesis best first (ties: lower j): out_vals the joint score, out_ids the token, out_att the attention
+ *   log-probability, out_psi log psi(h), out_full log p_ctc(h) (the full-sequence probability; -inf for eos / blank).
+ *   0 < ctc_weight <= 1.  fp64 log domain inside (the log1p(exp) correction in fp32).
+ * asr_ctc_prefix_gather: for every r with alive[r] != 0, st_rb / st_rt[., r] = cand_rb / cand_rt[., p * C + j] where p = b * beam +
+ *   parent[r] and j the candidate of p with token last_tok[r] (att_ids[p, j]; the ids of a row are distinct).
+ * asr_joint_beam_step: asr_beam_step on the joint scores of asr_ctc_prefix_score (score + out_vals), with three differences:
+ *   candidates of score -inf are dropped (an utterance whose every extension is -inf ends with no hypothesis); per slot
+ *   att_score (sum of the attention log-probabilities) and ctc_score (log psi, or log p_ctc once ended) go along, with records
+ *   rec_att / rec_ctc; a hypothesis that emits eos ends with it also at the last step (rec_end 1), every other survivor of the last
+ *   step gets eos appended (rec_end 2) and its CTC part replaced by log p_ctc(h): score += ctc_weight * (full - psi).
+ */
+int asr_ctc_prefix_logprobs(const void* logits, float* lpT, int B, int T, int V, int ld, int dtype, void* stream);
+int asr_ctc_prefix_score(const float* lpT, const int32_t* in_len, const double* st_rb, const double* st_rt, const float* hyp_psi,
+                         const int32_t* last_tok, const int32_t* alive, const float* att_vals, const int32_t* att_ids, double* cand_rb,
+                         double* cand_rt, float* out_vals, int32_t* out_ids, float* out_att, float* out_psi, float* out_full, int B, int T,
+                         int V, int beam, int C, int step, float ctc_weight, int eos, int blank, void* stream);
+int asr_ctc_prefix_gather(const double* cand_rb, const double* cand_rt, double* st_rb, double* st_rt, const int32_t* parent,
+                          const int32_t* last_tok, const int32_t* alive, const int32_t* att_ids, const int32_t* in_len, int B, int T,
+                          int beam, int C, void* stream);
+int asr_joint_beam_step(const float* top_vals, const int32_t* top_ids, const float* top_att, const float* top_psi, const float* top_full,
+                        float* score, float* att_score, float* ctc_score, int32_t* alive, int32_t* last_tok, int32_t* parent, int32_t* rec_tok,
+                        int32_t* rec_par, int32_t* rec_end, float* rec_score, float* rec_att, float* rec_ctc, const int32_t* maxlen,
+                        int32_t* alive_total, int B, int beam, int step, int eos, float ctc_weight, void* stream);
+
 /* Character error rate per utterance on the device.
  * Replaces: calculate_cer (Predictor/Utils/score.py:4-13) over Vocab.convert_id2str strings
  *           (data_handler/vocab.py:75-79), called per step from cal_metrics

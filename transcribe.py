@@ -11,7 +11,9 @@ trained with rebuild it.  Inference flags:
   --wavs         comma-separated 16-bit PCM WAV files, or
   --manifest     a collector manifest (one JSON object {"wave": path, ...} per line)
   --beam_size    beam of the search (default 5)
-  --ctc_weight   joint models: weight of the CTC score in the rescoring (default: the model's ctc_weight)
+  --ctc_weight   joint models: weight of the CTC score in the search (default: the model's ctc_weight)
+  --joint        joint models: rescore (default; CTC re-ranks the attention beam's n-best list) or one_pass (CTC prefix scores
+                 take part in every step of the search)
   --batch_size   utterances per batch (default 16)
   --timestamps   per-character times from the CTC head (default: on when the model has one)
 Audio goes through load_wav -> AudioParser.parse_batch on the device -> model.transcribe; one JSON line per file is printed:
@@ -33,7 +35,7 @@ from asr_chinese_e2e_amd.data_handler import AudioParser, Vocab, load_wav  # noq
 from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps")
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint")
 
 
 def _finite(x):
@@ -84,6 +86,9 @@ def transcribe(**flags):
     beam = int(cli.get("beam_size", 5))
     bs = max(1, int(cli.get("batch_size", 16)))
     timestamps = bool(cli.get("timestamps", model.use_ctc))
+    joint = str(cli.get("joint", "rescore"))
+    if joint not in ("rescore", "one_pass"):
+        raise SystemExit(f"transcribe.py: --joint must be rescore or one_pass (got {joint!r})")
     for i in range(0, len(files), bs):
         chunk = files[i:i + bs]
         waves = []
@@ -98,7 +103,8 @@ def transcribe(**flags):
             wav[b, : len(w)] = w
         wav_len = torch.tensor([len(w) for w in waves], dtype=torch.int32)
         feats, flen = parser.parse_batch(torch.from_numpy(wav).cuda(), wav_len.cuda())
-        out = model.transcribe(Pack(wave=feats, wave_len=flen), beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps)
+        out = model.transcribe(Pack(wave=feats, wave_len=flen), beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps,
+                               joint=joint)
         for path, w, r in zip(chunk, waves, out):
             dur = len(w) / float(config.sample_rate)
             for t in r["tokens"] or ():          # the last encoder frame may reach past the end of the audio
