@@ -239,6 +239,11 @@ class _SpeechTransformer(BaseModel):
             self._tgt_len32 = None
             return eng, x, self._len32_of(input.wave_len, (), ()).contiguous(), None
         tgt = input.tgt_for_input.contiguous()
+        tl = input.tgt_len
+        if self.cross_mask == "ref_compat" and tl is not None and tl.device.type == "cpu" and tl.numel() and int(tl.max()) > tgt.shape[1]:
+            # the cross-attention's key rows are cut at the padded target width (Engine.cross_rows): a longer text length would see frames
+            # that were never projected
+            raise ValueError(f"tgt_len {int(tl.max())} exceeds the padded target width {tgt.shape[1]} of tgt_for_input")
         # the batch contract hands lengths over as int64 (ai_shell_1.py:75-88): the label preprocessing launch also makes the int32 copies
         lens64 = [t.contiguous() for t in (input.wave_len, input.tgt_len) if t is not None and t.dtype == torch.int64 and t.device == tgt.device]
         out = K.dec_preprocess(tgt, SOS_ID, EOS_ID, lens64=lens64)
@@ -246,6 +251,12 @@ class _SpeechTransformer(BaseModel):
         wave_len = self._len32_of(input.wave_len, lens64, lens32)
         self._tgt_len32 = self._len32_of(input.tgt_len, lens64, lens32) if input.tgt_len is not None else None
         return eng, x, wave_len, prep
+
+    def _cross(self, eng, input, wave_len, T):
+        """(key lengths, key rows Tk) of the decoder's encoder-decoder attention."""
+        if self.cross_mask == "ref_compat":
+            return self._tgt_len32, eng.cross_rows(input.tgt_for_input.shape[1], T, self._tgt_len32 is not None)
+        return wave_len, T
 
     @staticmethod
     def _len32_of(t, lens64, lens32):
@@ -264,8 +275,8 @@ class _SpeechTransformer(BaseModel):
         pack = Pack()
         pack.add(encoder_out=enc.view(B, T, -1))
         if self.use_decoder and prep is not None:      # teacher forcing needs the transcript
-            cross_len = self._tgt_len32 if self.cross_mask == "ref_compat" else wave_len
-            pred, _ = eng.decoder_fwd(prep, enc, cross_len, B, T)
+            cross_len, Tk = self._cross(eng, input, wave_len, T)
+            pred, _ = eng.decoder_fwd(prep, enc, cross_len, B, T, Tk)
             pack.add(pred=pred.view(B, -1, self.V), gold=prep[1].long())
         if self.use_ctc:
             logits = eng.ctc_lo.fwd(enc)
@@ -531,12 +542,13 @@ class _SpeechTransformer(BaseModel):
         ctc_done = None
         ctc_scale = dict(grad_scale=lam * loss_scale, grad_scale_div=batch_div) if batch_div is not None else dict(grad_scale=lam * loss_scale / float(B))
         ctc_async = (self.use_decoder and self.use_ctc and eng.overlap_ctc and not eng.deterministic and not torch.cuda.is_current_stream_capturing())
+        if self.use_decoder:
+            cross_len, Tk = self._cross(eng, input, wave_len, T)
         if ctc_async:      # joint model: the CTC branch runs beside the decoder's forward pass
-            eng.decoder_kv_async(prep, enc, B, T)      # ... behind the K|V projections the decoder's first cross-attention waits for
+            eng.decoder_kv_async(prep, enc, B, T, Tk)      # ... behind the K|V projections the decoder's first cross-attention waits for
             nll, d_enc, ctc_done = eng.ctc_branch_async(enc, wave_len, labels32, lab_len, B, T, **ctc_scale)
         if self.use_decoder:
-            cross_len = self._tgt_len32 if self.cross_mask == "ref_compat" else wave_len
-            pred, dcache = eng.decoder_fwd(prep, enc, cross_len, B, T)
+            pred, dcache = eng.decoder_fwd(prep, enc, cross_len, B, T, Tk)
             # the greedy ids of the step's CER come out of the loss kernel (it reads every row anyway; the gradient overwrites the logits in place)
             ids = torch.empty(ys_out.shape, dtype=torch.int32, device=pred.device) if self.cer_in_iterate else None
             w_ce = (1.0 - lam) if self.use_ctc else 1.0

@@ -58,7 +58,8 @@ class DecLayerPlan(ctypes.Structure):
                                   "dz_s", "g_as", "g_qkv", "dx_s",
                                   "dctx", "gb_2", "gb_fc_c", "gb_fc_s",
                                   "part_f", "part_c", "part_s", "delta")] +
-                [("delta_bytes", Z), ("d_enc", P), ("wgrad_stream", P), ("aux_cus", I), ("ld_kv_c", I), ("kv_dgrad_cols", I), ("g_kv_group", P), ("ctx_s_lo", P), ("ctx_c_lo", P)])
+                [("delta_bytes", Z), ("d_enc", P), ("wgrad_stream", P), ("aux_cus", I), ("ld_kv_c", I), ("kv_dgrad_cols", I), ("g_kv_group", P), ("ctx_s_lo", P), ("ctx_c_lo", P),
+                 ("w_kv_c", P), ("g_enc_x", P), ("T_enc", I)])
 
 # name -> (restype, argtypes); order and meaning exactly as in include/asr_hip.h
 SIGNATURES = {
@@ -107,6 +108,8 @@ SIGNATURES = {
     "asr_colsum_workspace_bytes": (Z, [I, I]),
     "asr_colsum": (I, [P, P, P, Z, I, I, I, I, I, P]),
     "asr_cast": (I, [P, P, Z, I, I, P]),
+    "asr_rows_gather": (I, [P, P, I, I, I, I, I, P]),
+    "asr_rows_scatter_add": (I, [P, P, I, I, I, I, I, P]),
     "asr_sumsq_workspace_bytes": (Z, [Z]),
     "asr_grad_sumsq": (I, [P, Z, P, P, Z, P]),
     "asr_noam_hyper": (I, [P, P, F, F, F, F, F, F, P]),

@@ -69,7 +69,8 @@ extern "C" int asr_decoder_layer_fwd(const asr_dec_layer_plan* p, void* stream) 
 // Also written, for the caller's weight-gradient GEMMs: g_o (dY of w_2), g_h (dY of w_1), g_ac (dY of the cross out-projection),
 // g_qc, g_kvc (dY of the cross Q and K|V projections), g_as (dY of the self out-projection), g_qkv (dY of the fused Q|K|V).
 // LayerNorm parameter gradients: per-workgroup partial sums are left in part_f / part_c / part_s (asr_add_ln_bwd_reduce_batched).
-// d_enc += g_kvc * W_kv (all encoder frames) runs on aux_stream behind a fork when aux_stream != NULL, else on `stream`.
+// d_enc += g_kvc * W_kv (over the key rows: all encoder frames, or with g_enc_x the first T of T_enc per utterance) runs on aux_stream behind a
+// fork when aux_stream != NULL, else on `stream`.
 extern "C" int asr_decoder_layer_bwd(const asr_dec_layer_plan* p, const void* dy, const void* dy2, void* stream, void* aux_stream) {
     DEC_TRY(dec_check(p, "asr_decoder_layer_bwd"));
     if (!dy) ASR_FAIL(ASR_EINVAL, "asr_decoder_layer_bwd: null dy");
@@ -93,9 +94,11 @@ extern "C" int asr_decoder_layer_bwd(const asr_dec_layer_plan* p, const void* dy
     char* gkv = (char*)p->g_kvc;
     // d_enc += dK|dV W_kv (a (B*T)-row GEMM off the decoder's dependent chain, on aux_stream) needs only the attention backward's dK|dV:
     // that kernel hands over by its own completion event (no event record - a barrier packet - in front of the chain's next kernel)
-    const bool kv_dgrad = p->d_enc && p->w_kv_c_T;
+    const bool compact = p->g_enc_x != nullptr;      // key rows t < T of T_enc encoder frames: g_enc_x = G W on them, then scattered into d_enc
+    const bool kv_dgrad = p->d_enc && (compact ? p->w_kv_c != nullptr : p->w_kv_c_T != nullptr);
     const int ldkv = p->ld_kv_c > 0 ? p->ld_kv_c : 2 * hd;
     if (p->kv_dgrad_cols > 0 && (!p->g_kv_group || p->kv_dgrad_cols % 8 || p->kv_dgrad_cols > ldkv)) ASR_FAIL(ASR_EINVAL, "asr_decoder_layer_bwd: kv_dgrad_cols = %d needs g_kv_group, a multiple of 8, <= ld_kv_c = %d", p->kv_dgrad_cols, ldkv);
+    if (compact && p->T_enc < T) ASR_FAIL(ASR_EINVAL, "asr_decoder_layer_bwd: T_enc = %d < T = %d key rows", p->T_enc, T);
     if (kv_dgrad && aux_stream) DEC_TRY(asr_stream_arm(stream, aux_stream));
     DEC_TRY(asr_sdpa_bwd(p->q_c, kv, kv + hd * e, p->ctx_c, p->dctx, p->lse_c, p->delta, p->delta_bytes, p->g_qc, gkv, gkv + hd * e, p->cross_len, B, H, To, T, dk, hd,
                          ldkv, ldkv, hd, 0, -1, scale, p->drop_p, p->seed[2], p->ctx_c_lo, ASR_BF16, stream));
@@ -107,7 +110,13 @@ extern "C" int asr_decoder_layer_bwd(const asr_dec_layer_plan* p, const void* dy
         // one layer's columns, or - this layer being the last of its group - the whole group's: ONE read-modify-write of d_enc per group
         const void* g_a = p->kv_dgrad_cols > 0 ? p->g_kv_group : p->g_kvc;
         const int cols = p->kv_dgrad_cols > 0 ? p->kv_dgrad_cols : 2 * hd;
-        const int rc_kv = asr_gemm_nt_bf16(g_a, p->w_kv_c_T, nullptr, p->d_enc, p->d_enc, B * T, d, cols, ldkv, p->ld_kv_c_T, d, ASR_ACT_NONE, st2);
+        int rc_kv;
+        if (compact) {      // B*T compact rows: the small-M kernel on W as stored, then one scatter-add into the utterances' first T frames of d_enc
+            rc_kv = asr_gemm_small_bf16(g_a, p->w_kv_c, nullptr, nullptr, p->g_enc_x, B * T, d, cols, ldkv, d, d, 1, ASR_ACT_NONE, st2);
+            if (rc_kv == ASR_OK) rc_kv = asr_rows_scatter_add(p->g_enc_x, p->d_enc, B, p->T_enc, T, d, ASR_BF16, st2);
+        } else {
+            rc_kv = asr_gemm_nt_bf16(g_a, p->w_kv_c_T, nullptr, p->d_enc, p->d_enc, B * T, d, cols, ldkv, p->ld_kv_c_T, d, ASR_ACT_NONE, st2);
+        }
         if (p->aux_cus > 0) asr_option_set(ASR_OPT_CU_LIMIT, old_lim);
         DEC_TRY(rc_kv);
     }

@@ -455,6 +455,53 @@ __global__ __launch_bounds__(EW_BLOCK) void adam_kernel(float* __restrict__ p, f
     }
 }
 
+// Rows t < Tk of each utterance of a (B*T, d) matrix <-> a compact (B*Tk, d) one, V elements per thread and step (V = 4 when d and
+// both pointers allow it).  ADD = false: compact = full rows (gather).  ADD = true: full rows += compact (fp32 add, one rounding).
+// n + grid stride < 2^31 (checked by the caller): 32-bit quotients - the 64-bit divisions are a long instruction sequence.
+template <typename T, bool ADD, int V>
+__global__ __launch_bounds__(EW_BLOCK) void rows_compact_kernel(const T* __restrict__ src, T* __restrict__ dst, int T_full, int Tk, int dv, int n) {
+    for (int i = blockIdx.x * EW_BLOCK + threadIdx.x; i < n; i += gridDim.x * EW_BLOCK) {
+        const unsigned r = (unsigned)i / (unsigned)dv, b = r / (unsigned)Tk;
+        const size_t full = (((size_t)b * T_full + (r - b * Tk)) * dv + (i - r * dv)) * V, comp = (size_t)i * V;
+        if constexpr (V == 4) {
+            if constexpr (ADD) {
+                const f32x4 a = load4<T>(dst + full), g = load4<T>(src + comp);
+                store4<T>(dst + full, a + g);
+            } else {
+                store4<T>(dst + comp, load4<T>(src + full));
+            }
+        } else {
+            if constexpr (ADD) dst[full] = from_f32<T>(to_f32<T>(dst[full]) + to_f32<T>(src[comp]));
+            else dst[comp] = src[full];
+        }
+    }
+}
+
+template <bool ADD>
+static int rows_compact(const void* src, void* dst, int B, int T, int Tk, int d, int dtype, void* stream, const char* who) {
+    if (!src || !dst) ASR_FAIL(ASR_EINVAL, "%s: null pointer", who);
+    if (B < 0 || d <= 0 || Tk < 0 || T < Tk) ASR_FAIL(ASR_EINVAL, "%s: bad shape B=%d T=%d Tk=%d d=%d", who, B, T, Tk, d);
+    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "%s: dtype %d", who, dtype);
+    if ((size_t)B * Tk == 0) return ASR_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t es = dtype == ASR_F32 ? 4 : 2;
+    const bool vec = d % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) % (4 * es) == 0);
+    const int dv = vec ? d / 4 : d;
+    const size_t n = (size_t)B * Tk * dv;
+    if (n > (size_t)INT32_MAX - (2048 * EW_BLOCK)) ASR_FAIL(ASR_EINVAL, "%s: too many rows (B=%d T=%d Tk=%d d=%d)", who, B, T, Tk, d);
+#define ROWS(T_, V_) rows_compact_kernel<T_, ADD, V_><<<ew_grid(n), EW_BLOCK, 0, st>>>((const T_*)src, (T_*)dst, T, Tk, dv, (int)n)
+    if (dtype == ASR_F32) {
+        if (vec) ROWS(float, 4);
+        else ROWS(float, 1);
+    } else {
+        if (vec) ROWS(bf16_t, 4);
+        else ROWS(bf16_t, 1);
+    }
+#undef ROWS
+    ASR_CHECK_LAUNCH(who);
+    return ASR_OK;
+}
+
 __global__ __launch_bounds__(256) void loss_combine_kernel(const float* row_nll, int M, const float* n_valid, const float* nll, int B,
                                                            float w_ce, float w_ctc, float* loss) {
     __shared__ float red[16];
@@ -570,6 +617,14 @@ extern "C" int asr_cast(const void* src, void* dst, size_t n, int sd, int dd, vo
     else ASR_FAIL(ASR_EDTYPE, "asr_cast: dtypes %d -> %d", sd, dd);
     ASR_CHECK_LAUNCH("asr_cast");
     return ASR_OK;
+}
+
+extern "C" int asr_rows_gather(const void* src, void* dst, int B, int T, int Tk, int d, int dtype, void* stream) {
+    return rows_compact<false>(src, dst, B, T, Tk, d, dtype, stream, "asr_rows_gather");
+}
+
+extern "C" int asr_rows_scatter_add(const void* src, void* dst, int B, int T, int Tk, int d, int dtype, void* stream) {
+    return rows_compact<true>(src, dst, B, T, Tk, d, dtype, stream, "asr_rows_scatter_add");
 }
 
 extern "C" size_t asr_colsum_workspace_bytes(int rows, int cols) {

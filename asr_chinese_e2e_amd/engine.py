@@ -496,8 +496,9 @@ class Engine:
         if flat.lp is not None:
             # encoder projections only: the decoder's B*To ~ 500 rows run on the 64 x 64-tile kernel with W as stored
             lins = [l for mha, ffn in self.enc for l in (mha.qkv, mha.fc, ffn.w1, ffn.w2)]
-            # ... and the decoder's cross-attention K|V weights (one matrix for all layers): they multiply all B*T encoder frames in the
-            # accumulating input gradient d_enc += dK|dV W_kv (the residual-add store tail of the own kernel, no library call)
+            # ... and the decoder's cross-attention K|V weights (one matrix for all layers): with key rows over all B*T encoder frames (cross_rows)
+            # they multiply them in the accumulating input gradient d_enc += dK|dV W_kv (the residual-add store tail of the own kernel, no library
+            # call); compact key rows use W as stored
             cross_qkv = [self.kv_all] if getattr(self, "dec", None) else []
             # ... and the CTC head (reduction over V = 4232 columns: the kernel's last k-step is ragged)
             head = [self.ctc_lo] if use_ctc else []
@@ -825,8 +826,10 @@ class Engine:
                 lin.wgrad(dy, x, with_bias=fused)
         self._keep += (dy, x)      # also while capturing (see flush_wgrads)
 
-    def _attn_block_fwd(self, m, x, kv_src, B, Tq, Tk, k_len, q_lens, causal, window, cross, site, kv_pre=None):
-        """x: (B*Tq, d) queries + residual; kv_src: (B*Tk, d).  Returns output and cache."""
+    def _attn_block_fwd(self, m, x, kv_src, B, Tq, Tk, k_len, q_lens, causal, window, cross, site, kv_pre=None, kv_rows=None):
+        """x: (B*Tq, d) queries + residual; kv_src: (B*Tk, d).  kv_rows: cross attention over compact key rows (cross_rows) - kv_src holds
+        the first Tk of kv_rows encoder frames per utterance, and the backward pass scatters its gradient back into them.  Returns output
+        and cache."""
         H, dk, hd = self.H, self.dk, self.H * self.dk
         c = {}
         if not cross:
@@ -852,7 +855,7 @@ class Engine:
         a = m.fc.fwd(ctx)
         y, xhat, rstd = K.add_ln_fwd(a, x, m.ln.g, m.ln.b, None, q_lens, B, Tq, xhat=a, drop_p=pf, drop_seed=sf, drop_mode=1)
         c.update(x=x, kv_src=kv_src, ctx=ctx, ctx_lo=ctx_lo, lse=lse, xhat=xhat, rstd=rstd, k_len=k_len, q_lens=q_lens, dims=(B, Tq, Tk), causal=causal,
-                 window=window, cross=cross, drop=(pa, sa, pf, sf))
+                 window=window, cross=cross, drop=(pa, sa, pf, sf), kv_rows=kv_rows)
         return y, c
 
     def _attn_block_bwd(self, m, c, dy, dy2, d_kv_src=None):
@@ -889,16 +892,22 @@ class Engine:
             self._wgrad(m.q, dq, c["x"], bias_from=dq)
             self._wgrad(m.kv, dkv, c["kv_src"], bias_from=dkv)
             dx = m.q.dgrad(dq)
+
+            def kv_src_grad():
+                if c["kv_rows"] is None:
+                    m.kv.dgrad(dkv, out=d_kv_src, accumulate=True)
+                else:      # compact key rows: dX of the B*Tk rows, added to the first Tk frames of each utterance
+                    K.rows_scatter_add(m.kv.dgrad(dkv), d_kv_src, B, c["kv_rows"], Tk)
             if self.aux_overlap and not torch.cuda.is_current_stream_capturing():
-                # d_enc += dK|dV W_kv (a 16000-row GEMM) is off the decoder's dependent chain: only the encoder's backward pass
+                # d_enc += dK|dV W_kv is off the decoder's dependent chain: only the encoder's backward pass
                 # needs d_enc.  It runs on the auxiliary stream (in order behind the CTC branch and the previous layers' adds);
                 # decoder_bwd joins that stream at its end.
                 self._fork(self.ctc_stream)
                 with torch.cuda.stream(self.ctc_stream):
-                    m.kv.dgrad(dkv, out=d_kv_src, accumulate=True)
+                    kv_src_grad()
                 self._keep.append(dkv)
             else:
-                m.kv.dgrad(dkv, out=d_kv_src, accumulate=True)
+                kv_src_grad()
         if self._block_flush:
             self.flush_wgrads()
         return dx, dz
@@ -1030,6 +1039,16 @@ class Engine:
     # ------------------------------------------------------------------ decoder layers through the native launch sequencer
     DEC_CACHE_SHAPES = 6
 
+    @staticmethod
+    def cross_rows(W, T, text_mask):
+        """Key rows Tk of the encoder-decoder attention.  text_mask: the keys are masked by TEXT lengths (the reference's cross mask,
+        transformer_official.py:78; cross_mask = "ref_compat"), which never exceed the padded target width W: a query then sees only
+        frames t < tgt_len[b] <= W, and every frame past them has zero weight forward and zero gradient backward.  The K|V projections,
+        their weight gradient and the encoder-output gradient then run on the first Tk = W rounded up to 16 (whole GEMM tiles; keys
+        past the length are masked) of each utterance's T frames instead of all of them - at the joint configuration 32 of 500.
+        Known on the host (no device read), so it can be captured in a graph.  Otherwise (wave lengths): all T frames."""
+        return min(T, (max(W, 1) + 15) // 16 * 16) if text_mask else T
+
     def _dec_exec_ok(self, B, To, T):
         """The C++ sequencer (csrc/decoder_exec.hip: asr_decoder_layer_fwd / _bwd) takes the decoder layers when every projection
         of the layer runs on the small-M kernel: bf16, B*To rows within its limit, widths multiples of 8.  ASR_DEC_EXEC=0 keeps
@@ -1038,11 +1057,11 @@ class Engine:
         return (self.dec_exec and self.dtype == torch.bfloat16 and K.TIMER is None and B * To <= Linear.SMALL_M and self.d % 8 == 0 and hd % 8 == 0
                 and self.ff % 8 == 0 and max(3 * hd, self.ff, self.d) <= Linear.SMALL_REDUCE)
 
-    def _dec_bufs(self, B, To, T, drop):
+    def _dec_bufs(self, B, To, T, Tk, drop):
         """Persistent activation / gradient buffers and launch plans of the decoder layers for one batch shape (the layer sequence
         is fixed, so nothing is allocated per step; steps are sequential and the optimizer joins every side stream before the
-        next forward pass touches these buffers)."""
-        key = (B, To, T, bool(drop))
+        next forward pass touches these buffers).  Tk: key rows of the cross-attention (cross_rows)."""
+        key = (B, To, T, Tk, bool(drop))
         hit = self._dec_cache.get(key)
         capturing = torch.cuda.is_current_stream_capturing()
         if hit is not None:
@@ -1058,14 +1077,17 @@ class Engine:
         bf = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=dev)
         f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         part_bytes = K.add_ln_bwd_workspace_bytes(M, d)
-        need = max(_lib.lib.asr_sdpa_bwd_workspace_bytes(B, H, To, T, self.dk, 0, -1, _lib.ASR_BF16), _lib.lib.asr_sdpa_bwd_workspace_bytes(B, H, To, To, self.dk, 1, -1, _lib.ASR_BF16))
+        need = max(_lib.lib.asr_sdpa_bwd_workspace_bytes(B, H, To, Tk, self.dk, 0, -1, _lib.ASR_BF16), _lib.lib.asr_sdpa_bwd_workspace_bytes(B, H, To, To, self.dk, 1, -1, _lib.ASR_BF16))
         delta = f32((need + 3) // 4)
         layers = []
         # K | V of the encoder frames for ALL layers in one buffer (layer i = columns [i 2hd, (i+1) 2hd): the attention kernels take a row
         # stride), and the gradient wrt it likewise: the six projections are one GEMM forward (two launches: layer 0's columns first), the
         # encoder-output gradient d_enc += G W_kv one GEMM per layer GROUP with the reduction over the group's columns, and the weight
-        # gradient one problem per group (self.kv_groups)
-        kv_all, g_kv_all = bf(B * T, self.L * 2 * hd), bf(B * T, self.L * 2 * hd)
+        # gradient one problem per group (self.kv_groups).  All of it over the B*Tk key rows: with Tk < T (compact rows, cross_rows) the
+        # first Tk frames of each utterance are gathered into enc_x, and the encoder-output gradient of those rows (g_enc_x) is scattered back
+        kv_all, g_kv_all = bf(B * Tk, self.L * 2 * hd), bf(B * Tk, self.L * 2 * hd)
+        compact = Tk < T
+        enc_x, g_enc_x = (bf(B * Tk, d), bf(B * Tk, d)) if compact else (None, None)
         for i, (slf, cross, ffn) in enumerate(self.dec):
             t = dict(qkv_s=bf(M, 3 * hd), ctx_s=bf(M, hd), a_s=bf(M, d), y_s=bf(M, d), lse_s=f32(B, H, To), rstd_s=f32(M),
                      q_c=bf(M, hd), kv_c=kv_all[:, i * 2 * hd:(i + 1) * 2 * hd], ctx_c=bf(M, hd), a_c=bf(M, d), y_c=bf(M, d), lse_c=f32(B, H, To), rstd_c=f32(M),
@@ -1077,8 +1099,10 @@ class Engine:
             if drop:      # pre-residual dropout: the gradient wrt a projection's output is its own tensor
                 t.update(g_o=bf(M, d), g_ac=bf(M, d), g_as=bf(M, d))
             pl = _lib.DecLayerPlan()
-            pl.B, pl.To, pl.T, pl.d, pl.H, pl.dk, pl.ff = B, To, T, d, H, self.dk, ff
+            pl.B, pl.To, pl.T, pl.d, pl.H, pl.dk, pl.ff = B, To, Tk, d, H, self.dk, ff
             pl.ld_kv_c = self.L * 2 * hd
+            pl.T_enc = T
+            pl.g_enc_x = g_enc_x.data_ptr() if compact else None
             for name, ten in t.items():
                 setattr(pl, name, ten.data_ptr())
             for name, lin in (("qkv_s", slf.qkv), ("fc_s", slf.fc), ("q_c", cross.q), ("fc_c", cross.fc), ("1", ffn.w1), ("2", ffn.w2)):
@@ -1088,30 +1112,39 @@ class Engine:
                 setattr(pl, "g_" + name, ln.g.data_ptr())
                 setattr(pl, "be_" + name, ln.b.data_ptr())
             pl.gb_2, pl.gb_fc_c, pl.gb_fc_s = ffn.w2.gb.data_ptr(), cross.fc.gb.data_ptr(), slf.fc.gb.data_ptr()
-            if cross.kv.wlpT is not None:
+            if cross.kv.wlpT is not None and not compact:
                 pl.w_kv_c_T, pl.ld_kv_c_T = cross.kv.wlpT.data_ptr(), cross.kv.wlpT.stride(0)
             pl.delta, pl.delta_bytes = delta.data_ptr(), delta.numel() * 4
             t["kv_event"] = torch.cuda.Event()
             layers.append((pl, t))
-        hit = self._dec_cache[key] = dict(layers=layers, delta=delta, pinned=capturing, kv_all=kv_all, g_kv_all=g_kv_all, kv_event_rest=torch.cuda.Event())
+        hit = self._dec_cache[key] = dict(layers=layers, delta=delta, pinned=capturing, kv_all=kv_all, g_kv_all=g_kv_all, kv_event_rest=torch.cuda.Event(),
+                                          rows=(B, T, Tk), enc_x=enc_x, g_enc_x=g_enc_x)
         return hit
 
+    def _kv_src(self, bufs, enc):
+        """The rows the K|V projections read: enc, or with compact key rows the first Tk frames of each utterance, gathered into
+        bufs["enc_x"] (1 MB at the joint configuration) on the current stream."""
+        if bufs["enc_x"] is None:
+            return enc
+        return K.rows_gather(enc, *bufs["rows"], out=bufs["enc_x"])
+
     def _kv_exec_async(self, bufs, enc):
-        """The six cross-attention K|V projections of the encoder output (16000-row GEMMs, ~24 us each) on the auxiliary stream, one event
-        each: they do not depend on the decoder state, and the main stream works through the decoder's small kernels meanwhile."""
+        """The six cross-attention K|V projections of the encoder output on the auxiliary stream, one event each: they do not depend on
+        the decoder state, and the main stream works through the decoder's small kernels meanwhile."""
         self._fork(self.ctc_stream)
         with torch.cuda.stream(self.ctc_stream):
             if self.dec_cu_limit:
                 K.set_cu_limit(self.dec_cu_limit)
             try:
+                src = self._kv_src(bufs, enc)
                 # layer 0's columns first (the chain's first cross-attention, ~80 us in, waits for them), then layers 1 .. L-1 as ONE GEMM
                 n0 = self.dec[0][1].kv.N
                 pl0, t0 = bufs["layers"][0]
-                self.dec[0][1].kv.fwd(enc, out=t0["kv_c"])
+                self.dec[0][1].kv.fwd(src, out=t0["kv_c"])
                 t0["kv_event"].record(self.ctc_stream)
                 pl0.kv_ready_event = t0["kv_event"].cuda_event
                 if self.L > 1:
-                    self.kv_all.rows(n0, self.kv_all.N).fwd(enc, out=bufs["kv_all"][:, n0:])
+                    self.kv_all.rows(n0, self.kv_all.N).fwd(src, out=bufs["kv_all"][:, n0:])
                     bufs["kv_event_rest"].record(self.ctc_stream)
                     for pl, t in bufs["layers"][1:]:
                         pl.kv_ready_event = bufs["kv_event_rest"].cuda_event
@@ -1120,7 +1153,7 @@ class Engine:
                     K.set_cu_limit(0)
         self._keep.append(enc)
 
-    def decoder_kv_async(self, prep, enc, B, T):
+    def decoder_kv_async(self, prep, enc, B, T, Tk=None):
         """Called by the training step BEFORE ctc_branch_async: queues the K|V projections on the auxiliary stream AHEAD of the CTC branch.
         Issued from decoder_fwd they sat behind the whole branch (head GEMM, loss kernels, its input gradient: ~0.3 ms), and the
         decoder's first cross-attention - ~80 us into the chain - waited for layer 0's projection at the end of that queue (kernel
@@ -1129,21 +1162,22 @@ class Engine:
         To = prep[0].shape[1]
         if not (self.aux_overlap and not torch.cuda.is_current_stream_capturing() and self._dec_exec_ok(B, To, T)):
             return
-        bufs = self._dec_bufs(B, To, T, self.training and self.drop_p > 0.0)
+        bufs = self._dec_bufs(B, To, T, T if Tk is None else Tk, self.training and self.drop_p > 0.0)
         self._kv_exec_async(bufs, enc)
         self._kv_ahead = (bufs, enc)
 
-    def _dec_exec_fwd(self, x, enc, dec_len, cross_len, B, To, T):
+    def _dec_exec_fwd(self, x, enc, dec_len, cross_len, B, To, T, Tk):
         drop = self.training and self.drop_p > 0.0
-        bufs = self._dec_bufs(B, To, T, drop)
+        bufs = self._dec_bufs(B, To, T, Tk, drop)
         main = K._stream()
         overlap = self.aux_overlap and not torch.cuda.is_current_stream_capturing()
         ahead, self._kv_ahead = self._kv_ahead, None
         if overlap and not (ahead is not None and ahead[0] is bufs and ahead[1] is enc):      # not issued ahead of the CTC branch (decoder_kv_async)
             self._kv_exec_async(bufs, enc)
+        src = self._kv_src(bufs, enc) if not overlap else None
         for i, ((pl, t), (_, cross, _)) in enumerate(zip(bufs["layers"], self.dec)):
             if not overlap:
-                cross.kv.fwd(enc, out=t["kv_c"])
+                cross.kv.fwd(src, out=t["kv_c"])
                 pl.kv_ready_event = None
             pl.x_in = x.data_ptr()
             pl.dec_len, pl.cross_len = dec_len.data_ptr(), cross_len.data_ptr()
@@ -1163,42 +1197,48 @@ class Engine:
         M = dy.shape[0]
         nkv = self.dec[0][1].kv.N
         groups = {lo: (lo, hi) for lo, hi in self.kv_groups}      # keyed by the layer that closes the group
+        compact = bufs["enc_x"] is not None      # compact key rows: the small-M kernel on W_kv as stored, no transposed copy
+        src = bufs["enc_x"] if compact else enc
         for i in reversed(range(self.L)):
             pl, t = bufs["layers"][i]
             slf, cross, ffn = self.dec[i]
-            if cross.kv.wlpT is not None:
+            own_kv = compact or cross.kv.wlpT is not None      # the sequencer runs the encoder-output gradient itself
+            if own_kv and not compact:
                 cross.kv._fresh_transpose()
             if d_enc_ready is not None:      # d_enc must hold the CTC branch's contribution before the first cross-attention add
                 torch.cuda.current_stream().wait_event(d_enc_ready)
                 d_enc_ready = None
             # the encoder-output gradient d_enc += G W_kv runs once per GROUP of layers (self.kv_groups), issued by the group's last layer
             # (the lowest index: the backward pass walks downwards) over the group's columns of the shared gradient buffer
-            grp = groups.get(i) if cross.kv.wlpT is not None else None
+            grp = groups.get(i) if own_kv else None
             pl.d_enc, pl.kv_dgrad_cols, pl.g_kv_group = None, 0, None
             if grp is not None:
                 c0, c1 = grp[0] * nkv, grp[1] * nkv
                 pl.d_enc, pl.kv_dgrad_cols = d_enc.data_ptr(), c1 - c0
                 pl.g_kv_group = bufs["g_kv_all"][:, c0:].data_ptr()
-                pl.w_kv_c_T, pl.ld_kv_c_T = self.kv_all.wlpT[:, c0:].data_ptr(), self.kv_all.wlpT.stride(0)
+                if compact:
+                    pl.w_kv_c = self.kv_all.wlp[c0:].data_ptr()
+                else:
+                    pl.w_kv_c_T, pl.ld_kv_c_T = self.kv_all.wlpT[:, c0:].data_ptr(), self.kv_all.wlpT.stride(0)
             hand_over = self.armed_fork and self.overlap_wgrad and not torch.cuda.is_current_stream_capturing()
             pl.wgrad_stream = self._side_handle if hand_over else None      # the layer's last kernel signals the weight-gradient stream itself
             pl.aux_cus = self.dec_cu_limit if aux is not None else 0
             _lib.check(_lib.fast.asr_decoder_layer_bwd(ctypes.addressof(pl), dy.data_ptr(), None if dy2 is None else dy2.data_ptr(), main, aux),
                        "asr_decoder_layer_bwd")
             self._armed = self._arm_covers_pending = hand_over      # consumed (or found pending) by the next _fork(self.side): flush_wgrads in _ready
-            if cross.kv.wlpT is None:      # no transposed copy (odd widths): the accumulating input gradient through the generic path
+            if not own_kv:      # no transposed copy (odd widths): the accumulating input gradient through the generic path
                 cross.kv.dgrad(t["g_kvc"], out=d_enc, accumulate=True)
             # weight gradients of the layer (one grouped launch on the side stream) and the LayerNorm parameter-gradient partial sums
             self._wgrad(ffn.w2, t["g_o"] if drop else t["dz_f"], t["h"])
             self._wgrad(ffn.w1, t["g_h"], t["y_c"], bias_from=t["g_h"])
             self._wgrad(cross.fc, t["g_ac"] if drop else t["dz_c"], t["ctx_c"])
             self._wgrad(cross.q, t["g_qc"], t["y_s"], bias_from=t["g_qc"])
-            if cross.kv.wlpT is None:
+            if not own_kv:
                 self._wgrad(cross.kv, t["g_kvc"], enc, bias_from=t["g_kvc"])
             elif grp is not None:      # the K | V weight gradients of the group's layers as ONE problem (their rows of the shared matrix are adjacent)
                 c0, c1 = grp[0] * nkv, grp[1] * nkv
                 g = bufs["g_kv_all"][:, c0:c1]
-                self._wgrad(self.kv_all.rows(c0, c1), g, enc, bias_from=g)
+                self._wgrad(self.kv_all.rows(c0, c1), g, src, bias_from=g)
             self._wgrad(slf.fc, t["g_as"] if drop else t["dz_s"], t["ctx_s"])
             self._wgrad(slf.qkv, t["g_qkv"], t["x_in"], bias_from=t["g_qkv"])
             self._ln_pending += [(t["part_f"], ffn.ln.gg, ffn.ln.gb, ffn.w2.gb, M), (t["part_c"], cross.ln.gg, cross.ln.gb, cross.fc.gb, M),
@@ -1209,35 +1249,39 @@ class Engine:
         return dy, dy2
 
     # ------------------------------------------------------------------ decoder
-    def decoder_fwd(self, prep, enc, cross_len, B, T):
-        """prep = kernels.dec_preprocess(tgt).  transformer_official.py:277-328."""
+    def decoder_fwd(self, prep, enc, cross_len, B, T, Tk=None):
+        """prep = kernels.dec_preprocess(tgt).  transformer_official.py:277-328.  Tk: key rows of the cross-attention (cross_rows;
+        None = all T frames)."""
         ys_in, ys_out, labels32, dec_len, lab_len, n_valid = prep
         To = ys_in.shape[1]
+        Tk = T if Tk is None else Tk
         pe_, se_ = self._drop(2)           # dropout(emb * scale + PE)  (transformer_official.py:306-307)
         x = K.embed_pe_fwd(ys_in.reshape(-1), self.emb32, self.pe, self.d ** -0.5, B, To, self.dtype, drop_p=pe_, drop_seed=se_)
         cache = dict(B=B, T=T, To=To, ys_in=ys_in, layers=[], drop=(pe_, se_))
         if self._dec_exec_ok(B, To, T):
-            x, bufs = self._dec_exec_fwd(x, enc, dec_len, cross_len, B, To, T)
+            x, bufs = self._dec_exec_fwd(x, enc, dec_len, cross_len, B, To, T, Tk)
             cache.update(exec_bufs=bufs, enc=enc, keep=(dec_len, cross_len))      # the plans hold raw pointers to the length vectors
             pred = self.prj.fwd(x)
             cache["x_last"] = x
             return pred, cache
         kv_pre = [None] * self.L
+        kv_rows = T if Tk < T else None
+        src = K.rows_gather(enc, B, T, Tk) if kv_rows else enc      # compact key rows: the first Tk frames of each utterance
         if self.aux_overlap and not torch.cuda.is_current_stream_capturing():
-            # the six cross-attention K|V projections of the encoder output (16000-row GEMMs, 26 us each) do not depend on the
+            # the six cross-attention K|V projections of the encoder output do not depend on the
             # decoder state: they run on the auxiliary stream while the main stream works through the decoder's small kernels
             self._fork(self.ctc_stream)
             with torch.cuda.stream(self.ctc_stream):
                 for i, (slf, cross, ffn) in enumerate(self.dec):
-                    kv = cross.kv.fwd(enc)
+                    kv = cross.kv.fwd(src)
                     e = torch.cuda.Event()
                     e.record(self.ctc_stream)
                     kv_pre[i] = (kv, e)
-            self._keep.append(enc)
+            self._keep += (enc, src)
             self._keep += [kv for kv, _ in kv_pre]      # blocks of the auxiliary stream's pool, read on the main stream
         for i, (slf, cross, ffn) in enumerate(self.dec):
             x1, c1 = self._attn_block_fwd(slf, x, x, B, To, To, dec_len, dec_len, True, -1, False, site=100 + 8 * i)
-            x2, c2 = self._attn_block_fwd(cross, x1, enc, B, To, T, cross_len, dec_len, False, -1, True, site=102 + 8 * i, kv_pre=kv_pre[i])
+            x2, c2 = self._attn_block_fwd(cross, x1, src, B, To, Tk, cross_len, dec_len, False, -1, True, site=102 + 8 * i, kv_pre=kv_pre[i], kv_rows=kv_rows)
             x, c3 = self._ffn_block_fwd(ffn, x2, B, To, dec_len, site=104 + 8 * i)
             cache["layers"].append((c1, c2, c3))
         pred = self.prj.fwd(x)

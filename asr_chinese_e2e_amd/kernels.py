@@ -600,6 +600,23 @@ def cast(src, dst):
     return dst
 
 
+def rows_gather(src, B, T, Tk, out=None):
+    """(B*Tk, d) = rows t < Tk of every utterance of src (B*T, d)."""
+    assert src.is_contiguous() and src.dim() == 2 and src.shape[0] == B * T and 0 <= Tk <= T
+    out = torch.empty(B * Tk, src.shape[1], dtype=src.dtype, device=src.device) if out is None else out
+    assert out.is_contiguous() and out.shape == (B * Tk, src.shape[1]) and out.dtype == src.dtype
+    check(lib.asr_rows_gather(_p(src), _p(out), B, T, Tk, src.shape[1], _dt(src), _stream()), "asr_rows_gather")
+    return out
+
+
+def rows_scatter_add(src, dst, B, T, Tk):
+    """dst (B*T, d) rows t < Tk of every utterance += src (B*Tk, d), in place."""
+    assert src.is_contiguous() and dst.is_contiguous() and src.dtype == dst.dtype and 0 <= Tk <= T
+    assert src.shape == (B * Tk, dst.shape[1]) and dst.shape[0] == B * T
+    check(lib.asr_rows_scatter_add(_p(src), _p(dst), B, T, Tk, dst.shape[1], _dt(dst), _stream()), "asr_rows_scatter_add")
+    return dst
+
+
 # --------------------------------------------------------------------------------- optimizer
 def grad_sumsq(g, out, ws):
     _chk_f32(g, out)

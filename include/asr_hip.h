@@ -415,6 +415,12 @@ int asr_relu_bwd(void* da, const void* a, float* dbias, void* ws, size_t ws_byte
 size_t asr_colsum_workspace_bytes(int rows, int cols);
 int asr_colsum(const void* x, float* out, void* ws, size_t ws_bytes, int rows, int cols, int ld,
                int accumulate, int dtype, void* stream);
+/* The first Tk of every T rows of a (B*T, d) `dtype` matrix and a compact (B*Tk, d) one (Tk <= T): the encoder frames the decoder's
+ * cross-attention can see under the reference's text-length mask (transformer_official.py:78).
+ *   asr_rows_gather:       dst (B*Tk, d) = src rows b*T + t, t < Tk
+ *   asr_rows_scatter_add:  dst rows b*T + t += src (B*Tk, d) row b*Tk + t  (fp32 add, one rounding) */
+int asr_rows_gather(const void* src, void* dst, int B, int T, int Tk, int d, int dtype, void* stream);
+int asr_rows_scatter_add(const void* src, void* dst, int B, int T, int Tk, int d, int dtype, void* stream);
 /* dst (n) `dst_dtype` = src (n) `src_dtype`  (f32 <-> bf16 conversion / copy) */
 int asr_cast(const void* src, void* dst, size_t n, int src_dtype, int dst_dtype, void* stream);
 /* Transposed copies of many matrices that live in one flat bf16 buffer, one launch: for tile t,
@@ -570,6 +576,14 @@ typedef struct asr_dec_layer_plan {
     const void* g_kv_group;
     /* ABI 10: the low-order pieces of the two attention outputs (asr_sdpa_fwd's o_lo), (M, H dk) each, or NULL */
     void *ctx_s_lo, *ctx_c_lo;
+    /* Compact key rows (still ABI 10, fields appended): when the cross-attention sees only the first T frames of each utterance (T <= T_enc;
+     * the reference's mask from text lengths, transformer_official.py:78), kv_c / g_kvc hold the K | V of those B*T rows only.  g_enc_x
+     * != NULL: the encoder-output gradient becomes g_enc_x (B*T, d) = g_kv_group W_group on the small-M kernel, with w_kv_c = the group's
+     * (kv_dgrad_cols, d) rows of the K|V weight AS STORED, then d_enc (B*T_enc, d) += g_enc_x scattered into rows t < T of each utterance
+     * (asr_rows_scatter_add); w_kv_c_T is not read.  g_enc_x == NULL: d_enc += ... over all B*T rows as above. */
+    const void* w_kv_c;
+    void* g_enc_x;
+    int T_enc;                             /* encoder frames per utterance of d_enc (row stride of its utterances); read only with g_enc_x */
 } asr_dec_layer_plan;
 int asr_decoder_layer_fwd(const asr_dec_layer_plan* plan, void* stream);
 /* (dy, dy2): gradient wrt y_f (dy2 may be NULL; the two are added).  Results: plan->dx_s and plan->dz_s = gradient wrt x_in through the
