@@ -479,10 +479,10 @@ __global__ __launch_bounds__(EW_BLOCK) void rows_compact_kernel(const T* __restr
 
 template <bool ADD>
 static int rows_compact(const void* src, void* dst, int B, int T, int Tk, int d, int dtype, void* stream, const char* who) {
-    if (!src || !dst) ASR_FAIL(ASR_EINVAL, "%s: null pointer", who);
     if (B < 0 || d <= 0 || Tk < 0 || T < Tk) ASR_FAIL(ASR_EINVAL, "%s: bad shape B=%d T=%d Tk=%d d=%d", who, B, T, Tk, d);
     if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "%s: dtype %d", who, dtype);
-    if ((size_t)B * Tk == 0) return ASR_OK;
+    if ((size_t)B * Tk == 0) return ASR_OK;      // nothing to move: the empty side may be an allocation of 0 bytes (NULL)
+    if (!src || !dst) ASR_FAIL(ASR_EINVAL, "%s: null pointer", who);
     hipStream_t st = (hipStream_t)stream;
     const size_t es = dtype == ASR_F32 ? 4 : 2;
     const bool vec = d % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) % (4 * es) == 0);

@@ -1088,6 +1088,10 @@ class Engine:
         kv_all, g_kv_all = bf(B * Tk, self.L * 2 * hd), bf(B * Tk, self.L * 2 * hd)
         compact = Tk < T
         enc_x, g_enc_x = (bf(B * Tk, d), bf(B * Tk, d)) if compact else (None, None)
+        # heads over more than 512 keys: the low-order piece of the attention output for the backward pass's delta (asr_sdpa_fwd's o_lo),
+        # as _attn_block_fwd allocates it - cross-attention over Tk > 512 encoder rows (cross_mask = "wave_len"), self-attention over
+        # To > 512 tokens (B = 1 within the sequencer's row limit)
+        lo_c, lo_s = Tk > 512, To > 512
         for i, (slf, cross, ffn) in enumerate(self.dec):
             t = dict(qkv_s=bf(M, 3 * hd), ctx_s=bf(M, hd), a_s=bf(M, d), y_s=bf(M, d), lse_s=f32(B, H, To), rstd_s=f32(M),
                      q_c=bf(M, hd), kv_c=kv_all[:, i * 2 * hd:(i + 1) * 2 * hd], ctx_c=bf(M, hd), a_c=bf(M, d), y_c=bf(M, d), lse_c=f32(B, H, To), rstd_c=f32(M),
@@ -1098,6 +1102,10 @@ class Engine:
                      part_s=torch.empty(part_bytes, dtype=torch.uint8, device=dev))
             if drop:      # pre-residual dropout: the gradient wrt a projection's output is its own tensor
                 t.update(g_o=bf(M, d), g_ac=bf(M, d), g_as=bf(M, d))
+            if lo_s:
+                t["ctx_s_lo"] = bf(M, hd)
+            if lo_c:
+                t["ctx_c_lo"] = bf(M, hd)
             pl = _lib.DecLayerPlan()
             pl.B, pl.To, pl.T, pl.d, pl.H, pl.dk, pl.ff = B, To, Tk, d, H, self.dk, ff
             pl.ld_kv_c = self.L * 2 * hd

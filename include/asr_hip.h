@@ -418,7 +418,8 @@ int asr_colsum(const void* x, float* out, void* ws, size_t ws_bytes, int rows, i
 /* The first Tk of every T rows of a (B*T, d) `dtype` matrix and a compact (B*Tk, d) one (Tk <= T): the encoder frames the decoder's
  * cross-attention can see under the reference's text-length mask (transformer_official.py:78).
  *   asr_rows_gather:       dst (B*Tk, d) = src rows b*T + t, t < Tk
- *   asr_rows_scatter_add:  dst rows b*T + t += src (B*Tk, d) row b*Tk + t  (fp32 add, one rounding) */
+ *   asr_rows_scatter_add:  dst rows b*T + t += src (B*Tk, d) row b*Tk + t  (fp32 add, one rounding)
+ * B*Tk == 0 is a no-op, and then src / dst may be NULL (empty allocations); T < Tk is refused. */
 int asr_rows_gather(const void* src, void* dst, int B, int T, int Tk, int d, int dtype, void* stream);
 int asr_rows_scatter_add(const void* src, void* dst, int B, int T, int Tk, int d, int dtype, void* stream);
 /* dst (n) `dst_dtype` = src (n) `src_dtype`  (f32 <-> bf16 conversion / copy) */

@@ -1029,16 +1029,19 @@ def test_beam_search_cross_attention_kernels_agree(T, monkeypatch):
         assert ha[0]["yseq"] == hb[0]["yseq"] or abs(ha[0]["score"] - hb[0]["score"]) < 0.05       # a near tie may swap ranks
 
 
+@pytest.mark.parametrize("cross_mask,T", [("ref_compat", 500), ("wave_len", 500), ("wave_len", 600)])
 @pytest.mark.parametrize("dropout", [0.0, 0.1])
-def test_decoder_sequencer_matches_per_kernel_path(dropout, monkeypatch):
+def test_decoder_sequencer_matches_per_kernel_path(dropout, cross_mask, T, monkeypatch):
     """The native launch sequencer of the decoder layers (csrc/decoder_exec.hip: one host call per layer and direction) issues the same
     kernels in the same order as the per-kernel Python path (ASR_DEC_EXEC=0): in deterministic mode (ordered reductions) loss, logits and
-    every gradient are bit-identical, with and without dropout (same per-site mask seeds)."""
+    every gradient are bit-identical, with and without dropout (same per-site mask seeds).  Under both cross masks: "ref_compat" runs the
+    compact key rows (Tk = round_up(W, 16) < T), "wave_len" all T frames with the transposed K|V weight - at T = 600 over more than 512
+    keys, where the cross-attention backward takes the two-kernel path that reads the low-order piece of the forward output (o_lo)."""
     from asr_chinese_e2e_amd import kernels as K
-    over = dict(d_model=512, hidden_size=64, num_head=8, ff_size=1024, layer_num=2, ctc_weight=0.3, dropout=dropout)
+    over = dict(d_model=512, hidden_size=64, num_head=8, ff_size=1024, layer_num=2, ctc_weight=0.3, dropout=dropout, cross_mask=cross_mask)
     # 9 x 500 = 4500 encoder frames: the accumulating input gradient d_enc += dK|dV W_kv takes the persistent NT kernel on both paths
     # (below 4096 rows the per-kernel path sends it through the fp32 kernel, which rounds differently)
-    cfg, sd, batch = oracle_case(9, 500, 80, 56, 12, over, seed=9)
+    cfg, sd, batch = oracle_case(9, T, 80, 56, 12, over, seed=9)
     pack = to_pack(batch)
     prev = K.set_deterministic(True)
     try:
@@ -1054,11 +1057,49 @@ def test_decoder_sequencer_matches_per_kernel_path(dropout, monkeypatch):
             loss, _ = model.train_step(pack)
             torch.cuda.synchronize()
             assert ("exec" if mode == "1" else "python") and bool(eng._dec_cache) == (mode == "1")      # the sequencer really ran (or did not)
+            if mode == "1":      # the key rows the case is meant to run: Tk of the cache key (B, To, T, Tk, drop)
+                Tks = {k[3] for k in eng._dec_cache}
+                assert (Tks == {T}) if cross_mask == "wave_len" else all(tk < T for tk in Tks), Tks
             res[mode] = (loss.clone(), model._flat.g.clone())
     finally:
         K.set_deterministic(prev)
     assert torch.equal(res["1"][0], res["0"][0]), (res["1"][0], res["0"][0])
     assert torch.equal(res["1"][1], res["0"][1]), float((res["1"][1] - res["0"][1]).abs().max())
+
+
+@pytest.mark.parametrize("dec_exec", ["1", "0"])
+def test_wave_len_cross_attention_over_long_keys_matches_oracle(dec_exec, monkeypatch):
+    """cross_mask = "wave_len" at T = 640 > 512 encoder frames, bf16, d_model 512, 2 layers: the decoder's cross-attention backward runs
+    the two-kernel path, whose delta needs the low-order piece of the forward output (asr_hip.h: asr_sdpa_fwd's o_lo) - on the sequencer
+    (ASR_DEC_EXEC=1) as on the per-kernel path (=0).  Gate: the gradients of every decoder enc_attn.w_qs / w_ks against the fp64 oracle
+    run on the weight matrices rounded to bf16 (the numbers the MFMA path multiplies by, as in test_long_form_window_matches_oracle),
+    cosine >= BF16_COS; the measured values are recorded through _report."""
+    over = dict(d_model=512, hidden_size=64, num_head=8, ff_size=1024, layer_num=2, ctc_weight=0.3, cross_mask="wave_len")
+    B, T, F, V, L = 2, 640, 80, 56, 12
+    cfg, sd, batch = oracle_case(B, T, F, V, L, over, seed=21)
+    sd["decoder.tgt_word_emb.weight"] = sd["decoder.tgt_word_emb.weight"] * 0.05
+    sd["decoder.tgt_word_prj.weight"] = sd["decoder.tgt_word_emb.weight"]
+    assert int(batch["wave_len"].max()) > 512
+    sd16 = {k: (v.bfloat16().float() if v.dim() == 2 else v).double() for k, v in sd.items()}
+    _, grads = R.RefTrainer(sd16, cfg, warmup=25).loss_and_grads(dict(batch, wave=batch["wave"].double()))
+    monkeypatch.setenv("ASR_DEC_EXEC", dec_exec)
+    model = build(cfg, V, "TransformerOffical", dtype="bf16").cuda()
+    model.load_state_dict(sd)
+    eng = model._ensure_engine(DEV)
+    assert eng.dec_exec == (dec_exec == "1")
+    model.zero_flat_grads()
+    model.train_step(to_pack(batch))
+    torch.cuda.synchronize()
+    assert bool(eng._dec_cache) == (dec_exec == "1")      # the sequencer ran (or did not)
+    params = dict(model.named_parameters())
+    rows = {}
+    for i in range(cfg.layer_num):
+        for n in (f"decoder.layer_stack.{i}.enc_attn.w_qs.weight", f"decoder.layer_stack.{i}.enc_attn.w_qs.bias",
+                  f"decoder.layer_stack.{i}.enc_attn.w_ks.weight"):
+            rows[n] = cos(params[n].grad, grads[n].float())
+    _report("wave_len_long_keys_dec_exec_" + dec_exec, rows)
+    for n, c in rows.items():
+        assert c >= BF16_COS, (n, c)
 
 
 def test_step_cer_beside_backward_matches_inline(monkeypatch):
