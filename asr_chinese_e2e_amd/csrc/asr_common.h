@@ -198,7 +198,7 @@ static __global__ __launch_bounds__(1024) void colsum_finalize_kernel(const floa
 // forward and backward regenerate identical masks, nothing is stored.  keep <=> 16 bits >= p*65536.
 // Round 3: two 24-bit multiplies (v_mul_u32_u24, full rate) instead of three 32-bit ones (v_mul_lo_u32, quarter rate): 9 full-rate
 // vector instructions per pair instead of ~19 issue slots; each xor-shift folds the bits the next multiply would drop (it reads the low
-// 24) into the ones it keeps.  Checked on 4 M consecutive indices (numpy emulation): drop rate 0.10006 / 0.09997 at p = 0.1 for the
+// 24) into the ones it keeps.  Checked on 4 M consecutive indices (numpy emulation: tests/dropout_ref.py): drop rate 0.10006 / 0.09997 at p = 0.1 for the
 // two halves, |correlation| of the keep bits <= 2.3e-3 at lags 1, 250, 256, 1024, between the halves and between seeds s, s + 1;
 // chi-square of the top byte 229 / 199 on 255 degrees of freedom.
 __device__ __forceinline__ uint32_t drop_hash(uint32_t pair, uint32_t seed) {

@@ -717,7 +717,7 @@ extern "C" int asr_dropout_mask(uint8_t* mask, int rows, int cols, float drop_p,
 
 extern "C" int asr_sdpa_dropout_mask(uint8_t* mask, int B, int H, int Tq, int Tk, float drop_p, uint32_t drop_seed, void* stream) {
     if (!mask || B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0) ASR_FAIL(ASR_EINVAL, "asr_sdpa_dropout_mask: bad arguments");
-    const size_t n = (size_t)B * H * Tq * Tk;   // element index ((b*H+h)*Tq+q)*Tk+k is the linear index
+    const size_t n = (size_t)B * H * Tq * Tk;   // mask[((b*H+h)*Tq+q)*Tk+k], element counter ((b*H+h)*Tq+q)*((Tk+1)&~1)+k (the attention kernels' even row stride)
     dropout_mask_kernel<<<(int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048), 256, 0, (hipStream_t)stream>>>(mask, (size_t)B * H * Tq, Tk, drop_seed, drop_thr16(drop_p));
     ASR_CHECK_LAUNCH("asr_sdpa_dropout_mask");
     return ASR_OK;

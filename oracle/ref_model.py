@@ -15,10 +15,22 @@ What it restates (file:line are into the reference, zqs01/ASR_chinese_e2e):
   * clip_grad_norm_(5.0) + NoamOpt + Adam           transformer_official.py:100-103,
                                                     Trainer/optimizer.py:15-28, main.py:81-83
   * CER string convention                           Predictor/Utils/score.py:4-13, vocab.py:75-79
+  * dropout (given masks, `drop`)                   transformer_official.py:175-177, 306-307; attention.py:59, 83;
+                                                    module.py:73
 It is written over a plain {name: tensor} state dict with the reference's own state_dict keys,
 so reference weights (tests/golden/*.npz, made by oracle/gen_golden.py) load directly.
 
 Pinned by: tests/test_oracle_golden.py against vectors produced by the reference itself.
+
+Dropout: the oracle draws no random numbers.  `drop` (optional, every forward entry point) maps a named site to the multiplicative
+mask (keep / (1 - p), or 0) applied there, in the oracle's layout: (B, T, d) for activations, (B, H, Tq, Tk) for attention
+probabilities.  The sites (dropout_sites) are the reference's five kinds of nn.Dropout, named after the module that owns them:
+  "encoder.input"                  dropout(LN(linear_in(x)) + PE)        transformer_official.py:175-177
+  "decoder.input"                  dropout(emb(ys_in) * d^-0.5 + PE)     transformer_official.py:306-307
+  "<attention prefix>attn"         on softmax(QK^T), before @ V          attention.py:83
+  "<attention prefix>fc"           on fc(ctx), before the residual       attention.py:59
+  "<feed-forward prefix>w_2"       on w_2(relu(w_1 x)), before residual  module.py:73
+with drop=None nothing is applied (the p = 0 step, bit for bit); a mapping that lacks a site the step reaches raises.
 
 Not in the reference (BASELINE.json north_star asks for it): a CTC head `ctc_lo` on the encoder
 output and the joint loss  lambda*CTC + (1-lambda)*CE.  Its oracle is torch's own
@@ -46,6 +58,32 @@ def default_cfg(**over):
 
 
 # ----------------------------------------------------------------------------- building blocks
+def dropout_sites(cfg):
+    """Names of every dropout site a training step of `cfg` reaches, in forward order."""
+    sites = ["encoder.input"]
+    for i in range(cfg.layer_num):
+        pre = f"encoder.layer_stack.{i}."
+        sites += [pre + "slf_attn.attn", pre + "slf_attn.fc", pre + "pos_ffn.w_2"]
+    if cfg.use_decoder:
+        sites.append("decoder.input")
+        for i in range(cfg.layer_num):
+            pre = f"decoder.layer_stack.{i}."
+            sites += [pre + "slf_attn.attn", pre + "slf_attn.fc", pre + "enc_attn.attn", pre + "enc_attn.fc", pre + "pos_ffn.w_2"]
+    return sites
+
+
+def apply_dropout(drop, site, x):
+    """x * drop[site]; x itself when drop is None.  A missing site or a mask of the wrong shape raises: no site is skipped silently."""
+    if drop is None:
+        return x
+    if site not in drop:
+        raise KeyError(f"dropout mask of site {site!r} missing")
+    m = torch.as_tensor(drop[site]).to(x.dtype)
+    if tuple(m.shape) != tuple(x.shape):
+        raise ValueError(f"dropout mask of site {site!r}: shape {tuple(m.shape)}, activation {tuple(x.shape)}")
+    return x * m
+
+
 def positional_encoding(length, d_model, dtype=torch.float32):
     """module.py:16-24.  pe[p, 2i] = sin(p * w_i), pe[p, 2i+1] = cos(p * w_i)."""
     pos = torch.arange(0, length).unsqueeze(1).float()
@@ -67,8 +105,8 @@ def valid_mask(lengths, T, loop=False):
     return torch.arange(T).unsqueeze(0) < lengths.view(-1, 1)
 
 
-def multi_head_attention(sd, pre, q_in, kv_in, masked, n_head, d_k):
-    """attention.py:33-62.  `masked` is (B, Lq, Lk) bool, True = excluded (score -> -inf)."""
+def multi_head_attention(sd, pre, q_in, kv_in, masked, n_head, d_k, drop=None):
+    """attention.py:33-62.  `masked` is (B, Lq, Lk) bool, True = excluded (score -> -inf).  drop: sites pre + "attn", pre + "fc"."""
     B, Lq, _ = q_in.shape
     Lk = kv_in.shape[1]
     q = F.linear(q_in, sd[pre + "w_qs.weight"], sd[pre + "w_qs.bias"]).view(B, Lq, n_head, d_k)
@@ -81,21 +119,23 @@ def multi_head_attention(sd, pre, q_in, kv_in, masked, n_head, d_k):
     dead = masked.all(dim=-1, keepdim=True)                              # (B, Lq, 1)
     s = s.masked_fill((masked & ~dead).unsqueeze(1), float("-inf"))      # attention.py:80
     p = torch.softmax(s, dim=-1) * (~dead).unsqueeze(1).to(s.dtype)
+    p = apply_dropout(drop, pre + "attn", p)                             # attention.py:83
     ctx = torch.einsum("bhqk,bkhd->bqhd", p, v).reshape(B, Lq, n_head * d_k)
-    out = F.linear(ctx, sd[pre + "fc.weight"], sd[pre + "fc.bias"])
+    out = apply_dropout(drop, pre + "fc", F.linear(ctx, sd[pre + "fc.weight"], sd[pre + "fc.bias"]))     # attention.py:59
     d = q_in.shape[-1]
     return F.layer_norm(out + q_in, (d,), sd[pre + "layer_norm.weight"], sd[pre + "layer_norm.bias"], LN_EPS)
 
 
-def feed_forward(sd, pre, x):
-    """module.py:68-75.  Conv1d(k=1) weights are (out, in, 1): squeeze -> Linear."""
+def feed_forward(sd, pre, x, drop=None):
+    """module.py:68-75.  Conv1d(k=1) weights are (out, in, 1): squeeze -> Linear.  drop: site pre + "w_2" (module.py:73)."""
     w1, w2 = sd[pre + "w_1.weight"].squeeze(-1), sd[pre + "w_2.weight"].squeeze(-1)
     h = F.linear(F.relu(F.linear(x, w1, sd[pre + "w_1.bias"])), w2, sd[pre + "w_2.bias"])
+    h = apply_dropout(drop, pre + "w_2", h)
     d = x.shape[-1]
     return F.layer_norm(h + x, (d,), sd[pre + "layer_norm.weight"], sd[pre + "layer_norm.bias"], LN_EPS)
 
 
-def encoder_forward(sd, cfg, wave, wave_len, loop_masks=False):
+def encoder_forward(sd, cfg, wave, wave_len, loop_masks=False, drop=None):
     """transformer_official.py:158-189."""
     B, T, _ = wave.shape
     keep = valid_mask(wave_len, T, loop_masks)                           # (B,T)
@@ -109,10 +149,11 @@ def encoder_forward(sd, cfg, wave, wave_len, loop_masks=False):
     x = F.linear(wave, sd["encoder.linear_in.weight"], sd["encoder.linear_in.bias"])
     x = F.layer_norm(x, (d,), sd["encoder.layer_norm_in.weight"], sd["encoder.layer_norm_in.bias"], LN_EPS)
     x = x + positional_encoding(T, d, wave.dtype).unsqueeze(0)           # :175-177 (no pad zeroing here)
+    x = apply_dropout(drop, "encoder.input", x)
     for i in range(cfg.layer_num):
         pre = f"encoder.layer_stack.{i}."
-        x = multi_head_attention(sd, pre + "slf_attn.", x, x, masked, cfg.num_head, cfg.hidden_size) * non_pad
-        x = feed_forward(sd, pre + "pos_ffn.", x) * non_pad
+        x = multi_head_attention(sd, pre + "slf_attn.", x, x, masked, cfg.num_head, cfg.hidden_size, drop) * non_pad
+        x = feed_forward(sd, pre + "pos_ffn.", x, drop) * non_pad
     return x
 
 
@@ -131,7 +172,7 @@ def decoder_preprocess(tgt):
     return ys_in, ys_out
 
 
-def decoder_forward(sd, cfg, tgt, enc_out, cross_len, loop_masks=False):
+def decoder_forward(sd, cfg, tgt, enc_out, cross_len, loop_masks=False, drop=None):
     """transformer_official.py:277-328.  `cross_len` is what the reference passes as
     encoder_input_lengths: the TEXT lengths (quirk, :78) - or wave_len for the corrected mask."""
     ys_in, ys_out = decoder_preprocess(tgt)
@@ -144,11 +185,12 @@ def decoder_forward(sd, cfg, tgt, enc_out, cross_len, loop_masks=False):
     cross_masked = (~valid_mask(cross_len, Ti, loop_masks)).unsqueeze(1).expand(B, To, Ti)  # :301-303
     emb = sd["decoder.tgt_word_emb.weight"]
     x = emb[ys_in] * (d ** -0.5) + positional_encoding(To, d, enc_out.dtype).unsqueeze(0)   # :306-307
+    x = apply_dropout(drop, "decoder.input", x)
     for i in range(cfg.layer_num):
         pre = f"decoder.layer_stack.{i}."
-        x = multi_head_attention(sd, pre + "slf_attn.", x, x, self_masked, cfg.num_head, cfg.hidden_size) * non_pad
-        x = multi_head_attention(sd, pre + "enc_attn.", x, enc_out, cross_masked, cfg.num_head, cfg.hidden_size) * non_pad
-        x = feed_forward(sd, pre + "pos_ffn.", x) * non_pad
+        x = multi_head_attention(sd, pre + "slf_attn.", x, x, self_masked, cfg.num_head, cfg.hidden_size, drop) * non_pad
+        x = multi_head_attention(sd, pre + "enc_attn.", x, enc_out, cross_masked, cfg.num_head, cfg.hidden_size, drop) * non_pad
+        x = feed_forward(sd, pre + "pos_ffn.", x, drop) * non_pad
     pred = F.linear(x, emb)                                              # :321 tied, no bias, no scaling
     return pred, ys_out
 
@@ -231,17 +273,17 @@ def ctc_loss(logits, in_len, labels, lab_len, zero_infinity=False):
     return total / logits.shape[0]
 
 
-def forward_losses(sd, cfg, batch, loop_masks=False):
+def forward_losses(sd, cfg, batch, loop_masks=False, drop=None):
     """TransformerOffical.forward + cal_performance (+ the added CTC branch).
-    batch: dict(wave, wave_len, tgt_for_input, tgt_len).  Returns dict of tensors."""
+    batch: dict(wave, wave_len, tgt_for_input, tgt_len); drop: {site: mask} (dropout_sites) or None.  Returns dict of tensors."""
     out = {}
-    enc = encoder_forward(sd, cfg, batch["wave"], batch["wave_len"], loop_masks)
+    enc = encoder_forward(sd, cfg, batch["wave"], batch["wave_len"], loop_masks, drop)
     out["enc_out"] = enc
     loss = 0.0
     lam = float(cfg.ctc_weight)
     if cfg.use_decoder:
         cross_len = batch["tgt_len"] if cfg.cross_mask == "ref_compat" else batch["wave_len"]
-        pred, gold = decoder_forward(sd, cfg, batch["tgt_for_input"], enc, cross_len, loop_masks)
+        pred, gold = decoder_forward(sd, cfg, batch["tgt_for_input"], enc, cross_len, loop_masks, drop)
         out["pred"], out["gold"] = pred, gold
         out["ce"] = ce_loss(pred, gold)
         loss = (1.0 - lam) * out["ce"] if lam > 0 else out["ce"]
@@ -360,19 +402,19 @@ class RefTrainer:
         self.id2token = id2token
         self.last = {}
 
-    def loss_and_grads(self, batch, loop_masks=False):
+    def loss_and_grads(self, batch, loop_masks=False, drop=None):
         leaves = {k: self.sd[k].detach().clone().requires_grad_(True) for k in self.trainable}
         sd = dict(self.sd)
         sd.update(leaves)
         if "decoder.tgt_word_emb.weight" in leaves:
             sd["decoder.tgt_word_prj.weight"] = leaves["decoder.tgt_word_emb.weight"]
-        out = forward_losses(sd, self.cfg, batch, loop_masks)
+        out = forward_losses(sd, self.cfg, batch, loop_masks, drop)
         grads = torch.autograd.grad(out["loss"], [leaves[k] for k in self.trainable], allow_unused=True)
         grads = {k: (g if g is not None else torch.zeros_like(leaves[k])) for k, g in zip(self.trainable, grads)}
         return out, grads
 
-    def iterate(self, batch, loop_masks=False, with_cer=False):
-        out, grads = self.loss_and_grads(batch, loop_masks)
+    def iterate(self, batch, loop_masks=False, with_cer=False, drop=None):
+        out, grads = self.loss_and_grads(batch, loop_masks, drop)
         assert not torch.isinf(out["loss"])                               # transformer_official.py:88
         cer = None
         if with_cer and self.id2token is not None and "pred" in out:

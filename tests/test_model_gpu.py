@@ -712,9 +712,10 @@ def test_w1_gradient_cosine_recovers_without_relu_flips():
     keep = {}
     orig_ff = R.feed_forward
 
-    def ff_capture(sd_, pre, x):
+    def ff_capture(sd_, pre, x, drop=None):
         if pre != "encoder.layer_stack.0.pos_ffn.":
-            return orig_ff(sd_, pre, x)
+            return orig_ff(sd_, pre, x, drop)
+        assert drop is None
         import torch.nn.functional as F
         w1, w2 = sd_[pre + "w_1.weight"].squeeze(-1), sd_[pre + "w_2.weight"].squeeze(-1)
         hp = F.linear(x, w1, sd_[pre + "w_1.bias"])
