@@ -15,7 +15,9 @@ Additions required by BASELINE.json's north_star (not in the reference):
   * config.cross_mask: "ref_compat" reproduces the reference's decoder cross-attention mask built
     from TEXT lengths (transformer_official.py:78, 301-303); "wave_len" is the corrected mask,
   * config.dtype: "bf16" (default) or "fp32" (exact-fp32 parity mode),
-  * config.attn_window: +-w frame band on encoder self-attention (long-form config), -1 = full.
+  * config.attn_window: +-w frame band on encoder self-attention (long-form config), -1 = full,
+  * config.chunk_size / left_chunks / decoding_chunk_size / decoding_left_chunks: chunk-masked encoder self-attention for
+    streaming (WeNet U2's subsequent_chunk_mask; encoder_mask() below), and model.stream() (stream.py).
 """
 import math
 
@@ -59,6 +61,18 @@ class _SpeechTransformer(BaseModel):
         self.cross_mask = getattr(c, "cross_mask", "ref_compat")
         self.lowp = str(getattr(c, "dtype", "bf16")).lower() in ("bf16", "bfloat16")
         self.attn_window = int(getattr(c, "attn_window", -1))
+        self.chunk_size = int(getattr(c, "chunk_size", 0))
+        self.left_chunks = int(getattr(c, "left_chunks", -1))
+        dcs, dlc = getattr(c, "decoding_chunk_size", None), getattr(c, "decoding_left_chunks", None)
+        static = self.chunk_size > 0
+        self.decoding_chunk_size = int(dcs) if dcs is not None else (self.chunk_size if static else 0)
+        self.decoding_left_chunks = int(dlc) if dlc is not None else (self.left_chunks if static else -1)
+        if self.chunk_size < -1 or self.left_chunks < -1 or self.decoding_chunk_size < 0 or self.decoding_left_chunks < -1:
+            raise ValueError(f"bad chunk configuration: chunk_size={self.chunk_size} left_chunks={self.left_chunks} "
+                             f"decoding_chunk_size={self.decoding_chunk_size} decoding_left_chunks={self.decoding_left_chunks}")
+        if (self.chunk_size != 0 or self.decoding_chunk_size > 0) and self.attn_window >= 0:
+            raise ValueError("a chunk mask (chunk_size / decoding_chunk_size) and attn_window are mutually exclusive")
+        self._enc_given = None      # (enc, B, T): an encoder output the inference paths take instead of running the encoder (stream.py)
         self.label_smoothing = float(getattr(c, "label_smoothing", 0.0))   # Utils/loss.py:30-45 (the reference never enables it)
         self.cer_in_iterate = bool(getattr(c, "cer_in_iterate", True))
         self._step_seed = int(getattr(c, "seed", 0))   # advanced once per training step (dropout masks)
@@ -266,12 +280,67 @@ class _SpeechTransformer(BaseModel):
                 return b
         return t.to(torch.int32)
 
+    # ------------------------------------------------------------------ encoder mask (every encoder_fwd caller goes through here)
+    DYN_CHUNK_MAX = 25      # dynamic chunk training: C uniform in [1, 25] (WeNet's dynamic-chunk recipe), full attention half the time
+
+    @staticmethod
+    def dynamic_chunk(step):
+        """chunk_size = -1: the chunk of training step `step` (0 = full attention) - a pure function of the step counter, so it is the
+        same on every data-parallel rank and on a replay."""
+        x = (int(step) * 0x9E3779B1 + 0x7F4A7C15) & 0xFFFFFFFF      # integer hash (murmur3 finaliser)
+        x ^= x >> 16
+        x = (x * 0x85EBCA6B) & 0xFFFFFFFF
+        x ^= x >> 13
+        x = (x * 0xC2B2AE35) & 0xFFFFFFFF
+        x ^= x >> 16
+        return 0 if (x & 1) == 0 else 1 + (x >> 1) % _SpeechTransformer.DYN_CHUNK_MAX
+
+    def encoder_mask(self, training=False):
+        """(chunk, left_chunks) of the encoder's self-attention: the training mask (chunk_size; -1 = this step's dynamic_chunk) or the
+        decoding mask of every inference path.  (0, -1) = full attention (or the attn_window band)."""
+        if training:
+            C = self.dynamic_chunk(self._step_seed) if self.chunk_size == -1 else self.chunk_size
+            return (C, self.left_chunks) if C > 0 else (0, -1)
+        return (self.decoding_chunk_size, self.decoding_left_chunks) if self.decoding_chunk_size > 0 else (0, -1)
+
+    def encode(self, eng, x, wave_len, training=False):
+        """Engine.encoder_fwd under encoder_mask(training): (enc (B*T, d), cache).  Inside given_encoder_output() the inference paths get
+        that output instead (cache None)."""
+        if self._enc_given is not None and not training:
+            enc, B, T = self._enc_given
+            if x.shape[0] != B or x.shape[1] != T:
+                raise ValueError(f"the given encoder output is for (B, T) = ({B}, {T}), the batch has {tuple(x.shape[:2])}")
+            return enc, None
+        chunk, left = self.encoder_mask(training)
+        return eng.encoder_fwd(x, wave_len, self.attn_window, chunk, left)
+
+    def given_encoder_output(self, enc):
+        """Context manager: the searches (forward, ctc_greedy_search, ctc_prefix_beam_search, beam_search, transcribe) use `enc`
+        ((B, T, d) in the model's dtype) as the encoder output of a batch of the same (B, T) instead of running the encoder."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            B, T = enc.shape[0], enc.shape[1]
+            prev, self._enc_given = self._enc_given, (enc.reshape(B * T, -1).contiguous(), B, T)
+            try:
+                yield self
+            finally:
+                self._enc_given = prev
+        return ctx()
+
+    def stream(self, batch_size):
+        """A streaming encoder for `batch_size` utterances (stream.StreamingEncoder): push chunks of encoder-rate features, get the
+        greedy CTC ids each chunk adds; finish() gives transcribe()'s result for the same decoding chunk mask."""
+        from ..stream import StreamingEncoder
+        return StreamingEncoder(self, batch_size)
+
     def forward(self, input):
         """transformer_official.py:68-81 (inference-style forward; no gradients).  A batch without a transcript (only wave / wave_len)
         gets the encoder output and the CTC logits; pred / gold need tgt_for_input."""
         eng, x, wave_len, prep = self._prepare(input)
         B, T, _ = x.shape
-        enc, _ = eng.encoder_fwd(x, wave_len, self.attn_window)
+        enc, _ = self.encode(eng, x, wave_len)
         pack = Pack()
         pack.add(encoder_out=enc.view(B, T, -1))
         if self.use_decoder and prep is not None:      # teacher forcing needs the transcript
@@ -532,7 +601,7 @@ class _SpeechTransformer(BaseModel):
         pending = count_hook(n_valid, B) if count_hook is not None else None
         zero, self._zero_lazy = (self._flat.g if getattr(self, "_zero_lazy", False) else None), False
         eng.refresh_transposes(zero=zero)      # W^T copies for this step's input-gradient GEMMs (side stream, beside the forward pass)
-        enc, ecache = eng.encoder_fwd(x, wave_len, self.attn_window)
+        enc, ecache = self.encode(eng, x, wave_len, training=True)
         batch_div = None
         if pending is not None:
             n_valid, batch_div = pending.wait()
@@ -622,6 +691,10 @@ class _SpeechTransformer(BaseModel):
             cross_mask = "ref_compat"
             dtype = "bf16"
             attn_window = -1
+            chunk_size = 0                  # encoder chunk mask in training: 0 = full, > 0 = static chunk, -1 = dynamic (encoder_mask)
+            left_chunks = -1                # chunks of left context, -1 = all
+            decoding_chunk_size = None      # inference mask: None = chunk_size when static, else full; 0 = full
+            decoding_left_chunks = None     # None = left_chunks when the chunk is static, else -1
 
         return ModelConfig
 

@@ -79,6 +79,9 @@ SIGNATURES = {
     "asr_sdpa_fwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, F, U, P, I, P]),
     "asr_sdpa_bwd_workspace_bytes": (Z, [I, I, I, I, I, I, I, I]),
     "asr_sdpa_bwd": (I, [P, P, P, P, P, P, P, Z, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, F, U, P, I, P]),
+    "asr_sdpa_chunk_fwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, F, U, P, I, P]),
+    "asr_sdpa_chunk_bwd_workspace_bytes": (Z, [I, I, I, I, I, I, I, I]),
+    "asr_sdpa_chunk_bwd": (I, [P, P, P, P, P, P, P, Z, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, F, U, P, I, P]),
     "asr_dropout_mask": (I, [P, I, I, F, U, P]),
     "asr_sdpa_dropout_mask": (I, [P, I, I, I, I, F, U, P]),
     "asr_ctc_workspace_bytes": (Z, [I, I, I]),

@@ -35,6 +35,24 @@ __device__ __forceinline__ bool visible(int qi, int kj, int klen, int causal, in
     if (window >= 0) ok = ok && (kj - qi <= window) && (qi - kj <= window);
     return ok;
 }
+// Chunk mask (the CHUNK instantiations; their causal / window arguments carry the chunk size C >= 1 and the left context
+// left >= -1 in chunks, both clamped by the host so that nothing below overflows): query qi sees keys [chunk_lo, chunk_hi) below klen.
+// Both bounds are non-decreasing in qi, so a query RANGE [qa, qb] sees at most [chunk_lo(qa), chunk_hi(qb)) and at least
+// [chunk_lo(qb), chunk_hi(qa)): the tile-skip and edge tests below use the two.
+__device__ __forceinline__ int chunk_lo(int qi, int C, int left) { return left < 0 ? 0 : max(0, (qi / C - left) * C); }
+__device__ __forceinline__ int chunk_hi(int qi, int C) { return (qi / C + 1) * C; }
+// ... and, the other way round, key kj is seen by the queries [chunk_qlo, chunk_qhi): (kj / C) C <= i < (kj / C + left + 1) C
+__device__ __forceinline__ int chunk_qlo(int kj, int C) { return (kj / C) * C; }
+__device__ __forceinline__ int chunk_qhi(int qlo, int C, int left) { return left < 0 ? 0x7fffffff : qlo + (left + 1) * C; }
+template <bool CHUNK>
+__device__ __forceinline__ bool visible_m(int qi, int kj, int klen, int a, int b) {
+    if constexpr (CHUNK) return kj < klen && kj < chunk_hi(qi, a) && kj >= chunk_lo(qi, a, b);
+    else return visible(qi, kj, klen, a, b);
+}
+// lse of a query that sees no key: -inf for the causal / band masks (as before), 0 under a chunk mask (finite; its O is 0 and it adds
+// nothing to dK / dV, as every one of its scores is masked)
+template <bool CHUNK>
+__device__ __forceinline__ float lse_none() { return CHUNK ? 0.f : -INFINITY; }
 
 // ------------------------------------------------------------------------------------------
 // bf16 MFMA path
@@ -159,7 +177,7 @@ __device__ __forceinline__ void store_rows_T_lo(const f32x16 (&acc)[2], float mu
 }
 
 // ---------------------------------------------------------------- forward
-template <bool DROP>
+template <bool DROP, bool CHUNK = false>
 __global__ __launch_bounds__(256, 2) void sdpa_fwd_bf16_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                             bf16_t* __restrict__ o, float* __restrict__ lse, const int32_t* __restrict__ k_len, int H,
                                                             int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int causal, int window, float scale,
@@ -177,8 +195,13 @@ __global__ __launch_bounds__(256, 2) void sdpa_fwd_bf16_kernel(const bf16_t* __r
     const bf16_t* vb = v + (size_t)b * Tk * ldv + h * DK;
     const int klen = min(k_len ? k_len[b] : Tk, Tk);
     int kend = klen, kbeg = 0;
+    if constexpr (CHUNK) {
+        kend = min(kend, chunk_hi(min(qblk + 127, Tq - 1), causal));
+        kbeg = chunk_lo(qblk, causal, window) & ~63;
+    } else {
     if (causal) kend = min(kend, min(qblk + 128, Tq));
     if (window >= 0) { kend = min(kend, min(qblk + 128, Tq) + window); kbeg = max(0, qblk - window) & ~63; }
+    }
     bf16x8 qf[4];
     frags_from_global(qf, qb, ldq, q0, Tq, lane);
     const int qi = q0 + (lane & 31);
@@ -207,10 +230,11 @@ __global__ __launch_bounds__(256, 2) void sdpa_fwd_bf16_kernel(const bf16_t* __r
         // the per-element work is kept to max / fma / exp2 / add: tiles that lie wholly inside every
         // mask skip the visibility test (wave-uniform branch), the 1/sqrt(dk)*log2(e) scale is folded
         // into one fma with the running maximum, and exp2 is the bare v_exp_f32.
-        const bool need_mask = (k0 + TILE > klen) || (causal && k0 + TILE - 1 > q0) ||
-                               (window >= 0 && (k0 + TILE - 1 - q0 > window || q0 + 31 - k0 > window));
+        const bool need_mask = CHUNK ? (k0 + TILE > klen) || k0 + TILE > chunk_hi(q0, causal) || k0 < chunk_lo(q0 + 31, causal, window)
+                                     : (k0 + TILE > klen) || (causal && k0 + TILE - 1 > q0) ||
+                                       (window >= 0 && (k0 + TILE - 1 - q0 > window || q0 + 31 - k0 > window));
         if (need_mask) {
-            if (!causal && window < 0) {   // key-length mask only (encoder self-attention): one compare per element
+            if (!CHUNK && !causal && window < 0) {   // key-length mask only (encoder self-attention): one compare per element
                 const int lim = klen - k0 - 4 * (lane >> 5);      // key (32*sub + (i&3) + 8*(i>>2)) + 4*hh + k0 < klen
 #pragma unroll
                 for (int sub = 0; sub < 2; ++sub)
@@ -223,7 +247,7 @@ __global__ __launch_bounds__(256, 2) void sdpa_fwd_bf16_kernel(const bf16_t* __r
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         const int kj = k0 + 32 * sub + acc_row(i, lane);
-                        if (!visible(qi, kj, klen, causal, window)) st[sub][i] = -INFINITY;
+                        if (!visible_m<CHUNK>(qi, kj, klen, causal, window)) st[sub][i] = -INFINITY;
                     }
             }
         }
@@ -274,7 +298,7 @@ __global__ __launch_bounds__(256, 2) void sdpa_fwd_bf16_kernel(const bf16_t* __r
     const float inv = l > 0.f ? 1.f / l : 0.f;
     store_rows_T(oacc, inv, o + (size_t)b * Tq * ldo + h * DK, ldo, q0, Tq, lane);
     if (o_lo) store_rows_T_lo(oacc, inv, o_lo + (size_t)b * Tq * ldo + h * DK, ldo, q0, Tq, lane);
-    if (lane < 32 && qi < Tq) lse[((size_t)b * H + h) * Tq + qi] = l > 0.f ? (m * sc2 + log2f(l)) * LN2 : -INFINITY;
+    if (lane < 32 && qi < Tq) lse[((size_t)b * H + h) * Tq + qi] = l > 0.f ? (m * sc2 + log2f(l)) * LN2 : lse_none<CHUNK>();
 }
 
 // delta[b,h,q] = sum_d dO * O   (one wave per 8 rows x 8 lanes... simple: one thread-group of 8 lanes per (row, head))
@@ -300,7 +324,7 @@ __global__ __launch_bounds__(256) void sdpa_delta_kernel(const T* __restrict__ o
 }
 
 // ---------------------------------------------------------------- backward: dQ
-template <bool DROP>
+template <bool DROP, bool CHUNK = false>
 __global__ __launch_bounds__(256, 3) void sdpa_bwd_dq_bf16_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                                const bf16_t* __restrict__ d_o, const bf16_t* __restrict__ o, const bf16_t* __restrict__ o_lo, const float* __restrict__ lse,
                                                                float* __restrict__ delta, bf16_t* __restrict__ dq, const int32_t* __restrict__ k_len, int H, int Tq, int Tk, int ldq,
@@ -318,8 +342,13 @@ __global__ __launch_bounds__(256, 3) void sdpa_bwd_dq_bf16_kernel(const bf16_t* 
     const bf16_t* vb = v + (size_t)b * Tk * ldv + h * DK;
     const int klen = min(k_len ? k_len[b] : Tk, Tk);
     int kend = klen, kbeg = 0;
+    if constexpr (CHUNK) {
+        kend = min(kend, chunk_hi(min(qblk + 127, Tq - 1), causal));
+        kbeg = chunk_lo(qblk, causal, window) & ~63;
+    } else {
     if (causal) kend = min(kend, min(qblk + 128, Tq));
     if (window >= 0) { kend = min(kend, min(qblk + 128, Tq) + window); kbeg = max(0, qblk - window) & ~63; }
+    }
     bf16x8 qf[4], dof[4];
     frags_from_global(qf, qb, ldq, q0, Tq, lane);
     frags_from_global(dof, dob, ldo, q0, Tq, lane);
@@ -372,9 +401,10 @@ __global__ __launch_bounds__(256, 3) void sdpa_bwd_dq_bf16_kernel(const bf16_t* 
                 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row(Vt, 32 * sub, ks, lane), dof[ks], dp, 0, 0, 0);
             }
             const int ks0 = k0 + 32 * sub;
-            const bool need_mask = (ks0 + 32 > klen) || (causal && ks0 + 31 > q0) || (window >= 0 && (ks0 + 31 - q0 > window || q0 + 31 - ks0 > window));
+            const bool need_mask = CHUNK ? (ks0 + 32 > klen) || ks0 + 32 > chunk_hi(q0, causal) || ks0 < chunk_lo(q0 + 31, causal, window)
+                                         : (ks0 + 32 > klen) || (causal && ks0 + 31 > q0) || (window >= 0 && (ks0 + 31 - q0 > window || q0 + 31 - ks0 > window));
             if (need_mask) {
-                if (!causal && window < 0) {   // key-length mask only
+                if (!CHUNK && !causal && window < 0) {   // key-length mask only
                     const int lim = klen - ks0 - 4 * (lane >> 5);
 #pragma unroll
                     for (int i = 0; i < 16; ++i)
@@ -382,7 +412,7 @@ __global__ __launch_bounds__(256, 3) void sdpa_bwd_dq_bf16_kernel(const bf16_t* 
                 } else {
 #pragma unroll
                     for (int i = 0; i < 16; ++i)
-                        if (!visible(qi, ks0 + acc_row(i, lane), klen, causal, window)) st[i] = -INFINITY;
+                        if (!visible_m<CHUNK>(qi, ks0 + acc_row(i, lane), klen, causal, window)) st[i] = -INFINITY;
                 }
             }
             if constexpr (DROP) {   // dP = (dO V^T) o keep / (1-p)
@@ -414,7 +444,7 @@ __global__ __launch_bounds__(256, 3) void sdpa_bwd_dq_bf16_kernel(const bf16_t* 
 // ---------------------------------------------------------------- backward: dK, dV
 // launch bound 2 waves/SIMD: without it the kernel takes 176 arch + 96 accumulator registers = 272
 // of the unified 512-entry file, i.e. ONE workgroup per CU (measured: 134 us, 2.8 waves/CU average)
-template <bool DROP>
+template <bool DROP, bool CHUNK = false>
 __global__ __launch_bounds__(256, 2) void sdpa_bwd_dkv_bf16_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                                 const bf16_t* __restrict__ d_o, const float* __restrict__ lse, const float* __restrict__ delta,
                                                                 bf16_t* __restrict__ dk_, bf16_t* __restrict__ dv, const int32_t* __restrict__ k_len, int H,
@@ -444,8 +474,13 @@ __global__ __launch_bounds__(256, 2) void sdpa_bwd_dkv_bf16_kernel(const bf16_t*
     for (int i = 0; i < 16; ++i) { dka[0][i] = dka[1][i] = dva[0][i] = dva[1][i] = 0.f; }
     // query range that can see this key block
     int qbeg = 0, qend = Tq;
+    if constexpr (CHUNK) {      // query i sees key j iff (j / C) C <= i < (j / C + left + 1) C  (left >= 0)
+        qbeg = (kblk / causal) * causal & ~63;
+        if (window >= 0) qend = min(Tq, (min(kblk + 127, Tk - 1) / causal + window + 1) * causal);
+    } else {
     if (causal) qbeg = kblk & ~63;
     if (window >= 0) { qbeg = max(qbeg, (kblk - window) & ~63); qbeg = max(qbeg, 0); qend = min(Tq, kblk + 128 + window); }
+    }
     if (kblk >= klen) qend = qbeg;  // whole key block is padding: gradients are zero
     const float* lseb = lse + ((size_t)b * H + h) * Tq;
     const float* delb = delta + ((size_t)b * H + h) * Tq;
@@ -479,9 +514,10 @@ __global__ __launch_bounds__(256, 2) void sdpa_bwd_dkv_bf16_kernel(const bf16_t*
             }
             f32x16 ds;
             const int qs0 = q0 + 32 * sub;   // wave-uniform: does this 32x32 sub-tile touch any mask edge?
-            const bool need_mask = (kk0 + 32 > klen) || (causal && kk0 + 31 > qs0) || (window >= 0 && (kk0 + 31 - qs0 > window || qs0 + 31 - kk0 > window));
+            const bool need_mask = CHUNK ? (kk0 + 32 > klen) || kk0 + 32 > chunk_hi(qs0, causal) || kk0 < chunk_lo(qs0 + 31, causal, window)
+                                         : (kk0 + 32 > klen) || (causal && kk0 + 31 > qs0) || (window >= 0 && (kk0 + 31 - qs0 > window || qs0 + 31 - kk0 > window));
             if (need_mask) {
-                if (!causal && window < 0) {   // key-length mask only: the key is this lane's, one test per tile
+                if (!CHUNK && !causal && window < 0) {   // key-length mask only: the key is this lane's, one test per tile
                     if (kj >= klen) {
 #pragma unroll
                         for (int i = 0; i < 16; ++i) st[i] = -INFINITY;
@@ -489,7 +525,7 @@ __global__ __launch_bounds__(256, 2) void sdpa_bwd_dkv_bf16_kernel(const bf16_t*
                 } else {
 #pragma unroll
                     for (int i = 0; i < 16; ++i)
-                        if (!visible(q0 + 32 * sub + acc_row(i, lane), kj, klen, causal, window)) st[i] = -INFINITY;
+                        if (!visible_m<CHUNK>(q0 + 32 * sub + acc_row(i, lane), kj, klen, causal, window)) st[i] = -INFINITY;
                 }
             }
 #pragma unroll
@@ -564,7 +600,7 @@ __device__ __forceinline__ void ff_wait_tiles(int younger) {      // at most `yo
     }
 }
 
-template <bool DROP, bool MASKED>
+template <bool DROP, bool MASKED, bool CHUNK = false>      // CHUNK: a chunk mask (MASKED too)
 __global__ __launch_bounds__(FF_THREADS, 2) void sdpa_fwd_fused_bf16_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                                          bf16_t* __restrict__ o, float* __restrict__ lse, const int32_t* __restrict__ k_len, int H,
                                                                          int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int causal, int window, float scale,
@@ -654,8 +690,14 @@ __global__ __launch_bounds__(FF_THREADS, 2) void sdpa_fwd_fused_bf16_kernel(cons
             float m = M_INIT, l = 0.f;
             int t0 = 0, t1 = ntile;
             if (MASKED) {
+                if constexpr (CHUNK) {      // key tiles wholly outside the block's chunk range: no LDS reads, no MFMA / softmax work
+                                            // (the DMA above still brings every key tile of the head into LDS, as for causal / band)
+                    t1 = min(t1, (chunk_hi(min(q0 + 31, Tq - 1), causal) + TILE - 1) / TILE);
+                    t0 = chunk_lo(q0, causal, window) / TILE;
+                } else {
                 if (causal) t1 = min(t1, (min(q0 + 32, Tq) + TILE - 1) / TILE);
                 if (window >= 0) { t1 = min(t1, (min(q0 + 32, Tq) + window + TILE - 1) / TILE); t0 = max(0, q0 - window) / TILE; }
+                }
                 if (!active) t1 = t0;
             }
             bf16x8 kf[2][4];
@@ -713,7 +755,8 @@ __global__ __launch_bounds__(FF_THREADS, 2) void sdpa_fwd_fused_bf16_kernel(cons
                 }
                 if (PREFETCH && !stream && t + 1 < t1) FF_LOAD_K(t + 1);
                 __builtin_amdgcn_sched_barrier(0);
-                const bool edge = (k0 + TILE > klen) || (MASKED && ((causal && k0 + TILE - 1 > q0) || (window >= 0 && (k0 + TILE - 1 - q0 > window || q0 + 31 - k0 > window))));
+                const bool edge = (k0 + TILE > klen) || (MASKED && (CHUNK ? k0 + TILE > chunk_hi(q0, causal) || k0 < chunk_lo(q0 + 31, causal, window)
+                                                                          : (causal && k0 + TILE - 1 > q0) || (window >= 0 && (k0 + TILE - 1 - q0 > window || q0 + 31 - k0 > window))));
                 if (edge) {
                     if (!MASKED) {      // key-length mask only: one compare per element
                         const int lim = klen - k0 - 4 * (lane >> 5);
@@ -722,12 +765,21 @@ __global__ __launch_bounds__(FF_THREADS, 2) void sdpa_fwd_fused_bf16_kernel(cons
 #pragma unroll
                             for (int i = 0; i < 16; ++i)
                                 if (32 * sub + (i & 3) + 8 * (i >> 2) >= lim) st[sub][i] = -INFINITY;
+                    } else if constexpr (CHUNK) {      // the lane's query sees keys [lo, hi): one division per lane, two compares per element
+                        const int lo = chunk_lo(qi, causal, window) - k0, hi = min(klen, chunk_hi(qi, causal)) - k0;
+#pragma unroll
+                        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+                            for (int i = 0; i < 16; ++i) {
+                                const int kr = 32 * sub + acc_row(i, lane);
+                                if (kr < lo || kr >= hi) st[sub][i] = -INFINITY;
+                            }
                     } else {
 #pragma unroll
                         for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
                             for (int i = 0; i < 16; ++i)
-                                if (!visible(qi, k0 + 32 * sub + acc_row(i, lane), klen, causal, window)) st[sub][i] = -INFINITY;
+                                if (!visible_m<CHUNK>(qi, k0 + 32 * sub + acc_row(i, lane), klen, causal, window)) st[sub][i] = -INFINITY;
                     }
                 }
                 // The loop is VALU-issue bound (dk = 64: 16 MFMAs against 32 softmax elements per lane), so the element work is
@@ -795,7 +847,7 @@ __global__ __launch_bounds__(FF_THREADS, 2) void sdpa_fwd_fused_bf16_kernel(cons
             else l = lacc[0];      // the contraction ran over all 64 keys of every tile: no cross-half add
             const float inv = l > 0.f ? 1.f / l : 0.f;
             store_rows_T(oacc, inv, ob, ldo, q0, Tq, lane);
-            if (lane < 32 && qi < Tq) lse[((size_t)b * H + h) * Tq + qi] = l > 0.f ? (m * sc2 + log2f(l)) * LN2 : -INFINITY;
+            if (lane < 32 && qi < Tq) lse[((size_t)b * H + h) * Tq + qi] = l > 0.f ? (m * sc2 + log2f(l)) * LN2 : lse_none<CHUNK>();
         }
     }
 }
@@ -1081,7 +1133,7 @@ __device__ __forceinline__ float row_sum_dpp(float v) {
     return v;
 }
 
-template <bool DROP, bool MASKED, bool BAND = false>
+template <bool DROP, bool MASKED, bool BAND = false, bool CHUNK = false>      // CHUNK: a chunk mask (MASKED too, not BAND)
 __global__ __launch_bounds__(FB_THREADS, 2) void sdpa_bwd_fused_bf16_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                                          const bf16_t* __restrict__ d_o, const bf16_t* __restrict__ o, const bf16_t* __restrict__ o_lo, const float* __restrict__ lse,
                                                                          bf16_t* __restrict__ dq, bf16_t* __restrict__ dk_, bf16_t* __restrict__ dv,
@@ -1104,7 +1156,7 @@ __global__ __launch_bounds__(FB_THREADS, 2) void sdpa_bwd_fused_bf16_kernel(cons
     float* s_neg = stats + 128;
     float* kbar = stats + 160;      // the head's mean key times scale * log2(e)
     // Short causal heads without dropout take delta from their own p and dP (phase_keys): exact, so neither remedy below is needed for them.
-    const bool own_delta = !DROP && MASKED && !BAND && Tk <= 64;
+    const bool own_delta = !DROP && MASKED && !BAND && !CHUNK && Tk <= 64;
     const bool centred = !BAND && !own_delta;      // the K image holds the keys minus their mean (workgroup-uniform)
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), hh = lane >> 5;
     const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
@@ -1140,7 +1192,7 @@ __global__ __launch_bounds__(FB_THREADS, 2) void sdpa_bwd_fused_bf16_kernel(cons
     for (int c = tid; c < 2 * FB_DS_BYTES / 16; c += FB_THREADS) *(u32x4*)((char*)dSimg + c * 16) = zero4;      // under the loads' latency
     if (tid < 32) s_neg[tid] = -1.0e30f;
     bf16_t* Vimg = (bf16_t*)(smem_fb + FB_LDS);      // short causal heads only (FB_VIMG_BYTES more LDS in that launch): V of the 64 keys, laid out as K's image
-    if constexpr (!DROP && MASKED && !BAND) {
+    if constexpr (!DROP && MASKED && !BAND && !CHUNK) {
         if (Tk <= 64) {
             const int row = tid >> 3, ch = tid & 7;
             const u32x4 raw = *(const u32x4*)(vb + (size_t)min(row, max(klen - 1, 0)) * ldv + ch * 8);
@@ -1247,12 +1299,14 @@ __global__ __launch_bounds__(FB_THREADS, 2) void sdpa_bwd_fused_bf16_kernel(cons
     auto phase_keys = [&](int t) {      // S, dP, P, dS, dV^T, dK^T of this wave's keys against query tile t; dS -> image t & 1
         const int buf = t & 1, qt0 = t * FB_QT;
         if (BAND && (kblk0 + kk0 > qt0 + FB_QT - 1 + window || kblk0 + kk0 + 63 < qt0 - window)) return;      // none of this wave's keys is in the tile's band
+        // CHUNK: none of this wave's keys is seen by the tile (phase_dq then reads the dS rows of the waves that ran only)
+        if (CHUNK && (kk0 >= min(klen, chunk_hi(min(qt0 + FB_QT - 1, Tq - 1), causal)) || kk0 + 64 <= chunk_lo(qt0, causal, window))) return;
         const bf16_t* Qt = tiles + buf * 2 * FB_TILE_ELEMS;
         const bf16_t* Dt = Qt + FB_TILE_ELEMS;
         const float* s_l = stats + buf * 64;
         const float* s_d = s_l + 32;
         bf16_t* dSw = dSimg + buf * (FB_DS_BYTES / 2);
-        if constexpr (!DROP && MASKED && !BAND) {
+        if constexpr (!DROP && MASKED && !BAND && !CHUNK) {
             // Short causal heads (the decoder's self-attention, Tk <= 64: this wave holds EVERY key of the head) take delta as
             // sum_j p_j dP_j / sum_j p_j from the p and dP of THIS kernel - what a softmax backward computes - instead of
             // rowsum(dO o O) from the rounded O.  The two are the same number in exact arithmetic; in bf16, where the rows of V are
@@ -1318,11 +1372,20 @@ __global__ __launch_bounds__(FB_THREADS, 2) void sdpa_bwd_fused_bf16_kernel(cons
             }
             if (MASKED) {
                 const int gk0 = kblk0 + key0;
-                const bool need = (causal && gk0 + 31 > qt0) || (window >= 0 && (gk0 + 31 - qt0 > window || qt0 + 31 - gk0 > window));
+                const bool need = CHUNK ? gk0 + 32 > chunk_hi(qt0, causal) || gk0 < chunk_lo(qt0 + 31, causal, window)
+                                        : (causal && gk0 + 31 > qt0) || (window >= 0 && (gk0 + 31 - qt0 > window || qt0 + 31 - gk0 > window));
                 if (need) {
+                    if constexpr (CHUNK) {      // the lane's key is seen by queries [qlo, qhi): one division per lane, two compares per element
+                        const int qlo = chunk_qlo(kj, causal), qhi = chunk_qhi(qlo, causal, window);
+                        const int lo = kj < klen_g ? qlo - qt0 : 0x7fffffff, hi = qhi == 0x7fffffff ? qhi : qhi - qt0;
+#pragma unroll
+                        for (int i = 0; i < 16; ++i)
+                            if (acc_row(i, lane) < lo || acc_row(i, lane) >= hi) st[i] = -1.0e30f;
+                    } else {
 #pragma unroll
                     for (int i = 0; i < 16; ++i)
-                        if (!visible(qt0 + acc_row(i, lane), kblk0 + kj, klen_g, causal, window)) st[i] = -1.0e30f;
+                        if (!visible_m<CHUNK>(qt0 + acc_row(i, lane), kblk0 + kj, klen_g, causal, window)) st[i] = -1.0e30f;
+                    }
                 }
             }
 #pragma unroll
@@ -1380,6 +1443,27 @@ __global__ __launch_bounds__(FB_THREADS, 2) void sdpa_bwd_fused_bf16_kernel(cons
         const int buf = t & 1, qt0 = t * FB_QT;
         f32x4_t acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
         const bf16_t* dSr = dSimg + buf * (FB_DS_BYTES / 2);
+        int s_lo = 0, s_hi = nks;
+        if constexpr (CHUNK) {      // the 32-key steps the tile sees, widened to whole waves = exactly the waves whose key phase ran
+            const int lo = chunk_lo(qt0, causal, window), hi = min(klen, chunk_hi(min(qt0 + FB_QT - 1, Tq - 1), causal));
+            s_lo = (lo >> 5) & ~1;
+            s_hi = hi > lo ? (hi + 31) >> 5 : s_lo;
+        }
+        if (CHUNK) {      // two 32-key steps (one wave's keys) per iteration: the full form's unrolled four cost a spill here
+            for (int s2 = s_lo; s2 < s_hi; s2 += 2) {
+                bf16x8 ka[2], da[2];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    ka[u] = fbs_tr(Kimg, 4096 * (s2 + u), fo.tr16);
+                    const bf16_t* pr = dSr + 32 * (s2 + u) * FB_QT;
+                    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(pr + ds_rd[0]));
+                    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(pr + ds_rd[1]));
+                    da[u] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                }
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[0], da[0], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[1], da[1], acc1, 0, 0, 0);
+            }
+        } else
         if (BAND) {      // only the waves that ran the key phase of this tile wrote dS rows: the product runs over their keys
             const int wv_lo = max(0, qt0 - window - kblk0) >> 6, wv_hi = min(min(qt0 + FB_QT - 1 + window, kblk0 + Tk - 1) - kblk0, FB_KEYS - 1) >> 6;
             for (int wv = wv_lo; wv <= wv_hi; ++wv) {
@@ -1396,7 +1480,7 @@ __global__ __launch_bounds__(FB_THREADS, 2) void sdpa_bwd_fused_bf16_kernel(cons
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[1], da[1], acc1, 0, 0, 0);
             }
         } else
-        for (int s4 = 0; s4 < nks; s4 += 4) {     // rows past the last key: K rows and dS rows are zeros
+        for (int s4 = s_lo; s4 < s_hi; s4 += 4) {     // rows past the last key: K rows and dS rows are zeros
             bf16x8 ka[4], da[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -1591,7 +1675,7 @@ __global__ __launch_bounds__(256) void sdpa_band_halo_kernel(const float* __rest
 // exact fp32 VALU path (any dk <= 128)
 // ------------------------------------------------------------------------------------------
 // one wave per (b, h, query): scores -> LDS, softmax, then lanes own output columns
-template <typename T>
+template <typename T, bool CHUNK = false>
 __global__ __launch_bounds__(64) void sdpa_fwd_generic_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ o,
                                                               float* __restrict__ lse, const int32_t* __restrict__ k_len, int H, int Tq, int Tk, int dk,
                                                               int ldq, int ldk, int ldv, int ldo, int causal, int window, float scale, uint32_t dseed,
@@ -1607,7 +1691,7 @@ __global__ __launch_bounds__(64) void sdpa_fwd_generic_kernel(const T* __restric
     float m = -INFINITY;
     for (int j = lane; j < Tk; j += 64) {
         float s = -INFINITY;
-        if (visible(qi, j, klen, causal, window)) {
+        if (visible_m<CHUNK>(qi, j, klen, causal, window)) {
             const T* kp = k + ((size_t)b * Tk + j) * ldk + (size_t)h * dk;
             float a = 0.f;
             for (int c = 0; c < dk; ++c) a += qrow[c] * to_f32<T>(kp[c]);
@@ -1640,11 +1724,11 @@ __global__ __launch_bounds__(64) void sdpa_fwd_generic_kernel(const T* __restric
         }
         op[c] = from_f32<T>(a * inv);
     }
-    if (lane == 0) lse[((size_t)b * H + h) * Tq + qi] = l > 0.f ? m + logf(l) : -INFINITY;
+    if (lane == 0) lse[((size_t)b * H + h) * Tq + qi] = l > 0.f ? m + logf(l) : lse_none<CHUNK>();
 }
 
 // dQ: one wave per (b,h,query)
-template <typename T>
+template <typename T, bool CHUNK = false>
 __global__ __launch_bounds__(64) void sdpa_bwd_dq_generic_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                                                  const T* __restrict__ d_o, const float* __restrict__ lse, const float* __restrict__ delta,
                                                                  T* __restrict__ dq, const int32_t* __restrict__ k_len, int H, int Tq, int Tk, int dk, int ldq,
@@ -1664,7 +1748,7 @@ __global__ __launch_bounds__(64) void sdpa_bwd_dq_generic_kernel(const T* __rest
     __syncthreads();
     for (int j = lane; j < Tk; j += 64) {
         float ds = 0.f;
-        if (visible(qi, j, klen, causal, window)) {
+        if (visible_m<CHUNK>(qi, j, klen, causal, window)) {
             const T* kp = k + ((size_t)b * Tk + j) * ldk + (size_t)h * dk;
             const T* vp = v + ((size_t)b * Tk + j) * ldv + (size_t)h * dk;
             float a = 0.f, dp = 0.f;
@@ -1687,7 +1771,7 @@ __global__ __launch_bounds__(64) void sdpa_bwd_dq_generic_kernel(const T* __rest
 }
 
 // dK, dV: one wave per (b,h,key)
-template <typename T>
+template <typename T, bool CHUNK = false>
 __global__ __launch_bounds__(64) void sdpa_bwd_dkv_generic_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                                                   const T* __restrict__ d_o, const float* __restrict__ lse, const float* __restrict__ delta,
                                                                   T* __restrict__ dk_, T* __restrict__ dv, const int32_t* __restrict__ k_len, int H, int Tq, int Tk,
@@ -1707,7 +1791,7 @@ __global__ __launch_bounds__(64) void sdpa_bwd_dkv_generic_kernel(const T* __res
     __syncthreads();
     for (int i = lane; i < Tq; i += 64) {
         float p = 0.f, ds = 0.f;
-        if (visible(i, kj, klen, causal, window)) {
+        if (visible_m<CHUNK>(i, kj, klen, causal, window)) {
             const T* qp = q + ((size_t)b * Tq + i) * ldq + (size_t)h * dk;
             const T* dop = d_o + ((size_t)b * Tq + i) * ldo + (size_t)h * dk;
             float a = 0.f, dp = 0.f;
@@ -1899,5 +1983,134 @@ extern "C" int asr_sdpa_bwd(const void* q, const void* k, const void* v, const v
         }
     }
     ASR_CHECK_LAUNCH("asr_sdpa_bwd");
+    return ASR_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// chunk-masked attention (streaming encoders): the CHUNK instantiations of the kernels above, the causal / window arguments
+// carrying (C, left): key length, chunk upper bound and (left >= 0) chunk lower bound.
+// ------------------------------------------------------------------------------------------
+static int chunk_check(const char* name, int chunk, int left_chunks) {
+    if (chunk < 1 || left_chunks < -1) ASR_FAIL(ASR_EINVAL, "%s: bad chunk mask chunk=%d left_chunks=%d (need chunk >= 1, left_chunks >= -1)", name, chunk, left_chunks);
+    return ASR_OK;
+}
+// clamp (C, left) to the shape: the same mask, and no overflow in the kernels' range arithmetic
+static void chunk_clamp(int Tq, int Tk, int& chunk, int& left) {
+    const int tmax = Tq > Tk ? Tq : Tk;
+    if (chunk > tmax) chunk = tmax;
+    const int nq = (Tq - 1) / chunk;      // last query chunk
+    if (left > nq) left = -1;             // every query sees back to key 0
+}
+
+extern "C" int asr_sdpa_chunk_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* k_len, int B, int H, int Tq, int Tk, int dk,
+                                  int ldq, int ldk, int ldv, int ldo, int chunk, int left_chunks, float scale, float drop_p, uint32_t dseed, void* o_lo,
+                                  int dtype, void* stream) {
+    if (int rc = chunk_check("asr_sdpa_chunk_fwd", chunk, left_chunks)) return rc;
+    if (!q || !k || !v || !o || !lse) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: null pointer");
+    if (o_lo && (dtype != ASR_BF16 || ((uintptr_t)o_lo % 16) != 0)) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: o_lo is the low-order piece of a bf16 output (16-byte aligned, the layout of o)");
+    if (int rc = check_common("asr_sdpa_chunk_fwd", B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo)) return rc;
+    if (drop_p < 0.f || drop_p >= 1.f) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: bad dropout p=%f", drop_p);
+    if ((double)B * H * Tq * (Tk + 1) >= 4294967296.0) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: B*H*Tq*Tk exceeds the 32-bit dropout counter");
+    int C = chunk, left = left_chunks;
+    chunk_clamp(Tq, Tk, C, left);
+    const uint32_t dthr = drop_thr16(drop_p);
+    const float dscale = 1.f / (1.f - drop_p);
+    hipStream_t st = (hipStream_t)stream;
+    const bool mfma = dtype == ASR_BF16 && mfma_ok(dk, ldq, ldk, ldv, ldo, q, k, v, o);
+    if (mfma && Tk <= FF_KEYS) {
+        static bool attr = false;
+        if (!attr) {
+            (void)hipFuncSetAttribute((const void*)sdpa_fwd_fused_bf16_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
+            (void)hipFuncSetAttribute((const void*)sdpa_fwd_fused_bf16_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
+            attr = true;
+        }
+        if (o_lo && hipMemset2DAsync(o_lo, (size_t)ldo * 2, 0, (size_t)H * dk * 2, (size_t)B * Tq, st) != hipSuccess) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: clearing o_lo failed");
+#define FF_ARGS (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale
+        if (dthr) sdpa_fwd_fused_bf16_kernel<true, true, true><<<B * H, FF_THREADS, FF_LDS, st>>>(FF_ARGS);
+        else sdpa_fwd_fused_bf16_kernel<false, true, true><<<B * H, FF_THREADS, FF_LDS, st>>>(FF_ARGS);
+#undef FF_ARGS
+    } else if (mfma) {
+        const int grid = ceil_div(Tq, 128) * H * B;
+#define TF_ARGS (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale, (bf16_t*)o_lo
+        if (dthr) sdpa_fwd_bf16_kernel<true, true><<<grid, 256, 0, st>>>(TF_ARGS);
+        else sdpa_fwd_bf16_kernel<false, true><<<grid, 256, 0, st>>>(TF_ARGS);
+#undef TF_ARGS
+    } else {
+        dim3 grid(Tq, H, B);
+        const size_t lds = (size_t)(Tk + dk) * sizeof(float);
+        if (lds > 64 * 1024) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: generic path needs Tk+dk <= 16384");
+        if (dtype == ASR_F32) sdpa_fwd_generic_kernel<float, true><<<grid, 64, lds, st>>>((const float*)q, (const float*)k, (const float*)v, (float*)o, lse, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);
+        else if (dtype == ASR_BF16) {
+            if (o_lo && hipMemset2DAsync(o_lo, (size_t)ldo * 2, 0, (size_t)H * dk * 2, (size_t)B * Tq, st) != hipSuccess) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: clearing o_lo failed");
+            sdpa_fwd_generic_kernel<bf16_t, true><<<grid, 64, lds, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);
+        }
+        else ASR_FAIL(ASR_EDTYPE, "asr_sdpa_chunk_fwd: dtype %d", dtype);
+    }
+    ASR_CHECK_LAUNCH("asr_sdpa_chunk_fwd");
+    return ASR_OK;
+}
+
+extern "C" size_t asr_sdpa_chunk_bwd_workspace_bytes(int B, int H, int Tq, int Tk, int dk, int chunk, int left_chunks, int dtype) {
+    if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0) return 0;
+    return (size_t)B * H * Tq * sizeof(float);      // row sums of dO o O (no band form under a chunk mask)
+}
+
+extern "C" int asr_sdpa_chunk_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, float* delta, size_t delta_bytes,
+                                  void* dq, void* dk_, void* dv, const int32_t* k_len, int B, int H, int Tq, int Tk, int dk, int ldq, int ldk, int ldv, int ldo,
+                                  int chunk, int left_chunks, float scale, float drop_p, uint32_t dseed, const void* o_lo, int dtype, void* stream) {
+    if (int rc = chunk_check("asr_sdpa_chunk_bwd", chunk, left_chunks)) return rc;
+    if (!q || !k || !v || !o || !d_o || !lse || !delta || !dq || !dk_ || !dv) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_bwd: null pointer");
+    if (o_lo && (dtype != ASR_BF16 || ((uintptr_t)o_lo % 16) != 0)) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_bwd: o_lo is the low-order piece of a bf16 output (16-byte aligned, the layout of o)");
+    if (int rc = check_common("asr_sdpa_chunk_bwd", B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo)) return rc;
+    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "asr_sdpa_chunk_bwd: dtype %d", dtype);
+    if (delta_bytes < (size_t)B * H * Tq * sizeof(float)) ASR_FAIL(ASR_EWORKSPACE, "asr_sdpa_chunk_bwd: scratch of %zu bytes, need at least B*H*Tq floats = %zu", delta_bytes, (size_t)B * H * Tq * sizeof(float));
+    if (drop_p < 0.f || drop_p >= 1.f) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_bwd: bad dropout p=%f", drop_p);
+    int C = chunk, left = left_chunks;
+    chunk_clamp(Tq, Tk, C, left);
+    const uint32_t dthr = drop_thr16(drop_p);
+    const float dscale = 1.f / (1.f - drop_p);
+    hipStream_t st = (hipStream_t)stream;
+    const int ngroups = B * Tq * H;
+    const bool mfma = dtype == ASR_BF16 && mfma_ok(dk, ldq, ldk, ldv, ldo, q, k, v, d_o) && mfma_ok(dk, ldq, ldk, ldv, ldo, dq, dk_, dv, o);
+    if (!mfma) {
+        if (dtype == ASR_F32) sdpa_delta_kernel<float><<<ceil_div(ngroups, 32), 256, 0, st>>>((const float*)o, (const float*)nullptr, (const float*)d_o, delta, B, H, Tq, dk, ldo);
+        else sdpa_delta_kernel<bf16_t><<<ceil_div(ngroups, 32), 256, 0, st>>>((const bf16_t*)o, (const bf16_t*)o_lo, (const bf16_t*)d_o, delta, B, H, Tq, dk, ldo);
+    }
+    if (mfma && Tk <= FB_KEYS) {
+        static bool attr = false;
+        if (!attr) {
+            (void)hipFuncSetAttribute((const void*)sdpa_bwd_fused_bf16_kernel<false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
+            (void)hipFuncSetAttribute((const void*)sdpa_bwd_fused_bf16_kernel<true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
+            attr = true;
+        }
+#define FB_ARGS (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, (const bf16_t*)o, (const bf16_t*)nullptr, lse, (bf16_t*)dq, (bf16_t*)dk_, (bf16_t*)dv, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale
+        if (dthr) asr_launch_armed(sdpa_bwd_fused_bf16_kernel<true, true, false, true>, dim3(B * H), dim3(FB_THREADS), FB_LDS, st, FB_ARGS, (float*)nullptr, 0);
+        else asr_launch_armed(sdpa_bwd_fused_bf16_kernel<false, true, false, true>, dim3(B * H), dim3(FB_THREADS), FB_LDS, st, FB_ARGS, (float*)nullptr, 0);
+#undef FB_ARGS
+    } else if (mfma) {
+        const int gq = ceil_div(Tq, 128) * H * B, gk = ceil_div(Tk, 128) * H * B;
+#define SDPA_BWD(D)                                                                                                                                        \
+    do {                                                                                                                                                   \
+        sdpa_bwd_dq_bf16_kernel<D, true><<<gq, 256, 0, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, (const bf16_t*)o, (const bf16_t*)o_lo, lse, delta, \
+                                                              (bf16_t*)dq, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);           \
+        sdpa_bwd_dkv_bf16_kernel<D, true><<<gk, 256, 0, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, lse, delta, (bf16_t*)dk_, \
+                                                               (bf16_t*)dv, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);          \
+    } while (0)
+        if (dthr) SDPA_BWD(true);
+        else SDPA_BWD(false);
+#undef SDPA_BWD
+    } else {
+        dim3 gq(Tq, H, B), gk(Tk, H, B);
+        const size_t l1 = (size_t)(Tk + 2 * dk) * sizeof(float), l2 = (size_t)(2 * Tq + 2 * dk) * sizeof(float);
+        if (l1 > 64 * 1024 || l2 > 64 * 1024) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_bwd: generic path sequence too long for LDS");
+        if (dtype == ASR_F32) {
+            sdpa_bwd_dq_generic_kernel<float, true><<<gq, 64, l1, st>>>((const float*)q, (const float*)k, (const float*)v, (const float*)d_o, lse, delta, (float*)dq, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);
+            sdpa_bwd_dkv_generic_kernel<float, true><<<gk, 64, l2, st>>>((const float*)q, (const float*)k, (const float*)v, (const float*)d_o, lse, delta, (float*)dk_, (float*)dv, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);
+        } else {
+            sdpa_bwd_dq_generic_kernel<bf16_t, true><<<gq, 64, l1, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, lse, delta, (bf16_t*)dq, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);
+            sdpa_bwd_dkv_generic_kernel<bf16_t, true><<<gk, 64, l2, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, lse, delta, (bf16_t*)dk_, (bf16_t*)dv, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);
+        }
+    }
+    ASR_CHECK_LAUNCH("asr_sdpa_chunk_bwd");
     return ASR_OK;
 }

@@ -54,7 +54,7 @@ class _DecoderSteps:
         self.dev = x.device
         self.eng, self.beam = eng, beam
         hd = eng.H * eng.dk
-        self.enc, _ = eng.encoder_fwd(x, self.wave_len, model.attn_window)            # (B*T, d)
+        self.enc, _ = model.encode(eng, x, self.wave_len)            # (B*T, d)
         self.maxlen = self.wave_len.clone() if decode_max_len == 0 else torch.full_like(self.wave_len, decode_max_len)
         self.Lcap = int(self.maxlen.max())
         if self.Lcap > eng.pe.shape[0]:

@@ -21,6 +21,9 @@ class GraphedStep:
         from .Models.transformer_official import CLIP_NORM
         if not hasattr(optimizer, "fused_step"):
             raise TypeError("graph capture needs the fused optimizer path (Trainer.NoamOpt over FusedAdam)")
+        if getattr(model, "chunk_size", 0) == -1 and model.training:
+            raise ValueError("graph capture with dynamic chunk training (chunk_size = -1) is not supported: the chunk is drawn per step "
+                             "and would be frozen into the graph; use a static chunk_size")
         eng = model._ensure_engine(example.wave.device)
         if eng.drop_p > 0 and model.training:
             raise ValueError("graph capture with dropout > 0 is not supported (seed is frozen at capture)")

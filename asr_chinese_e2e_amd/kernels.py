@@ -231,9 +231,12 @@ def _strided_rows(t, H, dk):
     return t.stride(0)
 
 
-def sdpa_fwd(q, k, v, k_len, B, H, Tq, Tk, dk, causal=False, window=-1, scale=None, o=None, lse=None, drop_p=0.0, drop_seed=0, o_lo=None):
+def sdpa_fwd(q, k, v, k_len, B, H, Tq, Tk, dk, causal=False, window=-1, scale=None, o=None, lse=None, drop_p=0.0, drop_seed=0, o_lo=None,
+             chunk=0, left_chunks=-1):
     """q: (B*Tq, H*dk) view, k/v: (B*Tk, H*dk) views (may be column slices of a fused buffer).
-    o_lo: a tensor of o's shape and strides for the low-order piece of the bf16 output (asr_hip.h; hand it to sdpa_bwd), or None."""
+    o_lo: a tensor of o's shape and strides for the low-order piece of the bf16 output (asr_hip.h; hand it to sdpa_bwd), or None.
+    chunk > 0: the chunk mask of asr_sdpa_chunk_fwd (chunk frames, left_chunks chunks of left context, -1 = all) instead of
+    causal / window, which must then be off."""
     ldq, ldk, ldv = _strided_rows(q, H, dk), _strided_rows(k, H, dk), _strided_rows(v, H, dk)
     assert q.shape[0] == B * Tq and k.shape[0] == B * Tk and v.shape[0] == B * Tk
     assert q.dtype == k.dtype == v.dtype
@@ -245,6 +248,13 @@ def sdpa_fwd(q, k, v, k_len, B, H, Tq, Tk, dk, causal=False, window=-1, scale=No
     assert o_lo is None or (o_lo.dtype == o.dtype == torch.bfloat16 and o_lo.shape == o.shape and o_lo.stride() == o.stride())
     scale = float(dk) ** -0.5 if scale is None else float(scale)
     e = q.element_size()
+    if chunk > 0:
+        assert not causal and window < 0, "a chunk mask replaces causal / window"
+        timed("sdpa_fwd", 4.0 * B * H * Tq * Tk * dk, lambda: check(
+            lib.asr_sdpa_chunk_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(k_len), B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo,
+                                   int(chunk), int(left_chunks), scale, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _p(o_lo), _dt(q), _stream()),
+            "asr_sdpa_chunk_fwd"), 2.0 * B * H * (Tq + Tk) * dk * e)
+        return o, lse
     timed("sdpa_fwd", 4.0 * B * H * Tq * Tk * dk, lambda: check(
         lib.asr_sdpa_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(k_len), B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo,
                          int(causal), int(window), scale, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _p(o_lo), _dt(q), _stream()), "asr_sdpa_fwd"),
@@ -253,7 +263,7 @@ def sdpa_fwd(q, k, v, k_len, B, H, Tq, Tk, dk, causal=False, window=-1, scale=No
 
 
 def sdpa_bwd(q, k, v, o, do, lse, k_len, B, H, Tq, Tk, dk, dq, dk_, dv, causal=False, window=-1, scale=None, delta=None,
-             drop_p=0.0, drop_seed=0, o_lo=None):
+             drop_p=0.0, drop_seed=0, o_lo=None, chunk=0, left_chunks=-1):
     ldq, ldk, ldv, ldo = (_strided_rows(t, H, dk) for t in (q, k, v, o))
     assert _strided_rows(do, H, dk) == ldo and _strided_rows(dq, H, dk) == ldq
     assert _strided_rows(dk_, H, dk) == ldk and _strided_rows(dv, H, dk) == ldv
@@ -261,6 +271,19 @@ def sdpa_bwd(q, k, v, o, do, lse, k_len, B, H, Tq, Tk, dk, dq, dk_, dv, causal=F
     _chk_i32(k_len)
     _chk_f32(lse)
     assert o_lo is None or (o_lo.dtype == o.dtype == torch.bfloat16 and o_lo.shape == o.shape and o_lo.stride() == o.stride())
+    if chunk > 0:
+        assert not causal and window < 0, "a chunk mask replaces causal / window"
+        if delta is None:
+            need = lib.asr_sdpa_chunk_bwd_workspace_bytes(B, H, Tq, Tk, dk, int(chunk), int(left_chunks), _dt(q))
+            delta = torch.empty((need + 3) // 4, dtype=torch.float32, device=q.device)
+        scale = float(dk) ** -0.5 if scale is None else float(scale)
+        e = q.element_size()
+        timed("sdpa_bwd", 10.0 * B * H * Tq * Tk * dk, lambda: check(
+            lib.asr_sdpa_chunk_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), delta.numel() * 4, _p(dq), _p(dk_), _p(dv), _p(k_len),
+                                   B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, int(chunk), int(left_chunks), scale, float(drop_p),
+                                   int(drop_seed) & 0xFFFFFFFF, _p(o_lo), _dt(q), _stream()), "asr_sdpa_chunk_bwd"),
+              B * H * (4.0 * Tq + 4.0 * Tk) * dk * e)
+        return dq, dk_, dv
     if delta is None:      # scratch: row sums of dO o O, or the band kernel's dQ partials of the tiles on a key-block boundary
         need = lib.asr_sdpa_bwd_workspace_bytes(B, H, Tq, Tk, dk, int(causal), int(window), _dt(q))
         delta = torch.empty((need + 3) // 4, dtype=torch.float32, device=q.device)
@@ -348,6 +371,16 @@ def ctc_greedy_decode(logits, in_len, blank=0):
     check(lib.asr_ctc_greedy_decode(_p(logits), _p(in_len), _p(ids), _p(lens), B, T, V, ld, int(blank), _dt(logits), _stream()),
           "asr_ctc_greedy_decode")
     return ids, lens
+
+
+def ctc_frame_argmax(logits, in_len, blank=0):
+    """logits (B,T,V) -> the frame-wise best path (B, T) int32 (frames t >= in_len[b] as asr_ctc_frame_argmax leaves them)."""
+    B, T, V = logits.shape
+    ld = _frame_rows(logits)
+    _chk_i32(in_len)
+    path = torch.empty(B, T, dtype=torch.int32, device=logits.device)
+    check(lib.asr_ctc_frame_argmax(_p(logits), _p(in_len), _p(path), B, T, V, ld, int(blank), _dt(logits), _stream()), "asr_ctc_frame_argmax")
+    return path
 
 
 def ctc_collapse(path, in_len, blank=0):

@@ -1,0 +1,149 @@
+"""Streaming encoder: the encoder under its decoding chunk mask, run one chunk of frames at a time (model.stream(batch_size)).
+
+Under the chunk mask (asr_hip.h: asr_sdpa_chunk_fwd) every valid query of chunk n sees exactly the valid keys of chunks
+n - left .. n (all of them when left = -1).  So a chunk's self-attention is the plain key-length attention of its C query rows over a
+per-layer K|V cache that holds those keys at rows [0, k_len) of each utterance: K.sdpa_fwd with k_len = cached + valid-in-chunk keys.
+The cache is one contiguous window per utterance: with left >= 0 it keeps the last left * C keys, copied down into a second buffer
+before each chunk (ping-pong) - a ring buffer would leave the stale rows of a partial last chunk visible, as the attention masks a key
+PREFIX only; with left = -1 it grows (doubling, at most to the positional-encoding table) and pushing past the table raises.
+
+Per push: input projection, LayerNorm + positional encoding at the chunk's absolute frame offset, the L encoder layers on B * C rows,
+the CTC head and its frame-wise argmax - the engine's kernels (gemm_small / NT, sdpa_fwd, add_ln_fwd, asr_ctc_frame_argmax).
+"""
+import torch
+
+from . import kernels as K
+from .Utils import Pack
+
+BLANK = 0      # the CTC blank (= PAD_ID of the model)
+
+
+class StreamingEncoder:
+    def __init__(self, model, batch_size):
+        C, left = model.decoding_chunk_size, model.decoding_left_chunks
+        if C <= 0:
+            raise ValueError("model.stream() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
+        self.model, self.B, self.C, self.left = model, int(batch_size), int(C), int(left)
+        if self.B < 1:
+            raise ValueError("batch_size must be >= 1")
+        self.eng = None
+        self.offset = 0                      # absolute frame of the next chunk (the same for every utterance)
+        self.valid = [0] * self.B            # valid frames pushed per utterance
+        self.ended = [False] * self.B        # a chunk with fewer than C valid frames ends the utterance
+        self.clen = [0] * self.B             # keys in the cache per utterance
+        self.last = [BLANK] * self.B         # best class of the previous valid frame (CTC collapse across chunk boundaries)
+        self.cap = 0                         # cache rows per utterance
+        self.caches = None                   # [buffer][layer] -> (B * cap, 2 H dk); the second buffer only with left >= 0 (_slide)
+        self.outs, self.feats = [], []
+
+    def _grow(self, eng, need, dev):
+        hd2 = 2 * eng.H * eng.dk
+        L = len(eng.enc)
+        if self.caches is None:
+            if self.left >= 0:      # fixed window: two buffers, the keys slide from one to the other
+                cap = self.left * self.C + self.C
+                self.caches = [[torch.zeros(self.B * cap, hd2, dtype=eng.dtype, device=dev) for _ in range(L)] for _ in range(2)]
+            else:                   # unlimited left context: one buffer that grows
+                cap = min(max(need, 4 * self.C), eng.pe.shape[0])
+                self.caches = [[torch.zeros(self.B * cap, hd2, dtype=eng.dtype, device=dev) for _ in range(L)]]
+            self.cap = cap
+            return
+        if need <= self.cap:
+            return
+        cap = min(max(2 * self.cap, need), eng.pe.shape[0])      # left = -1 only: the fixed window never needs more
+        new = [torch.zeros(self.B * cap, hd2, dtype=eng.dtype, device=dev) for _ in range(L)]
+        for i in range(L):
+            new[i].view(self.B, cap, hd2)[:, : self.cap] = self.caches[0][i].view(self.B, self.cap, hd2)
+        self.caches, self.cap = [new], cap
+
+    def _slide(self, dev):
+        """left >= 0: keep the last left * C keys of each utterance at rows [0, left * C) (copied into the other buffer)."""
+        keep = self.left * self.C
+        if self.left < 0 or not any(c > keep for c in self.clen):
+            return
+        src, dst = [], []
+        for b, c in enumerate(self.clen):
+            s0 = c - min(c, keep)
+            src += [b * self.cap + s0 + j for j in range(keep)]
+            dst += [b * self.cap + j for j in range(keep)]
+            self.clen[b] = min(c, keep)
+        src = torch.tensor(src, dtype=torch.long, device=dev)
+        dst = torch.tensor(dst, dtype=torch.long, device=dev)
+        for i, cur in enumerate(self.caches[0]):
+            self.caches[1][i].index_copy_(0, dst, cur.index_select(0, src))
+        self.caches = [self.caches[1], self.caches[0]]
+
+    def push(self, feats, n_valid):
+        """feats (B, C, F): one chunk of encoder-rate features (after LFR and normalisation) in the model's dtype; n_valid (B,): the valid
+        frames of each utterance in it (0 once an utterance has ended).  Returns per utterance the greedy CTC ids this chunk adds
+        (repeats collapsed across chunk boundaries; empty lists for a model without a CTC head)."""
+        model, B, C = self.model, self.B, self.C
+        if feats.dim() != 3 or feats.shape[0] != B or feats.shape[1] != C:
+            raise ValueError(f"push: feats must be (B, C, F) = ({B}, {C}, F), got {tuple(feats.shape)}")
+        nv = [int(x) for x in (n_valid.tolist() if torch.is_tensor(n_valid) else n_valid)]
+        if len(nv) != B or any(x < 0 or x > C for x in nv):
+            raise ValueError(f"push: n_valid must hold {B} values in [0, {C}], got {nv}")
+        for b in range(B):
+            if self.ended[b] and nv[b] > 0:
+                raise ValueError(f"push: utterance {b} has ended (an earlier chunk had fewer than {C} valid frames)")
+        eng = self.eng = model._ensure_engine(feats.device)
+        if self.offset + C > eng.pe.shape[0]:
+            raise ValueError(f"push: frame {self.offset + C} exceeds the positional-encoding table ({eng.pe.shape[0]} frames)")
+        dev = feats.device
+        H, dk, hd = eng.H, eng.dk, eng.H * eng.dk
+        was_training, eng.training = eng.training, False
+        try:
+            with torch.no_grad():
+                self._slide(dev)
+                self._grow(eng, max(self.clen) + C, dev)
+                caches = self.caches[0]
+                nv_dev = torch.tensor(nv, dtype=torch.int32, device=dev)
+                klen = torch.tensor([c + n for c, n in zip(self.clen, nv)], dtype=torch.int32, device=dev)
+                rows = torch.tensor([b * self.cap + self.clen[b] + t for b in range(B) for t in range(C)], dtype=torch.long, device=dev)
+                x = feats.to(eng.dtype).contiguous().reshape(B * C, -1)
+                e0 = eng.lin_in.fwd(x)
+                h, _, _ = K.add_ln_fwd(e0, None, eng.ln_in.g, eng.ln_in.b, eng.pe[self.offset:], None, B, C, xhat=e0)
+                for i, (mha, ffn) in enumerate(eng.enc):
+                    qkv = mha.qkv.fwd(h)
+                    cache = caches[i]
+                    cache.index_copy_(0, rows, qkv[:, hd:])
+                    ctx, _ = K.sdpa_fwd(qkv[:, :hd], cache[:, :hd], cache[:, hd:], klen, B, H, C, self.cap, dk)
+                    a = mha.fc.fwd(ctx)
+                    h1, _, _ = K.add_ln_fwd(a, h, mha.ln.g, mha.ln.b, None, nv_dev, B, C, xhat=a)
+                    h, _ = eng._ffn_block_fwd(ffn, h1, B, C, nv_dev, site=0)
+                out = [[] for _ in range(B)]
+                if model.use_ctc:
+                    logits = eng.ctc_lo.fwd(h).view(B, C, -1)
+                    path = K.ctc_frame_argmax(logits, nv_dev, BLANK).cpu().tolist()
+                    for b in range(B):
+                        for t in range(nv[b]):
+                            s = path[b][t]
+                            if s != BLANK and s != self.last[b]:
+                                out[b].append(s)
+                            self.last[b] = s
+        finally:
+            eng.training = was_training
+        self.outs.append(h.view(B, C, -1))
+        self.feats.append(feats)
+        for b in range(B):
+            self.clen[b] += nv[b]
+            self.valid[b] += nv[b]
+            if nv[b] < C:
+                self.ended[b] = True
+        self.offset += C
+        return out
+
+    def encoder_output(self):
+        """(enc (B, T, d) with T = chunks pushed * C, lengths (B,) int32): frames past an utterance's length are not meaningful."""
+        if not self.outs:
+            raise ValueError("encoder_output: nothing pushed yet")
+        dev = self.outs[0].device
+        return torch.cat(self.outs, dim=1), torch.tensor(self.valid, dtype=torch.int32, device=dev)
+
+    def finish(self, beam_size=5, **kw):
+        """model.transcribe(...) of the pushed features under the same decoding chunk mask, computed from the streamed encoder output
+        (the encoder does not run again).  kw: transcribe's other arguments (ctc_weight, timestamps, joint)."""
+        enc, lens = self.encoder_output()
+        wave = torch.cat(self.feats, dim=1)
+        with self.model.given_encoder_output(enc):
+            return self.model.transcribe(Pack(wave=wave, wave_len=lens), beam_size=beam_size, **kw)

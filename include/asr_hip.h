@@ -183,6 +183,26 @@ int asr_sdpa_bwd(const void* q, const void* k, const void* v, const void* o, con
                  int ldv, int ldo, int causal, int window, float scale, float drop_p,
                  uint32_t drop_seed, const void* o_lo, int dtype, void* stream);      /* o_lo: what asr_sdpa_fwd wrote there, or NULL */
 
+/* Chunk-masked attention (streaming encoders; WeNet's subsequent_chunk_mask with num_left_chunks, plus the key-length mask).
+ * Same arguments as asr_sdpa_fwd / asr_sdpa_bwd with (causal, window) replaced by (chunk, left_chunks), in key / query frames:
+ * key j is visible to query i of utterance b iff
+ *     j < k_len[b]  and  j < (i / chunk + 1) * chunk  and  (left_chunks < 0  or  j >= (i / chunk - left_chunks) * chunk)
+ * (integer division).  chunk >= Tk with left_chunks = -1 is full attention; chunk = 1, left_chunks = -1 is causal attention.  A query that sees no key (a padded frame of a chunk past the left context of
+ * every valid key, any query of an utterance with k_len = 0) gets o = 0 and lse = 0 (finite) and adds nothing to dk / dv.
+ * chunk < 1 or left_chunks < -1: ASR_EINVAL before anything is launched.  Dropout masks: the counters of asr_sdpa_fwd.
+ * Every path of asr_sdpa_fwd / _bwd has a chunk form except the band kernel (no window here); o_lo as there.
+ * The backward scratch needs asr_sdpa_chunk_bwd_workspace_bytes(...) = B*H*Tq floats. */
+int asr_sdpa_chunk_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
+                       const int32_t* k_len, int B, int H, int Tq, int Tk, int dk, int ldq, int ldk,
+                       int ldv, int ldo, int chunk, int left_chunks, float scale, float drop_p,
+                       uint32_t drop_seed, void* o_lo, int dtype, void* stream);
+size_t asr_sdpa_chunk_bwd_workspace_bytes(int B, int H, int Tq, int Tk, int dk, int chunk, int left_chunks, int dtype);
+int asr_sdpa_chunk_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o,
+                       const float* lse, float* delta, size_t delta_bytes, void* dq, void* dk_, void* dv,
+                       const int32_t* k_len, int B, int H, int Tq, int Tk, int dk, int ldq, int ldk,
+                       int ldv, int ldo, int chunk, int left_chunks, float scale, float drop_p,
+                       uint32_t drop_seed, const void* o_lo, int dtype, void* stream);
+
 /* Test helpers: materialise the keep masks the kernels regenerate (1 = kept), uint8.
  * asr_dropout_mask: (rows, cols) mask of the LayerNorm / embedding sites;
  * asr_sdpa_dropout_mask: (B, H, Tq, Tk) mask of the attention-probability site. */

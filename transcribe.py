@@ -16,6 +16,10 @@ trained with rebuild it.  Inference flags:
                  take part in every step of the search)
   --batch_size   utterances per batch (default 16)
   --timestamps   per-character times from the CTC head (default: on when the model has one)
+  --stream       1 = run the encoder chunk by chunk (model.stream) under the decoding chunk mask (--decoding_chunk_size /
+                 --decoding_left_chunks, or the model's static --chunk_size / --left_chunks): one JSON line
+                 {"file", "chunk", "partial"} of greedy CTC text per chunk, then the final line as without it.  The features are
+                 still normalised over the whole utterance: this emulates streaming over files, it is not a live-audio front end.
 Audio goes through load_wav -> AudioParser.parse_batch on the device -> model.transcribe; one JSON line per file is printed:
 {"file", "duration_s", "text", "ids", "score", "tokens": [{"id", "token", "start_frame", "end_frame", "start_s", "end_s", "logp"}]}.
 """
@@ -35,7 +39,7 @@ from asr_chinese_e2e_amd.data_handler import AudioParser, Vocab, load_wav  # noq
 from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint")
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream")
 
 
 def _finite(x):
@@ -68,6 +72,26 @@ def audio_files(flags):
     raise SystemExit("transcribe.py: give --wavs=a.wav,b.wav or --manifest=<collector json>")
 
 
+def stream_batch(model, files, feats, flen, id2tok, **search):
+    """model.stream over a batch of feature sequences in chunks of the decoding chunk size: prints the partial greedy CTC text of every
+    file after every chunk, returns what model.transcribe returns (finish())."""
+    B, T, F = feats.shape
+    C = model.decoding_chunk_size
+    lens = [int(x) for x in flen.tolist()]
+    st = model.stream(B)
+    text = [""] * B
+    for i, c0 in enumerate(range(0, T, C)):
+        x = feats[:, c0:c0 + C]
+        if x.shape[1] < C:
+            x = torch.nn.functional.pad(x, (0, 0, 0, C - x.shape[1]))
+        nv = [max(0, min(C, n - c0)) for n in lens]
+        for b, ids in enumerate(st.push(x.contiguous(), nv)):
+            if nv[b] > 0:
+                text[b] += "".join(id2tok[t] for t in ids)
+                print(json.dumps({"file": files[b], "chunk": i, "partial": text[b]}, ensure_ascii=False), flush=True)
+    return st.finish(**search)
+
+
 def transcribe(**flags):
     cli = {k: flags.pop(k) for k in CLI_KEYS if k in flags}
     ctc_weight = flags.get("ctc_weight")          # model flag and decoding weight: the search uses the model's unless given
@@ -89,6 +113,10 @@ def transcribe(**flags):
     joint = str(cli.get("joint", "rescore"))
     if joint not in ("rescore", "one_pass"):
         raise SystemExit(f"transcribe.py: --joint must be rescore or one_pass (got {joint!r})")
+    stream = bool(int(cli.get("stream", 0)))
+    if stream and model.decoding_chunk_size <= 0:
+        raise SystemExit("transcribe.py: --stream=1 needs a decoding chunk (--decoding_chunk_size, or a static --chunk_size)")
+    id2tok = vocab._id2token
     for i in range(0, len(files), bs):
         chunk = files[i:i + bs]
         waves = []
@@ -103,8 +131,11 @@ def transcribe(**flags):
             wav[b, : len(w)] = w
         wav_len = torch.tensor([len(w) for w in waves], dtype=torch.int32)
         feats, flen = parser.parse_batch(torch.from_numpy(wav).cuda(), wav_len.cuda())
-        out = model.transcribe(Pack(wave=feats, wave_len=flen), beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps,
-                               joint=joint)
+        if stream:
+            out = stream_batch(model, chunk, feats, flen, id2tok, beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps, joint=joint)
+        else:
+            out = model.transcribe(Pack(wave=feats, wave_len=flen), beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps,
+                                   joint=joint)
         for path, w, r in zip(chunk, waves, out):
             dur = len(w) / float(config.sample_rate)
             for t in r["tokens"] or ():          # the last encoder frame may reach past the end of the audio
