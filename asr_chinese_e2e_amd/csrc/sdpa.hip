@@ -19,7 +19,14 @@
 //
 // f32 path: exact-fp32 VALU kernels with the same decomposition (used for fp32 parity mode and
 // for head sizes other than 64); one wave per query (fwd, dQ) or per key (dKV).
+//
+// Dispatch (end of the file): the four entry points share one forward and one backward launcher, templates on CHUNK as the kernels are.
+// bf16, head dim 64, aligned rows: the one-workgroup-per-head kernels up to 512 keys, beyond them the band kernel (backward, a window
+// over self-attention) or the tiled kernels above; anything else: the f32-accumulating generic kernels.  Dropout, mask and element type
+// reach the kernels as template arguments through with_bools().
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "asr_common.h"
 
@@ -1823,294 +1830,197 @@ __global__ __launch_bounds__(64) void sdpa_bwd_dkv_generic_kernel(const T* __res
     }
 }
 
-static bool mfma_ok(int dk, int ldq, int ldk, int ldv, int ldo, const void* a, const void* b, const void* c, const void* d) {
+// ------------------------------------------------------------------------------------------
+// host side: one forward and one backward launcher for every mask, CHUNK as in the kernels; the entry points at the end are wrappers.
+// Their a, b are (causal, window), or - CHUNK, streaming encoders - the chunk size and the left context in chunks, as chunk_check passed them.
+// ------------------------------------------------------------------------------------------
+// Run-time bools to template arguments: with_bools(f, x, y) calls f(std::bool_constant<x>(), std::bool_constant<y>()), so that a generic
+// lambda names its kernel instantiation with them; each_bools<2>(f) calls f for all four pairs. A combination that is not built - a chunk
+// mask is a mask: no <.., MASKED = false, CHUNK = true> - is ruled out with `if constexpr`. Both compile to the if / else ladders they stand for.
+template <typename F> inline void with_bools(F&& f) { f(); }
+template <typename F, typename... Bs> inline void with_bools(F&& f, bool b, Bs... bs) {
+    if (b) with_bools([&](auto... cs) { f(std::true_type(), cs...); }, bs...);
+    else with_bools([&](auto... cs) { f(std::false_type(), cs...); }, bs...);
+}
+template <int N, typename F> inline bool each_bools(F&& f) {
+    if constexpr (N == 0) f();
+    else {
+        each_bools<N - 1>([&](auto... cs) { f(std::false_type(), cs...); });
+        each_bools<N - 1>([&](auto... cs) { f(std::true_type(), cs...); });
+    }
+    return true;
+}
+// more than 64 KB of dynamic LDS has to be allowed per kernel: the first call of a path does it for every instantiation the path launches
+template <typename K> inline void allow_lds(K* kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
+bool mfma_ok(int dk, int ldq, int ldk, int ldv, int ldo, const void* a, const void* b, const void* c, const void* d) {
     return dk == DK && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 &&
            (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) % 16) == 0;
 }
-
-static int check_common(const char* name, int B, int H, int Tq, int Tk, int dk, int ldq, int ldk, int ldv, int ldo) {
+int check_common(const char* name, int B, int H, int Tq, int Tk, int dk, int ldq, int ldk, int ldv, int ldo, const void* o_lo, int dtype) {
+    if (o_lo && (dtype != ASR_BF16 || ((uintptr_t)o_lo % 16) != 0)) ASR_FAIL(ASR_EINVAL, "%s: o_lo is the low-order piece of a bf16 output (16-byte aligned, the layout of o)", name);
     if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || dk <= 0 || dk > 128) ASR_FAIL(ASR_EINVAL, "%s: bad shape B=%d H=%d Tq=%d Tk=%d dk=%d", name, B, H, Tq, Tk, dk);
     if (ldq < H * dk || ldk < H * dk || ldv < H * dk || ldo < H * dk) ASR_FAIL(ASR_EINVAL, "%s: row stride smaller than H*dk", name);
     if (B > 65535 || H > 65535) ASR_FAIL(ASR_EINVAL, "%s: B or H exceeds grid limits", name);
     return ASR_OK;
 }
 
-}  // namespace
-
-extern "C" int asr_sdpa_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* k_len, int B, int H, int Tq, int Tk, int dk,
-                            int ldq, int ldk, int ldv, int ldo, int causal, int window, float scale, float drop_p, uint32_t dseed, void* o_lo,
-                            int dtype, void* stream) {
-    if (!q || !k || !v || !o || !lse) ASR_FAIL(ASR_EINVAL, "asr_sdpa_fwd: null pointer");
-    if (o_lo && (dtype != ASR_BF16 || ((uintptr_t)o_lo % 16) != 0)) ASR_FAIL(ASR_EINVAL, "asr_sdpa_fwd: o_lo is the low-order piece of a bf16 output (16-byte aligned, the layout of o)");
-    if (int rc = check_common("asr_sdpa_fwd", B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo)) return rc;
-    if (drop_p < 0.f || drop_p >= 1.f) ASR_FAIL(ASR_EINVAL, "asr_sdpa_fwd: bad dropout p=%f", drop_p);
-    if ((double)B * H * Tq * (Tk + 1) >= 4294967296.0) ASR_FAIL(ASR_EINVAL, "asr_sdpa_fwd: B*H*Tq*Tk exceeds the 32-bit dropout counter");
-    const uint32_t dthr = drop_thr16(drop_p);
-    const float dscale = 1.f / (1.f - drop_p);
-    hipStream_t st = (hipStream_t)stream;
-    const bool ff_fused = dtype == ASR_BF16 && mfma_ok(dk, ldq, ldk, ldv, ldo, q, k, v, o) && Tk <= FF_KEYS;      // else (more keys than LDS holds): the tiled kernel of round 1
-    if (ff_fused) {   // K and V of a head fit LDS: one workgroup per (b, h)
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)sdpa_fwd_fused_bf16_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
-            (void)hipFuncSetAttribute((const void*)sdpa_fwd_fused_bf16_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
-            (void)hipFuncSetAttribute((const void*)sdpa_fwd_fused_bf16_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
-            (void)hipFuncSetAttribute((const void*)sdpa_fwd_fused_bf16_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
-            (void)hipFuncSetAttribute((const void*)sdpa_fwd_pair_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
-            attr = true;
-        }
-        // the backward pass of these shapes (every key of a head in one workgroup) does not read a low-order piece: a buffer given anyway is cleared
-        if (o_lo && hipMemset2DAsync(o_lo, (size_t)ldo * 2, 0, (size_t)H * dk * 2, (size_t)B * Tq, st) != hipSuccess) ASR_FAIL(ASR_EINVAL, "asr_sdpa_fwd: clearing o_lo failed");
-#define FF_ARGS (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale
-        const bool masked = causal || window >= 0;
-        if (dthr && masked) sdpa_fwd_fused_bf16_kernel<true, true><<<B * H, FF_THREADS, FF_LDS, st>>>(FF_ARGS);
-        else if (dthr) sdpa_fwd_fused_bf16_kernel<true, false><<<B * H, FF_THREADS, FF_LDS, st>>>(FF_ARGS);
-        else if (masked) sdpa_fwd_fused_bf16_kernel<false, true><<<B * H, FF_THREADS, FF_LDS, st>>>(FF_ARGS);
-        else if (asr_option(ASR_OPT_SDPA_PAIR)) sdpa_fwd_pair_bf16_kernel<<<B * H, FF_THREADS, FF_LDS, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, scale);
-        else sdpa_fwd_fused_bf16_kernel<false, false><<<B * H, FF_THREADS, FF_LDS, st>>>(FF_ARGS);
-#undef FF_ARGS
-    } else if (dtype == ASR_BF16 && mfma_ok(dk, ldq, ldk, ldv, ldo, q, k, v, o)) {
-        const int grid = ceil_div(Tq, 128) * H * B;
-        if (dthr) sdpa_fwd_bf16_kernel<true><<<grid, 256, 0, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale, (bf16_t*)o_lo);
-        else sdpa_fwd_bf16_kernel<false><<<grid, 256, 0, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale, (bf16_t*)o_lo);
-    } else {
-        dim3 grid(Tq, H, B);
-        const size_t lds = (size_t)(Tk + dk) * sizeof(float);
-        if (lds > 64 * 1024) ASR_FAIL(ASR_EINVAL, "asr_sdpa_fwd: generic path needs Tk+dk <= 16384");
-        if (dtype == ASR_F32) sdpa_fwd_generic_kernel<float><<<grid, 64, lds, st>>>((const float*)q, (const float*)k, (const float*)v, (float*)o, lse, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale);
-        else if (dtype == ASR_BF16) {
-            // this path writes no low-order piece: zeros (the backward pass then takes delta from o alone)
-            if (o_lo && hipMemset2DAsync(o_lo, (size_t)ldo * 2, 0, (size_t)H * dk * 2, (size_t)B * Tq, st) != hipSuccess) ASR_FAIL(ASR_EINVAL, "asr_sdpa_fwd: clearing o_lo failed");
-            sdpa_fwd_generic_kernel<bf16_t><<<grid, 64, lds, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale);
-        }
-        else ASR_FAIL(ASR_EDTYPE, "asr_sdpa_fwd: dtype %d", dtype);
-    }
-    ASR_CHECK_LAUNCH("asr_sdpa_fwd");
-    return ASR_OK;
-}
-
-// single-pass band kernel: bf16 MFMA shapes, self-attention (Tq == Tk) inside a +-window band, more keys than one workgroup holds,
-// and the band of a 32-query tile touches at most two 512-key blocks
-static bool sdpa_band_shape(int Tq, int Tk, int dk, int causal, int window, int dtype) {
-    return dtype == ASR_BF16 && dk == DK && Tq == Tk && Tk > FB_KEYS && !causal && window >= 0 && 2 * window + FB_QT <= FB_KEYS;
-}
-static int sdpa_band_slots(int window) { return (2 * window + FB_QT - 1) / FB_QT + 2; }
-
-extern "C" size_t asr_sdpa_bwd_workspace_bytes(int B, int H, int Tq, int Tk, int dk, int causal, int window, int dtype) {
-    if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0) return 0;
-    size_t need = (size_t)B * H * Tq * sizeof(float);
-    if (sdpa_band_shape(Tq, Tk, dk, causal, window, dtype)) {
-        const size_t halo = (size_t)B * H * (ceil_div(Tk, FB_KEYS) - 1) * 2 * sdpa_band_slots(window) * FB_QT * DK * sizeof(float);
-        if (halo > need) need = halo;
-    }
-    return need;
-}
-
-extern "C" int asr_sdpa_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, float* delta, size_t delta_bytes,
-                            void* dq, void* dk_, void* dv, const int32_t* k_len, int B, int H, int Tq, int Tk, int dk, int ldq, int ldk, int ldv, int ldo,
-                            int causal, int window, float scale, float drop_p, uint32_t dseed, const void* o_lo, int dtype, void* stream) {
-    if (!q || !k || !v || !o || !d_o || !lse || !delta || !dq || !dk_ || !dv) ASR_FAIL(ASR_EINVAL, "asr_sdpa_bwd: null pointer");
-    if (o_lo && (dtype != ASR_BF16 || ((uintptr_t)o_lo % 16) != 0)) ASR_FAIL(ASR_EINVAL, "asr_sdpa_bwd: o_lo is the low-order piece of a bf16 output (16-byte aligned, the layout of o)");
-    if (int rc = check_common("asr_sdpa_bwd", B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo)) return rc;
-    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "asr_sdpa_bwd: dtype %d", dtype);
-    if (delta_bytes < (size_t)B * H * Tq * sizeof(float)) ASR_FAIL(ASR_EWORKSPACE, "asr_sdpa_bwd: scratch of %zu bytes, need at least B*H*Tq floats = %zu", delta_bytes, (size_t)B * H * Tq * sizeof(float));
-    if (drop_p < 0.f || drop_p >= 1.f) ASR_FAIL(ASR_EINVAL, "asr_sdpa_bwd: bad dropout p=%f", drop_p);
-    const uint32_t dthr = drop_thr16(drop_p);
-    const float dscale = 1.f / (1.f - drop_p);
-    hipStream_t st = (hipStream_t)stream;
-    const int ngroups = B * Tq * H;
-    const bool mfma = dtype == ASR_BF16 && mfma_ok(dk, ldq, ldk, ldv, ldo, q, k, v, d_o) && mfma_ok(dk, ldq, ldk, ldv, ldo, dq, dk_, dv, o);
-    if (!mfma) {   // the MFMA dQ kernel computes delta itself
-        if (dtype == ASR_F32) sdpa_delta_kernel<float><<<ceil_div(ngroups, 32), 256, 0, st>>>((const float*)o, (const float*)nullptr, (const float*)d_o, delta, B, H, Tq, dk, ldo);
-        else sdpa_delta_kernel<bf16_t><<<ceil_div(ngroups, 32), 256, 0, st>>>((const bf16_t*)o, (const bf16_t*)o_lo, (const bf16_t*)d_o, delta, B, H, Tq, dk, ldo);
-    }
-    const bool fb_fused = mfma && Tk <= FB_KEYS;      // else: the band kernel (windowed attention over many keys) or the dQ + dK/dV pair of round 1
-    if (fb_fused) {   // every key of a head fits one workgroup: single-pass backward
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)sdpa_bwd_fused_bf16_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
-            (void)hipFuncSetAttribute((const void*)sdpa_bwd_fused_bf16_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS + FB_VIMG_BYTES);
-            (void)hipFuncSetAttribute((const void*)sdpa_bwd_fused_bf16_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
-            (void)hipFuncSetAttribute((const void*)sdpa_bwd_fused_bf16_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
-            attr = true;
-        }
-#define FB_ARGS (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, (const bf16_t*)o, (const bf16_t*)nullptr, lse, (bf16_t*)dq, (bf16_t*)dk_, (bf16_t*)dv, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale
-        const bool masked = causal || window >= 0;
-        // the only kernel of this path: it may carry an armed completion event (asr_stream_arm)
-        if (dthr && masked) asr_launch_armed(sdpa_bwd_fused_bf16_kernel<true, true>, dim3(B * H), dim3(FB_THREADS), FB_LDS, st, FB_ARGS, (float*)nullptr, 0);
-        else if (dthr) asr_launch_armed(sdpa_bwd_fused_bf16_kernel<true, false>, dim3(B * H), dim3(FB_THREADS), FB_LDS, st, FB_ARGS, (float*)nullptr, 0);
-        else if (masked) asr_launch_armed(sdpa_bwd_fused_bf16_kernel<false, true>, dim3(B * H), dim3(FB_THREADS), FB_LDS + (Tk <= 64 ? FB_VIMG_BYTES : 0), st, FB_ARGS, (float*)nullptr, 0);
-        else asr_launch_armed(sdpa_bwd_fused_bf16_kernel<false, false>, dim3(B * H), dim3(FB_THREADS), FB_LDS, st, FB_ARGS, (float*)nullptr, 0);
-#undef FB_ARGS
-    } else if (mfma && sdpa_band_shape(Tq, Tk, dk, causal, window, dtype) && delta_bytes >= asr_sdpa_bwd_workspace_bytes(B, H, Tq, Tk, dk, causal, window, dtype)
-               && ((uintptr_t)delta % 16) == 0) {
-        // long-form band: one workgroup per (b, h, 512-key block), single pass; dQ of the tiles on a block boundary through fp32 slabs
-        static bool attr_b = false;
-        if (!attr_b) {
-            (void)hipFuncSetAttribute((const void*)sdpa_bwd_fused_bf16_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
-            (void)hipFuncSetAttribute((const void*)sdpa_bwd_fused_bf16_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
-            attr_b = true;
-        }
-        const int nblk = ceil_div(Tk, FB_KEYS), slots = sdpa_band_slots(window);
-        const dim3 grid(B * H, nblk);
-#define FBB_ARGS (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, (const bf16_t*)o, (const bf16_t*)o_lo, lse, (bf16_t*)dq, (bf16_t*)dk_, (bf16_t*)dv, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale, delta, slots
-        if (dthr) sdpa_bwd_fused_bf16_kernel<true, true, true><<<grid, FB_THREADS, FB_LDS, st>>>(FBB_ARGS);
-        else sdpa_bwd_fused_bf16_kernel<false, true, true><<<grid, FB_THREADS, FB_LDS, st>>>(FBB_ARGS);
-#undef FBB_ARGS
-        sdpa_band_halo_kernel<<<dim3(slots, nblk - 1, B * H), 256, 0, st>>>(delta, (bf16_t*)dq, H, Tq, Tk, ldq, window, slots);
-    } else if (mfma) {
-        const int gq = ceil_div(Tq, 128) * H * B, gk = ceil_div(Tk, 128) * H * B;
-#define SDPA_BWD(D)                                                                                                                                        \
-    do {                                                                                                                                                   \
-        sdpa_bwd_dq_bf16_kernel<D><<<gq, 256, 0, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, (const bf16_t*)o, (const bf16_t*)o_lo, lse, delta, (bf16_t*)dq, \
-                                                        k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale);                  \
-        sdpa_bwd_dkv_bf16_kernel<D><<<gk, 256, 0, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, lse, delta, (bf16_t*)dk_, \
-                                                         (bf16_t*)dv, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale);    \
-    } while (0)
-        if (dthr) SDPA_BWD(true);
-        else SDPA_BWD(false);
-#undef SDPA_BWD
-    } else {
-        dim3 gq(Tq, H, B), gk(Tk, H, B);
-        const size_t l1 = (size_t)(Tk + 2 * dk) * sizeof(float), l2 = (size_t)(2 * Tq + 2 * dk) * sizeof(float);
-        if (l1 > 64 * 1024 || l2 > 64 * 1024) ASR_FAIL(ASR_EINVAL, "asr_sdpa_bwd: generic path sequence too long for LDS");
-        if (dtype == ASR_F32) {
-            sdpa_bwd_dq_generic_kernel<float><<<gq, 64, l1, st>>>((const float*)q, (const float*)k, (const float*)v, (const float*)d_o, lse, delta, (float*)dq, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale);
-            sdpa_bwd_dkv_generic_kernel<float><<<gk, 64, l2, st>>>((const float*)q, (const float*)k, (const float*)v, (const float*)d_o, lse, delta, (float*)dk_, (float*)dv, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale);
-        } else {
-            sdpa_bwd_dq_generic_kernel<bf16_t><<<gq, 64, l1, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, lse, delta, (bf16_t*)dq, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale);
-            sdpa_bwd_dkv_generic_kernel<bf16_t><<<gk, 64, l2, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, lse, delta, (bf16_t*)dk_, (bf16_t*)dv, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, causal, window, scale, dseed, dthr, dscale);
-        }
-    }
-    ASR_CHECK_LAUNCH("asr_sdpa_bwd");
-    return ASR_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// chunk-masked attention (streaming encoders): the CHUNK instantiations of the kernels above, the causal / window arguments
-// carrying (C, left): key length, chunk upper bound and (left >= 0) chunk lower bound.
-// ------------------------------------------------------------------------------------------
-static int chunk_check(const char* name, int chunk, int left_chunks) {
+int chunk_check(const char* name, int chunk, int left_chunks) {
     if (chunk < 1 || left_chunks < -1) ASR_FAIL(ASR_EINVAL, "%s: bad chunk mask chunk=%d left_chunks=%d (need chunk >= 1, left_chunks >= -1)", name, chunk, left_chunks);
     return ASR_OK;
 }
-// clamp (C, left) to the shape: the same mask, and no overflow in the kernels' range arithmetic
-static void chunk_clamp(int Tq, int Tk, int& chunk, int& left) {
+// clamp a checked (chunk, left) to a checked shape: the same mask, and no overflow in the kernels' range arithmetic
+void chunk_clamp(int Tq, int Tk, int& chunk, int& left) {
     const int tmax = Tq > Tk ? Tq : Tk;
     if (chunk > tmax) chunk = tmax;
     const int nq = (Tq - 1) / chunk;      // last query chunk
     if (left > nq) left = -1;             // every query sees back to key 0
 }
 
-extern "C" int asr_sdpa_chunk_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* k_len, int B, int H, int Tq, int Tk, int dk,
-                                  int ldq, int ldk, int ldv, int ldo, int chunk, int left_chunks, float scale, float drop_p, uint32_t dseed, void* o_lo,
-                                  int dtype, void* stream) {
-    if (int rc = chunk_check("asr_sdpa_chunk_fwd", chunk, left_chunks)) return rc;
-    if (!q || !k || !v || !o || !lse) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: null pointer");
-    if (o_lo && (dtype != ASR_BF16 || ((uintptr_t)o_lo % 16) != 0)) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: o_lo is the low-order piece of a bf16 output (16-byte aligned, the layout of o)");
-    if (int rc = check_common("asr_sdpa_chunk_fwd", B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo)) return rc;
-    if (drop_p < 0.f || drop_p >= 1.f) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: bad dropout p=%f", drop_p);
-    if ((double)B * H * Tq * (Tk + 1) >= 4294967296.0) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: B*H*Tq*Tk exceeds the 32-bit dropout counter");
-    int C = chunk, left = left_chunks;
-    chunk_clamp(Tq, Tk, C, left);
+template <bool CHUNK>
+int sdpa_fwd(const char* name, const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* k_len, int B, int H, int Tq, int Tk, int dk,
+             int ldq, int ldk, int ldv, int ldo, int a, int b, float scale, float drop_p, uint32_t dseed, void* o_lo, int dtype, void* stream) {
+    if (!q || !k || !v || !o || !lse) ASR_FAIL(ASR_EINVAL, "%s: null pointer", name);
+    if (int rc = check_common(name, B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, o_lo, dtype)) return rc;
+    if (drop_p < 0.f || drop_p >= 1.f) ASR_FAIL(ASR_EINVAL, "%s: bad dropout p=%f", name, drop_p);
+    if ((double)B * H * Tq * (Tk + 1) >= 4294967296.0) ASR_FAIL(ASR_EINVAL, "%s: B*H*Tq*Tk exceeds the 32-bit dropout counter", name);
+    if (CHUNK) chunk_clamp(Tq, Tk, a, b);
     const uint32_t dthr = drop_thr16(drop_p);
     const float dscale = 1.f / (1.f - drop_p);
     hipStream_t st = (hipStream_t)stream;
     const bool mfma = dtype == ASR_BF16 && mfma_ok(dk, ldq, ldk, ldv, ldo, q, k, v, o);
-    if (mfma && Tk <= FF_KEYS) {
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)sdpa_fwd_fused_bf16_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
-            (void)hipFuncSetAttribute((const void*)sdpa_fwd_fused_bf16_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
-            attr = true;
-        }
-        if (o_lo && hipMemset2DAsync(o_lo, (size_t)ldo * 2, 0, (size_t)H * dk * 2, (size_t)B * Tq, st) != hipSuccess) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: clearing o_lo failed");
-#define FF_ARGS (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale
-        if (dthr) sdpa_fwd_fused_bf16_kernel<true, true, true><<<B * H, FF_THREADS, FF_LDS, st>>>(FF_ARGS);
-        else sdpa_fwd_fused_bf16_kernel<false, true, true><<<B * H, FF_THREADS, FF_LDS, st>>>(FF_ARGS);
-#undef FF_ARGS
+    const bool fused = mfma && Tk <= FF_KEYS;      // K and V of a head fit LDS: one workgroup per (b, h); more keys: the tiled kernel
+    const bool has_mask = CHUNK || a || b >= 0;
+    const size_t lds_generic = (size_t)(Tk + dk) * sizeof(float);
+    if (!mfma && lds_generic > 64 * 1024) ASR_FAIL(ASR_EINVAL, "%s: generic path needs Tk+dk <= 16384", name);
+    if (!mfma && dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "%s: dtype %d", name, dtype);
+    // o_lo: only the tiled kernel writes it (the backward pass of the fused shapes reads none): elsewhere a buffer given anyway is cleared, and delta comes from o alone
+    if (o_lo && (fused || !mfma) && hipMemset2DAsync(o_lo, (size_t)ldo * 2, 0, (size_t)H * dk * 2, (size_t)B * Tq, st) != hipSuccess) ASR_FAIL(ASR_EINVAL, "%s: clearing o_lo failed", name);
+    const bf16_t *qb = (const bf16_t*)q, *kb = (const bf16_t*)k, *vb = (const bf16_t*)v;
+    bf16_t* ob = (bf16_t*)o;
+    if (fused) {
+        static const bool lds_allowed = each_bools<2>([](auto drop, auto masked) {
+            if constexpr (masked || !CHUNK) allow_lds(sdpa_fwd_fused_bf16_kernel<drop, masked, CHUNK>, FF_LDS);
+            if constexpr (!drop && !masked && !CHUNK) allow_lds(sdpa_fwd_pair_bf16_kernel, FF_LDS);      // its stand-in under the sdpa_pair option
+        });
+        // the sdpa_pair option's two-queries-per-lane kernel: there is no mask, dropout or chunk form of it
+        if (!dthr && !has_mask && asr_option(ASR_OPT_SDPA_PAIR)) sdpa_fwd_pair_bf16_kernel<<<B * H, FF_THREADS, FF_LDS, st>>>(qb, kb, vb, ob, lse, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, scale);
+        else with_bools([&](auto drop, auto masked) {
+            if constexpr (masked || !CHUNK) sdpa_fwd_fused_bf16_kernel<drop, masked, CHUNK><<<B * H, FF_THREADS, FF_LDS, st>>>(qb, kb, vb, ob, lse, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, a, b, scale, dseed, dthr, dscale);
+        }, dthr != 0, has_mask);
     } else if (mfma) {
-        const int grid = ceil_div(Tq, 128) * H * B;
-#define TF_ARGS (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale, (bf16_t*)o_lo
-        if (dthr) sdpa_fwd_bf16_kernel<true, true><<<grid, 256, 0, st>>>(TF_ARGS);
-        else sdpa_fwd_bf16_kernel<false, true><<<grid, 256, 0, st>>>(TF_ARGS);
-#undef TF_ARGS
+        with_bools([&](auto drop) {
+            sdpa_fwd_bf16_kernel<drop, CHUNK><<<ceil_div(Tq, 128) * H * B, 256, 0, st>>>(qb, kb, vb, ob, lse, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, a, b, scale, dseed, dthr, dscale, (bf16_t*)o_lo);
+        }, dthr != 0);
     } else {
-        dim3 grid(Tq, H, B);
-        const size_t lds = (size_t)(Tk + dk) * sizeof(float);
-        if (lds > 64 * 1024) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: generic path needs Tk+dk <= 16384");
-        if (dtype == ASR_F32) sdpa_fwd_generic_kernel<float, true><<<grid, 64, lds, st>>>((const float*)q, (const float*)k, (const float*)v, (float*)o, lse, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);
-        else if (dtype == ASR_BF16) {
-            if (o_lo && hipMemset2DAsync(o_lo, (size_t)ldo * 2, 0, (size_t)H * dk * 2, (size_t)B * Tq, st) != hipSuccess) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_fwd: clearing o_lo failed");
-            sdpa_fwd_generic_kernel<bf16_t, true><<<grid, 64, lds, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);
-        }
-        else ASR_FAIL(ASR_EDTYPE, "asr_sdpa_chunk_fwd: dtype %d", dtype);
+        with_bools([&](auto f32) {
+            using T = std::conditional_t<f32, float, bf16_t>;
+            sdpa_fwd_generic_kernel<T, CHUNK><<<dim3(Tq, H, B), 64, lds_generic, st>>>((const T*)q, (const T*)k, (const T*)v, (T*)o, lse, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, a, b, scale, dseed, dthr, dscale);
+        }, dtype == ASR_F32);
     }
-    ASR_CHECK_LAUNCH("asr_sdpa_chunk_fwd");
+    ASR_CHECK_LAUNCH(name);
     return ASR_OK;
 }
 
-extern "C" size_t asr_sdpa_chunk_bwd_workspace_bytes(int B, int H, int Tq, int Tk, int dk, int chunk, int left_chunks, int dtype) {
+// single-pass band kernel: bf16 MFMA shapes, self-attention (Tq == Tk) inside a +-window band (there is no chunk form of it), more keys than
+// one workgroup holds, and the band of a 32-query tile touches at most two 512-key blocks
+bool sdpa_band_shape(bool chunk, int Tq, int Tk, int dk, int causal, int window, int dtype) {
+    return !chunk && dtype == ASR_BF16 && dk == DK && Tq == Tk && Tk > FB_KEYS && !causal && window >= 0 && 2 * window + FB_QT <= FB_KEYS;
+}
+int sdpa_band_slots(int window) { return (2 * window + FB_QT - 1) / FB_QT + 2; }
+// scratch of the backward pass: row sums of dO o O, or the band kernel's dQ partials of the tiles on a key-block boundary
+size_t sdpa_bwd_workspace(bool chunk, int B, int H, int Tq, int Tk, int dk, int a, int b, int dtype) {
     if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0) return 0;
-    return (size_t)B * H * Tq * sizeof(float);      // row sums of dO o O (no band form under a chunk mask)
+    const size_t rows = (size_t)B * H * Tq * sizeof(float);
+    const size_t halo = sdpa_band_shape(chunk, Tq, Tk, dk, a, b, dtype) ? (size_t)B * H * (ceil_div(Tk, FB_KEYS) - 1) * 2 * sdpa_band_slots(b) * FB_QT * DK * sizeof(float) : 0;
+    return halo > rows ? halo : rows;
+}
+// the one-workgroup kernel keeps an image of V for the delta pass of heads of at most 64 keys where it is masked, without dropout or chunks: more LDS in that launch
+template <bool DROP, bool MASKED, bool CHUNK> constexpr int fb_vimg = !DROP && MASKED && !CHUNK ? FB_VIMG_BYTES : 0;
+
+template <bool CHUNK>
+int sdpa_bwd(const char* name, const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, float* delta, size_t delta_bytes,
+             void* dq, void* dk_, void* dv, const int32_t* k_len, int B, int H, int Tq, int Tk, int dk, int ldq, int ldk, int ldv, int ldo,
+             int a, int b, float scale, float drop_p, uint32_t dseed, const void* o_lo, int dtype, void* stream) {
+    if (!q || !k || !v || !o || !d_o || !lse || !delta || !dq || !dk_ || !dv) ASR_FAIL(ASR_EINVAL, "%s: null pointer", name);
+    if (int rc = check_common(name, B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, o_lo, dtype)) return rc;
+    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "%s: dtype %d", name, dtype);
+    if (delta_bytes < (size_t)B * H * Tq * sizeof(float)) ASR_FAIL(ASR_EWORKSPACE, "%s: scratch of %zu bytes, need at least B*H*Tq floats = %zu", name, delta_bytes, (size_t)B * H * Tq * sizeof(float));
+    if (drop_p < 0.f || drop_p >= 1.f) ASR_FAIL(ASR_EINVAL, "%s: bad dropout p=%f", name, drop_p);
+    if (CHUNK) chunk_clamp(Tq, Tk, a, b);
+    const uint32_t dthr = drop_thr16(drop_p);
+    const float dscale = 1.f / (1.f - drop_p);
+    hipStream_t st = (hipStream_t)stream;
+    const bool mfma = dtype == ASR_BF16 && mfma_ok(dk, ldq, ldk, ldv, ldo, q, k, v, d_o) && mfma_ok(dk, ldq, ldk, ldv, ldo, dq, dk_, dv, o);
+    const bf16_t *qb = (const bf16_t*)q, *kb = (const bf16_t*)k, *vb = (const bf16_t*)v, *ob = (const bf16_t*)o, *dob = (const bf16_t*)d_o, *lob = (const bf16_t*)o_lo;
+    bf16_t *dqb = (bf16_t*)dq, *dkb = (bf16_t*)dk_, *dvb = (bf16_t*)dv;
+    if (!mfma) with_bools([&](auto f32) {      // the MFMA kernels compute delta themselves (an o_lo comes with bf16 only: check_common)
+        using T = std::conditional_t<f32, float, bf16_t>;
+        sdpa_delta_kernel<T><<<ceil_div(B * Tq * H, 32), 256, 0, st>>>((const T*)o, (const T*)o_lo, (const T*)d_o, delta, B, H, Tq, dk, ldo);
+    }, dtype == ASR_F32);
+    if (mfma && Tk <= FB_KEYS) {      // every key of a head fits one workgroup: single-pass backward, which reads no o_lo
+        static const bool lds_allowed = each_bools<2>([](auto drop, auto masked) {
+            if constexpr (masked || !CHUNK) allow_lds(sdpa_bwd_fused_bf16_kernel<drop, masked, false, CHUNK>, FB_LDS + fb_vimg<drop, masked, CHUNK>);
+        });
+        // the only kernel of this path, and the only launch of this file that may carry an armed completion event (asr_stream_arm)
+        with_bools([&](auto drop, auto masked) {
+            if constexpr (masked || !CHUNK)
+                asr_launch_armed(sdpa_bwd_fused_bf16_kernel<drop, masked, false, CHUNK>, dim3(B * H), dim3(FB_THREADS), FB_LDS + (Tk <= 64 ? fb_vimg<drop, masked, CHUNK> : 0), st, qb, kb, vb, dob, ob,
+                                 (const bf16_t*)nullptr, lse, dqb, dkb, dvb, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, a, b, scale, dseed, dthr, dscale, (float*)nullptr, 0);
+        }, dthr != 0, CHUNK || a || b >= 0);
+    } else if (mfma && sdpa_band_shape(CHUNK, Tq, Tk, dk, a, b, dtype) && delta_bytes >= sdpa_bwd_workspace(CHUNK, B, H, Tq, Tk, dk, a, b, dtype) && ((uintptr_t)delta % 16) == 0) {
+        // long-form band: one workgroup per (b, h, 512-key block), single pass; the halo kernel adds dQ of the tiles on a block boundary from fp32 slabs in the scratch
+        static const bool lds_allowed = each_bools<1>([](auto drop) { allow_lds(sdpa_bwd_fused_bf16_kernel<drop, true, true>, FB_LDS); });
+        const int nblk = ceil_div(Tk, FB_KEYS), slots = sdpa_band_slots(b);
+        with_bools([&](auto drop) {
+            sdpa_bwd_fused_bf16_kernel<drop, true, true><<<dim3(B * H, nblk), FB_THREADS, FB_LDS, st>>>(qb, kb, vb, dob, ob, lob, lse, dqb, dkb, dvb, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, a, b, scale, dseed, dthr, dscale, delta, slots);
+        }, dthr != 0);
+        sdpa_band_halo_kernel<<<dim3(slots, nblk - 1, B * H), 256, 0, st>>>(delta, dqb, H, Tq, Tk, ldq, b, slots);
+    } else if (mfma) {      // the dQ + dK/dV pair: 128 queries, 128 keys per workgroup
+        with_bools([&](auto drop) {
+            sdpa_bwd_dq_bf16_kernel<drop, CHUNK><<<ceil_div(Tq, 128) * H * B, 256, 0, st>>>(qb, kb, vb, dob, ob, lob, lse, delta, dqb, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, a, b, scale, dseed, dthr, dscale);
+            sdpa_bwd_dkv_bf16_kernel<drop, CHUNK><<<ceil_div(Tk, 128) * H * B, 256, 0, st>>>(qb, kb, vb, dob, lse, delta, dkb, dvb, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, a, b, scale, dseed, dthr, dscale);
+        }, dthr != 0);
+    } else {
+        const size_t l1 = (size_t)(Tk + 2 * dk) * sizeof(float), l2 = (size_t)(2 * Tq + 2 * dk) * sizeof(float);
+        if (l1 > 64 * 1024 || l2 > 64 * 1024) ASR_FAIL(ASR_EINVAL, "%s: generic path sequence too long for LDS", name);
+        with_bools([&](auto f32) {
+            using T = std::conditional_t<f32, float, bf16_t>;
+            sdpa_bwd_dq_generic_kernel<T, CHUNK><<<dim3(Tq, H, B), 64, l1, st>>>((const T*)q, (const T*)k, (const T*)v, (const T*)d_o, lse, delta, (T*)dq, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, a, b, scale, dseed, dthr, dscale);
+            sdpa_bwd_dkv_generic_kernel<T, CHUNK><<<dim3(Tk, H, B), 64, l2, st>>>((const T*)q, (const T*)k, (const T*)v, (const T*)d_o, lse, delta, (T*)dk_, (T*)dv, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, a, b, scale, dseed, dthr, dscale);
+        }, dtype == ASR_F32);
+    }
+    ASR_CHECK_LAUNCH(name);
+    return ASR_OK;
+}
+}  // namespace
+
+extern "C" int asr_sdpa_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* k_len, int B, int H, int Tq, int Tk, int dk,
+                            int ldq, int ldk, int ldv, int ldo, int causal, int window, float scale, float drop_p, uint32_t dseed, void* o_lo,
+                            int dtype, void* stream) {
+    return sdpa_fwd<false>("asr_sdpa_fwd", q, k, v, o, lse, k_len, B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, causal, window, scale, drop_p, dseed, o_lo, dtype, stream);
+}
+extern "C" size_t asr_sdpa_bwd_workspace_bytes(int B, int H, int Tq, int Tk, int dk, int causal, int window, int dtype) {
+    return sdpa_bwd_workspace(false, B, H, Tq, Tk, dk, causal, window, dtype);
+}
+extern "C" int asr_sdpa_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, float* delta, size_t delta_bytes,
+                            void* dq, void* dk_, void* dv, const int32_t* k_len, int B, int H, int Tq, int Tk, int dk, int ldq, int ldk, int ldv, int ldo,
+                            int causal, int window, float scale, float drop_p, uint32_t dseed, const void* o_lo, int dtype, void* stream) {
+    return sdpa_bwd<false>("asr_sdpa_bwd", q, k, v, o, d_o, lse, delta, delta_bytes, dq, dk_, dv, k_len, B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, causal, window, scale, drop_p, dseed, o_lo, dtype, stream);
 }
 
+// chunk-masked attention: a bad chunk mask is reported before anything else; the launchers clamp a good one once they have checked the shape
+extern "C" int asr_sdpa_chunk_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* k_len, int B, int H, int Tq, int Tk, int dk,
+                                  int ldq, int ldk, int ldv, int ldo, int chunk, int left_chunks, float scale, float drop_p, uint32_t dseed, void* o_lo,
+                                  int dtype, void* stream) {
+    if (int rc = chunk_check("asr_sdpa_chunk_fwd", chunk, left_chunks)) return rc;
+    return sdpa_fwd<true>("asr_sdpa_chunk_fwd", q, k, v, o, lse, k_len, B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, chunk, left_chunks, scale, drop_p, dseed, o_lo, dtype, stream);
+}
+extern "C" size_t asr_sdpa_chunk_bwd_workspace_bytes(int B, int H, int Tq, int Tk, int dk, int chunk, int left_chunks, int dtype) {
+    return sdpa_bwd_workspace(true, B, H, Tq, Tk, dk, chunk, left_chunks, dtype);
+}
 extern "C" int asr_sdpa_chunk_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, float* delta, size_t delta_bytes,
                                   void* dq, void* dk_, void* dv, const int32_t* k_len, int B, int H, int Tq, int Tk, int dk, int ldq, int ldk, int ldv, int ldo,
                                   int chunk, int left_chunks, float scale, float drop_p, uint32_t dseed, const void* o_lo, int dtype, void* stream) {
     if (int rc = chunk_check("asr_sdpa_chunk_bwd", chunk, left_chunks)) return rc;
-    if (!q || !k || !v || !o || !d_o || !lse || !delta || !dq || !dk_ || !dv) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_bwd: null pointer");
-    if (o_lo && (dtype != ASR_BF16 || ((uintptr_t)o_lo % 16) != 0)) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_bwd: o_lo is the low-order piece of a bf16 output (16-byte aligned, the layout of o)");
-    if (int rc = check_common("asr_sdpa_chunk_bwd", B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo)) return rc;
-    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "asr_sdpa_chunk_bwd: dtype %d", dtype);
-    if (delta_bytes < (size_t)B * H * Tq * sizeof(float)) ASR_FAIL(ASR_EWORKSPACE, "asr_sdpa_chunk_bwd: scratch of %zu bytes, need at least B*H*Tq floats = %zu", delta_bytes, (size_t)B * H * Tq * sizeof(float));
-    if (drop_p < 0.f || drop_p >= 1.f) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_bwd: bad dropout p=%f", drop_p);
-    int C = chunk, left = left_chunks;
-    chunk_clamp(Tq, Tk, C, left);
-    const uint32_t dthr = drop_thr16(drop_p);
-    const float dscale = 1.f / (1.f - drop_p);
-    hipStream_t st = (hipStream_t)stream;
-    const int ngroups = B * Tq * H;
-    const bool mfma = dtype == ASR_BF16 && mfma_ok(dk, ldq, ldk, ldv, ldo, q, k, v, d_o) && mfma_ok(dk, ldq, ldk, ldv, ldo, dq, dk_, dv, o);
-    if (!mfma) {
-        if (dtype == ASR_F32) sdpa_delta_kernel<float><<<ceil_div(ngroups, 32), 256, 0, st>>>((const float*)o, (const float*)nullptr, (const float*)d_o, delta, B, H, Tq, dk, ldo);
-        else sdpa_delta_kernel<bf16_t><<<ceil_div(ngroups, 32), 256, 0, st>>>((const bf16_t*)o, (const bf16_t*)o_lo, (const bf16_t*)d_o, delta, B, H, Tq, dk, ldo);
-    }
-    if (mfma && Tk <= FB_KEYS) {
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)sdpa_bwd_fused_bf16_kernel<false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
-            (void)hipFuncSetAttribute((const void*)sdpa_bwd_fused_bf16_kernel<true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
-            attr = true;
-        }
-#define FB_ARGS (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, (const bf16_t*)o, (const bf16_t*)nullptr, lse, (bf16_t*)dq, (bf16_t*)dk_, (bf16_t*)dv, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale
-        if (dthr) asr_launch_armed(sdpa_bwd_fused_bf16_kernel<true, true, false, true>, dim3(B * H), dim3(FB_THREADS), FB_LDS, st, FB_ARGS, (float*)nullptr, 0);
-        else asr_launch_armed(sdpa_bwd_fused_bf16_kernel<false, true, false, true>, dim3(B * H), dim3(FB_THREADS), FB_LDS, st, FB_ARGS, (float*)nullptr, 0);
-#undef FB_ARGS
-    } else if (mfma) {
-        const int gq = ceil_div(Tq, 128) * H * B, gk = ceil_div(Tk, 128) * H * B;
-#define SDPA_BWD(D)                                                                                                                                        \
-    do {                                                                                                                                                   \
-        sdpa_bwd_dq_bf16_kernel<D, true><<<gq, 256, 0, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, (const bf16_t*)o, (const bf16_t*)o_lo, lse, delta, \
-                                                              (bf16_t*)dq, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);           \
-        sdpa_bwd_dkv_bf16_kernel<D, true><<<gk, 256, 0, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, lse, delta, (bf16_t*)dk_, \
-                                                               (bf16_t*)dv, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);          \
-    } while (0)
-        if (dthr) SDPA_BWD(true);
-        else SDPA_BWD(false);
-#undef SDPA_BWD
-    } else {
-        dim3 gq(Tq, H, B), gk(Tk, H, B);
-        const size_t l1 = (size_t)(Tk + 2 * dk) * sizeof(float), l2 = (size_t)(2 * Tq + 2 * dk) * sizeof(float);
-        if (l1 > 64 * 1024 || l2 > 64 * 1024) ASR_FAIL(ASR_EINVAL, "asr_sdpa_chunk_bwd: generic path sequence too long for LDS");
-        if (dtype == ASR_F32) {
-            sdpa_bwd_dq_generic_kernel<float, true><<<gq, 64, l1, st>>>((const float*)q, (const float*)k, (const float*)v, (const float*)d_o, lse, delta, (float*)dq, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);
-            sdpa_bwd_dkv_generic_kernel<float, true><<<gk, 64, l2, st>>>((const float*)q, (const float*)k, (const float*)v, (const float*)d_o, lse, delta, (float*)dk_, (float*)dv, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);
-        } else {
-            sdpa_bwd_dq_generic_kernel<bf16_t, true><<<gq, 64, l1, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, lse, delta, (bf16_t*)dq, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);
-            sdpa_bwd_dkv_generic_kernel<bf16_t, true><<<gk, 64, l2, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, lse, delta, (bf16_t*)dk_, (bf16_t*)dv, k_len, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, C, left, scale, dseed, dthr, dscale);
-        }
-    }
-    ASR_CHECK_LAUNCH("asr_sdpa_chunk_bwd");
-    return ASR_OK;
+    return sdpa_bwd<true>("asr_sdpa_chunk_bwd", q, k, v, o, d_o, lse, delta, delta_bytes, dq, dk_, dv, k_len, B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, chunk, left_chunks, scale, drop_p, dseed, o_lo, dtype, stream);
 }

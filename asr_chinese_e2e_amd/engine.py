@@ -826,8 +826,9 @@ class Engine:
                 lin.wgrad(dy, x, with_bias=fused)
         self._keep += (dy, x)      # also while capturing (see flush_wgrads)
 
-    def _attn_block_fwd(self, m, x, kv_src, B, Tq, Tk, k_len, q_lens, causal, window, cross, site, kv_pre=None, kv_rows=None, chunk=0, left_chunks=-1):
-        """x: (B*Tq, d) queries + residual; kv_src: (B*Tk, d).  chunk > 0: chunk-masked self-attention (asr_sdpa_chunk_fwd).  kv_rows: cross attention over compact key rows (cross_rows) - kv_src holds
+    def _attn_block_fwd(self, m, x, kv_src, B, Tq, Tk, k_len, q_lens, mask, cross, site, kv_pre=None, kv_rows=None):
+        """x: (B*Tq, d) queries + residual; kv_src: (B*Tk, d).  mask: the mask keywords of K.sdpa_fwd / sdpa_bwd beyond k_len, as a dict
+        (causal=, window=, or chunk= and left_chunks=).  kv_rows: cross attention over compact key rows (cross_rows) - kv_src holds
         the first Tk of kv_rows encoder frames per utterance, and the backward pass scatters its gradient back into them.  Returns output
         and cache."""
         H, dk, hd = self.H, self.dk, self.H * self.dk
@@ -851,14 +852,11 @@ class Engine:
         # its bf16 output for the backward pass's delta (asr_hip.h: asr_sdpa_fwd's o_lo) - the band form of the backward kernel and the two-kernel path
         # hold no head-wide mean for the remedies of the one-workgroup form (centred keys, dK's mean removed: sdpa.hip)
         ctx_lo = torch.empty(B * Tq, hd, dtype=q.dtype, device=q.device) if (Tk > 512 and q.dtype == torch.bfloat16 and torch.is_grad_enabled()) else None
-        if chunk > 0:
-            ctx, lse = K.sdpa_fwd(q, k, v, k_len, B, H, Tq, Tk, dk, drop_p=pa, drop_seed=sa, o_lo=ctx_lo, chunk=chunk, left_chunks=left_chunks)
-        else:
-            ctx, lse = K.sdpa_fwd(q, k, v, k_len, B, H, Tq, Tk, dk, causal, window, drop_p=pa, drop_seed=sa, o_lo=ctx_lo)
+        ctx, lse = K.sdpa_fwd(q, k, v, k_len, B, H, Tq, Tk, dk, drop_p=pa, drop_seed=sa, o_lo=ctx_lo, **mask)
         a = m.fc.fwd(ctx)
         y, xhat, rstd = K.add_ln_fwd(a, x, m.ln.g, m.ln.b, None, q_lens, B, Tq, xhat=a, drop_p=pf, drop_seed=sf, drop_mode=1)
-        c.update(x=x, kv_src=kv_src, ctx=ctx, ctx_lo=ctx_lo, lse=lse, xhat=xhat, rstd=rstd, k_len=k_len, q_lens=q_lens, dims=(B, Tq, Tk), causal=causal,
-                 window=window, cross=cross, drop=(pa, sa, pf, sf), kv_rows=kv_rows, chunk=chunk, left_chunks=left_chunks)
+        c.update(x=x, kv_src=kv_src, ctx=ctx, ctx_lo=ctx_lo, lse=lse, xhat=xhat, rstd=rstd, k_len=k_len, q_lens=q_lens, dims=(B, Tq, Tk), mask=mask,
+                 cross=cross, drop=(pa, sa, pf, sf), kv_rows=kv_rows)
         return y, c
 
     def _attn_block_bwd(self, m, c, dy, dy2, d_kv_src=None):
@@ -882,13 +880,8 @@ class Engine:
             self._release_deferred()      # before the attention launch (after it: 3.59 vs 3.50 ms)
             self._disarm()      # nothing was released: the arm must not leak into the attention kernel's launch
             self._arm()
-            if c["chunk"] > 0:
-                K.sdpa_bwd(qkv[:, :hd], qkv[:, hd:2 * hd], qkv[:, 2 * hd:], c["ctx"], dctx, c["lse"], c["k_len"], B, H, Tq, Tk, dk,
-                           dqkv[:, :hd], dqkv[:, hd:2 * hd], dqkv[:, 2 * hd:], drop_p=pa, drop_seed=sa, o_lo=c["ctx_lo"],
-                           chunk=c["chunk"], left_chunks=c["left_chunks"])
-            else:
-                K.sdpa_bwd(qkv[:, :hd], qkv[:, hd:2 * hd], qkv[:, 2 * hd:], c["ctx"], dctx, c["lse"], c["k_len"], B, H, Tq, Tk, dk,
-                           dqkv[:, :hd], dqkv[:, hd:2 * hd], dqkv[:, 2 * hd:], c["causal"], c["window"], drop_p=pa, drop_seed=sa, o_lo=c["ctx_lo"])
+            K.sdpa_bwd(qkv[:, :hd], qkv[:, hd:2 * hd], qkv[:, 2 * hd:], c["ctx"], dctx, c["lse"], c["k_len"], B, H, Tq, Tk, dk,
+                       dqkv[:, :hd], dqkv[:, hd:2 * hd], dqkv[:, 2 * hd:], drop_p=pa, drop_seed=sa, o_lo=c["ctx_lo"], **c["mask"])
             self._wgrad(m.qkv, dqkv, c["x"], bias_from=dqkv)
             dx = m.qkv.dgrad(dqkv)
         else:
@@ -896,7 +889,7 @@ class Engine:
             dq = torch.empty_like(q)
             dkv = torch.empty_like(kv)
             K.sdpa_bwd(q, kv[:, :hd], kv[:, hd:], c["ctx"], dctx, c["lse"], c["k_len"], B, H, Tq, Tk, dk, dq, dkv[:, :hd], dkv[:, hd:],
-                       c["causal"], c["window"], drop_p=pa, drop_seed=sa, o_lo=c["ctx_lo"])
+                       drop_p=pa, drop_seed=sa, o_lo=c["ctx_lo"], **c["mask"])
             self._wgrad(m.q, dq, c["x"], bias_from=dq)
             self._wgrad(m.kv, dkv, c["kv_src"], bias_from=dkv)
             dx = m.q.dgrad(dq)
@@ -967,8 +960,9 @@ class Engine:
         p0, s0 = self._drop(1)             # dropout(LN(linear_in(x)) + PE)  (transformer_official.py:175-177)
         h, xhat, rstd = K.add_ln_fwd(e0, None, self.ln_in.g, self.ln_in.b, self.pe, None, B, T, xhat=e0, drop_p=p0, drop_seed=s0, drop_mode=2)
         cache = dict(x_in=x_in, xhat_in=xhat, rstd_in=rstd, B=B, T=T, layers=[], drop=(p0, s0))
+        mask = dict(chunk=chunk, left_chunks=left_chunks) if chunk > 0 else dict(window=window)
         for i, (mha, ffn) in enumerate(self.enc):
-            h1, c1 = self._attn_block_fwd(mha, h, h, B, T, T, wave_len, wave_len, False, window, False, site=10 + 4 * i, chunk=chunk, left_chunks=left_chunks)
+            h1, c1 = self._attn_block_fwd(mha, h, h, B, T, T, wave_len, wave_len, mask, cross=False, site=10 + 4 * i)
             h, c2 = self._ffn_block_fwd(ffn, h1, B, T, wave_len, site=12 + 4 * i)
             cache["layers"].append((c1, c2))
         return h, cache
@@ -1299,8 +1293,8 @@ class Engine:
             self._keep += (enc, src)
             self._keep += [kv for kv, _ in kv_pre]      # blocks of the auxiliary stream's pool, read on the main stream
         for i, (slf, cross, ffn) in enumerate(self.dec):
-            x1, c1 = self._attn_block_fwd(slf, x, x, B, To, To, dec_len, dec_len, True, -1, False, site=100 + 8 * i)
-            x2, c2 = self._attn_block_fwd(cross, x1, src, B, To, Tk, cross_len, dec_len, False, -1, True, site=102 + 8 * i, kv_pre=kv_pre[i], kv_rows=kv_rows)
+            x1, c1 = self._attn_block_fwd(slf, x, x, B, To, To, dec_len, dec_len, dict(causal=True), cross=False, site=100 + 8 * i)
+            x2, c2 = self._attn_block_fwd(cross, x1, src, B, To, Tk, cross_len, dec_len, {}, cross=True, site=102 + 8 * i, kv_pre=kv_pre[i], kv_rows=kv_rows)
             x, c3 = self._ffn_block_fwd(ffn, x2, B, To, dec_len, site=104 + 8 * i)
             cache["layers"].append((c1, c2, c3))
         pred = self.prj.fwd(x)

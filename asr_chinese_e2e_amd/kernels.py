@@ -231,6 +231,22 @@ def _strided_rows(t, H, dk):
     return t.stride(0)
 
 
+def _sdpa_entries(name):
+    return (getattr(lib, name + "_fwd"), name + "_fwd"), (getattr(lib, name + "_bwd"), name + "_bwd"), getattr(lib, name + "_bwd_workspace_bytes")
+
+
+_SDPA_PLAIN, _SDPA_CHUNK = _sdpa_entries("asr_sdpa"), _sdpa_entries("asr_sdpa_chunk")
+
+
+def _sdpa_mask(causal, window, chunk, left_chunks):
+    """The entry points of a mask and the two integers they take for it: ((fwd, its name), (bwd, its name), workspace_bytes, a, b).
+    chunk > 0 is the chunk mask of asr_sdpa_chunk_*, which replaces causal / window."""
+    if chunk > 0:
+        assert not causal and window < 0, "a chunk mask replaces causal / window"
+        return *_SDPA_CHUNK, int(chunk), int(left_chunks)
+    return *_SDPA_PLAIN, int(causal), int(window)
+
+
 def sdpa_fwd(q, k, v, k_len, B, H, Tq, Tk, dk, causal=False, window=-1, scale=None, o=None, lse=None, drop_p=0.0, drop_seed=0, o_lo=None,
              chunk=0, left_chunks=-1):
     """q: (B*Tq, H*dk) view, k/v: (B*Tk, H*dk) views (may be column slices of a fused buffer).
@@ -248,16 +264,10 @@ def sdpa_fwd(q, k, v, k_len, B, H, Tq, Tk, dk, causal=False, window=-1, scale=No
     assert o_lo is None or (o_lo.dtype == o.dtype == torch.bfloat16 and o_lo.shape == o.shape and o_lo.stride() == o.stride())
     scale = float(dk) ** -0.5 if scale is None else float(scale)
     e = q.element_size()
-    if chunk > 0:
-        assert not causal and window < 0, "a chunk mask replaces causal / window"
-        timed("sdpa_fwd", 4.0 * B * H * Tq * Tk * dk, lambda: check(
-            lib.asr_sdpa_chunk_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(k_len), B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo,
-                                   int(chunk), int(left_chunks), scale, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _p(o_lo), _dt(q), _stream()),
-            "asr_sdpa_chunk_fwd"), 2.0 * B * H * (Tq + Tk) * dk * e)
-        return o, lse
+    (fwd, name), _, _, a, b = _sdpa_mask(causal, window, chunk, left_chunks)
     timed("sdpa_fwd", 4.0 * B * H * Tq * Tk * dk, lambda: check(
-        lib.asr_sdpa_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(k_len), B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo,
-                         int(causal), int(window), scale, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _p(o_lo), _dt(q), _stream()), "asr_sdpa_fwd"),
+        fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(k_len), B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo,
+            a, b, scale, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _p(o_lo), _dt(q), _stream()), name),
           2.0 * B * H * (Tq + Tk) * dk * e)          # Q, O + K, V (4 B H T dk e at Tq = Tk)
     return o, lse
 
@@ -271,28 +281,16 @@ def sdpa_bwd(q, k, v, o, do, lse, k_len, B, H, Tq, Tk, dk, dq, dk_, dv, causal=F
     _chk_i32(k_len)
     _chk_f32(lse)
     assert o_lo is None or (o_lo.dtype == o.dtype == torch.bfloat16 and o_lo.shape == o.shape and o_lo.stride() == o.stride())
-    if chunk > 0:
-        assert not causal and window < 0, "a chunk mask replaces causal / window"
-        if delta is None:
-            need = lib.asr_sdpa_chunk_bwd_workspace_bytes(B, H, Tq, Tk, dk, int(chunk), int(left_chunks), _dt(q))
-            delta = torch.empty((need + 3) // 4, dtype=torch.float32, device=q.device)
-        scale = float(dk) ** -0.5 if scale is None else float(scale)
-        e = q.element_size()
-        timed("sdpa_bwd", 10.0 * B * H * Tq * Tk * dk, lambda: check(
-            lib.asr_sdpa_chunk_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), delta.numel() * 4, _p(dq), _p(dk_), _p(dv), _p(k_len),
-                                   B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, int(chunk), int(left_chunks), scale, float(drop_p),
-                                   int(drop_seed) & 0xFFFFFFFF, _p(o_lo), _dt(q), _stream()), "asr_sdpa_chunk_bwd"),
-              B * H * (4.0 * Tq + 4.0 * Tk) * dk * e)
-        return dq, dk_, dv
+    _, (bwd, name), workspace_bytes, a, b = _sdpa_mask(causal, window, chunk, left_chunks)
     if delta is None:      # scratch: row sums of dO o O, or the band kernel's dQ partials of the tiles on a key-block boundary
-        need = lib.asr_sdpa_bwd_workspace_bytes(B, H, Tq, Tk, dk, int(causal), int(window), _dt(q))
+        need = workspace_bytes(B, H, Tq, Tk, dk, a, b, _dt(q))
         delta = torch.empty((need + 3) // 4, dtype=torch.float32, device=q.device)
     scale = float(dk) ** -0.5 if scale is None else float(scale)
     e = q.element_size()
     timed("sdpa_bwd", 10.0 * B * H * Tq * Tk * dk, lambda: check(
-        lib.asr_sdpa_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), delta.numel() * 4, _p(dq), _p(dk_), _p(dv), _p(k_len),
-                         B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, int(causal), int(window), scale, float(drop_p),
-                         int(drop_seed) & 0xFFFFFFFF, _p(o_lo), _dt(q), _stream()), "asr_sdpa_bwd"),
+        bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), delta.numel() * 4, _p(dq), _p(dk_), _p(dv), _p(k_len),
+            B, H, Tq, Tk, dk, ldq, ldk, ldv, ldo, a, b, scale, float(drop_p),
+            int(drop_seed) & 0xFFFFFFFF, _p(o_lo), _dt(q), _stream()), name),
           B * H * (4.0 * Tq + 4.0 * Tk) * dk * e)    # Q, O, dO, dQ + K, V, dK, dV (8 x 16.4 MB at config 2); 5 products
     return dq, dk_, dv
 
