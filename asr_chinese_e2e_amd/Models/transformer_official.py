@@ -367,39 +367,20 @@ class _SpeechTransformer(BaseModel):
 
     CER_BESIDE_BACKWARD = True      # False: score the step's CER on the main stream behind the optimizer (A/B, tests)
 
-    def _cer_beside_backward(self, eng, pg):
-        """The per-step CER of the greedy ids (five small launches, ~65 us behind the optimizer on the main stream: 1.3 % of the joint step) on
-        the auxiliary stream instead, which is idle once the decoder's backward pass has joined it: it runs beside the encoder's backward pass,
-        and iterate() makes the main stream wait for its event before handing the metric out.  Returns (cer, event); the ids stay referenced by
-        the model until the next step (blocks of the main stream's pool read on another stream)."""
-        if not (self.CER_BESIDE_BACKWARD and eng.aux_overlap) or torch.cuda.is_current_stream_capturing():
-            return pg
-        eng._disarm()      # this fork is for the auxiliary stream: it must not consume a hand-over meant for the weight-gradient stream
-        eng._fork(eng.ctc_stream)
-        with torch.cuda.stream(eng.ctc_stream):
-            cer = self._cer_ids(pg[0], pg[1])
+    def _cer_beside_backward(self, eng, score, keep, inline):
+        """The per-step CER (five small launches, ~65 us behind the optimizer on the main stream: 1.3 % of the joint step) on the auxiliary
+        stream instead, which is idle once the decoder's backward pass has joined it: it runs beside the encoder's backward pass, and iterate()
+        makes the main stream wait for its event before handing the metric out.  score: closure that returns the CER tensor; keep: what it
+        reads (blocks of the main stream's pool read on another stream), referenced by the model until the next step.  Returns (cer, event),
+        or inline() when the step runs on one stream (or is being captured): what _cer_of takes for a score on the main stream."""
+        if not (self.CER_BESIDE_BACKWARD and eng._aux_active()):
+            return inline()
         if getattr(self, "_cer_event", None) is None:
             self._cer_event = torch.cuda.Event()
-        self._cer_event.record(eng.ctc_stream)
-        self._cer_keep = pg
-        return cer, self._cer_event
-
-    def _ctc_cer_beside_backward(self, eng, path, wave_len, labels32, lab_len):
-        """CTC-only model: collapse the greedy path and score it against the label strings (as cal_metrics does for a CTC-only model), on the
-        auxiliary stream beside the encoder's backward pass when the step runs on several streams.  Returns what _cer_of takes."""
-        def score():
-            ids, lens = K.ctc_collapse(path, wave_len, PAD_ID)
-            return self._cer_ids(ids, labels32, hyp_len=lens, ref_len=lab_len)
-        if not (self.CER_BESIDE_BACKWARD and eng.aux_overlap) or torch.cuda.is_current_stream_capturing():
-            return score(), None
-        eng._disarm()
-        eng._fork(eng.ctc_stream)
-        with torch.cuda.stream(eng.ctc_stream):
+        # disarm: this fork is for the auxiliary stream, it must not consume a hand-over meant for the weight-gradient stream
+        with E._OnAux(eng, event=self._cer_event, disarm=True):
             cer = score()
-        if getattr(self, "_cer_event", None) is None:
-            self._cer_event = torch.cuda.Event()
-        self._cer_event.record(eng.ctc_stream)
-        self._cer_keep = (path, wave_len, labels32, lab_len)      # blocks of the main stream's pool read on another stream: alive until the next step
+        self._cer_keep = keep
         return cer, self._cer_event
 
     def _cer_of(self, pg):
@@ -610,7 +591,7 @@ class _SpeechTransformer(BaseModel):
         pg = None
         ctc_done = None
         ctc_scale = dict(grad_scale=lam * loss_scale, grad_scale_div=batch_div) if batch_div is not None else dict(grad_scale=lam * loss_scale / float(B))
-        ctc_async = (self.use_decoder and self.use_ctc and eng.overlap_ctc and not eng.deterministic and not torch.cuda.is_current_stream_capturing())
+        ctc_async = (self.use_decoder and self.use_ctc and eng._aux_active() and not eng.deterministic)
         if self.use_decoder:
             cross_len, Tk = self._cross(eng, input, wave_len, T)
         if ctc_async:      # joint model: the CTC branch runs beside the decoder's forward pass
@@ -630,14 +611,17 @@ class _SpeechTransformer(BaseModel):
             # greedy CTC path, which the loss kernels hand out (the gradient overwrites the logits in place)
             path = torch.empty(B, T, dtype=torch.int32, device=enc.device) if (self.cer_in_iterate and not self.use_decoder) else None
             nll, d_enc = eng.ctc_fwd_bwd(enc, wave_len, labels32, lab_len, B, T, best_path=path, **ctc_scale)
-            if path is not None:
-                pg = self._ctc_cer_beside_backward(eng, path, wave_len, labels32, lab_len)
+            if path is not None:      # collapse the greedy path and score it against the label strings, as cal_metrics does for a CTC-only model
+                def score():
+                    ids, lens = K.ctc_collapse(path, wave_len, PAD_ID)
+                    return self._cer_ids(ids, labels32, hyp_len=lens, ref_len=lab_len)
+                pg = self._cer_beside_backward(eng, score, (path, wave_len, labels32, lab_len), inline=lambda: (score(), None))
         if self.use_decoder:
             if d_enc is None:
                 d_enc = torch.zeros_like(enc)
             eng.decoder_bwd(dcache, dpred, d_enc, d_enc_ready=ctc_done)
             if pg is not None:
-                pg = self._cer_beside_backward(eng, pg)
+                pg = self._cer_beside_backward(eng, lambda: self._cer_ids(ids, ys_out), pg, inline=lambda: pg)      # inline: (ids, gold), scored by _cer_of
         eng.encoder_bwd(ecache, d_enc)
         loss = K.loss_combine(row_nll, n_valid, nll, (1.0 - lam) if self.use_ctc else 1.0, lam)
         return loss, pg

@@ -202,16 +202,18 @@ class Linear:
             out.copy_(res)
         return out
 
+    def own_wgrad(self, dy, x):
+        """True when the own weight-gradient kernel (asr_gemm_tn_bf16) takes (dy, x): bf16, widths and leading dimensions multiples of 8."""
+        return dy.dtype == torch.bfloat16 and self.N % 8 == 0 and self.K % 8 == 0 and dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0
+
     def fused_bias_wgrad(self, dy, x):
         """True when wgrad can also produce the bias gradient (MFMA weight-gradient kernel path)."""
-        return (self.gb is not None and dy.dtype == torch.bfloat16 and self.N % 8 == 0 and self.K % 8 == 0 and
-                dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0)
+        return self.gb is not None and self.own_wgrad(dy, x)
 
     def wgrad(self, dy, x, with_bias=False, ws=None):
         """gw += dy^T x  (fp32 accumulation into the flat gradient buffer); with_bias (only when
         fused_bias_wgrad): also gb += column sums of dy, inside the same kernel.  ws: scratch for the deterministic mode."""
-        M = x.shape[0]
-        if dy.dtype == torch.bfloat16 and self.N % 8 == 0 and self.K % 8 == 0 and dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0:
+        if self.own_wgrad(dy, x):
             K.gemm_tn(dy, x, self.gw, accumulate=True, dbias=self.gb if with_bias else None, ws=ws)
         elif dy.dtype == torch.bfloat16:      # odd shapes: through the fp32 kernel
             K.gemm_f32(dy.float(), x.float(), self.gw, trans_a=True, accumulate=True)
@@ -422,9 +424,6 @@ def shared_stream(device, kind):
     return _STREAMS[key]
 
 
-_shared_stream = shared_stream
-
-
 def registered_streams(device):
     """Every stream chosen so far for this device (weight-gradient, auxiliary, loader, ...): what a stream chosen later must run beside."""
     dev = torch.device(device)
@@ -438,14 +437,61 @@ def _side_stream(device):
     whenever both have workgroups pending (the LayerNorm backward ran 30 us beside them against 14 us alone).
     torch.cuda.Stream only offers normal / high, so the stream comes from asr_stream_create (the HIP runtime the library and
     torch share) and is wrapped as an ExternalStream (host plumbing; it lives as long as the process)."""
-    import ctypes
-    from . import _lib
     with torch.cuda.device(device):
         h = ctypes.c_void_p()
         # created inside libasr_hip.so, i.e. by the HIP runtime the kernels (and torch) are bound to: a second dlopen of
         # libamdhip64 by bare name could map another runtime whose stream handles mean nothing to this one
         _lib.check(_lib.lib.asr_stream_create(-1, ctypes.byref(h)), "asr_stream_create")
     return torch.cuda.ExternalStream(h.value, device=device)
+
+
+class _OnSide:
+    """`with _OnSide(engine._side_handle, cu_limit):` own kernels launched inside go to the weight-gradient stream (kernels.STREAM_OVERRIDE: a switch of torch's
+    current stream costs ~6 us of host time, 25 times per step), the large ones sized for cu_limit CUs (0 = all).  _fork(engine.side) is the caller's."""
+
+    def __init__(self, handle, cu_limit=0):
+        self.handle, self.cu_limit = handle, cu_limit
+
+    def __enter__(self):
+        if self.cu_limit:
+            K.set_cu_limit(self.cu_limit)
+        K.STREAM_OVERRIDE = self.handle
+
+    def __exit__(self, *exc):
+        K.STREAM_OVERRIDE = None
+        if self.cu_limit:
+            K.set_cu_limit(0)
+
+
+class _OnAux:
+    """`with _OnAux(engine, ...):` the block runs on the auxiliary stream, behind everything queued on the current stream so far: the fork first (_fork
+    takes its source from the current stream), then the switch of torch's current stream.  disarm: drop a pending arm first (else the fork consumes a
+    hand-over meant for the weight-gradient stream).  cu_limit: as _OnSide.  event: recorded on the auxiliary stream behind a block that did not raise."""
+
+    def __init__(self, eng, cu_limit=0, event=None, disarm=False):
+        self.eng, self.cu_limit, self.event, self.disarm = eng, cu_limit, event, disarm
+        self.ctx = torch.cuda.stream(eng.ctc_stream)
+
+    def __enter__(self):
+        if self.disarm:
+            self.eng._disarm()
+        self.eng._fork(self.eng.ctc_stream)
+        self.ctx.__enter__()
+        if self.cu_limit:      # last: what raises in here leaves nothing to undo but the stream switch
+            try:
+                K.set_cu_limit(self.cu_limit)
+            except BaseException:
+                self.ctx.__exit__(None, None, None)
+                raise
+
+    def __exit__(self, *exc):
+        try:
+            if self.cu_limit:
+                K.set_cu_limit(0)
+            if self.event is not None and exc[0] is None:
+                self.event.record(self.eng.ctc_stream)
+        finally:
+            self.ctx.__exit__(*exc)
 
 
 class Engine:
@@ -468,6 +514,7 @@ class Engine:
         self.ln_in = LayerNormP(flat, "encoder.layer_norm_in")
         self.enc = [(MHA(flat, f"encoder.layer_stack.{i}.slf_attn.", H, dk, d), FFN(flat, f"encoder.layer_stack.{i}.pos_ffn.", d, ff))
                     for i in range(self.L)]
+        self.dec = []
         if use_decoder:
             self.emb32 = flat.view(flat.p, "decoder.tgt_word_emb.weight")
             self.gemb = flat.view(flat.g, "decoder.tgt_word_emb.weight")
@@ -499,7 +546,7 @@ class Engine:
             # ... and the decoder's cross-attention K|V weights (one matrix for all layers): with key rows over all B*T encoder frames (cross_rows)
             # they multiply them in the accumulating input gradient d_enc += dK|dV W_kv (the residual-add store tail of the own kernel, no library
             # call); compact key rows use W as stored
-            cross_qkv = [self.kv_all] if getattr(self, "dec", None) else []
+            cross_qkv = [self.kv_all] if self.dec else []
             # ... and the CTC head (reduction over V = 4232 columns: the kernel's last k-step is ragged)
             head = [self.ctc_lo] if use_ctc else []
             lins = [l for l in lins + cross_qkv + head if l.N % 8 == 0 and l.K % 8 == 0]
@@ -517,7 +564,7 @@ class Engine:
                     dst_off, ldd = l.w_off, l.N
                     l.wlpT = flat.lpT[l.w_off:l.w_off + l.N * l.K].view(l.K, l.N)
                 tiles += [[l.w_off, l.N, l.K, (r << 16) | c, dst_off, ldd] for r in range((l.N + 63) // 64) for c in range((l.K + 63) // 64)]
-            for i, (_, cross, _) in enumerate(self.dec if getattr(self, "dec", None) else []):
+            for i, (_, cross, _) in enumerate(self.dec):
                 if self.kv_all.wlpT is not None:
                     cross.kv.wlpT = self.kv_all.wlpT[:, i * cross.kv.N:(i + 1) * cross.kv.N]      # (d, 2 H dk) view, row stride L 2 H dk
             self._tr_tiles = torch.tensor(tiles, dtype=torch.int32, device=flat.device)
@@ -526,13 +573,10 @@ class Engine:
         # Weight/bias gradients are off the critical path (only the optimizer reads them): they run
         # on a side stream, concurrently with the dgrad chain on the main stream, so the short,
         # latency-bound kernels of both chains fill each other's idle CUs.
-        # the CTC branch of the joint model runs on its own stream beside the decoder's forward pass (ctc_branch_async);
-        # off in deterministic mode (the weight gradients then share one scratch buffer on whatever stream is current)
-        self.side = _shared_stream(flat.device, "wgrad")      # first: the stream the step depends on most gets the first pick
-        self.ctc_stream = _shared_stream(flat.device, "aux")
+        self.side = shared_stream(flat.device, "wgrad")      # first: the stream the step depends on most gets the first pick
+        self.ctc_stream = shared_stream(flat.device, "aux")
         self.ws_ctc = K.Workspace(flat.device)
         self._side_handle = self.side.cuda_stream
-        self._events, self._ev_next = [torch.cuda.Event() for _ in range(64)], 0     # reused round-robin (a wait captures the record it follows)
         # ---- environment switches of the engine (all read here, when the engine is built; the complete list is in README.md):
         # ASR_WGRAD_OVERLAP=0: ONE stream - weight gradients, the CTC branch and the cross-attention K|V work stay on the main stream
         self.overlap_wgrad = os.environ.get("ASR_WGRAD_OVERLAP", "1") == "1"
@@ -546,7 +590,7 @@ class Engine:
         # the CTC branch of the joint model beside the decoder's forward pass (ctc_branch_async), and the cross-attention K|V projections /
         # their input gradients, on the auxiliary stream: with the weight-gradient overlap (off in deterministic mode: the weight gradients
         # then share one scratch buffer on whatever stream is current)
-        self.overlap_ctc = self.aux_overlap = self.overlap_wgrad
+        self.aux_overlap = self.overlap_wgrad
         # ASR_WGRAD_GROUP: "decoder" (default): the seven weight gradients of a DECODER layer (self-attention, cross
         # attention incl. the K|V projection of all encoder frames, feed-forward) go out as ONE grouped GEMM
         # (asr_gemm_tn_grouped_bf16) - the decoder's main stream is a chain of small launches (B*To rows) that
@@ -618,9 +662,15 @@ class Engine:
     # ------------------------------------------------------------------ helpers
     def _drop(self, site):
         """(p, seed) of a dropout site for the current step; p = 0 in eval mode."""
-        if not self.training or self.drop_p <= 0.0:
+        if not self._dropping():
             return 0.0, 0
         return self.drop_p, (self.step_seed * 0x9E3779B1 + site * 0x85EBCA77 + 0x165667B1) & 0xFFFFFFFF
+
+    def _dropping(self):
+        return self.training and self.drop_p > 0.0
+
+    def _aux_active(self):      # this step uses the auxiliary stream: several streams, and no graph being captured (nothing is forked to it then)
+        return self.aux_overlap and not torch.cuda.is_current_stream_capturing()
 
     def _ready(self, name):
         """Gradients at flat offsets >= this tensor's offset are final once the work queued so far
@@ -658,13 +708,6 @@ class Engine:
         """First tensor of the block that encoder_bwd marks final in the middle of layer 0 (see dist.DataParallel)."""
         return "encoder.layer_stack.0.pos_ffn.w_1.weight"
 
-    def _event(self):
-        if torch.cuda.is_current_stream_capturing():      # events recorded in a capture belong to that graph
-            return torch.cuda.Event()
-        ev = self._events[self._ev_next]
-        self._ev_next = (self._ev_next + 1) & 63
-        return ev
-
     def _arm(self):
         """The NEXT library entry point called on the current stream hands its output over to the weight-gradient stream by itself: its
         last kernel carries the completion event (asr_stream_arm), and the next _fork(self.side) is then a no-op.  Without it the
@@ -677,8 +720,8 @@ class Engine:
     def _disarm(self):
         """Drop an arm that no _fork(self.side) consumed right behind its producer.  If the producer's launch took it, the side stream
         merely waits for that kernel (harmless); what must not happen is that a LATER _fork finds `_armed` set and skips its event
-        although other main-stream kernels ran since (round-3 ADVICE: ASR_WGRAD_DEFER=w2 at B*T < 4096, ASR_WGRAD_GROUP=block with
-        ASR_FUSE_RELU_BWD=0 - the side stream then read a dY ordered only behind the armed kernel)."""
+        although other main-stream kernels ran since (round-3 ADVICE: ASR_WGRAD_DEFER=w2 at B*T < 4096, ASR_WGRAD_GROUP=block where the
+        ReLU backward is its own kernel - the side stream then read a dY ordered only behind the armed kernel)."""
         if self._armed:
             self._armed = False
             K.stream_arm_pending()
@@ -722,11 +765,8 @@ class Engine:
         if zero is not None:      # the step's gradient buffer, zeroed beside the forward pass (Models.zero_flat_grads); ordered by _tr_event below
             with torch.cuda.stream(self.side):
                 zero.zero_()
-        K.STREAM_OVERRIDE = self._side_handle
-        try:
+        with _OnSide(self._side_handle):
             K.transpose_batched(self.flat.lp, self.flat.lpT, self._tr_tiles)
-        finally:
-            K.STREAM_OVERRIDE = None
         self._tr_event.record(self.side)
         self._tr_pending = True
         self.flat.lpT_version = self.flat.version
@@ -754,16 +794,8 @@ class Engine:
             K.gemm_tn_grouped(probs, accumulate=True)
             return
         self._fork(self.side)
-        K.STREAM_OVERRIDE = self._side_handle
-        lim = self.dec_cu_limit if self._in_decoder else 0
-        try:
-            if lim:
-                K.set_cu_limit(lim)
+        with _OnSide(self._side_handle, self.dec_cu_limit if self._in_decoder else 0):
             K.gemm_tn_grouped(probs, accumulate=True)
-        finally:
-            K.STREAM_OVERRIDE = None
-            if lim:
-                K.set_cu_limit(0)
         # also while capturing: a graph's private pool DOES reuse a block freed earlier in the same capture, and without the mark a
         # replay overwrote dY / X tensors that the side stream's weight-gradient kernel had not read yet (round 3: gradients of the
         # replayed step differed from the eager step; tests/test_train_loop_gpu.py::test_graphed_step_matches_eager)
@@ -774,17 +806,16 @@ class Engine:
         """Launch the weight gradients held back by ASR_WGRAD_DEFER (see _wgrad)."""
         if self._deferred:
             items, self._deferred = self._deferred, []
-            hold, self.defer_wgrad = self.defer_wgrad, ""
-            try:
-                for lin, dy, x, bias_from in items:
-                    self._wgrad(lin, dy, x, bias_from)
-            finally:
-                self.defer_wgrad = hold
+            for item in items:
+                self._wgrad_issue(*item)
+
+    def _wgrad_held(self, lin):
+        """True when ASR_WGRAD_DEFER holds this projection's weight gradient back (_wgrad); one that goes out in a pair (ASR_WGRAD_GROUP=pair*) is not held."""
+        return not self._in_decoder and lin.tag in self.defer_wgrad and self.overlap_wgrad and lin.tag not in self._pair_tags
 
     def _wgrad(self, lin, dy, x, bias_from=None):
-        """lin.gw += dy^T x (and lin.gb += colsum(bias_from)) on the side stream."""
-        pair = self._pair_tags and not self._in_decoder and lin.tag in self._pair_tags
-        if self.defer_wgrad and self.overlap_wgrad and not self._in_decoder and lin.tag in self.defer_wgrad and not pair:
+        """lin.gw += dy^T x (and lin.gb += colsum(bias_from)) on the side stream (all but the input projection's, which encoder_bwd launches on the main stream)."""
+        if self._wgrad_held(lin):
             # ASR_WGRAD_DEFER (default "fc"): hold this projection's weight gradient until the layer's attention backward is
             # about to be launched.  For the out-projection that takes it from beside its own (short) dgrad GEMM to beside the
             # 83-us attention kernel: step 3.53 -> 3.50 ms.  Holding back any other projection (w1, w2, qkv) or releasing after
@@ -792,10 +823,14 @@ class Engine:
             self._deferred.append((lin, dy, x, bias_from))
             self._disarm()      # no fork here: the arm must not outlive its producer (a later _fork would skip its event)
             return
-        fused = bias_from is dy and lin.fused_bias_wgrad(dy, x)     # bias gradient inside the weight-gradient GEMM
+        self._wgrad_issue(lin, dy, x, bias_from)
+
+    def _wgrad_issue(self, lin, dy, x, bias_from):      # collect the weight gradient for the next grouped launch (flush_wgrads), or launch it now
+        pair = not self._in_decoder and lin.tag in self._pair_tags
+        own = lin.own_wgrad(dy, x)
+        fused = own and bias_from is dy and lin.gb is not None     # bias gradient inside the weight-gradient GEMM (Linear.fused_bias_wgrad)
         grouped_here = self.group_wgrad and (self._in_decoder or pair or self.group_wgrad in ("layer", "block"))      # ("decoder", "pair*": the decoder's layers)
-        if grouped_here and (bias_from is None or fused) and dy.dtype == torch.bfloat16 and lin.N % 8 == 0 and lin.K % 8 == 0 \
-                and dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0 and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0:
+        if grouped_here and (bias_from is None or fused) and own and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0:
             self._pending.append((dy, x, lin.gw, lin.gb if fused else None))     # launched by flush_wgrads (end of the layer)
             if pair and lin.tag in ("w1", "qkv"):
                 # the block's second weight gradient: its dY was written by the kernel launched last (the w_2 input gradient, the attention
@@ -805,26 +840,24 @@ class Engine:
                 self._disarm()
             return
         if not self.overlap_wgrad:
-            if bias_from is not None and not fused:
-                lin.bgrad(bias_from, self.ws_side)
-            lin.wgrad(dy, x, with_bias=fused, ws=self.ws_side)
+            self._wgrad_launch(lin, dy, x, bias_from, fused)
             return
         self._fork(self.side)
-        own = dy.dtype == torch.bfloat16 and lin.N % 8 == 0 and lin.K % 8 == 0 and dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0
-        if own:     # only own kernels run: hand them the side stream directly instead of switching torch's current stream
+        if own:     # only own kernels run: they take the side stream directly.  The bracket of _OnSide written out: ~25 times per step, host time counts
             K.STREAM_OVERRIDE = self._side_handle
             try:
-                if bias_from is not None and not fused:
-                    lin.bgrad(bias_from, self.ws_side)
-                lin.wgrad(dy, x, with_bias=fused, ws=self.ws_side)
+                self._wgrad_launch(lin, dy, x, bias_from, fused)
             finally:
                 K.STREAM_OVERRIDE = None
-        else:
+        else:       # the fp32 path's operand copies follow torch's current stream
             with torch.cuda.stream(self.side):
-                if bias_from is not None and not fused:
-                    lin.bgrad(bias_from, self.ws_side)
-                lin.wgrad(dy, x, with_bias=fused)
+                self._wgrad_launch(lin, dy, x, bias_from, fused)
         self._keep += (dy, x)      # also while capturing (see flush_wgrads)
+
+    def _wgrad_launch(self, lin, dy, x, bias_from, fused):      # on the stream in force; fused: the bias gradient comes out of the weight-gradient GEMM
+        if bias_from is not None and not fused:
+            lin.bgrad(bias_from, self.ws_side)
+        lin.wgrad(dy, x, with_bias=fused, ws=self.ws_side)
 
     def _attn_block_fwd(self, m, x, kv_src, B, Tq, Tk, k_len, q_lens, mask, cross, site, kv_pre=None, kv_rows=None):
         """x: (B*Tq, d) queries + residual; kv_src: (B*Tk, d).  mask: the mask keywords of K.sdpa_fwd / sdpa_bwd beyond k_len, as a dict
@@ -866,7 +899,7 @@ class Engine:
         H, dk, hd = self.H, self.dk, self.H * self.dk
         B, Tq, Tk = c["dims"]
         pa, sa, pf, sf = c["drop"]
-        fc_deferred = bool(self.defer_wgrad) and self.overlap_wgrad and not self._in_decoder and m.fc.tag in self.defer_wgrad and "fc" not in self._pair_tags
+        fc_deferred = self._wgrad_held(m.fc)
         if not fc_deferred:
             self._arm()
         dz, dxg = self._ln_bwd(m.ln, m.fc.gb, dy, dy2, c["xhat"], c["rstd"], c["q_lens"], B, Tq, drop_p=pf, drop_seed=sf, drop_mode=1)
@@ -899,12 +932,11 @@ class Engine:
                     m.kv.dgrad(dkv, out=d_kv_src, accumulate=True)
                 else:      # compact key rows: dX of the B*Tk rows, added to the first Tk frames of each utterance
                     K.rows_scatter_add(m.kv.dgrad(dkv), d_kv_src, B, c["kv_rows"], Tk)
-            if self.aux_overlap and not torch.cuda.is_current_stream_capturing():
+            if self._aux_active():
                 # d_enc += dK|dV W_kv is off the decoder's dependent chain: only the encoder's backward pass
                 # needs d_enc.  It runs on the auxiliary stream (in order behind the CTC branch and the previous layers' adds);
                 # decoder_bwd joins that stream at its end.
-                self._fork(self.ctc_stream)
-                with torch.cuda.stream(self.ctc_stream):
+                with _OnAux(self):
                     kv_src_grad()
                 self._keep.append(dkv)
             else:
@@ -985,7 +1017,6 @@ class Engine:
         # the last weight gradient runs on the MAIN stream: the side stream is still busy with layer 0,
         # and a cross-stream hand-over costs ~20 us of latency that nothing would hide at this point
         self.lin_in.wgrad(dz, cache["x_in"], ws=self.ws)      # A/B: 8.50 vs 8.45 k utt/s
-        self._block_flush = self.group_wgrad == "block"
         self.flush_ln_reduce()
         self.join_side()
         # every stream has been joined (the auxiliary stream at the end of decoder_bwd; without a decoder nothing runs on it): the
@@ -999,18 +1030,9 @@ class Engine:
         beside the decoder's forward pass: the decoder is a chain of ~70 launches on B*To ~ 550 rows that leaves most of the
         GPU idle, the CTC branch is four large kernels (~0.3 ms at config 3) that do not depend on it.  Returns (nll, d_enc,
         event): consumers on the main stream wait for the event (decoder_bwd does, before its first write into d_enc)."""
-        main = torch.cuda.current_stream()
-        self._fork(self.ctc_stream)
-        with torch.cuda.stream(self.ctc_stream):
-            if self.dec_cu_limit:      # beside the decoder's forward chain: leave it some CUs (see self.dec_cu_limit)
-                K.set_cu_limit(self.dec_cu_limit)
-            try:
-                nll, d_enc = self.ctc_fwd_bwd(enc, wave_len, labels32, lab_len, B, T, grad_scale, grad_scale_div=grad_scale_div, ws=self.ws_ctc)
-            finally:
-                if self.dec_cu_limit:
-                    K.set_cu_limit(0)
-            done = torch.cuda.Event()
-            done.record(self.ctc_stream)
+        done = torch.cuda.Event()
+        with _OnAux(self, cu_limit=self.dec_cu_limit, event=done):      # beside the decoder's forward chain: leave it some CUs (see self.dec_cu_limit)
+            nll, d_enc = self.ctc_fwd_bwd(enc, wave_len, labels32, lab_len, B, T, grad_scale, grad_scale_div=grad_scale_div, ws=self.ws_ctc)
         # inputs read on the auxiliary stream, and the two results (blocks of that stream's pool, read on the main stream): alive until
         # the step has joined the stream (decoder_bwd), see self._keep
         self._keep += (enc, wave_len, labels32, lab_len, nll, d_enc)
@@ -1144,26 +1166,19 @@ class Engine:
     def _kv_exec_async(self, bufs, enc):
         """The six cross-attention K|V projections of the encoder output on the auxiliary stream, one event each: they do not depend on
         the decoder state, and the main stream works through the decoder's small kernels meanwhile."""
-        self._fork(self.ctc_stream)
-        with torch.cuda.stream(self.ctc_stream):
-            if self.dec_cu_limit:
-                K.set_cu_limit(self.dec_cu_limit)
-            try:
-                src = self._kv_src(bufs, enc)
-                # layer 0's columns first (the chain's first cross-attention, ~80 us in, waits for them), then layers 1 .. L-1 as ONE GEMM
-                n0 = self.dec[0][1].kv.N
-                pl0, t0 = bufs["layers"][0]
-                self.dec[0][1].kv.fwd(src, out=t0["kv_c"])
-                t0["kv_event"].record(self.ctc_stream)
-                pl0.kv_ready_event = t0["kv_event"].cuda_event
-                if self.L > 1:
-                    self.kv_all.rows(n0, self.kv_all.N).fwd(src, out=bufs["kv_all"][:, n0:])
-                    bufs["kv_event_rest"].record(self.ctc_stream)
-                    for pl, t in bufs["layers"][1:]:
-                        pl.kv_ready_event = bufs["kv_event_rest"].cuda_event
-            finally:
-                if self.dec_cu_limit:
-                    K.set_cu_limit(0)
+        with _OnAux(self, cu_limit=self.dec_cu_limit):
+            src = self._kv_src(bufs, enc)
+            # layer 0's columns first (the chain's first cross-attention, ~80 us in, waits for them), then layers 1 .. L-1 as ONE GEMM
+            n0 = self.dec[0][1].kv.N
+            pl0, t0 = bufs["layers"][0]
+            self.dec[0][1].kv.fwd(src, out=t0["kv_c"])
+            t0["kv_event"].record(self.ctc_stream)
+            pl0.kv_ready_event = t0["kv_event"].cuda_event
+            if self.L > 1:
+                self.kv_all.rows(n0, self.kv_all.N).fwd(src, out=bufs["kv_all"][:, n0:])
+                bufs["kv_event_rest"].record(self.ctc_stream)
+                for pl, t in bufs["layers"][1:]:
+                    pl.kv_ready_event = bufs["kv_event_rest"].cuda_event
         self._keep.append(enc)
 
     def decoder_kv_async(self, prep, enc, B, T, Tk=None):
@@ -1173,17 +1188,17 @@ class Engine:
         trace, round 4: the chain stood still for ~240 us).  The CTC results are needed only when the decoder's backward pass starts."""
         self._kv_ahead = None
         To = prep[0].shape[1]
-        if not (self.aux_overlap and not torch.cuda.is_current_stream_capturing() and self._dec_exec_ok(B, To, T)):
+        if not (self._aux_active() and self._dec_exec_ok(B, To, T)):
             return
-        bufs = self._dec_bufs(B, To, T, T if Tk is None else Tk, self.training and self.drop_p > 0.0)
+        bufs = self._dec_bufs(B, To, T, T if Tk is None else Tk, self._dropping())
         self._kv_exec_async(bufs, enc)
         self._kv_ahead = (bufs, enc)
 
     def _dec_exec_fwd(self, x, enc, dec_len, cross_len, B, To, T, Tk):
-        drop = self.training and self.drop_p > 0.0
+        drop = self._dropping()
         bufs = self._dec_bufs(B, To, T, Tk, drop)
         main = K._stream()
-        overlap = self.aux_overlap and not torch.cuda.is_current_stream_capturing()
+        overlap = self._aux_active()
         ahead, self._kv_ahead = self._kv_ahead, None
         if overlap and not (ahead is not None and ahead[0] is bufs and ahead[1] is enc):      # not issued ahead of the CTC branch (decoder_kv_async)
             self._kv_exec_async(bufs, enc)
@@ -1203,9 +1218,9 @@ class Engine:
         return x, bufs
 
     def _dec_exec_bwd(self, bufs, dy, enc, d_enc, d_enc_ready):
-        drop = self.training and self.drop_p > 0.0
+        drop = self._dropping()
         main = K._stream()
-        aux = self.ctc_stream.cuda_stream if (self.aux_overlap and not torch.cuda.is_current_stream_capturing()) else None
+        aux = self.ctc_stream.cuda_stream if self._aux_active() else None
         dy2 = None
         M = dy.shape[0]
         nkv = self.dec[0][1].kv.N
@@ -1249,7 +1264,6 @@ class Engine:
             if not own_kv:
                 self._wgrad(cross.kv, t["g_kvc"], enc, bias_from=t["g_kvc"])
             elif grp is not None:      # the K | V weight gradients of the group's layers as ONE problem (their rows of the shared matrix are adjacent)
-                c0, c1 = grp[0] * nkv, grp[1] * nkv
                 g = bufs["g_kv_all"][:, c0:c1]
                 self._wgrad(self.kv_all.rows(c0, c1), g, src, bias_from=g)
             self._wgrad(slf.fc, t["g_as"] if drop else t["dz_s"], t["ctx_s"])
@@ -1280,11 +1294,10 @@ class Engine:
         kv_pre = [None] * self.L
         kv_rows = T if Tk < T else None
         src = K.rows_gather(enc, B, T, Tk) if kv_rows else enc      # compact key rows: the first Tk frames of each utterance
-        if self.aux_overlap and not torch.cuda.is_current_stream_capturing():
+        if self._aux_active():
             # the six cross-attention K|V projections of the encoder output do not depend on the
             # decoder state: they run on the auxiliary stream while the main stream works through the decoder's small kernels
-            self._fork(self.ctc_stream)
-            with torch.cuda.stream(self.ctc_stream):
+            with _OnAux(self):
                 for i, (slf, cross, ffn) in enumerate(self.dec):
                     kv = cross.kv.fwd(src)
                     e = torch.cuda.Event()
@@ -1311,17 +1324,18 @@ class Engine:
         dy, dy2 = self.prj.dgrad(dpred), None
         if "exec_bufs" in cache:
             dy, dy2 = self._dec_exec_bwd(cache["exec_bufs"], dy, cache["enc"], d_enc, d_enc_ready)
-        for i in (reversed(range(self.L)) if "exec_bufs" not in cache else ()):
-            slf, cross, ffn = self.dec[i]
-            c1, c2, c3 = cache["layers"][i]
-            dx, dz = self._ffn_block_bwd(ffn, c3, dy, dy2)
-            if d_enc_ready is not None:
-                torch.cuda.current_stream().wait_event(d_enc_ready)
-                d_enc_ready = None
-            dx, dz = self._attn_block_bwd(cross, c2, dx, dz, d_kv_src=d_enc)
-            dx, dz = self._attn_block_bwd(slf, c1, dx, dz)
-            dy, dy2 = dx, dz
-            self._ready(f"decoder.layer_stack.{i}.slf_attn.w_qs.weight")
+        else:
+            for i in reversed(range(self.L)):
+                slf, cross, ffn = self.dec[i]
+                c1, c2, c3 = cache["layers"][i]
+                dx, dz = self._ffn_block_bwd(ffn, c3, dy, dy2)
+                if d_enc_ready is not None:
+                    torch.cuda.current_stream().wait_event(d_enc_ready)
+                    d_enc_ready = None
+                dx, dz = self._attn_block_bwd(cross, c2, dx, dz, d_kv_src=d_enc)
+                dx, dz = self._attn_block_bwd(slf, c1, dx, dz)
+                dy, dy2 = dx, dz
+                self._ready(f"decoder.layer_stack.{i}.slf_attn.w_qs.weight")
         # gradient wrt the embedding output = projection path + residual path, added inside the scatter kernel.  The embedding's gradient IS
         # the output projection's (tied weights, transformer_official.py:253-256): the scatter's atomic adds and the projection's weight-gradient
         # GEMM (a plain read-modify-write when it has one M-split) must not overlap - the scatter goes to the weight-gradient stream, behind
@@ -1332,15 +1346,12 @@ class Engine:
         if self.overlap_wgrad:
             self._disarm()
             self._fork(self.side)
-            K.STREAM_OVERRIDE = self._side_handle
-            try:
+            with _OnSide(self._side_handle):
                 K.embed_bwd(ids_flat, dyc, self.gemb, self.d ** -0.5, drop_p=cache["drop"][0], drop_seed=cache["drop"][1], dy2=dy2c)
-            finally:
-                K.STREAM_OVERRIDE = None
             self._keep += (ids_flat, dyc) + ((dy2c,) if dy2c is not None else ())
         else:
             K.embed_bwd(ids_flat, dyc, self.gemb, self.d ** -0.5, drop_p=cache["drop"][0], drop_seed=cache["drop"][1], dy2=dy2c)
-        if self.aux_overlap and not torch.cuda.is_current_stream_capturing():      # nothing is forked to that stream while capturing
+        if self._aux_active():      # nothing is forked to that stream while capturing
             torch.cuda.current_stream().wait_stream(self.ctc_stream)      # d_enc is complete (CTC branch + every cross-attention add)
         self._in_decoder = False
         self._ready("decoder.tgt_word_emb.weight")

@@ -20,8 +20,8 @@ if os.environ.get("PROBE", "1") == "0":
 if os.environ.get("SIDE", "low") == "normal":      # experiment: the weight-gradient stream at normal priority (a torch pool stream)
     E._side_stream = lambda device: torch.cuda.Stream(device=device)
 if os.environ.get("NOAUX", "0") == "1":            # experiment: no separate auxiliary stream (the weight-gradient stream serves as "aux" too)
-    _orig_shared = E._shared_stream
-    E._shared_stream = lambda device, kind: _orig_shared(device, "wgrad")
+    _orig_shared = E.shared_stream
+    E.shared_stream = lambda device, kind: _orig_shared(device, "wgrad")
 if os.environ.get("BURN", "0") != "0":             # experiment: take N streams from torch's pool first (shifts the pool index of every later stream)
     _burn = [torch.cuda.Stream() for _ in range(int(os.environ["BURN"]))]
 late = os.environ.get("ORDER", "early") == "late"      # late: the process group is created AFTER the model, its streams and a few steps
