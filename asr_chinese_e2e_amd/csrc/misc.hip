@@ -40,8 +40,10 @@ extern "C" int asr_set_deterministic(int on) {
 // fewer M-splits); 0 = the 256 x 128-tile grouped kernel for every group (A/B timing inside one process).
 // "sdpa_pair" (round 5; default 0): 1 = the attention forward without causal / band mask and without dropout on the kernel that takes both 32-query
 // blocks of a wave through ONE pass over the key tiles (sdpa_fwd_pair_bf16_kernel: bit-identical results, measured 33.5 vs 31.6 us - opt-in).
-static const char* const g_opt_names[ASR_OPT_COUNT] = {"cu_limit", "tn_multi", "sdpa_pair"};
-static int g_opt_val[ASR_OPT_COUNT] = {0, 1, 0};
+// "sdpa_small" (default 1): asr_sdpa_fwd / _bwd run bf16 heads of at most 64 queries and 64 keys (causal or unmasked: the decoder's) on the one-wave-per-head
+// kernels (sdpa_fwd_small_bf16_kernel, sdpa_bwd_small_bf16_kernel); 0 = on the one-workgroup-per-head kernels built for 512 keys (A/B timing, parity tests).
+static const char* const g_opt_names[ASR_OPT_COUNT] = {"cu_limit", "tn_multi", "sdpa_pair", "sdpa_small"};
+static int g_opt_val[ASR_OPT_COUNT] = {0, 1, 0, 1};
 static void opt_init() {}
 int asr_option(int key) {
     opt_init();

@@ -21,7 +21,7 @@
 // for head sizes other than 64); one wave per query (fwd, dQ) or per key (dKV).
 //
 // Dispatch (end of the file): the four entry points share one forward and one backward launcher, templates on CHUNK as the kernels are.
-// bf16, head dim 64, aligned rows: the one-workgroup-per-head kernels up to 512 keys, beyond them the band kernel (backward, a window
+// bf16, head dim 64, aligned rows: the one-wave-per-head kernels up to 64 queries and keys (causal or unmasked), the one-workgroup-per-head kernels up to 512 keys, beyond them the band kernel (backward, a window
 // over self-attention) or the tiled kernels above; anything else: the f32-accumulating generic kernels.  Dropout, mask and element type
 // reach the kernels as template arguments through with_bools().
 #include <stdlib.h>
@@ -1678,6 +1678,317 @@ __global__ __launch_bounds__(256) void sdpa_band_halo_kernel(const float* __rest
     store8<bf16_t>(dq + ((size_t)b * Tq + qi) * ldq + h * DK + c8, x);
 }
 
+// ---------------------------------------------------------------- short heads: ONE WAVE per (b, h), Tq <= 64 and Tk <= 64
+// The decoder's heads have To ~ 17 - 23 queries and To (self) or 32 (cross, after the cross-rows compaction) keys: in the one-workgroup
+// kernels above one wave of eight has keys, one 32-query block has queries, and the other seven waves only join the barriers of a
+// prologue built for 512 keys (DMA ring, 64 KiB images, centring sums).  Here the whole head is one wave's registers:
+//   * Q, K, V (and dO) are read ONCE, as row fragments straight from global memory (16-byte loads, all issued before the first use: one
+//     round trip; k_len is not waited for - rows past it are zeroed after the load).  A row fragment is both an A and a B operand, so the
+//     same registers give S^T = K Q^T (query on the lane) and S = Q K^T (key on the lane);
+//   * the only LDS traffic is the wave writing the fragments whose TRANSPOSE a product needs (V forward; Q, dO, K backward) into padded
+//     64-row tiles and reading them back with ds_read_b64_tr_b16; the workgroup IS the wave, so its barriers are waits on its own LDS writes;
+//   * forward: one pass, no running maximum (every key of the head is in registers when the softmax starts);
+//   * backward: query on the lane first - p, dP, delta = sum_j p_j dP_j / sum_j p_j from the kernel's OWN p and dP (with dropout: the
+//     dropped dP), the form section 2 of DESIGN.md found necessary for the decoder - dS^T, dQ^T += K^T dS^T; then key on the lane - S and
+//     dP again (8 MFMAs per block: cheaper than carrying dS through LDS), dV^T += dO^T P, dK^T += Q^T dS.  No atomics, fixed order.
+// Same arithmetic per element, same masks, same dropout counters, same lse as the kernels above; 33 - 64 queries or keys are a second
+// 32-block in the same wave.
+__device__ __forceinline__ void small_rows(bf16x8 (&f)[4], const bf16_t* __restrict__ base, size_t ld, int row0, int rows, int lane) {
+    // rows = rows of the matrix (>= 1): every address read is inside it; what lies past the caller's limit is zeroed by small_zero()
+    const int row = min(row0 + (lane & 31), rows - 1);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) f[ks] = *(const bf16x8*)(base + (size_t)row * ld + 16 * ks + 8 * (lane >> 5));
+}
+__device__ __forceinline__ void small_zero(bf16x8 (&f)[4], bool zero) {
+    if (zero) {
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[ks][j] = (bf16_t)0.f;
+    }
+}
+// the inverse of frag_row: the 32 rows a wave holds as fragments -> rows row0 .. row0 + 31 of a padded tile
+__device__ __forceinline__ void small_stage(bf16_t* tile, int row0, const bf16x8 (&f)[4], int lane) {
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) *(bf16x8*)(tile + (row0 + (lane & 31)) * TS + 16 * ks + 8 * (lane >> 5)) = f[ks];
+}
+constexpr int SM_T = 64;      // most queries and most keys of a head
+
+template <bool DROP>
+__global__ __launch_bounds__(64) void sdpa_fwd_small_bf16_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                                 bf16_t* __restrict__ o, float* __restrict__ lse, const int32_t* __restrict__ k_len, int H,
+                                                                 int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int causal, float scale,
+                                                                 uint32_t dseed, uint32_t dthr, float dscale) {
+    __shared__ __attribute__((aligned(16))) bf16_t Vt[TILE_ELEMS];
+    const int lane = threadIdx.x;
+    const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+    const bf16_t* qb = q + (size_t)b * Tq * ldq + h * DK;
+    const bf16_t* kb = k + (size_t)b * Tk * ldk + h * DK;
+    const bf16_t* vb = v + (size_t)b * Tk * ldv + h * DK;
+    const int nqb = (Tq + 31) >> 5, nkb = (Tk + 31) >> 5;      // 1 or 2 each
+    bf16x8 qf[2][4], kf[2][4], vf[2][4];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (u < nqb) small_rows(qf[u], qb, ldq, 32 * u, Tq, lane);
+        if (u < nkb) { small_rows(kf[u], kb, ldk, 32 * u, Tk, lane); small_rows(vf[u], vb, ldv, 32 * u, Tk, lane); }
+    }
+    const int klen = min(k_len ? k_len[b] : Tk, Tk);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (u < nqb) small_zero(qf[u], 32 * u + (lane & 31) >= Tq);
+        if (u < nkb) {
+            const bool past = 32 * u + (lane & 31) >= klen;      // padded keys: K is masked below, V must not bring a NaN to a zero probability
+            small_zero(kf[u], past);
+            small_zero(vf[u], past);
+            small_stage(Vt, 32 * u, vf[u], lane);
+        }
+    }
+    __syncthreads();
+    const float sc2 = scale * LOG2E;
+    bf16x8 ones;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ones[j] = (bf16_t)1.0f;
+#pragma unroll
+    for (int qbk = 0; qbk < 2; ++qbk) {
+        if (qbk >= nqb) break;
+        const int q0 = 32 * qbk, qi = q0 + (lane & 31);
+        int kend = klen;
+        if (causal) kend = min(kend, min(q0 + 32, Tq));
+        const int nsub = (max(kend, 0) + 31) >> 5;      // key blocks that hold a key some query of this block sees
+        f32x16 st[2], oacc[2];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { oacc[0][i] = 0.f; oacc[1][i] = 0.f; }
+        float tmax = M_INIT;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) st[sub][i] = -INFINITY;
+            if (sub < nsub) {
+                f32x16 s;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) s[i] = 0.f;
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[sub][ks], qf[qbk][ks], s, 0, 0, 0);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    st[sub][i] = visible(qi, 32 * sub + acc_row(i, lane), klen, causal, -1) ? s[i] : -INFINITY;
+                    tmax = fmaxf(tmax, st[sub][i]);
+                }
+            }
+        }
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+        const float m = tmax, mc = m * sc2;
+        float l = 0.f;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float p = __builtin_amdgcn_exp2f(fmaf(st[sub][i], sc2, -mc));
+                st[sub][i] = p;
+                if constexpr (DROP) l += p;
+            }
+        // The normaliser, as sdpa_fwd_fused_bf16_kernel forms it: with dropout the fp32 sum of the undropped p; without, the sum of the
+        // bf16-ROUNDED p that feed the P V product, out of the matrix pipe (an all-ones A operand; every register of lacc is the lane's
+        // query's sum over all keys) - o is then a convex combination of V's rows exactly, and o and lse keep the bits they had.
+        f32x16 lacc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) lacc[i] = 0.f;
+        if constexpr (DROP) {
+            l += __shfl_xor(l, 32, 64);
+            // dropout on the probabilities; the normaliser l stays undropped (sdpa_fwd_bf16_kernel's counters)
+            const uint32_t rowbase = (((uint32_t)(b * H + h)) * Tq + min(qi, Tq - 1)) * ((Tk + 1) & ~1);
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+                for (int i = 0; i < 16; i += 2) {
+                    const uint32_t hsh = drop_hash((rowbase + 32 * sub + acc_row(i, lane)) >> 1, dseed);
+                    st[sub][i] = drop_keep(hsh, 0, dthr) ? st[sub][i] * dscale : 0.f;
+                    st[sub][i + 1] = drop_keep(hsh, 1, dthr) ? st[sub][i + 1] * dscale : 0.f;
+                }
+        }
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            if (sub >= nsub) break;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const bf16x8 pf = acc_to_frag(st[sub], s);
+#pragma unroll
+                for (int db = 0; db < 2; ++db)
+                    oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(Vt, 32 * sub, 32 * db, s, lane), pf, oacc[db], 0, 0, 0);
+                if constexpr (!DROP) lacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pf, lacc, 0, 0, 0);
+            }
+        }
+        if constexpr (!DROP) l = lacc[0];
+        const float inv = l > 0.f ? 1.f / l : 0.f;
+        store_rows_T(oacc, inv, o + (size_t)b * Tq * ldo + h * DK, ldo, q0, Tq, lane);
+        if (lane < 32 && qi < Tq) lse[((size_t)b * H + h) * Tq + qi] = l > 0.f ? (m * sc2 + log2f(l)) * LN2 : -INFINITY;
+    }
+}
+
+template <bool DROP>
+__global__ __launch_bounds__(64) void sdpa_bwd_small_bf16_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                                 const bf16_t* __restrict__ d_o, const float* __restrict__ lse, bf16_t* __restrict__ dq,
+                                                                 bf16_t* __restrict__ dk_, bf16_t* __restrict__ dv, const int32_t* __restrict__ k_len, int H,
+                                                                 int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int causal, float scale,
+                                                                 uint32_t dseed, uint32_t dthr, float dscale) {
+    __shared__ __attribute__((aligned(16))) bf16_t smem[3 * TILE_ELEMS];
+    __shared__ __attribute__((aligned(16))) float stats[2 * SM_T];
+    bf16_t* Qt = smem;
+    bf16_t* Dt = smem + TILE_ELEMS;
+    bf16_t* Kt = smem + 2 * TILE_ELEMS;
+    float* s_lse = stats;           // lse log2(e) of every query (1e30: a row past the end, or one that saw no key)
+    float* s_del = stats + SM_T;    // delta of every query
+    const int lane = threadIdx.x, hh = lane >> 5;
+    const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+    const bf16_t* qb = q + (size_t)b * Tq * ldq + h * DK;
+    const bf16_t* dob = d_o + (size_t)b * Tq * ldo + h * DK;
+    const bf16_t* kb = k + (size_t)b * Tk * ldk + h * DK;
+    const bf16_t* vb = v + (size_t)b * Tk * ldv + h * DK;
+    const int nqb = (Tq + 31) >> 5, nkb = (Tk + 31) >> 5;      // 1 or 2 each
+    bf16x8 qf[2][4], dof[2][4], kf[2][4], vf[2][4];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (u < nqb) { small_rows(qf[u], qb, ldq, 32 * u, Tq, lane); small_rows(dof[u], dob, ldo, 32 * u, Tq, lane); }
+        if (u < nkb) { small_rows(kf[u], kb, ldk, 32 * u, Tk, lane); small_rows(vf[u], vb, ldv, 32 * u, Tk, lane); }
+    }
+    const float lse_raw = lse[((size_t)b * H + h) * Tq + min(lane, Tq - 1)];      // lane = query 0 .. 63
+    const int klen = min(k_len ? k_len[b] : Tk, Tk);
+    s_lse[lane] = (lane >= Tq || lse_raw == -INFINITY) ? 1.0e30f : lse_raw * LOG2E;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (u < nqb) {
+            const bool past = 32 * u + (lane & 31) >= Tq;
+            small_zero(qf[u], past);
+            small_zero(dof[u], past);
+            small_stage(Qt, 32 * u, qf[u], lane);
+            small_stage(Dt, 32 * u, dof[u], lane);
+        }
+        if (u < nkb) {
+            const bool past = 32 * u + (lane & 31) >= klen;      // padded keys: zero rows, so that dS = 0 meets no NaN
+            small_zero(kf[u], past);
+            small_zero(vf[u], past);
+            small_stage(Kt, 32 * u, kf[u], lane);
+        }
+    }
+    __syncthreads();
+    const float sc2 = scale * LOG2E;
+    // ---- query on the lane: delta and dQ of each 32-query block
+#pragma unroll
+    for (int qbk = 0; qbk < 2; ++qbk) {
+        if (qbk >= nqb) break;
+        const int q0 = 32 * qbk, qi = q0 + (lane & 31);
+        int kend = klen;
+        if (causal) kend = min(kend, min(q0 + 32, Tq));
+        const int nsub = (max(kend, 0) + 31) >> 5;
+        const float lse2 = s_lse[min(qi, SM_T - 1)];
+        f32x16 st[2], dp[2];
+        float sp = 0.f, spd = 0.f;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            if (sub >= nsub) break;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { st[sub][i] = 0.f; dp[sub][i] = 0.f; }
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                st[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[sub][ks], qf[qbk][ks], st[sub], 0, 0, 0);
+                dp[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[sub][ks], dof[qbk][ks], dp[sub], 0, 0, 0);
+            }
+            if constexpr (DROP) {   // dP = (dO V^T) o keep / (1 - p)
+                const uint32_t rowbase = (((uint32_t)(b * H + h)) * Tq + min(qi, Tq - 1)) * ((Tk + 1) & ~1);
+#pragma unroll
+                for (int i = 0; i < 16; i += 2) {
+                    const uint32_t hsh = drop_hash((rowbase + 32 * sub + acc_row(i, lane)) >> 1, dseed);
+                    dp[sub][i] = drop_keep(hsh, 0, dthr) ? dp[sub][i] * dscale : 0.f;
+                    dp[sub][i + 1] = drop_keep(hsh, 1, dthr) ? dp[sub][i + 1] * dscale : 0.f;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float sv = visible(qi, 32 * sub + acc_row(i, lane), klen, causal, -1) ? st[sub][i] : -INFINITY;
+                const float p = __builtin_amdgcn_exp2f(fmaf(sv, sc2, -lse2));
+                st[sub][i] = p;
+                sp += p;
+                spd += p * dp[sub][i];
+            }
+        }
+        sp += __shfl_xor(sp, 32, 64);
+        spd += __shfl_xor(spd, 32, 64);
+        const float dl = sp > 0.f ? spd / sp : 0.f;
+        if (lane < 32) s_del[qi] = dl;
+        f32x16 acc[2];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            if (sub >= nsub) break;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) st[sub][i] *= dp[sub][i] - dl;      // dS^T / scale: the factor is applied once, when dQ is stored
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const bf16x8 df = acc_to_frag(st[sub], s);
+#pragma unroll
+                for (int db = 0; db < 2; ++db)
+                    acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(Kt, 32 * sub, 32 * db, s, lane), df, acc[db], 0, 0, 0);
+            }
+        }
+        store_rows_T(acc, scale, dq + (size_t)b * Tq * ldq + h * DK, ldq, q0, Tq, lane);
+    }
+    __syncthreads();      // s_del
+    // ---- key on the lane: dK and dV of each 32-key block
+#pragma unroll
+    for (int kbk = 0; kbk < 2; ++kbk) {
+        if (kbk >= nkb) break;
+        const int key0 = 32 * kbk, kj = key0 + (lane & 31);
+        f32x16 dka[2], dva[2];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { dka[0][i] = dka[1][i] = dva[0][i] = dva[1][i] = 0.f; }
+#pragma unroll
+        for (int qbk = 0; qbk < 2; ++qbk) {
+            const int q0 = 32 * qbk;
+            if (qbk >= nqb || key0 >= klen || (causal && key0 > q0 + 31)) continue;      // no query of the block sees a key of the block
+            f32x16 st, dp, ds;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { st[i] = 0.f; dp[i] = 0.f; }
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf[qbk][ks], kf[kbk][ks], st, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof[qbk][ks], vf[kbk][ks], dp, 0, 0, 0);
+            }
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const int r0 = q0 + 8 * g4 + 4 * hh;
+                const f32x4 l4 = *(const f32x4*)(s_lse + r0);
+                const f32x4 d4 = *(const f32x4*)(s_del + r0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int i = 4 * g4 + e;
+                    const float sv = visible(r0 + e, kj, klen, causal, -1) ? st[i] : -INFINITY;
+                    const float p = __builtin_amdgcn_exp2f(fmaf(sv, sc2, -l4[e]));
+                    float keepf = 1.f;
+                    if constexpr (DROP) {
+                        const uint32_t el = (((uint32_t)(b * H + h)) * Tq + min(r0 + e, Tq - 1)) * ((Tk + 1) & ~1) + min(kj, Tk - 1);
+                        keepf = drop_keep_at(el, dseed, dthr) ? dscale : 0.f;
+                    }
+                    st[i] = p * keepf;                               // dropped probabilities feed dV
+                    ds[i] = p * (dp[i] * keepf - d4[e]);             // dS / scale: applied once, when dK is stored
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const bf16x8 pf = acc_to_frag(st, s);
+                const bf16x8 df = acc_to_frag(ds, s);
+#pragma unroll
+                for (int db = 0; db < 2; ++db) {
+                    dva[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(Dt, q0, 32 * db, s, lane), pf, dva[db], 0, 0, 0);
+                    dka[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(Qt, q0, 32 * db, s, lane), df, dka[db], 0, 0, 0);
+                }
+            }
+        }
+        store_rows_T(dka, scale, dk_ + (size_t)b * Tk * ldk + h * DK, ldk, key0, Tk, lane);
+        store_rows_T(dva, 1.f, dv + (size_t)b * Tk * ldv + h * DK, ldv, key0, Tk, lane);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // exact fp32 VALU path (any dk <= 128)
 // ------------------------------------------------------------------------------------------
@@ -1856,6 +2167,9 @@ bool mfma_ok(int dk, int ldq, int ldk, int ldv, int ldo, const void* a, const vo
     return dk == DK && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 &&
            (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) % 16) == 0;
 }
+// the one-wave kernels: causal or no mask (no band, no chunks), at most SM_T queries and keys; tuning option "sdpa_small" = 0 keeps such heads on the
+// one-workgroup kernels (A/B timing, kernel-against-kernel tests)
+bool sdpa_small_shape(bool chunk, int Tq, int Tk, int window) { return !chunk && window < 0 && Tq <= SM_T && Tk <= SM_T && asr_option(ASR_OPT_SDPA_SMALL) != 0; }
 int check_common(const char* name, int B, int H, int Tq, int Tk, int dk, int ldq, int ldk, int ldv, int ldo, const void* o_lo, int dtype) {
     if (o_lo && (dtype != ASR_BF16 || ((uintptr_t)o_lo % 16) != 0)) ASR_FAIL(ASR_EINVAL, "%s: o_lo is the low-order piece of a bf16 output (16-byte aligned, the layout of o)", name);
     if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || dk <= 0 || dk > 128) ASR_FAIL(ASR_EINVAL, "%s: bad shape B=%d H=%d Tq=%d Tk=%d dk=%d", name, B, H, Tq, Tk, dk);
@@ -1890,6 +2204,7 @@ int sdpa_fwd(const char* name, const void* q, const void* k, const void* v, void
     const bool mfma = dtype == ASR_BF16 && mfma_ok(dk, ldq, ldk, ldv, ldo, q, k, v, o);
     const bool fused = mfma && Tk <= FF_KEYS;      // K and V of a head fit LDS: one workgroup per (b, h); more keys: the tiled kernel
     const bool has_mask = CHUNK || a || b >= 0;
+    const bool small = fused && sdpa_small_shape(CHUNK, Tq, Tk, b);      // a head of at most 64 queries and keys: one wave per (b, h)
     const size_t lds_generic = (size_t)(Tk + dk) * sizeof(float);
     if (!mfma && lds_generic > 64 * 1024) ASR_FAIL(ASR_EINVAL, "%s: generic path needs Tk+dk <= 16384", name);
     if (!mfma && dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "%s: dtype %d", name, dtype);
@@ -1897,7 +2212,11 @@ int sdpa_fwd(const char* name, const void* q, const void* k, const void* v, void
     if (o_lo && (fused || !mfma) && hipMemset2DAsync(o_lo, (size_t)ldo * 2, 0, (size_t)H * dk * 2, (size_t)B * Tq, st) != hipSuccess) ASR_FAIL(ASR_EINVAL, "%s: clearing o_lo failed", name);
     const bf16_t *qb = (const bf16_t*)q, *kb = (const bf16_t*)k, *vb = (const bf16_t*)v;
     bf16_t* ob = (bf16_t*)o;
-    if (fused) {
+    if (small) {
+        with_bools([&](auto drop) {
+            sdpa_fwd_small_bf16_kernel<drop><<<B * H, 64, 0, st>>>(qb, kb, vb, ob, lse, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, a, scale, dseed, dthr, dscale);
+        }, dthr != 0);
+    } else if (fused) {
         static const bool lds_allowed = each_bools<2>([](auto drop, auto masked) {
             if constexpr (masked || !CHUNK) allow_lds(sdpa_fwd_fused_bf16_kernel<drop, masked, CHUNK>, FF_LDS);
             if constexpr (!drop && !masked && !CHUNK) allow_lds(sdpa_fwd_pair_bf16_kernel, FF_LDS);      // its stand-in under the sdpa_pair option
@@ -1957,7 +2276,13 @@ int sdpa_bwd(const char* name, const void* q, const void* k, const void* v, cons
         using T = std::conditional_t<f32, float, bf16_t>;
         sdpa_delta_kernel<T><<<ceil_div(B * Tq * H, 32), 256, 0, st>>>((const T*)o, (const T*)o_lo, (const T*)d_o, delta, B, H, Tq, dk, ldo);
     }, dtype == ASR_F32);
-    if (mfma && Tk <= FB_KEYS) {      // every key of a head fits one workgroup: single-pass backward, which reads no o_lo
+    if (mfma && sdpa_small_shape(CHUNK, Tq, Tk, b)) {      // a head of at most 64 queries and keys: one wave per (b, h); reads neither o nor o_lo
+        // like the one-workgroup kernel below, the only kernel of its path: it may carry an armed completion event (asr_stream_arm)
+        with_bools([&](auto drop) {
+            asr_launch_armed(sdpa_bwd_small_bf16_kernel<drop>, dim3(B * H), dim3(64), 0, st, qb, kb, vb, dob, lse, dqb, dkb, dvb, k_len, H, Tq, Tk, ldq, ldk, ldv, ldo, a, scale,
+                             dseed, dthr, dscale);
+        }, dthr != 0);
+    } else if (mfma && Tk <= FB_KEYS) {      // every key of a head fits one workgroup: single-pass backward, which reads no o_lo
         static const bool lds_allowed = each_bools<2>([](auto drop, auto masked) {
             if constexpr (masked || !CHUNK) allow_lds(sdpa_bwd_fused_bf16_kernel<drop, masked, false, CHUNK>, FB_LDS + fb_vimg<drop, masked, CHUNK>);
         });

@@ -86,6 +86,8 @@ int asr_stream_create(int priority, void** out_stream);
  * code of the single-problem kernel in one launch; 0 = always the 256 x 128-tile grouped kernel (A/B timing).
  * "sdpa_pair" (round 5; initial value 0): 1 = asr_sdpa_fwd without causal / band mask and without dropout on the kernel that takes both 32-query
  * blocks of a wave through one pass over the key tiles (same bits; measured slower, kept for A/B).
+ * "sdpa_small" (initial value 1): asr_sdpa_fwd / asr_sdpa_bwd run bf16 heads of at most 64 queries and 64 keys, causal or unmasked, on the kernels
+ * that give a head to ONE wave; 0 = on the one-workgroup-per-head kernels as before (results agree to the order of fp32 sums; kept for A/B).
  * previous (may be NULL) receives the old value.  Unknown name: ASR_EINVAL. */
 int asr_set_option(const char* name, int value, int* previous);
 int asr_get_deterministic(void);

@@ -13,14 +13,18 @@ DROPOUT = float(os.environ.get("DROPOUT", "0"))
 SETTINGS = [{}, {"ASR_WGRAD_OVERLAP": "0"}, {"ASR_DETERMINISTIC": "1"}, {"ASR_WGRAD_GROUP": "0"}, {"ASR_WGRAD_GROUP": "layer"}, {"ASR_WGRAD_GROUP": "block"},
             {"ASR_WGRAD_GROUP": "pair"}, {"ASR_WGRAD_GROUP": "pair_ffn"}, {"ASR_WGRAD_GROUP": "pair_attn"}, {"ASR_KV_GROUPS": "1"}, {"ASR_KV_GROUPS": "2"},
             {"ASR_KV_GROUPS": "6"}, {"ASR_WGRAD_DEFER": ""}, {"ASR_WGRAD_DEFER": "fc,w2"}, {"ASR_ARMED_FORK": "0"}, {"ASR_DEC_EXEC": "0"},
-            {"ASR_DEC_CU_LIMIT": "0"}, {"ASR_DEC_CU_LIMIT": "96"}, {"ASR_WGRAD_GROUP": "block", "ASR_WGRAD_DEFER": "w2"}]
+            {"ASR_DEC_CU_LIMIT": "0"}, {"ASR_DEC_CU_LIMIT": "96"}, {"ASR_WGRAD_GROUP": "block", "ASR_WGRAD_DEFER": "w2"},
+            {"option:sdpa_small": "0"}, {"option:sdpa_small": "0", "ASR_DEC_EXEC": "0"}]      # "option:name" = a tuning option of the library (asr_set_option), not an environment variable
 pack = synthetic_pack(B, T, 80, V, seed=27, ragged=True, Lmin=max(2, TO - 3), Lmax=TO, device="cuda", dtype=torch.bfloat16)
 names, ref, ref_loss, bad = None, None, None, 0
 for cfg_name in (("joint", "ctc") if os.environ.get("MODEL", "both") == "both" else (os.environ["MODEL"],)):
     ref = None
     for env in SETTINGS:
-        saved = {k: os.environ.get(k) for k in env}
-        os.environ.update(env)
+        opts = {k[7:]: int(v) for k, v in env.items() if k.startswith("option:")}
+        env_vars = {k: v for k, v in env.items() if not k.startswith("option:")}
+        saved = {k: os.environ.get(k) for k in env_vars}
+        os.environ.update(env_vars)
+        saved_opts = {k: K.set_option(k, v) for k, v in opts.items()}
         K.set_deterministic(env.get("ASR_DETERMINISTIC") == "1")
         try:
             torch.manual_seed(5)
@@ -53,4 +57,5 @@ for cfg_name in (("joint", "ctc") if os.environ.get("MODEL", "both") == "both" e
                 if v is None: os.environ.pop(k, None)
                 else: os.environ[k] = v
             K.set_deterministic(False)
+            for k, v in saved_opts.items(): K.set_option(k, v)
 print("settings to look at:", bad)
