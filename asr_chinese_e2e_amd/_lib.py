@@ -22,6 +22,7 @@ ASR_F32, ASR_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_RELU_MASK = 0, 1, 2
 ABI_VERSION = 10
 DROP_PRE, DROP_POST = 1, 2
+SPEED_TILE = 1024      # ASR_SPEED_TILE of include/asr_hip.h: output samples per workgroup of asr_speed_perturb_fwd
 
 P, I, F, Z, U = c_void_p, c_int, c_float, c_size_t, c_uint32
 
@@ -133,6 +134,7 @@ SIGNATURES = {
     "asr_logmel_fwd": (I, [P, P, P, P, P, I, I, I, I, P]),
     "asr_utt_norm_lfr_fwd": (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
     "asr_utt_norm_augment_lfr_fwd": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "asr_speed_perturb_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
 }
 
 

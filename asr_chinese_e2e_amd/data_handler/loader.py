@@ -24,6 +24,7 @@ import torch
 from ..Utils import Pack
 from .padder import Padder
 from .processor import AudioParser
+from . import speed as speed_mod
 
 
 def load_wav(path):
@@ -131,6 +132,35 @@ def shard_batches(batches, rank, world):
     return batches[: len(batches) // world * world][rank::world]
 
 
+class BatchPlan:
+    """The batch list of every epoch, host logic only (no GPU): what BucketedWaveLoader iterates over.  `rng` drives the batch order (and,
+    in the loader, the SpecAugment masks); with speed perturbation (`speed_pq`: list of (p, q)) each epoch first draws a factor index per
+    utterance - speed.draw_factors, a pure function of (seed, epoch, utterance index) that never touches `rng` - and forms the buckets on
+    the PERTURBED lengths, so padding stays small.  The epoch is the number of next_epoch() calls so far.  Every data-parallel rank
+    builds the same full list and takes its shard."""
+
+    def __init__(self, lengths, batch_size, bucket_size=None, shuffle=True, drop_last=False, seed=0, rank=0, world=1, speed_pq=None):
+        self.lengths, self.batch_size, self.bucket_size, self.shuffle = list(lengths), batch_size, bucket_size, shuffle
+        self.rank, self.world = int(rank), int(world)
+        assert 0 <= self.rank < self.world
+        self.drop_last = True if self.world > 1 else drop_last
+        self.seed, self.rng, self.epoch = seed, random.Random(seed), 0
+        self.speed_pq = [tuple(x) for x in speed_pq] if speed_pq else None
+
+    def batches(self, rng, lengths=None):
+        full = bucket_batches(self.lengths if lengths is None else lengths, self.batch_size, self.bucket_size, self.shuffle, self.drop_last, rng)
+        return shard_batches(full, self.rank, self.world), full
+
+    def next_epoch(self):
+        """-> (this rank's batches, the full batch list, factor index per utterance of the data set or None)."""
+        epoch, self.epoch = self.epoch, self.epoch + 1
+        if self.speed_pq is None:
+            return self.batches(self.rng) + (None,)
+        fidx = speed_mod.draw_factors(self.seed, epoch, len(self.lengths), len(self.speed_pq))
+        lengths = [speed_mod.perturbed_len(n, *self.speed_pq[f]) for n, f in zip(self.lengths, fidx)]
+        return self.batches(self.rng, lengths) + (fidx,)
+
+
 _LOADERS = weakref.WeakSet()      # loaders of this process (paused() holds every one's gate)
 
 
@@ -157,23 +187,27 @@ class BucketedWaveLoader:
     longer)."""
 
     def __init__(self, dataset, batch_size, parser=None, augment=False, shuffle=True, drop_last=False, seed=0, bucket_size=None,
-                 device="cuda", dtype=torch.bfloat16, rank=0, world=1):
+                 device="cuda", dtype=torch.bfloat16, rank=0, world=1, speed_perturb=None):
         """rank / world: data-parallel sharding.  Every rank draws the SAME batch list (same seed), keeps only the full
         batches when world > 1 (dist.DataParallel normalises by world x local batch and every rank must take the same
-        number of steps), drops the ragged tail of len(batches) % world and takes batches[rank::world]."""
-        self.ds, self.batch_size, self.augment, self.shuffle, self.drop_last = dataset, batch_size, augment, shuffle, drop_last
-        self.rank, self.world = int(rank), int(world)
-        assert 0 <= self.rank < self.world
-        if self.world > 1:
-            self.drop_last = True
+        number of steps), drops the ragged tail of len(batches) % world and takes batches[rank::world].
+        speed_perturb: sequence of speed factors such as (0.9, 1.0, 1.1) (speed.parse_factor); every epoch each utterance draws one of
+        them (BatchPlan) and is resampled on the loader's stream in front of the log-mel kernel, so lengths and frame counts change
+        from epoch to epoch.  None / empty: no perturbation, nothing of it is called."""
+        self.ds, self.batch_size, self.augment = dataset, batch_size, augment
         self.device, self.dtype = torch.device(device), dtype
         if self.device.type != "cuda":
             raise RuntimeError("the feature front end runs on the GPU only (no CPU fallback)")
         self.parser = parser or AudioParser(device=self.device)
-        self.rng = random.Random(seed)          # batch order AND SpecAugment masks (the reference uses the global `random`)
-        self.bucket_size = bucket_size
         self.stream = self._copy_stream()
         self.lengths = [dataset.num_samples(i) for i in range(len(dataset))]
+        self.speed = None      # (pq list, pq (F, 2) int32, taps (F, qmax, ntaps) f32): built once, resident on the device
+        if speed_perturb is not None and len(speed_perturb) > 0:
+            pq, taps = speed_mod.build_tables(speed_perturb)
+            self.speed = ([tuple(int(v) for v in r) for r in pq], torch.from_numpy(pq).to(self.device), torch.from_numpy(taps).to(self.device))
+        self.plan = BatchPlan(self.lengths, batch_size, bucket_size, shuffle, drop_last, seed, rank, world, self.speed[0] if self.speed else None)
+        self.rank, self.world, self.shuffle, self.drop_last, self.bucket_size = self.plan.rank, self.plan.world, shuffle, self.plan.drop_last, bucket_size
+        self.rng = self.plan.rng                # batch order AND SpecAugment masks (the reference uses the global `random`)
         self._gate = threading.Lock()      # held by the helper thread around _prepare; paused() takes it
         _LOADERS.add(self)
 
@@ -220,17 +254,19 @@ class BucketedWaveLoader:
             slots[k] = s
         return s
 
-    def _prepare(self, idx, k=0):
+    def _prepare(self, idx, k=0, fidx=None):
+        """fidx: speed-factor index per utterance of the data set (BatchPlan.next_epoch), None = no perturbation."""
         tgt = [self.ds.ids(i) for i in idx]
         B = len(idx)
+        nf = B if fidx is not None else 0      # the factor indices ride behind the labels in the one integer buffer
         into = getattr(self.ds, "wave_into", None)
         waves = None if into is not None else [self.ds.wave(i) for i in idx]
         smax = max(self.lengths[i] for i in idx) if waves is None else max(w.size for w in waves)
         lmax = max(1, max(len(t) for t in tgt))
-        slot = self._slot(k % self.SLOTS, B * smax, 2 * B + B * lmax)
+        slot = self._slot(k % self.SLOTS, B * smax, 2 * B + B * lmax + nf)
         buf = slot["wave_np"][:B * smax].reshape(B, smax)
-        meta = slot["meta_np"][:2 * B + B * lmax]
-        tg = meta[2 * B:].reshape(B, lmax)
+        meta = slot["meta_np"][:2 * B + B * lmax + nf]
+        tg = meta[2 * B:2 * B + B * lmax].reshape(B, lmax)
         items = getattr(self.ds, "items", None)
         if waves is None and items is not None and any(isinstance(items[i][0], str) for i in idx):
             # files: read / decode the rows in parallel (file reads and numpy loops run without the GIL); 3.4 - 3.8 ms/step against 4 - 6 serially
@@ -251,17 +287,28 @@ class BucketedWaveLoader:
             meta[r], meta[B + r] = sizes[r], len(t)
             tg[r, :len(t)] = t
             tg[r, len(t):] = 0
+        smax_out = 0      # > 0: at least one utterance of the batch is resampled
+        if fidx is not None:
+            pq = self.speed[0]
+            fs = [fidx[i] for i in idx]
+            meta[2 * B + B * lmax:] = fs
+            if any(pq[f][0] != pq[f][1] for f in fs):
+                smax_out = max(1, max(speed_mod.perturbed_len(sizes[r], *pq[f]) for r, f in enumerate(fs)))
         with torch.cuda.stream(self.stream):
             dev_wav = slot["wave"][:B * smax].view(B, smax).to(self.device, non_blocking=True)
             dev_meta = slot["meta"][:meta.size].to(self.device, non_blocking=True)
             slot["copied"].record()
-            feat, feat_len = self.parser.parse_batch(dev_wav, dev_meta[:B], self.dtype, augment=self.augment, rng=self.rng)
-            tgt_dev = dev_meta[2 * B:].view(B, lmax).long()
+            wav_in, len_in = dev_wav, dev_meta[:B]
+            if smax_out:
+                from .. import kernels as K
+                wav_in, len_in = K.speed_perturb(dev_wav, len_in, dev_meta[2 * B + B * lmax:], self.speed[1], self.speed[2], smax_out)
+            feat, feat_len = self.parser.parse_batch(wav_in, len_in, self.dtype, augment=self.augment, rng=self.rng)
+            tgt_dev = dev_meta[2 * B:2 * B + B * lmax].view(B, lmax).long()
             pack = Pack()
             pack.add(wave=feat, wave_len=feat_len.long(), tgt_for_input=tgt_dev, tgt_for_metric=tgt_dev.clone(), tgt_len=dev_meta[B:2 * B].long())
             done = torch.cuda.Event()
             done.record()
-        slot["keep"] = (dev_wav, dev_meta, feat, feat_len) + tuple(v for v in pack.values() if torch.is_tensor(v))
+        slot["keep"] = (dev_wav, dev_meta, wav_in, len_in, feat, feat_len) + tuple(v for v in pack.values() if torch.is_tensor(v))
         return pack, done, slot
 
     PREFETCH = 2      # batches prepared ahead by the helper thread
@@ -271,7 +318,7 @@ class BucketedWaveLoader:
         host-to-device copies and the feature kernels on the loader's stream.  The consumer's stream waits for the batch's event."""
         import queue
         from .. import kernels as K
-        batches = self._batches(self.rng)
+        batches, _, fidx = self.plan.next_epoch()
         q = queue.Queue(maxsize=self.PREFETCH)
         stop = threading.Event()
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()      # the consumer's device
@@ -291,7 +338,7 @@ class BucketedWaveLoader:
                 torch.cuda.set_device(dev_index)
                 for k, idx in enumerate(batches):
                     with self._gate:      # paused() (a hipGraph capture on the consumer thread) keeps this thread off the GPU runtime
-                        item = self._prepare(idx, k)
+                        item = self._prepare(idx, k, fidx)
                     if not hand_over(item):
                         return
                 hand_over(None)
@@ -327,12 +374,13 @@ class BucketedWaveLoader:
 
 def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=True, sample_rate=16000, window_size=400, n_mels=40,
                      augment=False, predump=False, use_old=False, lfr_m=4, lfr_n=3, dtype=torch.bfloat16, shuffle=None, seed=0,
-                     rank=0, world=1):
+                     rank=0, world=1, speed_perturb=None):
     """build_dataloader of the reference (data/data_loader/ai_shell_1.py:91-104), same arguments: reads the manifest
     `<collector_path>_<part>.json` written by the reference's collector (one JSON object {"wave": path, "tgt": text}
     per line, data_collector/ai_shell_1.py:73-79) and returns an iterable of Packs.  The reference computes features
     on the CPU per utterance and can cache them as .t files (predump / use_old); here they are computed on the GPU
-    per batch, so both flags are accepted and ignored.  drop_last=True as in the reference (:103)."""
+    per batch, so both flags are accepted and ignored.  drop_last=True as in the reference (:103).
+    speed_perturb: speed factors such as (0.9, 1.0, 1.1) for BucketedWaveLoader (the reference has none); None = off."""
     import json
     if not use_cuda:
         raise RuntimeError("the feature front end runs on the GPU only (no CPU fallback)")
@@ -347,4 +395,4 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
     ds = WaveDataset(items, vocab, sample_rate=sample_rate)
     parser = AudioParser(sample_rate=sample_rate, n_mels=n_mels, lfr_m=lfr_m, lfr_n=lfr_n, device="cuda")
     return BucketedWaveLoader(ds, batch_size, parser=parser, augment=augment, shuffle=(part == "train") if shuffle is None else shuffle,
-                              drop_last=True, seed=seed, dtype=dtype, rank=rank, world=world)
+                              drop_last=True, seed=seed, dtype=dtype, rank=rank, world=world, speed_perturb=speed_perturb)

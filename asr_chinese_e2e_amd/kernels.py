@@ -868,3 +868,23 @@ def utt_norm_lfr(feat, wav_len, m, n, Tlfr_max, dtype=torch.float32, masks=None)
     check(lib.asr_utt_norm_augment_lfr_fwd(_p(feat), _p(wav_len), _p(masks), _p(out), _p(out_len), B, Tmax, n_mels, m, n, Tlfr_max,
                                            _dt(out), _stream()), "asr_utt_norm_augment_lfr_fwd")
     return out, out_len
+
+
+SPEED_TILE = _lib.SPEED_TILE      # output samples per workgroup of the speed-perturbation kernel
+
+
+def speed_perturb(wav, wav_len, factor, pq, taps, Smax_out, out=None, out_len=None):
+    """Every utterance of wav (B, Smax) f32 resampled by the factor p/q = pq[factor[b]] with the phase table taps[factor[b]]
+    (data_handler.speed.build_tables; include/asr_hip.h: asr_speed_perturb_fwd).  -> (out (B, Smax_out) f32, zero at and beyond each
+    n_out, out_len (B) int32 = n_out = ceil(wav_len q / p)).  Smax_out: at least the largest n_out (data_handler.speed.perturbed_len)."""
+    _chk_f32(wav, taps, out)
+    _chk_i32(wav_len, factor, pq, out_len)
+    B, Smax = wav.shape
+    assert taps.dim() == 3 and pq.dim() == 2 and pq.shape[1] == 2 and pq.shape[0] == taps.shape[0] and wav_len.numel() == B and factor.numel() == B
+    F, qmax, ntaps = taps.shape
+    out = torch.empty(B, Smax_out, dtype=torch.float32, device=wav.device) if out is None else out
+    out_len = torch.empty(B, dtype=torch.int32, device=wav.device) if out_len is None else out_len
+    assert tuple(out.shape) == (B, Smax_out) and out_len.numel() == B and out.data_ptr() != wav.data_ptr()
+    check(lib.asr_speed_perturb_fwd(_p(wav), _p(wav_len), _p(factor), _p(pq), _p(taps), _p(out), _p(out_len), B, Smax, int(Smax_out), F, qmax, ntaps,
+                                    _stream()), "asr_speed_perturb_fwd")
+    return out, out_len

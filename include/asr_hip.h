@@ -639,6 +639,27 @@ int asr_utt_norm_augment_lfr_fwd(const float* feat, const int32_t* wav_len, cons
                                  void* out, int32_t* out_len, int B, int Tmax, int n_mels, int m,
                                  int n, int Tlfr_max, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Speed perturbation of a waveform batch (the 0.9 / 1.0 / 1.1 augmentation of the AISHELL-1 recipes), in front of
+ * asr_logmel_fwd.
+ * Stands in for:  sox / Kaldi `speed` (resampling by p/q, pitch and tempo together).  The reference has no
+ *                 waveform-side augmentation: parity unpinned by the reference; the definition (Hann-windowed sinc,
+ *                 width 6, roll-off 0.99, as torchaudio's resampler) is restated in float64 in tests/speed_ref.py.
+ * wav: (B, Smax) f32, wav_len: (B) int32 samples, factor: (B) int32 index f into pq / taps.  pq: (F, 2) int32 = (p, q)
+ * of factor p/q, 1 <= p <= 20, 1 <= q <= qmax <= 20; taps: (F, qmax, ntaps) f32, ntaps = 2 W + 1 odd,
+ * taps[f][r][j + W] = h(r/q - j) for r < q, every unused entry 0 (narrower filters are centred).  Per utterance
+ *   n_out = ceil(wav_len q / p),   out[b, n] = sum_j wav[b, (n p)/q + j] taps[f][(n p) % q][j + W]   (wav = 0 outside
+ * [0, wav_len)),   out[b, n] = 0 for n_out <= n < Smax_out,   out_len[b] = n_out (never more than Smax_out: pass Smax_out
+ * >= every n_out).  p == q: out[b, :wav_len] = wav[b, :wav_len] bit for bit, the table is not read.  A factor index
+ * outside [0, F) is clamped; a (p, q) outside the ranges above is taken as factor 1.  All index arithmetic is exact
+ * (64 bits where n p can pass 2^31).  out must not alias wav.  16-byte loads and stores are used where wav / out are
+ * 16-byte aligned; any Smax / Smax_out is accepted.
+ */
+#define ASR_SPEED_TILE 1024      /* output samples per workgroup (tests cover the tile edges) */
+int asr_speed_perturb_fwd(const float* wav, const int32_t* wav_len, const int32_t* factor, const int32_t* pq,
+                          const float* taps, float* out, int32_t* out_len, int B, int Smax, int Smax_out, int F,
+                          int qmax, int ntaps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

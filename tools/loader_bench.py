@@ -1,5 +1,8 @@
 """Training from WAVEFORMS: in-memory 5-s utterances -> BucketedWaveLoader (pinned copy + log-mel / normalisation / SpecAugment on a side stream) ->
-model.iterate, against the same model fed one resident batch (what bench.py times).  python tools/loader_bench.py [joint]"""
+model.iterate, against the same model fed one resident batch (what bench.py times).  python tools/loader_bench.py [joint]
+python tools/loader_bench.py --speed_perturb[=0.9,1.0,1.1] [--out=profiles/speed_perturb_bench.json]: the speed-perturbation kernel alone
+(B = 32 x 5 s, factors mixed in thirds) beside a device-to-device copy of the same input plus output bytes, and the waveform-fed joint
+step with the perturbation off and on, alternated in one process; the figures go to the JSON file."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -7,7 +10,8 @@ import torch
 from asr_chinese_e2e_amd import Models
 from asr_chinese_e2e_amd.data_handler import AudioParser, BucketedWaveLoader, Vocab, WaveDataset
 from asr_chinese_e2e_amd.Trainer import FusedAdam, NoamOpt
-JOINT = len(sys.argv) > 1 and sys.argv[1] == "joint"
+SPEED = next((a for a in sys.argv[1:] if a.startswith("--speed_perturb")), None)
+JOINT = SPEED is not None or (len(sys.argv) > 1 and sys.argv[1] == "joint")
 B, S, NB = 32, 16000 * 5, 40
 rng = np.random.RandomState(0)
 vocab = Vocab.synthetic(4232)
@@ -29,6 +33,85 @@ cfg = M.get_default_config()(); cfg.fn_build(dict(n_mels=80, lfr_m=1, dropout=0.
 model = M(cfg, vocab).cuda()
 opt = NoamOpt(512, 1, 4000, FusedAdam(model.parameters(), lr=3e-4, betas=(0.9, 0.98), eps=1e-9))
 loader = BucketedWaveLoader(ds, B, parser=parser, augment=True, shuffle=True, seed=1, dtype=torch.bfloat16)
+
+
+def speed_bench():
+    import json
+    from asr_chinese_e2e_amd import kernels as K
+    from asr_chinese_e2e_amd.data_handler import speed
+    factors = tuple(SPEED.split("=", 1)[1].split(",")) if "=" in SPEED else ("0.9", "1.0", "1.1")
+    out_path = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--out=")), "profiles/speed_perturb_bench.json")
+    pq, taps = speed.build_tables(factors)
+    fac = [i % len(factors) for i in range(B)]                                   # mixed in thirds
+    n_out = [speed.perturbed_len(S, int(pq[f][0]), int(pq[f][1])) for f in fac]
+    smax_out = max(n_out)
+    wav = torch.from_numpy(np.stack([items[i][0] for i in range(B)])).cuda() if not isinstance(items[0][0], str) else torch.randn(B, S, device="cuda") * 0.1
+    wl = torch.full((B,), S, dtype=torch.int32, device="cuda")
+    args = (wav, wl, torch.tensor(fac, dtype=torch.int32, device="cuda"), torch.from_numpy(pq).cuda(), torch.from_numpy(taps).cuda(), smax_out)
+    out, out_len = K.speed_perturb(*args)
+    assert out_len.tolist() == n_out
+    half = (B * S + B * smax_out) // 2                                            # a copy of `half` floats reads and writes the kernel's bytes in all
+    src, dst = torch.randn(half, device="cuda"), torch.empty(half, device="cuda")
+
+    def timed(fn, reps=200):
+        for _ in range(20): fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps): fn()
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3
+    kern, copy = [], []
+    for _ in range(5):                                                            # alternated
+        kern.append(timed(lambda: K.speed_perturb(*args, out=out, out_len=out_len)))
+        copy.append(timed(lambda: dst.copy_(src)))
+    algo_bytes = 4 * (B * S + B * smax_out)                                      # every input sample read once, every output sample (padding included) written once
+    res = dict(device=torch.cuda.get_device_name(0), factors=list(factors), B=B, samples=S, Smax_out=smax_out, ntaps=int(taps.shape[2]), phases=int(taps.shape[1]),
+               kernel_us=kern, kernel_us_median=float(np.median(kern)), bytes_read_plus_written=algo_bytes,
+               kernel_GBps=algo_bytes / float(np.median(kern)) / 1e3,
+               d2d_copy_same_bytes_us=copy, d2d_copy_us_median=float(np.median(copy)), d2d_copy_GBps=8 * half / float(np.median(copy)) / 1e3,
+               timing="HIP events around 200 back-to-back launches after 20 warm-up launches, 5 rounds alternating kernel and copy")
+    print(json.dumps({k: res[k] for k in ("kernel_us_median", "d2d_copy_us_median", "kernel_GBps", "d2d_copy_GBps")}), flush=True)
+    # the waveform-fed joint step, perturbation off and on, alternated; same model, same data set, SpecAugment on
+    mk = lambda sp: BucketedWaveLoader(ds, B, parser=parser, augment=True, shuffle=True, seed=1, dtype=torch.bfloat16, speed_perturb=sp)
+    loaders = dict(off=mk(None), on=mk(factors))
+
+    def run(ld):
+        n = 0
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for pack in ld:
+            model.iterate(pack, optimizer=opt)
+            n += 1
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3
+    for ld in loaders.values(): run(ld)                                           # warm-up epoch each (new shapes: allocator, code objects)
+    step = dict(off=[], on=[])
+    for _ in range(4):
+        for name, ld in loaders.items():
+            step[name].append(run(ld))
+            print(f"joint step from waveforms, speed perturbation {name}: {step[name][-1]:.3f} ms/step", flush=True)
+    prep = {}
+    for name, ld in loaders.items():                                              # host time of preparing a batch alone
+        _, _, fidx = ld.plan.next_epoch()
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for k in range(20): ld._prepare(list(range(B)), k, fidx)
+        prep[name] = (time.perf_counter() - t0) / 20 * 1e3
+        torch.cuda.synchronize()
+    res.update(joint_step_ms_off=step["off"], joint_step_ms_on=step["on"], joint_step_ms_off_median=float(np.median(step["off"])),
+               joint_step_ms_on_median=float(np.median(step["on"])), prepare_host_ms_off=prep["off"], prepare_host_ms_on=prep["on"],
+               joint_config=f"{NB} batches of {B} x 5 s per epoch in host memory, SpecAugment on, bf16 joint model at the default width; 1 warm-up epoch each, "
+                            "then 4 epochs each, alternating off / on; host clock around an epoch that ends in a device synchronise")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out_path)
+
+
+if SPEED is not None:
+    speed_bench()
+    sys.exit(0)
+
+
 def epoch():
     n = 0
     torch.cuda.synchronize(); t0 = time.perf_counter()

@@ -15,6 +15,8 @@ Differences that come with the MI355X path:
   * multi-GPU: launch one process per GPU (python -m torch.distributed.run --nproc-per-node N train.py ...): the model is
     wrapped in dist.DataParallel (bucketed RCCL all-reduce overlapped with backward) and the loaders are sharded by rank -
     the reference's only multi-GPU hook is the commented-out `model.wrap()` (main.py:80);
+  * `--speed_perturb=0.9,1.0,1.1` resamples every training utterance by one of these factors, drawn anew each epoch, on the GPU in
+    front of the log-mel kernel (the reference has no waveform-side augmentation; dev and test are never perturbed);
   * `--synthetic=N` trains on N synthetic AISHELL-1-shaped utterances (no dataset ships with this repository);
   * `--trainer=BaseTrainer` selects the twin of Trainer/base_trainer.py instead of Trainer11.
 """
@@ -59,6 +61,7 @@ class TrainConfig(DataConfigAiShell1):      # main.py:14-36
     synthetic_frames = 500
     synthetic_vocab = 4232
     trainer = "Trainer11"
+    speed_perturb = ()                      # --speed_perturb=0.9,1.0,1.1: speed factors of the train part (never dev / test); empty = off
 
 
 def get_model_class(model_name):            # main.py:38-41
@@ -87,6 +90,16 @@ def parse_flags(argv):
         out[k.replace("-", "_")] = v
         i += 1
     return out
+
+
+def speed_factors(v):
+    """The value of --speed_perturb as a tuple of factors, or None: `0.9,1.0,1.1` parses as a tuple, `0.9` as one number, anything else
+    stays a comma-separated string."""
+    if v is None or v is False or v == "" or v == ():
+        return None
+    if isinstance(v, str):
+        return tuple(x.strip() for x in v.split(",") if x.strip()) or None
+    return tuple(v) if isinstance(v, (tuple, list)) else (v,)
 
 
 class _SyntheticLoader:
@@ -136,7 +149,8 @@ def train(**kwargs):                        # main.py:55-98
         common = dict(collector_path=config.collector_path, vocab=vocab, sample_rate=config.sample_rate, window_size=config.window_size,
                       n_mels=config.n_mels, predump=config.predump, use_old=config.use_old, lfr_m=config.lfr_m, lfr_n=config.lfr_n,
                       rank=rank, world=world)
-        train_iter = build_dataloader(batch_size=config.batch_size, part="train", augment=config.augment, **common)
+        train_iter = build_dataloader(batch_size=config.batch_size, part="train", augment=config.augment, speed_perturb=speed_factors(config.speed_perturb),
+                                      **common)
         test_iter = build_dataloader(batch_size=config.eval_batch_size, part="test", augment=False, **common)
         dev_iter = build_dataloader(batch_size=config.eval_batch_size, part="dev", augment=False, **common)
 
