@@ -329,11 +329,12 @@ class _SpeechTransformer(BaseModel):
                 self._enc_given = prev
         return ctx()
 
-    def stream(self, batch_size):
+    def stream(self, batch_size, parser=None):
         """A streaming encoder for `batch_size` utterances (stream.StreamingEncoder): push chunks of encoder-rate features, get the
-        greedy CTC ids each chunk adds; finish() gives transcribe()'s result for the same decoding chunk mask."""
+        greedy CTC ids each chunk adds; finish() gives transcribe()'s result for the same decoding chunk mask.  With an AudioParser
+        of norm="global" it also takes audio as it arrives: push_audio(pcm, n_samples, final)."""
         from ..stream import StreamingEncoder
-        return StreamingEncoder(self, batch_size)
+        return StreamingEncoder(self, batch_size, parser=parser)
 
     def forward(self, input):
         """transformer_official.py:68-81 (inference-style forward; no gradients).  A batch without a transcript (only wave / wave_len)

@@ -23,6 +23,7 @@ ACT_NONE, ACT_RELU, ACT_RELU_MASK = 0, 1, 2
 ABI_VERSION = 10
 DROP_PRE, DROP_POST = 1, 2
 SPEED_TILE = 1024      # ASR_SPEED_TILE of include/asr_hip.h: output samples per workgroup of asr_speed_perturb_fwd
+STREAM_OPEN = 0x3fffffff      # ASR_STREAM_OPEN: "length not known yet" in the streaming front end's parameter arrays
 
 P, I, F, Z, U = c_void_p, c_int, c_float, c_size_t, c_uint32
 
@@ -135,6 +136,11 @@ SIGNATURES = {
     "asr_utt_norm_lfr_fwd": (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
     "asr_utt_norm_augment_lfr_fwd": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "asr_speed_perturb_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "asr_cmvn_accumulate": (I, [P, P, P, I, I, I, P]),
+    "asr_global_norm_augment_lfr_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "asr_stream_append": (I, [P, P, P, I, I, I, I, I, P]),
+    "asr_stream_logmel": (I, [P, P, P, P, P, I, I, I, I, I, P]),
+    "asr_stream_norm_lfr": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
 }
 
 

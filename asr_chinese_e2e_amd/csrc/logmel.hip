@@ -23,27 +23,24 @@ constexpr int NC = 2 * NBIN;      // 402 DFT output columns (re | im)
 constexpr int CS = 417;           // LDS row stride of C (13 column tiles of 32 = 416, +1)
 constexpr int CT = 13;            // column tiles
 
-__global__ __launch_bounds__(256, 2) void logmel_kernel(const float* __restrict__ wav, const int32_t* __restrict__ wav_len, const float* __restrict__ window,
-                                                     const float* __restrict__ melfb, float* __restrict__ feat, int Smax, int Tmax, int n_mels) {
+// The tile body shared by the offline and the streaming kernel: 32 frames t0 .. t0 + 31 of one utterance.  fetch(idx) is the sample at
+// absolute index idx of [0, len) (how the samples are stored is the caller's business); row(frame) is where frame t0 + frame goes, or
+// nullptr for a row that is not written.  A frame's value depends on its own samples only: every MFMA accumulator row is the
+// sum over its own A row, and the rotation recurrence runs along the columns - so a frame has the same bits in whichever tile
+// and row it is computed, which is what lets streamed frames equal offline ones.
+template <typename Fetch, typename Row>
+__device__ __forceinline__ void logmel_tile(Fetch fetch, Row row, const float* __restrict__ window, const float* __restrict__ melfb, int len, int Tb, int t0,
+                                            int n_mels) {
     __shared__ float buf[FR * CS];            // frames (32 x 401), later C (32 x 417)
     __shared__ float tw_c[NFFT], tw_s[NFFT];
-    const int t0 = blockIdx.x * FR, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int len = wav_len[b];
-    const int Tb = len > 0 ? min(1 + len / HOP, Tmax) : 0;
-    float* out = feat + ((size_t)b * Tmax + t0) * n_mels;
-    const int rows_here = min(FR, Tmax - t0);
-    if (t0 >= Tb) {                            // nothing but padding: zeros
-        for (int i = tid; i < rows_here * n_mels; i += 256) out[i] = 0.f;
-        return;
-    }
-    const float* wv = wav + (size_t)b * Smax;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     for (int i = tid; i < FR * NFFT; i += 256) {
         const int f = i / NFFT, n = i - f * NFFT;
         int idx = (t0 + f) * HOP - NFFT / 2 + n;
         if (idx < 0) idx = -idx;                       // reflect (no edge repeat)
         if (idx >= len) idx = 2 * (len - 1) - idx;
         idx = idx < 0 ? 0 : (idx >= len ? len - 1 : idx);
-        buf[f * XS + n] = (t0 + f < Tb) ? wv[idx] * window[n] : 0.f;
+        buf[f * XS + n] = (t0 + f < Tb) ? fetch(idx) * window[n] : 0.f;
     }
     for (int n = tid; n < NFFT; n += 256) {            // exact cos / sin(2 pi n / 400): start values and rotation steps
         float sv, cv;
@@ -133,10 +130,46 @@ __global__ __launch_bounds__(256, 2) void logmel_kernel(const float* __restrict_
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int frame = (i & 3) + 8 * (i >> 2) + 4 * kh;
-                if (frame < rows_here) out[(size_t)frame * n_mels + m] = (t0 + frame < Tb) ? logf(o[i] + 1e-20f) : 0.f;
+                float* dst = row(frame);
+                if (dst) dst[m] = (t0 + frame < Tb) ? logf(o[i] + 1e-20f) : 0.f;
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256, 2) void logmel_kernel(const float* __restrict__ wav, const int32_t* __restrict__ wav_len, const float* __restrict__ window,
+                                                     const float* __restrict__ melfb, float* __restrict__ feat, int Smax, int Tmax, int n_mels) {
+    const int t0 = blockIdx.x * FR, b = blockIdx.y, tid = threadIdx.x;
+    const int len = wav_len[b];
+    const int Tb = len > 0 ? min(1 + len / HOP, Tmax) : 0;
+    float* out = feat + ((size_t)b * Tmax + t0) * n_mels;
+    const int rows_here = min(FR, Tmax - t0);
+    if (t0 >= Tb) {                            // nothing but padding: zeros
+        for (int i = tid; i < rows_here * n_mels; i += 256) out[i] = 0.f;
+        return;
+    }
+    const float* wv = wav + (size_t)b * Smax;
+    logmel_tile([=](int idx) { return wv[idx]; }, [=](int frame) { return frame < rows_here ? out + (size_t)frame * n_mels : nullptr; }, window, melfb, len, Tb,
+                t0, n_mels);
+}
+
+// Streaming: frames [t_begin, t_begin + n_new) of each utterance from a ring of its most recent samples, into a ring of its most
+// recent frames.  par[b] = {t_begin, n_new, total}: total = the utterance's length in samples once it is closed (the end is then
+// reflected and clamped as above, and the last frame is 1 + total / 160 - 1), ASR_STREAM_OPEN while it is open (no frame the
+// host asks for touches the end then).  Sample s lives at wav_ring[b][s & (scap - 1)], frame t at feat_ring[b][t & (fcap - 1)].
+__global__ __launch_bounds__(256, 2) void stream_logmel_kernel(const float* __restrict__ wav_ring, const int32_t* __restrict__ par, const float* __restrict__ window,
+                                                            const float* __restrict__ melfb, float* __restrict__ feat_ring, int scap, int fcap, int n_mels) {
+    const int b = blockIdx.y;
+    const int t_begin = par[3 * b], n_new = par[3 * b + 1], len = par[3 * b + 2];
+    const int f0 = blockIdx.x * FR;
+    if (f0 >= n_new) return;
+    const int t0 = t_begin + f0;
+    const int Tb = 1 + len / HOP;              // closed: the host never asks for a frame of an empty utterance
+    const float* wv = wav_ring + (size_t)b * scap;
+    float* fr = feat_ring + (size_t)b * fcap * n_mels;
+    const int smask = scap - 1, fmask = fcap - 1, rows_here = n_new - f0;
+    logmel_tile([=](int idx) { return wv[idx & smask]; },
+                [=](int frame) { return frame < rows_here ? fr + (size_t)((t0 + frame) & fmask) * n_mels : nullptr; }, window, melfb, len, Tb, t0, n_mels);
 }
 
 template <typename T>
@@ -195,6 +228,137 @@ __global__ __launch_bounds__(1024) void utt_norm_lfr_kernel(const float* __restr
     if (tid == 0) out_len[b] = Tl;
 }
 
+// ---- global CMVN ------------------------------------------------------------------------------------------------------------------
+// Corpus statistics: per mel bin sum x, sum x^2 over every valid frame (t < Tb), and the frame count, added to float64 accumulators
+// acc[0 .. n_mels) | acc[n_mels .. 2 n_mels) | acc[2 n_mels] that persist across launches.  One workgroup = CMVN_ROWS frames of
+// one utterance; thread (g, c) sums rows g, g + G, .. of column c in float64 (consecutive threads read consecutive bins), the
+// G partial sums of a column meet in LDS, and one float64 vector atomic per column and workgroup reaches memory.
+constexpr int CMVN_ROWS = 64, CMVN_MAX_MELS = 256;
+
+__global__ __launch_bounds__(256) void cmvn_stats_kernel(const float* __restrict__ feat, const int32_t* __restrict__ wav_len, double* __restrict__ acc, int Tmax,
+                                                         int n_mels) {
+    __shared__ double red[2][256];
+    const int b = blockIdx.y, t0 = blockIdx.x * CMVN_ROWS, tid = threadIdx.x;
+    const int len = wav_len[b];
+    const int Tb = len > 0 ? min(1 + len / HOP, Tmax) : 0;
+    const int rows = min(CMVN_ROWS, Tb - t0);
+    if (rows <= 0) return;
+    const int G = 256 / n_mels, g = tid / n_mels, c = tid - g * n_mels;
+    double s = 0., q = 0.;
+    if (g < G) {
+        const float* f = feat + ((size_t)b * Tmax + t0) * n_mels + c;
+        for (int r = g; r < rows; r += G) {
+            const double x = (double)f[(size_t)r * n_mels];
+            s += x;
+            q += x * x;
+        }
+    }
+    red[0][tid] = s;
+    red[1][tid] = q;
+    __syncthreads();
+    if (tid < n_mels) {
+        for (int k = 1; k < G; ++k) {
+            s += red[0][tid + k * n_mels];
+            q += red[1][tid + k * n_mels];
+        }
+        atomicAdd(acc + tid, s);
+        atomicAdd(acc + n_mels + tid, q);
+    }
+    if (tid == 0) atomicAdd(acc + 2 * n_mels, (double)rows);
+}
+
+// The one place the global normalisation is written: element (LFR row r, column c) of an utterance of Tb frames, frame_at(t) = the
+// log-mel row of frame t.  src = min(r n + j, Tb - 1) (tail rows repeat the last frame), then one subtraction and one
+// multiplication in fp32.  The offline and the streaming kernel both call it, so their rows agree bit for bit.
+template <typename FrameAt>
+__device__ __forceinline__ float cmvn_lfr_elem(FrameAt frame_at, int r, int c, int n_mels, int n, int Tb, const float* __restrict__ mean,
+                                               const float* __restrict__ istd, int* src_out, int* mm_out) {
+    const int j = c / n_mels, mm = c - j * n_mels;
+    const int src = min(r * n + j, Tb - 1);
+    *src_out = src;
+    *mm_out = mm;
+    return (frame_at(src)[mm] - mean[mm]) * istd[mm];
+}
+
+// Global normalisation + SpecAugment + LFR: utt_norm_lfr_kernel without its two statistics passes.  Without masks it is elementwise
+// and the grid's x dimension tiles the output; with masks one workgroup per utterance first reduces the two fill values.
+template <typename T>
+__global__ __launch_bounds__(1024) void global_norm_lfr_kernel(const float* __restrict__ feat, const int32_t* __restrict__ wav_len, const int32_t* __restrict__ masks,
+                                                               const float* __restrict__ mean, const float* __restrict__ istd, T* __restrict__ out,
+                                                               int32_t* __restrict__ out_len, int Tmax, int n_mels, int m, int n, int Tlfr_max) {
+    __shared__ float red[16];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int len = wav_len[b];
+    const int Tb = len > 0 ? min(1 + len / HOP, Tmax) : 0;
+    const int Tl = min((Tb + n - 1) / n, Tlfr_max);
+    const float* f = feat + (size_t)b * Tmax * n_mels;
+    const int cnt = Tb * n_mels;
+    int t0 = 0, t1 = 0, f0 = 0, f1 = 0;
+    float fill_t = 0.f, fill_f = 0.f;
+    if (masks) {                               // the semantics of utt_norm_lfr_kernel's masks (gridDim.x == 1 here)
+        t0 = min(max(masks[4 * b + 0], 0), Tb);
+        t1 = min(max(masks[4 * b + 1], t0), Tb);
+        f0 = min(max(masks[4 * b + 2], 0), n_mels);
+        f1 = min(max(masks[4 * b + 3], f0), n_mels);
+        float sa = 0.f, sm = 0.f;
+        for (int i = tid; i < cnt; i += 1024) {
+            const int t = i / n_mels, mm = i - t * n_mels;
+            const float v = (f[i] - mean[mm]) * istd[mm];
+            sa += v;
+            if (t >= t0 && t < t1) sm += v;
+        }
+        const float sum_all = block_sum(sa, red), sum_masked = block_sum(sm, red);
+        fill_t = cnt > 0 ? sum_all / (float)cnt : 0.f;
+        fill_f = cnt > 0 ? (sum_all - sum_masked + (float)((t1 - t0) * n_mels) * fill_t) / (float)cnt : 0.f;
+    }
+    const int W = m * n_mels;
+    T* o = out + (size_t)b * Tlfr_max * W;
+    const int total = Tlfr_max * W;
+    for (int i = blockIdx.x * 1024 + tid; i < total; i += gridDim.x * 1024) {
+        const int r = i / W, c = i - r * W;
+        float val = 0.f;
+        if (r < Tl) {
+            int src, mm;
+            val = cmvn_lfr_elem([=](int t) { return f + (size_t)t * n_mels; }, r, c, n_mels, n, Tb, mean, istd, &src, &mm);
+            if (mm >= f0 && mm < f1) val = fill_f;
+            else if (src >= t0 && src < t1) val = fill_t;
+        }
+        o[i] = from_f32<T>(val);
+    }
+    if (tid == 0 && blockIdx.x == 0) out_len[b] = Tl;
+}
+
+// Streaming: LFR rows [r_begin, r_begin + n_rows) of each utterance out of its frame ring into one encoder chunk (B, C, m n_mels),
+// rows past n_rows zero.  par[b] = {r_begin, n_rows, Tb}: Tb = the utterance's frame count once it is closed, ASR_STREAM_OPEN before.
+template <typename T>
+__global__ __launch_bounds__(256) void stream_norm_lfr_kernel(const float* __restrict__ feat_ring, const int32_t* __restrict__ par, const float* __restrict__ mean,
+                                                              const float* __restrict__ istd, T* __restrict__ out, int fcap, int n_mels, int m, int n, int C) {
+    const int b = blockIdx.y;
+    const int r_begin = par[3 * b], n_rows = par[3 * b + 1], Tb = par[3 * b + 2];
+    const float* f = feat_ring + (size_t)b * fcap * n_mels;
+    const int fmask = fcap - 1, W = m * n_mels, total = C * W;
+    T* o = out + (size_t)b * total;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        const int r = i / W, c = i - r * W;
+        float val = 0.f;
+        if (r < n_rows) {
+            int src, mm;
+            val = cmvn_lfr_elem([=](int t) { return f + (size_t)(t & fmask) * n_mels; }, r_begin + r, c, n_mels, n, Tb, mean, istd, &src, &mm);
+        }
+        o[i] = from_f32<T>(val);
+    }
+}
+
+// Streaming: n_new[b] new samples of pcm (B, S) go behind the received[b] samples each utterance's ring has seen: par[b] = {received, n_new}.
+__global__ __launch_bounds__(256) void stream_append_kernel(const float* __restrict__ pcm, const int32_t* __restrict__ par, float* __restrict__ wav_ring, int S,
+                                                            int pcm_off, int max_new, int scap) {
+    const int b = blockIdx.y;
+    const int received = par[2 * b], n_new = min(par[2 * b + 1], max_new);      // never past the row of pcm
+    const float* src = pcm + (size_t)b * S + pcm_off;
+    float* ring = wav_ring + (size_t)b * scap;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n_new; i += gridDim.x * 256) ring[(received + i) & (scap - 1)] = src[i];
+}
+
 }  // namespace
 
 extern "C" int asr_logmel_fwd(const float* wav, const int32_t* wav_len, const float* window, const float* melfb, float* feat, int B, int Smax, int Tmax,
@@ -222,4 +386,70 @@ extern "C" int asr_utt_norm_augment_lfr_fwd(const float* feat, const int32_t* wa
 extern "C" int asr_utt_norm_lfr_fwd(const float* feat, const int32_t* wav_len, void* out, int32_t* out_len, int B, int Tmax, int n_mels, int m, int n,
                                     int Tlfr_max, int dtype, void* stream) {
     return asr_utt_norm_augment_lfr_fwd(feat, wav_len, nullptr, out, out_len, B, Tmax, n_mels, m, n, Tlfr_max, dtype, stream);
+}
+
+// ---- global CMVN and the streaming front end -----------------------------------------------------------------------------------------
+extern "C" int asr_cmvn_accumulate(const float* feat, const int32_t* wav_len, double* acc, int B, int Tmax, int n_mels, void* stream) {
+    if (!feat || !wav_len || !acc) ASR_FAIL(ASR_EINVAL, "asr_cmvn_accumulate: null pointer");
+    if (B <= 0 || B > 65535 || Tmax <= 0 || n_mels <= 0 || n_mels > CMVN_MAX_MELS)
+        ASR_FAIL(ASR_EINVAL, "asr_cmvn_accumulate: bad shape B=%d Tmax=%d n_mels=%d (n_mels at most %d)", B, Tmax, n_mels, CMVN_MAX_MELS);
+    dim3 grid(ceil_div(Tmax, CMVN_ROWS), B);
+    cmvn_stats_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(feat, wav_len, acc, Tmax, n_mels);
+    ASR_CHECK_LAUNCH("asr_cmvn_accumulate");
+    return ASR_OK;
+}
+
+extern "C" int asr_global_norm_augment_lfr_fwd(const float* feat, const int32_t* wav_len, const int32_t* masks, const float* mean, const float* istd, void* out,
+                                               int32_t* out_len, int B, int Tmax, int n_mels, int m, int n, int Tlfr_max, int dtype, void* stream) {
+    if (!feat || !wav_len || !mean || !istd || !out || !out_len) ASR_FAIL(ASR_EINVAL, "asr_global_norm_augment_lfr_fwd: null pointer");
+    if (B <= 0 || B > 65535 || Tmax <= 0 || n_mels <= 0 || m <= 0 || n <= 0 || Tlfr_max <= 0)
+        ASR_FAIL(ASR_EINVAL, "asr_global_norm_augment_lfr_fwd: bad shape B=%d Tmax=%d n_mels=%d m=%d n=%d Tlfr_max=%d", B, Tmax, n_mels, m, n, Tlfr_max);
+    if ((long long)Tlfr_max * m * n_mels > INT32_MAX) ASR_FAIL(ASR_EINVAL, "asr_global_norm_augment_lfr_fwd: Tlfr_max * m * n_mels does not fit an int");
+    hipStream_t st = (hipStream_t)stream;
+    // 4 elements per thread without masks; with masks one workgroup per utterance owns the fill reductions
+    dim3 grid(masks ? 1 : max(1, min(ceil_div(Tlfr_max * m * n_mels, 4096), 256)), B);
+    if (dtype == ASR_F32) global_norm_lfr_kernel<float><<<grid, 1024, 0, st>>>(feat, wav_len, masks, mean, istd, (float*)out, out_len, Tmax, n_mels, m, n, Tlfr_max);
+    else if (dtype == ASR_BF16) global_norm_lfr_kernel<bf16_t><<<grid, 1024, 0, st>>>(feat, wav_len, masks, mean, istd, (bf16_t*)out, out_len, Tmax, n_mels, m, n, Tlfr_max);
+    else ASR_FAIL(ASR_EDTYPE, "asr_global_norm_augment_lfr_fwd: dtype %d", dtype);
+    ASR_CHECK_LAUNCH("asr_global_norm_augment_lfr_fwd");
+    return ASR_OK;
+}
+
+static bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+
+extern "C" int asr_stream_append(const float* pcm, const int32_t* par, float* wav_ring, int B, int S, int pcm_off, int max_new, int scap, void* stream) {
+    if (!pcm || !par || !wav_ring) ASR_FAIL(ASR_EINVAL, "asr_stream_append: null pointer");
+    if (B <= 0 || B > 65535 || S <= 0 || pcm_off < 0 || max_new <= 0 || pcm_off > S - max_new || !pow2(scap) || max_new > scap)
+        ASR_FAIL(ASR_EINVAL, "asr_stream_append: bad shape B=%d S=%d pcm_off=%d max_new=%d scap=%d (scap a power of two, pcm_off + max_new <= S, max_new <= scap)",
+                 B, S, pcm_off, max_new, scap);
+    dim3 grid(min(ceil_div(max_new, 1024), 64), B);
+    stream_append_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(pcm, par, wav_ring, S, pcm_off, max_new, scap);
+    ASR_CHECK_LAUNCH("asr_stream_append");
+    return ASR_OK;
+}
+
+extern "C" int asr_stream_logmel(const float* wav_ring, const int32_t* par, const float* window, const float* melfb, float* feat_ring, int B, int max_new, int scap,
+                                 int fcap, int n_mels, void* stream) {
+    if (!wav_ring || !par || !window || !melfb || !feat_ring) ASR_FAIL(ASR_EINVAL, "asr_stream_logmel: null pointer");
+    if (B <= 0 || B > 65535 || max_new <= 0 || n_mels <= 0 || !pow2(scap) || scap < 1024 || !pow2(fcap) || max_new > fcap)
+        ASR_FAIL(ASR_EINVAL, "asr_stream_logmel: bad shape B=%d max_new=%d scap=%d fcap=%d n_mels=%d (scap >= 1024 and fcap powers of two, max_new <= fcap)", B,
+                 max_new, scap, fcap, n_mels);
+    dim3 grid(ceil_div(max_new, FR), B);
+    stream_logmel_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(wav_ring, par, window, melfb, feat_ring, scap, fcap, n_mels);
+    ASR_CHECK_LAUNCH("asr_stream_logmel");
+    return ASR_OK;
+}
+
+extern "C" int asr_stream_norm_lfr(const float* feat_ring, const int32_t* par, const float* mean, const float* istd, void* out, int B, int C, int fcap, int n_mels,
+                                   int m, int n, int dtype, void* stream) {
+    if (!feat_ring || !par || !mean || !istd || !out) ASR_FAIL(ASR_EINVAL, "asr_stream_norm_lfr: null pointer");
+    if (B <= 0 || B > 65535 || C <= 0 || n_mels <= 0 || m <= 0 || n <= 0 || !pow2(fcap) || (long long)C * m * n_mels > INT32_MAX)
+        ASR_FAIL(ASR_EINVAL, "asr_stream_norm_lfr: bad shape B=%d C=%d fcap=%d n_mels=%d m=%d n=%d (fcap a power of two)", B, C, fcap, n_mels, m, n);
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid(max(1, min(ceil_div(C * m * n_mels, 1024), 64)), B);
+    if (dtype == ASR_F32) stream_norm_lfr_kernel<float><<<grid, 256, 0, st>>>(feat_ring, par, mean, istd, (float*)out, fcap, n_mels, m, n, C);
+    else if (dtype == ASR_BF16) stream_norm_lfr_kernel<bf16_t><<<grid, 256, 0, st>>>(feat_ring, par, mean, istd, (bf16_t*)out, fcap, n_mels, m, n, C);
+    else ASR_FAIL(ASR_EDTYPE, "asr_stream_norm_lfr: dtype %d", dtype);
+    ASR_CHECK_LAUNCH("asr_stream_norm_lfr");
+    return ASR_OK;
 }

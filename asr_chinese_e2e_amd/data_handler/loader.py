@@ -372,15 +372,22 @@ class BucketedWaveLoader:
                 last["consumed"].record(torch.cuda.current_stream())
                 last["handed"] = True
 
+def parser_norm(cmvn):
+    """AudioParser's normalisation arguments for the value of a cmvn flag: a path selects global CMVN, None / empty today's."""
+    return dict(norm="global", cmvn=str(cmvn)) if cmvn else {}
+
+
 def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=True, sample_rate=16000, window_size=400, n_mels=40,
                      augment=False, predump=False, use_old=False, lfr_m=4, lfr_n=3, dtype=torch.bfloat16, shuffle=None, seed=0,
-                     rank=0, world=1, speed_perturb=None):
+                     rank=0, world=1, speed_perturb=None, cmvn=None):
     """build_dataloader of the reference (data/data_loader/ai_shell_1.py:91-104), same arguments: reads the manifest
     `<collector_path>_<part>.json` written by the reference's collector (one JSON object {"wave": path, "tgt": text}
     per line, data_collector/ai_shell_1.py:73-79) and returns an iterable of Packs.  The reference computes features
     on the CPU per utterance and can cache them as .t files (predump / use_old); here they are computed on the GPU
     per batch, so both flags are accepted and ignored.  drop_last=True as in the reference (:103).
-    speed_perturb: speed factors such as (0.9, 1.0, 1.1) for BucketedWaveLoader (the reference has none); None = off."""
+    speed_perturb: speed factors such as (0.9, 1.0, 1.1) for BucketedWaveLoader (the reference has none); None = off.
+    cmvn: path of a global-CMVN statistics file (tools/compute_cmvn.py): the features of this part are normalised per mel bin by
+    the corpus statistics (AudioParser norm="global"); None / empty = the reference's per-utterance normalisation."""
     import json
     if not use_cuda:
         raise RuntimeError("the feature front end runs on the GPU only (no CPU fallback)")
@@ -393,6 +400,6 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
                 rec = json.loads(line)
                 items.append((rec["wave"], rec["tgt"]))
     ds = WaveDataset(items, vocab, sample_rate=sample_rate)
-    parser = AudioParser(sample_rate=sample_rate, n_mels=n_mels, lfr_m=lfr_m, lfr_n=lfr_n, device="cuda")
+    parser = AudioParser(sample_rate=sample_rate, n_mels=n_mels, lfr_m=lfr_m, lfr_n=lfr_n, device="cuda", **parser_norm(cmvn))
     return BucketedWaveLoader(ds, batch_size, parser=parser, augment=augment, shuffle=(part == "train") if shuffle is None else shuffle,
                               drop_last=True, seed=seed, dtype=dtype, rank=rank, world=world, speed_perturb=speed_perturb)

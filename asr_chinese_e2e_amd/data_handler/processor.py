@@ -1,6 +1,8 @@
 """Log-mel front end on the GPU (Predictor/data_handler/processor.py:18-100 of the reference ran
-torchaudio on the CPU): waveform batch -> log-mel -> scalar mean/std normalisation -> LFR."""
+torchaudio on the CPU): waveform batch -> log-mel -> scalar mean/std normalisation -> LFR.
+norm="global" normalises every mel bin by corpus statistics instead (cmvn.py): the variant that can stream."""
 import math
+import os
 
 import numpy as np
 import random
@@ -8,6 +10,7 @@ import random
 import torch
 
 from .. import kernels as K
+from .cmvn import load_cmvn
 
 SR, N_FFT, HOP = 16000, 400, 160
 
@@ -58,9 +61,24 @@ class AudioParser:
     """Batched device front end: parse_batch(wav (B,S) f32 cuda, wav_len (B) int) ->
     (features (B, T_lfr, lfr_m*n_mels), feature_len (B) int32)."""
 
-    def __init__(self, sample_rate=SR, n_mels=80, window_size=N_FFT, hop=HOP, lfr_m=4, lfr_n=3, device="cuda"):
+    def __init__(self, sample_rate=SR, n_mels=80, window_size=N_FFT, hop=HOP, lfr_m=4, lfr_n=3, device="cuda", norm="utterance", cmvn=None):
+        """norm: "utterance" (the reference's scalar mean / std of each utterance) or "global" (per-bin corpus statistics): then
+        cmvn = (mean, istd), one value per mel bin, or the path of a file tools/compute_cmvn.py wrote."""
         assert sample_rate == SR and window_size == N_FFT and hop == HOP, "kernel is specialised to 16 kHz / 400 / 160"
-        self.n_mels, self.lfr_m, self.lfr_n = n_mels, lfr_m, lfr_n
+        if norm not in ("utterance", "global"):
+            raise ValueError(f"norm must be 'utterance' or 'global', got {norm!r}")
+        self.n_mels, self.lfr_m, self.lfr_n, self.norm = n_mels, lfr_m, lfr_n, norm
+        self.mean = self.istd = None
+        if norm == "global":
+            if cmvn is None or (isinstance(cmvn, str) and not cmvn):
+                raise ValueError("norm='global' needs cmvn=(mean, istd) or the path of a statistics file (tools/compute_cmvn.py)")
+            mean, istd = load_cmvn(cmvn)[:2] if isinstance(cmvn, (str, os.PathLike)) else cmvn
+            mean, istd = (np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.float64) for v in (mean, istd))
+            if mean.shape != (n_mels,) or istd.shape != (n_mels,):
+                raise ValueError(f"cmvn statistics are for {mean.shape} / {istd.shape} mel bins, the parser has {n_mels}")
+            self.mean, self.istd = (torch.from_numpy(v.astype(np.float32)).to(device) for v in (mean, istd))
+        elif cmvn is not None:
+            raise ValueError("cmvn statistics given, but norm is 'utterance': pass norm='global' to use them")
         self.window = torch.hann_window(N_FFT, periodic=True, dtype=torch.float32).to(device)
         self.melfb = mel_filterbank(n_mels).to(device)
 
@@ -77,4 +95,6 @@ class AudioParser:
         if augment:
             frames = [min(1 + int(l) // HOP, Tmax) if int(l) > 0 else 0 for l in wav_len.tolist()]
             masks = torch.tensor([sample_spec_augment(self.n_mels, fr, rng) for fr in frames], dtype=torch.int32).to(wav.device)
+        if self.norm == "global":
+            return K.global_norm_lfr(feat, wl, self.mean, self.istd, self.lfr_m, self.lfr_n, Tl, dtype, masks=masks)
         return K.utt_norm_lfr(feat, wl, self.lfr_m, self.lfr_n, Tl, dtype, masks=masks)

@@ -888,3 +888,71 @@ def speed_perturb(wav, wav_len, factor, pq, taps, Smax_out, out=None, out_len=No
     check(lib.asr_speed_perturb_fwd(_p(wav), _p(wav_len), _p(factor), _p(pq), _p(taps), _p(out), _p(out_len), B, Smax, int(Smax_out), F, qmax, ntaps,
                                     _stream()), "asr_speed_perturb_fwd")
     return out, out_len
+
+
+# --------------------------------------------------------------------------------- global CMVN, streaming front end
+STREAM_OPEN = _lib.STREAM_OPEN
+
+
+def cmvn_accumulate(feat, wav_len, acc):
+    """acc (2 n_mels + 1) float64 += per-bin sum, sum of squares and the frame count of the valid frames of feat (B, Tmax, n_mels)
+    (include/asr_hip.h: asr_cmvn_accumulate)."""
+    _chk_f32(feat)
+    _chk_i32(wav_len)
+    B, Tmax, n_mels = feat.shape
+    if acc.dtype != torch.float64 or not acc.is_contiguous() or acc.numel() != 2 * n_mels + 1:
+        raise ValueError(f"acc must be a contiguous float64 tensor of 2 * n_mels + 1 = {2 * n_mels + 1} elements")
+    assert wav_len.numel() == B
+    check(lib.asr_cmvn_accumulate(_p(feat), _p(wav_len), _p(acc), B, Tmax, n_mels, _stream()), "asr_cmvn_accumulate")
+    return acc
+
+
+def global_norm_lfr(feat, wav_len, mean, istd, m, n, Tlfr_max, dtype=torch.float32, masks=None):
+    """utt_norm_lfr under global CMVN: (x - mean[bin]) * istd[bin]; mean, istd (n_mels) f32."""
+    _chk_f32(feat, mean, istd)
+    _chk_i32(wav_len, masks)
+    B, Tmax, n_mels = feat.shape
+    assert masks is None or tuple(masks.shape) == (B, 4)
+    assert mean.numel() == n_mels and istd.numel() == n_mels and wav_len.numel() == B
+    out = torch.empty(B, Tlfr_max, m * n_mels, dtype=dtype, device=feat.device)
+    out_len = torch.empty(B, dtype=torch.int32, device=feat.device)
+    check(lib.asr_global_norm_augment_lfr_fwd(_p(feat), _p(wav_len), _p(masks), _p(mean), _p(istd), _p(out), _p(out_len), B, Tmax, n_mels, m, n,
+                                              Tlfr_max, _dt(out), _stream()), "asr_global_norm_augment_lfr_fwd")
+    return out, out_len
+
+
+def _pow2(v):
+    return v > 0 and v & (v - 1) == 0
+
+
+def stream_append(pcm, par, wav_ring, pcm_off, max_new):
+    """Samples pcm[b, pcm_off : pcm_off + n_new[b]] go behind the received[b] samples of ring b: par (B, 2) int32 = {received, n_new}."""
+    _chk_f32(pcm, wav_ring)
+    _chk_i32(par)
+    B, S = pcm.shape
+    assert tuple(par.shape) == (B, 2) and wav_ring.shape[0] == B and _pow2(wav_ring.shape[1]) and 0 <= pcm_off and pcm_off + max_new <= S
+    check(lib.asr_stream_append(_p(pcm), _p(par), _p(wav_ring), B, S, int(pcm_off), int(max_new), wav_ring.shape[1], _stream()), "asr_stream_append")
+
+
+def stream_logmel(wav_ring, par, window, melfb, feat_ring, max_new):
+    """Frames t_begin .. t_begin + n_new - 1 of every utterance from its sample ring into its frame ring: par (B, 3) int32 =
+    {t_begin, n_new, total samples or STREAM_OPEN}."""
+    _chk_f32(wav_ring, window, melfb, feat_ring)
+    _chk_i32(par)
+    B, scap = wav_ring.shape
+    _, fcap, n_mels = feat_ring.shape
+    assert tuple(par.shape) == (B, 3) and feat_ring.shape[0] == B and melfb.shape == (201, n_mels) and window.numel() == 400
+    check(lib.asr_stream_logmel(_p(wav_ring), _p(par), _p(window), _p(melfb), _p(feat_ring), B, int(max_new), scap, fcap, n_mels, _stream()),
+          "asr_stream_logmel")
+
+
+def stream_norm_lfr(feat_ring, par, mean, istd, m, n, C, dtype=torch.float32):
+    """One encoder chunk (B, C, m n_mels) out of the frame rings under global CMVN: par (B, 3) int32 = {r_begin, n_rows, frames or STREAM_OPEN}."""
+    _chk_f32(feat_ring, mean, istd)
+    _chk_i32(par)
+    B, fcap, n_mels = feat_ring.shape
+    assert tuple(par.shape) == (B, 3) and mean.numel() == n_mels and istd.numel() == n_mels
+    out = torch.empty(B, C, m * n_mels, dtype=dtype, device=feat_ring.device)
+    check(lib.asr_stream_norm_lfr(_p(feat_ring), _p(par), _p(mean), _p(istd), _p(out), B, int(C), fcap, n_mels, m, n, _dt(out), _stream()),
+          "asr_stream_norm_lfr")
+    return out

@@ -9,6 +9,8 @@ PREFIX only; with left = -1 it grows (doubling, at most to the positional-encodi
 
 Per push: input projection, LayerNorm + positional encoding at the chunk's absolute frame offset, the L encoder layers on B * C rows,
 the CTC head and its frame-wise argmax - the engine's kernels (gemm_small / NT, sdpa_fwd, add_ln_fwd, asr_ctc_frame_argmax).
+
+push_audio takes samples instead: a StreamingFrontEnd (data_handler/stream_frontend.py) turns them into chunks, each of which is pushed.
 """
 import torch
 
@@ -19,7 +21,7 @@ BLANK = 0      # the CTC blank (= PAD_ID of the model)
 
 
 class StreamingEncoder:
-    def __init__(self, model, batch_size):
+    def __init__(self, model, batch_size, parser=None):
         C, left = model.decoding_chunk_size, model.decoding_left_chunks
         if C <= 0:
             raise ValueError("model.stream() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
@@ -35,6 +37,7 @@ class StreamingEncoder:
         self.cap = 0                         # cache rows per utterance
         self.caches = None                   # [buffer][layer] -> (B * cap, 2 H dk); the second buffer only with left >= 0 (_slide)
         self.outs, self.feats = [], []
+        self.parser, self.frontend = parser, None      # the front end is built by the first push_audio
 
     def _grow(self, eng, need, dev):
         hd2 = 2 * eng.H * eng.dk
@@ -132,6 +135,30 @@ class StreamingEncoder:
                 self.ended[b] = True
         self.offset += C
         return out
+
+    def _ensure_frontend(self):
+        if self.parser is None:
+            raise ValueError("push_audio: this stream has no front end - model.stream(B, parser=AudioParser(norm='global', cmvn=...))")
+        if self.frontend is None:
+            from .data_handler.stream_frontend import StreamingFrontEnd
+            eng = self.model._ensure_engine(self.parser.window.device)
+            self.frontend = StreamingFrontEnd(self.parser, self.B, self.C, dtype=eng.dtype)
+
+    def push_audio(self, pcm, n_samples, final):
+        """pcm (B, S) f32 on the host or the device: n_samples[b] <= S new samples of utterance b (0 is fine), final[b] closes it.  Runs
+        every chunk the audio completes (StreamingFrontEnd: the utterances advance in lock-step) and returns per utterance the greedy CTC
+        ids they add.  Needs model.stream(B, parser=...) with a parser of norm="global"; audio for a closed utterance raises."""
+        out = [[] for _ in range(self.B)]
+        for _, ids in self.push_audio_chunks(pcm, n_samples, final):
+            for b in range(self.B):
+                out[b] += ids[b]
+        return out
+
+    def push_audio_chunks(self, pcm, n_samples, final):
+        """push_audio chunk by chunk: yields (n_valid, ids) = push()'s arguments and result for every chunk the audio completes."""
+        self._ensure_frontend()
+        for feats, nv in self.frontend.push_audio(pcm, n_samples, final):
+            yield nv, self.push(feats, nv)
 
     def encoder_output(self):
         """(enc (B, T, d) with T = chunks pushed * C, lengths (B,) int32): frames past an utterance's length are not meaningful."""

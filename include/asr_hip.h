@@ -660,6 +660,54 @@ int asr_speed_perturb_fwd(const float* wav, const int32_t* wav_len, const int32_
                           const float* taps, float* out, int32_t* out_len, int B, int Smax, int Smax_out, int F,
                           int qmax, int ntaps, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Global CMVN: one mean and one inverse standard deviation per mel bin, fixed for a corpus (WeNet / ESPnet / Kaldi
+ * global_cmvn), as the alternative to the per-utterance scalar normalisation above - the one that can stream.
+ * Stands in for:  nothing in the reference (it has no global CMVN): parity unpinned by the reference; the definition is
+ *                 restated in float64 in tests/cmvn_ref.py.
+ *
+ * asr_cmvn_accumulate: feat (B, Tmax, n_mels) f32 as asr_logmel_fwd writes it.  acc: 2 n_mels + 1 doubles that persist
+ * across calls (zero them once): acc[m] += sum x, acc[n_mels + m] += sum x^2 over every valid frame (t < Tb,
+ * Tb = min(1 + wav_len / 160, Tmax), 0 for wav_len = 0), acc[2 n_mels] += the number of such frames.  n_mels <= 256.
+ * The host then takes mean = sum / N, var = sumsq / N - mean^2 (population variance), istd = 1 / sqrt(max(var, 1e-20)).
+ *
+ * asr_global_norm_augment_lfr_fwd: asr_utt_norm_augment_lfr_fwd with (x - mean[bin]) * istd[bin] - one fp32
+ * subtraction, one fp32 multiplication - in place of the utterance's scalar statistics; mean, istd: (n_mels) f32.
+ * Same masks (may be NULL: then no reduction runs at all), same stacking rule, same outputs.
+ */
+int asr_cmvn_accumulate(const float* feat, const int32_t* wav_len, double* acc, int B, int Tmax, int n_mels,
+                        void* stream);
+int asr_global_norm_augment_lfr_fwd(const float* feat, const int32_t* wav_len, const int32_t* masks,
+                                    const float* mean, const float* istd, void* out, int32_t* out_len, int B,
+                                    int Tmax, int n_mels, int m, int n, int Tlfr_max, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Streaming front end: samples in, encoder chunks out, with the state on the device and the counters on the host.
+ * Each utterance owns a ring of its most recent samples, wav_ring (B, scap) f32 with sample s at [b][s & (scap - 1)],
+ * and a ring of its most recent log-mel frames, feat_ring (B, fcap, n_mels) f32 with frame t at [b][t & (fcap - 1)];
+ * scap and fcap are powers of two, and the host asks only for what the rings still hold.  Every `par` is a small int32
+ * device array the host fills per call.  ASR_STREAM_OPEN stands for "length not known yet".
+ *
+ * asr_stream_append:   par (B, 2) = {received, n_new}: pcm[b][pcm_off .. pcm_off + n_new) becomes samples
+ *                      received .. received + n_new - 1 of utterance b.  pcm (B, S) f32; n_new <= max_new <= scap.
+ * asr_stream_logmel:   par (B, 3) = {t_begin, n_new, total}: frames t_begin .. t_begin + n_new - 1 (n_new <= max_new <=
+ *                      fcap) computed by the tile body of asr_logmel_fwd - bit for bit the frames it gives for the
+ *                      whole utterance.  total = the length in samples of a closed utterance (reflection and clamping at
+ *                      the end as offline), ASR_STREAM_OPEN otherwise; the ring must hold samples
+ *                      max(0, 160 t_begin - 200) .. the last one the frames touch.
+ * asr_stream_norm_lfr: par (B, 3) = {r_begin, n_rows, Tb}: LFR rows r_begin .. r_begin + n_rows - 1 (n_rows <= C) under
+ *                      global CMVN, by the function asr_global_norm_augment_lfr_fwd uses, into out (B, C, m n_mels) f32 or
+ *                      bf16; rows past n_rows are zero.  Tb = the frame count of a closed utterance (tail rows repeat
+ *                      frame Tb - 1), ASR_STREAM_OPEN otherwise.
+ */
+#define ASR_STREAM_OPEN 0x3fffffff
+int asr_stream_append(const float* pcm, const int32_t* par, float* wav_ring, int B, int S, int pcm_off, int max_new,
+                      int scap, void* stream);
+int asr_stream_logmel(const float* wav_ring, const int32_t* par, const float* window, const float* melfb,
+                      float* feat_ring, int B, int max_new, int scap, int fcap, int n_mels, void* stream);
+int asr_stream_norm_lfr(const float* feat_ring, const int32_t* par, const float* mean, const float* istd, void* out,
+                        int B, int C, int fcap, int n_mels, int m, int n, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,65 @@
+#!/usr/bin/env python3
+"""compute_cmvn.py - global CMVN statistics of a corpus, one pass on the GPU.
+
+    python tools/compute_cmvn.py --collector_path=data/aishell1 --out=exp/cmvn.npz [--part=train] [--n_mels=40] [--batch_size=32]
+
+Reads the manifest `<collector_path>_<part>.json` train.py reads, decodes the files, and for every batch runs the training front
+end's own log-mel kernel and adds the per-bin sums of its valid frames to float64 accumulators on the device (data_handler/cmvn.py);
+the audio is never perturbed or augmented.  Writes mean, istd, count and n_mels as .npz: pass it to train.py --cmvn and to
+transcribe.py --cmvn.
+"""
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from asr_chinese_e2e_amd.data_handler import AudioParser, CmvnAccumulator, load_wav, save_cmvn  # noqa: E402
+from train import parse_flags  # noqa: E402
+
+
+def manifest_waves(collector_path, part):
+    with open(f"{collector_path}_{part}.json", encoding="utf-8") as f:
+        return [json.loads(line)["wave"] for line in f if line.strip()]
+
+
+def compute(files, n_mels=40, batch_size=32, sample_rate=16000, device="cuda"):
+    """-> (mean, istd, count) over the log-mel frames of `files`."""
+    acc = CmvnAccumulator(AudioParser(sample_rate=sample_rate, n_mels=n_mels, device=device))
+    order = sorted(range(len(files)), key=lambda i: os.path.getsize(files[i]))      # batches of similar length: little padding
+    for i in range(0, len(order), batch_size):
+        waves = []
+        for j in order[i:i + batch_size]:
+            pcm, sr = load_wav(files[j])
+            if sr != sample_rate:
+                raise SystemExit(f"compute_cmvn.py: {files[j]}: sample rate {sr}, expected {sample_rate}")
+            waves.append(pcm)
+        S = max(256, max(len(w) for w in waves))
+        wav = np.zeros((len(waves), S), dtype=np.float32)
+        for b, w in enumerate(waves):
+            wav[b, :len(w)] = w
+        acc.update(torch.from_numpy(wav).to(device), torch.tensor([len(w) for w in waves], dtype=torch.int32, device=device))
+    return acc.finalize()
+
+
+def main(argv):
+    flags = parse_flags(argv)
+    if not flags.get("collector_path") or not flags.get("out"):
+        raise SystemExit("compute_cmvn.py: give --collector_path=<manifest prefix> and --out=<file.npz>")
+    if not torch.cuda.is_available():
+        raise SystemExit("compute_cmvn.py needs an MI355X: the front end has no CPU fallback")
+    files = manifest_waves(flags["collector_path"], str(flags.get("part", "train")))
+    n_mels = int(flags.get("n_mels", 40))
+    mean, istd, count = compute(files, n_mels=n_mels, batch_size=int(flags.get("batch_size", 32)), sample_rate=int(flags.get("sample_rate", 16000)))
+    save_cmvn(str(flags["out"]), mean, istd, count)
+    print(json.dumps({"out": str(flags["out"]), "files": len(files), "frames": count, "n_mels": n_mels,
+                      "mean_range": [float(mean.min()), float(mean.max())], "std_range": [float(1 / istd.max()), float(1 / istd.min())]}))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -17,6 +17,8 @@ Differences that come with the MI355X path:
     the reference's only multi-GPU hook is the commented-out `model.wrap()` (main.py:80);
   * `--speed_perturb=0.9,1.0,1.1` resamples every training utterance by one of these factors, drawn anew each epoch, on the GPU in
     front of the log-mel kernel (the reference has no waveform-side augmentation; dev and test are never perturbed);
+  * `--cmvn=stats.npz` normalises the features of every part per mel bin with corpus statistics (tools/compute_cmvn.py) instead of
+    per utterance: the causal features a streaming model is trained on (transcribe.py --stream=1 --cmvn=...);
   * `--synthetic=N` trains on N synthetic AISHELL-1-shaped utterances (no dataset ships with this repository);
   * `--trainer=BaseTrainer` selects the twin of Trainer/base_trainer.py instead of Trainer11.
 """
@@ -61,6 +63,7 @@ class TrainConfig(DataConfigAiShell1):      # main.py:14-36
     synthetic_frames = 500
     synthetic_vocab = 4232
     trainer = "Trainer11"
+    cmvn = ""                               # --cmvn=stats.npz: global CMVN statistics for train, dev and test; empty = per-utterance normalisation
     speed_perturb = ()                      # --speed_perturb=0.9,1.0,1.1: speed factors of the train part (never dev / test); empty = off
 
 
@@ -148,7 +151,7 @@ def train(**kwargs):                        # main.py:55-98
         vocab = Vocab.load(config.vocab_path)
         common = dict(collector_path=config.collector_path, vocab=vocab, sample_rate=config.sample_rate, window_size=config.window_size,
                       n_mels=config.n_mels, predump=config.predump, use_old=config.use_old, lfr_m=config.lfr_m, lfr_n=config.lfr_n,
-                      rank=rank, world=world)
+                      rank=rank, world=world, cmvn=config.cmvn or None)
         train_iter = build_dataloader(batch_size=config.batch_size, part="train", augment=config.augment, speed_perturb=speed_factors(config.speed_perturb),
                                       **common)
         test_iter = build_dataloader(batch_size=config.eval_batch_size, part="test", augment=False, **common)
