@@ -12,8 +12,9 @@ constexpr int NFFT = 400, HOP = 160, NBIN = NFFT / 2 + 1;
 //   C[32 frames][402] = X[32][400] (windowed frames, LDS)  x  D[400][402],
 //   D[n][c] = cos(2 pi n c / 400) for c < 201,  -sin(2 pi n (c-201) / 400) for 201 <= c < 402,
 // with D never stored: the lane that owns column c keeps cos / sin of its angle in registers and
-// rotates them by 2 theta per step (exact restart every 50 steps).  v_mfma_f32_32x32x2_f32 is exact fp32 multiply-accumulate, so the
-// accuracy is that of the direct sum.  Then power = re^2 + im^2 (from C, kept in LDS) times the mel
+// rotates them by 2 theta per step: 200 steps of an fp32 recurrence from exact start values, never restarted (its drift is the
+// larger part of the error budget that tests/logmel_emul.py states and tests/test_logmel_gpu.py measures; DESIGN.md has the
+// table).  v_mfma_f32_32x32x2_f32 is exact fp32 multiply-accumulate, so the rest is the error of the direct sum.  Then power = re^2 + im^2 (from C, kept in LDS) times the mel
 // filterbank, again on the matrix pipe, log, store.  (The first version gave one DFT bin to each
 // thread and one frame to each workgroup: 80 k scalar MACs per frame through LDS reads, 0.6 ms for
 // 32 x 5 s of audio = 17 % of a training step.)
@@ -140,7 +141,7 @@ __device__ __forceinline__ void logmel_tile(Fetch fetch, Row row, const float* _
 __global__ __launch_bounds__(256, 2) void logmel_kernel(const float* __restrict__ wav, const int32_t* __restrict__ wav_len, const float* __restrict__ window,
                                                      const float* __restrict__ melfb, float* __restrict__ feat, int Smax, int Tmax, int n_mels) {
     const int t0 = blockIdx.x * FR, b = blockIdx.y, tid = threadIdx.x;
-    const int len = wav_len[b];
+    const int len = min(max(wav_len[b], 0), Smax);     // a length past the row would read the next row (or past the tensor)
     const int Tb = len > 0 ? min(1 + len / HOP, Tmax) : 0;
     float* out = feat + ((size_t)b * Tmax + t0) * n_mels;
     const int rows_here = min(FR, Tmax - t0);

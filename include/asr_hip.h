@@ -619,9 +619,14 @@ int asr_decoder_layer_bwd(const asr_dec_layer_plan* plan, const void* dy, const 
  * Replaces:  MelSpectrogram(sr=16000, ws=400, hop=160, n_mels) -> log(x+1e-20)
  *              Predictor/data_handler/processor.py:33-40
  *            (f - mean)/std (scalar, unbiased) and build_LFR_features   processor.py:42-46, 74-100
- * wav: (B, Smax) f32, wav_len: (B) int32 samples.  feat: (B, Tmax, n_mels) f32 log-mel with
- * Tmax >= 1 + Smax/160; frames t >= 1 + wav_len[b]/160 are written as 0.
- * melfb: (201, n_mels) f32 filterbank; window: (400) f32; twiddle: (400) float2 cos/sin table.
+ * wav: (B, Smax) f32, wav_len: (B) int32 samples, taken as min(max(wav_len[b], 0), Smax): a length past the row
+ * never reads the next row.  feat: (B, Tmax, n_mels) f32 log-mel: utterance b has T_b = min(1 + wav_len[b]/160, Tmax)
+ * frames (none for wav_len[b] = 0; a smaller Tmax truncates), frames t >= T_b are written as 0.  Frame t, tap n reads
+ * sample i = 160 t - 200 + n; i < 0 -> -i; i >= len -> 2 (len - 1) - i; then clamped to [0, len - 1]: reflect padding
+ * for len > 200, the same rule for shorter utterances, which reflect padding does not define.
+ * melfb: (201, n_mels) f32 filterbank; window: (400) f32.
+ * The normalisation entry points below are not given Smax: their frame count is min(1 + wav_len[b]/160, Tmax), 0 for
+ * wav_len[b] <= 0, so they stay inside feat whatever the length says.
  */
 int asr_logmel_fwd(const float* wav, const int32_t* wav_len, const float* window,
                    const float* melfb, float* feat, int B, int Smax, int Tmax, int n_mels,
