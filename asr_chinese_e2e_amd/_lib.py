@@ -23,6 +23,8 @@ ACT_NONE, ACT_RELU, ACT_RELU_MASK = 0, 1, 2
 ABI_VERSION = 10
 DROP_PRE, DROP_POST = 1, 2
 SPEED_TILE = 1024      # ASR_SPEED_TILE of include/asr_hip.h: output samples per workgroup of asr_speed_perturb_fwd
+REVERB_TILE, REVERB_CHUNK, REVERB_MAX_TAPS = 1024, 256, 8192      # ASR_REVERB_* of include/asr_hip.h: outputs per workgroup, taps per staged pass, tap limit
+NOISE_MIX_TILE = 4096      # ASR_NOISE_MIX_TILE: samples per workgroup and energy partial of asr_noise_mix_fwd
 STREAM_OPEN = 0x3fffffff      # ASR_STREAM_OPEN: "length not known yet" in the streaming front end's parameter arrays
 
 P, I, F, Z, U = c_void_p, c_int, c_float, c_size_t, c_uint32
@@ -136,6 +138,9 @@ SIGNATURES = {
     "asr_utt_norm_lfr_fwd": (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
     "asr_utt_norm_augment_lfr_fwd": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "asr_speed_perturb_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "asr_reverb_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
+    "asr_noise_mix_workspace_bytes": (Z, [I, I]),
+    "asr_noise_mix_fwd": (I, [P, P, P, P, P, P, P, P, Z, I, I, I, P]),
     "asr_cmvn_accumulate": (I, [P, P, P, I, I, I, P]),
     "asr_global_norm_augment_lfr_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "asr_stream_append": (I, [P, P, P, I, I, I, I, I, P]),

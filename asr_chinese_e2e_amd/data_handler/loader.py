@@ -25,6 +25,7 @@ from ..Utils import Pack
 from .padder import Padder
 from .processor import AudioParser
 from . import speed as speed_mod
+from . import noise as noise_mod
 
 
 def load_wav(path):
@@ -187,13 +188,19 @@ class BucketedWaveLoader:
     longer)."""
 
     def __init__(self, dataset, batch_size, parser=None, augment=False, shuffle=True, drop_last=False, seed=0, bucket_size=None,
-                 device="cuda", dtype=torch.bfloat16, rank=0, world=1, speed_perturb=None):
+                 device="cuda", dtype=torch.bfloat16, rank=0, world=1, speed_perturb=None, noise=None, noise_prob=0.5, snr_db=(5, 20), rir=None,
+                 rir_prob=0.5):
         """rank / world: data-parallel sharding.  Every rank draws the SAME batch list (same seed), keeps only the full
         batches when world > 1 (dist.DataParallel normalises by world x local batch and every rank must take the same
         number of steps), drops the ragged tail of len(batches) % world and takes batches[rank::world].
         speed_perturb: sequence of speed factors such as (0.9, 1.0, 1.1) (speed.parse_factor); every epoch each utterance draws one of
         them (BatchPlan) and is resampled on the loader's stream in front of the log-mel kernel, so lengths and frame counts change
-        from epoch to epoch.  None / empty: no perturbation, nothing of it is called."""
+        from epoch to epoch.  None / empty: no perturbation, nothing of it is called.
+        noise / rir: a noise.NoiseBank / noise.RirBank, or a list of wav paths (or arrays) from which one is built.  Every epoch each
+        utterance draws (noise.draw_augment) a response with probability rir_prob and a noise clip, a start offset in it and a
+        signal-to-noise ratio uniform in snr_db = (lo, hi) dB with probability noise_prob; on the loader's stream the utterance is then
+        speed-perturbed, reverberated, mixed with the noise - the room first, as Kaldi does - and only then parsed.  Lengths, buckets
+        and labels do not change.  Both None: nothing of it is called."""
         self.ds, self.batch_size, self.augment = dataset, batch_size, augment
         self.device, self.dtype = torch.device(device), dtype
         if self.device.type != "cuda":
@@ -205,6 +212,9 @@ class BucketedWaveLoader:
         if speed_perturb is not None and len(speed_perturb) > 0:
             pq, taps = speed_mod.build_tables(speed_perturb)
             self.speed = ([tuple(int(v) for v in r) for r in pq], torch.from_numpy(pq).to(self.device), torch.from_numpy(taps).to(self.device))
+        bank = lambda v, cls: None if v is None else v if isinstance(v, cls) else cls(v, self.device) if len(v) > 0 else None
+        self.noise, self.rir = bank(noise, noise_mod.NoiseBank), bank(rir, noise_mod.RirBank)
+        self.noise_prob, self.rir_prob, self.snr_db = float(noise_prob), float(rir_prob), snr_db
         self.plan = BatchPlan(self.lengths, batch_size, bucket_size, shuffle, drop_last, seed, rank, world, self.speed[0] if self.speed else None)
         self.rank, self.world, self.shuffle, self.drop_last, self.bucket_size = self.plan.rank, self.plan.world, shuffle, self.plan.drop_last, bucket_size
         self.rng = self.plan.rng                # batch order AND SpecAugment masks (the reference uses the global `random`)
@@ -254,18 +264,20 @@ class BucketedWaveLoader:
             slots[k] = s
         return s
 
-    def _prepare(self, idx, k=0, fidx=None):
-        """fidx: speed-factor index per utterance of the data set (BatchPlan.next_epoch), None = no perturbation."""
+    def _prepare(self, idx, k=0, fidx=None, aug=None):
+        """fidx: speed-factor index per utterance of the data set (BatchPlan.next_epoch), None = no perturbation.
+        aug: noise.draw_augment's four lists for the data set, None = neither noise nor reverberation."""
         tgt = [self.ds.ids(i) for i in idx]
         B = len(idx)
         nf = B if fidx is not None else 0      # the factor indices ride behind the labels in the one integer buffer
+        na = 5 * B if aug is not None else 0   # and behind them the response indices (B) and the noise parameters (B, 4)
         into = getattr(self.ds, "wave_into", None)
         waves = None if into is not None else [self.ds.wave(i) for i in idx]
         smax = max(self.lengths[i] for i in idx) if waves is None else max(w.size for w in waves)
         lmax = max(1, max(len(t) for t in tgt))
-        slot = self._slot(k % self.SLOTS, B * smax, 2 * B + B * lmax + nf)
+        slot = self._slot(k % self.SLOTS, B * smax, 2 * B + B * lmax + nf + na)
         buf = slot["wave_np"][:B * smax].reshape(B, smax)
-        meta = slot["meta_np"][:2 * B + B * lmax + nf]
+        meta = slot["meta_np"][:2 * B + B * lmax + nf + na]
         tg = meta[2 * B:2 * B + B * lmax].reshape(B, lmax)
         items = getattr(self.ds, "items", None)
         if waves is None and items is not None and any(isinstance(items[i][0], str) for i in idx):
@@ -291,9 +303,19 @@ class BucketedWaveLoader:
         if fidx is not None:
             pq = self.speed[0]
             fs = [fidx[i] for i in idx]
-            meta[2 * B + B * lmax:] = fs
+            meta[2 * B + B * lmax:2 * B + B * lmax + nf] = fs
             if any(pq[f][0] != pq[f][1] for f in fs):
                 smax_out = max(1, max(speed_mod.perturbed_len(sizes[r], *pq[f]) for r, f in enumerate(fs)))
+        a0 = 2 * B + B * lmax + nf      # [a0, a0 + B): response index, [a0 + B, a0 + 5 B): {clip, offset, scale as float bits, 0}
+        any_rir = any_noise = False
+        if aug is not None:
+            nidx, noff, snr, ridx = aug
+            par = meta[a0 + B:].reshape(B, 4)
+            for r, i in enumerate(idx):
+                meta[a0 + r] = ridx[i]
+                par[r] = (nidx[i], noff[i], noise_mod.snr_scale_bits(snr[i]), 0)
+            any_rir, any_noise = any(ridx[i] >= 0 for i in idx), any(nidx[i] >= 0 for i in idx)
+        extra = ()
         with torch.cuda.stream(self.stream):
             dev_wav = slot["wave"][:B * smax].view(B, smax).to(self.device, non_blocking=True)
             dev_meta = slot["meta"][:meta.size].to(self.device, non_blocking=True)
@@ -301,14 +323,22 @@ class BucketedWaveLoader:
             wav_in, len_in = dev_wav, dev_meta[:B]
             if smax_out:
                 from .. import kernels as K
-                wav_in, len_in = K.speed_perturb(dev_wav, len_in, dev_meta[2 * B + B * lmax:], self.speed[1], self.speed[2], smax_out)
+                wav_in, len_in = K.speed_perturb(dev_wav, len_in, dev_meta[2 * B + B * lmax:2 * B + B * lmax + nf], self.speed[1], self.speed[2], smax_out)
+            if any_rir:      # a batch in which no utterance drew a response launches nothing
+                from .. import kernels as K
+                extra += (wav_in,)
+                wav_in = K.reverb(wav_in, len_in, dev_meta[a0:a0 + B], self.rir.table, self.rir.lens, self.rir.peaks)
+            if any_noise:
+                from .. import kernels as K
+                ws = K.noise_mix_workspace(B, wav_in.shape[1], self.device)
+                extra += (ws,) + K.noise_mix(wav_in, len_in, dev_meta[a0 + B:a0 + 5 * B].view(B, 4), self.noise.noise, self.noise.noise_off, out=wav_in, ws=ws)
             feat, feat_len = self.parser.parse_batch(wav_in, len_in, self.dtype, augment=self.augment, rng=self.rng)
             tgt_dev = dev_meta[2 * B:2 * B + B * lmax].view(B, lmax).long()
             pack = Pack()
             pack.add(wave=feat, wave_len=feat_len.long(), tgt_for_input=tgt_dev, tgt_for_metric=tgt_dev.clone(), tgt_len=dev_meta[B:2 * B].long())
             done = torch.cuda.Event()
             done.record()
-        slot["keep"] = (dev_wav, dev_meta, wav_in, len_in, feat, feat_len) + tuple(v for v in pack.values() if torch.is_tensor(v))
+        slot["keep"] = (dev_wav, dev_meta, wav_in, len_in, feat, feat_len) + extra + tuple(v for v in pack.values() if torch.is_tensor(v))
         return pack, done, slot
 
     PREFETCH = 2      # batches prepared ahead by the helper thread
@@ -318,7 +348,12 @@ class BucketedWaveLoader:
         host-to-device copies and the feature kernels on the loader's stream.  The consumer's stream waits for the batch's event."""
         import queue
         from .. import kernels as K
+        epoch = self.plan.epoch
         batches, _, fidx = self.plan.next_epoch()
+        aug = None
+        if self.noise is not None or self.rir is not None:
+            aug = noise_mod.draw_augment(self.plan.seed, epoch, len(self.ds), self.noise_prob, len(self.noise) if self.noise else 0,
+                                         self.noise.lens if self.noise else (), self.snr_db, self.rir_prob, len(self.rir) if self.rir else 0)
         q = queue.Queue(maxsize=self.PREFETCH)
         stop = threading.Event()
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()      # the consumer's device
@@ -338,7 +373,7 @@ class BucketedWaveLoader:
                 torch.cuda.set_device(dev_index)
                 for k, idx in enumerate(batches):
                     with self._gate:      # paused() (a hipGraph capture on the consumer thread) keeps this thread off the GPU runtime
-                        item = self._prepare(idx, k, fidx)
+                        item = self._prepare(idx, k, fidx, aug)
                     if not hand_over(item):
                         return
                 hand_over(None)
@@ -379,13 +414,15 @@ def parser_norm(cmvn):
 
 def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=True, sample_rate=16000, window_size=400, n_mels=40,
                      augment=False, predump=False, use_old=False, lfr_m=4, lfr_n=3, dtype=torch.bfloat16, shuffle=None, seed=0,
-                     rank=0, world=1, speed_perturb=None, cmvn=None):
+                     rank=0, world=1, speed_perturb=None, cmvn=None, noise=None, noise_prob=0.5, snr_db=(5, 20), rir=None, rir_prob=0.5):
     """build_dataloader of the reference (data/data_loader/ai_shell_1.py:91-104), same arguments: reads the manifest
     `<collector_path>_<part>.json` written by the reference's collector (one JSON object {"wave": path, "tgt": text}
     per line, data_collector/ai_shell_1.py:73-79) and returns an iterable of Packs.  The reference computes features
     on the CPU per utterance and can cache them as .t files (predump / use_old); here they are computed on the GPU
     per batch, so both flags are accepted and ignored.  drop_last=True as in the reference (:103).
     speed_perturb: speed factors such as (0.9, 1.0, 1.1) for BucketedWaveLoader (the reference has none); None = off.
+    noise / rir, noise_prob, snr_db, rir_prob: BucketedWaveLoader's noise and reverberation augmentation, applied to part="train" only
+    (the reference has none); None = off.
     cmvn: path of a global-CMVN statistics file (tools/compute_cmvn.py): the features of this part are normalised per mel bin by
     the corpus statistics (AudioParser norm="global"); None / empty = the reference's per-utterance normalisation."""
     import json
@@ -401,5 +438,6 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
                 items.append((rec["wave"], rec["tgt"]))
     ds = WaveDataset(items, vocab, sample_rate=sample_rate)
     parser = AudioParser(sample_rate=sample_rate, n_mels=n_mels, lfr_m=lfr_m, lfr_n=lfr_n, device="cuda", **parser_norm(cmvn))
+    wave_aug = dict(noise=noise, noise_prob=noise_prob, snr_db=snr_db, rir=rir, rir_prob=rir_prob) if part == "train" else {}
     return BucketedWaveLoader(ds, batch_size, parser=parser, augment=augment, shuffle=(part == "train") if shuffle is None else shuffle,
-                              drop_last=True, seed=seed, dtype=dtype, rank=rank, world=world, speed_perturb=speed_perturb)
+                              drop_last=True, seed=seed, dtype=dtype, rank=rank, world=world, speed_perturb=speed_perturb, **wave_aug)

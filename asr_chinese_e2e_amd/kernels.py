@@ -890,6 +890,51 @@ def speed_perturb(wav, wav_len, factor, pq, taps, Smax_out, out=None, out_len=No
     return out, out_len
 
 
+REVERB_TILE, REVERB_CHUNK, REVERB_MAX_TAPS = _lib.REVERB_TILE, _lib.REVERB_CHUNK, _lib.REVERB_MAX_TAPS
+NOISE_MIX_TILE = _lib.NOISE_MIX_TILE
+
+
+def reverb(wav, wav_len, rir_idx, rir, rir_len, rir_peak, out=None):
+    """Every utterance of wav (B, Smax) f32 convolved with the response rir[rir_idx[b]] (R, Lcap) f32 of rir_len taps, its peak at
+    rir_peak kept on the direct path (include/asr_hip.h: asr_reverb_fwd; data_handler.noise.RirBank builds the table).  An index
+    outside [0, R) copies the utterance.  -> out (B, Smax) f32, zero at and beyond each wav_len; the lengths do not change."""
+    _chk_f32(wav, rir, out)
+    _chk_i32(wav_len, rir_idx, rir_len, rir_peak)
+    B, Smax = wav.shape
+    assert rir.dim() == 2 and wav_len.numel() == B and rir_idx.numel() == B
+    R, Lcap = rir.shape
+    assert rir_len.numel() == R and rir_peak.numel() == R
+    out = torch.empty(B, Smax, dtype=torch.float32, device=wav.device) if out is None else out
+    assert tuple(out.shape) == (B, Smax)
+    check(lib.asr_reverb_fwd(_p(wav), _p(wav_len), _p(rir_idx), _p(rir), _p(rir_len), _p(rir_peak), _p(out), B, Smax, R, Lcap, _stream()), "asr_reverb_fwd")
+    return out
+
+
+def noise_mix_workspace(B, Smax, device):
+    """The per-tile energy partials of noise_mix (float64; asr_noise_mix_workspace_bytes)."""
+    return torch.empty((lib.asr_noise_mix_workspace_bytes(B, Smax) + 7) // 8, dtype=torch.float64, device=device)
+
+
+def noise_mix(wav, wav_len, par, noise, noise_off, out=None, gain_out=None, ws=None):
+    """wav (B, Smax) f32 + gain x the noise clip par[b] = {clip index, start offset, 10^(-snr_dB / 20) as fp32 bits, 0} names, wrapped
+    to the utterance's length; the gain makes the mix's signal-to-noise ratio the requested one (include/asr_hip.h:
+    asr_noise_mix_fwd; data_handler.noise.NoiseBank holds noise / noise_off).  A clip index outside [0, N) copies the utterance.
+    -> (out (B, Smax) f32, zero at and beyond each wav_len - out may be wav itself -, gain (B) f32)."""
+    _chk_f32(wav, noise, out, gain_out)
+    _chk_i32(wav_len, par, noise_off)
+    B, Smax = wav.shape
+    N = noise_off.numel() - 1
+    assert wav_len.numel() == B and tuple(par.shape) == (B, 4) and noise.dim() == 1
+    out = torch.empty(B, Smax, dtype=torch.float32, device=wav.device) if out is None else out
+    gain_out = torch.empty(B, dtype=torch.float32, device=wav.device) if gain_out is None else gain_out
+    assert tuple(out.shape) == (B, Smax) and gain_out.numel() == B
+    if ws is None:
+        ws = noise_mix_workspace(B, Smax, wav.device)
+    check(lib.asr_noise_mix_fwd(_p(wav), _p(wav_len), _p(par), _p(noise), _p(noise_off), _p(out), _p(gain_out), _p(ws), ws.numel() * ws.element_size(),
+                                B, Smax, N, _stream()), "asr_noise_mix_fwd")
+    return out, gain_out
+
+
 # --------------------------------------------------------------------------------- global CMVN, streaming front end
 STREAM_OPEN = _lib.STREAM_OPEN
 

@@ -666,6 +666,44 @@ int asr_speed_perturb_fwd(const float* wav, const int32_t* wav_len, const int32_
                           int qmax, int ntaps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Reverberation and additive noise of a waveform batch (the other two waveform-side augmentations of the Kaldi / WeNet /
+ * ESPnet recipes), behind asr_speed_perturb_fwd and in front of asr_logmel_fwd: first the room, then the noise.
+ * Stands in for:  Kaldi steps/data/reverberate_data_dir.py (wav-reverberate --shift-output) / WeNet add_reverb and
+ *                 add_noise.  The reference has no waveform-side augmentation: parity unpinned by the reference; both
+ *                 definitions are restated in float64 in tests/noise_ref.py.
+ *
+ * asr_reverb_fwd: wav, out (B, Smax) f32 (out must not alias wav), wav_len (B) int32, rir_idx (B) int32, rir (R, Lcap)
+ * f32 with rir_len, rir_peak (R) int32; 1 <= Lcap <= ASR_REVERB_MAX_TAPS.  Per utterance r = rir_idx[b],
+ * L = clamp(rir_len[r], 1, Lcap), p = clamp(rir_peak[r], 0, L - 1), len = clamp(wav_len[b], 0, Smax) and
+ *   out[b, n] = sum_{k < L} rir[r][k] x[n + p - k]   for n < len (x = wav[b], 0 outside [0, len)),   out[b, n] = 0 for
+ * len <= n < Smax: the length does not change and the direct path (the response's peak) stays where it was, so
+ * lengths and labels are untouched.  r outside [0, R): out[b, :len] = wav[b, :len] bit for bit, the bank is not read.
+ * fp32 accumulation; the order of the sum is the kernel's.  16-byte accesses are used only where wav and out are
+ * 16-byte aligned; any Smax is accepted.
+ *
+ * asr_noise_mix_fwd: par (B, 4) int32 = {clip index j, start offset o, scale as fp32 bits, 0} with scale =
+ * 10^(-snr_dB / 20) computed by the host.  noise: all clips in one f32 buffer, clip j at [noise_off[j], noise_off[j + 1])
+ * (noise_off: N + 1 int32, ascending, inside the buffer: the host's responsibility).  With nlen the clip's length,
+ *   v[n] = noise[noise_off[j] + (o + n) mod nlen]   (the clip wraps as often as needed; exact for o + n up to 2^31),
+ *   Ex = sum_{n < len} x[n]^2,   Ev = sum_{n < len} v[n]^2   (fp64 sums of fp64 products, per-tile partials in ws added in
+ *   tile order: no atomics, the same input gives the same bits),   g = scale sqrt(Ex / Ev) in fp64, rounded once to fp32,
+ *   out[b, n] = x[n] + g v[n] for n < len, 0 for len <= n < Smax;   gain_out[b] = g (gain_out may be NULL).
+ * j outside [0, N), nlen <= 0, len = 0, Ex = 0 or Ev = 0: out[b, :len] = wav[b, :len] bit for bit and g = 0.  out may
+ * alias wav.  ws: asr_noise_mix_workspace_bytes(B, Smax) bytes, 8-byte aligned.
+ */
+#define ASR_REVERB_TILE 1024         /* output samples per workgroup (tests cover the tile edges) */
+#define ASR_REVERB_CHUNK 256         /* taps per staged pass over the input (tests cover the chunk edges) */
+#define ASR_REVERB_MAX_TAPS 8192
+#define ASR_NOISE_MIX_TILE 4096      /* samples per workgroup and energy partial of asr_noise_mix_fwd (tests cover the tile edges) */
+int asr_reverb_fwd(const float* wav, const int32_t* wav_len, const int32_t* rir_idx, const float* rir,
+                   const int32_t* rir_len, const int32_t* rir_peak, float* out, int B, int Smax, int R, int Lcap,
+                   void* stream);
+size_t asr_noise_mix_workspace_bytes(int B, int Smax);
+int asr_noise_mix_fwd(const float* wav, const int32_t* wav_len, const int32_t* par, const float* noise,
+                      const int32_t* noise_off, float* out, float* gain_out, void* ws, size_t ws_bytes, int B, int Smax,
+                      int N, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Global CMVN: one mean and one inverse standard deviation per mel bin, fixed for a corpus (WeNet / ESPnet / Kaldi
  * global_cmvn), as the alternative to the per-utterance scalar normalisation above - the one that can stream.
  * Stands in for:  nothing in the reference (it has no global CMVN): parity unpinned by the reference; the definition is

@@ -2,7 +2,11 @@
 model.iterate, against the same model fed one resident batch (what bench.py times).  python tools/loader_bench.py [joint]
 python tools/loader_bench.py --speed_perturb[=0.9,1.0,1.1] [--out=profiles/speed_perturb_bench.json]: the speed-perturbation kernel alone
 (B = 32 x 5 s, factors mixed in thirds) beside a device-to-device copy of the same input plus output bytes, and the waveform-fed joint
-step with the perturbation off and on, alternated in one process; the figures go to the JSON file."""
+step with the perturbation off and on, alternated in one process; the figures go to the JSON file.
+python tools/loader_bench.py --noise_reverb [--out=profiles/noise_reverb_bench.json]: asr_reverb_fwd at 1024, 4096 and 8192 taps with every
+utterance of B = 32 x 5 s reverberated (achieved fp32 FLOP/s against the vector peak) beside the same convolution through torch.fft,
+asr_noise_mix_fwd beside a device-to-device copy of its bytes, and the waveform-fed joint step with the augmentation off, at the default
+probabilities and with both probabilities 1, alternated in one process."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -11,7 +15,8 @@ from asr_chinese_e2e_amd import Models
 from asr_chinese_e2e_amd.data_handler import AudioParser, BucketedWaveLoader, Vocab, WaveDataset
 from asr_chinese_e2e_amd.Trainer import FusedAdam, NoamOpt
 SPEED = next((a for a in sys.argv[1:] if a.startswith("--speed_perturb")), None)
-JOINT = SPEED is not None or (len(sys.argv) > 1 and sys.argv[1] == "joint")
+NOISE_REVERB = any(a == "--noise_reverb" for a in sys.argv[1:])
+JOINT = SPEED is not None or NOISE_REVERB or (len(sys.argv) > 1 and sys.argv[1] == "joint")
 B, S, NB = 32, 16000 * 5, 40
 rng = np.random.RandomState(0)
 vocab = Vocab.synthetic(4232)
@@ -107,8 +112,109 @@ def speed_bench():
     print("wrote", out_path)
 
 
+def noise_reverb_bench():
+    import json
+    from asr_chinese_e2e_amd import kernels as K
+    from asr_chinese_e2e_amd.data_handler import noise
+    out_path = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--out=")), "profiles/noise_reverb_bench.json")
+    PEAK = 157.3e12                                                               # fp32 vector peak of the MI355X, FLOP/s
+    wav = torch.from_numpy(np.stack([items[i][0] for i in range(B)])).cuda() if not isinstance(items[0][0], str) else torch.randn(B, S, device="cuda") * 0.1
+    wl = torch.full((B,), S, dtype=torch.int32, device="cuda")
+    r = np.random.RandomState(5)
+
+    def timed(fn, reps, warm=3):
+        for _ in range(warm): fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps): fn()
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3
+
+    def responses(n, L):                                                          # exponentially decaying noise behind a direct path at sample 64
+        hs = []
+        for _ in range(n):
+            h = r.randn(L + 40) * np.exp(-np.arange(L + 40) / (L / 6.0)) * 0.1
+            h[:104] *= 0.01
+            h[104] = 1.0
+            hs.append(h)
+        return hs
+    res = dict(device=torch.cuda.get_device_name(0), B=B, samples=S, fp32_vector_peak_TFLOPs=PEAK / 1e12, reverb=[])
+    out = torch.empty_like(wav)
+    for L in (1024, 4096, 8192):
+        bank = noise.RirBank(responses(8, L), "cuda", max_taps=L)
+        assert bank.lens.tolist() == [L] * 8 and bank.peaks.tolist() == [64] * 8
+        ridx = torch.tensor([i % 8 for i in range(B)], dtype=torch.int32, device="cuda")
+        args = (wav, wl, ridx, bank.table, bank.lens, bank.peaks)
+        nfft = 1 << int(np.ceil(np.log2(S + L - 1)))
+
+        def fft_conv():
+            X, H = torch.fft.rfft(wav, nfft), torch.fft.rfft(bank.table[ridx.long()], nfft)
+            return torch.fft.irfft(X * H, nfft)[:, 64:64 + S]
+        K.reverb(*args, out=out)
+        ref = fft_conv()
+        diff = float((out - ref).abs().max())                                     # the two computations agree (fp32 FFT round-off)
+        kern, fft = [], []
+        for _ in range(3):                                                        # alternated
+            kern.append(timed(lambda: K.reverb(*args, out=out), reps=20))
+            fft.append(timed(fft_conv, reps=20))
+        flops = 2.0 * B * S * L
+        k, f = float(np.median(kern)), float(np.median(fft))
+        res["reverb"].append(dict(taps=L, kernel_us=kern, kernel_us_median=k, multiply_adds=B * S * L, lower_bound_us=flops / PEAK * 1e6,
+                                  achieved_TFLOPs=flops / k / 1e6, share_of_vector_peak=flops / k / 1e6 / (PEAK / 1e12),
+                                  torch_fft_us=fft, torch_fft_us_median=f, nfft=nfft, max_abs_diff_vs_torch_fft=diff))
+        print(json.dumps(res["reverb"][-1]), flush=True)
+    res["reverb_timing"] = ("HIP events around 20 back-to-back launches after 3 warm-up launches, 3 rounds alternating the kernel and torch.fft (rfft of the "
+                            "batch and of the gathered responses at the next power of two, product, irfft, slice); lower bound = B S L multiply-adds = "
+                            "2 B S L FLOP at the fp32 vector peak; edge tiles skip the taps that fall in front of the utterance, so slightly fewer are executed")
+    # noise mix beside a copy of the same bytes: x and v read twice (energies, then the mix), out written once = 5 floats per sample
+    nb = noise.NoiseBank([(r.randn(n) * 0.05).astype(np.float32) for n in (16000, 50000, 160000, 400000)], "cuda")
+    par = torch.tensor([[i % 4, (7919 * i) % nb.lens[i % 4], noise.snr_scale_bits(5 + i % 16), 0] for i in range(B)], dtype=torch.int32, device="cuda")
+    ws, gain = K.noise_mix_workspace(B, S, "cuda"), torch.empty(B, device="cuda")
+    src, dst = torch.randn(B * S * 5 // 2, device="cuda"), torch.empty(B * S * 5 // 2, device="cuda")
+    mix, copy = [], []
+    for _ in range(5):
+        mix.append(timed(lambda: K.noise_mix(wav, wl, par, nb.noise, nb.noise_off, out=out, gain_out=gain, ws=ws), reps=200, warm=20))
+        copy.append(timed(lambda: dst.copy_(src), reps=200, warm=20))
+    res["noise_mix"] = dict(kernel_us=mix, kernel_us_median=float(np.median(mix)), bytes_read_plus_written=4 * 5 * B * S, d2d_copy_same_bytes_us=copy,
+                            d2d_copy_us_median=float(np.median(copy)), launches=2,
+                            timing="HIP events around 200 back-to-back calls (two launches each) after 20 warm-up calls, 5 rounds alternating mix and copy")
+    print(json.dumps({k: res["noise_mix"][k] for k in ("kernel_us_median", "d2d_copy_us_median")}), flush=True)
+    # the waveform-fed joint step: augmentation off, default probabilities, both probabilities 1; responses of 4096 taps (0.25 s)
+    rb = noise.RirBank(responses(8, 4096), "cuda", max_taps=4096)
+    mk = lambda **kw: BucketedWaveLoader(ds, B, parser=parser, augment=True, shuffle=True, seed=1, dtype=torch.bfloat16, **kw)
+    loaders = dict(off=mk(), default=mk(noise=nb, rir=rb), all=mk(noise=nb, rir=rb, noise_prob=1.0, rir_prob=1.0))
+
+    def run(ld):
+        n = 0
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for pack in ld:
+            model.iterate(pack, optimizer=opt)
+            n += 1
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3
+    for ld in loaders.values(): run(ld)                                           # warm-up epoch each
+    step = {name: [] for name in loaders}
+    for _ in range(4):
+        for name, ld in loaders.items():
+            step[name].append(run(ld))
+            print(f"joint step from waveforms, noise and reverberation {name}: {step[name][-1]:.3f} ms/step", flush=True)
+    res["joint_step_ms"] = step
+    res["joint_step_ms_median"] = {name: float(np.median(v)) for name, v in step.items()}
+    res["joint_config"] = (f"{NB} batches of {B} x 5 s per epoch in host memory, SpecAugment on, bf16 joint model at the default width, 8 responses of 4096 taps, "
+                           "4 noise clips of 1 - 25 s, SNR 5 - 20 dB; off = no banks, default = both probabilities 0.5, all = both 1.0; 1 warm-up epoch each, "
+                           "then 4 epochs each, alternating; host clock around an epoch that ends in a device synchronise")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out_path)
+
+
 if SPEED is not None:
     speed_bench()
+    sys.exit(0)
+if NOISE_REVERB:
+    noise_reverb_bench()
     sys.exit(0)
 
 

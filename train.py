@@ -17,6 +17,10 @@ Differences that come with the MI355X path:
     the reference's only multi-GPU hook is the commented-out `model.wrap()` (main.py:80);
   * `--speed_perturb=0.9,1.0,1.1` resamples every training utterance by one of these factors, drawn anew each epoch, on the GPU in
     front of the log-mel kernel (the reference has no waveform-side augmentation; dev and test are never perturbed);
+  * `--noise_list=FILE --rir_list=FILE` (one wav path per line each) add noise and reverberation to the training utterances on the GPU,
+    behind the speed perturbation: with probability `--rir_prob` (0.5) a room impulse response of the list is convolved in, with
+    probability `--noise_prob` (0.5) a noise clip is mixed in at a signal-to-noise ratio drawn uniformly from `--snr_db=5,20` (dB);
+    drawn anew each epoch, never for dev / test (the reference has no waveform-side augmentation);
   * `--cmvn=stats.npz` normalises the features of every part per mel bin with corpus statistics (tools/compute_cmvn.py) instead of
     per utterance: the causal features a streaming model is trained on (transcribe.py --stream=1 --cmvn=...);
   * `--synthetic=N` trains on N synthetic AISHELL-1-shaped utterances (no dataset ships with this repository);
@@ -64,6 +68,11 @@ class TrainConfig(DataConfigAiShell1):      # main.py:14-36
     synthetic_vocab = 4232
     trainer = "Trainer11"
     cmvn = ""                               # --cmvn=stats.npz: global CMVN statistics for train, dev and test; empty = per-utterance normalisation
+    noise_list = ""                         # --noise_list=FILE: wav paths of noise clips, one per line (train part only); empty = off
+    rir_list = ""                           # --rir_list=FILE: wav paths of room impulse responses, one per line (train part only); empty = off
+    noise_prob = 0.5                        # probability that an utterance gets noise / a response, drawn per epoch
+    rir_prob = 0.5
+    snr_db = (5, 20)                        # --snr_db=5,20: the signal-to-noise ratio of a noisy utterance is uniform in this range (dB)
     speed_perturb = ()                      # --speed_perturb=0.9,1.0,1.1: speed factors of the train part (never dev / test); empty = off
 
 
@@ -103,6 +112,24 @@ def speed_factors(v):
     if isinstance(v, str):
         return tuple(x.strip() for x in v.split(",") if x.strip()) or None
     return tuple(v) if isinstance(v, (tuple, list)) else (v,)
+
+
+def path_list(v):
+    """The value of --noise_list / --rir_list: the non-empty lines of that file, or None when the flag is empty."""
+    if not v:
+        return None
+    with open(v, encoding="utf-8") as f:
+        return [line.strip() for line in f if line.strip()]
+
+
+def snr_range(v):
+    """The value of --snr_db as (lo, hi): `5,20` parses as a tuple, `10` as one number (lo = hi)."""
+    if isinstance(v, str):
+        v = tuple(float(x) for x in v.split(",") if x.strip())
+    v = tuple(float(x) for x in v) if isinstance(v, (tuple, list)) else (float(v),)
+    if len(v) not in (1, 2) or v[0] > v[-1]:
+        raise ValueError(f"--snr_db={v}: one number or lo,hi")
+    return v[0], v[-1]
 
 
 class _SyntheticLoader:
@@ -153,7 +180,8 @@ def train(**kwargs):                        # main.py:55-98
                       n_mels=config.n_mels, predump=config.predump, use_old=config.use_old, lfr_m=config.lfr_m, lfr_n=config.lfr_n,
                       rank=rank, world=world, cmvn=config.cmvn or None)
         train_iter = build_dataloader(batch_size=config.batch_size, part="train", augment=config.augment, speed_perturb=speed_factors(config.speed_perturb),
-                                      **common)
+                                      noise=path_list(config.noise_list), rir=path_list(config.rir_list), noise_prob=float(config.noise_prob),
+                                      rir_prob=float(config.rir_prob), snr_db=snr_range(config.snr_db), **common)
         test_iter = build_dataloader(batch_size=config.eval_batch_size, part="test", augment=False, **common)
         dev_iter = build_dataloader(batch_size=config.eval_batch_size, part="dev", augment=False, **common)
 
