@@ -189,7 +189,7 @@ class BucketedWaveLoader:
 
     def __init__(self, dataset, batch_size, parser=None, augment=False, shuffle=True, drop_last=False, seed=0, bucket_size=None,
                  device="cuda", dtype=torch.bfloat16, rank=0, world=1, speed_perturb=None, noise=None, noise_prob=0.5, snr_db=(5, 20), rir=None,
-                 rir_prob=0.5):
+                 rir_prob=0.5, rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS):
         """rank / world: data-parallel sharding.  Every rank draws the SAME batch list (same seed), keeps only the full
         batches when world > 1 (dist.DataParallel normalises by world x local batch and every rank must take the same
         number of steps), drops the ragged tail of len(batches) % world and takes batches[rank::world].
@@ -200,7 +200,10 @@ class BucketedWaveLoader:
         utterance draws (noise.draw_augment) a response with probability rir_prob and a noise clip, a start offset in it and a
         signal-to-noise ratio uniform in snr_db = (lo, hi) dB with probability noise_prob; on the loader's stream the utterance is then
         speed-perturbed, reverberated, mixed with the noise - the room first, as Kaldi does - and only then parsed.  Lengths, buckets
-        and labels do not change.  Both None: nothing of it is called."""
+        and labels do not change.  Both None: nothing of it is called.
+        rir_method, rir_max_taps: for a bank built here from paths - "direct" (asr_reverb_fwd, responses cut to at most 8192 taps), "fft"
+        (asr_reverb_fft_fwd, at most 65536 taps, cost nearly flat in the length) or "auto" (decided once from the bank's longest response:
+        noise.RirBank).  A ready-made RirBank decides by its own method.  Draws, lengths and buckets do not depend on the method."""
         self.ds, self.batch_size, self.augment = dataset, batch_size, augment
         self.device, self.dtype = torch.device(device), dtype
         if self.device.type != "cuda":
@@ -212,8 +215,10 @@ class BucketedWaveLoader:
         if speed_perturb is not None and len(speed_perturb) > 0:
             pq, taps = speed_mod.build_tables(speed_perturb)
             self.speed = ([tuple(int(v) for v in r) for r in pq], torch.from_numpy(pq).to(self.device), torch.from_numpy(taps).to(self.device))
-        bank = lambda v, cls: None if v is None else v if isinstance(v, cls) else cls(v, self.device) if len(v) > 0 else None
-        self.noise, self.rir = bank(noise, noise_mod.NoiseBank), bank(rir, noise_mod.RirBank)
+        bank = lambda v, cls, **kw: None if v is None else v if isinstance(v, cls) else cls(v, self.device, **kw) if len(v) > 0 else None
+        if rir_method not in noise_mod.METHODS + ("auto",):
+            raise ValueError(f"rir_method={rir_method!r}: one of 'direct', 'fft', 'auto'")
+        self.noise, self.rir = bank(noise, noise_mod.NoiseBank), bank(rir, noise_mod.RirBank, max_taps=rir_max_taps, method=rir_method)
         self.noise_prob, self.rir_prob, self.snr_db = float(noise_prob), float(rir_prob), snr_db
         self.plan = BatchPlan(self.lengths, batch_size, bucket_size, shuffle, drop_last, seed, rank, world, self.speed[0] if self.speed else None)
         self.rank, self.world, self.shuffle, self.drop_last, self.bucket_size = self.plan.rank, self.plan.world, shuffle, self.plan.drop_last, bucket_size
@@ -327,7 +332,12 @@ class BucketedWaveLoader:
             if any_rir:      # a batch in which no utterance drew a response launches nothing
                 from .. import kernels as K
                 extra += (wav_in,)
-                wav_in = K.reverb(wav_in, len_in, dev_meta[a0:a0 + B], self.rir.table, self.rir.lens, self.rir.peaks)
+                if self.rir.method == "fft":
+                    ws = K.reverb_fft_workspace(B, wav_in.shape[1], self.rir.table.shape[1], self.device)
+                    extra += (ws,)
+                    wav_in = K.reverb_fft(wav_in, len_in, dev_meta[a0:a0 + B], self.rir.table, self.rir.lens, self.rir.peaks, ws=ws)
+                else:
+                    wav_in = K.reverb(wav_in, len_in, dev_meta[a0:a0 + B], self.rir.table, self.rir.lens, self.rir.peaks)
             if any_noise:
                 from .. import kernels as K
                 ws = K.noise_mix_workspace(B, wav_in.shape[1], self.device)
@@ -414,7 +424,8 @@ def parser_norm(cmvn):
 
 def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=True, sample_rate=16000, window_size=400, n_mels=40,
                      augment=False, predump=False, use_old=False, lfr_m=4, lfr_n=3, dtype=torch.bfloat16, shuffle=None, seed=0,
-                     rank=0, world=1, speed_perturb=None, cmvn=None, noise=None, noise_prob=0.5, snr_db=(5, 20), rir=None, rir_prob=0.5):
+                     rank=0, world=1, speed_perturb=None, cmvn=None, noise=None, noise_prob=0.5, snr_db=(5, 20), rir=None, rir_prob=0.5,
+                     rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS):
     """build_dataloader of the reference (data/data_loader/ai_shell_1.py:91-104), same arguments: reads the manifest
     `<collector_path>_<part>.json` written by the reference's collector (one JSON object {"wave": path, "tgt": text}
     per line, data_collector/ai_shell_1.py:73-79) and returns an iterable of Packs.  The reference computes features
@@ -422,7 +433,7 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
     per batch, so both flags are accepted and ignored.  drop_last=True as in the reference (:103).
     speed_perturb: speed factors such as (0.9, 1.0, 1.1) for BucketedWaveLoader (the reference has none); None = off.
     noise / rir, noise_prob, snr_db, rir_prob: BucketedWaveLoader's noise and reverberation augmentation, applied to part="train" only
-    (the reference has none); None = off.
+    (the reference has none); None = off.  rir_method, rir_max_taps: BucketedWaveLoader's, for the same part.
     cmvn: path of a global-CMVN statistics file (tools/compute_cmvn.py): the features of this part are normalised per mel bin by
     the corpus statistics (AudioParser norm="global"); None / empty = the reference's per-utterance normalisation."""
     import json
@@ -438,6 +449,7 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
                 items.append((rec["wave"], rec["tgt"]))
     ds = WaveDataset(items, vocab, sample_rate=sample_rate)
     parser = AudioParser(sample_rate=sample_rate, n_mels=n_mels, lfr_m=lfr_m, lfr_n=lfr_n, device="cuda", **parser_norm(cmvn))
-    wave_aug = dict(noise=noise, noise_prob=noise_prob, snr_db=snr_db, rir=rir, rir_prob=rir_prob) if part == "train" else {}
+    wave_aug = dict(noise=noise, noise_prob=noise_prob, snr_db=snr_db, rir=rir, rir_prob=rir_prob, rir_method=rir_method,
+                    rir_max_taps=rir_max_taps) if part == "train" else {}
     return BucketedWaveLoader(ds, batch_size, parser=parser, augment=augment, shuffle=(part == "train") if shuffle is None else shuffle,
                               drop_last=True, seed=seed, dtype=dtype, rank=rank, world=world, speed_perturb=speed_perturb, **wave_aug)

@@ -10,7 +10,12 @@ import numpy as np
 import torch
 
 SAMPLE_RATE = 16000
-MAX_TAPS = 8192      # ASR_REVERB_MAX_TAPS
+MAX_TAPS = 8192      # ASR_REVERB_MAX_TAPS: the direct kernel's limit, and the default cap
+FFT_MAX_TAPS = 65536      # ASR_REVERB_FFT_MAX_TAPS: the FFT path's limit
+# "auto" takes the FFT path for a bank whose longest response has at least this many taps: the smallest measured length from which
+# asr_reverb_fft_fwd beats asr_reverb_fwd - 42 us against 110 us at 1024 taps, 43 against 30 at 256 (profiles/reverb_fft_bench.json)
+AUTO_FFT_FROM_TAPS = 1024
+METHODS = ("direct", "fft")
 PRE_PEAK = 64        # samples kept in front of a response's peak
 
 
@@ -27,9 +32,12 @@ def _read(src, what):
     return np.asarray(src).reshape(-1), None
 
 
-def rir_entry(h, max_taps=MAX_TAPS, name="response"):
+def rir_entry(h, max_taps=MAX_TAPS, name="response", tap_limit=MAX_TAPS):
     """One response -> (taps float32, peak index inside them): the samples [s0, s0 + max_taps) with s0 = max(0, argmax |h| - 64),
-    scaled to unit energy (sum h^2 = 1, as WeNet's add_reverb) in float64 AFTER the truncation and rounded once."""
+    scaled to unit energy (sum h^2 = 1, as WeNet's add_reverb) in float64 AFTER the truncation and rounded once.
+    tap_limit: as rir_table's."""
+    if not 1 <= int(max_taps) <= int(tap_limit) <= FFT_MAX_TAPS:
+        raise ValueError(f"{name}: max_taps={max_taps} outside 1 .. {int(tap_limit)} (at most {FFT_MAX_TAPS})")
     h = np.asarray(h, dtype=np.float64).reshape(-1)
     if h.size == 0 or not np.any(h):
         raise ValueError(f"{name}: the impulse response is empty or all zeros")
@@ -39,11 +47,14 @@ def rir_entry(h, max_taps=MAX_TAPS, name="response"):
     return (h / np.sqrt(np.sum(h * h))).astype(np.float32), peak - s0
 
 
-def rir_table(responses, max_taps=MAX_TAPS, names=None):
-    """The table maths of RirBank on the host: -> (table (R, Lcap) float32 zero-padded, lens (R) int32, peaks (R) int32)."""
-    if not 1 <= int(max_taps) <= MAX_TAPS:
-        raise ValueError(f"max_taps={max_taps}: the reverberation kernel takes 1 .. {MAX_TAPS} taps")
-    entries = [rir_entry(h, max_taps, names[i] if names and names[i] else f"response {i}") for i, h in enumerate(responses)]
+def rir_table(responses, max_taps=MAX_TAPS, names=None, tap_limit=MAX_TAPS):
+    """The table maths of RirBank on the host: -> (table (R, Lcap) float32 zero-padded, lens (R) int32, peaks (R) int32).
+    tap_limit: the largest max_taps admitted - the direct kernel's 8192 unless the caller names the FFT path's FFT_MAX_TAPS."""
+    if not 1 <= int(tap_limit) <= FFT_MAX_TAPS:
+        raise ValueError(f"tap_limit={tap_limit}: no reverberation kernel takes more than {FFT_MAX_TAPS} taps")
+    if not 1 <= int(max_taps) <= int(tap_limit):
+        raise ValueError(f"max_taps={max_taps}: the reverberation kernel takes 1 .. {int(tap_limit)} taps")
+    entries = [rir_entry(h, max_taps, names[i] if names and names[i] else f"response {i}", tap_limit) for i, h in enumerate(responses)]
     if not entries:
         raise ValueError("no impulse responses")
     table = np.zeros((len(entries), max(e[0].size for e in entries)), dtype=np.float32)
@@ -53,11 +64,19 @@ def rir_table(responses, max_taps=MAX_TAPS, names=None):
 
 
 class RirBank:
-    """Room impulse responses resident on `device`: table (R, Lcap) f32, lens, peaks (R) int32 (rir_table)."""
+    """Room impulse responses resident on `device`: table (R, Lcap) f32, lens, peaks (R) int32 (rir_table).
+    method: the kernel the loader convolves with - "direct" (asr_reverb_fwd, at most 8192 taps) or "fft" (asr_reverb_fft_fwd, at most
+    65536); "auto" reads the responses with the FFT path's limit and settles on "fft" when the longest one kept has at least
+    AUTO_FFT_FROM_TAPS taps, on "direct" otherwise.  self.method is always one of METHODS."""
 
-    def __init__(self, paths_or_arrays, device="cuda", max_taps=MAX_TAPS):
+    def __init__(self, paths_or_arrays, device="cuda", max_taps=MAX_TAPS, method="direct"):
+        if method not in METHODS + ("auto",):
+            raise ValueError(f"method={method!r}: one of 'direct', 'fft', 'auto'")
         read = [_read(s, "impulse-response") for s in paths_or_arrays]
-        table, lens, peaks = rir_table([w for w, _ in read], max_taps, [n for _, n in read])
+        table, lens, peaks = rir_table([w for w, _ in read], max_taps, [n for _, n in read], MAX_TAPS if method == "direct" else FFT_MAX_TAPS)
+        if method == "auto":
+            method = "fft" if int(lens.max()) >= AUTO_FFT_FROM_TAPS else "direct"
+        self.method = method
         self.n, self.max_taps = int(lens.size), int(max_taps)
         self.table, self.lens, self.peaks = (torch.from_numpy(a).to(device) for a in (table, lens, peaks))
 

@@ -2,6 +2,7 @@
 assumes (device, dtype, contiguity, shapes) ON THE HOST before launching, and passes raw device
 pointers + the current HIP stream.  PyTorch is only the allocator / stream provider here.
 """
+import math
 import threading
 import ctypes
 
@@ -907,6 +908,46 @@ def reverb(wav, wav_len, rir_idx, rir, rir_len, rir_peak, out=None):
     out = torch.empty(B, Smax, dtype=torch.float32, device=wav.device) if out is None else out
     assert tuple(out.shape) == (B, Smax)
     check(lib.asr_reverb_fwd(_p(wav), _p(wav_len), _p(rir_idx), _p(rir), _p(rir_len), _p(rir_peak), _p(out), B, Smax, R, Lcap, _stream()), "asr_reverb_fwd")
+    return out
+
+
+REVERB_FFT_N, REVERB_FFT_MAX_TAPS = _lib.REVERB_FFT_N, _lib.REVERB_FFT_MAX_TAPS
+_REVERB_FFT_TWIDDLE = {}      # device -> the (N, 2) f32 table, uploaded the first time that device needs it
+
+
+def reverb_fft_twiddle(device):
+    """(cos, -sin)(2 pi t / N), t < N = REVERB_FFT_N: computed in float64 on the host, rounded once, resident on `device`."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    tw = _REVERB_FFT_TWIDDLE.get(device)
+    if tw is None:
+        a = 2.0 * math.pi * torch.arange(REVERB_FFT_N, dtype=torch.float64) / REVERB_FFT_N
+        tw = _REVERB_FFT_TWIDDLE[device] = torch.stack((torch.cos(a), -torch.sin(a)), dim=1).to(torch.float32).to(device)
+    return tw
+
+
+def reverb_fft_workspace(B, Smax, Lcap, device):
+    """The window and response spectra of reverb_fft (asr_reverb_fft_workspace_bytes); need not be initialised."""
+    return torch.empty((lib.asr_reverb_fft_workspace_bytes(B, Smax, Lcap) + 3) // 4, dtype=torch.float32, device=device)
+
+
+def reverb_fft(wav, wav_len, rir_idx, rir, rir_len, rir_peak, out=None, ws=None):
+    """reverb's result for responses of up to REVERB_FFT_MAX_TAPS taps, as a partitioned overlap-save FFT convolution whose cost is
+    nearly flat in the response length (include/asr_hip.h: asr_reverb_fft_fwd).  Same arguments and semantics as reverb; ws: a
+    reverb_fft_workspace(B, Smax, Lcap, device), taken here when None.  -> out (B, Smax) f32."""
+    _chk_f32(wav, rir, out, ws)
+    _chk_i32(wav_len, rir_idx, rir_len, rir_peak)
+    B, Smax = wav.shape
+    assert rir.dim() == 2 and wav_len.numel() == B and rir_idx.numel() == B
+    R, Lcap = rir.shape
+    assert rir_len.numel() == R and rir_peak.numel() == R
+    out = torch.empty(B, Smax, dtype=torch.float32, device=wav.device) if out is None else out
+    assert tuple(out.shape) == (B, Smax)
+    if ws is None:
+        ws = reverb_fft_workspace(B, Smax, min(Lcap, REVERB_FFT_MAX_TAPS), wav.device)
+    check(lib.asr_reverb_fft_fwd(_p(wav), _p(wav_len), _p(rir_idx), _p(rir), _p(rir_len), _p(rir_peak), _p(reverb_fft_twiddle(wav.device)), _p(out), _p(ws),
+                                 ws.numel() * ws.element_size(), B, Smax, R, Lcap, _stream()), "asr_reverb_fft_fwd")
     return out
 
 

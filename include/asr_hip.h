@@ -704,6 +704,30 @@ int asr_noise_mix_fwd(const float* wav, const int32_t* wav_len, const int32_t* p
                       int N, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Reverberation with long responses: the definition of asr_reverb_fwd (same arguments, same clamping of len, L and p, same
+ * copies for r outside [0, R), zeros from len on, out must not alias wav, any Smax and any alignment of wav / out, nothing
+ * at or beyond rir_len[r] is read), evaluated as a uniformly partitioned overlap-save convolution with transforms of
+ * ASR_REVERB_FFT_N points, for 1 <= Lcap <= ASR_REVERB_FFT_MAX_TAPS.  With Bk = ASR_REVERB_FFT_N / 2, window j of an utterance
+ * x[(j - 1) Bk, (j + 1) Bk) and partition q of its response h[q Bk, (q + 1) Bk):
+ *   full[i Bk, (i + 1) Bk) = last Bk samples of IFFT(sum_{q < P_b, q <= i} FFT(partition q) FFT(window i - q)),
+ *   out[b, m - p] = full[m],   P_b = ceil(L / Bk) per utterance (a short response does not pay for the bank's longest).
+ * fp32 throughout, the products summed over q in ascending order, no atomics: the same input gives the same bits.  The
+ * rounding error scales with S_i = sum_q ||partition q||_2 ||window i - q||_2 per output block (tests/reverb_fft_ref.py).
+ * twiddle: ASR_REVERB_FFT_N pairs (cos, -sin)(2 pi t / ASR_REVERB_FFT_N), t = 0 .. N - 1, computed in float64 and rounded
+ * once (kernels.reverb_fft_twiddle), 8-byte aligned.
+ * ws: asr_reverb_fft_workspace_bytes(B, Smax, Lcap) bytes, 16-byte aligned; need not be initialised:
+ *   B * (ceil(Smax / Bk) + 1 + ceil(Lcap / Bk)) * Bk * 8
+ * - the spectra (Bk complex words each) of the ceil(Smax / Bk) + 1 windows of every utterance and of the ceil(Lcap / Bk)
+ * partitions of the response it drew; spectra are computed per batch, never kept for the bank.  0 for B, Smax or Lcap < 1.
+ */
+#define ASR_REVERB_FFT_N 4096             /* transform points; N / 2 = 2048 new samples per block */
+#define ASR_REVERB_FFT_MAX_TAPS 65536     /* 32 partitions of 2048 taps */
+size_t asr_reverb_fft_workspace_bytes(int B, int Smax, int Lcap);
+int asr_reverb_fft_fwd(const float* wav, const int32_t* wav_len, const int32_t* rir_idx, const float* rir,
+                       const int32_t* rir_len, const int32_t* rir_peak, const float* twiddle, float* out, void* ws,
+                       size_t ws_bytes, int B, int Smax, int R, int Lcap, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Global CMVN: one mean and one inverse standard deviation per mel bin, fixed for a corpus (WeNet / ESPnet / Kaldi
  * global_cmvn), as the alternative to the per-utterance scalar normalisation above - the one that can stream.
  * Stands in for:  nothing in the reference (it has no global CMVN): parity unpinned by the reference; the definition is

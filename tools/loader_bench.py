@@ -6,7 +6,9 @@ step with the perturbation off and on, alternated in one process; the figures go
 python tools/loader_bench.py --noise_reverb [--out=profiles/noise_reverb_bench.json]: asr_reverb_fwd at 1024, 4096 and 8192 taps with every
 utterance of B = 32 x 5 s reverberated (achieved fp32 FLOP/s against the vector peak) beside the same convolution through torch.fft,
 asr_noise_mix_fwd beside a device-to-device copy of its bytes, and the waveform-fed joint step with the augmentation off, at the default
-probabilities and with both probabilities 1, alternated in one process."""
+probabilities and with both probabilities 1, alternated in one process.
+python tools/loader_bench.py --reverb_fft [--out=profiles/reverb_fft_bench.json]: asr_reverb_fft_fwd, asr_reverb_fwd (up to its 8192 taps) and
+the torch.fft stand-in at 256 .. 65536 taps, same protocol, and the waveform-fed joint step with rir_method direct and fft at 4096 taps."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -16,7 +18,8 @@ from asr_chinese_e2e_amd.data_handler import AudioParser, BucketedWaveLoader, Vo
 from asr_chinese_e2e_amd.Trainer import FusedAdam, NoamOpt
 SPEED = next((a for a in sys.argv[1:] if a.startswith("--speed_perturb")), None)
 NOISE_REVERB = any(a == "--noise_reverb" for a in sys.argv[1:])
-JOINT = SPEED is not None or NOISE_REVERB or (len(sys.argv) > 1 and sys.argv[1] == "joint")
+REVERB_FFT = any(a == "--reverb_fft" for a in sys.argv[1:])
+JOINT = SPEED is not None or NOISE_REVERB or REVERB_FFT or (len(sys.argv) > 1 and sys.argv[1] == "joint")
 B, S, NB = 32, 16000 * 5, 40
 rng = np.random.RandomState(0)
 vocab = Vocab.synthetic(4232)
@@ -210,8 +213,101 @@ def noise_reverb_bench():
     print("wrote", out_path)
 
 
+def reverb_fft_bench():
+    import json
+    from asr_chinese_e2e_amd import kernels as K
+    from asr_chinese_e2e_amd.data_handler import noise
+    out_path = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--out=")), "profiles/reverb_fft_bench.json")
+    wav = torch.from_numpy(np.stack([items[i][0] for i in range(B)])).cuda() if not isinstance(items[0][0], str) else torch.randn(B, S, device="cuda") * 0.1
+    wl = torch.full((B,), S, dtype=torch.int32, device="cuda")
+    r = np.random.RandomState(5)
+
+    def timed(fn, reps=20, warm=3):
+        for _ in range(warm): fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps): fn()
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3
+
+    def responses(n, L):                                                          # exponentially decaying noise behind a direct path at sample 64
+        hs = []
+        for _ in range(n):
+            h = r.randn(L + 40) * np.exp(-np.arange(L + 40) / (L / 6.0)) * 0.1
+            h[:104] *= 0.01
+            h[104] = 1.0
+            hs.append(h)
+        return hs
+    res = dict(device=torch.cuda.get_device_name(0), B=B, samples=S, fft_points=K.REVERB_FFT_N, reverb=[])
+    out = torch.empty_like(wav)
+    ridx = torch.tensor([i % 8 for i in range(B)], dtype=torch.int32, device="cuda")
+    for L in (256, 1024, 4096, 8192, 16384, 32768, 65536):
+        bank = noise.RirBank(responses(8, L), "cuda", max_taps=L, method="fft")
+        assert bank.lens.tolist() == [L] * 8 and bank.peaks.tolist() == [64] * 8
+        args = (wav, wl, ridx, bank.table, bank.lens, bank.peaks)
+        ws = K.reverb_fft_workspace(B, S, L, "cuda")
+        nfft = 1 << int(np.ceil(np.log2(S + L - 1)))
+
+        def fft_conv():
+            X, H = torch.fft.rfft(wav, nfft), torch.fft.rfft(bank.table[ridx.long()], nfft)
+            return torch.fft.irfft(X * H, nfft)[:, 64:64 + S]
+        contenders = dict(fft_kernel=lambda: K.reverb_fft(*args, out=out, ws=ws), torch_fft=fft_conv)
+        if L <= K.REVERB_MAX_TAPS:
+            contenders["direct_kernel"] = lambda: K.reverb(*args, out=out)
+        K.reverb_fft(*args, out=out, ws=ws)
+        diff = float((out - fft_conv()).abs().max())                              # the two computations agree (fp32 FFT round-off)
+        us = {name: [] for name in contenders}
+        for _ in range(3):                                                        # alternated
+            for name, fn in contenders.items():
+                us[name].append(timed(fn))
+        row = dict(taps=L, partitions=-(-L // (K.REVERB_FFT_N // 2)), workspace_MB=ws.numel() * 4 / 1e6, nfft_torch=nfft, max_abs_diff_vs_torch_fft=diff)
+        for name, v in us.items():
+            row[name + "_us"], row[name + "_us_median"] = v, float(np.median(v))
+        res["reverb"].append(row)
+        print(json.dumps(row), flush=True)
+        del ws, bank
+    res["reverb_timing"] = ("every utterance of the batch reverberated, 8 responses; HIP events around 20 back-to-back calls after 3 warm-up calls, 3 rounds "
+                            "alternating the contenders in one process; asr_reverb_fft_fwd = two launches per call; torch.fft = rfft of the batch and of the "
+                            "gathered responses at the next power of two, product, irfft, slice")
+    wins = [row["taps"] for row in res["reverb"] if "direct_kernel_us_median" in row and row["fft_kernel_us_median"] < row["direct_kernel_us_median"]]
+    res["smallest_measured_taps_where_fft_kernel_beats_direct"] = min(wins) if wins else None
+    # the waveform-fed joint step, every utterance reverberated with a response of 4096 taps, by either kernel
+    hs = responses(8, 4096)
+    mk = lambda **kw: BucketedWaveLoader(ds, B, parser=parser, augment=True, shuffle=True, seed=1, dtype=torch.bfloat16, **kw)
+    loaders = dict(off=mk(), direct=mk(rir=noise.RirBank(hs, "cuda", max_taps=4096, method="direct"), rir_prob=1.0),
+                   fft=mk(rir=noise.RirBank(hs, "cuda", max_taps=4096, method="fft"), rir_prob=1.0))
+
+    def run(ld):
+        n = 0
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for pack in ld:
+            model.iterate(pack, optimizer=opt)
+            n += 1
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3
+    for ld in loaders.values(): run(ld)                                           # warm-up epoch each
+    step = {name: [] for name in loaders}
+    for _ in range(3):
+        for name, ld in loaders.items():
+            step[name].append(run(ld))
+            print(f"joint step from waveforms, reverberation {name}: {step[name][-1]:.3f} ms/step", flush=True)
+    res["joint_step_ms"] = step
+    res["joint_step_ms_median"] = {name: float(np.median(v)) for name, v in step.items()}
+    res["joint_config"] = (f"{NB} batches of {B} x 5 s per epoch in host memory, SpecAugment on, bf16 joint model at the default width, 8 responses of 4096 taps, "
+                           "rir_prob 1; off = no bank; 1 warm-up epoch each, then 3 epochs each, alternating; host clock around an epoch that ends in a "
+                           "device synchronise")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out_path)
+
+
 if SPEED is not None:
     speed_bench()
+    sys.exit(0)
+if REVERB_FFT:
+    reverb_fft_bench()
     sys.exit(0)
 if NOISE_REVERB:
     noise_reverb_bench()

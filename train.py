@@ -20,7 +20,9 @@ Differences that come with the MI355X path:
   * `--noise_list=FILE --rir_list=FILE` (one wav path per line each) add noise and reverberation to the training utterances on the GPU,
     behind the speed perturbation: with probability `--rir_prob` (0.5) a room impulse response of the list is convolved in, with
     probability `--noise_prob` (0.5) a noise clip is mixed in at a signal-to-noise ratio drawn uniformly from `--snr_db=5,20` (dB);
-    drawn anew each epoch, never for dev / test (the reference has no waveform-side augmentation);
+    drawn anew each epoch, never for dev / test (the reference has no waveform-side augmentation); `--rir_method=direct|fft|auto` picks
+    the reverberation kernel and `--rir_max_taps=N` the number of taps kept of a response (direct: at most 8192, the default; fft and
+    auto: at most 65536, 4.1 s at 16 kHz);
   * `--cmvn=stats.npz` normalises the features of every part per mel bin with corpus statistics (tools/compute_cmvn.py) instead of
     per utterance: the causal features a streaming model is trained on (transcribe.py --stream=1 --cmvn=...);
   * `--synthetic=N` trains on N synthetic AISHELL-1-shaped utterances (no dataset ships with this repository);
@@ -72,6 +74,8 @@ class TrainConfig(DataConfigAiShell1):      # main.py:14-36
     rir_list = ""                           # --rir_list=FILE: wav paths of room impulse responses, one per line (train part only); empty = off
     noise_prob = 0.5                        # probability that an utterance gets noise / a response, drawn per epoch
     rir_prob = 0.5
+    rir_method = "direct"                   # --rir_method=direct|fft|auto: the direct FIR kernel, the FFT overlap-save kernels, or chosen per bank
+    rir_max_taps = 8192                     # --rir_max_taps=N: taps kept of a response (direct: at most 8192; fft / auto: at most 65536)
     snr_db = (5, 20)                        # --snr_db=5,20: the signal-to-noise ratio of a noisy utterance is uniform in this range (dB)
     speed_perturb = ()                      # --speed_perturb=0.9,1.0,1.1: speed factors of the train part (never dev / test); empty = off
 
@@ -181,7 +185,8 @@ def train(**kwargs):                        # main.py:55-98
                       rank=rank, world=world, cmvn=config.cmvn or None)
         train_iter = build_dataloader(batch_size=config.batch_size, part="train", augment=config.augment, speed_perturb=speed_factors(config.speed_perturb),
                                       noise=path_list(config.noise_list), rir=path_list(config.rir_list), noise_prob=float(config.noise_prob),
-                                      rir_prob=float(config.rir_prob), snr_db=snr_range(config.snr_db), **common)
+                                      rir_prob=float(config.rir_prob), snr_db=snr_range(config.snr_db), rir_method=str(config.rir_method),
+                                      rir_max_taps=int(config.rir_max_taps), **common)
         test_iter = build_dataloader(batch_size=config.eval_batch_size, part="test", augment=False, **common)
         dev_iter = build_dataloader(batch_size=config.eval_batch_size, part="dev", augment=False, **common)
 
