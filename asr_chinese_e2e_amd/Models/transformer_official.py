@@ -329,12 +329,13 @@ class _SpeechTransformer(BaseModel):
                 self._enc_given = prev
         return ctx()
 
-    def stream(self, batch_size, parser=None):
+    def stream(self, batch_size, parser=None, source_rate=None):
         """A streaming encoder for `batch_size` utterances (stream.StreamingEncoder): push chunks of encoder-rate features, get the
         greedy CTC ids each chunk adds; finish() gives transcribe()'s result for the same decoding chunk mask.  With an AudioParser
-        of norm="global" it also takes audio as it arrives: push_audio(pcm, n_samples, final)."""
+        of norm="global" it also takes audio as it arrives: push_audio(pcm, n_samples, final) - at source_rate, converted to
+        16 kHz on the GPU as it arrives (data_handler.resample.StreamResampler); None = 16 kHz, nothing is converted."""
         from ..stream import StreamingEncoder
-        return StreamingEncoder(self, batch_size, parser=parser)
+        return StreamingEncoder(self, batch_size, parser=parser, source_rate=source_rate)
 
     def forward(self, input):
         """transformer_official.py:68-81 (inference-style forward; no gradients).  A batch without a transcript (only wave / wave_len)

@@ -23,6 +23,7 @@ ACT_NONE, ACT_RELU, ACT_RELU_MASK = 0, 1, 2
 ABI_VERSION = 10
 DROP_PRE, DROP_POST = 1, 2
 SPEED_TILE = 1024      # ASR_SPEED_TILE of include/asr_hip.h: output samples per workgroup of asr_speed_perturb_fwd
+RESAMPLE_TILE = 1024   # ASR_RESAMPLE_TILE: output samples per workgroup of asr_resample_fwd
 REVERB_TILE, REVERB_CHUNK, REVERB_MAX_TAPS = 1024, 256, 8192      # ASR_REVERB_* of include/asr_hip.h: outputs per workgroup, taps per staged pass, tap limit
 REVERB_FFT_N, REVERB_FFT_MAX_TAPS = 4096, 65536      # ASR_REVERB_FFT_*: transform points (N / 2 new samples per block), tap limit of asr_reverb_fft_fwd
 NOISE_MIX_TILE = 4096      # ASR_NOISE_MIX_TILE: samples per workgroup and energy partial of asr_noise_mix_fwd
@@ -139,6 +140,7 @@ SIGNATURES = {
     "asr_utt_norm_lfr_fwd": (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
     "asr_utt_norm_augment_lfr_fwd": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "asr_speed_perturb_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "asr_resample_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "asr_reverb_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
     "asr_reverb_fft_workspace_bytes": (Z, [I, I, I]),
     "asr_reverb_fft_fwd": (I, [P, P, P, P, P, P, P, P, P, Z, I, I, I, I, P]),

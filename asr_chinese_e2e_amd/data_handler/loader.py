@@ -26,6 +26,7 @@ from .padder import Padder
 from .processor import AudioParser
 from . import speed as speed_mod
 from . import noise as noise_mod
+from . import resample as resample_mod
 
 
 def load_wav(path):
@@ -44,11 +45,34 @@ def load_wav(path):
 class WaveDataset:
     """items: list of (waveform, text) where waveform is a 1-D float array / tensor or a path to a
     16-bit WAV file, and text is a string (converted by `vocab.convert_str(..., use_bos=False,
-    use_eos=False)` as ai_shell_1.py:53-54) or a list of ids."""
+    use_eos=False)` as ai_shell_1.py:53-54) or a list of ids.
+    resample=True: a file at another rate the resampler takes (resample.plan) is accepted and handed on at ITS rate - wave(), wave_into()
+    and num_samples() stay in source samples, rate(i) tells the rate, and the consumer (BucketedWaveLoader(resample=True), transcribe.py)
+    converts on the GPU; an array in memory carries its rate as a third element (waveform, text, rate).  False: today's ValueError."""
 
-    def __init__(self, items, vocab=None, sample_rate=16000):
-        self.items, self.vocab, self.sample_rate = items, vocab, sample_rate
+    def __init__(self, items, vocab=None, sample_rate=16000, resample=False):
+        self.items, self.vocab, self.sample_rate, self.resample = items, vocab, sample_rate, bool(resample)
         self._len = [None] * len(items)
+        self._rate = [None] * len(items)
+
+    def _check_rate(self, name, sr):
+        if sr != self.sample_rate:
+            if not self.resample:
+                raise ValueError(f"{name}: sample rate {sr}, expected {self.sample_rate}")
+            resample_mod.plan(sr)      # an unsupported rate raises here, naming it
+
+    def rate(self, i):
+        """Source rate of utterance i: a file's header, an array's third element, else sample_rate; cached."""
+        if self._rate[i] is None:
+            it = self.items[i]
+            if isinstance(it[0], str):
+                with wave_module.open(it[0], "rb") as f:
+                    sr = f.getframerate()
+            else:
+                sr = int(it[2]) if len(it) > 2 else self.sample_rate
+            self._check_rate(it[0] if isinstance(it[0], str) else f"utterance {i}", sr)
+            self._rate[i] = sr
+        return self._rate[i]
 
     def __len__(self):
         return len(self.items)
@@ -57,8 +81,7 @@ class WaveDataset:
         w = self.items[i][0]
         if isinstance(w, str):
             w, sr = load_wav(w)
-            if sr != self.sample_rate:
-                raise ValueError(f"{self.items[i][0]}: sample rate {sr}, expected {self.sample_rate}")
+            self._check_rate(self.items[i][0], sr)
         return np.asarray(w, dtype=np.float32).reshape(-1)
 
     def wave_into(self, i, row):
@@ -70,8 +93,7 @@ class WaveDataset:
                 if f.getsampwidth() != 2:
                     raise ValueError(f"{w}: only 16-bit PCM is supported (sample width {f.getsampwidth()})")
                 sr, ch, n = f.getframerate(), f.getnchannels(), f.getnframes()
-                if sr != self.sample_rate:
-                    raise ValueError(f"{w}: sample rate {sr}, expected {self.sample_rate}")
+                self._check_rate(w, sr)
                 pcm = np.frombuffer(f.readframes(n), dtype="<i2")
             # the sample count is what the file actually holds (a data chunk shorter than its header says is a truncated recording, not an
             # error), never more than the row the loader sized from the header
@@ -162,6 +184,15 @@ class BatchPlan:
         return self.batches(self.rng, lengths) + (fidx,)
 
 
+def source_rates(dataset, lengths):
+    """-> (rate of every utterance, or None when all are at 16 kHz; lengths at 16 kHz), host logic only.  The converted lengths are what
+    BatchPlan forms its buckets on (and what a speed factor then perturbs); `lengths` stay source samples."""
+    rates = [dataset.rate(i) for i in range(len(dataset))]
+    if all(r == resample_mod.TARGET for r in rates):
+        return None, lengths
+    return rates, [resample_mod.plan(r).n_out(n) for n, r in zip(lengths, rates)]
+
+
 _LOADERS = weakref.WeakSet()      # loaders of this process (paused() holds every one's gate)
 
 
@@ -189,7 +220,7 @@ class BucketedWaveLoader:
 
     def __init__(self, dataset, batch_size, parser=None, augment=False, shuffle=True, drop_last=False, seed=0, bucket_size=None,
                  device="cuda", dtype=torch.bfloat16, rank=0, world=1, speed_perturb=None, noise=None, noise_prob=0.5, snr_db=(5, 20), rir=None,
-                 rir_prob=0.5, rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS):
+                 rir_prob=0.5, rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS, resample=False):
         """rank / world: data-parallel sharding.  Every rank draws the SAME batch list (same seed), keeps only the full
         batches when world > 1 (dist.DataParallel normalises by world x local batch and every rank must take the same
         number of steps), drops the ragged tail of len(batches) % world and takes batches[rank::world].
@@ -203,14 +234,21 @@ class BucketedWaveLoader:
         and labels do not change.  Both None: nothing of it is called.
         rir_method, rir_max_taps: for a bank built here from paths - "direct" (asr_reverb_fwd, responses cut to at most 8192 taps), "fft"
         (asr_reverb_fft_fwd, at most 65536 taps, cost nearly flat in the length) or "auto" (decided once from the bank's longest response:
-        noise.RirBank).  A ready-made RirBank decides by its own method.  Draws, lengths and buckets do not depend on the method."""
+        noise.RirBank).  A ready-made RirBank decides by its own method.  Draws, lengths and buckets do not depend on the method.
+        resample: True = utterances at another rate than 16 kHz (dataset.rate(i); WaveDataset(resample=True)) are converted on the loader's
+        stream in front of everything else - one asr_resample_fwd launch per batch, whatever rates it mixes; a batch that is all 16 kHz
+        launches nothing.  Buckets, and the speed perturbation's lengths, are formed on the converted lengths; the staging slot holds
+        source samples.  False: nothing of it is called."""
         self.ds, self.batch_size, self.augment = dataset, batch_size, augment
         self.device, self.dtype = torch.device(device), dtype
         if self.device.type != "cuda":
             raise RuntimeError("the feature front end runs on the GPU only (no CPU fallback)")
         self.parser = parser or AudioParser(device=self.device)
         self.stream = self._copy_stream()
-        self.lengths = [dataset.num_samples(i) for i in range(len(dataset))]
+        self.lengths = [dataset.num_samples(i) for i in range(len(dataset))]      # source samples: what the staging slot holds
+        # per-utterance source rates (None: all 16 kHz, or resample off) and the lengths at 16 kHz the buckets are formed on
+        self.rates, lengths16 = source_rates(dataset, self.lengths) if resample else (None, self.lengths)
+        self.rate_table = resample_mod.RateTable(self.rates, self.device) if self.rates is not None else None      # resident on the device
         self.speed = None      # (pq list, pq (F, 2) int32, taps (F, qmax, ntaps) f32): built once, resident on the device
         if speed_perturb is not None and len(speed_perturb) > 0:
             pq, taps = speed_mod.build_tables(speed_perturb)
@@ -218,9 +256,9 @@ class BucketedWaveLoader:
         bank = lambda v, cls, **kw: None if v is None else v if isinstance(v, cls) else cls(v, self.device, **kw) if len(v) > 0 else None
         if rir_method not in noise_mod.METHODS + ("auto",):
             raise ValueError(f"rir_method={rir_method!r}: one of 'direct', 'fft', 'auto'")
-        self.noise, self.rir = bank(noise, noise_mod.NoiseBank), bank(rir, noise_mod.RirBank, max_taps=rir_max_taps, method=rir_method)
+        self.noise, self.rir = bank(noise, noise_mod.NoiseBank, resample=resample), bank(rir, noise_mod.RirBank, max_taps=rir_max_taps, method=rir_method, resample=resample)
         self.noise_prob, self.rir_prob, self.snr_db = float(noise_prob), float(rir_prob), snr_db
-        self.plan = BatchPlan(self.lengths, batch_size, bucket_size, shuffle, drop_last, seed, rank, world, self.speed[0] if self.speed else None)
+        self.plan = BatchPlan(lengths16, batch_size, bucket_size, shuffle, drop_last, seed, rank, world, self.speed[0] if self.speed else None)
         self.rank, self.world, self.shuffle, self.drop_last, self.bucket_size = self.plan.rank, self.plan.world, shuffle, self.plan.drop_last, bucket_size
         self.rng = self.plan.rng                # batch order AND SpecAugment masks (the reference uses the global `random`)
         self._gate = threading.Lock()      # held by the helper thread around _prepare; paused() takes it
@@ -240,7 +278,7 @@ class BucketedWaveLoader:
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
     def _batches(self, rng):
-        batches = bucket_batches(self.lengths, self.batch_size, self.bucket_size, self.shuffle, self.drop_last, rng)
+        batches = bucket_batches(self.plan.lengths, self.batch_size, self.bucket_size, self.shuffle, self.drop_last, rng)
         return shard_batches(batches, self.rank, self.world)
 
     # ---- staging: pinned host buffers that are REUSED (a fresh pageable tensor + pin_memory() + 32 tensor-slice assignments + six small
@@ -275,14 +313,15 @@ class BucketedWaveLoader:
         tgt = [self.ds.ids(i) for i in idx]
         B = len(idx)
         nf = B if fidx is not None else 0      # the factor indices ride behind the labels in the one integer buffer
+        nr = 6 * B if self.rates is not None else 0      # behind them the rate indices (B) and the resampler's windows (B, 5)
         na = 5 * B if aug is not None else 0   # and behind them the response indices (B) and the noise parameters (B, 4)
         into = getattr(self.ds, "wave_into", None)
         waves = None if into is not None else [self.ds.wave(i) for i in idx]
         smax = max(self.lengths[i] for i in idx) if waves is None else max(w.size for w in waves)
         lmax = max(1, max(len(t) for t in tgt))
-        slot = self._slot(k % self.SLOTS, B * smax, 2 * B + B * lmax + nf + na)
+        slot = self._slot(k % self.SLOTS, B * smax, 2 * B + B * lmax + nf + nr + na)
         buf = slot["wave_np"][:B * smax].reshape(B, smax)
-        meta = slot["meta_np"][:2 * B + B * lmax + nf + na]
+        meta = slot["meta_np"][:2 * B + B * lmax + nf + nr + na]
         tg = meta[2 * B:2 * B + B * lmax].reshape(B, lmax)
         items = getattr(self.ds, "items", None)
         if waves is None and items is not None and any(isinstance(items[i][0], str) for i in idx):
@@ -304,6 +343,15 @@ class BucketedWaveLoader:
             meta[r], meta[B + r] = sizes[r], len(t)
             tg[r, :len(t)] = t
             tg[r, len(t):] = 0
+        q0 = 2 * B + B * lmax + nf      # [q0, q0 + B): rate index, [q0 + B, q0 + 6 B): {in_base, n_avail, n_total, out_start, n_emit}
+        smax16 = 0        # > 0: at least one utterance of the batch is at another rate than 16 kHz
+        if nr:
+            rates = [self.rates[i] for i in idx]
+            win, ridx = self.rate_table.windows(sizes, rates)
+            meta[q0:q0 + B], meta[q0 + B:q0 + 6 * B] = ridx, win.reshape(-1)
+            if any(r >= 0 for r in ridx):
+                sizes = [int(v) for v in win[:, 4]]      # from here on the lengths are those at 16 kHz
+                smax16 = max(1, max(sizes))
         smax_out = 0      # > 0: at least one utterance of the batch is resampled
         if fidx is not None:
             pq = self.speed[0]
@@ -311,7 +359,7 @@ class BucketedWaveLoader:
             meta[2 * B + B * lmax:2 * B + B * lmax + nf] = fs
             if any(pq[f][0] != pq[f][1] for f in fs):
                 smax_out = max(1, max(speed_mod.perturbed_len(sizes[r], *pq[f]) for r, f in enumerate(fs)))
-        a0 = 2 * B + B * lmax + nf      # [a0, a0 + B): response index, [a0 + B, a0 + 5 B): {clip, offset, scale as float bits, 0}
+        a0 = q0 + nr      # [a0, a0 + B): response index, [a0 + B, a0 + 5 B): {clip, offset, scale as float bits, 0}
         any_rir = any_noise = False
         if aug is not None:
             nidx, noff, snr, ridx = aug
@@ -326,9 +374,14 @@ class BucketedWaveLoader:
             dev_meta = slot["meta"][:meta.size].to(self.device, non_blocking=True)
             slot["copied"].record()
             wav_in, len_in = dev_wav, dev_meta[:B]
+            if smax16:
+                from .. import kernels as K
+                wav_in, len_in = K.resample(dev_wav, dev_meta[q0:q0 + B], dev_meta[q0 + B:q0 + 6 * B].view(B, 5), *self.rate_table.dev, smax16)
             if smax_out:
                 from .. import kernels as K
-                wav_in, len_in = K.speed_perturb(dev_wav, len_in, dev_meta[2 * B + B * lmax:2 * B + B * lmax + nf], self.speed[1], self.speed[2], smax_out)
+                if smax16:
+                    extra += (wav_in, len_in)
+                wav_in, len_in = K.speed_perturb(wav_in, len_in, dev_meta[2 * B + B * lmax:2 * B + B * lmax + nf], self.speed[1], self.speed[2], smax_out)
             if any_rir:      # a batch in which no utterance drew a response launches nothing
                 from .. import kernels as K
                 extra += (wav_in,)
@@ -425,7 +478,7 @@ def parser_norm(cmvn):
 def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=True, sample_rate=16000, window_size=400, n_mels=40,
                      augment=False, predump=False, use_old=False, lfr_m=4, lfr_n=3, dtype=torch.bfloat16, shuffle=None, seed=0,
                      rank=0, world=1, speed_perturb=None, cmvn=None, noise=None, noise_prob=0.5, snr_db=(5, 20), rir=None, rir_prob=0.5,
-                     rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS):
+                     rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS, resample=False):
     """build_dataloader of the reference (data/data_loader/ai_shell_1.py:91-104), same arguments: reads the manifest
     `<collector_path>_<part>.json` written by the reference's collector (one JSON object {"wave": path, "tgt": text}
     per line, data_collector/ai_shell_1.py:73-79) and returns an iterable of Packs.  The reference computes features
@@ -435,7 +488,9 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
     noise / rir, noise_prob, snr_db, rir_prob: BucketedWaveLoader's noise and reverberation augmentation, applied to part="train" only
     (the reference has none); None = off.  rir_method, rir_max_taps: BucketedWaveLoader's, for the same part.
     cmvn: path of a global-CMVN statistics file (tools/compute_cmvn.py): the features of this part are normalised per mel bin by
-    the corpus statistics (AudioParser norm="global"); None / empty = the reference's per-utterance normalisation."""
+    the corpus statistics (AudioParser norm="global"); None / empty = the reference's per-utterance normalisation.
+    resample: True = files (and noise / response files of a bank built here) at another rate than 16 kHz are converted on the GPU
+    (WaveDataset / BucketedWaveLoader / noise banks, every part); False = they raise, as before."""
     import json
     if not use_cuda:
         raise RuntimeError("the feature front end runs on the GPU only (no CPU fallback)")
@@ -447,9 +502,9 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
             if line.strip():
                 rec = json.loads(line)
                 items.append((rec["wave"], rec["tgt"]))
-    ds = WaveDataset(items, vocab, sample_rate=sample_rate)
+    ds = WaveDataset(items, vocab, sample_rate=sample_rate, resample=resample)
     parser = AudioParser(sample_rate=sample_rate, n_mels=n_mels, lfr_m=lfr_m, lfr_n=lfr_n, device="cuda", **parser_norm(cmvn))
     wave_aug = dict(noise=noise, noise_prob=noise_prob, snr_db=snr_db, rir=rir, rir_prob=rir_prob, rir_method=rir_method,
                     rir_max_taps=rir_max_taps) if part == "train" else {}
     return BucketedWaveLoader(ds, batch_size, parser=parser, augment=augment, shuffle=(part == "train") if shuffle is None else shuffle,
-                              drop_last=True, seed=seed, dtype=dtype, rank=rank, world=world, speed_perturb=speed_perturb, **wave_aug)
+                              drop_last=True, seed=seed, dtype=dtype, rank=rank, world=world, speed_perturb=speed_perturb, resample=resample, **wave_aug)

@@ -19,13 +19,21 @@ METHODS = ("direct", "fft")
 PRE_PEAK = 64        # samples kept in front of a response's peak
 
 
-def _read(src, what):
-    """A path -> (float32 samples, name) through load_wav, refusing another rate; an array -> itself, in its own precision."""
+def _read(src, what, resample=False, device="cuda"):
+    """A path -> (float32 samples, name) through load_wav, refusing another rate - or, with resample=True, converting it to 16 kHz on
+    `device` (data_handler.resample, one asr_resample_fwd launch per file, when the bank is built: before any truncation or scaling);
+    an array -> itself, in its own precision."""
     if isinstance(src, str):
         from .loader import load_wav
         w, sr = load_wav(src)
         if sr != SAMPLE_RATE:
-            raise ValueError(f"{src}: sample rate {sr}, the {what} bank needs {SAMPLE_RATE}")
+            if not resample:
+                raise ValueError(f"{src}: sample rate {sr}, the {what} bank needs {SAMPLE_RATE}")
+            from . import resample as resample_mod
+            resample_mod.plan(sr)      # an unsupported rate raises here, naming it
+            if w.size:
+                out, _, n_out = resample_mod.resample_batch(torch.from_numpy(w)[None].to(device), [w.size], [sr])
+                w = out[0, :n_out[0]].cpu().numpy()
         return w, src
     if torch.is_tensor(src):
         src = src.detach().cpu().numpy()
@@ -67,12 +75,13 @@ class RirBank:
     """Room impulse responses resident on `device`: table (R, Lcap) f32, lens, peaks (R) int32 (rir_table).
     method: the kernel the loader convolves with - "direct" (asr_reverb_fwd, at most 8192 taps) or "fft" (asr_reverb_fft_fwd, at most
     65536); "auto" reads the responses with the FFT path's limit and settles on "fft" when the longest one kept has at least
-    AUTO_FFT_FROM_TAPS taps, on "direct" otherwise.  self.method is always one of METHODS."""
+    AUTO_FFT_FROM_TAPS taps, on "direct" otherwise.  self.method is always one of METHODS.
+    resample: True = files at another rate are converted to 16 kHz on the device (_read) before the truncation and the energy scaling."""
 
-    def __init__(self, paths_or_arrays, device="cuda", max_taps=MAX_TAPS, method="direct"):
+    def __init__(self, paths_or_arrays, device="cuda", max_taps=MAX_TAPS, method="direct", resample=False):
         if method not in METHODS + ("auto",):
             raise ValueError(f"method={method!r}: one of 'direct', 'fft', 'auto'")
-        read = [_read(s, "impulse-response") for s in paths_or_arrays]
+        read = [_read(s, "impulse-response", resample, device) for s in paths_or_arrays]
         table, lens, peaks = rir_table([w for w, _ in read], max_taps, [n for _, n in read], MAX_TAPS if method == "direct" else FFT_MAX_TAPS)
         if method == "auto":
             method = "fft" if int(lens.max()) >= AUTO_FFT_FROM_TAPS else "direct"
@@ -105,14 +114,14 @@ def noise_table(clips, names=None, max_seconds=600):
 
 class NoiseBank:
     """Noise clips resident on `device`: one flat f32 buffer `noise`, clip j at [off[j], off[j + 1]) (`noise_off`, N + 1 int32);
-    `lens`: the clip lengths on the host (the offsets are drawn there)."""
+    `lens`: the clip lengths on the host (the offsets are drawn there).  resample: True = files at another rate are converted (_read)."""
 
-    def __init__(self, paths_or_arrays, device="cuda", max_seconds=600):
+    def __init__(self, paths_or_arrays, device="cuda", max_seconds=600, resample=False):
         clips, names, total = [], [], 0
         for s in paths_or_arrays:
             if total >= max_seconds * SAMPLE_RATE:      # full: the remaining files are not even read
                 break
-            w, name = _read(s, "noise")
+            w, name = _read(s, "noise", resample, device)
             clips.append(w)
             names.append(name)
             total += w.size

@@ -891,6 +891,26 @@ def speed_perturb(wav, wav_len, factor, pq, taps, Smax_out, out=None, out_len=No
     return out, out_len
 
 
+RESAMPLE_TILE = _lib.RESAMPLE_TILE      # output samples per workgroup of the sample-rate conversion kernel
+
+
+def resample(wav, rate_idx, win, pq, tap_off, taps, Smax_out, out=None, out_len=None):
+    """Every utterance of wav (B, Smax) f32 converted to 16 kHz from the source rate of plan rate_idx[b] (outside [0, R): a copy), over
+    the window win[b] = {in_base, n_avail, n_total, out_start, n_emit} (data_handler.resample.RateTable builds pq, tap_off, taps and the
+    offline windows; include/asr_hip.h: asr_resample_fwd).  -> (out (B, Smax_out) f32, zero at and beyond each n_emit, out_len (B) int32)."""
+    _chk_f32(wav, taps, out)
+    _chk_i32(rate_idx, win, pq, tap_off, out_len)
+    B, Smax = wav.shape
+    R = pq.shape[0]
+    assert pq.dim() == 2 and pq.shape[1] == 2 and tap_off.numel() == R + 1 and rate_idx.numel() == B and tuple(win.shape) == (B, 5) and taps.dim() == 1
+    out = torch.empty(B, Smax_out, dtype=torch.float32, device=wav.device) if out is None else out
+    out_len = torch.empty(B, dtype=torch.int32, device=wav.device) if out_len is None else out_len
+    assert tuple(out.shape) == (B, Smax_out) and out_len.numel() == B and out.data_ptr() != wav.data_ptr()
+    check(lib.asr_resample_fwd(_p(wav), _p(rate_idx), _p(win), _p(pq), _p(tap_off), _p(taps), _p(out), _p(out_len), B, Smax, int(Smax_out), R,
+                               taps.numel(), _stream()), "asr_resample_fwd")
+    return out, out_len
+
+
 REVERB_TILE, REVERB_CHUNK, REVERB_MAX_TAPS = _lib.REVERB_TILE, _lib.REVERB_CHUNK, _lib.REVERB_MAX_TAPS
 NOISE_MIX_TILE = _lib.NOISE_MIX_TILE
 

@@ -21,7 +21,7 @@ BLANK = 0      # the CTC blank (= PAD_ID of the model)
 
 
 class StreamingEncoder:
-    def __init__(self, model, batch_size, parser=None):
+    def __init__(self, model, batch_size, parser=None, source_rate=None):
         C, left = model.decoding_chunk_size, model.decoding_left_chunks
         if C <= 0:
             raise ValueError("model.stream() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
@@ -38,6 +38,11 @@ class StreamingEncoder:
         self.caches = None                   # [buffer][layer] -> (B * cap, 2 H dk); the second buffer only with left >= 0 (_slide)
         self.outs, self.feats = [], []
         self.parser, self.frontend = parser, None      # the front end is built by the first push_audio
+        # source_rate: the rate of the audio push_audio receives; other than 16 kHz it goes through a StreamResampler first (None: 16 kHz)
+        self.source_rate, self.resampler = source_rate, None
+        if source_rate is not None:
+            from .data_handler import resample
+            resample.plan(source_rate)      # an unsupported rate raises here
 
     def _grow(self, eng, need, dev):
         hd2 = 2 * eng.H * eng.dk
@@ -143,9 +148,12 @@ class StreamingEncoder:
             from .data_handler.stream_frontend import StreamingFrontEnd
             eng = self.model._ensure_engine(self.parser.window.device)
             self.frontend = StreamingFrontEnd(self.parser, self.B, self.C, dtype=eng.dtype)
+            if self.source_rate is not None and int(self.source_rate) != 16000:
+                from .data_handler.resample import StreamResampler
+                self.resampler = StreamResampler(self.B, self.source_rate, self.parser.window.device)
 
     def push_audio(self, pcm, n_samples, final):
-        """pcm (B, S) f32 on the host or the device: n_samples[b] <= S new samples of utterance b (0 is fine), final[b] closes it.  Runs
+        """pcm (B, S) f32 on the host or the device (at model.stream's source_rate, 16 kHz by default): n_samples[b] <= S new samples of utterance b (0 is fine), final[b] closes it.  Runs
         every chunk the audio completes (StreamingFrontEnd: the utterances advance in lock-step) and returns per utterance the greedy CTC
         ids they add.  Needs model.stream(B, parser=...) with a parser of norm="global"; audio for a closed utterance raises."""
         out = [[] for _ in range(self.B)]
@@ -157,6 +165,8 @@ class StreamingEncoder:
     def push_audio_chunks(self, pcm, n_samples, final):
         """push_audio chunk by chunk: yields (n_valid, ids) = push()'s arguments and result for every chunk the audio completes."""
         self._ensure_frontend()
+        if self.resampler is not None:      # samples at source_rate -> the 16 kHz samples they complete (bit for bit the offline conversion)
+            pcm, n_samples, final = self.resampler.push(pcm, n_samples, final)
         for feats, nv in self.frontend.push_audio(pcm, n_samples, final):
             yield nv, self.push(feats, nv)
 

@@ -666,6 +666,34 @@ int asr_speed_perturb_fwd(const float* wav, const int32_t* wav_len, const int32_
                           int qmax, int ntaps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sample-rate conversion of a waveform batch to 16 kHz, in front of asr_speed_perturb_fwd and everything behind it.
+ * Stands in for:  the "kaiser_best" resamplers of the common toolkits (Kaiser-windowed sinc, 64 zero crossings, roll-off
+ *                 0.9476, beta 14.77).  The reference has no resampler: parity unpinned by the reference; the definition is
+ *                 in data_handler/resample.py and restated in float64 in tests/resample_ref.py.
+ * wav: (B, Smax) f32.  rate_idx: (B) int32 index r into the plans; outside [0, R) (16 kHz itself) the row is copied.
+ * pq: (R, 2) int32 = (p, q), source rate = 16000 p / q in lowest terms, q <= ASR_RESAMPLE_Q_MAX; tap_off: (R + 1) int32,
+ * ascending; taps: taps_len f32, plan r at taps[tap_off[r] : tap_off[r + 1]] as T[j][m], j < ntaps = 2 W + 1 <=
+ * ASR_RESAMPLE_NTAPS_MAX (odd), m < q, T[j][n mod q] = h((n p mod q) / q - (j - W)) - the phase table in the order the
+ * kernel reads it.  A plan outside these ranges, or with p == q, is taken as a copy.  R <= ASR_RESAMPLE_PLANS_MAX.
+ * win: (B, 5) int32 = {in_base, n_avail, n_total, out_start, n_emit} per utterance: the row holds samples
+ * [in_base, in_base + n_avail) of an utterance of n_total samples (in_base may be negative; x[k] = 0 for k < 0, k >= n_total
+ * and outside the row), and
+ *   out[b, t] = y[out_start + t] = sum_{j = -W .. W} x[((out_start + t) p) / q + j] T[j + W][(out_start + t) mod q]
+ * for t < n_emit, exact zeros for n_emit <= t < Smax_out, out_len[b] = n_emit (clamped to Smax_out).  Offline: {0, n_in,
+ * n_in, 0, ceil(n_in q / p)}.  Per output acc = 0, then acc = fmaf(x, T, acc) for j ascending, one accumulator: the bits
+ * do not depend on the window, so a stream cut anywhere reproduces the offline call.  Index arithmetic is exact (64 bits
+ * once per workgroup).  out must not alias wav.  16-byte accesses are used where wav / out are 16-byte aligned; any Smax /
+ * Smax_out is accepted.  No atomics, no workspace.
+ */
+#define ASR_RESAMPLE_TILE 1024        /* output samples per workgroup (tests cover the tile edges) */
+#define ASR_RESAMPLE_Q_MAX 640
+#define ASR_RESAMPLE_NTAPS_MAX 1023
+#define ASR_RESAMPLE_PLANS_MAX 16
+int asr_resample_fwd(const float* wav, const int32_t* rate_idx, const int32_t* win, const int32_t* pq,
+                     const int32_t* tap_off, const float* taps, float* out, int32_t* out_len, int B, int Smax,
+                     int Smax_out, int R, int taps_len, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Reverberation and additive noise of a waveform batch (the other two waveform-side augmentations of the Kaldi / WeNet /
  * ESPnet recipes), behind asr_speed_perturb_fwd and in front of asr_logmel_fwd: first the room, then the noise.
  * Stands in for:  Kaldi steps/data/reverberate_data_dir.py (wav-reverberate --shift-output) / WeNet add_reverb and

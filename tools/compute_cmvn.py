@@ -2,10 +2,12 @@
 """compute_cmvn.py - global CMVN statistics of a corpus, one pass on the GPU.
 
     python tools/compute_cmvn.py --collector_path=data/aishell1 --out=exp/cmvn.npz [--part=train] [--n_mels=40] [--batch_size=32]
+                                 [--resample=1]
 
 Reads the manifest `<collector_path>_<part>.json` train.py reads, decodes the files, and for every batch runs the training front
 end's own log-mel kernel and adds the per-bin sums of its valid frames to float64 accumulators on the device (data_handler/cmvn.py);
-the audio is never perturbed or augmented.  Writes mean, istd, count and n_mels as .npz: pass it to train.py --cmvn and to
+the audio is never perturbed or augmented.  With --resample=1 files at another rate than 16 kHz are converted on the GPU first (one
+launch per batch, data_handler/resample.py) instead of ending the run.  Writes mean, istd, count and n_mels as .npz: pass it to train.py --cmvn and to
 transcribe.py --cmvn.
 """
 import json
@@ -28,22 +30,33 @@ def manifest_waves(collector_path, part):
         return [json.loads(line)["wave"] for line in f if line.strip()]
 
 
-def compute(files, n_mels=40, batch_size=32, sample_rate=16000, device="cuda"):
+def compute(files, n_mels=40, batch_size=32, sample_rate=16000, device="cuda", resample=False):
     """-> (mean, istd, count) over the log-mel frames of `files`."""
+    from asr_chinese_e2e_amd.data_handler import resample as resample_mod
     acc = CmvnAccumulator(AudioParser(sample_rate=sample_rate, n_mels=n_mels, device=device))
     order = sorted(range(len(files)), key=lambda i: os.path.getsize(files[i]))      # batches of similar length: little padding
     for i in range(0, len(order), batch_size):
-        waves = []
+        waves, rates = [], []
         for j in order[i:i + batch_size]:
             pcm, sr = load_wav(files[j])
             if sr != sample_rate:
-                raise SystemExit(f"compute_cmvn.py: {files[j]}: sample rate {sr}, expected {sample_rate}")
+                if not resample:
+                    raise SystemExit(f"compute_cmvn.py: {files[j]}: sample rate {sr}, expected {sample_rate}")
+                try:
+                    resample_mod.plan(sr)
+                except ValueError as e:
+                    raise SystemExit(f"compute_cmvn.py: {files[j]}: {e}") from e
             waves.append(pcm)
+            rates.append(sr)
         S = max(256, max(len(w) for w in waves))
         wav = np.zeros((len(waves), S), dtype=np.float32)
         for b, w in enumerate(waves):
             wav[b, :len(w)] = w
-        acc.update(torch.from_numpy(wav).to(device), torch.tensor([len(w) for w in waves], dtype=torch.int32, device=device))
+        dev_wav, dev_len = torch.from_numpy(wav).to(device), torch.tensor([len(w) for w in waves], dtype=torch.int32, device=device)
+        if any(r != sample_rate for r in rates):      # one launch for the batch, whatever rates it mixes
+            n16 = [resample_mod.plan(r).n_out(len(w)) for w, r in zip(waves, rates)]
+            dev_wav, dev_len, _ = resample_mod.resample_batch(dev_wav, [len(w) for w in waves], rates, max(256, max(n16)))
+        acc.update(dev_wav, dev_len)
     return acc.finalize()
 
 
@@ -55,7 +68,8 @@ def main(argv):
         raise SystemExit("compute_cmvn.py needs an MI355X: the front end has no CPU fallback")
     files = manifest_waves(flags["collector_path"], str(flags.get("part", "train")))
     n_mels = int(flags.get("n_mels", 40))
-    mean, istd, count = compute(files, n_mels=n_mels, batch_size=int(flags.get("batch_size", 32)), sample_rate=int(flags.get("sample_rate", 16000)))
+    mean, istd, count = compute(files, n_mels=n_mels, batch_size=int(flags.get("batch_size", 32)), sample_rate=int(flags.get("sample_rate", 16000)),
+                               resample=bool(int(flags.get("resample", 0))))
     save_cmvn(str(flags["out"]), mean, istd, count)
     print(json.dumps({"out": str(flags["out"]), "files": len(files), "frames": count, "n_mels": n_mels,
                       "mean_range": [float(mean.min()), float(mean.max())], "std_range": [float(1 / istd.max()), float(1 / istd.min())]}))

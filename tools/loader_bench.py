@@ -8,7 +8,10 @@ utterance of B = 32 x 5 s reverberated (achieved fp32 FLOP/s against the vector 
 asr_noise_mix_fwd beside a device-to-device copy of its bytes, and the waveform-fed joint step with the augmentation off, at the default
 probabilities and with both probabilities 1, alternated in one process.
 python tools/loader_bench.py --reverb_fft [--out=profiles/reverb_fft_bench.json]: asr_reverb_fft_fwd, asr_reverb_fwd (up to its 8192 taps) and
-the torch.fft stand-in at 256 .. 65536 taps, same protocol, and the waveform-fed joint step with rir_method direct and fft at 4096 taps."""
+the torch.fft stand-in at 256 .. 65536 taps, same protocol, and the waveform-fed joint step with rir_method direct and fft at 4096 taps.
+python tools/loader_bench.py --resample [--out=profiles/resample_bench.json]: asr_resample_fwd on B = 32 x 5 s at 8, 44.1 and 48 kHz beside a
+device-to-device copy of its bytes and the strided conv1d polyphase form in torch, the waveform-fed joint step from a 16 kHz corpus (resample
+off and on) and from a 48 kHz one, alternated, and the host time of StreamResampler.push for one 480 ms block."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -19,7 +22,8 @@ from asr_chinese_e2e_amd.Trainer import FusedAdam, NoamOpt
 SPEED = next((a for a in sys.argv[1:] if a.startswith("--speed_perturb")), None)
 NOISE_REVERB = any(a == "--noise_reverb" for a in sys.argv[1:])
 REVERB_FFT = any(a == "--reverb_fft" for a in sys.argv[1:])
-JOINT = SPEED is not None or NOISE_REVERB or REVERB_FFT or (len(sys.argv) > 1 and sys.argv[1] == "joint")
+RESAMPLE = any(a == "--resample" for a in sys.argv[1:])
+JOINT = SPEED is not None or NOISE_REVERB or REVERB_FFT or RESAMPLE or (len(sys.argv) > 1 and sys.argv[1] == "joint")
 B, S, NB = 32, 16000 * 5, 40
 rng = np.random.RandomState(0)
 vocab = Vocab.synthetic(4232)
@@ -303,8 +307,120 @@ def reverb_fft_bench():
     print("wrote", out_path)
 
 
+def resample_bench():
+    import json
+    from asr_chinese_e2e_amd import kernels as K
+    from asr_chinese_e2e_amd.data_handler import resample as R
+    out_path = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--out=")), "profiles/resample_bench.json")
+    PEAK = 157.3e12                                                               # fp32 vector peak of one MI355X, FLOP/s
+    res = dict(device=torch.cuda.get_device_name(0), B=B, seconds=5, rates=[])
+
+    def timed(fn, reps=20, warm=3):
+        for _ in range(warm): fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps): fn()
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3
+    for fs in (8000, 44100, 48000):
+        pl = R.plan(fs)
+        n_in = 5 * fs
+        n_out = pl.n_out(n_in)
+        table = R.RateTable([fs], "cuda")
+        wav = torch.randn(B, n_in, device="cuda") * 0.1
+        win, ridx = table.windows([n_in] * B, [fs] * B)
+        args = (wav, torch.from_numpy(ridx).cuda(), torch.from_numpy(win).cuda()) + table.dev + (n_out,)
+        out, out_len = K.resample(*args)
+        assert out_len.tolist() == [n_out] * B
+        half = (B * n_in + B * n_out) // 2                                        # a copy of `half` floats reads and writes the kernel's bytes in all
+        src, dst = torch.randn(half, device="cuda"), torch.empty(half, device="cuda")
+        # the stand-in: the polyphase filter as ONE strided conv1d, a channel per phase, as the common toolkits do it - channel i holds
+        # H[(i p) mod q] shifted by floor(i p / q), so every channel is wider than the filter by up to p taps (those products are wasted)
+        H = R.phase_table(pl).astype(np.float32)
+        shift = (np.arange(pl.q) * pl.p) // pl.q
+        wt = np.zeros((pl.q, 1, pl.ntaps + int(shift.max())), dtype=np.float32)
+        for i in range(pl.q):
+            wt[i, 0, shift[i]:shift[i] + pl.ntaps] = H[(i * pl.p) % pl.q]
+        wt = torch.from_numpy(wt).cuda()
+        M = -(-n_out // pl.q)
+        need = (M - 1) * pl.p + wt.shape[2]
+        xp = torch.nn.functional.pad(wav, (pl.W, max(need - pl.W - n_in, 0)))[:, None]
+
+        def stand_in():
+            return torch.nn.functional.conv1d(xp, wt, stride=pl.p).transpose(1, 2).reshape(B, -1)[:, :n_out]
+        diff = float((stand_in() - out).abs().max())
+        kern, copy, conv = [], [], []
+        for _ in range(3):                                                        # alternated
+            kern.append(timed(lambda: K.resample(*args, out=out, out_len=out_len)))
+            copy.append(timed(lambda: dst.copy_(src)))
+            conv.append(timed(stand_in))
+        flop = 2.0 * B * n_out * pl.ntaps
+        k, c, t = float(np.median(kern)), float(np.median(copy)), float(np.median(conv))
+        row = dict(source_rate=fs, p=pl.p, q=pl.q, ntaps=pl.ntaps, samples_in=n_in, samples_out=n_out, table_KB=table.taps.size * 4 / 1024,
+                   kernel_us=kern, kernel_us_median=k, flop=flop, kernel_TFLOPs=flop / k / 1e6, share_of_vector_peak=flop / k / 1e6 / (PEAK / 1e12),
+                   bytes_read_plus_written=8 * half, d2d_copy_same_bytes_us=copy, d2d_copy_us_median=c, torch_conv1d_us=conv, torch_conv1d_us_median=t,
+                   torch_conv1d_taps_per_channel=int(wt.shape[2]), max_abs_diff_vs_torch_conv1d=diff)
+        res["rates"].append(row)
+        print(json.dumps({a: row[a] for a in ("source_rate", "kernel_us_median", "d2d_copy_us_median", "torch_conv1d_us_median", "kernel_TFLOPs",
+                                              "max_abs_diff_vs_torch_conv1d")}), flush=True)
+        del wav, out, src, dst, xp, wt
+    res["timing"] = ("every utterance at the one source rate; HIP events around 20 back-to-back calls after 3 warm-up calls, 3 rounds alternating the "
+                     "contenders in one process; FLOP = 2 B n_out ntaps; peak = 157.3 TFLOP/s fp32 vector")
+    # StreamResampler.push: host time of one 480 ms block at 48 kHz
+    res["stream_push"] = {}
+    for Bs in (1, 32):
+        sr = R.StreamResampler(Bs, 48000, "cuda")
+        blk = torch.randn(Bs, 23040, device="cuda") * 0.1
+        host, wall = [], []
+        for i in range(40):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            sr.push(blk, [23040] * Bs, [False] * Bs)
+            t1 = time.perf_counter(); torch.cuda.synchronize(); t2 = time.perf_counter()
+            host.append((t1 - t0) * 1e3); wall.append((t2 - t0) * 1e3)
+        res["stream_push"][f"B={Bs}"] = dict(block_samples=23040, block_ms=480, host_ms_median=float(np.median(host[5:])), with_sync_ms_median=float(np.median(wall[5:])))
+    print(json.dumps(res["stream_push"]), flush=True)
+    # the waveform-fed joint step: the 16 kHz corpus with resample off (the code path of before) and on (nothing launched), and a corpus of
+    # as many 5-s utterances stored at 48 kHz
+    nb = 10
+    sub = items[:B * nb]
+    r48 = np.random.RandomState(1)
+    items48 = [((r48.randn(5 * 48000) * 0.1).astype(np.float32), t, 48000) for _, t in sub]
+    mk = lambda it, **kw: BucketedWaveLoader(WaveDataset(it, vocab, resample=bool(kw.get("resample"))), B, parser=parser, augment=True, shuffle=True, seed=1,
+                                             dtype=torch.bfloat16, **kw)
+    loaders = {"16k_off": mk(sub), "16k_on": mk(sub, resample=True), "48k_on": mk(items48, resample=True)}
+    assert loaders["16k_on"].rate_table is None and loaders["48k_on"].rate_table is not None
+
+    def run(ld):
+        n = 0
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for pack in ld:
+            model.iterate(pack, optimizer=opt)
+            n += 1
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3
+    for ld in loaders.values(): run(ld)                                           # warm-up epoch each
+    step = {name: [] for name in loaders}
+    for _ in range(4):
+        for name, ld in loaders.items():
+            step[name].append(run(ld))
+            print(f"joint step from waveforms, {name}: {step[name][-1]:.3f} ms/step", flush=True)
+    res["joint_step_ms"] = step
+    res["joint_step_ms_median"] = {name: float(np.median(v)) for name, v in step.items()}
+    res["joint_config"] = (f"{nb} batches of {B} x 5 s per epoch in host memory, SpecAugment on, bf16 joint model at the default width; 16k_off = resample=False "
+                           "(the loader of before), 16k_on = resample=True on the same 16 kHz corpus (no launch), 48k_on = as many 5-s utterances stored at "
+                           "48 kHz; 1 warm-up epoch each, then 4 epochs each, alternating; host clock around an epoch that ends in a device synchronise")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out_path)
+
+
 if SPEED is not None:
     speed_bench()
+    sys.exit(0)
+if RESAMPLE:
+    resample_bench()
     sys.exit(0)
 if REVERB_FFT:
     reverb_fft_bench()

@@ -25,6 +25,8 @@ Differences that come with the MI355X path:
     auto: at most 65536, 4.1 s at 16 kHz);
   * `--cmvn=stats.npz` normalises the features of every part per mel bin with corpus statistics (tools/compute_cmvn.py) instead of
     per utterance: the causal features a streaming model is trained on (transcribe.py --stream=1 --cmvn=...);
+  * `--resample=1` accepts files at 8, 11.025, 12, 22.05, 24, 32, 44.1, 48, 88.2 and 96 kHz (corpus, noise clips, responses) and converts
+    them to 16 kHz on the GPU (data_handler/resample.py); without it a file at another rate raises, as before;
   * `--synthetic=N` trains on N synthetic AISHELL-1-shaped utterances (no dataset ships with this repository);
   * `--trainer=BaseTrainer` selects the twin of Trainer/base_trainer.py instead of Trainer11.
 """
@@ -77,6 +79,7 @@ class TrainConfig(DataConfigAiShell1):      # main.py:14-36
     rir_method = "direct"                   # --rir_method=direct|fft|auto: the direct FIR kernel, the FFT overlap-save kernels, or chosen per bank
     rir_max_taps = 8192                     # --rir_max_taps=N: taps kept of a response (direct: at most 8192; fft / auto: at most 65536)
     snr_db = (5, 20)                        # --snr_db=5,20: the signal-to-noise ratio of a noisy utterance is uniform in this range (dB)
+    resample = 0                            # --resample=1: files (corpus, noise, responses) at another rate than 16 kHz are converted on the GPU; 0 = they raise
     speed_perturb = ()                      # --speed_perturb=0.9,1.0,1.1: speed factors of the train part (never dev / test); empty = off
 
 
@@ -182,7 +185,7 @@ def train(**kwargs):                        # main.py:55-98
         vocab = Vocab.load(config.vocab_path)
         common = dict(collector_path=config.collector_path, vocab=vocab, sample_rate=config.sample_rate, window_size=config.window_size,
                       n_mels=config.n_mels, predump=config.predump, use_old=config.use_old, lfr_m=config.lfr_m, lfr_n=config.lfr_n,
-                      rank=rank, world=world, cmvn=config.cmvn or None)
+                      rank=rank, world=world, cmvn=config.cmvn or None, resample=bool(int(config.resample)))
         train_iter = build_dataloader(batch_size=config.batch_size, part="train", augment=config.augment, speed_perturb=speed_factors(config.speed_perturb),
                                       noise=path_list(config.noise_list), rir=path_list(config.rir_list), noise_prob=float(config.noise_prob),
                                       rir_prob=float(config.rir_prob), snr_db=snr_range(config.snr_db), rir_method=str(config.rir_method),

@@ -24,6 +24,9 @@ trained with rebuild it.  Inference flags:
                  the encoder streams: that emulates streaming over files.
   --cmvn         global CMVN statistics (tools/compute_cmvn.py) the model was trained with (train.py --cmvn); empty = the
                  per-utterance normalisation
+  --resample     1 = files at 8, 11.025, 12, 22.05, 24, 32, 44.1, 48, 88.2 or 96 kHz are converted to 16 kHz on the GPU (one launch per
+                 batch; with --stream=1 --cmvn a batch whose files share one rate is converted as it streams) and their JSON line
+                 gains "source_rate"; 0 (default) = a file at another rate ends the run
 Audio goes through load_wav -> AudioParser.parse_batch on the device -> model.transcribe; one JSON line per file is printed:
 {"file", "duration_s", "text", "ids", "score", "tokens": [{"id", "token", "start_frame", "end_frame", "start_s", "end_s", "logp"}]}.
 """
@@ -42,9 +45,10 @@ if ROOT not in sys.path:
 from asr_chinese_e2e_amd.data_handler import AudioParser, Vocab, load_wav  # noqa: E402
 from asr_chinese_e2e_amd.data_handler.loader import parser_norm  # noqa: E402
 from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
+from asr_chinese_e2e_amd.data_handler import resample as resample_mod  # noqa: E402
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples")
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample")
 
 
 def _finite(x):
@@ -97,11 +101,11 @@ def stream_batch(model, files, feats, flen, id2tok, **search):
     return st.finish(**search)
 
 
-def stream_audio_batch(model, parser, files, wav, wav_len, id2tok, block, **search):
+def stream_audio_batch(model, parser, files, wav, wav_len, id2tok, block, source_rate=None, **search):
     """model.stream fed with the samples themselves, `block` at a time (wav (B, S) f32 on the host, wav_len list): the same lines as
-    stream_batch prints, the same result."""
+    stream_batch prints, the same result.  source_rate: the rate of wav when it is not 16 kHz (converted as it streams)."""
     B, S = wav.shape
-    st = model.stream(B, parser=parser)
+    st = model.stream(B, parser=parser, source_rate=source_rate)
     text, chunk = [""] * B, 0
     for s0 in range(0, max(S, 1), block):
         n = [max(0, min(block, l - s0)) for l in wav_len]
@@ -143,40 +147,56 @@ def transcribe(**flags):
     if joint not in ("rescore", "one_pass"):
         raise SystemExit(f"transcribe.py: --joint must be rescore or one_pass (got {joint!r})")
     stream = bool(int(cli.get("stream", 0)))
+    resample = bool(int(cli.get("resample", 0)))      # --resample=1: files at another rate are converted on the GPU instead of ending the run
     if stream and model.decoding_chunk_size <= 0:
         raise SystemExit("transcribe.py: --stream=1 needs a decoding chunk (--decoding_chunk_size, or a static --chunk_size)")
     id2tok = vocab._id2token
     for i in range(0, len(files), bs):
         chunk = files[i:i + bs]
-        waves = []
+        waves, rates = [], []
         for path in chunk:
             pcm, sr = load_wav(path)
             if sr != config.sample_rate:
-                raise SystemExit(f"transcribe.py: {path}: sample rate {sr}, the model expects {config.sample_rate}")
+                if not resample:
+                    raise SystemExit(f"transcribe.py: {path}: sample rate {sr}, the model expects {config.sample_rate}")
+                try:
+                    resample_mod.plan(sr)
+                except ValueError as e:
+                    raise SystemExit(f"transcribe.py: {path}: {e}") from e
             waves.append(pcm)
+            rates.append(sr)
         S = max(1, max(len(w) for w in waves))
         wav = np.zeros((len(waves), S), dtype=np.float32)
         for b, w in enumerate(waves):
             wav[b, : len(w)] = w
         wav_len = torch.tensor([len(w) for w in waves], dtype=torch.int32)
+        wav = torch.from_numpy(wav)
+        stream_rate = None      # the batch streams at its source rate when every file shares it; otherwise it is converted first
+        if any(r != config.sample_rate for r in rates):
+            if stream and parser.norm == "global" and len(set(rates)) == 1:
+                stream_rate = rates[0]
+            else:      # one launch for the batch, whatever rates it mixes
+                wav, wav_len, _ = resample_mod.resample_batch(wav.cuda(), wav_len.tolist(), rates)
         search = dict(beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps, joint=joint)
         if stream and parser.norm == "global":      # the samples stream: blocks of one chunk's worth of audio unless told otherwise
-            block = int(cli.get("stream_block_samples", 0)) or model.decoding_chunk_size * config.lfr_n * 160
-            out = stream_audio_batch(model, parser, chunk, torch.from_numpy(wav), wav_len.tolist(), id2tok, block, **search)
+            block = int(cli.get("stream_block_samples", 0)) or model.decoding_chunk_size * config.lfr_n * 160 * (stream_rate or 16000) // 16000
+            out = stream_audio_batch(model, parser, chunk, wav, wav_len.tolist(), id2tok, block, source_rate=stream_rate, **search)
         else:
-            feats, flen = parser.parse_batch(torch.from_numpy(wav).cuda(), wav_len.cuda())
+            feats, flen = parser.parse_batch(wav.cuda(), wav_len.cuda())
             if stream:
                 out = stream_batch(model, chunk, feats, flen, id2tok, **search)
             else:
                 out = model.transcribe(Pack(wave=feats, wave_len=flen), **search)
-        for path, w, r in zip(chunk, waves, out):
-            dur = len(w) / float(config.sample_rate)
+        for path, w, sr, r in zip(chunk, waves, rates, out):
+            dur = len(w) / float(sr)
             for t in r["tokens"] or ():          # the last encoder frame may reach past the end of the audio
                 for k in ("start_s", "end_s"):
                     if t[k] is not None:
                         t[k] = min(t[k], dur)
             line = {"file": path, "duration_s": dur, "text": r["text"], "ids": r["ids"],
                     "score": _finite(r["score"]), "tokens": r["tokens"]}
+            if sr != config.sample_rate:
+                line["source_rate"] = sr
             print(json.dumps(line, ensure_ascii=False), flush=True)
 
 
