@@ -6,6 +6,7 @@
 // definition - acc = 0, then acc = fmaf(x, h, acc) over j ascending, one accumulator - so that a stream cut anywhere (the window form:
 // a row that holds only part of the utterance, an output range that starts anywhere) gives the bits of the offline call.
 #include "asr_common.h"
+#include "polyphase_tile.h"
 
 namespace {
 
@@ -16,29 +17,9 @@ namespace {
 // output of the workgroup shares it and the taps are scalar operands.  Each multiply-add still takes one 4-byte LDS read: the LDS
 // (32 lanes per clock against the VALU's 64) bounds the kernel at half the vector rate.
 constexpr int TILE = ASR_RESAMPLE_TILE;
-constexpr int NT = 256, NR = 4;
+constexpr int NT = ptile::NT, NR = 4;
 constexpr int Q_MAX = ASR_RESAMPLE_Q_MAX, NTAPS_MAX = ASR_RESAMPLE_NTAPS_MAX, R_MAX = ASR_RESAMPLE_PLANS_MAX;
 constexpr int XS = 8832;                  // staged samples: (TILE - 1) p/q + 1 + 2 W + 1 + alignment pads at the largest p/q (7.56) 1023 taps admit
-
-// Row-relative samples [lo, lo + count) -> xs[pad + i]; only [vlo, vhi) of the row is real, everything else is 0.  pad = (row0 + lo) mod 4
-// places every 16-byte-aligned quad of global memory on a 16-byte-aligned quad of LDS (speed.hip's stage()).
-__device__ __forceinline__ int stage(float* xs, const float* __restrict__ wav, long long row0, int lo, int count, int vlo, int vhi, bool vec, int tid) {
-    const int pad = (int)(((row0 + lo) % 4 + 4) % 4);
-    const int lo_al = lo - pad;
-    const int nquads = (pad + count + 3) >> 2;
-    for (int qd = tid; qd < nquads; qd += NT) {
-        const int k = lo_al + 4 * qd;
-        f32x4 v;
-        if (vec && k >= vlo && k + 4 <= vhi) {
-            v = *(const f32x4*)(wav + row0 + k);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (k + e >= vlo && k + e < vhi) ? wav[row0 + k + e] : 0.f;
-        }
-        *(f32x4*)(xs + 4 * qd) = v;
-    }
-    return pad;
-}
 
 // MODE 0: q == 1, one phase for the workgroup (uniform tap address: scalar loads); 1: the lane's NR outputs share the phase m[0];
 // 2: q > NT, a phase per output.  THE summation order: j ascending, one accumulator per output.
@@ -87,9 +68,8 @@ __global__ __launch_bounds__(NT) void resample_kernel(const float* __restrict__ 
     const bool copy = p == q;
     const int W = (ntaps - 1) >> 1;
     const long long row_in = (long long)b * Smax, row_out = (long long)b * Smax_out;
-    const int opad = (int)((row_out + n0) & 3);         // ys[opad + t] = output n0 + t: global quads sit on LDS quads
     const int tlive = min(tcount, n_emit - n0);         // outputs of this tile below n_emit (<= 0: the tile is padding only)
-    for (int t = tlive > 0 ? tlive + tid : tid; t < tcount; t += NT) ys[opad + t] = 0.f;
+    const int opad = ptile::begin_tile(ys, row_out + n0, tlive, tcount, tid);      // ys[opad + t] = output n0 + t
     if (tlive > 0) {
         // exact index arithmetic: 64 bits once per workgroup ((out_start + n0) p passes 2^31 in a long stream), 32 bits per output
         const long long nf = (long long)out_start + n0, np0 = nf * p;
@@ -101,7 +81,7 @@ __global__ __launch_bounds__(NT) void resample_kernel(const float* __restrict__ 
         const long long lo64 = base0 - W - in_base;     // row-relative index of the first sample the tile reads
         const int lo = (int)min(max(lo64, -(1LL << 30)), 1LL << 30);      // far outside the row either way: zeros
         const int count = (r0 + (tlive - 1) * p) / q + ntaps;
-        const int ipad = stage(xs, wav, row_in, lo, count, vlo, vhi, vec_in != 0, tid);
+        const int ipad = ptile::stage(xs, wav, row_in, lo, count, vlo, vhi, vec_in != 0, tid);
         __syncthreads();
         const int stride = q <= NT ? q * (NT / q) : NT;
         for (int tb = 0; tb < tlive; tb += NR * stride) {
@@ -133,19 +113,7 @@ __global__ __launch_bounds__(NT) void resample_kernel(const float* __restrict__ 
             }
         }
     }
-    __syncthreads();
-    // ---- store: quad i of ys = outputs n0 - opad + 4 i ... + 3
-    float* orow = out + row_out + n0 - opad;
-    for (int i = tid; 4 * i < opad + tcount; i += NT) {
-        const int t = 4 * i - opad;
-        if (vec_out && t >= 0 && t + 4 <= tcount) {
-            *(f32x4*)(orow + 4 * i) = *(const f32x4*)(ys + 4 * i);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (t + e >= 0 && t + e < tcount) orow[4 * i + e] = ys[4 * i + e];
-        }
-    }
+    ptile::store_tile(out + row_out + n0, ys, opad, tcount, vec_out != 0, tid);
 }
 
 }  // namespace

@@ -5,6 +5,7 @@
 // reference has no waveform-side augmentation: parity unpinned by the reference; the definition and its float64 restatement are in
 // tests/speed_ref.py.  Factor 1 (p == q) is a copy, bit for bit, inside the same launch.
 #include "asr_common.h"
+#include "polyphase_tile.h"
 
 namespace {
 
@@ -15,30 +16,9 @@ namespace {
 // per output and does 2 W + 1 multiply-adds from LDS for it: at the 15 taps of 9/10 and 11/10 it takes 10.6 us for 32 x 5 s, three times a
 // device-to-device copy of the same bytes (profiles/speed_perturb_bench.json) - the LDS reads, not memory, set its time.
 constexpr int TILE = ASR_SPEED_TILE;      // output samples per workgroup
-constexpr int NT = 256;                   // threads
+constexpr int NT = ptile::NT;             // threads
 constexpr int SPAN = 2048;                // staged input samples per pass: a whole tile up to p/q ~ 1.9, several passes beyond
 constexpr int PQ_MAX = 20, NTAPS_MAX = 255, F_MAX = 64;
-
-// Samples [lo, lo + count) of the row at `row` (row-relative indices; valid ones are [0, len)) -> xs[pad + i], zeros outside the valid range.
-// pad = (row0 + lo) mod 4 places every 16-byte-aligned quad of global memory on a 16-byte-aligned quad of LDS; a quad that lies inside
-// the valid range is one 16-byte load, the others (row ends, halo) go element by element.  row0 = element index of the row's start.
-__device__ __forceinline__ int stage(float* xs, const float* __restrict__ wav, long long row0, int lo, int count, int len, bool vec, int tid) {
-    const int pad = (int)(((row0 + lo) % 4 + 4) % 4);
-    const int lo_al = lo - pad;                         // row-relative index of xs[0]
-    const int nquads = (pad + count + 3) >> 2;
-    for (int qd = tid; qd < nquads; qd += NT) {
-        const int k = lo_al + 4 * qd;
-        f32x4 v;
-        if (vec && k >= 0 && k + 4 <= len) {
-            v = *(const f32x4*)(wav + row0 + k);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (k + e >= 0 && k + e < len) ? wav[row0 + k + e] : 0.f;
-        }
-        *(f32x4*)(xs + 4 * qd) = v;
-    }
-    return pad;
-}
 
 constexpr int NTAPS_FAST = 15;            // 2 W + 1 of every factor in [1/2, 1): the taps of a lane's phase live in registers
 
@@ -60,9 +40,8 @@ __global__ __launch_bounds__(NT) void speed_perturb_kernel(const float* __restri
     const int n_out = (int)min(((long long)len * q + p - 1) / p, (long long)Smax_out);
     if (blockIdx.x == 0 && tid == 0) out_len[b] = n_out;
     const long long row_in = (long long)b * Smax, row_out = (long long)b * Smax_out;
-    const int opad = (int)((row_out + n0) & 3);         // ys[opad + t] = output n0 + t: global quads sit on LDS quads
     const int tlive = min(tcount, n_out - n0);          // outputs of this tile below n_out (<= 0: the tile is padding only)
-    for (int t = tlive > 0 ? tlive + tid : tid; t < tcount; t += NT) ys[opad + t] = 0.f;
+    const int opad = ptile::begin_tile(ys, row_out + n0, tlive, tcount, tid);      // ys[opad + t] = output n0 + t
     if (tlive > 0) {
         const int W = copy ? 0 : (ntaps - 1) >> 1;
         if (!copy) {
@@ -78,7 +57,7 @@ __global__ __launch_bounds__(NT) void speed_perturb_kernel(const float* __restri
             const int lo = base0 + (r0 + t0 * p) / q - W;
             const int count = base0 + (r0 + (t1 - 1) * p) / q + W - lo + 1;
             if (t0 > 0) __syncthreads();                // the previous pass is done with xs
-            const int ipad = stage(xs, wav, row_in, lo, count, len, vec_in != 0, tid);
+            const int ipad = ptile::stage(xs, wav, row_in, lo, count, 0, len, vec_in != 0, tid);      // valid samples: [0, len)
             __syncthreads();
             // lane l takes outputs t0 + l, t0 + l + stride, ... with stride = q floor(NT / q): all of them at ONE phase r (its taps are
             // fetched once) and dstep input samples apart, so the one division per lane and pass is all the index arithmetic there is
@@ -110,19 +89,7 @@ __global__ __launch_bounds__(NT) void speed_perturb_kernel(const float* __restri
             }
         }
     }
-    __syncthreads();
-    // ---- store: quad i of ys = outputs n0 - opad + 4 i ... + 3
-    float* orow = out + row_out + n0 - opad;
-    for (int i = tid; 4 * i < opad + tcount; i += NT) {
-        const int t = 4 * i - opad;
-        if (vec_out && t >= 0 && t + 4 <= tcount) {
-            *(f32x4*)(orow + 4 * i) = *(const f32x4*)(ys + 4 * i);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (t + e >= 0 && t + e < tcount) orow[4 * i + e] = ys[4 * i + e];
-        }
-    }
+    ptile::store_tile(out + row_out + n0, ys, opad, tcount, vec_out != 0, tid);
 }
 
 }  // namespace

@@ -12,6 +12,7 @@ from length buckets so that padding stays small.
 The yielded Pack has the reference's batch contract (collat, ai_shell_1.py:75-88): wave (B, T, F),
 wave_len, tgt_for_input, tgt_for_metric (0-padded, int64), tgt_len.
 """
+import collections
 import contextlib
 import random
 import threading
@@ -29,17 +30,32 @@ from . import noise as noise_mod
 from . import resample as resample_mod
 
 
-def load_wav(path):
-    """16-bit PCM WAV -> (float32 mono waveform in [-1, 1), sample_rate); channels are averaged
-    (loader.py:5-17 of the reference did the same through torchaudio with normalization=True)."""
+def read_pcm(path):
+    """16-bit PCM WAV -> (interleaved int16 samples AS THE FILE HOLDS THEM, channels, sample_rate): the one reader of load_wav and
+    WaveDataset.wave_into.  A data chunk shorter than its header says is a truncated recording, not an error: fewer samples come back."""
     with wave_module.open(path, "rb") as f:
         if f.getsampwidth() != 2:
             raise ValueError(f"{path}: only 16-bit PCM is supported (sample width {f.getsampwidth()})")
-        sr, ch, n = f.getframerate(), f.getnchannels(), f.getnframes()
-        pcm = np.frombuffer(f.readframes(n), dtype="<i2").astype(np.float32) / 32768.0
+        sr, ch = f.getframerate(), f.getnchannels()
+        return np.frombuffer(f.readframes(f.getnframes()), dtype="<i2"), ch, sr
+
+
+def pcm_to_float(pcm, ch, out):
+    """The first out.size frames of interleaved int16 `pcm` -> out (float32, in [-1, 1)): scale in float32, then average the channels.
+    Mono goes int16 -> float32 in one pass (no intermediate array); numpy releases the GIL for it."""
     if ch > 1:
-        pcm = pcm.reshape(-1, ch).mean(axis=1)
-    return pcm, sr
+        out[:] = (pcm[:out.size * ch].astype(np.float32) / np.float32(32768.0)).reshape(-1, ch).mean(axis=1)
+    else:
+        np.multiply(pcm[:out.size], np.float32(1.0 / 32768.0), out=out, casting="unsafe")
+
+
+def load_wav(path):
+    """16-bit PCM WAV -> (float32 mono waveform in [-1, 1), sample_rate); channels are averaged
+    (loader.py:5-17 of the reference did the same through torchaudio with normalization=True)."""
+    pcm, ch, sr = read_pcm(path)
+    out = np.empty(pcm.size // ch, dtype=np.float32)
+    pcm_to_float(pcm, ch, out)
+    return out, sr
 
 
 class WaveDataset:
@@ -86,22 +102,13 @@ class WaveDataset:
 
     def wave_into(self, i, row):
         """Utterance i decoded straight into `row` (a float32 numpy view of the loader's pinned staging buffer), the rest of the row zeroed;
-        returns the sample count.  16-bit PCM goes int16 -> float32 in one pass (no intermediate array); numpy releases the GIL for it."""
+        returns the sample count (read_pcm, pcm_to_float)."""
         w = self.items[i][0]
         if isinstance(w, str):
-            with wave_module.open(w, "rb") as f:
-                if f.getsampwidth() != 2:
-                    raise ValueError(f"{w}: only 16-bit PCM is supported (sample width {f.getsampwidth()})")
-                sr, ch, n = f.getframerate(), f.getnchannels(), f.getnframes()
-                self._check_rate(w, sr)
-                pcm = np.frombuffer(f.readframes(n), dtype="<i2")
-            # the sample count is what the file actually holds (a data chunk shorter than its header says is a truncated recording, not an
-            # error), never more than the row the loader sized from the header
-            n = min(pcm.size // ch, row.size)
-            if ch > 1:      # same arithmetic as load_wav: scale in float32, then average the channels
-                row[:n] = (pcm[:n * ch].astype(np.float32) / np.float32(32768.0)).reshape(-1, ch).mean(axis=1)
-            else:
-                np.multiply(pcm[:n], np.float32(1.0 / 32768.0), out=row[:n], casting="unsafe")
+            pcm, ch, sr = read_pcm(w)
+            self._check_rate(w, sr)
+            n = min(pcm.size // ch, row.size)      # what the file really holds, never more than the row the loader sized from the header
+            pcm_to_float(pcm, ch, row[:n])
         else:
             a = np.asarray(w, dtype=np.float32).reshape(-1)
             n = a.size
@@ -193,6 +200,78 @@ def source_rates(dataset, lengths):
     return rates, [resample_mod.plan(r).n_out(n) for n, r in zip(lengths, rates)]
 
 
+class MetaLayout:
+    """THE layout of the one int32 buffer that carries every integer of a batch to the device, stated once: a field's offset exists
+    here and nowhere else, and field() slices the numpy view of the pinned buffer and its device copy alike.  A feature that is off
+    contributes no words (all off: 2 B + B lmax words, the copy the first loader made)."""
+
+    def __init__(self, B, lmax, factor=False, rate=False, aug=False):
+        fields = [("n_samples", (B,)), ("tgt_len", (B,)), ("tgt", (B, lmax))]
+        if factor:
+            fields += [("factor", (B,))]                               # speed-factor index per utterance
+        if rate:
+            fields += [("rate_idx", (B,)), ("win", (B, 5))]            # {in_base, n_avail, n_total, out_start, n_emit}
+        if aug:
+            fields += [("rir_idx", (B,)), ("noise_par", (B, 4))]       # {clip, offset, scale as float bits, 0}
+        self.B, self.lmax, self.at, self.size = B, lmax, {}, 0
+        for name, shape in fields:
+            words = B * (shape[1] if len(shape) > 1 else 1)
+            self.at[name] = (self.size, self.size + words, shape)
+            self.size += words
+
+    def __contains__(self, name):
+        return name in self.at
+
+    def field(self, buf, name):
+        """Field `name` of `buf` (1-D, numpy or torch, at least `size` words) as a view of its shape."""
+        lo, hi, shape = self.at[name]
+        return buf[lo:hi].reshape(shape)
+
+
+# BucketedWaveLoader.speed: the (p, q) list on the host, pq (F, 2) int32 and taps (F, qmax, ntaps) f32 on the device (speed.build_tables)
+SpeedTables = collections.namedtuple("SpeedTables", "pq_host pq taps")
+
+# what pack_meta decides: the lengths at 16 kHz and after the speed perturbation (each the one before it where its stage does not run), the
+# row widths of the two length-changing stages (0: the batch does not launch that stage) and whether any utterance drew a response / a clip
+BatchMeta = collections.namedtuple("BatchMeta", "len16 len_out smax16 smax_out any_rir any_noise")
+
+
+def pack_meta(lay, meta, sizes, tgt, fs=None, pq=None, rates=None, rate_table=None, aug=None):
+    """The host half of a batch, no GPU: fills `meta` (numpy int32, lay.size words) field by field and decides what the batch launches.
+    sizes: sample counts, tgt: label lists; fs, pq: the batch's speed-factor indices and the (p, q) list; rates, rate_table: the batch's
+    source rates and a resample.RateTable (one built with device=None does); aug: noise.draw_augment's four lists, the batch's rows.
+    Each group is read only when `lay` has its fields.  -> BatchMeta."""
+    assert meta.shape == (lay.size,) and meta.dtype == np.int32 and len(sizes) == len(tgt) == lay.B
+    lay.field(meta, "n_samples")[:] = sizes
+    lay.field(meta, "tgt_len")[:] = [len(t) for t in tgt]
+    tg = lay.field(meta, "tgt")
+    for r, t in enumerate(tgt):
+        tg[r, :len(t)] = t
+        tg[r, len(t):] = 0
+    len16, smax16 = sizes, 0          # smax16 > 0: at least one utterance of the batch is at another rate than 16 kHz
+    if "rate_idx" in lay:
+        win, ridx = rate_table.windows(sizes, rates)
+        lay.field(meta, "rate_idx")[:], lay.field(meta, "win")[:] = ridx, win
+        if any(r >= 0 for r in ridx):
+            len16 = [int(v) for v in win[:, 4]]      # from here on the lengths are those at 16 kHz
+            smax16 = max(1, max(len16))
+    len_out, smax_out = len16, 0      # smax_out > 0: at least one utterance of the batch is speed-perturbed
+    if "factor" in lay:
+        lay.field(meta, "factor")[:] = fs
+        if any(pq[f][0] != pq[f][1] for f in fs):
+            len_out = [speed_mod.perturbed_len(n, *pq[f]) for n, f in zip(len16, fs)]
+            smax_out = max(1, max(len_out))
+    any_rir = any_noise = False
+    if "rir_idx" in lay:
+        nidx, noff, snr, ridx = aug
+        lay.field(meta, "rir_idx")[:] = ridx
+        par = lay.field(meta, "noise_par")
+        for r in range(lay.B):
+            par[r] = (nidx[r], noff[r], noise_mod.snr_scale_bits(snr[r]), 0)
+        any_rir, any_noise = any(v >= 0 for v in ridx), any(v >= 0 for v in nidx)
+    return BatchMeta(len16, len_out, smax16, smax_out, any_rir, any_noise)
+
+
 _LOADERS = weakref.WeakSet()      # loaders of this process (paused() holds every one's gate)
 
 
@@ -249,16 +328,16 @@ class BucketedWaveLoader:
         # per-utterance source rates (None: all 16 kHz, or resample off) and the lengths at 16 kHz the buckets are formed on
         self.rates, lengths16 = source_rates(dataset, self.lengths) if resample else (None, self.lengths)
         self.rate_table = resample_mod.RateTable(self.rates, self.device) if self.rates is not None else None      # resident on the device
-        self.speed = None      # (pq list, pq (F, 2) int32, taps (F, qmax, ntaps) f32): built once, resident on the device
+        self.speed = None      # built once, resident on the device
         if speed_perturb is not None and len(speed_perturb) > 0:
             pq, taps = speed_mod.build_tables(speed_perturb)
-            self.speed = ([tuple(int(v) for v in r) for r in pq], torch.from_numpy(pq).to(self.device), torch.from_numpy(taps).to(self.device))
+            self.speed = SpeedTables([tuple(int(v) for v in r) for r in pq], torch.from_numpy(pq).to(self.device), torch.from_numpy(taps).to(self.device))
         bank = lambda v, cls, **kw: None if v is None else v if isinstance(v, cls) else cls(v, self.device, **kw) if len(v) > 0 else None
         if rir_method not in noise_mod.METHODS + ("auto",):
             raise ValueError(f"rir_method={rir_method!r}: one of 'direct', 'fft', 'auto'")
         self.noise, self.rir = bank(noise, noise_mod.NoiseBank, resample=resample), bank(rir, noise_mod.RirBank, max_taps=rir_max_taps, method=rir_method, resample=resample)
         self.noise_prob, self.rir_prob, self.snr_db = float(noise_prob), float(rir_prob), snr_db
-        self.plan = BatchPlan(lengths16, batch_size, bucket_size, shuffle, drop_last, seed, rank, world, self.speed[0] if self.speed else None)
+        self.plan = BatchPlan(lengths16, batch_size, bucket_size, shuffle, drop_last, seed, rank, world, self.speed.pq_host if self.speed else None)
         self.rank, self.world, self.shuffle, self.drop_last, self.bucket_size = self.plan.rank, self.plan.world, shuffle, self.plan.drop_last, bucket_size
         self.rng = self.plan.rng                # batch order AND SpecAugment masks (the reference uses the global `random`)
         self._gate = threading.Lock()      # held by the helper thread around _prepare; paused() takes it
@@ -274,12 +353,11 @@ class BucketedWaveLoader:
     def __len__(self):
         n = len(self.ds)
         if self.world > 1:      # full batches only (per bucket), the same count on every rank
-            return len(self._batches(random.Random(0)))
+            return len(self.plan.batches(random.Random(0))[0])
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
-    def _batches(self, rng):
-        batches = bucket_batches(self.plan.lengths, self.batch_size, self.bucket_size, self.shuffle, self.drop_last, rng)
-        return shard_batches(batches, self.rank, self.world)
+    def _batches(self, rng):      # this rank's batch list for `rng` (tests/test_train_loop_gpu.py reads the order through it)
+        return self.plan.batches(rng)[0]
 
     # ---- staging: pinned host buffers that are REUSED (a fresh pageable tensor + pin_memory() + 32 tensor-slice assignments + six small
     # pageable host-to-device copies cost 25 ms of host time per batch of 32 x 5 s - the training step takes 3 ms), filled through
@@ -309,20 +387,16 @@ class BucketedWaveLoader:
 
     def _prepare(self, idx, k=0, fidx=None, aug=None):
         """fidx: speed-factor index per utterance of the data set (BatchPlan.next_epoch), None = no perturbation.
-        aug: noise.draw_augment's four lists for the data set, None = neither noise nor reverberation."""
+        aug: noise.draw_augment's four lists for the data set, None = neither noise nor reverberation.
+        The integers of the batch travel in one buffer whose layout is MetaLayout; pack_meta fills it and decides what is launched."""
         tgt = [self.ds.ids(i) for i in idx]
         B = len(idx)
-        nf = B if fidx is not None else 0      # the factor indices ride behind the labels in the one integer buffer
-        nr = 6 * B if self.rates is not None else 0      # behind them the rate indices (B) and the resampler's windows (B, 5)
-        na = 5 * B if aug is not None else 0   # and behind them the response indices (B) and the noise parameters (B, 4)
+        lay = MetaLayout(B, max(1, max(len(t) for t in tgt)), factor=fidx is not None, rate=self.rates is not None, aug=aug is not None)
         into = getattr(self.ds, "wave_into", None)
         waves = None if into is not None else [self.ds.wave(i) for i in idx]
         smax = max(self.lengths[i] for i in idx) if waves is None else max(w.size for w in waves)
-        lmax = max(1, max(len(t) for t in tgt))
-        slot = self._slot(k % self.SLOTS, B * smax, 2 * B + B * lmax + nf + nr + na)
+        slot = self._slot(k % self.SLOTS, B * smax, lay.size)
         buf = slot["wave_np"][:B * smax].reshape(B, smax)
-        meta = slot["meta_np"][:2 * B + B * lmax + nf + nr + na]
-        tg = meta[2 * B:2 * B + B * lmax].reshape(B, lmax)
         items = getattr(self.ds, "items", None)
         if waves is None and items is not None and any(isinstance(items[i][0], str) for i in idx):
             # files: read / decode the rows in parallel (file reads and numpy loops run without the GIL); 3.4 - 3.8 ms/step against 4 - 6 serially
@@ -339,69 +413,46 @@ class BucketedWaveLoader:
                 buf[r, :w.size] = w
                 buf[r, w.size:] = 0.0
                 sizes.append(w.size)
-        for r, t in enumerate(tgt):
-            meta[r], meta[B + r] = sizes[r], len(t)
-            tg[r, :len(t)] = t
-            tg[r, len(t):] = 0
-        q0 = 2 * B + B * lmax + nf      # [q0, q0 + B): rate index, [q0 + B, q0 + 6 B): {in_base, n_avail, n_total, out_start, n_emit}
-        smax16 = 0        # > 0: at least one utterance of the batch is at another rate than 16 kHz
-        if nr:
-            rates = [self.rates[i] for i in idx]
-            win, ridx = self.rate_table.windows(sizes, rates)
-            meta[q0:q0 + B], meta[q0 + B:q0 + 6 * B] = ridx, win.reshape(-1)
-            if any(r >= 0 for r in ridx):
-                sizes = [int(v) for v in win[:, 4]]      # from here on the lengths are those at 16 kHz
-                smax16 = max(1, max(sizes))
-        smax_out = 0      # > 0: at least one utterance of the batch is resampled
-        if fidx is not None:
-            pq = self.speed[0]
-            fs = [fidx[i] for i in idx]
-            meta[2 * B + B * lmax:2 * B + B * lmax + nf] = fs
-            if any(pq[f][0] != pq[f][1] for f in fs):
-                smax_out = max(1, max(speed_mod.perturbed_len(sizes[r], *pq[f]) for r, f in enumerate(fs)))
-        a0 = q0 + nr      # [a0, a0 + B): response index, [a0 + B, a0 + 5 B): {clip, offset, scale as float bits, 0}
-        any_rir = any_noise = False
-        if aug is not None:
-            nidx, noff, snr, ridx = aug
-            par = meta[a0 + B:].reshape(B, 4)
-            for r, i in enumerate(idx):
-                meta[a0 + r] = ridx[i]
-                par[r] = (nidx[i], noff[i], noise_mod.snr_scale_bits(snr[i]), 0)
-            any_rir, any_noise = any(ridx[i] >= 0 for i in idx), any(nidx[i] >= 0 for i in idx)
-        extra = ()
+        take = lambda per_utt: [per_utt[i] for i in idx]
+        m = pack_meta(lay, slot["meta_np"][:lay.size], sizes, tgt, fs=take(fidx) if fidx is not None else None,
+                      pq=self.speed.pq_host if self.speed else None, rates=take(self.rates) if self.rates is not None else None,
+                      rate_table=self.rate_table, aug=[take(a) for a in aug] if aug is not None else None)
+        from .. import kernels as K
         with torch.cuda.stream(self.stream):
             dev_wav = slot["wave"][:B * smax].view(B, smax).to(self.device, non_blocking=True)
-            dev_meta = slot["meta"][:meta.size].to(self.device, non_blocking=True)
+            dev_meta = slot["meta"][:lay.size].to(self.device, non_blocking=True)
             slot["copied"].record()
-            wav_in, len_in = dev_wav, dev_meta[:B]
-            if smax16:
-                from .. import kernels as K
-                wav_in, len_in = K.resample(dev_wav, dev_meta[q0:q0 + B], dev_meta[q0 + B:q0 + 6 * B].view(B, 5), *self.rate_table.dev, smax16)
-            if smax_out:
-                from .. import kernels as K
-                if smax16:
-                    extra += (wav_in, len_in)
-                wav_in, len_in = K.speed_perturb(wav_in, len_in, dev_meta[2 * B + B * lmax:2 * B + B * lmax + nf], self.speed[1], self.speed[2], smax_out)
-            if any_rir:      # a batch in which no utterance drew a response launches nothing
-                from .. import kernels as K
-                extra += (wav_in,)
+            field = lambda name: lay.field(dev_meta, name)
+            wav, wav_len = dev_wav, field("n_samples")
+            # the chain: each stage takes (wav, wav_len) and gives (wav, wav_len), launched or skipped by pack_meta's flags.  `keep` is what
+            # the slot holds until it is reused: the copies, then everything a stage makes (outputs and workspaces) - a stage's input is
+            # the output of the one before it - so nothing a kernel queued on this stream touches goes back to the pool early.
+            keep = [dev_wav, dev_meta]
+            if m.smax16:
+                wav, wav_len = K.resample(wav, field("rate_idx"), field("win"), *self.rate_table.dev, m.smax16)
+                keep += [wav, wav_len]
+            if m.smax_out:
+                wav, wav_len = K.speed_perturb(wav, wav_len, field("factor"), self.speed.pq, self.speed.taps, m.smax_out)
+                keep += [wav, wav_len]
+            if m.any_rir:      # a batch in which no utterance drew a response launches nothing
+                rir = (wav, wav_len, field("rir_idx"), self.rir.table, self.rir.lens, self.rir.peaks)
                 if self.rir.method == "fft":
-                    ws = K.reverb_fft_workspace(B, wav_in.shape[1], self.rir.table.shape[1], self.device)
-                    extra += (ws,)
-                    wav_in = K.reverb_fft(wav_in, len_in, dev_meta[a0:a0 + B], self.rir.table, self.rir.lens, self.rir.peaks, ws=ws)
+                    ws = K.reverb_fft_workspace(B, wav.shape[1], self.rir.table.shape[1], self.device)
+                    wav = K.reverb_fft(*rir, ws=ws)
+                    keep += [wav, ws]
                 else:
-                    wav_in = K.reverb(wav_in, len_in, dev_meta[a0:a0 + B], self.rir.table, self.rir.lens, self.rir.peaks)
-            if any_noise:
-                from .. import kernels as K
-                ws = K.noise_mix_workspace(B, wav_in.shape[1], self.device)
-                extra += (ws,) + K.noise_mix(wav_in, len_in, dev_meta[a0 + B:a0 + 5 * B].view(B, 4), self.noise.noise, self.noise.noise_off, out=wav_in, ws=ws)
-            feat, feat_len = self.parser.parse_batch(wav_in, len_in, self.dtype, augment=self.augment, rng=self.rng)
-            tgt_dev = dev_meta[2 * B:2 * B + B * lmax].view(B, lmax).long()
+                    wav = K.reverb(*rir)
+                    keep += [wav]
+            if m.any_noise:      # in place
+                ws = K.noise_mix_workspace(B, wav.shape[1], self.device)
+                keep += [ws, *K.noise_mix(wav, wav_len, field("noise_par"), self.noise.noise, self.noise.noise_off, out=wav, ws=ws)]
+            feat, feat_len = self.parser.parse_batch(wav, wav_len, self.dtype, augment=self.augment, rng=self.rng)
+            tgt_dev = field("tgt").long()
             pack = Pack()
-            pack.add(wave=feat, wave_len=feat_len.long(), tgt_for_input=tgt_dev, tgt_for_metric=tgt_dev.clone(), tgt_len=dev_meta[B:2 * B].long())
+            pack.add(wave=feat, wave_len=feat_len.long(), tgt_for_input=tgt_dev, tgt_for_metric=tgt_dev.clone(), tgt_len=field("tgt_len").long())
             done = torch.cuda.Event()
             done.record()
-        slot["keep"] = (dev_wav, dev_meta, wav_in, len_in, feat, feat_len) + extra + tuple(v for v in pack.values() if torch.is_tensor(v))
+        slot["keep"] = tuple(keep) + (feat, feat_len) + tuple(v for v in pack.values() if torch.is_tensor(v))
         return pack, done, slot
 
     PREFETCH = 2      # batches prepared ahead by the helper thread
