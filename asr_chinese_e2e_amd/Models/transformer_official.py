@@ -329,13 +329,16 @@ class _SpeechTransformer(BaseModel):
                 self._enc_given = prev
         return ctx()
 
-    def stream(self, batch_size, parser=None, source_rate=None):
+    def stream(self, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10):
         """A streaming encoder for `batch_size` utterances (stream.StreamingEncoder): push chunks of encoder-rate features, get the
         greedy CTC ids each chunk adds; finish() gives transcribe()'s result for the same decoding chunk mask.  With an AudioParser
         of norm="global" it also takes audio as it arrives: push_audio(pcm, n_samples, final) - at source_rate, converted to
-        16 kHz on the GPU as it arrives (data_handler.resample.StreamResampler); None = 16 kHz, nothing is converted."""
+        16 kHz on the GPU as it arrives (data_handler.resample.StreamResampler); None = 16 kHz, nothing is converted.
+        search="prefix_beam" (needs the CTC head): a CTC prefix beam search of `beam_size` over the `frame_topk` best classes of each
+        frame runs with the audio (asr_ctc_prefix_beam_chunk); push then returns the tokens by which the stable prefix grew, partial() /
+        nbest() the revisable hypotheses, and finish(joint="ctc_rescore") re-ranks the n-best with the decoder."""
         from ..stream import StreamingEncoder
-        return StreamingEncoder(self, batch_size, parser=parser, source_rate=source_rate)
+        return StreamingEncoder(self, batch_size, parser=parser, source_rate=source_rate, search=search, beam_size=beam_size, frame_topk=frame_topk)
 
     def forward(self, input):
         """transformer_official.py:68-81 (inference-style forward; no gradients).  A batch without a transcript (only wave / wave_len)
@@ -432,12 +435,19 @@ class _SpeechTransformer(BaseModel):
         log p_att (decode.joint_beam_search; entries then also carry 'att_score' and 'ctc_score').
         joint="one_pass": CTC prefix scores take part in every step of the search instead (decode.one_pass_beam_search, same result
         format; needs both heads and 0 < ctc_weight <= 1); ctc_pre_beam = attention candidates per hypothesis (default
-        min(16, int(1.5 * beam_size)), at least beam_size)."""
+        min(16, int(1.5 * beam_size)), at least beam_size).
+        joint="ctc_rescore": the U2 two-pass search instead (decode.ctc_rescore_search; needs both heads): the CTC prefix beam search
+        proposes beam_size hypotheses, one teacher-forced decoder pass re-ranks them by the same combination; 'yseq' then carries no
+        sos / eos, and decode_max_len does not apply."""
         from .. import decode
-        if joint not in ("rescore", "one_pass"):
-            raise ValueError(f"joint must be 'rescore' or 'one_pass' (got {joint!r})")
+        if joint not in ("rescore", "one_pass", "ctc_rescore"):
+            raise ValueError(f"joint must be 'rescore', 'one_pass' or 'ctc_rescore' (got {joint!r})")
         if joint == "one_pass":
             return decode.one_pass_beam_search(self, input, beam_size, nbest, decode_max_len, ctc_weight, ctc_pre_beam)
+        if joint == "ctc_rescore":
+            if ctc_pre_beam is not None:
+                raise ValueError("ctc_pre_beam applies to joint='one_pass' only")
+            return decode.ctc_rescore_search(self, input, beam_size, nbest, ctc_weight)
         if ctc_pre_beam is not None:
             raise ValueError("ctc_pre_beam applies to joint='one_pass' only")
         if ctc_weight > 0.0:
@@ -532,11 +542,12 @@ class _SpeechTransformer(BaseModel):
         the best hypothesis without sos / eos, text = their vocabulary tokens joined (pad / sos / eos dropped), score = the search's
         score, tokens = ctc_align's token list of the hypothesis (one launch for the batch; None when timestamps=False).  A hypothesis
         the CTC head cannot spell (infeasible for the frames, containing the blank id, longer than 255) keeps its text with None times.
-        joint: the joint model's search, "rescore" (two-pass) or "one_pass" (beam_search(joint=...)); "one_pass" needs both heads."""
-        if joint not in ("rescore", "one_pass"):
-            raise ValueError(f"joint must be 'rescore' or 'one_pass' (got {joint!r})")
-        if joint == "one_pass" and not (self.use_decoder and self.use_ctc):
-            raise RuntimeError("joint='one_pass' needs a model with both the attention decoder and the CTC head")
+        joint: the joint model's search, "rescore" (two-pass), "one_pass" or "ctc_rescore" (CTC n-best re-ranked by the decoder)
+        (beam_search(joint=...)); "one_pass" and "ctc_rescore" need both heads."""
+        if joint not in ("rescore", "one_pass", "ctc_rescore"):
+            raise ValueError(f"joint must be 'rescore', 'one_pass' or 'ctc_rescore' (got {joint!r})")
+        if joint in ("one_pass", "ctc_rescore") and not (self.use_decoder and self.use_ctc):
+            raise RuntimeError(f"joint={joint!r} needs a model with both the attention decoder and the CTC head")
         if timestamps and not self.use_ctc:
             raise ValueError("timestamps come from the CTC head, and this model has none (config.ctc_weight = 0)")
         if self.use_decoder:
@@ -551,18 +562,22 @@ class _SpeechTransformer(BaseModel):
                 scores.append(float("-inf"))
                 continue
             seq = list(h[0]["yseq"])
-            if self.use_decoder:
+            if self.use_decoder and joint != "ctc_rescore":      # the CTC n-best is spelled without sos / eos
                 seq = seq[1:] if seq and seq[0] == SOS_ID else seq
                 seq = seq[:-1] if seq and seq[-1] == EOS_ID else seq
             ids.append(seq)
             scores.append(float(h[0]["score"]))
+        return self._hyp_dicts(ids, scores, timestamps, lambda: self._ctc_logits(input), input.wave_len)
+
+    def _hyp_dicts(self, ids, scores, timestamps, ctc_logits, wave_len):
+        """transcribe's result dicts for the best ids / score of each utterance; ctc_logits() -> (B, T, V) is called for timestamps only."""
         id2tok = self.vocab._id2token
         out = [{"text": "".join(id2tok[x] for x in seq if x not in (PAD_ID, SOS_ID, EOS_ID)), "ids": seq, "score": sc, "tokens": None}
                for seq, sc in zip(ids, scores)]
         if timestamps:
             V = self.V
             ok = [len(seq) <= 255 and all(0 <= x < V and x != PAD_ID for x in seq) for seq in ids]
-            al = self._align_lists(self._ctc_logits(input), input.wave_len, ids, alignable=ok)
+            al = self._align_lists(ctc_logits(), wave_len, ids, alignable=ok)
             for o, a in zip(out, al):
                 o["tokens"] = a["tokens"]
         return out

@@ -102,6 +102,10 @@ SIGNATURES = {
     "asr_ctc_frame_topk": (I, [P, P, P, P, I, I, I, I, I, I, P]),
     "asr_ctc_prefix_beam_workspace_bytes": (Z, [I, I, I]),
     "asr_ctc_prefix_beam": (I, [P, P, P, P, P, Z, P, P, P, I, I, I, I, I, I, I, P]),
+    "asr_ctc_prefix_beam_state_bytes": (Z, [I, I]),
+    "asr_ctc_prefix_beam_stream_workspace_bytes": (Z, [I, I, I]),
+    "asr_ctc_prefix_beam_state_init": (I, [P, P, I, I, I, P]),
+    "asr_ctc_prefix_beam_chunk": (I, [P, P, P, P, P, P, Z, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "asr_beam_step": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "asr_cache_gather": (I, [P, P, P, I, I, I, I, I, I, P]),
     "asr_ctc_prefix_logprobs": (I, [P, P, I, I, I, I, I, P]),

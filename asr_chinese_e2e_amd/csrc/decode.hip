@@ -372,110 +372,111 @@ __device__ __forceinline__ double pb_logadd(double a, double b) {
 
 constexpr int PB_MAX_BEAM = 16, PB_MAX_K = 32;
 
-__global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __restrict__ vals, const int32_t* __restrict__ ids, const float* __restrict__ blank_lp,
-                                                             const int32_t* __restrict__ in_len, int32_t* __restrict__ nodes, int32_t* __restrict__ out_tok,
-                                                             int32_t* __restrict__ out_len, float* __restrict__ out_score, int T, int k, int beam, int nbest,
-                                                             int Lcap, int blank) {
-    __shared__ double s_pb[PB_MAX_BEAM], s_pnb[PB_MAX_BEAM], s_merge[PB_MAX_BEAM], s_sc[64], s_npb[64], s_npnb[64];
-    __shared__ int s_node[PB_MAX_BEAM], s_tok[PB_MAX_BEAM], s_par[PB_MAX_BEAM], s_id[PB_MAX_K], s_nnode[64], s_ntok[64], s_npar[64], s_rank[64];
-    __shared__ float s_lp[PB_MAX_K];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int cap_nodes = T * beam + 1;                  // node 0 = the empty prefix; at most `beam` new nodes per frame
-    int32_t* npar = nodes + (size_t)b * 2 * cap_nodes;   // [parent | token] per node
-    int32_t* ntok = npar + cap_nodes;
-    const int len = min(in_len ? in_len[b] : T, T);
-    if (lane == 0) {
-        npar[0] = -1;
-        ntok[0] = -1;
-        s_node[0] = 0; s_tok[0] = -1; s_par[0] = -1; s_pb[0] = 0.0; s_pnb[0] = -INFINITY;
-    }
-    int nb = 1, next_node = 1;                           // wave-uniform copies
+// The search's LDS: the beam (rank order) and one frame's slots.  s_dep = the prefix length of a beam entry (its trie node's depth).
+struct PbLds {
+    double pb[PB_MAX_BEAM], pnb[PB_MAX_BEAM], merge[PB_MAX_BEAM], sc[64], npb[64], npnb[64];
+    int node[PB_MAX_BEAM], tok[PB_MAX_BEAM], par[PB_MAX_BEAM], dep[PB_MAX_BEAM], id[PB_MAX_K], nnode[64], ntok_[64], npar_[64], ndep_[64];
+    float lp[PB_MAX_K];
+};
+
+// The empty-prefix beam every search starts from (lane 0 writes; the caller synchronises).
+__device__ __forceinline__ void pb_empty_beam(PbLds& s) {
+    s.node[0] = 0; s.tok[0] = -1; s.par[0] = -1; s.dep[0] = 0; s.pb[0] = 0.0; s.pnb[0] = -INFINITY;
+}
+
+// One frame of the search: the only copy, run by the offline kernel and by the resumable one.  row_* = the frame's candidates;
+// nb / next_node = beam entries / trie nodes in use (wave-uniform, carried across frames).
+// All 64 lanes call it; it ends with a barrier.
+__device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict__ row_vals, const int32_t* __restrict__ row_ids, double lb, int k, int beam,
+                                              int blank, int& nb, int& next_node, int32_t* npar, int32_t* ntok) {
+    const int lane = threadIdx.x, per = k + 1;
+    if (lane < k) { s.id[lane] = row_ids[lane]; s.lp[lane] = row_vals[lane]; }
+    if (lane < PB_MAX_BEAM) s.merge[lane] = -INFINITY;
     __syncthreads();
-    const int per = k + 1;
-    for (int t = 0; t < len; ++t) {
-        const size_t row = (size_t)b * T + t;
-        if (lane < k) { s_id[lane] = ids[row * k + lane]; s_lp[lane] = vals[row * k + lane]; }
-        if (lane < PB_MAX_BEAM) s_merge[lane] = -INFINITY;
-        __syncthreads();
-        const double lb = (double)blank_lp[row];
-        const int j = lane / per, m = lane - j * per;
-        bool valid = j < nb;
-        double pb2 = -INFINITY, pnb2 = -INFINITY;
-        int c = -1, ident_par = -1;
-        if (valid) {
-            const double pb = s_pb[j], pnb = s_pnb[j], tot = pb_logadd(pb, pnb);
-            const int e = s_tok[j];
-            if (m == 0) {                                // stay
-                pb2 = tot + lb;
-                for (int q = 0; q < k; ++q)
-                    if (s_id[q] == e && e != blank) pnb2 = pb_logadd(pnb2, pnb + (double)s_lp[q]);
-                c = e;
-                ident_par = s_par[j];
-            } else {                                     // extend with the (m-1)-th candidate
-                c = s_id[m - 1];
-                if (c == blank) valid = false;
-                else {
-                    pnb2 = (c == e ? pb : tot) + (double)s_lp[m - 1];
-                    ident_par = s_node[j];
-                }
+    const int j = lane / per, m = lane - j * per;
+    bool valid = j < nb;
+    double pb2 = -INFINITY, pnb2 = -INFINITY;
+    int c = -1, ident_par = -1, dep = 0;
+    if (valid) {
+        const double pb = s.pb[j], pnb = s.pnb[j], tot = pb_logadd(pb, pnb);
+        const int e = s.tok[j];
+        if (m == 0) {                                // stay
+            pb2 = tot + lb;
+            for (int q = 0; q < k; ++q)
+                if (s.id[q] == e && e != blank) pnb2 = pb_logadd(pnb2, pnb + (double)s.lp[q]);
+            c = e;
+            ident_par = s.par[j];
+            dep = s.dep[j];
+        } else {                                     // extend with the (m-1)-th candidate
+            c = s.id[m - 1];
+            if (c == blank) valid = false;
+            else {
+                pnb2 = (c == e ? pb : tot) + (double)s.lp[m - 1];
+                ident_par = s.node[j];
+                dep = s.dep[j] + 1;
             }
         }
-        // an extension that spells a prefix of the current beam goes into that entry's stay slot
-        if (valid && m > 0) {
-            for (int i = 0; i < nb; ++i)
-                if (s_par[i] == ident_par && s_tok[i] == c) {
-                    s_merge[i] = pnb2;                   // at most one extension matches an entry (parent and token are unique)
-                    valid = false;
-                    break;
-                }
-        }
-        __syncthreads();
-        if (valid && m == 0) pnb2 = pb_logadd(pnb2, s_merge[j]);
-        const double sc = valid ? pb_logadd(pb2, pnb2) : -INFINITY;
-        // a slot whose whole probability is zero cannot enter the beam (the host dictionary would hold it with -inf, ranked last)
-        valid = valid && sc > -INFINITY;
-        s_sc[lane] = sc;
-        __syncthreads();
-        int rank = 0;
-        if (valid) {
-            for (int o = 0; o < 64; ++o) {
-                const double so = s_sc[o];
-                if (so > sc || (so == sc && o < lane && so > -INFINITY)) ++rank;
-            }
-        }
-        const bool keep = valid && rank < beam;
-        const unsigned long long keep_mask = __ballot(keep);
-        const unsigned long long ext_mask = __ballot(keep && m > 0);
-        s_rank[lane] = keep ? rank : -1;
-        if (keep) {
-            int node = m == 0 ? s_node[j] : next_node + __popcll(ext_mask & ((1ull << lane) - 1ull));
-            if (m > 0) { npar[node] = ident_par; ntok[node] = c; }
-            s_nnode[rank] = node;
-            s_ntok[rank] = c;
-            s_npar[rank] = ident_par;
-            s_npb[rank] = pb2;
-            s_npnb[rank] = pnb2;
-        }
-        __syncthreads();
-        nb = __popcll(keep_mask);
-        next_node += __popcll(ext_mask);
-        if (lane < nb) {
-            s_node[lane] = s_nnode[lane]; s_tok[lane] = s_ntok[lane]; s_par[lane] = s_npar[lane];
-            s_pb[lane] = s_npb[lane]; s_pnb[lane] = s_npnb[lane];
-        }
-        __syncthreads();
     }
-    // the beam is in rank order of its total probability: spell the n best
+    // an extension that spells a prefix of the current beam goes into that entry's stay slot
+    if (valid && m > 0) {
+        for (int i = 0; i < nb; ++i)
+            if (s.par[i] == ident_par && s.tok[i] == c) {
+                s.merge[i] = pnb2;                   // at most one extension matches an entry (parent and token are unique)
+                valid = false;
+                break;
+            }
+    }
+    __syncthreads();
+    if (valid && m == 0) pnb2 = pb_logadd(pnb2, s.merge[j]);
+    const double sc = valid ? pb_logadd(pb2, pnb2) : -INFINITY;
+    // a slot whose whole probability is zero cannot enter the beam (the host dictionary would hold it with -inf, ranked last)
+    valid = valid && sc > -INFINITY;
+    s.sc[lane] = sc;
+    __syncthreads();
+    int rank = 0;
+    if (valid) {
+        for (int o = 0; o < 64; ++o) {
+            const double so = s.sc[o];
+            if (so > sc || (so == sc && o < lane && so > -INFINITY)) ++rank;
+        }
+    }
+    const bool keep = valid && rank < beam;
+    const unsigned long long keep_mask = __ballot(keep);
+    const unsigned long long ext_mask = __ballot(keep && m > 0);
+    if (keep) {
+        int node = m == 0 ? s.node[j] : next_node + __popcll(ext_mask & ((1ull << lane) - 1ull));
+        if (m > 0) { npar[node] = ident_par; ntok[node] = c; }
+        s.nnode[rank] = node;
+        s.ntok_[rank] = c;
+        s.npar_[rank] = ident_par;
+        s.ndep_[rank] = dep;
+        s.npb[rank] = pb2;
+        s.npnb[rank] = pnb2;
+    }
+    __syncthreads();
+    nb = __popcll(keep_mask);
+    next_node += __popcll(ext_mask);
+    if (lane < nb) {
+        s.node[lane] = s.nnode[lane]; s.tok[lane] = s.ntok_[lane]; s.par[lane] = s.npar_[lane]; s.dep[lane] = s.ndep_[lane];
+        s.pb[lane] = s.npb[lane]; s.pnb[lane] = s.npnb[lane];
+    }
+    __syncthreads();
+}
+
+// The beam is in rank order of its total probability: spell the n best of utterance b by walking parents.
+__device__ __forceinline__ void pb_spell(const PbLds& s, int nb, const int32_t* npar, const int32_t* ntok, int32_t* __restrict__ out_tok,
+                                         int32_t* __restrict__ out_len, float* __restrict__ out_score, int b, int nbest, int Lcap) {
+    const int lane = threadIdx.x;
     if (lane < nbest) {
         int32_t* dst = out_tok + ((size_t)b * nbest + lane) * Lcap;
         if (lane < nb) {
             int n = 0;
-            for (int nd = s_node[lane]; nd > 0; nd = npar[nd]) ++n;
+            for (int nd = s.node[lane]; nd > 0; nd = npar[nd]) ++n;
             out_len[b * nbest + lane] = n;
-            out_score[b * nbest + lane] = (float)pb_logadd(s_pb[lane], s_pnb[lane]);
+            out_score[b * nbest + lane] = (float)pb_logadd(s.pb[lane], s.pnb[lane]);
             int pos = min(n, Lcap);
             int skip = n - pos;                          // a prefix longer than the output row keeps its first Lcap tokens
-            for (int nd = s_node[lane]; nd > 0; nd = npar[nd]) {
+            for (int nd = s.node[lane]; nd > 0; nd = npar[nd]) {
                 if (skip > 0) { --skip; continue; }
                 dst[--pos] = ntok[nd];
             }
@@ -484,6 +485,111 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
             out_score[b * nbest + lane] = -INFINITY;
         }
     }
+}
+
+__global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __restrict__ vals, const int32_t* __restrict__ ids, const float* __restrict__ blank_lp,
+                                                             const int32_t* __restrict__ in_len, int32_t* nodes, int32_t* __restrict__ out_tok,
+                                                             int32_t* __restrict__ out_len, float* __restrict__ out_score, int T, int k, int beam, int nbest,
+                                                             int Lcap, int blank) {
+    __shared__ PbLds s;
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int cap_nodes = T * beam + 1;                  // node 0 = the empty prefix; at most `beam` new nodes per frame
+    int32_t* npar = nodes + (size_t)b * 2 * cap_nodes;   // [parent | token] per node
+    int32_t* ntok = npar + cap_nodes;
+    const int len = min(in_len ? in_len[b] : T, T);
+    if (lane == 0) {
+        npar[0] = -1;
+        ntok[0] = -1;
+        pb_empty_beam(s);
+    }
+    int nb = 1, next_node = 1;                           // wave-uniform copies
+    __syncthreads();
+    for (int t = 0; t < len; ++t) {
+        const size_t row = (size_t)b * T + t;
+        pb_frame_step(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
+    }
+    pb_spell(s, nb, npar, ntok, out_tok, out_len, out_score, b, nbest, Lcap);
+}
+
+// ---- the resumable search: the beam leaves LDS between launches ------------------------------------------------------------------
+// State of one utterance (asr_ctc_prefix_beam_state_bytes / B bytes, 8-aligned): int32 {nb, next_node, frames consumed, 0}, then per beam
+// entry int32 node[beam], token[beam], parent[beam], depth[beam], then fp64 pb[beam], pnb[beam] - everything pb_frame_step carries from
+// one frame to the next.  Trie of one utterance: int32 [parent | token] x (T_cap * beam + 1) nodes, numbered and laid out as offline; an entry's depth
+// (its prefix length, for the stable prefix) travels with the entry, so the trie needs none.
+constexpr int PB_STATE_HDR = 4;
+
+__host__ __device__ inline size_t pb_state_bytes1(int beam) { return (size_t)PB_STATE_HDR * 4 + (size_t)beam * (4 * 4 + 2 * 8); }
+
+__global__ __launch_bounds__(64) void ctc_prefix_beam_state_init_kernel(char* state, int32_t* nodes, int B, int beam, int T_cap) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const size_t cap_nodes = (size_t)T_cap * beam + 1;
+    int32_t* hdr = (int32_t*)(state + (size_t)b * pb_state_bytes1(beam));
+    int32_t* ent = hdr + PB_STATE_HDR;
+    double* sc = (double*)(ent + 4 * beam);
+    hdr[0] = 1; hdr[1] = 1; hdr[2] = 0; hdr[3] = 0;
+    for (int i = 0; i < beam; ++i) {
+        ent[i] = 0; ent[beam + i] = -1; ent[2 * beam + i] = -1; ent[3 * beam + i] = 0;
+        sc[i] = i == 0 ? 0.0 : -INFINITY; sc[beam + i] = -INFINITY;
+    }
+    int32_t* npar = nodes + (size_t)b * 2 * cap_nodes;
+    npar[0] = -1; npar[cap_nodes] = -1;
+}
+
+__global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* __restrict__ vals, const int32_t* __restrict__ ids, const float* __restrict__ blank_lp,
+                                                                   const int32_t* __restrict__ n_valid, char* state, int32_t* nodes, int32_t* __restrict__ out_tok,
+                                                                   int32_t* __restrict__ out_len, float* __restrict__ out_score, int32_t* __restrict__ out_stable,
+                                                                   int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank) {
+    __shared__ PbLds s;
+    __shared__ int s_walk[PB_MAX_BEAM];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int cap_nodes = T_cap * beam + 1;
+    int32_t* npar = nodes + (size_t)b * 2 * cap_nodes;   // [parent | token] per node
+    int32_t* ntok = npar + cap_nodes;
+    int32_t* hdr = (int32_t*)(state + (size_t)b * pb_state_bytes1(beam));
+    int32_t* ent = hdr + PB_STATE_HDR;
+    double* sc = (double*)(ent + 4 * beam);
+    int nb = min(max(hdr[0], 0), beam), next_node = hdr[1];      // wave-uniform copies
+    const int frames = hdr[2];
+    if (lane < nb) {
+        s.node[lane] = ent[lane]; s.tok[lane] = ent[beam + lane]; s.par[lane] = ent[2 * beam + lane]; s.dep[lane] = ent[3 * beam + lane];
+        s.pb[lane] = sc[lane]; s.pnb[lane] = sc[beam + lane];
+    }
+    __syncthreads();
+    // never past the trie: at most T_cap frames in all (the wrapper refuses such a push; this keeps every write inside the workspace)
+    const int n = max(0, min(min(n_valid[b], C), T_cap - frames));
+    int done = 0;
+    for (int t = 0; t < n; ++t) {
+        if (next_node < 1 || next_node + beam > cap_nodes) break;
+        const size_t row = (size_t)b * C + t;
+        pb_frame_step(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
+        ++done;
+    }
+    if (done > 0) {                                      // a chunk without frames leaves every byte of the state as it is
+        if (lane == 0) { hdr[0] = nb; hdr[1] = next_node; hdr[2] = frames + done; }
+        if (lane < nb) {
+            ent[lane] = s.node[lane]; ent[beam + lane] = s.tok[lane]; ent[2 * beam + lane] = s.par[lane]; ent[3 * beam + lane] = s.dep[lane];
+            sc[lane] = s.pb[lane]; sc[beam + lane] = s.pnb[lane];
+        }
+    }
+    pb_spell(s, nb, npar, ntok, out_tok, out_len, out_score, b, nbest, Lcap);
+    // the stable prefix: the depth of the lowest common ancestor of the beam's nodes.  Every entry first climbs to the smallest depth
+    // among them, then all climb together until they stand on one node.
+    int mind = INT_MAX;
+    for (int i = 0; i < nb; ++i) mind = min(mind, s.dep[i]);
+    int nd = lane < nb ? s.node[lane] : 0, d = lane < nb ? s.dep[lane] : 0;
+    while (d > mind && nd > 0) { nd = npar[nd]; --d; }
+    for (;;) {
+        if (lane < nb) s_walk[lane] = nd;
+        __syncthreads();
+        bool same = true;
+        for (int i = 1; i < nb; ++i) same = same && s_walk[i] == s_walk[0];
+        __syncthreads();
+        if (same || mind <= 0) break;                    // wave-uniform
+        if (lane < nb && nd > 0) nd = npar[nd];
+        --mind;
+    }
+    if (lane == 0) out_stable[b] = nb > 0 ? mind : 0;
 }
 
 }  // namespace
@@ -503,6 +609,46 @@ extern "C" int asr_ctc_prefix_beam(const float* vals, const int32_t* ids, const 
     if (ws_bytes < asr_ctc_prefix_beam_workspace_bytes(B, T, beam) || ((uintptr_t)ws % 4)) ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_workspace_bytes(B, T, beam), ws_bytes);
     ctc_prefix_beam_kernel<<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank);
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam");
+    return ASR_OK;
+}
+
+extern "C" size_t asr_ctc_prefix_beam_state_bytes(int B, int beam) {
+    if (B <= 0 || beam <= 0) return 0;
+    return (size_t)B * pb_state_bytes1(beam);
+}
+
+extern "C" size_t asr_ctc_prefix_beam_stream_workspace_bytes(int B, int T_cap, int beam) {
+    if (B <= 0 || T_cap <= 0 || beam <= 0) return 0;
+    return asr_ctc_prefix_beam_workspace_bytes(B, T_cap, beam);      // the offline search's trie for T_cap frames
+}
+
+extern "C" int asr_ctc_prefix_beam_state_init(void* state, void* ws, int B, int beam, int T_cap, void* stream) {
+    if (!state || !ws) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_state_init: null pointer");
+    if (B <= 0 || beam <= 0 || beam > PB_MAX_BEAM || T_cap <= 0 || (size_t)T_cap * beam + 1 > (size_t)INT_MAX)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_state_init: bad shape B=%d beam=%d (<= %d) T_cap=%d", B, beam, PB_MAX_BEAM, T_cap);
+    if (((uintptr_t)state % 8) || ((uintptr_t)ws % 4)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_state_init: misaligned pointer (state: 8 bytes, workspace: 4)");
+    ctc_prefix_beam_state_init_kernel<<<ceil_div(B, 64), 64, 0, (hipStream_t)stream>>>((char*)state, (int32_t*)ws, B, beam, T_cap);
+    ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_state_init");
+    return ASR_OK;
+}
+
+extern "C" int asr_ctc_prefix_beam_chunk(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* n_valid, void* state, void* ws,
+                                         size_t ws_bytes, int32_t* out_tok, int32_t* out_len, float* out_score, int32_t* out_stable, int B, int C, int k,
+                                         int beam, int nbest, int Lcap, int T_cap, int blank, void* stream) {
+    if (!vals || !ids || !blank_lp || !n_valid || !state || !ws || !out_tok || !out_len || !out_score || !out_stable)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk: null pointer");
+    if (B <= 0 || C < 1 || T_cap < 1 || k <= 0 || beam <= 0 || nbest <= 0 || Lcap <= 0)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk: bad shape B=%d C=%d T_cap=%d k=%d beam=%d nbest=%d Lcap=%d", B, C, T_cap, k, beam, nbest, Lcap);
+    if (beam > PB_MAX_BEAM || k > PB_MAX_K || beam * (k + 1) > 64 || nbest > beam)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk: one wave ranks the beam * (k + 1) candidates of a frame: beam * (k + 1) <= 64, beam <= %d, nbest <= beam (beam=%d k=%d nbest=%d)", PB_MAX_BEAM, beam, k, nbest);
+    if ((size_t)T_cap * beam + 1 > (size_t)INT_MAX) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk: T_cap * beam + 1 nodes do not fit an int32 (T_cap=%d beam=%d)", T_cap, beam);
+    if (((uintptr_t)state % 8) || (((uintptr_t)vals | (uintptr_t)ids | (uintptr_t)blank_lp | (uintptr_t)n_valid | (uintptr_t)out_tok | (uintptr_t)out_len | (uintptr_t)out_score | (uintptr_t)out_stable) % 4))
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk: misaligned pointer (state: 8 bytes, the others: 4)");
+    if (ws_bytes < asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam) || ((uintptr_t)ws % 4))
+        ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_chunk: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam), ws_bytes);
+    ctc_prefix_beam_chunk_kernel<<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score, out_stable,
+                                                                    C, k, beam, nbest, Lcap, T_cap, blank);
+    ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_chunk");
     return ASR_OK;
 }
 

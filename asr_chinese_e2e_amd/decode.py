@@ -274,6 +274,83 @@ def joint_beam_search(model, input, beam_size=5, nbest=1, decode_max_len=0, ctc_
     return out
 
 
+# --------------------------------------------------------------------------------------------- attention rescoring of a CTC n-best (U2)
+def attention_rescore(model, enc, wave_len, nbest_lists, ctc_weight):
+    """Second pass of the U2 recipe (Zhang et al. 2020; WeNet's attention_rescoring): the decoder scores the CTC search's n-best
+    teacher-forced in ONE forward pass and the list is re-ranked.  enc (B, T, d): the encoder output (offline or streamed), wave_len
+    (B,): its valid frames, nbest_lists: per utterance at most n {'yseq': ids without sos / eos, 'score': the prefix beam's score}.
+    Over the N = B * n hypotheses: input [sos] + y, target y + [eos], cross-attention over all T encoder rows with key length
+    wave_len (the mask of beam_search / _DecoderSteps, not the ref_compat training mask); att_score = the sum of the target's
+    log-probabilities (asr_xent_fwd_bwd without the gradient, summed per hypothesis).  The encoder rows are repeated per hypothesis, as
+    joint_beam_search repeats its logits.  Returns per utterance the list sorted by score = ctc_weight * ctc_score + (1 - ctc_weight) *
+    att_score (joint_beam_search's convention; ties keep the CTC order), entries {'yseq', 'score', 'att_score', 'ctc_score'}.  Missing
+    ranks are skipped, an empty hypothesis scores log p(eos | sos), a hypothesis longer than the positional-encoding table admits gets
+    att_score = score = -inf and so stays behind the others in its CTC order."""
+    eng = model._ensure_engine(enc.device)
+    if not eng.use_decoder:
+        raise RuntimeError("attention rescoring needs a model with the attention decoder")
+    B, T = enc.shape[0], enc.shape[1]
+    if len(nbest_lists) != B:
+        raise ValueError(f"{len(nbest_lists)} n-best lists for a batch of {B}")
+    n = max([len(l) for l in nbest_lists] + [0])
+    if n == 0:
+        return [[] for _ in range(B)]
+    lam = float(ctc_weight)
+    limit = eng.pe.shape[0] - 1                                # [sos] + y takes len(y) + 1 positions
+    seqs = [[[int(x) for x in l[j]["yseq"]] if j < len(l) else [] for j in range(n)] for l in nbest_lists]
+    # id 0 is the padding the decoder's target preparation drops: a hypothesis that holds it (no CTC search spells the blank) cannot be
+    # teacher-forced as it is spelled and is treated like one that does not fit
+    fits = [[len(y) <= limit and BLANK_ID not in y for y in row] for row in seqs]
+    Lmax = max([len(y) for row, f in zip(seqs, fits) for y, ok in zip(row, f) if ok] + [1])
+    N = B * n
+    tgt = torch.zeros(N, Lmax, dtype=torch.int64)
+    for b in range(B):
+        for j, y in enumerate(seqs[b]):
+            if y and fits[b][j]:
+                tgt[b * n + j, : len(y)] = torch.tensor(y, dtype=torch.int64)
+    dev = enc.device
+    was_training, eng.training = eng.training, False
+    try:
+        with torch.no_grad():
+            prep = K.dec_preprocess(tgt.to(dev), SOS_ID, EOS_ID)
+            rep = enc.reshape(B, T, -1).to(eng.dtype).repeat_interleave(n, dim=0).reshape(N * T, -1).contiguous()
+            cross_len = wave_len.to(torch.int32).repeat_interleave(n).contiguous()
+            pred, _ = eng.decoder_fwd(prep, rep, cross_len, N, T)
+            row_nll, _ = K.xent_fwd_bwd(pred.contiguous(), prep[1].reshape(-1), prep[5], BLANK_ID, smoothing=0.0, want_grad=False)
+    finally:
+        eng.training = was_training
+    att = (-row_nll.view(N, Lmax + 1).cpu().double().sum(dim=1)).tolist()      # padded target rows (id 0) carry 0
+    out = []
+    for b in range(B):
+        cands = []
+        for j, h in enumerate(nbest_lists[b]):
+            a = att[b * n + j] if fits[b][j] else -math.inf
+            ctc = float(h["score"])
+            sc = lam * ctc + (1.0 - lam) * a if a != -math.inf else -math.inf
+            cands.append(dict(yseq=list(seqs[b][j]), score=sc, att_score=a, ctc_score=ctc))
+        out.append(sorted(cands, key=lambda c: c["score"], reverse=True))
+    return out
+
+
+def ctc_rescore_search(model, input, beam_size=5, nbest=1, ctc_weight=0.0, frame_topk=10):
+    """The U2 two-pass search offline: ctc_prefix_beam_search with n-best = beam_size, then attention_rescore of that list against the
+    same encoder output (the encoder runs once).  Returns per utterance at most `nbest` {'yseq' (no sos / eos), 'score', 'att_score',
+    'ctc_score'}."""
+    eng = model._ensure_engine(input.wave.device)
+    if not (eng.use_ctc and eng.use_decoder):
+        raise RuntimeError("CTC n-best rescoring needs a model with both the attention decoder and the CTC head (0 < config.ctc_weight < 1)")
+    was_training, eng.training = eng.training, False
+    try:
+        with torch.no_grad():
+            enc = model.forward(input).encoder_out             # (B, T, d)
+    finally:
+        eng.training = was_training
+    with model.given_encoder_output(enc):
+        hyps = ctc_prefix_beam_search(model, input, beam_size, beam_size, frame_topk)
+    res = attention_rescore(model, enc, input.wave_len, hyps, ctc_weight)
+    return [r[:nbest] for r in res]
+
+
 # --------------------------------------------------------------------------------------------- one-pass joint CTC / attention search
 def default_pre_beam(beam_size):
     """Attention candidates per hypothesis of the one-pass search: min(16, int(1.5 * beam)), ESPnet's ratio."""

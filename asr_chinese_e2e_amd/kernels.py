@@ -443,6 +443,66 @@ def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max
     return out_tok, out_len, out_score
 
 
+class PrefixBeamState:
+    """The resumable prefix beam search's device memory (include/asr_hip.h): `state` (the beam of each utterance between chunks) and
+    `ws` (the trie, room for T_cap frames per utterance); `frames` = frames consumed per utterance, kept on the host so that a
+    chunk past T_cap is refused before any launch."""
+
+    def __init__(self, state, ws, B, beam, T_cap):
+        self.state, self.ws, self.B, self.beam, self.T_cap = state, ws, B, beam, T_cap
+        self.frames = [0] * B
+
+
+def ctc_prefix_beam_state(B, beam, T_cap, device="cuda"):
+    """A fresh PrefixBeamState: the empty-prefix beam for B utterances of at most T_cap frames each."""
+    B, beam, T_cap = int(B), int(beam), int(T_cap)
+    if B < 1 or beam < 1 or T_cap < 1:
+        raise ValueError(f"ctc_prefix_beam_state: B, beam and T_cap must be >= 1 (got {B}, {beam}, {T_cap})")
+    state = torch.zeros(lib.asr_ctc_prefix_beam_state_bytes(B, beam) // 8, dtype=torch.int64, device=device)      # 8-aligned
+    ws = torch.empty(lib.asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam), dtype=torch.uint8, device=device)
+    check(lib.asr_ctc_prefix_beam_state_init(_p(state), _p(ws), B, beam, T_cap, _stream()), "asr_ctc_prefix_beam_state_init")
+    return PrefixBeamState(state, ws, B, beam, T_cap)
+
+
+def prefix_beam_unpack(buf, B, nbest, Lcap):
+    """(tokens (B, nbest, Lcap) int32, lengths (B, nbest) int32, scores (B, nbest) f32, stable (B) int32) as views of the int32 buffer of
+    B * (nbest * (Lcap + 2) + 1) words that ctc_prefix_beam_chunk fills (on the device or copied to the host)."""
+    tok_n, len_n = B * nbest * Lcap, B * nbest
+    assert buf.dtype == torch.int32 and buf.numel() == tok_n + 2 * len_n + B and buf.is_contiguous()
+    return (buf[:tok_n].view(B, nbest, Lcap), buf[tok_n:tok_n + len_n].view(B, nbest),
+            buf[tok_n + len_n:tok_n + 2 * len_n].view(torch.float32).view(B, nbest), buf[tok_n + 2 * len_n:])
+
+
+def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, max_len=None, packed=False):
+    """One chunk of the resumable search: vals / ids (B*C, k), blank_lp (B*C) = the chunk's rows of ctc_frame_topk; n_valid = the
+    frames of each utterance to consume (a list of B ints in [0, C]).  A chunk that would take an utterance past st.T_cap frames raises
+    before anything is launched.  Returns (tokens (B, nbest, Lcap) int32, lengths (B, nbest) int32 with -1 for missing ranks, scores
+    (B, nbest) f32, stable (B) int32 = the length of the prefix every beam entry shares) - views of one int32 buffer (prefix_beam_unpack);
+    packed=True returns (that buffer, Lcap) instead, so that one copy brings all four to the host.  Lcap = max_len, by default the most
+    frames any utterance has consumed after this chunk: no prefix is longer than that."""
+    B, beam, k = st.B, st.beam, vals.shape[1]
+    C, nbest = int(C), int(nbest)
+    nv = [int(x) for x in n_valid]
+    if len(nv) != B or any(x < 0 or x > C for x in nv):
+        raise ValueError(f"ctc_prefix_beam_chunk: n_valid must hold {B} values in [0, {C}], got {nv}")
+    for b in range(B):
+        if st.frames[b] + nv[b] > st.T_cap:
+            raise ValueError(f"ctc_prefix_beam_chunk: utterance {b} would reach {st.frames[b] + nv[b]} frames, the trie holds {st.T_cap}")
+    assert vals.shape == (B * C, k) and ids.shape == (B * C, k) and blank_lp.numel() == B * C
+    _chk_f32(vals, blank_lp)
+    _chk_i32(ids)
+    Lcap = int(max(1, max(f + n for f, n in zip(st.frames, nv))) if max_len is None else max_len)
+    out = torch.zeros(B * (nbest * (Lcap + 2) + 1), dtype=torch.int32, device=vals.device)
+    out_tok, out_len, out_score, out_stable = prefix_beam_unpack(out, B, nbest, Lcap)
+    nv_dev = torch.tensor(nv, dtype=torch.int32, device=vals.device)
+    check(lib.asr_ctc_prefix_beam_chunk(_p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(), _p(out_tok), _p(out_len),
+                                        _p(out_score), _p(out_stable), B, C, k, beam, nbest, Lcap, st.T_cap, int(blank), _stream()),
+          "asr_ctc_prefix_beam_chunk")
+    for b in range(B):
+        st.frames[b] += nv[b]
+    return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable)
+
+
 def beam_step(top_vals, top_ids, score, alive, last_tok, parent, rec_tok, rec_par, rec_end, rec_score, maxlen, alive_total, B, beam, step, eos):
     _chk_f32(top_vals, score, rec_score)
     _chk_i32(top_ids, alive, last_tok, parent, rec_tok, rec_par, rec_end, maxlen, alive_total)

@@ -11,6 +11,11 @@ Per push: input projection, LayerNorm + positional encoding at the chunk's absol
 the CTC head and its frame-wise argmax - the engine's kernels (gemm_small / NT, sdpa_fwd, add_ln_fwd, asr_ctc_frame_argmax).
 
 push_audio takes samples instead: a StreamingFrontEnd (data_handler/stream_frontend.py) turns them into chunks, each of which is pushed.
+
+search="prefix_beam" (the first pass of the U2 recipe): instead of the argmax, each push feeds the chunk's per-frame candidates
+(asr_ctc_frame_topk) to the resumable CTC prefix beam search (asr_ctc_prefix_beam_chunk), whose beam lives on the device between
+pushes.  push returns the tokens by which the STABLE prefix grew - the prefix all beam entries share, which no later chunk can retract;
+partial() / nbest() give the revisable hypotheses, finish(joint="ctc_rescore") re-ranks the n-best with the decoder (second pass).
 """
 import torch
 
@@ -21,7 +26,7 @@ BLANK = 0      # the CTC blank (= PAD_ID of the model)
 
 
 class StreamingEncoder:
-    def __init__(self, model, batch_size, parser=None, source_rate=None):
+    def __init__(self, model, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10):
         C, left = model.decoding_chunk_size, model.decoding_left_chunks
         if C <= 0:
             raise ValueError("model.stream() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
@@ -37,6 +42,19 @@ class StreamingEncoder:
         self.cap = 0                         # cache rows per utterance
         self.caches = None                   # [buffer][layer] -> (B * cap, 2 H dk); the second buffer only with left >= 0 (_slide)
         self.outs, self.feats = [], []
+        if search not in ("greedy", "prefix_beam"):
+            raise ValueError(f"search must be 'greedy' or 'prefix_beam' (got {search!r})")
+        self.search, self.beam_size, self.frame_topk = search, int(beam_size), int(frame_topk)
+        if search == "prefix_beam":
+            if not model.use_ctc:
+                raise RuntimeError("search='prefix_beam' needs a model with the CTC head (config.ctc_weight > 0)")
+            k = max(1, min(self.frame_topk, model.V))
+            if self.beam_size < 1 or self.beam_size > 16 or self.beam_size * (k + 1) > 64:
+                raise ValueError(f"the device search ranks beam * (frame_topk + 1) <= 64 candidates per frame, beam <= 16 (beam {beam_size}, frame_topk {k})")
+            self.frame_topk = k
+        self.beam = None                     # K.PrefixBeamState, allocated by the first push for the positional-encoding table's frames
+        self.stable = [0] * self.B           # tokens of each utterance handed out by push so far (beam mode)
+        self._hyps = None                    # the last push's (tokens, lengths, scores) as host arrays
         self.parser, self.frontend = parser, None      # the front end is built by the first push_audio
         # source_rate: the rate of the audio push_audio receives; other than 16 kHz it goes through a StreamResampler first (None: 16 kHz)
         self.source_rate, self.resampler = source_rate, None
@@ -84,7 +102,8 @@ class StreamingEncoder:
     def push(self, feats, n_valid):
         """feats (B, C, F): one chunk of encoder-rate features (after LFR and normalisation) in the model's dtype; n_valid (B,): the valid
         frames of each utterance in it (0 once an utterance has ended).  Returns per utterance the greedy CTC ids this chunk adds
-        (repeats collapsed across chunk boundaries; empty lists for a model without a CTC head)."""
+        (repeats collapsed across chunk boundaries; empty lists for a model without a CTC head).  search="prefix_beam": the tokens by
+        which the stable prefix of the prefix beam search grew in this chunk - append-only as well; partial() / nbest() for the rest."""
         model, B, C = self.model, self.B, self.C
         if feats.dim() != 3 or feats.shape[0] != B or feats.shape[1] != C:
             raise ValueError(f"push: feats must be (B, C, F) = ({B}, {C}, F), got {tuple(feats.shape)}")
@@ -120,7 +139,19 @@ class StreamingEncoder:
                     h1, _, _ = K.add_ln_fwd(a, h, mha.ln.g, mha.ln.b, None, nv_dev, B, C, xhat=a)
                     h, _ = eng._ffn_block_fwd(ffn, h1, B, C, nv_dev, site=0)
                 out = [[] for _ in range(B)]
-                if model.use_ctc:
+                if self.search == "prefix_beam":
+                    if self.beam is None:      # the trie for every frame push admits: B * 2 * (table * beam + 1) * 4 bytes
+                        self.beam = K.ctc_prefix_beam_state(B, self.beam_size, eng.pe.shape[0], dev)
+                    vals, ids, blank_lp = K.ctc_frame_topk(eng.ctc_lo.fwd(h), self.frame_topk, BLANK)
+                    buf, Lcap = K.ctc_prefix_beam_chunk(self.beam, vals, ids, blank_lp, nv, C, self.beam_size, BLANK, packed=True)
+                    # one copy: tokens, lengths, scores and stable lengths travel in one buffer
+                    # (kept as arrays: the token rows are Lcap wide, and only the first `length` of each are ever turned into lists)
+                    tok, ln, sc, stable = (t.numpy() for t in K.prefix_beam_unpack(buf.cpu(), B, self.beam_size, Lcap))
+                    self._hyps = (tok, ln, sc)
+                    for b in range(B):
+                        out[b] = tok[b, 0, self.stable[b]:int(stable[b])].tolist()
+                        self.stable[b] = int(stable[b])
+                elif model.use_ctc:
                     logits = eng.ctc_lo.fwd(h).view(B, C, -1)
                     path = K.ctc_frame_argmax(logits, nv_dev, BLANK).cpu().tolist()
                     for b in range(B):
@@ -177,9 +208,52 @@ class StreamingEncoder:
         dev = self.outs[0].device
         return torch.cat(self.outs, dim=1), torch.tensor(self.valid, dtype=torch.int32, device=dev)
 
+    def _need_beam(self, what):
+        if self.search != "prefix_beam":
+            raise ValueError(f"{what} needs a stream opened with search='prefix_beam'")
+
+    def nbest(self):
+        """search="prefix_beam": per utterance the search's current list of {"yseq", "score"}, best first (at most beam_size)."""
+        self._need_beam("nbest()")
+        if self._hyps is None:
+            return [[{"yseq": [], "score": 0.0}] for _ in range(self.B)]
+        tok, ln, sc = self._hyps
+        return [[{"yseq": tok[b, r, :ln[b, r]].tolist(), "score": float(sc[b, r])} for r in range(self.beam_size) if ln[b, r] >= 0]
+                for b in range(self.B)]
+
+    def partial(self):
+        """search="prefix_beam": per utterance {"ids": the best prefix now (revisable past stable_len), "stable_len": how many of its
+        tokens are final (the concatenation of what push returned), "score": its log-probability}."""
+        return [{"ids": h[0]["yseq"] if h else [], "stable_len": self.stable[b], "score": h[0]["score"] if h else float("-inf")}
+                for b, h in enumerate(self.nbest())]
+
+    def _finish_rescore(self, ctc_weight=None, timestamps=True):
+        """The second pass: the decoder re-ranks the streamed search's n-best (decode.attention_rescore) against the streamed encoder
+        output; a CTC-only model keeps the CTC best.  transcribe's result dicts, timestamps from the CTC head over the same output."""
+        from . import decode
+        self._need_beam("finish(joint='ctc_rescore')")
+        model = self.model
+        enc, lens = self.encoder_output()
+        hyps = self.nbest()
+        if model.use_decoder:
+            w = float(getattr(model.config, "ctc_weight", 0.0)) if ctc_weight is None else float(ctc_weight)
+            hyps = decode.attention_rescore(model, enc, lens, hyps, w)
+        ids = [list(h[0]["yseq"]) if h else [] for h in hyps]
+        scores = [float(h[0]["score"]) if h else float("-inf") for h in hyps]
+        B, T = enc.shape[0], enc.shape[1]
+
+        def ctc_logits():
+            with torch.no_grad():
+                return self.eng.ctc_lo.fwd(enc.reshape(B * T, -1).contiguous()).view(B, T, -1)
+        return model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens)
+
     def finish(self, beam_size=5, **kw):
         """model.transcribe(...) of the pushed features under the same decoding chunk mask, computed from the streamed encoder output
-        (the encoder does not run again).  kw: transcribe's other arguments (ctc_weight, timestamps, joint)."""
+        (the encoder does not run again).  kw: transcribe's other arguments (ctc_weight, timestamps, joint).
+        joint="ctc_rescore" (a stream opened with search="prefix_beam"): no new search - the streamed prefix beam search's n-best is
+        re-ranked by the decoder (_finish_rescore); beam_size does not apply, the list is the stream's."""
+        if kw.get("joint") == "ctc_rescore":
+            return self._finish_rescore(ctc_weight=kw.get("ctc_weight"), timestamps=kw.get("timestamps", True))
         enc, lens = self.encoder_output()
         wave = torch.cat(self.feats, dim=1)
         with self.model.given_encoder_output(enc):

@@ -317,6 +317,24 @@ size_t asr_ctc_prefix_beam_workspace_bytes(int B, int T, int beam);
 int asr_ctc_prefix_beam(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* in_len, void* ws, size_t ws_bytes,
                         int32_t* out_tok, int32_t* out_len, float* out_score, int B, int T, int k, int beam, int nbest, int Lcap,
                         int blank, void* stream);
+/* The same search, resumable (additive to ABI 10): the beam leaves the kernel between launches, so the frames may arrive in chunks.
+ *   state: asr_ctc_prefix_beam_state_bytes(B, beam) bytes, 8-aligned; per utterance int32 {nb, next_node, frames consumed, 0}, int32
+ *   node / token / parent / depth [beam], fp64 pb / pnb [beam].  ws: asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam) bytes, the
+ *   trie ([parent | token] x (T_cap * beam + 1) nodes per utterance, numbered as asr_ctc_prefix_beam numbers them).
+ * asr_ctc_prefix_beam_state_init: the empty-prefix beam asr_ctc_prefix_beam starts from, and the trie's root.
+ * asr_ctc_prefix_beam_chunk: vals / ids (B*C, k), blank_lp (B*C) = one chunk's rows of asr_ctc_frame_topk; consumes the first
+ *   n_valid[b] in [0, C] frames of utterance b (clamped to what T_cap still admits: nothing is ever written outside ws), stores the state
+ *   back and writes out_tok / out_len / out_score as asr_ctc_prefix_beam does - after any cutting of the frames into chunks bit for bit what
+ *   asr_ctc_prefix_beam gives on the frames consumed so far (both run one frame-step body).  n_valid[b] == 0: the state keeps every byte,
+ *   the outputs are spelled from it.  out_stable[b] = the length of the longest common prefix of all beam entries (the depth of their
+ *   lowest common ancestor in the trie): every later entry descends from a current one, so these tokens are never retracted and the
+ *   length never decreases.  Limits as asr_ctc_prefix_beam, and C >= 1, T_cap >= 1; one wave per utterance. */
+size_t asr_ctc_prefix_beam_state_bytes(int B, int beam);
+size_t asr_ctc_prefix_beam_stream_workspace_bytes(int B, int T_cap, int beam);
+int asr_ctc_prefix_beam_state_init(void* state, void* ws, int B, int beam, int T_cap, void* stream);
+int asr_ctc_prefix_beam_chunk(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* n_valid, void* state, void* ws,
+                              size_t ws_bytes, int32_t* out_tok, int32_t* out_len, float* out_score, int32_t* out_stable, int B, int C, int k,
+                              int beam, int nbest, int Lcap, int T_cap, int blank, void* stream);
 int asr_decode_attn(const void* q, const void* k, const void* v, void* o, const int32_t* k_len,
                     int k_len_uniform, int len_div, int R, int H, int dk, int Tk_cap, int kv_div,
                     int ldq, int ldk, int ldv, int ldo, float scale, int dtype, void* stream);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Chunk-masked encoder attention: what the mask costs or saves, one JSON object on stdout.
 
-  python tools/chunk_bench.py [--reps 50] [--steps 20] [--warmup 5] [--skip-step] [--skip-stream]
+  python tools/chunk_bench.py [--reps 50] [--steps 20] [--warmup 5] [--skip-attention] [--skip-step] [--skip-stream] [--skip-stream-search]
 
 * attention: sdpa_fwd / sdpa_bwd us at the headline head shape (B = 32, H = 8, T = 500, dk = 64, bf16, every key valid), full
   attention against chunk C = 16 with unlimited and with 4 chunks of left context (device events, median of --reps after a warm-up of
@@ -9,7 +9,10 @@
 * step: the joint training step (bench.py's configs[2] shapes: B = 32, T = 500, 6 layers, vocab 4232, bf16, dropout 0) with
   chunk_size = 0, 16 and -1 (dynamic), the three models alternated in ONE process in rounds of --warmup untimed + --steps timed steps;
 * stream: model.stream(B).push() latency per chunk of C = 16 frames at B = 1 and B = 32 (host wall time: push returns the chunk's
-  greedy CTC ids, so it synchronises), unlimited left context, over a 496-frame utterance.
+  greedy CTC ids, so it synchronises), unlimited left context, over a 496-frame utterance;
+* stream_search: the same push with search="greedy" against search="prefix_beam" (beam 5, 10 classes per frame: asr_ctc_frame_topk +
+  asr_ctc_prefix_beam_chunk instead of the argmax), the two streams alternated in ONE process, three rounds, median over the chunks of
+  each round.
 """
 import argparse
 import json
@@ -117,6 +120,34 @@ def stream(C=16, T=496):
     return out
 
 
+def stream_search(C=16, T=496, rounds=3):
+    from asr_chinese_e2e_amd import Models
+    from asr_chinese_e2e_amd.data_handler import Vocab
+    M = Models.TransformerOffical
+    cfg = M.get_default_config()()
+    cfg.fn_build(dict(n_mels=80, lfr_m=1, dropout=0.0, layer_num=6, ctc_weight=0.3, dtype="bf16", chunk_size=C))
+    torch.manual_seed(0)
+    model = M(cfg, Vocab.synthetic(4232)).to(DEV).eval()
+    modes = {"greedy": dict(search="greedy"), "prefix_beam": dict(search="prefix_beam", beam_size=5, frame_topk=10)}
+    out = {}
+    for B in (1, 32):
+        feats = torch.randn(B, T, 80, device=DEV).bfloat16()
+        med = {m: [] for m in modes}
+        for r in range(rounds + 1):      # round 0 warms every cache size and is not reported
+            for m, kw in modes.items():
+                st = model.stream(B, **kw)
+                lat = []
+                for c0 in range(0, T, C):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    st.push(feats[:, c0:c0 + C].contiguous(), [C] * B)
+                    lat.append((time.perf_counter() - t0) * 1e3)
+                if r > 0:
+                    med[m].append(statistics.median(lat))
+        out[f"B={B}"] = {m: {"median_ms": round(statistics.median(v), 3), "rounds_ms": [round(x, 3) for x in v]} for m, v in med.items()}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
@@ -124,12 +155,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--skip-step", action="store_true")
     ap.add_argument("--skip-stream", action="store_true")
+    ap.add_argument("--skip-attention", action="store_true")
+    ap.add_argument("--skip-stream-search", action="store_true")
     a = ap.parse_args()
-    res = {"device": torch.cuda.get_device_name(0), "attention_B32_H8_T500_dk64_bf16": attention(a.reps)}
+    res = {"device": torch.cuda.get_device_name(0)}
+    if not a.skip_attention:
+        res["attention_B32_H8_T500_dk64_bf16"] = attention(a.reps)
     if not a.skip_step:
         res["joint_step_B32_T500"] = step(a.steps, a.warmup)
     if not a.skip_stream:
         res["stream_push_C16"] = stream()
+    if not a.skip_stream_search:
+        res["stream_push_C16_search"] = stream_search()
     print(json.dumps(res))
 
 

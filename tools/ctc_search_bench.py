@@ -1,5 +1,7 @@
-"""CTC prefix beam search / joint rescoring throughput at the BASELINE shape (B=32, T=500, V=4232), random weights."""
-import os, sys, time
+"""CTC prefix beam search / joint rescoring throughput at the BASELINE shape (B=32, T=500, V=4232), random weights.
+The last line is one JSON object: the three joint searches (two-pass rescore, one_pass, ctc_rescore; beam 5) alternated in this
+process, three rounds of three searches each, the median round per search."""
+import json, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from asr_chinese_e2e_amd import Models
@@ -18,3 +20,12 @@ c = t(lambda: model.ctc_greedy_search(pack))
 print(f"ctc prefix beam search (beam 5, top-10 classes per frame): {a:8.1f} ms per batch of 32 = {32e3 / a:7.1f} utt/s")
 print(f"attention beam 5 + CTC rescoring (lambda 0.3):            {b:8.1f} ms per batch of 32 = {32e3 / b:7.1f} utt/s")
 print(f"ctc greedy:                                                {c:8.1f} ms per batch of 32 = {32e3 / c:7.1f} utt/s")
+joint = {"rescore": lambda: model.beam_search(pack, beam_size=5, nbest=1, decode_max_len=32, ctc_weight=0.3),
+         "one_pass": lambda: model.beam_search(pack, beam_size=5, nbest=1, decode_max_len=32, ctc_weight=0.3, joint="one_pass"),
+         "ctc_rescore": lambda: model.beam_search(pack, beam_size=5, nbest=1, ctc_weight=0.3, joint="ctc_rescore")}
+rounds = {k: [] for k in joint}
+for _ in range(3):
+    for k, fn in joint.items():
+        rounds[k].append(t(fn))
+print(json.dumps({"joint_search_B32_T500_beam5_ms": {k: {"median_ms": round(statistics.median(v), 2), "rounds_ms": [round(x, 2) for x in v]}
+                                                     for k, v in rounds.items()}}))

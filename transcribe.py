@@ -12,8 +12,9 @@ trained with rebuild it.  Inference flags:
   --manifest     a collector manifest (one JSON object {"wave": path, ...} per line)
   --beam_size    beam of the search (default 5)
   --ctc_weight   joint models: weight of the CTC score in the search (default: the model's ctc_weight)
-  --joint        joint models: rescore (default; CTC re-ranks the attention beam's n-best list) or one_pass (CTC prefix scores
-                 take part in every step of the search)
+  --joint        joint models: rescore (default; CTC re-ranks the attention beam's n-best list), one_pass (CTC prefix scores
+                 take part in every step of the search) or ctc_rescore (the CTC prefix beam search's n-best list re-ranked by one
+                 teacher-forced decoder pass)
   --batch_size   utterances per batch (default 16)
   --timestamps   per-character times from the CTC head (default: on when the model has one)
   --stream       1 = run the encoder chunk by chunk (model.stream) under the decoding chunk mask (--decoding_chunk_size /
@@ -22,6 +23,10 @@ trained with rebuild it.  Inference flags:
                  samples themselves are streamed (push_audio, in blocks of --stream_block_samples, default one chunk's worth of
                  audio): the live-audio path.  Without it the features are normalised over the whole utterance first and only
                  the encoder streams: that emulates streaming over files.
+  --stream_search  with --stream=1: greedy (default) or prefix_beam - a CTC prefix beam search of --beam_size over the --frame_topk
+                 (default 10) best classes of each frame runs with the audio; the per-chunk line becomes {"file", "chunk", "partial",
+                 "stable"}: the best hypothesis now (revisable) and the part of it no later chunk can change.  The final line then
+                 comes from finish(joint="ctc_rescore"): the decoder re-ranks the streamed n-best (a CTC-only model keeps the CTC best)
   --cmvn         global CMVN statistics (tools/compute_cmvn.py) the model was trained with (train.py --cmvn); empty = the
                  per-utterance normalisation
   --resample     1 = files at 8, 11.025, 12, 22.05, 24, 32, 44.1, 48, 88.2 or 96 kHz are converted to 16 kHz on the GPU (one launch per
@@ -48,7 +53,7 @@ from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
 from asr_chinese_e2e_amd.data_handler import resample as resample_mod  # noqa: E402
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample")
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk")
 
 
 def _finite(x):
@@ -81,40 +86,49 @@ def audio_files(flags):
     raise SystemExit("transcribe.py: give --wavs=a.wav,b.wav or --manifest=<collector json>")
 
 
-def stream_batch(model, files, feats, flen, id2tok, **search):
-    """model.stream over a batch of feature sequences in chunks of the decoding chunk size: prints the partial greedy CTC text of every
-    file after every chunk, returns what model.transcribe returns (finish())."""
+def _chunk_lines(st, files, nv, ids, text, chunk, id2tok):
+    """The per-chunk JSON lines of the files that got frames: greedy = the text so far; prefix beam = the best hypothesis now and its
+    stable part."""
+    part = st.partial() if st.search == "prefix_beam" else None
+    spell = lambda seq: "".join(id2tok[t] for t in seq if part is None or t not in (0, 2, 3))      # noqa: E731  (beam mode: as the final text, without pad / sos / eos)
+    for b in range(len(files)):
+        if nv[b] <= 0:
+            continue
+        text[b] += spell(ids[b])
+        line = {"file": files[b], "chunk": chunk, "partial": text[b]}
+        if part is not None:
+            line.update(partial=spell(part[b]["ids"]), stable=text[b])
+        print(json.dumps(line, ensure_ascii=False), flush=True)
+
+
+def stream_batch(model, files, feats, flen, id2tok, stream_kw=None, **search):
+    """model.stream over a batch of feature sequences in chunks of the decoding chunk size: prints the partial text of every
+    file after every chunk, returns what model.transcribe returns (finish()).  stream_kw: model.stream's search arguments."""
     B, T, F = feats.shape
     C = model.decoding_chunk_size
     lens = [int(x) for x in flen.tolist()]
-    st = model.stream(B)
+    st = model.stream(B, **(stream_kw or {}))
     text = [""] * B
     for i, c0 in enumerate(range(0, T, C)):
         x = feats[:, c0:c0 + C]
         if x.shape[1] < C:
             x = torch.nn.functional.pad(x, (0, 0, 0, C - x.shape[1]))
         nv = [max(0, min(C, n - c0)) for n in lens]
-        for b, ids in enumerate(st.push(x.contiguous(), nv)):
-            if nv[b] > 0:
-                text[b] += "".join(id2tok[t] for t in ids)
-                print(json.dumps({"file": files[b], "chunk": i, "partial": text[b]}, ensure_ascii=False), flush=True)
+        _chunk_lines(st, files, nv, st.push(x.contiguous(), nv), text, i, id2tok)
     return st.finish(**search)
 
 
-def stream_audio_batch(model, parser, files, wav, wav_len, id2tok, block, source_rate=None, **search):
+def stream_audio_batch(model, parser, files, wav, wav_len, id2tok, block, source_rate=None, stream_kw=None, **search):
     """model.stream fed with the samples themselves, `block` at a time (wav (B, S) f32 on the host, wav_len list): the same lines as
     stream_batch prints, the same result.  source_rate: the rate of wav when it is not 16 kHz (converted as it streams)."""
     B, S = wav.shape
-    st = model.stream(B, parser=parser, source_rate=source_rate)
+    st = model.stream(B, parser=parser, source_rate=source_rate, **(stream_kw or {}))
     text, chunk = [""] * B, 0
     for s0 in range(0, max(S, 1), block):
         n = [max(0, min(block, l - s0)) for l in wav_len]
         final = [l <= s0 + block for l in wav_len]
         for nv, ids in st.push_audio_chunks(wav[:, s0:s0 + block].contiguous(), n, final):
-            for b in range(B):
-                if nv[b] > 0:
-                    text[b] += "".join(id2tok[t] for t in ids[b])
-                    print(json.dumps({"file": files[b], "chunk": chunk, "partial": text[b]}, ensure_ascii=False), flush=True)
+            _chunk_lines(st, files, nv, ids, text, chunk, id2tok)
             chunk += 1
     return st.finish(**search)
 
@@ -144,9 +158,17 @@ def transcribe(**flags):
     bs = max(1, int(cli.get("batch_size", 16)))
     timestamps = bool(cli.get("timestamps", model.use_ctc))
     joint = str(cli.get("joint", "rescore"))
-    if joint not in ("rescore", "one_pass"):
-        raise SystemExit(f"transcribe.py: --joint must be rescore or one_pass (got {joint!r})")
+    if joint not in ("rescore", "one_pass", "ctc_rescore"):
+        raise SystemExit(f"transcribe.py: --joint must be rescore, one_pass or ctc_rescore (got {joint!r})")
     stream = bool(int(cli.get("stream", 0)))
+    stream_search = str(cli.get("stream_search", "greedy"))
+    if stream_search not in ("greedy", "prefix_beam"):
+        raise SystemExit(f"transcribe.py: --stream_search must be greedy or prefix_beam (got {stream_search!r})")
+    if stream_search == "prefix_beam" and not stream:
+        raise SystemExit("transcribe.py: --stream_search=prefix_beam applies to --stream=1")
+    if stream_search == "prefix_beam" and not model.use_ctc:
+        raise SystemExit("transcribe.py: --stream_search=prefix_beam needs a model with the CTC head")
+    stream_kw = dict(search="prefix_beam", beam_size=beam, frame_topk=int(cli.get("frame_topk", 10))) if stream_search == "prefix_beam" else {}
     resample = bool(int(cli.get("resample", 0)))      # --resample=1: files at another rate are converted on the GPU instead of ending the run
     if stream and model.decoding_chunk_size <= 0:
         raise SystemExit("transcribe.py: --stream=1 needs a decoding chunk (--decoding_chunk_size, or a static --chunk_size)")
@@ -178,13 +200,15 @@ def transcribe(**flags):
             else:      # one launch for the batch, whatever rates it mixes
                 wav, wav_len, _ = resample_mod.resample_batch(wav.cuda(), wav_len.tolist(), rates)
         search = dict(beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps, joint=joint)
+        if stream_kw:      # the streamed search's own n-best, re-ranked by the decoder
+            search = dict(ctc_weight=ctc_weight, timestamps=timestamps, joint="ctc_rescore")
         if stream and parser.norm == "global":      # the samples stream: blocks of one chunk's worth of audio unless told otherwise
             block = int(cli.get("stream_block_samples", 0)) or model.decoding_chunk_size * config.lfr_n * 160 * (stream_rate or 16000) // 16000
-            out = stream_audio_batch(model, parser, chunk, wav, wav_len.tolist(), id2tok, block, source_rate=stream_rate, **search)
+            out = stream_audio_batch(model, parser, chunk, wav, wav_len.tolist(), id2tok, block, source_rate=stream_rate, stream_kw=stream_kw, **search)
         else:
             feats, flen = parser.parse_batch(wav.cuda(), wav_len.cuda())
             if stream:
-                out = stream_batch(model, chunk, feats, flen, id2tok, **search)
+                out = stream_batch(model, chunk, feats, flen, id2tok, stream_kw=stream_kw, **search)
             else:
                 out = model.transcribe(Pack(wave=feats, wave_len=flen), **search)
         for path, w, sr, r in zip(chunk, waves, rates, out):
