@@ -155,6 +155,8 @@ SIGNATURES = {
     "asr_stream_append": (I, [P, P, P, I, I, I, I, I, P]),
     "asr_stream_logmel": (I, [P, P, P, P, P, I, I, I, I, I, P]),
     "asr_stream_norm_lfr": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "asr_fbank_fwd": (I, [P, P, P, P, P, I, I, I, I, F, F, P]),
+    "asr_stream_fbank": (I, [P, P, P, P, P, I, I, I, I, I, F, F, P]),
 }
 
 

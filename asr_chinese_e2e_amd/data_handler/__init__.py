@@ -7,5 +7,5 @@ from . import speed
 from . import noise
 from .noise import NoiseBank, RirBank
 from . import cmvn
-from .cmvn import CmvnAccumulator, load_cmvn, save_cmvn
+from .cmvn import CmvnAccumulator, load_cmvn, load_cmvn_meta, save_cmvn, save_wenet_cmvn
 from .stream_frontend import StreamingFrontEnd

@@ -529,7 +529,7 @@ def parser_norm(cmvn):
 def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=True, sample_rate=16000, window_size=400, n_mels=40,
                      augment=False, predump=False, use_old=False, lfr_m=4, lfr_n=3, dtype=torch.bfloat16, shuffle=None, seed=0,
                      rank=0, world=1, speed_perturb=None, cmvn=None, noise=None, noise_prob=0.5, snr_db=(5, 20), rir=None, rir_prob=0.5,
-                     rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS, resample=False):
+                     rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS, resample=False, frontend="reference"):
     """build_dataloader of the reference (data/data_loader/ai_shell_1.py:91-104), same arguments: reads the manifest
     `<collector_path>_<part>.json` written by the reference's collector (one JSON object {"wave": path, "tgt": text}
     per line, data_collector/ai_shell_1.py:73-79) and returns an iterable of Packs.  The reference computes features
@@ -541,7 +541,8 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
     cmvn: path of a global-CMVN statistics file (tools/compute_cmvn.py): the features of this part are normalised per mel bin by
     the corpus statistics (AudioParser norm="global"); None / empty = the reference's per-utterance normalisation.
     resample: True = files (and noise / response files of a bank built here) at another rate than 16 kHz are converted on the GPU
-    (WaveDataset / BucketedWaveLoader / noise banks, every part); False = they raise, as before."""
+    (WaveDataset / BucketedWaveLoader / noise banks, every part); False = they raise, as before.
+    frontend: "reference" (the reference's log-mel) or "kaldi" (Kaldi fbank): AudioParser's."""
     import json
     if not use_cuda:
         raise RuntimeError("the feature front end runs on the GPU only (no CPU fallback)")
@@ -554,7 +555,7 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
                 rec = json.loads(line)
                 items.append((rec["wave"], rec["tgt"]))
     ds = WaveDataset(items, vocab, sample_rate=sample_rate, resample=resample)
-    parser = AudioParser(sample_rate=sample_rate, n_mels=n_mels, lfr_m=lfr_m, lfr_n=lfr_n, device="cuda", **parser_norm(cmvn))
+    parser = AudioParser(sample_rate=sample_rate, n_mels=n_mels, lfr_m=lfr_m, lfr_n=lfr_n, device="cuda", frontend=frontend, **parser_norm(cmvn))
     wave_aug = dict(noise=noise, noise_prob=noise_prob, snr_db=snr_db, rir=rir, rir_prob=rir_prob, rir_method=rir_method,
                     rir_max_taps=rir_max_taps) if part == "train" else {}
     return BucketedWaveLoader(ds, batch_size, parser=parser, augment=augment, shuffle=(part == "train") if shuffle is None else shuffle,

@@ -10,9 +10,11 @@ import random
 import torch
 
 from .. import kernels as K
-from .cmvn import load_cmvn
+from .cmvn import load_cmvn_meta
 
 SR, N_FFT, HOP = 16000, 400, 160
+FRONTENDS = ("reference", "kaldi")
+KALDI_NFFT, KALDI_WAV_SCALE, KALDI_PREEMPH, KALDI_LOW_FREQ = 512, 32768.0, 0.97, 20.0      # Kaldi's fbank defaults as WeNet uses them
 
 
 def mel_filterbank(n_mels, f_min=40.0, f_max=SR / 2 - 200.0):
@@ -26,6 +28,35 @@ def mel_filterbank(n_mels, f_min=40.0, f_max=SR / 2 - 200.0):
     slopes = f_pts[None, :] - freqs[:, None]
     fb = np.maximum(0.0, np.minimum(-slopes[:, :-2] / f_diff[:-1], slopes[:, 2:] / f_diff[1:]))
     return torch.from_numpy(fb.astype(np.float32))
+
+
+def povey_window():
+    """Kaldi's default window, (0.5 - 0.5 cos(2 pi n / 399))^0.85, float64 rounded once."""
+    w = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(N_FFT) / (N_FFT - 1))) ** 0.85
+    return torch.from_numpy(w.astype(np.float32))
+
+
+def kaldi_mel_filterbank(n_mels, low_freq=KALDI_LOW_FREQ, high_freq=SR / 2):
+    """(256, n_mels) Kaldi mel banks over the bins 0 .. 255 of the 512-point transform: triangles in the mel domain,
+    mel(f) = 1127 ln(1 + f / 700), n_mels + 2 points equally spaced from mel(low_freq) to mel(high_freq); float64 rounded once."""
+    mel = lambda f: 1127.0 * np.log(1.0 + f / 700.0)
+    lo, hi = mel(low_freq), mel(high_freq)
+    delta = (hi - lo) / (n_mels + 1)
+    m = mel(np.arange(KALDI_NFFT // 2, dtype=np.float64) * SR / KALDI_NFFT)[:, None]
+    left = lo + np.arange(n_mels, dtype=np.float64)[None, :] * delta
+    centre, right = left + delta, left + 2.0 * delta
+    fb = np.where((m > left) & (m <= centre), (m - left) / (centre - left), np.where((m > centre) & (m < right), (right - m) / (right - centre), 0.0))
+    return torch.from_numpy(fb.astype(np.float32))
+
+
+def equivalent_length(frames):
+    """The length in samples that the normalisation kernels (which count frames as 1 + len // 160, 0 for len = 0) take for `frames`
+    frames: 160 (frames - 1) + 1, and 0 for no frame.  How the Kaldi front end, whose count is another function of the length, hands
+    its frame counts to asr_utt_norm_augment_lfr_fwd, asr_global_norm_augment_lfr_fwd and asr_cmvn_accumulate.  An int, or a tensor of
+    frame counts (then computed where the tensor lives)."""
+    if torch.is_tensor(frames):
+        return ((frames - 1) * HOP + 1).clamp(min=0)
+    return HOP * (frames - 1) + 1 if frames >= 1 else 0
 
 
 def build_LFR_features(inputs, m, n):
@@ -61,40 +92,102 @@ class AudioParser:
     """Batched device front end: parse_batch(wav (B,S) f32 cuda, wav_len (B) int) ->
     (features (B, T_lfr, lfr_m*n_mels), feature_len (B) int32)."""
 
-    def __init__(self, sample_rate=SR, n_mels=80, window_size=N_FFT, hop=HOP, lfr_m=4, lfr_n=3, device="cuda", norm="utterance", cmvn=None):
+    def __init__(self, sample_rate=SR, n_mels=80, window_size=N_FFT, hop=HOP, lfr_m=4, lfr_n=3, device="cuda", norm="utterance", cmvn=None,
+                 frontend="reference"):
         """norm: "utterance" (the reference's scalar mean / std of each utterance) or "global" (per-bin corpus statistics): then
-        cmvn = (mean, istd), one value per mel bin, or the path of a file tools/compute_cmvn.py wrote."""
+        cmvn = (mean, istd), one value per mel bin, or the path of a statistics file (tools/compute_cmvn.py, WeNet's JSON, Kaldi's text).
+        frontend: "reference" (the reference's log-mel: centred reflect-padded frames, Hann, 400-point DFT, HTK banks) or "kaldi"
+        (Kaldi fbank as WeNet configures it: snip_edges frames, DC removal, pre-emphasis, Povey window, 512-point DFT, Kaldi banks)."""
         assert sample_rate == SR and window_size == N_FFT and hop == HOP, "kernel is specialised to 16 kHz / 400 / 160"
         if norm not in ("utterance", "global"):
             raise ValueError(f"norm must be 'utterance' or 'global', got {norm!r}")
-        self.n_mels, self.lfr_m, self.lfr_n, self.norm = n_mels, lfr_m, lfr_n, norm
+        if frontend not in FRONTENDS:
+            raise ValueError(f"frontend must be one of {FRONTENDS}, got {frontend!r}")
+        self.n_mels, self.lfr_m, self.lfr_n, self.norm, self.frontend = n_mels, lfr_m, lfr_n, norm, frontend
         self.mean = self.istd = None
         if norm == "global":
             if cmvn is None or (isinstance(cmvn, str) and not cmvn):
                 raise ValueError("norm='global' needs cmvn=(mean, istd) or the path of a statistics file (tools/compute_cmvn.py)")
-            mean, istd = load_cmvn(cmvn)[:2] if isinstance(cmvn, (str, os.PathLike)) else cmvn
+            if isinstance(cmvn, (str, os.PathLike)):
+                mean, istd, _, file_frontend = load_cmvn_meta(cmvn)
+                if file_frontend != frontend:
+                    raise ValueError(f"{os.fspath(cmvn)}: statistics of the {file_frontend!r} front end, the parser's is {frontend!r}")
+            else:
+                mean, istd = cmvn
             mean, istd = (np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.float64) for v in (mean, istd))
             if mean.shape != (n_mels,) or istd.shape != (n_mels,):
                 raise ValueError(f"cmvn statistics are for {mean.shape} / {istd.shape} mel bins, the parser has {n_mels}")
             self.mean, self.istd = (torch.from_numpy(v.astype(np.float32)).to(device) for v in (mean, istd))
         elif cmvn is not None:
             raise ValueError("cmvn statistics given, but norm is 'utterance': pass norm='global' to use them")
-        self.window = torch.hann_window(N_FFT, periodic=True, dtype=torch.float32).to(device)
-        self.melfb = mel_filterbank(n_mels).to(device)
+        self.wav_scale, self.preemph = (KALDI_WAV_SCALE, KALDI_PREEMPH) if frontend == "kaldi" else (1.0, 0.0)
+        if frontend == "kaldi":
+            self.window, self.melfb = povey_window().to(device), kaldi_mel_filterbank(n_mels).to(device)
+        else:
+            self.window = torch.hann_window(N_FFT, periodic=True, dtype=torch.float32).to(device)
+            self.melfb = mel_filterbank(n_mels).to(device)
+
+    # ---- the frame arithmetic of the two front ends: the one place it is written
+    def num_frames(self, length):
+        """Frames of an utterance of `length` samples."""
+        length = int(length)
+        if self.frontend == "kaldi":
+            return 1 + (length - N_FFT) // HOP if length >= N_FFT else 0
+        return 1 + length // HOP if length > 0 else 0
+
+    def max_frames(self, S):
+        """Rows of the feature buffer of a batch whose rows hold S samples (at least 1: the kernels take no empty buffer)."""
+        return max(self.num_frames(S), 1) if self.frontend == "kaldi" else 1 + int(S) // HOP
+
+    def frames_ready(self, received, closed=False):
+        """Streaming: frames that can be computed after `received` samples; closed: `received` is the whole utterance.  A Kaldi frame
+        touches its own 400 samples only, so the close changes nothing."""
+        if self.frontend == "kaldi":
+            return self.num_frames(received)
+        from . import stream_frontend as SF
+        return SF.frames_ready(received, closed)
+
+    def oldest_sample(self, t):
+        """Streaming: the first sample frame t (and so any later frame) touches."""
+        return HOP * t if self.frontend == "kaldi" else max(0, HOP * t - N_FFT // 2)
+
+    def frame_centre_sample(self, t):
+        """The sample at the centre of frame t's window."""
+        return HOP * t + N_FFT // 2 if self.frontend == "kaldi" else HOP * t
+
+    def frame_counts(self, wav_len, S, Tmax):
+        """Frames per utterance, a host list (wav_len is read back), of a batch whose rows hold S samples, cut at Tmax."""
+        return [min(self.num_frames(min(int(l), S)), Tmax) for l in wav_len.tolist()]
+
+    def norm_lengths(self, wav_len, S, Tmax):
+        """The int32 lengths that make the normalisation kernels count this front end's frames (rows of S samples, cut at Tmax): the
+        lengths themselves, for "kaldi" the equivalent lengths - computed where wav_len lives, nothing is read back."""
+        wl = wav_len.to(torch.int32)
+        if self.frontend != "kaldi":
+            return wl
+        frames = (torch.div(wl.clamp(0, S) - N_FFT, HOP, rounding_mode="floor") + 1).clamp(0, Tmax)
+        return equivalent_length(frames).to(torch.int32)
+
+    def features(self, wav, wav_len, Tmax, feat=None):
+        """wav (B, S) f32, wav_len (B) int32 -> (B, Tmax, n_mels) f32 frames of this parser's front end."""
+        if self.frontend == "kaldi":
+            return K.fbank(wav, wav_len, self.window, self.melfb, Tmax, self.wav_scale, self.preemph, feat=feat)
+        return K.logmel(wav, wav_len, self.window, self.melfb, Tmax, feat=feat)
 
     def parse_batch(self, wav, wav_len, dtype=torch.float32, augment=False, rng=random):
         """augment=True: SpecAugment as AudioParser.parse(path, augment=True) of the reference, masks
         drawn on the host from `rng` (the `random` module by default, as the reference), applied on the
         device between normalisation and frame stacking."""
         B, S = wav.shape
-        Tmax = 1 + S // HOP
+        Tmax = self.max_frames(S)
         wl = wav_len.to(torch.int32)
-        feat = K.logmel(wav.contiguous(), wl, self.window, self.melfb, Tmax)
+        feat = self.features(wav.contiguous(), wl, Tmax)
         Tl = (Tmax + self.lfr_n - 1) // self.lfr_n
         masks = None
         if augment:
-            frames = [min(1 + int(l) // HOP, Tmax) if int(l) > 0 else 0 for l in wav_len.tolist()]
+            frames = self.frame_counts(wav_len, S, Tmax)
             masks = torch.tensor([sample_spec_augment(self.n_mels, fr, rng) for fr in frames], dtype=torch.int32).to(wav.device)
+        wl = self.norm_lengths(wl, S, Tmax)
         if self.norm == "global":
             return K.global_norm_lfr(feat, wl, self.mean, self.istd, self.lfr_m, self.lfr_n, Tl, dtype, masks=masks)
         return K.utt_norm_lfr(feat, wl, self.lfr_m, self.lfr_n, Tl, dtype, masks=masks)

@@ -7,6 +7,12 @@ emitted as soon as every sample it touches has arrived, so frame 0 needs 201 sam
 kernel's reflection and clamping at the end.  LFR row r stacks frames r n .. r n + m - 1: it is emitted when the last of them exists,
 and after the close every row r < ceil(frames / n) is, the tail repeating the last frame.
 
+The four functions are the rules of the reference front end.  The class asks its parser how many frames are ready
+(AudioParser.frames_ready), so a parser with frontend="kaldi" streams by its own rule: frame t is samples 160 t .. 160 t + 399 and
+nothing else, it is emitted once sample 160 t + 399 has arrived, and the close adds no frame - only the LFR tail rows, which repeat the
+last frame.  What keeps a live sample in the ring is the same for both front ends: once every frame that can leave has left, fewer than
+400 received samples are still needed (the `piece` of __init__).
+
 State: per utterance a ring of samples and a ring of log-mel frames on the device (kernels.stream_append / stream_logmel /
 stream_norm_lfr; include/asr_hip.h), and the counters below on the host - n_samples is host data, so nothing is read back."""
 import torch
@@ -75,6 +81,7 @@ class StreamingFrontEnd:
         self.m, self.n, self.n_mels = parser.lfr_m, parser.lfr_n, parser.n_mels
         self.dev = parser.window.device
         self.scap = int(sample_cap)
+        self.kaldi = getattr(parser, "frontend", "reference") == "kaldi"
         self.piece = self.scap - 512      # fewer than 400 samples of history are ever live (every frame that can leave has left)
         self.fcap = _pow2_at_least(self.C * self.n + self.m + self.piece // HOP + 34)
         self.max_frames = max(int(max_frames), self.fcap)
@@ -91,7 +98,8 @@ class StreamingFrontEnd:
     def plan(self, ns, fin):
         """The launches push_audio makes for n_samples = ns and final = fin, from the counters alone (nothing is launched or changed):
         -> (actions, counters after the call).  Actions, in order: ("append", pcm offset, [[received, n_new]], max n_new),
-        ("grow", new frame capacity, [(first live frame, end)] per utterance), ("logmel", [[t_begin, n_new, total or OPEN]], max n_new),
+        ("grow", new frame capacity, [(first live frame, end)] per utterance), ("logmel", [[t_begin, n_new, total or OPEN]], max n_new)
+        (the frames of the parser's front end; a Kaldi parser's kernel reads the first two columns only),
         ("chunk", [[r_begin, n_rows, frames or OPEN]], n_valid)."""
         B, C, m, n = self.B, self.C, self.m, self.n
         received, closed, next_frame, next_row, fcap = list(self.received), list(self.closed), list(self.next_frame), list(self.next_row), self.fcap
@@ -104,7 +112,7 @@ class StreamingFrontEnd:
                 received[b] += take[b]
                 if fin[b] and off + take[b] >= ns[b]:
                     closed[b] = True
-            new = [frames_ready(received[b], closed[b]) - next_frame[b] for b in range(B)]
+            new = [self.parser.frames_ready(received[b], closed[b]) - next_frame[b] for b in range(B)]
             if max(new) > 0:
                 # live frames of an utterance: from the first one its next row stacks (none once every row has left) to its last
                 live = [(min(next_row[b] * n, next_frame[b] + new[b]), next_frame[b] + new[b]) for b in range(B)]
@@ -127,6 +135,10 @@ class StreamingFrontEnd:
                 acts.append(("chunk", [[next_row[b], nv[b], next_frame[b] if closed[b] else K.STREAM_OPEN] for b in range(B)], nv))
                 for b in range(B):
                     next_row[b] += nv[b]
+        # Kaldi: utterances of fewer than 400 samples have no frame.  When this call closes the last of them and no row has ever left,
+        # one empty chunk tells the consumer that every utterance has ended (a reference utterance of any sample has a frame).
+        if self.kaldi and all(closed) and not all(self.closed) and not any(next_row) and not any(a[0] == "chunk" for a in acts):
+            acts.append(("chunk", [[0, 0, 0] for _ in range(B)], [0] * B))
         return acts, (received, closed, next_frame, next_row)
 
     def _grow_frames(self, cap, live):
@@ -161,6 +173,9 @@ class StreamingFrontEnd:
                 K.stream_append(pcm, self._par(act[2]), self.wav_ring, act[1], act[3])
             elif act[0] == "grow":
                 self._grow_frames(act[1], act[2])
+            elif act[0] == "logmel" and self.kaldi:
+                par = self._par([row[:2] for row in act[1]])
+                K.stream_fbank(self.wav_ring, par, self.parser.window, self.parser.melfb, self.feat_ring, act[2], self.parser.wav_scale, self.parser.preemph)
             elif act[0] == "logmel":
                 K.stream_logmel(self.wav_ring, self._par(act[1]), self.parser.window, self.parser.melfb, self.feat_ring, act[2])
             else:

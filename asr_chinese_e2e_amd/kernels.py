@@ -1112,6 +1112,33 @@ def stream_logmel(wav_ring, par, window, melfb, feat_ring, max_new):
           "asr_stream_logmel")
 
 
+def fbank(wav, wav_len, window, melfb, Tmax, wav_scale, preemph, feat=None):
+    """Kaldi fbank of wav (B, Smax) f32 -> (B, Tmax, n_mels) f32 (include/asr_hip.h: asr_fbank_fwd): window (400) f32, melfb (256, n_mels) f32."""
+    _chk_f32(wav, window, melfb)
+    _chk_i32(wav_len)
+    B, Smax = wav.shape
+    n_mels = melfb.shape[1]
+    assert melfb.shape == (256, n_mels) and window.numel() == 400 and wav_len.numel() == B
+    feat = torch.empty(B, Tmax, n_mels, dtype=torch.float32, device=wav.device) if feat is None else feat
+    assert tuple(feat.shape) == (B, Tmax, n_mels)
+    _chk_f32(feat)
+    check(lib.asr_fbank_fwd(_p(wav), _p(wav_len), _p(window), _p(melfb), _p(feat), B, Smax, int(Tmax), n_mels, float(wav_scale), float(preemph), _stream()),
+          "asr_fbank_fwd")
+    return feat
+
+
+def stream_fbank(wav_ring, par, window, melfb, feat_ring, max_new, wav_scale, preemph):
+    """Kaldi fbank frames t_begin .. t_begin + n_new - 1 of every utterance from its sample ring into its frame ring: par (B, 2) int32 =
+    {t_begin, n_new}."""
+    _chk_f32(wav_ring, window, melfb, feat_ring)
+    _chk_i32(par)
+    B, scap = wav_ring.shape
+    _, fcap, n_mels = feat_ring.shape
+    assert tuple(par.shape) == (B, 2) and feat_ring.shape[0] == B and melfb.shape == (256, n_mels) and window.numel() == 400
+    check(lib.asr_stream_fbank(_p(wav_ring), _p(par), _p(window), _p(melfb), _p(feat_ring), B, int(max_new), scap, fcap, n_mels, float(wav_scale),
+                               float(preemph), _stream()), "asr_stream_fbank")
+
+
 def stream_norm_lfr(feat_ring, par, mean, istd, m, n, C, dtype=torch.float32):
     """One encoder chunk (B, C, m n_mels) out of the frame rings under global CMVN: par (B, 3) int32 = {r_begin, n_rows, frames or STREAM_OPEN}."""
     _chk_f32(feat_ring, mean, istd)

@@ -125,7 +125,9 @@ class StreamingEncoder:
                 self._grow(eng, max(self.clen) + C, dev)
                 caches = self.caches[0]
                 nv_dev = torch.tensor(nv, dtype=torch.int32, device=dev)
-                klen = torch.tensor([c + n for c, n in zip(self.clen, nv)], dtype=torch.int32, device=dev)
+                # at least one key: an utterance that ended without a single frame (fewer than 400 samples under the Kaldi front end) still
+                # sits in the batch; its rows are not valid and nothing reads them, and a length of 1 keeps zero-key attention off the kernels
+                klen = torch.tensor([max(c + n, 1) for c, n in zip(self.clen, nv)], dtype=torch.int32, device=dev)
                 rows = torch.tensor([b * self.cap + self.clen[b] + t for b in range(B) for t in range(C)], dtype=torch.long, device=dev)
                 x = feats.to(eng.dtype).contiguous().reshape(B * C, -1)
                 e0 = eng.lin_in.fwd(x)
@@ -227,25 +229,39 @@ class StreamingEncoder:
         return [{"ids": h[0]["yseq"] if h else [], "stable_len": self.stable[b], "score": h[0]["score"] if h else float("-inf")}
                 for b, h in enumerate(self.nbest())]
 
+    def _live_only(self, timestamps, search):
+        """finish() over the utterances that have a frame: search(rows) -> their result dicts, rows = their indices in the batch (every
+        one of them in the common case).  An utterance without a frame gets the empty transcript and reaches no search kernel."""
+        live = [b for b in range(self.B) if self.valid[b] > 0]
+        res = search(live) if live else []
+        out = [{"text": "", "ids": [], "score": float("-inf"), "tokens": [] if timestamps else None} for _ in range(self.B)]
+        for b, r in zip(live, res):
+            out[b] = r
+        return out
+
     def _finish_rescore(self, ctc_weight=None, timestamps=True):
         """The second pass: the decoder re-ranks the streamed search's n-best (decode.attention_rescore) against the streamed encoder
         output; a CTC-only model keeps the CTC best.  transcribe's result dicts, timestamps from the CTC head over the same output."""
         from . import decode
         self._need_beam("finish(joint='ctc_rescore')")
         model = self.model
-        enc, lens = self.encoder_output()
-        hyps = self.nbest()
-        if model.use_decoder:
-            w = float(getattr(model.config, "ctc_weight", 0.0)) if ctc_weight is None else float(ctc_weight)
-            hyps = decode.attention_rescore(model, enc, lens, hyps, w)
-        ids = [list(h[0]["yseq"]) if h else [] for h in hyps]
-        scores = [float(h[0]["score"]) if h else float("-inf") for h in hyps]
-        B, T = enc.shape[0], enc.shape[1]
+        all_enc, all_lens = self.encoder_output()
+        all_hyps = self.nbest()
 
-        def ctc_logits():
-            with torch.no_grad():
-                return self.eng.ctc_lo.fwd(enc.reshape(B * T, -1).contiguous()).view(B, T, -1)
-        return model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens)
+        def search(rows):
+            enc, lens, hyps = (all_enc, all_lens, all_hyps) if len(rows) == self.B else (all_enc[rows].contiguous(), all_lens[rows], [all_hyps[b] for b in rows])
+            if model.use_decoder:
+                w = float(getattr(model.config, "ctc_weight", 0.0)) if ctc_weight is None else float(ctc_weight)
+                hyps = decode.attention_rescore(model, enc, lens, hyps, w)
+            ids = [list(h[0]["yseq"]) if h else [] for h in hyps]
+            scores = [float(h[0]["score"]) if h else float("-inf") for h in hyps]
+            B, T = enc.shape[0], enc.shape[1]
+
+            def ctc_logits():
+                with torch.no_grad():
+                    return self.eng.ctc_lo.fwd(enc.reshape(B * T, -1).contiguous()).view(B, T, -1)
+            return model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens)
+        return self._live_only(timestamps, search)
 
     def finish(self, beam_size=5, **kw):
         """model.transcribe(...) of the pushed features under the same decoding chunk mask, computed from the streamed encoder output
@@ -254,7 +270,11 @@ class StreamingEncoder:
         re-ranked by the decoder (_finish_rescore); beam_size does not apply, the list is the stream's."""
         if kw.get("joint") == "ctc_rescore":
             return self._finish_rescore(ctc_weight=kw.get("ctc_weight"), timestamps=kw.get("timestamps", True))
-        enc, lens = self.encoder_output()
-        wave = torch.cat(self.feats, dim=1)
-        with self.model.given_encoder_output(enc):
-            return self.model.transcribe(Pack(wave=wave, wave_len=lens), beam_size=beam_size, **kw)
+        all_enc, all_lens = self.encoder_output()
+        all_wave = torch.cat(self.feats, dim=1)
+
+        def search(rows):
+            enc, lens, wave = (all_enc, all_lens, all_wave) if len(rows) == self.B else (all_enc[rows].contiguous(), all_lens[rows], all_wave[rows].contiguous())
+            with self.model.given_encoder_output(enc):
+                return self.model.transcribe(Pack(wave=wave, wave_len=lens), beam_size=beam_size, **kw)
+        return self._live_only(kw.get("timestamps", True), search)

@@ -821,6 +821,34 @@ int asr_stream_logmel(const float* wav_ring, const int32_t* par, const float* wi
 int asr_stream_norm_lfr(const float* feat_ring, const int32_t* par, const float* mean, const float* istd, void* out,
                         int B, int C, int fcap, int n_mels, int m, int n, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Kaldi fbank front end: the features of compute-fbank-feats / torchaudio.compliance.kaldi.fbank / kaldi-native-fbank
+ * with WeNet's settings (25 ms / 10 ms at 16 kHz, dither 0, snip_edges, remove_dc_offset, Povey window, no energy column),
+ * as the alternative to asr_logmel_fwd.
+ * Stands in for:  nothing in the reference (its features are asr_logmel_fwd's): parity unpinned by Kaldi's binaries;
+ *                 the definition is restated in float64 in tests/fbank_ref.py.
+ *
+ * asr_fbank_fwd: wav (B, Smax) f32, wav_len (B) int32 samples, taken as min(max(wav_len[b], 0), Smax).  Utterance b has
+ * T_b = min(1 + (len - 400) / 160, Tmax) frames, none for len < 400 (a smaller Tmax truncates); frame t is samples
+ * 160 t .. 160 t + 399 and nothing else: no padding at either end, trailing samples that fill no frame are dropped.
+ * Per frame: x = wav_scale * sample; subtract the frame's mean; y[n] = x[n] - preemph x[n - 1] (y[0] = x[0] - preemph x[0]);
+ * times window[n]; zero-padded 512-point power spectrum, bins 0 .. 255; feat = log(max(power x melfb, FLT_EPSILON)).
+ * feat: (B, Tmax, n_mels) f32, frames t >= T_b written as 0.  window: (400) f32; melfb: (256, n_mels) f32.
+ * A frame's bits depend on its 400 samples only, not on the batch, tile or row it is computed in.
+ * The normalisation entry points above count frames as 1 + wav_len / 160: hand them 160 (T_b - 1) + 1 (0 for T_b = 0).
+ *
+ * asr_stream_fbank: the streaming twin on the rings of the streaming front end above.  par (B, 2) = {t_begin, n_new}: frames
+ * t_begin .. t_begin + n_new - 1 (n_new <= max_new <= fcap) by the same tile body - bit for bit the offline frames.  No
+ * length is passed: the ring must hold samples 160 t_begin .. 160 (t_begin + n_new - 1) + 399.  wav_ring (B, scap) f32 and
+ * feat_ring (B, fcap, n_mels) f32 as above; refused with ASR_EINVAL unless scap is a power of two of at least 1024, fcap a
+ * power of two, 1 <= max_new <= fcap, n_mels >= 1 and 1 <= B <= 65535.
+ */
+int asr_fbank_fwd(const float* wav, const int32_t* wav_len, const float* window, const float* melfb, float* feat,
+                  int B, int Smax, int Tmax, int n_mels, float wav_scale, float preemph, void* stream);
+int asr_stream_fbank(const float* wav_ring, const int32_t* par, const float* window, const float* melfb,
+                     float* feat_ring, int B, int max_new, int scap, int fcap, int n_mels, float wav_scale,
+                     float preemph, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

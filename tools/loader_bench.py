@@ -11,7 +11,10 @@ python tools/loader_bench.py --reverb_fft [--out=profiles/reverb_fft_bench.json]
 the torch.fft stand-in at 256 .. 65536 taps, same protocol, and the waveform-fed joint step with rir_method direct and fft at 4096 taps.
 python tools/loader_bench.py --resample [--out=profiles/resample_bench.json]: asr_resample_fwd on B = 32 x 5 s at 8, 44.1 and 48 kHz beside a
 device-to-device copy of its bytes and the strided conv1d polyphase form in torch, the waveform-fed joint step from a 16 kHz corpus (resample
-off and on) and from a 48 kHz one, alternated, and the host time of StreamResampler.push for one 480 ms block."""
+off and on) and from a 48 kHz one, alternated, and the host time of StreamResampler.push for one 480 ms block.
+python tools/loader_bench.py --fbank [--out=profiles/fbank_bench.json]: asr_fbank_fwd (Kaldi fbank) beside asr_logmel_fwd on the same batch of
+B = 32 x 5 s at 80 bins, a device-to-device copy of the same bytes, and a torch stand-in (unfold, the frame arithmetic, torch.fft.rfft,
+matmul, log); then push_audio of one 480 ms block with each front end (tools/stream_frontend_bench.py)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -19,11 +22,13 @@ import torch
 from asr_chinese_e2e_amd import Models
 from asr_chinese_e2e_amd.data_handler import AudioParser, BucketedWaveLoader, Vocab, WaveDataset
 from asr_chinese_e2e_amd.Trainer import FusedAdam, NoamOpt
+
 SPEED = next((a for a in sys.argv[1:] if a.startswith("--speed_perturb")), None)
 NOISE_REVERB = any(a == "--noise_reverb" for a in sys.argv[1:])
 REVERB_FFT = any(a == "--reverb_fft" for a in sys.argv[1:])
 RESAMPLE = any(a == "--resample" for a in sys.argv[1:])
-JOINT = SPEED is not None or NOISE_REVERB or REVERB_FFT or RESAMPLE or (len(sys.argv) > 1 and sys.argv[1] == "joint")
+FBANK = any(a == "--fbank" for a in sys.argv[1:])
+JOINT = SPEED is not None or NOISE_REVERB or REVERB_FFT or RESAMPLE or FBANK or (len(sys.argv) > 1 and sys.argv[1] == "joint")
 B, S, NB = 32, 16000 * 5, 40
 rng = np.random.RandomState(0)
 vocab = Vocab.synthetic(4232)
@@ -416,6 +421,61 @@ def resample_bench():
     print("wrote", out_path)
 
 
+def fbank_bench():
+    import json
+    from asr_chinese_e2e_amd import kernels as K
+    out_path = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--out=")), "profiles/fbank_bench.json")
+    B, S, n_mels = 32, 16000 * 5, 80
+    wav = torch.from_numpy((np.random.RandomState(0).randn(B, S) * 0.1).astype(np.float32)).cuda()
+    wl = torch.full((B,), S, dtype=torch.int32, device="cuda")
+    ref, kal = AudioParser(n_mels=n_mels, lfr_m=1, lfr_n=1, device="cuda"), AudioParser(n_mels=n_mels, lfr_m=1, lfr_n=1, device="cuda", frontend="kaldi")
+    T_ref, T_kal = ref.max_frames(S), kal.max_frames(S)
+    f_ref, f_kal = torch.empty(B, T_ref, n_mels, device="cuda"), torch.empty(B, T_kal, n_mels, device="cuda")
+    half = (B * S + B * T_kal * n_mels) // 2                                      # a copy of `half` floats reads and writes the fbank kernel's bytes in all
+    src, dst = torch.randn(half, device="cuda"), torch.empty(half, device="cuda")
+    win64, fb64 = kal.window.double(), kal.melfb.double()
+
+    def stand_in(dtype=torch.float32):
+        w, fb = (win64, fb64) if dtype == torch.float64 else (kal.window, kal.melfb)
+        x = (wav.to(dtype) * 32768.0).unfold(1, 400, 160)                         # (B, T, 400) frames, snip_edges
+        x = x - x.mean(dim=2, keepdim=True)
+        x = (x - 0.97 * torch.cat([x[:, :, :1], x[:, :, :-1]], dim=2)) * w
+        p = torch.fft.rfft(x, n=512, dim=2)[:, :, :256].abs() ** 2
+        return torch.log(torch.clamp(p @ fb, min=2.0 ** -23))
+
+    def timed(fn, reps=20, warm=3):
+        for _ in range(warm): fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps): fn()
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3
+    contenders = dict(fbank_kernel=lambda: kal.features(wav, wl, T_kal, feat=f_kal), logmel_kernel=lambda: ref.features(wav, wl, T_ref, feat=f_ref),
+                      d2d_copy_same_bytes=lambda: dst.copy_(src), torch_stand_in=stand_in)
+    contenders["fbank_kernel"]()
+    diff = float((f_kal.double() - stand_in(torch.float64)).abs().max())           # the two computations agree (log domain)
+    us = {name: [] for name in contenders}
+    for _ in range(3):                                                            # alternated
+        for name, fn in contenders.items():
+            us[name].append(timed(fn))
+    res = dict(device=torch.cuda.get_device_name(0), B=B, samples=S, n_mels=n_mels, frames_fbank=T_kal, frames_logmel=T_ref,
+               bytes_read_plus_written=8 * half, max_abs_log_diff_vs_torch_float64=diff)
+    for name, v in us.items():
+        res[name + "_us"], res[name + "_us_median"] = v, float(np.median(v))
+    res["fbank_over_logmel"] = res["fbank_kernel_us_median"] / res["logmel_kernel_us_median"]
+    res["timing"] = ("HIP events around 20 back-to-back calls after 3 warm-up calls, 3 rounds alternating the contenders in one process; torch stand-in = "
+                     "unfold, mean removal, pre-emphasis, window, torch.fft.rfft at 512 points, |.|^2, matmul with the banks, clamp, log, in fp32")
+    print(json.dumps({k: v for k, v in res.items() if k.endswith("_median") or k in ("fbank_over_logmel", "max_abs_log_diff_vs_torch_float64")}), flush=True)
+    from tools import stream_frontend_bench as SB
+    res["push_audio"] = {f: SB.run(50, f) for f in ("reference", "kaldi")}
+    print(json.dumps({f: {b: r[b]["frontend_ms"] for b in ("B=1", "B=32")} for f, r in res["push_audio"].items()}), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out_path)
+
+
 if SPEED is not None:
     speed_bench()
     sys.exit(0)
@@ -427,6 +487,9 @@ if REVERB_FFT:
     sys.exit(0)
 if NOISE_REVERB:
     noise_reverb_bench()
+    sys.exit(0)
+if FBANK:
+    fbank_bench()
     sys.exit(0)
 
 

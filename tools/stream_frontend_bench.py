@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Streaming waveform front end: what push_audio of one chunk's worth of audio costs, one JSON object on stdout.
 
-  python tools/stream_frontend_bench.py [--reps 50]
+  python tools/stream_frontend_bench.py [--reps 50] [--frontend reference|kaldi|both]
 
 C = 16, LFR 4/3, n_mels = 80 (one chunk = 16 * 3 * 160 = 7680 samples = 0.48 s of audio), the 6-layer bf16 joint model of
 tools/chunk_bench.py with a 320-wide input, B = 1 and B = 32, over a 31-chunk utterance, host wall time per call as in
@@ -13,6 +13,7 @@ synchronised for the measurement):
 * push_alone_ms: StreamingEncoder.push on precomputed features (the figure of tools/chunk_bench.py, at this model's input width);
 * parse_batch_5s_us: offline AudioParser.parse_batch of B x 5 s under global CMVN (device events, median of --reps);
 * rtf:           push_audio_ms / 480 ms of audio per utterance - the share of real time one session (B = 1) or 32 of them take.
+--frontend kaldi measures a parser of Kaldi fbank features instead; both: one object per front end, {"reference": .., "kaldi": ..}.
 """
 import argparse
 import json
@@ -41,7 +42,15 @@ def med(v):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--frontend", choices=("reference", "kaldi", "both"), default="reference")
     a = ap.parse_args()
+    if a.frontend == "both":
+        print(json.dumps({f: run(a.reps, f) for f in ("reference", "kaldi")}))
+    else:
+        print(json.dumps(run(a.reps, a.frontend)))
+
+
+def run(reps, frontend):
     from asr_chinese_e2e_amd import Models
     from asr_chinese_e2e_amd.data_handler import AudioParser, StreamingFrontEnd, Vocab
     M = Models.TransformerOffical
@@ -50,10 +59,10 @@ def main():
     torch.manual_seed(0)
     model = M(cfg, Vocab.synthetic(4232)).to(DEV).eval()
     parser = AudioParser(n_mels=N_MELS, lfr_m=LFR_M, lfr_n=LFR_N, device=DEV, norm="global",
-                         cmvn=(np.full(N_MELS, -1.0), np.full(N_MELS, 0.4)))
+                         cmvn=(np.full(N_MELS, -1.0), np.full(N_MELS, 0.4)), frontend=frontend)
     block = C * LFR_N * 160
     res = {"device": torch.cuda.get_device_name(0), "C": C, "lfr": [LFR_M, LFR_N], "n_mels": N_MELS, "block_samples": block,
-           "block_audio_ms": block / 16.0}
+           "block_audio_ms": block / 16.0, "frontend": frontend}
     for B in (1, 32):
         wav = torch.randn(B, block * CHUNKS, device=DEV)
         blocks = [wav[:, k * block:(k + 1) * block].contiguous() for k in range(CHUNKS)]
@@ -95,9 +104,9 @@ def main():
         # the first block completes no chunk (a row needs frames past it): steady state is every block after it
         res[f"B={B}"] = {"blocks": CHUNKS, "chunks_per_block": chunks, "frontend_ms": med(t_fe[1:]), "push_ms": med(t_push), "push_audio_ms": med(t_both[1:]),
                          "push_audio_max_ms": round(max(t_both[1:]), 3), "push_alone_ms": med(t_alone),
-                         "parse_batch_5s_us": round(time_us(lambda: parser.parse_batch(wav5, wl5, torch.bfloat16), a.reps), 2),
+                         "parse_batch_5s_us": round(time_us(lambda: parser.parse_batch(wav5, wl5, torch.bfloat16), reps), 2),
                          "rtf": round(statistics.median(t_both[1:]) / (block / 16.0), 5)}
-    print(json.dumps(res))
+    return res
 
 
 if __name__ == "__main__":

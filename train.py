@@ -25,6 +25,8 @@ Differences that come with the MI355X path:
     auto: at most 65536, 4.1 s at 16 kHz);
   * `--cmvn=stats.npz` normalises the features of every part per mel bin with corpus statistics (tools/compute_cmvn.py) instead of
     per utterance: the causal features a streaming model is trained on (transcribe.py --stream=1 --cmvn=...);
+  * `--frontend=kaldi` computes Kaldi fbank features (the front end of the Kaldi / WeNet / ESPnet / k2 recipes) instead of the
+    reference's log-mel; statistics for `--cmvn` must then come from the same front end (tools/compute_cmvn.py --frontend=kaldi);
   * `--resample=1` accepts files at 8, 11.025, 12, 22.05, 24, 32, 44.1, 48, 88.2 and 96 kHz (corpus, noise clips, responses) and converts
     them to 16 kHz on the GPU (data_handler/resample.py); without it a file at another rate raises, as before;
   * `--synthetic=N` trains on N synthetic AISHELL-1-shaped utterances (no dataset ships with this repository);
@@ -72,6 +74,7 @@ class TrainConfig(DataConfigAiShell1):      # main.py:14-36
     synthetic_vocab = 4232
     trainer = "Trainer11"
     cmvn = ""                               # --cmvn=stats.npz: global CMVN statistics for train, dev and test; empty = per-utterance normalisation
+    frontend = "reference"                  # --frontend=kaldi: Kaldi fbank features (AudioParser(frontend="kaldi")) for train, dev and test
     noise_list = ""                         # --noise_list=FILE: wav paths of noise clips, one per line (train part only); empty = off
     rir_list = ""                           # --rir_list=FILE: wav paths of room impulse responses, one per line (train part only); empty = off
     noise_prob = 0.5                        # probability that an utterance gets noise / a response, drawn per epoch
@@ -185,7 +188,7 @@ def train(**kwargs):                        # main.py:55-98
         vocab = Vocab.load(config.vocab_path)
         common = dict(collector_path=config.collector_path, vocab=vocab, sample_rate=config.sample_rate, window_size=config.window_size,
                       n_mels=config.n_mels, predump=config.predump, use_old=config.use_old, lfr_m=config.lfr_m, lfr_n=config.lfr_n,
-                      rank=rank, world=world, cmvn=config.cmvn or None, resample=bool(int(config.resample)))
+                      rank=rank, world=world, cmvn=config.cmvn or None, resample=bool(int(config.resample)), frontend=str(config.frontend))
         train_iter = build_dataloader(batch_size=config.batch_size, part="train", augment=config.augment, speed_perturb=speed_factors(config.speed_perturb),
                                       noise=path_list(config.noise_list), rir=path_list(config.rir_list), noise_prob=float(config.noise_prob),
                                       rir_prob=float(config.rir_prob), snr_db=snr_range(config.snr_db), rir_method=str(config.rir_method),

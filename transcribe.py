@@ -27,6 +27,9 @@ trained with rebuild it.  Inference flags:
                  (default 10) best classes of each frame runs with the audio; the per-chunk line becomes {"file", "chunk", "partial",
                  "stable"}: the best hypothesis now (revisable) and the part of it no later chunk can change.  The final line then
                  comes from finish(joint="ctc_rescore"): the decoder re-ranks the streamed n-best (a CTC-only model keeps the CTC best)
+  --frontend     reference (default: the reference's log-mel) or kaldi (Kaldi fbank, the features of the Kaldi / WeNet / ESPnet / k2
+                 recipes: for models trained with train.py --frontend=kaldi, and CMVN files of those features); token times are frame
+                 centres, which for kaldi lie 12.5 ms later than the reference's for the same frame index.
   --cmvn         global CMVN statistics (tools/compute_cmvn.py) the model was trained with (train.py --cmvn); empty = the
                  per-utterance normalisation
   --resample     1 = files at 8, 11.025, 12, 22.05, 24, 32, 44.1, 48, 88.2 or 96 kHz are converted to 16 kHz on the GPU (one launch per
@@ -53,7 +56,7 @@ from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
 from asr_chinese_e2e_amd.data_handler import resample as resample_mod  # noqa: E402
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk")
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend")
 
 
 def _finite(x):
@@ -153,7 +156,8 @@ def transcribe(**flags):
     model = load_model(config, vocab, cli.get("ckpt"))
     files = audio_files(cli)
     parser = AudioParser(sample_rate=config.sample_rate, n_mels=config.n_mels, window_size=config.window_size,
-                         lfr_m=config.lfr_m, lfr_n=config.lfr_n, **parser_norm(cmvn_path(cli)))
+                         lfr_m=config.lfr_m, lfr_n=config.lfr_n, frontend=str(cli.get("frontend", "reference")), **parser_norm(cmvn_path(cli)))
+    shift_s = parser.frame_centre_sample(0) / float(config.sample_rate)      # token times are frame centres: a Kaldi frame's lies 12.5 ms later
     beam = int(cli.get("beam_size", 5))
     bs = max(1, int(cli.get("batch_size", 16)))
     timestamps = bool(cli.get("timestamps", model.use_ctc))
@@ -216,7 +220,7 @@ def transcribe(**flags):
             for t in r["tokens"] or ():          # the last encoder frame may reach past the end of the audio
                 for k in ("start_s", "end_s"):
                     if t[k] is not None:
-                        t[k] = min(t[k], dur)
+                        t[k] = min(t[k] + shift_s, dur)
             line = {"file": path, "duration_s": dur, "text": r["text"], "ids": r["ids"],
                     "score": _finite(r["score"]), "tokens": r["tokens"]}
             if sr != config.sample_rate:
