@@ -340,6 +340,14 @@ class _SpeechTransformer(BaseModel):
         from ..stream import StreamingEncoder
         return StreamingEncoder(self, batch_size, parser=parser, source_rate=source_rate, search=search, beam_size=beam_size, frame_topk=frame_topk)
 
+    def sessions(self, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None):
+        """`slots` independent streaming sessions in one batch (sessions.Sessions): each slot is opened, fed (push / push_audio),
+        closed, finished and reopened at its own pace - open(b), push(feats, n_valid, final), finish(b) - and with endpoint={...} the
+        CTC endpoint rules report per slot when its speaker has stopped (endpoints()).  parser, search, beam_size, frame_topk as
+        stream()'s; only 16 kHz audio."""
+        from ..sessions import Sessions
+        return Sessions(self, slots, parser=parser, search=search, beam_size=beam_size, frame_topk=frame_topk, endpoint=endpoint, source_rate=source_rate)
+
     def forward(self, input):
         """transformer_official.py:68-81 (inference-style forward; no gradients).  A batch without a transcript (only wave / wave_len)
         gets the encoder output and the CTC logits; pred / gold need tgt_for_input."""

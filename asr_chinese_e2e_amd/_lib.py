@@ -79,6 +79,7 @@ SIGNATURES = {
     "asr_get_deterministic": (I, []),
     "asr_set_deterministic": (I, [I]),
     "asr_add_ln_fwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, F, U, I, I, P]),
+    "asr_add_ln_slots_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "asr_add_ln_bwd_workspace_bytes": (Z, [I, I]),
     "asr_add_ln_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, Z, I, I, I, F, U, I, I, P]),
     "asr_add_ln_bwd_reduce_batched": (I, [P, I, I, P]),
@@ -106,6 +107,7 @@ SIGNATURES = {
     "asr_ctc_prefix_beam_stream_workspace_bytes": (Z, [I, I, I]),
     "asr_ctc_prefix_beam_state_init": (I, [P, P, I, I, I, P]),
     "asr_ctc_prefix_beam_chunk": (I, [P, P, P, P, P, P, Z, P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "asr_ctc_prefix_beam_state_reset": (I, [P, P, P, I, I, I, P]),
     "asr_beam_step": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "asr_cache_gather": (I, [P, P, P, I, I, I, I, I, I, P]),
     "asr_ctc_prefix_logprobs": (I, [P, P, I, I, I, I, I, P]),
@@ -157,6 +159,10 @@ SIGNATURES = {
     "asr_stream_norm_lfr": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "asr_fbank_fwd": (I, [P, P, P, P, P, I, I, I, I, F, F, P]),
     "asr_stream_fbank": (I, [P, P, P, P, P, I, I, I, I, I, F, F, P]),
+    "asr_slot_rows_put": (I, [P, P, P, P, I, I, I, I, I, I, P]),
+    "asr_slot_rows_slide": (I, [P, P, P, P, I, I, I, I, I, P]),
+    "asr_ctc_frame_best_blank": (I, [P, P, P, P, I, I, I, I, I, I, P]),
+    "asr_session_ctc_step": (I, [P, P, P, P, P, P, I, I, I, F, P]),
 }
 
 

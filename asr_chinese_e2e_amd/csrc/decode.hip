@@ -520,9 +520,8 @@ constexpr int PB_STATE_HDR = 4;
 
 __host__ __device__ inline size_t pb_state_bytes1(int beam) { return (size_t)PB_STATE_HDR * 4 + (size_t)beam * (4 * 4 + 2 * 8); }
 
-__global__ __launch_bounds__(64) void ctc_prefix_beam_state_init_kernel(char* state, int32_t* nodes, int B, int beam, int T_cap) {
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= B) return;
+// The empty-prefix state of utterance b and its trie's root: what the init kernel leaves for every utterance and the reset kernel for the flagged ones.
+__device__ __forceinline__ void pb_state_init_one(char* state, int32_t* nodes, int b, int beam, int T_cap) {
     const size_t cap_nodes = (size_t)T_cap * beam + 1;
     int32_t* hdr = (int32_t*)(state + (size_t)b * pb_state_bytes1(beam));
     int32_t* ent = hdr + PB_STATE_HDR;
@@ -534,6 +533,19 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_state_init_kernel(char* st
     }
     int32_t* npar = nodes + (size_t)b * 2 * cap_nodes;
     npar[0] = -1; npar[cap_nodes] = -1;
+}
+
+__global__ __launch_bounds__(64) void ctc_prefix_beam_state_init_kernel(char* state, int32_t* nodes, int B, int beam, int T_cap) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    pb_state_init_one(state, nodes, b, beam, T_cap);
+}
+
+// only the utterances with flags[b] != 0 (independent sessions: a slot that is reopened); the others keep every byte
+__global__ __launch_bounds__(64) void ctc_prefix_beam_state_reset_kernel(char* state, int32_t* nodes, const int32_t* __restrict__ flags, int B, int beam, int T_cap) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B || flags[b] == 0) return;
+    pb_state_init_one(state, nodes, b, beam, T_cap);
 }
 
 __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* __restrict__ vals, const int32_t* __restrict__ ids, const float* __restrict__ blank_lp,
@@ -629,6 +641,17 @@ extern "C" int asr_ctc_prefix_beam_state_init(void* state, void* ws, int B, int 
     if (((uintptr_t)state % 8) || ((uintptr_t)ws % 4)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_state_init: misaligned pointer (state: 8 bytes, workspace: 4)");
     ctc_prefix_beam_state_init_kernel<<<ceil_div(B, 64), 64, 0, (hipStream_t)stream>>>((char*)state, (int32_t*)ws, B, beam, T_cap);
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_state_init");
+    return ASR_OK;
+}
+
+extern "C" int asr_ctc_prefix_beam_state_reset(void* state, void* ws, const int32_t* flags, int B, int beam, int T_cap, void* stream) {
+    if (!state || !ws || !flags) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_state_reset: null pointer");
+    if (B <= 0 || beam <= 0 || beam > PB_MAX_BEAM || T_cap <= 0 || (size_t)T_cap * beam + 1 > (size_t)INT_MAX)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_state_reset: bad shape B=%d beam=%d (<= %d) T_cap=%d", B, beam, PB_MAX_BEAM, T_cap);
+    if (((uintptr_t)state % 8) || ((uintptr_t)ws % 4) || ((uintptr_t)flags % 4))
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_state_reset: misaligned pointer (state: 8 bytes, workspace and flags: 4)");
+    ctc_prefix_beam_state_reset_kernel<<<ceil_div(B, 64), 64, 0, (hipStream_t)stream>>>((char*)state, (int32_t*)ws, flags, B, beam, T_cap);
+    ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_state_reset");
     return ASR_OK;
 }
 

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(LN_WAVES* WAVE) void add_ln_fwd_kernel(
     const T* __restrict__ x, const T* __restrict__ res, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ pe, const int32_t* __restrict__ lens,
     T* __restrict__ y, T* __restrict__ xhat, float* __restrict__ rstd_out, int rows, int T_, int d,
-    uint32_t seed, uint32_t thr, float dscale) {
+    uint32_t seed, uint32_t thr, float dscale, const int32_t* __restrict__ pe_off, int pe_rows) {
     using RS = RowSlice<T, N, VEC8>;
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // uniform: row indices, and with them lens[b], live in scalar registers
     float g[N], bt[N];
@@ -177,7 +177,10 @@ __global__ __launch_bounds__(LN_WAVES* WAVE) void add_ln_fwd_kernel(
             }
             if (pe) {
                 float p[N];
-                RS::loadf(pe + (size_t)t * d, d, lane, p);
+                // pe_off (independent sessions, asr_add_ln_slots_fwd): utterance b's table starts at row pe_off[b] - a wave-uniform load, as
+                // lens[b]; the row is clamped into the table (the caller has refused such an offset; a wrong one reads nothing outside)
+                const int pt = pe_off ? min(max(pe_off[b] + t, 0), pe_rows - 1) : t;
+                RS::loadf(pe + (size_t)pt * d, d, lane, p);
 #pragma unroll
                 for (int i = 0; i < N; ++i) out[i] += p[i];
             }
@@ -323,11 +326,12 @@ extern "C" size_t asr_add_ln_bwd_workspace_bytes(int rows, int d) {
 template <typename T, int DROP>
 static int launch_ln_fwd(const void* x, const void* res, const float* gamma, const float* beta,
                          const float* pe, const int32_t* lens, void* y, void* xhat, float* rstd,
-                         int rows, int T_, int d, uint32_t seed, uint32_t thr, float dscale, hipStream_t st) {
+                         int rows, int T_, int d, uint32_t seed, uint32_t thr, float dscale, hipStream_t st,
+                         const int32_t* pe_off = nullptr, int pe_rows = 0) {
     const int grid = ln_grid_fwd(rows);
 #define LN_FWD(N, V)                                                                              \
     add_ln_fwd_kernel<T, N, V, DROP><<<grid, LN_WAVES * WAVE, 0, st>>>(                            \
-        (const T*)x, (const T*)res, gamma, beta, pe, lens, (T*)y, (T*)xhat, rstd, rows, T_, d, seed, thr, dscale)
+        (const T*)x, (const T*)res, gamma, beta, pe, lens, (T*)y, (T*)xhat, rstd, rows, T_, d, seed, thr, dscale, pe_off, pe_rows)
     if (d % 512 == 0 && d <= 2048) {
         switch (d / 512) {
             case 1: LN_FWD(8, true); break;
@@ -366,6 +370,26 @@ extern "C" int asr_add_ln_fwd(const void* x, const void* res, const float* gamma
     else { if (mode == 0) LN_FWD_D(bf16_t, 0); else if (mode == 1) LN_FWD_D(bf16_t, 1); else LN_FWD_D(bf16_t, 2); }
 #undef LN_FWD_D
     ASR_CHECK_LAUNCH("asr_add_ln_fwd");
+    return ASR_OK;
+}
+
+// The sessions' input LayerNorm: asr_add_ln_fwd's kernel instantiation (no residual, no dropout) with each utterance's positional rows
+// taken from its own offset - the same launch shape and arithmetic as the lock-step stream's call, so the same bits.
+extern "C" int asr_add_ln_slots_fwd(void* x, const float* gamma, const float* beta, const float* pe, const int32_t* pe_off, const int32_t* lens,
+                                    void* y, float* rstd, int slots, int T, int d, int pe_rows, int dtype, void* stream) {
+    if (!x || !gamma || !beta || !pe || !pe_off || !lens || !y || !rstd) ASR_FAIL(ASR_EINVAL, "asr_add_ln_slots_fwd: null pointer");
+    if (slots <= 0 || T <= 0 || d <= 0 || d > 2048 || (size_t)slots * T > (size_t)INT_MAX) ASR_FAIL(ASR_EINVAL, "asr_add_ln_slots_fwd: bad shape slots=%d T=%d d=%d", slots, T, d);
+    if (pe_rows < T) ASR_FAIL(ASR_EINVAL, "asr_add_ln_slots_fwd: the positional table has %d rows, a chunk has %d", pe_rows, T);
+    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "asr_add_ln_slots_fwd: dtype %d", dtype);
+    if (x == y) ASR_FAIL(ASR_EINVAL, "asr_add_ln_slots_fwd: y must not be x (x receives the normalised rows)");
+    // the 512-column paths move 16 / 32 bytes per lane
+    if (d % 512 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)pe) % 16))
+        ASR_FAIL(ASR_EINVAL, "asr_add_ln_slots_fwd: misaligned pointer (16 bytes when d is a multiple of 512)");
+    if (((uintptr_t)pe_off | (uintptr_t)lens | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)pe | (uintptr_t)rstd) % 4) ASR_FAIL(ASR_EINVAL, "asr_add_ln_slots_fwd: misaligned pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == ASR_F32) launch_ln_fwd<float, 0>(x, nullptr, gamma, beta, pe, lens, y, x, rstd, slots * T, T, d, 0u, 0u, 1.f, st, pe_off, pe_rows);
+    else launch_ln_fwd<bf16_t, 0>(x, nullptr, gamma, beta, pe, lens, y, x, rstd, slots * T, T, d, 0u, 0u, 1.f, st, pe_off, pe_rows);
+    ASR_CHECK_LAUNCH("asr_add_ln_slots_fwd");
     return ASR_OK;
 }
 

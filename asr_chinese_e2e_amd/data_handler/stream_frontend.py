@@ -62,14 +62,17 @@ class StreamingFrontEnd:
     """push_audio(pcm (B, S), n_samples, final) -> list of (feats (B, C, lfr_m * n_mels) in `dtype`, n_valid list of B ints): the encoder
     chunks that became complete.  The B utterances advance in lock-step (one chunk index for all, as StreamingEncoder's frame offset is
     shared): a chunk leaves when every utterance that is still open has C rows ready; a closed utterance contributes what it has left
-    (n_valid < C, then 0).  Independent sessions use B = 1.  sample_cap: samples per ring (a power of two); longer blocks are worked
+    (n_valid < C, then 0).  independent=True (sessions.py) lifts the lock-step: a chunk leaves whenever one utterance has C rows ready or
+    is closed with rows left, the others ride along with n_valid 0 and keep their rows - per utterance the chunks of a B = 1 front
+    end - and reset(b) starts utterance b again; push_audio then returns (feats, n_valid, done) with done[b] = utterance b's last row
+    left with this chunk (feats None for an empty chunk that only carries an end).  sample_cap: samples per ring (a power of two); longer blocks are worked
     through in pieces.  An utterance that runs ahead of one that stalls the chunk keeps its log-mel frames (the frame rings are re-laid
     at a larger size), up to max_frames of them (163 s by default): past that push_audio raises before it takes anything of the call.
 
     push_audio first plans the whole call on the host (plan(): which pieces, frames and chunks, from the counters alone), then
     launches what the plan lists and commits the counters - so a refused call leaves the front end as it was."""
 
-    def __init__(self, parser, B, C, dtype=torch.float32, sample_cap=16384, max_frames=16384):
+    def __init__(self, parser, B, C, dtype=torch.float32, sample_cap=16384, max_frames=16384, independent=False):
         if getattr(parser, "norm", None) != "global":
             raise ValueError("streaming needs a parser with norm='global': per-utterance normalisation needs the whole utterance "
                              "before its first frame (AudioParser(norm='global', cmvn=...))")
@@ -78,6 +81,7 @@ class StreamingFrontEnd:
         if sample_cap < 1024 or sample_cap & (sample_cap - 1):
             raise ValueError(f"sample_cap must be a power of two of at least 1024, got {sample_cap}")
         self.parser, self.B, self.C, self.dtype = parser, int(B), int(C), dtype
+        self.independent = bool(independent)      # independent sessions (sessions.py): every utterance leaves at its own cadence
         self.m, self.n, self.n_mels = parser.lfr_m, parser.lfr_n, parser.n_mels
         self.dev = parser.window.device
         self.scap = int(sample_cap)
@@ -129,17 +133,47 @@ class StreamingFrontEnd:
                     next_frame[b] += new[b]
             while True:
                 ready = [rows_ready(next_frame[b], m, n, closed[b]) - next_row[b] for b in range(B)]
+                if self.independent:
+                    # a chunk runs whenever one utterance has C rows, or is closed with rows left; the others ride along with no row and
+                    # keep theirs: per utterance this is the cadence of a front end that serves it alone.  done: the utterances whose
+                    # last row leaves with this chunk (they are closed and nothing is left).
+                    nv = [min(C, r) if (r >= C or (closed[b] and r > 0)) else 0 for b, r in enumerate(ready)]
+                    if not any(nv):
+                        break
+                    done = [closed[b] and nv[b] > 0 and nv[b] == ready[b] for b in range(B)]
+                    acts.append(("chunk", [[next_row[b], nv[b], next_frame[b] if closed[b] else K.STREAM_OPEN] for b in range(B)], nv, done))
+                    for b in range(B):
+                        next_row[b] += nv[b]
+                    continue
                 if not any(r > 0 for r in ready) or not all(closed[b] or ready[b] >= C for b in range(B)):
                     break
                 nv = [min(C, r) for r in ready]
                 acts.append(("chunk", [[next_row[b], nv[b], next_frame[b] if closed[b] else K.STREAM_OPEN] for b in range(B)], nv))
                 for b in range(B):
                     next_row[b] += nv[b]
+        if self.independent:
+            # an utterance this call closes whose rows were all out before the close (it added none), or that never had one: an empty
+            # chunk carries its end to the consumer
+            done = [closed[b] and not self.closed[b] and not any(a[0] == "chunk" and a[3][b] for a in acts) for b in range(B)]
+            if any(done):
+                acts.append(("chunk", [[next_row[b], 0, next_frame[b] if closed[b] else K.STREAM_OPEN] for b in range(B)], [0] * B, done))
+            return acts, (received, closed, next_frame, next_row)
         # Kaldi: utterances of fewer than 400 samples have no frame.  When this call closes the last of them and no row has ever left,
         # one empty chunk tells the consumer that every utterance has ended (a reference utterance of any sample has a frame).
         if self.kaldi and all(closed) and not all(self.closed) and not any(next_row) and not any(a[0] == "chunk" for a in acts):
             acts.append(("chunk", [[0, 0, 0] for _ in range(B)], [0] * B))
         return acts, (received, closed, next_frame, next_row)
+
+    def reset(self, b):
+        """Utterance b starts again at sample 0 (independent sessions: its slot is reopened).  Only the host counters: after it every
+        sample and frame a kernel reads for b was written after the reset - stream_append writes [received, received + n), the
+        log-mel / fbank tile reads the samples of the frames it is asked for (all received; reflected at sample 0 and at the closed
+        end, never past them), and a tile row that is not asked for is computed from whatever its ring positions hold but never
+        stored; stream_norm_lfr reads frames [r n, r n + m) clamped to the closed utterance's last frame.  So no stale ring content
+        can reach a result, and the rings are not cleared."""
+        if not 0 <= b < self.B:
+            raise ValueError(f"reset: utterance {b} of {self.B}")
+        self.received[b], self.closed[b], self.next_frame[b], self.next_row[b] = 0, False, 0, 0
 
     def _grow_frames(self, cap, live):
         """The frame rings re-laid at capacity `cap`: frame t of [lo, hi) moves from slot t mod the old capacity to t mod cap."""
@@ -178,8 +212,10 @@ class StreamingFrontEnd:
                 K.stream_fbank(self.wav_ring, par, self.parser.window, self.parser.melfb, self.feat_ring, act[2], self.parser.wav_scale, self.parser.preemph)
             elif act[0] == "logmel":
                 K.stream_logmel(self.wav_ring, self._par(act[1]), self.parser.window, self.parser.melfb, self.feat_ring, act[2])
-            else:
+            elif any(act[2]) or not self.independent:
                 out.append((K.stream_norm_lfr(self.feat_ring, self._par(act[1]), self.parser.mean, self.parser.istd, self.m, self.n, self.C,
-                                              self.dtype), act[2]))
+                                              self.dtype),) + tuple(act[2:]))
+            else:      # independent: an empty chunk that only carries the end of some utterance - no features, no launch
+                out.append((None,) + tuple(act[2:]))
         self.received, self.closed, self.next_frame, self.next_row = after
         return out

@@ -473,13 +473,15 @@ def prefix_beam_unpack(buf, B, nbest, Lcap):
             buf[tok_n + len_n:tok_n + 2 * len_n].view(torch.float32).view(B, nbest), buf[tok_n + 2 * len_n:])
 
 
-def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, max_len=None, packed=False):
+def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, max_len=None, packed=False, nv_dev=None, extra_words=0):
     """One chunk of the resumable search: vals / ids (B*C, k), blank_lp (B*C) = the chunk's rows of ctc_frame_topk; n_valid = the
     frames of each utterance to consume (a list of B ints in [0, C]).  A chunk that would take an utterance past st.T_cap frames raises
     before anything is launched.  Returns (tokens (B, nbest, Lcap) int32, lengths (B, nbest) int32 with -1 for missing ranks, scores
     (B, nbest) f32, stable (B) int32 = the length of the prefix every beam entry shares) - views of one int32 buffer (prefix_beam_unpack);
     packed=True returns (that buffer, Lcap) instead, so that one copy brings all four to the host.  Lcap = max_len, by default the most
-    frames any utterance has consumed after this chunk: no prefix is longer than that."""
+    frames any utterance has consumed after this chunk: no prefix is longer than that.  nv_dev: n_valid as an int32 device tensor the
+    caller has uploaded already; extra_words (packed only): int32 words left free behind the results in the returned buffer, for
+    what else travels to the host in the same copy."""
     B, beam, k = st.B, st.beam, vals.shape[1]
     C, nbest = int(C), int(nbest)
     nv = [int(x) for x in n_valid]
@@ -492,15 +494,106 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
     _chk_f32(vals, blank_lp)
     _chk_i32(ids)
     Lcap = int(max(1, max(f + n for f, n in zip(st.frames, nv))) if max_len is None else max_len)
-    out = torch.zeros(B * (nbest * (Lcap + 2) + 1), dtype=torch.int32, device=vals.device)
-    out_tok, out_len, out_score, out_stable = prefix_beam_unpack(out, B, nbest, Lcap)
-    nv_dev = torch.tensor(nv, dtype=torch.int32, device=vals.device)
+    n_words = B * (nbest * (Lcap + 2) + 1)
+    out = torch.zeros(n_words + (int(extra_words) if packed else 0), dtype=torch.int32, device=vals.device)
+    out_tok, out_len, out_score, out_stable = prefix_beam_unpack(out[:n_words], B, nbest, Lcap)
+    if nv_dev is None:
+        nv_dev = torch.tensor(nv, dtype=torch.int32, device=vals.device)
+    _chk_i32(nv_dev)
+    assert nv_dev.numel() == B
     check(lib.asr_ctc_prefix_beam_chunk(_p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(), _p(out_tok), _p(out_len),
                                         _p(out_score), _p(out_stable), B, C, k, beam, nbest, Lcap, st.T_cap, int(blank), _stream()),
           "asr_ctc_prefix_beam_chunk")
     for b in range(B):
         st.frames[b] += nv[b]
     return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable)
+
+
+def ctc_prefix_beam_state_reset(st, flags, slots=()):
+    """Re-initialise the utterances of a PrefixBeamState whose flags[b] != 0 (flags: (B) int32 on the device; `slots`: the same
+    utterances as host ints, for the host-side frame counters): byte for byte what ctc_prefix_beam_state leaves for them."""
+    _chk_i32(flags)
+    assert flags.numel() == st.B
+    check(lib.asr_ctc_prefix_beam_state_reset(_p(st.state), _p(st.ws), _p(flags), st.B, st.beam, st.T_cap, _stream()), "asr_ctc_prefix_beam_state_reset")
+    for b in slots:
+        st.frames[int(b)] = 0
+
+
+# --------------------------------------------------------------------------------- independent sessions (csrc/session.hip)
+def add_ln_slots_fwd(x, gamma, beta, pe, pe_off, pe_off_host, lens, slots, T, y=None, rstd=None):
+    """y[b, t] = LN(x[b, t]) * gamma + beta + pe[pe_off[b] + t], rows t >= lens[b] zeroed (asr_add_ln_slots_fwd); x is overwritten with
+    the normalised rows, as add_ln_fwd(xhat=x) does.  pe_off, lens: (slots) int32 on the device; pe_off_host: the same offsets as host
+    ints - an offset that would leave the table raises before the launch."""
+    d = x.shape[-1]
+    assert x.is_contiguous() and x.numel() == slots * T * d
+    _chk_f32(gamma, beta, pe, rstd)
+    _chk_i32(pe_off, lens)
+    assert gamma.numel() == d and beta.numel() == d and pe.dim() == 2 and pe.shape[1] == d
+    assert pe_off.numel() == slots and lens.numel() == slots and len(pe_off_host) == slots
+    for b, o in enumerate(pe_off_host):
+        if o < 0 or o + T > pe.shape[0]:
+            raise ValueError(f"add_ln_slots_fwd: slot {b} at frame offset {o} with {T} frames leaves the positional table ({pe.shape[0]} rows)")
+    y = torch.empty_like(x) if y is None else y
+    rstd = torch.empty(slots * T, dtype=torch.float32, device=x.device) if rstd is None else rstd
+    assert y.is_contiguous() and y.shape == x.shape and y.dtype == x.dtype and y.data_ptr() != x.data_ptr() and rstd.numel() >= slots * T
+    check(lib.asr_add_ln_slots_fwd(_p(x), _p(gamma), _p(beta), _p(pe), _p(pe_off), _p(lens), _p(y), _p(rstd), int(slots), int(T), d, pe.shape[0], _dt(x),
+                                   _stream()), "asr_add_ln_slots_fwd")
+    return y
+
+
+def _slot_buffer(t, what):
+    assert t.dim() == 3 and t.is_contiguous(), f"{what} must be a dense (slots, cap, cols) buffer"
+    return t.shape
+
+
+def slot_rows_put(src, dst, start, n, C):
+    """dst[b, start[b] + t] = src[b * C + t] for t < n[b] (asr_slot_rows_put).  src: (slots * C, cols), rows may be a column slice of a
+    wider matrix; dst: (slots, cap, cols) dense; start, n: (slots) int32 on the device."""
+    slots, cap, cols = _slot_buffer(dst, "dst")
+    assert src.dim() == 2 and src.shape == (slots * C, cols) and src.stride(1) == 1 and src.dtype == dst.dtype
+    _chk_i32(start, n)
+    assert start.numel() == slots and n.numel() == slots
+    check(lib.asr_slot_rows_put(_p(src), _p(dst), _p(start), _p(n), slots, int(C), cap, cols, src.stride(0) if slots * C > 1 else cols, _dt(dst), _stream()),
+          "asr_slot_rows_put")
+    return dst
+
+
+def slot_rows_slide(src, dst, frm, count, max_count):
+    """dst[b, t] = src[b, frm[b] + t] for t < count[b] <= max_count (asr_slot_rows_slide); src, dst: two (slots, cap, cols) buffers."""
+    slots, cap, cols = _slot_buffer(src, "src")
+    assert _slot_buffer(dst, "dst") == (slots, cap, cols) and src.dtype == dst.dtype
+    _chk_i32(frm, count)
+    assert frm.numel() == slots and count.numel() == slots
+    check(lib.asr_slot_rows_slide(_p(src), _p(dst), _p(frm), _p(count), slots, int(max_count), cap, cols, _dt(dst), _stream()), "asr_slot_rows_slide")
+    return dst
+
+
+def ctc_frame_best_blank(logits, in_len=None, blank=0):
+    """logits (B, T, V) -> (path (B, T) int32 as ctc_frame_argmax, blank_lp (B, T) f32 as ctc_frame_topk's) in one pass per frame."""
+    B, T, V = logits.shape
+    ld = _frame_rows(logits)
+    _chk_i32(in_len)
+    assert in_len is None or in_len.numel() == B
+    path = torch.empty(B, T, dtype=torch.int32, device=logits.device)
+    blank_lp = torch.empty(B, T, dtype=torch.float32, device=logits.device)
+    check(lib.asr_ctc_frame_best_blank(_p(logits), _p(in_len), _p(path), _p(blank_lp), B, T, V, ld, int(blank), _dt(logits), _stream()),
+          "asr_ctc_frame_best_blank")
+    return path, blank_lp
+
+
+def session_ctc_step(path, blank_lp, n_valid, reset, state, C, silence_lp, blank=0, out=None):
+    """One tick of the per-slot CTC bookkeeping (asr_session_ctc_step): path (slots, C) int32 or None (beam sessions), blank_lp
+    (slots, C) f32, n_valid / reset (slots) int32, state (slots, 4) int32 (updated in place).  Returns out (slots, 4 + C) int32 =
+    {ids emitted, trailing silent frames, frames, decoded, ids...} on the device."""
+    slots = state.shape[0]
+    _chk_i32(path, n_valid, reset, state)
+    _chk_f32(blank_lp)
+    assert state.shape == (slots, 4) and blank_lp.numel() == slots * C and (path is None or path.numel() == slots * C)
+    assert n_valid.numel() == slots and reset.numel() == slots
+    out = torch.empty(slots, 4 + C, dtype=torch.int32, device=state.device) if out is None else out
+    check(lib.asr_session_ctc_step(_p(path), _p(blank_lp), _p(n_valid), _p(reset), _p(state), _p(out), slots, int(C), int(blank), float(silence_lp), _stream()),
+          "asr_session_ctc_step")
+    return out
 
 
 def beam_step(top_vals, top_ids, score, alive, last_tok, parent, rec_tok, rec_par, rec_end, rec_score, maxlen, alive_total, B, beam, step, eos):

@@ -1,0 +1,427 @@
+"""Independent streaming sessions in one batch (model.sessions(slots)): every slot of the batch holds a session that is opened, fed,
+closed, finished and reopened at its own pace, and CTC endpointing tells when a slot's speaker has stopped.
+
+model.stream(B) runs its B utterances in lock-step: one frame offset, one cadence, one start.  Here each slot b has its own frame
+offset (the positional-encoding row of its next frame), its own key cache length and its own CTC state; a tick (push) computes
+slots * C encoder rows - a slot that sits the tick out (n_valid 0) is computed but nothing of it is kept or changed.  Per push the
+host builds ONE int32 parameter block (PAR_ROWS x slots: positional offset, cache length, n_valid, reset flag, slide source and count,
+key length, output row) and uploads it once; the kernels take its rows as their per-slot arguments (csrc/session.hip,
+asr_add_ln_slots_fwd, asr_ctc_prefix_beam_state_reset).  No row-index tensors, no index_copy_ / index_select, no per-row loops.
+
+Why a slot's bits do not depend on its neighbours: the GEMMs, LayerNorm and the CTC head work row by row, attention works per
+(slot, head) over that slot's key prefix, and every session kernel reads only its own slot's parameters.  The cache capacity (the Tk of
+the attention launch) follows StreamingEncoder._grow's rule, so a slot fed what an utterance of model.stream(slots) is fed gets that
+utterance's bits (tests/test_sessions_gpu.py).
+
+Endpointing (endpoint=dict(...)): WeNet's CTC endpoint rules, evaluated per slot from counters the device keeps
+(asr_session_ctc_step): a frame is silent iff p(blank) > blank_threshold; trailing silence = the current run of silent frames; length
+= the frames consumed; decoded = the greedy output so far is non-empty (beam sessions: the best hypothesis is).  A rule
+(must_have_decoded, min_trailing_silence_ms, min_length_ms) fires when all three hold; endpoints() reports the first that does.
+Endpointing only reports: the caller closes the slot (final), finishes it and opens it again for what follows.
+
+Out of scope: input rates other than 16 kHz (StreamResampler has no per-slot reset), compaction of idle slots (every tick computes
+slots * C rows), carrying audio across an endpoint, a varying number of slots, capture into a hipGraph."""
+import math
+
+import torch
+
+from . import kernels as K
+from .Utils import Pack
+
+BLANK = 0      # the CTC blank (= PAD_ID of the model)
+FREE, OPEN, ENDED = "free", "open", "ended"
+# rows of the per-push parameter block
+P_PE_OFF, P_CLEN, P_NV, P_RESET, P_SLIDE_FROM, P_SLIDE_COUNT, P_KLEN, P_OUT_ROW, PAR_ROWS = 0, 1, 2, 3, 4, 5, 6, 7, 8
+
+ENDPOINT_DEFAULTS = dict(
+    blank_threshold=0.8,
+    # WeNet's CtcEndpointConfig: (must_have_decoded, min_trailing_silence_ms, min_length_ms)
+    rules=(("silence_start", False, 5000, 0), ("silence_after_speech", True, 1000, 0), ("max_length", False, 0, 20000)),
+)
+
+
+def endpoint_config(endpoint):
+    """endpoint=None -> None; a dict -> the defaults overridden by it: blank_threshold, and per rule name a (must_have_decoded,
+    min_trailing_silence_ms, min_length_ms) triple, or the three WeNet-style keys min_trailing_silence_ms etc. inside a dict."""
+    if endpoint is None:
+        return None
+    cfg = dict(blank_threshold=float(endpoint.get("blank_threshold", ENDPOINT_DEFAULTS["blank_threshold"])))
+    if not 0.0 < cfg["blank_threshold"] < 1.0:
+        raise ValueError(f"endpoint: blank_threshold must lie in (0, 1), got {cfg['blank_threshold']}")
+    known = {"blank_threshold"} | {r[0] for r in ENDPOINT_DEFAULTS["rules"]}
+    if set(endpoint) - known:
+        raise ValueError(f"endpoint: unknown keys {sorted(set(endpoint) - known)} (known: {sorted(known)})")
+    rules = []
+    for name, must, sil, length in ENDPOINT_DEFAULTS["rules"]:
+        v = endpoint.get(name)
+        if isinstance(v, dict):
+            must, sil, length = v.get("must_have_decoded", must), v.get("min_trailing_silence_ms", sil), v.get("min_length_ms", length)
+        elif v is not None:
+            must, sil, length = v
+        rules.append((name, bool(must), int(sil), int(length)))
+    cfg["rules"] = tuple(rules)
+    return cfg
+
+
+def endpoint_rule(rules, frame_us, trailing, frames, decoded):
+    """The first rule that fires, or None.  Times in whole microseconds (frame_us = the encoder frame's duration), so that a rule
+    fires at the frame that reaches its threshold whatever the float representation of 30 ms is."""
+    for name, must, sil_ms, len_ms in rules:
+        if (decoded or not must) and trailing * frame_us >= sil_ms * 1000 and frames * frame_us >= len_ms * 1000:
+            return name
+    return None
+
+
+class Sessions:
+    def __init__(self, model, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None):
+        C, left = model.decoding_chunk_size, model.decoding_left_chunks
+        if C <= 0:
+            raise ValueError("model.sessions() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
+        if source_rate is not None and int(source_rate) != 16000:
+            raise ValueError("model.sessions(): only 16 kHz audio (StreamResampler has no per-slot reset yet)")
+        if not model.use_ctc:
+            raise RuntimeError("model.sessions() needs a model with the CTC head (config.ctc_weight > 0): ids and endpointing come from it")
+        self.model, self.S, self.C, self.left = model, int(slots), int(C), int(left)
+        if self.S < 1:
+            raise ValueError("slots must be >= 1")
+        if search not in ("greedy", "prefix_beam"):
+            raise ValueError(f"search must be 'greedy' or 'prefix_beam' (got {search!r})")
+        self.search, self.beam_size, self.frame_topk = search, int(beam_size), int(frame_topk)
+        if search == "prefix_beam":
+            k = max(1, min(self.frame_topk, model.V))
+            if self.beam_size < 1 or self.beam_size > 16 or self.beam_size * (k + 1) > 64:
+                raise ValueError(f"the device search ranks beam * (frame_topk + 1) <= 64 candidates per frame, beam <= 16 (beam {beam_size}, frame_topk {k})")
+            self.frame_topk = k
+        self.endpoint = endpoint_config(endpoint)
+        thr = self.endpoint["blank_threshold"] if self.endpoint else ENDPOINT_DEFAULTS["blank_threshold"]
+        self.silence_lp = math.log(thr)      # the kernel compares float32(log threshold) with float32 log p(blank)
+        self.frame_us = int(round(model.frame_seconds() * 1e6))
+        S = self.S
+        self.eng = None
+        self.state = [FREE] * S
+        self.frames = [0] * S                # frames consumed = the positional offset of the slot's next frame
+        self.clen = [0] * S                  # keys in the slot's cache window
+        self.fresh = [False] * S             # opened, and no launch has reset its device state yet
+        self.trailing = [0] * S
+        self.decoded = [False] * S
+        self.stable = [0] * S
+        self.cap = 0                         # cache rows per slot
+        self.caches = None                   # [buffer][layer] -> (slots, cap, 2 H dk); two buffers with left >= 0 (the slide's ping-pong)
+        self.enc = None                      # (slots, ecap, d): each slot's encoder output rows
+        self.ctc_state = None                # (slots, 4) int32 {last, trailing, frames, decoded}
+        self.beam = None
+        self._hyps = None
+        self.parser, self.frontend = parser, None
+
+    # ------------------------------------------------------------------ slot life cycle
+    def _slot(self, b):
+        b = int(b)
+        if not 0 <= b < self.S:
+            raise ValueError(f"slot {b} of {self.S}")
+        return b
+
+    def open(self, b):
+        """Slot b (free) starts a session at frame 0."""
+        b = self._slot(b)
+        if self.state[b] != FREE:
+            raise ValueError(f"open: slot {b} is {self.state[b]} (finish or drop it first)")
+        self.state[b], self.frames[b], self.clen[b], self.fresh[b] = OPEN, 0, 0, True
+        self.trailing[b], self.decoded[b], self.stable[b] = 0, False, 0
+        if self.frontend is not None:
+            self.frontend.reset(b)
+
+    def drop(self, b):
+        """Free slot b without a result."""
+        b = self._slot(b)
+        if self.state[b] == FREE:
+            raise ValueError(f"drop: slot {b} is free")
+        self.state[b], self.frames[b], self.clen[b], self.fresh[b] = FREE, 0, 0, False
+
+    def status(self, b):
+        b = self._slot(b)
+        return {"state": self.state[b], "frames": self.frames[b], "trailing_silence_frames": self.trailing[b], "decoded": self._decoded(b)}
+
+    def _decoded(self, b):
+        if self.state[b] == FREE:
+            return False
+        if self.search == "prefix_beam":
+            h = self.nbest(b)
+            return bool(h and h[0]["yseq"])
+        return self.decoded[b]
+
+    def endpoints(self):
+        """Per slot None, or the name of the first endpoint rule that fires ("silence_start", "silence_after_speech", "max_length")."""
+        if self.endpoint is None:
+            raise ValueError("endpoints() needs model.sessions(..., endpoint={...})")
+        return [None if self.state[b] == FREE else endpoint_rule(self.endpoint["rules"], self.frame_us, self.trailing[b], self.frames[b], self._decoded(b))
+                for b in range(self.S)]
+
+    # ------------------------------------------------------------------ device buffers
+    def _grow(self, eng, need, dev):
+        """StreamingEncoder._grow's capacities, so that the attention launches have the lock-step stream's shapes."""
+        hd2, L, S = 2 * eng.H * eng.dk, len(eng.enc), self.S
+        if self.caches is None:
+            if self.left >= 0:
+                cap, nbuf = self.left * self.C + self.C, 2
+            else:
+                cap, nbuf = min(max(need, 4 * self.C), eng.pe.shape[0]), 1
+            self.caches = [[torch.zeros(S, cap, hd2, dtype=eng.dtype, device=dev) for _ in range(L)] for _ in range(nbuf)]
+            self.cap = cap
+            return
+        if self.left >= 0 or need <= self.cap:      # the fixed window never needs more: an active slot's keys were slid down first
+            return
+        cap = min(max(2 * self.cap, need), eng.pe.shape[0])
+        new = [torch.zeros(S, cap, hd2, dtype=eng.dtype, device=dev) for _ in range(L)]
+        for i in range(L):
+            new[i][:, : self.cap] = self.caches[0][i]
+        self.caches, self.cap = [new], cap
+
+    def _grow_enc(self, eng, need, dev):
+        d = eng.ln_in.g.numel()
+        need = min(-(-need // self.C) * self.C, eng.pe.shape[0])      # whole chunks: finish() pads its batch to whole chunks
+        if self.enc is None:
+            self.enc = torch.zeros(self.S, min(max(need, 8 * self.C), eng.pe.shape[0]), d, dtype=eng.dtype, device=dev)
+        elif need > self.enc.shape[1]:
+            new = torch.zeros(self.S, min(max(2 * self.enc.shape[1], need), eng.pe.shape[0]), d, dtype=eng.dtype, device=dev)
+            new[:, : self.enc.shape[1]] = self.enc
+            self.enc = new
+
+    # ------------------------------------------------------------------ one tick
+    def push(self, feats, n_valid, final):
+        """feats (slots, C, F): one chunk of encoder-rate features per slot; n_valid[b] = C, or 0 (the slot sits this tick out: nothing of
+        it changes), or any value in [0, C] together with final[b], which ends the session's input.  Returns per slot what
+        StreamingEncoder.push returns: the greedy ids the chunk adds (repeats collapsed across chunks), or the growth of the stable
+        prefix (search="prefix_beam").  A push that is refused (a free slot with frames, a partial chunk without final, a session that
+        would pass the positional table) raises before any launch and leaves every slot as it was."""
+        model, S, C = self.model, self.S, self.C
+        if not torch.is_tensor(feats) or feats.dim() != 3 or feats.shape[0] != S or feats.shape[1] != C:
+            raise ValueError(f"push: feats must be (slots, C, F) = ({S}, {C}, F), got {tuple(feats.shape) if torch.is_tensor(feats) else type(feats)}")
+        nv = [int(x) for x in (n_valid.tolist() if torch.is_tensor(n_valid) else n_valid)]
+        fin = [bool(x) for x in (final.tolist() if torch.is_tensor(final) else final)]
+        if len(nv) != S or len(fin) != S or any(x < 0 or x > C for x in nv):
+            raise ValueError(f"push: n_valid and final must hold {S} values, n_valid in [0, {C}], got {nv} and {fin}")
+        eng = self.eng = model._ensure_engine(feats.device)
+        table = eng.pe.shape[0]
+        for b in range(S):
+            if self.state[b] == FREE and (nv[b] > 0 or fin[b]):
+                raise ValueError(f"push: slot {b} is free (open it first)")
+            if self.state[b] == ENDED and nv[b] > 0:
+                raise ValueError(f"push: slot {b} has ended (final was sent)")
+            if 0 < nv[b] < C and not fin[b]:
+                raise ValueError(f"push: slot {b} brings {nv[b]} of {C} frames without final: a partial chunk in the middle of a session would misalign the chunk mask")
+            if nv[b] > 0 and self.frames[b] + C > table:
+                raise ValueError(f"push: slot {b} would reach frame {self.frames[b] + C}, past the positional-encoding table ({table} frames): close the session (endpointing tells when)")
+        out = [[] for _ in range(S)]
+        if any(nv):
+            self._tick(eng, feats, nv, out)
+        for b in range(S):
+            if fin[b] and self.state[b] == OPEN:
+                self.state[b] = ENDED
+        return out
+
+    def _tick(self, eng, feats, nv, out):
+        S, C, dev = self.S, self.C, feats.device
+        H, dk, hd = eng.H, eng.dk, eng.H * eng.dk
+        keep = self.left * C
+        # ---- the parameter block (host ints only), then one upload
+        slide = self.left > 0 and any(nv[b] > 0 and self.clen[b] > keep for b in range(S))
+        if self.left == 0:      # no key is kept: every chunk starts on an empty window, nothing to move
+            self.clen = [0 if nv[b] > 0 else self.clen[b] for b in range(S)]
+        par = [[0] * S for _ in range(PAR_ROWS)]
+        for b in range(S):
+            c = self.clen[b]
+            if slide:      # every slot moves to the other buffer: its last `keep` keys, or all it has
+                par[P_SLIDE_FROM][b], par[P_SLIDE_COUNT][b] = c - min(c, keep), min(c, keep)
+                c = self.clen[b] = min(c, keep)
+            par[P_PE_OFF][b] = self.frames[b] if nv[b] > 0 else 0
+            par[P_CLEN][b], par[P_NV][b], par[P_RESET][b] = c, nv[b], int(self.fresh[b])
+            par[P_KLEN][b] = max(c + nv[b], 1)      # at least one key, as StreamingEncoder.push
+            par[P_OUT_ROW][b] = self.frames[b]
+        reset_slots = [b for b in range(S) if self.fresh[b]]
+        was_training, eng.training = eng.training, False
+        try:
+            with torch.no_grad():
+                self._grow(eng, max(self.clen) + C, dev)
+                self._grow_enc(eng, max(f + n for f, n in zip(self.frames, nv)), dev)
+                pd = torch.tensor(par, dtype=torch.int32, device=dev)
+                if slide:
+                    for i, cur in enumerate(self.caches[0]):
+                        K.slot_rows_slide(cur, self.caches[1][i], pd[P_SLIDE_FROM], pd[P_SLIDE_COUNT], keep)
+                    self.caches = [self.caches[1], self.caches[0]]
+                caches, cap = self.caches[0], self.cap
+                nv_dev = pd[P_NV]
+                # ---- the encoder chunk body (StreamingEncoder.push's, with per-slot offsets and appends)
+                x = feats.to(eng.dtype).contiguous().reshape(S * C, -1)
+                e0 = eng.lin_in.fwd(x)
+                h = K.add_ln_slots_fwd(e0, eng.ln_in.g, eng.ln_in.b, eng.pe, pd[P_PE_OFF], par[P_PE_OFF], nv_dev, S, C)
+                for i, (mha, ffn) in enumerate(eng.enc):
+                    qkv = mha.qkv.fwd(h)
+                    cache = caches[i]
+                    K.slot_rows_put(qkv[:, hd:], cache, pd[P_CLEN], nv_dev, C)
+                    flat = cache.view(S * cap, 2 * hd)
+                    ctx, _ = K.sdpa_fwd(qkv[:, :hd], flat[:, :hd], flat[:, hd:], pd[P_KLEN], S, H, C, cap, dk)
+                    a = mha.fc.fwd(ctx)
+                    h1, _, _ = K.add_ln_fwd(a, h, mha.ln.g, mha.ln.b, None, nv_dev, S, C, xhat=a)
+                    h, _ = eng._ffn_block_fwd(ffn, h1, S, C, nv_dev, site=0)
+                K.slot_rows_put(h, self.enc, pd[P_OUT_ROW], nv_dev, C)
+                # ---- CTC: ids, counters; one copy to the host
+                if self.ctc_state is None:
+                    self.ctc_state = torch.zeros(S, 4, dtype=torch.int32, device=dev)
+                logits = eng.ctc_lo.fwd(h)
+                if self.search == "prefix_beam":
+                    if self.beam is None:
+                        self.beam = K.ctc_prefix_beam_state(S, self.beam_size, eng.pe.shape[0], dev)
+                    elif reset_slots:
+                        K.ctc_prefix_beam_state_reset(self.beam, pd[P_RESET], reset_slots)
+                    vals, ids, blank_lp = K.ctc_frame_topk(logits, self.frame_topk, BLANK)
+                    buf, Lcap = K.ctc_prefix_beam_chunk(self.beam, vals, ids, blank_lp, nv, C, self.beam_size, BLANK, packed=True, nv_dev=nv_dev,
+                                                        extra_words=S * (4 + C))
+                    n_words = buf.numel() - S * (4 + C)
+                    K.session_ctc_step(None, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK, out=buf[n_words:].view(S, 4 + C))
+                    host = buf.cpu()
+                    tok, ln, sc, stable = (t.numpy() for t in K.prefix_beam_unpack(host[:n_words], S, self.beam_size, Lcap))
+                    self._hyps = (tok, ln, sc)
+                    step = host[n_words:].view(S, 4 + C).tolist()
+                    for b in reset_slots:
+                        self.stable[b] = 0
+                    for b in range(S):
+                        if nv[b] > 0:
+                            out[b] = tok[b, 0, self.stable[b]:int(stable[b])].tolist()
+                            self.stable[b] = int(stable[b])
+                else:
+                    path, blank_lp = K.ctc_frame_best_blank(logits.view(S, C, -1), nv_dev, BLANK)
+                    step = K.session_ctc_step(path, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK).cpu().tolist()
+                    for b in range(S):
+                        if nv[b] > 0:
+                            out[b] = step[b][4:4 + step[b][0]]
+                # this tick's frame-wise log p(blank) (slots * C) f32 and best path (slots, C) int32 (None: beam sessions), on the device: diagnostics
+                self.last_blank_lp, self.last_path = blank_lp, (None if self.search == "prefix_beam" else path)
+        finally:
+            eng.training = was_training
+        for b in range(S):
+            self.fresh[b] = False
+            if nv[b] > 0 or b in reset_slots:
+                self.trailing[b], self.decoded[b] = step[b][1], bool(step[b][3])
+            self.clen[b] += nv[b]
+            self.frames[b] += nv[b]
+
+    # ------------------------------------------------------------------ audio in
+    def _ensure_frontend(self):
+        if self.parser is None:
+            raise ValueError("push_audio: these sessions have no front end - model.sessions(slots, parser=AudioParser(norm='global', cmvn=...))")
+        if self.frontend is None:
+            from .data_handler.stream_frontend import StreamingFrontEnd
+            eng = self.model._ensure_engine(self.parser.window.device)
+            self.frontend = StreamingFrontEnd(self.parser, self.S, self.C, dtype=eng.dtype, independent=True)
+
+    def push_audio(self, pcm, n_samples, final):
+        """pcm (slots, S) f32 at 16 kHz: n_samples[b] <= S new samples of slot b's session (0 is fine), final[b] closes its audio.  Runs a
+        chunk whenever one slot has C rows ready or is closed with rows left - no slot waits for another - and returns per slot the ids
+        the chunks add.  A slot whose audio is closed and whose rows are all out becomes ended."""
+        out = [[] for _ in range(self.S)]
+        for _, ids in self.push_audio_chunks(pcm, n_samples, final):
+            for b in range(self.S):
+                out[b] += ids[b]
+        return out
+
+    def push_audio_chunks(self, pcm, n_samples, final):
+        """push_audio chunk by chunk: yields (n_valid, ids) for every chunk the audio completes."""
+        self._ensure_frontend()
+        ns = [int(x) for x in (n_samples.tolist() if torch.is_tensor(n_samples) else n_samples)]
+        fin = [bool(x) for x in (final.tolist() if torch.is_tensor(final) else final)]
+        if len(ns) != self.S or len(fin) != self.S:
+            raise ValueError(f"push_audio: n_samples and final must hold {self.S} values")
+        for b in range(self.S):
+            if self.state[b] != OPEN and (ns[b] > 0 or fin[b]):
+                raise ValueError(f"push_audio: slot {b} is {self.state[b]}")
+        table = self.model._ensure_engine(self.parser.window.device).pe.shape[0]
+        acts, _ = self.frontend.plan(ns, fin)      # refuse a call that would pass the table before the front end takes its samples
+        rows = list(self.frames)
+        for act in acts:
+            if act[0] == "chunk":
+                for b, n in enumerate(act[2]):
+                    if n > 0 and rows[b] + self.C > table:
+                        raise ValueError(f"push_audio: slot {b} would reach frame {rows[b] + self.C}, past the positional-encoding table ({table} frames)")
+                    rows[b] += n
+        for feats, nv, done in self.frontend.push_audio(pcm, ns, fin):
+            if feats is None:      # only ends
+                feats = torch.empty(self.S, self.C, 0, device=self.parser.window.device)
+            yield nv, self.push(feats, nv, done)
+
+    # ------------------------------------------------------------------ hypotheses and results
+    def _need_beam(self, what):
+        if self.search != "prefix_beam":
+            raise ValueError(f"{what} needs sessions opened with search='prefix_beam'")
+
+    def nbest(self, b):
+        """search="prefix_beam": slot b's current list of {"yseq", "score"}, best first (at most beam_size)."""
+        self._need_beam("nbest()")
+        b = self._slot(b)
+        if self.state[b] == FREE:
+            raise ValueError(f"nbest: slot {b} is free")
+        if self._hyps is None or self.fresh[b]:
+            return [{"yseq": [], "score": 0.0}]
+        tok, ln, sc = self._hyps
+        return [{"yseq": tok[b, r, :ln[b, r]].tolist(), "score": float(sc[b, r])} for r in range(self.beam_size) if ln[b, r] >= 0]
+
+    def partial(self, b):
+        """search="prefix_beam": {"ids": slot b's best prefix now, "stable_len": how many of its tokens are final, "score"}."""
+        h = self.nbest(b)
+        return {"ids": h[0]["yseq"] if h else [], "stable_len": self.stable[self._slot(b)], "score": h[0]["score"] if h else float("-inf")}
+
+    def encoder_output(self, slots):
+        """(enc (n, T, d), lengths (n,) int32) of the listed slots: T = the longest, rounded up to whole chunks; rows past a slot's
+        length are zero."""
+        slots = [self._slot(b) for b in slots]
+        lens = [self.frames[b] for b in slots]
+        T = min(max(self.C, -(-max(lens) // self.C) * self.C), self.enc.shape[1])
+        dev = self.enc.device
+        rows = self.enc[:, :T] if slots == list(range(self.S)) else torch.stack([self.enc[b, :T] for b in slots])
+        lens_dev = torch.tensor(lens, dtype=torch.int32, device=dev)
+        live = (torch.arange(T, device=dev)[None, :] < lens_dev[:, None])[:, :, None]
+        return torch.where(live, rows, torch.zeros((), dtype=rows.dtype, device=dev)).contiguous(), lens_dev
+
+    def finish(self, slots, beam_size=5, **kw):
+        """model.transcribe(...)'s result dicts for the session of each listed slot (one slot: one dict), computed from the slot's own
+        streamed encoder rows - the searches StreamingEncoder.finish runs, joint="ctc_rescore" included (search="prefix_beam") - as one
+        batch padded to the longest.  The slots become free."""
+        single = not isinstance(slots, (list, tuple))
+        slots = [self._slot(b) for b in ([slots] if single else slots)]
+        if len(set(slots)) != len(slots):
+            raise ValueError(f"finish: slots listed twice in {slots}")
+        for b in slots:
+            if self.state[b] == FREE:
+                raise ValueError(f"finish: slot {b} is free")
+        model, timestamps = self.model, kw.get("timestamps", True)
+        rescore = kw.get("joint") == "ctc_rescore"
+        if rescore:
+            self._need_beam("finish(joint='ctc_rescore')")
+        res = [{"text": "", "ids": [], "score": float("-inf"), "tokens": [] if timestamps else None} for _ in slots]
+        live = [i for i, b in enumerate(slots) if self.frames[b] > 0]
+        if live:
+            rows = [slots[i] for i in live]
+            enc, lens = self.encoder_output(rows)
+            n, T = enc.shape[0], enc.shape[1]
+            if rescore:
+                from . import decode
+                hyps = [self.nbest(b) for b in rows]
+                if model.use_decoder:
+                    w = float(getattr(model.config, "ctc_weight", 0.0)) if kw.get("ctc_weight") is None else float(kw["ctc_weight"])
+                    hyps = decode.attention_rescore(model, enc, lens, hyps, w)
+                ids = [list(h[0]["yseq"]) if h else [] for h in hyps]
+                scores = [float(h[0]["score"]) if h else float("-inf") for h in hyps]
+
+                def ctc_logits():
+                    with torch.no_grad():
+                        return self.eng.ctc_lo.fwd(enc.reshape(n * T, -1).contiguous()).view(n, T, -1)
+                got = model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens)
+            else:
+                # under given_encoder_output the searches take the batch's features for their (B, T) only: none are kept
+                wave = torch.zeros(n, T, 1, dtype=enc.dtype, device=enc.device)
+                with model.given_encoder_output(enc):
+                    got = model.transcribe(Pack(wave=wave, wave_len=lens), beam_size=beam_size, **kw)
+            for i, r in zip(live, got):
+                res[i] = r
+        for b in slots:
+            self.state[b], self.frames[b], self.clen[b], self.fresh[b] = FREE, 0, 0, False
+        return res[0] if single else res

@@ -116,6 +116,17 @@ int asr_add_ln_fwd(const void* x, const void* res, const float* gamma, const flo
                    int B, int T, int d, float drop_p, uint32_t drop_seed, int drop_mode, int dtype,
                    void* stream);
 
+/* asr_add_ln_slots_fwd (additive to ABI 10; independent sessions): the input LayerNorm of one tick of `slots` sessions, each at its
+ * own frame offset.  y[b, t] = LN(x[b, t]) * gamma + beta + pe[pe_off[b] + t]; rows t >= lens[b] are zeroed.  Inference only: no
+ * residual, no dropout.  x: (slots*T, d) `dtype`, overwritten with the normalised rows (asr_add_ln_fwd's xhat, in place); y:
+ * (slots*T, d), not x; rstd: (slots*T) f32 scratch; gamma, beta: (d) f32; pe: (pe_rows, d) f32; pe_off, lens: (slots) int32 on the
+ * device (wave-uniform loads).  It launches asr_add_ln_fwd's own kernel with one more argument, so a row has the bits asr_add_ln_fwd
+ * gives it with pe + pe_off[b] * d as its table.  The caller checks pe_off[b] + T <= pe_rows on the host before the call (the
+ * offsets are device data here); the kernel clamps the table row to [0, pe_rows) so that a wrong offset reads nothing outside.
+ * ASR_EINVAL: a null pointer, slots, T or d < 1, d > 2048, pe_rows < T, y == x, a misaligned pointer. */
+int asr_add_ln_slots_fwd(void* x, const float* gamma, const float* beta, const float* pe, const int32_t* pe_off,
+                         const int32_t* lens, void* y, float* rstd, int slots, int T, int d, int pe_rows, int dtype, void* stream);
+
 /* Backward of the above.  dy (+ dy2 if not NULL) is the gradient wrt y.
  *   g = (dy + dy2) * mask * gamma ;  dz = rstd * (g - mean(g) - xhat * mean(g * xhat))
  * dz: (B*T, d) `dtype` (gradient wrt x and wrt res).  Column sums over all rows are ACCUMULATED
@@ -335,6 +346,10 @@ int asr_ctc_prefix_beam_state_init(void* state, void* ws, int B, int beam, int T
 int asr_ctc_prefix_beam_chunk(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* n_valid, void* state, void* ws,
                               size_t ws_bytes, int32_t* out_tok, int32_t* out_len, float* out_score, int32_t* out_stable, int B, int C, int k,
                               int beam, int nbest, int Lcap, int T_cap, int blank, void* stream);
+/* asr_ctc_prefix_beam_state_reset (additive to ABI 10; independent sessions): re-initialises the utterances b with flags[b] != 0
+ *   (flags: (B) int32 on the device) - their beam and their trie's root, byte for byte what asr_ctc_prefix_beam_state_init leaves
+ *   for them (one device function writes both); every other utterance keeps every byte.  Arguments and limits as state_init. */
+int asr_ctc_prefix_beam_state_reset(void* state, void* ws, const int32_t* flags, int B, int beam, int T_cap, void* stream);
 int asr_decode_attn(const void* q, const void* k, const void* v, void* o, const int32_t* k_len,
                     int k_len_uniform, int len_div, int R, int H, int dk, int Tk_cap, int kv_div,
                     int ldq, int ldk, int ldv, int ldo, float scale, int dtype, void* stream);
@@ -848,6 +863,40 @@ int asr_fbank_fwd(const float* wav, const int32_t* wav_len, const float* window,
 int asr_stream_fbank(const float* wav_ring, const int32_t* par, const float* window, const float* melfb,
                      float* feat_ring, int B, int max_new, int scap, int fcap, int n_mels, float wav_scale,
                      float preemph, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Independent streaming sessions (additive to ABI 10; csrc/session.hip, asr_chinese_e2e_amd/sessions.py): `slots` sessions share one
+ * batch, each at its own frame offset and cache length.  The per-slot parameters are (slots) int32 device arrays - rows of the one
+ * parameter block a tick uploads - and no kernel lets a slot's result depend on another slot's parameters.
+ *
+ * asr_slot_rows_put: dst[b, start[b] + t, :] = src[b * C + t, :] for t < min(n[b], C).  src: (slots*C) rows of `cols` elements, row
+ *   stride ld_src elements (a column slice of a wider matrix: the K | V columns of qkv); dst: (slots, cap, cols) dense.  Appends a
+ *   layer's new keys to its cache, and the encoder's output rows to the per-slot output buffer.  Only valid rows are written; a row
+ *   that would land outside [0, cap) is dropped.  16-byte vectors: cols and ld_src times the element size are multiples of 16, src and
+ *   dst 16-byte aligned; 1 <= C <= cap, slots <= 65535 (ASR_EINVAL otherwise, before any launch).
+ * asr_slot_rows_slide: dst[b, t, :] = src[b, from[b] + t, :] for t < count[b] <= max_count; src and dst are two different
+ *   (slots, cap, cols) buffers (the ping-pong of the fixed-window cache: never in place - overlapping buffers are refused).  Rows
+ *   read outside [0, cap) are dropped.  Alignment as above; 1 <= max_count <= cap.
+ * asr_ctc_frame_best_blank: one pass per frame of the CTC head's logits (B, T, V) (row stride ld): path = the best class, the first
+ *   maximum winning, as asr_ctc_frame_argmax (same 16-byte bf16 path and scalar tail); blank_lp = log_softmax of class `blank`, bit
+ *   for bit asr_ctc_frame_topk's (the maximum is order-free, the sum of exponentials is taken in that kernel's order).  Frames
+ *   t >= in_len[b] (in_len may be NULL) get path = blank and blank_lp = 0.
+ * asr_session_ctc_step: one wave per slot over its n_valid[b] <= C frames in order.  state (slots, 4) int32 = {last class, trailing
+ *   silent frames, frames consumed, decoded}; reset[b] != 0: the slot starts from {blank, 0, 0, 0} instead of its stored state.
+ *   A class c of frame t is emitted when c != blank and c != the class of the frame before (the carried last class at t = 0): the
+ *   CTC collapse across chunk boundaries.  A frame is silent iff blank_lp > silence_lp (the caller passes log(blank_threshold));
+ *   trailing = the current run of silent frames, frames += n_valid[b], decoded = 1 once anything was emitted.  path == NULL (beam
+ *   sessions): nothing is emitted, last and decoded keep their values.  out (slots, 4 + C) int32 = {ids emitted, trailing, frames,
+ *   decoded, the ids, 0-padded}: one buffer, one copy to the host.  n_valid[b] == 0 without reset leaves the slot's state as it is.
+ */
+int asr_slot_rows_put(const void* src, void* dst, const int32_t* start, const int32_t* n, int slots, int C, int cap, int cols,
+                      int ld_src, int dtype, void* stream);
+int asr_slot_rows_slide(const void* src, void* dst, const int32_t* from, const int32_t* count, int slots, int max_count, int cap,
+                        int cols, int dtype, void* stream);
+int asr_ctc_frame_best_blank(const void* logits, const int32_t* in_len, int32_t* path, float* blank_lp, int B, int T, int V,
+                             int ld, int blank, int dtype, void* stream);
+int asr_session_ctc_step(const int32_t* path, const float* blank_lp, const int32_t* n_valid, const int32_t* reset, int32_t* state,
+                         int32_t* out, int slots, int C, int blank, float silence_lp, void* stream);
 
 #ifdef __cplusplus
 }

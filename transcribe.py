@@ -35,6 +35,12 @@ trained with rebuild it.  Inference flags:
   --resample     1 = files at 8, 11.025, 12, 22.05, 24, 32, 44.1, 48, 88.2 or 96 kHz are converted to 16 kHz on the GPU (one launch per
                  batch; with --stream=1 --cmvn a batch whose files share one rate is converted as it streams) and their JSON line
                  gains "source_rate"; 0 (default) = a file at another rate ends the run
+  --sessions     N (with --stream=1 and --cmvn): the files go through N independent slots of one batch (model.sessions) instead of
+                 batches that advance in lock-step - each file streams at its own pace, and when one finishes the next file takes
+                 its slot in the same tick loop.  The same per-chunk lines ("chunk" counts the file's own chunks), the final lines in
+                 order of completion.  16 kHz files only.
+  --endpoint     1 (with --sessions): the per-chunk lines gain "endpoint": null, or the CTC endpoint rule that fires for the file now
+                 (silence_start, silence_after_speech, max_length - WeNet's rules); it only reports, the file streams on
 Audio goes through load_wav -> AudioParser.parse_batch on the device -> model.transcribe; one JSON line per file is printed:
 {"file", "duration_s", "text", "ids", "score", "tokens": [{"id", "token", "start_frame", "end_frame", "start_s", "end_s", "logp"}]}.
 """
@@ -56,7 +62,7 @@ from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
 from asr_chinese_e2e_amd.data_handler import resample as resample_mod  # noqa: E402
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend")
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint")
 
 
 def _finite(x):
@@ -136,6 +142,65 @@ def stream_audio_batch(model, parser, files, wav, wav_len, id2tok, block, source
     return st.finish(**search)
 
 
+def final_line(path, n_samples, sr, r, shift_s, sample_rate):
+    """The JSON line of one finished file from its result dict r (token times moved to frame centres, never past the audio's end)."""
+    dur = n_samples / float(sr)
+    for t in r["tokens"] or ():          # the last encoder frame may reach past the end of the audio
+        for k in ("start_s", "end_s"):
+            if t[k] is not None:
+                t[k] = min(t[k] + shift_s, dur)
+    line = {"file": path, "duration_s": dur, "text": r["text"], "ids": r["ids"],
+            "score": _finite(r["score"]), "tokens": r["tokens"]}
+    if sr != sample_rate:
+        line["source_rate"] = sr
+    return line
+
+
+def stream_sessions(model, parser, files, n_slots, id2tok, block, shift_s, sample_rate, endpoint=False, stream_kw=None, **search):
+    """The files through n_slots independent sessions (model.sessions): every tick feeds each open slot its file's next `block`
+    samples; a slot whose file has ended is finished, its final line printed, and the next file takes it in the same loop."""
+    ss = model.sessions(n_slots, parser=parser, endpoint={} if endpoint else None, **(stream_kw or {}))
+    beam_mode = ss.search == "prefix_beam"
+    spell = lambda seq: "".join(id2tok[t] for t in seq if not beam_mode or t not in (0, 2, 3))      # noqa: E731  (as _chunk_lines)
+    queue = list(files)
+    slot = [None] * n_slots      # per slot: {"file", "pcm", "pos", "text", "chunk"}
+    while queue or any(slot):
+        for b in range(n_slots):
+            if slot[b] is None and queue:
+                path = queue.pop(0)
+                pcm, sr = load_wav(path)
+                if sr != sample_rate:
+                    raise SystemExit(f"transcribe.py: {path}: sample rate {sr}; --sessions streams {sample_rate} Hz files only")
+                slot[b] = dict(file=path, pcm=torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.float32)), pos=0, text="", chunk=0)
+                ss.open(b)
+        n, final = [0] * n_slots, [False] * n_slots
+        wav = torch.zeros(n_slots, block)
+        for b, f in enumerate(slot):
+            if f is not None:
+                n[b] = max(0, min(block, len(f["pcm"]) - f["pos"]))
+                wav[b, :n[b]] = f["pcm"][f["pos"]:f["pos"] + n[b]]
+                f["pos"] += n[b]
+                final[b] = f["pos"] >= len(f["pcm"])
+        for nv, ids in ss.push_audio_chunks(wav, n, final):
+            ends = ss.endpoints() if endpoint else None
+            for b, f in enumerate(slot):
+                if f is None or nv[b] <= 0:
+                    continue
+                f["text"] += spell(ids[b])
+                line = {"file": f["file"], "chunk": f["chunk"], "partial": f["text"]}
+                if beam_mode:
+                    line.update(partial=spell(ss.partial(b)["ids"]), stable=f["text"])
+                if endpoint:
+                    line["endpoint"] = ends[b]
+                f["chunk"] += 1
+                print(json.dumps(line, ensure_ascii=False), flush=True)
+        for b, f in enumerate(slot):
+            if f is not None and ss.status(b)["state"] == "ended":
+                r = ss.finish(b, **search)
+                print(json.dumps(final_line(f["file"], len(f["pcm"]), sample_rate, r, shift_s, sample_rate), ensure_ascii=False), flush=True)
+                slot[b] = None
+
+
 def cmvn_path(cli):
     """The value of --cmvn as a path, or None (absent / empty: per-utterance normalisation)."""
     v = cli.get("cmvn")
@@ -177,6 +242,19 @@ def transcribe(**flags):
     if stream and model.decoding_chunk_size <= 0:
         raise SystemExit("transcribe.py: --stream=1 needs a decoding chunk (--decoding_chunk_size, or a static --chunk_size)")
     id2tok = vocab._id2token
+    n_sessions = int(cli.get("sessions", 0) or 0)
+    if bool(int(cli.get("endpoint", 0) or 0)) and not n_sessions:
+        raise SystemExit("transcribe.py: --endpoint=1 applies to --sessions=N")
+    if n_sessions:
+        if not stream or parser.norm != "global":
+            raise SystemExit("transcribe.py: --sessions=N needs --stream=1 and --cmvn (the samples themselves are streamed)")
+        if not model.use_ctc:
+            raise SystemExit("transcribe.py: --sessions=N needs a model with the CTC head")
+        search = dict(ctc_weight=ctc_weight, timestamps=timestamps, joint="ctc_rescore") if stream_kw else dict(beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps, joint=joint)
+        block = int(cli.get("stream_block_samples", 0)) or model.decoding_chunk_size * config.lfr_n * 160
+        stream_sessions(model, parser, files, n_sessions, id2tok, block, shift_s, config.sample_rate, endpoint=bool(int(cli.get("endpoint", 0) or 0)),
+                        stream_kw=stream_kw, **search)
+        return
     for i in range(0, len(files), bs):
         chunk = files[i:i + bs]
         waves, rates = [], []
@@ -216,16 +294,7 @@ def transcribe(**flags):
             else:
                 out = model.transcribe(Pack(wave=feats, wave_len=flen), **search)
         for path, w, sr, r in zip(chunk, waves, rates, out):
-            dur = len(w) / float(sr)
-            for t in r["tokens"] or ():          # the last encoder frame may reach past the end of the audio
-                for k in ("start_s", "end_s"):
-                    if t[k] is not None:
-                        t[k] = min(t[k] + shift_s, dur)
-            line = {"file": path, "duration_s": dur, "text": r["text"], "ids": r["ids"],
-                    "score": _finite(r["score"]), "tokens": r["tokens"]}
-            if sr != config.sample_rate:
-                line["source_rate"] = sr
-            print(json.dumps(line, ensure_ascii=False), flush=True)
+            print(json.dumps(final_line(path, len(w), sr, r, shift_s, config.sample_rate), ensure_ascii=False), flush=True)
 
 
 if __name__ == "__main__":
