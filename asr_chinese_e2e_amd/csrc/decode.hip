@@ -379,6 +379,75 @@ struct PbLds {
     float lp[PB_MAX_K];
 };
 
+// ---- hotword biasing (CTX instantiations only; the tables come from asr_chinese_e2e_amd/context.py::ContextGraph) --------------------
+// A beam entry carries (context state, bias): a function of its prefix alone, so the entry an extension is merged into holds the same
+// pair and the merge rule needs no change.  Candidates are ranked by log p + bias; pb / pnb stay pure probabilities.
+struct PbCtx {
+    const int32_t* __restrict__ st_off;
+    const int32_t* __restrict__ arc_tok;
+    const int32_t* __restrict__ arc_next;
+    const double* __restrict__ st_held;
+    int S, A;
+    double w;
+};
+
+// the beam's (state, bias) in rank order and one frame's slots, beside PbLds
+struct PbCtxLds {
+    double bias[PB_MAX_BEAM], nbias[64];
+    int st[PB_MAX_BEAM], nst[64];
+};
+
+// the state the arc (st, c) leads to, or -1: binary search of st's arc range (ascending tokens).  Every index is clamped to its table.
+__device__ __forceinline__ int pb_ctx_find(const PbCtx& g, int st, int c) {
+    int lo = min(max(g.st_off[st], 0), g.A);
+    const int end = min(max(g.st_off[st + 1], lo), g.A);
+    int hi = end;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (g.arc_tok[mid] < c) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo < end && g.arc_tok[lo] == c) {
+        const int nx = g.arc_next[lo];
+        return (unsigned)nx < (unsigned)g.S ? nx : -1;
+    }
+    return -1;
+}
+
+// (st, bias) of a prefix -> of the prefix + c (context.py::ContextGraph.advance, the same fp64 additions in the same order).
+// root < 0: the utterance is not biased, (st, bias) stays (-1, 0.0).
+__device__ __forceinline__ void pb_ctx_advance(const PbCtx& g, int root, int c, int& st, double& bias) {
+    if (root < 0) return;
+    if ((unsigned)st >= (unsigned)g.S) st = root;    // never from a state outside the table
+    int m = pb_ctx_find(g, st, c);
+    if (m >= 0) { bias = bias + g.w; st = m; return; }
+    bias = bias - g.st_held[st];
+    st = root;
+    m = pb_ctx_find(g, root, c);
+    if (m >= 0) { bias = bias + g.w; st = m; }
+}
+
+// what the CTX kernels take beside the plain ones' arguments (nothing for CTX = false)
+template <bool CTX> struct PbCtxArgs {};
+template <> struct PbCtxArgs<true> {
+    PbCtx g;
+    const int32_t* root;      // offline: (B) the utterance's root state, -1 = not biased; resumable: unused, the root lives in the state
+    double* out_bias;         // (B, nbest) the entries' raw bias (held(state) not yet taken off)
+    int32_t* out_state;       // (B, nbest) their context state (-1: no entry, or not biased)
+};
+
+// a root outside the table means "not biased"
+__device__ __forceinline__ int pb_ctx_root(const PbCtx& g, int root) { return (root >= 0 && root < g.S) ? root : -1; }
+
+// (state, bias) of the n best, beside pb_spell's outputs
+__device__ __forceinline__ void pb_ctx_report(const PbCtxLds& cs, int nb, double* __restrict__ out_bias, int32_t* __restrict__ out_state, int b, int nbest) {
+    const int lane = threadIdx.x;
+    if (lane < nbest) {
+        out_bias[b * nbest + lane] = lane < nb ? cs.bias[lane] : 0.0;
+        out_state[b * nbest + lane] = lane < nb ? cs.st[lane] : -1;
+    }
+}
+
 // The empty-prefix beam every search starts from (lane 0 writes; the caller synchronises).
 __device__ __forceinline__ void pb_empty_beam(PbLds& s) {
     s.node[0] = 0; s.tok[0] = -1; s.par[0] = -1; s.dep[0] = 0; s.pb[0] = 0.0; s.pnb[0] = -INFINITY;
@@ -386,9 +455,12 @@ __device__ __forceinline__ void pb_empty_beam(PbLds& s) {
 
 // One frame of the search: the only copy, run by the offline kernel and by the resumable one.  row_* = the frame's candidates;
 // nb / next_node = beam entries / trie nodes in use (wave-uniform, carried across frames).
-// All 64 lanes call it; it ends with a barrier.
+// All 64 lanes call it; it ends with a barrier.  CTX = false is the search without biasing (cs / g / root unused); CTX = true adds the
+// entries' context state and bias (cs) and ranks by log p + bias.
+template <bool CTX>
 __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict__ row_vals, const int32_t* __restrict__ row_ids, double lb, int k, int beam,
-                                              int blank, int& nb, int& next_node, int32_t* npar, int32_t* ntok) {
+                                              int blank, int& nb, int& next_node, int32_t* npar, int32_t* ntok, PbCtxLds* cs = nullptr,
+                                              const PbCtx* g = nullptr, int root = -1) {
     const int lane = threadIdx.x, per = k + 1;
     if (lane < k) { s.id[lane] = row_ids[lane]; s.lp[lane] = row_vals[lane]; }
     if (lane < PB_MAX_BEAM) s.merge[lane] = -INFINITY;
@@ -397,6 +469,11 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
     bool valid = j < nb;
     double pb2 = -INFINITY, pnb2 = -INFINITY;
     int c = -1, ident_par = -1, dep = 0;
+    int cst = -1;
+    double cbias = 0.0;
+    if constexpr (CTX) {
+        if (valid) { cst = cs->st[j]; cbias = cs->bias[j]; }     // a stay slot inherits them
+    }
     if (valid) {
         const double pb = s.pb[j], pnb = s.pnb[j], tot = pb_logadd(pb, pnb);
         const int e = s.tok[j];
@@ -414,6 +491,7 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
                 pnb2 = (c == e ? pb : tot) + (double)s.lp[m - 1];
                 ident_par = s.node[j];
                 dep = s.dep[j] + 1;
+                if constexpr (CTX) pb_ctx_advance(*g, root, c, cst, cbias);
             }
         }
     }
@@ -428,7 +506,10 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
     }
     __syncthreads();
     if (valid && m == 0) pnb2 = pb_logadd(pnb2, s.merge[j]);
-    const double sc = valid ? pb_logadd(pb2, pnb2) : -INFINITY;
+    double sc = valid ? pb_logadd(pb2, pnb2) : -INFINITY;
+    if constexpr (CTX) {
+        if (sc > -INFINITY) sc = sc + cbias;         // -inf stays -inf
+    }
     // a slot whose whole probability is zero cannot enter the beam (the host dictionary would hold it with -inf, ranked last)
     valid = valid && sc > -INFINITY;
     s.sc[lane] = sc;
@@ -452,6 +533,7 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
         s.ndep_[rank] = dep;
         s.npb[rank] = pb2;
         s.npnb[rank] = pnb2;
+        if constexpr (CTX) { cs->nst[rank] = cst; cs->nbias[rank] = cbias; }
     }
     __syncthreads();
     nb = __popcll(keep_mask);
@@ -459,6 +541,7 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
     if (lane < nb) {
         s.node[lane] = s.nnode[lane]; s.tok[lane] = s.ntok_[lane]; s.par[lane] = s.npar_[lane]; s.dep[lane] = s.ndep_[lane];
         s.pb[lane] = s.npb[lane]; s.pnb[lane] = s.npnb[lane];
+        if constexpr (CTX) { cs->st[lane] = cs->nst[lane]; cs->bias[lane] = cs->nbias[lane]; }
     }
     __syncthreads();
 }
@@ -487,11 +570,20 @@ __device__ __forceinline__ void pb_spell(const PbLds& s, int nb, const int32_t* 
     }
 }
 
+template <bool CTX>
 __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __restrict__ vals, const int32_t* __restrict__ ids, const float* __restrict__ blank_lp,
                                                              const int32_t* __restrict__ in_len, int32_t* nodes, int32_t* __restrict__ out_tok,
                                                              int32_t* __restrict__ out_len, float* __restrict__ out_score, int T, int k, int beam, int nbest,
-                                                             int Lcap, int blank) {
+                                                             int Lcap, int blank, PbCtxArgs<CTX> cx) {
     __shared__ PbLds s;
+    [[maybe_unused]] PbCtxLds* cs = nullptr;
+    [[maybe_unused]] PbCtx g{};
+    [[maybe_unused]] int root = -1;
+    if constexpr (CTX) {
+        __shared__ PbCtxLds cs_mem;
+        cs = &cs_mem;
+        g = cx.g;
+    }
     const int b = blockIdx.x, lane = threadIdx.x;
     const int cap_nodes = T * beam + 1;                  // node 0 = the empty prefix; at most `beam` new nodes per frame
     int32_t* npar = nodes + (size_t)b * 2 * cap_nodes;   // [parent | token] per node
@@ -502,13 +594,19 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
         ntok[0] = -1;
         pb_empty_beam(s);
     }
+    if constexpr (CTX) {
+        root = pb_ctx_root(g, cx.root[b]);
+        if (lane == 0) { cs->st[0] = root; cs->bias[0] = 0.0; }
+    }
     int nb = 1, next_node = 1;                           // wave-uniform copies
     __syncthreads();
     for (int t = 0; t < len; ++t) {
         const size_t row = (size_t)b * T + t;
-        pb_frame_step(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
+        if constexpr (CTX) pb_frame_step<true>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, cs, &g, root);
+        else pb_frame_step<false>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
     }
     pb_spell(s, nb, npar, ntok, out_tok, out_len, out_score, b, nbest, Lcap);
+    if constexpr (CTX) pb_ctx_report(*cs, nb, cx.out_bias, cx.out_state, b, nbest);
 }
 
 // ---- the resumable search: the beam leaves LDS between launches ------------------------------------------------------------------
@@ -519,11 +617,14 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
 constexpr int PB_STATE_HDR = 4;
 
 __host__ __device__ inline size_t pb_state_bytes1(int beam) { return (size_t)PB_STATE_HDR * 4 + (size_t)beam * (4 * 4 + 2 * 8); }
+// The context state of one utterance: the plain state, then fp64 bias[beam], int32 ctx[beam], int32 root, padded to 8 bytes.
+__host__ __device__ inline size_t pb_ctx_state_bytes1(int beam) { return pb_state_bytes1(beam) + (size_t)beam * 8 + (((size_t)beam * 4 + 4 + 7) & ~(size_t)7); }
 
 // The empty-prefix state of utterance b and its trie's root: what the init kernel leaves for every utterance and the reset kernel for the flagged ones.
-__device__ __forceinline__ void pb_state_init_one(char* state, int32_t* nodes, int b, int beam, int T_cap) {
+// bytes1: the bytes of one utterance's state (pb_state_bytes1, or pb_ctx_state_bytes1 when a context part follows).
+__device__ __forceinline__ void pb_state_init_one(char* state, int32_t* nodes, int b, int beam, int T_cap, size_t bytes1) {
     const size_t cap_nodes = (size_t)T_cap * beam + 1;
-    int32_t* hdr = (int32_t*)(state + (size_t)b * pb_state_bytes1(beam));
+    int32_t* hdr = (int32_t*)(state + (size_t)b * bytes1);
     int32_t* ent = hdr + PB_STATE_HDR;
     double* sc = (double*)(ent + 4 * beam);
     hdr[0] = 1; hdr[1] = 1; hdr[2] = 0; hdr[3] = 0;
@@ -538,27 +639,54 @@ __device__ __forceinline__ void pb_state_init_one(char* state, int32_t* nodes, i
 __global__ __launch_bounds__(64) void ctc_prefix_beam_state_init_kernel(char* state, int32_t* nodes, int B, int beam, int T_cap) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
-    pb_state_init_one(state, nodes, b, beam, T_cap);
+    pb_state_init_one(state, nodes, b, beam, T_cap, pb_state_bytes1(beam));
 }
 
 // only the utterances with flags[b] != 0 (independent sessions: a slot that is reopened); the others keep every byte
 __global__ __launch_bounds__(64) void ctc_prefix_beam_state_reset_kernel(char* state, int32_t* nodes, const int32_t* __restrict__ flags, int B, int beam, int T_cap) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B || flags[b] == 0) return;
-    pb_state_init_one(state, nodes, b, beam, T_cap);
+    pb_state_init_one(state, nodes, b, beam, T_cap, pb_state_bytes1(beam));
 }
 
+// the context part of utterance b's state: every entry on the root with no bias, the root, a zero pad word
+__device__ __forceinline__ void pb_ctx_state_init_one(char* state, int b, int beam, int root) {
+    char* base = state + (size_t)b * pb_ctx_state_bytes1(beam) + pb_state_bytes1(beam);
+    double* bias = (double*)base;
+    int32_t* ctx = (int32_t*)(base + (size_t)beam * 8);
+    for (int i = 0; i < beam; ++i) { bias[i] = 0.0; ctx[i] = root; }
+    ctx[beam] = root;
+    if ((beam & 1) == 0) ctx[beam + 1] = 0;
+}
+
+// flags == nullptr: every utterance (init); otherwise the flagged ones (reset), each with its new root
+__global__ __launch_bounds__(64) void ctc_prefix_beam_ctx_state_init_kernel(char* state, int32_t* nodes, const int32_t* __restrict__ flags,
+                                                                            const int32_t* __restrict__ root, int B, int beam, int T_cap) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B || (flags && flags[b] == 0)) return;
+    pb_state_init_one(state, nodes, b, beam, T_cap, pb_ctx_state_bytes1(beam));
+    pb_ctx_state_init_one(state, b, beam, max(root[b], -1));
+}
+
+template <bool CTX>
 __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* __restrict__ vals, const int32_t* __restrict__ ids, const float* __restrict__ blank_lp,
                                                                    const int32_t* __restrict__ n_valid, char* state, int32_t* nodes, int32_t* __restrict__ out_tok,
                                                                    int32_t* __restrict__ out_len, float* __restrict__ out_score, int32_t* __restrict__ out_stable,
-                                                                   int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank) {
+                                                                   int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank, PbCtxArgs<CTX> cx) {
     __shared__ PbLds s;
     __shared__ int s_walk[PB_MAX_BEAM];
+    [[maybe_unused]] PbCtxLds* cs = nullptr;
+    [[maybe_unused]] PbCtx g{};
+    if constexpr (CTX) {
+        __shared__ PbCtxLds cs_mem;
+        cs = &cs_mem;
+        g = cx.g;
+    }
     const int b = blockIdx.x, lane = threadIdx.x;
     const int cap_nodes = T_cap * beam + 1;
     int32_t* npar = nodes + (size_t)b * 2 * cap_nodes;   // [parent | token] per node
     int32_t* ntok = npar + cap_nodes;
-    int32_t* hdr = (int32_t*)(state + (size_t)b * pb_state_bytes1(beam));
+    int32_t* hdr = (int32_t*)(state + (size_t)b * (CTX ? pb_ctx_state_bytes1(beam) : pb_state_bytes1(beam)));
     int32_t* ent = hdr + PB_STATE_HDR;
     double* sc = (double*)(ent + 4 * beam);
     int nb = min(max(hdr[0], 0), beam), next_node = hdr[1];      // wave-uniform copies
@@ -567,6 +695,13 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* 
         s.node[lane] = ent[lane]; s.tok[lane] = ent[beam + lane]; s.par[lane] = ent[2 * beam + lane]; s.dep[lane] = ent[3 * beam + lane];
         s.pb[lane] = sc[lane]; s.pnb[lane] = sc[beam + lane];
     }
+    [[maybe_unused]] double* st_bias = sc + 2 * beam;            // the context part of the state (CTX only)
+    [[maybe_unused]] int32_t* st_ctx = (int32_t*)(st_bias + beam);
+    [[maybe_unused]] int root = -1;
+    if constexpr (CTX) {
+        root = pb_ctx_root(g, st_ctx[beam]);
+        if (lane < nb) { cs->st[lane] = root < 0 ? -1 : st_ctx[lane]; cs->bias[lane] = st_bias[lane]; }
+    }
     __syncthreads();
     // never past the trie: at most T_cap frames in all (the wrapper refuses such a push; this keeps every write inside the workspace)
     const int n = max(0, min(min(n_valid[b], C), T_cap - frames));
@@ -574,7 +709,8 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* 
     for (int t = 0; t < n; ++t) {
         if (next_node < 1 || next_node + beam > cap_nodes) break;
         const size_t row = (size_t)b * C + t;
-        pb_frame_step(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
+        if constexpr (CTX) pb_frame_step<true>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, cs, &g, root);
+        else pb_frame_step<false>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
         ++done;
     }
     if (done > 0) {                                      // a chunk without frames leaves every byte of the state as it is
@@ -582,9 +718,11 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* 
         if (lane < nb) {
             ent[lane] = s.node[lane]; ent[beam + lane] = s.tok[lane]; ent[2 * beam + lane] = s.par[lane]; ent[3 * beam + lane] = s.dep[lane];
             sc[lane] = s.pb[lane]; sc[beam + lane] = s.pnb[lane];
+            if constexpr (CTX) { st_ctx[lane] = cs->st[lane]; st_bias[lane] = cs->bias[lane]; }
         }
     }
     pb_spell(s, nb, npar, ntok, out_tok, out_len, out_score, b, nbest, Lcap);
+    if constexpr (CTX) pb_ctx_report(*cs, nb, cx.out_bias, cx.out_state, b, nbest);
     // the stable prefix: the depth of the lowest common ancestor of the beam's nodes.  Every entry first climbs to the smallest depth
     // among them, then all climb together until they stand on one node.
     int mind = INT_MAX;
@@ -619,7 +757,7 @@ extern "C" int asr_ctc_prefix_beam(const float* vals, const int32_t* ids, const 
     if (beam > PB_MAX_BEAM || k > PB_MAX_K || beam * (k + 1) > 64 || nbest > beam)
         ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam: one wave ranks the beam * (k + 1) candidates of a frame: beam * (k + 1) <= 64, beam <= %d, nbest <= beam (beam=%d k=%d nbest=%d)", PB_MAX_BEAM, beam, k, nbest);
     if (ws_bytes < asr_ctc_prefix_beam_workspace_bytes(B, T, beam) || ((uintptr_t)ws % 4)) ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_workspace_bytes(B, T, beam), ws_bytes);
-    ctc_prefix_beam_kernel<<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank);
+    ctc_prefix_beam_kernel<false><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, PbCtxArgs<false>{});
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam");
     return ASR_OK;
 }
@@ -669,9 +807,88 @@ extern "C" int asr_ctc_prefix_beam_chunk(const float* vals, const int32_t* ids, 
         ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk: misaligned pointer (state: 8 bytes, the others: 4)");
     if (ws_bytes < asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam) || ((uintptr_t)ws % 4))
         ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_chunk: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam), ws_bytes);
-    ctc_prefix_beam_chunk_kernel<<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score, out_stable,
-                                                                    C, k, beam, nbest, Lcap, T_cap, blank);
+    ctc_prefix_beam_chunk_kernel<false><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score,
+                                                                           out_stable, C, k, beam, nbest, Lcap, T_cap, blank, PbCtxArgs<false>{});
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_chunk");
+    return ASR_OK;
+}
+
+// ---- hotword biasing: the same searches with a context graph (additive to ABI 10) -----------------------------------------------------
+namespace {
+const char* pb_ctx_check(const asr_context_graph* ctx) {
+    if (!ctx || !ctx->st_off || !ctx->arc_tok || !ctx->arc_next || !ctx->st_held) return "null context table";
+    if (ctx->S < 1 || ctx->A < 0) return "a context graph has S >= 1 states and A >= 0 arcs";
+    if ((((uintptr_t)ctx->st_off | (uintptr_t)ctx->arc_tok | (uintptr_t)ctx->arc_next) % 4) || ((uintptr_t)ctx->st_held % 8))
+        return "misaligned context table (int32 tables: 4 bytes, st_held: 8)";
+    if (!(ctx->w == ctx->w) || ctx->w - ctx->w != 0.0) return "the context score w must be finite";
+    return nullptr;
+}
+PbCtx pb_ctx_of(const asr_context_graph* ctx) { return PbCtx{ctx->st_off, ctx->arc_tok, ctx->arc_next, ctx->st_held, ctx->S, ctx->A, ctx->w}; }
+}  // namespace
+
+extern "C" int asr_ctc_prefix_beam_ctx(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* in_len, const int32_t* root,
+                                       const asr_context_graph* ctx, void* ws, size_t ws_bytes, int32_t* out_tok, int32_t* out_len, float* out_score,
+                                       double* out_bias, int32_t* out_state, int B, int T, int k, int beam, int nbest, int Lcap, int blank, void* stream) {
+    if (!vals || !ids || !blank_lp || !root || !ws || !out_tok || !out_len || !out_score || !out_bias || !out_state) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_ctx: null pointer");
+    if (const char* why = pb_ctx_check(ctx)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_ctx: %s", why);
+    if (B <= 0 || T <= 0 || k <= 0 || beam <= 0 || nbest <= 0 || Lcap <= 0) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_ctx: bad shape B=%d T=%d k=%d beam=%d nbest=%d Lcap=%d", B, T, k, beam, nbest, Lcap);
+    if (beam > PB_MAX_BEAM || k > PB_MAX_K || beam * (k + 1) > 64 || nbest > beam)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_ctx: one wave ranks the beam * (k + 1) candidates of a frame: beam * (k + 1) <= 64, beam <= %d, nbest <= beam (beam=%d k=%d nbest=%d)", PB_MAX_BEAM, beam, k, nbest);
+    if (((uintptr_t)out_bias % 8) || (((uintptr_t)root | (uintptr_t)out_state) % 4)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_ctx: misaligned pointer (out_bias: 8 bytes, root and out_state: 4)");
+    if (ws_bytes < asr_ctc_prefix_beam_workspace_bytes(B, T, beam) || ((uintptr_t)ws % 4)) ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_ctx: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_workspace_bytes(B, T, beam), ws_bytes);
+    PbCtxArgs<true> cx{pb_ctx_of(ctx), root, out_bias, out_state};
+    ctc_prefix_beam_kernel<true><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, cx);
+    ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_ctx");
+    return ASR_OK;
+}
+
+extern "C" size_t asr_ctc_prefix_beam_ctx_state_bytes(int B, int beam) {
+    if (B <= 0 || beam <= 0) return 0;
+    return (size_t)B * pb_ctx_state_bytes1(beam);
+}
+
+namespace {
+int pb_ctx_state_launch(const char* what, void* state, void* ws, const int32_t* flags, const int32_t* root, int B, int beam, int T_cap, void* stream) {
+    if (B <= 0 || beam <= 0 || beam > PB_MAX_BEAM || T_cap <= 0 || (size_t)T_cap * beam + 1 > (size_t)INT_MAX)
+        ASR_FAIL(ASR_EINVAL, "%s: bad shape B=%d beam=%d (<= %d) T_cap=%d", what, B, beam, PB_MAX_BEAM, T_cap);
+    if (((uintptr_t)state % 8) || ((uintptr_t)ws % 4) || ((uintptr_t)flags % 4) || ((uintptr_t)root % 4))
+        ASR_FAIL(ASR_EINVAL, "%s: misaligned pointer (state: 8 bytes, workspace, flags and root: 4)", what);
+    ctc_prefix_beam_ctx_state_init_kernel<<<ceil_div(B, 64), 64, 0, (hipStream_t)stream>>>((char*)state, (int32_t*)ws, flags, root, B, beam, T_cap);
+    ASR_CHECK_LAUNCH(what);
+    return ASR_OK;
+}
+}  // namespace
+
+extern "C" int asr_ctc_prefix_beam_ctx_state_init(void* state, void* ws, const int32_t* root, int B, int beam, int T_cap, void* stream) {
+    if (!state || !ws || !root) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_ctx_state_init: null pointer");
+    return pb_ctx_state_launch("asr_ctc_prefix_beam_ctx_state_init", state, ws, nullptr, root, B, beam, T_cap, stream);
+}
+
+extern "C" int asr_ctc_prefix_beam_ctx_state_reset(void* state, void* ws, const int32_t* flags, const int32_t* root, int B, int beam, int T_cap, void* stream) {
+    if (!state || !ws || !flags || !root) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_ctx_state_reset: null pointer");
+    return pb_ctx_state_launch("asr_ctc_prefix_beam_ctx_state_reset", state, ws, flags, root, B, beam, T_cap, stream);
+}
+
+extern "C" int asr_ctc_prefix_beam_chunk_ctx(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* n_valid, void* state, void* ws,
+                                             size_t ws_bytes, const asr_context_graph* ctx, int32_t* out_tok, int32_t* out_len, float* out_score,
+                                             double* out_bias, int32_t* out_state, int32_t* out_stable, int B, int C, int k, int beam, int nbest, int Lcap,
+                                             int T_cap, int blank, void* stream) {
+    if (!vals || !ids || !blank_lp || !n_valid || !state || !ws || !out_tok || !out_len || !out_score || !out_bias || !out_state || !out_stable)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_ctx: null pointer");
+    if (const char* why = pb_ctx_check(ctx)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_ctx: %s", why);
+    if (B <= 0 || C < 1 || T_cap < 1 || k <= 0 || beam <= 0 || nbest <= 0 || Lcap <= 0)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_ctx: bad shape B=%d C=%d T_cap=%d k=%d beam=%d nbest=%d Lcap=%d", B, C, T_cap, k, beam, nbest, Lcap);
+    if (beam > PB_MAX_BEAM || k > PB_MAX_K || beam * (k + 1) > 64 || nbest > beam)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_ctx: one wave ranks the beam * (k + 1) candidates of a frame: beam * (k + 1) <= 64, beam <= %d, nbest <= beam (beam=%d k=%d nbest=%d)", PB_MAX_BEAM, beam, k, nbest);
+    if ((size_t)T_cap * beam + 1 > (size_t)INT_MAX) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_ctx: T_cap * beam + 1 nodes do not fit an int32 (T_cap=%d beam=%d)", T_cap, beam);
+    if (((uintptr_t)state % 8) || ((uintptr_t)out_bias % 8) || (((uintptr_t)vals | (uintptr_t)ids | (uintptr_t)blank_lp | (uintptr_t)n_valid | (uintptr_t)out_tok | (uintptr_t)out_len | (uintptr_t)out_score | (uintptr_t)out_state | (uintptr_t)out_stable) % 4))
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_ctx: misaligned pointer (state and out_bias: 8 bytes, the others: 4)");
+    if (ws_bytes < asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam) || ((uintptr_t)ws % 4))
+        ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_chunk_ctx: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam), ws_bytes);
+    PbCtxArgs<true> cx{pb_ctx_of(ctx), nullptr, out_bias, out_state};
+    ctc_prefix_beam_chunk_kernel<true><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score,
+                                                                          out_stable, C, k, beam, nbest, Lcap, T_cap, blank, cx);
+    ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_chunk_ctx");
     return ASR_OK;
 }
 

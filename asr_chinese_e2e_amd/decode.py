@@ -165,7 +165,28 @@ def _logadd(a, b):
     return m + math.log(math.exp(a - m) + math.exp(b - m))
 
 
-def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on_device=None):
+def context_entries(context, tok, ln, sc, bias, state, nbest=None):
+    """One utterance's result list under hotword biasing from the search's outputs in beam rank order (rows of tokens, lengths with -1
+    for missing ranks, log p, raw bias, context state): bias = raw bias - held(state), score = ctc_score + bias, ordered by score
+    (a stable sort of the rank order), cut to nbest."""
+    out = []
+    for r in range(len(ln)):
+        if ln[r] < 0:
+            continue
+        b = float(bias[r]) - context.held(int(state[r]))
+        out.append({"yseq": [int(x) for x in tok[r][:ln[r]]], "score": float(sc[r]) + b, "ctc_score": float(sc[r]), "bias": b})
+    out.sort(key=lambda h: h["score"], reverse=True)
+    return out if nbest is None else out[:nbest]
+
+
+def _check_context(model, context):
+    from .context import ContextGraph
+    if not isinstance(context, ContextGraph):
+        raise TypeError(f"context must be a context.ContextGraph (got {type(context).__name__})")
+    context.check_vocab(model.V)
+
+
+def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on_device=None, context=None, context_ids=None):
     """CTC prefix beam search (Hannun et al. 2014, algorithm 1 without a language model) over the CTC head's posteriors:
     per utterance a list of at most `nbest` dicts {'yseq': [ids], 'score': log p(yseq | x)}, best first.
     Everything runs on the GPU: encoder, CTC projection, per frame the `frame_topk` best classes with their log-softmax values
@@ -173,7 +194,13 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
     prefixes as trie nodes; 2 ms per batch of 32 x 500 frames against 630 ms for the host loop below).  on_device=False (or a
     beam / top-k beyond the kernel's beam * (frame_topk + 1) <= 64) selects the host loop over the same candidates - the
     restatement the kernel is tested against, written like the reference's own search (a host loop, transformer_official.py:358-420).
-    SURVEY.md 8(f) rank 1; the reference has no CTC (its greedy_search / beam_search are empty stubs, :106-110)."""
+    SURVEY.md 8(f) rank 1; the reference has no CTC (its greedy_search / beam_search are empty stubs, :106-110).
+    context (a context.ContextGraph): hotword biasing - hypotheses that spell the graph's phrases are preferred (candidates of a frame
+    are ranked by log p + bias; only tokens among the frame's `frame_topk` can be chosen).  context_ids[b] = the graph of utterance b
+    (None: graph 0 for all, -1: not biased).  Entries are then {'yseq', 'score' = ctc_score + bias, 'ctc_score' = log p(yseq | x),
+    'bias'}, ordered by score.  Without a context the call and its result are unchanged."""
+    if context is None and context_ids is not None:
+        raise ValueError("context_ids needs a context")
     eng = model._ensure_engine(input.wave.device)
     if not eng.use_ctc:
         raise RuntimeError("this model has no CTC head (config.ctc_weight = 0)")
@@ -185,6 +212,10 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
         eng.training = was_training
     logits = out.ctc_logits                                    # (B, T, V)
     B, T, V = logits.shape
+    if context is not None:
+        _check_context(model, context)
+        graphs = [0] * B if context_ids is None else [int(g) for g in context_ids]
+        roots = context.roots(graphs, B)
     k = max(1, min(int(frame_topk), V))
     vals, ids, blank_lp = K.ctc_frame_topk(logits.reshape(B * T, V), k, BLANK_ID)
     fits = beam_size * (k + 1) <= 64 and beam_size <= 16 and nbest <= beam_size
@@ -193,6 +224,11 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
     if on_device:
         if not fits:
             raise ValueError(f"the device search ranks beam * (frame_topk + 1) <= 64 candidates per frame (beam {beam_size}, frame_topk {k})")
+        if context is not None:      # the whole beam comes back: the order by ctc_score + bias - held is settled here, then cut to nbest
+            res = K.ctc_prefix_beam(vals, ids, blank_lp, input.wave_len.to(torch.int32).contiguous(), B, T, beam_size, beam_size, BLANK_ID,
+                                    context=context, roots=roots)
+            tok, ln, sc, bias, state = (t.cpu().tolist() for t in res)
+            return [context_entries(context, tok[b], ln[b], sc[b], bias[b], state[b], nbest) for b in range(B)]
         tok, ln, sc = K.ctc_prefix_beam(vals, ids, blank_lp, input.wave_len.to(torch.int32).contiguous(), B, T, beam_size, nbest, BLANK_ID)
         tok, ln, sc = tok.cpu().tolist(), ln.cpu().tolist(), sc.cpu().tolist()
         return [[{"yseq": tok[b][r][:ln[b][r]], "score": sc[b][r]} for r in range(nbest) if ln[b][r] >= 0] for b in range(B)]
@@ -200,6 +236,17 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
     lens = input.wave_len.cpu().tolist()
     results = []
     for b in range(B):
+        if context is not None:      # the same loop; a prefix's (state, bias) is a function of the prefix (ContextGraph.walk)
+            g = graphs[b]
+            walked = {}
+
+            def rank(kv):
+                if kv[0] not in walked:
+                    walked[kv[0]] = context.walk(g, kv[0])
+                tot = _logadd(kv[1][0], kv[1][1])
+                return tot + walked[kv[0]][1] if tot != -math.inf else tot
+        else:
+            rank = lambda kv: _logadd(kv[1][0], kv[1][1])      # noqa: E731
         beam = {(): (0.0, -math.inf)}                        # prefix -> (log p ending in blank, log p ending in a symbol)
         for t in range(int(lens[b])):
             lb = blank_lp[b][t]
@@ -220,8 +267,19 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
                     else:
                         new = nxt.setdefault(prefix + (c,), [-math.inf, -math.inf])
                         new[1] = _logadd(new[1], tot + lp)
-            ranked = sorted(nxt.items(), key=lambda kv: _logadd(kv[1][0], kv[1][1]), reverse=True)[:beam_size]
+            ranked = sorted(nxt.items(), key=rank, reverse=True)[:beam_size]
             beam = {p: (v[0], v[1]) for p, v in ranked}
+        if context is not None:
+            ents = []
+            for p, v in sorted(beam.items(), key=rank, reverse=True):
+                tot = _logadd(v[0], v[1])
+                if tot == -math.inf:
+                    continue
+                st, raw = context.walk(g, p)
+                bias = raw - context.held(st)
+                ents.append({"yseq": list(p), "score": tot + bias, "ctc_score": tot, "bias": bias})
+            results.append(sorted(ents, key=lambda h: h["score"], reverse=True)[:nbest])
+            continue
         final = sorted(((p, _logadd(v[0], v[1])) for p, v in beam.items()), key=lambda kv: kv[1], reverse=True)[:nbest]
         results.append([{"yseq": list(p), "score": sc} for p, sc in final])
     return results
@@ -285,7 +343,9 @@ def attention_rescore(model, enc, wave_len, nbest_lists, ctc_weight):
     joint_beam_search repeats its logits.  Returns per utterance the list sorted by score = ctc_weight * ctc_score + (1 - ctc_weight) *
     att_score (joint_beam_search's convention; ties keep the CTC order), entries {'yseq', 'score', 'att_score', 'ctc_score'}.  Missing
     ranks are skipped, an empty hypothesis scores log p(eos | sos), a hypothesis longer than the positional-encoding table admits gets
-    att_score = score = -inf and so stays behind the others in its CTC order."""
+    att_score = score = -inf and so stays behind the others in its CTC order.
+    Entries of a hotword-biased search (they carry 'bias' and a pure 'ctc_score'): score = ctc_weight * (ctc_score + bias) + (1 -
+    ctc_weight) * att_score; ctc_score stays pure and 'bias' is kept."""
     eng = model._ensure_engine(enc.device)
     if not eng.use_decoder:
         raise RuntimeError("attention rescoring needs a model with the attention decoder")
@@ -325,6 +385,11 @@ def attention_rescore(model, enc, wave_len, nbest_lists, ctc_weight):
         cands = []
         for j, h in enumerate(nbest_lists[b]):
             a = att[b * n + j] if fits[b][j] else -math.inf
+            if "bias" in h:
+                ctc, bias = float(h["ctc_score"]), float(h["bias"])
+                sc = lam * (ctc + bias) + (1.0 - lam) * a if a != -math.inf else -math.inf
+                cands.append(dict(yseq=list(seqs[b][j]), score=sc, att_score=a, ctc_score=ctc, bias=bias))
+                continue
             ctc = float(h["score"])
             sc = lam * ctc + (1.0 - lam) * a if a != -math.inf else -math.inf
             cands.append(dict(yseq=list(seqs[b][j]), score=sc, att_score=a, ctc_score=ctc))
@@ -332,10 +397,10 @@ def attention_rescore(model, enc, wave_len, nbest_lists, ctc_weight):
     return out
 
 
-def ctc_rescore_search(model, input, beam_size=5, nbest=1, ctc_weight=0.0, frame_topk=10):
+def ctc_rescore_search(model, input, beam_size=5, nbest=1, ctc_weight=0.0, frame_topk=10, context=None, context_ids=None):
     """The U2 two-pass search offline: ctc_prefix_beam_search with n-best = beam_size, then attention_rescore of that list against the
     same encoder output (the encoder runs once).  Returns per utterance at most `nbest` {'yseq' (no sos / eos), 'score', 'att_score',
-    'ctc_score'}."""
+    'ctc_score'}.  context / context_ids: the first pass is hotword-biased (ctc_prefix_beam_search); entries gain 'bias'."""
     eng = model._ensure_engine(input.wave.device)
     if not (eng.use_ctc and eng.use_decoder):
         raise RuntimeError("CTC n-best rescoring needs a model with both the attention decoder and the CTC head (0 < config.ctc_weight < 1)")
@@ -346,7 +411,7 @@ def ctc_rescore_search(model, input, beam_size=5, nbest=1, ctc_weight=0.0, frame
     finally:
         eng.training = was_training
     with model.given_encoder_output(enc):
-        hyps = ctc_prefix_beam_search(model, input, beam_size, beam_size, frame_topk)
+        hyps = ctc_prefix_beam_search(model, input, beam_size, beam_size, frame_topk, context=context, context_ids=context_ids)
     res = attention_rescore(model, enc, input.wave_len, hyps, ctc_weight)
     return [r[:nbest] for r in res]
 

@@ -426,9 +426,20 @@ def ctc_frame_topk(logits, k, blank=0):
     return vals, ids, blank_lp
 
 
-def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max_len=None):
+def _context_roots(context, roots, B, device):
+    """The per-utterance roots of a ContextGraph as host ints and as an int32 device tensor (roots=None: graph 0 for all)."""
+    host = [context.root(0)] * B if roots is None else [int(r) for r in roots]
+    if len(host) != B or any(r < -1 or r >= context.S for r in host):
+        raise ValueError(f"context roots must hold {B} states in [-1, {context.S}), got {host}")
+    return host, torch.tensor(host, dtype=torch.int32, device=device)
+
+
+def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max_len=None, context=None, roots=None):
     """CTC prefix beam search on the device over the per-frame candidates of ctc_frame_topk (include/asr_hip.h).
-    Returns (tokens (B, nbest, Lcap) int32, lengths (B, nbest) int32 with -1 for missing ranks, scores (B, nbest) float32)."""
+    Returns (tokens (B, nbest, Lcap) int32, lengths (B, nbest) int32 with -1 for missing ranks, scores (B, nbest) float32).
+    context (a context.ContextGraph): the hotword-biased search (asr_ctc_prefix_beam_ctx) - roots = the root state of each utterance's
+    graph (-1: not biased; None: graph 0 for all); the result gains (bias (B, nbest) float64, the raw bias before held(state) is taken
+    off, state (B, nbest) int32), and the entries are in the beam's rank order (log p + raw bias)."""
     k = vals.shape[1]
     assert vals.shape == (B * T, k) and ids.shape == (B * T, k) and blank_lp.numel() == B * T
     _chk_f32(vals, blank_lp)
@@ -438,6 +449,15 @@ def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max
     out_tok = torch.zeros(B, nbest, Lcap, dtype=torch.int32, device=vals.device)
     out_len = torch.empty(B, nbest, dtype=torch.int32, device=vals.device)
     out_score = torch.empty(B, nbest, dtype=torch.float32, device=vals.device)
+    if context is not None:
+        _, root_dev = _context_roots(context, roots, B, vals.device)
+        _, tabs = context.on(vals.device)
+        out_bias = torch.empty(B, nbest, dtype=torch.float64, device=vals.device)
+        out_state = torch.empty(B, nbest, dtype=torch.int32, device=vals.device)
+        check(lib.asr_ctc_prefix_beam_ctx(_p(vals), _p(ids), _p(blank_lp), _p(in_len), _p(root_dev), ctypes.addressof(tabs), _p(ws), ws.numel(),
+                                          _p(out_tok), _p(out_len), _p(out_score), _p(out_bias), _p(out_state), B, T, k, int(beam), int(nbest), Lcap,
+                                          int(blank), _stream()), "asr_ctc_prefix_beam_ctx")
+        return out_tok, out_len, out_score, out_bias, out_state
     check(lib.asr_ctc_prefix_beam(_p(vals), _p(ids), _p(blank_lp), _p(in_len), _p(ws), ws.numel(), _p(out_tok), _p(out_len), _p(out_score),
                                   B, T, k, int(beam), int(nbest), Lcap, int(blank), _stream()), "asr_ctc_prefix_beam")
     return out_tok, out_len, out_score
@@ -446,18 +466,27 @@ def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max
 class PrefixBeamState:
     """The resumable prefix beam search's device memory (include/asr_hip.h): `state` (the beam of each utterance between chunks) and
     `ws` (the trie, room for T_cap frames per utterance); `frames` = frames consumed per utterance, kept on the host so that a
-    chunk past T_cap is refused before any launch."""
+    chunk past T_cap is refused before any launch.  context: the ContextGraph of a context state (None: a plain state) - a context state
+    is larger (bias, context state and root per utterance) and only ever reaches the _ctx entry points."""
 
-    def __init__(self, state, ws, B, beam, T_cap):
+    def __init__(self, state, ws, B, beam, T_cap, context=None, roots=None):
         self.state, self.ws, self.B, self.beam, self.T_cap = state, ws, B, beam, T_cap
         self.frames = [0] * B
+        self.context, self.roots = context, roots
 
 
-def ctc_prefix_beam_state(B, beam, T_cap, device="cuda"):
-    """A fresh PrefixBeamState: the empty-prefix beam for B utterances of at most T_cap frames each."""
+def ctc_prefix_beam_state(B, beam, T_cap, device="cuda", context=None, roots=None):
+    """A fresh PrefixBeamState: the empty-prefix beam for B utterances of at most T_cap frames each.  context / roots: a context
+    state for the hotword-biased search (roots as ctc_prefix_beam's)."""
     B, beam, T_cap = int(B), int(beam), int(T_cap)
     if B < 1 or beam < 1 or T_cap < 1:
         raise ValueError(f"ctc_prefix_beam_state: B, beam and T_cap must be >= 1 (got {B}, {beam}, {T_cap})")
+    if context is not None:
+        host, root_dev = _context_roots(context, roots, B, device)
+        state = torch.zeros(lib.asr_ctc_prefix_beam_ctx_state_bytes(B, beam) // 8, dtype=torch.int64, device=device)      # 8-aligned
+        ws = torch.empty(lib.asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam), dtype=torch.uint8, device=device)
+        check(lib.asr_ctc_prefix_beam_ctx_state_init(_p(state), _p(ws), _p(root_dev), B, beam, T_cap, _stream()), "asr_ctc_prefix_beam_ctx_state_init")
+        return PrefixBeamState(state, ws, B, beam, T_cap, context, host)
     state = torch.zeros(lib.asr_ctc_prefix_beam_state_bytes(B, beam) // 8, dtype=torch.int64, device=device)      # 8-aligned
     ws = torch.empty(lib.asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam), dtype=torch.uint8, device=device)
     check(lib.asr_ctc_prefix_beam_state_init(_p(state), _p(ws), B, beam, T_cap, _stream()), "asr_ctc_prefix_beam_state_init")
@@ -473,6 +502,22 @@ def prefix_beam_unpack(buf, B, nbest, Lcap):
             buf[tok_n + len_n:tok_n + 2 * len_n].view(torch.float32).view(B, nbest), buf[tok_n + 2 * len_n:])
 
 
+def prefix_beam_ctx_words(B, nbest, Lcap):
+    """int32 words of a context state's packed result: the plain B * (nbest * (Lcap + 2) + 1), one pad word if that is odd (the fp64
+    bias is 8-aligned), then bias (2 words per entry) and state (1 word per entry)."""
+    n = B * (nbest * (Lcap + 2) + 1)
+    return n + (n & 1) + 3 * B * nbest
+
+
+def prefix_beam_ctx_unpack(buf, B, nbest, Lcap):
+    """(bias (B, nbest) float64 - raw, before held(state) is taken off -, state (B, nbest) int32) as views of a context state's packed
+    result of prefix_beam_ctx_words(B, nbest, Lcap) words; its first B * (nbest * (Lcap + 2) + 1) words are prefix_beam_unpack's."""
+    n = B * (nbest * (Lcap + 2) + 1)
+    n += n & 1
+    assert buf.dtype == torch.int32 and buf.numel() == n + 3 * B * nbest and buf.is_contiguous()
+    return buf[n:n + 2 * B * nbest].view(torch.float64).view(B, nbest), buf[n + 2 * B * nbest:].view(B, nbest)
+
+
 def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, max_len=None, packed=False, nv_dev=None, extra_words=0):
     """One chunk of the resumable search: vals / ids (B*C, k), blank_lp (B*C) = the chunk's rows of ctc_frame_topk; n_valid = the
     frames of each utterance to consume (a list of B ints in [0, C]).  A chunk that would take an utterance past st.T_cap frames raises
@@ -481,7 +526,9 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
     packed=True returns (that buffer, Lcap) instead, so that one copy brings all four to the host.  Lcap = max_len, by default the most
     frames any utterance has consumed after this chunk: no prefix is longer than that.  nv_dev: n_valid as an int32 device tensor the
     caller has uploaded already; extra_words (packed only): int32 words left free behind the results in the returned buffer, for
-    what else travels to the host in the same copy."""
+    what else travels to the host in the same copy.
+    A context state (st.context): the biased search (asr_ctc_prefix_beam_chunk_ctx); the result gains bias (B, nbest) float64 (raw) and
+    state (B, nbest) int32, and the packed buffer grows to prefix_beam_ctx_words (prefix_beam_ctx_unpack reads the two)."""
     B, beam, k = st.B, st.beam, vals.shape[1]
     C, nbest = int(C), int(nbest)
     nv = [int(x) for x in n_valid]
@@ -495,12 +542,22 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
     _chk_i32(ids)
     Lcap = int(max(1, max(f + n for f, n in zip(st.frames, nv))) if max_len is None else max_len)
     n_words = B * (nbest * (Lcap + 2) + 1)
-    out = torch.zeros(n_words + (int(extra_words) if packed else 0), dtype=torch.int32, device=vals.device)
+    n_all = n_words if st.context is None else prefix_beam_ctx_words(B, nbest, Lcap)
+    out = torch.zeros(n_all + (int(extra_words) if packed else 0), dtype=torch.int32, device=vals.device)
     out_tok, out_len, out_score, out_stable = prefix_beam_unpack(out[:n_words], B, nbest, Lcap)
     if nv_dev is None:
         nv_dev = torch.tensor(nv, dtype=torch.int32, device=vals.device)
     _chk_i32(nv_dev)
     assert nv_dev.numel() == B
+    if st.context is not None:
+        out_bias, out_state = prefix_beam_ctx_unpack(out[:n_all], B, nbest, Lcap)
+        _, tabs = st.context.on(vals.device)
+        check(lib.asr_ctc_prefix_beam_chunk_ctx(_p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(), ctypes.addressof(tabs),
+                                                _p(out_tok), _p(out_len), _p(out_score), _p(out_bias), _p(out_state), _p(out_stable), B, C, k, beam, nbest,
+                                                Lcap, st.T_cap, int(blank), _stream()), "asr_ctc_prefix_beam_chunk_ctx")
+        for b in range(B):
+            st.frames[b] += nv[b]
+        return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable, out_bias, out_state)
     check(lib.asr_ctc_prefix_beam_chunk(_p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(), _p(out_tok), _p(out_len),
                                         _p(out_score), _p(out_stable), B, C, k, beam, nbest, Lcap, st.T_cap, int(blank), _stream()),
           "asr_ctc_prefix_beam_chunk")
@@ -509,11 +566,22 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
     return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable)
 
 
-def ctc_prefix_beam_state_reset(st, flags, slots=()):
+def ctc_prefix_beam_state_reset(st, flags, slots=(), roots=None):
     """Re-initialise the utterances of a PrefixBeamState whose flags[b] != 0 (flags: (B) int32 on the device; `slots`: the same
-    utterances as host ints, for the host-side frame counters): byte for byte what ctc_prefix_beam_state leaves for them."""
+    utterances as host ints, for the host-side frame counters): byte for byte what ctc_prefix_beam_state leaves for them.
+    A context state: roots = the B roots after the reset (those of the flagged utterances are applied; None: all as they are)."""
     _chk_i32(flags)
     assert flags.numel() == st.B
+    if st.context is not None:
+        host, root_dev = _context_roots(st.context, st.roots if roots is None else roots, st.B, st.state.device)
+        check(lib.asr_ctc_prefix_beam_ctx_state_reset(_p(st.state), _p(st.ws), _p(flags), _p(root_dev), st.B, st.beam, st.T_cap, _stream()),
+              "asr_ctc_prefix_beam_ctx_state_reset")
+        for b in slots:
+            st.frames[int(b)] = 0
+            st.roots[int(b)] = host[int(b)]
+        return
+    if roots is not None:
+        raise ValueError("ctc_prefix_beam_state_reset: roots apply to a context state")
     check(lib.asr_ctc_prefix_beam_state_reset(_p(st.state), _p(st.ws), _p(flags), st.B, st.beam, st.T_cap, _stream()), "asr_ctc_prefix_beam_state_reset")
     for b in slots:
         st.frames[int(b)] = 0

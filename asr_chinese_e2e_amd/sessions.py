@@ -73,7 +73,7 @@ def endpoint_rule(rules, frame_us, trailing, frames, decoded):
 
 
 class Sessions:
-    def __init__(self, model, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None):
+    def __init__(self, model, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None):
         C, left = model.decoding_chunk_size, model.decoding_left_chunks
         if C <= 0:
             raise ValueError("model.sessions() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
@@ -92,6 +92,14 @@ class Sessions:
             if self.beam_size < 1 or self.beam_size > 16 or self.beam_size * (k + 1) > 64:
                 raise ValueError(f"the device search ranks beam * (frame_topk + 1) <= 64 candidates per frame, beam <= 16 (beam {beam_size}, frame_topk {k})")
             self.frame_topk = k
+        # hotword biasing (context.ContextGraph): open(b, context=i) picks slot b's graph; the reset kernel applies it on the slot's first tick
+        self.context = context
+        if context is not None:
+            if search != "prefix_beam":
+                raise ValueError("hotword biasing (context=...) is supported by search='prefix_beam' (the CTC prefix beam search), not by search='greedy'")
+            from . import decode
+            decode._check_context(model, context)
+        self.graph = [0 if context is not None else -1] * self.S      # the graph of each slot's session (-1: not biased)
         self.endpoint = endpoint_config(endpoint)
         thr = self.endpoint["blank_threshold"] if self.endpoint else ENDPOINT_DEFAULTS["blank_threshold"]
         self.silence_lp = math.log(thr)      # the kernel compares float32(log threshold) with float32 log p(blank)
@@ -120,11 +128,19 @@ class Sessions:
             raise ValueError(f"slot {b} of {self.S}")
         return b
 
-    def open(self, b):
-        """Slot b (free) starts a session at frame 0."""
+    def open(self, b, context=None):
+        """Slot b (free) starts a session at frame 0.  context (sessions with a ContextGraph): the graph that biases this session
+        (default 0; -1: none) - fixed while the session is open."""
         b = self._slot(b)
         if self.state[b] != FREE:
             raise ValueError(f"open: slot {b} is {self.state[b]} (finish or drop it first)")
+        if self.context is None:
+            if context is not None:
+                raise ValueError("open(context=...) needs model.sessions(..., context=ContextGraph(...))")
+        else:
+            graph = 0 if context is None else int(context)
+            self.context.root(graph)      # an unknown graph raises here
+            self.graph[b] = graph
         self.state[b], self.frames[b], self.clen[b], self.fresh[b] = OPEN, 0, 0, True
         self.trailing[b], self.decoded[b], self.stable[b] = 0, False, 0
         if self.frontend is not None:
@@ -269,18 +285,22 @@ class Sessions:
                     self.ctc_state = torch.zeros(S, 4, dtype=torch.int32, device=dev)
                 logits = eng.ctc_lo.fwd(h)
                 if self.search == "prefix_beam":
+                    roots = None if self.context is None else self.context.roots(self.graph, S)
                     if self.beam is None:
-                        self.beam = K.ctc_prefix_beam_state(S, self.beam_size, eng.pe.shape[0], dev)
+                        self.beam = K.ctc_prefix_beam_state(S, self.beam_size, eng.pe.shape[0], dev, context=self.context, roots=roots)
                     elif reset_slots:
-                        K.ctc_prefix_beam_state_reset(self.beam, pd[P_RESET], reset_slots)
+                        K.ctc_prefix_beam_state_reset(self.beam, pd[P_RESET], reset_slots, roots=roots)
                     vals, ids, blank_lp = K.ctc_frame_topk(logits, self.frame_topk, BLANK)
                     buf, Lcap = K.ctc_prefix_beam_chunk(self.beam, vals, ids, blank_lp, nv, C, self.beam_size, BLANK, packed=True, nv_dev=nv_dev,
                                                         extra_words=S * (4 + C))
-                    n_words = buf.numel() - S * (4 + C)
+                    n_words = buf.numel() - S * (4 + C)      # the search's words (with a context: bias and state included)
                     K.session_ctc_step(None, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK, out=buf[n_words:].view(S, 4 + C))
                     host = buf.cpu()
-                    tok, ln, sc, stable = (t.numpy() for t in K.prefix_beam_unpack(host[:n_words], S, self.beam_size, Lcap))
+                    n_plain = S * (self.beam_size * (Lcap + 2) + 1)
+                    tok, ln, sc, stable = (t.numpy() for t in K.prefix_beam_unpack(host[:n_plain], S, self.beam_size, Lcap))
                     self._hyps = (tok, ln, sc)
+                    if self.context is not None:
+                        self._hyps += tuple(t.numpy() for t in K.prefix_beam_ctx_unpack(host[:n_words], S, self.beam_size, Lcap))
                     step = host[n_words:].view(S, 4 + C).tolist()
                     for b in reset_slots:
                         self.stable[b] = 0
@@ -354,20 +374,28 @@ class Sessions:
             raise ValueError(f"{what} needs sessions opened with search='prefix_beam'")
 
     def nbest(self, b):
-        """search="prefix_beam": slot b's current list of {"yseq", "score"}, best first (at most beam_size)."""
+        """search="prefix_beam": slot b's current list of {"yseq", "score"}, best first (at most beam_size).  With a context:
+        {"yseq", "score", "ctc_score", "bias"}, ordered by score = ctc_score + bias."""
         self._need_beam("nbest()")
         b = self._slot(b)
         if self.state[b] == FREE:
             raise ValueError(f"nbest: slot {b} is free")
         if self._hyps is None or self.fresh[b]:
-            return [{"yseq": [], "score": 0.0}]
+            return [{"yseq": [], "score": 0.0, "ctc_score": 0.0, "bias": 0.0}] if self.context is not None else [{"yseq": [], "score": 0.0}]
+        if self.context is not None:
+            from .decode import context_entries
+            tok, ln, sc, bias, state = self._hyps
+            return context_entries(self.context, tok[b], ln[b], sc[b], bias[b], state[b])
         tok, ln, sc = self._hyps
         return [{"yseq": tok[b, r, :ln[b, r]].tolist(), "score": float(sc[b, r])} for r in range(self.beam_size) if ln[b, r] >= 0]
 
     def partial(self, b):
         """search="prefix_beam": {"ids": slot b's best prefix now, "stable_len": how many of its tokens are final, "score"}."""
         h = self.nbest(b)
-        return {"ids": h[0]["yseq"] if h else [], "stable_len": self.stable[self._slot(b)], "score": h[0]["score"] if h else float("-inf")}
+        out = {"ids": h[0]["yseq"] if h else [], "stable_len": self.stable[self._slot(b)], "score": h[0]["score"] if h else float("-inf")}
+        if self.context is not None:
+            out["bias"] = h[0]["bias"] if h else 0.0
+        return out
 
     def encoder_output(self, slots):
         """(enc (n, T, d), lengths (n,) int32) of the listed slots: T = the longest, rounded up to whole chunks; rows past a slot's
@@ -397,6 +425,9 @@ class Sessions:
         if rescore:
             self._need_beam("finish(joint='ctc_rescore')")
         res = [{"text": "", "ids": [], "score": float("-inf"), "tokens": [] if timestamps else None} for _ in slots]
+        if self.context is not None:
+            for r in res:
+                r["bias"] = 0.0
         live = [i for i, b in enumerate(slots) if self.frames[b] > 0]
         if live:
             rows = [slots[i] for i in live]
@@ -410,16 +441,18 @@ class Sessions:
                     hyps = decode.attention_rescore(model, enc, lens, hyps, w)
                 ids = [list(h[0]["yseq"]) if h else [] for h in hyps]
                 scores = [float(h[0]["score"]) if h else float("-inf") for h in hyps]
+                biases = [float(h[0]["bias"]) if h else 0.0 for h in hyps] if self.context is not None else None
 
                 def ctc_logits():
                     with torch.no_grad():
                         return self.eng.ctc_lo.fwd(enc.reshape(n * T, -1).contiguous()).view(n, T, -1)
-                got = model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens)
+                got = model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens, biases)
             else:
                 # under given_encoder_output the searches take the batch's features for their (B, T) only: none are kept
                 wave = torch.zeros(n, T, 1, dtype=enc.dtype, device=enc.device)
+                ctx = dict(context=self.context, context_ids=[self.graph[b] for b in rows]) if self.context is not None else {}
                 with model.given_encoder_output(enc):
-                    got = model.transcribe(Pack(wave=wave, wave_len=lens), beam_size=beam_size, **kw)
+                    got = model.transcribe(Pack(wave=wave, wave_len=lens), beam_size=beam_size, **kw, **ctx)
             for i, r in zip(live, got):
                 res[i] = r
         for b in slots:

@@ -26,7 +26,7 @@ BLANK = 0      # the CTC blank (= PAD_ID of the model)
 
 
 class StreamingEncoder:
-    def __init__(self, model, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10):
+    def __init__(self, model, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None):
         C, left = model.decoding_chunk_size, model.decoding_left_chunks
         if C <= 0:
             raise ValueError("model.stream() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
@@ -52,9 +52,20 @@ class StreamingEncoder:
             if self.beam_size < 1 or self.beam_size > 16 or self.beam_size * (k + 1) > 64:
                 raise ValueError(f"the device search ranks beam * (frame_topk + 1) <= 64 candidates per frame, beam <= 16 (beam {beam_size}, frame_topk {k})")
             self.frame_topk = k
+        # hotword biasing (context.ContextGraph): the streamed search ranks by log p + bias; context_ids = the graph per utterance
+        self.context, self.roots = context, None
+        if context is None and context_ids is not None:
+            raise ValueError("context_ids needs a context")
+        if context is not None:
+            if search != "prefix_beam":
+                raise ValueError("hotword biasing (context=...) is supported by search='prefix_beam' (the CTC prefix beam search), not by search='greedy'")
+            from . import decode
+            decode._check_context(model, context)
+            self.graphs = [0] * self.B if context_ids is None else [int(g) for g in context_ids]
+            self.roots = context.roots(self.graphs, self.B)
         self.beam = None                     # K.PrefixBeamState, allocated by the first push for the positional-encoding table's frames
         self.stable = [0] * self.B           # tokens of each utterance handed out by push so far (beam mode)
-        self._hyps = None                    # the last push's (tokens, lengths, scores) as host arrays
+        self._hyps = None                    # the last push's (tokens, lengths, scores) as host arrays; with a context also (bias, state)
         self.parser, self.frontend = parser, None      # the front end is built by the first push_audio
         # source_rate: the rate of the audio push_audio receives; other than 16 kHz it goes through a StreamResampler first (None: 16 kHz)
         self.source_rate, self.resampler = source_rate, None
@@ -143,14 +154,18 @@ class StreamingEncoder:
                 out = [[] for _ in range(B)]
                 if self.search == "prefix_beam":
                     if self.beam is None:      # the trie for every frame push admits: B * 2 * (table * beam + 1) * 4 bytes
-                        self.beam = K.ctc_prefix_beam_state(B, self.beam_size, eng.pe.shape[0], dev)
+                        self.beam = K.ctc_prefix_beam_state(B, self.beam_size, eng.pe.shape[0], dev, context=self.context, roots=self.roots)
                     vals, ids, blank_lp = K.ctc_frame_topk(eng.ctc_lo.fwd(h), self.frame_topk, BLANK)
                     buf, Lcap = K.ctc_prefix_beam_chunk(self.beam, vals, ids, blank_lp, nv, C, self.beam_size, BLANK, packed=True)
-                    # one copy: tokens, lengths, scores and stable lengths travel in one buffer
+                    # one copy: tokens, lengths, scores and stable lengths (with a context also bias and state) travel in one buffer
                     # (kept as arrays: the token rows are Lcap wide, and only the first `length` of each are ever turned into lists)
-                    tok, ln, sc, stable = (t.numpy() for t in K.prefix_beam_unpack(buf.cpu(), B, self.beam_size, Lcap))
+                    host = buf.cpu()
+                    n_words = B * (self.beam_size * (Lcap + 2) + 1)
+                    tok, ln, sc, stable = (t.numpy() for t in K.prefix_beam_unpack(host[:n_words], B, self.beam_size, Lcap))
                     self._hyps = (tok, ln, sc)
-                    for b in range(B):
+                    if self.context is not None:
+                        self._hyps += tuple(t.numpy() for t in K.prefix_beam_ctx_unpack(host, B, self.beam_size, Lcap))
+                    for b in range(B):      # every entry shares the stable prefix, so rank 0 spells it whatever the order by score
                         out[b] = tok[b, 0, self.stable[b]:int(stable[b])].tolist()
                         self.stable[b] = int(stable[b])
                 elif model.use_ctc:
@@ -215,19 +230,31 @@ class StreamingEncoder:
             raise ValueError(f"{what} needs a stream opened with search='prefix_beam'")
 
     def nbest(self):
-        """search="prefix_beam": per utterance the search's current list of {"yseq", "score"}, best first (at most beam_size)."""
+        """search="prefix_beam": per utterance the search's current list of {"yseq", "score"}, best first (at most beam_size).
+        With a context: {"yseq", "score", "ctc_score", "bias"}, ordered by score = ctc_score + bias."""
         self._need_beam("nbest()")
         if self._hyps is None:
+            if self.context is not None:
+                return [[{"yseq": [], "score": 0.0, "ctc_score": 0.0, "bias": 0.0}] for _ in range(self.B)]
             return [[{"yseq": [], "score": 0.0}] for _ in range(self.B)]
+        if self.context is not None:
+            from .decode import context_entries
+            tok, ln, sc, bias, state = self._hyps
+            return [context_entries(self.context, tok[b], ln[b], sc[b], bias[b], state[b]) for b in range(self.B)]
         tok, ln, sc = self._hyps
         return [[{"yseq": tok[b, r, :ln[b, r]].tolist(), "score": float(sc[b, r])} for r in range(self.beam_size) if ln[b, r] >= 0]
                 for b in range(self.B)]
 
     def partial(self):
         """search="prefix_beam": per utterance {"ids": the best prefix now (revisable past stable_len), "stable_len": how many of its
-        tokens are final (the concatenation of what push returned), "score": its log-probability}."""
-        return [{"ids": h[0]["yseq"] if h else [], "stable_len": self.stable[b], "score": h[0]["score"] if h else float("-inf")}
-                for b, h in enumerate(self.nbest())]
+        tokens are final (the concatenation of what push returned), "score": its log-probability}; with a context also "bias" (and the
+        score includes it)."""
+        out = [{"ids": h[0]["yseq"] if h else [], "stable_len": self.stable[b], "score": h[0]["score"] if h else float("-inf")}
+               for b, h in enumerate(self.nbest())]
+        if self.context is not None:
+            for o, h in zip(out, self.nbest()):
+                o["bias"] = h[0]["bias"] if h else 0.0
+        return out
 
     def _live_only(self, timestamps, search):
         """finish() over the utterances that have a frame: search(rows) -> their result dicts, rows = their indices in the batch (every
@@ -235,6 +262,9 @@ class StreamingEncoder:
         live = [b for b in range(self.B) if self.valid[b] > 0]
         res = search(live) if live else []
         out = [{"text": "", "ids": [], "score": float("-inf"), "tokens": [] if timestamps else None} for _ in range(self.B)]
+        if self.context is not None:
+            for o in out:
+                o["bias"] = 0.0
         for b, r in zip(live, res):
             out[b] = r
         return out
@@ -255,12 +285,13 @@ class StreamingEncoder:
                 hyps = decode.attention_rescore(model, enc, lens, hyps, w)
             ids = [list(h[0]["yseq"]) if h else [] for h in hyps]
             scores = [float(h[0]["score"]) if h else float("-inf") for h in hyps]
+            biases = [float(h[0]["bias"]) if h else 0.0 for h in hyps] if self.context is not None else None
             B, T = enc.shape[0], enc.shape[1]
 
             def ctc_logits():
                 with torch.no_grad():
                     return self.eng.ctc_lo.fwd(enc.reshape(B * T, -1).contiguous()).view(B, T, -1)
-            return model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens)
+            return model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens, biases)
         return self._live_only(timestamps, search)
 
     def finish(self, beam_size=5, **kw):
@@ -275,6 +306,9 @@ class StreamingEncoder:
 
         def search(rows):
             enc, lens, wave = (all_enc, all_lens, all_wave) if len(rows) == self.B else (all_enc[rows].contiguous(), all_lens[rows], all_wave[rows].contiguous())
+            ctx = {}
+            if self.context is not None:      # a fresh offline search over the streamed encoder output, biased as the stream is
+                ctx = dict(context=self.context, context_ids=[self.graphs[b] for b in rows])
             with self.model.given_encoder_output(enc):
-                return self.model.transcribe(Pack(wave=wave, wave_len=lens), beam_size=beam_size, **kw)
+                return self.model.transcribe(Pack(wave=wave, wave_len=lens), beam_size=beam_size, **kw, **ctx)
         return self._live_only(kw.get("timestamps", True), search)

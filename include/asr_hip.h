@@ -350,6 +350,44 @@ int asr_ctc_prefix_beam_chunk(const float* vals, const int32_t* ids, const float
  *   (flags: (B) int32 on the device) - their beam and their trie's root, byte for byte what asr_ctc_prefix_beam_state_init leaves
  *   for them (one device function writes both); every other utterance keeps every byte.  Arguments and limits as state_init. */
 int asr_ctc_prefix_beam_state_reset(void* state, void* ws, const int32_t* flags, int B, int beam, int T_cap, void* stream);
+/* Hotword (context) biasing of the CTC prefix beam search (additive to ABI 10; the definition: asr_chinese_e2e_amd/context.py, restated in
+ *   fp64 by tests/context_ref.py).  asr_context_graph: the phrase lists of one or more graphs as one flat automaton on the device - arcs of
+ *   state s = [st_off[s], st_off[s + 1]) with ascending arc_tok, arc_next the state an arc leads to (an arc onto a final leaf leads to its
+ *   graph's root), st_held[s] = w * (depth(s) - depth of the deepest final state on its path), w the bonus per matched token.  A beam entry
+ *   carries (state, bias) from (root, 0.0); appending token c: an arc (state, c) -> bias += w and the state follows it; otherwise bias -=
+ *   st_held[state], the state is the root and the arc (root, c) is tried once.  Candidates of a frame are ranked by log p + bias; nothing
+ *   else of the search changes, and out_score stays log p.
+ *   THE WRAPPERS CHECK pointers, alignment (8 bytes for anything fp64), S >= 1, A >= 0 and the searches' limits; THEY CANNOT CHECK THE
+ *   TABLES' CONTENTS, which live on the device: ContextGraph is their only producer and validates them (tokens in [1, V), every arc_next <
+ *   S, arcs sorted and unique, offsets ascending within [0, A]).  The kernels still clamp every table index they form.
+ * asr_ctc_prefix_beam_ctx: asr_ctc_prefix_beam with a graph.  root: (B) int32 on the device, the root state of each utterance's graph, -1
+ *   (or anything outside [0, S)) = this utterance is not biased and gets asr_ctc_prefix_beam's outputs bit for bit.  Two more outputs per
+ *   n-best entry: out_bias (B, nbest) fp64, 8-aligned - the entry's RAW bias, st_held[out_state] is not yet taken off (the caller reports
+ *   bias - held, so that a phrase begun and not finished earns nothing) - and out_state (B, nbest) int32 (-1: no entry / not biased).  The
+ *   entries are in the beam's rank order (log p + raw bias); the caller sorts by log p + bias - held (stable).
+ * asr_ctc_prefix_beam_ctx_state_bytes / _ctx_state_init / _ctx_state_reset / asr_ctc_prefix_beam_chunk_ctx: the resumable form.  The state
+ *   of one utterance is asr_ctc_prefix_beam_chunk's, followed by fp64 bias[beam], int32 ctx[beam], int32 root, padded to 8 bytes; init and
+ *   reset take root (B) int32 on the device (reset reads it for the flagged utterances only: a reopened session may bring another list).  A
+ *   context state is only ever passed to the _ctx entry points and a plain state to the plain ones.  Cutting the frames into chunks changes
+ *   no bit of any output, and a chunk that consumes nothing changes no byte of the state, as for the plain search. */
+typedef struct asr_context_graph {
+    const int32_t* st_off;    /* device, (S + 1) */
+    const int32_t* arc_tok;   /* device, (A) */
+    const int32_t* arc_next;  /* device, (A) */
+    const double* st_held;    /* device, (S), 8-aligned */
+    int S, A;
+    double w;
+} asr_context_graph;
+int asr_ctc_prefix_beam_ctx(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* in_len, const int32_t* root,
+                            const asr_context_graph* ctx, void* ws, size_t ws_bytes, int32_t* out_tok, int32_t* out_len, float* out_score,
+                            double* out_bias, int32_t* out_state, int B, int T, int k, int beam, int nbest, int Lcap, int blank, void* stream);
+size_t asr_ctc_prefix_beam_ctx_state_bytes(int B, int beam);
+int asr_ctc_prefix_beam_ctx_state_init(void* state, void* ws, const int32_t* root, int B, int beam, int T_cap, void* stream);
+int asr_ctc_prefix_beam_ctx_state_reset(void* state, void* ws, const int32_t* flags, const int32_t* root, int B, int beam, int T_cap, void* stream);
+int asr_ctc_prefix_beam_chunk_ctx(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* n_valid, void* state, void* ws,
+                                  size_t ws_bytes, const asr_context_graph* ctx, int32_t* out_tok, int32_t* out_len, float* out_score,
+                                  double* out_bias, int32_t* out_state, int32_t* out_stable, int B, int C, int k, int beam, int nbest, int Lcap,
+                                  int T_cap, int blank, void* stream);
 int asr_decode_attn(const void* q, const void* k, const void* v, void* o, const int32_t* k_len,
                     int k_len_uniform, int len_div, int R, int H, int dk, int Tk_cap, int kv_div,
                     int ldq, int ldk, int ldv, int ldo, float scale, int dtype, void* stream);

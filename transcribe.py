@@ -41,6 +41,11 @@ trained with rebuild it.  Inference flags:
                  order of completion.  16 kHz files only.
   --endpoint     1 (with --sessions): the per-chunk lines gain "endpoint": null, or the CTC endpoint rule that fires for the file now
                  (silence_start, silence_after_speech, max_length - WeNet's rules); it only reports, the file streams on
+  --context      a UTF-8 file of hotwords, one phrase per line (every character must be in the vocabulary): the CTC prefix beam search
+                 prefers hypotheses that spell them (context.ContextGraph, one graph for all files), and the final lines gain "bias".
+                 Offline it needs a search that runs the prefix beam search (a CTC-only model, or --joint=ctc_rescore); with --stream=1
+                 (--sessions=N included) it needs --stream_search=prefix_beam
+  --context_score  the bonus per matched hotword token (default 3.0, WeNet's context_score)
 Audio goes through load_wav -> AudioParser.parse_batch on the device -> model.transcribe; one JSON line per file is printed:
 {"file", "duration_s", "text", "ids", "score", "tokens": [{"id", "token", "start_frame", "end_frame", "start_s", "end_s", "logp"}]}.
 """
@@ -62,7 +67,7 @@ from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
 from asr_chinese_e2e_amd.data_handler import resample as resample_mod  # noqa: E402
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint")
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint", "context", "context_score")
 
 
 def _finite(x):
@@ -151,6 +156,8 @@ def final_line(path, n_samples, sr, r, shift_s, sample_rate):
                 t[k] = min(t[k] + shift_s, dur)
     line = {"file": path, "duration_s": dur, "text": r["text"], "ids": r["ids"],
             "score": _finite(r["score"]), "tokens": r["tokens"]}
+    if "bias" in r:
+        line["bias"] = r["bias"]
     if sr != sample_rate:
         line["source_rate"] = sr
     return line
@@ -238,6 +245,19 @@ def transcribe(**flags):
     if stream_search == "prefix_beam" and not model.use_ctc:
         raise SystemExit("transcribe.py: --stream_search=prefix_beam needs a model with the CTC head")
     stream_kw = dict(search="prefix_beam", beam_size=beam, frame_topk=int(cli.get("frame_topk", 10))) if stream_search == "prefix_beam" else {}
+    context = None
+    if cli.get("context") not in (None, "", False):
+        from asr_chinese_e2e_amd.context import ContextGraph
+        if stream and stream_search != "prefix_beam":
+            raise SystemExit("transcribe.py: --context with --stream=1 needs --stream_search=prefix_beam (hotwords bias the CTC prefix beam search)")
+        if not stream and model.use_decoder and joint != "ctc_rescore":
+            raise SystemExit("transcribe.py: --context needs a search that runs the CTC prefix beam search: a CTC-only model or --joint=ctc_rescore")
+        try:
+            context = ContextGraph.from_file(str(cli["context"]), vocab, score=float(cli.get("context_score", 3.0)), device="cuda")
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"transcribe.py: --context: {e}") from e
+        if stream:
+            stream_kw["context"] = context
     resample = bool(int(cli.get("resample", 0)))      # --resample=1: files at another rate are converted on the GPU instead of ending the run
     if stream and model.decoding_chunk_size <= 0:
         raise SystemExit("transcribe.py: --stream=1 needs a decoding chunk (--decoding_chunk_size, or a static --chunk_size)")
@@ -282,6 +302,8 @@ def transcribe(**flags):
             else:      # one launch for the batch, whatever rates it mixes
                 wav, wav_len, _ = resample_mod.resample_batch(wav.cuda(), wav_len.tolist(), rates)
         search = dict(beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps, joint=joint)
+        if context is not None and not stream:
+            search["context"] = context
         if stream_kw:      # the streamed search's own n-best, re-ranked by the decoder
             search = dict(ctc_weight=ctc_weight, timestamps=timestamps, joint="ctc_rescore")
         if stream and parser.norm == "global":      # the samples stream: blocks of one chunk's worth of audio unless told otherwise
