@@ -329,7 +329,7 @@ class _SpeechTransformer(BaseModel):
                 self._enc_given = prev
         return ctx()
 
-    def stream(self, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None):
+    def stream(self, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None, lm=None):
         """A streaming encoder for `batch_size` utterances (stream.StreamingEncoder): push chunks of encoder-rate features, get the
         greedy CTC ids each chunk adds; finish() gives transcribe()'s result for the same decoding chunk mask.  With an AudioParser
         of norm="global" it also takes audio as it arrives: push_audio(pcm, n_samples, final) - at source_rate, converted to
@@ -338,19 +338,22 @@ class _SpeechTransformer(BaseModel):
         frame runs with the audio (asr_ctc_prefix_beam_chunk); push then returns the tokens by which the stable prefix grew, partial() /
         nbest() the revisable hypotheses, and finish(joint="ctc_rescore") re-ranks the n-best with the decoder.
         context (a context.ContextGraph; search="prefix_beam" only) / context_ids (the graph per utterance; None: graph 0, -1: none):
-        hotword biasing of the streamed search - partial(), nbest() and finish() then report 'bias' and order by 'score'."""
+        hotword biasing of the streamed search - partial(), nbest() and finish() then report 'bias' and order by 'score'.
+        lm (an lm.NgramLM; search="prefix_beam" only, not with a context): n-gram LM shallow fusion of the streamed search - partial(),
+        nbest() and finish() then report 'lm_score' and order by 'score'."""
         from ..stream import StreamingEncoder
         return StreamingEncoder(self, batch_size, parser=parser, source_rate=source_rate, search=search, beam_size=beam_size, frame_topk=frame_topk,
-                                context=context, context_ids=context_ids)
+                                context=context, context_ids=context_ids, lm=lm)
 
-    def sessions(self, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None):
+    def sessions(self, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None):
         """`slots` independent streaming sessions in one batch (sessions.Sessions): each slot is opened, fed (push / push_audio),
         closed, finished and reopened at its own pace - open(b), push(feats, n_valid, final), finish(b) - and with endpoint={...} the
         CTC endpoint rules report per slot when its speaker has stopped (endpoints()).  parser, search, beam_size, frame_topk as
-        stream()'s; only 16 kHz audio.  context (search="prefix_beam" only): hotword biasing, open(b, context=i) picks the session's graph."""
+        stream()'s; only 16 kHz audio.  context (search="prefix_beam" only): hotword biasing, open(b, context=i) picks the session's graph.
+        lm (search="prefix_beam" only, not with a context): one n-gram LM for all slots; a reopened slot restarts on its start state."""
         from ..sessions import Sessions
         return Sessions(self, slots, parser=parser, search=search, beam_size=beam_size, frame_topk=frame_topk, endpoint=endpoint, source_rate=source_rate,
-                        context=context)
+                        context=context, lm=lm)
 
     def forward(self, input):
         """transformer_official.py:68-81 (inference-style forward; no gradients).  A batch without a transcript (only wave / wave_len)
@@ -440,7 +443,7 @@ class _SpeechTransformer(BaseModel):
         return pack
 
     def beam_search(self, input, beam_size=5, nbest=1, decode_max_len=0, ctc_weight=0.0, joint="rescore", ctc_pre_beam=None, context=None,
-                    context_ids=None):
+                    context_ids=None, lm=None):
         """Attention-decoder beam search for a batch (Decoder.recognize_beam, transformer_official.py:
         331-434, batched on the GPU with key/value caches): per utterance a list of at most `nbest`
         {'yseq': [sos, ..., eos], 'score': float}.
@@ -453,10 +456,15 @@ class _SpeechTransformer(BaseModel):
         proposes beam_size hypotheses, one teacher-forced decoder pass re-ranks them by the same combination; 'yseq' then carries no
         sos / eos, and decode_max_len does not apply.
         context / context_ids: hotword biasing (ctc_prefix_beam_search) - joint="ctc_rescore" only, whose first pass it biases; the
-        attention beam search and the other joint searches raise."""
+        attention beam search and the other joint searches raise.
+        lm (an lm.NgramLM): n-gram LM shallow fusion, under the same rule - joint="ctc_rescore" only, and not together with a context."""
         from .. import decode
         if joint not in ("rescore", "one_pass", "ctc_rescore"):
             raise ValueError(f"joint must be 'rescore', 'one_pass' or 'ctc_rescore' (got {joint!r})")
+        if lm is not None and joint != "ctc_rescore":
+            what = "the attention beam search" if joint == "rescore" and not ctc_weight > 0.0 else f"joint={joint!r}"
+            raise ValueError(f"an n-gram LM (lm=...) is not supported by {what}: it is fused into the CTC prefix beam search - "
+                             "ctc_prefix_beam_search, beam_search(joint='ctc_rescore'), stream / sessions with search='prefix_beam'")
         if (context is not None or context_ids is not None) and joint != "ctc_rescore":
             what = "the attention beam search" if joint == "rescore" and not ctc_weight > 0.0 else f"joint={joint!r}"
             raise ValueError(f"hotword biasing (context=...) is not supported by {what}: it biases the CTC prefix beam search - "
@@ -466,19 +474,20 @@ class _SpeechTransformer(BaseModel):
         if joint == "ctc_rescore":
             if ctc_pre_beam is not None:
                 raise ValueError("ctc_pre_beam applies to joint='one_pass' only")
-            return decode.ctc_rescore_search(self, input, beam_size, nbest, ctc_weight, context=context, context_ids=context_ids)
+            return decode.ctc_rescore_search(self, input, beam_size, nbest, ctc_weight, context=context, context_ids=context_ids, lm=lm)
         if ctc_pre_beam is not None:
             raise ValueError("ctc_pre_beam applies to joint='one_pass' only")
         if ctc_weight > 0.0:
             return decode.joint_beam_search(self, input, beam_size, nbest, decode_max_len, ctc_weight)
         return decode.beam_search(self, input, beam_size, nbest, decode_max_len)
 
-    def ctc_prefix_beam_search(self, input, beam_size=5, nbest=1, frame_topk=10, on_device=None, context=None, context_ids=None):
+    def ctc_prefix_beam_search(self, input, beam_size=5, nbest=1, frame_topk=10, on_device=None, context=None, context_ids=None, lm=None):
         """CTC prefix beam search over the CTC head (decode.ctc_prefix_beam_search): per utterance at most `nbest`
         {'yseq': [ids], 'score': log p(yseq | x)}.  on_device: None = the device kernel when beam * (frame_topk + 1) <= 64.
-        context / context_ids: hotword biasing; entries are then {'yseq', 'score', 'ctc_score', 'bias'} (decode.ctc_prefix_beam_search)."""
+        context / context_ids: hotword biasing; entries are then {'yseq', 'score', 'ctc_score', 'bias'} (decode.ctc_prefix_beam_search).
+        lm: n-gram LM shallow fusion (lm.NgramLM); entries are then {'yseq', 'score', 'ctc_score', 'lm_score'}."""
         from .. import decode
-        return decode.ctc_prefix_beam_search(self, input, beam_size, nbest, frame_topk, on_device, context=context, context_ids=context_ids)
+        return decode.ctc_prefix_beam_search(self, input, beam_size, nbest, frame_topk, on_device, context=context, context_ids=context_ids, lm=lm)
 
     def ctc_greedy_search(self, input):
         """Best-path CTC hypotheses of a batch: list of id lists (repeats merged, blanks removed)."""
@@ -555,7 +564,7 @@ class _SpeechTransformer(BaseModel):
             out.append({"score": score[b] if ok[b] else None, "tokens": toks})
         return out
 
-    def transcribe(self, input, beam_size=5, ctc_weight=None, timestamps=True, joint="rescore", context=None, context_ids=None):
+    def transcribe(self, input, beam_size=5, ctc_weight=None, timestamps=True, joint="rescore", context=None, context_ids=None, lm=None):
         """Audio in, text out, for a batch that needs only wave / wave_len.  The search follows the model's heads: joint model =
         beam_search(ctc_weight = config.ctc_weight unless given), CTC-only model = ctc_prefix_beam_search, attention-only model =
         beam_search (no timestamps: they come from the CTC head).  Returns per utterance {"text", "ids", "score", "tokens"}: ids of
@@ -565,7 +574,8 @@ class _SpeechTransformer(BaseModel):
         joint: the joint model's search, "rescore" (two-pass), "one_pass" or "ctc_rescore" (CTC n-best re-ranked by the decoder)
         (beam_search(joint=...)); "one_pass" and "ctc_rescore" need both heads.
         context / context_ids: hotword biasing of the CTC prefix beam search (a CTC-only model, or joint="ctc_rescore"; any other
-        search raises ValueError); the result dicts gain "bias"."""
+        search raises ValueError); the result dicts gain "bias".
+        lm: n-gram LM shallow fusion in the CTC prefix beam search, under the same rule; the result dicts gain "lm_score"."""
         if joint not in ("rescore", "one_pass", "ctc_rescore"):
             raise ValueError(f"joint must be 'rescore', 'one_pass' or 'ctc_rescore' (got {joint!r})")
         if joint in ("one_pass", "ctc_rescore") and not (self.use_decoder and self.use_ctc):
@@ -574,12 +584,13 @@ class _SpeechTransformer(BaseModel):
             raise ValueError("timestamps come from the CTC head, and this model has none (config.ctc_weight = 0)")
         if self.use_decoder:
             w = float(getattr(self.config, "ctc_weight", 0.0)) if ctc_weight is None else float(ctc_weight)
-            hyps = self.beam_search(input, beam_size, 1, ctc_weight=w if self.use_ctc else 0.0, joint=joint, context=context, context_ids=context_ids)
+            hyps = self.beam_search(input, beam_size, 1, ctc_weight=w if self.use_ctc else 0.0, joint=joint, context=context, context_ids=context_ids, lm=lm)
         else:
-            hyps = self.ctc_prefix_beam_search(input, beam_size, 1, context=context, context_ids=context_ids)
+            hyps = self.ctc_prefix_beam_search(input, beam_size, 1, context=context, context_ids=context_ids, lm=lm)
         ids, scores, biases = [], [], []
+        bias_key = "lm_score" if lm is not None else "bias"
         for h in hyps:
-            biases.append(float(h[0]["bias"]) if h and "bias" in h[0] else 0.0)
+            biases.append(float(h[0][bias_key]) if h and bias_key in h[0] else 0.0)
             if not h:
                 ids.append([])
                 scores.append(float("-inf"))
@@ -590,17 +601,18 @@ class _SpeechTransformer(BaseModel):
                 seq = seq[:-1] if seq and seq[-1] == EOS_ID else seq
             ids.append(seq)
             scores.append(float(h[0]["score"]))
-        return self._hyp_dicts(ids, scores, timestamps, lambda: self._ctc_logits(input), input.wave_len, biases if context is not None else None)
+        return self._hyp_dicts(ids, scores, timestamps, lambda: self._ctc_logits(input), input.wave_len,
+                               biases if context is not None or lm is not None else None, bias_key)
 
-    def _hyp_dicts(self, ids, scores, timestamps, ctc_logits, wave_len, biases=None):
+    def _hyp_dicts(self, ids, scores, timestamps, ctc_logits, wave_len, biases=None, bias_key="bias"):
         """transcribe's result dicts for the best ids / score of each utterance; ctc_logits() -> (B, T, V) is called for timestamps only.
-        biases (hotword-biased searches): the "bias" of each result."""
+        biases (hotword-biased searches, or searches with an n-gram LM): the "bias" (bias_key="lm_score": the "lm_score") of each result."""
         id2tok = self.vocab._id2token
         out = [{"text": "".join(id2tok[x] for x in seq if x not in (PAD_ID, SOS_ID, EOS_ID)), "ids": seq, "score": sc, "tokens": None}
                for seq, sc in zip(ids, scores)]
         if biases is not None:
             for o, bias in zip(out, biases):
-                o["bias"] = bias
+                o[bias_key] = bias
         if timestamps:
             V = self.V
             ok = [len(seq) <= 255 and all(0 <= x < V and x != PAD_ID for x in seq) for seq in ids]

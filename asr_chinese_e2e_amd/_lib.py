@@ -113,6 +113,12 @@ SIGNATURES = {
     "asr_ctc_prefix_beam_ctx_state_init": (I, [P, P, P, I, I, I, P]),
     "asr_ctc_prefix_beam_ctx_state_reset": (I, [P, P, P, P, I, I, I, P]),
     "asr_ctc_prefix_beam_chunk_ctx": (I, [P, P, P, P, P, P, Z, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "asr_ctc_prefix_beam_lm": (I, [P, P, P, P, P, P, Z, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "asr_ctc_prefix_beam_lm_workspace_bytes": (Z, [I, I, I]),
+    "asr_ctc_prefix_beam_lm_state_bytes": (Z, [I, I]),
+    "asr_ctc_prefix_beam_lm_state_init": (I, [P, P, P, I, I, I, P]),
+    "asr_ctc_prefix_beam_lm_state_reset": (I, [P, P, P, P, I, I, I, P]),
+    "asr_ctc_prefix_beam_chunk_lm": (I, [P, P, P, P, P, P, Z, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "asr_beam_step": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "asr_cache_gather": (I, [P, P, P, I, I, I, I, I, I, P]),
     "asr_ctc_prefix_logprobs": (I, [P, P, I, I, I, I, I, P]),

@@ -427,13 +427,94 @@ __device__ __forceinline__ void pb_ctx_advance(const PbCtx& g, int root, int c, 
     if (m >= 0) { bias = bias + g.w; st = m; }
 }
 
-// what the CTX kernels take beside the plain ones' arguments (nothing for CTX = false)
-template <bool CTX> struct PbCtxArgs {};
-template <> struct PbCtxArgs<true> {
+// ---- n-gram LM shallow fusion (PB_LM instantiations only; the tables come from asr_chinese_e2e_amd/lm.py::NgramLM) -------------------------
+// A beam entry carries (LM state, bias): the state is the longest suffix of the prefix's last order - 1 tokens that the model knows as a
+// context, the bias the sum of the weighted LM log-probabilities of its tokens - both functions of the prefix alone, so merging and the
+// stable prefix hold as they do for hotwords.  Every table entry is an fp64 term, weights folded in on the host; the device only adds.
+struct PbLm {
+    const int32_t* __restrict__ st_off;      // (S + 1) arcs of state s = [st_off[s], st_off[s + 1]); state 0 (the empty history) has none
+    const int32_t* __restrict__ arc_tok;     // (A) ascending within a state
+    const int32_t* __restrict__ arc_next;    // (A) the state after the token; ~state when the n-gram itself is not listed (only longer ones are)
+    const double* __restrict__ arc_term;     // (A) the listed n-gram's term
+    const int32_t* __restrict__ st_back;     // (S) the state of the longest proper suffix that is a state
+    const double* __restrict__ st_bow;       // (S) the back-off term (0.0: none)
+    const double* __restrict__ uni_term;     // (V) the unigram's term, the unk term where there is none
+    const int32_t* __restrict__ uni_next;    // (V)
+    int S, A, V, order, start;
+    double ins;
+};
+
+// the beam's (LM state, bias) in rank order and one frame's slots, beside PbLds; apart from PbCtxLds, so that a later change can run both
+struct PbLmLds {
+    double bias[PB_MAX_BEAM], nbias[64];
+    int st[PB_MAX_BEAM], nst[64];
+    int nnew[PB_MAX_BEAM], nold[PB_MAX_BEAM];      // per survivor: it got a new trie node; its parent's first child before this frame
+};
+
+// the index of the arc (st, c), or -1: binary search of st's arc range.  Every index is clamped to its table.
+__device__ __forceinline__ int pb_lm_find(const PbLm& g, int st, int c) {
+    int lo = min(max(g.st_off[st], 0), g.A);
+    const int end = min(max(g.st_off[st + 1], lo), g.A);
+    int hi = end;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (g.arc_tok[mid] < c) lo = mid + 1;
+        else hi = mid;
+    }
+    return (lo < end && g.arc_tok[lo] == c) ? lo : -1;
+}
+
+// (st, bias) of a prefix -> of the prefix + c (lm.py::NgramLM.advance, the same fp64 additions in the same order): down the back-off
+// chain from st, one term per back-off weight met, then the term of the n-gram found - at the latest the dense unigram level, one
+// indexed load that cannot miss -, then the insertion bonus.  The next state is that of the first arc met on the chain.
+__device__ __forceinline__ void pb_lm_advance(const PbLm& g, int c, int& st, double& bias) {
+    if ((unsigned)st >= (unsigned)g.S) st = 0;       // never from a state outside the table
+    int nx = -1;
+    bool hit = false;
+    for (int i = 1; i < g.order && st != 0; ++i) {   // a state spells at most order - 1 tokens, and st_back shortens it
+        const int a = pb_lm_find(g, st, c);
+        if (a >= 0) {
+            const int raw = g.arc_next[a];
+            if (nx < 0) nx = raw >= 0 ? raw : ~raw;
+            if (raw >= 0) { bias = bias + g.arc_term[a]; hit = true; break; }
+        }
+        bias = bias + g.st_bow[st];
+        const int bk = g.st_back[st];
+        st = (unsigned)bk < (unsigned)g.S ? bk : 0;
+    }
+    if (!hit) {
+        const int cc = min(max(c, 0), g.V - 1);
+        bias = bias + g.uni_term[cc];
+        if (nx < 0) nx = g.uni_next[cc];
+    }
+    bias = bias + g.ins;
+    st = (unsigned)nx < (unsigned)g.S ? nx : 0;
+}
+
+// (state, bias) of the n best, beside pb_spell's outputs
+__device__ __forceinline__ void pb_lm_report(const PbLmLds& ls, int nb, double* __restrict__ out_bias, int32_t* __restrict__ out_state, int b, int nbest) {
+    const int lane = threadIdx.x;
+    if (lane < nbest) {
+        out_bias[b * nbest + lane] = lane < nb ? ls.bias[lane] : 0.0;
+        out_state[b * nbest + lane] = lane < nb ? ls.st[lane] : -1;
+    }
+}
+
+// The three flavours of the one frame step: the plain search, hotword biasing, n-gram LM fusion.
+constexpr int PB_PLAIN = 0, PB_CTX = 1, PB_LM = 2;
+
+// what the PB_CTX / PB_LM kernels take beside the plain ones' arguments (nothing for PB_PLAIN)
+template <int MODE> struct PbArgs {};
+template <> struct PbArgs<PB_CTX> {
     PbCtx g;
     const int32_t* root;      // offline: (B) the utterance's root state, -1 = not biased; resumable: unused, the root lives in the state
     double* out_bias;         // (B, nbest) the entries' raw bias (held(state) not yet taken off)
     int32_t* out_state;       // (B, nbest) their context state (-1: no entry, or not biased)
+};
+template <> struct PbArgs<PB_LM> {
+    PbLm lm;
+    double* out_bias;         // (B, nbest) the entries' bias (the end-of-sentence term not yet added)
+    int32_t* out_state;       // (B, nbest) their LM state (-1: no entry)
 };
 
 // a root outside the table means "not biased"
@@ -455,12 +536,18 @@ __device__ __forceinline__ void pb_empty_beam(PbLds& s) {
 
 // One frame of the search: the only copy, run by the offline kernel and by the resumable one.  row_* = the frame's candidates;
 // nb / next_node = beam entries / trie nodes in use (wave-uniform, carried across frames).
-// All 64 lanes call it; it ends with a barrier.  CTX = false is the search without biasing (cs / g / root unused); CTX = true adds the
-// entries' context state and bias (cs) and ranks by log p + bias.
-template <bool CTX>
+// PB_LM also keeps child lists in the trie (nfirst: a node's newest child, nsib: the next older child of the same parent): with an insertion
+// bonus a prefix can leave the beam while a longer one stays, and come back later.  The plain search gives it a new node then, and the
+// longer one - whose parent is the old node - is no longer recognised as its extension, so the same string would enter the beam twice with
+// its probability split.  Here a surviving extension takes the node its (parent, token) already has, so node = string as in the definition.
+// All 64 lanes call it; it ends with a barrier.  PB_PLAIN is the search without biasing (cs / g / root / ls / lm unused); PB_CTX adds the
+// entries' context state and bias (cs), PB_LM their LM state and bias (ls), and both rank by log p + bias.
+template <int MODE>
 __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict__ row_vals, const int32_t* __restrict__ row_ids, double lb, int k, int beam,
                                               int blank, int& nb, int& next_node, int32_t* npar, int32_t* ntok, PbCtxLds* cs = nullptr,
-                                              const PbCtx* g = nullptr, int root = -1) {
+                                              const PbCtx* g = nullptr, int root = -1, PbLmLds* ls = nullptr, const PbLm* lm = nullptr, int32_t* nfirst = nullptr,
+                                              int32_t* nsib = nullptr) {
+    constexpr bool CTX = MODE == PB_CTX, LM = MODE == PB_LM;
     const int lane = threadIdx.x, per = k + 1;
     if (lane < k) { s.id[lane] = row_ids[lane]; s.lp[lane] = row_vals[lane]; }
     if (lane < PB_MAX_BEAM) s.merge[lane] = -INFINITY;
@@ -473,6 +560,9 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
     double cbias = 0.0;
     if constexpr (CTX) {
         if (valid) { cst = cs->st[j]; cbias = cs->bias[j]; }     // a stay slot inherits them
+    }
+    if constexpr (LM) {
+        if (valid) { cst = ls->st[j]; cbias = ls->bias[j]; }
     }
     if (valid) {
         const double pb = s.pb[j], pnb = s.pnb[j], tot = pb_logadd(pb, pnb);
@@ -492,6 +582,7 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
                 ident_par = s.node[j];
                 dep = s.dep[j] + 1;
                 if constexpr (CTX) pb_ctx_advance(*g, root, c, cst, cbias);
+                if constexpr (LM) pb_lm_advance(*lm, c, cst, cbias);
             }
         }
     }
@@ -507,7 +598,7 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
     __syncthreads();
     if (valid && m == 0) pnb2 = pb_logadd(pnb2, s.merge[j]);
     double sc = valid ? pb_logadd(pb2, pnb2) : -INFINITY;
-    if constexpr (CTX) {
+    if constexpr (CTX || LM) {
         if (sc > -INFINITY) sc = sc + cbias;         // -inf stays -inf
     }
     // a slot whose whole probability is zero cannot enter the beam (the host dictionary would hold it with -inf, ranked last)
@@ -523,10 +614,22 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
     }
     const bool keep = valid && rank < beam;
     const unsigned long long keep_mask = __ballot(keep);
-    const unsigned long long ext_mask = __ballot(keep && m > 0);
+    [[maybe_unused]] int found = -1, old_first = 0;
+    if constexpr (LM) {
+        if (keep && m > 0) {                         // the node this string already has, if it was in the beam before (bounded walk, inside the trie)
+            old_first = nfirst[ident_par];
+            int ch = old_first;
+            for (int it = 0; ch > 0 && ch < next_node && it < next_node; ++it) {
+                if (ntok[ch] == c) { found = ch; break; }
+                ch = nsib[ch];
+            }
+        }
+    }
+    const unsigned long long ext_mask = __ballot(keep && m > 0 && found < 0);      // the survivors that need a new node
     if (keep) {
-        int node = m == 0 ? s.node[j] : next_node + __popcll(ext_mask & ((1ull << lane) - 1ull));
-        if (m > 0) { npar[node] = ident_par; ntok[node] = c; }
+        int node = m == 0 ? s.node[j] : found >= 0 ? found : next_node + __popcll(ext_mask & ((1ull << lane) - 1ull));
+        if (m > 0 && found < 0) { npar[node] = ident_par; ntok[node] = c; }
+        if constexpr (LM) { ls->nnew[rank] = m > 0 && found < 0; ls->nold[rank] = old_first; }
         s.nnode[rank] = node;
         s.ntok_[rank] = c;
         s.npar_[rank] = ident_par;
@@ -534,6 +637,7 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
         s.npb[rank] = pb2;
         s.npnb[rank] = pnb2;
         if constexpr (CTX) { cs->nst[rank] = cst; cs->nbias[rank] = cbias; }
+        if constexpr (LM) { ls->nst[rank] = cst; ls->nbias[rank] = cbias; }
     }
     __syncthreads();
     nb = __popcll(keep_mask);
@@ -542,6 +646,22 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
         s.node[lane] = s.nnode[lane]; s.tok[lane] = s.ntok_[lane]; s.par[lane] = s.npar_[lane]; s.dep[lane] = s.ndep_[lane];
         s.pb[lane] = s.npb[lane]; s.pnb[lane] = s.npnb[lane];
         if constexpr (CTX) { cs->st[lane] = cs->nst[lane]; cs->bias[lane] = cs->nbias[lane]; }
+        if constexpr (LM) {
+            ls->st[lane] = ls->nst[lane]; ls->bias[lane] = ls->nbias[lane];
+            if (ls->nnew[lane]) {                    // link the new node in front of its parent's children; each address has one writer
+                const int par = s.npar_[lane], node = s.nnode[lane];
+                int prev = -1;
+                bool last = true;
+                for (int r = 0; r < nb; ++r)
+                    if (r != lane && ls->nnew[r] && s.npar_[r] == par) {
+                        if (r < lane) prev = s.nnode[r];
+                        else last = false;
+                    }
+                nsib[node] = prev >= 0 ? prev : ls->nold[lane];
+                nfirst[node] = 0;
+                if (last) nfirst[par] = node;
+            }
+        }
     }
     __syncthreads();
 }
@@ -570,11 +690,12 @@ __device__ __forceinline__ void pb_spell(const PbLds& s, int nb, const int32_t* 
     }
 }
 
-template <bool CTX>
+template <int MODE>
 __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __restrict__ vals, const int32_t* __restrict__ ids, const float* __restrict__ blank_lp,
                                                              const int32_t* __restrict__ in_len, int32_t* nodes, int32_t* __restrict__ out_tok,
                                                              int32_t* __restrict__ out_len, float* __restrict__ out_score, int T, int k, int beam, int nbest,
-                                                             int Lcap, int blank, PbCtxArgs<CTX> cx) {
+                                                             int Lcap, int blank, PbArgs<MODE> cx) {
+    constexpr bool CTX = MODE == PB_CTX, LM = MODE == PB_LM;
     __shared__ PbLds s;
     [[maybe_unused]] PbCtxLds* cs = nullptr;
     [[maybe_unused]] PbCtx g{};
@@ -584,29 +705,42 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
         cs = &cs_mem;
         g = cx.g;
     }
+    [[maybe_unused]] PbLmLds* ls = nullptr;
+    if constexpr (LM) {
+        __shared__ PbLmLds ls_mem;
+        ls = &ls_mem;
+    }
     const int b = blockIdx.x, lane = threadIdx.x;
     const int cap_nodes = T * beam + 1;                  // node 0 = the empty prefix; at most `beam` new nodes per frame
-    int32_t* npar = nodes + (size_t)b * 2 * cap_nodes;   // [parent | token] per node
+    int32_t* npar = nodes + (size_t)b * (LM ? 4 : 2) * cap_nodes;   // [parent | token] per node; PB_LM: [parent | token | first child | sibling]
     int32_t* ntok = npar + cap_nodes;
+    [[maybe_unused]] int32_t* nfirst = ntok + cap_nodes;
+    [[maybe_unused]] int32_t* nsib = ntok + 2 * (size_t)cap_nodes;
     const int len = min(in_len ? in_len[b] : T, T);
     if (lane == 0) {
         npar[0] = -1;
         ntok[0] = -1;
+        if constexpr (LM) nfirst[0] = 0;
         pb_empty_beam(s);
     }
     if constexpr (CTX) {
         root = pb_ctx_root(g, cx.root[b]);
         if (lane == 0) { cs->st[0] = root; cs->bias[0] = 0.0; }
     }
+    if constexpr (LM) {
+        if (lane == 0) { ls->st[0] = (unsigned)cx.lm.start < (unsigned)cx.lm.S ? cx.lm.start : 0; ls->bias[0] = 0.0; }
+    }
     int nb = 1, next_node = 1;                           // wave-uniform copies
     __syncthreads();
     for (int t = 0; t < len; ++t) {
         const size_t row = (size_t)b * T + t;
-        if constexpr (CTX) pb_frame_step<true>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, cs, &g, root);
-        else pb_frame_step<false>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
+        if constexpr (CTX) pb_frame_step<PB_CTX>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, cs, &g, root);
+        else if constexpr (LM) pb_frame_step<PB_LM>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, nullptr, nullptr, -1, ls, &cx.lm, nfirst, nsib);
+        else pb_frame_step<PB_PLAIN>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
     }
     pb_spell(s, nb, npar, ntok, out_tok, out_len, out_score, b, nbest, Lcap);
     if constexpr (CTX) pb_ctx_report(*cs, nb, cx.out_bias, cx.out_state, b, nbest);
+    if constexpr (LM) pb_lm_report(*ls, nb, cx.out_bias, cx.out_state, b, nbest);
 }
 
 // ---- the resumable search: the beam leaves LDS between launches ------------------------------------------------------------------
@@ -620,9 +754,12 @@ __host__ __device__ inline size_t pb_state_bytes1(int beam) { return (size_t)PB_
 // The context state of one utterance: the plain state, then fp64 bias[beam], int32 ctx[beam], int32 root, padded to 8 bytes.
 __host__ __device__ inline size_t pb_ctx_state_bytes1(int beam) { return pb_state_bytes1(beam) + (size_t)beam * 8 + (((size_t)beam * 4 + 4 + 7) & ~(size_t)7); }
 
+// The LM state of one utterance: the plain state, then fp64 bias[beam], int32 st[beam], padded to 8 bytes.
+__host__ __device__ inline size_t pb_lm_state_bytes1(int beam) { return pb_state_bytes1(beam) + (size_t)beam * 8 + (((size_t)beam * 4 + 7) & ~(size_t)7); }
+
 // The empty-prefix state of utterance b and its trie's root: what the init kernel leaves for every utterance and the reset kernel for the flagged ones.
-// bytes1: the bytes of one utterance's state (pb_state_bytes1, or pb_ctx_state_bytes1 when a context part follows).
-__device__ __forceinline__ void pb_state_init_one(char* state, int32_t* nodes, int b, int beam, int T_cap, size_t bytes1) {
+// bytes1: the bytes of one utterance's state (pb_state_bytes1, or pb_ctx_state_bytes1 / pb_lm_state_bytes1 when a context / LM part follows).
+__device__ __forceinline__ void pb_state_init_one(char* state, int32_t* nodes, int b, int beam, int T_cap, size_t bytes1, int narr = 2) {
     const size_t cap_nodes = (size_t)T_cap * beam + 1;
     int32_t* hdr = (int32_t*)(state + (size_t)b * bytes1);
     int32_t* ent = hdr + PB_STATE_HDR;
@@ -632,8 +769,9 @@ __device__ __forceinline__ void pb_state_init_one(char* state, int32_t* nodes, i
         ent[i] = 0; ent[beam + i] = -1; ent[2 * beam + i] = -1; ent[3 * beam + i] = 0;
         sc[i] = i == 0 ? 0.0 : -INFINITY; sc[beam + i] = -INFINITY;
     }
-    int32_t* npar = nodes + (size_t)b * 2 * cap_nodes;
+    int32_t* npar = nodes + (size_t)b * narr * cap_nodes;      // narr = 4: the LM trie, whose root has no child yet
     npar[0] = -1; npar[cap_nodes] = -1;
+    if (narr == 4) npar[2 * cap_nodes] = 0;
 }
 
 __global__ __launch_bounds__(64) void ctc_prefix_beam_state_init_kernel(char* state, int32_t* nodes, int B, int beam, int T_cap) {
@@ -668,11 +806,26 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_ctx_state_init_kernel(char
     pb_ctx_state_init_one(state, b, beam, max(root[b], -1));
 }
 
-template <bool CTX>
+// the LM part of utterance b's state: every entry on the start state with no bias, a zero pad word
+// flags == nullptr: every utterance (init); otherwise the flagged ones (reset)
+__global__ __launch_bounds__(64) void ctc_prefix_beam_lm_state_init_kernel(char* state, int32_t* nodes, const int32_t* __restrict__ flags, int start, int B,
+                                                                           int beam, int T_cap) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B || (flags && flags[b] == 0)) return;
+    pb_state_init_one(state, nodes, b, beam, T_cap, pb_lm_state_bytes1(beam), 4);
+    char* base = state + (size_t)b * pb_lm_state_bytes1(beam) + pb_state_bytes1(beam);
+    double* bias = (double*)base;
+    int32_t* st = (int32_t*)(base + (size_t)beam * 8);
+    for (int i = 0; i < beam; ++i) { bias[i] = 0.0; st[i] = start; }
+    if (beam & 1) st[beam] = 0;
+}
+
+template <int MODE>
 __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* __restrict__ vals, const int32_t* __restrict__ ids, const float* __restrict__ blank_lp,
                                                                    const int32_t* __restrict__ n_valid, char* state, int32_t* nodes, int32_t* __restrict__ out_tok,
                                                                    int32_t* __restrict__ out_len, float* __restrict__ out_score, int32_t* __restrict__ out_stable,
-                                                                   int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank, PbCtxArgs<CTX> cx) {
+                                                                   int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank, PbArgs<MODE> cx) {
+    constexpr bool CTX = MODE == PB_CTX, LM = MODE == PB_LM;
     __shared__ PbLds s;
     __shared__ int s_walk[PB_MAX_BEAM];
     [[maybe_unused]] PbCtxLds* cs = nullptr;
@@ -682,11 +835,18 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* 
         cs = &cs_mem;
         g = cx.g;
     }
+    [[maybe_unused]] PbLmLds* ls = nullptr;
+    if constexpr (LM) {
+        __shared__ PbLmLds ls_mem;
+        ls = &ls_mem;
+    }
     const int b = blockIdx.x, lane = threadIdx.x;
     const int cap_nodes = T_cap * beam + 1;
-    int32_t* npar = nodes + (size_t)b * 2 * cap_nodes;   // [parent | token] per node
+    int32_t* npar = nodes + (size_t)b * (LM ? 4 : 2) * cap_nodes;   // [parent | token] per node; PB_LM: [parent | token | first child | sibling]
     int32_t* ntok = npar + cap_nodes;
-    int32_t* hdr = (int32_t*)(state + (size_t)b * (CTX ? pb_ctx_state_bytes1(beam) : pb_state_bytes1(beam)));
+    [[maybe_unused]] int32_t* nfirst = ntok + cap_nodes;
+    [[maybe_unused]] int32_t* nsib = ntok + 2 * (size_t)cap_nodes;
+    int32_t* hdr = (int32_t*)(state + (size_t)b * (CTX ? pb_ctx_state_bytes1(beam) : LM ? pb_lm_state_bytes1(beam) : pb_state_bytes1(beam)));
     int32_t* ent = hdr + PB_STATE_HDR;
     double* sc = (double*)(ent + 4 * beam);
     int nb = min(max(hdr[0], 0), beam), next_node = hdr[1];      // wave-uniform copies
@@ -695,12 +855,15 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* 
         s.node[lane] = ent[lane]; s.tok[lane] = ent[beam + lane]; s.par[lane] = ent[2 * beam + lane]; s.dep[lane] = ent[3 * beam + lane];
         s.pb[lane] = sc[lane]; s.pnb[lane] = sc[beam + lane];
     }
-    [[maybe_unused]] double* st_bias = sc + 2 * beam;            // the context part of the state (CTX only)
+    [[maybe_unused]] double* st_bias = sc + 2 * beam;            // the context / LM part of the state (PB_CTX: bias, ctx, root; PB_LM: bias, st)
     [[maybe_unused]] int32_t* st_ctx = (int32_t*)(st_bias + beam);
     [[maybe_unused]] int root = -1;
     if constexpr (CTX) {
         root = pb_ctx_root(g, st_ctx[beam]);
         if (lane < nb) { cs->st[lane] = root < 0 ? -1 : st_ctx[lane]; cs->bias[lane] = st_bias[lane]; }
+    }
+    if constexpr (LM) {
+        if (lane < nb) { ls->st[lane] = st_ctx[lane]; ls->bias[lane] = st_bias[lane]; }
     }
     __syncthreads();
     // never past the trie: at most T_cap frames in all (the wrapper refuses such a push; this keeps every write inside the workspace)
@@ -709,8 +872,9 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* 
     for (int t = 0; t < n; ++t) {
         if (next_node < 1 || next_node + beam > cap_nodes) break;
         const size_t row = (size_t)b * C + t;
-        if constexpr (CTX) pb_frame_step<true>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, cs, &g, root);
-        else pb_frame_step<false>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
+        if constexpr (CTX) pb_frame_step<PB_CTX>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, cs, &g, root);
+        else if constexpr (LM) pb_frame_step<PB_LM>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, nullptr, nullptr, -1, ls, &cx.lm, nfirst, nsib);
+        else pb_frame_step<PB_PLAIN>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
         ++done;
     }
     if (done > 0) {                                      // a chunk without frames leaves every byte of the state as it is
@@ -719,10 +883,12 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* 
             ent[lane] = s.node[lane]; ent[beam + lane] = s.tok[lane]; ent[2 * beam + lane] = s.par[lane]; ent[3 * beam + lane] = s.dep[lane];
             sc[lane] = s.pb[lane]; sc[beam + lane] = s.pnb[lane];
             if constexpr (CTX) { st_ctx[lane] = cs->st[lane]; st_bias[lane] = cs->bias[lane]; }
+            if constexpr (LM) { st_ctx[lane] = ls->st[lane]; st_bias[lane] = ls->bias[lane]; }
         }
     }
     pb_spell(s, nb, npar, ntok, out_tok, out_len, out_score, b, nbest, Lcap);
     if constexpr (CTX) pb_ctx_report(*cs, nb, cx.out_bias, cx.out_state, b, nbest);
+    if constexpr (LM) pb_lm_report(*ls, nb, cx.out_bias, cx.out_state, b, nbest);
     // the stable prefix: the depth of the lowest common ancestor of the beam's nodes.  Every entry first climbs to the smallest depth
     // among them, then all climb together until they stand on one node.
     int mind = INT_MAX;
@@ -757,7 +923,7 @@ extern "C" int asr_ctc_prefix_beam(const float* vals, const int32_t* ids, const 
     if (beam > PB_MAX_BEAM || k > PB_MAX_K || beam * (k + 1) > 64 || nbest > beam)
         ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam: one wave ranks the beam * (k + 1) candidates of a frame: beam * (k + 1) <= 64, beam <= %d, nbest <= beam (beam=%d k=%d nbest=%d)", PB_MAX_BEAM, beam, k, nbest);
     if (ws_bytes < asr_ctc_prefix_beam_workspace_bytes(B, T, beam) || ((uintptr_t)ws % 4)) ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_workspace_bytes(B, T, beam), ws_bytes);
-    ctc_prefix_beam_kernel<false><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, PbCtxArgs<false>{});
+    ctc_prefix_beam_kernel<PB_PLAIN><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, PbArgs<PB_PLAIN>{});
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam");
     return ASR_OK;
 }
@@ -807,8 +973,8 @@ extern "C" int asr_ctc_prefix_beam_chunk(const float* vals, const int32_t* ids, 
         ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk: misaligned pointer (state: 8 bytes, the others: 4)");
     if (ws_bytes < asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam) || ((uintptr_t)ws % 4))
         ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_chunk: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam), ws_bytes);
-    ctc_prefix_beam_chunk_kernel<false><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score,
-                                                                           out_stable, C, k, beam, nbest, Lcap, T_cap, blank, PbCtxArgs<false>{});
+    ctc_prefix_beam_chunk_kernel<PB_PLAIN><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score,
+                                                                           out_stable, C, k, beam, nbest, Lcap, T_cap, blank, PbArgs<PB_PLAIN>{});
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_chunk");
     return ASR_OK;
 }
@@ -836,8 +1002,8 @@ extern "C" int asr_ctc_prefix_beam_ctx(const float* vals, const int32_t* ids, co
         ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_ctx: one wave ranks the beam * (k + 1) candidates of a frame: beam * (k + 1) <= 64, beam <= %d, nbest <= beam (beam=%d k=%d nbest=%d)", PB_MAX_BEAM, beam, k, nbest);
     if (((uintptr_t)out_bias % 8) || (((uintptr_t)root | (uintptr_t)out_state) % 4)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_ctx: misaligned pointer (out_bias: 8 bytes, root and out_state: 4)");
     if (ws_bytes < asr_ctc_prefix_beam_workspace_bytes(B, T, beam) || ((uintptr_t)ws % 4)) ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_ctx: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_workspace_bytes(B, T, beam), ws_bytes);
-    PbCtxArgs<true> cx{pb_ctx_of(ctx), root, out_bias, out_state};
-    ctc_prefix_beam_kernel<true><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, cx);
+    PbArgs<PB_CTX> cx{pb_ctx_of(ctx), root, out_bias, out_state};
+    ctc_prefix_beam_kernel<PB_CTX><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, cx);
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_ctx");
     return ASR_OK;
 }
@@ -885,10 +1051,100 @@ extern "C" int asr_ctc_prefix_beam_chunk_ctx(const float* vals, const int32_t* i
         ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_ctx: misaligned pointer (state and out_bias: 8 bytes, the others: 4)");
     if (ws_bytes < asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam) || ((uintptr_t)ws % 4))
         ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_chunk_ctx: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam), ws_bytes);
-    PbCtxArgs<true> cx{pb_ctx_of(ctx), nullptr, out_bias, out_state};
-    ctc_prefix_beam_chunk_kernel<true><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score,
+    PbArgs<PB_CTX> cx{pb_ctx_of(ctx), nullptr, out_bias, out_state};
+    ctc_prefix_beam_chunk_kernel<PB_CTX><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score,
                                                                           out_stable, C, k, beam, nbest, Lcap, T_cap, blank, cx);
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_chunk_ctx");
+    return ASR_OK;
+}
+
+// ---- n-gram LM shallow fusion: the same searches with an LM (additive to ABI 10) ------------------------------------------------------
+namespace {
+const char* pb_lm_check(const asr_ngram_lm* lm) {
+    if (!lm || !lm->st_off || !lm->arc_tok || !lm->arc_next || !lm->arc_term || !lm->st_back || !lm->st_bow || !lm->uni_term || !lm->uni_next) return "null LM table";
+    if (lm->S < 1 || lm->A < 0 || lm->V < 1) return "an LM has S >= 1 states, A >= 0 arcs and V >= 1 tokens";
+    if (lm->order < 1 || lm->order > 5) return "LM orders 1 to 5";
+    if (lm->start < 0 || lm->start >= lm->S) return "the LM's start state is one of its states";
+    if ((((uintptr_t)lm->st_off | (uintptr_t)lm->arc_tok | (uintptr_t)lm->arc_next | (uintptr_t)lm->st_back | (uintptr_t)lm->uni_next) % 4) ||
+        (((uintptr_t)lm->arc_term | (uintptr_t)lm->st_bow | (uintptr_t)lm->uni_term) % 8))
+        return "misaligned LM table (int32 tables: 4 bytes, fp64 tables: 8)";
+    if (!(lm->ins == lm->ins) || lm->ins - lm->ins != 0.0) return "the LM's insertion bonus must be finite";
+    return nullptr;
+}
+PbLm pb_lm_of(const asr_ngram_lm* lm) {
+    return PbLm{lm->st_off, lm->arc_tok, lm->arc_next, lm->arc_term, lm->st_back, lm->st_bow, lm->uni_term, lm->uni_next, lm->S, lm->A, lm->V, lm->order, lm->start, lm->ins};
+}
+}  // namespace
+
+extern "C" size_t asr_ctc_prefix_beam_lm_workspace_bytes(int B, int T, int beam) {
+    if (B <= 0 || T <= 0 || beam <= 0) return 0;
+    return (size_t)B * 4 * ((size_t)T * beam + 1) * sizeof(int32_t);      // [parent | token | first child | sibling] per node
+}
+
+extern "C" int asr_ctc_prefix_beam_lm(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* in_len, const asr_ngram_lm* lm, void* ws,
+                                      size_t ws_bytes, int32_t* out_tok, int32_t* out_len, float* out_score, double* out_bias, int32_t* out_state, int B,
+                                      int T, int k, int beam, int nbest, int Lcap, int blank, void* stream) {
+    if (!vals || !ids || !blank_lp || !ws || !out_tok || !out_len || !out_score || !out_bias || !out_state) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_lm: null pointer");
+    if (const char* why = pb_lm_check(lm)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_lm: %s", why);
+    if (B <= 0 || T <= 0 || k <= 0 || beam <= 0 || nbest <= 0 || Lcap <= 0) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_lm: bad shape B=%d T=%d k=%d beam=%d nbest=%d Lcap=%d", B, T, k, beam, nbest, Lcap);
+    if (beam > PB_MAX_BEAM || k > PB_MAX_K || beam * (k + 1) > 64 || nbest > beam)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_lm: one wave ranks the beam * (k + 1) candidates of a frame: beam * (k + 1) <= 64, beam <= %d, nbest <= beam (beam=%d k=%d nbest=%d)", PB_MAX_BEAM, beam, k, nbest);
+    if (((uintptr_t)out_bias % 8) || ((uintptr_t)out_state % 4)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_lm: misaligned pointer (out_bias: 8 bytes, out_state: 4)");
+    if (ws_bytes < asr_ctc_prefix_beam_lm_workspace_bytes(B, T, beam) || ((uintptr_t)ws % 4)) ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_lm: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_lm_workspace_bytes(B, T, beam), ws_bytes);
+    PbArgs<PB_LM> cx{pb_lm_of(lm), out_bias, out_state};
+    ctc_prefix_beam_kernel<PB_LM><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, cx);
+    ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_lm");
+    return ASR_OK;
+}
+
+extern "C" size_t asr_ctc_prefix_beam_lm_state_bytes(int B, int beam) {
+    if (B <= 0 || beam <= 0) return 0;
+    return (size_t)B * pb_lm_state_bytes1(beam);
+}
+
+namespace {
+int pb_lm_state_launch(const char* what, void* state, void* ws, const int32_t* flags, const asr_ngram_lm* lm, int B, int beam, int T_cap, void* stream) {
+    if (const char* why = pb_lm_check(lm)) ASR_FAIL(ASR_EINVAL, "%s: %s", what, why);
+    if (B <= 0 || beam <= 0 || beam > PB_MAX_BEAM || T_cap <= 0 || (size_t)T_cap * beam + 1 > (size_t)INT_MAX)
+        ASR_FAIL(ASR_EINVAL, "%s: bad shape B=%d beam=%d (<= %d) T_cap=%d", what, B, beam, PB_MAX_BEAM, T_cap);
+    if (((uintptr_t)state % 8) || ((uintptr_t)ws % 4) || ((uintptr_t)flags % 4))
+        ASR_FAIL(ASR_EINVAL, "%s: misaligned pointer (state: 8 bytes, workspace and flags: 4)", what);
+    ctc_prefix_beam_lm_state_init_kernel<<<ceil_div(B, 64), 64, 0, (hipStream_t)stream>>>((char*)state, (int32_t*)ws, flags, lm->start, B, beam, T_cap);
+    ASR_CHECK_LAUNCH(what);
+    return ASR_OK;
+}
+}  // namespace
+
+extern "C" int asr_ctc_prefix_beam_lm_state_init(void* state, void* ws, const asr_ngram_lm* lm, int B, int beam, int T_cap, void* stream) {
+    if (!state || !ws) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_lm_state_init: null pointer");
+    return pb_lm_state_launch("asr_ctc_prefix_beam_lm_state_init", state, ws, nullptr, lm, B, beam, T_cap, stream);
+}
+
+extern "C" int asr_ctc_prefix_beam_lm_state_reset(void* state, void* ws, const int32_t* flags, const asr_ngram_lm* lm, int B, int beam, int T_cap, void* stream) {
+    if (!state || !ws || !flags) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_lm_state_reset: null pointer");
+    return pb_lm_state_launch("asr_ctc_prefix_beam_lm_state_reset", state, ws, flags, lm, B, beam, T_cap, stream);
+}
+
+extern "C" int asr_ctc_prefix_beam_chunk_lm(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* n_valid, void* state, void* ws,
+                                            size_t ws_bytes, const asr_ngram_lm* lm, int32_t* out_tok, int32_t* out_len, float* out_score, double* out_bias,
+                                            int32_t* out_state, int32_t* out_stable, int B, int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank,
+                                            void* stream) {
+    if (!vals || !ids || !blank_lp || !n_valid || !state || !ws || !out_tok || !out_len || !out_score || !out_bias || !out_state || !out_stable)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_lm: null pointer");
+    if (const char* why = pb_lm_check(lm)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_lm: %s", why);
+    if (B <= 0 || C < 1 || T_cap < 1 || k <= 0 || beam <= 0 || nbest <= 0 || Lcap <= 0)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_lm: bad shape B=%d C=%d T_cap=%d k=%d beam=%d nbest=%d Lcap=%d", B, C, T_cap, k, beam, nbest, Lcap);
+    if (beam > PB_MAX_BEAM || k > PB_MAX_K || beam * (k + 1) > 64 || nbest > beam)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_lm: one wave ranks the beam * (k + 1) candidates of a frame: beam * (k + 1) <= 64, beam <= %d, nbest <= beam (beam=%d k=%d nbest=%d)", PB_MAX_BEAM, beam, k, nbest);
+    if ((size_t)T_cap * beam + 1 > (size_t)INT_MAX) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_lm: T_cap * beam + 1 nodes do not fit an int32 (T_cap=%d beam=%d)", T_cap, beam);
+    if (((uintptr_t)state % 8) || ((uintptr_t)out_bias % 8) || (((uintptr_t)vals | (uintptr_t)ids | (uintptr_t)blank_lp | (uintptr_t)n_valid | (uintptr_t)out_tok | (uintptr_t)out_len | (uintptr_t)out_score | (uintptr_t)out_state | (uintptr_t)out_stable) % 4))
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_lm: misaligned pointer (state and out_bias: 8 bytes, the others: 4)");
+    if (ws_bytes < asr_ctc_prefix_beam_lm_workspace_bytes(B, T_cap, beam) || ((uintptr_t)ws % 4))
+        ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_chunk_lm: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_lm_workspace_bytes(B, T_cap, beam), ws_bytes);
+    PbArgs<PB_LM> cx{pb_lm_of(lm), out_bias, out_state};
+    ctc_prefix_beam_chunk_kernel<PB_LM><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score,
+                                                                            out_stable, C, k, beam, nbest, Lcap, T_cap, blank, cx);
+    ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_chunk_lm");
     return ASR_OK;
 }
 

@@ -179,6 +179,29 @@ def context_entries(context, tok, ln, sc, bias, state, nbest=None):
     return out if nbest is None else out[:nbest]
 
 
+def lm_entries(lm, tok, ln, sc, bias, state, nbest=None):
+    """The n-best dicts of one utterance from the LM kernels' outputs over the whole beam (host lists: tokens, lengths with -1 for
+    missing ranks, log p, bias, LM state): lm_score = bias + term(</s> | state) (NgramLM.final), score = ctc_score + lm_score, ordered
+    by score (a stable sort of the rank order), cut to nbest."""
+    out = []
+    for r in range(len(ln)):
+        if ln[r] < 0:
+            continue
+        l = lm.final(int(state[r]), float(bias[r]))
+        out.append({"yseq": [int(x) for x in tok[r][:ln[r]]], "score": float(sc[r]) + l, "ctc_score": float(sc[r]), "lm_score": l})
+    out.sort(key=lambda h: h["score"], reverse=True)
+    return out if nbest is None else out[:nbest]
+
+
+def _check_lm(model, lm, context=None):
+    from .lm import NgramLM
+    if not isinstance(lm, NgramLM):
+        raise TypeError(f"lm must be an lm.NgramLM (got {type(lm).__name__})")
+    if context is not None:
+        raise ValueError("an n-gram LM (lm=...) and a hotword context (context=...) cannot be combined: the search runs one of the two")
+    lm.check_vocab(model.V)
+
+
 def _check_context(model, context):
     from .context import ContextGraph
     if not isinstance(context, ContextGraph):
@@ -186,7 +209,7 @@ def _check_context(model, context):
     context.check_vocab(model.V)
 
 
-def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on_device=None, context=None, context_ids=None):
+def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on_device=None, context=None, context_ids=None, lm=None):
     """CTC prefix beam search (Hannun et al. 2014, algorithm 1 without a language model) over the CTC head's posteriors:
     per utterance a list of at most `nbest` dicts {'yseq': [ids], 'score': log p(yseq | x)}, best first.
     Everything runs on the GPU: encoder, CTC projection, per frame the `frame_topk` best classes with their log-softmax values
@@ -198,9 +221,14 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
     context (a context.ContextGraph): hotword biasing - hypotheses that spell the graph's phrases are preferred (candidates of a frame
     are ranked by log p + bias; only tokens among the frame's `frame_topk` can be chosen).  context_ids[b] = the graph of utterance b
     (None: graph 0 for all, -1: not biased).  Entries are then {'yseq', 'score' = ctc_score + bias, 'ctc_score' = log p(yseq | x),
-    'bias'}, ordered by score.  Without a context the call and its result are unchanged."""
+    'bias'}, ordered by score.  Without a context the call and its result are unchanged.
+    lm (an lm.NgramLM): n-gram LM shallow fusion - candidates of a frame are ranked by log p + the hypothesis's accumulated weighted LM
+    log-probability (only tokens among the frame's `frame_topk` can be chosen).  Entries are then {'yseq', 'score' = ctc_score +
+    lm_score, 'ctc_score' = log p(yseq | x), 'lm_score' (the end-of-sentence term included)}, ordered by score.  Not with a context."""
     if context is None and context_ids is not None:
         raise ValueError("context_ids needs a context")
+    if lm is not None:
+        _check_lm(model, lm, context)
     eng = model._ensure_engine(input.wave.device)
     if not eng.use_ctc:
         raise RuntimeError("this model has no CTC head (config.ctc_weight = 0)")
@@ -229,6 +257,10 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
                                     context=context, roots=roots)
             tok, ln, sc, bias, state = (t.cpu().tolist() for t in res)
             return [context_entries(context, tok[b], ln[b], sc[b], bias[b], state[b], nbest) for b in range(B)]
+        if lm is not None:           # the same: the end-of-sentence term is added on the host, then the order is settled and cut
+            res = K.ctc_prefix_beam(vals, ids, blank_lp, input.wave_len.to(torch.int32).contiguous(), B, T, beam_size, beam_size, BLANK_ID, lm=lm)
+            tok, ln, sc, bias, state = (t.cpu().tolist() for t in res)
+            return [lm_entries(lm, tok[b], ln[b], sc[b], bias[b], state[b], nbest) for b in range(B)]
         tok, ln, sc = K.ctc_prefix_beam(vals, ids, blank_lp, input.wave_len.to(torch.int32).contiguous(), B, T, beam_size, nbest, BLANK_ID)
         tok, ln, sc = tok.cpu().tolist(), ln.cpu().tolist(), sc.cpu().tolist()
         return [[{"yseq": tok[b][r][:ln[b][r]], "score": sc[b][r]} for r in range(nbest) if ln[b][r] >= 0] for b in range(B)]
@@ -243,6 +275,14 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
             def rank(kv):
                 if kv[0] not in walked:
                     walked[kv[0]] = context.walk(g, kv[0])
+                tot = _logadd(kv[1][0], kv[1][1])
+                return tot + walked[kv[0]][1] if tot != -math.inf else tot
+        elif lm is not None:         # a prefix's (state, bias) is a function of the prefix (NgramLM.walk)
+            walked = {}
+
+            def rank(kv):
+                if kv[0] not in walked:
+                    walked[kv[0]] = lm.walk(kv[0])
                 tot = _logadd(kv[1][0], kv[1][1])
                 return tot + walked[kv[0]][1] if tot != -math.inf else tot
         else:
@@ -278,6 +318,16 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
                 st, raw = context.walk(g, p)
                 bias = raw - context.held(st)
                 ents.append({"yseq": list(p), "score": tot + bias, "ctc_score": tot, "bias": bias})
+            results.append(sorted(ents, key=lambda h: h["score"], reverse=True)[:nbest])
+            continue
+        if lm is not None:
+            ents = []
+            for p, v in sorted(beam.items(), key=rank, reverse=True):
+                tot = _logadd(v[0], v[1])
+                if tot == -math.inf:
+                    continue
+                l = lm.final(*lm.walk(p))
+                ents.append({"yseq": list(p), "score": tot + l, "ctc_score": tot, "lm_score": l})
             results.append(sorted(ents, key=lambda h: h["score"], reverse=True)[:nbest])
             continue
         final = sorted(((p, _logadd(v[0], v[1])) for p, v in beam.items()), key=lambda kv: kv[1], reverse=True)[:nbest]
@@ -345,7 +395,8 @@ def attention_rescore(model, enc, wave_len, nbest_lists, ctc_weight):
     ranks are skipped, an empty hypothesis scores log p(eos | sos), a hypothesis longer than the positional-encoding table admits gets
     att_score = score = -inf and so stays behind the others in its CTC order.
     Entries of a hotword-biased search (they carry 'bias' and a pure 'ctc_score'): score = ctc_weight * (ctc_score + bias) + (1 -
-    ctc_weight) * att_score; ctc_score stays pure and 'bias' is kept."""
+    ctc_weight) * att_score; ctc_score stays pure and 'bias' is kept.  Entries of a search with an n-gram LM (they carry 'lm_score'): score =
+    ctc_weight * (ctc_score + lm_score) + (1 - ctc_weight) * att_score; ctc_score and att_score are unchanged by the LM."""
     eng = model._ensure_engine(enc.device)
     if not eng.use_decoder:
         raise RuntimeError("attention rescoring needs a model with the attention decoder")
@@ -390,6 +441,11 @@ def attention_rescore(model, enc, wave_len, nbest_lists, ctc_weight):
                 sc = lam * (ctc + bias) + (1.0 - lam) * a if a != -math.inf else -math.inf
                 cands.append(dict(yseq=list(seqs[b][j]), score=sc, att_score=a, ctc_score=ctc, bias=bias))
                 continue
+            if "lm_score" in h:
+                ctc, l = float(h["ctc_score"]), float(h["lm_score"])
+                sc = lam * (ctc + l) + (1.0 - lam) * a if a != -math.inf else -math.inf
+                cands.append(dict(yseq=list(seqs[b][j]), score=sc, att_score=a, ctc_score=ctc, lm_score=l))
+                continue
             ctc = float(h["score"])
             sc = lam * ctc + (1.0 - lam) * a if a != -math.inf else -math.inf
             cands.append(dict(yseq=list(seqs[b][j]), score=sc, att_score=a, ctc_score=ctc))
@@ -397,10 +453,13 @@ def attention_rescore(model, enc, wave_len, nbest_lists, ctc_weight):
     return out
 
 
-def ctc_rescore_search(model, input, beam_size=5, nbest=1, ctc_weight=0.0, frame_topk=10, context=None, context_ids=None):
+def ctc_rescore_search(model, input, beam_size=5, nbest=1, ctc_weight=0.0, frame_topk=10, context=None, context_ids=None, lm=None):
     """The U2 two-pass search offline: ctc_prefix_beam_search with n-best = beam_size, then attention_rescore of that list against the
     same encoder output (the encoder runs once).  Returns per utterance at most `nbest` {'yseq' (no sos / eos), 'score', 'att_score',
-    'ctc_score'}.  context / context_ids: the first pass is hotword-biased (ctc_prefix_beam_search); entries gain 'bias'."""
+    'ctc_score'}.  context / context_ids: the first pass is hotword-biased (ctc_prefix_beam_search); entries gain 'bias'.  lm: the first
+    pass runs with the n-gram LM; entries gain 'lm_score'."""
+    if lm is not None:
+        _check_lm(model, lm, context)
     eng = model._ensure_engine(input.wave.device)
     if not (eng.use_ctc and eng.use_decoder):
         raise RuntimeError("CTC n-best rescoring needs a model with both the attention decoder and the CTC head (0 < config.ctc_weight < 1)")
@@ -411,7 +470,7 @@ def ctc_rescore_search(model, input, beam_size=5, nbest=1, ctc_weight=0.0, frame
     finally:
         eng.training = was_training
     with model.given_encoder_output(enc):
-        hyps = ctc_prefix_beam_search(model, input, beam_size, beam_size, frame_topk, context=context, context_ids=context_ids)
+        hyps = ctc_prefix_beam_search(model, input, beam_size, beam_size, frame_topk, context=context, context_ids=context_ids, lm=lm)
     res = attention_rescore(model, enc, input.wave_len, hyps, ctc_weight)
     return [r[:nbest] for r in res]
 

@@ -434,18 +434,27 @@ def _context_roots(context, roots, B, device):
     return host, torch.tensor(host, dtype=torch.int32, device=device)
 
 
-def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max_len=None, context=None, roots=None):
+def _no_lm_with_context(lm, context):
+    if lm is not None and context is not None:
+        raise ValueError("an n-gram LM (lm=...) and a hotword context (context=...) cannot be combined: the search runs one of the two")
+
+
+def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max_len=None, context=None, roots=None, lm=None):
     """CTC prefix beam search on the device over the per-frame candidates of ctc_frame_topk (include/asr_hip.h).
     Returns (tokens (B, nbest, Lcap) int32, lengths (B, nbest) int32 with -1 for missing ranks, scores (B, nbest) float32).
     context (a context.ContextGraph): the hotword-biased search (asr_ctc_prefix_beam_ctx) - roots = the root state of each utterance's
     graph (-1: not biased; None: graph 0 for all); the result gains (bias (B, nbest) float64, the raw bias before held(state) is taken
-    off, state (B, nbest) int32), and the entries are in the beam's rank order (log p + raw bias)."""
+    off, state (B, nbest) int32), and the entries are in the beam's rank order (log p + raw bias).
+    lm (an lm.NgramLM): n-gram LM shallow fusion (asr_ctc_prefix_beam_lm); the result gains (bias (B, nbest) float64, the entries' LM bias
+    without the end-of-sentence term, state (B, nbest) int32, their LM state), in the beam's rank order (log p + bias).  Not with a context."""
+    _no_lm_with_context(lm, context)
     k = vals.shape[1]
     assert vals.shape == (B * T, k) and ids.shape == (B * T, k) and blank_lp.numel() == B * T
     _chk_f32(vals, blank_lp)
     _chk_i32(ids, in_len)
     Lcap = int(T if max_len is None else max_len)
-    ws = torch.empty(lib.asr_ctc_prefix_beam_workspace_bytes(B, T, beam), dtype=torch.uint8, device=vals.device)
+    ws_bytes = lib.asr_ctc_prefix_beam_workspace_bytes(B, T, beam) if lm is None else lib.asr_ctc_prefix_beam_lm_workspace_bytes(B, T, beam)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=vals.device)
     out_tok = torch.zeros(B, nbest, Lcap, dtype=torch.int32, device=vals.device)
     out_len = torch.empty(B, nbest, dtype=torch.int32, device=vals.device)
     out_score = torch.empty(B, nbest, dtype=torch.float32, device=vals.device)
@@ -458,6 +467,14 @@ def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max
                                           _p(out_tok), _p(out_len), _p(out_score), _p(out_bias), _p(out_state), B, T, k, int(beam), int(nbest), Lcap,
                                           int(blank), _stream()), "asr_ctc_prefix_beam_ctx")
         return out_tok, out_len, out_score, out_bias, out_state
+    if lm is not None:
+        _, tabs = lm.on(vals.device)
+        out_bias = torch.empty(B, nbest, dtype=torch.float64, device=vals.device)
+        out_state = torch.empty(B, nbest, dtype=torch.int32, device=vals.device)
+        check(lib.asr_ctc_prefix_beam_lm(_p(vals), _p(ids), _p(blank_lp), _p(in_len), ctypes.addressof(tabs), _p(ws), ws.numel(), _p(out_tok), _p(out_len),
+                                         _p(out_score), _p(out_bias), _p(out_state), B, T, k, int(beam), int(nbest), Lcap, int(blank), _stream()),
+              "asr_ctc_prefix_beam_lm")
+        return out_tok, out_len, out_score, out_bias, out_state
     check(lib.asr_ctc_prefix_beam(_p(vals), _p(ids), _p(blank_lp), _p(in_len), _p(ws), ws.numel(), _p(out_tok), _p(out_len), _p(out_score),
                                   B, T, k, int(beam), int(nbest), Lcap, int(blank), _stream()), "asr_ctc_prefix_beam")
     return out_tok, out_len, out_score
@@ -467,20 +484,28 @@ class PrefixBeamState:
     """The resumable prefix beam search's device memory (include/asr_hip.h): `state` (the beam of each utterance between chunks) and
     `ws` (the trie, room for T_cap frames per utterance); `frames` = frames consumed per utterance, kept on the host so that a
     chunk past T_cap is refused before any launch.  context: the ContextGraph of a context state (None: a plain state) - a context state
-    is larger (bias, context state and root per utterance) and only ever reaches the _ctx entry points."""
+    is larger (bias, context state and root per utterance) and only ever reaches the _ctx entry points.  lm: the NgramLM of an LM state
+    (bias and LM state per entry), which only ever reaches the _lm entry points."""
 
-    def __init__(self, state, ws, B, beam, T_cap, context=None, roots=None):
+    def __init__(self, state, ws, B, beam, T_cap, context=None, roots=None, lm=None):
         self.state, self.ws, self.B, self.beam, self.T_cap = state, ws, B, beam, T_cap
         self.frames = [0] * B
-        self.context, self.roots = context, roots
+        self.context, self.roots, self.lm = context, roots, lm
 
 
-def ctc_prefix_beam_state(B, beam, T_cap, device="cuda", context=None, roots=None):
+def ctc_prefix_beam_state(B, beam, T_cap, device="cuda", context=None, roots=None, lm=None):
     """A fresh PrefixBeamState: the empty-prefix beam for B utterances of at most T_cap frames each.  context / roots: a context
-    state for the hotword-biased search (roots as ctc_prefix_beam's)."""
+    state for the hotword-biased search (roots as ctc_prefix_beam's).  lm: an LM state, every utterance on the LM's start state."""
+    _no_lm_with_context(lm, context)
     B, beam, T_cap = int(B), int(beam), int(T_cap)
     if B < 1 or beam < 1 or T_cap < 1:
         raise ValueError(f"ctc_prefix_beam_state: B, beam and T_cap must be >= 1 (got {B}, {beam}, {T_cap})")
+    if lm is not None:
+        _, tabs = lm.on(device)
+        state = torch.zeros(lib.asr_ctc_prefix_beam_lm_state_bytes(B, beam) // 8, dtype=torch.int64, device=device)      # 8-aligned
+        ws = torch.empty(lib.asr_ctc_prefix_beam_lm_workspace_bytes(B, T_cap, beam), dtype=torch.uint8, device=device)      # the trie with child lists
+        check(lib.asr_ctc_prefix_beam_lm_state_init(_p(state), _p(ws), ctypes.addressof(tabs), B, beam, T_cap, _stream()), "asr_ctc_prefix_beam_lm_state_init")
+        return PrefixBeamState(state, ws, B, beam, T_cap, lm=lm)
     if context is not None:
         host, root_dev = _context_roots(context, roots, B, device)
         state = torch.zeros(lib.asr_ctc_prefix_beam_ctx_state_bytes(B, beam) // 8, dtype=torch.int64, device=device)      # 8-aligned
@@ -528,7 +553,9 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
     caller has uploaded already; extra_words (packed only): int32 words left free behind the results in the returned buffer, for
     what else travels to the host in the same copy.
     A context state (st.context): the biased search (asr_ctc_prefix_beam_chunk_ctx); the result gains bias (B, nbest) float64 (raw) and
-    state (B, nbest) int32, and the packed buffer grows to prefix_beam_ctx_words (prefix_beam_ctx_unpack reads the two)."""
+    state (B, nbest) int32, and the packed buffer grows to prefix_beam_ctx_words (prefix_beam_ctx_unpack reads the two).
+    An LM state (st.lm): the search with the n-gram LM (asr_ctc_prefix_beam_chunk_lm); the same two additions, bias without the
+    end-of-sentence term and the LM state."""
     B, beam, k = st.B, st.beam, vals.shape[1]
     C, nbest = int(C), int(nbest)
     nv = [int(x) for x in n_valid]
@@ -542,7 +569,7 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
     _chk_i32(ids)
     Lcap = int(max(1, max(f + n for f, n in zip(st.frames, nv))) if max_len is None else max_len)
     n_words = B * (nbest * (Lcap + 2) + 1)
-    n_all = n_words if st.context is None else prefix_beam_ctx_words(B, nbest, Lcap)
+    n_all = n_words if st.context is None and st.lm is None else prefix_beam_ctx_words(B, nbest, Lcap)
     out = torch.zeros(n_all + (int(extra_words) if packed else 0), dtype=torch.int32, device=vals.device)
     out_tok, out_len, out_score, out_stable = prefix_beam_unpack(out[:n_words], B, nbest, Lcap)
     if nv_dev is None:
@@ -558,6 +585,15 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
         for b in range(B):
             st.frames[b] += nv[b]
         return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable, out_bias, out_state)
+    if st.lm is not None:
+        out_bias, out_state = prefix_beam_ctx_unpack(out[:n_all], B, nbest, Lcap)
+        _, tabs = st.lm.on(vals.device)
+        check(lib.asr_ctc_prefix_beam_chunk_lm(_p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(), ctypes.addressof(tabs),
+                                               _p(out_tok), _p(out_len), _p(out_score), _p(out_bias), _p(out_state), _p(out_stable), B, C, k, beam, nbest,
+                                               Lcap, st.T_cap, int(blank), _stream()), "asr_ctc_prefix_beam_chunk_lm")
+        for b in range(B):
+            st.frames[b] += nv[b]
+        return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable, out_bias, out_state)
     check(lib.asr_ctc_prefix_beam_chunk(_p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(), _p(out_tok), _p(out_len),
                                         _p(out_score), _p(out_stable), B, C, k, beam, nbest, Lcap, st.T_cap, int(blank), _stream()),
           "asr_ctc_prefix_beam_chunk")
@@ -566,12 +602,24 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
     return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable)
 
 
-def ctc_prefix_beam_state_reset(st, flags, slots=(), roots=None):
+def ctc_prefix_beam_state_reset(st, flags, slots=(), roots=None, lm=None):
     """Re-initialise the utterances of a PrefixBeamState whose flags[b] != 0 (flags: (B) int32 on the device; `slots`: the same
     utterances as host ints, for the host-side frame counters): byte for byte what ctc_prefix_beam_state leaves for them.
-    A context state: roots = the B roots after the reset (those of the flagged utterances are applied; None: all as they are)."""
+    A context state: roots = the B roots after the reset (those of the flagged utterances are applied; None: all as they are).
+    An LM state: the flagged utterances restart on the LM's start state (lm, if given, is the state's own)."""
     _chk_i32(flags)
     assert flags.numel() == st.B
+    if lm is not None and lm is not st.lm:
+        raise ValueError("ctc_prefix_beam_state_reset: lm must be the NgramLM the state was made with (one LM serves every utterance)")
+    if st.lm is not None:
+        if roots is not None:
+            raise ValueError("ctc_prefix_beam_state_reset: roots apply to a context state")
+        _, tabs = st.lm.on(st.state.device)
+        check(lib.asr_ctc_prefix_beam_lm_state_reset(_p(st.state), _p(st.ws), _p(flags), ctypes.addressof(tabs), st.B, st.beam, st.T_cap, _stream()),
+              "asr_ctc_prefix_beam_lm_state_reset")
+        for b in slots:
+            st.frames[int(b)] = 0
+        return
     if st.context is not None:
         host, root_dev = _context_roots(st.context, st.roots if roots is None else roots, st.B, st.state.device)
         check(lib.asr_ctc_prefix_beam_ctx_state_reset(_p(st.state), _p(st.ws), _p(flags), _p(root_dev), st.B, st.beam, st.T_cap, _stream()),

@@ -73,7 +73,7 @@ def endpoint_rule(rules, frame_us, trailing, frames, decoded):
 
 
 class Sessions:
-    def __init__(self, model, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None):
+    def __init__(self, model, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None):
         C, left = model.decoding_chunk_size, model.decoding_left_chunks
         if C <= 0:
             raise ValueError("model.sessions() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
@@ -100,6 +100,13 @@ class Sessions:
             from . import decode
             decode._check_context(model, context)
         self.graph = [0 if context is not None else -1] * self.S      # the graph of each slot's session (-1: not biased)
+        # n-gram LM shallow fusion (lm.NgramLM): one LM for all slots; the reset kernel puts a reopened slot on its start state
+        self.lm = lm
+        if lm is not None:
+            if search != "prefix_beam":
+                raise ValueError("an n-gram LM (lm=...) is supported by search='prefix_beam' (the CTC prefix beam search), not by search='greedy'")
+            from . import decode
+            decode._check_lm(model, lm, context)
         self.endpoint = endpoint_config(endpoint)
         thr = self.endpoint["blank_threshold"] if self.endpoint else ENDPOINT_DEFAULTS["blank_threshold"]
         self.silence_lp = math.log(thr)      # the kernel compares float32(log threshold) with float32 log p(blank)
@@ -287,7 +294,7 @@ class Sessions:
                 if self.search == "prefix_beam":
                     roots = None if self.context is None else self.context.roots(self.graph, S)
                     if self.beam is None:
-                        self.beam = K.ctc_prefix_beam_state(S, self.beam_size, eng.pe.shape[0], dev, context=self.context, roots=roots)
+                        self.beam = K.ctc_prefix_beam_state(S, self.beam_size, eng.pe.shape[0], dev, context=self.context, roots=roots, lm=self.lm)
                     elif reset_slots:
                         K.ctc_prefix_beam_state_reset(self.beam, pd[P_RESET], reset_slots, roots=roots)
                     vals, ids, blank_lp = K.ctc_frame_topk(logits, self.frame_topk, BLANK)
@@ -299,7 +306,7 @@ class Sessions:
                     n_plain = S * (self.beam_size * (Lcap + 2) + 1)
                     tok, ln, sc, stable = (t.numpy() for t in K.prefix_beam_unpack(host[:n_plain], S, self.beam_size, Lcap))
                     self._hyps = (tok, ln, sc)
-                    if self.context is not None:
+                    if self.context is not None or self.lm is not None:
                         self._hyps += tuple(t.numpy() for t in K.prefix_beam_ctx_unpack(host[:n_words], S, self.beam_size, Lcap))
                     step = host[n_words:].view(S, 4 + C).tolist()
                     for b in reset_slots:
@@ -375,11 +382,19 @@ class Sessions:
 
     def nbest(self, b):
         """search="prefix_beam": slot b's current list of {"yseq", "score"}, best first (at most beam_size).  With a context:
-        {"yseq", "score", "ctc_score", "bias"}, ordered by score = ctc_score + bias."""
+        {"yseq", "score", "ctc_score", "bias"}, ordered by score = ctc_score + bias.  With an LM: {"yseq", "score", "ctc_score",
+        "lm_score"}, ordered by score = ctc_score + lm_score."""
         self._need_beam("nbest()")
         b = self._slot(b)
         if self.state[b] == FREE:
             raise ValueError(f"nbest: slot {b} is free")
+        if self.lm is not None:
+            from .decode import lm_entries
+            if self._hyps is None or self.fresh[b]:      # the empty hypothesis on the start state: only the end-of-sentence term
+                l = self.lm.final(self.lm.start, 0.0)
+                return [{"yseq": [], "score": 0.0 + l, "ctc_score": 0.0, "lm_score": l}]
+            tok, ln, sc, bias, state = self._hyps
+            return lm_entries(self.lm, tok[b], ln[b], sc[b], bias[b], state[b])
         if self._hyps is None or self.fresh[b]:
             return [{"yseq": [], "score": 0.0, "ctc_score": 0.0, "bias": 0.0}] if self.context is not None else [{"yseq": [], "score": 0.0}]
         if self.context is not None:
@@ -395,6 +410,8 @@ class Sessions:
         out = {"ids": h[0]["yseq"] if h else [], "stable_len": self.stable[self._slot(b)], "score": h[0]["score"] if h else float("-inf")}
         if self.context is not None:
             out["bias"] = h[0]["bias"] if h else 0.0
+        if self.lm is not None:
+            out["lm_score"] = h[0]["lm_score"] if h else 0.0
         return out
 
     def encoder_output(self, slots):
@@ -428,6 +445,9 @@ class Sessions:
         if self.context is not None:
             for r in res:
                 r["bias"] = 0.0
+        if self.lm is not None:
+            for r in res:
+                r["lm_score"] = 0.0
         live = [i for i, b in enumerate(slots) if self.frames[b] > 0]
         if live:
             rows = [slots[i] for i in live]
@@ -442,15 +462,19 @@ class Sessions:
                 ids = [list(h[0]["yseq"]) if h else [] for h in hyps]
                 scores = [float(h[0]["score"]) if h else float("-inf") for h in hyps]
                 biases = [float(h[0]["bias"]) if h else 0.0 for h in hyps] if self.context is not None else None
+                if self.lm is not None:
+                    biases = [float(h[0]["lm_score"]) if h else 0.0 for h in hyps]
 
                 def ctc_logits():
                     with torch.no_grad():
                         return self.eng.ctc_lo.fwd(enc.reshape(n * T, -1).contiguous()).view(n, T, -1)
-                got = model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens, biases)
+                got = model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens, biases, "lm_score" if self.lm is not None else "bias")
             else:
                 # under given_encoder_output the searches take the batch's features for their (B, T) only: none are kept
                 wave = torch.zeros(n, T, 1, dtype=enc.dtype, device=enc.device)
                 ctx = dict(context=self.context, context_ids=[self.graph[b] for b in rows]) if self.context is not None else {}
+                if self.lm is not None:
+                    ctx = dict(lm=self.lm)
                 with model.given_encoder_output(enc):
                     got = model.transcribe(Pack(wave=wave, wave_len=lens), beam_size=beam_size, **kw, **ctx)
             for i, r in zip(live, got):

@@ -26,7 +26,7 @@ BLANK = 0      # the CTC blank (= PAD_ID of the model)
 
 
 class StreamingEncoder:
-    def __init__(self, model, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None):
+    def __init__(self, model, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None, lm=None):
         C, left = model.decoding_chunk_size, model.decoding_left_chunks
         if C <= 0:
             raise ValueError("model.stream() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
@@ -63,9 +63,16 @@ class StreamingEncoder:
             decode._check_context(model, context)
             self.graphs = [0] * self.B if context_ids is None else [int(g) for g in context_ids]
             self.roots = context.roots(self.graphs, self.B)
+        # n-gram LM shallow fusion (lm.NgramLM): the streamed search ranks by log p + the hypothesis's LM bias; one LM for every utterance
+        self.lm = lm
+        if lm is not None:
+            if search != "prefix_beam":
+                raise ValueError("an n-gram LM (lm=...) is supported by search='prefix_beam' (the CTC prefix beam search), not by search='greedy'")
+            from . import decode
+            decode._check_lm(model, lm, context)
         self.beam = None                     # K.PrefixBeamState, allocated by the first push for the positional-encoding table's frames
         self.stable = [0] * self.B           # tokens of each utterance handed out by push so far (beam mode)
-        self._hyps = None                    # the last push's (tokens, lengths, scores) as host arrays; with a context also (bias, state)
+        self._hyps = None                    # the last push's (tokens, lengths, scores) as host arrays; with a context or an LM also (bias, state)
         self.parser, self.frontend = parser, None      # the front end is built by the first push_audio
         # source_rate: the rate of the audio push_audio receives; other than 16 kHz it goes through a StreamResampler first (None: 16 kHz)
         self.source_rate, self.resampler = source_rate, None
@@ -154,7 +161,7 @@ class StreamingEncoder:
                 out = [[] for _ in range(B)]
                 if self.search == "prefix_beam":
                     if self.beam is None:      # the trie for every frame push admits: B * 2 * (table * beam + 1) * 4 bytes
-                        self.beam = K.ctc_prefix_beam_state(B, self.beam_size, eng.pe.shape[0], dev, context=self.context, roots=self.roots)
+                        self.beam = K.ctc_prefix_beam_state(B, self.beam_size, eng.pe.shape[0], dev, context=self.context, roots=self.roots, lm=self.lm)
                     vals, ids, blank_lp = K.ctc_frame_topk(eng.ctc_lo.fwd(h), self.frame_topk, BLANK)
                     buf, Lcap = K.ctc_prefix_beam_chunk(self.beam, vals, ids, blank_lp, nv, C, self.beam_size, BLANK, packed=True)
                     # one copy: tokens, lengths, scores and stable lengths (with a context also bias and state) travel in one buffer
@@ -163,7 +170,7 @@ class StreamingEncoder:
                     n_words = B * (self.beam_size * (Lcap + 2) + 1)
                     tok, ln, sc, stable = (t.numpy() for t in K.prefix_beam_unpack(host[:n_words], B, self.beam_size, Lcap))
                     self._hyps = (tok, ln, sc)
-                    if self.context is not None:
+                    if self.context is not None or self.lm is not None:
                         self._hyps += tuple(t.numpy() for t in K.prefix_beam_ctx_unpack(host, B, self.beam_size, Lcap))
                     for b in range(B):      # every entry shares the stable prefix, so rank 0 spells it whatever the order by score
                         out[b] = tok[b, 0, self.stable[b]:int(stable[b])].tolist()
@@ -231,8 +238,16 @@ class StreamingEncoder:
 
     def nbest(self):
         """search="prefix_beam": per utterance the search's current list of {"yseq", "score"}, best first (at most beam_size).
-        With a context: {"yseq", "score", "ctc_score", "bias"}, ordered by score = ctc_score + bias."""
+        With a context: {"yseq", "score", "ctc_score", "bias"}, ordered by score = ctc_score + bias.  With an LM: {"yseq", "score",
+        "ctc_score", "lm_score"}, ordered by score = ctc_score + lm_score."""
         self._need_beam("nbest()")
+        if self.lm is not None:
+            from .decode import lm_entries
+            if self._hyps is None:      # the empty hypothesis on the start state: only the end-of-sentence term
+                l = self.lm.final(self.lm.start, 0.0)
+                return [[{"yseq": [], "score": 0.0 + l, "ctc_score": 0.0, "lm_score": l}] for _ in range(self.B)]
+            tok, ln, sc, bias, state = self._hyps
+            return [lm_entries(self.lm, tok[b], ln[b], sc[b], bias[b], state[b]) for b in range(self.B)]
         if self._hyps is None:
             if self.context is not None:
                 return [[{"yseq": [], "score": 0.0, "ctc_score": 0.0, "bias": 0.0}] for _ in range(self.B)]
@@ -247,13 +262,16 @@ class StreamingEncoder:
 
     def partial(self):
         """search="prefix_beam": per utterance {"ids": the best prefix now (revisable past stable_len), "stable_len": how many of its
-        tokens are final (the concatenation of what push returned), "score": its log-probability}; with a context also "bias" (and the
-        score includes it)."""
+        tokens are final (the concatenation of what push returned), "score": its log-probability}; with a context also "bias", with an
+        LM "lm_score" (and the score includes it)."""
         out = [{"ids": h[0]["yseq"] if h else [], "stable_len": self.stable[b], "score": h[0]["score"] if h else float("-inf")}
                for b, h in enumerate(self.nbest())]
         if self.context is not None:
             for o, h in zip(out, self.nbest()):
                 o["bias"] = h[0]["bias"] if h else 0.0
+        if self.lm is not None:
+            for o, h in zip(out, self.nbest()):
+                o["lm_score"] = h[0]["lm_score"] if h else 0.0
         return out
 
     def _live_only(self, timestamps, search):
@@ -265,6 +283,9 @@ class StreamingEncoder:
         if self.context is not None:
             for o in out:
                 o["bias"] = 0.0
+        if self.lm is not None:
+            for o in out:
+                o["lm_score"] = 0.0
         for b, r in zip(live, res):
             out[b] = r
         return out
@@ -286,12 +307,14 @@ class StreamingEncoder:
             ids = [list(h[0]["yseq"]) if h else [] for h in hyps]
             scores = [float(h[0]["score"]) if h else float("-inf") for h in hyps]
             biases = [float(h[0]["bias"]) if h else 0.0 for h in hyps] if self.context is not None else None
+            if self.lm is not None:
+                biases = [float(h[0]["lm_score"]) if h else 0.0 for h in hyps]
             B, T = enc.shape[0], enc.shape[1]
 
             def ctc_logits():
                 with torch.no_grad():
                     return self.eng.ctc_lo.fwd(enc.reshape(B * T, -1).contiguous()).view(B, T, -1)
-            return model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens, biases)
+            return model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens, biases, "lm_score" if self.lm is not None else "bias")
         return self._live_only(timestamps, search)
 
     def finish(self, beam_size=5, **kw):
@@ -309,6 +332,8 @@ class StreamingEncoder:
             ctx = {}
             if self.context is not None:      # a fresh offline search over the streamed encoder output, biased as the stream is
                 ctx = dict(context=self.context, context_ids=[self.graphs[b] for b in rows])
+            if self.lm is not None:
+                ctx = dict(lm=self.lm)
             with self.model.given_encoder_output(enc):
                 return self.model.transcribe(Pack(wave=wave, wave_len=lens), beam_size=beam_size, **kw, **ctx)
         return self._live_only(kw.get("timestamps", True), search)

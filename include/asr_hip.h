@@ -388,6 +388,54 @@ int asr_ctc_prefix_beam_chunk_ctx(const float* vals, const int32_t* ids, const f
                                   size_t ws_bytes, const asr_context_graph* ctx, int32_t* out_tok, int32_t* out_len, float* out_score,
                                   double* out_bias, int32_t* out_state, int32_t* out_stable, int B, int C, int k, int beam, int nbest, int Lcap,
                                   int T_cap, int blank, void* stream);
+/* N-gram LM shallow fusion in the CTC prefix beam search (additive to ABI 10; the definition: asr_chinese_e2e_amd/lm.py, restated in fp64 by
+ *   tests/lm_ref.py).  asr_ngram_lm: a back-off n-gram model (ARPA semantics, orders 1 to 5) as one flat automaton on the device.  State 0
+ *   is the empty history and has no arcs; a state s >= 1 is a context of 1 .. order - 1 tokens with the arcs [st_off[s], st_off[s + 1]),
+ *   ascending arc_tok.  An arc (s, c) carries arc_term, the term of the listed n-gram s.c, and arc_next >= 0, the state after c; arc_next =
+ *   ~state marks an arc whose n-gram is not listed itself (only longer ones are): it fixes the next state and the chain goes on.  st_back[s] =
+ *   the state of the longest proper suffix of s that is a state, st_bow[s] = the back-off term (0.0: none).  uni_term[c] / uni_next[c]: the
+ *   unigram level, dense over the V tokens (the unk term and state 0 where there is no unigram), so every chain ends in one indexed load.
+ *   Every term is fp64 weight * ln p, folded on the host.  A beam entry carries (state, bias) from (start, 0.0); appending token c walks
+ *   the chain from its state: bias += st_bow per state left, bias += the term of the n-gram found, bias += ins; the state becomes that of the
+ *   first arc met (uni_next at the end of the chain).  Candidates of a frame are ranked by log p + bias; nothing else of the search changes,
+ *   and out_score stays log p.  An LM and a context graph are not combined: each has its own entry points and its own state layout.
+ *   THE WRAPPERS CHECK pointers, alignment (8 bytes for anything fp64), S >= 1, A >= 0, V >= 1, 1 <= order <= 5, 0 <= start < S, a finite ins
+ *   and the searches' limits; THEY CANNOT CHECK THE TABLES' CONTENTS, which live on the device: NgramLM is their only producer and validates
+ *   them.  The kernels still clamp every table index they form and bound the chain by `order`.
+ * asr_ctc_prefix_beam_lm: asr_ctc_prefix_beam with an LM.  Two more outputs per n-best entry: out_bias (B, nbest) fp64, 8-aligned - the
+ *   entry's bias WITHOUT the end-of-sentence term (the caller adds term(</s> | out_state) and sorts by log p + that, stable) - and out_state
+ *   (B, nbest) int32 (-1: no entry).  The entries are in the beam's rank order (log p + bias).
+ * asr_ctc_prefix_beam_lm_workspace_bytes: the LM searches' trie, offline (T frames) and resumable (T = T_cap): twice the plain search's,
+ *   int32 [parent | token | first child | sibling] x (T * beam + 1) nodes per utterance.  The child lists make a prefix that left the beam
+ *   and comes back take the node it had, so that a longer prefix that stayed is still recognised as its extension (with an insertion bonus
+ *   that happens; the plain search would hold the same string twice and split its probability).
+ * asr_ctc_prefix_beam_lm_state_bytes / _lm_state_init / _lm_state_reset / asr_ctc_prefix_beam_chunk_lm: the resumable form.  The state of one
+ *   utterance is asr_ctc_prefix_beam_chunk's, followed by fp64 bias[beam], int32 st[beam], padded to 8 bytes; init puts every utterance on
+ *   lm->start, reset the flagged ones, every other utterance keeps every byte; their workspace is asr_ctc_prefix_beam_lm_workspace_bytes(B, T_cap, beam).  An LM state is only ever passed to the _lm entry points.
+ *   Cutting the frames into chunks changes no bit of any output, and a chunk that consumes nothing changes no byte of the state. */
+typedef struct asr_ngram_lm {
+    const int32_t* st_off;    /* device, (S + 1) */
+    const int32_t* arc_tok;   /* device, (A) */
+    const int32_t* arc_next;  /* device, (A) */
+    const double* arc_term;   /* device, (A), 8-aligned */
+    const int32_t* st_back;   /* device, (S) */
+    const double* st_bow;     /* device, (S), 8-aligned */
+    const double* uni_term;   /* device, (V), 8-aligned */
+    const int32_t* uni_next;  /* device, (V) */
+    int S, A, V, order, start;
+    double ins;
+} asr_ngram_lm;
+int asr_ctc_prefix_beam_lm(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* in_len, const asr_ngram_lm* lm, void* ws,
+                           size_t ws_bytes, int32_t* out_tok, int32_t* out_len, float* out_score, double* out_bias, int32_t* out_state, int B,
+                           int T, int k, int beam, int nbest, int Lcap, int blank, void* stream);
+size_t asr_ctc_prefix_beam_lm_workspace_bytes(int B, int T, int beam);
+size_t asr_ctc_prefix_beam_lm_state_bytes(int B, int beam);
+int asr_ctc_prefix_beam_lm_state_init(void* state, void* ws, const asr_ngram_lm* lm, int B, int beam, int T_cap, void* stream);
+int asr_ctc_prefix_beam_lm_state_reset(void* state, void* ws, const int32_t* flags, const asr_ngram_lm* lm, int B, int beam, int T_cap, void* stream);
+int asr_ctc_prefix_beam_chunk_lm(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* n_valid, void* state, void* ws,
+                                 size_t ws_bytes, const asr_ngram_lm* lm, int32_t* out_tok, int32_t* out_len, float* out_score, double* out_bias,
+                                 int32_t* out_state, int32_t* out_stable, int B, int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank,
+                                 void* stream);
 int asr_decode_attn(const void* q, const void* k, const void* v, void* o, const int32_t* k_len,
                     int k_len_uniform, int len_div, int R, int H, int dk, int Tk_cap, int kv_div,
                     int ldq, int ldk, int ldv, int ldo, float scale, int dtype, void* stream);

@@ -46,6 +46,11 @@ trained with rebuild it.  Inference flags:
                  Offline it needs a search that runs the prefix beam search (a CTC-only model, or --joint=ctc_rescore); with --stream=1
                  (--sessions=N included) it needs --stream_search=prefix_beam
   --context_score  the bonus per matched hotword token (default 3.0, WeNet's context_score)
+  --lm           an n-gram language model in ARPA format over the vocabulary's characters (orders 1 to 5; lm.NgramLM.from_arpa), or the
+                 .npz that NgramLM.save wrote (its weights are the saved ones): shallow fusion in the CTC prefix beam search, and the
+                 final lines gain "lm_score".  The same searches as --context admits; not together with --context
+  --lm_weight    the LM weight (default 0.3)
+  --lm_ins       the bonus per token of a hypothesis (default 0.0)
 Audio goes through load_wav -> AudioParser.parse_batch on the device -> model.transcribe; one JSON line per file is printed:
 {"file", "duration_s", "text", "ids", "score", "tokens": [{"id", "token", "start_frame", "end_frame", "start_s", "end_s", "logp"}]}.
 """
@@ -67,7 +72,7 @@ from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
 from asr_chinese_e2e_amd.data_handler import resample as resample_mod  # noqa: E402
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint", "context", "context_score")
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint", "context", "context_score", "lm", "lm_weight", "lm_ins")
 
 
 def _finite(x):
@@ -158,6 +163,8 @@ def final_line(path, n_samples, sr, r, shift_s, sample_rate):
             "score": _finite(r["score"]), "tokens": r["tokens"]}
     if "bias" in r:
         line["bias"] = r["bias"]
+    if "lm_score" in r:
+        line["lm_score"] = r["lm_score"]
     if sr != sample_rate:
         line["source_rate"] = sr
     return line
@@ -258,6 +265,25 @@ def transcribe(**flags):
             raise SystemExit(f"transcribe.py: --context: {e}") from e
         if stream:
             stream_kw["context"] = context
+    lm = None
+    if cli.get("lm") not in (None, "", False):
+        from asr_chinese_e2e_amd.lm import NgramLM
+        if context is not None:
+            raise SystemExit("transcribe.py: --lm and --context cannot be combined: the search runs one of the two")
+        if stream and stream_search != "prefix_beam":
+            raise SystemExit("transcribe.py: --lm with --stream=1 needs --stream_search=prefix_beam (the LM is fused into the CTC prefix beam search)")
+        if not stream and model.use_decoder and joint != "ctc_rescore":
+            raise SystemExit("transcribe.py: --lm needs a search that runs the CTC prefix beam search: a CTC-only model or --joint=ctc_rescore")
+        try:
+            if str(cli["lm"]).endswith(".npz"):
+                lm = NgramLM.load(str(cli["lm"]), device="cuda")
+            else:
+                lm = NgramLM.from_arpa(str(cli["lm"]), vocab, weight=float(cli.get("lm_weight", 0.3)), ins=float(cli.get("lm_ins", 0.0)), device="cuda")
+            lm.check_vocab(model.V)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"transcribe.py: --lm: {e}") from e
+        if stream:
+            stream_kw["lm"] = lm
     resample = bool(int(cli.get("resample", 0)))      # --resample=1: files at another rate are converted on the GPU instead of ending the run
     if stream and model.decoding_chunk_size <= 0:
         raise SystemExit("transcribe.py: --stream=1 needs a decoding chunk (--decoding_chunk_size, or a static --chunk_size)")
@@ -304,6 +330,8 @@ def transcribe(**flags):
         search = dict(beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps, joint=joint)
         if context is not None and not stream:
             search["context"] = context
+        if lm is not None and not stream:
+            search["lm"] = lm
         if stream_kw:      # the streamed search's own n-best, re-ranked by the decoder
             search = dict(ctc_weight=ctc_weight, timestamps=timestamps, joint="ctc_rescore")
         if stream and parser.norm == "global":      # the samples stream: blocks of one chunk's worth of audio unless told otherwise
