@@ -329,7 +329,8 @@ class _SpeechTransformer(BaseModel):
                 self._enc_given = prev
         return ctx()
 
-    def stream(self, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None, lm=None):
+    def stream(self, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None, lm=None,
+               timed=False, confidence="post_max"):
         """A streaming encoder for `batch_size` utterances (stream.StreamingEncoder): push chunks of encoder-rate features, get the
         greedy CTC ids each chunk adds; finish() gives transcribe()'s result for the same decoding chunk mask.  With an AudioParser
         of norm="global" it also takes audio as it arrives: push_audio(pcm, n_samples, final) - at source_rate, converted to
@@ -340,20 +341,25 @@ class _SpeechTransformer(BaseModel):
         context (a context.ContextGraph; search="prefix_beam" only) / context_ids (the graph per utterance; None: graph 0, -1: none):
         hotword biasing of the streamed search - partial(), nbest() and finish() then report 'bias' and order by 'score'.
         lm (an lm.NgramLM; search="prefix_beam" only, not with a context): n-gram LM shallow fusion of the streamed search - partial(),
-        nbest() and finish() then report 'lm_score' and order by 'score'."""
+        nbest() and finish() then report 'lm_score' and order by 'score'.
+        timed=True (search="greedy" only): tokens() gives every emitted character's frames, times and confidence as the audio arrives
+        (confidence.TokenLog); confidence picks the measure reported as "confidence" (confidence.MEASURES).  push returns what it returns."""
         from ..stream import StreamingEncoder
         return StreamingEncoder(self, batch_size, parser=parser, source_rate=source_rate, search=search, beam_size=beam_size, frame_topk=frame_topk,
-                                context=context, context_ids=context_ids, lm=lm)
+                                context=context, context_ids=context_ids, lm=lm, timed=timed, confidence=confidence)
 
-    def sessions(self, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None):
+    def sessions(self, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None,
+                 timed=False, confidence="post_max"):
         """`slots` independent streaming sessions in one batch (sessions.Sessions): each slot is opened, fed (push / push_audio),
         closed, finished and reopened at its own pace - open(b), push(feats, n_valid, final), finish(b) - and with endpoint={...} the
         CTC endpoint rules report per slot when its speaker has stopped (endpoints()).  parser, search, beam_size, frame_topk as
         stream()'s; only 16 kHz audio.  context (search="prefix_beam" only): hotword biasing, open(b, context=i) picks the session's graph.
-        lm (search="prefix_beam" only, not with a context): one n-gram LM for all slots; a reopened slot restarts on its start state."""
+        lm (search="prefix_beam" only, not with a context): one n-gram LM for all slots; a reopened slot restarts on its start state.
+        timed=True (search="greedy" only): tokens(b) gives slot b's characters with frames, times and confidence as the audio arrives;
+        confidence picks the measure reported as "confidence".  A reopened slot starts an empty list."""
         from ..sessions import Sessions
         return Sessions(self, slots, parser=parser, search=search, beam_size=beam_size, frame_topk=frame_topk, endpoint=endpoint, source_rate=source_rate,
-                        context=context, lm=lm)
+                        context=context, lm=lm, timed=timed, confidence=confidence)
 
     def forward(self, input):
         """transformer_official.py:68-81 (inference-style forward; no gradients).  A batch without a transcript (only wave / wave_len)
@@ -503,13 +509,20 @@ class _SpeechTransformer(BaseModel):
         from ..data_handler.processor import HOP
         return int(getattr(self.config, "lfr_n", 3) or 3) * HOP / float(getattr(self.config, "sample_rate", 16000) or 16000)
 
-    def ctc_align(self, input, labels=None):
+    def ctc_align(self, input, labels=None, confidence=None):
         """CTC forced alignment (Viterbi over the CTC head, asr_ctc_align) of a batch.
         labels=None aligns the batch's own transcripts (tgt_for_input); otherwise one list of token ids per utterance.
         Returns per utterance {"score": log-probability of the best path (-inf when the labels do not fit the frames),
         "tokens": [{"id", "token", "start_frame", "end_frame", "start_s", "end_s", "logp"}]}, where frames count encoder frames,
         start_s = start_frame * d and end_s = (end_frame + 1) * d with d = frame_seconds(), and logp is the sum of the token's
-        log-probabilities over its frames.  Tokens of an utterance that cannot be aligned carry None for the frames, times and logp."""
+        log-probabilities over its frames.  Tokens of an utterance that cannot be aligned carry None for the frames, times and logp.
+        confidence (None, True = "post_max", or one of confidence.MEASURES): every token gains "confidence" (that measure over its
+        frames) and "measures" (all five), the utterance "confidence" (the mean over its tokens, None without one) - one
+        asr_ctc_frame_stats and one asr_ctc_token_conf launch behind the alignment's."""
+        from ..confidence import measure
+        confidence = measure(confidence)
+        if confidence is not None and not self.use_ctc:
+            raise ValueError("confidence comes from the CTC head, and this model has none (config.ctc_weight = 0)")
         if not self.use_ctc:
             raise RuntimeError("this model has no CTC head (config.ctc_weight = 0)")
         if labels is None:
@@ -518,7 +531,7 @@ class _SpeechTransformer(BaseModel):
             prep = K.dec_preprocess(input.tgt_for_input.contiguous(), SOS_ID, EOS_ID)
             lab, lens = prep[2].cpu(), prep[4].cpu().tolist()
             labels = [lab[b, : lens[b]].tolist() for b in range(lab.shape[0])]
-        return self._align_lists(self._ctc_logits(input), input.wave_len, labels)
+        return self._align_lists(self._ctc_logits(input), input.wave_len, labels, confidence=confidence)
 
     def _ctc_logits(self, input):
         eng = self._ensure_engine(input.wave.device)
@@ -529,8 +542,9 @@ class _SpeechTransformer(BaseModel):
         finally:
             eng.training = was_training
 
-    def _align_lists(self, logits, wave_len, labels, alignable=None):
-        """One asr_ctc_align launch for a batch of id lists; entries with alignable[b] False are not aligned (times None)."""
+    def _align_lists(self, logits, wave_len, labels, alignable=None, confidence=None):
+        """One asr_ctc_align launch for a batch of id lists; entries with alignable[b] False are not aligned (times None).
+        confidence (a measure's name): two more launches, asr_ctc_frame_stats and asr_ctc_token_conf, over the same logits and spans."""
         B, T, V = logits.shape
         if len(labels) != B:
             raise ValueError(f"{len(labels)} label sequences for a batch of {B}")
@@ -547,8 +561,13 @@ class _SpeechTransformer(BaseModel):
                 lab[b, : len(l)] = torch.tensor(l, dtype=torch.int32)
         dev = logits.device
         lab_len = torch.tensor([len(l) for l in use], dtype=torch.int32)
-        _, spans, tlp, score = K.ctc_align(logits, wave_len.to(torch.int32).contiguous(), lab.to(dev), lab_len.to(dev), blank=PAD_ID,
-                                           ws=self._engine.ws)
+        in_len, lab, lab_len = wave_len.to(torch.int32).contiguous(), lab.to(dev), lab_len.to(dev)
+        _, spans, tlp, score = K.ctc_align(logits, in_len, lab, lab_len, blank=PAD_ID, ws=self._engine.ws)
+        conf = None
+        if confidence is not None:
+            from ..confidence import measures_dict, utterance
+            _, _, _, lse, ent = K.ctc_frame_stats(logits, in_len, PAD_ID)
+            conf = K.ctc_token_conf(logits, lab, lab_len, spans, lse, ent).cpu().tolist()
         spans, tlp, score = spans.cpu().tolist(), tlp.cpu().tolist(), score.cpu().tolist()
         d = self.frame_seconds()
         id2tok = self.vocab._id2token
@@ -561,10 +580,15 @@ class _SpeechTransformer(BaseModel):
                 toks.append({"id": x, "token": id2tok[x] if 0 <= x < len(id2tok) else None, "start_frame": st, "end_frame": en,
                              "start_s": st * d if timed else None, "end_s": (en + 1) * d if timed else None,
                              "logp": tlp[b][i] if timed else None})
+                if conf is not None:
+                    m = measures_dict(conf[b][i]) if timed else None
+                    toks[-1]["measures"], toks[-1]["confidence"] = m, (m[confidence] if m else None)
             out.append({"score": score[b] if ok[b] else None, "tokens": toks})
+            if conf is not None:
+                out[-1]["confidence"] = utterance(t["confidence"] for t in toks)
         return out
 
-    def transcribe(self, input, beam_size=5, ctc_weight=None, timestamps=True, joint="rescore", context=None, context_ids=None, lm=None):
+    def transcribe(self, input, beam_size=5, ctc_weight=None, timestamps=True, joint="rescore", context=None, context_ids=None, lm=None, confidence=None):
         """Audio in, text out, for a batch that needs only wave / wave_len.  The search follows the model's heads: joint model =
         beam_search(ctc_weight = config.ctc_weight unless given), CTC-only model = ctc_prefix_beam_search, attention-only model =
         beam_search (no timestamps: they come from the CTC head).  Returns per utterance {"text", "ids", "score", "tokens"}: ids of
@@ -575,7 +599,15 @@ class _SpeechTransformer(BaseModel):
         (beam_search(joint=...)); "one_pass" and "ctc_rescore" need both heads.
         context / context_ids: hotword biasing of the CTC prefix beam search (a CTC-only model, or joint="ctc_rescore"; any other
         search raises ValueError); the result dicts gain "bias".
-        lm: n-gram LM shallow fusion in the CTC prefix beam search, under the same rule; the result dicts gain "lm_score"."""
+        lm: n-gram LM shallow fusion in the CTC prefix beam search, under the same rule; the result dicts gain "lm_score".
+        confidence (None, True = "post_max", or one of confidence.MEASURES; needs timestamps and the CTC head, ValueError otherwise):
+        every token gains "confidence" and "measures", the result "confidence" (ctc_align's); tokens without times carry None."""
+        from ..confidence import measure
+        confidence = measure(confidence)
+        if confidence is not None and not timestamps:
+            raise ValueError("confidence needs timestamps=True: a token's confidence is taken over the frames of its alignment")
+        if confidence is not None and not self.use_ctc:
+            raise ValueError("confidence comes from the CTC head, and this model has none (config.ctc_weight = 0)")
         if joint not in ("rescore", "one_pass", "ctc_rescore"):
             raise ValueError(f"joint must be 'rescore', 'one_pass' or 'ctc_rescore' (got {joint!r})")
         if joint in ("one_pass", "ctc_rescore") and not (self.use_decoder and self.use_ctc):
@@ -602,9 +634,9 @@ class _SpeechTransformer(BaseModel):
             ids.append(seq)
             scores.append(float(h[0]["score"]))
         return self._hyp_dicts(ids, scores, timestamps, lambda: self._ctc_logits(input), input.wave_len,
-                               biases if context is not None or lm is not None else None, bias_key)
+                               biases if context is not None or lm is not None else None, bias_key, confidence=confidence)
 
-    def _hyp_dicts(self, ids, scores, timestamps, ctc_logits, wave_len, biases=None, bias_key="bias"):
+    def _hyp_dicts(self, ids, scores, timestamps, ctc_logits, wave_len, biases=None, bias_key="bias", confidence=None):
         """transcribe's result dicts for the best ids / score of each utterance; ctc_logits() -> (B, T, V) is called for timestamps only.
         biases (hotword-biased searches, or searches with an n-gram LM): the "bias" (bias_key="lm_score": the "lm_score") of each result."""
         id2tok = self.vocab._id2token
@@ -616,9 +648,11 @@ class _SpeechTransformer(BaseModel):
         if timestamps:
             V = self.V
             ok = [len(seq) <= 255 and all(0 <= x < V and x != PAD_ID for x in seq) for seq in ids]
-            al = self._align_lists(ctc_logits(), wave_len, ids, alignable=ok)
+            al = self._align_lists(ctc_logits(), wave_len, ids, alignable=ok, confidence=confidence)
             for o, a in zip(out, al):
                 o["tokens"] = a["tokens"]
+                if confidence is not None:
+                    o["confidence"] = a["confidence"]
         return out
 
     def _ctc_cer(self, logits, wave_len, labels32, lab_len):

@@ -174,6 +174,9 @@ SIGNATURES = {
     "asr_slot_rows_slide": (I, [P, P, P, P, I, I, I, I, I, P]),
     "asr_ctc_frame_best_blank": (I, [P, P, P, P, I, I, I, I, I, I, P]),
     "asr_session_ctc_step": (I, [P, P, P, P, P, P, I, I, I, F, P]),
+    "asr_ctc_frame_stats": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "asr_ctc_token_conf": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "asr_session_ctc_step_tokens": (I, [P, P, P, P, P, P, P, P, P, I, I, I, F, P]),
 }
 
 

@@ -712,6 +712,62 @@ def session_ctc_step(path, blank_lp, n_valid, reset, state, C, silence_lp, blank
     return out
 
 
+def ctc_frame_stats(logits, in_len=None, blank=0):
+    """logits (B, T, V) -> (path (B, T) int32 as ctc_frame_argmax, best_lp, blank_lp, lse, ent: (B, T) f32) in one pass per frame
+    (asr_ctc_frame_stats): log p of the best class and of the blank, the log-sum-exp, and the entropy confidence 1 - H / ln V."""
+    B, T, V = logits.shape
+    ld = _frame_rows(logits)
+    _chk_i32(in_len)
+    assert in_len is None or in_len.numel() == B
+    path = torch.empty(B, T, dtype=torch.int32, device=logits.device)
+    best_lp, blank_lp, lse, ent = torch.empty(4, B, T, dtype=torch.float32, device=logits.device).unbind(0)
+    check(lib.asr_ctc_frame_stats(_p(logits), _p(in_len), _p(path), _p(best_lp), _p(blank_lp), _p(lse), _p(ent), B, T, V, ld, int(blank), _dt(logits),
+                                  _stream()), "asr_ctc_frame_stats")
+    return path, best_lp, blank_lp, lse, ent
+
+
+def ctc_token_conf(logits, labels, lab_len, spans, lse, ent):
+    """The five confidence measures of every aligned token (asr_ctc_token_conf): logits (B, T, V), labels (B, Lmax) / lab_len (B,) /
+    spans (B, Lmax, 2) as ctc_align takes and returns them, lse / ent (B, T) from ctc_frame_stats over the same logits.
+    Returns (B, Lmax, 5) f32 = {post_max, post_min, post_mean, ent_mean, ent_min}: 0 past lab_len, NaN for a token without a span."""
+    B, T, V = logits.shape
+    ld = _frame_rows(logits)
+    _chk_i32(labels, lab_len, spans)
+    _chk_f32(lse, ent)
+    Lmax = labels.shape[1]
+    assert labels.shape == (B, Lmax) and lab_len.numel() == B and spans.shape == (B, Lmax, 2) and lse.shape == (B, T) and ent.shape == (B, T)
+    assert lse.is_contiguous() and ent.is_contiguous()
+    dev = logits.device
+    if Lmax == 0:      # the entry point takes Lmax >= 1, as asr_ctc_align
+        labels, spans = torch.zeros(B, 1, dtype=torch.int32, device=dev), torch.full((B, 1, 2), -1, dtype=torch.int32, device=dev)
+    labels, spans = labels.contiguous(), spans.contiguous()
+    La = labels.shape[1]
+    out = torch.empty(B, La, 5, dtype=torch.float32, device=dev)
+    check(lib.asr_ctc_token_conf(_p(logits), _p(labels), _p(lab_len), _p(spans), _p(lse), _p(ent), _p(out), B, T, V, ld, La, _dt(logits), _stream()),
+          "asr_ctc_token_conf")
+    return out[:, :Lmax]
+
+
+STEP_TOKENS_REC = 8      # words of a run's record in session_ctc_step_tokens' buffer: id, first frame, last frame, the five measures
+
+
+def session_ctc_step_tokens(path, blank_lp, best_lp, ent, n_valid, reset, state, run, C, silence_lp, blank=0):
+    """session_ctc_step with the greedy path's runs (asr_session_ctc_step_tokens): best_lp, ent (slots, C) f32 from ctc_frame_stats,
+    run (slots, 8) int32 = the open run between ticks (updated in place, as state).  Returns out (slots, 13 + 9 C) int32 on the
+    device: session_ctc_step's 4 + C words, the count of runs closed, C records of 8 words, the open run's record (include/asr_hip.h)."""
+    slots = state.shape[0]
+    _chk_i32(path, n_valid, reset, state, run)
+    _chk_f32(blank_lp, best_lp, ent)
+    assert state.shape == (slots, 4) and run.shape == (slots, STEP_TOKENS_REC) and state.is_contiguous() and run.is_contiguous()
+    assert path.numel() == slots * C and blank_lp.numel() == slots * C and best_lp.numel() == slots * C and ent.numel() == slots * C
+    assert path.is_contiguous() and blank_lp.is_contiguous() and best_lp.is_contiguous() and ent.is_contiguous()
+    assert n_valid.numel() == slots and reset.numel() == slots
+    out = torch.empty(slots, 13 + 9 * C, dtype=torch.int32, device=state.device)
+    check(lib.asr_session_ctc_step_tokens(_p(path), _p(blank_lp), _p(best_lp), _p(ent), _p(n_valid), _p(reset), _p(state), _p(run), _p(out), slots, int(C),
+                                          int(blank), float(silence_lp), _stream()), "asr_session_ctc_step_tokens")
+    return out
+
+
 def beam_step(top_vals, top_ids, score, alive, last_tok, parent, rec_tok, rec_par, rec_end, rec_score, maxlen, alive_total, B, beam, step, eos):
     _chk_f32(top_vals, score, rec_score)
     _chk_i32(top_ids, alive, last_tok, parent, rec_tok, rec_par, rec_end, maxlen, alive_total)

@@ -19,6 +19,10 @@ Endpointing (endpoint=dict(...)): WeNet's CTC endpoint rules, evaluated per slot
 (must_have_decoded, min_trailing_silence_ms, min_length_ms) fires when all three hold; endpoints() reports the first that does.
 Endpointing only reports: the caller closes the slot (final), finishes it and opens it again for what follows.
 
+timed=True (greedy sessions): the tick runs asr_ctc_frame_stats + asr_session_ctc_step_tokens instead of asr_ctc_frame_best_blank +
+asr_session_ctc_step - the same ids and counters, and per slot the runs of the best path that closed in this tick with their frames and
+confidence measures, still in one buffer and one copy; tokens(b) lists them (confidence.TokenLog).  push returns what it returns.
+
 Out of scope: input rates other than 16 kHz (StreamResampler has no per-slot reset), compaction of idle slots (every tick computes
 slots * C rows), carrying audio across an endpoint, a varying number of slots, capture into a hipGraph."""
 import math
@@ -73,7 +77,8 @@ def endpoint_rule(rules, frame_us, trailing, frames, decoded):
 
 
 class Sessions:
-    def __init__(self, model, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None):
+    def __init__(self, model, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None,
+                 timed=False, confidence="post_max"):
         C, left = model.decoding_chunk_size, model.decoding_left_chunks
         if C <= 0:
             raise ValueError("model.sessions() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
@@ -87,6 +92,13 @@ class Sessions:
         if search not in ("greedy", "prefix_beam"):
             raise ValueError(f"search must be 'greedy' or 'prefix_beam' (got {search!r})")
         self.search, self.beam_size, self.frame_topk = search, int(beam_size), int(frame_topk)
+        # timed=True (greedy sessions): every emitted token's frames, times and confidence (confidence.TokenLog, tokens(b))
+        self.timed, self.log, self.run_state = bool(timed), None, None
+        if self.timed:
+            if search != "greedy":
+                raise ValueError("timed=True needs search='greedy': the frame-wise best path is the alignment there; times for the prefix beam's stable prefix are not supported")
+            from .confidence import TokenLog
+            self.log = TokenLog(self.S, confidence, model.vocab._id2token, model.frame_seconds())
         if search == "prefix_beam":
             k = max(1, min(self.frame_topk, model.V))
             if self.beam_size < 1 or self.beam_size > 16 or self.beam_size * (k + 1) > 64:
@@ -150,6 +162,8 @@ class Sessions:
             self.graph[b] = graph
         self.state[b], self.frames[b], self.clen[b], self.fresh[b] = OPEN, 0, 0, True
         self.trailing[b], self.decoded[b], self.stable[b] = 0, False, 0
+        if self.log is not None:
+            self.log.reset(b)
         if self.frontend is not None:
             self.frontend.reset(b)
 
@@ -240,7 +254,17 @@ class Sessions:
         for b in range(S):
             if fin[b] and self.state[b] == OPEN:
                 self.state[b] = ENDED
+                if self.log is not None:      # the input has ended: the run still open is a token like the others
+                    self.log.close(b)
         return out
+
+    def tokens(self, b):
+        """timed=True: slot b's tokens so far, each {"id", "token", "start_frame", "end_frame", "start_s", "end_s", "measures",
+        "confidence", "final"} (times as ctc_align's).  The run still open is the last entry, final=False: its end and measures may
+        still move, the others are settled.  The list of a finished slot stays until the slot is opened again."""
+        if self.log is None:
+            raise ValueError("tokens() needs model.sessions(..., timed=True)")
+        return self.log.tokens(self._slot(b))
 
     def _tick(self, eng, feats, nv, out):
         S, C, dev = self.S, self.C, feats.device
@@ -315,9 +339,18 @@ class Sessions:
                         if nv[b] > 0:
                             out[b] = tok[b, 0, self.stable[b]:int(stable[b])].tolist()
                             self.stable[b] = int(stable[b])
+                elif self.timed:
+                    if self.run_state is None:
+                        self.run_state = torch.zeros(S, K.STEP_TOKENS_REC, dtype=torch.int32, device=dev)
+                    path, best_lp, blank_lp, _, ent = K.ctc_frame_stats(logits.view(S, C, -1), nv_dev, BLANK)
+                    buf = K.session_ctc_step_tokens(path, blank_lp, best_lp, ent, nv_dev, pd[P_RESET], self.ctc_state, self.run_state, C, self.silence_lp,
+                                                    BLANK).cpu()
+                    step = buf[:, :4 + C].tolist()
+                    self.log.ingest(buf, C, [b for b in range(S) if nv[b] > 0 or b in reset_slots])
                 else:
                     path, blank_lp = K.ctc_frame_best_blank(logits.view(S, C, -1), nv_dev, BLANK)
                     step = K.session_ctc_step(path, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK).cpu().tolist()
+                if self.search != "prefix_beam":
                     for b in range(S):
                         if nv[b] > 0:
                             out[b] = step[b][4:4 + step[b][0]]
@@ -438,6 +471,10 @@ class Sessions:
             if self.state[b] == FREE:
                 raise ValueError(f"finish: slot {b} is free")
         model, timestamps = self.model, kw.get("timestamps", True)
+        from .confidence import measure
+        which = measure(kw.get("confidence"))
+        if which is not None and not timestamps:
+            raise ValueError("confidence needs timestamps=True: a token's confidence is taken over the frames of its alignment")
         rescore = kw.get("joint") == "ctc_rescore"
         if rescore:
             self._need_beam("finish(joint='ctc_rescore')")
@@ -448,6 +485,9 @@ class Sessions:
         if self.lm is not None:
             for r in res:
                 r["lm_score"] = 0.0
+        if which is not None:
+            for r in res:
+                r["confidence"] = None
         live = [i for i, b in enumerate(slots) if self.frames[b] > 0]
         if live:
             rows = [slots[i] for i in live]
@@ -468,7 +508,7 @@ class Sessions:
                 def ctc_logits():
                     with torch.no_grad():
                         return self.eng.ctc_lo.fwd(enc.reshape(n * T, -1).contiguous()).view(n, T, -1)
-                got = model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens, biases, "lm_score" if self.lm is not None else "bias")
+                got = model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens, biases, "lm_score" if self.lm is not None else "bias", confidence=which)
             else:
                 # under given_encoder_output the searches take the batch's features for their (B, T) only: none are kept
                 wave = torch.zeros(n, T, 1, dtype=enc.dtype, device=enc.device)

@@ -16,6 +16,10 @@ search="prefix_beam" (the first pass of the U2 recipe): instead of the argmax, e
 (asr_ctc_frame_topk) to the resumable CTC prefix beam search (asr_ctc_prefix_beam_chunk), whose beam lives on the device between
 pushes.  push returns the tokens by which the STABLE prefix grew - the prefix all beam entries share, which no later chunk can retract;
 partial() / nbest() give the revisable hypotheses, finish(joint="ctc_rescore") re-ranks the n-best with the decoder (second pass).
+
+timed=True (greedy only): the frame-wise best path is the alignment, so every emitted token's first and last frame and its confidence
+are known when its run of frames closes; the push then runs the two kernels of a timed sessions tick (asr_ctc_frame_stats,
+asr_session_ctc_step_tokens) and tokens() lists the tokens so far, the run still open last (confidence.TokenLog).
 """
 import torch
 
@@ -23,10 +27,12 @@ from . import kernels as K
 from .Utils import Pack
 
 BLANK = 0      # the CTC blank (= PAD_ID of the model)
+SILENCE_LP = -0.2231435513142097      # log 0.8, the sessions' default blank threshold: a timed stream's step counts silence, nothing reads it
 
 
 class StreamingEncoder:
-    def __init__(self, model, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None, lm=None):
+    def __init__(self, model, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None, lm=None,
+                 timed=False, confidence="post_max"):
         C, left = model.decoding_chunk_size, model.decoding_left_chunks
         if C <= 0:
             raise ValueError("model.stream() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
@@ -45,6 +51,16 @@ class StreamingEncoder:
         if search not in ("greedy", "prefix_beam"):
             raise ValueError(f"search must be 'greedy' or 'prefix_beam' (got {search!r})")
         self.search, self.beam_size, self.frame_topk = search, int(beam_size), int(frame_topk)
+        # timed=True (greedy streams): every emitted token's frames, times and confidence (confidence.TokenLog, tokens()), from the two
+        # kernels of a timed sessions tick - asr_ctc_frame_stats and asr_session_ctc_step_tokens, the reset flag set on the first push
+        self.timed, self.log, self.ctc_state, self.run_state = bool(timed), None, None, None
+        if self.timed:
+            if search != "greedy":
+                raise ValueError("timed=True needs search='greedy': the frame-wise best path is the alignment there; times for the prefix beam's stable prefix are not supported")
+            if not model.use_ctc:
+                raise ValueError("timed=True needs a model with the CTC head (config.ctc_weight > 0): times and confidence come from it")
+            from .confidence import TokenLog
+            self.log = TokenLog(self.B, confidence, model.vocab._id2token, model.frame_seconds())
         if search == "prefix_beam":
             if not model.use_ctc:
                 raise RuntimeError("search='prefix_beam' needs a model with the CTC head (config.ctc_weight > 0)")
@@ -175,6 +191,20 @@ class StreamingEncoder:
                     for b in range(B):      # every entry shares the stable prefix, so rank 0 spells it whatever the order by score
                         out[b] = tok[b, 0, self.stable[b]:int(stable[b])].tolist()
                         self.stable[b] = int(stable[b])
+                elif self.timed:
+                    first = self.ctc_state is None
+                    if first:
+                        self.ctc_state = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+                        self.run_state = torch.zeros(B, K.STEP_TOKENS_REC, dtype=torch.int32, device=dev)
+                    reset = torch.full((B,), int(first), dtype=torch.int32, device=dev)
+                    path, best_lp, blank_lp, _, ent = K.ctc_frame_stats(eng.ctc_lo.fwd(h).view(B, C, -1), nv_dev, BLANK)
+                    buf = K.session_ctc_step_tokens(path, blank_lp, best_lp, ent, nv_dev, reset, self.ctc_state, self.run_state, C, SILENCE_LP, BLANK).cpu()
+                    step = buf[:, :4 + C].tolist()
+                    self.log.ingest(buf, C, [b for b in range(B) if nv[b] > 0])
+                    for b in range(B):
+                        out[b] = step[b][4:4 + step[b][0]]
+                        if nv[b] < C:      # the utterance ends here: the run still open is a token like the others
+                            self.log.close(b)
                 elif model.use_ctc:
                     logits = eng.ctc_lo.fwd(h).view(B, C, -1)
                     path = K.ctc_frame_argmax(logits, nv_dev, BLANK).cpu().tolist()
@@ -195,6 +225,14 @@ class StreamingEncoder:
                 self.ended[b] = True
         self.offset += C
         return out
+
+    def tokens(self):
+        """timed=True: per utterance its tokens so far, each {"id", "token", "start_frame", "end_frame", "start_s", "end_s", "measures",
+        "confidence", "final"} (times as ctc_align's).  The run still open is the last entry, final=False: its end and measures may
+        still move, the others are settled."""
+        if self.log is None:
+            raise ValueError("tokens() needs model.stream(..., timed=True)")
+        return [self.log.tokens(b) for b in range(self.B)]
 
     def _ensure_frontend(self):
         if self.parser is None:
@@ -274,7 +312,7 @@ class StreamingEncoder:
                 o["lm_score"] = h[0]["lm_score"] if h else 0.0
         return out
 
-    def _live_only(self, timestamps, search):
+    def _live_only(self, timestamps, search, confidence=None):
         """finish() over the utterances that have a frame: search(rows) -> their result dicts, rows = their indices in the batch (every
         one of them in the common case).  An utterance without a frame gets the empty transcript and reaches no search kernel."""
         live = [b for b in range(self.B) if self.valid[b] > 0]
@@ -286,11 +324,14 @@ class StreamingEncoder:
         if self.lm is not None:
             for o in out:
                 o["lm_score"] = 0.0
+        if confidence is not None:
+            for o in out:
+                o["confidence"] = None
         for b, r in zip(live, res):
             out[b] = r
         return out
 
-    def _finish_rescore(self, ctc_weight=None, timestamps=True):
+    def _finish_rescore(self, ctc_weight=None, timestamps=True, confidence=None):
         """The second pass: the decoder re-ranks the streamed search's n-best (decode.attention_rescore) against the streamed encoder
         output; a CTC-only model keeps the CTC best.  transcribe's result dicts, timestamps from the CTC head over the same output."""
         from . import decode
@@ -314,16 +355,20 @@ class StreamingEncoder:
             def ctc_logits():
                 with torch.no_grad():
                     return self.eng.ctc_lo.fwd(enc.reshape(B * T, -1).contiguous()).view(B, T, -1)
-            return model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens, biases, "lm_score" if self.lm is not None else "bias")
-        return self._live_only(timestamps, search)
+            return model._hyp_dicts(ids, scores, timestamps, ctc_logits, lens, biases, "lm_score" if self.lm is not None else "bias", confidence=confidence)
+        return self._live_only(timestamps, search, confidence)
 
     def finish(self, beam_size=5, **kw):
         """model.transcribe(...) of the pushed features under the same decoding chunk mask, computed from the streamed encoder output
-        (the encoder does not run again).  kw: transcribe's other arguments (ctc_weight, timestamps, joint).
+        (the encoder does not run again).  kw: transcribe's other arguments (ctc_weight, timestamps, joint, confidence).
         joint="ctc_rescore" (a stream opened with search="prefix_beam"): no new search - the streamed prefix beam search's n-best is
         re-ranked by the decoder (_finish_rescore); beam_size does not apply, the list is the stream's."""
+        from .confidence import measure
+        which = measure(kw.get("confidence"))
+        if which is not None and not kw.get("timestamps", True):
+            raise ValueError("confidence needs timestamps=True: a token's confidence is taken over the frames of its alignment")
         if kw.get("joint") == "ctc_rescore":
-            return self._finish_rescore(ctc_weight=kw.get("ctc_weight"), timestamps=kw.get("timestamps", True))
+            return self._finish_rescore(ctc_weight=kw.get("ctc_weight"), timestamps=kw.get("timestamps", True), confidence=which)
         all_enc, all_lens = self.encoder_output()
         all_wave = torch.cat(self.feats, dim=1)
 
@@ -336,4 +381,4 @@ class StreamingEncoder:
                 ctx = dict(lm=self.lm)
             with self.model.given_encoder_output(enc):
                 return self.model.transcribe(Pack(wave=wave, wave_len=lens), beam_size=beam_size, **kw, **ctx)
-        return self._live_only(kw.get("timestamps", True), search)
+        return self._live_only(kw.get("timestamps", True), search, which)

@@ -984,6 +984,43 @@ int asr_ctc_frame_best_blank(const void* logits, const int32_t* in_len, int32_t*
 int asr_session_ctc_step(const int32_t* path, const float* blank_lp, const int32_t* n_valid, const int32_t* reset, int32_t* state,
                          int32_t* out, int slots, int C, int blank, float silence_lp, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Token confidence and streamed token times from the CTC posteriors (additive to ABI 10; csrc/confidence.hip,
+ * asr_chinese_e2e_amd/confidence.py; the definitions in float64: tests/confidence_ref.py).  p = softmax of a frame's logits over V >= 2 classes.
+ *
+ * asr_ctc_frame_stats: one wave per frame of logits (B, T, V) f32 / bf16 (row stride ld).  path = the best class, the first maximum
+ *   winning, bit for bit asr_ctc_frame_argmax's; blank_lp = log p[blank], bit for bit asr_ctc_frame_best_blank's (same passes, same
+ *   order of the sum of exponentials); lse = m + logf(s) with m the maximum and s = sum e^(x - m); best_lp = m - lse = log p[path];
+ *   ent = 1 - H / ln V clamped to [0, 1], H = ln s - u / s with u = sum (x - m) e^(x - m), a class whose exponential is 0 (a -inf
+ *   logit, an underflow) adding exactly 0 - a one-hot row gives 1, a constant row 0, no row with a finite maximum gives NaN.  All
+ *   outputs (B, T); frames t >= in_len[b] (in_len may be NULL) get path = blank and 0 in the four float outputs.
+ * asr_ctc_token_conf: one wave per utterance, a lane per token.  labels (B, Lmax), lab_len (B), spans (B, Lmax, 2) as asr_ctc_align
+ *   takes and writes them, lse / ent (B, T) from asr_ctc_frame_stats over the same logits.  For token l < lab_len[b] with class y on
+ *   frames s..e (n = e - s + 1), lp_t = logits[b, t, y] - lse[b, t]: out (B, Lmax, 5) f32 = {post_max = exp(max lp_t), post_min =
+ *   exp(min lp_t), post_mean = exp(sum lp_t / n), ent_mean = sum ent_t / n, ent_min = min ent_t}.  The sums are fp32, start at 0.f
+ *   and take the frames one at a time in ascending t.  Entries l >= lab_len[b] hold 0; a token whose span is -1 (asr_ctc_align found
+ *   no alignment), or is no span of [0, T), holds NaN in all five.  1 <= Lmax <= 255.
+ * asr_session_ctc_step_tokens: asr_session_ctc_step with path required, plus the greedy path's runs.  best_lp, ent (slots, C) from
+ *   asr_ctc_frame_stats.  A run is a maximal sequence of frames of one non-blank class (it continues across ticks); the token
+ *   asr_session_ctc_step emits when a run opens gets its record when the run closes, i.e. at the first frame of another class.
+ *   run (slots, 8) int32, the open run between ticks = {class (blank: none), first frame, frames, then as float bits: sum, max, min of
+ *   lp = best_lp, sum, min of ent}, the sums in the order above; reset[b] != 0 clears it with state; n_valid[b] == 0 without reset
+ *   leaves both untouched.  out (slots, 13 + 9 C) int32, one copy to the host:
+ *     [0, 4 + C)           asr_session_ctc_step's out, the same values
+ *     [4 + C]              runs closed in this tick (<= C)
+ *     [5 + C, 5 + 9 C)     a record of 8 words per closed run, in order, 0 behind the last: {id, first frame, last frame, post_max,
+ *                          post_min, post_mean, ent_mean, ent_min} (floats as their bits), frames counted from the session's frame 0
+ *     [5 + 9 C, 13 + 9 C)  the record of the run still open after this tick (id -1 and zeros: none); the host closes it when the
+ *                          session's input ends
+ */
+int asr_ctc_frame_stats(const void* logits, const int32_t* in_len, int32_t* path, float* best_lp, float* blank_lp, float* lse,
+                        float* ent, int B, int T, int V, int ld, int blank, int dtype, void* stream);
+int asr_ctc_token_conf(const void* logits, const int32_t* labels, const int32_t* lab_len, const int32_t* spans, const float* lse,
+                       const float* ent, float* out, int B, int T, int V, int ld, int Lmax, int dtype, void* stream);
+int asr_session_ctc_step_tokens(const int32_t* path, const float* blank_lp, const float* best_lp, const float* ent,
+                                const int32_t* n_valid, const int32_t* reset, int32_t* state, int32_t* run, int32_t* out, int slots,
+                                int C, int blank, float silence_lp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

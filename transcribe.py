@@ -51,6 +51,12 @@ trained with rebuild it.  Inference flags:
                  final lines gain "lm_score".  The same searches as --context admits; not together with --context
   --lm_weight    the LM weight (default 0.3)
   --lm_ins       the bonus per token of a hypothesis (default 0.0)
+  --confidence   post_max (WeNet's measure), post_min, post_mean, ent_mean or ent_min: every token of the final lines gains "confidence"
+                 (that measure over the token's frames) and "measures" (all five), the line "confidence" (the mean over its tokens);
+                 from the CTC posteriors, so it needs the CTC head and timestamps
+  --timed        1 (with --stream=1, --sessions=N included; greedy search only): the per-chunk lines gain "tokens", the characters so
+                 far with frames, times and confidence (the measure of --confidence, default post_max); the last one may still be
+                 open ("final": false)
 Audio goes through load_wav -> AudioParser.parse_batch on the device -> model.transcribe; one JSON line per file is printed:
 {"file", "duration_s", "text", "ids", "score", "tokens": [{"id", "token", "start_frame", "end_frame", "start_s", "end_s", "logp"}]}.
 """
@@ -72,7 +78,7 @@ from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
 from asr_chinese_e2e_amd.data_handler import resample as resample_mod  # noqa: E402
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint", "context", "context_score", "lm", "lm_weight", "lm_ins")
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint", "context", "context_score", "lm", "lm_weight", "lm_ins", "confidence", "timed")
 
 
 def _finite(x):
@@ -105,11 +111,19 @@ def audio_files(flags):
     raise SystemExit("transcribe.py: give --wavs=a.wav,b.wav or --manifest=<collector json>")
 
 
-def _chunk_lines(st, files, nv, ids, text, chunk, id2tok):
+def _shifted(tokens, shift_s):
+    """A timed stream's tokens with their times moved to frame centres, as the final lines' are."""
+    for t in tokens:
+        t["start_s"], t["end_s"] = t["start_s"] + shift_s, t["end_s"] + shift_s
+    return tokens
+
+
+def _chunk_lines(st, files, nv, ids, text, chunk, id2tok, shift_s=0.0):
     """The per-chunk JSON lines of the files that got frames: greedy = the text so far; prefix beam = the best hypothesis now and its
     stable part."""
     part = st.partial() if st.search == "prefix_beam" else None
     spell = lambda seq: "".join(id2tok[t] for t in seq if part is None or t not in (0, 2, 3))      # noqa: E731  (beam mode: as the final text, without pad / sos / eos)
+    timed = st.tokens() if st.timed else None
     for b in range(len(files)):
         if nv[b] <= 0:
             continue
@@ -117,10 +131,12 @@ def _chunk_lines(st, files, nv, ids, text, chunk, id2tok):
         line = {"file": files[b], "chunk": chunk, "partial": text[b]}
         if part is not None:
             line.update(partial=spell(part[b]["ids"]), stable=text[b])
+        if timed is not None:
+            line["tokens"] = _shifted(timed[b], shift_s)
         print(json.dumps(line, ensure_ascii=False), flush=True)
 
 
-def stream_batch(model, files, feats, flen, id2tok, stream_kw=None, **search):
+def stream_batch(model, files, feats, flen, id2tok, stream_kw=None, shift_s=0.0, **search):
     """model.stream over a batch of feature sequences in chunks of the decoding chunk size: prints the partial text of every
     file after every chunk, returns what model.transcribe returns (finish()).  stream_kw: model.stream's search arguments."""
     B, T, F = feats.shape
@@ -133,11 +149,11 @@ def stream_batch(model, files, feats, flen, id2tok, stream_kw=None, **search):
         if x.shape[1] < C:
             x = torch.nn.functional.pad(x, (0, 0, 0, C - x.shape[1]))
         nv = [max(0, min(C, n - c0)) for n in lens]
-        _chunk_lines(st, files, nv, st.push(x.contiguous(), nv), text, i, id2tok)
+        _chunk_lines(st, files, nv, st.push(x.contiguous(), nv), text, i, id2tok, shift_s)
     return st.finish(**search)
 
 
-def stream_audio_batch(model, parser, files, wav, wav_len, id2tok, block, source_rate=None, stream_kw=None, **search):
+def stream_audio_batch(model, parser, files, wav, wav_len, id2tok, block, source_rate=None, stream_kw=None, shift_s=0.0, **search):
     """model.stream fed with the samples themselves, `block` at a time (wav (B, S) f32 on the host, wav_len list): the same lines as
     stream_batch prints, the same result.  source_rate: the rate of wav when it is not 16 kHz (converted as it streams)."""
     B, S = wav.shape
@@ -147,7 +163,7 @@ def stream_audio_batch(model, parser, files, wav, wav_len, id2tok, block, source
         n = [max(0, min(block, l - s0)) for l in wav_len]
         final = [l <= s0 + block for l in wav_len]
         for nv, ids in st.push_audio_chunks(wav[:, s0:s0 + block].contiguous(), n, final):
-            _chunk_lines(st, files, nv, ids, text, chunk, id2tok)
+            _chunk_lines(st, files, nv, ids, text, chunk, id2tok, shift_s)
             chunk += 1
     return st.finish(**search)
 
@@ -165,6 +181,8 @@ def final_line(path, n_samples, sr, r, shift_s, sample_rate):
         line["bias"] = r["bias"]
     if "lm_score" in r:
         line["lm_score"] = r["lm_score"]
+    if "confidence" in r:
+        line["confidence"] = r["confidence"]
     if sr != sample_rate:
         line["source_rate"] = sr
     return line
@@ -206,6 +224,8 @@ def stream_sessions(model, parser, files, n_slots, id2tok, block, shift_s, sampl
                     line.update(partial=spell(ss.partial(b)["ids"]), stable=f["text"])
                 if endpoint:
                     line["endpoint"] = ends[b]
+                if ss.timed:
+                    line["tokens"] = _shifted(ss.tokens(b), shift_s)
                 f["chunk"] += 1
                 print(json.dumps(line, ensure_ascii=False), flush=True)
         for b, f in enumerate(slot):
@@ -251,7 +271,20 @@ def transcribe(**flags):
         raise SystemExit("transcribe.py: --stream_search=prefix_beam applies to --stream=1")
     if stream_search == "prefix_beam" and not model.use_ctc:
         raise SystemExit("transcribe.py: --stream_search=prefix_beam needs a model with the CTC head")
-    stream_kw = dict(search="prefix_beam", beam_size=beam, frame_topk=int(cli.get("frame_topk", 10))) if stream_search == "prefix_beam" else {}
+    beam_stream = stream_search == "prefix_beam"
+    stream_kw = dict(search="prefix_beam", beam_size=beam, frame_topk=int(cli.get("frame_topk", 10))) if beam_stream else {}
+    confidence = cli.get("confidence") if cli.get("confidence") not in (None, "", False, 0) else None
+    if confidence is not None:
+        from asr_chinese_e2e_amd.confidence import MEASURES
+        if str(confidence) not in MEASURES:
+            raise SystemExit(f"transcribe.py: --confidence must be one of {', '.join(MEASURES)} (got {confidence!r})")
+        confidence = str(confidence)
+        if not model.use_ctc or not timestamps:
+            raise SystemExit("transcribe.py: --confidence needs a model with the CTC head and timestamps: it is taken over the frames of the CTC alignment")
+    if bool(int(cli.get("timed", 0) or 0)):
+        if not stream or beam_stream or not model.use_ctc:
+            raise SystemExit("transcribe.py: --timed=1 applies to --stream=1 with the greedy search of a model with the CTC head")
+        stream_kw.update(timed=True, confidence=confidence or "post_max")
     context = None
     if cli.get("context") not in (None, "", False):
         from asr_chinese_e2e_amd.context import ContextGraph
@@ -296,7 +329,9 @@ def transcribe(**flags):
             raise SystemExit("transcribe.py: --sessions=N needs --stream=1 and --cmvn (the samples themselves are streamed)")
         if not model.use_ctc:
             raise SystemExit("transcribe.py: --sessions=N needs a model with the CTC head")
-        search = dict(ctc_weight=ctc_weight, timestamps=timestamps, joint="ctc_rescore") if stream_kw else dict(beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps, joint=joint)
+        search = dict(ctc_weight=ctc_weight, timestamps=timestamps, joint="ctc_rescore") if beam_stream else dict(beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps, joint=joint)
+        if confidence is not None:
+            search["confidence"] = confidence
         block = int(cli.get("stream_block_samples", 0)) or model.decoding_chunk_size * config.lfr_n * 160
         stream_sessions(model, parser, files, n_sessions, id2tok, block, shift_s, config.sample_rate, endpoint=bool(int(cli.get("endpoint", 0) or 0)),
                         stream_kw=stream_kw, **search)
@@ -332,15 +367,17 @@ def transcribe(**flags):
             search["context"] = context
         if lm is not None and not stream:
             search["lm"] = lm
-        if stream_kw:      # the streamed search's own n-best, re-ranked by the decoder
+        if beam_stream:      # the streamed search's own n-best, re-ranked by the decoder
             search = dict(ctc_weight=ctc_weight, timestamps=timestamps, joint="ctc_rescore")
+        if confidence is not None:
+            search["confidence"] = confidence
         if stream and parser.norm == "global":      # the samples stream: blocks of one chunk's worth of audio unless told otherwise
             block = int(cli.get("stream_block_samples", 0)) or model.decoding_chunk_size * config.lfr_n * 160 * (stream_rate or 16000) // 16000
-            out = stream_audio_batch(model, parser, chunk, wav, wav_len.tolist(), id2tok, block, source_rate=stream_rate, stream_kw=stream_kw, **search)
+            out = stream_audio_batch(model, parser, chunk, wav, wav_len.tolist(), id2tok, block, source_rate=stream_rate, stream_kw=stream_kw, shift_s=shift_s, **search)
         else:
             feats, flen = parser.parse_batch(wav.cuda(), wav_len.cuda())
             if stream:
-                out = stream_batch(model, chunk, feats, flen, id2tok, stream_kw=stream_kw, **search)
+                out = stream_batch(model, chunk, feats, flen, id2tok, stream_kw=stream_kw, shift_s=shift_s, **search)
             else:
                 out = model.transcribe(Pack(wave=feats, wave_len=flen), **search)
         for path, w, sr, r in zip(chunk, waves, rates, out):
