@@ -636,6 +636,16 @@ class _SpeechTransformer(BaseModel):
         return self._hyp_dicts(ids, scores, timestamps, lambda: self._ctc_logits(input), input.wave_len,
                                biases if context is not None or lm is not None else None, bias_key, confidence=confidence)
 
+    def transcribe_long(self, parser, wav, wav_len, vad=None, batch_size=16, source_rate=None, min_silence_s=0.3, min_speech_s=0.1, pad_s=0.1,
+                        max_segment_s=20.0, **transcribe_kw):
+        """Whole recordings in, text out (longform.transcribe_long): wav (B, S) f32 samples (at source_rate when given, else 16 kHz) are
+        cut at their pauses by the energy VAD (vad.EnergyVad; None: Kaldi's defaults), the segments of each recording go through
+        transcribe(**transcribe_kw) in time order, batch_size at a time, and come back on the recording's time axis: per recording
+        {"text", "ids", "duration_s", "segments": [{"start_s", "end_s", "start_sample", and transcribe's result for the segment}]}."""
+        from ..longform import transcribe_long
+        return transcribe_long(self, parser, wav, wav_len, vad=vad, batch_size=batch_size, source_rate=source_rate, min_silence_s=min_silence_s,
+                               min_speech_s=min_speech_s, pad_s=pad_s, max_segment_s=max_segment_s, **transcribe_kw)
+
     def _hyp_dicts(self, ids, scores, timestamps, ctc_logits, wave_len, biases=None, bias_key="bias", confidence=None):
         """transcribe's result dicts for the best ids / score of each utterance; ctc_logits() -> (B, T, V) is called for timestamps only.
         biases (hotword-biased searches, or searches with an n-gram LM): the "bias" (bias_key="lm_score": the "lm_score") of each result."""

@@ -27,6 +27,7 @@ RESAMPLE_TILE = 1024   # ASR_RESAMPLE_TILE: output samples per workgroup of asr_
 REVERB_TILE, REVERB_CHUNK, REVERB_MAX_TAPS = 1024, 256, 8192      # ASR_REVERB_* of include/asr_hip.h: outputs per workgroup, taps per staged pass, tap limit
 REVERB_FFT_N, REVERB_FFT_MAX_TAPS = 4096, 65536      # ASR_REVERB_FFT_*: transform points (N / 2 new samples per block), tap limit of asr_reverb_fft_fwd
 NOISE_MIX_TILE = 4096      # ASR_NOISE_MIX_TILE: samples per workgroup and energy partial of asr_noise_mix_fwd
+VAD_CTX_MAX = 1024     # ASR_VAD_CTX_MAX: the largest frames_context asr_vad_decide takes
 STREAM_OPEN = 0x3fffffff      # ASR_STREAM_OPEN: "length not known yet" in the streaming front end's parameter arrays
 
 P, I, F, Z, U = c_void_p, c_int, c_float, c_size_t, c_uint32
@@ -177,6 +178,10 @@ SIGNATURES = {
     "asr_ctc_frame_stats": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "asr_ctc_token_conf": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "asr_session_ctc_step_tokens": (I, [P, P, P, P, P, P, P, P, P, I, I, I, F, P]),
+    "asr_vad_energy": (I, [P, P, P, I, I, I, P]),
+    "asr_vad_decide_workspace_bytes": (Z, [I, I]),
+    "asr_vad_decide": (I, [P, P, P, P, P, P, I, I, I, P]),
+    "asr_segment_gather": (I, [P, I, P, P, P, P, I, I, P]),
 }
 
 

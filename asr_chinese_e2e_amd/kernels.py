@@ -1414,3 +1414,62 @@ def stream_norm_lfr(feat_ring, par, mean, istd, m, n, C, dtype=torch.float32):
     check(lib.asr_stream_norm_lfr(_p(feat_ring), _p(par), _p(mean), _p(istd), _p(out), B, int(C), fcap, n_mels, m, n, _dt(out), _stream()),
           "asr_stream_norm_lfr")
     return out
+
+
+VAD_CTX_MAX = _lib.VAD_CTX_MAX
+
+
+def vad_energy(wav, wav_len, Tmax, E=None):
+    """Raw log-energy of every snip_edges frame of wav (B, S) f32 -> E (B, Tmax) f32, zeros at and past each recording's frame count
+    (include/asr_hip.h: asr_vad_energy)."""
+    _chk_f32(wav, E)
+    _chk_i32(wav_len)
+    if wav.dim() != 2 or wav_len.numel() != wav.shape[0]:
+        raise ValueError(f"vad_energy: wav must be (B, S) with one length per row, got {tuple(wav.shape)} and {wav_len.numel()} lengths")
+    B, S = wav.shape
+    E = torch.empty(B, int(Tmax), dtype=torch.float32, device=wav.device) if E is None else E
+    assert tuple(E.shape) == (B, int(Tmax))
+    check(lib.asr_vad_energy(_p(wav), _p(wav_len), _p(E), B, S, int(Tmax), _stream()), "asr_vad_energy")
+    return E
+
+
+def vad_decide(E, wav_len, params, ctx, speech=None, thr=None):
+    """The speech mask (B, Tmax) uint8 and the threshold (B) f64 of the log-energies E (B, Tmax) f32: params (3) f64 on the device =
+    {energy_threshold, energy_mean_scale, proportion_threshold}, ctx = frames_context (include/asr_hip.h: asr_vad_decide)."""
+    _chk_f32(E)
+    _chk_i32(wav_len)
+    B, Tmax = E.shape
+    if params.dtype != torch.float64 or params.numel() != 3 or not params.is_contiguous() or wav_len.numel() != B:
+        raise ValueError("vad_decide: params must be 3 contiguous float64 values and wav_len one length per row of E")
+    speech = torch.empty(B, Tmax, dtype=torch.uint8, device=E.device) if speech is None else speech
+    thr = torch.empty(B, dtype=torch.float64, device=E.device) if thr is None else thr
+    assert tuple(speech.shape) == (B, Tmax) and speech.dtype == torch.uint8 and speech.is_contiguous()
+    assert thr.numel() == B and thr.dtype == torch.float64 and thr.is_contiguous()
+    ws = torch.empty(max(lib.asr_vad_decide_workspace_bytes(B, Tmax) // 8, 1), dtype=torch.float64, device=E.device)
+    check(lib.asr_vad_decide(_p(E), _p(wav_len), _p(params), _p(speech), _p(thr), _p(ws), B, Tmax, int(ctx), _stream()), "asr_vad_decide")
+    return speech, thr
+
+
+def segment_gather(wav, seg_rec, seg_start, seg_len, Smax, out=None):
+    """N stretches of the recordings wav (B, S) f32 as a zero-padded batch (N, Smax) f32, bit for bit (include/asr_hip.h:
+    asr_segment_gather).  seg_rec / seg_start / seg_len: N host integers each (lists or numpy) - checked here against the batch, since the
+    kernel clamps a window to its row but cannot know how many rows there are - uploaded in one copy."""
+    import numpy as np
+    _chk_f32(wav, out)
+    if wav.dim() != 2:
+        raise ValueError(f"segment_gather: wav must be (B, S), got {tuple(wav.shape)}")
+    B, S = wav.shape
+    seg = np.asarray([seg_rec, seg_start, seg_len], dtype=np.int64).reshape(3, -1)
+    N, Smax = seg.shape[1], int(Smax)
+    if N < 1 or Smax < 1:
+        raise ValueError(f"segment_gather: {N} segments into rows of {Smax} samples")
+    bad = (seg[0] < 0) | (seg[0] >= B) | (seg[1] < 0) | (seg[2] < 0) | (seg[1] + seg[2] > S) | (seg[2] > Smax)
+    if bad.any():
+        n = int(np.argmax(bad))
+        raise ValueError(f"segment_gather: segment {n} = samples [{seg[1, n]}, {seg[1, n] + seg[2, n]}) of recording {seg[0, n]} does not lie in a batch of "
+                         f"{B} recordings of {S} samples, or is longer than Smax = {Smax}")
+    dseg = torch.from_numpy(seg.astype(np.int32)).to(wav.device, non_blocking=True)
+    out = torch.empty(N, Smax, dtype=torch.float32, device=wav.device) if out is None else out
+    assert tuple(out.shape) == (N, Smax) and out.data_ptr() != wav.data_ptr()
+    check(lib.asr_segment_gather(_p(wav), S, _p(dseg[0]), _p(dseg[1]), _p(dseg[2]), _p(out), N, Smax, _stream()), "asr_segment_gather")
+    return out

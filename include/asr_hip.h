@@ -1021,6 +1021,38 @@ int asr_session_ctc_step_tokens(const int32_t* path, const float* blank_lp, cons
                                 const int32_t* n_valid, const int32_t* reset, int32_t* state, int32_t* run, int32_t* out, int slots,
                                 int C, int blank, float silence_lp, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Energy voice-activity detection and segment gather for long recordings (additive to ABI 10; csrc/vad.hip,
+ * asr_chinese_e2e_amd/vad.py, longform.py).
+ * Stands in for:  nothing in the reference (it has no segmenter); Kaldi's compute-vad-energy restated - parity unpinned by Kaldi's
+ *                 binaries; the definition in float64 is tests/vad_ref.py.
+ *
+ * asr_vad_energy: wav (B, S) f32, wav_len (B) int32 samples, taken as min(max(wav_len[b], 0), S).  Recording b has
+ *   T_b = min(1 + (len - 400) / 160, Tmax) frames, none for len < 400; frame t is samples 160 t .. 160 t + 399 (asr_fbank_fwd's
+ *   frames).  E (B, Tmax) f32: E[b][t] = logf(max(sum_i (x_i - mean)^2, FLT_EPSILON)) with x = 32768 * sample and mean = the frame's
+ *   mean (Kaldi's raw log-energy, dither 0); frames t >= T_b hold 0.  One fixed summation order (csrc/vad.hip): a frame's bits depend
+ *   on its 400 samples only, not on the batch, the tile or the recording's length; an all-zero frame gives logf(FLT_EPSILON).
+ *   16-byte loads when S is a multiple of 4 and wav is 16-byte aligned, else a scalar path with the same bits.  1 <= B <= 65535.
+ * asr_vad_decide: E as above (Tmax the same; wav_len should not pass S), params (3) f64 on the device = {energy_threshold,
+ *   energy_mean_scale, proportion_threshold}.  thr_out[b] = params[0] + params[1] * (sum_t E[b][t]) / T_b in fp64, the sum by
+ *   per-workgroup partials in ws and a final pass, both in a fixed order and without atomics: bit-reproducible.  speech (B, Tmax)
+ *   uint8: frame t < T_b is 1 iff num >= den * params[2] in fp64, den = the frames of [t - ctx, t + ctx] inside [0, T_b), num = those
+ *   of them with (double)E > thr; frames t >= T_b hold 0.  T_b = 0: the row is zeros, thr_out[b] = params[0], nothing is divided.
+ *   ws: asr_vad_decide_workspace_bytes(B, Tmax) bytes, 8-byte aligned.  0 <= ctx <= ASR_VAD_CTX_MAX.  Two launches.
+ * asr_segment_gather: out (N, Smax) f32 row n = samples [seg_start[n], seg_start[n] + seg_len[n]) of row seg_rec[n] of wav (rows of
+ *   S samples), bit for bit, zeros behind.  The window is clamped to its row (an empty row for a negative seg_rec or a start outside
+ *   [0, S); at most min(Smax, S - start) samples); seg_rec must be below the number of rows, which the caller guarantees.  16-byte
+ *   pieces when S and Smax are multiples of 4, wav and out are 16-byte aligned and the start is a multiple of 4; else scalar.
+ *   1 <= N <= 65535.
+ */
+#define ASR_VAD_CTX_MAX 1024
+int asr_vad_energy(const float* wav, const int32_t* wav_len, float* E, int B, int S, int Tmax, void* stream);
+size_t asr_vad_decide_workspace_bytes(int B, int Tmax);
+int asr_vad_decide(const float* E, const int32_t* wav_len, const double* params, uint8_t* speech, double* thr_out, void* ws,
+                   int B, int Tmax, int ctx, void* stream);
+int asr_segment_gather(const float* wav, int S, const int32_t* seg_rec, const int32_t* seg_start, const int32_t* seg_len,
+                       float* out, int N, int Smax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,18 @@ trained with rebuild it.  Inference flags:
   --timed        1 (with --stream=1, --sessions=N included; greedy search only): the per-chunk lines gain "tokens", the characters so
                  far with frames, times and confidence (the measure of --confidence, default post_max); the last one may still be
                  open ("final": false)
+  --long         1 = the files are whole recordings (a meeting, a lecture) rather than utterances: each is cut at its pauses by the energy
+                 VAD on the GPU (Kaldi's compute-vad-energy; model.transcribe_long), its segments are transcribed in time order,
+                 --batch_size at a time, by the search the other flags choose, and one JSON line per segment is printed: {"file",
+                 "segment", "start_s", "end_s", "text", "ids", "score", "tokens", ...} with token times on the recording's axis (frame
+                 centres, as the final lines'), then the file's final line {"file", "duration_s", "text", "ids", "segments"} with the
+                 joined text.  Not with --stream=1: long streaming is what --sessions is for.  --resample=1 as above
+  --vad_energy_threshold, --vad_energy_mean_scale, --vad_frames_context, --vad_proportion_threshold
+                 the VAD's options under Kaldi's names (defaults 5.0, 0.5, 0, 0.6); with --long=1 only
+  --min_silence_s, --min_speech_s, --pad_s, --max_segment_s
+                 the segmenter's: pauses shorter than min_silence_s (0.3) do not cut, speech shorter than min_speech_s (0.1) is dropped,
+                 every segment is widened by pad_s (0.1) on both sides, a segment longer than max_segment_s (20.0) is cut at the longest
+                 pause in its second half; with --long=1 only
 Audio goes through load_wav -> AudioParser.parse_batch on the device -> model.transcribe; one JSON line per file is printed:
 {"file", "duration_s", "text", "ids", "score", "tokens": [{"id", "token", "start_frame", "end_frame", "start_s", "end_s", "logp"}]}.
 """
@@ -78,7 +90,10 @@ from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
 from asr_chinese_e2e_amd.data_handler import resample as resample_mod  # noqa: E402
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint", "context", "context_score", "lm", "lm_weight", "lm_ins", "confidence", "timed")
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint", "context", "context_score", "lm", "lm_weight", "lm_ins", "confidence", "timed", "long", "vad_energy_threshold", "vad_energy_mean_scale", "vad_frames_context", "vad_proportion_threshold", "min_silence_s", "min_speech_s", "pad_s", "max_segment_s")
+VAD_FLAGS = {"vad_energy_threshold": "energy_threshold", "vad_energy_mean_scale": "energy_mean_scale", "vad_frames_context": "frames_context",
+             "vad_proportion_threshold": "proportion_threshold"}
+SEGMENT_FLAGS = ("min_silence_s", "min_speech_s", "pad_s", "max_segment_s")
 
 
 def _finite(x):
@@ -235,6 +250,68 @@ def stream_sessions(model, parser, files, n_slots, id2tok, block, shift_s, sampl
                 slot[b] = None
 
 
+def long_options(cli):
+    """--long and its flags -> None without --long=1, else (EnergyVad, the segmenter's keywords).  SystemExit for --long=1 with a streaming
+    flag, for a VAD or segmenter flag without --long=1, and for values the VAD or the segmenter refuses - before any model is loaded."""
+    from asr_chinese_e2e_amd.vad import EnergyVad, segment_frames
+    given = [k for k in tuple(VAD_FLAGS) + SEGMENT_FLAGS if k in cli]
+    if not bool(int(cli.get("long", 0) or 0)):
+        if given:
+            raise SystemExit(f"transcribe.py: --{given[0]} applies to --long=1")
+        return None
+    for k in ("stream", "sessions"):
+        if bool(int(cli.get(k, 0) or 0)):
+            raise SystemExit(f"transcribe.py: --long=1 cannot be combined with --{k}: it segments whole recordings offline, long streaming is what "
+                             "--stream=1 --sessions=N is for")
+    seg = {k: cli[k] for k in SEGMENT_FLAGS if k in cli}
+    try:
+        vad = EnergyVad(**{VAD_FLAGS[k]: cli[k] for k in VAD_FLAGS if k in cli})
+        segment_frames(**seg)
+    except (TypeError, ValueError) as e:
+        raise SystemExit(f"transcribe.py: --long=1: {e}") from e
+    return vad, seg
+
+
+def segment_lines(path, n_samples, sr, res, shift_s, sample_rate):
+    """The JSON lines of one recording from transcribe_long's result: one per segment (token times moved to frame centres, never past the
+    recording's end), then the file's final line."""
+    lines = []
+    for i, seg in enumerate(res["segments"]):
+        for t in seg["tokens"] or ():
+            for k in ("start_s", "end_s"):
+                if t[k] is not None:
+                    t[k] = min(t[k] + shift_s, res["duration_s"])
+        line = {"file": path, "segment": i}
+        line.update({k: (_finite(v) if k == "score" else v) for k, v in seg.items()})
+        lines.append(line)
+    final = {"file": path, "duration_s": res["duration_s"], "text": res["text"], "ids": res["ids"], "segments": len(res["segments"])}
+    if sr != sample_rate:
+        final["source_rate"] = sr
+    return lines + [final]
+
+
+def transcribe_long_files(model, parser, files, vad, seg_kw, bs, resample, shift_s, sample_rate, **search):
+    """--long=1: every file through model.transcribe_long (which moves the samples to the parser's device), a file at a time."""
+    for path in files:
+        pcm, sr = load_wav(path)
+        if sr != sample_rate:
+            if not resample:
+                raise SystemExit(f"transcribe.py: {path}: sample rate {sr}, the model expects {sample_rate}")
+            try:
+                resample_mod.plan(sr)
+            except ValueError as e:
+                raise SystemExit(f"transcribe.py: {path}: {e}") from e
+        wav = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.float32).reshape(1, -1))
+        if wav.shape[1] == 0:
+            wav = torch.zeros(1, 1)
+        try:
+            res = model.transcribe_long(parser, wav, [len(pcm)], vad=vad, batch_size=bs, source_rate=sr if sr != sample_rate else None, **seg_kw, **search)[0]
+        except ValueError as e:
+            raise SystemExit(f"transcribe.py: --long=1: {e}") from e
+        for line in segment_lines(path, len(pcm), sr, res, shift_s, sample_rate):
+            print(json.dumps(line, ensure_ascii=False), flush=True)
+
+
 def cmvn_path(cli):
     """The value of --cmvn as a path, or None (absent / empty: per-utterance normalisation)."""
     v = cli.get("cmvn")
@@ -244,6 +321,7 @@ def cmvn_path(cli):
 def transcribe(**flags):
     cli = {k: flags.pop(k) for k in CLI_KEYS if k in flags}
     ctc_weight = flags.get("ctc_weight")          # model flag and decoding weight: the search uses the model's unless given
+    long_form = long_options(cli)
     config = TrainConfig()
     config.fn_build(flags)
     Model, ModelConfig = get_model_class(config.model_name)
@@ -335,6 +413,16 @@ def transcribe(**flags):
         block = int(cli.get("stream_block_samples", 0)) or model.decoding_chunk_size * config.lfr_n * 160
         stream_sessions(model, parser, files, n_sessions, id2tok, block, shift_s, config.sample_rate, endpoint=bool(int(cli.get("endpoint", 0) or 0)),
                         stream_kw=stream_kw, **search)
+        return
+    if long_form is not None:
+        search = dict(beam_size=beam, ctc_weight=ctc_weight, timestamps=timestamps, joint=joint)
+        if context is not None:
+            search["context"] = context
+        if lm is not None:
+            search["lm"] = lm
+        if confidence is not None:
+            search["confidence"] = confidence
+        transcribe_long_files(model, parser, files, long_form[0], long_form[1], bs, resample, shift_s, config.sample_rate, **search)
         return
     for i in range(0, len(files), bs):
         chunk = files[i:i + bs]
