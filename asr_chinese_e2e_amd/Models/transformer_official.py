@@ -330,7 +330,7 @@ class _SpeechTransformer(BaseModel):
         return ctx()
 
     def stream(self, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None, lm=None,
-               timed=False, confidence="post_max"):
+               timed=False, confidence="post_max", beam_times=False):
         """A streaming encoder for `batch_size` utterances (stream.StreamingEncoder): push chunks of encoder-rate features, get the
         greedy CTC ids each chunk adds; finish() gives transcribe()'s result for the same decoding chunk mask.  With an AudioParser
         of norm="global" it also takes audio as it arrives: push_audio(pcm, n_samples, final) - at source_rate, converted to
@@ -343,23 +343,28 @@ class _SpeechTransformer(BaseModel):
         lm (an lm.NgramLM; search="prefix_beam" only, not with a context): n-gram LM shallow fusion of the streamed search - partial(),
         nbest() and finish() then report 'lm_score' and order by 'score'.
         timed=True (search="greedy" only): tokens() gives every emitted character's frames, times and confidence as the audio arrives
-        (confidence.TokenLog); confidence picks the measure reported as "confidence" (confidence.MEASURES).  push returns what it returns."""
+        (confidence.TokenLog); confidence picks the measure reported as "confidence" (confidence.MEASURES).  push returns what it returns.
+        beam_times=True (search="prefix_beam" only, not with a context or an LM): the search also carries every hypothesis' best single
+        alignment (asr_ctc_prefix_beam_chunk_timed); nbest() entries gain "viterbi_score" and "tokens", partial() "tokens", and tokens()
+        lists the best hypothesis' tokens with "final" flags.  confidence: post_max, post_min or post_mean."""
         from ..stream import StreamingEncoder
         return StreamingEncoder(self, batch_size, parser=parser, source_rate=source_rate, search=search, beam_size=beam_size, frame_topk=frame_topk,
-                                context=context, context_ids=context_ids, lm=lm, timed=timed, confidence=confidence)
+                                context=context, context_ids=context_ids, lm=lm, timed=timed, confidence=confidence, beam_times=beam_times)
 
     def sessions(self, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None,
-                 timed=False, confidence="post_max"):
+                 timed=False, confidence="post_max", beam_times=False):
         """`slots` independent streaming sessions in one batch (sessions.Sessions): each slot is opened, fed (push / push_audio),
         closed, finished and reopened at its own pace - open(b), push(feats, n_valid, final), finish(b) - and with endpoint={...} the
         CTC endpoint rules report per slot when its speaker has stopped (endpoints()).  parser, search, beam_size, frame_topk as
         stream()'s; only 16 kHz audio.  context (search="prefix_beam" only): hotword biasing, open(b, context=i) picks the session's graph.
         lm (search="prefix_beam" only, not with a context): one n-gram LM for all slots; a reopened slot restarts on its start state.
         timed=True (search="greedy" only): tokens(b) gives slot b's characters with frames, times and confidence as the audio arrives;
-        confidence picks the measure reported as "confidence".  A reopened slot starts an empty list."""
+        confidence picks the measure reported as "confidence".  A reopened slot starts an empty list.
+        beam_times=True (search="prefix_beam" only, not with a context or an LM): as stream()'s - nbest(b) / partial(b) gain "tokens",
+        tokens(b) lists slot b's best hypothesis with "final" flags; finish, drop and reopening drop the records."""
         from ..sessions import Sessions
         return Sessions(self, slots, parser=parser, search=search, beam_size=beam_size, frame_topk=frame_topk, endpoint=endpoint, source_rate=source_rate,
-                        context=context, lm=lm, timed=timed, confidence=confidence)
+                        context=context, lm=lm, timed=timed, confidence=confidence, beam_times=beam_times)
 
     def forward(self, input):
         """transformer_official.py:68-81 (inference-style forward; no gradients).  A batch without a transcript (only wave / wave_len)
@@ -487,13 +492,17 @@ class _SpeechTransformer(BaseModel):
             return decode.joint_beam_search(self, input, beam_size, nbest, decode_max_len, ctc_weight)
         return decode.beam_search(self, input, beam_size, nbest, decode_max_len)
 
-    def ctc_prefix_beam_search(self, input, beam_size=5, nbest=1, frame_topk=10, on_device=None, context=None, context_ids=None, lm=None):
+    def ctc_prefix_beam_search(self, input, beam_size=5, nbest=1, frame_topk=10, on_device=None, context=None, context_ids=None, lm=None,
+                               beam_times=False, confidence="post_max"):
         """CTC prefix beam search over the CTC head (decode.ctc_prefix_beam_search): per utterance at most `nbest`
         {'yseq': [ids], 'score': log p(yseq | x)}.  on_device: None = the device kernel when beam * (frame_topk + 1) <= 64.
         context / context_ids: hotword biasing; entries are then {'yseq', 'score', 'ctc_score', 'bias'} (decode.ctc_prefix_beam_search).
-        lm: n-gram LM shallow fusion (lm.NgramLM); entries are then {'yseq', 'score', 'ctc_score', 'lm_score'}."""
+        lm: n-gram LM shallow fusion (lm.NgramLM); entries are then {'yseq', 'score', 'ctc_score', 'lm_score'}.
+        beam_times=True (the device search, not with a context or an LM): entries gain 'viterbi_score' and 'tokens' - per token its frames and
+        times in the hypothesis' best single alignment, the measures post_max / post_min / post_mean over them and 'confidence' (the one picked)."""
         from .. import decode
-        return decode.ctc_prefix_beam_search(self, input, beam_size, nbest, frame_topk, on_device, context=context, context_ids=context_ids, lm=lm)
+        return decode.ctc_prefix_beam_search(self, input, beam_size, nbest, frame_topk, on_device, context=context, context_ids=context_ids, lm=lm,
+                                             beam_times=beam_times, confidence=confidence)
 
     def ctc_greedy_search(self, input):
         """Best-path CTC hypotheses of a batch: list of id lists (repeats merged, blanks removed)."""

@@ -120,6 +120,12 @@ SIGNATURES = {
     "asr_ctc_prefix_beam_lm_state_init": (I, [P, P, P, I, I, I, P]),
     "asr_ctc_prefix_beam_lm_state_reset": (I, [P, P, P, P, I, I, I, P]),
     "asr_ctc_prefix_beam_chunk_lm": (I, [P, P, P, P, P, P, Z, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "asr_ctc_prefix_beam_timed_workspace_bytes": (Z, [I, I, I]),
+    "asr_ctc_prefix_beam_timed": (I, [P, P, P, P, P, Z] + [P] * 9 + [I] * 7 + [P]),
+    "asr_ctc_prefix_beam_timed_state_bytes": (Z, [I, I]),
+    "asr_ctc_prefix_beam_timed_state_init": (I, [P, P, I, I, I, P]),
+    "asr_ctc_prefix_beam_timed_state_reset": (I, [P, P, P, I, I, I, P]),
+    "asr_ctc_prefix_beam_chunk_timed": (I, [P, P, P, P, P, P, Z] + [P] * 11 + [I] * 8 + [P]),
     "asr_beam_step": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "asr_cache_gather": (I, [P, P, P, I, I, I, I, I, I, P]),
     "asr_ctc_prefix_logprobs": (I, [P, P, I, I, I, I, I, P]),

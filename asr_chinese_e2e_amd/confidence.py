@@ -29,6 +29,40 @@ def measure(confidence):
     return confidence
 
 
+BEAM_MEASURES = MEASURES[:3]      # what the prefix beam search can report: it sees a token's own posteriors, never a full row
+
+
+def beam_times_check(search, use_ctc, context, lm, confidence):
+    """The refusals of beam_times=True (token times of prefix beam hypotheses), before anything is launched; returns the measure."""
+    if search != "prefix_beam":
+        raise ValueError("beam_times=True needs search='prefix_beam': the greedy path reports times with timed=True")
+    if context is not None or lm is not None:
+        raise ValueError("beam_times=True is not combined with a hotword context or an n-gram LM: only the plain prefix beam search carries times")
+    which = measure(confidence) or "post_max"
+    if which not in BEAM_MEASURES:
+        raise ValueError(f"beam_times=True reports {BEAM_MEASURES}: the entropy measures need full posterior rows, which the search never sees (got {which!r})")
+    if not use_ctc:
+        raise ValueError("beam_times=True needs a model with the CTC head (config.ctc_weight > 0): times and confidence come from it")
+    return which
+
+
+def beam_tokens(ids, start, end, mx, mn, sm, which, id2tok, frame_seconds, n_final=None):
+    """The tokens of one prefix beam hypothesis from its records (asr_ctc_prefix_beam_timed: per token the first and last frame of its run
+    in the hypothesis' best single alignment, the largest, smallest and summed log-posterior over the run): {"id", "token", "start_frame",
+    "end_frame", "start_s", "end_s", "measures", "confidence"} as TokenLog's, the three measures of BEAM_MEASURES.  n_final (streams): the
+    first n_final entries get "final": True, the others False.  A hypothesis longer than its record row keeps the tokens that have one."""
+    out, d = [], float(frame_seconds)
+    for i in range(min(len(ids), len(start))):
+        x, st, en = int(ids[i]), int(start[i]), int(end[i])
+        m = {"post_max": math.exp(float(mx[i])), "post_min": math.exp(float(mn[i])), "post_mean": math.exp(float(sm[i]) / (en - st + 1))}
+        t = {"id": x, "token": id2tok[x] if 0 <= x < len(id2tok) else None, "start_frame": st, "end_frame": en, "start_s": st * d,
+             "end_s": (en + 1) * d, "measures": m, "confidence": m[which]}
+        if n_final is not None:
+            t["final"] = i < n_final
+        out.append(t)
+    return out
+
+
 def measures_dict(five):
     """{measure: value} of a token's five values; None when the token has none (NaN: its utterance could not be aligned)."""
     if five[0] != five[0]:      # the kernel writes NaN to all five or to none

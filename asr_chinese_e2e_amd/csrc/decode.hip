@@ -500,6 +500,42 @@ __device__ __forceinline__ void pb_lm_report(const PbLmLds& ls, int nb, double* 
     }
 }
 
+// ---- token times (TIMES instantiations only) ----------------------------------------------------------------------------------------------
+// Beside pb / pnb a beam entry carries the best single alignment of its prefix that ends in blank / in non-blank: its fp64 log-probability
+// (vb / vnb) and the frames of its tokens (hb / hnb), a persistent list in a second trie: node = one record {parent, depth, start, end,
+// mx, mn, sm} (32 bytes with a pad word: one hop of a walk is one cache line) = the list without its last record, the list's length, the first and last frame of the last token's run and the largest,
+// the smallest and the float32 sum of the token's log-posteriors over the run.  Node 0 is the empty list; a copy is the same index, `append`
+// makes a node under the source list's head, `ext` (the run grows by a frame) a node beside it.  The definition the tests check against is
+// tests/beam_times_ref.py.
+struct alignas(8) PbTimeNode {
+    int32_t par, dep, start, end;
+    float mx, mn, sm;
+    int32_t pad;
+};
+using PbTimeTrie = PbTimeNode*;
+
+constexpr int PB_TIME_WORDS = sizeof(PbTimeNode) / 4;      // words per node of the time trie
+
+// utterance b's time trie: the B time tries lie behind the B prefix tries (2 words per node, so 8-aligned when the workspace is)
+__device__ __forceinline__ PbTimeTrie pb_time_trie(int32_t* nodes, int B, int b, size_t cap_nodes) {
+    return (PbTimeNode*)(nodes + (size_t)B * 2 * cap_nodes) + (size_t)b * cap_nodes;
+}
+
+// the beam's Viterbi values and list heads in rank order, what a merged extension hands to the stay slot (next to s.merge), one frame's slots
+struct PbTimesLds {
+    double vb[PB_MAX_BEAM], vnb[PB_MAX_BEAM], mv[PB_MAX_BEAM], nvb[64], nvnb[64];
+    int hb[PB_MAX_BEAM], hnb[PB_MAX_BEAM], mh[PB_MAX_BEAM], nhb[64], nhnb[64];
+    float mlp[PB_MAX_BEAM];
+};
+
+// what a TIMES frame step takes beside the others: the LDS part, the trie, the absolute frame and the nodes in use (wave-uniform, carried across frames)
+struct PbTimes {
+    PbTimesLds* ts;
+    PbTimeTrie tt;
+    int t;
+    int next;
+};
+
 // The three flavours of the one frame step: the plain search, hotword biasing, n-gram LM fusion.
 constexpr int PB_PLAIN = 0, PB_CTX = 1, PB_LM = 2;
 
@@ -534,6 +570,12 @@ __device__ __forceinline__ void pb_empty_beam(PbLds& s) {
     s.node[0] = 0; s.tok[0] = -1; s.par[0] = -1; s.dep[0] = 0; s.pb[0] = 0.0; s.pnb[0] = -INFINITY;
 }
 
+// ... and its Viterbi part: the empty alignment, probability one, ends "in blank"; both lists empty.  Node 0 of the time trie is the empty list.
+__device__ __forceinline__ void pb_time_empty(PbTimesLds& ts, PbTimeTrie tt) {
+    ts.vb[0] = 0.0; ts.vnb[0] = -INFINITY; ts.hb[0] = 0; ts.hnb[0] = 0;
+    tt[0] = PbTimeNode{-1, 0, -1, -1, 0.0f, 0.0f, 0.0f, 0};
+}
+
 // One frame of the search: the only copy, run by the offline kernel and by the resumable one.  row_* = the frame's candidates;
 // nb / next_node = beam entries / trie nodes in use (wave-uniform, carried across frames).
 // PB_LM also keeps child lists in the trie (nfirst: a node's newest child, nsib: the next older child of the same parent): with an insertion
@@ -542,15 +584,20 @@ __device__ __forceinline__ void pb_empty_beam(PbLds& s) {
 // its probability split.  Here a surviving extension takes the node its (parent, token) already has, so node = string as in the definition.
 // All 64 lanes call it; it ends with a barrier.  PB_PLAIN is the search without biasing (cs / g / root / ls / lm unused); PB_CTX adds the
 // entries' context state and bias (cs), PB_LM their LM state and bias (ls), and both rank by log p + bias.
-template <int MODE>
+// TIMES (orthogonal to MODE): the entries' best single alignments ride along (tm); a kept entry whose non-blank alignment is finite gets a
+// node of the time trie, so at most `beam` per frame.  Every Viterbi sum is v + (double)lp in that order.
+template <int MODE, bool TIMES = false>
 __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict__ row_vals, const int32_t* __restrict__ row_ids, double lb, int k, int beam,
                                               int blank, int& nb, int& next_node, int32_t* npar, int32_t* ntok, PbCtxLds* cs = nullptr,
                                               const PbCtx* g = nullptr, int root = -1, PbLmLds* ls = nullptr, const PbLm* lm = nullptr, int32_t* nfirst = nullptr,
-                                              int32_t* nsib = nullptr) {
+                                              int32_t* nsib = nullptr, PbTimes* tm = nullptr) {
     constexpr bool CTX = MODE == PB_CTX, LM = MODE == PB_LM;
     const int lane = threadIdx.x, per = k + 1;
     if (lane < k) { s.id[lane] = row_ids[lane]; s.lp[lane] = row_vals[lane]; }
     if (lane < PB_MAX_BEAM) s.merge[lane] = -INFINITY;
+    if constexpr (TIMES) {
+        if (lane < PB_MAX_BEAM) tm->ts->mv[lane] = -INFINITY;
+    }
     __syncthreads();
     const int j = lane / per, m = lane - j * per;
     bool valid = j < nb;
@@ -564,6 +611,10 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
     if constexpr (LM) {
         if (valid) { cst = ls->st[j]; cbias = ls->bias[j]; }
     }
+    // TIMES: the slot's Viterbi values; its non-blank list is `tkind` of list tsrc with the frame's tlp (0: none, 1: ext, 2: append)
+    [[maybe_unused]] double vb2 = -INFINITY, vnb2 = -INFINITY;
+    [[maybe_unused]] int hb2 = 0, tsrc = 0, tkind = 0;
+    [[maybe_unused]] float tlp = 0.0f;
     if (valid) {
         const double pb = s.pb[j], pnb = s.pnb[j], tot = pb_logadd(pb, pnb);
         const int e = s.tok[j];
@@ -574,6 +625,17 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
             c = e;
             ident_par = s.par[j];
             dep = s.dep[j];
+            if constexpr (TIMES) {
+                const double vb = tm->ts->vb[j], vnb = tm->ts->vnb[j];
+                const bool nbw = vnb > vb;               // best(): the non-blank alignment only if it is strictly better
+                vb2 = (nbw ? vnb : vb) + lb;
+                hb2 = vb2 > -INFINITY ? (nbw ? tm->ts->hnb[j] : tm->ts->hb[j]) : 0;
+                for (int q = 0; q < k; ++q)
+                    if (s.id[q] == e && e != blank) {
+                        const double x = vnb + (double)s.lp[q];
+                        if (x > vnb2) { vnb2 = x; tsrc = tm->ts->hnb[j]; tkind = 1; tlp = s.lp[q]; }
+                    }
+            }
         } else {                                     // extend with the (m-1)-th candidate
             c = s.id[m - 1];
             if (c == blank) valid = false;
@@ -583,6 +645,12 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
                 dep = s.dep[j] + 1;
                 if constexpr (CTX) pb_ctx_advance(*g, root, c, cst, cbias);
                 if constexpr (LM) pb_lm_advance(*lm, c, cst, cbias);
+                if constexpr (TIMES) {
+                    const double vb = tm->ts->vb[j], vnb = tm->ts->vnb[j];
+                    const bool nbw = vnb > vb, rep = c == e;
+                    const double x = (rep ? vb : nbw ? vnb : vb) + (double)s.lp[m - 1];
+                    if (x > -INFINITY) { vnb2 = x; tsrc = (rep || !nbw) ? tm->ts->hb[j] : tm->ts->hnb[j]; tkind = 2; tlp = s.lp[m - 1]; }
+                }
             }
         }
     }
@@ -591,12 +659,19 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
         for (int i = 0; i < nb; ++i)
             if (s.par[i] == ident_par && s.tok[i] == c) {
                 s.merge[i] = pnb2;                   // at most one extension matches an entry (parent and token are unique)
+                if constexpr (TIMES) { tm->ts->mv[i] = vnb2; tm->ts->mh[i] = tsrc; tm->ts->mlp[i] = tlp; }
                 valid = false;
                 break;
             }
     }
     __syncthreads();
     if (valid && m == 0) pnb2 = pb_logadd(pnb2, s.merge[j]);
+    if constexpr (TIMES) {
+        if (valid && m == 0) {                       // the prefix's own repeat against its parent's extension: the repeat wins a tie
+            const double mv = tm->ts->mv[j];
+            if (mv > vnb2) { vnb2 = mv; tsrc = tm->ts->mh[j]; tkind = 2; tlp = tm->ts->mlp[j]; }
+        }
+    }
     double sc = valid ? pb_logadd(pb2, pnb2) : -INFINITY;
     if constexpr (CTX || LM) {
         if (sc > -INFINITY) sc = sc + cbias;         // -inf stays -inf
@@ -626,6 +701,24 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
         }
     }
     const unsigned long long ext_mask = __ballot(keep && m > 0 && found < 0);      // the survivors that need a new node
+    [[maybe_unused]] unsigned long long time_mask = 0;
+    if constexpr (TIMES) {
+        time_mask = __ballot(keep && tkind != 0);    // ... and those that need a node of the time trie
+        if (keep) {
+            int hnb2 = 0;
+            if (tkind != 0) {
+                const PbTimeTrie tt = tm->tt;
+                hnb2 = tm->next + __popcll(time_mask & ((1ull << lane) - 1ull));
+                if (tkind == 2) {                    // append: a new token's run opens under the source list
+                    tt[hnb2] = PbTimeNode{tsrc, dep, tm->t, tm->t, tlp, tlp, tlp, 0};
+                } else {                             // ext: the last token's run grows by this frame
+                    const PbTimeNode o = tt[tsrc];
+                    tt[hnb2] = PbTimeNode{o.par, dep, o.start, tm->t, tlp > o.mx ? tlp : o.mx, tlp < o.mn ? tlp : o.mn, o.sm + tlp, 0};
+                }
+            }
+            tm->ts->nvb[rank] = vb2; tm->ts->nvnb[rank] = vnb2; tm->ts->nhb[rank] = hb2; tm->ts->nhnb[rank] = hnb2;
+        }
+    }
     if (keep) {
         int node = m == 0 ? s.node[j] : found >= 0 ? found : next_node + __popcll(ext_mask & ((1ull << lane) - 1ull));
         if (m > 0 && found < 0) { npar[node] = ident_par; ntok[node] = c; }
@@ -642,6 +735,13 @@ __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict_
     __syncthreads();
     nb = __popcll(keep_mask);
     next_node += __popcll(ext_mask);
+    if constexpr (TIMES) {
+        tm->next += __popcll(time_mask);
+        if (lane < nb) {
+            PbTimesLds& ts = *tm->ts;
+            ts.vb[lane] = ts.nvb[lane]; ts.vnb[lane] = ts.nvnb[lane]; ts.hb[lane] = ts.nhb[lane]; ts.hnb[lane] = ts.nhnb[lane];
+        }
+    }
     if (lane < nb) {
         s.node[lane] = s.nnode[lane]; s.tok[lane] = s.ntok_[lane]; s.par[lane] = s.npar_[lane]; s.dep[lane] = s.ndep_[lane];
         s.pb[lane] = s.npb[lane]; s.pnb[lane] = s.npnb[lane];
@@ -690,12 +790,50 @@ __device__ __forceinline__ void pb_spell(const PbLds& s, int nb, const int32_t* 
     }
 }
 
-template <int MODE>
+// what the TIMES kernels take beside the others' arguments (nothing without TIMES)
+template <bool TIMES> struct PbTimeArgs {};
+template <> struct PbTimeArgs<true> {
+    double* out_vit;          // (B, nbest) the log-probability of the entry's best single alignment (-inf: no entry)
+    int32_t* out_start;       // (B, nbest, Lcap) per token of the entry the first ...
+    int32_t* out_end;         // ... and the last frame of its run in that alignment
+    float* out_mx;            // (B, nbest, Lcap) the largest, ...
+    float* out_mn;            // ... the smallest ...
+    float* out_sm;            // ... and the sum of the token's log-posteriors over the run
+    int32_t* out_final;       // resumable: (B) the count of final records; offline: unused
+};
+
+// The records of the n best of utterance b: the list of best(), spelled by walking parents as pb_spell walks the prefixes.  A list longer
+// than the output row keeps its first Lcap records.  Every index is kept inside the trie (n_nodes in use).
+__device__ __forceinline__ void pb_spell_times(const PbTimesLds& ts, const PbTimeTrie tt, int nb, int n_nodes, const PbTimeArgs<true>& o, int b, int nbest, int Lcap) {
+    const int lane = threadIdx.x;
+    if (lane < nbest) {
+        if (lane < nb) {
+            const bool nbw = ts.vnb[lane] > ts.vb[lane];
+            o.out_vit[b * nbest + lane] = nbw ? ts.vnb[lane] : ts.vb[lane];
+            const size_t row = ((size_t)b * nbest + lane) * Lcap;
+            int nd = nbw ? ts.hnb[lane] : ts.hb[lane];
+            for (int it = 0; nd > 0 && nd < n_nodes && it < n_nodes; ++it) {
+                const PbTimeNode x = tt[nd];
+                const int pos = x.dep - 1;
+                if (pos >= 0 && pos < Lcap) {
+                    o.out_start[row + pos] = x.start; o.out_end[row + pos] = x.end;
+                    o.out_mx[row + pos] = x.mx; o.out_mn[row + pos] = x.mn; o.out_sm[row + pos] = x.sm;
+                }
+                nd = x.par;
+            }
+        } else {
+            o.out_vit[b * nbest + lane] = -INFINITY;
+        }
+    }
+}
+
+template <int MODE, bool TIMES = false>
 __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __restrict__ vals, const int32_t* __restrict__ ids, const float* __restrict__ blank_lp,
                                                              const int32_t* __restrict__ in_len, int32_t* nodes, int32_t* __restrict__ out_tok,
                                                              int32_t* __restrict__ out_len, float* __restrict__ out_score, int T, int k, int beam, int nbest,
-                                                             int Lcap, int blank, PbArgs<MODE> cx) {
+                                                             int Lcap, int blank, PbArgs<MODE> cx, PbTimeArgs<TIMES> tx) {
     constexpr bool CTX = MODE == PB_CTX, LM = MODE == PB_LM;
+    static_assert(!TIMES || MODE == PB_PLAIN, "the time trie lies behind the plain trie");
     __shared__ PbLds s;
     [[maybe_unused]] PbCtxLds* cs = nullptr;
     [[maybe_unused]] PbCtx g{};
@@ -723,6 +861,14 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
         if constexpr (LM) nfirst[0] = 0;
         pb_empty_beam(s);
     }
+    [[maybe_unused]] PbTimes tm{};
+    if constexpr (TIMES) {                               // the time tries lie behind the B prefix tries
+        __shared__ PbTimesLds ts_mem;
+        tm.ts = &ts_mem;
+        tm.tt = pb_time_trie(nodes, gridDim.x, b, cap_nodes);
+        tm.next = 1;
+        if (lane == 0) pb_time_empty(ts_mem, tm.tt);
+    }
     if constexpr (CTX) {
         root = pb_ctx_root(g, cx.root[b]);
         if (lane == 0) { cs->st[0] = root; cs->bias[0] = 0.0; }
@@ -736,11 +882,15 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
         const size_t row = (size_t)b * T + t;
         if constexpr (CTX) pb_frame_step<PB_CTX>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, cs, &g, root);
         else if constexpr (LM) pb_frame_step<PB_LM>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, nullptr, nullptr, -1, ls, &cx.lm, nfirst, nsib);
-        else pb_frame_step<PB_PLAIN>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
+        else if constexpr (TIMES) {
+            tm.t = t;
+            pb_frame_step<PB_PLAIN, true>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, nullptr, nullptr, -1, nullptr, nullptr, nullptr, nullptr, &tm);
+        } else pb_frame_step<PB_PLAIN>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
     }
     pb_spell(s, nb, npar, ntok, out_tok, out_len, out_score, b, nbest, Lcap);
     if constexpr (CTX) pb_ctx_report(*cs, nb, cx.out_bias, cx.out_state, b, nbest);
     if constexpr (LM) pb_lm_report(*ls, nb, cx.out_bias, cx.out_state, b, nbest);
+    if constexpr (TIMES) pb_spell_times(*tm.ts, tm.tt, nb, min(tm.next, cap_nodes), tx, b, nbest, Lcap);
 }
 
 // ---- the resumable search: the beam leaves LDS between launches ------------------------------------------------------------------
@@ -756,6 +906,9 @@ __host__ __device__ inline size_t pb_ctx_state_bytes1(int beam) { return pb_stat
 
 // The LM state of one utterance: the plain state, then fp64 bias[beam], int32 st[beam], padded to 8 bytes.
 __host__ __device__ inline size_t pb_lm_state_bytes1(int beam) { return pb_state_bytes1(beam) + (size_t)beam * 8 + (((size_t)beam * 4 + 7) & ~(size_t)7); }
+
+// The timed state of one utterance: the plain state, then fp64 vb[beam], vnb[beam], int32 hb[beam], hnb[beam], the time trie's nodes in use, padded to 8 bytes.
+__host__ __device__ inline size_t pb_time_state_bytes1(int beam) { return pb_state_bytes1(beam) + (size_t)beam * 16 + (((size_t)beam * 8 + 4 + 7) & ~(size_t)7); }
 
 // The empty-prefix state of utterance b and its trie's root: what the init kernel leaves for every utterance and the reset kernel for the flagged ones.
 // bytes1: the bytes of one utterance's state (pb_state_bytes1, or pb_ctx_state_bytes1 / pb_lm_state_bytes1 when a context / LM part follows).
@@ -820,14 +973,30 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_lm_state_init_kernel(char*
     if (beam & 1) st[beam] = 0;
 }
 
-template <int MODE>
+// the Viterbi part of utterance b's timed state and the root of its time trie (behind the B prefix tries)
+// flags == nullptr: every utterance (init); otherwise the flagged ones (reset)
+__global__ __launch_bounds__(64) void ctc_prefix_beam_timed_state_init_kernel(char* state, int32_t* nodes, const int32_t* __restrict__ flags, int B, int beam, int T_cap) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B || (flags && flags[b] == 0)) return;
+    pb_state_init_one(state, nodes, b, beam, T_cap, pb_time_state_bytes1(beam));
+    const size_t cap_nodes = (size_t)T_cap * beam + 1;
+    double* v = (double*)(state + (size_t)b * pb_time_state_bytes1(beam) + pb_state_bytes1(beam));
+    int32_t* h = (int32_t*)(v + 2 * beam);
+    for (int i = 0; i < beam; ++i) { v[i] = i == 0 ? 0.0 : -INFINITY; v[beam + i] = -INFINITY; h[i] = 0; h[beam + i] = 0; }
+    h[2 * beam] = 1;
+    h[2 * beam + 1] = 0;
+    pb_time_trie(nodes, B, b, cap_nodes)[0] = PbTimeNode{-1, 0, -1, -1, 0.0f, 0.0f, 0.0f, 0};
+}
+
+template <int MODE, bool TIMES = false>
 __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* __restrict__ vals, const int32_t* __restrict__ ids, const float* __restrict__ blank_lp,
                                                                    const int32_t* __restrict__ n_valid, char* state, int32_t* nodes, int32_t* __restrict__ out_tok,
                                                                    int32_t* __restrict__ out_len, float* __restrict__ out_score, int32_t* __restrict__ out_stable,
-                                                                   int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank, PbArgs<MODE> cx) {
+                                                                   int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank, PbArgs<MODE> cx, PbTimeArgs<TIMES> tx) {
     constexpr bool CTX = MODE == PB_CTX, LM = MODE == PB_LM;
+    static_assert(!TIMES || MODE == PB_PLAIN, "the time trie lies behind the plain trie");
     __shared__ PbLds s;
-    __shared__ int s_walk[PB_MAX_BEAM];
+    __shared__ int s_walk[TIMES ? 2 * PB_MAX_BEAM : PB_MAX_BEAM];
     [[maybe_unused]] PbCtxLds* cs = nullptr;
     [[maybe_unused]] PbCtx g{};
     if constexpr (CTX) {
@@ -846,7 +1015,7 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* 
     int32_t* ntok = npar + cap_nodes;
     [[maybe_unused]] int32_t* nfirst = ntok + cap_nodes;
     [[maybe_unused]] int32_t* nsib = ntok + 2 * (size_t)cap_nodes;
-    int32_t* hdr = (int32_t*)(state + (size_t)b * (CTX ? pb_ctx_state_bytes1(beam) : LM ? pb_lm_state_bytes1(beam) : pb_state_bytes1(beam)));
+    int32_t* hdr = (int32_t*)(state + (size_t)b * (CTX ? pb_ctx_state_bytes1(beam) : LM ? pb_lm_state_bytes1(beam) : TIMES ? pb_time_state_bytes1(beam) : pb_state_bytes1(beam)));
     int32_t* ent = hdr + PB_STATE_HDR;
     double* sc = (double*)(ent + 4 * beam);
     int nb = min(max(hdr[0], 0), beam), next_node = hdr[1];      // wave-uniform copies
@@ -865,16 +1034,37 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* 
     if constexpr (LM) {
         if (lane < nb) { ls->st[lane] = st_ctx[lane]; ls->bias[lane] = st_bias[lane]; }
     }
+    [[maybe_unused]] PbTimes tm{};
+    [[maybe_unused]] double* st_v = sc + 2 * beam;               // the Viterbi part of a timed state: vb, vnb, then hb, hnb, the time trie's nodes in use
+    [[maybe_unused]] int32_t* st_h = (int32_t*)(st_v + 2 * beam);
+    if constexpr (TIMES) {
+        __shared__ PbTimesLds ts_mem;
+        tm.ts = &ts_mem;
+        tm.tt = pb_time_trie(nodes, gridDim.x, b, cap_nodes);
+        tm.next = st_h[2 * beam];
+        if (lane < nb) {                                         // a list head outside the trie reads as the empty list
+            ts_mem.vb[lane] = st_v[lane]; ts_mem.vnb[lane] = st_v[beam + lane];
+            const int hb = st_h[lane], hnb = st_h[beam + lane];
+            ts_mem.hb[lane] = (hb > 0 && hb < min(tm.next, cap_nodes)) ? hb : 0;
+            ts_mem.hnb[lane] = (hnb > 0 && hnb < min(tm.next, cap_nodes)) ? hnb : 0;
+        }
+    }
     __syncthreads();
     // never past the trie: at most T_cap frames in all (the wrapper refuses such a push; this keeps every write inside the workspace)
     const int n = max(0, min(min(n_valid[b], C), T_cap - frames));
     int done = 0;
     for (int t = 0; t < n; ++t) {
         if (next_node < 1 || next_node + beam > cap_nodes) break;
+        if constexpr (TIMES) {
+            if (tm.next < 1 || tm.next + beam > cap_nodes) break;
+        }
         const size_t row = (size_t)b * C + t;
         if constexpr (CTX) pb_frame_step<PB_CTX>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, cs, &g, root);
         else if constexpr (LM) pb_frame_step<PB_LM>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, nullptr, nullptr, -1, ls, &cx.lm, nfirst, nsib);
-        else pb_frame_step<PB_PLAIN>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
+        else if constexpr (TIMES) {
+            tm.t = frames + t;
+            pb_frame_step<PB_PLAIN, true>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok, nullptr, nullptr, -1, nullptr, nullptr, nullptr, nullptr, &tm);
+        } else pb_frame_step<PB_PLAIN>(s, vals + row * k, ids + row * k, (double)blank_lp[row], k, beam, blank, nb, next_node, npar, ntok);
         ++done;
     }
     if (done > 0) {                                      // a chunk without frames leaves every byte of the state as it is
@@ -884,11 +1074,16 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* 
             sc[lane] = s.pb[lane]; sc[beam + lane] = s.pnb[lane];
             if constexpr (CTX) { st_ctx[lane] = cs->st[lane]; st_bias[lane] = cs->bias[lane]; }
             if constexpr (LM) { st_ctx[lane] = ls->st[lane]; st_bias[lane] = ls->bias[lane]; }
+            if constexpr (TIMES) { st_v[lane] = tm.ts->vb[lane]; st_v[beam + lane] = tm.ts->vnb[lane]; st_h[lane] = tm.ts->hb[lane]; st_h[beam + lane] = tm.ts->hnb[lane]; }
+        }
+        if constexpr (TIMES) {
+            if (lane == 0) st_h[2 * beam] = tm.next;
         }
     }
     pb_spell(s, nb, npar, ntok, out_tok, out_len, out_score, b, nbest, Lcap);
     if constexpr (CTX) pb_ctx_report(*cs, nb, cx.out_bias, cx.out_state, b, nbest);
     if constexpr (LM) pb_lm_report(*ls, nb, cx.out_bias, cx.out_state, b, nbest);
+    if constexpr (TIMES) pb_spell_times(*tm.ts, tm.tt, nb, min(tm.next, cap_nodes), tx, b, nbest, Lcap);
     // the stable prefix: the depth of the lowest common ancestor of the beam's nodes.  Every entry first climbs to the smallest depth
     // among them, then all climb together until they stand on one node.
     int mind = INT_MAX;
@@ -906,6 +1101,43 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_chunk_kernel(const float* 
         --mind;
     }
     if (lane == 0) out_stable[b] = nb > 0 ? mind : 0;
+    if constexpr (TIMES) {
+        // the final records: the depth of the lowest common ancestor of S = the lists without their last record, over every non-empty list
+        // of a finite alignment (two walkers per entry, lane = 2 * entry + (0: hb, 1: hnb)).  An empty list among them: nothing is final.
+        // A list of entry i has dep[i] records, so its parent stands at depth dep[i] - 1; the walk is the stable prefix's.
+        __syncthreads();                                 // s_walk is free again
+        const PbTimesLds& ts = *tm.ts;
+        const int n_nodes = min(tm.next, cap_nodes), e = lane >> 1;
+        const bool live = lane < 2 * nb && ((lane & 1) ? ts.vnb[e] : ts.vb[e]) > -INFINITY;
+        const int head = live ? ((lane & 1) ? ts.hnb[e] : ts.hb[e]) : 0;
+        const unsigned long long live_mask = __ballot(live), empty_mask = __ballot(live && head <= 0);
+        int fin = 0;
+        if (live_mask != 0 && empty_mask == 0) {         // wave-uniform
+            int w = tm.tt[head < n_nodes ? head : 0].par, wd = live ? s.dep[e] - 1 : INT_MAX;
+            if (!live || w < 0) w = 0;
+            fin = wd;
+            for (int o = 32; o > 0; o >>= 1) fin = min(fin, __shfl_xor(fin, o));
+            fin = max(fin, 0);
+            while (live && wd > fin && w > 0 && w < n_nodes) { w = tm.tt[w].par; --wd; }
+            for (;;) {
+                if (lane < 2 * PB_MAX_BEAM) s_walk[lane] = live ? w : -1;
+                __syncthreads();
+                int first = -1;
+                bool same = true;
+                for (int i = 0; i < 2 * nb; ++i) {
+                    const int x = s_walk[i];
+                    if (x < 0) continue;
+                    if (first < 0) first = x;
+                    same = same && x == first;
+                }
+                __syncthreads();
+                if (same || fin <= 0) break;             // wave-uniform
+                if (live && w > 0 && w < n_nodes) w = tm.tt[w].par;
+                --fin;
+            }
+        }
+        if (lane == 0) tx.out_final[b] = fin;
+    }
 }
 
 }  // namespace
@@ -923,7 +1155,7 @@ extern "C" int asr_ctc_prefix_beam(const float* vals, const int32_t* ids, const 
     if (beam > PB_MAX_BEAM || k > PB_MAX_K || beam * (k + 1) > 64 || nbest > beam)
         ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam: one wave ranks the beam * (k + 1) candidates of a frame: beam * (k + 1) <= 64, beam <= %d, nbest <= beam (beam=%d k=%d nbest=%d)", PB_MAX_BEAM, beam, k, nbest);
     if (ws_bytes < asr_ctc_prefix_beam_workspace_bytes(B, T, beam) || ((uintptr_t)ws % 4)) ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_workspace_bytes(B, T, beam), ws_bytes);
-    ctc_prefix_beam_kernel<PB_PLAIN><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, PbArgs<PB_PLAIN>{});
+    ctc_prefix_beam_kernel<PB_PLAIN><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, PbArgs<PB_PLAIN>{}, PbTimeArgs<false>{});
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam");
     return ASR_OK;
 }
@@ -974,7 +1206,7 @@ extern "C" int asr_ctc_prefix_beam_chunk(const float* vals, const int32_t* ids, 
     if (ws_bytes < asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam) || ((uintptr_t)ws % 4))
         ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_chunk: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam), ws_bytes);
     ctc_prefix_beam_chunk_kernel<PB_PLAIN><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score,
-                                                                           out_stable, C, k, beam, nbest, Lcap, T_cap, blank, PbArgs<PB_PLAIN>{});
+                                                                           out_stable, C, k, beam, nbest, Lcap, T_cap, blank, PbArgs<PB_PLAIN>{}, PbTimeArgs<false>{});
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_chunk");
     return ASR_OK;
 }
@@ -1003,7 +1235,7 @@ extern "C" int asr_ctc_prefix_beam_ctx(const float* vals, const int32_t* ids, co
     if (((uintptr_t)out_bias % 8) || (((uintptr_t)root | (uintptr_t)out_state) % 4)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_ctx: misaligned pointer (out_bias: 8 bytes, root and out_state: 4)");
     if (ws_bytes < asr_ctc_prefix_beam_workspace_bytes(B, T, beam) || ((uintptr_t)ws % 4)) ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_ctx: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_workspace_bytes(B, T, beam), ws_bytes);
     PbArgs<PB_CTX> cx{pb_ctx_of(ctx), root, out_bias, out_state};
-    ctc_prefix_beam_kernel<PB_CTX><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, cx);
+    ctc_prefix_beam_kernel<PB_CTX><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, cx, PbTimeArgs<false>{});
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_ctx");
     return ASR_OK;
 }
@@ -1053,7 +1285,7 @@ extern "C" int asr_ctc_prefix_beam_chunk_ctx(const float* vals, const int32_t* i
         ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_chunk_ctx: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam), ws_bytes);
     PbArgs<PB_CTX> cx{pb_ctx_of(ctx), nullptr, out_bias, out_state};
     ctc_prefix_beam_chunk_kernel<PB_CTX><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score,
-                                                                          out_stable, C, k, beam, nbest, Lcap, T_cap, blank, cx);
+                                                                          out_stable, C, k, beam, nbest, Lcap, T_cap, blank, cx, PbTimeArgs<false>{});
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_chunk_ctx");
     return ASR_OK;
 }
@@ -1092,7 +1324,7 @@ extern "C" int asr_ctc_prefix_beam_lm(const float* vals, const int32_t* ids, con
     if (((uintptr_t)out_bias % 8) || ((uintptr_t)out_state % 4)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_lm: misaligned pointer (out_bias: 8 bytes, out_state: 4)");
     if (ws_bytes < asr_ctc_prefix_beam_lm_workspace_bytes(B, T, beam) || ((uintptr_t)ws % 4)) ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_lm: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_lm_workspace_bytes(B, T, beam), ws_bytes);
     PbArgs<PB_LM> cx{pb_lm_of(lm), out_bias, out_state};
-    ctc_prefix_beam_kernel<PB_LM><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, cx);
+    ctc_prefix_beam_kernel<PB_LM><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, cx, PbTimeArgs<false>{});
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_lm");
     return ASR_OK;
 }
@@ -1143,8 +1375,91 @@ extern "C" int asr_ctc_prefix_beam_chunk_lm(const float* vals, const int32_t* id
         ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_chunk_lm: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_lm_workspace_bytes(B, T_cap, beam), ws_bytes);
     PbArgs<PB_LM> cx{pb_lm_of(lm), out_bias, out_state};
     ctc_prefix_beam_chunk_kernel<PB_LM><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score,
-                                                                            out_stable, C, k, beam, nbest, Lcap, T_cap, blank, cx);
+                                                                            out_stable, C, k, beam, nbest, Lcap, T_cap, blank, cx, PbTimeArgs<false>{});
     ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_chunk_lm");
+    return ASR_OK;
+}
+
+// ---- token times: the plain searches with the best single alignment of every prefix riding along (additive to ABI 10) ----------------------
+extern "C" size_t asr_ctc_prefix_beam_timed_workspace_bytes(int B, int T, int beam) {
+    if (B <= 0 || T <= 0 || beam <= 0) return 0;
+    return (size_t)B * (2 + PB_TIME_WORDS) * ((size_t)T * beam + 1) * sizeof(int32_t);      // the B prefix tries, then the B time tries
+}
+
+namespace {
+const char* pb_time_out_check(const double* out_vit, const int32_t* out_start, const int32_t* out_end, const float* out_mx, const float* out_mn, const float* out_sm) {
+    if (!out_vit || !out_start || !out_end || !out_mx || !out_mn || !out_sm) return "null pointer";
+    if (((uintptr_t)out_vit % 8) || (((uintptr_t)out_start | (uintptr_t)out_end | (uintptr_t)out_mx | (uintptr_t)out_mn | (uintptr_t)out_sm) % 4))
+        return "misaligned pointer (out_vit: 8 bytes, the other time outputs: 4)";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" int asr_ctc_prefix_beam_timed(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* in_len, void* ws, size_t ws_bytes,
+                                         int32_t* out_tok, int32_t* out_len, float* out_score, double* out_vit, int32_t* out_start, int32_t* out_end,
+                                         float* out_mx, float* out_mn, float* out_sm, int B, int T, int k, int beam, int nbest, int Lcap, int blank,
+                                         void* stream) {
+    if (!vals || !ids || !blank_lp || !ws || !out_tok || !out_len || !out_score) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_timed: null pointer");
+    if (const char* why = pb_time_out_check(out_vit, out_start, out_end, out_mx, out_mn, out_sm)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_timed: %s", why);
+    if (B <= 0 || T <= 0 || k <= 0 || beam <= 0 || nbest <= 0 || Lcap <= 0) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_timed: bad shape B=%d T=%d k=%d beam=%d nbest=%d Lcap=%d", B, T, k, beam, nbest, Lcap);
+    if (beam > PB_MAX_BEAM || k > PB_MAX_K || beam * (k + 1) > 64 || nbest > beam)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_timed: one wave ranks the beam * (k + 1) candidates of a frame: beam * (k + 1) <= 64, beam <= %d, nbest <= beam (beam=%d k=%d nbest=%d)", PB_MAX_BEAM, beam, k, nbest);
+    if ((size_t)T * beam + 1 > (size_t)INT_MAX) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_timed: T * beam + 1 nodes do not fit an int32 (T=%d beam=%d)", T, beam);
+    if (ws_bytes < asr_ctc_prefix_beam_timed_workspace_bytes(B, T, beam) || ((uintptr_t)ws % 8))
+        ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_timed: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_timed_workspace_bytes(B, T, beam), ws_bytes);
+    PbTimeArgs<true> tx{out_vit, out_start, out_end, out_mx, out_mn, out_sm, nullptr};
+    ctc_prefix_beam_kernel<PB_PLAIN, true><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, in_len, (int32_t*)ws, out_tok, out_len, out_score, T, k, beam, nbest, Lcap, blank, PbArgs<PB_PLAIN>{}, tx);
+    ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_timed");
+    return ASR_OK;
+}
+
+extern "C" size_t asr_ctc_prefix_beam_timed_state_bytes(int B, int beam) {
+    if (B <= 0 || beam <= 0) return 0;
+    return (size_t)B * pb_time_state_bytes1(beam);
+}
+
+namespace {
+int pb_time_state_launch(const char* what, void* state, void* ws, const int32_t* flags, int B, int beam, int T_cap, void* stream) {
+    if (B <= 0 || beam <= 0 || beam > PB_MAX_BEAM || T_cap <= 0 || (size_t)T_cap * beam + 1 > (size_t)INT_MAX)
+        ASR_FAIL(ASR_EINVAL, "%s: bad shape B=%d beam=%d (<= %d) T_cap=%d", what, B, beam, PB_MAX_BEAM, T_cap);
+    if (((uintptr_t)state % 8) || ((uintptr_t)ws % 8) || ((uintptr_t)flags % 4))
+        ASR_FAIL(ASR_EINVAL, "%s: misaligned pointer (state and workspace: 8 bytes, flags: 4)", what);
+    ctc_prefix_beam_timed_state_init_kernel<<<ceil_div(B, 64), 64, 0, (hipStream_t)stream>>>((char*)state, (int32_t*)ws, flags, B, beam, T_cap);
+    ASR_CHECK_LAUNCH(what);
+    return ASR_OK;
+}
+}  // namespace
+
+extern "C" int asr_ctc_prefix_beam_timed_state_init(void* state, void* ws, int B, int beam, int T_cap, void* stream) {
+    if (!state || !ws) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_timed_state_init: null pointer");
+    return pb_time_state_launch("asr_ctc_prefix_beam_timed_state_init", state, ws, nullptr, B, beam, T_cap, stream);
+}
+
+extern "C" int asr_ctc_prefix_beam_timed_state_reset(void* state, void* ws, const int32_t* flags, int B, int beam, int T_cap, void* stream) {
+    if (!state || !ws || !flags) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_timed_state_reset: null pointer");
+    return pb_time_state_launch("asr_ctc_prefix_beam_timed_state_reset", state, ws, flags, B, beam, T_cap, stream);
+}
+
+extern "C" int asr_ctc_prefix_beam_chunk_timed(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* n_valid, void* state, void* ws,
+                                               size_t ws_bytes, int32_t* out_tok, int32_t* out_len, float* out_score, double* out_vit, int32_t* out_start,
+                                               int32_t* out_end, float* out_mx, float* out_mn, float* out_sm, int32_t* out_stable, int32_t* out_final, int B,
+                                               int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank, void* stream) {
+    if (!vals || !ids || !blank_lp || !n_valid || !state || !ws || !out_tok || !out_len || !out_score || !out_stable || !out_final)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_timed: null pointer");
+    if (const char* why = pb_time_out_check(out_vit, out_start, out_end, out_mx, out_mn, out_sm)) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_timed: %s", why);
+    if (B <= 0 || C < 1 || T_cap < 1 || k <= 0 || beam <= 0 || nbest <= 0 || Lcap <= 0)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_timed: bad shape B=%d C=%d T_cap=%d k=%d beam=%d nbest=%d Lcap=%d", B, C, T_cap, k, beam, nbest, Lcap);
+    if (beam > PB_MAX_BEAM || k > PB_MAX_K || beam * (k + 1) > 64 || nbest > beam)
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_timed: one wave ranks the beam * (k + 1) candidates of a frame: beam * (k + 1) <= 64, beam <= %d, nbest <= beam (beam=%d k=%d nbest=%d)", PB_MAX_BEAM, beam, k, nbest);
+    if ((size_t)T_cap * beam + 1 > (size_t)INT_MAX) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_timed: T_cap * beam + 1 nodes do not fit an int32 (T_cap=%d beam=%d)", T_cap, beam);
+    if (((uintptr_t)state % 8) || (((uintptr_t)vals | (uintptr_t)ids | (uintptr_t)blank_lp | (uintptr_t)n_valid | (uintptr_t)out_tok | (uintptr_t)out_len | (uintptr_t)out_score | (uintptr_t)out_stable | (uintptr_t)out_final) % 4))
+        ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_chunk_timed: misaligned pointer (state: 8 bytes, the others: 4)");
+    if (ws_bytes < asr_ctc_prefix_beam_timed_workspace_bytes(B, T_cap, beam) || ((uintptr_t)ws % 8))
+        ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_prefix_beam_chunk_timed: workspace of %zu bytes needed (got %zu)", asr_ctc_prefix_beam_timed_workspace_bytes(B, T_cap, beam), ws_bytes);
+    PbTimeArgs<true> tx{out_vit, out_start, out_end, out_mx, out_mn, out_sm, out_final};
+    ctc_prefix_beam_chunk_kernel<PB_PLAIN, true><<<B, 64, 0, (hipStream_t)stream>>>(vals, ids, blank_lp, n_valid, (char*)state, (int32_t*)ws, out_tok, out_len, out_score,
+                                                                                 out_stable, C, k, beam, nbest, Lcap, T_cap, blank, PbArgs<PB_PLAIN>{}, tx);
+    ASR_CHECK_LAUNCH("asr_ctc_prefix_beam_chunk_timed");
     return ASR_OK;
 }
 

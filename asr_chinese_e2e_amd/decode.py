@@ -209,7 +209,8 @@ def _check_context(model, context):
     context.check_vocab(model.V)
 
 
-def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on_device=None, context=None, context_ids=None, lm=None):
+def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on_device=None, context=None, context_ids=None, lm=None, beam_times=False,
+                           confidence="post_max"):
     """CTC prefix beam search (Hannun et al. 2014, algorithm 1 without a language model) over the CTC head's posteriors:
     per utterance a list of at most `nbest` dicts {'yseq': [ids], 'score': log p(yseq | x)}, best first.
     Everything runs on the GPU: encoder, CTC projection, per frame the `frame_topk` best classes with their log-softmax values
@@ -224,9 +225,19 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
     'bias'}, ordered by score.  Without a context the call and its result are unchanged.
     lm (an lm.NgramLM): n-gram LM shallow fusion - candidates of a frame are ranked by log p + the hypothesis's accumulated weighted LM
     log-probability (only tokens among the frame's `frame_topk` can be chosen).  Entries are then {'yseq', 'score' = ctc_score +
-    lm_score, 'ctc_score' = log p(yseq | x), 'lm_score' (the end-of-sentence term included)}, ordered by score.  Not with a context."""
+    lm_score, 'ctc_score' = log p(yseq | x), 'lm_score' (the end-of-sentence term included)}, ordered by score.  Not with a context.
+    beam_times=True (the device search only, not with a context or an LM): the search carries the best single alignment of every prefix
+    (asr_ctc_prefix_beam_timed); entries gain 'viterbi_score' (its log-probability) and 'tokens' = per token {"id", "token", "start_frame",
+    "end_frame", "start_s", "end_s", "measures": {post_max, post_min, post_mean}, "confidence"}, times as tokens() of the greedy streams;
+    confidence picks the measure reported as "confidence"."""
     if context is None and context_ids is not None:
         raise ValueError("context_ids needs a context")
+    which = None
+    if beam_times:
+        from .confidence import beam_times_check
+        which = beam_times_check("prefix_beam", model.use_ctc, context, lm, confidence)
+        if on_device is not None and not on_device:
+            raise ValueError("beam_times=True runs the device search only (on_device=False is the host loop without times)")
     if lm is not None:
         _check_lm(model, lm, context)
     eng = model._ensure_engine(input.wave.device)
@@ -248,7 +259,7 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
     vals, ids, blank_lp = K.ctc_frame_topk(logits.reshape(B * T, V), k, BLANK_ID)
     fits = beam_size * (k + 1) <= 64 and beam_size <= 16 and nbest <= beam_size
     if on_device is None:
-        on_device = fits
+        on_device = fits or bool(beam_times)      # times come from the device search alone: a shape beyond it raises below
     if on_device:
         if not fits:
             raise ValueError(f"the device search ranks beam * (frame_topk + 1) <= 64 candidates per frame (beam {beam_size}, frame_topk {k})")
@@ -261,6 +272,14 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
             res = K.ctc_prefix_beam(vals, ids, blank_lp, input.wave_len.to(torch.int32).contiguous(), B, T, beam_size, beam_size, BLANK_ID, lm=lm)
             tok, ln, sc, bias, state = (t.cpu().tolist() for t in res)
             return [lm_entries(lm, tok[b], ln[b], sc[b], bias[b], state[b], nbest) for b in range(B)]
+        if beam_times:
+            from .confidence import beam_tokens
+            res = K.ctc_prefix_beam(vals, ids, blank_lp, input.wave_len.to(torch.int32).contiguous(), B, T, beam_size, nbest, BLANK_ID, times=True)
+            tok, ln, sc, vit, start, end, mx, mn, sm = (t.cpu().numpy() for t in res)
+            d, id2tok = model.frame_seconds(), model.vocab._id2token
+            return [[{"yseq": tok[b, r, :ln[b, r]].tolist(), "score": float(sc[b, r]), "viterbi_score": float(vit[b, r]),
+                      "tokens": beam_tokens(tok[b, r, :ln[b, r]], *(x[b, r, :ln[b, r]] for x in (start, end, mx, mn, sm)), which, id2tok, d)}
+                     for r in range(nbest) if ln[b, r] >= 0] for b in range(B)]
         tok, ln, sc = K.ctc_prefix_beam(vals, ids, blank_lp, input.wave_len.to(torch.int32).contiguous(), B, T, beam_size, nbest, BLANK_ID)
         tok, ln, sc = tok.cpu().tolist(), ln.cpu().tolist(), sc.cpu().tolist()
         return [[{"yseq": tok[b][r][:ln[b][r]], "score": sc[b][r]} for r in range(nbest) if ln[b][r] >= 0] for b in range(B)]

@@ -439,21 +439,32 @@ def _no_lm_with_context(lm, context):
         raise ValueError("an n-gram LM (lm=...) and a hotword context (context=...) cannot be combined: the search runs one of the two")
 
 
-def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max_len=None, context=None, roots=None, lm=None):
+def _no_times_with_bias(times, context, lm):
+    if times and (context is not None or lm is not None):
+        raise ValueError("token times of the prefix beam search (beam_times) are not combined with a hotword context or an n-gram LM: the plain search carries them")
+
+
+def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max_len=None, context=None, roots=None, lm=None, times=False):
     """CTC prefix beam search on the device over the per-frame candidates of ctc_frame_topk (include/asr_hip.h).
     Returns (tokens (B, nbest, Lcap) int32, lengths (B, nbest) int32 with -1 for missing ranks, scores (B, nbest) float32).
     context (a context.ContextGraph): the hotword-biased search (asr_ctc_prefix_beam_ctx) - roots = the root state of each utterance's
     graph (-1: not biased; None: graph 0 for all); the result gains (bias (B, nbest) float64, the raw bias before held(state) is taken
     off, state (B, nbest) int32), and the entries are in the beam's rank order (log p + raw bias).
     lm (an lm.NgramLM): n-gram LM shallow fusion (asr_ctc_prefix_beam_lm); the result gains (bias (B, nbest) float64, the entries' LM bias
-    without the end-of-sentence term, state (B, nbest) int32, their LM state), in the beam's rank order (log p + bias).  Not with a context."""
+    without the end-of-sentence term, state (B, nbest) int32, their LM state), in the beam's rank order (log p + bias).  Not with a context.
+    times=True (the plain search only): asr_ctc_prefix_beam_timed; the result gains (vit (B, nbest) float64, the log-probability of each
+    entry's best single alignment, and that alignment's records per token: start, end (B, nbest, Lcap) int32 frames, mx, mn, sm (B, nbest,
+    Lcap) float32 - the largest, smallest and summed log-posterior over the token's run); positions past an entry's length are zero."""
     _no_lm_with_context(lm, context)
+    _no_times_with_bias(times, context, lm)
     k = vals.shape[1]
     assert vals.shape == (B * T, k) and ids.shape == (B * T, k) and blank_lp.numel() == B * T
     _chk_f32(vals, blank_lp)
     _chk_i32(ids, in_len)
     Lcap = int(T if max_len is None else max_len)
     ws_bytes = lib.asr_ctc_prefix_beam_workspace_bytes(B, T, beam) if lm is None else lib.asr_ctc_prefix_beam_lm_workspace_bytes(B, T, beam)
+    if times:
+        ws_bytes = lib.asr_ctc_prefix_beam_timed_workspace_bytes(B, T, beam)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=vals.device)
     out_tok = torch.zeros(B, nbest, Lcap, dtype=torch.int32, device=vals.device)
     out_len = torch.empty(B, nbest, dtype=torch.int32, device=vals.device)
@@ -475,6 +486,14 @@ def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max
                                          _p(out_score), _p(out_bias), _p(out_state), B, T, k, int(beam), int(nbest), Lcap, int(blank), _stream()),
               "asr_ctc_prefix_beam_lm")
         return out_tok, out_len, out_score, out_bias, out_state
+    if times:
+        out_vit = torch.empty(B, nbest, dtype=torch.float64, device=vals.device)
+        out_start, out_end = (torch.zeros(B, nbest, Lcap, dtype=torch.int32, device=vals.device) for _ in range(2))
+        out_mx, out_mn, out_sm = (torch.zeros(B, nbest, Lcap, dtype=torch.float32, device=vals.device) for _ in range(3))
+        check(lib.asr_ctc_prefix_beam_timed(_p(vals), _p(ids), _p(blank_lp), _p(in_len), _p(ws), ws.numel(), _p(out_tok), _p(out_len), _p(out_score),
+                                            _p(out_vit), _p(out_start), _p(out_end), _p(out_mx), _p(out_mn), _p(out_sm), B, T, k, int(beam), int(nbest),
+                                            Lcap, int(blank), _stream()), "asr_ctc_prefix_beam_timed")
+        return out_tok, out_len, out_score, out_vit, out_start, out_end, out_mx, out_mn, out_sm
     check(lib.asr_ctc_prefix_beam(_p(vals), _p(ids), _p(blank_lp), _p(in_len), _p(ws), ws.numel(), _p(out_tok), _p(out_len), _p(out_score),
                                   B, T, k, int(beam), int(nbest), Lcap, int(blank), _stream()), "asr_ctc_prefix_beam")
     return out_tok, out_len, out_score
@@ -485,21 +504,29 @@ class PrefixBeamState:
     `ws` (the trie, room for T_cap frames per utterance); `frames` = frames consumed per utterance, kept on the host so that a
     chunk past T_cap is refused before any launch.  context: the ContextGraph of a context state (None: a plain state) - a context state
     is larger (bias, context state and root per utterance) and only ever reaches the _ctx entry points.  lm: the NgramLM of an LM state
-    (bias and LM state per entry), which only ever reaches the _lm entry points."""
+    (bias and LM state per entry), which only ever reaches the _lm entry points.  times: a timed state (the entries' best single alignments
+    and a second trie for their records), which only ever reaches the _timed entry points."""
 
-    def __init__(self, state, ws, B, beam, T_cap, context=None, roots=None, lm=None):
+    def __init__(self, state, ws, B, beam, T_cap, context=None, roots=None, lm=None, times=False):
         self.state, self.ws, self.B, self.beam, self.T_cap = state, ws, B, beam, T_cap
         self.frames = [0] * B
-        self.context, self.roots, self.lm = context, roots, lm
+        self.context, self.roots, self.lm, self.times = context, roots, lm, bool(times)
 
 
-def ctc_prefix_beam_state(B, beam, T_cap, device="cuda", context=None, roots=None, lm=None):
+def ctc_prefix_beam_state(B, beam, T_cap, device="cuda", context=None, roots=None, lm=None, times=False):
     """A fresh PrefixBeamState: the empty-prefix beam for B utterances of at most T_cap frames each.  context / roots: a context
-    state for the hotword-biased search (roots as ctc_prefix_beam's).  lm: an LM state, every utterance on the LM's start state."""
+    state for the hotword-biased search (roots as ctc_prefix_beam's).  lm: an LM state, every utterance on the LM's start state.
+    times: a timed state (asr_ctc_prefix_beam_chunk_timed); its workspace holds both tries, 10 words per node."""
     _no_lm_with_context(lm, context)
+    _no_times_with_bias(times, context, lm)
     B, beam, T_cap = int(B), int(beam), int(T_cap)
     if B < 1 or beam < 1 or T_cap < 1:
         raise ValueError(f"ctc_prefix_beam_state: B, beam and T_cap must be >= 1 (got {B}, {beam}, {T_cap})")
+    if times:
+        state = torch.zeros(lib.asr_ctc_prefix_beam_timed_state_bytes(B, beam) // 8, dtype=torch.int64, device=device)      # 8-aligned
+        ws = torch.empty(lib.asr_ctc_prefix_beam_timed_workspace_bytes(B, T_cap, beam), dtype=torch.uint8, device=device)
+        check(lib.asr_ctc_prefix_beam_timed_state_init(_p(state), _p(ws), B, beam, T_cap, _stream()), "asr_ctc_prefix_beam_timed_state_init")
+        return PrefixBeamState(state, ws, B, beam, T_cap, times=True)
     if lm is not None:
         _, tabs = lm.on(device)
         state = torch.zeros(lib.asr_ctc_prefix_beam_lm_state_bytes(B, beam) // 8, dtype=torch.int64, device=device)      # 8-aligned
@@ -543,6 +570,27 @@ def prefix_beam_ctx_unpack(buf, B, nbest, Lcap):
     return buf[n:n + 2 * B * nbest].view(torch.float64).view(B, nbest), buf[n + 2 * B * nbest:].view(B, nbest)
 
 
+def prefix_beam_times_words(B, nbest, Lcap):
+    """int32 words of a timed state's packed result: the plain B * (nbest * (Lcap + 2) + 1), one pad word if that is odd (the fp64 vit is
+    8-aligned), then vit (2 words per entry), start, end, mx, mn, sm (Lcap words per entry each) and final (one word per utterance)."""
+    n = B * (nbest * (Lcap + 2) + 1)
+    return n + (n & 1) + B * nbest * (2 + 5 * Lcap) + B
+
+
+def prefix_beam_times_unpack(buf, B, nbest, Lcap):
+    """(vit (B, nbest) float64, start, end (B, nbest, Lcap) int32, mx, mn, sm (B, nbest, Lcap) float32, final (B) int32) as views of a timed
+    state's packed result of prefix_beam_times_words(B, nbest, Lcap) words; its first B * (nbest * (Lcap + 2) + 1) words are prefix_beam_unpack's."""
+    n = B * (nbest * (Lcap + 2) + 1)
+    n += n & 1
+    assert buf.dtype == torch.int32 and buf.numel() == prefix_beam_times_words(B, nbest, Lcap) and buf.is_contiguous()
+    e, r = B * nbest, B * nbest * Lcap
+    vit = buf[n:n + 2 * e].view(torch.float64).view(B, nbest)
+    n += 2 * e
+    start, end = buf[n:n + r].view(B, nbest, Lcap), buf[n + r:n + 2 * r].view(B, nbest, Lcap)
+    mx, mn, sm = (buf[n + i * r:n + (i + 1) * r].view(torch.float32).view(B, nbest, Lcap) for i in (2, 3, 4))
+    return vit, start, end, mx, mn, sm, buf[n + 5 * r:]
+
+
 def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, max_len=None, packed=False, nv_dev=None, extra_words=0):
     """One chunk of the resumable search: vals / ids (B*C, k), blank_lp (B*C) = the chunk's rows of ctc_frame_topk; n_valid = the
     frames of each utterance to consume (a list of B ints in [0, C]).  A chunk that would take an utterance past st.T_cap frames raises
@@ -555,7 +603,10 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
     A context state (st.context): the biased search (asr_ctc_prefix_beam_chunk_ctx); the result gains bias (B, nbest) float64 (raw) and
     state (B, nbest) int32, and the packed buffer grows to prefix_beam_ctx_words (prefix_beam_ctx_unpack reads the two).
     An LM state (st.lm): the search with the n-gram LM (asr_ctc_prefix_beam_chunk_lm); the same two additions, bias without the
-    end-of-sentence term and the LM state."""
+    end-of-sentence term and the LM state.
+    A timed state (st.times): asr_ctc_prefix_beam_chunk_timed; the result gains (vit, start, end, mx, mn, sm) as ctc_prefix_beam(times=True)
+    and final (B) int32 = how many leading records of every list no later frame can change; the packed buffer grows to
+    prefix_beam_times_words (prefix_beam_times_unpack reads the seven)."""
     B, beam, k = st.B, st.beam, vals.shape[1]
     C, nbest = int(C), int(nbest)
     nv = [int(x) for x in n_valid]
@@ -570,6 +621,8 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
     Lcap = int(max(1, max(f + n for f, n in zip(st.frames, nv))) if max_len is None else max_len)
     n_words = B * (nbest * (Lcap + 2) + 1)
     n_all = n_words if st.context is None and st.lm is None else prefix_beam_ctx_words(B, nbest, Lcap)
+    if st.times:
+        n_all = prefix_beam_times_words(B, nbest, Lcap)
     out = torch.zeros(n_all + (int(extra_words) if packed else 0), dtype=torch.int32, device=vals.device)
     out_tok, out_len, out_score, out_stable = prefix_beam_unpack(out[:n_words], B, nbest, Lcap)
     if nv_dev is None:
@@ -594,6 +647,14 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
         for b in range(B):
             st.frames[b] += nv[b]
         return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable, out_bias, out_state)
+    if st.times:
+        tv = prefix_beam_times_unpack(out[:n_all], B, nbest, Lcap)
+        check(lib.asr_ctc_prefix_beam_chunk_timed(_p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(), _p(out_tok), _p(out_len),
+                                                  _p(out_score), *(_p(t) for t in tv[:6]), _p(out_stable), _p(tv[6]), B, C, k, beam, nbest, Lcap, st.T_cap,
+                                                  int(blank), _stream()), "asr_ctc_prefix_beam_chunk_timed")
+        for b in range(B):
+            st.frames[b] += nv[b]
+        return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable) + tv
     check(lib.asr_ctc_prefix_beam_chunk(_p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(), _p(out_tok), _p(out_len),
                                         _p(out_score), _p(out_stable), B, C, k, beam, nbest, Lcap, st.T_cap, int(blank), _stream()),
           "asr_ctc_prefix_beam_chunk")
@@ -630,6 +691,12 @@ def ctc_prefix_beam_state_reset(st, flags, slots=(), roots=None, lm=None):
         return
     if roots is not None:
         raise ValueError("ctc_prefix_beam_state_reset: roots apply to a context state")
+    if st.times:
+        check(lib.asr_ctc_prefix_beam_timed_state_reset(_p(st.state), _p(st.ws), _p(flags), st.B, st.beam, st.T_cap, _stream()),
+              "asr_ctc_prefix_beam_timed_state_reset")
+        for b in slots:
+            st.frames[int(b)] = 0
+        return
     check(lib.asr_ctc_prefix_beam_state_reset(_p(st.state), _p(st.ws), _p(flags), st.B, st.beam, st.T_cap, _stream()), "asr_ctc_prefix_beam_state_reset")
     for b in slots:
         st.frames[int(b)] = 0

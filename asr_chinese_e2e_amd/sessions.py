@@ -23,6 +23,10 @@ timed=True (greedy sessions): the tick runs asr_ctc_frame_stats + asr_session_ct
 asr_session_ctc_step - the same ids and counters, and per slot the runs of the best path that closed in this tick with their frames and
 confidence measures, still in one buffer and one copy; tokens(b) lists them (confidence.TokenLog).  push returns what it returns.
 
+beam_times=True (prefix beam sessions): the tick runs asr_ctc_prefix_beam_chunk_timed on a timed state - the plain search's results and
+each hypothesis' token records in the same buffer; nbest(b) / partial(b) / tokens(b) as StreamingEncoder's.  The reset kernel restarts a
+reopened slot's lists at frame 0; finish, drop and open drop the slot's records on the host.
+
 Out of scope: input rates other than 16 kHz (StreamResampler has no per-slot reset), compaction of idle slots (every tick computes
 slots * C rows), carrying audio across an endpoint, a varying number of slots, capture into a hipGraph."""
 import math
@@ -78,12 +82,18 @@ def endpoint_rule(rules, frame_us, trailing, frames, decoded):
 
 class Sessions:
     def __init__(self, model, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None,
-                 timed=False, confidence="post_max"):
+                 timed=False, confidence="post_max", beam_times=False):
         C, left = model.decoding_chunk_size, model.decoding_left_chunks
         if C <= 0:
             raise ValueError("model.sessions() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
         if source_rate is not None and int(source_rate) != 16000:
             raise ValueError("model.sessions(): only 16 kHz audio (StreamResampler has no per-slot reset yet)")
+        # beam_times=True (prefix beam sessions): every hypothesis' tokens with the frames and confidence of its best single alignment
+        # (asr_ctc_prefix_beam_chunk_timed); tokens(b) lists the best hypothesis', the records no later frame can change flagged final
+        self.beam_times, self.which = bool(beam_times), None
+        if self.beam_times:
+            from .confidence import beam_times_check
+            self.which = beam_times_check(search, model.use_ctc, context, lm, confidence)
         if not model.use_ctc:
             raise RuntimeError("model.sessions() needs a model with the CTC head (config.ctc_weight > 0): ids and endpointing come from it")
         self.model, self.S, self.C, self.left = model, int(slots), int(C), int(left)
@@ -138,6 +148,8 @@ class Sessions:
         self.ctc_state = None                # (slots, 4) int32 {last, trailing, frames, decoded}
         self.beam = None
         self._hyps = None
+        self._times = None                   # beam_times: the last tick's (vit, start, end, mx, mn, sm, final) as host arrays
+        self.has_times = [False] * S         # ... and whether slot b's rows of them belong to its session (dropped by finish / drop / open)
         self.parser, self.frontend = parser, None
 
     # ------------------------------------------------------------------ slot life cycle
@@ -162,6 +174,7 @@ class Sessions:
             self.graph[b] = graph
         self.state[b], self.frames[b], self.clen[b], self.fresh[b] = OPEN, 0, 0, True
         self.trailing[b], self.decoded[b], self.stable[b] = 0, False, 0
+        self.has_times[b] = False
         if self.log is not None:
             self.log.reset(b)
         if self.frontend is not None:
@@ -173,6 +186,7 @@ class Sessions:
         if self.state[b] == FREE:
             raise ValueError(f"drop: slot {b} is free")
         self.state[b], self.frames[b], self.clen[b], self.fresh[b] = FREE, 0, 0, False
+        self.has_times[b] = False
 
     def status(self, b):
         b = self._slot(b)
@@ -262,9 +276,23 @@ class Sessions:
         """timed=True: slot b's tokens so far, each {"id", "token", "start_frame", "end_frame", "start_s", "end_s", "measures",
         "confidence", "final"} (times as ctc_align's).  The run still open is the last entry, final=False: its end and measures may
         still move, the others are settled.  The list of a finished slot stays until the slot is opened again."""
+        if self.beam_times:
+            b = self._slot(b)
+            if not self.has_times[b] or self.fresh[b] or self._hyps[1][b, 0] < 0:
+                return []
+            return self._beam_tokens(b, 0, final=True)
         if self.log is None:
             raise ValueError("tokens() needs model.sessions(..., timed=True)")
         return self.log.tokens(self._slot(b))
+
+    def _beam_tokens(self, b, r, final=False):
+        """beam_times: the tokens of the r-th hypothesis of slot b, from the last tick's records."""
+        from .confidence import beam_tokens
+        tok, ln = self._hyps[0], self._hyps[1]
+        _, start, end, mx, mn, sm, fin = self._times
+        n = max(int(ln[b, r]), 0)
+        return beam_tokens(tok[b, r, :n], start[b, r, :n], end[b, r, :n], mx[b, r, :n], mn[b, r, :n], sm[b, r, :n], self.which, self.model.vocab._id2token,
+                           self.model.frame_seconds(), int(fin[b]) if final else None)
 
     def _tick(self, eng, feats, nv, out):
         S, C, dev = self.S, self.C, feats.device
@@ -318,7 +346,8 @@ class Sessions:
                 if self.search == "prefix_beam":
                     roots = None if self.context is None else self.context.roots(self.graph, S)
                     if self.beam is None:
-                        self.beam = K.ctc_prefix_beam_state(S, self.beam_size, eng.pe.shape[0], dev, context=self.context, roots=roots, lm=self.lm)
+                        self.beam = K.ctc_prefix_beam_state(S, self.beam_size, eng.pe.shape[0], dev, context=self.context, roots=roots, lm=self.lm,
+                                                            times=self.beam_times)
                     elif reset_slots:
                         K.ctc_prefix_beam_state_reset(self.beam, pd[P_RESET], reset_slots, roots=roots)
                     vals, ids, blank_lp = K.ctc_frame_topk(logits, self.frame_topk, BLANK)
@@ -332,6 +361,11 @@ class Sessions:
                     self._hyps = (tok, ln, sc)
                     if self.context is not None or self.lm is not None:
                         self._hyps += tuple(t.numpy() for t in K.prefix_beam_ctx_unpack(host[:n_words], S, self.beam_size, Lcap))
+                    if self.beam_times:
+                        self._times = tuple(t.numpy() for t in K.prefix_beam_times_unpack(host[:n_words], S, self.beam_size, Lcap))
+                        for b in range(S):
+                            if self.state[b] != FREE:
+                                self.has_times[b] = True
                     step = host[n_words:].view(S, 4 + C).tolist()
                     for b in reset_slots:
                         self.stable[b] = 0
@@ -435,7 +469,11 @@ class Sessions:
             tok, ln, sc, bias, state = self._hyps
             return context_entries(self.context, tok[b], ln[b], sc[b], bias[b], state[b])
         tok, ln, sc = self._hyps
-        return [{"yseq": tok[b, r, :ln[b, r]].tolist(), "score": float(sc[b, r])} for r in range(self.beam_size) if ln[b, r] >= 0]
+        out = [{"yseq": tok[b, r, :ln[b, r]].tolist(), "score": float(sc[b, r])} for r in range(self.beam_size) if ln[b, r] >= 0]
+        if self.beam_times and self.has_times[b]:      # ranks without an entry are the last ones: list index = rank
+            for r, h in enumerate(out):
+                h["viterbi_score"], h["tokens"] = float(self._times[0][b, r]), self._beam_tokens(b, r)
+        return out
 
     def partial(self, b):
         """search="prefix_beam": {"ids": slot b's best prefix now, "stable_len": how many of its tokens are final, "score"}."""
@@ -445,6 +483,8 @@ class Sessions:
             out["bias"] = h[0]["bias"] if h else 0.0
         if self.lm is not None:
             out["lm_score"] = h[0]["lm_score"] if h else 0.0
+        if self.beam_times:
+            out["tokens"] = h[0].get("tokens", []) if h else []
         return out
 
     def encoder_output(self, slots):
@@ -478,6 +518,8 @@ class Sessions:
         rescore = kw.get("joint") == "ctc_rescore"
         if rescore:
             self._need_beam("finish(joint='ctc_rescore')")
+        for b in slots:      # beam_times: the records are dropped; what follows is what it is without them
+            self.has_times[b] = False
         res = [{"text": "", "ids": [], "score": float("-inf"), "tokens": [] if timestamps else None} for _ in slots]
         if self.context is not None:
             for r in res:

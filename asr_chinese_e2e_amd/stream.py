@@ -20,6 +20,10 @@ partial() / nbest() give the revisable hypotheses, finish(joint="ctc_rescore") r
 timed=True (greedy only): the frame-wise best path is the alignment, so every emitted token's first and last frame and its confidence
 are known when its run of frames closes; the push then runs the two kernels of a timed sessions tick (asr_ctc_frame_stats,
 asr_session_ctc_step_tokens) and tokens() lists the tokens so far, the run still open last (confidence.TokenLog).
+
+beam_times=True (prefix beam only): the search carries the best single alignment of every prefix (asr_ctc_prefix_beam_chunk_timed), so
+nbest() / partial() also give each hypothesis' tokens with frames, times and confidence, and tokens() the best hypothesis' with the
+records that no later frame can change flagged final; the records travel in the push's one copy.
 """
 import torch
 
@@ -32,7 +36,7 @@ SILENCE_LP = -0.2231435513142097      # log 0.8, the sessions' default blank thr
 
 class StreamingEncoder:
     def __init__(self, model, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None, lm=None,
-                 timed=False, confidence="post_max"):
+                 timed=False, confidence="post_max", beam_times=False):
         C, left = model.decoding_chunk_size, model.decoding_left_chunks
         if C <= 0:
             raise ValueError("model.stream() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
@@ -61,6 +65,12 @@ class StreamingEncoder:
                 raise ValueError("timed=True needs a model with the CTC head (config.ctc_weight > 0): times and confidence come from it")
             from .confidence import TokenLog
             self.log = TokenLog(self.B, confidence, model.vocab._id2token, model.frame_seconds())
+        # beam_times=True (prefix beam streams): every hypothesis' tokens with the frames and confidence of its best single alignment
+        # (asr_ctc_prefix_beam_chunk_timed); tokens() lists the best hypothesis', the records no later frame can change flagged final
+        self.beam_times, self.which = bool(beam_times), None
+        if self.beam_times:
+            from .confidence import beam_times_check
+            self.which = beam_times_check(search, model.use_ctc, context, lm, confidence)
         if search == "prefix_beam":
             if not model.use_ctc:
                 raise RuntimeError("search='prefix_beam' needs a model with the CTC head (config.ctc_weight > 0)")
@@ -89,6 +99,7 @@ class StreamingEncoder:
         self.beam = None                     # K.PrefixBeamState, allocated by the first push for the positional-encoding table's frames
         self.stable = [0] * self.B           # tokens of each utterance handed out by push so far (beam mode)
         self._hyps = None                    # the last push's (tokens, lengths, scores) as host arrays; with a context or an LM also (bias, state)
+        self._times = None                   # beam_times: the last push's (vit, start, end, mx, mn, sm, final) as host arrays; dropped by finish()
         self.parser, self.frontend = parser, None      # the front end is built by the first push_audio
         # source_rate: the rate of the audio push_audio receives; other than 16 kHz it goes through a StreamResampler first (None: 16 kHz)
         self.source_rate, self.resampler = source_rate, None
@@ -177,7 +188,8 @@ class StreamingEncoder:
                 out = [[] for _ in range(B)]
                 if self.search == "prefix_beam":
                     if self.beam is None:      # the trie for every frame push admits: B * 2 * (table * beam + 1) * 4 bytes
-                        self.beam = K.ctc_prefix_beam_state(B, self.beam_size, eng.pe.shape[0], dev, context=self.context, roots=self.roots, lm=self.lm)
+                        self.beam = K.ctc_prefix_beam_state(B, self.beam_size, eng.pe.shape[0], dev, context=self.context, roots=self.roots, lm=self.lm,
+                                                            times=self.beam_times)
                     vals, ids, blank_lp = K.ctc_frame_topk(eng.ctc_lo.fwd(h), self.frame_topk, BLANK)
                     buf, Lcap = K.ctc_prefix_beam_chunk(self.beam, vals, ids, blank_lp, nv, C, self.beam_size, BLANK, packed=True)
                     # one copy: tokens, lengths, scores and stable lengths (with a context also bias and state) travel in one buffer
@@ -188,6 +200,8 @@ class StreamingEncoder:
                     self._hyps = (tok, ln, sc)
                     if self.context is not None or self.lm is not None:
                         self._hyps += tuple(t.numpy() for t in K.prefix_beam_ctx_unpack(host, B, self.beam_size, Lcap))
+                    if self.beam_times:
+                        self._times = tuple(t.numpy() for t in K.prefix_beam_times_unpack(host, B, self.beam_size, Lcap))
                     for b in range(B):      # every entry shares the stable prefix, so rank 0 spells it whatever the order by score
                         out[b] = tok[b, 0, self.stable[b]:int(stable[b])].tolist()
                         self.stable[b] = int(stable[b])
@@ -226,10 +240,25 @@ class StreamingEncoder:
         self.offset += C
         return out
 
+    def _beam_tokens(self, b, r, final=False):
+        """beam_times: the tokens of the r-th hypothesis of utterance b, from the last push's records."""
+        from .confidence import beam_tokens
+        tok, ln = self._hyps[0], self._hyps[1]
+        _, start, end, mx, mn, sm, fin = self._times
+        n = max(int(ln[b, r]), 0)
+        return beam_tokens(tok[b, r, :n], start[b, r, :n], end[b, r, :n], mx[b, r, :n], mn[b, r, :n], sm[b, r, :n], self.which, self.model.vocab._id2token,
+                           self.model.frame_seconds(), int(fin[b]) if final else None)
+
     def tokens(self):
         """timed=True: per utterance its tokens so far, each {"id", "token", "start_frame", "end_frame", "start_s", "end_s", "measures",
         "confidence", "final"} (times as ctc_align's).  The run still open is the last entry, final=False: its end and measures may
-        still move, the others are settled."""
+        still move, the others are settled.
+        beam_times=True: the tokens of the best hypothesis now, over its best single alignment; final=True for the leading records that no
+        later frame can change (their count only grows), the others may still move or be replaced.  Empty after finish()."""
+        if self.beam_times:
+            if self._hyps is None or self._times is None:
+                return [[] for _ in range(self.B)]
+            return [self._beam_tokens(b, 0, final=True) if self._hyps[1][b, 0] >= 0 else [] for b in range(self.B)]
         if self.log is None:
             raise ValueError("tokens() needs model.stream(..., timed=True)")
         return [self.log.tokens(b) for b in range(self.B)]
@@ -295,8 +324,13 @@ class StreamingEncoder:
             tok, ln, sc, bias, state = self._hyps
             return [context_entries(self.context, tok[b], ln[b], sc[b], bias[b], state[b]) for b in range(self.B)]
         tok, ln, sc = self._hyps
-        return [[{"yseq": tok[b, r, :ln[b, r]].tolist(), "score": float(sc[b, r])} for r in range(self.beam_size) if ln[b, r] >= 0]
-                for b in range(self.B)]
+        out = [[{"yseq": tok[b, r, :ln[b, r]].tolist(), "score": float(sc[b, r])} for r in range(self.beam_size) if ln[b, r] >= 0]
+               for b in range(self.B)]
+        if self.beam_times and self._times is not None:      # ranks without an entry are the last ones: list index = rank
+            for b, hyps in enumerate(out):
+                for r, h in enumerate(hyps):
+                    h["viterbi_score"], h["tokens"] = float(self._times[0][b, r]), self._beam_tokens(b, r)
+        return out
 
     def partial(self):
         """search="prefix_beam": per utterance {"ids": the best prefix now (revisable past stable_len), "stable_len": how many of its
@@ -310,6 +344,9 @@ class StreamingEncoder:
         if self.lm is not None:
             for o, h in zip(out, self.nbest()):
                 o["lm_score"] = h[0]["lm_score"] if h else 0.0
+        if self.beam_times:
+            for o, h in zip(out, self.nbest()):
+                o["tokens"] = h[0].get("tokens", []) if h else []
         return out
 
     def _live_only(self, timestamps, search, confidence=None):
@@ -367,6 +404,7 @@ class StreamingEncoder:
         which = measure(kw.get("confidence"))
         if which is not None and not kw.get("timestamps", True):
             raise ValueError("confidence needs timestamps=True: a token's confidence is taken over the frames of its alignment")
+        self._times = None      # beam_times: the records are dropped; what follows is what it is without them
         if kw.get("joint") == "ctc_rescore":
             return self._finish_rescore(ctc_weight=kw.get("ctc_weight"), timestamps=kw.get("timestamps", True), confidence=which)
         all_enc, all_lens = self.encoder_output()

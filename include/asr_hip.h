@@ -436,6 +436,39 @@ int asr_ctc_prefix_beam_chunk_lm(const float* vals, const int32_t* ids, const fl
                                  size_t ws_bytes, const asr_ngram_lm* lm, int32_t* out_tok, int32_t* out_len, float* out_score, double* out_bias,
                                  int32_t* out_state, int32_t* out_stable, int B, int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank,
                                  void* stream);
+/* Token times and confidence for the plain prefix beam search (additive to ABI 10; the definition the tests check against, bit for bit, is
+ * tests/beam_times_ref.py).  Beside pb / pnb every beam entry carries the best single alignment of its prefix that ends in blank and in
+ * non-blank: its fp64 log-probability (every sum is v + (double)lp in that order) and one record per token {start, end, mx, mn, sm} = the
+ * first and last absolute frame of the token's run in that alignment, the largest and smallest log-posterior of the token over the run and
+ * their float32 sum in ascending frame order.  An extension that is merged into an entry of the beam competes with that entry's own repeat:
+ * the larger alignment wins, the repeat on equality.  The records are persistent lists in a second trie behind the B prefix tries: per
+ * utterance (T * beam + 1) nodes of 8 words {parent, depth, start, end, mx, mn, sm, 0}; a kept entry with a finite non-blank alignment takes
+ * one node per frame.  out_tok / out_len / out_score (and out_stable) are bit for bit the plain entry points'.
+ * asr_ctc_prefix_beam_timed: asr_ctc_prefix_beam with, per n-best entry, out_vit (B, nbest) fp64, 8-aligned = the log-probability of the better
+ *   of its two alignments (the blank one on equality; -inf: no entry) and that alignment's records out_start / out_end (B, nbest, Lcap) int32,
+ *   out_mx / out_mn / out_sm (B, nbest, Lcap) float.  Only the first min(out_len, Lcap) positions of a row are written.
+ * asr_ctc_prefix_beam_timed_workspace_bytes: both tries, offline (T frames) and resumable (T = T_cap): B * 10 * (T * beam + 1) * 4 bytes, 8-aligned.
+ * asr_ctc_prefix_beam_timed_state_bytes / _timed_state_init / _timed_state_reset / asr_ctc_prefix_beam_chunk_timed: the resumable form.  The
+ *   state of one utterance is asr_ctc_prefix_beam_chunk's, followed by fp64 vb[beam], vnb[beam], int32 hb[beam], hnb[beam] (list heads) and the
+ *   time trie's nodes in use, padded to 8 bytes.  Reset touches the flagged utterances only; a chunk that consumes nothing changes no byte of
+ *   state or workspace; cutting the frames into chunks changes no bit of any output.  out_final (B) int32: how many leading records of every
+ *   reported list are final - the depth of the lowest common ancestor of the lists without their last record, over every non-empty list of
+ *   a finite alignment in the beam (0 when one of those lists is empty).  It never decreases and final records never change.  A timed state is
+ *   only ever passed to the _timed entry points.
+ *   THE WRAPPERS CHECK pointers, alignment (8 bytes for the state, the workspace and out_vit) and the plain searches' limits; the kernels keep every index
+ *   they form inside the workspace of T_cap frames. */
+size_t asr_ctc_prefix_beam_timed_workspace_bytes(int B, int T, int beam);
+int asr_ctc_prefix_beam_timed(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* in_len, void* ws, size_t ws_bytes,
+                              int32_t* out_tok, int32_t* out_len, float* out_score, double* out_vit, int32_t* out_start, int32_t* out_end,
+                              float* out_mx, float* out_mn, float* out_sm, int B, int T, int k, int beam, int nbest, int Lcap, int blank,
+                              void* stream);
+size_t asr_ctc_prefix_beam_timed_state_bytes(int B, int beam);
+int asr_ctc_prefix_beam_timed_state_init(void* state, void* ws, int B, int beam, int T_cap, void* stream);
+int asr_ctc_prefix_beam_timed_state_reset(void* state, void* ws, const int32_t* flags, int B, int beam, int T_cap, void* stream);
+int asr_ctc_prefix_beam_chunk_timed(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* n_valid, void* state, void* ws,
+                                    size_t ws_bytes, int32_t* out_tok, int32_t* out_len, float* out_score, double* out_vit, int32_t* out_start,
+                                    int32_t* out_end, float* out_mx, float* out_mn, float* out_sm, int32_t* out_stable, int32_t* out_final, int B,
+                                    int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank, void* stream);
 int asr_decode_attn(const void* q, const void* k, const void* v, void* o, const int32_t* k_len,
                     int k_len_uniform, int len_div, int R, int H, int dk, int Tk_cap, int kv_div,
                     int ldq, int ldk, int ldv, int ldo, float scale, int dtype, void* stream);

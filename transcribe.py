@@ -57,6 +57,10 @@ trained with rebuild it.  Inference flags:
   --timed        1 (with --stream=1, --sessions=N included; greedy search only): the per-chunk lines gain "tokens", the characters so
                  far with frames, times and confidence (the measure of --confidence, default post_max); the last one may still be
                  open ("final": false)
+  --beam_times   1 (with --stream=1 --stream_search=prefix_beam, --sessions=N included; not with --context or --lm): the per-chunk lines
+                 gain "tokens", the characters of the best hypothesis now with frames, times and confidence over its best single
+                 alignment (the measure of --confidence: post_max, post_min or post_mean); "final": true marks those that can no
+                 longer change
   --long         1 = the files are whole recordings (a meeting, a lecture) rather than utterances: each is cut at its pauses by the energy
                  VAD on the GPU (Kaldi's compute-vad-energy; model.transcribe_long), its segments are transcribed in time order,
                  --batch_size at a time, by the search the other flags choose, and one JSON line per segment is printed: {"file",
@@ -90,7 +94,7 @@ from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
 from asr_chinese_e2e_amd.data_handler import resample as resample_mod  # noqa: E402
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint", "context", "context_score", "lm", "lm_weight", "lm_ins", "confidence", "timed", "long", "vad_energy_threshold", "vad_energy_mean_scale", "vad_frames_context", "vad_proportion_threshold", "min_silence_s", "min_speech_s", "pad_s", "max_segment_s")
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint", "context", "context_score", "lm", "lm_weight", "lm_ins", "confidence", "timed", "beam_times", "long", "vad_energy_threshold", "vad_energy_mean_scale", "vad_frames_context", "vad_proportion_threshold", "min_silence_s", "min_speech_s", "pad_s", "max_segment_s")
 VAD_FLAGS = {"vad_energy_threshold": "energy_threshold", "vad_energy_mean_scale": "energy_mean_scale", "vad_frames_context": "frames_context",
              "vad_proportion_threshold": "proportion_threshold"}
 SEGMENT_FLAGS = ("min_silence_s", "min_speech_s", "pad_s", "max_segment_s")
@@ -138,7 +142,7 @@ def _chunk_lines(st, files, nv, ids, text, chunk, id2tok, shift_s=0.0):
     stable part."""
     part = st.partial() if st.search == "prefix_beam" else None
     spell = lambda seq: "".join(id2tok[t] for t in seq if part is None or t not in (0, 2, 3))      # noqa: E731  (beam mode: as the final text, without pad / sos / eos)
-    timed = st.tokens() if st.timed else None
+    timed = st.tokens() if st.timed or st.beam_times else None
     for b in range(len(files)):
         if nv[b] <= 0:
             continue
@@ -239,7 +243,7 @@ def stream_sessions(model, parser, files, n_slots, id2tok, block, shift_s, sampl
                     line.update(partial=spell(ss.partial(b)["ids"]), stable=f["text"])
                 if endpoint:
                     line["endpoint"] = ends[b]
-                if ss.timed:
+                if ss.timed or ss.beam_times:
                     line["tokens"] = _shifted(ss.tokens(b), shift_s)
                 f["chunk"] += 1
                 print(json.dumps(line, ensure_ascii=False), flush=True)
@@ -363,6 +367,15 @@ def transcribe(**flags):
         if not stream or beam_stream or not model.use_ctc:
             raise SystemExit("transcribe.py: --timed=1 applies to --stream=1 with the greedy search of a model with the CTC head")
         stream_kw.update(timed=True, confidence=confidence or "post_max")
+    if bool(int(cli.get("beam_times", 0) or 0)):
+        from asr_chinese_e2e_amd.confidence import BEAM_MEASURES
+        if not stream or not beam_stream:
+            raise SystemExit("transcribe.py: --beam_times=1 applies to --stream=1 --stream_search=prefix_beam")
+        if cli.get("context") not in (None, "", False) or cli.get("lm") not in (None, "", False):
+            raise SystemExit("transcribe.py: --beam_times=1 is not combined with --context or --lm: only the plain prefix beam search carries times")
+        if (confidence or "post_max") not in BEAM_MEASURES:
+            raise SystemExit(f"transcribe.py: --beam_times=1 reports {', '.join(BEAM_MEASURES)}: the entropy measures need full posterior rows")
+        stream_kw.update(beam_times=True, confidence=confidence or "post_max")
     context = None
     if cli.get("context") not in (None, "", False):
         from asr_chinese_e2e_amd.context import ContextGraph
