@@ -14,6 +14,9 @@
 //       (4 consecutive rows land on disjoint bank quarters).  The M range is split across
 //       workgroups (grid.y); partial tiles are added with fp32 atomics (full-rate shape: every
 //       wave-instruction adds two 128-byte row segments).
+//   asr_gemm_small_bf16 : the same products for M of a few hundred rows (the decoder), B as (N, K) or as stored (K, N):
+//       64 x 64 tiles, 256-deep k-steps, one wave per SIMD; a ring of four register stages keeps 1024 of K in flight behind
+//       counted waits, bias / ReLU mask are requested before the first operand, the fragments of an MFMA are read four MFMAs ahead.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -450,7 +453,7 @@ static void launch_nt_spec(const bf16_t* a, const bf16_t* w, const float* bias, 
 // The decoder works on B * To ~ 550 rows: a 256 x 128 persistent tile gives such a GEMM 12 workgroups and ~11 us of
 // mostly fixed cost (144 KiB ring prologue, store tail), and the library GEMM its input gradients go to costs the host
 // ~28 us per call (the joint step is host-bound as much as GPU-bound).  This kernel: 64 x 64 tiles (72 .. 216 workgroups),
-// 4 waves (2 x 2, one MFMA 32x32x16 block each), register-staged double-buffered LDS tiles, one barrier per 64-deep k-step.
+// 4 waves (2 x 2, one MFMA 32x32x16 block each), register-staged double-buffered LDS tiles, one barrier per 256-deep k-step.
 //   TB = false: B is (N, K), K-contiguous: C = A B^T            (forward: y = x W^T + bias, optional ReLU)
 //   TB = true : B is (K, N), N-contiguous: C = A B              (input gradient: dx = dy W; W as stored, no transposed copy:
 //               the operand fragments come from transposed LDS reads in natural k order)
@@ -458,7 +461,8 @@ static void launch_nt_spec(const bf16_t* a, const bf16_t* w, const float* bias, 
 constexpr int SM = 64, SS = 72;      // tile edge, LDS row stride (elements) of a 64-column tile
 // k-step: 256.  With 64-deep steps the kernel ran one global-load round trip per step (the next step's loads are only
 // covered by 4 MFMAs): 8 .. 24 round trips, 13 us on average.  A 256-deep step is 2 .. 6 round trips; the step's operands
-// (A 64 x 256, B 64 x 256 or 256 x 64) are 16 16-byte loads per thread, in flight together.
+// (A 64 x 256, B 64 x 256 or 256 x 64) are 16 16-byte loads per thread, in flight together.  gemm_small_kernel keeps four such steps
+// in flight (one round trip for K <= 1024); the form with two stages is kept as gemm_small_d2_kernel for A/B.
 constexpr int SK = 256;
 constexpr int SAS = SK + 8;          // row stride (elements) of a K-contiguous 64 x 256 tile: 528 B, rows 4 banks apart
 constexpr int S_A = SM * SAS;        // elements of the A tile (and of a K-contiguous B tile)
@@ -510,10 +514,14 @@ __device__ __forceinline__ bf16x8 sm_frag_tr(const bf16_t* tile, int col0, int s
 template <bool TB>
 constexpr int small_lds_bytes() { return 2 * (S_A + (TB ? S_BT : S_A)) * 2; }
 
+// Depth-2 form (tuning option "gemm_small_ring" = 0, A/B timing): two register stages, operands that fall outside the matrices skipped by
+// per-lane branches - hipcc then cannot count the loads in flight and waits for ALL of them (vmcnt(0)) before every LDS store, so each
+// k-step past the second is a dependent round trip to memory - and bias / mask loaded in the store tail.  Same tile, same LDS image, same
+// MFMA order as gemm_small_kernel below: the same bits.
 template <bool TB, int ACT>
-__global__ __launch_bounds__(256) void gemm_small_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm, const float* __restrict__ bias,
-                                                         const bf16_t* __restrict__ mask, bf16_t* __restrict__ C, int M, int N, int K, int lda, int ldb,
-                                                         int ldc, int tiles_n) {
+__global__ __launch_bounds__(256) void gemm_small_d2_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm, const float* __restrict__ bias,
+                                                            const bf16_t* __restrict__ mask, bf16_t* __restrict__ C, int M, int N, int K, int lda, int ldb,
+                                                            int ldc, int tiles_n) {
     extern __shared__ __attribute__((aligned(16))) char smem_s[];      // [2 buffers][A | B]
     constexpr int BUF = S_A + (TB ? S_BT : S_A);
     bf16_t* smem = (bf16_t*)smem_s;
@@ -587,6 +595,224 @@ __global__ __launch_bounds__(256) void gemm_small_kernel(const bf16_t* __restric
         }
         if (ACT == ASR_ACT_RELU_MASK) {
             const f32x4 h4 = load4<bf16_t>(mask + (size_t)m * ldc + n);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = h4[e] > 0.f ? o[e] : 0.f;
+        }
+        store4<bf16_t>(C + (size_t)m * ldc + n, o);
+    }
+}
+
+// Register ring of SD stages: SD * 256 of K in flight.  Every load is issued for every lane - a row or column outside the matrix reads the
+// last one inside (such rows of the product are never stored; k past K, possible in the last step only, is zeroed in LDS) - so the number
+// of loads behind any stage is fixed in program order and hipcc waits for that stage alone with a counted vmcnt.  For the same reason no
+// load sits behind a branch that joins the k-loop again: the k-steps run as sr_run<R> for a count R known at compile time (fewer than SD
+// steps, and the last SD .. 2 SD - 1 steps of a longer K) around a loop whose four phases all refill.
+// Registers: 4 stages x (A + B) x 32 = 256 of the 512 a lane has at one wave per SIMD.  What else lives across the k-loop is kept to one
+// offset per address family (sr_fresh below), and the fragment reads of a k-step run at most four MFMAs ahead.
+constexpr int SD = 4;
+template <bool TB, int PF>      // PF: fragment reads run this many MFMAs ahead (sr_mma)
+struct SmallCtx {
+    const bf16_t *A, *Bm;
+    bf16_t* smem;
+    int K, lda, ldb;
+    int a_row, a_max;      // element offsets of the thread's first A row, and of the last row of A
+    int b_row, b_max;      // the same for B (TB: the thread's first k row of step 0; NT: its first n row)
+    int b_col;             // TB: the thread's (clamped) n column
+    int ch8;               // NT / A: the thread's k column inside a step
+    int st_a, st_b;        // LDS element offsets of the thread's first chunk in the A / B tile
+    int fr_a, fr_b;        // LDS element offsets of the lane's fragment rows
+};
+// the value again, through an empty asm the compiler cannot see through: everything computed from it is computed where it is used, instead of
+// being hoisted out of the k-loop into registers that live as long as the loop (16 row offsets per operand, 16 LDS addresses, ...)
+__device__ __forceinline__ int sr_fresh(int x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+// the thread's 8 chunks of a 64 x 256 tile with K contiguous: rows 8 apart from `row` (clamped to `row_max`), columns k0 + ch8 (clamped to K - 8).
+// 32-bit element offsets from a uniform base (the launcher keeps operands of 2^31 elements or more off this kernel)
+__device__ __forceinline__ void sr_load_rows(StageK& st, const bf16_t* __restrict__ base, int ld, int row, int row_max, int k0, int ch8, int K) {
+    const int ro = sr_fresh(row), gc = min(k0 + ch8, K - 8);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) st.v[c] = *(const u32x4*)(base + (unsigned)(min(ro + 8 * c * ld, row_max) + gc));
+}
+// the thread's 8 chunks of a 256 x 64 tile with N contiguous: rows (= k) 32 apart from k0 * ld + `row` (clamped to `row_max`), column `col`
+__device__ __forceinline__ void sr_load_cols(StageK& st, const bf16_t* __restrict__ base, int ld, int row, int row_max, int k0, int col) {
+    const int ro = sr_fresh(row) + k0 * ld;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) st.v[c] = *(const u32x4*)(base + (unsigned)(min(ro + 32 * c * ld, row_max) + col));
+}
+// kleft: K - k0 of the step, < SK in a partial last step only (uniform).  The clamped copies that stand for k >= K are overwritten with zeros by the
+// thread that wrote them (LDS operations of a thread stay in order); a select on the way would be a use of the loaded registers inside a
+// branch, and the compiler sinks loads to such a use - out of the order the ring issues them in
+__device__ __forceinline__ void sr_store_rows(const StageK& st, bf16_t* tile, int off, int kleft, int ch8) {
+    bf16_t* t = tile + sr_fresh(off);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) *(u32x4*)(t + 8 * c * SAS) = st.v[c];
+    if (kleft >= SK) return;
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    if (ch8 >= kleft) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) *(u32x4*)(t + 8 * c * SAS) = z;
+    }
+}
+__device__ __forceinline__ void sr_store_cols(const StageK& st, bf16_t* tile, int off, int kleft, int row) {
+    bf16_t* t = tile + sr_fresh(off);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) *(u32x4*)(t + 32 * c * SS) = st.v[c];
+    if (kleft >= SK) return;
+    const u32x4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+        if (row + 32 * c >= kleft) *(u32x4*)(t + 32 * c * SS) = z;
+}
+template <bool TB, int PF>
+__device__ __forceinline__ void sr_load(const SmallCtx<TB, PF>& c, StageK& a, StageK& b, int kt) {
+    sr_load_rows(a, c.A, c.lda, c.a_row, c.a_max, kt * SK, c.ch8, c.K);
+    if (TB) sr_load_cols(b, c.Bm, c.ldb, c.b_row, c.b_max, kt * SK, c.b_col);      // rows = k, columns = n
+    else sr_load_rows(b, c.Bm, c.ldb, c.b_row, c.b_max, kt * SK, c.ch8, c.K);       // rows = n, columns = k
+    __builtin_amdgcn_sched_barrier(0);      // the stages leave in step order, each one's 16 loads back to back
+}
+template <bool TB, int PF>
+__device__ __forceinline__ void sr_store(const SmallCtx<TB, PF>& c, const StageK& a, const StageK& b, int buf, int kt) {
+    constexpr int BUF = S_A + (TB ? S_BT : S_A);
+    bf16_t* t = c.smem + buf * BUF;
+    const int kleft = c.K - kt * SK;
+    sr_store_rows(a, t, c.st_a, kleft, c.ch8);
+    if (TB) sr_store_cols(b, t + S_A, c.st_b, kleft, threadIdx.x >> 3);
+    else sr_store_rows(b, t + S_A, c.st_b, kleft, c.ch8);
+}
+// the 16 MFMA steps of one k-step, all of them (a partial last step is zero-padded): even steps into acc[0], odd ones into acc[1].
+// The fragments of step ks + SPF are requested before the MFMA of step ks.  Left to itself the scheduler, short of registers beside the ring,
+// reads each pair of fragments into the same registers right before its MFMA - 16 LDS round trips per k-step, ~3 x the MFMA time; the
+// sched_group_barrier sequence pins the order read x SPF, (MFMA, read) x 16.  SPF = 4, and 3 beside the 8 registers of a ReLU mask.
+template <bool TB>
+__device__ __forceinline__ void sr_frag(const bf16_t* As, const bf16_t* Bs, int ks, bf16x8& af, bf16x8& bf) {
+    af = *(const bf16x8*)(As + 16 * ks);
+    if (TB) {      // transposed reads, natural k order (sm_frag_tr)
+        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(Bs + 16 * ks * SS));
+        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(Bs + (16 * ks + 4) * SS));
+        bf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    } else {
+        bf = *(const bf16x8*)(Bs + 16 * ks);
+    }
+}
+template <bool TB, int SPF>
+__device__ __forceinline__ void sr_mma(const SmallCtx<TB, SPF>& c, f32x16 (&acc)[2], int buf) {
+    constexpr int BUF = S_A + (TB ? S_BT : S_A);
+    constexpr int NR = TB ? 3 : 2;      // LDS reads per step
+    const bf16_t* As = c.smem + buf * BUF + sr_fresh(c.fr_a);
+    const bf16_t* Bs = c.smem + buf * BUF + S_A + sr_fresh(c.fr_b);
+    bf16x8 af[SPF], bf[SPF];
+#pragma unroll
+    for (int ks = 0; ks < SPF; ++ks) sr_frag<TB>(As, Bs, ks, af[ks], bf[ks]);
+#pragma unroll
+    for (int ks = 0; ks < SK / 16; ++ks) {
+        acc[ks & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[ks % SPF], af[ks % SPF], acc[ks & 1], 0, 0, 0);
+        if (ks + SPF < SK / 16) sr_frag<TB>(As, Bs, ks + SPF, af[ks % SPF], bf[ks % SPF]);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x100, NR * SPF, 0);
+#pragma unroll
+    for (int ks = 0; ks < SK / 16; ++ks) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        if (ks + SPF < SK / 16) __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);      // the LDS stores of the next step's stage stay behind the MFMAs
+}
+// The last R k-steps, kt .. kt + R - 1 (kt % SD == 0): LDS buffer 0 holds step kt, stage j % SD holds step kt + j for 0 < j < min(R, SD), in flight.
+// FIRST: they are all the steps there are (kt = 0), and their loads and the first LDS image are still to be made.
+template <bool TB, int R, bool FIRST, int PF>
+__device__ __forceinline__ void sr_run(const SmallCtx<TB, PF>& c, StageK (&sa)[SD], StageK (&sb)[SD], f32x16 (&acc)[2], int kt) {
+    if (FIRST) {
+#pragma unroll
+        for (int j = 0; j < (R < SD ? R : SD); ++j) sr_load<TB>(c, sa[j], sb[j], j);
+        sr_store<TB>(c, sa[0], sb[0], 0, 0);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        if (j + SD < R) sr_load<TB>(c, sa[j % SD], sb[j % SD], kt + j + SD);      // stage j went to LDS in the phase before
+        sr_mma<TB>(c, acc, j & 1);
+        if (j + 1 < R) sr_store<TB>(c, sa[(j + 1) % SD], sb[(j + 1) % SD], (j + 1) & 1, kt + j + 1);      // that buffer was last read before the barrier of phase j - 1
+        __syncthreads();
+    }
+}
+
+template <bool TB, int ACT>
+__global__ __launch_bounds__(256) void gemm_small_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm, const float* __restrict__ bias,
+                                                         const bf16_t* __restrict__ mask, bf16_t* __restrict__ C, int M, int N, int K, int lda, int ldb,
+                                                         int ldc, int tiles_n) {
+    extern __shared__ __attribute__((aligned(16))) char smem_s[];      // [2 buffers][A | B]
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tn = blockIdx.x % tiles_n, tm = blockIdx.x / tiles_n;
+    const int m0 = tm * SM, n0 = tn * SM;
+    const int wm = w >> 1, wn = w & 1, r = lane & 31, hh = lane >> 5;
+    const int G = lane >> 4, i16 = lane & 15;      // sm_frag_tr's lane split
+    const SmallCtx<TB, ACT == ASR_ACT_RELU_MASK ? 3 : 4> c = {A, Bm, (bf16_t*)smem_s, K, lda, ldb,
+                            (m0 + (tid >> 5)) * lda, (M - 1) * lda,
+                            TB ? (tid >> 3) * ldb : (n0 + (tid >> 5)) * ldb, TB ? (K - 1) * ldb : (N - 1) * ldb,
+                            min(n0 + (tid & 7) * 8, N - 8), (tid & 31) * 8,
+                            (tid >> 5) * SAS + (tid & 31) * 8, TB ? (tid >> 3) * SS + (tid & 7) * 8 : (tid >> 5) * SAS + (tid & 31) * 8,
+                            (wm * 32 + r) * SAS + 8 * hh,
+                            TB ? (8 * (G >> 1) + (i16 >> 2)) * SS + wn * 32 + 16 * (G & 1) + 4 * (i16 & 3) : (wn * 32 + r) * SAS + 8 * hh};
+    // what the store tail adds and masks with, requested before the first operand load: the tail waits for nothing, and the loads behind
+    // which the ring's waits are counted are the ring's own.  Rows / columns outside C are clamped (and not stored).  The bias of the wave's
+    // 32 columns is wave-uniform: scalar loads into scalar registers, the lane's half picked in the tail.
+    const int m = m0 + wm * 32 + r, nb = n0 + wn * 32 + 4 * hh;
+    f32x8u bs[4];      // [g4]: elements 0 .. 3 for the lanes with hh = 0, 4 .. 7 for hh = 1
+    u32x2 hm[4];
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+        const f32x8u z8 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        bs[g4] = bias ? *(const f32x8u*)(bias + min(n0 + wn * 32 + 8 * g4, N - 8)) : z8;      // N % 8 == 0: a group of 8 columns is inside or outside as a whole
+    }
+    if (ACT == ASR_ACT_RELU_MASK) {
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) hm[g4] = *(const u32x2*)(mask + (size_t)min(m, M - 1) * ldc + min(nb + 8 * g4, N - 4));      // N % 8 == 0
+    }
+    f32x16 acc[2];   // C^T block: n in registers, m on the lane; two accumulators (even / odd k-steps) halve the dependent MFMA chain
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
+    StageK sa[SD], sb[SD];
+    const int nk = (K + SK - 1) / SK;
+    if (nk == 1) sr_run<TB, 1, true>(c, sa, sb, acc, 0);
+    else if (nk == 2) sr_run<TB, 2, true>(c, sa, sb, acc, 0);
+    else if (nk == 3) sr_run<TB, 3, true>(c, sa, sb, acc, 0);
+    else {
+#pragma unroll
+        for (int j = 0; j < SD; ++j) sr_load<TB>(c, sa[j], sb[j], j);
+        sr_store<TB>(c, sa[0], sb[0], 0, 0);
+        __syncthreads();
+        int kt = 0;
+        for (; kt + 2 * SD <= nk; kt += SD) {      // steps kt .. kt + 3, each refilling its stage with the step SD further on
+#pragma unroll
+            for (int j = 0; j < SD; ++j) {
+                sr_load<TB>(c, sa[j], sb[j], kt + j + SD);
+                sr_mma<TB>(c, acc, j & 1);
+                sr_store<TB>(c, sa[(j + 1) % SD], sb[(j + 1) % SD], (j + 1) & 1, kt + j + 1);
+                __syncthreads();
+            }
+        }
+        const int left = nk - kt;      // SD .. 2 SD - 1
+        if (left == 4) sr_run<TB, 4, false>(c, sa, sb, acc, kt);
+        else if (left == 5) sr_run<TB, 5, false>(c, sa, sb, acc, kt);
+        else if (left == 6) sr_run<TB, 6, false>(c, sa, sb, acc, kt);
+        else sr_run<TB, 7, false>(c, sa, sb, acc, kt);
+    }
+    if (m >= M) return;
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+        const int n = nb + 8 * g4;
+        if (n >= N) continue;      // N % 8 == 0: a 4-element piece is inside or outside as a whole
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float x = acc[0][4 * g4 + e] + acc[1][4 * g4 + e] + (hh ? bs[g4][4 + e] : bs[g4][e]);
+            if (ACT == ASR_ACT_RELU) x = fmaxf(x, 0.f);
+            o[e] = x;
+        }
+        if (ACT == ASR_ACT_RELU_MASK) {
+            const float h4[4] = {__uint_as_float(hm[g4][0] << 16), __uint_as_float(hm[g4][0] & 0xffff0000u), __uint_as_float(hm[g4][1] << 16),
+                                 __uint_as_float(hm[g4][1] & 0xffff0000u)};
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = h4[e] > 0.f ? o[e] : 0.f;
         }
@@ -1248,15 +1474,24 @@ extern "C" int asr_gemm_small_bf16(const void* A, const void* Bm, const float* b
     bf16_t* c = (bf16_t*)C;
     static bool attr = false;
     if (!attr) {      // 135 / 141 KiB of dynamic LDS
-        (void)hipFuncSetAttribute((const void*)gemm_small_kernel<true, ASR_ACT_RELU_MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, small_lds_bytes<true>());
-        (void)hipFuncSetAttribute((const void*)gemm_small_kernel<true, ASR_ACT_RELU>, hipFuncAttributeMaxDynamicSharedMemorySize, small_lds_bytes<true>());
-        (void)hipFuncSetAttribute((const void*)gemm_small_kernel<true, ASR_ACT_NONE>, hipFuncAttributeMaxDynamicSharedMemorySize, small_lds_bytes<true>());
-        (void)hipFuncSetAttribute((const void*)gemm_small_kernel<false, ASR_ACT_RELU_MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, small_lds_bytes<false>());
-        (void)hipFuncSetAttribute((const void*)gemm_small_kernel<false, ASR_ACT_RELU>, hipFuncAttributeMaxDynamicSharedMemorySize, small_lds_bytes<false>());
-        (void)hipFuncSetAttribute((const void*)gemm_small_kernel<false, ASR_ACT_NONE>, hipFuncAttributeMaxDynamicSharedMemorySize, small_lds_bytes<false>());
+#define SMALL_ATTR(TB_, ACT_)                                                                                                                       \
+    (void)hipFuncSetAttribute((const void*)gemm_small_kernel<TB_, ACT_>, hipFuncAttributeMaxDynamicSharedMemorySize, small_lds_bytes<TB_>());      \
+    (void)hipFuncSetAttribute((const void*)gemm_small_d2_kernel<TB_, ACT_>, hipFuncAttributeMaxDynamicSharedMemorySize, small_lds_bytes<TB_>())
+        SMALL_ATTR(true, ASR_ACT_RELU_MASK);
+        SMALL_ATTR(true, ASR_ACT_RELU);
+        SMALL_ATTR(true, ASR_ACT_NONE);
+        SMALL_ATTR(false, ASR_ACT_RELU_MASK);
+        SMALL_ATTR(false, ASR_ACT_RELU);
+        SMALL_ATTR(false, ASR_ACT_NONE);
+#undef SMALL_ATTR
         attr = true;
     }
-#define SMALL(TB_, ACT_) asr_launch_armed(gemm_small_kernel<TB_, ACT_>, dim3(grid), dim3(256), small_lds_bytes<TB_>(), st, a, b, bias, mk, c, M, N, K, lda, ldb, ldc, tiles_n)      /* may carry an armed completion event */
+    // the ring kernel addresses its operands with 32-bit element offsets (rows up to one tile past the end enter the clamp)
+    const long long lim = 1ll << 31;
+    const bool ring = asr_option(ASR_OPT_GEMM_SMALL_RING) != 0 && ((long long)M + SM) * lda < lim && ((long long)(trans_b ? K : N) + SK) * ldb < lim;
+#define SMALL(TB_, ACT_)                                                                                                                                       \
+    asr_launch_armed(ring ? gemm_small_kernel<TB_, ACT_> : gemm_small_d2_kernel<TB_, ACT_>, dim3(grid), dim3(256), small_lds_bytes<TB_>(), st, a, b, bias, mk, \
+                     c, M, N, K, lda, ldb, ldc, tiles_n)      /* may carry an armed completion event */
     if (trans_b) {
         if (act == ASR_ACT_RELU_MASK) SMALL(true, ASR_ACT_RELU_MASK);
         else if (act == ASR_ACT_RELU) SMALL(true, ASR_ACT_RELU);

@@ -42,8 +42,11 @@ extern "C" int asr_set_deterministic(int on) {
 // blocks of a wave through ONE pass over the key tiles (sdpa_fwd_pair_bf16_kernel: bit-identical results, measured 33.5 vs 31.6 us - opt-in).
 // "sdpa_small" (default 1): asr_sdpa_fwd / _bwd run bf16 heads of at most 64 queries and 64 keys (causal or unmasked: the decoder's) on the one-wave-per-head
 // kernels (sdpa_fwd_small_bf16_kernel, sdpa_bwd_small_bf16_kernel); 0 = on the one-workgroup-per-head kernels built for 512 keys (A/B timing, parity tests).
-static const char* const g_opt_names[ASR_OPT_COUNT] = {"cu_limit", "tn_multi", "sdpa_pair", "sdpa_small"};
-static int g_opt_val[ASR_OPT_COUNT] = {0, 1, 0, 1};
+// "gemm_small_ring" (default 1): asr_gemm_small_bf16 keeps four 256-deep k-steps of its operands in flight and requests bias / ReLU mask before the first of
+// them (gemm_small_kernel); 0 = two steps, each LDS store waiting for every load issued, bias / mask loaded in the store tail (gemm_small_d2_kernel: the same
+// bits; A/B timing, parity tests).
+static const char* const g_opt_names[ASR_OPT_COUNT] = {"cu_limit", "tn_multi", "sdpa_pair", "sdpa_small", "gemm_small_ring"};
+static int g_opt_val[ASR_OPT_COUNT] = {0, 1, 0, 1, 1};
 static void opt_init() {}
 int asr_option(int key) {
     opt_init();

@@ -88,6 +88,8 @@ int asr_stream_create(int priority, void** out_stream);
  * blocks of a wave through one pass over the key tiles (same bits; measured slower, kept for A/B).
  * "sdpa_small" (initial value 1): asr_sdpa_fwd / asr_sdpa_bwd run bf16 heads of at most 64 queries and 64 keys, causal or unmasked, on the kernels
  * that give a head to ONE wave; 0 = on the one-workgroup-per-head kernels as before (results agree to the order of fp32 sums; kept for A/B).
+ * "gemm_small_ring" (initial value 1): asr_gemm_small_bf16 keeps four 256-deep k-steps of both operands in flight and requests bias and ReLU mask before
+ * the first of them; 0 = two k-steps in flight and bias / mask loaded in the store tail, as before (the same bits; kept for A/B).
  * previous (may be NULL) receives the old value.  Unknown name: ASR_EINVAL. */
 int asr_set_option(const char* name, int value, int* previous);
 int asr_get_deterministic(void);
