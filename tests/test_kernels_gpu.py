@@ -90,8 +90,10 @@ def test_add_ln(K, ws, dtype, d, use_res, use_pe, use_len):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_add_ln_bwd_batched_reduce(K, ws, dtype):
     """Parameter gradients of several LayerNorm sites reduced by ONE asr_add_ln_bwd_reduce_batched launch ==
-    the per-site reduction inside asr_add_ln_bwd: a small site (one workgroup per column group, plain adds), a
-    site with > 1024 partial rows (split + atomic adds), one without a bias gradient, accumulate semantics."""
+    the per-site reduction inside asr_add_ln_bwd: a small site (20 partial rows), a site at the cap of ln_grid() (5600 rows ->
+    512 partial rows), one without a bias gradient, accumulate semantics.  Every site takes the one-workgroup-per-column-group
+    path with plain adds: the split + atomic-add branches of both reductions ask for >= 1024 partial rows, which ln_grid()'s cap
+    of 512 never yields.  Both routes are compared with each other only; tests/test_rowwise_states_gpu.py holds the sums to fp64."""
     d = 512
     sites = [(2, 40, True), (8, 700, True), (3, 37, False)]
     items, want = [], []
