@@ -331,8 +331,10 @@ class _SpeechTransformer(BaseModel):
 
     def stream(self, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None, lm=None,
                timed=False, confidence="post_max", beam_times=False):
-        """A streaming encoder for `batch_size` utterances (stream.StreamingEncoder): push chunks of encoder-rate features, get the
-        greedy CTC ids each chunk adds; finish() gives transcribe()'s result for the same decoding chunk mask.  With an AudioParser
+        """A streaming encoder for `batch_size` utterances in lock-step (stream.StreamingEncoder, a view of sessions.Sessions with every
+        slot opened at once): push chunks of encoder-rate features, get the greedy CTC ids each chunk adds; finish() gives transcribe()'s
+        result for the same decoding chunk mask, frees nothing and may be repeated.  A model without the CTC head streams too: push
+        returns empty lists and finish runs the attention beam.  With an AudioParser
         of norm="global" it also takes audio as it arrives: push_audio(pcm, n_samples, final) - at source_rate, converted to
         16 kHz on the GPU as it arrives (data_handler.resample.StreamResampler); None = 16 kHz, nothing is converted.
         search="prefix_beam" (needs the CTC head): a CTC prefix beam search of `beam_size` over the `frame_topk` best classes of each
@@ -353,8 +355,9 @@ class _SpeechTransformer(BaseModel):
 
     def sessions(self, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None,
                  timed=False, confidence="post_max", beam_times=False):
-        """`slots` independent streaming sessions in one batch (sessions.Sessions): each slot is opened, fed (push / push_audio),
-        closed, finished and reopened at its own pace - open(b), push(feats, n_valid, final), finish(b) - and with endpoint={...} the
+        """`slots` independent streaming sessions in one batch (sessions.Sessions, the owner of the streaming state and tick that
+        stream() views in lock-step; needs the CTC head): each slot is opened, fed (push / push_audio), closed, finished and reopened at
+        its own pace - open(b), push(feats, n_valid, final), results(b) without freeing, finish(b) - and with endpoint={...} the
         CTC endpoint rules report per slot when its speaker has stopped (endpoints()).  parser, search, beam_size, frame_topk as
         stream()'s; only 16 kHz audio.  context (search="prefix_beam" only): hotword biasing, open(b, context=i) picks the session's graph.
         lm (search="prefix_beam" only, not with a context): one n-gram LM for all slots; a reopened slot restarts on its start state.

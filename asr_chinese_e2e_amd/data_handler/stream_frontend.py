@@ -60,8 +60,8 @@ def _pow2_at_least(v):
 
 class StreamingFrontEnd:
     """push_audio(pcm (B, S), n_samples, final) -> list of (feats (B, C, lfr_m * n_mels) in `dtype`, n_valid list of B ints): the encoder
-    chunks that became complete.  The B utterances advance in lock-step (one chunk index for all, as StreamingEncoder's frame offset is
-    shared): a chunk leaves when every utterance that is still open has C rows ready; a closed utterance contributes what it has left
+    chunks that became complete.  The B utterances advance in lock-step (one chunk index for all, as StreamingEncoder.push takes one chunk
+    of every utterance): a chunk leaves when every utterance that is still open has C rows ready; a closed utterance contributes what it has left
     (n_valid < C, then 0).  independent=True (sessions.py) lifts the lock-step: a chunk leaves whenever one utterance has C rows ready or
     is closed with rows left, the others ride along with n_valid 0 and keep their rows - per utterance the chunks of a B = 1 front
     end - and reset(b) starts utterance b again; push_audio then returns (feats, n_valid, done) with done[b] = utterance b's last row

@@ -1,17 +1,34 @@
-"""Independent streaming sessions in one batch (model.sessions(slots)): every slot of the batch holds a session that is opened, fed,
-closed, finished and reopened at its own pace, and CTC endpointing tells when a slot's speaker has stopped.
+"""Streaming state and the one streaming tick of the package: independent sessions in one batch (model.sessions(slots)), and - through
+the lock-step view of stream.py - model.stream(B).  Every slot of the batch holds a session that is opened, fed, closed, finished and
+reopened at its own pace, and CTC endpointing tells when a slot's speaker has stopped.
 
-model.stream(B) runs its B utterances in lock-step: one frame offset, one cadence, one start.  Here each slot b has its own frame
-offset (the positional-encoding row of its next frame), its own key cache length and its own CTC state; a tick (push) computes
-slots * C encoder rows - a slot that sits the tick out (n_valid 0) is computed but nothing of it is kept or changed.  Per push the
-host builds ONE int32 parameter block (PAR_ROWS x slots: positional offset, cache length, n_valid, reset flag, slide source and count,
-key length, output row) and uploads it once; the kernels take its rows as their per-slot arguments (csrc/session.hip,
-asr_add_ln_slots_fwd, asr_ctc_prefix_beam_state_reset).  No row-index tensors, no index_copy_ / index_select, no per-row loops.
+The tick.  Under the chunk mask (asr_hip.h: asr_sdpa_chunk_fwd) every valid query of chunk n sees exactly the valid keys of chunks
+n - left .. n (all of them when left = -1).  So a chunk's self-attention is the plain key-length attention of its C query rows over a
+per-layer K|V cache that holds those keys at rows [0, k_len) of the slot: K.sdpa_fwd with k_len = cached + valid-in-chunk keys.  A tick
+(push) computes slots * C encoder rows: input projection, LayerNorm + positional encoding at each slot's own frame offset, the L encoder
+layers (QKV GEMM, cache append, key-length attention, fc, LayerNorm, feed-forward), the append of the output rows to the slot's rows of
+self.enc, then the CTC head and its tail (greedy step, timed step or prefix beam chunk) with one copy to the host.  A slot that sits the
+tick out (n_valid 0) is computed but nothing of it is kept or changed.
+
+Capacities.  The cache is one contiguous window per slot.  left >= 0: left * C + C rows and two buffers; before a chunk for a
+window that holds more than left * C keys, each slot's last left * C keys are copied down into the other buffer (asr_slot_rows_slide,
+ping-pong) - a ring buffer would leave the stale rows of a partial last chunk visible, as the attention masks a key PREFIX only.
+left = -1: one buffer of max(4 C, need) rows that doubles, at most to the positional-encoding table; a session that would pass the
+table is refused.  The output rows double from 8 C rows in the same way.  The capacity is the Tk of the attention launch, so it
+depends on the schedule only through the longest window.
+
+Parameters.  Each slot b has its own frame offset (the positional-encoding row of its next frame), its own key cache length and its own
+CTC state.  Per push the host builds ONE int32 parameter block (PAR_ROWS x slots: positional offset, cache length, n_valid, reset flag,
+slide source and count, key length, output row) and uploads it once; the kernels take its rows as their per-slot arguments
+(csrc/session.hip, asr_add_ln_slots_fwd, asr_ctc_prefix_beam_state_reset).  No row-index tensors, no per-row loops on the host.
 
 Why a slot's bits do not depend on its neighbours: the GEMMs, LayerNorm and the CTC head work row by row, attention works per
-(slot, head) over that slot's key prefix, and every session kernel reads only its own slot's parameters.  The cache capacity (the Tk of
-the attention launch) follows StreamingEncoder._grow's rule, so a slot fed what an utterance of model.stream(slots) is fed gets that
-utterance's bits (tests/test_sessions_gpu.py).
+(slot, head) over that slot's key prefix, and every session kernel reads only its own slot's parameters (tests/test_sessions_gpu.py).
+
+search="prefix_beam" (the first pass of the U2 recipe): instead of the argmax, each tick feeds the chunk's per-frame candidates
+(asr_ctc_frame_topk) to the resumable CTC prefix beam search (asr_ctc_prefix_beam_chunk), whose beam lives on the device between
+ticks.  push returns the tokens by which the STABLE prefix grew - the prefix all beam entries share, which no later chunk can retract;
+partial(b) / nbest(b) give the revisable hypotheses, results / finish(joint="ctc_rescore") re-rank the n-best with the decoder.
 
 Endpointing (endpoint=dict(...)): WeNet's CTC endpoint rules, evaluated per slot from counters the device keeps
 (asr_session_ctc_step): a frame is silent iff p(blank) > blank_threshold; trailing silence = the current run of silent frames; length
@@ -19,16 +36,21 @@ Endpointing (endpoint=dict(...)): WeNet's CTC endpoint rules, evaluated per slot
 (must_have_decoded, min_trailing_silence_ms, min_length_ms) fires when all three hold; endpoints() reports the first that does.
 Endpointing only reports: the caller closes the slot (final), finishes it and opens it again for what follows.
 
-timed=True (greedy sessions): the tick runs asr_ctc_frame_stats + asr_session_ctc_step_tokens instead of asr_ctc_frame_best_blank +
-asr_session_ctc_step - the same ids and counters, and per slot the runs of the best path that closed in this tick with their frames and
-confidence measures, still in one buffer and one copy; tokens(b) lists them (confidence.TokenLog).  push returns what it returns.
+timed=True (greedy sessions): the frame-wise best path is the alignment, so every emitted token's first and last frame and its
+confidence are known when its run of frames closes.  The tick runs asr_ctc_frame_stats + asr_session_ctc_step_tokens instead of
+asr_ctc_frame_best_blank + asr_session_ctc_step - the same ids and counters, and per slot the runs of the best path that closed in this
+tick with their frames and confidence measures, still in one buffer and one copy; tokens(b) lists them, the run still open last
+(confidence.TokenLog).  push returns what it returns.
 
-beam_times=True (prefix beam sessions): the tick runs asr_ctc_prefix_beam_chunk_timed on a timed state - the plain search's results and
-each hypothesis' token records in the same buffer; nbest(b) / partial(b) / tokens(b) as StreamingEncoder's.  The reset kernel restarts a
-reopened slot's lists at frame 0; finish, drop and open drop the slot's records on the host.
+beam_times=True (prefix beam sessions): the search carries the best single alignment of every prefix (asr_ctc_prefix_beam_chunk_timed
+on a timed state) - the plain search's results and each hypothesis' token records in the same buffer; nbest(b) / partial(b) also give
+each hypothesis' tokens with frames, times and confidence, and tokens(b) the best hypothesis' with the records that no later frame can
+change flagged final.  The reset kernel restarts a reopened slot's lists at frame 0; results, finish, drop and open drop the slot's
+records on the host.
 
-Out of scope: input rates other than 16 kHz (StreamResampler has no per-slot reset), compaction of idle slots (every tick computes
-slots * C rows), carrying audio across an endpoint, a varying number of slots, capture into a hipGraph."""
+Out of scope: input rates other than 16 kHz for sessions (StreamResampler has no per-slot reset; the lock-step view resamples in front
+of its own front end), compaction of idle slots (every tick computes slots * C rows), carrying audio across an endpoint, a varying
+number of slots, capture into a hipGraph."""
 import math
 
 import torch
@@ -82,23 +104,18 @@ def endpoint_rule(rules, frame_us, trailing, frames, decoded):
 
 class Sessions:
     def __init__(self, model, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None,
-                 timed=False, confidence="post_max", beam_times=False):
+                 timed=False, confidence="post_max", beam_times=False, _lockstep=False):
+        """_lockstep: set by stream.StreamingEncoder alone - the messages name model.stream(), and a model without the CTC head is
+        admitted: its tick ends once the encoder rows are stored, push returns empty lists and the results come from the attention beam."""
+        who = "model.stream()" if _lockstep else "model.sessions()"
         C, left = model.decoding_chunk_size, model.decoding_left_chunks
         if C <= 0:
-            raise ValueError("model.sessions() needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
+            raise ValueError(f"{who} needs a decoding chunk: config decoding_chunk_size > 0 (or a static chunk_size)")
         if source_rate is not None and int(source_rate) != 16000:
             raise ValueError("model.sessions(): only 16 kHz audio (StreamResampler has no per-slot reset yet)")
-        # beam_times=True (prefix beam sessions): every hypothesis' tokens with the frames and confidence of its best single alignment
-        # (asr_ctc_prefix_beam_chunk_timed); tokens(b) lists the best hypothesis', the records no later frame can change flagged final
-        self.beam_times, self.which = bool(beam_times), None
-        if self.beam_times:
-            from .confidence import beam_times_check
-            self.which = beam_times_check(search, model.use_ctc, context, lm, confidence)
-        if not model.use_ctc:
-            raise RuntimeError("model.sessions() needs a model with the CTC head (config.ctc_weight > 0): ids and endpointing come from it")
         self.model, self.S, self.C, self.left = model, int(slots), int(C), int(left)
         if self.S < 1:
-            raise ValueError("slots must be >= 1")
+            raise ValueError("batch_size must be >= 1" if _lockstep else "slots must be >= 1")
         if search not in ("greedy", "prefix_beam"):
             raise ValueError(f"search must be 'greedy' or 'prefix_beam' (got {search!r})")
         self.search, self.beam_size, self.frame_topk = search, int(beam_size), int(frame_topk)
@@ -107,8 +124,21 @@ class Sessions:
         if self.timed:
             if search != "greedy":
                 raise ValueError("timed=True needs search='greedy': the frame-wise best path is the alignment there; times for the prefix beam's stable prefix are not supported")
+            if not model.use_ctc:
+                raise ValueError("timed=True needs a model with the CTC head (config.ctc_weight > 0): times and confidence come from it")
             from .confidence import TokenLog
             self.log = TokenLog(self.S, confidence, model.vocab._id2token, model.frame_seconds())
+        # beam_times=True (prefix beam sessions): every hypothesis' tokens with the frames and confidence of its best single alignment
+        # (asr_ctc_prefix_beam_chunk_timed); tokens(b) lists the best hypothesis', the records no later frame can change flagged final
+        self.beam_times, self.which = bool(beam_times), None
+        if self.beam_times:
+            from .confidence import beam_times_check
+            self.which = beam_times_check(search, model.use_ctc, context, lm, confidence)
+        if not model.use_ctc:
+            if search == "prefix_beam":
+                raise RuntimeError("search='prefix_beam' needs a model with the CTC head (config.ctc_weight > 0)")
+            if not _lockstep or endpoint is not None:
+                raise RuntimeError("model.sessions() needs a model with the CTC head (config.ctc_weight > 0): ids and endpointing come from it")
         if search == "prefix_beam":
             k = max(1, min(self.frame_topk, model.V))
             if self.beam_size < 1 or self.beam_size > 16 or self.beam_size * (k + 1) > 64:
@@ -209,7 +239,7 @@ class Sessions:
 
     # ------------------------------------------------------------------ device buffers
     def _grow(self, eng, need, dev):
-        """StreamingEncoder._grow's capacities, so that the attention launches have the lock-step stream's shapes."""
+        """The cache capacity (module docstring): the fixed window's left * C + C rows, or a buffer that doubles up to the table."""
         hd2, L, S = 2 * eng.H * eng.dk, len(eng.enc), self.S
         if self.caches is None:
             if self.left >= 0:
@@ -240,8 +270,8 @@ class Sessions:
     # ------------------------------------------------------------------ one tick
     def push(self, feats, n_valid, final):
         """feats (slots, C, F): one chunk of encoder-rate features per slot; n_valid[b] = C, or 0 (the slot sits this tick out: nothing of
-        it changes), or any value in [0, C] together with final[b], which ends the session's input.  Returns per slot what
-        StreamingEncoder.push returns: the greedy ids the chunk adds (repeats collapsed across chunks), or the growth of the stable
+        it changes), or any value in [0, C] together with final[b], which ends the session's input.  Returns per slot the greedy CTC
+        ids the chunk adds (repeats collapsed across chunks; empty lists for a model without the CTC head), or the growth of the stable
         prefix (search="prefix_beam").  A push that is refused (a free slot with frames, a partial chunk without final, a session that
         would pass the positional table) raises before any launch and leaves every slot as it was."""
         model, S, C = self.model, self.S, self.C
@@ -275,7 +305,9 @@ class Sessions:
     def tokens(self, b):
         """timed=True: slot b's tokens so far, each {"id", "token", "start_frame", "end_frame", "start_s", "end_s", "measures",
         "confidence", "final"} (times as ctc_align's).  The run still open is the last entry, final=False: its end and measures may
-        still move, the others are settled.  The list of a finished slot stays until the slot is opened again."""
+        still move, the others are settled.  The list of a finished slot stays until the slot is opened again.
+        beam_times=True: the tokens of the best hypothesis now, over its best single alignment; final=True for the leading records that no
+        later frame can change (their count only grows), the others may still move or be replaced.  Empty after results() / finish()."""
         if self.beam_times:
             b = self._slot(b)
             if not self.has_times[b] or self.fresh[b] or self._hyps[1][b, 0] < 0:
@@ -310,7 +342,9 @@ class Sessions:
                 c = self.clen[b] = min(c, keep)
             par[P_PE_OFF][b] = self.frames[b] if nv[b] > 0 else 0
             par[P_CLEN][b], par[P_NV][b], par[P_RESET][b] = c, nv[b], int(self.fresh[b])
-            par[P_KLEN][b] = max(c + nv[b], 1)      # at least one key, as StreamingEncoder.push
+            # at least one key: a slot without a frame (idle, or ended with fewer than 400 samples under the Kaldi front end) still sits in
+            # the batch; its rows are not valid and nothing reads them, and a length of 1 keeps zero-key attention off the kernels
+            par[P_KLEN][b] = max(c + nv[b], 1)
             par[P_OUT_ROW][b] = self.frames[b]
         reset_slots = [b for b in range(S) if self.fresh[b]]
         was_training, eng.training = eng.training, False
@@ -325,7 +359,7 @@ class Sessions:
                     self.caches = [self.caches[1], self.caches[0]]
                 caches, cap = self.caches[0], self.cap
                 nv_dev = pd[P_NV]
-                # ---- the encoder chunk body (StreamingEncoder.push's, with per-slot offsets and appends)
+                # ---- the encoder chunk body, with per-slot offsets and appends
                 x = feats.to(eng.dtype).contiguous().reshape(S * C, -1)
                 e0 = eng.lin_in.fwd(x)
                 h = K.add_ln_slots_fwd(e0, eng.ln_in.g, eng.ln_in.b, eng.pe, pd[P_PE_OFF], par[P_PE_OFF], nv_dev, S, C)
@@ -339,65 +373,73 @@ class Sessions:
                     h1, _, _ = K.add_ln_fwd(a, h, mha.ln.g, mha.ln.b, None, nv_dev, S, C, xhat=a)
                     h, _ = eng._ffn_block_fwd(ffn, h1, S, C, nv_dev, site=0)
                 K.slot_rows_put(h, self.enc, pd[P_OUT_ROW], nv_dev, C)
-                # ---- CTC: ids, counters; one copy to the host
-                if self.ctc_state is None:
-                    self.ctc_state = torch.zeros(S, 4, dtype=torch.int32, device=dev)
-                logits = eng.ctc_lo.fwd(h)
-                if self.search == "prefix_beam":
-                    roots = None if self.context is None else self.context.roots(self.graph, S)
-                    if self.beam is None:
-                        self.beam = K.ctc_prefix_beam_state(S, self.beam_size, eng.pe.shape[0], dev, context=self.context, roots=roots, lm=self.lm,
-                                                            times=self.beam_times)
-                    elif reset_slots:
-                        K.ctc_prefix_beam_state_reset(self.beam, pd[P_RESET], reset_slots, roots=roots)
-                    vals, ids, blank_lp = K.ctc_frame_topk(logits, self.frame_topk, BLANK)
-                    buf, Lcap = K.ctc_prefix_beam_chunk(self.beam, vals, ids, blank_lp, nv, C, self.beam_size, BLANK, packed=True, nv_dev=nv_dev,
-                                                        extra_words=S * (4 + C))
-                    n_words = buf.numel() - S * (4 + C)      # the search's words (with a context: bias and state included)
-                    K.session_ctc_step(None, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK, out=buf[n_words:].view(S, 4 + C))
-                    host = buf.cpu()
-                    n_plain = S * (self.beam_size * (Lcap + 2) + 1)
-                    tok, ln, sc, stable = (t.numpy() for t in K.prefix_beam_unpack(host[:n_plain], S, self.beam_size, Lcap))
-                    self._hyps = (tok, ln, sc)
-                    if self.context is not None or self.lm is not None:
-                        self._hyps += tuple(t.numpy() for t in K.prefix_beam_ctx_unpack(host[:n_words], S, self.beam_size, Lcap))
-                    if self.beam_times:
-                        self._times = tuple(t.numpy() for t in K.prefix_beam_times_unpack(host[:n_words], S, self.beam_size, Lcap))
-                        for b in range(S):
-                            if self.state[b] != FREE:
-                                self.has_times[b] = True
-                    step = host[n_words:].view(S, 4 + C).tolist()
-                    for b in reset_slots:
-                        self.stable[b] = 0
-                    for b in range(S):
-                        if nv[b] > 0:
-                            out[b] = tok[b, 0, self.stable[b]:int(stable[b])].tolist()
-                            self.stable[b] = int(stable[b])
-                elif self.timed:
-                    if self.run_state is None:
-                        self.run_state = torch.zeros(S, K.STEP_TOKENS_REC, dtype=torch.int32, device=dev)
-                    path, best_lp, blank_lp, _, ent = K.ctc_frame_stats(logits.view(S, C, -1), nv_dev, BLANK)
-                    buf = K.session_ctc_step_tokens(path, blank_lp, best_lp, ent, nv_dev, pd[P_RESET], self.ctc_state, self.run_state, C, self.silence_lp,
-                                                    BLANK).cpu()
-                    step = buf[:, :4 + C].tolist()
-                    self.log.ingest(buf, C, [b for b in range(S) if nv[b] > 0 or b in reset_slots])
-                else:
-                    path, blank_lp = K.ctc_frame_best_blank(logits.view(S, C, -1), nv_dev, BLANK)
-                    step = K.session_ctc_step(path, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK).cpu().tolist()
-                if self.search != "prefix_beam":
-                    for b in range(S):
-                        if nv[b] > 0:
-                            out[b] = step[b][4:4 + step[b][0]]
-                # this tick's frame-wise log p(blank) (slots * C) f32 and best path (slots, C) int32 (None: beam sessions), on the device: diagnostics
-                self.last_blank_lp, self.last_path = blank_lp, (None if self.search == "prefix_beam" else path)
+                # a model without the CTC head (the lock-step view alone admits one): the tick ends here
+                step = self._ctc_tail(eng, h, pd, nv, reset_slots, out) if self.model.use_ctc else None
         finally:
             eng.training = was_training
         for b in range(S):
             self.fresh[b] = False
-            if nv[b] > 0 or b in reset_slots:
+            if step is not None and (nv[b] > 0 or b in reset_slots):
                 self.trailing[b], self.decoded[b] = step[b][1], bool(step[b][3])
             self.clen[b] += nv[b]
             self.frames[b] += nv[b]
+
+    def _ctc_tail(self, eng, h, pd, nv, reset_slots, out):
+        """The CTC end of a tick over its encoder rows h: the ids (or the stable prefix's growth) of the slots with frames into `out`, the
+        hypotheses and records onto the host in one copy; returns per slot the step words {n_ids, trailing, frames, decoded, ids ...}."""
+        S, C, dev = self.S, self.C, h.device
+        nv_dev = pd[P_NV]
+        if self.ctc_state is None:
+            self.ctc_state = torch.zeros(S, 4, dtype=torch.int32, device=dev)
+        logits = eng.ctc_lo.fwd(h)
+        if self.search == "prefix_beam":
+            roots = None if self.context is None else self.context.roots(self.graph, S)
+            if self.beam is None:
+                self.beam = K.ctc_prefix_beam_state(S, self.beam_size, eng.pe.shape[0], dev, context=self.context, roots=roots, lm=self.lm,
+                                                    times=self.beam_times)
+            elif reset_slots:
+                K.ctc_prefix_beam_state_reset(self.beam, pd[P_RESET], reset_slots, roots=roots)
+            vals, ids, blank_lp = K.ctc_frame_topk(logits, self.frame_topk, BLANK)
+            buf, Lcap = K.ctc_prefix_beam_chunk(self.beam, vals, ids, blank_lp, nv, C, self.beam_size, BLANK, packed=True, nv_dev=nv_dev,
+                                                extra_words=S * (4 + C))
+            n_words = buf.numel() - S * (4 + C)      # the search's words (with a context: bias and state included)
+            K.session_ctc_step(None, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK, out=buf[n_words:].view(S, 4 + C))
+            host = buf.cpu()
+            n_plain = S * (self.beam_size * (Lcap + 2) + 1)
+            tok, ln, sc, stable = (t.numpy() for t in K.prefix_beam_unpack(host[:n_plain], S, self.beam_size, Lcap))
+            self._hyps = (tok, ln, sc)
+            if self.context is not None or self.lm is not None:
+                self._hyps += tuple(t.numpy() for t in K.prefix_beam_ctx_unpack(host[:n_words], S, self.beam_size, Lcap))
+            if self.beam_times:
+                self._times = tuple(t.numpy() for t in K.prefix_beam_times_unpack(host[:n_words], S, self.beam_size, Lcap))
+                for b in range(S):
+                    if self.state[b] != FREE:
+                        self.has_times[b] = True
+            step = host[n_words:].view(S, 4 + C).tolist()
+            for b in reset_slots:
+                self.stable[b] = 0
+            for b in range(S):
+                if nv[b] > 0:
+                    out[b] = tok[b, 0, self.stable[b]:int(stable[b])].tolist()
+                    self.stable[b] = int(stable[b])
+        elif self.timed:
+            if self.run_state is None:
+                self.run_state = torch.zeros(S, K.STEP_TOKENS_REC, dtype=torch.int32, device=dev)
+            path, best_lp, blank_lp, _, ent = K.ctc_frame_stats(logits.view(S, C, -1), nv_dev, BLANK)
+            buf = K.session_ctc_step_tokens(path, blank_lp, best_lp, ent, nv_dev, pd[P_RESET], self.ctc_state, self.run_state, C, self.silence_lp,
+                                            BLANK).cpu()
+            step = buf[:, :4 + C].tolist()
+            self.log.ingest(buf, C, [b for b in range(S) if nv[b] > 0 or b in reset_slots])
+        else:
+            path, blank_lp = K.ctc_frame_best_blank(logits.view(S, C, -1), nv_dev, BLANK)
+            step = K.session_ctc_step(path, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK).cpu().tolist()
+        if self.search != "prefix_beam":
+            for b in range(S):
+                if nv[b] > 0:
+                    out[b] = step[b][4:4 + step[b][0]]
+        # this tick's frame-wise log p(blank) (slots * C) f32 and best path (slots, C) int32 (None: beam sessions), on the device: diagnostics
+        self.last_blank_lp, self.last_path = blank_lp, (None if self.search == "prefix_beam" else path)
+        return step
 
     # ------------------------------------------------------------------ audio in
     def _ensure_frontend(self):
@@ -476,7 +518,9 @@ class Sessions:
         return out
 
     def partial(self, b):
-        """search="prefix_beam": {"ids": slot b's best prefix now, "stable_len": how many of its tokens are final, "score"}."""
+        """search="prefix_beam": {"ids": slot b's best prefix now (revisable past stable_len), "stable_len": how many of its tokens are
+        final (the concatenation of what push returned), "score": its log-probability}; with a context also "bias", with an LM "lm_score"
+        (and the score includes it), with beam_times "tokens"."""
         h = self.nbest(b)
         out = {"ids": h[0]["yseq"] if h else [], "stable_len": self.stable[self._slot(b)], "score": h[0]["score"] if h else float("-inf")}
         if self.context is not None:
@@ -490,6 +534,9 @@ class Sessions:
     def encoder_output(self, slots):
         """(enc (n, T, d), lengths (n,) int32) of the listed slots: T = the longest, rounded up to whole chunks; rows past a slot's
         length are zero."""
+        if self.eng is None:
+            raise ValueError("encoder_output: nothing pushed yet")
+        self._grow_enc(self.eng, self.C, self.eng.pe.device)      # pushes without a single frame so far: one chunk of zero rows
         slots = [self._slot(b) for b in slots]
         lens = [self.frames[b] for b in slots]
         T = min(max(self.C, -(-max(lens) // self.C) * self.C), self.enc.shape[1])
@@ -499,10 +546,24 @@ class Sessions:
         live = (torch.arange(T, device=dev)[None, :] < lens_dev[:, None])[:, :, None]
         return torch.where(live, rows, torch.zeros((), dtype=rows.dtype, device=dev)).contiguous(), lens_dev
 
-    def finish(self, slots, beam_size=5, **kw):
-        """model.transcribe(...)'s result dicts for the session of each listed slot (one slot: one dict), computed from the slot's own
-        streamed encoder rows - the searches StreamingEncoder.finish runs, joint="ctc_rescore" included (search="prefix_beam") - as one
-        batch padded to the longest.  The slots become free."""
+    def _empty_result(self, timestamps, which):
+        """The result dict of a session without a frame: the empty transcript, with the keys the others of its call carry."""
+        r = {"text": "", "ids": [], "score": float("-inf"), "tokens": [] if timestamps else None}
+        if self.context is not None:
+            r["bias"] = 0.0
+        if self.lm is not None:
+            r["lm_score"] = 0.0
+        if which is not None:
+            r["confidence"] = None
+        return r
+
+    def results(self, slots, beam_size=5, **kw):
+        """model.transcribe(...)'s result dicts for the session of each listed slot (one slot: one dict) under the same decoding chunk
+        mask, computed from the slot's own streamed encoder rows (the encoder does not run again) as one batch padded to the longest.
+        kw: transcribe's other arguments (ctc_weight, timestamps, joint, confidence).  joint="ctc_rescore" (search="prefix_beam"): no new
+        search - the decoder re-ranks the streamed prefix beam search's n-best (decode.attention_rescore; a CTC-only model keeps the CTC
+        best), beam_size does not apply.  A session without a frame gets the empty transcript and reaches no search kernel.  The sessions
+        stay as they are, open ones included - only their beam-time records are dropped - so the call may be repeated."""
         single = not isinstance(slots, (list, tuple))
         slots = [self._slot(b) for b in ([slots] if single else slots)]
         if len(set(slots)) != len(slots):
@@ -520,16 +581,7 @@ class Sessions:
             self._need_beam("finish(joint='ctc_rescore')")
         for b in slots:      # beam_times: the records are dropped; what follows is what it is without them
             self.has_times[b] = False
-        res = [{"text": "", "ids": [], "score": float("-inf"), "tokens": [] if timestamps else None} for _ in slots]
-        if self.context is not None:
-            for r in res:
-                r["bias"] = 0.0
-        if self.lm is not None:
-            for r in res:
-                r["lm_score"] = 0.0
-        if which is not None:
-            for r in res:
-                r["confidence"] = None
+        res = [self._empty_result(timestamps, which) for _ in slots]
         live = [i for i, b in enumerate(slots) if self.frames[b] > 0]
         if live:
             rows = [slots[i] for i in live]
@@ -561,6 +613,12 @@ class Sessions:
                     got = model.transcribe(Pack(wave=wave, wave_len=lens), beam_size=beam_size, **kw, **ctx)
             for i, r in zip(live, got):
                 res[i] = r
-        for b in slots:
-            self.state[b], self.frames[b], self.clen[b], self.fresh[b] = FREE, 0, 0, False
         return res[0] if single else res
+
+    def finish(self, slots, beam_size=5, **kw):
+        """results(slots, ...), after which the slots become free."""
+        res = self.results(slots, beam_size=beam_size, **kw)
+        for b in (slots if isinstance(slots, (list, tuple)) else [slots]):
+            b = self._slot(b)
+            self.state[b], self.frames[b], self.clen[b], self.fresh[b] = FREE, 0, 0, False
+        return res

@@ -236,8 +236,10 @@ def test_chunk_at_least_T_reproduces_full_attention(deterministic_mode):
 
 
 # ----------------------------------------------------------------------------------------------- streaming
-def _stream_model(dtype, left, cls_name="TransformerOffical", C=8, dk=16):
-    over = dict(d_model=4 * dk, hidden_size=dk, num_head=4, ff_size=8 * dk, layer_num=2, ctc_weight=0.5 if cls_name == "TransformerOffical" else 1.0)
+def _stream_model(dtype, left, cls_name="TransformerOffical", C=8, dk=16, ctc_weight=None):
+    if ctc_weight is None:
+        ctc_weight = 0.5 if cls_name == "TransformerOffical" else 1.0
+    over = dict(d_model=4 * dk, hidden_size=dk, num_head=4, ff_size=8 * dk, layer_num=2, ctc_weight=ctc_weight)
     if cls_name == "TransformerCTC":
         over["use_decoder"] = False
     cfg, sd, _ = _case(1, 8, 16, 30, 4, over, seed=11)
@@ -333,9 +335,86 @@ def test_streaming_past_the_positional_table_raises():
     model = _stream_model("fp32", -1, "TransformerCTC", C=8)
     st = model.stream(1)
     eng = model._ensure_engine(DEV)
-    st.offset = eng.pe.shape[0] - 4
+    st.core.frames[0] = eng.pe.shape[0] - 4      # the frame counter of slot 0 of the sessions under the lock-step view
     with pytest.raises(ValueError, match="positional-encoding"):
         st.push(torch.zeros(1, 8, 16, device=DEV), [8])
+
+
+def test_attention_only_model_streams_and_finishes_with_the_attention_beam():
+    """A model without the CTC head (ctc_weight = 0): the tick ends once the encoder rows are stored, push has no ids to return, and
+    finish runs the attention beam over the streamed rows.  model.sessions keeps refusing such a model."""
+    from asr_chinese_e2e_amd.Utils import Pack
+    C = 8
+    model = _stream_model("fp32", 1, C=C, ctc_weight=0.0)
+    assert not model.use_ctc
+    torch.manual_seed(6)
+    lens = [3 * C, C + 3]
+    feats = torch.randn(2, 3 * C, 16, device=DEV)
+    wl = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    st = model.stream(2)
+    for c0 in range(0, 3 * C, C):
+        assert st.push(feats[:, c0:c0 + C].contiguous(), [max(0, min(C, l - c0)) for l in lens]) == [[], []]
+    enc, got_lens = st.encoder_output()
+    assert got_lens.tolist() == lens
+    with torch.no_grad():
+        ref = model.forward(Pack(wave=feats, wave_len=wl)).encoder_out
+    for b, l in enumerate(lens):
+        err = float((enc[b, :l] - ref[b, :l]).abs().max())
+        assert err <= 1e-4, (b, err)
+    # timestamps come from the CTC head: without one, transcribe - and so finish - gives results only with timestamps=False
+    want = model.transcribe(Pack(wave=feats, wave_len=wl), beam_size=3, ctc_weight=0.0, timestamps=False)
+    got = st.finish(beam_size=3, ctc_weight=0.0, timestamps=False)
+    assert [g["ids"] for g in got] == [w["ids"] for w in want]
+    with pytest.raises(ValueError, match="timestamps come from the CTC head"):
+        st.finish(beam_size=3, ctc_weight=0.0)
+    with pytest.raises(RuntimeError, match="CTC head"):
+        model.sessions(2)
+    for kw in (dict(timed=True), dict(beam_times=True, search="prefix_beam")):
+        with pytest.raises(ValueError, match="CTC head"):
+            model.stream(2, **kw)
+    with pytest.raises(RuntimeError, match="CTC head"):
+        model.stream(2, search="prefix_beam")
+
+
+def test_finish_does_not_consume_the_stream():
+    """finish() reads: the hypotheses, the encoder rows and a second finish are what they were.  The last utterance ends without a
+    frame: the empty result, the single empty hypothesis, and zero rows like every row past an utterance's length."""
+    C = 8
+    model = _stream_model("fp32", -1, C=C)
+    torch.manual_seed(8)
+    lens = [2 * C + 5, C - 2, 0]
+    feats = torch.randn(3, 3 * C, 16, device=DEV)
+    st = model.stream(3, search="prefix_beam", beam_size=4, frame_topk=6)
+    for c0 in range(0, 3 * C, C):
+        st.push(feats[:, c0:c0 + C].contiguous(), [max(0, min(C, l - c0)) for l in lens])
+    assert st.ended == [True, True, True] and st.valid == lens and st.offset == 3 * C
+    before = st.nbest()
+    first = st.finish(joint="ctc_rescore")
+    assert st.nbest() == before
+    assert st.finish(joint="ctc_rescore") == first
+    assert first[2] == {"text": "", "ids": [], "score": float("-inf"), "tokens": []} and before[2] == [{"yseq": [], "score": 0.0}]
+    assert any(r["ids"] for r in first)
+    enc, got_lens = st.encoder_output()
+    assert got_lens.tolist() == lens and enc.shape[1] == 3 * C
+    for b, l in enumerate(lens):
+        assert not enc[b, l:].any() and (l == 0 or enc[b, :l].any()), b
+
+
+def test_sessions_results_is_finish_without_the_freeing():
+    C = 8
+    model = _stream_model("fp32", -1, C=C)
+    torch.manual_seed(9)
+    feats = torch.zeros(2, 2 * C, 16, device=DEV)
+    feats[0] = torch.randn(2 * C, 16, device=DEV)
+    ss = model.sessions(2)
+    ss.open(0)
+    ss.push(feats[:, :C].contiguous(), [C, 0], [False, False])
+    ss.push(feats[:, C:].contiguous(), [C, 0], [True, False])
+    assert ss.status(0)["state"] == "ended"
+    res = ss.results([0])
+    assert ss.status(0)["state"] == "ended" and ss.status(0)["frames"] == 2 * C
+    assert res == ss.finish([0]) and set(res[0]) >= {"text", "ids", "score", "tokens"}
+    assert ss.status(0)["state"] == "free"
 
 
 def test_static_chunk_graphed_step_replays_the_eager_step(deterministic_mode):

@@ -273,6 +273,10 @@ def test_lockstep_stream_is_deterministic():
 @pytest.mark.parametrize("left", [-1, 0, 2])
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_sessions_in_lockstep_equal_the_stream_bit_for_bit(dtype, left, search):
+    """model.stream is the lock-step view of model.sessions, so both sides run one tick: this pins the view's plumbing - every slot
+    opened at construction, final = n_valid < C, the batch-list forms of nbest / encoder_output, a finish that frees nothing - against
+    sessions driven by hand, no longer one implementation against another.  The independent oracles of the tick are the offline
+    chunk-masked model (tests/test_chunk_gpu.py) and the offline prefix beam search (tests/test_stream_beam_gpu.py)."""
     C = 8
     model = _model(dtype, left)
     lens = [8 * C, 8 * C - 3, 2 * C + 5, C - 2]      # the unlimited cache grows past its first capacity; one ends inside its first chunk
@@ -546,7 +550,8 @@ def test_push_audio_serves_every_slot_at_its_own_pace(frontend):
         assert float((enc[u].float() - e1[0, :int(l1[0])].float()).abs().max()) <= 1e-4, u
         assert ids[u] == want_ids and fins[u]["ids"] == st.finish(beam_size=3)[0]["ids"], u
     assert any(ids.values())
-    # ---- fed in lock-step, everything equals model.stream(slots, parser=...) bit for bit
+    # ---- fed in lock-step, everything equals model.stream(slots, parser=...) bit for bit: one tick under both, so this pins the
+    # lock-step view's plumbing and the two front-end modes (independent or not) against each other
     st = model.stream(S, parser=parser)
     ss = model.sessions(S, parser=parser)
     for b in range(S):
