@@ -28,6 +28,7 @@ REVERB_TILE, REVERB_CHUNK, REVERB_MAX_TAPS = 1024, 256, 8192      # ASR_REVERB_*
 REVERB_FFT_N, REVERB_FFT_MAX_TAPS = 4096, 65536      # ASR_REVERB_FFT_*: transform points (N / 2 new samples per block), tap limit of asr_reverb_fft_fwd
 NOISE_MIX_TILE = 4096      # ASR_NOISE_MIX_TILE: samples per workgroup and energy partial of asr_noise_mix_fwd
 VAD_CTX_MAX = 1024     # ASR_VAD_CTX_MAX: the largest frames_context asr_vad_decide takes
+ALIGN_LONG_MAX_LABELS = 8192      # ASR_ALIGN_LONG_MAX_LABELS: labels per recording of asr_ctc_align_long
 STREAM_OPEN = 0x3fffffff      # ASR_STREAM_OPEN: "length not known yet" in the streaming front end's parameter arrays
 
 P, I, F, Z, U = c_void_p, c_int, c_float, c_size_t, c_uint32
@@ -188,6 +189,8 @@ SIGNATURES = {
     "asr_vad_decide_workspace_bytes": (Z, [I, I]),
     "asr_vad_decide": (I, [P, P, P, P, P, P, I, I, I, P]),
     "asr_segment_gather": (I, [P, I, P, P, P, P, I, I, P]),
+    "asr_ctc_align_long_workspace_bytes": (Z, [I, I, I]),
+    "asr_ctc_align_long": (I, [P] * 10 + [Z, I, I, I, I, I, P]),
 }
 
 

@@ -1540,3 +1540,62 @@ def segment_gather(wav, seg_rec, seg_start, seg_len, Smax, out=None):
     assert tuple(out.shape) == (N, Smax) and out.data_ptr() != wav.data_ptr()
     check(lib.asr_segment_gather(_p(wav), S, _p(dseg[0]), _p(dseg[1]), _p(dseg[2]), _p(out), N, Smax, _stream()), "asr_segment_gather")
     return out
+
+
+def ctc_align_long_workspace_bytes(R, T_total, Lmax):
+    """Bytes of back-pointer workspace ctc_align_long needs for R recordings of T_total frames in all and at most Lmax labels each."""
+    return int(lib.asr_ctc_align_long_workspace_bytes(int(R), int(T_total), int(Lmax)))
+
+
+def ctc_align_long(rows, lse, row_off, labels, lab_off, blank=0, ws=None):
+    """CTC forced alignment of whole recordings in one call (asr_ctc_align_long; the definition is tests/align_long_ref.py, and the kernel
+    agrees with it bit for bit).  rows (sum T, V) f32 / bf16 on the device, dense or rows of a buffer padded to ld >= V elements; lse
+    (sum T) f32 from ctc_frame_stats over the same rows; row_off / lab_off: R + 1 host integers (lists or numpy), recording r owns rows
+    [row_off[r], row_off[r+1]) and labels [lab_off[r], lab_off[r+1]); labels: host integers (sum L).  Everything the kernel would have to
+    trust is checked here, on the host: ascending offsets that end at the tables' sizes, at most ALIGN_LONG_MAX_LABELS labels per recording,
+    labels in [0, V) other than the blank.  Returns device tensors (path (sum T) int32: the token's index within its recording per frame,
+    -1 on blank frames; spans (sum L, 2) int32; tok (sum L, 3) f32 = the sum, the largest and the smallest log posterior over the token's
+    frames; score (R) f64).  An infeasible recording has score -inf, spans -1, tok -inf and a path of -1."""
+    import numpy as np
+    if rows.dim() != 2 or rows.stride(1) != 1:
+        raise ValueError(f"ctc_align_long: rows must be (sum T, V) with unit column stride, got {tuple(rows.shape)} / {rows.stride()}")
+    Tt, V = rows.shape
+    ld = rows.stride(0) if Tt > 1 else V
+    if ld < V:
+        raise ValueError(f"ctc_align_long: row stride {ld} below V = {V}")
+    _chk_f32(lse)
+    if lse.numel() != Tt:
+        raise ValueError(f"ctc_align_long: lse holds {lse.numel()} values for {Tt} rows")
+    ro, lo = np.asarray(row_off, dtype=np.int64).reshape(-1), np.asarray(lab_off, dtype=np.int64).reshape(-1)
+    lab = np.asarray(labels, dtype=np.int64).reshape(-1)
+    R = ro.shape[0] - 1
+    if R < 1 or lo.shape[0] != R + 1:
+        raise ValueError(f"ctc_align_long: row_off holds {ro.shape[0]} and lab_off {lo.shape[0]} entries: R + 1 each, R >= 1")
+    if ro[0] != 0 or lo[0] != 0 or (np.diff(ro) < 0).any() or (np.diff(lo) < 0).any() or ro[-1] != Tt or lo[-1] != lab.shape[0]:
+        raise ValueError(f"ctc_align_long: offsets must ascend from 0 to the {Tt} rows and the {lab.shape[0]} labels (got {ro.tolist()}, {lo.tolist()})")
+    Lmax = int(np.diff(lo).max())
+    if Lmax > _lib.ALIGN_LONG_MAX_LABELS:
+        r = int(np.argmax(np.diff(lo)))
+        raise ValueError(f"ctc_align_long: recording {r} has {Lmax} labels, the limit is {_lib.ALIGN_LONG_MAX_LABELS}")
+    if not 0 <= int(blank) < V:
+        raise ValueError(f"ctc_align_long: blank = {blank} outside [0, {V})")
+    bad = (lab < 0) | (lab >= V) | (lab == int(blank))
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"ctc_align_long: label {i} = {int(lab[i])}: labels are classes in [0, {V}) other than the blank ({int(blank)})")
+    dev = rows.device
+    off = torch.from_numpy(np.concatenate((ro, lo)).astype(np.int32)).to(dev)
+    dlab = torch.from_numpy(lab.astype(np.int32) if lab.shape[0] else np.zeros(1, np.int32)).to(dev)
+    Ls = max(lab.shape[0], 1)
+    path = torch.empty(max(Tt, 1), dtype=torch.int32, device=dev)
+    spans = torch.empty(Ls, 2, dtype=torch.int32, device=dev)
+    tok = torch.empty(Ls, 3, dtype=torch.float32, device=dev)
+    score = torch.empty(R, dtype=torch.float64, device=dev)
+    nbytes = ctc_align_long_workspace_bytes(R, Tt, Lmax)
+    w = ws.get(nbytes) if ws is not None else torch.empty(max(nbytes, 64), dtype=torch.uint8, device=dev)
+    if Tt == 0:      # no row to point at: the kernel reads none
+        rows, lse = torch.zeros(1, V, dtype=rows.dtype, device=dev), torch.zeros(1, dtype=torch.float32, device=dev)
+    timed("ctc_align_long", 0.0, lambda: check(
+        lib.asr_ctc_align_long(_p(rows), _p(lse), _p(off[:R + 1]), _p(dlab), _p(off[R + 1:]), _p(path), _p(spans), _p(tok), _p(score), _p(w), w.numel(),
+                               R, V, ld, _dt(rows), int(blank), _stream()), "asr_ctc_align_long"))
+    return path[:Tt], spans[:lab.shape[0]], tok[:lab.shape[0]], score

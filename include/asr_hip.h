@@ -1088,6 +1088,32 @@ int asr_vad_decide(const float* E, const int32_t* wav_len, const double* params,
 int asr_segment_gather(const float* wav, int S, const int32_t* seg_rec, const int32_t* seg_start, const int32_t* seg_len,
                        float* out, int N, int Smax, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * CTC forced alignment of whole recordings (csrc/align_long.hip).  Additive to ABI 10.  The definition, in float64 and plain numpy, is
+ * tests/align_long_ref.py; the kernel agrees with it bit for bit.
+ * R recordings share one call.  Recording r owns rows [row_off[r], row_off[r+1]) of rows (sum T, ld) `dtype` (f32 / bf16, ld >= V) and of
+ * lse (sum T) f32 (asr_ctc_frame_stats' log-sum-exp of the same rows), and labels [lab_off[r], lab_off[r+1]) of labels (sum L) int32,
+ * classes in [0, V) other than `blank`.  The emission is lp(t, c) = (float)rows[t][c] - lse[t], one f32 subtraction.
+ * States s = 0 .. 2L, blanks at even s, label (s - 1) / 2 at odd s:
+ *   v_0(0) = lp(0, blank), v_0(1) = lp(0, l_0), v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2)) + (double)lp(t, sym(s)) in fp64,
+ *   the s-2 term for odd s >= 3 whose label differs from the one before.  Ties: s before s-1 before s-2; the end 2L before 2L-1.
+ * path (sum T) int32: the index (within the recording) of the token frame t belongs to, -1 on blank frames.
+ * spans (sum L, 2) int32: first and last frame (inclusive, within the recording) of each token.
+ * tok (sum L, 3) f32: over the token's frames in ascending t, the f32 sum from 0.f of lp(t, l_i), its largest and its smallest value.
+ * score (R) f64: v_{T-1} of the end state.  T = 0 is feasible iff L = 0 (score 0).  An infeasible recording has score -inf, spans -1,
+ *   tok -inf and a path of -1.
+ * L <= ASR_ALIGN_LONG_MAX_LABELS per recording (a longer one is reported as infeasible); T is bounded by the workspace alone, which
+ * holds one back-pointer byte per label (rows of L rounded up to 64) and frame: asr_ctc_align_long_workspace_bytes(R, sum T, max L) is
+ * enough for any split of the frames and labels among R recordings; a recording whose rows pass ws_bytes is reported as infeasible.
+ * The offsets are device data: the kernel clamps what it forms from them and from the labels, the caller checks them on the host
+ * (kernels.ctc_align_long).  ws 16-byte aligned.  Four launches (one per workgroup size; a workgroup of another size leaves at once).
+ */
+#define ASR_ALIGN_LONG_MAX_LABELS 8192
+size_t asr_ctc_align_long_workspace_bytes(int R, int T_total, int Lmax);
+int asr_ctc_align_long(const void* rows, const float* lse, const int32_t* row_off, const int32_t* labels, const int32_t* lab_off,
+                       int32_t* path, int32_t* spans, float* tok, double* score, void* ws, size_t ws_bytes, int R, int V, int ld,
+                       int dtype, int blank, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
