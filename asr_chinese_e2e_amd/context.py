@@ -7,7 +7,7 @@ A hypothesis carries (n, bias), starting at (root, 0.0).  Appending token c:
     1. n has a child m on c: bias += w, n = m; a final m without children sends n back to the root (the bonus stays);
     2. otherwise: bias -= held(n), n = root, and rule 1 is tried once from the root.
 (n, bias) is a function of the token string alone, computed by the same fp64 additions on the host (walk) and in the kernels
-(csrc/decode.hip, pb_ctx_advance) - so the two agree bit for bit.  A result reports bias - held(n): an unfinished phrase earns nothing.
+(csrc/prefix_beam.hip, pb_ctx_advance) - so the two agree bit for bit.  A result reports bias - held(n): an unfinished phrase earns nothing.
 
 The tables (all graphs in one object, states numbered graph after graph, breadth first):
     st_off   int32 [S + 1]  arcs of state s = [st_off[s], st_off[s + 1])

@@ -12,6 +12,7 @@ themselves are (token, parent) records per step; the n-best lists are rebuilt on
 following the parents, in the order the reference's lists would have (steps ascending, beam order
 inside a step, stable sort by score).
 """
+import functools
 import math
 import os
 
@@ -165,32 +166,39 @@ def _logadd(a, b):
     return m + math.log(math.exp(a - m) + math.exp(b - m))
 
 
-def context_entries(context, tok, ln, sc, bias, state, nbest=None):
-    """One utterance's result list under hotword biasing from the search's outputs in beam rank order (rows of tokens, lengths with -1
-    for missing ranks, log p, raw bias, context state): bias = raw bias - held(state), score = ctc_score + bias, ordered by score
-    (a stable sort of the rank order), cut to nbest."""
+def _bias_mode(context, lm):
+    """What a biased search adds to an entry, or None without a context and an LM: (the entry's key, the function (state, raw bias) ->
+    the reported term).  A context reports bias - held(state): an unfinished phrase earns nothing; an LM reports lm_score = bias +
+    term(</s> | state) (NgramLM.final)."""
+    if context is not None:
+        return "bias", lambda state, bias: bias - context.held(state)
+    if lm is not None:
+        return "lm_score", lm.final
+    return None
+
+
+def _bias_entries(key, final, tok, ln, sc, bias, state, nbest=None):
+    """One utterance's result list of a biased search from its outputs in beam rank order (rows of tokens, lengths with -1 for missing
+    ranks, log p, raw bias, state): entry[key] = final(state, raw bias), score = ctc_score + entry[key], ordered by score (a stable sort of
+    the rank order), cut to nbest."""
     out = []
     for r in range(len(ln)):
         if ln[r] < 0:
             continue
-        b = float(bias[r]) - context.held(int(state[r]))
-        out.append({"yseq": [int(x) for x in tok[r][:ln[r]]], "score": float(sc[r]) + b, "ctc_score": float(sc[r]), "bias": b})
+        term = final(int(state[r]), float(bias[r]))
+        out.append({"yseq": [int(x) for x in tok[r][:ln[r]]], "score": float(sc[r]) + term, "ctc_score": float(sc[r]), key: term})
     out.sort(key=lambda h: h["score"], reverse=True)
     return out if nbest is None else out[:nbest]
+
+
+def context_entries(context, tok, ln, sc, bias, state, nbest=None):
+    """_bias_entries under hotword biasing: 'bias' = raw bias - held(context state)."""
+    return _bias_entries(*_bias_mode(context, None), tok, ln, sc, bias, state, nbest)
 
 
 def lm_entries(lm, tok, ln, sc, bias, state, nbest=None):
-    """The n-best dicts of one utterance from the LM kernels' outputs over the whole beam (host lists: tokens, lengths with -1 for
-    missing ranks, log p, bias, LM state): lm_score = bias + term(</s> | state) (NgramLM.final), score = ctc_score + lm_score, ordered
-    by score (a stable sort of the rank order), cut to nbest."""
-    out = []
-    for r in range(len(ln)):
-        if ln[r] < 0:
-            continue
-        l = lm.final(int(state[r]), float(bias[r]))
-        out.append({"yseq": [int(x) for x in tok[r][:ln[r]]], "score": float(sc[r]) + l, "ctc_score": float(sc[r]), "lm_score": l})
-    out.sort(key=lambda h: h["score"], reverse=True)
-    return out if nbest is None else out[:nbest]
+    """_bias_entries with an n-gram LM over the LM kernels' outputs: 'lm_score' = bias + the end-of-sentence term."""
+    return _bias_entries(*_bias_mode(None, lm), tok, ln, sc, bias, state, nbest)
 
 
 def _check_lm(model, lm, context=None):
@@ -251,10 +259,12 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
         eng.training = was_training
     logits = out.ctc_logits                                    # (B, T, V)
     B, T, V = logits.shape
+    roots = None
     if context is not None:
         _check_context(model, context)
         graphs = [0] * B if context_ids is None else [int(g) for g in context_ids]
         roots = context.roots(graphs, B)
+    biased = _bias_mode(context, lm)
     k = max(1, min(int(frame_topk), V))
     vals, ids, blank_lp = K.ctc_frame_topk(logits.reshape(B * T, V), k, BLANK_ID)
     fits = beam_size * (k + 1) <= 64 and beam_size <= 16 and nbest <= beam_size
@@ -263,45 +273,33 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
     if on_device:
         if not fits:
             raise ValueError(f"the device search ranks beam * (frame_topk + 1) <= 64 candidates per frame (beam {beam_size}, frame_topk {k})")
-        if context is not None:      # the whole beam comes back: the order by ctc_score + bias - held is settled here, then cut to nbest
-            res = K.ctc_prefix_beam(vals, ids, blank_lp, input.wave_len.to(torch.int32).contiguous(), B, T, beam_size, beam_size, BLANK_ID,
-                                    context=context, roots=roots)
+        in_len = input.wave_len.to(torch.int32).contiguous()
+        if biased is not None:      # the whole beam comes back: the reported term is settled on the host, then the order, then the cut to nbest
+            res = K.ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam_size, beam_size, BLANK_ID, context=context, roots=roots, lm=lm)
             tok, ln, sc, bias, state = (t.cpu().tolist() for t in res)
-            return [context_entries(context, tok[b], ln[b], sc[b], bias[b], state[b], nbest) for b in range(B)]
-        if lm is not None:           # the same: the end-of-sentence term is added on the host, then the order is settled and cut
-            res = K.ctc_prefix_beam(vals, ids, blank_lp, input.wave_len.to(torch.int32).contiguous(), B, T, beam_size, beam_size, BLANK_ID, lm=lm)
-            tok, ln, sc, bias, state = (t.cpu().tolist() for t in res)
-            return [lm_entries(lm, tok[b], ln[b], sc[b], bias[b], state[b], nbest) for b in range(B)]
+            return [_bias_entries(*biased, tok[b], ln[b], sc[b], bias[b], state[b], nbest) for b in range(B)]
         if beam_times:
             from .confidence import beam_tokens
-            res = K.ctc_prefix_beam(vals, ids, blank_lp, input.wave_len.to(torch.int32).contiguous(), B, T, beam_size, nbest, BLANK_ID, times=True)
+            res = K.ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam_size, nbest, BLANK_ID, times=True)
             tok, ln, sc, vit, start, end, mx, mn, sm = (t.cpu().numpy() for t in res)
             d, id2tok = model.frame_seconds(), model.vocab._id2token
             return [[{"yseq": tok[b, r, :ln[b, r]].tolist(), "score": float(sc[b, r]), "viterbi_score": float(vit[b, r]),
                       "tokens": beam_tokens(tok[b, r, :ln[b, r]], *(x[b, r, :ln[b, r]] for x in (start, end, mx, mn, sm)), which, id2tok, d)}
                      for r in range(nbest) if ln[b, r] >= 0] for b in range(B)]
-        tok, ln, sc = K.ctc_prefix_beam(vals, ids, blank_lp, input.wave_len.to(torch.int32).contiguous(), B, T, beam_size, nbest, BLANK_ID)
+        tok, ln, sc = K.ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam_size, nbest, BLANK_ID)
         tok, ln, sc = tok.cpu().tolist(), ln.cpu().tolist(), sc.cpu().tolist()
         return [[{"yseq": tok[b][r][:ln[b][r]], "score": sc[b][r]} for r in range(nbest) if ln[b][r] >= 0] for b in range(B)]
     vals, ids, blank_lp = vals.view(B, T, k).cpu().tolist(), ids.view(B, T, k).cpu().tolist(), blank_lp.view(B, T).cpu().tolist()
     lens = input.wave_len.cpu().tolist()
     results = []
     for b in range(B):
-        if context is not None:      # the same loop; a prefix's (state, bias) is a function of the prefix (ContextGraph.walk)
-            g = graphs[b]
+        if biased is not None:       # the same loop; a prefix's (state, bias) is a function of the prefix (ContextGraph.walk / NgramLM.walk)
+            walk = functools.partial(context.walk, graphs[b]) if context is not None else lm.walk
             walked = {}
 
             def rank(kv):
                 if kv[0] not in walked:
-                    walked[kv[0]] = context.walk(g, kv[0])
-                tot = _logadd(kv[1][0], kv[1][1])
-                return tot + walked[kv[0]][1] if tot != -math.inf else tot
-        elif lm is not None:         # a prefix's (state, bias) is a function of the prefix (NgramLM.walk)
-            walked = {}
-
-            def rank(kv):
-                if kv[0] not in walked:
-                    walked[kv[0]] = lm.walk(kv[0])
+                    walked[kv[0]] = walk(kv[0])
                 tot = _logadd(kv[1][0], kv[1][1])
                 return tot + walked[kv[0]][1] if tot != -math.inf else tot
         else:
@@ -328,25 +326,15 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
                         new[1] = _logadd(new[1], tot + lp)
             ranked = sorted(nxt.items(), key=rank, reverse=True)[:beam_size]
             beam = {p: (v[0], v[1]) for p, v in ranked}
-        if context is not None:
+        if biased is not None:
+            key, final = biased
             ents = []
             for p, v in sorted(beam.items(), key=rank, reverse=True):
                 tot = _logadd(v[0], v[1])
                 if tot == -math.inf:
                     continue
-                st, raw = context.walk(g, p)
-                bias = raw - context.held(st)
-                ents.append({"yseq": list(p), "score": tot + bias, "ctc_score": tot, "bias": bias})
-            results.append(sorted(ents, key=lambda h: h["score"], reverse=True)[:nbest])
-            continue
-        if lm is not None:
-            ents = []
-            for p, v in sorted(beam.items(), key=rank, reverse=True):
-                tot = _logadd(v[0], v[1])
-                if tot == -math.inf:
-                    continue
-                l = lm.final(*lm.walk(p))
-                ents.append({"yseq": list(p), "score": tot + l, "ctc_score": tot, "lm_score": l})
+                x = final(*walk(p))
+                ents.append({"yseq": list(p), "score": tot + x, "ctc_score": tot, key: x})
             results.append(sorted(ents, key=lambda h: h["score"], reverse=True)[:nbest])
             continue
         final = sorted(((p, _logadd(v[0], v[1])) for p, v in beam.items()), key=lambda kv: kv[1], reverse=True)[:nbest]
@@ -455,19 +443,13 @@ def attention_rescore(model, enc, wave_len, nbest_lists, ctc_weight):
         cands = []
         for j, h in enumerate(nbest_lists[b]):
             a = att[b * n + j] if fits[b][j] else -math.inf
-            if "bias" in h:
-                ctc, bias = float(h["ctc_score"]), float(h["bias"])
-                sc = lam * (ctc + bias) + (1.0 - lam) * a if a != -math.inf else -math.inf
-                cands.append(dict(yseq=list(seqs[b][j]), score=sc, att_score=a, ctc_score=ctc, bias=bias))
-                continue
-            if "lm_score" in h:
-                ctc, l = float(h["ctc_score"]), float(h["lm_score"])
-                sc = lam * (ctc + l) + (1.0 - lam) * a if a != -math.inf else -math.inf
-                cands.append(dict(yseq=list(seqs[b][j]), score=sc, att_score=a, ctc_score=ctc, lm_score=l))
-                continue
-            ctc = float(h["score"])
-            sc = lam * ctc + (1.0 - lam) * a if a != -math.inf else -math.inf
-            cands.append(dict(yseq=list(seqs[b][j]), score=sc, att_score=a, ctc_score=ctc))
+            key = "bias" if "bias" in h else "lm_score" if "lm_score" in h else None      # a biased first pass: its term joins the CTC score
+            ctc = float(h["score"] if key is None else h["ctc_score"])
+            first = ctc if key is None else ctc + float(h[key])
+            cand = dict(yseq=list(seqs[b][j]), score=lam * first + (1.0 - lam) * a if a != -math.inf else -math.inf, att_score=a, ctc_score=ctc)
+            if key is not None:
+                cand[key] = float(h[key])
+            cands.append(cand)
         out.append(sorted(cands, key=lambda c: c["score"], reverse=True))
     return out
 

@@ -444,6 +444,80 @@ def _no_times_with_bias(times, context, lm):
         raise ValueError("token times of the prefix beam search (beam_times) are not combined with a hotword context or an n-gram LM: the plain search carries them")
 
 
+# The four modes of the CTC prefix beam search (csrc/prefix_beam.hip), a row each: the suffix of its entry points (asr_ctc_prefix_beam<sfx>,
+# asr_ctc_prefix_beam_chunk<sfx>, asr_ctc_prefix_beam<sfx>_state_init / _reset), its size queries (offline workspace, resumable workspace,
+# state) and the outputs it adds to the plain search's as (name, dtype, kind) in the order of the packed result.
+_PB_ENTRY, _PB_TOKEN, _PB_UTT = "entry", "token", "utterance"      # an output's shape: (B, nbest), (B, nbest, Lcap), (B)
+_PB_PLAIN_OUT = (("tok", torch.int32, _PB_TOKEN), ("len", torch.int32, _PB_ENTRY), ("score", torch.float32, _PB_ENTRY), ("stable", torch.int32, _PB_UTT))
+_PB_BIAS_OUT = (("bias", torch.float64, _PB_ENTRY), ("state", torch.int32, _PB_ENTRY))
+_PB_TIMES_OUT = (("vit", torch.float64, _PB_ENTRY), ("start", torch.int32, _PB_TOKEN), ("end", torch.int32, _PB_TOKEN), ("mx", torch.float32, _PB_TOKEN),
+                 ("mn", torch.float32, _PB_TOKEN), ("sm", torch.float32, _PB_TOKEN), ("final", torch.int32, _PB_UTT))
+_PB_MODES = {
+    "plain": ("", lib.asr_ctc_prefix_beam_workspace_bytes, lib.asr_ctc_prefix_beam_stream_workspace_bytes, lib.asr_ctc_prefix_beam_state_bytes, ()),
+    "ctx": ("_ctx", lib.asr_ctc_prefix_beam_workspace_bytes, lib.asr_ctc_prefix_beam_stream_workspace_bytes, lib.asr_ctc_prefix_beam_ctx_state_bytes, _PB_BIAS_OUT),
+    "lm": ("_lm", lib.asr_ctc_prefix_beam_lm_workspace_bytes, lib.asr_ctc_prefix_beam_lm_workspace_bytes, lib.asr_ctc_prefix_beam_lm_state_bytes, _PB_BIAS_OUT),
+    "timed": ("_timed", lib.asr_ctc_prefix_beam_timed_workspace_bytes, lib.asr_ctc_prefix_beam_timed_workspace_bytes, lib.asr_ctc_prefix_beam_timed_state_bytes,
+              _PB_TIMES_OUT),
+}
+
+
+def _pb_mode(context=None, lm=None, times=False):
+    """The row of _PB_MODES a search with these options runs."""
+    _no_lm_with_context(lm, context)
+    _no_times_with_bias(times, context, lm)
+    return "timed" if times else "lm" if lm is not None else "ctx" if context is not None else "plain"
+
+
+def _pb_tables(mode, context, lm, device):
+    """The mode's table argument, [] or [the address of the ContextGraph's / NgramLM's struct of device tables] (the object keeps the struct)."""
+    src = context if mode == "ctx" else lm if mode == "lm" else None
+    return [] if src is None else [ctypes.addressof(src.on(device)[1])]
+
+
+def _pb_call(name, *args):
+    check(getattr(lib, name)(*args), name)
+
+
+def prefix_beam_layout(B, nbest, Lcap, mode="plain"):
+    """The packed int32 result of ctc_prefix_beam_chunk: ([(name, dtype, kind, shape, first word, words)], words in all).  The plain search's
+    B * (nbest * (Lcap + 2) + 1) words: tok, len, score, stable; behind them the mode's own outputs, after one pad word if that count is odd
+    (the first of them is fp64 and 8-aligned): ctx / lm: bias (2 words per entry), state; timed: vit (2 words per entry), start, end, mx, mn,
+    sm (Lcap words per entry each), final (a word per utterance)."""
+    shapes = {_PB_TOKEN: ((B, nbest, Lcap), B * nbest * Lcap), _PB_ENTRY: ((B, nbest), B * nbest), _PB_UTT: ((B,), B)}
+    fields, n = [], 0
+    for group in (_PB_PLAIN_OUT, _PB_MODES[mode][4]):
+        if group:
+            n += n & 1
+        for name, dtype, kind in group:
+            shape, words = shapes[kind]
+            if dtype == torch.float64:
+                words *= 2
+            fields.append((name, dtype, kind, shape, n, words))
+            n += words
+    return fields, n
+
+
+def _pb_views(buf, fields):
+    """The fields of prefix_beam_layout as views of the int32 buffer that holds them."""
+    out = []
+    for _, dtype, _, shape, first, words in fields:
+        v = buf[first:first + words]
+        if dtype != torch.int32:
+            v = v.view(dtype)
+        out.append(v if len(shape) == 1 else v.view(shape))
+    return tuple(out)
+
+
+def prefix_beam_unpack(buf, B, nbest, Lcap, mode="plain"):
+    """(tokens (B, nbest, Lcap) int32, lengths (B, nbest) int32, scores (B, nbest) f32, stable (B) int32) as views of the int32 buffer of
+    B * (nbest * (Lcap + 2) + 1) words that ctc_prefix_beam_chunk fills (on the device or copied to the host).  mode "ctx" / "lm" / "timed":
+    the buffer of that mode's state (prefix_beam_layout); the mode's outputs follow the four as views too - (bias (B, nbest) float64,
+    state (B, nbest) int32), or (vit (B, nbest) float64, start, end (B, nbest, Lcap) int32, mx, mn, sm (B, nbest, Lcap) float32, final (B) int32)."""
+    fields, n = prefix_beam_layout(B, nbest, Lcap, mode)
+    assert buf.dtype == torch.int32 and buf.numel() == n and buf.is_contiguous()
+    return _pb_views(buf, fields)
+
+
 def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max_len=None, context=None, roots=None, lm=None, times=False):
     """CTC prefix beam search on the device over the per-frame candidates of ctc_frame_topk (include/asr_hip.h).
     Returns (tokens (B, nbest, Lcap) int32, lengths (B, nbest) int32 with -1 for missing ranks, scores (B, nbest) float32).
@@ -455,48 +529,22 @@ def ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam, nbest, blank=0, max
     times=True (the plain search only): asr_ctc_prefix_beam_timed; the result gains (vit (B, nbest) float64, the log-probability of each
     entry's best single alignment, and that alignment's records per token: start, end (B, nbest, Lcap) int32 frames, mx, mn, sm (B, nbest,
     Lcap) float32 - the largest, smallest and summed log-posterior over the token's run); positions past an entry's length are zero."""
-    _no_lm_with_context(lm, context)
-    _no_times_with_bias(times, context, lm)
+    mode = _pb_mode(context, lm, times)
+    sfx, ws_bytes = _PB_MODES[mode][:2]
     k = vals.shape[1]
     assert vals.shape == (B * T, k) and ids.shape == (B * T, k) and blank_lp.numel() == B * T
     _chk_f32(vals, blank_lp)
     _chk_i32(ids, in_len)
     Lcap = int(T if max_len is None else max_len)
-    ws_bytes = lib.asr_ctc_prefix_beam_workspace_bytes(B, T, beam) if lm is None else lib.asr_ctc_prefix_beam_lm_workspace_bytes(B, T, beam)
-    if times:
-        ws_bytes = lib.asr_ctc_prefix_beam_timed_workspace_bytes(B, T, beam)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=vals.device)
-    out_tok = torch.zeros(B, nbest, Lcap, dtype=torch.int32, device=vals.device)
-    out_len = torch.empty(B, nbest, dtype=torch.int32, device=vals.device)
-    out_score = torch.empty(B, nbest, dtype=torch.float32, device=vals.device)
-    if context is not None:
-        _, root_dev = _context_roots(context, roots, B, vals.device)
-        _, tabs = context.on(vals.device)
-        out_bias = torch.empty(B, nbest, dtype=torch.float64, device=vals.device)
-        out_state = torch.empty(B, nbest, dtype=torch.int32, device=vals.device)
-        check(lib.asr_ctc_prefix_beam_ctx(_p(vals), _p(ids), _p(blank_lp), _p(in_len), _p(root_dev), ctypes.addressof(tabs), _p(ws), ws.numel(),
-                                          _p(out_tok), _p(out_len), _p(out_score), _p(out_bias), _p(out_state), B, T, k, int(beam), int(nbest), Lcap,
-                                          int(blank), _stream()), "asr_ctc_prefix_beam_ctx")
-        return out_tok, out_len, out_score, out_bias, out_state
-    if lm is not None:
-        _, tabs = lm.on(vals.device)
-        out_bias = torch.empty(B, nbest, dtype=torch.float64, device=vals.device)
-        out_state = torch.empty(B, nbest, dtype=torch.int32, device=vals.device)
-        check(lib.asr_ctc_prefix_beam_lm(_p(vals), _p(ids), _p(blank_lp), _p(in_len), ctypes.addressof(tabs), _p(ws), ws.numel(), _p(out_tok), _p(out_len),
-                                         _p(out_score), _p(out_bias), _p(out_state), B, T, k, int(beam), int(nbest), Lcap, int(blank), _stream()),
-              "asr_ctc_prefix_beam_lm")
-        return out_tok, out_len, out_score, out_bias, out_state
-    if times:
-        out_vit = torch.empty(B, nbest, dtype=torch.float64, device=vals.device)
-        out_start, out_end = (torch.zeros(B, nbest, Lcap, dtype=torch.int32, device=vals.device) for _ in range(2))
-        out_mx, out_mn, out_sm = (torch.zeros(B, nbest, Lcap, dtype=torch.float32, device=vals.device) for _ in range(3))
-        check(lib.asr_ctc_prefix_beam_timed(_p(vals), _p(ids), _p(blank_lp), _p(in_len), _p(ws), ws.numel(), _p(out_tok), _p(out_len), _p(out_score),
-                                            _p(out_vit), _p(out_start), _p(out_end), _p(out_mx), _p(out_mn), _p(out_sm), B, T, k, int(beam), int(nbest),
-                                            Lcap, int(blank), _stream()), "asr_ctc_prefix_beam_timed")
-        return out_tok, out_len, out_score, out_vit, out_start, out_end, out_mx, out_mn, out_sm
-    check(lib.asr_ctc_prefix_beam(_p(vals), _p(ids), _p(blank_lp), _p(in_len), _p(ws), ws.numel(), _p(out_tok), _p(out_len), _p(out_score),
-                                  B, T, k, int(beam), int(nbest), Lcap, int(blank), _stream()), "asr_ctc_prefix_beam")
-    return out_tok, out_len, out_score
+    dev = vals.device
+    ws = torch.empty(ws_bytes(B, T, beam), dtype=torch.uint8, device=dev)
+    # the per-utterance outputs (stable, final) are the resumable search's; per-token outputs are zero past an entry's length
+    outs = [(torch.zeros if kind == _PB_TOKEN else torch.empty)(shape, dtype=dtype, device=dev)
+            for _, dtype, kind, shape, _, _ in prefix_beam_layout(B, nbest, Lcap, mode)[0] if kind != _PB_UTT]
+    lead = [_p(_context_roots(context, roots, B, dev)[1])] if mode == "ctx" else []
+    _pb_call("asr_ctc_prefix_beam" + sfx, _p(vals), _p(ids), _p(blank_lp), _p(in_len), *lead, *_pb_tables(mode, context, lm, dev), _p(ws), ws.numel(),
+             *(_p(t) for t in outs), B, T, k, int(beam), int(nbest), Lcap, int(blank), _stream())
+    return tuple(outs)
 
 
 class PrefixBeamState:
@@ -505,90 +553,31 @@ class PrefixBeamState:
     chunk past T_cap is refused before any launch.  context: the ContextGraph of a context state (None: a plain state) - a context state
     is larger (bias, context state and root per utterance) and only ever reaches the _ctx entry points.  lm: the NgramLM of an LM state
     (bias and LM state per entry), which only ever reaches the _lm entry points.  times: a timed state (the entries' best single alignments
-    and a second trie for their records), which only ever reaches the _timed entry points."""
+    and a second trie for their records), which only ever reaches the _timed entry points.  mode: the state's row of the mode table."""
 
     def __init__(self, state, ws, B, beam, T_cap, context=None, roots=None, lm=None, times=False):
         self.state, self.ws, self.B, self.beam, self.T_cap = state, ws, B, beam, T_cap
         self.frames = [0] * B
         self.context, self.roots, self.lm, self.times = context, roots, lm, bool(times)
+        self.mode = _pb_mode(context, lm, times)
 
 
 def ctc_prefix_beam_state(B, beam, T_cap, device="cuda", context=None, roots=None, lm=None, times=False):
     """A fresh PrefixBeamState: the empty-prefix beam for B utterances of at most T_cap frames each.  context / roots: a context
     state for the hotword-biased search (roots as ctc_prefix_beam's).  lm: an LM state, every utterance on the LM's start state.
     times: a timed state (asr_ctc_prefix_beam_chunk_timed); its workspace holds both tries, 10 words per node."""
-    _no_lm_with_context(lm, context)
-    _no_times_with_bias(times, context, lm)
+    mode = _pb_mode(context, lm, times)
+    sfx, _, ws_bytes, state_bytes, _ = _PB_MODES[mode]
     B, beam, T_cap = int(B), int(beam), int(T_cap)
     if B < 1 or beam < 1 or T_cap < 1:
         raise ValueError(f"ctc_prefix_beam_state: B, beam and T_cap must be >= 1 (got {B}, {beam}, {T_cap})")
-    if times:
-        state = torch.zeros(lib.asr_ctc_prefix_beam_timed_state_bytes(B, beam) // 8, dtype=torch.int64, device=device)      # 8-aligned
-        ws = torch.empty(lib.asr_ctc_prefix_beam_timed_workspace_bytes(B, T_cap, beam), dtype=torch.uint8, device=device)
-        check(lib.asr_ctc_prefix_beam_timed_state_init(_p(state), _p(ws), B, beam, T_cap, _stream()), "asr_ctc_prefix_beam_timed_state_init")
-        return PrefixBeamState(state, ws, B, beam, T_cap, times=True)
-    if lm is not None:
-        _, tabs = lm.on(device)
-        state = torch.zeros(lib.asr_ctc_prefix_beam_lm_state_bytes(B, beam) // 8, dtype=torch.int64, device=device)      # 8-aligned
-        ws = torch.empty(lib.asr_ctc_prefix_beam_lm_workspace_bytes(B, T_cap, beam), dtype=torch.uint8, device=device)      # the trie with child lists
-        check(lib.asr_ctc_prefix_beam_lm_state_init(_p(state), _p(ws), ctypes.addressof(tabs), B, beam, T_cap, _stream()), "asr_ctc_prefix_beam_lm_state_init")
-        return PrefixBeamState(state, ws, B, beam, T_cap, lm=lm)
-    if context is not None:
-        host, root_dev = _context_roots(context, roots, B, device)
-        state = torch.zeros(lib.asr_ctc_prefix_beam_ctx_state_bytes(B, beam) // 8, dtype=torch.int64, device=device)      # 8-aligned
-        ws = torch.empty(lib.asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam), dtype=torch.uint8, device=device)
-        check(lib.asr_ctc_prefix_beam_ctx_state_init(_p(state), _p(ws), _p(root_dev), B, beam, T_cap, _stream()), "asr_ctc_prefix_beam_ctx_state_init")
-        return PrefixBeamState(state, ws, B, beam, T_cap, context, host)
-    state = torch.zeros(lib.asr_ctc_prefix_beam_state_bytes(B, beam) // 8, dtype=torch.int64, device=device)      # 8-aligned
-    ws = torch.empty(lib.asr_ctc_prefix_beam_stream_workspace_bytes(B, T_cap, beam), dtype=torch.uint8, device=device)
-    check(lib.asr_ctc_prefix_beam_state_init(_p(state), _p(ws), B, beam, T_cap, _stream()), "asr_ctc_prefix_beam_state_init")
-    return PrefixBeamState(state, ws, B, beam, T_cap)
-
-
-def prefix_beam_unpack(buf, B, nbest, Lcap):
-    """(tokens (B, nbest, Lcap) int32, lengths (B, nbest) int32, scores (B, nbest) f32, stable (B) int32) as views of the int32 buffer of
-    B * (nbest * (Lcap + 2) + 1) words that ctc_prefix_beam_chunk fills (on the device or copied to the host)."""
-    tok_n, len_n = B * nbest * Lcap, B * nbest
-    assert buf.dtype == torch.int32 and buf.numel() == tok_n + 2 * len_n + B and buf.is_contiguous()
-    return (buf[:tok_n].view(B, nbest, Lcap), buf[tok_n:tok_n + len_n].view(B, nbest),
-            buf[tok_n + len_n:tok_n + 2 * len_n].view(torch.float32).view(B, nbest), buf[tok_n + 2 * len_n:])
-
-
-def prefix_beam_ctx_words(B, nbest, Lcap):
-    """int32 words of a context state's packed result: the plain B * (nbest * (Lcap + 2) + 1), one pad word if that is odd (the fp64
-    bias is 8-aligned), then bias (2 words per entry) and state (1 word per entry)."""
-    n = B * (nbest * (Lcap + 2) + 1)
-    return n + (n & 1) + 3 * B * nbest
-
-
-def prefix_beam_ctx_unpack(buf, B, nbest, Lcap):
-    """(bias (B, nbest) float64 - raw, before held(state) is taken off -, state (B, nbest) int32) as views of a context state's packed
-    result of prefix_beam_ctx_words(B, nbest, Lcap) words; its first B * (nbest * (Lcap + 2) + 1) words are prefix_beam_unpack's."""
-    n = B * (nbest * (Lcap + 2) + 1)
-    n += n & 1
-    assert buf.dtype == torch.int32 and buf.numel() == n + 3 * B * nbest and buf.is_contiguous()
-    return buf[n:n + 2 * B * nbest].view(torch.float64).view(B, nbest), buf[n + 2 * B * nbest:].view(B, nbest)
-
-
-def prefix_beam_times_words(B, nbest, Lcap):
-    """int32 words of a timed state's packed result: the plain B * (nbest * (Lcap + 2) + 1), one pad word if that is odd (the fp64 vit is
-    8-aligned), then vit (2 words per entry), start, end, mx, mn, sm (Lcap words per entry each) and final (one word per utterance)."""
-    n = B * (nbest * (Lcap + 2) + 1)
-    return n + (n & 1) + B * nbest * (2 + 5 * Lcap) + B
-
-
-def prefix_beam_times_unpack(buf, B, nbest, Lcap):
-    """(vit (B, nbest) float64, start, end (B, nbest, Lcap) int32, mx, mn, sm (B, nbest, Lcap) float32, final (B) int32) as views of a timed
-    state's packed result of prefix_beam_times_words(B, nbest, Lcap) words; its first B * (nbest * (Lcap + 2) + 1) words are prefix_beam_unpack's."""
-    n = B * (nbest * (Lcap + 2) + 1)
-    n += n & 1
-    assert buf.dtype == torch.int32 and buf.numel() == prefix_beam_times_words(B, nbest, Lcap) and buf.is_contiguous()
-    e, r = B * nbest, B * nbest * Lcap
-    vit = buf[n:n + 2 * e].view(torch.float64).view(B, nbest)
-    n += 2 * e
-    start, end = buf[n:n + r].view(B, nbest, Lcap), buf[n + r:n + 2 * r].view(B, nbest, Lcap)
-    mx, mn, sm = (buf[n + i * r:n + (i + 1) * r].view(torch.float32).view(B, nbest, Lcap) for i in (2, 3, 4))
-    return vit, start, end, mx, mn, sm, buf[n + 5 * r:]
+    host, root_dev = _context_roots(context, roots, B, device) if mode == "ctx" else (None, None)
+    state = torch.zeros(state_bytes(B, beam) // 8, dtype=torch.int64, device=device)      # 8-aligned
+    ws = torch.empty(ws_bytes(B, T_cap, beam), dtype=torch.uint8, device=device)
+    # a context state takes its roots (the graph reaches the chunks), an LM state the LM (for its start state)
+    lead = [_p(root_dev)] if mode == "ctx" else _pb_tables(mode, context, lm, device)
+    _pb_call(f"asr_ctc_prefix_beam{sfx}_state_init", _p(state), _p(ws), *lead, B, beam, T_cap, _stream())
+    return PrefixBeamState(state, ws, B, beam, T_cap, context, host, lm, times)
 
 
 def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, max_len=None, packed=False, nv_dev=None, extra_words=0):
@@ -601,12 +590,11 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
     caller has uploaded already; extra_words (packed only): int32 words left free behind the results in the returned buffer, for
     what else travels to the host in the same copy.
     A context state (st.context): the biased search (asr_ctc_prefix_beam_chunk_ctx); the result gains bias (B, nbest) float64 (raw) and
-    state (B, nbest) int32, and the packed buffer grows to prefix_beam_ctx_words (prefix_beam_ctx_unpack reads the two).
+    state (B, nbest) int32, and the packed buffer grows by them (prefix_beam_layout; prefix_beam_unpack(..., "ctx") reads all six).
     An LM state (st.lm): the search with the n-gram LM (asr_ctc_prefix_beam_chunk_lm); the same two additions, bias without the
     end-of-sentence term and the LM state.
     A timed state (st.times): asr_ctc_prefix_beam_chunk_timed; the result gains (vit, start, end, mx, mn, sm) as ctc_prefix_beam(times=True)
-    and final (B) int32 = how many leading records of every list no later frame can change; the packed buffer grows to
-    prefix_beam_times_words (prefix_beam_times_unpack reads the seven)."""
+    and final (B) int32 = how many leading records of every list no later frame can change; the packed buffer grows by the seven."""
     B, beam, k = st.B, st.beam, vals.shape[1]
     C, nbest = int(C), int(nbest)
     nv = [int(x) for x in n_valid]
@@ -619,48 +607,20 @@ def ctc_prefix_beam_chunk(st, vals, ids, blank_lp, n_valid, C, nbest, blank=0, m
     _chk_f32(vals, blank_lp)
     _chk_i32(ids)
     Lcap = int(max(1, max(f + n for f, n in zip(st.frames, nv))) if max_len is None else max_len)
-    n_words = B * (nbest * (Lcap + 2) + 1)
-    n_all = n_words if st.context is None and st.lm is None else prefix_beam_ctx_words(B, nbest, Lcap)
-    if st.times:
-        n_all = prefix_beam_times_words(B, nbest, Lcap)
+    fields, n_all = prefix_beam_layout(B, nbest, Lcap, st.mode)
     out = torch.zeros(n_all + (int(extra_words) if packed else 0), dtype=torch.int32, device=vals.device)
-    out_tok, out_len, out_score, out_stable = prefix_beam_unpack(out[:n_words], B, nbest, Lcap)
+    views = _pb_views(out, fields)
     if nv_dev is None:
         nv_dev = torch.tensor(nv, dtype=torch.int32, device=vals.device)
     _chk_i32(nv_dev)
     assert nv_dev.numel() == B
-    if st.context is not None:
-        out_bias, out_state = prefix_beam_ctx_unpack(out[:n_all], B, nbest, Lcap)
-        _, tabs = st.context.on(vals.device)
-        check(lib.asr_ctc_prefix_beam_chunk_ctx(_p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(), ctypes.addressof(tabs),
-                                                _p(out_tok), _p(out_len), _p(out_score), _p(out_bias), _p(out_state), _p(out_stable), B, C, k, beam, nbest,
-                                                Lcap, st.T_cap, int(blank), _stream()), "asr_ctc_prefix_beam_chunk_ctx")
-        for b in range(B):
-            st.frames[b] += nv[b]
-        return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable, out_bias, out_state)
-    if st.lm is not None:
-        out_bias, out_state = prefix_beam_ctx_unpack(out[:n_all], B, nbest, Lcap)
-        _, tabs = st.lm.on(vals.device)
-        check(lib.asr_ctc_prefix_beam_chunk_lm(_p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(), ctypes.addressof(tabs),
-                                               _p(out_tok), _p(out_len), _p(out_score), _p(out_bias), _p(out_state), _p(out_stable), B, C, k, beam, nbest,
-                                               Lcap, st.T_cap, int(blank), _stream()), "asr_ctc_prefix_beam_chunk_lm")
-        for b in range(B):
-            st.frames[b] += nv[b]
-        return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable, out_bias, out_state)
-    if st.times:
-        tv = prefix_beam_times_unpack(out[:n_all], B, nbest, Lcap)
-        check(lib.asr_ctc_prefix_beam_chunk_timed(_p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(), _p(out_tok), _p(out_len),
-                                                  _p(out_score), *(_p(t) for t in tv[:6]), _p(out_stable), _p(tv[6]), B, C, k, beam, nbest, Lcap, st.T_cap,
-                                                  int(blank), _stream()), "asr_ctc_prefix_beam_chunk_timed")
-        for b in range(B):
-            st.frames[b] += nv[b]
-        return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable) + tv
-    check(lib.asr_ctc_prefix_beam_chunk(_p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(), _p(out_tok), _p(out_len),
-                                        _p(out_score), _p(out_stable), B, C, k, beam, nbest, Lcap, st.T_cap, int(blank), _stream()),
-          "asr_ctc_prefix_beam_chunk")
+    # the entry points take the per-utterance outputs (stable, final) behind the others
+    outs = [_p(v) for f, v in zip(fields, views) if f[2] != _PB_UTT] + [_p(v) for f, v in zip(fields, views) if f[2] == _PB_UTT]
+    _pb_call("asr_ctc_prefix_beam_chunk" + _PB_MODES[st.mode][0], _p(vals), _p(ids), _p(blank_lp), _p(nv_dev), _p(st.state), _p(st.ws), st.ws.numel(),
+             *_pb_tables(st.mode, st.context, st.lm, vals.device), *outs, B, C, k, beam, nbest, Lcap, st.T_cap, int(blank), _stream())
     for b in range(B):
         st.frames[b] += nv[b]
-    return (out, Lcap) if packed else (out_tok, out_len, out_score, out_stable)
+    return (out, Lcap) if packed else views
 
 
 def ctc_prefix_beam_state_reset(st, flags, slots=(), roots=None, lm=None):
@@ -672,34 +632,16 @@ def ctc_prefix_beam_state_reset(st, flags, slots=(), roots=None, lm=None):
     assert flags.numel() == st.B
     if lm is not None and lm is not st.lm:
         raise ValueError("ctc_prefix_beam_state_reset: lm must be the NgramLM the state was made with (one LM serves every utterance)")
-    if st.lm is not None:
-        if roots is not None:
-            raise ValueError("ctc_prefix_beam_state_reset: roots apply to a context state")
-        _, tabs = st.lm.on(st.state.device)
-        check(lib.asr_ctc_prefix_beam_lm_state_reset(_p(st.state), _p(st.ws), _p(flags), ctypes.addressof(tabs), st.B, st.beam, st.T_cap, _stream()),
-              "asr_ctc_prefix_beam_lm_state_reset")
-        for b in slots:
-            st.frames[int(b)] = 0
-        return
-    if st.context is not None:
-        host, root_dev = _context_roots(st.context, st.roots if roots is None else roots, st.B, st.state.device)
-        check(lib.asr_ctc_prefix_beam_ctx_state_reset(_p(st.state), _p(st.ws), _p(flags), _p(root_dev), st.B, st.beam, st.T_cap, _stream()),
-              "asr_ctc_prefix_beam_ctx_state_reset")
-        for b in slots:
-            st.frames[int(b)] = 0
-            st.roots[int(b)] = host[int(b)]
-        return
-    if roots is not None:
+    if roots is not None and st.mode != "ctx":
         raise ValueError("ctc_prefix_beam_state_reset: roots apply to a context state")
-    if st.times:
-        check(lib.asr_ctc_prefix_beam_timed_state_reset(_p(st.state), _p(st.ws), _p(flags), st.B, st.beam, st.T_cap, _stream()),
-              "asr_ctc_prefix_beam_timed_state_reset")
-        for b in slots:
-            st.frames[int(b)] = 0
-        return
-    check(lib.asr_ctc_prefix_beam_state_reset(_p(st.state), _p(st.ws), _p(flags), st.B, st.beam, st.T_cap, _stream()), "asr_ctc_prefix_beam_state_reset")
+    dev = st.state.device
+    host, root_dev = _context_roots(st.context, st.roots if roots is None else roots, st.B, dev) if st.mode == "ctx" else (None, None)
+    lead = [_p(root_dev)] if st.mode == "ctx" else _pb_tables(st.mode, st.context, st.lm, dev)      # as ctc_prefix_beam_state's
+    _pb_call(f"asr_ctc_prefix_beam{_PB_MODES[st.mode][0]}_state_reset", _p(st.state), _p(st.ws), _p(flags), *lead, st.B, st.beam, st.T_cap, _stream())
     for b in slots:
         st.frames[int(b)] = 0
+        if host is not None:
+            st.roots[int(b)] = host[int(b)]
 
 
 # --------------------------------------------------------------------------------- independent sessions (csrc/session.hip)

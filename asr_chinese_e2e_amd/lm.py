@@ -9,7 +9,7 @@ the history (<s>) if <s> is listed, otherwise from the empty history.
 Weights are folded in here: every table entry is the fp64 TERM weight * (log10value * math.log(10.0)).  A hypothesis carries
 (state, bias) from (start, 0.0).  Appending token c does bias = bias + term once per back-off weight met on the chain, in chain
 order, then once for the probability found, then bias = bias + ins.  Nothing but these fp64 additions touches the bias on the host
-(advance) or on the device (csrc/decode.hip, pb_lm_advance) - so the two agree bit for bit.  A reported hypothesis carries lm_score =
+(advance) or on the device (csrc/prefix_beam.hip, pb_lm_advance) - so the two agree bit for bit.  A reported hypothesis carries lm_score =
 bias + term(</s> | its state) (final); the end term is 0.0 if </s> is not listed.  The search ranks by log p + bias without it.
 
 States: 0 is the empty history; the others are the prefixes of 1 .. order - 1 tokens of the listed n-grams (every context a listed

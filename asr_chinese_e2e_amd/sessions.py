@@ -405,16 +405,15 @@ class Sessions:
             n_words = buf.numel() - S * (4 + C)      # the search's words (with a context: bias and state included)
             K.session_ctc_step(None, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK, out=buf[n_words:].view(S, 4 + C))
             host = buf.cpu()
-            n_plain = S * (self.beam_size * (Lcap + 2) + 1)
-            tok, ln, sc, stable = (t.numpy() for t in K.prefix_beam_unpack(host[:n_plain], S, self.beam_size, Lcap))
+            tok, ln, sc, stable, *extra = (t.numpy() for t in K.prefix_beam_unpack(host[:n_words], S, self.beam_size, Lcap, self.beam.mode))
             self._hyps = (tok, ln, sc)
-            if self.context is not None or self.lm is not None:
-                self._hyps += tuple(t.numpy() for t in K.prefix_beam_ctx_unpack(host[:n_words], S, self.beam_size, Lcap))
             if self.beam_times:
-                self._times = tuple(t.numpy() for t in K.prefix_beam_times_unpack(host[:n_words], S, self.beam_size, Lcap))
+                self._times = tuple(extra)
                 for b in range(S):
                     if self.state[b] != FREE:
                         self.has_times[b] = True
+            else:
+                self._hyps += tuple(extra)      # with a context / an LM: bias and state
             step = host[n_words:].view(S, 4 + C).tolist()
             for b in reset_slots:
                 self.stable[b] = 0
@@ -497,19 +496,16 @@ class Sessions:
         b = self._slot(b)
         if self.state[b] == FREE:
             raise ValueError(f"nbest: slot {b} is free")
-        if self.lm is not None:
-            from .decode import lm_entries
-            if self._hyps is None or self.fresh[b]:      # the empty hypothesis on the start state: only the end-of-sentence term
-                l = self.lm.final(self.lm.start, 0.0)
-                return [{"yseq": [], "score": 0.0 + l, "ctc_score": 0.0, "lm_score": l}]
+        from .decode import _bias_entries, _bias_mode
+        biased = _bias_mode(self.context, self.lm)
+        if self._hyps is None or self.fresh[b]:      # the empty hypothesis: an LM's start state (only the end-of-sentence term), a context's -1 (nothing held)
+            if biased is None:
+                return [{"yseq": [], "score": 0.0}]
+            x = biased[1](self.lm.start if self.lm is not None else -1, 0.0)
+            return [{"yseq": [], "score": 0.0 + x, "ctc_score": 0.0, biased[0]: x}]
+        if biased is not None:
             tok, ln, sc, bias, state = self._hyps
-            return lm_entries(self.lm, tok[b], ln[b], sc[b], bias[b], state[b])
-        if self._hyps is None or self.fresh[b]:
-            return [{"yseq": [], "score": 0.0, "ctc_score": 0.0, "bias": 0.0}] if self.context is not None else [{"yseq": [], "score": 0.0}]
-        if self.context is not None:
-            from .decode import context_entries
-            tok, ln, sc, bias, state = self._hyps
-            return context_entries(self.context, tok[b], ln[b], sc[b], bias[b], state[b])
+            return _bias_entries(*biased, tok[b], ln[b], sc[b], bias[b], state[b])
         tok, ln, sc = self._hyps
         out = [{"yseq": tok[b, r, :ln[b, r]].tolist(), "score": float(sc[b, r])} for r in range(self.beam_size) if ln[b, r] >= 0]
         if self.beam_times and self.has_times[b]:      # ranks without an entry are the last ones: list index = rank
