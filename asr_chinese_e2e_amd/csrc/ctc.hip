@@ -1,7 +1,7 @@
 // CTC forward-backward fused with the log-softmax over the vocabulary, and softmax
 // cross-entropy.  Both are HBM-bound passes over (rows, V) logits.
 //
-// CTC, three kernels on one stream:
+// CTC, four kernels on one stream:
 //   1. ctc_lse_gather : one wave per frame (b,t < in_len[b]).  Streams the V logits once
 //      (16 B per lane per load), online max/sum-exp per lane, wave-shuffle reduction -> lse[b,t];
 //      then gathers the S = 2L+1 lattice inputs lp[b,t,s] = x[l'_s] - lse (row is L1/L2-hot).
@@ -15,6 +15,8 @@
 //      softmax_s(alpha+beta-lp) (exact: the sum over s is p(l|x) at every t) and scatters them into an LDS
 //      table indexed by label (ds_add_f32), then one streaming pass: read logits, write
 //      dlogits = scale * (softmax - posterior).  Padded frames are written as zeros.
+//   4. ctc_rescue     : one workgroup per utterance, idle unless kernels 2 / 3 found that the utterance left the range of the scaled
+//      lattice (see LATTICE_TINY); such an utterance is redone in the log domain.
 // Algorithmic HBM bytes: logits read twice + dlogits written once = 3 * B*T*V*e;
 // the lattice (B*T*S*4 B * 3 arrays) stays in L2 / Infinity Cache.
 #include "asr_common.h"
@@ -168,7 +170,8 @@ __device__ __forceinline__ int wave_row_argmax_regs(const u32x4 (&xv)[NV], int n
 // with c[i] = lab[i] != lab[i-1], c'[i] = lab[i] != lab[i+1] (the skip transitions).
 
 // ---------------------------------------------------------------------------------- kernel 1
-template <typename T>
+// LOGD: the lattice inputs stay log-probabilities (-inf beyond the valid entries): the forced alignment's max / add recursion
+template <typename T, bool LOGD>
 __global__ __launch_bounds__(256) void ctc_lse_gather_kernel(const T* __restrict__ logits, const int32_t* __restrict__ in_len,
                                                              const int32_t* __restrict__ labels, const int32_t* __restrict__ lab_len,
                                                              double* __restrict__ lp, float* __restrict__ lse_out, int B, int T_, int V, int ld, int Lmax,
@@ -183,10 +186,13 @@ __global__ __launch_bounds__(256) void ctc_lse_gather_kernel(const T* __restrict
         if (lane == 0) lse_out[row] = lse;
         const int L = lab_len[b];
         double* out = lp + (size_t)row * 2 * W;
-        const double yb = exp((double)(to_f32<T>(x[blank]) - lse));   // y_t(blank): linear domain, fp64
+        const double lb = (double)(to_f32<T>(x[blank]) - lse);
+        const double yb = LOGD ? lb : exp(lb);   // y_t(blank): linear domain, fp64
+        const double none = LOGD ? -INFINITY : 0.0;
         for (int i = lane; i < W; i += 64) {   // zero beyond the valid entries: the recursion runs unpredicated
             const int c = labels[(size_t)b * Lmax + min(i, Lmax - 1)];
-            const f64x2 e = {i <= L ? yb : 0.0, i < L ? exp((double)(to_f32<T>(x[c]) - lse)) : 0.0};
+            const double ll = (double)(to_f32<T>(x[c]) - lse);
+            const f64x2 e = {i <= L ? yb : none, i < L ? (LOGD ? ll : exp(ll)) : none};
             *(f64x2*)(out + 2 * i) = e;
         }
     }
@@ -199,7 +205,8 @@ __global__ __launch_bounds__(256) void ctc_lse_gather_kernel(const T* __restrict
 // the gathers below must stay in front of the stores).
 // PATH: the wave also writes the frame's best class (first index of the row maximum; `blank` for padded frames) to best_path - the
 // greedy CTC path of the training step's CER, taken from the row while it is in registers (the gradient overwrites the logits in place).
-template <int NV, bool WRITE, bool PATH>
+// LOGD: as ctc_lse_gather_kernel
+template <int NV, bool WRITE, bool PATH, bool LOGD = false>
 __global__ __launch_bounds__(256) void ctc_lse_gather_rows_kernel(const bf16_t* logits, const int32_t* __restrict__ in_len,
                                                                   const int32_t* __restrict__ labels, const int32_t* __restrict__ lab_len,
                                                                   double* __restrict__ lp, float* __restrict__ lse_out, int B, int T_, int V, int ld, int Lmax,
@@ -253,12 +260,13 @@ __global__ __launch_bounds__(256) void ctc_lse_gather_rows_kernel(const bf16_t* 
             }
         }
         double* out = lp + (size_t)row * 2 * W;
-        const double yb = exp((double)(xb - lse));   // y_t(blank): linear domain, fp64
+        const double yb = LOGD ? (double)(xb - lse) : exp((double)(xb - lse));   // y_t(blank): linear domain, fp64
+        const double none = LOGD ? -INFINITY : 0.0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int i = lane + 64 * j;
             if (i < W) {   // zero beyond the valid entries: the recursion runs unpredicated
-                const f64x2 e = {i <= L ? yb : 0.0, i < L ? exp((double)(xl[j] - lse)) : 0.0};
+                const f64x2 e = {i <= L ? yb : none, i < L ? (LOGD ? (double)(xl[j] - lse) : exp((double)(xl[j] - lse))) : none};
                 *(f64x2*)(out + 2 * i) = e;
             }
         }
@@ -306,6 +314,14 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
 #undef DPP_MAX
     return (unsigned)__builtin_amdgcn_readlane((int)v, LAST);
 }
+
+// What the scaled lattice holds.  A column is scaled by its MAXIMUM, so a state further than the fp64 range below it becomes 0 although
+// it may be the one that matters: the final states of a long label sequence under blank-dominated posteriors (blank ~ 0.99, every label
+// ~ 1e-5: the all-blank prefix is the maximum and the final states sit (p_label / p_blank)^L below it), or every alpha * beta of a frame.
+// A loss tail or a frame's posterior sum below LATTICE_TINY (scaled units; ordinary utterances are within 1e-40 of 1) has left that
+// range or is about to: what was lost on the way to a sum >= 2^-600 is below 2^-1022 * S / y, a relative 1e-120.  Such an utterance is
+// marked (nll_raw = NaN) and ctc_rescue_kernel redoes it in the log domain; +inf is left to the utterances whose LENGTHS are infeasible.
+constexpr double LATTICE_TINY = 0x1p-600;
 
 // W = row half-width (compile time: 32, 64, 128, 256), NS = registers per lane per array (entry
 // i = lane + 64 j).  Every load and store of the steady-state loop is unconditional, at an
@@ -488,7 +504,15 @@ __global__ __launch_bounds__(128) void ctc_alpha_beta_kernel(const double* __res
         } else {
             const double* last = ab + (size_t)(Tb - 1) * RW;
             const double tail = last[2 * L] + (L > 0 ? last[2 * (L - 1) + 1] : 0.0);      // interleaved rows: (blank, label) pairs
-            nll = (tail > 0.0 && s_logc != -INFINITY) ? (float)(-(s_logc + log(tail))) : INFINITY;
+            nll = (tail >= LATTICE_TINY && s_logc != -INFINITY) ? (float)(-(s_logc + log(tail))) : INFINITY;
+        }
+        if (nll == INFINITY) {
+            // The lattice ended at 0 (or below what it holds at full precision).  Whether the labels fit the frames is a matter of the
+            // lengths alone: in_len >= L + adjacent repeats.  If they fit, the lattice left the fp64 range below its column maxima
+            // (blank-dominated posteriors, long labels): NaN hands the utterance to ctc_rescue_kernel.
+            int need = L;
+            for (int i = 1; i < L; ++i) need += lab[i] == lab[i - 1];
+            if (Tb >= need && Tb > 0) nll = NAN;
         }
         nll_raw[b] = nll;
         nll_out[b] = (nll == INFINITY && zero_infinity) ? 0.f : nll;
@@ -501,7 +525,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const T* __restrict__ log
                                                        const double* __restrict__ alpha, const double* __restrict__ beta,
                                                        const float* __restrict__ lse_in, const int32_t* __restrict__ in_len,
                                                        const int32_t* __restrict__ labels, const int32_t* __restrict__ lab_len,
-                                                       const float* __restrict__ nll_raw, int B, int T_, int V, int ld, int Lmax, int W, int blank,
+                                                       float* nll_raw, int B, int T_, int V, int ld, int Lmax, int W, int blank,
                                                        float scale_in, int det, const float* __restrict__ scale_div) {
     const float scale = scale_div ? scale_in / *scale_div : scale_in;
     extern __shared__ __attribute__((aligned(16))) float occ[];  // V floats: posterior mass per label
@@ -527,7 +551,8 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const T* __restrict__ log
         const T* x = logits + (size_t)row * ld;
         const int L = lab_len[b];
         const float lse = lse_in[row];
-        if (threadIdx.x < 64) {
+        // nll_raw = NaN: the utterance waits for ctc_rescue_kernel, which overwrites the label classes; the row is the plain softmax until then
+        if (threadIdx.x < 64 && nll_raw[b] == nll_raw[b]) {
             // posterior of a state at this frame, up to a per-frame constant: alpha * beta / y
             // (both recursions include y_t).  sum_s alpha_t(s) beta_t(s) / y_t(l'_s) = p(l|x) for
             // EVERY t, so normalising over s is exact and needs neither nll nor the scale factors.
@@ -544,7 +569,9 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const T* __restrict__ log
                 sum_l += __shfl_xor(sum_l, off, 64);
             }
             const double sum = sum_b + sum_l;
-            if (sum > 0.0) {
+            if (!(sum >= LATTICE_TINY)) {      // every alpha * beta of this frame left the fp64 range: the whole utterance is redone
+                if (threadIdx.x == 0) nll_raw[b] = NAN;
+            } else {
                 if (threadIdx.x == 0) occ[blank] = (float)(sum_b / sum);      // all blank states share one class
                 if (det) {   // repeated labels share a class: add their states in label order (fixed order)
                     if (threadIdx.x == 0)
@@ -584,7 +611,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const T* __restrict__ log
 __global__ __launch_bounds__(256) void ctc_label_fix_kernel(bf16_t* __restrict__ dlogits, const double* __restrict__ lp, const double* __restrict__ alpha,
                                                             const double* __restrict__ beta, const int32_t* __restrict__ in_len,
                                                             const int32_t* __restrict__ labels, const int32_t* __restrict__ lab_len,
-                                                            const float* __restrict__ nll_raw, int B, int T_, int V, int ld, int Lmax, int W, int blank, float scale_in, const float* __restrict__ scale_div) {
+                                                            float* nll_raw, int B, int T_, int V, int ld, int Lmax, int W, int blank, float scale_in, const float* __restrict__ scale_div) {
     const float scale = scale_div ? scale_in / *scale_div : scale_in;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int rows = B * T_, nvec = V >> 3;
@@ -597,6 +624,7 @@ __global__ __launch_bounds__(256) void ctc_label_fix_kernel(bf16_t* __restrict__
             for (int i = lane; i < nvec; i += 64) *(u32x4*)(dl + (size_t)i * 8) = z;
             continue;
         }
+        if (nll_raw[b] != nll_raw[b]) continue;      // NaN: waits for ctc_rescue_kernel; the row holds the plain softmax, which is what that kernel expects
         const int L = lab_len[b];
         // posterior of a state at this frame, up to a per-frame constant: alpha * beta / y; normalising over the
         // states is exact (see ctc_grad_kernel: the sum over s of alpha beta / y is p(l | x) at EVERY t, so it needs neither nll nor the scale factors)
@@ -626,7 +654,11 @@ __global__ __launch_bounds__(256) void ctc_label_fix_kernel(bf16_t* __restrict__
             sum += __shfl_xor(sum, off, 64);
             pb += __shfl_xor(pb, off, 64);
         }
-        const double inv = sum > 0.0 ? 1.0 / sum : 0.0;
+        if (!(sum >= LATTICE_TINY)) {      // every alpha * beta of this frame left the fp64 range: the whole utterance is redone (ctc_rescue_kernel)
+            if (lane == 0) nll_raw[b] = NAN;
+            continue;
+        }
+        const double inv = 1.0 / sum;
         float occ[4] = {0.f, 0.f, 0.f, 0.f};   // occupancy of each label's class = sum over the positions that carry the same label
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
@@ -647,10 +679,159 @@ __global__ __launch_bounds__(256) void ctc_label_fix_kernel(bf16_t* __restrict__
     }
 }
 
+// Loss without a gradient: no kernel 3 looks at the frames, and a loss tail in range does not show that no path mass was lost on the
+// way (alpha may have dropped states that only a far-away beta maximum would have shown to matter).  One wave per frame forms the sum
+// kernel 3 forms and marks the utterance by the same rule.
+__global__ __launch_bounds__(256) void ctc_frame_check_kernel(const double* __restrict__ lp, const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                              const int32_t* __restrict__ in_len, const int32_t* __restrict__ lab_len, float* nll_raw,
+                                                              int B, int T_, int W) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int rows = B * T_;
+    for (int row = blockIdx.x * 4 + w; row < rows; row += gridDim.x * 4) {
+        const int b = row / T_, t = row - b * T_;
+        const float raw = nll_raw[b];
+        if (t >= in_len[b] || raw == INFINITY || raw != raw) continue;
+        const int L = lab_len[b];
+        const size_t o = (size_t)row * 2 * W;
+        double sum = 0.0;
+        for (int i = lane; i <= L; i += 64) {
+            const f64x2 yv = *(const f64x2*)(lp + o + 2 * i), av = *(const f64x2*)(alpha + o + 2 * i), bv = *(const f64x2*)(beta + o + 2 * i);
+            sum += yv[0] > 0.0 ? av[0] * bv[0] / yv[0] : 0.0;
+            sum += (i < L && yv[1] > 0.0) ? av[1] * bv[1] / yv[1] : 0.0;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+        if (!(sum >= LATTICE_TINY) && lane == 0) nll_raw[b] = NAN;
+    }
+}
+
+// ---------------------------------------------------------------------------------- kernel 4: out-of-range utterances
+// Runs after the gradient kernels, one workgroup per utterance; returns at once unless the utterance is marked (nll_raw = NaN: the
+// scaled lattice lost the loss tail or a frame's posteriors, see LATTICE_TINY).  A marked utterance is redone in the LOG domain in fp64,
+// exact at any range and ~50 x slower per frame than the scaled recursion (an LDS exchange, three exp and a log per state and frame):
+//   forward : log alpha, thread i = entry i = states 2i (blank) and 2i+1 (label), written over the utterance's rows of `alpha`;
+//   loss    : nll = -logaddexp of the two final states;
+//   backward: log beta in registers, frame by frame; the frame's state posteriors exp(la + lb - log y - log p) summed per class in
+//             label order (fixed order) and the classes of the label sequence overwritten with scale * (y - posterior).
+// Every other class of the row already holds scale * softmax: the gradient kernels subtract no label mass from a marked utterance.
+// An utterance that is feasible by its lengths but has p = 0 (a y of exactly 0 on its only paths) ends as the infeasible ones do.
+__device__ __forceinline__ double log_add(double a, double b) {
+    const double m = fmax(a, b);
+    return m == -INFINITY ? -INFINITY : m + log(exp(a - m) + exp(b - m));
+}
+__device__ __forceinline__ double log_of(double y) { return y > 0.0 ? log(y) : -INFINITY; }
+
+template <typename T>
+__global__ __launch_bounds__(256) void ctc_rescue_kernel(const double* __restrict__ lp, double* __restrict__ alpha, const int32_t* __restrict__ in_len,
+                                                         const int32_t* __restrict__ labels, const int32_t* __restrict__ lab_len,
+                                                         float* __restrict__ nll_out, float* nll_raw, T* dlogits, int T_, int V, int ld, int Lmax,
+                                                         int W, int blank, float scale_in, const float* __restrict__ scale_div, int zero_infinity) {
+    const int b = blockIdx.x, i = threadIdx.x;
+    if (nll_raw[b] == nll_raw[b]) return;      // uniform over the workgroup
+    __shared__ double s_a[2][257], s_b[2][257], s_pb[2][256], s_pl[2][256];
+    __shared__ int s_lab[256];
+    __shared__ double s_fin[2];
+    const int Tb = in_len[b], L = lab_len[b];
+    const size_t RW = 2 * (size_t)W;
+    const double* lpb = lp + (size_t)b * T_ * RW;
+    double* ab = alpha + (size_t)b * T_ * RW;
+    const int32_t* lab = labels + (size_t)b * Lmax;
+    const bool in_row = i < W;                  // a row has W entries; L + 1 <= W of them are states
+    const int mylab = i < L ? lab[i] : -1;
+    const bool skip_in = i >= 1 && i < L && lab[i] != lab[i - 1];      // label-to-label transition into state 2i+1
+    const bool skip_out = i + 1 < L && lab[i] != lab[i + 1];           // ... out of state 2i+1
+    s_lab[i] = mylab;
+    if (i < 2) { s_a[i][0] = -INFINITY; s_a[i][256] = -INFINITY; s_b[i][256] = -INFINITY; }
+    // ---- forward.  s_a[p][i + 1] = log alpha of label state 2i+1 at the previous frame
+    double a_b = -INFINITY, a_l = -INFINITY;
+    for (int t = 0; t < Tb; ++t) {
+        const int p = t & 1;
+        f64x2 y = {0.0, 0.0};
+        if (in_row) y = *(const f64x2*)(lpb + (size_t)t * RW + 2 * i);
+        const double ly_b = log_of(y[0]), ly_l = log_of(y[1]);
+        if (t == 0) {
+            a_b = i == 0 ? ly_b : -INFINITY;
+            a_l = i == 0 ? ly_l : -INFINITY;
+        } else {
+            s_a[p][i + 1] = a_l;
+            __syncthreads();
+            const double prev = s_a[p][i];      // state 2i-1
+            const double n_b = ly_b + log_add(a_b, prev);
+            const double n_l = ly_l + log_add(log_add(a_l, a_b), skip_in ? prev : -INFINITY);
+            a_b = n_b;
+            a_l = n_l;
+        }
+        if (in_row) {
+            const f64x2 o = {a_b, a_l};
+            *(f64x2*)(ab + (size_t)t * RW + 2 * i) = o;
+        }
+    }
+    if (i == L) s_fin[0] = a_b;
+    if (i == L - 1) s_fin[1] = a_l;
+    if (L == 0 && i == 0) s_fin[1] = -INFINITY;
+    __syncthreads();
+    const double log_p = log_add(s_fin[0], s_fin[1]);
+    const bool finite = log_p != -INFINITY;
+    __syncthreads();      // everyone has read nll_raw[b] (top) before it changes
+    if (i == 0) {
+        const float nll = finite ? (float)(-log_p) : INFINITY;
+        nll_raw[b] = nll;
+        nll_out[b] = (!finite && zero_infinity) ? 0.f : nll;
+    }
+    if (!dlogits) return;
+    T* dlb = dlogits + (size_t)b * T_ * ld;
+    if (!finite) {
+        for (int t = 0; t < Tb; ++t)
+            for (int v = i; v < V; v += 256) dlb[(size_t)t * ld + v] = from_f32<T>(0.f);
+        return;
+    }
+    const float scale = scale_div ? scale_in / *scale_div : scale_in;
+    // ---- backward, and the frame's gradient.  s_a / s_b[p][i] = log beta of states 2i / 2i+1 at the frame after this one
+    double b_b = -INFINITY, b_l = -INFINITY;
+    for (int t = Tb - 1; t >= 0; --t) {
+        const int p = t & 1;
+        f64x2 y = {0.0, 0.0}, la = {-INFINITY, -INFINITY};
+        if (in_row) {
+            y = *(const f64x2*)(lpb + (size_t)t * RW + 2 * i);
+            la = *(const f64x2*)(ab + (size_t)t * RW + 2 * i);
+        }
+        const double ly_b = log_of(y[0]), ly_l = log_of(y[1]);
+        if (t == Tb - 1) {
+            b_b = i == L ? ly_b : -INFINITY;
+            b_l = i == L - 1 ? ly_l : -INFINITY;
+        } else {
+            const double nb_b = s_a[p ^ 1][i + 1], nb_l = s_b[p ^ 1][i + 1];      // states 2i+2, 2i+3
+            const double n_b = ly_b + log_add(b_b, b_l);
+            const double n_l = ly_l + log_add(log_add(b_l, nb_b), skip_out ? nb_l : -INFINITY);
+            b_b = n_b;
+            b_l = n_l;
+        }
+        s_a[p][i] = b_b;
+        s_b[p][i] = b_l;
+        // posterior of a state = alpha beta / (y p); a state that cannot be reached or cannot finish has none
+        s_pb[p][i] = (la[0] == -INFINITY || b_b == -INFINITY) ? 0.0 : exp(la[0] + b_b - ly_b - log_p);
+        s_pl[p][i] = (la[1] == -INFINITY || b_l == -INFINITY) ? 0.0 : exp(la[1] + b_l - ly_l - log_p);
+        __syncthreads();
+        T* dl = dlb + (size_t)t * ld;
+        if (i == 0) {
+            double occ = 0.0;
+            for (int j = 0; j <= L; ++j) occ += s_pb[p][j];
+            dl[blank] = from_f32<T>(scale * ((float)y[0] - (float)occ));      // every blank state has the same y
+        }
+        if (mylab >= 0) {
+            double occ = 0.0;      // positions that carry the same label share a class and write equal values
+            for (int j = 0; j < L; ++j) occ += s_lab[j] == mylab ? s_pl[p][j] : 0.0;
+            dl[mylab] = from_f32<T>(scale * ((float)y[1] - (float)occ));
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------- forced alignment (Viterbi)
 // The best single path through the lattice of kernel 1 (asr_ctc_align): the alpha recursion with max in place of +, one wave per
-// utterance, same layout (entry i = lane + 64 j, interleaved (blank, label) rows), same prefetch and the same power-of-two rescaling by the
-// column maximum (a per-frame factor does not change which predecessor wins).  Every step also writes one back-pointer byte per entry:
+// utterance, same layout (entry i = lane + 64 j, interleaved (blank, label) rows) and the same prefetch, in the LOG domain (kernel 1 with
+// LOGD): max and add cost what max and multiply do, nothing has to be rescaled, and no state can leave the fp64 range below the column
+// maximum - which a best path under blank-dominated posteriors does in the scaled linear form (the all-blank prefix is the maximum, the
+// path that spells L labels sits (p_label / p_blank)^L below it).  -inf = no path.  Every step also writes one back-pointer byte per entry:
 //   bit 0      blank state 2i:   0 = stay, 1 = from Lb[i-1]
 //   bits 1..2  label state 2i+1: 0 = stay, 1 = from Bk[i], 2 = from Lb[i-1] (skip)
 // Ties prefer the state itself, then s-1, then s-2 (strict > below).  The rows (T x W bytes) live in LDS when they fit VIT_LDS_BP,
@@ -658,14 +839,12 @@ __global__ __launch_bounds__(256) void ctc_label_fix_kernel(bf16_t* __restrict__
 // and pays LDS latency per step instead of a global round trip.
 constexpr int VIT_LDS_BP = 64 * 1024;
 
-// Returns ln of the scale taken out (or -inf once every state reached 0); fin_b / fin_l = the final column's Bk[L] and Lb[L-1] (scaled).
+// fin_b / fin_l = the final column's Bk[L] and Lb[L-1] (log-probabilities of the best paths that end there; -inf = none).
 template <int W>
-__device__ __forceinline__ double ctc_viterbi_recursion(const double* __restrict__ y, uint8_t* bp, const int32_t* __restrict__ lab,
+__device__ __forceinline__ void ctc_viterbi_recursion(const double* __restrict__ y, uint8_t* bp, const int32_t* __restrict__ lab,
                                                         int Tb, int L, int lane, double& fin_b, double& fin_l) {
     constexpr int NS = W <= 64 ? 1 : W / 64;
     constexpr ptrdiff_t RW = 2 * W;
-    int esum = 0;
-    bool dead = false;
     bool skip[NS];         // the label-to-label transition into Lb[i] exists
 #pragma unroll
     for (int j = 0; j < NS; ++j) {
@@ -679,8 +858,8 @@ __device__ __forceinline__ double ctc_viterbi_recursion(const double* __restrict
     for (int j = 0; j < NS; ++j) {
         const int i = lane + 64 * j;
         const f64x2 y0 = *(const f64x2*)(yp + 128 * j);
-        bk[j] = i == 0 ? y0[0] : 0.0;
-        lb[j] = i == 0 ? y0[1] : 0.0;
+        bk[j] = i == 0 ? y0[0] : -INFINITY;
+        lb[j] = i == 0 ? y0[1] : -INFINITY;
     }
     constexpr int CH = 8;
     constexpr int NB = NS == 1 ? 4 : 2;   // chunk buffers, as ctc_recursion (CH loads + CH byte stores per chunk)
@@ -701,44 +880,24 @@ __device__ __forceinline__ double ctc_viterbi_recursion(const double* __restrict
             for (int j = 0; j < NS; ++j) d.v[k][j] = *(const f64x2*)(yp + (ptrdiff_t)step * RW + 128 * j);
         }
     };
-    double sc = 1.0;
-    int e_pending = 0;
-    auto one_step = [&](const f64x2 (&yv)[NS], uint8_t* o, int k) {
-        double yb[NS], yl[NS];
-#pragma unroll
-        for (int j = 0; j < NS; ++j) { yb[j] = yv[j][0]; yl[j] = yv[j][1]; }
-        if ((k & 3) == 1) {
-#pragma unroll
-            for (int j = 0; j < NS; ++j) { yb[j] *= sc; yl[j] *= sc; }
-            esum += e_pending;
-        }
+    auto one_step = [&](const f64x2 (&yv)[NS], uint8_t* o) {
         double nb[NS], nl[NS];
         unsigned code[NS];
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
-            double sh = wave_shr1(lb[j]);          // Lb[i-1]
-            if (j > 0) sh = lane == 0 ? lane_bcast(lb[j > 0 ? j - 1 : 0], 63) : sh;
+            double sh = wave_shr1(lb[j]);          // Lb[i-1]; the shift leaves 0 in lane 0
+            sh = lane == 0 ? (j > 0 ? lane_bcast(lb[j > 0 ? j - 1 : 0], 63) : -INFINITY) : sh;
             const bool fb = sh > bk[j];
             double ml = lb[j];
             unsigned cl = 0u;
             if (bk[j] > ml) { ml = bk[j]; cl = 1u; }
             if (skip[j] && sh > ml) { ml = sh; cl = 2u; }
-            nb[j] = yb[j] * (fb ? sh : bk[j]);
-            nl[j] = yl[j] * ml;
+            nb[j] = yv[j][0] + (fb ? sh : bk[j]);      // -inf stays -inf: no term is ever +inf
+            nl[j] = yv[j][1] + ml;
             code[j] = (fb ? 1u : 0u) | (cl << 1);
         }
 #pragma unroll
         for (int j = 0; j < NS; ++j) { bk[j] = nb[j]; lb[j] = nl[j]; }
-        if ((k & 3) == 3) {      // rescaling: see ctc_recursion
-            unsigned hi = 0u;
-#pragma unroll
-            for (int j = 0; j < NS; ++j) hi = max(hi, max((unsigned)__double2hiint(bk[j]), (unsigned)__double2hiint(lb[j])));
-            hi = wave_max_u32<(W < 64 ? W : 64) - 1>(hi);
-            const bool zero = (hi >> 20) == 0u;
-            e_pending = zero ? 0 : (int)(hi >> 20) - 1023;
-            sc = __hiloint2double((1023 - e_pending) << 20, 0);
-            dead |= zero;
-        }
 #pragma unroll
         for (int j = 0; j < NS; ++j) o[64 * j] = (uint8_t)code[j];
     };
@@ -753,7 +912,7 @@ __device__ __forceinline__ double ctc_viterbi_recursion(const double* __restrict
         for (int i = 0; i < NB; ++i) {
             fetch(q[(i + NB - 1) % NB], yq + (i + NB - 1) * CH * RW);
 #pragma unroll
-            for (int k = 0; k < CH; ++k) one_step(q[i].v[k], oq + (i * CH + k) * W, k);
+            for (int k = 0; k < CH; ++k) one_step(q[i].v[k], oq + (i * CH + k) * W);
         }
         yq += NB * CH * RW;
         oq += NB * CH * W;
@@ -763,20 +922,19 @@ __device__ __forceinline__ double ctc_viterbi_recursion(const double* __restrict
 #pragma unroll
         for (int k = 0; k < CH; ++k) {
             if (1 + c * CH + k > nsteps) break;
-            one_step(q[0].v[k], oq + k * W, k);
+            one_step(q[0].v[k], oq + k * W);
         }
         oq += CH * W;
 #pragma unroll
         for (int i = 0; i + 1 < NB; ++i) q[i] = q[i + 1];
     }
-    fin_b = 0.0;
-    fin_l = 0.0;
+    fin_b = -INFINITY;
+    fin_l = -INFINITY;
 #pragma unroll
     for (int j = 0; j < NS; ++j) {      // L is uniform: readlane of the one register that holds each end state
         if ((L >> 6) == j) fin_b = lane_bcast(bk[j], L & 63);
         if (L > 0 && ((L - 1) >> 6) == j) fin_l = lane_bcast(lb[j], (L - 1) & 63);
     }
-    return dead ? -INFINITY : (double)esum * 0.6931471805599453;
 }
 
 // One wave per utterance: recursion, backtrace (state indices into path[]), then one pass over the frames, 64 at a time, that turns
@@ -787,7 +945,7 @@ __global__ __launch_bounds__(64) void ctc_viterbi_kernel(const double* __restric
                                                          int32_t* __restrict__ spans, float* __restrict__ token_logp, float* __restrict__ score,
                                                          int T_, int Lmax, int blank) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_bp[];
-    __shared__ double s_fin[3];
+    __shared__ double s_fin[2];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int Tb = min(max(in_len[b], 0), T_);
     const int L = min(max(lab_len[b], 0), Lmax);
@@ -805,18 +963,18 @@ __global__ __launch_bounds__(64) void ctc_viterbi_kernel(const double* __restric
     }
     if (Tb > 0 && (W >= 64 || lane < W)) {      // W = 32: half a wave
         double fb, fl;
-        const double logc = ctc_viterbi_recursion<W>(lpb, LDS_BP ? s_bp : bpg, lab, Tb, L, lane, fb, fl);
-        if (lane == 0) { s_fin[0] = fb; s_fin[1] = fl; s_fin[2] = logc; }
+        ctc_viterbi_recursion<W>(lpb, LDS_BP ? s_bp : bpg, lab, Tb, L, lane, fb, fl);
+        if (lane == 0) { s_fin[0] = fb; s_fin[1] = fl; }
     }
     __syncthreads();
     bool feasible = L == 0;      // Tb = 0
     int s = 2 * L;
     if (Tb > 0) {
-        const double fb = s_fin[0], fl = s_fin[1], logc = s_fin[2];
+        const double fb = s_fin[0], fl = s_fin[1];
         s = fb >= fl ? 2 * L : 2 * L - 1;       // ties: end in the blank
         const double best = fb >= fl ? fb : fl;
-        feasible = best > 0.0 && logc != -INFINITY;
-        if (lane == 0) score[b] = feasible ? (float)(logc + log(best)) : -INFINITY;
+        feasible = best > -INFINITY;            // a path exists: in_len >= L + adjacent repeats
+        if (lane == 0) score[b] = (float)best;
     } else if (lane == 0) {
         score[b] = feasible ? 0.f : -INFINITY;
     }
@@ -853,7 +1011,7 @@ __global__ __launch_bounds__(64) void ctc_viterbi_kernel(const double* __restric
         int pv = __shfl_up(st, 1, 64);
         if (lane == 0) pv = s_last;
         const bool tok = st > 0 && (st & 1);
-        double v = tok ? log(lpb[(size_t)t * RW + st]) : 0.0;     // the state index is the double's index in the interleaved row
+        double v = tok ? lpb[(size_t)t * RW + st] : 0.0;     // log y: the state index is the double's index in the interleaved row
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {      // inclusive scan over runs of one state (a token's frames are contiguous)
             const double u = __shfl_up(v, o, 64);
@@ -1065,8 +1223,8 @@ extern "C" int asr_ctc_fwd_bwd(const void* logits, void* dlogits, const int32_t*
             ROWS_DISPATCH(K1);
 #undef K1
         }
-    } else if (dtype == ASR_F32) ctc_lse_gather_kernel<float><<<g1, 256, 0, st>>>((const float*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
-    else ctc_lse_gather_kernel<bf16_t><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
+    } else if (dtype == ASR_F32) ctc_lse_gather_kernel<float, false><<<g1, 256, 0, st>>>((const float*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
+    else ctc_lse_gather_kernel<bf16_t, false><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
 #define AB(N) ctc_alpha_beta_kernel<N><<<B, 128, 0, st>>>(lp, alpha, beta, in_len, labels, lab_len, nll, nll_raw, T, Lmax, blank, zero_infinity)
     if (W == 32) AB(32);
     else if (W == 64) AB(64);
@@ -1076,10 +1234,16 @@ extern "C" int asr_ctc_fwd_bwd(const void* logits, void* dlogits, const int32_t*
     if (dlogits) {
         int g3 = rows < 2048 ? rows : 2048;
         if (rows_path) {
-            asr_launch_armed(ctc_label_fix_kernel, dim3(g1), dim3(256), 0, st, (bf16_t*)dlogits, lp, alpha, beta, in_len, labels, lab_len, nll_raw, B, T, V, ld, Lmax, W, blank, grad_scale, grad_scale_div);      // last kernel: may carry an armed completion event
+            ctc_label_fix_kernel<<<g1, 256, 0, st>>>((bf16_t*)dlogits, lp, alpha, beta, in_len, labels, lab_len, nll_raw, B, T, V, ld, Lmax, W, blank, grad_scale, grad_scale_div);
         } else if (dtype == ASR_F32) ctc_grad_kernel<float><<<g3, 256, lds, st>>>((const float*)logits, (float*)dlogits, lp, alpha, beta, lse, in_len, labels, lab_len, nll_raw, B, T, V, ld, Lmax, W, blank, grad_scale, asr_deterministic(), grad_scale_div);
         else ctc_grad_kernel<bf16_t><<<g3, 256, lds, st>>>((const bf16_t*)logits, (bf16_t*)dlogits, lp, alpha, beta, lse, in_len, labels, lab_len, nll_raw, B, T, V, ld, Lmax, W, blank, grad_scale, asr_deterministic(), grad_scale_div);
     }
+    if (!dlogits) ctc_frame_check_kernel<<<g1, 256, 0, st>>>(lp, alpha, beta, in_len, lab_len, nll_raw, B, T, W);
+    // utterances whose lattice left the fp64 range (marked by the kernels above): redone in the log domain; a workgroup of any other returns at once
+    if (rows_path && dlogits) {
+        asr_launch_armed(ctc_rescue_kernel<bf16_t>, dim3(B), dim3(256), 0, st, lp, alpha, in_len, labels, lab_len, nll, nll_raw, (bf16_t*)dlogits, T, V, ld, Lmax, W, blank, grad_scale, grad_scale_div, zero_infinity);      // last kernel: may carry an armed completion event
+    } else if (dtype == ASR_F32) ctc_rescue_kernel<float><<<B, 256, 0, st>>>(lp, alpha, in_len, labels, lab_len, nll, nll_raw, (float*)dlogits, T, V, ld, Lmax, W, blank, grad_scale, grad_scale_div, zero_infinity);
+    else ctc_rescue_kernel<bf16_t><<<B, 256, 0, st>>>(lp, alpha, in_len, labels, lab_len, nll, nll_raw, (bf16_t*)dlogits, T, V, ld, Lmax, W, blank, grad_scale, grad_scale_div, zero_infinity);
     ASR_CHECK_LAUNCH("asr_ctc_fwd_bwd");
     return ASR_OK;
 }
@@ -1099,7 +1263,7 @@ extern "C" int asr_xent_fwd_bwd(const void* logits, const int32_t* gold, const f
 }
 
 // ---------------------------------------------------------------------------------- forced alignment
-// workspace: the lattice of kernel 1 (B T 2W doubles), back-pointer rows (B T W bytes; used when T W > VIT_LDS_BP), lse (B T floats)
+// workspace: the lattice of kernel 1 in the log domain (B T 2W doubles), back-pointer rows (B T W bytes; used when T W > VIT_LDS_BP), lse (B T floats)
 extern "C" size_t asr_ctc_align_workspace_bytes(int B, int T, int Lmax) {
     if (B <= 0 || T <= 0) return 0;
     const size_t n = (size_t)B * T, W = (size_t)width_of(Lmax);
@@ -1126,16 +1290,16 @@ extern "C" int asr_ctc_align(const void* logits, const int32_t* in_len, const in
     if (g1 > 4096) g1 = 4096;
     const int cu_lim = asr_option(ASR_OPT_CU_LIMIT);
     if (cu_lim > 0 && g1 > 8 * cu_lim) g1 = 8 * cu_lim;
-    // kernel 1 of asr_ctc_fwd_bwd without gradient or path: the logits are read once into the linear-domain lattice
+    // kernel 1 of asr_ctc_fwd_bwd without gradient or path: the logits are read once into the lattice, kept as log-probabilities
     const int need_v = ceil_div(V / 8, 64);
     const bool rows_path = dtype == ASR_BF16 && V % 8 == 0 && ld % 8 == 0 && need_v <= 16 && ((uintptr_t)logits % 16) == 0;
     if (rows_path) {
         const int need = need_v;
-#define K1(NV) ctc_lse_gather_rows_kernel<NV, false, false><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank, nullptr, 0.f, nullptr, nullptr)
+#define K1(NV) ctc_lse_gather_rows_kernel<NV, false, false, true><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank, nullptr, 0.f, nullptr, nullptr)
         ROWS_DISPATCH(K1);
 #undef K1
-    } else if (dtype == ASR_F32) ctc_lse_gather_kernel<float><<<g1, 256, 0, st>>>((const float*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
-    else ctc_lse_gather_kernel<bf16_t><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
+    } else if (dtype == ASR_F32) ctc_lse_gather_kernel<float, true><<<g1, 256, 0, st>>>((const float*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
+    else ctc_lse_gather_kernel<bf16_t, true><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
     const bool lds_bp = (size_t)T * W <= (size_t)VIT_LDS_BP;
     const size_t lds = lds_bp ? (size_t)T * W : (size_t)VIT_LDS_BP;
 #define VIT(N, M)                                                                                                                        \

@@ -233,7 +233,9 @@ int asr_sdpa_dropout_mask(uint8_t* mask, int B, int H, int Tq, int Tk, float dro
  * multiple of 64 elements so that every row starts on a 128-byte line - with V = 4232 the head GEMM that writes them is 14 %
  * faster; columns V .. ld are never read or written);  in_len: (B) int32 frames per utterance (<= T);
  * labels: (B, Lmax) int32 padded; lab_len: (B) int32 (<= Lmax <= 255).
- * nll: (B) f32 = -log p(labels | x) (+inf when infeasible; 0 if zero_infinity).
+ * nll: (B) f32 = -log p(labels | x) (+inf when infeasible, i.e. in_len < L + number of adjacent repeats; 0 if zero_infinity).
+ * The lattice runs in a scaled linear domain; an utterance that leaves its fp64 range (long labels under blank-dominated
+ * posteriors) is redone in the log domain, so a feasible utterance never reads as infeasible.
  * dlogits: (B, T, V) `dtype`, same row stride (may alias logits) = scale * d(sum_b nll_b)/dlogits,
  * rows t >= in_len[b] are 0.  If dlogits is NULL only nll is computed.
  * scale = grad_scale, or grad_scale / *grad_scale_div when grad_scale_div (a DEVICE f32 scalar) is not NULL: under data
