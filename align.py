@@ -16,6 +16,11 @@ Model flags are train.py's (same parser as transcribe.py); the model needs the C
                    build_dataloader reads - the output can go straight into train.py.  Kept: lines with tokens whose recording could be
                    aligned and whose confidence is at least --min_confidence
   --part           train (default), dev or test: the collector file's part
+  --filler         PENALTY (nats, >= 0; default: off): audio the script does not cover (a spoken title, an advertisement, an ad-lib) may
+                   rest in filler frames in front of a line and behind the last one, where the blank lies more than PENALTY below the
+                   frame's best class (model.align_long's filler).  One JSON line {"filler": true, "start_s", "end_s", "frames",
+                   "before_line"} per run of such frames is printed after the transcript lines; the wav cuts stay a line's own tokens
+  --filler_scope   lines (default: in front of every line) or tokens (in front of every token); needs --filler
   --vad_energy_threshold, --vad_energy_mean_scale, --vad_frames_context, --vad_proportion_threshold, --min_silence_s, --min_speech_s,
   --pad_s, --max_segment_s      the VAD's and the segmenter's options, as transcribe.py --long=1
 The recording is cut at its pauses by the energy VAD, its segments go through the CTC head, and one launch aligns the whole script (at most
@@ -42,7 +47,8 @@ from asr_chinese_e2e_amd.data_handler import resample as resample_mod  # noqa: E
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 from transcribe import SEGMENT_FLAGS, VAD_FLAGS, _finite, cmvn_path, load_model  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wav", "text", "cmvn", "frontend", "resample", "batch_size", "confidence", "min_confidence", "out_prefix", "part") + tuple(VAD_FLAGS) + SEGMENT_FLAGS
+CLI_KEYS = ("ckpt", "wav", "text", "cmvn", "frontend", "resample", "batch_size", "confidence", "min_confidence", "out_prefix", "part", "filler",
+            "filler_scope") + tuple(VAD_FLAGS) + SEGMENT_FLAGS
 
 
 def align_options(cli):
@@ -72,6 +78,28 @@ def align_options(cli):
     if part not in ("train", "dev", "test"):
         raise SystemExit(f"align.py: --part must be train, dev or test (got {part!r})")
     return vad, seg, min_conf, conf, part
+
+
+def filler_options(cli):
+    """--filler / --filler_scope -> the keywords model.align_long takes for them ({} when the filler is off); SystemExit naming the flag
+    for a penalty that is no finite number >= 0, an unknown scope, or a scope without a penalty."""
+    from asr_chinese_e2e_amd.align_long import FILLER_SCOPES
+    filler, scope = cli.get("filler"), cli.get("filler_scope")
+    if scope is not None and scope not in FILLER_SCOPES:
+        raise SystemExit(f"align.py: --filler_scope must be one of {', '.join(FILLER_SCOPES)} (got {scope!r})")
+    if filler is None:
+        if scope is not None:
+            raise SystemExit(f"align.py: --filler_scope={scope} needs --filler=PENALTY")
+        return {}
+    if isinstance(filler, bool) or not isinstance(filler, (int, float)) or not np.isfinite(filler) or filler < 0:
+        raise SystemExit(f"align.py: --filler must be a finite penalty >= 0 in nats (got {filler!r})")
+    return {"filler": float(filler), "filler_scope": scope or "lines"}
+
+
+def filler_lines(res):
+    """One JSON line per filler run of align_long's result (none without --filler), times never past the recording's end."""
+    return [{"filler": True, "start_s": min(f["start_s"], res["duration_s"]), "end_s": min(f["end_s"], res["duration_s"]), "frames": f["frames"],
+             "before_line": f["before_line"]} for f in res.get("fillers", ())]
 
 
 def read_lines(path):
@@ -123,7 +151,7 @@ def write_collector(out_prefix, part, lines, pcm, ch, sr):
     return paths
 
 
-def align_file(model, parser, path, texts, vad, seg_kw, bs, resample, sample_rate, conf, min_conf, out_prefix, part):
+def align_file(model, parser, path, texts, vad, seg_kw, bs, resample, sample_rate, conf, min_conf, out_prefix, part, fill_kw=None):
     pcm, ch, sr = read_pcm(path)
     if sr != sample_rate:
         if not resample:
@@ -137,11 +165,12 @@ def align_file(model, parser, path, texts, vad, seg_kw, bs, resample, sample_rat
     pcm_to_float(pcm, ch, x)
     wav = torch.from_numpy(x.reshape(1, -1)) if n else torch.zeros(1, 1)
     try:
-        res = model.align_long(parser, wav, [n], [texts], vad=vad, batch_size=bs, source_rate=sr if sr != sample_rate else None, confidence=conf, **seg_kw)[0]
+        res = model.align_long(parser, wav, [n], [texts], vad=vad, batch_size=bs, source_rate=sr if sr != sample_rate else None, confidence=conf, **seg_kw,
+                               **(fill_kw or {}))[0]
     except ValueError as e:
         raise SystemExit(f"align.py: {e}") from e
     lines = result_lines(path, n, sr, res, min_conf)
-    for line in lines:
+    for line in lines[:-1] + filler_lines(res) + lines[-1:]:      # the transcript lines, the filler runs, the summary
         print(json.dumps(line, ensure_ascii=False), flush=True)
     if out_prefix:
         write_collector(str(out_prefix), part, lines[:-1], pcm, ch, sr)
@@ -151,6 +180,7 @@ def align_file(model, parser, path, texts, vad, seg_kw, bs, resample, sample_rat
 def align(**flags):
     cli = {k: flags.pop(k) for k in CLI_KEYS if k in flags}
     vad, seg_kw, min_conf, conf, part = align_options(cli)
+    fill_kw = filler_options(cli)
     texts = read_lines(str(cli["text"]))
     config = TrainConfig()
     config.fn_build(flags)
@@ -167,7 +197,7 @@ def align(**flags):
                          lfr_m=config.lfr_m, lfr_n=config.lfr_n, frontend=str(cli.get("frontend", "reference")), **parser_norm(cmvn_path(cli)))
     out_prefix = cli.get("out_prefix") if cli.get("out_prefix") not in (None, "", False) else None
     align_file(model, parser, str(cli["wav"]), texts, vad, seg_kw, max(1, int(cli.get("batch_size", 16))), bool(int(cli.get("resample", 0) or 0)),
-               config.sample_rate, conf, min_conf, out_prefix, part)
+               config.sample_rate, conf, min_conf, out_prefix, part, fill_kw)
 
 
 if __name__ == "__main__":

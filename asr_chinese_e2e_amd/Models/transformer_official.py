@@ -659,14 +659,18 @@ class _SpeechTransformer(BaseModel):
                                min_speech_s=min_speech_s, pad_s=pad_s, max_segment_s=max_segment_s, **transcribe_kw)
 
     def align_long(self, parser, wav, wav_len, texts, vad=None, batch_size=16, source_rate=None, min_silence_s=0.3, min_speech_s=0.1, pad_s=0.1,
-                   max_segment_s=20.0, confidence="post_mean", max_bytes=4 << 30):
+                   max_segment_s=20.0, confidence="post_mean", max_bytes=4 << 30, filler=None, filler_scope="lines"):
         """Whole recordings and their transcripts in, per-token and per-line times out (align_long.align_long): the VAD's segments go
         through the CTC head in time order, their frames are laid end to end on the device, and one asr_ctc_align_long launch aligns every
         recording's transcript (a string, a list of lines or a list of id lists; up to 8192 tokens) to them.  Per recording {"score",
-        "duration_s", "frames", "tokens", "lines", "segments"}; a transcript that does not fit its frames comes back with None times."""
+        "duration_s", "frames", "tokens", "lines", "segments"}; a transcript that does not fit its frames comes back with None times.
+        filler (a penalty in nats; None = off) lets frames the transcript does not cover rest in wide blanks in front of every line
+        (filler_scope "lines") or token ("tokens") and behind the last token (asr_ctc_align_long_filler): the results gain "fillers" and
+        "filler_frames"."""
         from ..align_long import align_long
         return align_long(self, parser, wav, wav_len, texts, vad=vad, batch_size=batch_size, source_rate=source_rate, min_silence_s=min_silence_s,
-                          min_speech_s=min_speech_s, pad_s=pad_s, max_segment_s=max_segment_s, confidence=confidence, max_bytes=max_bytes)
+                          min_speech_s=min_speech_s, pad_s=pad_s, max_segment_s=max_segment_s, confidence=confidence, max_bytes=max_bytes, filler=filler,
+                          filler_scope=filler_scope)
 
     def _hyp_dicts(self, ids, scores, timestamps, ctc_logits, wave_len, biases=None, bias_key="bias", confidence=None):
         """transcribe's result dicts for the best ids / score of each utterance; ctc_logits() -> (B, T, V) is called for timestamps only.

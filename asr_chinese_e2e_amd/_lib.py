@@ -191,6 +191,7 @@ SIGNATURES = {
     "asr_segment_gather": (I, [P, I, P, P, P, P, I, I, P]),
     "asr_ctc_align_long_workspace_bytes": (Z, [I, I, I]),
     "asr_ctc_align_long": (I, [P] * 10 + [Z, I, I, I, I, I, P]),
+    "asr_ctc_align_long_filler": (I, [P] * 13 + [Z, I, I, I, I, I, P]),
 }
 
 

@@ -15,6 +15,12 @@
 // moves down by at most one per frame, so AL_F frames need the AL_F + 1 columns below the current one: that window of the back-pointer
 // rows is staged into LDS by the whole workgroup, one thread walks it, and the workgroup writes the block's frames of path[].
 // Spans come from a pass with a thread per frame, the token sums from a pass with a thread per token over its run, ascending t.
+//
+// FILL (asr_ctc_align_long_filler; the definition is tests/align_filler_ref.py): the blank states whose flag is set (gap[i] for state 2i,
+// gap_tail for 2L) are wide: on frame t they emit star[t] where star[t] > lp(t, blank), the blank's value otherwise.  The blank column,
+// lse[t] and star[t] are the same for the whole workgroup, so the wide emission is ONE more value per frame and every pair selects
+// between two uniform values by its flag, which - like skip[] - does not change over the frames.  Nothing more is stored per frame: the
+// per-block pass of the backtrace, which has a thread per frame, recomputes the choice and writes -2 for a filler frame.
 #include "asr_common.h"
 
 namespace {
@@ -43,10 +49,18 @@ __device__ __forceinline__ int al_row_bytes(int L) { return (max(L, 1) + 63) & ~
 __host__ __device__ constexpr int al_threads(int P) { return P == 1 ? 64 : P == 2 ? 128 : P == 4 ? 256 : 1024; }
 __device__ __forceinline__ int al_class(int L) { return L <= 64 ? 1 : L <= 256 ? 2 : L <= 1024 ? 4 : 8; }
 
-template <typename T, int P>
+template <bool FILL> struct al_star { float v; };      // a ring slot's star[t]: no member without FILL
+template <> struct al_star<false> {};
+
+// what a wide blank state emits on a frame whose blank emits eb (strict >: the blank wins ties)
+__device__ __forceinline__ float al_wide(float star, float eb) { return star > eb ? star : eb; }
+
+template <typename T, int P, bool FILL>
 __global__ __launch_bounds__(al_threads(P)) void ctc_align_long_kernel(const T* __restrict__ rows, const float* __restrict__ lse,
                                                                        const int32_t* __restrict__ row_off, const int32_t* __restrict__ labels,
-                                                                       const int32_t* __restrict__ lab_off, int32_t* __restrict__ path,
+                                                                       const int32_t* __restrict__ lab_off, const float* __restrict__ star,
+                                                                       const uint8_t* __restrict__ gap,
+                                                                       const uint8_t* __restrict__ gap_tail, int32_t* __restrict__ path,
                                                                        int32_t* __restrict__ spans, float* __restrict__ tok,
                                                                        double* __restrict__ score, uint8_t* __restrict__ ws, size_t ws_bytes,
                                                                        int V, int ld, int blank) {
@@ -83,6 +97,9 @@ __global__ __launch_bounds__(al_threads(P)) void ctc_align_long_kernel(const T* 
     int32_t* pth = path + max(r0, 0);
     int32_t* spn = spans + (size_t)max(l0, 0) * 2;
     float* tk = tok + (size_t)max(l0, 0) * 3;
+    const float* sr = FILL ? star + max(r0, 0) : nullptr;
+    const uint8_t* gp = FILL ? gap + max(l0, 0) : nullptr;
+    const bool wtail = FILL && gap_tail[r] != 0;
 
     for (int i = tid; i < L; i += NT) {      // overwritten below for a feasible alignment
         spn[2 * i] = -1;
@@ -98,11 +115,16 @@ __global__ __launch_bounds__(al_threads(P)) void ctc_align_long_kernel(const T* 
             double v = (L == 0 && Lraw == 0 && ws_ok) ? 0.0 : -INFINITY;      // T = 0 is feasible iff L = 0
             if (L == 0 && !too_long)
                 for (int t = 0; t < Tn; ++t) {
-                    const double e = (double)(al_ld(rw + (size_t)t * ld + blank) - ls[t]);
+                    float eb = al_ld(rw + (size_t)t * ld + blank) - ls[t];
+                    if (FILL && wtail) eb = al_wide(sr[t], eb);
+                    const double e = (double)eb;
                     v = t == 0 ? e : v + e;
                 }
             score[r] = v;
         }
+        if (FILL && wtail && L == 0 && !too_long)      // the one state is the tail; pth[t] = -1 above came from the same thread
+            for (int t = tid; t < Tn; t += NT)
+                if (sr[t] > al_ld(rw + (size_t)t * ld + blank) - ls[t]) pth[t] = -2;
         return;
     }
 
@@ -110,32 +132,38 @@ __global__ __launch_bounds__(al_threads(P)) void ctc_align_long_kernel(const T* 
     const int i0 = tid * P;
     const bool active = wave * 64 * P < L;      // wave-uniform: a wave without pairs only keeps the barriers
     unsigned cls[P];      // byte offsets of the thread's labels in a row
-    bool skip[P];
+    bool skip[P], wide[P];
 #pragma unroll
     for (int j = 0; j < P; ++j) {
         const int i = i0 + j;
         const int c = i < L ? lab[i] : blank;
         cls[j] = (unsigned)min(max(c, 0), V - 1) * (unsigned)sizeof(T);
         skip[j] = i >= 1 && i < L && lab[i] != lab[i - 1];
+        wide[j] = false;
+        if constexpr (FILL) wide[j] = i < L && gp[i] != 0;
     }
     const int jl = L - 1 - i0;      // the pair L-1 within this thread, if 0 <= jl < P
     double bk[P], lb[P], tl = -INFINITY;
     {
         const float l = ls[0];
-        const float e0 = al_ld(rw + blank) - l, e1 = al_ld((const T*)((const char*)rw + cls[0])) - l;
+        float e0 = al_ld(rw + blank) - l;
+        const float e1 = al_ld((const T*)((const char*)rw + cls[0])) - l;
+        if constexpr (FILL)
+            if (gp[0] != 0) e0 = al_wide(sr[0], e0);      // state 0 of the recording (used by thread 0 alone)
 #pragma unroll
         for (int j = 0; j < P; ++j) {
             bk[j] = (tid == 0 && j == 0) ? (double)e0 : -INFINITY;
             lb[j] = (tid == 0 && j == 0) ? (double)e1 : -INFINITY;
         }
     }
-    struct Ring { float lse; T eb, el[P]; };      // as loaded: a conversion at load time would wait for the load
+    struct Ring { float lse; T eb, el[P]; al_star<FILL> st; };      // as loaded: a conversion at load time would wait for the load
     Ring q[AL_DEPTH];
     auto fetch = [&](Ring& d, int t) {
         t = min(t, Tn - 1);
         const T* p = rw + (size_t)t * ld;
         d.lse = ls[t];
         d.eb = p[blank];
+        if constexpr (FILL) d.st.v = sr[t];
 #pragma unroll
         for (int j = 0; j < P; ++j) d.el[j] = *(const T*)((const char*)p + cls[j]);
     };
@@ -157,7 +185,10 @@ __global__ __launch_bounds__(al_threads(P)) void ctc_align_long_kernel(const T* 
             }
             if (active) {
                 if (tid == 0) up = -INFINITY;
-                const double eb = (double)(to_f32<T>(q[k].eb) - q[k].lse);
+                const float ebf = to_f32<T>(q[k].eb) - q[k].lse;
+                const double eb = (double)ebf;
+                double ew = eb;      // what a wide blank emits on this frame: uniform, like eb
+                if constexpr (FILL) ew = (double)al_wide(q[k].st.v, ebf);
                 double lsel = -INFINITY;      // Lb[L-1] of the previous frame, in the thread that owns it
                 code_t code = 0;
                 double carry = up;
@@ -171,14 +202,14 @@ __global__ __launch_bounds__(al_threads(P)) void ctc_align_long_kernel(const T* 
                     unsigned cl = 0u;
                     if (b > ml) { ml = b; cl = 1u; }
                     if (skip[j] && carry > ml) { ml = carry; cl = 2u; }
-                    bk[j] = (fb ? carry : b) + eb;
+                    bk[j] = (fb ? carry : b) + (FILL && wide[j] ? ew : eb);
                     lb[j] = ml + el;
                     unsigned cj = (fb ? 1u : 0u) | (cl << 1);
                     if (j == jl && lsel > tl) cj |= 8u;
                     code |= (code_t)cj << (8 * j);
                     carry = l;
                 }
-                tl = (lsel > tl ? lsel : tl) + eb;
+                tl = (lsel > tl ? lsel : tl) + (wtail ? ew : eb);
                 if (i0 < Wr) *(code_t*)(bp + (size_t)t * Wr + i0) = code;
                 fetch(q[k], t + AL_DEPTH);      // the slot's next frame
             }
@@ -230,7 +261,14 @@ __global__ __launch_bounds__(al_threads(P)) void ctc_align_long_kernel(const T* 
         s = s_state;
         for (int k = tid; k < nrow; k += NT) {
             const int st = s_path[k];
-            pth[tlo + k] = (st & 1) ? min(st >> 1, L - 1) : -1;
+            int out = (st & 1) ? min(st >> 1, L - 1) : -1;
+            if constexpr (FILL) {
+                if (!(st & 1) && (st >= 2 * L ? wtail : gp[max(st >> 1, 0)] != 0)) {
+                    const int t = tlo + k;
+                    if (sr[t] > al_ld(rw + (size_t)t * ld + blank) - ls[t]) out = -2;
+                }
+            }
+            pth[tlo + k] = out;
         }
     }
     __syncthreads();      // path[] of the whole recording
@@ -267,28 +305,54 @@ extern "C" size_t asr_ctc_align_long_workspace_bytes(int R, int T_total, int Lma
     return (size_t)T_total * row + 64;
 }
 
+// validation shared by the two entry points (what = the entry point's name, for the message)
+static int al_validate(const char* what, const void* rows, const float* lse, const int32_t* row_off, const int32_t* labels, const int32_t* lab_off,
+                       const int32_t* path, const int32_t* spans, const float* tok, const double* score, const void* ws, size_t ws_bytes, int R,
+                       int V, int ld, int dtype, int blank) {
+    if (!rows || !lse || !row_off || !labels || !lab_off || !path || !spans || !tok || !score || !ws) ASR_FAIL(ASR_EINVAL, "%s: null pointer", what);
+    if (R <= 0 || V <= 1 || blank < 0 || blank >= V) ASR_FAIL(ASR_EINVAL, "%s: bad shape R=%d V=%d blank=%d", what, R, V, blank);
+    if (ld < V) ASR_FAIL(ASR_EINVAL, "%s: row stride ld=%d below V=%d", what, ld, V);
+    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "%s: dtype %d", what, dtype);
+    if (ws_bytes < 64) ASR_FAIL(ASR_EINVAL, "%s: workspace %zu < 64", what, ws_bytes);
+    if (((uintptr_t)ws & 15) || ((uintptr_t)score & 7) || ((uintptr_t)rows & (dtype == ASR_F32 ? 3 : 1))) ASR_FAIL(ASR_EINVAL, "%s: misaligned pointer", what);
+    return 0;
+}
+
+// one launch per instantiation: a workgroup whose recording belongs to another one leaves at once
+#define AL_LAUNCH(TY, PP, FF)                                                                                                                  \
+    ctc_align_long_kernel<TY, PP, FF><<<R, al_threads(PP), 0, st>>>((const TY*)rows, lse, row_off, labels, lab_off, star, gap, gap_tail, path, \
+                                                                      spans, tok, score, (uint8_t*)ws, ws_bytes, V, ld, blank)
+#define AL_LAUNCH_ALL(FF)                                                                                                    \
+    if (dtype == ASR_F32) {                                                                                                  \
+        AL_LAUNCH(float, 1, FF); AL_LAUNCH(float, 2, FF); AL_LAUNCH(float, 4, FF); AL_LAUNCH(float, 8, FF);                  \
+    } else {                                                                                                                 \
+        AL_LAUNCH(bf16_t, 1, FF); AL_LAUNCH(bf16_t, 2, FF); AL_LAUNCH(bf16_t, 4, FF); AL_LAUNCH(bf16_t, 8, FF);              \
+    }
+
 extern "C" int asr_ctc_align_long(const void* rows, const float* lse, const int32_t* row_off, const int32_t* labels, const int32_t* lab_off,
                                   int32_t* path, int32_t* spans, float* tok, double* score, void* ws, size_t ws_bytes, int R, int V, int ld,
                                   int dtype, int blank, void* stream) {
-    if (!rows || !lse || !row_off || !labels || !lab_off || !path || !spans || !tok || !score || !ws)
-        ASR_FAIL(ASR_EINVAL, "asr_ctc_align_long: null pointer");
-    if (R <= 0 || V <= 1 || blank < 0 || blank >= V) ASR_FAIL(ASR_EINVAL, "asr_ctc_align_long: bad shape R=%d V=%d blank=%d", R, V, blank);
-    if (ld < V) ASR_FAIL(ASR_EINVAL, "asr_ctc_align_long: row stride ld=%d below V=%d", ld, V);
-    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "asr_ctc_align_long: dtype %d", dtype);
-    if (ws_bytes < 64) ASR_FAIL(ASR_EINVAL, "asr_ctc_align_long: workspace %zu < 64", ws_bytes);
-    if (((uintptr_t)ws & 15) || ((uintptr_t)score & 7) || ((uintptr_t)rows & (dtype == ASR_F32 ? 3 : 1)))
-        ASR_FAIL(ASR_EINVAL, "asr_ctc_align_long: misaligned pointer");
+    if (int rc = al_validate("asr_ctc_align_long", rows, lse, row_off, labels, lab_off, path, spans, tok, score, ws, ws_bytes, R, V, ld, dtype, blank)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    // one launch per instantiation: a workgroup whose recording belongs to another one leaves at once
-#define AL_LAUNCH(TY, PP)                                                                                                                      \
-    ctc_align_long_kernel<TY, PP><<<R, al_threads(PP), 0, st>>>((const TY*)rows, lse, row_off, labels, lab_off, path, spans, tok, score,     \
-                                                                  (uint8_t*)ws, ws_bytes, V, ld, blank)
-    if (dtype == ASR_F32) {
-        AL_LAUNCH(float, 1); AL_LAUNCH(float, 2); AL_LAUNCH(float, 4); AL_LAUNCH(float, 8);
-    } else {
-        AL_LAUNCH(bf16_t, 1); AL_LAUNCH(bf16_t, 2); AL_LAUNCH(bf16_t, 4); AL_LAUNCH(bf16_t, 8);
-    }
-#undef AL_LAUNCH
+    const float* star = nullptr;
+    const uint8_t *gap = nullptr, *gap_tail = nullptr;      // never read without FILL
+    AL_LAUNCH_ALL(false)
     ASR_CHECK_LAUNCH("asr_ctc_align_long");
     return 0;
 }
+
+extern "C" int asr_ctc_align_long_filler(const void* rows, const float* lse, const float* star, const int32_t* row_off, const int32_t* labels,
+                                         const int32_t* lab_off, const uint8_t* gap, const uint8_t* gap_tail, int32_t* path, int32_t* spans,
+                                         float* tok, double* score, void* ws, size_t ws_bytes, int R, int V, int ld, int dtype, int blank,
+                                         void* stream) {
+    if (!star || !gap || !gap_tail) ASR_FAIL(ASR_EINVAL, "asr_ctc_align_long_filler: null pointer");
+    if (int rc = al_validate("asr_ctc_align_long_filler", rows, lse, row_off, labels, lab_off, path, spans, tok, score, ws, ws_bytes, R, V, ld, dtype, blank))
+        return rc;
+    if ((uintptr_t)star & 3) ASR_FAIL(ASR_EINVAL, "asr_ctc_align_long_filler: misaligned pointer");
+    hipStream_t st = (hipStream_t)stream;
+    AL_LAUNCH_ALL(true)
+    ASR_CHECK_LAUNCH("asr_ctc_align_long_filler");
+    return 0;
+}
+#undef AL_LAUNCH_ALL
+#undef AL_LAUNCH

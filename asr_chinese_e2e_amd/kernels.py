@@ -1489,42 +1489,50 @@ def ctc_align_long_workspace_bytes(R, T_total, Lmax):
     return int(lib.asr_ctc_align_long_workspace_bytes(int(R), int(T_total), int(Lmax)))
 
 
-def ctc_align_long(rows, lse, row_off, labels, lab_off, blank=0, ws=None):
-    """CTC forced alignment of whole recordings in one call (asr_ctc_align_long; the definition is tests/align_long_ref.py, and the kernel
-    agrees with it bit for bit).  rows (sum T, V) f32 / bf16 on the device, dense or rows of a buffer padded to ld >= V elements; lse
-    (sum T) f32 from ctc_frame_stats over the same rows; row_off / lab_off: R + 1 host integers (lists or numpy), recording r owns rows
-    [row_off[r], row_off[r+1]) and labels [lab_off[r], lab_off[r+1]); labels: host integers (sum L).  Everything the kernel would have to
-    trust is checked here, on the host: ascending offsets that end at the tables' sizes, at most ALIGN_LONG_MAX_LABELS labels per recording,
-    labels in [0, V) other than the blank.  Returns device tensors (path (sum T) int32: the token's index within its recording per frame,
-    -1 on blank frames; spans (sum L, 2) int32; tok (sum L, 3) f32 = the sum, the largest and the smallest log posterior over the token's
-    frames; score (R) f64).  An infeasible recording has score -inf, spans -1, tok -inf and a path of -1."""
+def _ctc_align_long(name, rows, lse, row_off, labels, lab_off, blank, ws, fill=None):
+    """The host checks and the launch of ctc_align_long (fill None) and ctc_align_long_filler (fill = (star, gap, gap_tail))."""
     import numpy as np
     if rows.dim() != 2 or rows.stride(1) != 1:
-        raise ValueError(f"ctc_align_long: rows must be (sum T, V) with unit column stride, got {tuple(rows.shape)} / {rows.stride()}")
+        raise ValueError(f"{name}: rows must be (sum T, V) with unit column stride, got {tuple(rows.shape)} / {rows.stride()}")
     Tt, V = rows.shape
     ld = rows.stride(0) if Tt > 1 else V
     if ld < V:
-        raise ValueError(f"ctc_align_long: row stride {ld} below V = {V}")
+        raise ValueError(f"{name}: row stride {ld} below V = {V}")
     _chk_f32(lse)
     if lse.numel() != Tt:
-        raise ValueError(f"ctc_align_long: lse holds {lse.numel()} values for {Tt} rows")
+        raise ValueError(f"{name}: lse holds {lse.numel()} values for {Tt} rows")
     ro, lo = np.asarray(row_off, dtype=np.int64).reshape(-1), np.asarray(lab_off, dtype=np.int64).reshape(-1)
     lab = np.asarray(labels, dtype=np.int64).reshape(-1)
     R = ro.shape[0] - 1
     if R < 1 or lo.shape[0] != R + 1:
-        raise ValueError(f"ctc_align_long: row_off holds {ro.shape[0]} and lab_off {lo.shape[0]} entries: R + 1 each, R >= 1")
+        raise ValueError(f"{name}: row_off holds {ro.shape[0]} and lab_off {lo.shape[0]} entries: R + 1 each, R >= 1")
     if ro[0] != 0 or lo[0] != 0 or (np.diff(ro) < 0).any() or (np.diff(lo) < 0).any() or ro[-1] != Tt or lo[-1] != lab.shape[0]:
-        raise ValueError(f"ctc_align_long: offsets must ascend from 0 to the {Tt} rows and the {lab.shape[0]} labels (got {ro.tolist()}, {lo.tolist()})")
+        raise ValueError(f"{name}: offsets must ascend from 0 to the {Tt} rows and the {lab.shape[0]} labels (got {ro.tolist()}, {lo.tolist()})")
     Lmax = int(np.diff(lo).max())
     if Lmax > _lib.ALIGN_LONG_MAX_LABELS:
         r = int(np.argmax(np.diff(lo)))
-        raise ValueError(f"ctc_align_long: recording {r} has {Lmax} labels, the limit is {_lib.ALIGN_LONG_MAX_LABELS}")
+        raise ValueError(f"{name}: recording {r} has {Lmax} labels, the limit is {_lib.ALIGN_LONG_MAX_LABELS}")
     if not 0 <= int(blank) < V:
-        raise ValueError(f"ctc_align_long: blank = {blank} outside [0, {V})")
+        raise ValueError(f"{name}: blank = {blank} outside [0, {V})")
     bad = (lab < 0) | (lab >= V) | (lab == int(blank))
     if bad.any():
         i = int(np.argmax(bad))
-        raise ValueError(f"ctc_align_long: label {i} = {int(lab[i])}: labels are classes in [0, {V}) other than the blank ({int(blank)})")
+        raise ValueError(f"{name}: label {i} = {int(lab[i])}: labels are classes in [0, {V}) other than the blank ({int(blank)})")
+    if fill is not None:      # star (sum T) f32 without NaN, gap one flag per label, gap_tail one per recording
+        star, gap, gap_tail = fill
+        if not torch.is_tensor(star) or star.dtype != torch.float32 or star.dim() != 1 or star.numel() != Tt or not star.is_contiguous():
+            raise ValueError(f"{name}: star must be a contiguous f32 tensor of {Tt} values, one per row (got {getattr(star, 'dtype', type(star))}, "
+                             f"{tuple(getattr(star, 'shape', ()))})")
+        if star.device != rows.device:
+            raise ValueError(f"{name}: star lives on {star.device}, the rows on {rows.device}")
+        if Tt and bool(torch.isnan(star).any()):
+            raise ValueError(f"{name}: star holds NaN")
+        g, gt = np.asarray(gap).reshape(-1), np.asarray(gap_tail).reshape(-1)
+        if g.shape[0] != lab.shape[0]:
+            raise ValueError(f"{name}: gap holds {g.shape[0]} flags for {lab.shape[0]} labels")
+        if gt.shape[0] != R:
+            raise ValueError(f"{name}: gap_tail holds {gt.shape[0]} flags for {R} recordings")
+        g, gt = (g != 0).astype(np.uint8), (gt != 0).astype(np.uint8)
     dev = rows.device
     off = torch.from_numpy(np.concatenate((ro, lo)).astype(np.int32)).to(dev)
     dlab = torch.from_numpy(lab.astype(np.int32) if lab.shape[0] else np.zeros(1, np.int32)).to(dev)
@@ -1537,7 +1545,39 @@ def ctc_align_long(rows, lse, row_off, labels, lab_off, blank=0, ws=None):
     w = ws.get(nbytes) if ws is not None else torch.empty(max(nbytes, 64), dtype=torch.uint8, device=dev)
     if Tt == 0:      # no row to point at: the kernel reads none
         rows, lse = torch.zeros(1, V, dtype=rows.dtype, device=dev), torch.zeros(1, dtype=torch.float32, device=dev)
-    timed("ctc_align_long", 0.0, lambda: check(
-        lib.asr_ctc_align_long(_p(rows), _p(lse), _p(off[:R + 1]), _p(dlab), _p(off[R + 1:]), _p(path), _p(spans), _p(tok), _p(score), _p(w), w.numel(),
-                               R, V, ld, _dt(rows), int(blank), _stream()), "asr_ctc_align_long"))
+    if fill is None:
+        timed("ctc_align_long", 0.0, lambda: check(
+            lib.asr_ctc_align_long(_p(rows), _p(lse), _p(off[:R + 1]), _p(dlab), _p(off[R + 1:]), _p(path), _p(spans), _p(tok), _p(score), _p(w), w.numel(),
+                                   R, V, ld, _dt(rows), int(blank), _stream()), "asr_ctc_align_long"))
+    else:
+        flags = torch.from_numpy(np.concatenate((g if g.shape[0] else np.zeros(1, np.uint8), gt))).to(dev)
+        ng = max(g.shape[0], 1)
+        if Tt == 0:
+            star = torch.zeros(1, dtype=torch.float32, device=dev)
+        timed("ctc_align_long_filler", 0.0, lambda: check(
+            lib.asr_ctc_align_long_filler(_p(rows), _p(lse), _p(star), _p(off[:R + 1]), _p(dlab), _p(off[R + 1:]), _p(flags), _p(flags[ng:]), _p(path), _p(spans),
+                                          _p(tok), _p(score), _p(w), w.numel(), R, V, ld, _dt(rows), int(blank), _stream()), "asr_ctc_align_long_filler"))
     return path[:Tt], spans[:lab.shape[0]], tok[:lab.shape[0]], score
+
+
+def ctc_align_long(rows, lse, row_off, labels, lab_off, blank=0, ws=None):
+    """CTC forced alignment of whole recordings in one call (asr_ctc_align_long; the definition is tests/align_long_ref.py, and the kernel
+    agrees with it bit for bit).  rows (sum T, V) f32 / bf16 on the device, dense or rows of a buffer padded to ld >= V elements; lse
+    (sum T) f32 from ctc_frame_stats over the same rows; row_off / lab_off: R + 1 host integers (lists or numpy), recording r owns rows
+    [row_off[r], row_off[r+1]) and labels [lab_off[r], lab_off[r+1]); labels: host integers (sum L).  Everything the kernel would have to
+    trust is checked here, on the host: ascending offsets that end at the tables' sizes, at most ALIGN_LONG_MAX_LABELS labels per recording,
+    labels in [0, V) other than the blank.  Returns device tensors (path (sum T) int32: the token's index within its recording per frame,
+    -1 on blank frames; spans (sum L, 2) int32; tok (sum L, 3) f32 = the sum, the largest and the smallest log posterior over the token's
+    frames; score (R) f64).  An infeasible recording has score -inf, spans -1, tok -inf and a path of -1."""
+    return _ctc_align_long("ctc_align_long", rows, lse, row_off, labels, lab_off, blank, ws)
+
+
+def ctc_align_long_filler(rows, lse, star, row_off, labels, lab_off, gap, gap_tail, blank=0, ws=None):
+    """ctc_align_long with filler frames for audio the transcript does not cover (asr_ctc_align_long_filler; the definition is
+    tests/align_filler_ref.py, and the kernel agrees with it bit for bit).  star (sum T) f32 on the device, indexed like lse: the
+    log-probability of "anything" per frame; gap: host flags (sum L), gap[i] marks the blank in front of label i as wide; gap_tail: host
+    flags (R), the blank behind a recording's last label.  A wide blank emits star[t] where star[t] > lp(t, blank) and the blank's value
+    otherwise; path is -2 on the frames it does (filler frames), -1 on plain blank frames.  Returns what ctc_align_long returns and
+    refuses what it refuses, and also (ValueError, on the host): a star that is not f32 or whose length is not the number of rows, NaN in
+    star, a gap whose length is not the number of labels, a gap_tail whose length is not R."""
+    return _ctc_align_long("ctc_align_long_filler", rows, lse, row_off, labels, lab_off, blank, ws, fill=(star, gap, gap_tail))

@@ -1116,6 +1116,23 @@ int asr_ctc_align_long(const void* rows, const float* lse, const int32_t* row_of
                        int32_t* path, int32_t* spans, float* tok, double* score, void* ws, size_t ws_bytes, int R, int V, int ld,
                        int dtype, int blank, void* stream);
 
+/* asr_ctc_align_long with filler frames for audio the transcript does not cover.  Additive to ABI 10.  The definition is
+ * tests/align_filler_ref.py; the kernel agrees with it bit for bit.
+ * No state is added and the topology does not change: some blank states are WIDE.  gap (sum L) uint8, indexed like labels: gap[i] != 0
+ * marks the blank state 2i in front of label i; gap_tail (R) uint8: gap_tail[r] != 0 marks the last state 2L of recording r.  star
+ * (sum T) f32, indexed like lse: the log-probability of "anything" on every frame (no NaN).  With eb = lp(t, blank), a wide blank state
+ * emits on frame t
+ *   star[t] if star[t] > eb, else eb      (strict: the blank wins ties; the chosen f32 is converted to double as every emission is)
+ * at t = 0 too, and in the L = 0 sum.  The recursion, the tie order, the choice of the end state and tok are asr_ctc_align_long's.
+ * path gains the value -2: the frame sits in a wide blank state and star[t] > eb (a filler frame); a plain blank frame stays -1.
+ * With every flag 0, or with star = -inf everywhere, every output has asr_ctc_align_long's bits.  A wide blank stays optional and
+ * skippable, so it never makes an infeasible recording feasible.  Workspace and back-pointer coding are asr_ctc_align_long's (the filler
+ * choice is a function of the frame and the state, so nothing more is stored per frame). */
+int asr_ctc_align_long_filler(const void* rows, const float* lse, const float* star, const int32_t* row_off, const int32_t* labels,
+                              const int32_t* lab_off, const uint8_t* gap, const uint8_t* gap_tail, int32_t* path, int32_t* spans,
+                              float* tok, double* score, void* ws, size_t ws_bytes, int R, int V, int ld, int dtype, int blank,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
