@@ -29,6 +29,7 @@ REVERB_FFT_N, REVERB_FFT_MAX_TAPS = 4096, 65536      # ASR_REVERB_FFT_*: transfo
 NOISE_MIX_TILE = 4096      # ASR_NOISE_MIX_TILE: samples per workgroup and energy partial of asr_noise_mix_fwd
 VAD_CTX_MAX = 1024     # ASR_VAD_CTX_MAX: the largest frames_context asr_vad_decide takes
 ALIGN_LONG_MAX_LABELS = 8192      # ASR_ALIGN_LONG_MAX_LABELS: labels per recording of asr_ctc_align_long
+SPECAUG_MAX_RANGES = 8     # ASR_SPECAUG_MAX_RANGES: ranges of one kind in a row of asr_*_norm_specaug_lfr_fwd
 STREAM_OPEN = 0x3fffffff      # ASR_STREAM_OPEN: "length not known yet" in the streaming front end's parameter arrays
 
 P, I, F, Z, U = c_void_p, c_int, c_float, c_size_t, c_uint32
@@ -173,6 +174,8 @@ SIGNATURES = {
     "asr_noise_mix_fwd": (I, [P, P, P, P, P, P, P, P, Z, I, I, I, P]),
     "asr_cmvn_accumulate": (I, [P, P, P, I, I, I, P]),
     "asr_global_norm_augment_lfr_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "asr_utt_norm_specaug_lfr_fwd": (I, [P, P, P, I, I, I, I, P, P, I, I, I, I, I, I, I, P]),
+    "asr_global_norm_specaug_lfr_fwd": (I, [P, P, P, I, I, I, I, P, P, P, P, I, I, I, I, I, I, I, P]),
     "asr_stream_append": (I, [P, P, P, I, I, I, I, I, P]),
     "asr_stream_logmel": (I, [P, P, P, P, P, I, I, I, I, I, P]),
     "asr_stream_norm_lfr": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),

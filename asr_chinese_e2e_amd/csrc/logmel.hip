@@ -329,6 +329,153 @@ __global__ __launch_bounds__(1024) void global_norm_lfr_kernel(const float* __re
     if (tid == 0 && blockIdx.x == 0) out_len[b] = Tl;
 }
 
+// ---- SpecAugment policies: several masks with zero fill, linear time warp, substitution (the definition: tests/specaug_ref.py) -----
+// An utterance's row is [wc, ww | (t0, t1) x n_t | (f0, f1) x n_f | (s, e, p) x n_s], resolved on the host (data_handler/specaug.py).
+// Zero is the mean under both normalisations, so nothing is reduced: the two kernels below are their siblings with another store loop.
+constexpr int SPEC_MAX = ASR_SPECAUG_MAX_RANGES, SPEC_ROW = 2 + 7 * SPEC_MAX;
+
+// The row of one utterance of T frames and F bins, clamped, into LDS: thread 0 takes the warp, the next n_t + n_f + n_s threads one range
+// each.  After it every range lies in [0, T] (or [0, F]), p <= s, and wc = ww = 0 unless 0 < wc < T and 0 < ww < T - whatever the row held.
+__device__ __forceinline__ void specaug_load_row(int* row, const int32_t* __restrict__ in, int n_t, int n_f, int n_s, int T, int F) {
+    const int k = threadIdx.x;
+    if (k == 0) {
+        const int wc = in[0], ww = in[1];
+        const bool on = wc > 0 && wc < T && ww > 0 && ww < T;
+        row[0] = on ? wc : 0;
+        row[1] = on ? ww : 0;
+    } else if (k <= n_t + n_f) {
+        const int at = 2 * k, lim = k <= n_t ? T : F;
+        const int lo = min(max(in[at], 0), lim);
+        row[at] = lo;
+        row[at + 1] = min(max(in[at + 1], lo), lim);
+    } else if (k <= n_t + n_f + n_s) {
+        const int at = 2 + 2 * (n_t + n_f) + 3 * (k - 1 - n_t - n_f);
+        const int s = min(max(in[at], 0), T);
+        row[at] = s;
+        row[at + 1] = min(max(in[at + 1], s), T);
+        row[at + 2] = min(max(in[at + 2], 0), s);
+    }
+    __syncthreads();
+}
+
+// Output cell (frame t, bin f) of an utterance of T frames, pulled through substitution source, masks and warp.  val_t = the normalised
+// x[t][f] (what the sibling kernel stores), norm(u) = the normalised x[u][f] for any 0 <= u < T.  The row is wave-uniform LDS, so every
+// range test is a broadcast read.  Frame indices: u = t - p lies in [0, t] as p <= s <= t; with the warp on, o < n_out gives
+// num < 2 n_out n_in, so i0 <= n_in - 1 and base + i1 <= T - 1 - no index is formed from anything but the clamped row.
+template <typename Norm>
+__device__ __forceinline__ float specaug_pull(const int* row, int n_t, int n_f, int n_s, int t, int f, int T, float val_t, Norm norm) {
+    const int* tm = row + 2;
+    const int* fm = tm + 2 * n_t;
+    const int* sb = fm + 2 * n_f;
+    int u = t;
+    for (int i = 0; i < n_s; ++i)                       // the last substitution that covers t wins; it reads augmented frames, never chains
+        if (t >= sb[3 * i] && t < sb[3 * i + 1]) u = t - sb[3 * i + 2];
+    bool masked = false;
+    for (int i = 0; i < n_t; ++i) masked |= u >= tm[2 * i] && u < tm[2 * i + 1];
+    for (int i = 0; i < n_f; ++i) masked |= f >= fm[2 * i] && f < fm[2 * i + 1];
+    if (masked) return 0.f;
+    const int wc = row[0], ww = row[1];
+    if (ww == 0) return u == t ? val_t : norm(u);
+    // linear warp: output frames [0, ww) resample input frames [0, wc), output frames [ww, T) input frames [wc, T), sample centres aligned
+    const bool left = u < ww;
+    const int o = left ? u : u - ww, n_out = left ? ww : T - ww, base = left ? 0 : wc, n_in = left ? wc : T - wc;
+    const long long num = max((2ll * o + 1) * n_in - n_out, 0ll);
+    const unsigned den = 2u * (unsigned)n_out;
+    unsigned q, rem;
+    if ((num >> 32) == 0) {                             // every utterance of fewer than 32768 frames: one 32-bit division
+        q = (unsigned)num / den;
+        rem = (unsigned)num - q * den;
+    } else {
+        q = (unsigned)((unsigned long long)num / den);
+        rem = (unsigned)((unsigned long long)num - (unsigned long long)q * den);
+    }
+    const int i0 = min((int)q, n_in - 1), i1 = min(i0 + 1, n_in - 1);
+    const float v0 = norm(base + i0), v1 = norm(base + i1);
+    {
+        // One division, subtraction, multiplication and addition, each rounded on its own.  The operators are written out under the pragma
+        // because that is what keeps them apart: the build contracts a * b + c into an fma wherever both operations allow it, and the
+        // header's __fmul_rn / __fadd_rn are plain inline operators that allow it (they came out as one v_fmac_f32 here).  There is no
+        // fast-math, so nothing is reassociated, and the division is the correctly rounded one.
+        #pragma clang fp contract(off)
+        const float w = (float)rem / (float)den;
+        const float d = v1 - v0;
+        const float wd = w * d;
+        return v0 + wd;
+    }
+}
+
+// utt_norm_lfr_kernel with the policies' store loop: the same two statistics passes over the un-augmented frames.
+template <typename T>
+__global__ __launch_bounds__(1024) void utt_norm_specaug_lfr_kernel(const float* __restrict__ feat, const int32_t* __restrict__ wav_len,
+                                                                    const int32_t* __restrict__ ranges, int ld, int n_t, int n_f, int n_s, T* __restrict__ out,
+                                                                    int32_t* __restrict__ out_len, int Tmax, int n_mels, int m, int n, int Tlfr_max) {
+    __shared__ float red[16];
+    __shared__ int row[SPEC_ROW];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int len = wav_len[b];
+    const int Tb = len > 0 ? min(1 + len / HOP, Tmax) : 0;
+    const int Tl = min((Tb + n - 1) / n, Tlfr_max);
+    const float* f = feat + (size_t)b * Tmax * n_mels;
+    const int cnt = Tb * n_mels;
+    float s = 0.f;
+    for (int i = tid; i < cnt; i += 1024) s += f[i];
+    const float mean = cnt > 0 ? block_sum(s, red) / (float)cnt : 0.f;
+    float q = 0.f;
+    for (int i = tid; i < cnt; i += 1024) { const float d = f[i] - mean; q += d * d; }
+    const float var = cnt > 1 ? block_sum(q, red) / (float)(cnt - 1) : 1.f;  // unbiased (torch .std())
+    const float rstd = rsqrtf(var);
+    specaug_load_row(row, ranges + (size_t)b * ld, n_t, n_f, n_s, Tb, n_mels);
+    const int W = m * n_mels;
+    T* o = out + (size_t)b * Tlfr_max * W;
+    const int total = Tlfr_max * W;
+    for (int i = tid; i < total; i += 1024) {
+        const int r = i / W, c = i - r * W;
+        float val = 0.f;
+        if (r < Tl) {
+            const int j = c / n_mels, mm = c - j * n_mels;
+            const int src = min(r * n + j, Tb - 1);   // tail frames repeat the last input frame
+            val = (f[(size_t)src * n_mels + mm] - mean) * rstd;
+            val = specaug_pull(row, n_t, n_f, n_s, src, mm, Tb, val, [=](int u) { return (f[(size_t)u * n_mels + mm] - mean) * rstd; });
+        }
+        o[i] = from_f32<T>(val);
+    }
+    if (tid == 0) out_len[b] = Tl;
+}
+
+// global_norm_lfr_kernel's tiled no-mask path with the policies' store loop; every workgroup of an utterance loads its row.
+template <typename T>
+__global__ __launch_bounds__(1024) void global_norm_specaug_lfr_kernel(const float* __restrict__ feat, const int32_t* __restrict__ wav_len,
+                                                                       const int32_t* __restrict__ ranges, int ld, int n_t, int n_f, int n_s,
+                                                                       const float* __restrict__ mean, const float* __restrict__ istd, T* __restrict__ out,
+                                                                       int32_t* __restrict__ out_len, int Tmax, int n_mels, int m, int n, int Tlfr_max) {
+    __shared__ int row[SPEC_ROW];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int len = wav_len[b];
+    const int Tb = len > 0 ? min(1 + len / HOP, Tmax) : 0;
+    const int Tl = min((Tb + n - 1) / n, Tlfr_max);
+    const float* f = feat + (size_t)b * Tmax * n_mels;
+    specaug_load_row(row, ranges + (size_t)b * ld, n_t, n_f, n_s, Tb, n_mels);
+    const int W = m * n_mels;
+    T* o = out + (size_t)b * Tlfr_max * W;
+    const int total = Tlfr_max * W;
+    const auto frame_at = [=](int t) { return f + (size_t)t * n_mels; };
+    for (int i = blockIdx.x * 1024 + tid; i < total; i += gridDim.x * 1024) {
+        const int r = i / W, c = i - r * W;
+        float val = 0.f;
+        if (r < Tl) {
+            int src, mm;
+            val = cmvn_lfr_elem(frame_at, r, c, n_mels, n, Tb, mean, istd, &src, &mm);
+            // frame u, bin mm through the same function: stacking factor 1, row u, column mm
+            val = specaug_pull(row, n_t, n_f, n_s, src, mm, Tb, val, [=](int u) {
+                int s2, m2;
+                return cmvn_lfr_elem(frame_at, u, mm, n_mels, 1, Tb, mean, istd, &s2, &m2);
+            });
+        }
+        o[i] = from_f32<T>(val);
+    }
+    if (tid == 0 && blockIdx.x == 0) out_len[b] = Tl;
+}
+
 // Streaming: LFR rows [r_begin, r_begin + n_rows) of each utterance out of its frame ring into one encoder chunk (B, C, m n_mels),
 // rows past n_rows zero.  par[b] = {r_begin, n_rows, Tb}: Tb = the utterance's frame count once it is closed, ASR_STREAM_OPEN before.
 template <typename T>
@@ -413,6 +560,52 @@ extern "C" int asr_global_norm_augment_lfr_fwd(const float* feat, const int32_t*
     else if (dtype == ASR_BF16) global_norm_lfr_kernel<bf16_t><<<grid, 1024, 0, st>>>(feat, wav_len, masks, mean, istd, (bf16_t*)out, out_len, Tmax, n_mels, m, n, Tlfr_max);
     else ASR_FAIL(ASR_EDTYPE, "asr_global_norm_augment_lfr_fwd: dtype %d", dtype);
     ASR_CHECK_LAUNCH("asr_global_norm_augment_lfr_fwd");
+    return ASR_OK;
+}
+
+// ---- SpecAugment policies ---------------------------------------------------------------------------------------------------------------
+static int specaug_check(const char* name, const int32_t* ranges, int ld, int n_t, int n_f, int n_s) {
+    if (!ranges) ASR_FAIL(ASR_EINVAL, "%s: null pointer", name);
+    if (n_t < 0 || n_f < 0 || n_s < 0 || n_t > SPEC_MAX || n_f > SPEC_MAX || n_s > SPEC_MAX)
+        ASR_FAIL(ASR_EINVAL, "%s: n_t=%d n_f=%d n_s=%d (each 0 .. %d)", name, n_t, n_f, n_s, SPEC_MAX);
+    if (ld < 2 + 2 * n_t + 2 * n_f + 3 * n_s) ASR_FAIL(ASR_EINVAL, "%s: ld=%d, a row has %d words", name, ld, 2 + 2 * n_t + 2 * n_f + 3 * n_s);
+    return ASR_OK;
+}
+
+extern "C" int asr_utt_norm_specaug_lfr_fwd(const float* feat, const int32_t* wav_len, const int32_t* ranges, int ld, int n_t, int n_f, int n_s, void* out,
+                                            int32_t* out_len, int B, int Tmax, int n_mels, int m, int n, int Tlfr_max, int dtype, void* stream) {
+    if (!feat || !wav_len || !out || !out_len) ASR_FAIL(ASR_EINVAL, "asr_utt_norm_specaug_lfr_fwd: null pointer");
+    if (B <= 0 || Tmax <= 0 || n_mels <= 0 || m <= 0 || n <= 0 || Tlfr_max <= 0)
+        ASR_FAIL(ASR_EINVAL, "asr_utt_norm_specaug_lfr_fwd: bad shape B=%d Tmax=%d n_mels=%d m=%d n=%d Tlfr_max=%d", B, Tmax, n_mels, m, n, Tlfr_max);
+    if (const int rc = specaug_check("asr_utt_norm_specaug_lfr_fwd", ranges, ld, n_t, n_f, n_s)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == ASR_F32)
+        utt_norm_specaug_lfr_kernel<float><<<B, 1024, 0, st>>>(feat, wav_len, ranges, ld, n_t, n_f, n_s, (float*)out, out_len, Tmax, n_mels, m, n, Tlfr_max);
+    else if (dtype == ASR_BF16)
+        utt_norm_specaug_lfr_kernel<bf16_t><<<B, 1024, 0, st>>>(feat, wav_len, ranges, ld, n_t, n_f, n_s, (bf16_t*)out, out_len, Tmax, n_mels, m, n, Tlfr_max);
+    else ASR_FAIL(ASR_EDTYPE, "asr_utt_norm_specaug_lfr_fwd: dtype %d", dtype);
+    ASR_CHECK_LAUNCH("asr_utt_norm_specaug_lfr_fwd");
+    return ASR_OK;
+}
+
+extern "C" int asr_global_norm_specaug_lfr_fwd(const float* feat, const int32_t* wav_len, const int32_t* ranges, int ld, int n_t, int n_f, int n_s,
+                                               const float* mean, const float* istd, void* out, int32_t* out_len, int B, int Tmax, int n_mels, int m, int n,
+                                               int Tlfr_max, int dtype, void* stream) {
+    if (!feat || !wav_len || !mean || !istd || !out || !out_len) ASR_FAIL(ASR_EINVAL, "asr_global_norm_specaug_lfr_fwd: null pointer");
+    if (B <= 0 || B > 65535 || Tmax <= 0 || n_mels <= 0 || m <= 0 || n <= 0 || Tlfr_max <= 0)
+        ASR_FAIL(ASR_EINVAL, "asr_global_norm_specaug_lfr_fwd: bad shape B=%d Tmax=%d n_mels=%d m=%d n=%d Tlfr_max=%d", B, Tmax, n_mels, m, n, Tlfr_max);
+    if ((long long)Tlfr_max * m * n_mels > INT32_MAX) ASR_FAIL(ASR_EINVAL, "asr_global_norm_specaug_lfr_fwd: Tlfr_max * m * n_mels does not fit an int");
+    if (const int rc = specaug_check("asr_global_norm_specaug_lfr_fwd", ranges, ld, n_t, n_f, n_s)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid(max(1, min(ceil_div(Tlfr_max * m * n_mels, 4096), 256)), B);      // the tiling of the sibling's no-mask path: 4 elements per thread
+    if (dtype == ASR_F32)
+        global_norm_specaug_lfr_kernel<float><<<grid, 1024, 0, st>>>(feat, wav_len, ranges, ld, n_t, n_f, n_s, mean, istd, (float*)out, out_len, Tmax, n_mels, m,
+                                                                     n, Tlfr_max);
+    else if (dtype == ASR_BF16)
+        global_norm_specaug_lfr_kernel<bf16_t><<<grid, 1024, 0, st>>>(feat, wav_len, ranges, ld, n_t, n_f, n_s, mean, istd, (bf16_t*)out, out_len, Tmax, n_mels,
+                                                                      m, n, Tlfr_max);
+    else ASR_FAIL(ASR_EDTYPE, "asr_global_norm_specaug_lfr_fwd: dtype %d", dtype);
+    ASR_CHECK_LAUNCH("asr_global_norm_specaug_lfr_fwd");
     return ASR_OK;
 }
 

@@ -6,6 +6,8 @@ from .loader import BatchPlan, BucketedWaveLoader, WaveDataset, bucket_batches, 
 from . import speed
 from . import noise
 from .noise import NoiseBank, RirBank
+from . import specaug
+from .specaug import SpecAugmentPolicy
 from . import cmvn
 from .cmvn import CmvnAccumulator, load_cmvn, load_cmvn_meta, save_cmvn, save_wenet_cmvn
 from .stream_frontend import StreamingFrontEnd

@@ -28,6 +28,7 @@ from .processor import AudioParser
 from . import speed as speed_mod
 from . import noise as noise_mod
 from . import resample as resample_mod
+from . import specaug as specaug_mod
 
 
 def read_pcm(path):
@@ -205,7 +206,7 @@ class MetaLayout:
     here and nowhere else, and field() slices the numpy view of the pinned buffer and its device copy alike.  A feature that is off
     contributes no words (all off: 2 B + B lmax words, the copy the first loader made)."""
 
-    def __init__(self, B, lmax, factor=False, rate=False, aug=False):
+    def __init__(self, B, lmax, factor=False, rate=False, aug=False, spec=0):
         fields = [("n_samples", (B,)), ("tgt_len", (B,)), ("tgt", (B, lmax))]
         if factor:
             fields += [("factor", (B,))]                               # speed-factor index per utterance
@@ -213,6 +214,8 @@ class MetaLayout:
             fields += [("rate_idx", (B,)), ("win", (B, 5))]            # {in_base, n_avail, n_total, out_start, n_emit}
         if aug:
             fields += [("rir_idx", (B,)), ("noise_par", (B, 4))]       # {clip, offset, scale as float bits, 0}
+        if spec:
+            fields += [("spec", (B, int(spec)))]                       # SpecAugment policy rows, spec = the policy's width (specaug.resolve)
         self.B, self.lmax, self.at, self.size = B, lmax, {}, 0
         for name, shape in fields:
             words = B * (shape[1] if len(shape) > 1 else 1)
@@ -236,11 +239,12 @@ SpeedTables = collections.namedtuple("SpeedTables", "pq_host pq taps")
 BatchMeta = collections.namedtuple("BatchMeta", "len16 len_out smax16 smax_out any_rir any_noise")
 
 
-def pack_meta(lay, meta, sizes, tgt, fs=None, pq=None, rates=None, rate_table=None, aug=None):
+def pack_meta(lay, meta, sizes, tgt, fs=None, pq=None, rates=None, rate_table=None, aug=None, *, spec=None):
     """The host half of a batch, no GPU: fills `meta` (numpy int32, lay.size words) field by field and decides what the batch launches.
     sizes: sample counts, tgt: label lists; fs, pq: the batch's speed-factor indices and the (p, q) list; rates, rate_table: the batch's
-    source rates and a resample.RateTable (one built with device=None does); aug: noise.draw_augment's four lists, the batch's rows.
-    Each group is read only when `lay` has its fields.  -> BatchMeta."""
+    source rates and a resample.RateTable (one built with device=None does); aug: noise.draw_augment's four lists, the batch's rows;
+    spec: the batch's SpecAugment policy rows (B, width), or a function that makes them from the batch's final lengths (len_out, which are
+    decided here).  Each group is read only when `lay` has its fields.  -> BatchMeta."""
     assert meta.shape == (lay.size,) and meta.dtype == np.int32 and len(sizes) == len(tgt) == lay.B
     lay.field(meta, "n_samples")[:] = sizes
     lay.field(meta, "tgt_len")[:] = [len(t) for t in tgt]
@@ -269,6 +273,8 @@ def pack_meta(lay, meta, sizes, tgt, fs=None, pq=None, rates=None, rate_table=No
         for r in range(lay.B):
             par[r] = (nidx[r], noff[r], noise_mod.snr_scale_bits(snr[r]), 0)
         any_rir, any_noise = any(v >= 0 for v in ridx), any(v >= 0 for v in nidx)
+    if "spec" in lay:
+        lay.field(meta, "spec")[:] = spec(len_out) if callable(spec) else spec
     return BatchMeta(len16, len_out, smax16, smax_out, any_rir, any_noise)
 
 
@@ -299,7 +305,7 @@ class BucketedWaveLoader:
 
     def __init__(self, dataset, batch_size, parser=None, augment=False, shuffle=True, drop_last=False, seed=0, bucket_size=None,
                  device="cuda", dtype=torch.bfloat16, rank=0, world=1, speed_perturb=None, noise=None, noise_prob=0.5, snr_db=(5, 20), rir=None,
-                 rir_prob=0.5, rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS, resample=False):
+                 rir_prob=0.5, rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS, resample=False, spec_augment=None):
         """rank / world: data-parallel sharding.  Every rank draws the SAME batch list (same seed), keeps only the full
         batches when world > 1 (dist.DataParallel normalises by world x local batch and every rank must take the same
         number of steps), drops the ragged tail of len(batches) % world and takes batches[rank::world].
@@ -317,12 +323,22 @@ class BucketedWaveLoader:
         resample: True = utterances at another rate than 16 kHz (dataset.rate(i); WaveDataset(resample=True)) are converted on the loader's
         stream in front of everything else - one asr_resample_fwd launch per batch, whatever rates it mixes; a batch that is all 16 kHz
         launches nothing.  Buckets, and the speed perturbation's lengths, are formed on the converted lengths; the staging slot holds
-        source samples.  False: nothing of it is called."""
+        source samples.  False: nothing of it is called.
+        spec_augment: a specaug.SpecAugmentPolicy or its string ("wenet", "espnet", "w5,t2x50,f2x10,s3x30,r200"): several time and mel masks
+        with zero fill, time warp and substitution on the normalised frames (tests/specaug_ref.py), in place of - never together with -
+        augment=True, the reference's one-mask variant.  Every epoch each utterance draws its numbers (specaug.draw: a function of seed,
+        epoch and utterance index that leaves `rng` alone); the ranges are resolved on the host from the lengths pack_meta decides and
+        travel in the one meta buffer, so nothing is read back from the device.  None / empty: nothing of it is called."""
+        self.spec = specaug_mod.as_policy(spec_augment)
+        if self.spec is not None and augment:
+            raise ValueError("spec_augment replaces the reference's SpecAugment: pass it or augment=True, not both")
         self.ds, self.batch_size, self.augment = dataset, batch_size, augment
         self.device, self.dtype = torch.device(device), dtype
         if self.device.type != "cuda":
             raise RuntimeError("the feature front end runs on the GPU only (no CPU fallback)")
         self.parser = parser or AudioParser(device=self.device)
+        if self.spec is not None:
+            self.spec.check_mels(self.parser.n_mels)
         self.stream = self._copy_stream()
         self.lengths = [dataset.num_samples(i) for i in range(len(dataset))]      # source samples: what the staging slot holds
         # per-utterance source rates (None: all 16 kHz, or resample off) and the lengths at 16 kHz the buckets are formed on
@@ -385,13 +401,15 @@ class BucketedWaveLoader:
             slots[k] = s
         return s
 
-    def _prepare(self, idx, k=0, fidx=None, aug=None):
+    def _prepare(self, idx, k=0, fidx=None, aug=None, spec=None):
         """fidx: speed-factor index per utterance of the data set (BatchPlan.next_epoch), None = no perturbation.
         aug: noise.draw_augment's four lists for the data set, None = neither noise nor reverberation.
+        spec: specaug.draw's table for the data set, None = no SpecAugment policy.
         The integers of the batch travel in one buffer whose layout is MetaLayout; pack_meta fills it and decides what is launched."""
         tgt = [self.ds.ids(i) for i in idx]
         B = len(idx)
-        lay = MetaLayout(B, max(1, max(len(t) for t in tgt)), factor=fidx is not None, rate=self.rates is not None, aug=aug is not None)
+        lay = MetaLayout(B, max(1, max(len(t) for t in tgt)), factor=fidx is not None, rate=self.rates is not None, aug=aug is not None,
+                         spec=self.spec.width if spec is not None else 0)
         into = getattr(self.ds, "wave_into", None)
         waves = None if into is not None else [self.ds.wave(i) for i in idx]
         smax = max(self.lengths[i] for i in idx) if waves is None else max(w.size for w in waves)
@@ -416,7 +434,8 @@ class BucketedWaveLoader:
         take = lambda per_utt: [per_utt[i] for i in idx]
         m = pack_meta(lay, slot["meta_np"][:lay.size], sizes, tgt, fs=take(fidx) if fidx is not None else None,
                       pq=self.speed.pq_host if self.speed else None, rates=take(self.rates) if self.rates is not None else None,
-                      rate_table=self.rate_table, aug=[take(a) for a in aug] if aug is not None else None)
+                      rate_table=self.rate_table, aug=[take(a) for a in aug] if aug is not None else None,
+                      spec=(lambda lens: self.parser.spec_ranges(self.spec, spec[idx], lens)) if spec is not None else None)
         from .. import kernels as K
         with torch.cuda.stream(self.stream):
             dev_wav = slot["wave"][:B * smax].view(B, smax).to(self.device, non_blocking=True)
@@ -446,7 +465,10 @@ class BucketedWaveLoader:
             if m.any_noise:      # in place
                 ws = K.noise_mix_workspace(B, wav.shape[1], self.device)
                 keep += [ws, *K.noise_mix(wav, wav_len, field("noise_par"), self.noise.noise, self.noise.noise_off, out=wav, ws=ws)]
-            feat, feat_len = self.parser.parse_batch(wav, wav_len, self.dtype, augment=self.augment, rng=self.rng)
+            if spec is not None:
+                feat, feat_len = self.parser.parse_batch(wav, wav_len, self.dtype, spec_ranges=field("spec"), spec_policy=self.spec)
+            else:
+                feat, feat_len = self.parser.parse_batch(wav, wav_len, self.dtype, augment=self.augment, rng=self.rng)
             tgt_dev = field("tgt").long()
             pack = Pack()
             pack.add(wave=feat, wave_len=feat_len.long(), tgt_for_input=tgt_dev, tgt_for_metric=tgt_dev.clone(), tgt_len=field("tgt_len").long())
@@ -468,6 +490,7 @@ class BucketedWaveLoader:
         if self.noise is not None or self.rir is not None:
             aug = noise_mod.draw_augment(self.plan.seed, epoch, len(self.ds), self.noise_prob, len(self.noise) if self.noise else 0,
                                          self.noise.lens if self.noise else (), self.snr_db, self.rir_prob, len(self.rir) if self.rir else 0)
+        spec = specaug_mod.draw(self.plan.seed, epoch, len(self.ds), self.spec) if self.spec is not None else None
         q = queue.Queue(maxsize=self.PREFETCH)
         stop = threading.Event()
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()      # the consumer's device
@@ -487,7 +510,7 @@ class BucketedWaveLoader:
                 torch.cuda.set_device(dev_index)
                 for k, idx in enumerate(batches):
                     with self._gate:      # paused() (a hipGraph capture on the consumer thread) keeps this thread off the GPU runtime
-                        item = self._prepare(idx, k, fidx, aug)
+                        item = self._prepare(idx, k, fidx, aug, spec)
                     if not hand_over(item):
                         return
                 hand_over(None)
@@ -529,7 +552,7 @@ def parser_norm(cmvn):
 def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=True, sample_rate=16000, window_size=400, n_mels=40,
                      augment=False, predump=False, use_old=False, lfr_m=4, lfr_n=3, dtype=torch.bfloat16, shuffle=None, seed=0,
                      rank=0, world=1, speed_perturb=None, cmvn=None, noise=None, noise_prob=0.5, snr_db=(5, 20), rir=None, rir_prob=0.5,
-                     rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS, resample=False, frontend="reference"):
+                     rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS, resample=False, frontend="reference", spec_augment=None):
     """build_dataloader of the reference (data/data_loader/ai_shell_1.py:91-104), same arguments: reads the manifest
     `<collector_path>_<part>.json` written by the reference's collector (one JSON object {"wave": path, "tgt": text}
     per line, data_collector/ai_shell_1.py:73-79) and returns an iterable of Packs.  The reference computes features
@@ -542,8 +565,15 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
     the corpus statistics (AudioParser norm="global"); None / empty = the reference's per-utterance normalisation.
     resample: True = files (and noise / response files of a bank built here) at another rate than 16 kHz are converted on the GPU
     (WaveDataset / BucketedWaveLoader / noise banks, every part); False = they raise, as before.
-    frontend: "reference" (the reference's log-mel) or "kaldi" (Kaldi fbank): AudioParser's."""
+    frontend: "reference" (the reference's log-mel) or "kaldi" (Kaldi fbank): AudioParser's.
+    spec_augment: BucketedWaveLoader's SpecAugment policy (a specaug.SpecAugmentPolicy or its string), applied to part="train" only and never
+    together with augment=True; None / empty = off."""
     import json
+    spec = specaug_mod.as_policy(spec_augment)      # a malformed string, or both augmentations, is refused before anything is built
+    if spec is not None:
+        spec.check_mels(n_mels)
+        if augment:
+            raise ValueError("spec_augment replaces the reference's SpecAugment: pass it or augment=True, not both")
     if not use_cuda:
         raise RuntimeError("the feature front end runs on the GPU only (no CPU fallback)")
     if window_size != 400:
@@ -557,6 +587,6 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
     ds = WaveDataset(items, vocab, sample_rate=sample_rate, resample=resample)
     parser = AudioParser(sample_rate=sample_rate, n_mels=n_mels, lfr_m=lfr_m, lfr_n=lfr_n, device="cuda", frontend=frontend, **parser_norm(cmvn))
     wave_aug = dict(noise=noise, noise_prob=noise_prob, snr_db=snr_db, rir=rir, rir_prob=rir_prob, rir_method=rir_method,
-                    rir_max_taps=rir_max_taps) if part == "train" else {}
+                    rir_max_taps=rir_max_taps, spec_augment=spec) if part == "train" else {}
     return BucketedWaveLoader(ds, batch_size, parser=parser, augment=augment, shuffle=(part == "train") if shuffle is None else shuffle,
                               drop_last=True, seed=seed, dtype=dtype, rank=rank, world=world, speed_perturb=speed_perturb, resample=resample, **wave_aug)

@@ -10,6 +10,7 @@ import random
 import torch
 
 from .. import kernels as K
+from . import specaug
 from .cmvn import load_cmvn_meta
 
 SR, N_FFT, HOP = 16000, 400, 160
@@ -174,15 +175,45 @@ class AudioParser:
             return K.fbank(wav, wav_len, self.window, self.melfb, Tmax, self.wav_scale, self.preemph, feat=feat)
         return K.logmel(wav, wav_len, self.window, self.melfb, Tmax, feat=feat)
 
-    def parse_batch(self, wav, wav_len, dtype=torch.float32, augment=False, rng=random):
+    def spec_ranges(self, policy, draws, lengths, S=None):
+        """The (B, policy.width) int32 row block (numpy) of a batch for parse_batch(spec_ranges=...): specaug.resolve for every utterance,
+        its frame count taken from the HOST lengths in samples by num_frames, capped at max_frames(S) as the kernels cap it (S: the width
+        of the waveform rows, the longest length when None).  draws: the batch's rows of specaug.draw's table.  Nothing touches the device."""
+        policy.check_mels(self.n_mels)
+        lengths = [int(l) for l in lengths]
+        S = max(lengths + [1]) if S is None else int(S)
+        Tmax = self.max_frames(S)
+        return specaug.resolve_batch(policy, draws, [min(self.num_frames(min(l, S)), Tmax) for l in lengths], self.n_mels)
+
+    def parse_batch(self, wav, wav_len, dtype=torch.float32, augment=False, rng=random, spec_ranges=None, spec_policy=None):
         """augment=True: SpecAugment as AudioParser.parse(path, augment=True) of the reference, masks
         drawn on the host from `rng` (the `random` module by default, as the reference), applied on the
-        device between normalisation and frame stacking."""
+        device between normalisation and frame stacking.
+        spec_ranges, spec_policy: a specaug.SpecAugmentPolicy and the batch's resolved rows (spec_ranges(); (B, >= policy.width) int32, on the
+        device or a host array that is then copied) - several masks with zero fill, time warp and substitution in place of the reference's
+        variant (tests/specaug_ref.py).  Both or neither, and never with augment=True."""
+        if (spec_ranges is None) != (spec_policy is None):
+            raise ValueError("parse_batch: spec_ranges and spec_policy come together (AudioParser.spec_ranges builds the rows)")
+        if spec_policy is not None and augment:
+            raise ValueError("parse_batch: spec_policy replaces the reference's SpecAugment - not both it and augment=True")
         B, S = wav.shape
+        if spec_policy is not None:      # refused before any launch
+            spec_policy.check_mels(self.n_mels)
+            if not torch.is_tensor(spec_ranges):
+                spec_ranges = torch.from_numpy(np.ascontiguousarray(spec_ranges, dtype=np.int32))
+            if spec_ranges.dim() != 2 or spec_ranges.shape[0] != B or spec_ranges.shape[1] < spec_policy.width or spec_ranges.dtype != torch.int32:
+                raise ValueError(f"parse_batch: spec_ranges must be (B = {B}, >= {spec_policy.width}) int32, got {tuple(spec_ranges.shape)} {spec_ranges.dtype}")
+            spec_ranges = spec_ranges.to(wav.device)
         Tmax = self.max_frames(S)
         wl = wav_len.to(torch.int32)
         feat = self.features(wav.contiguous(), wl, Tmax)
         Tl = (Tmax + self.lfr_n - 1) // self.lfr_n
+        if spec_policy is not None:
+            counts = (spec_policy.n_t, spec_policy.n_f, spec_policy.n_s)
+            wl = self.norm_lengths(wl, S, Tmax)
+            if self.norm == "global":
+                return K.global_norm_specaug_lfr(feat, wl, spec_ranges, counts, self.mean, self.istd, self.lfr_m, self.lfr_n, Tl, dtype)
+            return K.utt_norm_specaug_lfr(feat, wl, spec_ranges, counts, self.lfr_m, self.lfr_n, Tl, dtype)
         masks = None
         if augment:
             frames = self.frame_counts(wav_len, S, Tmax)

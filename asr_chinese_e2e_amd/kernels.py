@@ -1361,6 +1361,46 @@ def global_norm_lfr(feat, wav_len, mean, istd, m, n, Tlfr_max, dtype=torch.float
     return out, out_len
 
 
+def _specaug_ranges(ranges, B, counts):
+    """(ranges, ld, n_t, n_f, n_s) of a specaug launch: ranges (B, >= width) int32 whose rows may lie ld >= width words apart."""
+    n_t, n_f, n_s = (int(v) for v in counts)
+    width = 2 + 2 * n_t + 2 * n_f + 3 * n_s
+    if ranges.dtype != torch.int32 or ranges.dim() != 2 or ranges.shape[0] != B or ranges.shape[1] < width or (ranges.shape[1] > 1 and ranges.stride(1) != 1):
+        raise ValueError(f"ranges must be (B = {B}, >= {width}) int32 with unit column stride, got {tuple(ranges.shape)} {ranges.dtype}")
+    if min(n_t, n_f, n_s) < 0 or max(n_t, n_f, n_s) > _lib.SPECAUG_MAX_RANGES:
+        raise ValueError(f"n_t, n_f, n_s = {n_t}, {n_f}, {n_s}: each 0 .. {_lib.SPECAUG_MAX_RANGES}")
+    return ranges, (ranges.stride(0) if B > 1 else ranges.shape[1]), n_t, n_f, n_s
+
+
+def utt_norm_specaug_lfr(feat, wav_len, ranges, counts, m, n, Tlfr_max, dtype=torch.float32):
+    """utt_norm_lfr with a SpecAugment policy (include/asr_hip.h; tests/specaug_ref.py): ranges (B, width) int32 rows
+    [wc, ww | (t0, t1) x n_t | (f0, f1) x n_f | (s, e, p) x n_s], counts = (n_t, n_f, n_s)."""
+    _chk_f32(feat)
+    _chk_i32(wav_len)
+    B, Tmax, n_mels = feat.shape
+    assert wav_len.numel() == B
+    ranges, ld, n_t, n_f, n_s = _specaug_ranges(ranges, B, counts)
+    out = torch.empty(B, Tlfr_max, m * n_mels, dtype=dtype, device=feat.device)
+    out_len = torch.empty(B, dtype=torch.int32, device=feat.device)
+    check(lib.asr_utt_norm_specaug_lfr_fwd(_p(feat), _p(wav_len), _p(ranges), ld, n_t, n_f, n_s, _p(out), _p(out_len), B, Tmax, n_mels, m, n, Tlfr_max,
+                                           _dt(out), _stream()), "asr_utt_norm_specaug_lfr_fwd")
+    return out, out_len
+
+
+def global_norm_specaug_lfr(feat, wav_len, ranges, counts, mean, istd, m, n, Tlfr_max, dtype=torch.float32):
+    """global_norm_lfr with a SpecAugment policy: utt_norm_specaug_lfr under global CMVN, on the tiled grid of the no-mask call."""
+    _chk_f32(feat, mean, istd)
+    _chk_i32(wav_len)
+    B, Tmax, n_mels = feat.shape
+    assert mean.numel() == n_mels and istd.numel() == n_mels and wav_len.numel() == B
+    ranges, ld, n_t, n_f, n_s = _specaug_ranges(ranges, B, counts)
+    out = torch.empty(B, Tlfr_max, m * n_mels, dtype=dtype, device=feat.device)
+    out_len = torch.empty(B, dtype=torch.int32, device=feat.device)
+    check(lib.asr_global_norm_specaug_lfr_fwd(_p(feat), _p(wav_len), _p(ranges), ld, n_t, n_f, n_s, _p(mean), _p(istd), _p(out), _p(out_len), B, Tmax,
+                                              n_mels, m, n, Tlfr_max, _dt(out), _stream()), "asr_global_norm_specaug_lfr_fwd")
+    return out, out_len
+
+
 def _pow2(v):
     return v > 0 and v & (v - 1) == 0
 

@@ -933,6 +933,42 @@ int asr_global_norm_augment_lfr_fwd(const float* feat, const int32_t* wav_len, c
                                     int Tmax, int n_mels, int m, int n, int Tlfr_max, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * SpecAugment policies: several time and mel masks with zero fill, a linear time warp and spectral substitution, between
+ * normalisation and frame stacking.  Additive to ABI 10; the augment entry points above are untouched.
+ * Stands in for:  the masking of the WeNet / ESPnet AISHELL recipes (spec_aug, spec_sub, time_warp).  The reference has one
+ *                 mask per axis with mean fill (the augment entry points): parity unpinned by the reference; the definition,
+ *                 in Python integers and numpy float32, is tests/specaug_ref.py, and the outputs equal it bit for bit.
+ *
+ * asr_utt_norm_specaug_lfr_fwd / asr_global_norm_specaug_lfr_fwd: the arguments of asr_utt_norm_augment_lfr_fwd /
+ * asr_global_norm_augment_lfr_fwd with `masks` replaced by
+ *   ranges: (B, ld) int32, rows ld >= 2 + 2 n_t + 2 n_f + 3 n_s words apart; never NULL.  Row b, for the T_b frames and
+ *           n_mels bins of utterance b (un-stacked frames, resolved on the host: data_handler/specaug.py):
+ *             [wc, ww | (t0, t1) x n_t | (f0, f1) x n_f | (s, e, p) x n_s]
+ *   n_t, n_f, n_s: 0 .. ASR_SPECAUG_MAX_RANGES each.
+ * The kernels clamp a row before use - t0 into [0, T_b], t1 into [t0, T_b]; f likewise against n_mels; s into [0, T_b], e into
+ * [s, T_b], p into [0, s]; the warp is on iff 0 < wc < T_b and 0 < ww < T_b - so no row reaches outside its utterance.
+ * With x the normalised frames (for the utterance normalisation: the statistics of the un-augmented frames), output frame t,
+ * bin f is
+ *   1. u = t - p_i for the last i with s_i <= t < e_i, else u = t           (substitution: reads augmented frames, never chains)
+ *   2. +0.0f if u lies in a [t0, t1) or f in a [f0, f1)                     (zero is the mean under both normalisations)
+ *   3. x[u][f] without a warp; with it, output frames [0, ww) resample input frames [0, wc) and [ww, T_b) resample [wc, T_b):
+ *      (o, n_out, base, n_in) = (u, ww, 0, wc) or (u - ww, T_b - ww, wc, T_b - wc); in 64-bit integers num =
+ *      max((2 o + 1) n_in - n_out, 0), den = 2 n_out, i0 = num / den, i1 = min(i0 + 1, n_in - 1), w = f32(num % den) / f32(den),
+ *      value = v0 + w * (v1 - v0) with v = x[base + i][f]: one fp32 division, subtraction, multiplication and addition, each
+ *      rounded on its own (never contracted).
+ * Frame stacking, out and out_len as the siblings; an all-zero row gives the bits of the siblings without masks.  No
+ * reduction runs for the augmentation: the global variant keeps the tiled grid of its sibling's no-mask path.
+ * ASR_EINVAL before any launch: a null pointer, n_* outside 0 .. 8, ld too small, the shape checks of the siblings.
+ */
+#define ASR_SPECAUG_MAX_RANGES 8
+int asr_utt_norm_specaug_lfr_fwd(const float* feat, const int32_t* wav_len, const int32_t* ranges, int ld, int n_t, int n_f,
+                                 int n_s, void* out, int32_t* out_len, int B, int Tmax, int n_mels, int m, int n,
+                                 int Tlfr_max, int dtype, void* stream);
+int asr_global_norm_specaug_lfr_fwd(const float* feat, const int32_t* wav_len, const int32_t* ranges, int ld, int n_t, int n_f,
+                                    int n_s, const float* mean, const float* istd, void* out, int32_t* out_len, int B,
+                                    int Tmax, int n_mels, int m, int n, int Tlfr_max, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Streaming front end: samples in, encoder chunks out, with the state on the device and the counters on the host.
  * Each utterance owns a ring of its most recent samples, wav_ring (B, scap) f32 with sample s at [b][s & (scap - 1)],
  * and a ring of its most recent log-mel frames, feat_ring (B, fcap, n_mels) f32 with frame t at [b][t & (fcap - 1)];

@@ -14,7 +14,10 @@ device-to-device copy of its bytes and the strided conv1d polyphase form in torc
 off and on) and from a 48 kHz one, alternated, and the host time of StreamResampler.push for one 480 ms block.
 python tools/loader_bench.py --fbank [--out=profiles/fbank_bench.json]: asr_fbank_fwd (Kaldi fbank) beside asr_logmel_fwd on the same batch of
 B = 32 x 5 s at 80 bins, a device-to-device copy of the same bytes, and a torch stand-in (unfold, the frame arithmetic, torch.fft.rfft,
-matmul, log); then push_audio of one 480 ms block with each front end (tools/stream_frontend_bench.py)."""
+matmul, log); then push_audio of one 480 ms block with each front end (tools/stream_frontend_bench.py).
+python tools/loader_bench.py --spec_augment [--out=profiles/spec_augment_bench.json]: per normalisation the no-mask call, the reference-mask call
+and asr_*_norm_specaug_lfr_fwd under `wenet`, `espnet` and `w5,t2x50,f2x10,s3x30` (B = 32 x 5 s, 80 bins, LFR 4/3, bf16), the host time of
+_prepare with augment=True and with spec_augment, and the waveform-fed joint step off, with augment=True and with `wenet`, alternated."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -28,7 +31,8 @@ NOISE_REVERB = any(a == "--noise_reverb" for a in sys.argv[1:])
 REVERB_FFT = any(a == "--reverb_fft" for a in sys.argv[1:])
 RESAMPLE = any(a == "--resample" for a in sys.argv[1:])
 FBANK = any(a == "--fbank" for a in sys.argv[1:])
-JOINT = SPEED is not None or NOISE_REVERB or REVERB_FFT or RESAMPLE or FBANK or (len(sys.argv) > 1 and sys.argv[1] == "joint")
+SPEC_AUGMENT = any(a == "--spec_augment" for a in sys.argv[1:])
+JOINT = SPEED is not None or NOISE_REVERB or REVERB_FFT or RESAMPLE or FBANK or SPEC_AUGMENT or (len(sys.argv) > 1 and sys.argv[1] == "joint")
 B, S, NB = 32, 16000 * 5, 40
 rng = np.random.RandomState(0)
 vocab = Vocab.synthetic(4232)
@@ -476,8 +480,102 @@ def fbank_bench():
     print("wrote", out_path)
 
 
+def spec_augment_bench():
+    import json
+    from asr_chinese_e2e_amd import kernels as K
+    from asr_chinese_e2e_amd.data_handler import specaug
+    from asr_chinese_e2e_amd.data_handler.processor import sample_spec_augment
+    import random
+    out_path = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--out=")), "profiles/spec_augment_bench.json")
+    n_mels, m, n = 80, 4, 3
+    ref = AudioParser(n_mels=n_mels, lfr_m=m, lfr_n=n, device="cuda")
+    wav = torch.from_numpy((np.random.RandomState(0).randn(B, S) * 0.1).astype(np.float32)).cuda()
+    wl = torch.full((B,), S, dtype=torch.int32, device="cuda")
+    Tmax = ref.max_frames(S)
+    Tl = (Tmax + n - 1) // n
+    feat = ref.features(wav, wl, Tmax)
+    g = np.random.RandomState(1)
+    mean, istd = torch.from_numpy((g.randn(n_mels) - 9.0).astype(np.float32)).cuda(), torch.from_numpy(g.uniform(0.2, 0.5, n_mels).astype(np.float32)).cuda()
+    r = random.Random(0)
+    masks = torch.tensor([sample_spec_augment(n_mels, Tmax, r) for _ in range(B)], dtype=torch.int32).cuda()
+    policies = {"wenet": "wenet", "espnet": "espnet", "w5_t2x50_f2x10_s3x30": "w5,t2x50,f2x10,s3x30"}
+    ranges = {}
+    for name, text in policies.items():
+        pol = specaug.SpecAugmentPolicy.from_string(text)
+        ranges[name] = (torch.from_numpy(ref.spec_ranges(pol, specaug.draw(0, 0, B, pol), [S] * B, S)).cuda(), (pol.n_t, pol.n_f, pol.n_s))
+
+    def timed(fn, reps=20, warm=3):
+        for _ in range(warm): fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps): fn()
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3
+    bf = torch.bfloat16
+    contenders = {
+        "global": dict(no_mask=lambda: K.global_norm_lfr(feat, wl, mean, istd, m, n, Tl, bf),
+                       reference_mask=lambda: K.global_norm_lfr(feat, wl, mean, istd, m, n, Tl, bf, masks=masks),
+                       **{name: (lambda rg=rg, c=c: K.global_norm_specaug_lfr(feat, wl, rg, c, mean, istd, m, n, Tl, bf)) for name, (rg, c) in ranges.items()}),
+        "utterance": dict(no_mask=lambda: K.utt_norm_lfr(feat, wl, m, n, Tl, bf),
+                          reference_mask=lambda: K.utt_norm_lfr(feat, wl, m, n, Tl, bf, masks=masks),
+                          **{name: (lambda rg=rg, c=c: K.utt_norm_specaug_lfr(feat, wl, rg, c, m, n, Tl, bf)) for name, (rg, c) in ranges.items()}),
+    }
+    res = dict(device=torch.cuda.get_device_name(0), B=B, samples=S, n_mels=n_mels, lfr=[m, n], frames=Tmax, dtype="bf16", policies=policies,
+               timing="HIP events around 20 back-to-back calls (output allocation included) after 3 warm-up calls, 3 rounds alternating the contenders in one process")
+    for norm, cs in contenders.items():
+        us = {name: [] for name in cs}
+        for _ in range(3):                                                        # alternated
+            for name, fn in cs.items():
+                us[name].append(timed(fn))
+        res[norm + "_norm_us"] = us
+        res[norm + "_norm_us_median"] = {name: float(np.median(v)) for name, v in us.items()}
+        print(json.dumps({norm: res[norm + "_norm_us_median"]}), flush=True)
+    # host time of preparing a batch: the reference's SpecAugment reads wav_len back for its masks, a policy resolves its rows from host lengths
+    mk = lambda **kw: BucketedWaveLoader(ds, B, parser=parser, shuffle=True, seed=1, dtype=torch.bfloat16, **kw)
+    loaders = {"off": mk(), "augment_true": mk(augment=True), "wenet": mk(spec_augment="wenet")}
+    prep = {name: [] for name in loaders}
+    table = specaug.draw(1, 0, len(ds), loaders["wenet"].spec)
+    for _ in range(3):
+        for name, ld in loaders.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for k in range(20): ld._prepare(list(range(B)), k, spec=table if name == "wenet" else None)
+            prep[name].append((time.perf_counter() - t0) / 20 * 1e3)
+            torch.cuda.synchronize()
+    res["prepare_host_ms"] = prep
+    res["prepare_host_ms_median"] = {name: float(np.median(v)) for name, v in prep.items()}
+    print(json.dumps({"prepare_host_ms_median": res["prepare_host_ms_median"]}), flush=True)
+
+    def run(ld):
+        k = 0
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for pack in ld:
+            model.iterate(pack, optimizer=opt)
+            k += 1
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / k * 1e3
+    for ld in loaders.values(): run(ld)                                           # warm-up epoch each
+    step = {name: [] for name in loaders}
+    for _ in range(3):
+        for name, ld in loaders.items():
+            step[name].append(run(ld))
+            print(f"joint step from waveforms, {name}: {step[name][-1]:.3f} ms/step", flush=True)
+    res["joint_step_ms"] = step
+    res["joint_step_ms_median"] = {name: float(np.median(v)) for name, v in step.items()}
+    res["joint_config"] = (f"{NB} batches of {B} x 5 s per epoch in host memory, 80 bins, LFR 1/1 (the model of this tool), bf16 joint model at the default width; "
+                           "off = no SpecAugment, augment_true = the reference's, wenet = spec_augment='wenet'; prepare_host_ms = host clock around 20 _prepare "
+                           "calls; joint step = 1 warm-up epoch each, then 3 epochs each, alternating; host clock around an epoch that ends in a device synchronise")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out_path)
+
+
 if SPEED is not None:
     speed_bench()
+    sys.exit(0)
+if SPEC_AUGMENT:
+    spec_augment_bench()
     sys.exit(0)
 if RESAMPLE:
     resample_bench()

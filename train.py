@@ -27,6 +27,9 @@ Differences that come with the MI355X path:
     per utterance: the causal features a streaming model is trained on (transcribe.py --stream=1 --cmvn=...);
   * `--frontend=kaldi` computes Kaldi fbank features (the front end of the Kaldi / WeNet / ESPnet / k2 recipes) instead of the
     reference's log-mel; statistics for `--cmvn` must then come from the same front end (tools/compute_cmvn.py --frontend=kaldi);
+  * `--spec_aug=wenet` (`t2x50,f2x10`), `--spec_aug=espnet` (`w5,t2x40,f2x30`) or a policy of its own such as
+    `--spec_aug=w5,t2x50,f2x10,s3x30,r200` masks, warps and substitutes the normalised frames of the train part on the GPU
+    (data_handler/specaug.py; never dev / test, and instead of - not together with - the reference's `--augment`);
   * `--resample=1` accepts files at 8, 11.025, 12, 22.05, 24, 32, 44.1, 48, 88.2 and 96 kHz (corpus, noise clips, responses) and converts
     them to 16 kHz on the GPU (data_handler/resample.py); without it a file at another rate raises, as before;
   * `--synthetic=N` trains on N synthetic AISHELL-1-shaped utterances (no dataset ships with this repository);
@@ -84,6 +87,7 @@ class TrainConfig(DataConfigAiShell1):      # main.py:14-36
     snr_db = (5, 20)                        # --snr_db=5,20: the signal-to-noise ratio of a noisy utterance is uniform in this range (dB)
     resample = 0                            # --resample=1: files (corpus, noise, responses) at another rate than 16 kHz are converted on the GPU; 0 = they raise
     speed_perturb = ()                      # --speed_perturb=0.9,1.0,1.1: speed factors of the train part (never dev / test); empty = off
+    spec_aug = ""                           # --spec_aug=wenet|espnet|w5,t2x50,f2x10,s3x30,r200: SpecAugment policy of the train part; empty = off
 
 
 def get_model_class(model_name):            # main.py:38-41
@@ -192,7 +196,7 @@ def train(**kwargs):                        # main.py:55-98
         train_iter = build_dataloader(batch_size=config.batch_size, part="train", augment=config.augment, speed_perturb=speed_factors(config.speed_perturb),
                                       noise=path_list(config.noise_list), rir=path_list(config.rir_list), noise_prob=float(config.noise_prob),
                                       rir_prob=float(config.rir_prob), snr_db=snr_range(config.snr_db), rir_method=str(config.rir_method),
-                                      rir_max_taps=int(config.rir_max_taps), **common)
+                                      rir_max_taps=int(config.rir_max_taps), spec_augment=str(config.spec_aug or "") or None, **common)
         test_iter = build_dataloader(batch_size=config.eval_batch_size, part="test", augment=False, **common)
         dev_iter = build_dataloader(batch_size=config.eval_batch_size, part="dev", augment=False, **common)
 
