@@ -330,7 +330,7 @@ class _SpeechTransformer(BaseModel):
         return ctx()
 
     def stream(self, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None, lm=None,
-               timed=False, confidence="post_max", beam_times=False):
+               timed=False, confidence="post_max", beam_times=False, blank_skip=None):
         """A streaming encoder for `batch_size` utterances in lock-step (stream.StreamingEncoder, a view of sessions.Sessions with every
         slot opened at once): push chunks of encoder-rate features, get the greedy CTC ids each chunk adds; finish() gives transcribe()'s
         result for the same decoding chunk mask, frees nothing and may be repeated.  A model without the CTC head streams too: push
@@ -348,13 +348,16 @@ class _SpeechTransformer(BaseModel):
         (confidence.TokenLog); confidence picks the measure reported as "confidence" (confidence.MEASURES).  push returns what it returns.
         beam_times=True (search="prefix_beam" only, not with a context or an LM): the search also carries every hypothesis' best single
         alignment (asr_ctc_prefix_beam_chunk_timed); nbest() entries gain "viterbi_score" and "tokens", partial() "tokens", and tokens()
-        lists the best hypothesis' tokens with "final" flags.  confidence: post_max, post_min or post_mean."""
+        lists the best hypothesis' tokens with "final" flags.  confidence: post_max, post_min or post_mean.
+        blank_skip=p in (0, 1] (search="prefix_beam" only): blank-frame skipping in front of the streamed search, with one carried bit
+        per utterance - after every push bit for bit ctc_prefix_beam_search(blank_skip=p) on the frames so far (sessions.py)."""
         from ..stream import StreamingEncoder
         return StreamingEncoder(self, batch_size, parser=parser, source_rate=source_rate, search=search, beam_size=beam_size, frame_topk=frame_topk,
-                                context=context, context_ids=context_ids, lm=lm, timed=timed, confidence=confidence, beam_times=beam_times)
+                                context=context, context_ids=context_ids, lm=lm, timed=timed, confidence=confidence, beam_times=beam_times,
+                                blank_skip=blank_skip)
 
     def sessions(self, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None,
-                 timed=False, confidence="post_max", beam_times=False):
+                 timed=False, confidence="post_max", beam_times=False, blank_skip=None):
         """`slots` independent streaming sessions in one batch (sessions.Sessions, the owner of the streaming state and tick that
         stream() views in lock-step; needs the CTC head): each slot is opened, fed (push / push_audio), closed, finished and reopened at
         its own pace - open(b), push(feats, n_valid, final), results(b) without freeing, finish(b) - and with endpoint={...} the
@@ -364,10 +367,12 @@ class _SpeechTransformer(BaseModel):
         timed=True (search="greedy" only): tokens(b) gives slot b's characters with frames, times and confidence as the audio arrives;
         confidence picks the measure reported as "confidence".  A reopened slot starts an empty list.
         beam_times=True (search="prefix_beam" only, not with a context or an LM): as stream()'s - nbest(b) / partial(b) gain "tokens",
-        tokens(b) lists slot b's best hypothesis with "final" flags; finish, drop and reopening drop the records."""
+        tokens(b) lists slot b's best hypothesis with "final" flags; finish, drop and reopening drop the records.
+        blank_skip=p (search="prefix_beam" only): as stream()'s; a reopened slot starts with a clear carry bit, and endpointing keeps
+        counting every frame."""
         from ..sessions import Sessions
         return Sessions(self, slots, parser=parser, search=search, beam_size=beam_size, frame_topk=frame_topk, endpoint=endpoint, source_rate=source_rate,
-                        context=context, lm=lm, timed=timed, confidence=confidence, beam_times=beam_times)
+                        context=context, lm=lm, timed=timed, confidence=confidence, beam_times=beam_times, blank_skip=blank_skip)
 
     def forward(self, input):
         """transformer_official.py:68-81 (inference-style forward; no gradients).  A batch without a transcript (only wave / wave_len)
@@ -457,7 +462,7 @@ class _SpeechTransformer(BaseModel):
         return pack
 
     def beam_search(self, input, beam_size=5, nbest=1, decode_max_len=0, ctc_weight=0.0, joint="rescore", ctc_pre_beam=None, context=None,
-                    context_ids=None, lm=None):
+                    context_ids=None, lm=None, blank_skip=None):
         """Attention-decoder beam search for a batch (Decoder.recognize_beam, transformer_official.py:
         331-434, batched on the GPU with key/value caches): per utterance a list of at most `nbest`
         {'yseq': [sos, ..., eos], 'score': float}.
@@ -471,10 +476,17 @@ class _SpeechTransformer(BaseModel):
         sos / eos, and decode_max_len does not apply.
         context / context_ids: hotword biasing (ctc_prefix_beam_search) - joint="ctc_rescore" only, whose first pass it biases; the
         attention beam search and the other joint searches raise.
-        lm (an lm.NgramLM): n-gram LM shallow fusion, under the same rule - joint="ctc_rescore" only, and not together with a context."""
+        lm (an lm.NgramLM): n-gram LM shallow fusion, under the same rule - joint="ctc_rescore" only, and not together with a context.
+        blank_skip (a probability in (0, 1]): blank-frame skipping in front of the CTC prefix beam search, under the same rule."""
         from .. import decode
         if joint not in ("rescore", "one_pass", "ctc_rescore"):
             raise ValueError(f"joint must be 'rescore', 'one_pass' or 'ctc_rescore' (got {joint!r})")
+        if blank_skip is not None:
+            K.blank_skip_threshold(blank_skip)
+            if joint != "ctc_rescore":
+                what = "the attention beam search" if joint == "rescore" and not ctc_weight > 0.0 else f"joint={joint!r}"
+                raise ValueError(f"blank_skip is not supported by {what}: it drops frames in front of the CTC prefix beam search - "
+                                 "ctc_prefix_beam_search, beam_search(joint='ctc_rescore'), stream / sessions with search='prefix_beam'")
         if lm is not None and joint != "ctc_rescore":
             what = "the attention beam search" if joint == "rescore" and not ctc_weight > 0.0 else f"joint={joint!r}"
             raise ValueError(f"an n-gram LM (lm=...) is not supported by {what}: it is fused into the CTC prefix beam search - "
@@ -488,7 +500,8 @@ class _SpeechTransformer(BaseModel):
         if joint == "ctc_rescore":
             if ctc_pre_beam is not None:
                 raise ValueError("ctc_pre_beam applies to joint='one_pass' only")
-            return decode.ctc_rescore_search(self, input, beam_size, nbest, ctc_weight, context=context, context_ids=context_ids, lm=lm)
+            return decode.ctc_rescore_search(self, input, beam_size, nbest, ctc_weight, context=context, context_ids=context_ids, lm=lm,
+                                             blank_skip=blank_skip)
         if ctc_pre_beam is not None:
             raise ValueError("ctc_pre_beam applies to joint='one_pass' only")
         if ctc_weight > 0.0:
@@ -496,16 +509,17 @@ class _SpeechTransformer(BaseModel):
         return decode.beam_search(self, input, beam_size, nbest, decode_max_len)
 
     def ctc_prefix_beam_search(self, input, beam_size=5, nbest=1, frame_topk=10, on_device=None, context=None, context_ids=None, lm=None,
-                               beam_times=False, confidence="post_max"):
+                               beam_times=False, confidence="post_max", blank_skip=None):
         """CTC prefix beam search over the CTC head (decode.ctc_prefix_beam_search): per utterance at most `nbest`
         {'yseq': [ids], 'score': log p(yseq | x)}.  on_device: None = the device kernel when beam * (frame_topk + 1) <= 64.
         context / context_ids: hotword biasing; entries are then {'yseq', 'score', 'ctc_score', 'bias'} (decode.ctc_prefix_beam_search).
         lm: n-gram LM shallow fusion (lm.NgramLM); entries are then {'yseq', 'score', 'ctc_score', 'lm_score'}.
         beam_times=True (the device search, not with a context or an LM): entries gain 'viterbi_score' and 'tokens' - per token its frames and
-        times in the hypothesis' best single alignment, the measures post_max / post_min / post_mean over them and 'confidence' (the one picked)."""
+        times in the hypothesis' best single alignment, the measures post_max / post_min / post_mean over them and 'confidence' (the one picked).
+        blank_skip=p in (0, 1]: frames whose blank posterior and whose predecessor's are above p are dropped in front of the search."""
         from .. import decode
         return decode.ctc_prefix_beam_search(self, input, beam_size, nbest, frame_topk, on_device, context=context, context_ids=context_ids, lm=lm,
-                                             beam_times=beam_times, confidence=confidence)
+                                             beam_times=beam_times, confidence=confidence, blank_skip=blank_skip)
 
     def ctc_greedy_search(self, input):
         """Best-path CTC hypotheses of a batch: list of id lists (repeats merged, blanks removed)."""
@@ -600,7 +614,8 @@ class _SpeechTransformer(BaseModel):
                 out[-1]["confidence"] = utterance(t["confidence"] for t in toks)
         return out
 
-    def transcribe(self, input, beam_size=5, ctc_weight=None, timestamps=True, joint="rescore", context=None, context_ids=None, lm=None, confidence=None):
+    def transcribe(self, input, beam_size=5, ctc_weight=None, timestamps=True, joint="rescore", context=None, context_ids=None, lm=None, confidence=None,
+                   blank_skip=None):
         """Audio in, text out, for a batch that needs only wave / wave_len.  The search follows the model's heads: joint model =
         beam_search(ctc_weight = config.ctc_weight unless given), CTC-only model = ctc_prefix_beam_search, attention-only model =
         beam_search (no timestamps: they come from the CTC head).  Returns per utterance {"text", "ids", "score", "tokens"}: ids of
@@ -612,6 +627,8 @@ class _SpeechTransformer(BaseModel):
         context / context_ids: hotword biasing of the CTC prefix beam search (a CTC-only model, or joint="ctc_rescore"; any other
         search raises ValueError); the result dicts gain "bias".
         lm: n-gram LM shallow fusion in the CTC prefix beam search, under the same rule; the result dicts gain "lm_score".
+        blank_skip (a probability in (0, 1]): blank-frame skipping in front of the CTC prefix beam search, under the same rule; "score"
+        then sums over the kept frames, and the token times still come from ctc_align over all frames.
         confidence (None, True = "post_max", or one of confidence.MEASURES; needs timestamps and the CTC head, ValueError otherwise):
         every token gains "confidence" and "measures", the result "confidence" (ctc_align's); tokens without times carry None."""
         from ..confidence import measure
@@ -628,9 +645,10 @@ class _SpeechTransformer(BaseModel):
             raise ValueError("timestamps come from the CTC head, and this model has none (config.ctc_weight = 0)")
         if self.use_decoder:
             w = float(getattr(self.config, "ctc_weight", 0.0)) if ctc_weight is None else float(ctc_weight)
-            hyps = self.beam_search(input, beam_size, 1, ctc_weight=w if self.use_ctc else 0.0, joint=joint, context=context, context_ids=context_ids, lm=lm)
+            hyps = self.beam_search(input, beam_size, 1, ctc_weight=w if self.use_ctc else 0.0, joint=joint, context=context, context_ids=context_ids, lm=lm,
+                                    blank_skip=blank_skip)
         else:
-            hyps = self.ctc_prefix_beam_search(input, beam_size, 1, context=context, context_ids=context_ids, lm=lm)
+            hyps = self.ctc_prefix_beam_search(input, beam_size, 1, context=context, context_ids=context_ids, lm=lm, blank_skip=blank_skip)
         ids, scores, biases = [], [], []
         bias_key = "lm_score" if lm is not None else "bias"
         for h in hyps:

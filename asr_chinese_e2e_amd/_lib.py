@@ -195,6 +195,8 @@ SIGNATURES = {
     "asr_ctc_align_long_workspace_bytes": (Z, [I, I, I]),
     "asr_ctc_align_long": (I, [P] * 10 + [Z, I, I, I, I, I, P]),
     "asr_ctc_align_long_filler": (I, [P] * 13 + [Z, I, I, I, I, I, P]),
+    "asr_ctc_blank_skip_compact": (I, [P, P, P, P, F, P, P, P, P, P, P, P, I, I, I, I, P]),
+    "asr_frame_index_remap": (I, [P, P, P, I, I, I, P]),
 }
 
 

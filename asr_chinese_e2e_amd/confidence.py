@@ -46,15 +46,19 @@ def beam_times_check(search, use_ctc, context, lm, confidence):
     return which
 
 
-def beam_tokens(ids, start, end, mx, mn, sm, which, id2tok, frame_seconds, n_final=None):
+def beam_tokens(ids, start, end, mx, mn, sm, which, id2tok, frame_seconds, n_final=None, real=None):
     """The tokens of one prefix beam hypothesis from its records (asr_ctc_prefix_beam_timed: per token the first and last frame of its run
     in the hypothesis' best single alignment, the largest, smallest and summed log-posterior over the run): {"id", "token", "start_frame",
     "end_frame", "start_s", "end_s", "measures", "confidence"} as TokenLog's, the three measures of BEAM_MEASURES.  n_final (streams): the
-    first n_final entries get "final": True, the others False.  A hypothesis longer than its record row keeps the tokens that have one."""
+    first n_final entries get "final": True, the others False.  A hypothesis longer than its record row keeps the tokens that have one.
+    real (a search behind blank-frame skipping): (start, end) in real frames (asr_frame_index_remap) - they are what is reported, while the
+    mean stays over the rows the search saw, whose count start / end give."""
     out, d = [], float(frame_seconds)
     for i in range(min(len(ids), len(start))):
         x, st, en = int(ids[i]), int(start[i]), int(end[i])
         m = {"post_max": math.exp(float(mx[i])), "post_min": math.exp(float(mn[i])), "post_mean": math.exp(float(sm[i]) / (en - st + 1))}
+        if real is not None:
+            st, en = int(real[0][i]), int(real[1][i])
         t = {"id": x, "token": id2tok[x] if 0 <= x < len(id2tok) else None, "start_frame": st, "end_frame": en, "start_s": st * d,
              "end_s": (en + 1) * d, "measures": m, "confidence": m[which]}
         if n_final is not None:

@@ -217,8 +217,20 @@ def _check_context(model, context):
     context.check_vocab(model.V)
 
 
+def blank_skip_kept(blank_lp, n, thr):
+    """The frames t < n that blank_skip keeps, in order (the definition: tests/blank_skip_ref.py): frame t is high iff blank_lp[t] > thr
+    (both float32 values; a NaN is not high) and dropped iff it and frame t - 1 are high."""
+    kept, prev = [], False
+    for t in range(n):
+        high = blank_lp[t] > thr
+        if not (high and prev):
+            kept.append(t)
+        prev = high
+    return kept
+
+
 def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on_device=None, context=None, context_ids=None, lm=None, beam_times=False,
-                           confidence="post_max"):
+                           confidence="post_max", blank_skip=None):
     """CTC prefix beam search (Hannun et al. 2014, algorithm 1 without a language model) over the CTC head's posteriors:
     per utterance a list of at most `nbest` dicts {'yseq': [ids], 'score': log p(yseq | x)}, best first.
     Everything runs on the GPU: encoder, CTC projection, per frame the `frame_topk` best classes with their log-softmax values
@@ -237,9 +249,15 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
     beam_times=True (the device search only, not with a context or an LM): the search carries the best single alignment of every prefix
     (asr_ctc_prefix_beam_timed); entries gain 'viterbi_score' (its log-probability) and 'tokens' = per token {"id", "token", "start_frame",
     "end_frame", "start_s", "end_s", "measures": {post_max, post_min, post_mean}, "confidence"}, times as tokens() of the greedy streams;
-    confidence picks the measure reported as "confidence"."""
+    confidence picks the measure reported as "confidence".
+    blank_skip=p in (0, 1] (every mode above, the host loop included): blank-frame skipping - a frame whose blank posterior is above p
+    (log p(blank) > float32(log p), strict) and whose predecessor's is too is dropped before the search (asr_ctc_blank_skip_compact
+    between the two kernels); the head of every run of such frames stays, so a doubled character keeps its separating blank.  The
+    result is by definition the search on the kept frames: 'score' / 'ctc_score' sum over them only, and the frames of beam_times are
+    mapped back to real frames (asr_frame_index_remap).  p = 1 keeps every frame; None (the default) launches what is launched without it."""
     if context is None and context_ids is not None:
         raise ValueError("context_ids needs a context")
+    thr = None if blank_skip is None else K.blank_skip_threshold(blank_skip)
     which = None
     if beam_times:
         from .confidence import beam_times_check
@@ -274,6 +292,9 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
         if not fits:
             raise ValueError(f"the device search ranks beam * (frame_topk + 1) <= 64 candidates per frame (beam {beam_size}, frame_topk {k})")
         in_len = input.wave_len.to(torch.int32).contiguous()
+        frame_map = None
+        if thr is not None:      # the search runs on the kept rows, with their count for its length
+            vals, ids, blank_lp, in_len, frame_map = K.ctc_blank_skip_compact(vals, ids, blank_lp, in_len, thr, B, T)
         if biased is not None:      # the whole beam comes back: the reported term is settled on the host, then the order, then the cut to nbest
             res = K.ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam_size, beam_size, BLANK_ID, context=context, roots=roots, lm=lm)
             tok, ln, sc, bias, state = (t.cpu().tolist() for t in res)
@@ -281,10 +302,13 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
         if beam_times:
             from .confidence import beam_tokens
             res = K.ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam_size, nbest, BLANK_ID, times=True)
+            # behind blank skipping the records count kept rows: the reported frames are the real ones, the measures stay over the kept rows
+            real = None if frame_map is None else [K.frame_index_remap(res[i], frame_map).cpu().numpy() for i in (4, 5)]
             tok, ln, sc, vit, start, end, mx, mn, sm = (t.cpu().numpy() for t in res)
             d, id2tok = model.frame_seconds(), model.vocab._id2token
             return [[{"yseq": tok[b, r, :ln[b, r]].tolist(), "score": float(sc[b, r]), "viterbi_score": float(vit[b, r]),
-                      "tokens": beam_tokens(tok[b, r, :ln[b, r]], *(x[b, r, :ln[b, r]] for x in (start, end, mx, mn, sm)), which, id2tok, d)}
+                      "tokens": beam_tokens(tok[b, r, :ln[b, r]], *(x[b, r, :ln[b, r]] for x in (start, end, mx, mn, sm)), which, id2tok, d,
+                                            real=None if real is None else [x[b, r, :ln[b, r]] for x in real])}
                      for r in range(nbest) if ln[b, r] >= 0] for b in range(B)]
         tok, ln, sc = K.ctc_prefix_beam(vals, ids, blank_lp, in_len, B, T, beam_size, nbest, BLANK_ID)
         tok, ln, sc = tok.cpu().tolist(), ln.cpu().tolist(), sc.cpu().tolist()
@@ -305,7 +329,7 @@ def ctc_prefix_beam_search(model, input, beam_size=5, nbest=1, frame_topk=10, on
         else:
             rank = lambda kv: _logadd(kv[1][0], kv[1][1])      # noqa: E731
         beam = {(): (0.0, -math.inf)}                        # prefix -> (log p ending in blank, log p ending in a symbol)
-        for t in range(int(lens[b])):
+        for t in (range(int(lens[b])) if thr is None else blank_skip_kept(blank_lp[b], int(lens[b]), thr)):
             lb = blank_lp[b][t]
             nxt = {}
             for prefix, (pb, pnb) in beam.items():
@@ -454,11 +478,14 @@ def attention_rescore(model, enc, wave_len, nbest_lists, ctc_weight):
     return out
 
 
-def ctc_rescore_search(model, input, beam_size=5, nbest=1, ctc_weight=0.0, frame_topk=10, context=None, context_ids=None, lm=None):
+def ctc_rescore_search(model, input, beam_size=5, nbest=1, ctc_weight=0.0, frame_topk=10, context=None, context_ids=None, lm=None, blank_skip=None):
     """The U2 two-pass search offline: ctc_prefix_beam_search with n-best = beam_size, then attention_rescore of that list against the
     same encoder output (the encoder runs once).  Returns per utterance at most `nbest` {'yseq' (no sos / eos), 'score', 'att_score',
     'ctc_score'}.  context / context_ids: the first pass is hotword-biased (ctc_prefix_beam_search); entries gain 'bias'.  lm: the first
-    pass runs with the n-gram LM; entries gain 'lm_score'."""
+    pass runs with the n-gram LM; entries gain 'lm_score'.  blank_skip: the first pass skips blank frames (ctc_prefix_beam_search); the
+    decoder pass is what it is."""
+    if blank_skip is not None:
+        K.blank_skip_threshold(blank_skip)      # refused before anything is launched
     if lm is not None:
         _check_lm(model, lm, context)
     eng = model._ensure_engine(input.wave.device)
@@ -471,7 +498,8 @@ def ctc_rescore_search(model, input, beam_size=5, nbest=1, ctc_weight=0.0, frame
     finally:
         eng.training = was_training
     with model.given_encoder_output(enc):
-        hyps = ctc_prefix_beam_search(model, input, beam_size, beam_size, frame_topk, context=context, context_ids=context_ids, lm=lm)
+        hyps = ctc_prefix_beam_search(model, input, beam_size, beam_size, frame_topk, context=context, context_ids=context_ids, lm=lm,
+                                      blank_skip=blank_skip)
     res = attention_rescore(model, enc, input.wave_len, hyps, ctc_weight)
     return [r[:nbest] for r in res]
 

@@ -6,6 +6,7 @@ import math
 import threading
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -642,6 +643,66 @@ def ctc_prefix_beam_state_reset(st, flags, slots=(), roots=None, lm=None):
         st.frames[int(b)] = 0
         if host is not None:
             st.roots[int(b)] = host[int(b)]
+
+
+# --------------------------------------------------------------------------------- blank-frame skipping (csrc/blank_skip.hip)
+def blank_skip_threshold(p):
+    """The kernel argument of blank_skip=p: float32(log(float32(p))) as a Python float; p outside (0, 1] or not finite raises ValueError."""
+    try:
+        p = float(p)
+    except (TypeError, ValueError):
+        raise ValueError(f"blank_skip must be a probability in (0, 1] (got {p!r})") from None
+    if not (math.isfinite(p) and 0.0 < p <= 1.0):
+        raise ValueError(f"blank_skip must be a probability in (0, 1] (got {p!r})")
+    with np.errstate(divide="ignore"):      # a p below float32's range: log 0 = -inf, every frame with a posterior is high
+        return float(np.float32(np.log(np.float32(p))))
+
+
+class BlankSkipState:
+    """The resumable compaction's device memory: `state` (B, 4) int32 {carry bit, frames seen, frames kept, 0} and `frame_map` (B, T_cap)
+    int32, the real frame of every kept row so far (include/asr_hip.h: asr_ctc_blank_skip_compact)."""
+
+    def __init__(self, B, T_cap, device):
+        self.B, self.T_cap = int(B), int(T_cap)
+        self.state = torch.zeros(self.B, 4, dtype=torch.int32, device=device)
+        self.frame_map = torch.zeros(self.B, self.T_cap, dtype=torch.int32, device=device)
+
+
+def ctc_blank_skip_compact(vals, ids, blank_lp, count, thr, B, T, st=None, reset=None):
+    """Drop the frames whose blank log-posterior and whose predecessor's are above thr (asr_ctc_blank_skip_compact): vals / ids (B*T, k),
+    blank_lp (B*T) from ctc_frame_topk, count (B) int32 on the device (None: T each), thr = blank_skip_threshold(p).  Returns (vals, ids,
+    blank_lp in the same layout with the kept rows first, out_len (B) int32, frame_map) - frame_map (B, T) int32 = the frame of every
+    kept row, zero behind them; with st (a BlankSkipState: the chunks of a stream, T = the chunk's rows) st.frame_map, extended by this
+    chunk's kept rows.  reset (B) int32 on the device, with st: the flagged utterances start over before this chunk."""
+    B, T, k = int(B), int(T), vals.shape[1]
+    assert vals.shape == (B * T, k) and ids.shape == (B * T, k) and blank_lp.numel() == B * T
+    assert vals.is_contiguous() and ids.is_contiguous() and blank_lp.is_contiguous()
+    _chk_f32(vals, blank_lp)
+    _chk_i32(ids, count, reset)
+    assert (count is None or count.numel() == B) and (reset is None or (st is not None and reset.numel() == B)) and (st is None or st.B == B)
+    dev = vals.device
+    out_vals, out_ids, out_blank_lp = torch.empty_like(vals), torch.empty_like(ids), torch.empty_like(blank_lp)
+    out_len = torch.zeros(B, dtype=torch.int32, device=dev)
+    frame_map = torch.zeros(B, T, dtype=torch.int32, device=dev) if st is None else st.frame_map
+    if B * T > 0:
+        check(lib.asr_ctc_blank_skip_compact(_p(vals), _p(ids), _p(blank_lp), _p(count), float(thr), _p(st.state) if st is not None else None, _p(reset),
+                                             _p(out_vals), _p(out_ids), _p(out_blank_lp), _p(out_len), _p(frame_map), B, T, k, frame_map.shape[1],
+                                             _stream()), "asr_ctc_blank_skip_compact")
+    return out_vals, out_ids, out_blank_lp, out_len, frame_map
+
+
+def frame_index_remap(idx, frame_map, out=None):
+    """idx (B, ...) int32 -> out of its shape (a new tensor unless given; idx itself is fine): every index >= 0 becomes frame_map[b, index],
+    a negative one stays (asr_frame_index_remap): frames over kept rows -> real frames."""
+    B = frame_map.shape[0]
+    out = torch.empty_like(idx) if out is None else out
+    _chk_i32(idx, frame_map, out)
+    assert idx.shape[0] == B and out.shape == idx.shape
+    if idx.numel() > 0 and frame_map.shape[1] > 0:
+        check(lib.asr_frame_index_remap(_p(idx), _p(frame_map), _p(out), B, idx.numel() // B, frame_map.shape[1], _stream()), "asr_frame_index_remap")
+    else:
+        out.copy_(idx)
+    return out
 
 
 # --------------------------------------------------------------------------------- independent sessions (csrc/session.hip)

@@ -48,6 +48,16 @@ each hypothesis' tokens with frames, times and confidence, and tokens(b) the bes
 change flagged final.  The reset kernel restarts a reopened slot's lists at frame 0; results, finish, drop and open drop the slot's
 records on the host.
 
+blank_skip=p (prefix beam sessions): blank-frame skipping in front of the search (decode.ctc_prefix_beam_search describes the rule).  Per
+tick asr_ctc_blank_skip_compact moves the chunk's kept rows to the front of each slot's rows and its device count takes the place of
+n_valid in asr_ctc_prefix_beam_chunk*; per slot it carries one bit (the last consumed frame was high), the frames seen and kept, and the
+real frame of every kept row, through which the records of beam_times go back to real frames (asr_frame_index_remap).  A slot that sits
+a tick out keeps its bit, the reset flags of a reopened slot clear it with its beam, and drop / finish leave nothing behind: the state is
+reset when the slot is next opened.  The host-side frame counter of the beam state keeps counting PUSHED frames - an upper bound of the
+kept ones, so the refusal of a chunk past the trie's T_cap stays safe (it may come early, never late).  Endpointing and the counters
+of asr_session_ctc_step read the uncompacted blank_lp: trailing silence and frame counts do not change.  After every push the
+hypotheses are bit for bit those of the offline search with blank_skip on the frames so far.
+
 Out of scope: input rates other than 16 kHz for sessions (StreamResampler has no per-slot reset; the lock-step view resamples in front
 of its own front end), compaction of idle slots (every tick computes slots * C rows), carrying audio across an endpoint, a varying
 number of slots, capture into a hipGraph."""
@@ -104,7 +114,7 @@ def endpoint_rule(rules, frame_us, trailing, frames, decoded):
 
 class Sessions:
     def __init__(self, model, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None,
-                 timed=False, confidence="post_max", beam_times=False, _lockstep=False):
+                 timed=False, confidence="post_max", beam_times=False, blank_skip=None, _lockstep=False):
         """_lockstep: set by stream.StreamingEncoder alone - the messages name model.stream(), and a model without the CTC head is
         admitted: its tick ends once the encoder rows are stored, push returns empty lists and the results come from the attention beam."""
         who = "model.stream()" if _lockstep else "model.sessions()"
@@ -119,6 +129,12 @@ class Sessions:
         if search not in ("greedy", "prefix_beam"):
             raise ValueError(f"search must be 'greedy' or 'prefix_beam' (got {search!r})")
         self.search, self.beam_size, self.frame_topk = search, int(beam_size), int(frame_topk)
+        # blank_skip=p (prefix beam sessions): the float32 log threshold of the compaction in front of the search, and its per-slot state
+        self.skip_thr, self.skip = None, None
+        if blank_skip is not None:
+            self.skip_thr = K.blank_skip_threshold(blank_skip)
+            if search != "prefix_beam":
+                raise ValueError("blank_skip needs search='prefix_beam': it drops frames in front of the CTC prefix beam search, the greedy path reads every frame")
         # timed=True (greedy sessions): every emitted token's frames, times and confidence (confidence.TokenLog, tokens(b))
         self.timed, self.log, self.run_state = bool(timed), None, None
         if self.timed:
@@ -179,6 +195,7 @@ class Sessions:
         self.beam = None
         self._hyps = None
         self._times = None                   # beam_times: the last tick's (vit, start, end, mx, mn, sm, final) as host arrays
+        self._real = None                    # ... behind blank_skip: the records' (start, end) in real frames
         self.has_times = [False] * S         # ... and whether slot b's rows of them belong to its session (dropped by finish / drop / open)
         self.parser, self.frontend = parser, None
 
@@ -323,8 +340,9 @@ class Sessions:
         tok, ln = self._hyps[0], self._hyps[1]
         _, start, end, mx, mn, sm, fin = self._times
         n = max(int(ln[b, r]), 0)
+        real = None if self._real is None else [x[b, r, :n] for x in self._real]
         return beam_tokens(tok[b, r, :n], start[b, r, :n], end[b, r, :n], mx[b, r, :n], mn[b, r, :n], sm[b, r, :n], self.which, self.model.vocab._id2token,
-                           self.model.frame_seconds(), int(fin[b]) if final else None)
+                           self.model.frame_seconds(), int(fin[b]) if final else None, real=real)
 
     def _tick(self, eng, feats, nv, out):
         S, C, dev = self.S, self.C, feats.device
@@ -400,21 +418,35 @@ class Sessions:
             elif reset_slots:
                 K.ctc_prefix_beam_state_reset(self.beam, pd[P_RESET], reset_slots, roots=roots)
             vals, ids, blank_lp = K.ctc_frame_topk(logits, self.frame_topk, BLANK)
-            buf, Lcap = K.ctc_prefix_beam_chunk(self.beam, vals, ids, blank_lp, nv, C, self.beam_size, BLANK, packed=True, nv_dev=nv_dev,
-                                                extra_words=S * (4 + C))
-            n_words = buf.numel() - S * (4 + C)      # the search's words (with a context: bias and state included)
-            K.session_ctc_step(None, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK, out=buf[n_words:].view(S, 4 + C))
+            cand, n_dev = (vals, ids, blank_lp), nv_dev
+            if self.skip_thr is not None:      # the search sees the kept rows and their count; nv stays the host's upper bound of it
+                if self.skip is None:
+                    self.skip = K.BlankSkipState(S, eng.pe.shape[0], dev)
+                *cand, n_dev, _ = K.ctc_blank_skip_compact(vals, ids, blank_lp, nv_dev, self.skip_thr, S, C, self.skip, pd[P_RESET])
+            # behind blank skipping the records of beam_times count kept rows: their real frames travel behind the step words in the same copy
+            Lcap = max(1, max(f + n for f, n in zip(self.beam.frames, nv)))      # ctc_prefix_beam_chunk's own default
+            n_real = S * self.beam_size * Lcap if self.skip is not None and self.beam_times else 0
+            buf, Lcap = K.ctc_prefix_beam_chunk(self.beam, *cand, nv, C, self.beam_size, BLANK, max_len=Lcap, packed=True, nv_dev=n_dev,
+                                                extra_words=S * (4 + C) + 2 * n_real)
+            n_words = buf.numel() - S * (4 + C) - 2 * n_real      # the search's words (with a context: bias and state included)
+            n_step = n_words + S * (4 + C)
+            if n_real:
+                views = K.prefix_beam_unpack(buf[:n_words], S, self.beam_size, Lcap, "timed")
+                for i, v in enumerate(views[5:7]):      # start, end
+                    K.frame_index_remap(v, self.skip.frame_map, out=buf[n_step + i * n_real:n_step + (i + 1) * n_real].view(v.shape))
+            K.session_ctc_step(None, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK, out=buf[n_words:n_step].view(S, 4 + C))
             host = buf.cpu()
             tok, ln, sc, stable, *extra = (t.numpy() for t in K.prefix_beam_unpack(host[:n_words], S, self.beam_size, Lcap, self.beam.mode))
             self._hyps = (tok, ln, sc)
             if self.beam_times:
                 self._times = tuple(extra)
+                self._real = tuple(host[n_step + i * n_real:n_step + (i + 1) * n_real].view(S, self.beam_size, Lcap).numpy() for i in (0, 1)) if n_real else None
                 for b in range(S):
                     if self.state[b] != FREE:
                         self.has_times[b] = True
             else:
                 self._hyps += tuple(extra)      # with a context / an LM: bias and state
-            step = host[n_words:].view(S, 4 + C).tolist()
+            step = host[n_words:n_step].view(S, 4 + C).tolist()
             for b in reset_slots:
                 self.stable[b] = 0
             for b in range(S):

@@ -1169,6 +1169,28 @@ int asr_ctc_align_long_filler(const void* rows, const float* lse, const float* s
                               float* tok, double* score, void* ws, size_t ws_bytes, int R, int V, int ld, int dtype, int blank,
                               void* stream);
 
+/* Blank-frame skipping in front of the CTC prefix beam search.  Additive to ABI 10.  The definition is tests/blank_skip_ref.py.
+ * asr_ctc_blank_skip_compact: vals / ids (B*T, k), blank_lp (B*T) = the per-frame candidates of asr_ctc_frame_topk; count (B) int32 on
+ *   the device = the frames of each utterance (in_len offline, n_valid per chunk; NULL = T; clamped to [0, T]).  Frame t < count[b] is
+ *   high iff blank_lp[b, t] > thr (float32 against float32, strict: a NaN is not high; thr = log p <= 0) and dropped iff it is high and
+ *   its predecessor exists and is high: the head of every run of high frames stays.  The kept rows are copied in order to the front of
+ *   the utterance's rows of out_vals / out_ids / out_blank_lp (the same (B, T) layout, never in place), out_len[b] = their number, and
+ *   out_frame[b, i] = the frame the i-th kept row was.  Rows at and past count[b] are neither read nor counted; output rows at and past
+ *   out_len[b] keep what they held.  No atomics and one fixed order: two runs write the same bytes.  k <= 63.
+ *   state == NULL (offline): out_frame is (B, map_cap) with map_cap >= T (or NULL with map_cap 0).
+ *   state (B, 4) int32 {carry = the last consumed frame was high, frames seen, frames kept, 0}, zeros at first (the resumable form, one
+ *   launch per chunk): the predecessor of a chunk's frame 0 is the carry bit, out_frame is a per-utterance map (B, map_cap) that the
+ *   launch extends at [kept, kept + out_len[b]) with seen + t (entries past map_cap are not written), and the state is advanced; after
+ *   any cutting of the frames into chunks (empty ones included: count 0 keeps every word of the state) the kept frames are those of one
+ *   launch over all of them.  reset (B) int32 or NULL, with a state only: reset[b] != 0 treats utterance b's state as zeros before the
+ *   chunk, with the meaning of asr_ctc_prefix_beam_state_reset's flags.
+ * asr_frame_index_remap: idx, out (B, per) int32 (out may be idx): out[b, i] = idx[b, i] < 0 ? idx[b, i] : map[b, idx[b, i]], map
+ *   (B, map_cap); an index >= map_cap stays.  Takes the start / end frames of the timed searches run on kept rows back to real frames. */
+int asr_ctc_blank_skip_compact(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* count, float thr,
+                               int32_t* state, const int32_t* reset, float* out_vals, int32_t* out_ids, float* out_blank_lp,
+                               int32_t* out_len, int32_t* out_frame, int B, int T, int k, int map_cap, void* stream);
+int asr_frame_index_remap(const int32_t* idx, const int32_t* map, int32_t* out, int B, int per, int map_cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,10 @@ trained with rebuild it.  Inference flags:
                  final lines gain "lm_score".  The same searches as --context admits; not together with --context
   --lm_weight    the LM weight (default 0.3)
   --lm_ins       the bonus per token of a hypothesis (default 0.0)
+  --blank_skip   a probability in (0, 1], e.g. 0.98: blank-frame skipping in front of the CTC prefix beam search - a frame whose blank
+                 posterior is above it, and whose predecessor's is too, is dropped before the search (the head of every such run stays);
+                 scores then sum over the kept frames.  The same searches as --context admits: offline, --long=1, and --stream=1
+                 --stream_search=prefix_beam (--sessions=N included)
   --confidence   post_max (WeNet's measure), post_min, post_mean, ent_mean or ent_min: every token of the final lines gains "confidence"
                  (that measure over the token's frames) and "measures" (all five), the line "confidence" (the mean over its tokens);
                  from the CTC posteriors, so it needs the CTC head and timestamps
@@ -94,7 +98,7 @@ from asr_chinese_e2e_amd.Utils import Pack  # noqa: E402
 from asr_chinese_e2e_amd.data_handler import resample as resample_mod  # noqa: E402
 from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 
-CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint", "context", "context_score", "lm", "lm_weight", "lm_ins", "confidence", "timed", "beam_times", "long", "vad_energy_threshold", "vad_energy_mean_scale", "vad_frames_context", "vad_proportion_threshold", "min_silence_s", "min_speech_s", "pad_s", "max_segment_s")
+CLI_KEYS = ("ckpt", "wavs", "manifest", "beam_size", "batch_size", "timestamps", "joint", "stream", "cmvn", "stream_block_samples", "resample", "stream_search", "frame_topk", "frontend", "sessions", "endpoint", "context", "context_score", "lm", "lm_weight", "lm_ins", "blank_skip", "confidence", "timed", "beam_times", "long", "vad_energy_threshold", "vad_energy_mean_scale", "vad_frames_context", "vad_proportion_threshold", "min_silence_s", "min_speech_s", "pad_s", "max_segment_s")
 VAD_FLAGS = {"vad_energy_threshold": "energy_threshold", "vad_energy_mean_scale": "energy_mean_scale", "vad_frames_context": "frames_context",
              "vad_proportion_threshold": "proportion_threshold"}
 SEGMENT_FLAGS = ("min_silence_s", "min_speech_s", "pad_s", "max_segment_s")
@@ -408,6 +412,22 @@ def transcribe(**flags):
             raise SystemExit(f"transcribe.py: --lm: {e}") from e
         if stream:
             stream_kw["lm"] = lm
+    blank_skip = None
+    if cli.get("blank_skip") is not None and cli["blank_skip"] != "":      # 0 is a value, and a refused one
+        from asr_chinese_e2e_amd.kernels import blank_skip_threshold
+        try:
+            if isinstance(cli["blank_skip"], bool):
+                raise ValueError("a flag without a value")
+            blank_skip = float(cli["blank_skip"])
+            blank_skip_threshold(blank_skip)
+        except (TypeError, ValueError) as e:
+            raise SystemExit(f"transcribe.py: --blank_skip must be a probability in (0, 1] (got {cli['blank_skip']!r})") from e
+        if stream and stream_search != "prefix_beam":
+            raise SystemExit("transcribe.py: --blank_skip with --stream=1 needs --stream_search=prefix_beam (frames are dropped in front of the CTC prefix beam search)")
+        if not stream and model.use_decoder and joint != "ctc_rescore":
+            raise SystemExit("transcribe.py: --blank_skip needs a search that runs the CTC prefix beam search: a CTC-only model or --joint=ctc_rescore")
+        if stream:
+            stream_kw["blank_skip"] = blank_skip
     resample = bool(int(cli.get("resample", 0)))      # --resample=1: files at another rate are converted on the GPU instead of ending the run
     if stream and model.decoding_chunk_size <= 0:
         raise SystemExit("transcribe.py: --stream=1 needs a decoding chunk (--decoding_chunk_size, or a static --chunk_size)")
@@ -433,6 +453,8 @@ def transcribe(**flags):
             search["context"] = context
         if lm is not None:
             search["lm"] = lm
+        if blank_skip is not None:
+            search["blank_skip"] = blank_skip
         if confidence is not None:
             search["confidence"] = confidence
         transcribe_long_files(model, parser, files, long_form[0], long_form[1], bs, resample, shift_s, config.sample_rate, **search)
@@ -468,6 +490,8 @@ def transcribe(**flags):
             search["context"] = context
         if lm is not None and not stream:
             search["lm"] = lm
+        if blank_skip is not None and not stream:
+            search["blank_skip"] = blank_skip
         if beam_stream:      # the streamed search's own n-best, re-ranked by the decoder
             search = dict(ctc_weight=ctc_weight, timestamps=timestamps, joint="ctc_rescore")
         if confidence is not None:
