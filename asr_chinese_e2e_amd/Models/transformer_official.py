@@ -330,7 +330,7 @@ class _SpeechTransformer(BaseModel):
         return ctx()
 
     def stream(self, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None, lm=None,
-               timed=False, confidence="post_max", beam_times=False, blank_skip=None):
+               timed=False, confidence="post_max", beam_times=False, blank_skip=None, keywords=None):
         """A streaming encoder for `batch_size` utterances in lock-step (stream.StreamingEncoder, a view of sessions.Sessions with every
         slot opened at once): push chunks of encoder-rate features, get the greedy CTC ids each chunk adds; finish() gives transcribe()'s
         result for the same decoding chunk mask, frees nothing and may be repeated.  A model without the CTC head streams too: push
@@ -350,14 +350,16 @@ class _SpeechTransformer(BaseModel):
         alignment (asr_ctc_prefix_beam_chunk_timed); nbest() entries gain "viterbi_score" and "tokens", partial() "tokens", and tokens()
         lists the best hypothesis' tokens with "final" flags.  confidence: post_max, post_min or post_mean.
         blank_skip=p in (0, 1] (search="prefix_beam" only): blank-frame skipping in front of the streamed search, with one carried bit
-        per utterance - after every push bit for bit ctc_prefix_beam_search(blank_skip=p) on the frames so far (sessions.py)."""
+        per utterance - after every push bit for bit ctc_prefix_beam_search(blank_skip=p) on the frames so far (sessions.py).
+        keywords (a keywords.KeywordList; any search, not with blank_skip): keyword spotting with the audio - keyword_hits() lists per
+        utterance the hits so far, as spot_keywords reports them."""
         from ..stream import StreamingEncoder
         return StreamingEncoder(self, batch_size, parser=parser, source_rate=source_rate, search=search, beam_size=beam_size, frame_topk=frame_topk,
                                 context=context, context_ids=context_ids, lm=lm, timed=timed, confidence=confidence, beam_times=beam_times,
-                                blank_skip=blank_skip)
+                                blank_skip=blank_skip, keywords=keywords)
 
     def sessions(self, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None,
-                 timed=False, confidence="post_max", beam_times=False, blank_skip=None):
+                 timed=False, confidence="post_max", beam_times=False, blank_skip=None, keywords=None):
         """`slots` independent streaming sessions in one batch (sessions.Sessions, the owner of the streaming state and tick that
         stream() views in lock-step; needs the CTC head): each slot is opened, fed (push / push_audio), closed, finished and reopened at
         its own pace - open(b), push(feats, n_valid, final), results(b) without freeing, finish(b) - and with endpoint={...} the
@@ -369,10 +371,12 @@ class _SpeechTransformer(BaseModel):
         beam_times=True (search="prefix_beam" only, not with a context or an LM): as stream()'s - nbest(b) / partial(b) gain "tokens",
         tokens(b) lists slot b's best hypothesis with "final" flags; finish, drop and reopening drop the records.
         blank_skip=p (search="prefix_beam" only): as stream()'s; a reopened slot starts with a clear carry bit, and endpointing keeps
-        counting every frame."""
+        counting every frame.
+        keywords (a keywords.KeywordList; any search, not with blank_skip): one phrase list for all slots - keyword_hits(b) lists slot
+        b's hits so far (final closes a match still open), a reopened slot starts an empty list."""
         from ..sessions import Sessions
         return Sessions(self, slots, parser=parser, search=search, beam_size=beam_size, frame_topk=frame_topk, endpoint=endpoint, source_rate=source_rate,
-                        context=context, lm=lm, timed=timed, confidence=confidence, beam_times=beam_times, blank_skip=blank_skip)
+                        context=context, lm=lm, timed=timed, confidence=confidence, beam_times=beam_times, blank_skip=blank_skip, keywords=keywords)
 
     def forward(self, input):
         """transformer_official.py:68-81 (inference-style forward; no gradients).  A batch without a transcript (only wave / wave_len)
@@ -689,6 +693,26 @@ class _SpeechTransformer(BaseModel):
         return align_long(self, parser, wav, wav_len, texts, vad=vad, batch_size=batch_size, source_rate=source_rate, min_silence_s=min_silence_s,
                           min_speech_s=min_speech_s, pad_s=pad_s, max_segment_s=max_segment_s, confidence=confidence, max_bytes=max_bytes, filler=filler,
                           filler_scope=filler_scope)
+
+    def spot_keywords(self, input, keywords):
+        """Keyword spotting on the CTC posteriors (keywords.spot_keywords; needs the CTC head, ValueError before any launch otherwise):
+        every phrase of `keywords` (a keywords.KeywordList) against every frame of the batch, with a free start and a free end - the
+        encoder and the CTC projection as ctc_align runs them, then asr_ctc_frame_stats, asr_kws_search and asr_kws_compact.
+        Returns per utterance {"hits": [{"keyword", "phrase", "ids", "start_frame", "end_frame", "start_s", "end_s", "score",
+        "confidence"}], "dropped"}: score = the log-probability of the phrase's best alignment ending on end_frame, confidence =
+        exp(score / L), start_frame = the last frame of the first character's run, times as ctc_align's; the hits sorted by
+        (end_frame, keyword); dropped = the hits past hits_per_keyword or the list's max_hits."""
+        from ..keywords import spot_keywords
+        return spot_keywords(self, input, keywords)
+
+    def spot_long(self, parser, wav, wav_len, keywords, vad=None, batch_size=16, source_rate=None, min_silence_s=0.3, min_speech_s=0.1, pad_s=0.1,
+                  max_segment_s=20.0):
+        """Keyword spotting over whole recordings (keywords.spot_long): transcribe_long's segments and batches with spot_keywords in
+        place of transcribe.  Per recording {"hits", "dropped", "duration_s", "segments"}: hit times on the recording's clock, frames
+        relative to the hit's "segment"; a recording without speech has hits []."""
+        from ..keywords import spot_long
+        return spot_long(self, parser, wav, wav_len, keywords, vad=vad, batch_size=batch_size, source_rate=source_rate, min_silence_s=min_silence_s,
+                         min_speech_s=min_speech_s, pad_s=pad_s, max_segment_s=max_segment_s)
 
     def _hyp_dicts(self, ids, scores, timestamps, ctc_logits, wave_len, biases=None, bias_key="bias", confidence=None):
         """transcribe's result dicts for the best ids / score of each utterance; ctc_logits() -> (B, T, V) is called for timestamps only.

@@ -30,7 +30,8 @@ NOISE_MIX_TILE = 4096      # ASR_NOISE_MIX_TILE: samples per workgroup and energ
 VAD_CTX_MAX = 1024     # ASR_VAD_CTX_MAX: the largest frames_context asr_vad_decide takes
 ALIGN_LONG_MAX_LABELS = 8192      # ASR_ALIGN_LONG_MAX_LABELS: labels per recording of asr_ctc_align_long
 SPECAUG_MAX_RANGES = 8     # ASR_SPECAUG_MAX_RANGES: ranges of one kind in a row of asr_*_norm_specaug_lfr_fwd
-STREAM_OPEN = 0x3fffffff      # ASR_STREAM_OPEN: "length not known yet" in the streaming front end's parameter arrays
+KWS_MAX_LEN, KWS_MAX_KEYWORDS, KWS_MAX_CAP = 16, 65536, 64      # ASR_KWS_*: tokens per keyword, keywords per list, records per (utterance, keyword)
+STREAM_OPEN = 0x3fffffff     # ASR_STREAM_OPEN: "length not known yet" in the streaming front end's parameter arrays
 
 P, I, F, Z, U = c_void_p, c_int, c_float, c_size_t, c_uint32
 
@@ -197,6 +198,13 @@ SIGNATURES = {
     "asr_ctc_align_long_filler": (I, [P] * 13 + [Z, I, I, I, I, I, P]),
     "asr_ctc_blank_skip_compact": (I, [P, P, P, P, F, P, P, P, P, P, P, P, I, I, I, I, P]),
     "asr_frame_index_remap": (I, [P, P, P, I, I, I, P]),
+    "asr_kws_state_bytes": (Z, [I, I]),
+    "asr_kws_records_bytes": (Z, [I, I, I]),
+    "asr_kws_search": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "asr_kws_chunk": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "asr_kws_compact": (I, [P, P, P, P, P, I, I, I, I, P]),
+    "asr_kws_state_init": (I, [P, I, I, P]),
+    "asr_kws_state_reset": (I, [P, P, I, I, P]),
 }
 
 

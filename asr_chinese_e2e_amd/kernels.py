@@ -1682,3 +1682,70 @@ def ctc_align_long_filler(rows, lse, star, row_off, labels, lab_off, gap, gap_ta
     refuses what it refuses, and also (ValueError, on the host): a star that is not f32 or whose length is not the number of rows, NaN in
     star, a gap whose length is not the number of labels, a gap_tail whose length is not R."""
     return _ctc_align_long("ctc_align_long_filler", rows, lse, row_off, labels, lab_off, blank, ws, fill=(star, gap, gap_tail))
+
+
+# ------------------------------------------------------------------------------------------------ keyword spotting (csrc/kws.hip)
+def kws_search(logits, lse, in_len, tables, K_, cap, blank=0):
+    """Every keyword of `tables` (the asr_kws_list of keywords.KeywordList.on) against logits (B, T, V), lse (B, T) from ctc_frame_stats
+    (asr_kws_search).  Returns (cnt (B, K) int32: the hits per keyword, counting past cap; rec (B, K, cap, 3) int32 {start, end, score
+    bits}: the first cap of each, in order of their end)."""
+    B, T, V = logits.shape
+    ld = _frame_rows(logits)
+    _chk_i32(in_len)
+    _chk_f32(lse)
+    assert lse.shape == (B, T) and (in_len is None or in_len.numel() == B)
+    cnt = torch.empty(B, K_, dtype=torch.int32, device=logits.device)
+    rec = torch.empty(B, K_, cap, 3, dtype=torch.int32, device=logits.device)
+    check(lib.asr_kws_search(_p(logits), _p(lse), _p(in_len), ctypes.addressof(tables), _p(cnt), _p(rec), B, T, V, ld, int(blank), int(cap), _dt(logits),
+                             _stream()), "asr_kws_search")
+    return cnt, rec
+
+
+def kws_state(slots, K_, device):
+    """The state of asr_kws_chunk for `slots` sessions and K keywords, initialised (asr_kws_state_init): an int32 tensor."""
+    state = torch.empty(lib.asr_kws_state_bytes(int(slots), int(K_)) // 4, dtype=torch.int32, device=device)
+    check(lib.asr_kws_state_init(_p(state), int(slots), int(K_), _stream()), "asr_kws_state_init")
+    return state
+
+
+def kws_state_reset(state, flags, K_):
+    """Slots b with flags[b] != 0 (int32, on the device) go back to the initial state (asr_kws_state_reset)."""
+    _chk_i32(state, flags)
+    check(lib.asr_kws_state_reset(_p(state), _p(flags), flags.numel(), int(K_), _stream()), "asr_kws_state_reset")
+
+
+def kws_chunk(logits, lse, n_valid, reset, final, tables, K_, state, cap, blank=0):
+    """One chunk of the resumable search (asr_kws_chunk): logits (slots, C, V), lse (slots, C), n_valid / reset / final (slots) int32,
+    state from kws_state (updated in place).  Returns (cnt, rec) as kws_search, for the runs this chunk closed; frames count from the
+    session's first frame."""
+    slots, C, V = logits.shape
+    ld = _frame_rows(logits)
+    _chk_i32(n_valid, reset, final, state)
+    _chk_f32(lse)
+    assert lse.shape == (slots, C) and n_valid.numel() == slots and reset.numel() == slots and final.numel() == slots
+    assert state.numel() * 4 == lib.asr_kws_state_bytes(slots, int(K_))
+    cnt = torch.empty(slots, K_, dtype=torch.int32, device=logits.device)
+    rec = torch.empty(slots, K_, cap, 3, dtype=torch.int32, device=logits.device)
+    check(lib.asr_kws_chunk(_p(logits), _p(lse), _p(n_valid), _p(reset), _p(final), ctypes.addressof(tables), _p(state), _p(cnt), _p(rec), slots, C, V, ld,
+                            int(blank), int(cap), _dt(logits), _stream()), "asr_kws_chunk")
+    return cnt, rec
+
+
+def kws_compact(cnt, rec, max_hits, out=None):
+    """(cnt, rec) of kws_search / kws_chunk -> (count (B), dropped (B), hits (B, max_hits, 4) int32 {keyword, start, end, score bits}) in
+    the fixed order keyword ascending, then end ascending (asr_kws_compact).  The three are views of one int32 buffer of
+    B * (2 + 4 max_hits) words (out, or a new one): one copy takes them to the host, kws_unpack reads them there."""
+    _chk_i32(cnt, rec, out)
+    B, K_, cap, _ = rec.shape
+    assert cnt.shape == (B, K_)
+    if out is None:
+        out = torch.empty(B * (2 + 4 * int(max_hits)), dtype=torch.int32, device=cnt.device)
+    count, dropped, hits = kws_unpack(out, B, max_hits)
+    check(lib.asr_kws_compact(_p(cnt), _p(rec), _p(count), _p(dropped), _p(hits), B, K_, cap, int(max_hits), _stream()), "asr_kws_compact")
+    return count, dropped, hits
+
+
+def kws_unpack(flat, B, max_hits):
+    """The views (count (B), dropped (B), hits (B, max_hits, 4)) of kws_compact's buffer, on the device or on the host."""
+    assert flat.numel() == B * (2 + 4 * int(max_hits))
+    return flat[:B], flat[B:2 * B], flat[2 * B:].view(B, int(max_hits), 4)

@@ -58,6 +58,14 @@ kept ones, so the refusal of a chunk past the trie's T_cap stays safe (it may co
 of asr_session_ctc_step read the uncompacted blank_lp: trailing silence and frame counts do not change.  After every push the
 hypotheses are bit for bit those of the offline search with blank_skip on the frames so far.
 
+keywords=KeywordList (any search): keyword spotting with the audio (keywords.py).  The tick needs each frame's log-sum-exp: the timed tick
+has it, the untimed greedy tick runs asr_ctc_frame_stats in place of asr_ctc_frame_best_blank (the same path and blank_lp bits), the
+prefix beam tick runs it as one more launch.  Then asr_kws_chunk advances every slot's lattice columns and open runs (one state for all
+slots, reset by the tick's reset flags, its runs closed by the tick's final flags) and asr_kws_compact lists the hits the tick closed
+(at most kw_rows per slot and tick, the rest counted as dropped) - behind the prefix beam's packed results in its one copy, otherwise in
+one copy of their own.  keyword_hits(b) lists the session's hits so far; after final, and while nothing was dropped, they are bit for
+bit model.spot_keywords' over the session's streamed encoder rows.  A final that arrives without frames for any slot runs the two kernels alone.
+
 Out of scope: input rates other than 16 kHz for sessions (StreamResampler has no per-slot reset; the lock-step view resamples in front
 of its own front end), compaction of idle slots (every tick computes slots * C rows), carrying audio across an endpoint, a varying
 number of slots, capture into a hipGraph."""
@@ -72,6 +80,8 @@ BLANK = 0      # the CTC blank (= PAD_ID of the model)
 FREE, OPEN, ENDED = "free", "open", "ended"
 # rows of the per-push parameter block
 P_PE_OFF, P_CLEN, P_NV, P_RESET, P_SLIDE_FROM, P_SLIDE_COUNT, P_KLEN, P_OUT_ROW, PAR_ROWS = 0, 1, 2, 3, 4, 5, 6, 7, 8
+P_FINAL = PAR_ROWS      # one more row, in sessions with keywords only: the final flags of the tick
+KW_ROWS = 128           # keyword hits a slot can report per tick (the rest are counted as dropped)
 
 ENDPOINT_DEFAULTS = dict(
     blank_threshold=0.8,
@@ -114,7 +124,7 @@ def endpoint_rule(rules, frame_us, trailing, frames, decoded):
 
 class Sessions:
     def __init__(self, model, slots, parser=None, search="greedy", beam_size=5, frame_topk=10, endpoint=None, source_rate=None, context=None, lm=None,
-                 timed=False, confidence="post_max", beam_times=False, blank_skip=None, _lockstep=False):
+                 timed=False, confidence="post_max", beam_times=False, blank_skip=None, keywords=None, _lockstep=False):
         """_lockstep: set by stream.StreamingEncoder alone - the messages name model.stream(), and a model without the CTC head is
         admitted: its tick ends once the encoder rows are stored, push returns empty lists and the results come from the attention beam."""
         who = "model.stream()" if _lockstep else "model.sessions()"
@@ -175,6 +185,15 @@ class Sessions:
                 raise ValueError("an n-gram LM (lm=...) is supported by search='prefix_beam' (the CTC prefix beam search), not by search='greedy'")
             from . import decode
             decode._check_lm(model, lm, context)
+        # keyword spotting (keywords.KeywordList): one list for all slots, one device state, the hits of each session on the host
+        self.kw, self.kw_state, self.kw_rows = keywords, None, 0
+        if keywords is not None:
+            from .keywords import _check
+            _check(model, keywords)
+            if blank_skip is not None:
+                raise ValueError("keywords with blank_skip is not supported: the spotter reads every frame")
+            self.kw_rows = min(keywords.max_hits, KW_ROWS)
+        self.kw_hits, self.kw_dropped = [[] for _ in range(self.S)], [0] * self.S
         self.endpoint = endpoint_config(endpoint)
         thr = self.endpoint["blank_threshold"] if self.endpoint else ENDPOINT_DEFAULTS["blank_threshold"]
         self.silence_lp = math.log(thr)      # the kernel compares float32(log threshold) with float32 log p(blank)
@@ -222,6 +241,7 @@ class Sessions:
         self.state[b], self.frames[b], self.clen[b], self.fresh[b] = OPEN, 0, 0, True
         self.trailing[b], self.decoded[b], self.stable[b] = 0, False, 0
         self.has_times[b] = False
+        self.kw_hits[b], self.kw_dropped[b] = [], 0
         if self.log is not None:
             self.log.reset(b)
         if self.frontend is not None:
@@ -234,6 +254,7 @@ class Sessions:
             raise ValueError(f"drop: slot {b} is free")
         self.state[b], self.frames[b], self.clen[b], self.fresh[b] = FREE, 0, 0, False
         self.has_times[b] = False
+        self.kw_hits[b], self.kw_dropped[b] = [], 0
 
     def status(self, b):
         b = self._slot(b)
@@ -310,8 +331,11 @@ class Sessions:
             if nv[b] > 0 and self.frames[b] + C > table:
                 raise ValueError(f"push: slot {b} would reach frame {self.frames[b] + C}, past the positional-encoding table ({table} frames): close the session (endpointing tells when)")
         out = [[] for _ in range(S)]
+        closing = [fin[b] and self.state[b] == OPEN for b in range(S)]
         if any(nv):
-            self._tick(eng, feats, nv, out)
+            self._tick(eng, feats, nv, out, closing)
+        elif self.kw is not None and any(closing):
+            self._kws_close(feats.device, closing)
         for b in range(S):
             if fin[b] and self.state[b] == OPEN:
                 self.state[b] = ENDED
@@ -344,7 +368,7 @@ class Sessions:
         return beam_tokens(tok[b, r, :n], start[b, r, :n], end[b, r, :n], mx[b, r, :n], mn[b, r, :n], sm[b, r, :n], self.which, self.model.vocab._id2token,
                            self.model.frame_seconds(), int(fin[b]) if final else None, real=real)
 
-    def _tick(self, eng, feats, nv, out):
+    def _tick(self, eng, feats, nv, out, closing):
         S, C, dev = self.S, self.C, feats.device
         H, dk, hd = eng.H, eng.dk, eng.H * eng.dk
         keep = self.left * C
@@ -352,7 +376,9 @@ class Sessions:
         slide = self.left > 0 and any(nv[b] > 0 and self.clen[b] > keep for b in range(S))
         if self.left == 0:      # no key is kept: every chunk starts on an empty window, nothing to move
             self.clen = [0 if nv[b] > 0 else self.clen[b] for b in range(S)]
-        par = [[0] * S for _ in range(PAR_ROWS)]
+        par = [[0] * S for _ in range(PAR_ROWS + (self.kw is not None))]
+        if self.kw is not None:
+            par[P_FINAL] = [int(c) for c in closing]
         for b in range(S):
             c = self.clen[b]
             if slide:      # every slot moves to the other buffer: its last `keep` keys, or all it has
@@ -407,6 +433,7 @@ class Sessions:
         hypotheses and records onto the host in one copy; returns per slot the step words {n_ids, trailing, frames, decoded, ids ...}."""
         S, C, dev = self.S, self.C, h.device
         nv_dev = pd[P_NV]
+        n_kw = S * (2 + 4 * self.kw_rows)      # the words of the tick's keyword hits (0 without keywords)
         if self.ctc_state is None:
             self.ctc_state = torch.zeros(S, 4, dtype=torch.int32, device=dev)
         logits = eng.ctc_lo.fwd(h)
@@ -427,15 +454,20 @@ class Sessions:
             Lcap = max(1, max(f + n for f, n in zip(self.beam.frames, nv)))      # ctc_prefix_beam_chunk's own default
             n_real = S * self.beam_size * Lcap if self.skip is not None and self.beam_times else 0
             buf, Lcap = K.ctc_prefix_beam_chunk(self.beam, *cand, nv, C, self.beam_size, BLANK, max_len=Lcap, packed=True, nv_dev=n_dev,
-                                                extra_words=S * (4 + C) + 2 * n_real)
-            n_words = buf.numel() - S * (4 + C) - 2 * n_real      # the search's words (with a context: bias and state included)
+                                                extra_words=S * (4 + C) + 2 * n_real + n_kw)
+            n_words = buf.numel() - S * (4 + C) - 2 * n_real - n_kw      # the search's words (with a context: bias and state included)
             n_step = n_words + S * (4 + C)
             if n_real:
                 views = K.prefix_beam_unpack(buf[:n_words], S, self.beam_size, Lcap, "timed")
                 for i, v in enumerate(views[5:7]):      # start, end
                     K.frame_index_remap(v, self.skip.frame_map, out=buf[n_step + i * n_real:n_step + (i + 1) * n_real].view(v.shape))
             K.session_ctc_step(None, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK, out=buf[n_words:n_step].view(S, 4 + C))
+            if self.kw is not None:      # the hits ride behind everything else in the same copy
+                lse = K.ctc_frame_stats(logits.view(S, C, -1), nv_dev, BLANK)[3]
+                self._kws_launch(logits.view(S, C, -1), lse, nv_dev, pd[P_RESET], pd[P_FINAL], buf[buf.numel() - n_kw:])
             host = buf.cpu()
+            if self.kw is not None:
+                self._kws_ingest(host[host.numel() - n_kw:])
             tok, ln, sc, stable, *extra = (t.numpy() for t in K.prefix_beam_unpack(host[:n_words], S, self.beam_size, Lcap, self.beam.mode))
             self._hyps = (tok, ln, sc)
             if self.beam_times:
@@ -456,14 +488,19 @@ class Sessions:
         elif self.timed:
             if self.run_state is None:
                 self.run_state = torch.zeros(S, K.STEP_TOKENS_REC, dtype=torch.int32, device=dev)
-            path, best_lp, blank_lp, _, ent = K.ctc_frame_stats(logits.view(S, C, -1), nv_dev, BLANK)
+            path, best_lp, blank_lp, lse, ent = K.ctc_frame_stats(logits.view(S, C, -1), nv_dev, BLANK)
             buf = K.session_ctc_step_tokens(path, blank_lp, best_lp, ent, nv_dev, pd[P_RESET], self.ctc_state, self.run_state, C, self.silence_lp,
                                             BLANK).cpu()
             step = buf[:, :4 + C].tolist()
             self.log.ingest(buf, C, [b for b in range(S) if nv[b] > 0 or b in reset_slots])
         else:
-            path, blank_lp = K.ctc_frame_best_blank(logits.view(S, C, -1), nv_dev, BLANK)
+            if self.kw is not None:      # the same path and blank_lp bits, and the frames' log-sum-exp
+                path, _, blank_lp, lse, _ = K.ctc_frame_stats(logits.view(S, C, -1), nv_dev, BLANK)
+            else:
+                path, blank_lp = K.ctc_frame_best_blank(logits.view(S, C, -1), nv_dev, BLANK)
             step = K.session_ctc_step(path, blank_lp, nv_dev, pd[P_RESET], self.ctc_state, C, self.silence_lp, BLANK).cpu().tolist()
+        if self.kw is not None and self.search != "prefix_beam":      # no packed buffer to ride in: one copy of their own
+            self._kws_ingest(self._kws_launch(logits.view(S, C, -1), lse, nv_dev, pd[P_RESET], pd[P_FINAL]).cpu())
         if self.search != "prefix_beam":
             for b in range(S):
                 if nv[b] > 0:
@@ -471,6 +508,49 @@ class Sessions:
         # this tick's frame-wise log p(blank) (slots * C) f32 and best path (slots, C) int32 (None: beam sessions), on the device: diagnostics
         self.last_blank_lp, self.last_path = blank_lp, (None if self.search == "prefix_beam" else path)
         return step
+
+    # ------------------------------------------------------------------ keyword spotting
+    def _kws_launch(self, logits, lse, nv_dev, reset, final, out=None):
+        """asr_kws_chunk + asr_kws_compact of one tick; the hits the tick closed, in `out` (or a new buffer) on the device."""
+        kw, S = self.kw, self.S
+        if self.kw_state is None:
+            self.kw_state = K.kws_state(S, kw.K, logits.device)
+        if out is None:
+            out = torch.empty(S * (2 + 4 * self.kw_rows), dtype=torch.int32, device=logits.device)
+        tabs = kw.on(logits.device, self.model.frame_seconds())
+        cnt, rec = K.kws_chunk(logits, lse, nv_dev, reset, final, tabs, kw.K, self.kw_state, kw.hits_per_keyword, BLANK)
+        K.kws_compact(cnt, rec, self.kw_rows, out=out)
+        return out
+
+    def _kws_ingest(self, flat):
+        for b, r in enumerate(self.kw.decode(flat, self.S, self.kw_rows, self.model.frame_seconds(), self.model.vocab._id2token)):
+            if self.state[b] != FREE:
+                self.kw_hits[b] += r["hits"]
+                self.kw_dropped[b] += r["dropped"]
+
+    def _kws_close(self, dev, closing):
+        """final without a frame for any slot: no tick runs, the open runs of the closing slots are closed by the two kernels alone (a
+        slot opened and never fed is reset here as in its first tick - the tick's own reset still follows)."""
+        S = self.S
+        par = torch.tensor([[0] * S, [int(f) for f in self.fresh], [int(c) for c in closing]], dtype=torch.int32, device=dev)
+        eng = self.model._ensure_engine(dev)
+        logits = torch.zeros(S, 1, self.model.V, dtype=eng.dtype, device=dev)      # n_valid = 0 everywhere: never read
+        lse = torch.zeros(S, 1, dtype=torch.float32, device=dev)
+        self._kws_ingest(self._kws_launch(logits, lse, par[0], par[1], par[2]).cpu())
+
+    def keyword_hits(self, b):
+        """keywords=...: slot b's hits so far, sorted by (end_frame, keyword), each as model.spot_keywords reports it with frames and
+        times counted from the session's first frame; a run still open is reported once it closes (final closes it).  The list of a
+        finished slot stays until the slot is opened again."""
+        if self.kw is None:
+            raise ValueError("keyword_hits() needs model.sessions(..., keywords=KeywordList(...))")
+        return sorted(self.kw_hits[self._slot(b)], key=lambda h: (h["end_frame"], h["keyword"]))
+
+    def keywords_dropped(self, b):
+        """keywords=...: the hits of slot b's session that were found and not reported (past hits_per_keyword or kw_rows in a tick)."""
+        if self.kw is None:
+            raise ValueError("keywords_dropped() needs model.sessions(..., keywords=KeywordList(...))")
+        return self.kw_dropped[self._slot(b)]
 
     # ------------------------------------------------------------------ audio in
     def _ensure_frontend(self):

@@ -10,9 +10,9 @@ from .sessions import ENDED, Sessions
 
 class StreamingEncoder:
     def __init__(self, model, batch_size, parser=None, source_rate=None, search="greedy", beam_size=5, frame_topk=10, context=None, context_ids=None, lm=None,
-                 timed=False, confidence="post_max", beam_times=False, blank_skip=None):
+                 timed=False, confidence="post_max", beam_times=False, blank_skip=None, keywords=None):
         self.core = Sessions(model, batch_size, search=search, beam_size=beam_size, frame_topk=frame_topk, context=context, lm=lm, timed=timed,
-                             confidence=confidence, beam_times=beam_times, blank_skip=blank_skip, _lockstep=True)
+                             confidence=confidence, beam_times=beam_times, blank_skip=blank_skip, keywords=keywords, _lockstep=True)
         self.model, self.B, self.C = model, self.core.S, self.core.C
         if context is None and context_ids is not None:
             raise ValueError("context_ids needs a context")
@@ -102,6 +102,10 @@ class StreamingEncoder:
     def tokens(self):
         """Per utterance Sessions.tokens (timed=True or beam_times=True).  beam_times: empty after finish()."""
         return [self.core.tokens(b) for b in range(self.B)]
+
+    def keyword_hits(self):
+        """Per utterance Sessions.keyword_hits (keywords=...)."""
+        return [self.core.keyword_hits(b) for b in range(self.B)]
 
     def encoder_output(self):
         """(enc (B, T, d), lengths (B,) int32): T = the longest utterance rounded up to whole chunks; rows past an utterance's length are zero."""

@@ -1191,6 +1191,73 @@ int asr_ctc_blank_skip_compact(const float* vals, const int32_t* ids, const floa
                                int32_t* out_len, int32_t* out_frame, int B, int T, int k, int map_cap, void* stream);
 int asr_frame_index_remap(const int32_t* idx, const int32_t* map, int32_t* out, int B, int per, int map_cap, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Keyword spotting on the CTC posteriors (additive to ABI 10; csrc/kws.hip, asr_chinese_e2e_amd/keywords.py).
+ * Stands in for:  nothing in the reference; a max-path keyword filler-free search in the spirit of wekws' CTC spotter - parity unpinned (none
+ *                 of its code or output was on hand); the definition in float32 is tests/kws_ref.py, the kernels agree with it bit for bit.
+ *
+ * Emission of frame t: lp_t(v) = (float)logits[b, t, v] - lse[b, t], one f32 subtraction; lse from asr_ctc_frame_stats over the same rows.
+ * A keyword w_0 .. w_{L-1} (1 <= L <= ASR_KWS_MAX_LEN, ids in [0, V), none the blank) has states s = 0 .. 2L-2: even s = 2i emits
+ * lp_t(w_i), odd s emits lp_t(blank), the optional blank between w_i and w_{i+1}.  No leading and no trailing blank.
+ *   D_{-1}(s) = -inf, start_{-1}(s) = -1.  Frame t:
+ *     s = 0:   best = 0.0f, bs = t                  (a match may begin on any frame: every continued path has D <= 0)
+ *     s >= 1:  best = D_{t-1}(s), bs = start_{t-1}(s); those of s-1 iff D_{t-1}(s-1) > best; then, for even s >= 2 with
+ *              w_{s/2} != w_{s/2-1}, those of s-2 iff D_{t-1}(s-2) > best      (both strict; compare-and-select, never fmaxf)
+ *     D_t(s) = best + e_t(s) (one f32 addition), start_t(s) = best > -inf ? bs : -1
+ *   H_t = D_t(2L-2), hs_t = start_t(2L-2): the largest log-probability of a CTC alignment of the keyword that ends on frame t, over every
+ *   start, and that alignment's first frame.  State 0 is entered afresh on every frame (a longer stay in w_0 never scores more), so a
+ *   hit's start is the LAST frame of the audio's run of w_0, not its first: the hit brackets the keyword from the inside.
+ * Frame t is a candidate of keyword k iff H_t >= thr[k] (a NaN is none) and hs_t >= 0 and t - hs_t + 1 <= span[k].  Each maximal run of
+ * candidate frames of one (utterance, keyword) is one hit {start = hs of the run's best frame, end = that frame, score = its H}, the
+ * best frame being the one of largest H, the first on ties.  A run closes on the first frame that is no candidate; offline also behind
+ * the utterance's last frame, streamed when the slot is pushed with `final`.  The logits must hold no NaN and no +inf (-inf is fine).
+ *
+ * asr_kws_list: the tables of K keywords.  Row j: tok[j, 0 .. len[j]) of tok (K, ASR_KWS_MAX_LEN), thr[j] f32, span[j], and index[j] =
+ *   the keyword's own number, the row of every output it writes (a permutation of [0, K): the rows may be sorted by length so that the
+ *   64 keywords of a wave share a length bucket, L <= 4 / 8 / 16, at no change to any output).  host_tok / host_len / host_index are host
+ *   copies of tok / len / index, which every launcher checks before any launch (K, the lengths, the ids against V and blank, the
+ *   permutation); the kernels clamp what they read from the device tables all the same.
+ * asr_kws_search: logits (B, T, V) f32 / bf16 (row stride ld), lse (B, T), in_len (B) or NULL (= T; clamped to [0, T]).  cnt (B, K):
+ *   the hits of keyword k in utterance b (it keeps counting past cap); rec (B, K, cap, 3) int32 {start, end, score as f32 bits}: the
+ *   first cap of them in order of their end, zeros behind.  One wave per (utterance, 64 table rows), one launch.
+ * asr_kws_chunk: the resumable form, one call per chunk: logits (slots, C, V), lse (slots, C), n_valid / reset / final (slots) int32 in
+ *   the sense of asr_session_ctc_step.  state: asr_kws_state_bytes(slots, K) bytes, initialised by asr_kws_state_init; per (slot, keyword)
+ *   the column D, start (in frames of the session) and the open run {open, start, end, H}, per slot the frames consumed.  reset[b] != 0:
+ *   the slot starts from the initial state; n_valid[b] == 0 without reset or final leaves every word of the slot's state as it is.
+ *   final[b] != 0 closes the open runs behind the chunk's frames.  cnt / rec as above, for the runs closed in this call.  After any
+ *   cutting of the frames into chunks the hits of all calls are those of asr_kws_search over all of them, bit for bit.
+ * asr_kws_compact: cnt / rec as written above -> hits (B, max_hits, 4) int32 {keyword, start, end, score bits} in one fixed order, keyword
+ *   ascending, then end ascending, zeros behind; count[b] = the rows written, dropped[b] = the hits found and not written (past cap,
+ *   or past max_hits).  Offsets by ballot and popcount; no atomics: two runs write the same bytes.
+ * asr_kws_state_reset: flags (slots) int32 on the device, flags[b] != 0 puts slot b back to the initial state.
+ * Limits: K <= ASR_KWS_MAX_KEYWORDS, cap <= ASR_KWS_MAX_CAP, B / slots <= 65535; 4-byte aligned pointers.
+ */
+#define ASR_KWS_MAX_LEN 16
+#define ASR_KWS_MAX_KEYWORDS 65536
+#define ASR_KWS_MAX_CAP 64
+typedef struct asr_kws_list {
+    const int32_t* tok;        /* device, (K, ASR_KWS_MAX_LEN) */
+    const int32_t* len;        /* device, (K) */
+    const float* thr;          /* device, (K) */
+    const int32_t* span;       /* device, (K) */
+    const int32_t* index;      /* device, (K) */
+    const int32_t* host_tok;   /* host copies, read by the launchers' checks */
+    const int32_t* host_len;
+    const int32_t* host_index;
+    int K;
+} asr_kws_list;
+size_t asr_kws_state_bytes(int slots, int K);
+size_t asr_kws_records_bytes(int B, int K, int cap);
+int asr_kws_search(const void* logits, const float* lse, const int32_t* in_len, const asr_kws_list* kw, int32_t* cnt, int32_t* rec, int B,
+                   int T, int V, int ld, int blank, int cap, int dtype, void* stream);
+int asr_kws_chunk(const void* logits, const float* lse, const int32_t* n_valid, const int32_t* reset, const int32_t* final,
+                  const asr_kws_list* kw, int32_t* state, int32_t* cnt, int32_t* rec, int slots, int C, int V, int ld, int blank, int cap,
+                  int dtype, void* stream);
+int asr_kws_compact(const int32_t* cnt, const int32_t* rec, int32_t* count, int32_t* dropped, int32_t* hits, int B, int K, int cap,
+                    int max_hits, void* stream);
+int asr_kws_state_init(int32_t* state, int slots, int K, void* stream);
+int asr_kws_state_reset(int32_t* state, const int32_t* flags, int slots, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
