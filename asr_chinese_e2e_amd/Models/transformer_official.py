@@ -714,6 +714,16 @@ class _SpeechTransformer(BaseModel):
         return spot_long(self, parser, wav, wav_len, keywords, vad=vad, batch_size=batch_size, source_rate=source_rate, min_silence_s=min_silence_s,
                          min_speech_s=min_speech_s, pad_s=pad_s, max_segment_s=max_segment_s)
 
+    def evaluate(self, batches, search="transcribe", nbest=1, scorer=None, **search_kwargs):
+        """Token-level scoring of a test set (scoring.evaluate): every pack of `batches` (what the loader yields) goes through `search` -
+        "transcribe" (1-best; transcribe(pack, timestamps=False, **search_kwargs), so joint=, context=, lm=, blank_skip= pass through),
+        "ctc_prefix_beam" (ctc_prefix_beam_search(pack, beam_size, nbest, ...)) or "attention_beam" (beam_search(pack, beam_size, nbest,
+        ...)) - and its hypotheses are aligned on the device (asr_edit_align) against the gold ids cal_metrics scores against.  Returns the
+        scoring.Scorer (a new one, or `scorer` with the batches added): summary() has the corpus CER with its substitutions, deletions and
+        insertions, the sentence error rate and, with nbest > 1, the oracle CER of the lists."""
+        from ..scoring import evaluate
+        return evaluate(self, batches, search=search, nbest=nbest, scorer=scorer, **search_kwargs)
+
     def _hyp_dicts(self, ids, scores, timestamps, ctc_logits, wave_len, biases=None, bias_key="bias", confidence=None):
         """transcribe's result dicts for the best ids / score of each utterance; ctc_logits() -> (B, T, V) is called for timestamps only.
         biases (hotword-biased searches, or searches with an n-gram LM): the "bias" (bias_key="lm_score": the "lm_score") of each result."""

@@ -31,6 +31,8 @@ VAD_CTX_MAX = 1024     # ASR_VAD_CTX_MAX: the largest frames_context asr_vad_dec
 ALIGN_LONG_MAX_LABELS = 8192      # ASR_ALIGN_LONG_MAX_LABELS: labels per recording of asr_ctc_align_long
 SPECAUG_MAX_RANGES = 8     # ASR_SPECAUG_MAX_RANGES: ranges of one kind in a row of asr_*_norm_specaug_lfr_fwd
 KWS_MAX_LEN, KWS_MAX_KEYWORDS, KWS_MAX_CAP = 16, 65536, 64      # ASR_KWS_*: tokens per keyword, keywords per list, records per (utterance, keyword)
+EDIT_LDS_DIR_BYTES, EDIT_MAX_REF = 98304, 16384      # ASR_EDIT_*: direction masks a pair keeps in LDS, tokens per reference of asr_edit_align
+EDIT_COR, EDIT_SUB, EDIT_DEL, EDIT_INS = 0, 1, 2, 3      # ASR_EDIT_COR .. ASR_EDIT_INS: the op codes of asr_edit_align
 STREAM_OPEN = 0x3fffffff     # ASR_STREAM_OPEN: "length not known yet" in the streaming front end's parameter arrays
 
 P, I, F, Z, U = c_void_p, c_int, c_float, c_size_t, c_uint32
@@ -205,6 +207,8 @@ SIGNATURES = {
     "asr_kws_compact": (I, [P, P, P, P, P, I, I, I, I, P]),
     "asr_kws_state_init": (I, [P, I, I, P]),
     "asr_kws_state_reset": (I, [P, P, I, I, P]),
+    "asr_edit_align_workspace_bytes": (Z, [P, P, P, I, I, I, I]),
+    "asr_edit_align": (I, [P, P, I, I, P, P, I, I, P, P, P, P, I, I, P, P, P, I, P, Z, P]),
 }
 
 

@@ -1749,3 +1749,68 @@ def kws_unpack(flat, B, max_hits):
     """The views (count (B), dropped (B), hits (B, max_hits, 4)) of kws_compact's buffer, on the device or on the host."""
     assert flat.numel() == B * (2 + 4 * int(max_hits))
     return flat[:B], flat[B:2 * B], flat[2 * B:].view(B, int(max_hits), 4)
+
+
+# ------------------------------------------------------------------------------------------------ token-level scoring (csrc/score.hip)
+EDIT_LDS_DIR_BYTES, EDIT_MAX_REF = _lib.EDIT_LDS_DIR_BYTES, _lib.EDIT_MAX_REF
+EDIT_COR, EDIT_SUB, EDIT_DEL, EDIT_INS = _lib.EDIT_COR, _lib.EDIT_SUB, _lib.EDIT_DEL, _lib.EDIT_INS
+
+
+def _edit_mirrors(hyp_len, ref_len, ref_of):
+    """The three small arrays as contiguous int32 numpy arrays (the launcher's host mirrors)."""
+    return tuple(np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1)) for a in (hyp_len, ref_len, ref_of))
+
+
+def edit_align_workspace_bytes(hyp_len, ref_len, ref_of, Lh, Lr):
+    """Bytes of direction-mask workspace edit_align(ops=True) needs for these pairs (host integers): 0 when every pair's masks fit LDS
+    (m * ceil(n / 64) * 16 <= EDIT_LDS_DIR_BYTES each)."""
+    hl, rl, ro = _edit_mirrors(hyp_len, ref_len, ref_of)
+    return int(lib.asr_edit_align_workspace_bytes(hl.ctypes.data, rl.ctypes.data, ro.ctypes.data, hl.shape[0], rl.shape[0], int(Lh), int(Lr)))
+
+
+def edit_align(hyp, hyp_len, ref, ref_len, ref_of, host_hyp_len, host_ref_len, host_ref_of, ops=True, ws=None, counts=None, ops_out=None, n_ops=None):
+    """Levenshtein alignment of P (hypothesis, reference) pairs in one launch (asr_edit_align; the definition is tests/score_ref.py, and
+    the kernel agrees with it integer for integer).  hyp (P, Lh), ref (R, Lr) int32 id rows with unit column stride, hyp_len (P), ref_len
+    (R), ref_of (P) int32 on the device: pair p is hyp row p against ref row ref_of[p].  host_*: the same three small arrays on the host
+    (lists or numpy), by which the launcher checks ref_of and sizes LDS and workspace.  Returns (counts (P, 5) int32 {distance, cor, sub,
+    del, ins}, ops (P, 3, ldo) int32 planes {code, ref_pos, hyp_pos} in forward order, n_ops (P)); ops=False: (counts, None, None), and
+    neither direction masks nor a workspace.  counts / ops_out / n_ops: buffers to write into (views of one buffer make one copy back);
+    ws: a Workspace, else the masks of pairs past the LDS budget get a fresh allocation."""
+    _chk_i32(hyp_len, ref_len, ref_of, counts, ops_out, n_ops)
+    for t in (hyp, ref):
+        if t.dtype != torch.int32 or t.dim() != 2 or (t.shape[1] > 0 and t.stride(1) != 1):
+            raise ValueError("edit_align: hyp and ref must be 2-D int32 tensors with unit column stride")
+    P_, Lh = hyp.shape
+    R, Lr = ref.shape
+    ldh, ldr = (hyp.stride(0) if P_ > 1 and Lh > 0 else Lh), (ref.stride(0) if R > 1 and Lr > 0 else Lr)
+    if hyp_len.numel() != P_ or ref_of.numel() != P_ or ref_len.numel() != R:
+        raise ValueError(f"edit_align: {hyp_len.numel()} hypothesis lengths and {ref_of.numel()} ref_of for {P_} pairs, {ref_len.numel()} reference lengths for {R}")
+    hl, rl, ro = _edit_mirrors(host_hyp_len, host_ref_len, host_ref_of)
+    if hl.shape[0] != P_ or ro.shape[0] != P_ or rl.shape[0] != R:
+        raise ValueError("edit_align: the host mirrors must have the device arrays' sizes")
+    dev = hyp.device
+    if counts is None:
+        counts = torch.empty(P_, 5, dtype=torch.int32, device=dev)
+    ldo, w, nbytes = 0, None, 0
+    if ops:
+        ldo = max(Lh + Lr, 1)
+        if ops_out is None:
+            ops_out = torch.empty(P_, 3, ldo, dtype=torch.int32, device=dev)
+        if n_ops is None:
+            n_ops = torch.empty(P_, dtype=torch.int32, device=dev)
+        if ops_out.numel() != P_ * 3 * ldo or n_ops.numel() != P_:
+            raise ValueError(f"edit_align: ops_out must hold {P_} x 3 x {ldo} words and n_ops {P_}")
+        nbytes = int(lib.asr_edit_align_workspace_bytes(hl.ctypes.data, rl.ctypes.data, ro.ctypes.data, P_, R, Lh, Lr))
+        if nbytes:
+            w = ws.get(nbytes) if ws is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            nbytes = w.numel()
+    else:
+        ops_out = n_ops = None
+    if counts.numel() != P_ * 5:
+        raise ValueError(f"edit_align: counts must hold {P_} x 5 words")
+    # an empty tensor has no storage to point at: the kernel reads no id of a zero-length row
+    one = torch.zeros(1, dtype=torch.int32, device=dev) if (hyp.numel() == 0 or ref.numel() == 0) else None
+    check(lib.asr_edit_align(_p(hyp) if hyp.numel() else _p(one), _p(hyp_len), Lh, ldh, _p(ref) if ref.numel() else _p(one), _p(ref_len), Lr, ldr, _p(ref_of),
+                             hl.ctypes.data, rl.ctypes.data, ro.ctypes.data, P_, R, _p(counts), _p(ops_out), _p(n_ops), ldo, _p(w), nbytes, _stream()),
+          "asr_edit_align")
+    return counts, ops_out, n_ops

@@ -1258,6 +1258,48 @@ int asr_kws_compact(const int32_t* cnt, const int32_t* rec, int32_t* count, int3
 int asr_kws_state_init(int32_t* state, int slots, int K, void* stream);
 int asr_kws_state_reset(int32_t* state, const int32_t* flags, int slots, int K, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Token-level scoring: Levenshtein alignment of hypotheses against references with its split into correct tokens, substitutions,
+ * deletions and insertions (additive to ABI 10; csrc/score.hip, asr_chinese_e2e_amd/scoring.py).
+ * Stands in for:  nothing in the reference, whose only scorer is the string convention of asr_cer (untouched).  The definition, in
+ *                 integers, is tests/score_ref.py; the kernel agrees with it integer for integer, ties included.
+ *
+ * For a reference r[0..m) and a hypothesis h[0..n):  D[i][0] = i, D[0][j] = j, D[i][j] = min(D[i-1][j-1] + (r[i-1] != h[j-1]),
+ * D[i-1][j] + 1, D[i][j-1] + 1).  The direction of a cell is the FIRST that applies of DIAG (D[i-1][j-1] + (r[i-1] != h[j-1]) ==
+ * D[i][j]), UP (D[i-1][j] + 1 == D[i][j]: r[i-1] is deleted), LEFT (h[j-1] is inserted); row 0 is LEFT, column 0 is UP.  The alignment
+ * is the walk from (m, n) to (0, 0) along the directions, reported from (0, 0) on.  Ids are compared, never used as indices.
+ *
+ * asr_edit_align: P pairs, one wave each, one launch.  hyp (P, Lh) int32 rows ldh apart, hyp_len (P); ref (R, Lr) rows ldr apart, ref_len
+ *   (R); ref_of (P): pair p scores hyp row p against ref row ref_of[p], so an n-best list shares its reference.  All of these on the
+ *   device; host_hyp_len / host_ref_len / host_ref_of are host copies of the three small arrays, by which the launcher checks ref_of
+ *   against [0, R) and sizes LDS and workspace without reading the device.  The kernel clamps lengths to [0, Lh] / [0, Lr] and ref_of to
+ *   [0, R) all the same (the host sizes by the same clamped lengths).
+ *   counts (P, 5) int32 = {distance, cor, sub, del, ins}.
+ *   ops == NULL: counts only; no direction is stored, no workspace is needed and n_ops is not written.
+ *   ops (P, 3, ldo) int32, ldo >= max(Lh + Lr, 1), n_ops (P): plane 0 holds the n_ops[p] codes ASR_EDIT_COR / SUB / DEL / INS in forward
+ *   order, plane 1 the op's reference position (-1 for an insertion), plane 2 its hypothesis position (-1 for a deletion).  Words at and
+ *   past n_ops[p] are scratch of the kernel.
+ *   The two direction bits of a cell are kept for the walk, 16 bytes per (reference token, 64 hypothesis tokens): in LDS for a pair with
+ *   m * ceil(n / 64) * 16 <= ASR_EDIT_LDS_DIR_BYTES, else in ws, of at least asr_edit_align_workspace_bytes(...) bytes (0 when every pair
+ *   fits LDS; ws may then be NULL), 16-byte aligned.  Should the device lengths ask for more than the host copies provided, the pair gets
+ *   its distance, -1 for the four counts and n_ops = -1; nothing is written out of bounds.
+ *   The launch's dynamic LDS is sized by its largest pair (at most 150 KB, as asr_cer).  Limits: ASR_EDIT_MAX_REF tokens per reference
+ *   (hypotheses have none); 4-byte aligned pointers.  No atomics: two runs write the same bytes.
+ *   Refused before any launch (ASR_EINVAL; ASR_EWORKSPACE for the last): null or misaligned pointers, P <= 0, R <= 0, negative Lh / Lr,
+ *   ldh < Lh, ldr < Lr, ldo too small, ref_of[p] outside [0, R), a reference above the limit, a workspace below the size query's answer.
+ */
+#define ASR_EDIT_LDS_DIR_BYTES 98304
+#define ASR_EDIT_MAX_REF 16384
+#define ASR_EDIT_COR 0
+#define ASR_EDIT_SUB 1
+#define ASR_EDIT_DEL 2
+#define ASR_EDIT_INS 3
+size_t asr_edit_align_workspace_bytes(const int32_t* host_hyp_len, const int32_t* host_ref_len, const int32_t* host_ref_of, int P, int R,
+                                      int Lh, int Lr);
+int asr_edit_align(const int32_t* hyp, const int32_t* hyp_len, int Lh, int ldh, const int32_t* ref, const int32_t* ref_len, int Lr,
+                   int ldr, const int32_t* ref_of, const int32_t* host_hyp_len, const int32_t* host_ref_len, const int32_t* host_ref_of,
+                   int P, int R, int32_t* counts, int32_t* ops, int32_t* n_ops, int ldo, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
