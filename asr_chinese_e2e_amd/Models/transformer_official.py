@@ -714,15 +714,27 @@ class _SpeechTransformer(BaseModel):
         return spot_long(self, parser, wav, wav_len, keywords, vad=vad, batch_size=batch_size, source_rate=source_rate, min_silence_s=min_silence_s,
                          min_speech_s=min_speech_s, pad_s=pad_s, max_segment_s=max_segment_s)
 
-    def evaluate(self, batches, search="transcribe", nbest=1, scorer=None, **search_kwargs):
+    def consensus(self, input, search="ctc_prefix_beam", beam_size=5, nbest=5, posterior_scale=1.0, alts=4, **search_kwargs):
+        """Consensus decoding of a batch's n-best lists (consensus.model_consensus): the lists of ctc_prefix_beam_search ("ctc_prefix_beam";
+        context=, lm=, blank_skip= pass through) or beam_search ("attention_beam"; sos / eos stripped) are weighted by
+        consensus.nbest_weights(their scores, posterior_scale) and voted on the device (asr_nbest_consensus).  Returns per utterance
+        {"text", "ids" (the consensus string), "mbr_ids" (the minimum-Bayes-risk entry), "mbr_rank", "best_ids" (rank 0), "confidence" (per
+        token of mbr_ids: the posterior mass of the entries that agree with it), "slots" (the confusion network: consensus.consensus_ids),
+        "nbest" (what the search returned)}.  ValueError before any launch for nbest above 64 or a posterior_scale that is not finite
+        and > 0; a hypothesis above 256 tokens raises before the votes."""
+        from ..consensus import model_consensus
+        return model_consensus(self, input, search=search, beam_size=beam_size, nbest=nbest, posterior_scale=posterior_scale, alts=alts, **search_kwargs)
+
+    def evaluate(self, batches, search="transcribe", nbest=1, scorer=None, consensus=False, posterior_scale=1.0, **search_kwargs):
         """Token-level scoring of a test set (scoring.evaluate): every pack of `batches` (what the loader yields) goes through `search` -
         "transcribe" (1-best; transcribe(pack, timestamps=False, **search_kwargs), so joint=, context=, lm=, blank_skip= pass through),
         "ctc_prefix_beam" (ctc_prefix_beam_search(pack, beam_size, nbest, ...)) or "attention_beam" (beam_search(pack, beam_size, nbest,
         ...)) - and its hypotheses are aligned on the device (asr_edit_align) against the gold ids cal_metrics scores against.  Returns the
         scoring.Scorer (a new one, or `scorer` with the batches added): summary() has the corpus CER with its substitutions, deletions and
-        insertions, the sentence error rate and, with nbest > 1, the oracle CER of the lists."""
+        insertions, the sentence error rate and, with nbest > 1, the oracle CER of the lists.  consensus=True (the two n-best searches):
+        also mbr_cer, consensus_cer and mbr_rank_hist, from consensus.consensus_ids over the lists with their scores and posterior_scale."""
         from ..scoring import evaluate
-        return evaluate(self, batches, search=search, nbest=nbest, scorer=scorer, **search_kwargs)
+        return evaluate(self, batches, search=search, nbest=nbest, scorer=scorer, consensus=consensus, posterior_scale=posterior_scale, **search_kwargs)
 
     def _hyp_dicts(self, ids, scores, timestamps, ctc_logits, wave_len, biases=None, bias_key="bias", confidence=None):
         """transcribe's result dicts for the best ids / score of each utterance; ctc_logits() -> (B, T, V) is called for timestamps only.

@@ -33,6 +33,7 @@ SPECAUG_MAX_RANGES = 8     # ASR_SPECAUG_MAX_RANGES: ranges of one kind in a row
 KWS_MAX_LEN, KWS_MAX_KEYWORDS, KWS_MAX_CAP = 16, 65536, 64      # ASR_KWS_*: tokens per keyword, keywords per list, records per (utterance, keyword)
 EDIT_LDS_DIR_BYTES, EDIT_MAX_REF = 98304, 16384      # ASR_EDIT_*: direction masks a pair keeps in LDS, tokens per reference of asr_edit_align
 EDIT_COR, EDIT_SUB, EDIT_DEL, EDIT_INS = 0, 1, 2, 3      # ASR_EDIT_COR .. ASR_EDIT_INS: the op codes of asr_edit_align
+NBEST_MAX_N, NBEST_MAX_LEN, NBEST_MAX_ALTS, NBEST_EPS = 64, 256, 8, -1      # ASR_NBEST_*: entries per list, tokens per entry, alternatives per slot, "no token"
 STREAM_OPEN = 0x3fffffff     # ASR_STREAM_OPEN: "length not known yet" in the streaming front end's parameter arrays
 
 P, I, F, Z, U = c_void_p, c_int, c_float, c_size_t, c_uint32
@@ -209,6 +210,11 @@ SIGNATURES = {
     "asr_kws_state_reset": (I, [P, P, I, I, P]),
     "asr_edit_align_workspace_bytes": (Z, [P, P, P, I, I, I, I]),
     "asr_edit_align": (I, [P, P, I, I, P, P, I, I, P, P, P, P, I, I, P, P, P, I, P, Z, P]),
+    "asr_nbest_out_bytes": (Z, [I, I, I, I]),
+    "asr_nbest_pair_dist": (I, [P, P, P, I, I, I, P, P, I, I, I, P, Z, P]),
+    "asr_nbest_pivot_votes": (I, [P, P, P, I, I, I, P, P, I, I, I, P, Z, P]),
+    "asr_nbest_slot_vote": (I, [P, P, P, I, I, I, P, P, I, I, I, P, Z, P]),
+    "asr_nbest_consensus": (I, [P, P, P, I, I, I, P, P, I, I, I, P, Z, P]),
 }
 
 

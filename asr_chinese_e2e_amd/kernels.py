@@ -1814,3 +1814,66 @@ def edit_align(hyp, hyp_len, ref, ref_len, ref_of, host_hyp_len, host_ref_len, h
                              hl.ctypes.data, rl.ctypes.data, ro.ctypes.data, P_, R, _p(counts), _p(ops_out), _p(n_ops), ldo, _p(w), nbytes, _stream()),
           "asr_edit_align")
     return counts, ops_out, n_ops
+
+
+# ------------------------------------------------------------------------------------------------ consensus of n-best lists (csrc/consensus.hip)
+NBEST_MAX_N, NBEST_MAX_LEN, NBEST_MAX_ALTS, NBEST_EPS = _lib.NBEST_MAX_N, _lib.NBEST_MAX_LEN, _lib.NBEST_MAX_ALTS, _lib.NBEST_EPS
+NBEST_STAGES = {"pair_dist": "asr_nbest_pair_dist", "pivot_votes": "asr_nbest_pivot_votes", "slot_vote": "asr_nbest_slot_vote", None: "asr_nbest_consensus"}
+
+
+def nbest_out_words(U, N, L, alts):
+    """int32 words of nbest_consensus' output buffer (asr_nbest_out_bytes / 4); raises for a shape the launcher would refuse."""
+    nbytes = int(lib.asr_nbest_out_bytes(int(U), int(N), int(L), int(alts)))
+    if not nbytes:
+        raise ValueError(f"nbest_consensus: {_lib.last_error()}")
+    return nbytes // 4
+
+
+def nbest_unpack(flat, U, N, L, alts):
+    """The views of nbest_consensus' buffer (an int32 tensor on the device or on the host, or a numpy array), in the order of
+    include/asr_hip.h: {"risk" (U, N) int64, "d" (U, N, N), "pivot" (U), "W" (U), "extra" (U, N), "n_alts" (U, S), "pivot_w" (U, S),
+    "votes" (U, N, S), "alts" (U, S, A, 2)} with S = 2 L + 1."""
+    S = 2 * L + 1
+    shapes = [("risk", (U, N, 2)), ("d", (U, N, N)), ("pivot", (U,)), ("W", (U,)), ("extra", (U, N)), ("n_alts", (U, S)), ("pivot_w", (U, S)),
+              ("votes", (U, N, S)), ("alts", (U, S, alts, 2))]
+    out, at = {}, 0
+    for name, shp in shapes:
+        n = int(np.prod(shp))
+        out[name] = flat[at:at + n].reshape(shp)
+        at += n
+    if at != flat.shape[0]:
+        raise ValueError(f"nbest_unpack: a buffer of {flat.shape[0]} words, the shape asks for {at}")
+    out["risk"] = out["risk"].reshape(-1).view(torch.int64 if isinstance(flat, torch.Tensor) else np.int64).reshape(U, N)
+    return out
+
+
+def nbest_consensus(tok, ln, weights, host_len, host_weights, alts=4, out=None, stage=None):
+    """Consensus decoding of U n-best lists in three launches (asr_nbest_consensus; the definition is tests/consensus_ref.py, and the
+    kernels agree with it integer for integer).  tok (U, N, L) int32 ids with unit stride along L; ln (U, N) int32, -1 = absent; weights
+    (U, N) int32 >= 0, at most 2**30 per utterance; host_len / host_weights: the two small arrays on the host (lists or numpy), by which
+    the launcher refuses before any launch.  Returns the output buffer, an int32 tensor of nbest_out_words(U, N, L, alts) words
+    (nbest_unpack gives its views); out: a buffer to write into.  stage: "pair_dist", "pivot_votes" or "slot_vote" launches that stage
+    alone (the later ones read what the earlier ones wrote into `out`)."""
+    _chk_i32(ln, weights, out)
+    if tok.dtype != torch.int32 or tok.dim() != 3 or (tok.shape[2] > 0 and tok.stride(2) != 1):
+        raise ValueError("nbest_consensus: tok must be a 3-D int32 tensor with unit stride along its last dimension")
+    if stage not in NBEST_STAGES:
+        raise ValueError(f"nbest_consensus: stage must be one of {[s for s in NBEST_STAGES if s]} or None (got {stage!r})")
+    U, N, L = tok.shape
+    if ln.shape != (U, N) or weights.shape != (U, N):
+        raise ValueError(f"nbest_consensus: len {tuple(ln.shape)} and weights {tuple(weights.shape)} for {U} x {N} entries")
+    hl = np.ascontiguousarray(np.asarray(host_len, dtype=np.int32).reshape(-1))
+    hw = np.ascontiguousarray(np.asarray(host_weights, dtype=np.int32).reshape(-1))
+    if hl.shape[0] != U * N or hw.shape[0] != U * N:
+        raise ValueError("nbest_consensus: the host mirrors must have the device arrays' sizes")
+    words = nbest_out_words(U, N, L, alts)
+    if out is None:
+        out = torch.empty(words, dtype=torch.int32, device=tok.device)
+    if out.numel() != words:
+        raise ValueError(f"nbest_consensus: out must hold {words} words")
+    ldn = tok.stride(1) if N > 1 and L > 0 else L
+    ldu = tok.stride(0) if U > 1 and L > 0 else max((N - 1) * ldn + L, 0)
+    one = torch.zeros(1, dtype=torch.int32, device=tok.device) if tok.numel() == 0 else None      # an empty tensor has no storage to point at
+    check(getattr(lib, NBEST_STAGES[stage])(_p(tok) if one is None else _p(one), _p(ln), _p(weights), L, ldn, ldu, hl.ctypes.data, hw.ctypes.data, U, N,
+                                            int(alts), _p(out), words * 4, _stream()), NBEST_STAGES[stage])
+    return out

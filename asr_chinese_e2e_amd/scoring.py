@@ -88,6 +88,7 @@ class Scorer:
         self.utts = []           # {"key", "ref", "hyp", "distance", "cor", "sub", "del", "ins", "ops"}
         self.oracle = []         # per n-best utterance (best distance, its rank, ranks)
         self.ref_conv = []       # the string-convention CER of each utterance's 1-best
+        self.consensus = []      # per utterance scored with n-best scores (MBR distance, consensus distance, the MBR entry's rank, ranks)
 
     def _clean(self, ids):
         return [int(i) for i in ids if int(i) not in self.drop]
@@ -98,11 +99,18 @@ class Scorer:
     def _string(self, ids):
         return " ".join(self.token(i) for i in ids)
 
-    def add(self, keys, hyps, refs, device="cuda"):
+    def add(self, keys, hyps, refs, device="cuda", scores=None, posterior_scale=1.0):
         """One hypothesis (an id list) or an n-best list (a list of id lists, best first) per utterance; refs: one id list each.  An n-best
-        list is aligned with ops for rank 0 and counts only for the other ranks: two launches."""
+        list is aligned with ops for rank 0 and counts only for the other ranks: two launches.
+        scores (one list of log-scores per utterance, entry for entry with its n-best list): the lists also go through
+        consensus.consensus_ids with nbest_weights(scores, posterior_scale), and the minimum-Bayes-risk entry and the consensus string of
+        each are aligned against the reference, counts only (one more launch of the same kernel): summary() then has mbr_cer,
+        consensus_cer and mbr_rank_hist."""
         if not (len(keys) == len(hyps) == len(refs)):
             raise ValueError(f"Scorer.add: {len(keys)} keys, {len(hyps)} hypotheses, {len(refs)} references")
+        if scores is not None:
+            self._add_with_consensus(keys, hyps, refs, device, scores, posterior_scale)
+            return
         nbest = any(_is_nbest(h) for h in hyps)
         lists = [[self._clean(x) for x in h] if _is_nbest(h) else [self._clean(h)] for h in hyps]
         gold = [self._clean(r) for r in refs]
@@ -114,12 +122,41 @@ class Scorer:
             results[u].append(r)
         self.add_aligned(keys, results if nbest else first, hyps, refs)
 
-    def add_aligned(self, keys, results, hyps, refs):
+    def _add_with_consensus(self, keys, hyps, refs, device, scores, posterior_scale):
+        from .consensus import consensus_ids
+        if not keys:
+            return
+        if len(scores) != len(hyps) or not all(_is_nbest(h) and len(s) == len(h) for h, s in zip(hyps, scores)):
+            raise ValueError("Scorer.add: scores need an n-best list for every utterance, and one score per entry")
+        lists = [[self._clean(x) for x in h] for h in hyps]
+        gold = [self._clean(r) for r in refs]
+        first = align_ids([l[0] for l in lists], gold, ops=True, device=device)
+        cons = consensus_ids(lists, scores=scores, scale=posterior_scale, alts=1, device=device)
+        rest = [(u, x) for u, l in enumerate(lists) for x in l[1:]]
+        U = len(lists)
+        tail = [c["mbr"] for c in cons] + [c["consensus"] for c in cons]
+        more = align_ids([x for _, x in rest] + tail, gold, ref_of=[u for u, _ in rest] + 2 * list(range(U)), ops=False, device=device)
+        results = [[r] for r in first]
+        for (u, _), r in zip(rest, more):
+            results[u].append(r)
+        extra = [{"mbr_rank": c["pivot"], "mbr": more[len(rest) + u], "consensus": more[len(rest) + U + u]} for u, c in enumerate(cons)]
+        self.add_aligned(keys, results, hyps, refs, consensus=extra)
+
+    def add_aligned(self, keys, results, hyps, refs, consensus=None):
         """The host half of add: results[u] is the alignment dict of utterance u's hypothesis (score_ref.align's or align_ids'), or for an
         n-best list one dict per rank, of which rank 0 carries "ops".  hyps / refs as add takes them; positions in the ops index the ids
-        that are left after ignore_ids, PAD, sos and eos are removed."""
+        that are left after ignore_ids, PAD, sos and eos are removed.
+        consensus[u] (n-best lists only): {"mbr_rank", "mbr": the alignment dict of the minimum-Bayes-risk entry against the reference,
+        "consensus": that of the consensus string}; only their distances are kept."""
         if not (len(keys) == len(hyps) == len(refs) == len(results)):
             raise ValueError(f"Scorer.add_aligned: {len(keys)} keys, {len(results)} results, {len(hyps)} hypotheses, {len(refs)} references")
+        if consensus is not None:
+            if len(consensus) != len(results) or not all(isinstance(r, (list, tuple)) for r in results):
+                raise ValueError("Scorer.add_aligned: consensus needs an n-best result and one entry for every utterance")
+            for c, res in zip(consensus, results):
+                if not 0 <= int(c["mbr_rank"]) < len(res):
+                    raise ValueError(f"Scorer.add_aligned: mbr_rank {c['mbr_rank']} outside a list of {len(res)}")
+                self.consensus.append((int(c["mbr"]["distance"]), int(c["consensus"]["distance"]), int(c["mbr_rank"]), len(res)))
         for key, res, h, r in zip(keys, results, hyps, refs):
             ranks = list(res) if isinstance(res, (list, tuple)) else None
             best = ranks[0] if ranks is not None else res
@@ -151,6 +188,14 @@ class Scorer:
             hist = np.bincount(np.asarray([o[1] for o in self.oracle], dtype=np.int64), minlength=max(o[2] for o in self.oracle))
             out["oracle_cer"] = best / ref_tokens if ref_tokens else (float("inf") if best else 0.0)
             out["oracle_rank_hist"] = hist.tolist()
+        if self.consensus:
+            if len(self.consensus) != n:
+                raise ValueError("mbr_cer and consensus_cer need n-best scores for every utterance that was added")
+            mbr, cons = sum(c[0] for c in self.consensus), sum(c[1] for c in self.consensus)
+            hist = np.bincount(np.asarray([c[2] for c in self.consensus], dtype=np.int64), minlength=max(c[3] for c in self.consensus))
+            out["mbr_cer"] = mbr / ref_tokens if ref_tokens else (float("inf") if mbr else 0.0)
+            out["consensus_cer"] = cons / ref_tokens if ref_tokens else (float("inf") if cons else 0.0)
+            out["mbr_rank_hist"] = hist.tolist()
         return out
 
     def _op_table(self):
@@ -193,9 +238,10 @@ class Scorer:
             f.write(json.dumps({"summary": self.summary()}, ensure_ascii=False) + "\n")
 
 
-def evaluate(model, batches, search="transcribe", nbest=1, scorer=None, **search_kwargs):
+def evaluate(model, batches, search="transcribe", nbest=1, scorer=None, consensus=False, posterior_scale=1.0, **search_kwargs):
     """model.evaluate: every batch of `batches` through one of the model's searches, its hypotheses scored against the batch's gold ids
-    (dec_preprocess of tgt_for_input: what cal_metrics scores against).  Returns the Scorer."""
+    (dec_preprocess of tgt_for_input: what cal_metrics scores against).  Returns the Scorer.  consensus=True (the n-best searches): the
+    lists' scores go to Scorer.add with posterior_scale, so the summary also has mbr_cer, consensus_cer and mbr_rank_hist."""
     import torch
 
     from . import kernels as K
@@ -203,6 +249,14 @@ def evaluate(model, batches, search="transcribe", nbest=1, scorer=None, **search
         raise ValueError(f"search must be 'transcribe', 'ctc_prefix_beam' or 'attention_beam' (got {search!r})")
     if int(nbest) < 1 or (search == "transcribe" and int(nbest) != 1):
         raise ValueError(f"nbest = {nbest}: at least 1, and exactly 1 with search='transcribe' (its searches return the best hypothesis)")
+    if consensus:
+        from .consensus import MAX_N
+        if search == "transcribe":
+            raise ValueError("consensus=True needs an n-best search: search='ctc_prefix_beam' or 'attention_beam'")
+        if int(nbest) > MAX_N:
+            raise ValueError(f"nbest = {nbest}: consensus takes lists of at most {MAX_N} entries")
+        if not np.isfinite(float(posterior_scale)) or float(posterior_scale) <= 0.0:
+            raise ValueError(f"posterior_scale must be finite and > 0 (got {posterior_scale})")
     scorer = Scorer(model.vocab) if scorer is None else scorer
     kw = dict(search_kwargs)
     beam = kw.pop("beam_size", 5)
@@ -216,13 +270,18 @@ def evaluate(model, batches, search="transcribe", nbest=1, scorer=None, **search
                 hyps = [r["ids"] for r in model.transcribe(pack, beam_size=beam, timestamps=False, **kw)]
             else:
                 fn = model.ctc_prefix_beam_search if search == "ctc_prefix_beam" else model.beam_search
-                lists = [[list(h["yseq"]) for h in utt] for utt in fn(pack, beam, int(nbest), **kw)]
+                found = fn(pack, beam, int(nbest), **kw)
+                lists = [[list(h["yseq"]) for h in utt] for utt in found]
                 for utt in lists:      # the attention searches spell sos ... eos
                     for i, seq in enumerate(utt):
                         seq = seq[1:] if seq and seq[0] == SOS_ID else seq
                         utt[i] = seq[:-1] if seq and seq[-1] == EOS_ID else seq
-                hyps = [utt or [[]] for utt in lists] if int(nbest) > 1 else [utt[0] if utt else [] for utt in lists]
+                hyps = [utt or [[]] for utt in lists] if int(nbest) > 1 or consensus else [utt[0] if utt else [] for utt in lists]
         keys = list(pack.key) if pack.get("key") is not None else [f"utt{seen + b}" for b in range(len(refs))]
-        scorer.add(keys, hyps, refs, device=pack.wave.device)
+        if consensus:
+            scores = [[float(h["score"]) for h in utt] or [0.0] for utt in found]
+            scorer.add(keys, hyps, refs, device=pack.wave.device, scores=scores, posterior_scale=posterior_scale)
+        else:
+            scorer.add(keys, hyps, refs, device=pack.wave.device)
         seen += len(refs)
     return scorer

@@ -12,6 +12,9 @@ Model flags are train.py's (same parser and loading as transcribe.py).  Scoring 
   --beam_size      the search's beam (5)
   --nbest          hypotheses kept per utterance (1); above 1 (ctc_prefix_beam, attention_beam) the summary gains the oracle CER: the
                    CER a perfect re-ranker of the lists would reach, and the histogram of the rank it would pick
+  --consensus      1: the lists also go through consensus decoding (asr_chinese_e2e_amd/consensus.py) with the search's scores as the
+                   posterior; the summary gains mbr_cer (the minimum-Bayes-risk entry), consensus_cer (the voted string) and mbr_rank_hist
+  --posterior_scale   the scores are multiplied by it before the softmax that makes the weights (1.0)
   --joint, --blank_skip, --context, --context_score, --lm, --lm_weight, --lm_ins     forwarded to the search, as transcribe.py's
   --frame_topk     candidates per frame of ctc_prefix_beam (10)
   --out            a JSONL file: one line per utterance with its alignment spelled in tokens, then the summary
@@ -39,7 +42,7 @@ from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 from transcribe import cmvn_path, load_model  # noqa: E402
 
 CLI_KEYS = ("ckpt", "manifest", "search", "beam_size", "nbest", "joint", "blank_skip", "context", "context_score", "lm", "lm_weight", "lm_ins", "frame_topk",
-            "out", "top", "cmvn", "frontend", "resample", "batch_size")
+            "out", "top", "cmvn", "frontend", "resample", "batch_size", "consensus", "posterior_scale")
 SEARCHES = ("transcribe", "ctc_prefix_beam", "attention_beam")
 
 
@@ -77,6 +80,19 @@ def eval_options(cli):
         raise SystemExit("evaluate.py: --nbest above 1 needs --search=ctc_prefix_beam or attention_beam (transcribe keeps the best hypothesis)")
     if num["nbest"] > num["beam_size"]:
         raise SystemExit(f"evaluate.py: --nbest={num['nbest']} above --beam_size={num['beam_size']}")
+    num["consensus"] = int(bool(int(cli.get("consensus", 0) or 0)))
+    if num["consensus"]:
+        if search == "transcribe":
+            raise SystemExit("evaluate.py: --consensus=1 needs --search=ctc_prefix_beam or attention_beam (it votes over an n-best list)")
+        if num["nbest"] > 64:
+            raise SystemExit(f"evaluate.py: --consensus=1 takes lists of at most 64 entries (--nbest={num['nbest']})")
+    try:
+        scale = float(cli.get("posterior_scale", 1.0))
+    except (TypeError, ValueError):
+        scale = float("nan")
+    if not np.isfinite(scale) or scale <= 0.0:
+        raise SystemExit(f"evaluate.py: --posterior_scale must be a finite number above 0 (got {cli.get('posterior_scale')!r})")
+    num["posterior_scale"] = scale
     return search, num
 
 
@@ -175,7 +191,8 @@ def evaluate(**flags):
     kw = search_options(cli, model, vocab, search)
     batches = manifest_batches(entries, vocab, parser, num["batch_size"], config.sample_rate, bool(int(cli.get("resample", 0) or 0)))
     try:
-        scorer = model.evaluate(batches, search=search, nbest=num["nbest"], beam_size=num["beam_size"], **kw)
+        scorer = model.evaluate(batches, search=search, nbest=num["nbest"], beam_size=num["beam_size"], consensus=bool(num["consensus"]),
+                                posterior_scale=num["posterior_scale"], **kw)
     except (ValueError, RuntimeError) as e:
         raise SystemExit(f"evaluate.py: {e}") from e
     if cli.get("out") not in (None, "", False):

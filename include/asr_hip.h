@@ -1300,6 +1300,54 @@ int asr_edit_align(const int32_t* hyp, const int32_t* hyp_len, int Lh, int ldh, 
                    int ldr, const int32_t* ref_of, const int32_t* host_hyp_len, const int32_t* host_ref_len, const int32_t* host_ref_of,
                    int P, int R, int32_t* counts, int32_t* ops, int32_t* n_ops, int ldo, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Consensus decoding of n-best lists: the minimum-Bayes-risk entry, a pivot-based confusion network with the posterior mass of its
+ * alternatives, the consensus string and a token confidence from the votes (additive to ABI 10; csrc/consensus.hip,
+ * asr_chinese_e2e_amd/consensus.py).
+ * Stands in for:  nothing in the reference.  The definition, in integers, is tests/consensus_ref.py; the kernels agree with it integer
+ *                 for integer, ties included.  Parity with SRILM's nbest-lattice or with ROVER is not pinned.
+ *
+ * Inputs, in the layout the prefix beam search produces: tok (U, N, L) int32 ids, entry rows ldn apart and utterances ldu apart; len
+ * (U, N) int32, -1 = absent (the entry keeps its index and takes part in nothing); weights (U, N) int32 >= 0, at most 2^30 per
+ * utterance over its present entries.  All three on the device; host_len / host_weights are host copies of the two small arrays, by which
+ * the launcher refuses.  The kernels clamp a length to [-1, L] and a weight to >= 0 all the same, and never use an id as an index.  The
+ * device sees no float: weights come from the caller (consensus.nbest_weights: floor(softmax * 2^20 + 0.5) in float64 on the host).
+ *
+ * With d[i][k] the edit distance of entries i and k (asr_edit_align's recurrence), risk[i] = sum_k w_k d[i][k] (int64), pivot = the
+ * present i of least risk (lowest i on ties), m = len[pivot] and S = 2 L + 1: the pivot's slots are 0 .. 2 m, slot 2 i + 1 pivot position
+ * i and slot 2 g the gap in front of position g.  Entry k, aligned to the pivot as asr_edit_align aligns a hypothesis to a reference (the
+ * pivot is the reference), votes its COR / SUB token at 2 i + 1, ASR_NBEST_EPS for a DEL, the FIRST token it inserts in gap g at 2 g
+ * (ASR_NBEST_EPS if none); later tokens of an insertion run vote nowhere and are counted in extra.  The alternatives of a slot are its
+ * distinct votes, ordered by weight (descending), then by their lowest voter (ascending).
+ *
+ * Output: one buffer `out` of asr_nbest_out_bytes(U, N, L, A) bytes, 8-byte aligned, of these arrays back to back (int32 but the first):
+ *   risk (U, N) int64 | d (U, N, N) | pivot (U) | W (U) | extra (U, N) | n_alts (U, S) | pivot_w (U, S) | votes (U, N, S) |
+ *   alts (U, S, A, 2) = (token, weight), the top A; entries past n_alts are (ASR_NBEST_EPS, 0).
+ *   pivot_w = the weight of the pivot's own vote; slots past 2 m hold n_alts = 0, pivot_w = 0, votes ASR_NBEST_EPS; an absent entry has
+ *   risk 0, d 0, extra 0 and votes ASR_NBEST_EPS.  Every word is written by exactly one lane: no atomics, two runs write the same bytes.
+ *
+ * asr_nbest_pair_dist (d), asr_nbest_pivot_votes (risk, pivot, W, votes, extra; reads d) and asr_nbest_slot_vote (alts, n_alts, pivot_w;
+ * reads pivot and votes) are the three stages, one launch each; asr_nbest_consensus is the three in order on `stream`.  All four take
+ * the same arguments and make the same checks.
+ * Refused before any launch (ASR_EINVAL; ASR_EWORKSPACE for the last): null or misaligned pointers, U <= 0 or above 65535, N outside
+ * [1, ASR_NBEST_MAX_N], L outside [0, ASR_NBEST_MAX_LEN], a host length above ASR_NBEST_MAX_LEN, ldn < L, ldu < (N - 1) ldn + L, A
+ * outside [1, ASR_NBEST_MAX_ALTS], a negative weight, a weight sum above 2^30, an utterance with no present entry, out_bytes below
+ * the size query's answer.
+ */
+#define ASR_NBEST_MAX_N 64
+#define ASR_NBEST_MAX_LEN 256
+#define ASR_NBEST_MAX_ALTS 8
+#define ASR_NBEST_EPS (-1)
+size_t asr_nbest_out_bytes(int U, int N, int L, int A);
+int asr_nbest_pair_dist(const int32_t* tok, const int32_t* len, const int32_t* weights, int L, int ldn, int ldu, const int32_t* host_len,
+                        const int32_t* host_weights, int U, int N, int A, int32_t* out, size_t out_bytes, void* stream);
+int asr_nbest_pivot_votes(const int32_t* tok, const int32_t* len, const int32_t* weights, int L, int ldn, int ldu, const int32_t* host_len,
+                          const int32_t* host_weights, int U, int N, int A, int32_t* out, size_t out_bytes, void* stream);
+int asr_nbest_slot_vote(const int32_t* tok, const int32_t* len, const int32_t* weights, int L, int ldn, int ldu, const int32_t* host_len,
+                        const int32_t* host_weights, int U, int N, int A, int32_t* out, size_t out_bytes, void* stream);
+int asr_nbest_consensus(const int32_t* tok, const int32_t* len, const int32_t* weights, int L, int ldn, int ldu, const int32_t* host_len,
+                        const int32_t* host_weights, int U, int N, int A, int32_t* out, size_t out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
