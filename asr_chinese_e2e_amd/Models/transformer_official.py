@@ -17,10 +17,15 @@ Additions required by BASELINE.json's north_star (not in the reference):
   * config.dtype: "bf16" (default) or "fp32" (exact-fp32 parity mode),
   * config.attn_window: +-w frame band on encoder self-attention (long-form config), -1 = full,
   * config.chunk_size / left_chunks / decoding_chunk_size / decoding_left_chunks: chunk-masked encoder self-attention for
-    streaming (WeNet U2's subsequent_chunk_mask; encoder_mask() below), and model.stream() (stream.py).
+    streaming (WeNet U2's subsequent_chunk_mask; encoder_mask() below), and model.stream() (stream.py),
+  * config.ema_decay in [0, 1) / ema_warmup: an exponential moving average of the parameters kept beside them in the flat buffers and
+    updated inside the fused Adam pass (include/asr_hip.h: asr_adam_ema_step); ema_state_dict() / save_ema() / load_ema() / ema_weights().
+    0 (the default) allocates nothing and launches what was launched without it.
 """
+import contextlib
 import math
 
+import numpy as np
 import torch
 
 from .. import engine as E
@@ -76,6 +81,18 @@ class _SpeechTransformer(BaseModel):
         self.label_smoothing = float(getattr(c, "label_smoothing", 0.0))   # Utils/loss.py:30-45 (the reference never enables it)
         self.cer_in_iterate = bool(getattr(c, "cer_in_iterate", True))
         self._step_seed = int(getattr(c, "seed", 0))   # advanced once per training step (dropout masks)
+        decay = getattr(c, "ema_decay", 0.0)
+        try:
+            ok = not isinstance(decay, (bool, str)) and math.isfinite(float(decay)) and 0.0 <= float(np.float32(decay)) < 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:      # as the kernel takes it: a float32 inside (0, 1), or 0 = off
+            raise ValueError(f"ema_decay={decay!r}: a finite number in [0, 1) (0 = no average)")
+        self.ema_decay = float(decay)
+        self.ema_warmup = bool(getattr(c, "ema_warmup", True))
+        self._ema_step = 0           # steps counted here for optimizers that keep no _step of their own
+        self._ema_active = False     # inside ema_weights(): p holds the average, ema the raw parameters
+        self._ema_pending = None     # an average loaded (load_ema) before the flat buffers existed
         d, H, dk, ff = c.d_model, c.num_head, c.hidden_size, c.ff_size
         d_in = c.n_mels * c.lfr_m
         V = vocab.vocab_size
@@ -186,7 +203,8 @@ class _SpeechTransformer(BaseModel):
         K.bind_device(device)
         old = {name: p.detach().to(device=device, dtype=torch.float32) for name, p in self._named_flat_params()}
         old_mv = (f.m.to(device), f.v.to(device)) if f.m is not None else None   # keep Adam state across a device move
-        f.allocate(device, self.lowp)
+        old_ema = f.ema.to(device) if f.ema is not None else None                # ... and the average
+        f.allocate(device, self.lowp, ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
         if old_mv is not None:
             f.m.copy_(old_mv[0])
             f.v.copy_(old_mv[1])
@@ -195,6 +213,11 @@ class _SpeechTransformer(BaseModel):
             view.copy_(old[name].view(view.shape))
             p.data = view
             p.grad = f.view(f.g, name)
+        if f.ema is not None:
+            f.ema.copy_(f.p if old_ema is None else old_ema)      # a new average starts as a copy of p (the gaps between blocks: zero, as in p)
+            if self._ema_pending is not None:
+                self._fill_ema(self._ema_pending)
+                self._ema_pending = None
         f.refresh_lowp()
         for b in self.buffers():
             b.data = b.data.to(device)
@@ -218,10 +241,107 @@ class _SpeechTransformer(BaseModel):
     def load_state_dict(self, state_dict, strict=True, **kw):
         state_dict = {k: v for k, v in state_dict.items()}
         self._views_checked = False
+        if self._ema_active:
+            raise RuntimeError("load_state_dict inside ema_weights(): the parameters are swapped with their average")
         out = super().load_state_dict(state_dict, strict=strict, **kw)
         if self._flat.p is not None:
             self._flat.refresh_lowp()
+        self._ema_pending = None
+        f = self._flat
+        if f.ema is not None:      # the average restarts from the loaded weights (load_ema overrides it)
+            if all(p.data_ptr() == f.p.data_ptr() + 4 * f.index[n][0] for n, p in self._named_flat_params()):
+                f.ema.copy_(f.p)
+            else:                  # the parameters left the flat buffer: _ensure_engine rebuilds it, and the average from p
+                f.ema = None
         return out
+
+    # ------------------------------------------------------------------ the average of the parameters (config.ema_decay > 0)
+    def _need_ema(self, what):
+        if self.ema_decay <= 0:
+            raise RuntimeError(f"{what}: the model keeps no average (config.ema_decay is 0)")
+
+    def _fill_ema(self, state):
+        """Write a state dict with the model's keys into the flat average (every parameter key must be there)."""
+        f = self._flat
+        names = [n for n, _ in self._named_flat_params()]
+        missing = [n for n in names if n not in state]
+        if missing:
+            raise KeyError(f"the average lacks {len(missing)} parameters of the model: {missing[:5]}")
+        for n in names:
+            view = f.view(f.ema, n)
+            if tuple(state[n].shape) != tuple(view.shape):
+                raise ValueError(f"the average's {n} has shape {tuple(state[n].shape)}, the model {tuple(view.shape)}")
+            view.copy_(state[n])
+
+    def ema_state_dict(self):
+        """The average as a plain state dict with the model's keys (buffers included, on the CPU): it loads into a model of this package
+        built with or without an average, and into the reference's."""
+        self._need_ema("ema_state_dict")
+        f = self._flat
+        if f.ema is None and self._ema_pending is not None:
+            return {k: v.detach().cpu().clone() for k, v in self._ema_pending.items()}
+        by_id = {id(p): n for n, p in self._named_flat_params()}
+        src = f.p if self._ema_active else f.ema
+        out = {}
+        for k, v in self.state_dict(keep_vars=True).items():
+            n = by_id.get(id(v))
+            if n is not None and src is not None:
+                out[k] = f.view(src, n).detach().cpu().clone()
+            else:                                    # buffers; before the flat buffers exist the average is the parameters themselves
+                out[k] = v.detach().cpu().clone()
+        return out
+
+    def save_ema(self, path):
+        torch.save(self.ema_state_dict(), path)
+        print(f"\nmodel average saved to {path}")
+
+    def load_ema(self, path):
+        """Override the average with a file written by save_ema (after load / load_state_dict, which reset it to the weights).  A missing
+        file or missing keys raise."""
+        self._need_ema("load_ema")
+        if self._ema_active:
+            raise RuntimeError("load_ema inside ema_weights(): the parameters are swapped with their average")
+        state = torch.load(path, map_location="cpu", weights_only=True)
+        missing = [n for n, _ in self._named_flat_params() if n not in state]
+        if missing:
+            raise KeyError(f"{path} lacks {len(missing)} parameters of the model: {missing[:5]}")
+        if self._flat.ema is None:
+            self._ema_pending = state                # the flat buffers do not exist yet: _ensure_engine applies it
+        else:
+            self._fill_ema(state)
+        print(f"\nLoaded model average from '{path}'")
+
+    def _swap_ema(self):
+        f = self._flat
+        tmp = f.p.clone()
+        f.p.copy_(f.ema)
+        f.ema.copy_(tmp)
+        f.refresh_lowp()
+        f.version += 1
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the parameters ARE the average (p and ema swapped, bf16 shadow refreshed): forward, transcribe, evaluate, the
+        searches and stream run on it.  On exit they are swapped back.  Training inside the block raises."""
+        self._need_ema("ema_weights")
+        if self._ema_active:
+            raise RuntimeError("ema_weights() is already active")
+        self._ensure_engine(next(self.parameters()).device)
+        self._swap_ema()
+        self._ema_active = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._ema_active = False
+
+    def _ema_after_step(self, optimizer):
+        """The average after a step of an optimizer that did not run the fused Adam + EMA pass: asr_ema_update with the optimizer's step
+        count where it keeps one (NoamOpt._step), else a count kept here."""
+        self._ema_step += 1
+        s = getattr(optimizer, "_step", None)
+        s = int(s) if isinstance(s, int) and not isinstance(s, bool) and s >= 1 else self._ema_step
+        K.ema_update(self._flat.p, self._flat.ema, self.ema_decay, s, self.ema_warmup)
 
     def zero_flat_grads(self):
         """Zero the flat gradient buffer for the step that follows.  With the multi-stream engine the fill (160 MB at the joint model's size,
@@ -823,6 +943,8 @@ class _SpeechTransformer(BaseModel):
             with torch.no_grad():
                 output = self.forward(input)
                 return self.cal_metrics(output, input), None
+        if self._ema_active:
+            raise RuntimeError("iterate(is_train=True) inside ema_weights(): the parameters are swapped with their average")
         self._ensure_engine(input.wave.device)
         optimizer.zero_grad()
         if getattr(optimizer, "fused_step", None) is None or not getattr(optimizer, "keeps_grad_views", False):
@@ -838,6 +960,8 @@ class _SpeechTransformer(BaseModel):
             torch.nn.utils.clip_grad_norm_(self.parameters(), CLIP_NORM)
             optimizer.step()
             self._flat.refresh_lowp()
+            if self._flat.ema is not None:
+                self._ema_after_step(optimizer)
         metrics = Pack()
         metrics.add(loss=loss[0])
         if self.use_decoder and self.use_ctc:
@@ -869,6 +993,8 @@ class _SpeechTransformer(BaseModel):
             left_chunks = -1                # chunks of left context, -1 = all
             decoding_chunk_size = None      # inference mask: None = chunk_size when static, else full; 0 = full
             decoding_left_chunks = None     # None = left_chunks when the chunk is static, else -1
+            ema_decay = 0.0                 # > 0: keep an exponential moving average of the parameters with this decay (0 = off, nothing allocated)
+            ema_warmup = True               # the decay of step s is min(ema_decay, (1 + s) / (10 + s))
 
         return ModelConfig
 

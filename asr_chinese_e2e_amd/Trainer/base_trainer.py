@@ -20,10 +20,10 @@ class BaseTrainer(Trainer11):
     reference = "-loss"
 
     def __init__(self, optimizer, model, train_iter, dev_iter, test_iter, ckpt_root="ckpt/", exp_name="base_exp", log_every_iter=100,
-                 eval_every_iter=1000, save_every_iter=5000, drop_exp=True, log_path=None):
+                 eval_every_iter=1000, save_every_iter=5000, drop_exp=True, log_path=None, eval_ema=True):
         super().__init__(optimizer, model, train_iter, dev_iter=dev_iter, test_iter=test_iter, ckpt_root=ckpt_root, exp_name=exp_name,
                          log_every_iter=log_every_iter, eval_every_iter=eval_every_iter, save_every_iter=save_every_iter, drop_exp=drop_exp,
-                         log_path=log_path)
+                         log_path=log_path, eval_ema=eval_ema)
         assert self.reference[0] in ["-", "+"]                     # base_trainer.py:39
         self.best = 1e10 if self.reference[0] == "-" else 0
 

@@ -10,6 +10,8 @@ is a FusedAdam and the model stores its parameters flat (engine.FlatParams), `fu
 grad-norm + clip + Noam LR + Adam + bf16 shadow refresh as three kernel launches over the flat
 buffers, with the step counter and learning rate computed on the device (graph-capturable).
 Any other torch.optim optimizer still works through step() (per-tensor path).
+When the model keeps an average of its parameters (flat.ema, config.ema_decay > 0), the fused path updates it inside the
+Adam pass (asr_adam_ema_step) and the other path with a pass of its own (asr_ema_update).
 """
 import torch
 
@@ -94,6 +96,8 @@ class NoamOpt:
             torch.nn.utils.clip_grad_norm_(params, max_norm)
             self.step()
             flat.refresh_lowp()
+            if flat.ema is not None:      # the average of the parameters, as a pass of its own (the step just taken is self._step)
+                K.ema_update(flat.p, flat.ema, flat.ema_decay, self._step, flat.ema_warmup)
             return
         step, hyper, sumsq, ws = self._device_state(flat)
         if self._pending_state is not None:          # checkpoint loaded before the flat buffers existed
@@ -102,8 +106,12 @@ class NoamOpt:
         g = self.optimizer.param_groups[0]
         b1, b2 = g["betas"]
         K.grad_sumsq_noam(flat.g, sumsq, ws, step, hyper, self.model_size, self.warmup, self.factor, 0.0, b1, b2)      # squared norm + Noam rate: two launches
-        K.adam_step(flat.p, flat.g, flat.m, flat.v, flat.lp, hyper, sumsq, max_norm, b1, b2, g["eps"], write_clipped=True)
-        flat.version += 1               # the bf16 weights changed: transposed copies (engine.refresh_transposes) are stale
+        if flat.ema is not None:      # the same pass also blends the fresh p into the average (its step is hyper[3], on the device)
+            K.adam_ema_step(flat.p, flat.g, flat.m, flat.v, flat.lp, hyper, sumsq, max_norm, b1, b2, g["eps"], flat.ema, flat.ema_decay, flat.ema_warmup,
+                            write_clipped=True)
+        else:
+            K.adam_step(flat.p, flat.g, flat.m, flat.v, flat.lp, hyper, sumsq, max_norm, b1, b2, g["eps"], write_clipped=True)
+        flat.version += 1              # the bf16 weights changed: transposed copies (engine.refresh_transposes) are stale
         self._step += 1                 # host mirror of the device counter (no sync)
         self._rate = self.rate()
         for gr in self.optimizer.param_groups:

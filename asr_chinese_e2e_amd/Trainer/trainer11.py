@@ -20,8 +20,9 @@ class Trainer11:
     reference = "-loss"
 
     def __init__(self, optimizer, model, train_iter, dev_iter=None, test_iter=None, ckpt_root="ckpt/", exp_name="base_exp",
-                 log_every_iter=100, eval_every_iter=1000, save_every_iter=5000, drop_exp=True, log_path=None):
+                 log_every_iter=100, eval_every_iter=1000, save_every_iter=5000, drop_exp=True, log_path=None, eval_ema=True):
         self.optimizer, self.model = optimizer, model
+        self.eval_ema = bool(eval_ema)      # models with an average of their parameters (config.ema_decay > 0): evaluate it too, under prefix + "ema/"
         self.train_iter, self.dev_iter, self.test_iter = train_iter, dev_iter, test_iter
         self.ckpt_root = ckpt_root
         self.exp_name = exp_name if exp_name is not None else self.get_time()
@@ -94,6 +95,9 @@ class Trainer11:
         prefix = f"e{epoch}_s{step}"
         self.global_step, self.global_epoch = step, epoch
         self.model.load(os.path.join(self.ckpt_root, exp_name, prefix + ".model"))
+        ema_path = os.path.join(self.ckpt_root, exp_name, prefix + ".ema.model")
+        if self._has_ema() and os.path.isfile(ema_path):      # without the file the average restarts from the loaded weights
+            self.model.load_ema(ema_path)
         # a fresh model allocates its flat HBM buffers at the first step: allocate them now when it already sits on
         # the GPU, so that Adam's moments land in them (otherwise NoamOpt keeps the state until the first fused step)
         ensure = getattr(self.model, "_ensure_engine", None)
@@ -106,14 +110,18 @@ class Trainer11:
     def save_ckpt(self):
         prefix = f"e{self.global_epoch}_s{self.global_step}"
         self.model.save(os.path.join(self.exp_root, prefix + ".model"))
+        if self._has_ema():
+            self.model.save_ema(os.path.join(self.exp_root, prefix + ".ema.model"))
         self.optimizer.save(os.path.join(self.exp_root, prefix + ".opt"))
 
     def summarize(self, pack, prefix="train/"):
         for k in pack:
             self.add_scalar(prefix + k, pack[k].detach().float().cpu().reshape(-1)[0], self.global_step)
 
-    def evaluate(self, dev_iter, prefix="dev/"):
-        self.model.eval()
+    def _has_ema(self):
+        return float(getattr(self.model, "ema_decay", 0.0) or 0.0) > 0
+
+    def _eval_pass(self, dev_iter, prefix):
         sums, n = {}, 0
         with torch.no_grad():
             for data in dev_iter:
@@ -123,8 +131,16 @@ class Trainer11:
                 n += 1
         for k, v in sums.items():
             self.add_scalar(prefix + k, v / max(n, 1), self.global_step)
-        self.model.train()
         return {k: v / max(n, 1) for k, v in sums.items()}
+
+    def evaluate(self, dev_iter, prefix="dev/"):
+        self.model.eval()
+        out = self._eval_pass(dev_iter, prefix)
+        if self.eval_ema and self._has_ema():      # a second pass on the average of the parameters: dev/ema/loss, dev/ema/cer
+            with self.model.ema_weights():
+                self._eval_pass(dev_iter, prefix + "ema/")
+        self.model.train()
+        return out
 
     def get_time(self):
         return (datetime.datetime.now() + datetime.timedelta(hours=8)).strftime("%Y%m%d%H%M")

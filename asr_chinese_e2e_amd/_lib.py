@@ -154,6 +154,8 @@ SIGNATURES = {
     "asr_noam_hyper": (I, [P, P, F, F, F, F, F, F, P]),
     "asr_grad_sumsq_noam": (I, [P, Z, P, P, Z, P, P, F, F, F, F, F, F, P]),
     "asr_adam_step": (I, [P, P, P, P, P, Z, P, P, F, F, F, F, I, P]),
+    "asr_adam_ema_step": (I, [P, P, P, P, P, Z, P, P, F, F, F, F, I, P, F, I, P]),
+    "asr_ema_update": (I, [P, P, Z, F, I, F, P]),
     "asr_loss_combine": (I, [P, I, P, P, I, F, F, P, P]),
     "asr_gemm_nt_bf16": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "asr_gemm_small_bf16": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P]),

@@ -418,11 +418,36 @@ __global__ void noam_hyper_kernel(int32_t* step, float* hyper, float model_size,
     noam_update(step, hyper, model_size, warmup, factor, lr_const, b1, b2);
 }
 
+// ---- exponential moving average of the parameters (include/asr_hip.h: asr_adam_ema_step, asr_ema_update)
+// 1 - d of the step s, once per thread in double: the division is the correctly rounded one whatever the fp32 division flags are (as in noam_update).
+__device__ __forceinline__ float ema_one_minus_decay(float decay, int warmup, float s) {
+    double d = (double)decay;
+    if (warmup) {
+        const double w = (1.0 + (double)s) / (10.0 + (double)s);
+        d = w < d ? w : d;
+    }
+    return (float)(1.0 - d);
+}
+// e' = e + omd * (p - e): a subtraction, a multiplication and an addition, each rounded on its own.  The operators stand under the pragma because
+// the build contracts a * b + c into one fma wherever both operations allow it (logmel.hip: the header's __fmul_rn / __fadd_rn allow it too).
+__device__ __forceinline__ float ema_blend(float e, float p, float omd) {
+#pragma clang fp contract(off)
+    const float t = p - e;
+    const float u = omd * t;
+    return e + u;
+}
+
+// EMA = false is asr_adam_step's kernel as it always was; EMA = true blends the fresh p into `ema` in the same pass (one more 16-byte load and
+// store per four parameters).
+template <bool EMA>
 __global__ __launch_bounds__(EW_BLOCK) void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, bf16_t* __restrict__ p_lp, size_t n4, size_t n,
                                                         const float* __restrict__ hyper, const float* __restrict__ sumsq,
-                                                        float max_norm, float b1, float b2, float eps, int write_clipped) {
+                                                        float max_norm, float b1, float b2, float eps, int write_clipped,
+                                                        float* __restrict__ ema, float decay, int ema_warmup) {
     const float lr = hyper[0], bc1 = hyper[1], bc2s = hyper[2];
+    float omd = 0.f;
+    if constexpr (EMA) omd = ema_one_minus_decay(decay, ema_warmup, hyper[3]);
     float coef = 1.f;
     if (max_norm > 0.f) {
         const float norm = sqrtf(*sumsq);
@@ -445,6 +470,12 @@ __global__ __launch_bounds__(EW_BLOCK) void adam_kernel(float* __restrict__ p, f
         *(f32x4*)(p + i * 4) = pv;
         if (write_clipped) *(f32x4*)(g + i * 4) = gv;
         if (p_lp) store4<bf16_t>(p_lp + i * 4, pv);
+        if constexpr (EMA) {
+            f32x4 ev = *(const f32x4*)(ema + i * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ev[j] = ema_blend(ev[j], pv[j], omd);
+            *(f32x4*)(ema + i * 4) = ev;
+        }
     }
     if (blockIdx.x == 0) {
         size_t i = n4 * 4 + threadIdx.x;
@@ -456,7 +487,25 @@ __global__ __launch_bounds__(EW_BLOCK) void adam_kernel(float* __restrict__ p, f
             m[i] = mm; v[i] = vv; p[i] = pp;
             if (write_clipped) g[i] = gg;
             if (p_lp) p_lp[i] = (bf16_t)pp;
+            if constexpr (EMA) ema[i] = ema_blend(ema[i], pp, omd);
         }
+    }
+}
+
+// the blend as a pass of its own, the step given by the host: for optimizers that do not go through adam_kernel
+__global__ __launch_bounds__(EW_BLOCK) void ema_update_kernel(const float* __restrict__ p, float* __restrict__ ema, size_t n4, size_t n, float decay,
+                                                              int ema_warmup, float step) {
+    const float omd = ema_one_minus_decay(decay, ema_warmup, step);
+    for (size_t i = blockIdx.x * (size_t)EW_BLOCK + threadIdx.x; i < n4; i += (size_t)gridDim.x * EW_BLOCK) {
+        const f32x4 pv = *(const f32x4*)(p + i * 4);
+        f32x4 ev = *(const f32x4*)(ema + i * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ev[j] = ema_blend(ev[j], pv[j], omd);
+        *(f32x4*)(ema + i * 4) = ev;
+    }
+    if (blockIdx.x == 0) {
+        size_t i = n4 * 4 + threadIdx.x;
+        if (i < n) ema[i] = ema_blend(ema[i], p[i], omd);
     }
 }
 
@@ -768,8 +817,34 @@ extern "C" int asr_adam_step(float* p, float* g, float* m, float* v, void* p_lp,
     if (!p || !g || !m || !v || !hyper) ASR_FAIL(ASR_EINVAL, "asr_adam_step: null pointer");
     if (max_norm > 0.f && !sumsq) ASR_FAIL(ASR_EINVAL, "asr_adam_step: clipping needs sumsq");
     if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) % 16) ASR_FAIL(ASR_EINVAL, "asr_adam_step: buffers must be 16-byte aligned");
-    adam_kernel<<<ew_grid(n / 4), EW_BLOCK, 0, (hipStream_t)stream>>>(p, g, m, v, (bf16_t*)p_lp, n / 4, n, hyper, sumsq, max_norm, b1, b2, eps, write_clipped);
+    adam_kernel<false><<<ew_grid(n / 4), EW_BLOCK, 0, (hipStream_t)stream>>>(p, g, m, v, (bf16_t*)p_lp, n / 4, n, hyper, sumsq, max_norm, b1, b2, eps, write_clipped,
+                                                                             nullptr, 0.f, 0);
     ASR_CHECK_LAUNCH("asr_adam_step");
+    return ASR_OK;
+}
+
+static int ema_decay_ok(float decay) { return decay > 0.f && decay < 1.f; }      // false for NaN and the infinities too
+
+extern "C" int asr_adam_ema_step(float* p, float* g, float* m, float* v, void* p_lp, size_t n, const float* hyper, const float* sumsq,
+                                 float max_norm, float b1, float b2, float eps, int write_clipped, float* ema, float decay, int warmup, void* stream) {
+    if (!p || !g || !m || !v || !hyper || !ema) ASR_FAIL(ASR_EINVAL, "asr_adam_ema_step: null pointer");
+    if (max_norm > 0.f && !sumsq) ASR_FAIL(ASR_EINVAL, "asr_adam_ema_step: clipping needs sumsq");
+    if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)ema)) % 16)
+        ASR_FAIL(ASR_EINVAL, "asr_adam_ema_step: buffers must be 16-byte aligned");
+    if (!ema_decay_ok(decay)) ASR_FAIL(ASR_EINVAL, "asr_adam_ema_step: decay %g is not inside (0, 1)", (double)decay);
+    adam_kernel<true><<<ew_grid(n / 4), EW_BLOCK, 0, (hipStream_t)stream>>>(p, g, m, v, (bf16_t*)p_lp, n / 4, n, hyper, sumsq, max_norm, b1, b2, eps, write_clipped,
+                                                                            ema, decay, warmup);
+    ASR_CHECK_LAUNCH("asr_adam_ema_step");
+    return ASR_OK;
+}
+
+extern "C" int asr_ema_update(const float* p, float* ema, size_t n, float decay, int warmup, float step, void* stream) {
+    if (!p || !ema) ASR_FAIL(ASR_EINVAL, "asr_ema_update: null pointer");
+    if ((((uintptr_t)p) | ((uintptr_t)ema)) % 16) ASR_FAIL(ASR_EINVAL, "asr_ema_update: buffers must be 16-byte aligned");
+    if (!ema_decay_ok(decay)) ASR_FAIL(ASR_EINVAL, "asr_ema_update: decay %g is not inside (0, 1)", (double)decay);
+    if (!(step >= 1.f)) ASR_FAIL(ASR_EINVAL, "asr_ema_update: step %g, the first optimizer step is 1", (double)step);
+    ema_update_kernel<<<ew_grid(n / 4), EW_BLOCK, 0, (hipStream_t)stream>>>(p, ema, n / 4, n, decay, warmup, step);
+    ASR_CHECK_LAUNCH("asr_ema_update");
     return ASR_OK;
 }
 

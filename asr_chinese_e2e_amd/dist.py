@@ -240,6 +240,8 @@ class DataParallel:
             self.pool_draws = E.steer_stream_pool(flat.g.device, avoid)
         dist.broadcast(flat.p, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)          # identical replicas
         flat.refresh_lowp()
+        if flat.ema is not None:      # the replicas' averages: identical from here on, being a function of identical p
+            dist.broadcast(flat.ema, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
         self._counts = _Counts(torch.zeros(2, dtype=torch.float32, device=flat.g.device), self.bucketer.comm_stream, group)
         eng.grad_ready = self.bucketer.ready
 
@@ -250,6 +252,8 @@ class DataParallel:
         model = self.model
         if optimizer is None or not is_train:
             return model.iterate(input, optimizer, is_train)
+        if getattr(model, "_ema_active", False):
+            raise RuntimeError("iterate(is_train=True) inside ema_weights(): the parameters are swapped with their average")
         from .Models.transformer_official import CLIP_NORM
         from .Utils import Pack
         model.zero_flat_grads()

@@ -62,12 +62,14 @@ class FlatParams:
             off = (off + ALIGN - 1) // ALIGN * ALIGN
         self.numel = off
         self.device = None
-        self.p = self.g = self.m = self.v = self.lp = None
+        self.p = self.g = self.m = self.v = self.lp = self.ema = None
 
-    def allocate(self, device, lowp):
+    def allocate(self, device, lowp, ema_decay=0.0, ema_warmup=True):
         self.device = torch.device(device)
         z = lambda dt: torch.zeros(self.numel, dtype=dt, device=self.device)
         self.p, self.g, self.m, self.v = z(torch.float32), z(torch.float32), z(torch.float32), z(torch.float32)
+        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
+        self.ema = z(torch.float32) if ema_decay > 0 else None      # exponential moving average of p (config.ema_decay), same layout, gaps zero
         self.lp = z(torch.bfloat16) if lowp else None
         self.lpT = None      # transposed copies of the projection weights (engine.refresh_transposes), same offsets as lp
         self.version = 0     # bumped whenever lp is rewritten (refresh_lowp, fused optimizer step)

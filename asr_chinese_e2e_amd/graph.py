@@ -34,6 +34,7 @@ class GraphedStep:
         optimizer._device_state(flat)
         step_dev = optimizer._dev[0]
         snap = [t.clone() for t in (flat.p, flat.m, flat.v)] + [step_dev.clone()]
+        ema_snap = flat.ema.clone() if flat.ema is not None else None      # the average of the parameters (config.ema_decay > 0)
         host_step, host_rate = optimizer._step, optimizer._rate
         seed = model._step_seed
 
@@ -61,6 +62,8 @@ class GraphedStep:
                 self.loss, self.cer = body()
         # restore: warm-up / capture leave no trace
         flat.p.copy_(snap[0]); flat.m.copy_(snap[1]); flat.v.copy_(snap[2]); step_dev.copy_(snap[3])
+        if ema_snap is not None:
+            flat.ema.copy_(ema_snap)
         flat.refresh_lowp()
         optimizer._step, optimizer._rate = host_step, host_rate
         model._step_seed = seed
@@ -94,6 +97,8 @@ class GraphedModel:
     def iterate(self, input, optimizer=None, is_train=True):
         if optimizer is None or not is_train:
             return self.model.iterate(input, optimizer, is_train)
+        if getattr(self.model, "_ema_active", False):
+            raise RuntimeError("iterate(is_train=True) inside ema_weights(): the parameters are swapped with their average")
         key = tuple(tuple(input[k].shape) for k in ("wave", "tgt_for_input"))
         g = self.graphs.get(key)
         if g is None:

@@ -1085,6 +1085,30 @@ def adam_step(p, g, m, v, p_lp, hyper, sumsq, max_norm, b1, b2, eps, write_clipp
           (28.0 + (4.0 if write_clipped else 0.0) + (2.0 if p_lp is not None else 0.0)) * n)
 
 
+def adam_ema_step(p, g, m, v, p_lp, hyper, sumsq, max_norm, b1, b2, eps, ema, decay, warmup=True, write_clipped=True):
+    """adam_step and, in the same pass, ema += (1 - d) * (p - ema) on the fresh p (include/asr_hip.h: asr_adam_ema_step); the step of the
+    warm-up is hyper[3].  p, g, m, v, p_lp get adam_step's bits."""
+    _chk_f32(p, g, m, v, hyper, sumsq, ema)
+    n = p.numel()
+    assert g.numel() == n and m.numel() == n and v.numel() == n and ema.numel() == n and hyper.numel() >= 4
+    if p_lp is not None:
+        assert p_lp.dtype == torch.bfloat16 and p_lp.numel() == n and p_lp.is_contiguous()
+    # adam_step's traffic + ema read and written: 8 B per parameter more
+    timed("adam", 0.0, lambda: check(
+        lib.asr_adam_ema_step(_p(p), _p(g), _p(m), _p(v), _p(p_lp), n, _p(hyper), _p(sumsq), float(max_norm), float(b1), float(b2), float(eps),
+                              int(write_clipped), _p(ema), float(decay), int(bool(warmup)), _stream()), "asr_adam_ema_step"),
+          (36.0 + (4.0 if write_clipped else 0.0) + (2.0 if p_lp is not None else 0.0)) * n)
+
+
+def ema_update(p, ema, decay, step, warmup=True):
+    """ema += (1 - d) * (p - ema) as a pass of its own, d of optimizer step `step` >= 1 (asr_ema_update): 12 B per parameter."""
+    _chk_f32(p, ema)
+    assert p.numel() == ema.numel()
+    timed("ema", 0.0, lambda: check(lib.asr_ema_update(_p(p), _p(ema), p.numel(), float(decay), int(bool(warmup)), float(step), _stream()),
+                                    "asr_ema_update"), 12.0 * p.numel())
+    return ema
+
+
 # --------------------------------------------------------------------------------- GEMM
 def gemm_nt_supported(M, N, K, lda, ldb, ldc):
     return K % 8 == 0 and lda % 8 == 0 and ldb % 8 == 0 and ldc % 4 == 0

@@ -634,6 +634,23 @@ int asr_grad_sumsq_noam(const float* g, size_t n, float* sumsq, void* ws, size_t
 int asr_adam_step(float* p, float* g, float* m, float* v, void* p_lp, size_t n,
                   const float* hyper, const float* sumsq, float max_norm, float b1, float b2,
                   float eps, int write_clipped, void* stream);
+/* Exponential moving average of the parameters (additive to ABI 10).  For optimizer step s >= 1 (the value asr_noam_hyper leaves in
+ * hyper[3]), p the parameter AFTER that step's Adam update and e the average before the step:
+ *
+ *   d   = min(float64(float32(decay)), (1.0 + s) / (10.0 + s))   if warmup else float64(float32(decay))     float64
+ *   omd = float32(1.0 - d)                                                                                  one rounding
+ *   t   = float32(p - e);   u = float32(omd * t);   e' = float32(e + u)                                     three float32 roundings, no FMA
+ *
+ * decay lies in (0, 1); p == e is an exact fixed point; numpy float32 restates the three roundings bit for bit (tests/ema_ref.py),
+ * and the kernels equal that restatement bit for bit.
+ * asr_adam_ema_step: asr_adam_step (the same arithmetic, the same bits in p, g, m, v, p_lp) and the blend of the fresh p into ema (n f32)
+ *   in the same pass, s read from hyper[3] on the device (graph-capturable).
+ * asr_ema_update: the blend as a pass of its own with s = step given by the host (optimizers that do not run asr_adam_ema_step); p is only read.
+ * Both refuse before any launch: null pointers, buffers that are not 16-byte aligned, decay not finite or outside (0, 1), step < 1. */
+int asr_adam_ema_step(float* p, float* g, float* m, float* v, void* p_lp, size_t n,
+                      const float* hyper, const float* sumsq, float max_norm, float b1, float b2,
+                      float eps, int write_clipped, float* ema, float decay, int warmup, void* stream);
+int asr_ema_update(const float* p, float* ema, size_t n, float decay, int warmup, float step, void* stream);
 /* loss[0] = w_ce * sum(row_nll[0..M)) / *n_valid + w_ctc * sum(nll[0..B)) / B ;
  * loss[1] = the CE term, loss[2] = the CTC term (either input may be NULL with weight 0). */
 int asr_loss_combine(const float* row_nll, int M, const float* n_valid, const float* nll, int B,

@@ -32,6 +32,10 @@ Differences that come with the MI355X path:
     (data_handler/specaug.py; never dev / test, and instead of - not together with - the reference's `--augment`);
   * `--resample=1` accepts files at 8, 11.025, 12, 22.05, 24, 32, 44.1, 48, 88.2 and 96 kHz (corpus, noise clips, responses) and converts
     them to 16 kHz on the GPU (data_handler/resample.py); without it a file at another rate raises, as before;
+  * `--ema_decay=0.999` keeps an exponential moving average of the parameters inside the fused Adam pass (`--ema_warmup=False` switches
+    the warm-up `min(decay, (1 + s) / (10 + s))` off); both are model-config keys and reach the model like every other one.  The trainers
+    then write e{E}_s{S}.ema.model beside every checkpoint and log dev/ema/loss, dev/ema/cer beside the raw figures; average.py takes the
+    mean of the last or best N checkpoints afterwards;
   * `--synthetic=N` trains on N synthetic AISHELL-1-shaped utterances (no dataset ships with this repository);
   * `--trainer=BaseTrainer` selects the twin of Trainer/base_trainer.py instead of Trainer11.
 """

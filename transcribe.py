@@ -6,7 +6,8 @@
 
 Model flags are train.py's (same parser, same TrainConfig / ModelConfig merge, same get_model_class), so the flags a model was
 trained with rebuild it.  Inference flags:
-  --ckpt         state dict as BaseModel.save writes it (required; a missing file or missing keys are errors)
+  --ckpt         state dict as BaseModel.save writes it (required; a missing file or missing keys are errors);
+                 several files, --ckpt=a.model,b.model,c.model, are averaged in memory (average.py writes such a mean to a file)
   --vocab_path   the vocabulary the model was trained with (Vocab.save)
   --wavs         comma-separated 16-bit PCM WAV files, or
   --manifest     a collector manifest (one JSON object {"wave": path, ...} per line)
@@ -109,11 +110,19 @@ def _finite(x):
 
 
 def load_model(config, vocab, ckpt, device="cuda"):
-    """Model of config.model_name with the checkpoint's weights; a missing file or missing keys raise."""
+    """Model of config.model_name with the checkpoint's weights; a missing file or missing keys raise.  `ckpt` may name several files,
+    `a.model,b.model,c.model` (or a list): their mean (asr_chinese_e2e_amd.averaging.average_state_dicts), taken in memory."""
     Model, _ = get_model_class(config.model_name)
-    if not ckpt or not os.path.isfile(ckpt):
-        raise SystemExit(f"transcribe.py: checkpoint not found: {ckpt!r}")
-    state = torch.load(ckpt, map_location="cpu", weights_only=True)
+    paths = [p for p in (ckpt if isinstance(ckpt, (list, tuple)) else str(ckpt or "").split(",")) if p]
+    for p in paths or [ckpt]:
+        if not p or not os.path.isfile(p):
+            raise SystemExit(f"transcribe.py: checkpoint not found: {p!r}")
+    if len(paths) > 1:
+        from asr_chinese_e2e_amd.averaging import average_state_dicts
+        state, ckpt = average_state_dicts(paths), ",".join(paths)
+    else:
+        ckpt = paths[0]
+        state = torch.load(ckpt, map_location="cpu", weights_only=True)
     model = Model(config, vocab)
     missing, unexpected = model.load_state_dict(state, strict=False)
     if missing:
