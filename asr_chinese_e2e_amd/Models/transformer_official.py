@@ -845,16 +845,34 @@ class _SpeechTransformer(BaseModel):
         from ..consensus import model_consensus
         return model_consensus(self, input, search=search, beam_size=beam_size, nbest=nbest, posterior_scale=posterior_scale, alts=alts, **search_kwargs)
 
-    def evaluate(self, batches, search="transcribe", nbest=1, scorer=None, consensus=False, posterior_scale=1.0, **search_kwargs):
+    def rescore(self, input, weights, search="attention_beam", beam_size=5, nbest=5, lm=None, **search_kwargs):
+        """The n-best lists of a batch re-ranked by a weighted sum of scores (rescore.rescore): weights = {column: w} over the scores the
+        search reports ("ctc_score", "att_score", "bias", "lm_score", "score"), "lm" (the n-gram LM score of the finished string, all entries
+        in one launch of asr_lm_score_nbest; lm= an NgramLM compiled with weight=1.0, ins=0.0) and "len" (the token count).  Returns the
+        lists re-ordered, every entry a copy with "score" = its total (-inf: unscorable), "first_rank" and "lm" / "len" where used."""
+        from ..rescore import model_rescore
+        return model_rescore(self, input, weights, search=search, beam_size=beam_size, nbest=nbest, lm=lm, **search_kwargs)
+
+    def tune(self, batches, grid, search="attention_beam", beam_size=10, nbest=10, lm=None, **search_kwargs):
+        """The error counts of every point of a rescore.Grid of weight vectors over a dev set: every pack goes through the search once, its
+        entries through asr_edit_align (counts only) and asr_nbest_sweep.  Returns a rescore.SweepResult (cer, ser, best, best_weights,
+        rank0_cer, oracle_cer, save)."""
+        from ..rescore import model_tune
+        return model_tune(self, batches, grid, search=search, beam_size=beam_size, nbest=nbest, lm=lm, **search_kwargs)
+
+    def evaluate(self, batches, search="transcribe", nbest=1, scorer=None, consensus=False, posterior_scale=1.0, rescore=None, rescore_lm=None, **search_kwargs):
         """Token-level scoring of a test set (scoring.evaluate): every pack of `batches` (what the loader yields) goes through `search` -
         "transcribe" (1-best; transcribe(pack, timestamps=False, **search_kwargs), so joint=, context=, lm=, blank_skip= pass through),
         "ctc_prefix_beam" (ctc_prefix_beam_search(pack, beam_size, nbest, ...)) or "attention_beam" (beam_search(pack, beam_size, nbest,
         ...)) - and its hypotheses are aligned on the device (asr_edit_align) against the gold ids cal_metrics scores against.  Returns the
         scoring.Scorer (a new one, or `scorer` with the batches added): summary() has the corpus CER with its substitutions, deletions and
         insertions, the sentence error rate and, with nbest > 1, the oracle CER of the lists.  consensus=True (the two n-best searches):
-        also mbr_cer, consensus_cer and mbr_rank_hist, from consensus.consensus_ids over the lists with their scores and posterior_scale."""
+        also mbr_cer, consensus_cer and mbr_rank_hist, from consensus.consensus_ids over the lists with their scores and posterior_scale.
+        rescore={column: w} (the two n-best searches; rescore_lm= the NgramLM of a column "lm"): the lists are re-ranked by self.rescore's
+        rule first, so the scores are those of the rescored rank 0 and a consensus sees the new totals."""
         from ..scoring import evaluate
-        return evaluate(self, batches, search=search, nbest=nbest, scorer=scorer, consensus=consensus, posterior_scale=posterior_scale, **search_kwargs)
+        return evaluate(self, batches, search=search, nbest=nbest, scorer=scorer, consensus=consensus, posterior_scale=posterior_scale, rescore=rescore,
+                        rescore_lm=rescore_lm, **search_kwargs)
 
     def _hyp_dicts(self, ids, scores, timestamps, ctc_logits, wave_len, biases=None, bias_key="bias", confidence=None):
         """transcribe's result dicts for the best ids / score of each utterance; ctc_logits() -> (B, T, V) is called for timestamps only.

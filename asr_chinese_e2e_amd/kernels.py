@@ -1901,3 +1901,82 @@ def nbest_consensus(tok, ln, weights, host_len, host_weights, alts=4, out=None, 
     check(getattr(lib, NBEST_STAGES[stage])(_p(tok) if one is None else _p(one), _p(ln), _p(weights), L, ldn, ldu, hl.ctypes.data, hw.ctypes.data, U, N,
                                             int(alts), _p(out), words * 4, _stream()), NBEST_STAGES[stage])
     return out
+
+
+# ------------------------------------------------------------------------------------------------ rescoring of n-best lists (csrc/rescore.hip)
+RESCORE_MAX_N, RESCORE_MAX_K, RESCORE_MAX_G, RESCORE_MAX_U = _lib.RESCORE_MAX_N, _lib.RESCORE_MAX_K, _lib.RESCORE_MAX_G, _lib.RESCORE_MAX_U
+
+
+def lm_score_nbest(tok, ln, host_len, lm, out=None):
+    """The n-gram LM score of P finished strings in one launch (asr_lm_score_nbest; the definition is lm.NgramLM.score / walk, and the
+    kernel agrees with them bit for bit).  tok (P, ld) int32 ids with unit column stride, ln (P) int32 on the device, -1 = absent; host_len:
+    ln on the host (a list or numpy), by which the launcher refuses before the launch.  Returns (score (P) float64 = lm.score, bias (P)
+    float64 and state (P) int32 = lm.walk, ntok (P) int32); an absent entry gives (0.0, 0.0, -1, 0).  out: a contiguous int32 buffer of
+    6 P words, 8-byte aligned, to write into [score | bias | state | ntok] (one copy brings everything back)."""
+    _chk_i32(ln, out)
+    if tok.dtype != torch.int32 or tok.dim() != 2 or (tok.shape[1] > 0 and tok.stride(1) != 1):
+        raise ValueError("lm_score_nbest: tok must be a 2-D int32 tensor with unit column stride")
+    P_, L = tok.shape
+    ld = tok.stride(0) if P_ > 1 and L > 0 else L
+    hl = np.ascontiguousarray(np.asarray(host_len, dtype=np.int32).reshape(-1))
+    if ln.numel() != P_ or hl.shape[0] != P_:
+        raise ValueError(f"lm_score_nbest: {ln.numel()} lengths and {hl.shape[0]} host lengths for {P_} hypotheses")
+    if P_ < 1:
+        raise ValueError("lm_score_nbest: no hypotheses")
+    dev = tok.device
+    if out is None:
+        out = torch.empty(6 * P_, dtype=torch.int32, device=dev)
+    if out.numel() != 6 * P_:
+        raise ValueError(f"lm_score_nbest: out must hold {6 * P_} words")
+    score, bias = out[:2 * P_].view(torch.float64), out[2 * P_:4 * P_].view(torch.float64)
+    state, ntok = out[4 * P_:5 * P_], out[5 * P_:]
+    one = torch.zeros(1, dtype=torch.int32, device=dev) if tok.numel() == 0 else None      # an empty tensor has no storage to point at
+    check(lib.asr_lm_score_nbest(_p(tok) if one is None else _p(one), _p(ln), hl.ctypes.data, P_, ld, ctypes.addressof(lm.on(dev)[1]), int(lm.has_eos),
+                                 int(lm.eos), _p(score), _p(bias), _p(state), _p(ntok), _stream()), "asr_lm_score_nbest")
+    return score, bias, state, ntok
+
+
+def nbest_sweep_workspace_bytes(U, N, K, G):
+    """Bytes of nbest_sweep's workspace (asr_nbest_sweep_workspace_bytes); raises for a shape the launcher would refuse."""
+    nbytes = int(lib.asr_nbest_sweep_workspace_bytes(int(U), int(N), int(K), int(G)))
+    if not nbytes:
+        raise ValueError(f"nbest_sweep: {_lib.last_error()}")
+    return nbytes
+
+
+def nbest_sweep(feat, ln, err, grid, host_feat, host_len, host_grid, totals=False, ws=None, out_pick=None, out_tot=None, out_total=None):
+    """The sweep of G weight vectors over U lists of N entries with K features (asr_nbest_sweep; the definition is tests/rescore_ref.py).
+    feat (K, N, U) float64, ln (N, U) int32 (-1 = absent), err (3, N, U) int32 (sub, del, ins of every entry), grid (G, K) float64:
+    contiguous device tensors; host_feat / host_len / host_grid: numpy arrays of the same layouts, by which the launcher refuses before any
+    launch.  Returns (pick (G, U) int32, tot (G, 4) int64 = summed sub, del, ins and wrong utterances of the picks, total (G, U, N) float64
+    with totals=True - the total of every present, scorable entry, -inf for the others - else None).  ws: a Workspace."""
+    _chk_i32(ln, err, out_pick)
+    for t, name in ((feat, "feat"), (grid, "grid"), (out_total, "out_total")):
+        if t is not None and (t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError(f"nbest_sweep: {name} must be a contiguous float64 tensor")
+    if feat.dim() != 3 or grid.dim() != 2:
+        raise ValueError("nbest_sweep: feat is (K, N, U) and grid (G, K)")
+    K_, N, U_ = feat.shape
+    G = grid.shape[0]
+    if grid.shape[1] != K_ or tuple(ln.shape) != (N, U_) or tuple(err.shape) != (3, N, U_):
+        raise ValueError(f"nbest_sweep: grid {tuple(grid.shape)}, len {tuple(ln.shape)} and err {tuple(err.shape)} for feat {tuple(feat.shape)}")
+    hf = np.ascontiguousarray(np.asarray(host_feat, dtype=np.float64))
+    hl = np.ascontiguousarray(np.asarray(host_len, dtype=np.int32))
+    hg = np.ascontiguousarray(np.asarray(host_grid, dtype=np.float64))
+    if hf.shape != (K_, N, U_) or hl.shape != (N, U_) or hg.shape != (G, K_):
+        raise ValueError("nbest_sweep: the host mirrors must have the device arrays' shapes")
+    nbytes = nbest_sweep_workspace_bytes(U_, N, K_, G)
+    dev = feat.device
+    w = ws.get(nbytes) if ws is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if out_pick is None:
+        out_pick = torch.empty(G, U_, dtype=torch.int32, device=dev)
+    if out_tot is None:
+        out_tot = torch.empty(G, 4, dtype=torch.int64, device=dev)
+    if totals and out_total is None:
+        out_total = torch.empty(G, U_, N, dtype=torch.float64, device=dev)
+    if out_pick.numel() != G * U_ or out_tot.dtype != torch.int64 or not out_tot.is_contiguous() or out_tot.numel() != G * 4 or \
+            (out_total is not None and out_total.numel() != G * U_ * N):
+        raise ValueError(f"nbest_sweep: out_pick holds {G} x {U_} int32, out_tot {G} x 4 int64 and out_total {G} x {U_} x {N} float64")
+    check(lib.asr_nbest_sweep(_p(feat), _p(ln), _p(err), _p(grid), hf.ctypes.data, hl.ctypes.data, hg.ctypes.data, U_, N, K_, G, _p(out_pick), _p(out_tot),
+                              _p(out_total), _p(w), w.numel(), _stream()), "asr_nbest_sweep")
+    return out_pick, out_tot, out_total

@@ -238,10 +238,12 @@ class Scorer:
             f.write(json.dumps({"summary": self.summary()}, ensure_ascii=False) + "\n")
 
 
-def evaluate(model, batches, search="transcribe", nbest=1, scorer=None, consensus=False, posterior_scale=1.0, **search_kwargs):
+def evaluate(model, batches, search="transcribe", nbest=1, scorer=None, consensus=False, posterior_scale=1.0, rescore=None, rescore_lm=None, **search_kwargs):
     """model.evaluate: every batch of `batches` through one of the model's searches, its hypotheses scored against the batch's gold ids
     (dec_preprocess of tgt_for_input: what cal_metrics scores against).  Returns the Scorer.  consensus=True (the n-best searches): the
-    lists' scores go to Scorer.add with posterior_scale, so the summary also has mbr_cer, consensus_cer and mbr_rank_hist."""
+    lists' scores go to Scorer.add with posterior_scale, so the summary also has mbr_cer, consensus_cer and mbr_rank_hist.
+    rescore={column: w} (the n-best searches; rescore_lm: the NgramLM of a column "lm"): every list is re-ordered by rescore.rescore before
+    anything is scored, so rank 0 is the rescored pick and a consensus sees the new totals as its scores."""
     import torch
 
     from . import kernels as K
@@ -257,6 +259,11 @@ def evaluate(model, batches, search="transcribe", nbest=1, scorer=None, consensu
             raise ValueError(f"nbest = {nbest}: consensus takes lists of at most {MAX_N} entries")
         if not np.isfinite(float(posterior_scale)) or float(posterior_scale) <= 0.0:
             raise ValueError(f"posterior_scale must be finite and > 0 (got {posterior_scale})")
+    if rescore is not None:
+        from .rescore import _filled, rescore as rescore_lists
+        if search == "transcribe":
+            raise ValueError("rescore= needs an n-best search: search='ctc_prefix_beam' or 'attention_beam'")
+        rescore = dict(rescore)
     scorer = Scorer(model.vocab) if scorer is None else scorer
     kw = dict(search_kwargs)
     beam = kw.pop("beam_size", 5)
@@ -271,6 +278,8 @@ def evaluate(model, batches, search="transcribe", nbest=1, scorer=None, consensu
             else:
                 fn = model.ctc_prefix_beam_search if search == "ctc_prefix_beam" else model.beam_search
                 found = fn(pack, beam, int(nbest), **kw)
+                if rescore is not None:
+                    found = rescore_lists(_filled(found), rescore, lm=rescore_lm, device=pack.wave.device)
                 lists = [[list(h["yseq"]) for h in utt] for utt in found]
                 for utt in lists:      # the attention searches spell sos ... eos
                     for i, seq in enumerate(utt):

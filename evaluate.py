@@ -15,6 +15,10 @@ Model flags are train.py's (same parser and loading as transcribe.py).  Scoring 
   --consensus      1: the lists also go through consensus decoding (asr_chinese_e2e_amd/consensus.py) with the search's scores as the
                    posterior; the summary gains mbr_cer (the minimum-Bayes-risk entry), consensus_cer (the voted string) and mbr_rank_hist
   --posterior_scale   the scores are multiplied by it before the softmax that makes the weights (1.0)
+  --rescore        a file tune.py wrote (or a JSON object {column: weight}): every n-best list is re-ranked by the weighted sum of its
+                   columns before it is scored (asr_chinese_e2e_amd/rescore.py; ctc_prefix_beam or attention_beam).  If the weights name
+                   the column "lm", --lm is the rescoring LM (an ARPA file, compiled with weight 1 and no insertion bonus, or an .npz
+                   saved so) and is not forwarded to the search
   --joint, --blank_skip, --context, --context_score, --lm, --lm_weight, --lm_ins     forwarded to the search, as transcribe.py's
   --frame_topk     candidates per frame of ctc_prefix_beam (10)
   --out            a JSONL file: one line per utterance with its alignment spelled in tokens, then the summary
@@ -42,7 +46,7 @@ from train import TrainConfig, get_model_class, parse_flags  # noqa: E402
 from transcribe import cmvn_path, load_model  # noqa: E402
 
 CLI_KEYS = ("ckpt", "manifest", "search", "beam_size", "nbest", "joint", "blank_skip", "context", "context_score", "lm", "lm_weight", "lm_ins", "frame_topk",
-            "out", "top", "cmvn", "frontend", "resample", "batch_size", "consensus", "posterior_scale")
+            "out", "top", "cmvn", "frontend", "resample", "batch_size", "consensus", "posterior_scale", "rescore")
 SEARCHES = ("transcribe", "ctc_prefix_beam", "attention_beam")
 
 
@@ -93,7 +97,32 @@ def eval_options(cli):
     if not np.isfinite(scale) or scale <= 0.0:
         raise SystemExit(f"evaluate.py: --posterior_scale must be a finite number above 0 (got {cli.get('posterior_scale')!r})")
     num["posterior_scale"] = scale
+    if cli.get("rescore") not in (None, "", False) and search == "transcribe":
+        raise SystemExit("evaluate.py: --rescore needs --search=ctc_prefix_beam or attention_beam (it re-ranks an n-best list)")
     return search, num
+
+
+def rescore_options(cli, vocab, V):
+    """(weights, the rescoring LM or None) of --rescore; an --lm the weights use is taken out of cli, so the search does not get it."""
+    if cli.get("rescore") in (None, "", False):
+        return None, None
+    from asr_chinese_e2e_amd.rescore import load_weights
+    try:
+        weights = load_weights(str(cli["rescore"]))
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"evaluate.py: --rescore: {e}") from e
+    lm = None
+    if "lm" in weights:
+        from asr_chinese_e2e_amd.lm import NgramLM
+        path = cli.pop("lm", None)
+        if path in (None, "", False):
+            raise SystemExit("evaluate.py: the weights of --rescore name the column 'lm': give --lm=<ARPA file or .npz compiled with weight 1, ins 0>")
+        try:
+            lm = NgramLM.load(str(path), device="cuda") if str(path).endswith(".npz") else NgramLM.from_arpa(str(path), vocab, weight=1.0, ins=0.0, device="cuda")
+            lm.check_vocab(V)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"evaluate.py: --lm: {e}") from e
+    return weights, lm
 
 
 def manifest_batches(entries, vocab, parser, bs, sample_rate, resample):
@@ -188,7 +217,10 @@ def evaluate(**flags):
     model = load_model(config, vocab, cli.get("ckpt"))
     parser = AudioParser(sample_rate=config.sample_rate, n_mels=config.n_mels, window_size=config.window_size,
                          lfr_m=config.lfr_m, lfr_n=config.lfr_n, frontend=str(cli.get("frontend", "reference")), **parser_norm(cmvn_path(cli)))
+    weights, rescore_lm = rescore_options(cli, vocab, model.V)
     kw = search_options(cli, model, vocab, search)
+    if weights is not None:
+        kw.update(rescore=weights, rescore_lm=rescore_lm)
     batches = manifest_batches(entries, vocab, parser, num["batch_size"], config.sample_rate, bool(int(cli.get("resample", 0) or 0)))
     try:
         scorer = model.evaluate(batches, search=search, nbest=num["nbest"], beam_size=num["beam_size"], consensus=bool(num["consensus"]),

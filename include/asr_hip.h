@@ -1365,6 +1365,49 @@ int asr_nbest_slot_vote(const int32_t* tok, const int32_t* len, const int32_t* w
 int asr_nbest_consensus(const int32_t* tok, const int32_t* len, const int32_t* weights, int L, int ldn, int ldu, const int32_t* host_len,
                         const int32_t* host_weights, int U, int N, int A, int32_t* out, size_t out_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Rescoring of n-best lists: the n-gram LM score of many finished strings in one launch, and the sweep of a grid of weight vectors over
+ * lists of feature vectors (additive to ABI 10; csrc/rescore.hip, asr_chinese_e2e_amd/rescore.py).
+ * Stands in for:  nothing in the reference.  The definition is tests/rescore_ref.py on top of lm.py::NgramLM's host methods; the kernels
+ *                 agree with it in integers and float bits, with no tolerance.
+ *
+ * asr_lm_score_nbest: P hypotheses, tok (P rows, ld apart) int32 ids and len (P) int32 on the device, -1 = absent; host_len is a host copy
+ *   of len, by which the launcher refuses.  One lane per hypothesis walks its tokens from (lm->start, 0.0) with the statements of the
+ *   prefix beam search's LM step (bias += st_bow per state left, += the term found, += ins; asr_ngram_lm above), then adds the
+ *   end-of-sentence chain for token `eos` without ins if has_eos != 0 (NgramLM.final; has_eos / eos are arguments, not fields of
+ *   asr_ngram_lm).  out_score (P) fp64 = NgramLM.score, out_bias (P) fp64 and out_state (P) = NgramLM.walk, out_ntok (P) = the token
+ *   count, bit for bit: the device only adds fp64 table terms in the host's order.  An absent entry gives (0.0, 0.0, -1, 0).  A token id
+ *   is an index only into the V-sized unigram tables, clamped to [0, V) there as the host clamps it; every other table index is clamped too.
+ *   Refused before any launch (ASR_EINVAL): null or misaligned pointers (fp64: 8 bytes), P <= 0, ld < 0, a host length below -1 or
+ *   above ld, and what the LM searches refuse of an asr_ngram_lm.
+ *
+ * asr_nbest_sweep: U lists of N entries with K features each, G weight vectors.  feat (K, N, U) fp64 planes, len (N, U) int32 (-1 =
+ *   absent), err (3, N, U) int32 = every entry's (sub, del, ins) against its reference, grid (G, K) fp64, all on the device with the
+ *   utterance as the unit-stride index; host_feat / host_len / host_grid are host copies in the same layouts, by which the launcher refuses.
+ *   The total of an entry under w: total = 0.0; for k ascending, if w[k] != 0.0: total = total + (w[k] * f[k]) - the product rounded,
+ *   then the sum, never fused; a term of weight 0.0 is skipped, so 0 * -inf never happens.  An entry is unscorable under w if some f[k]
+ *   with w[k] != 0.0 is not finite.  The pick of (g, u) is the present, scorable entry of greatest total, the lowest index on ties; the
+ *   present entry of lowest index if none is scorable.
+ *   out_pick (G, U) int32; out_tot (G, 4) int64 = the picks' summed sub, del, ins and the number of utterances whose pick has
+ *   sub + del + ins > 0; out_total (G, U, N) fp64 or NULL: every present, scorable entry's total, -inf for the others.
+ *   One wave per (grid point, 64 utterances) writes its partial counts into ws (asr_nbest_sweep_workspace_bytes(U, N, K, G) bytes,
+ *   8-aligned); a second launch sums them.  Integers and no atomics: two runs write the same bytes.
+ *   Refused before any launch (ASR_EINVAL; ASR_EWORKSPACE for the last): null or misaligned pointers, U outside [1, ASR_RESCORE_MAX_U],
+ *   N outside [1, ASR_RESCORE_MAX_N], K outside [1, ASR_RESCORE_MAX_K], G outside [1, ASR_RESCORE_MAX_G], a non-finite weight, a NaN or
+ *   +inf feature, an utterance with no present entry, a workspace below the size query's answer.  The kernel treats a non-finite
+ *   feature as unscorable and clamps the pick all the same.
+ */
+#define ASR_RESCORE_MAX_N 64
+#define ASR_RESCORE_MAX_K 8
+#define ASR_RESCORE_MAX_G 65536
+#define ASR_RESCORE_MAX_U 1048576
+int asr_lm_score_nbest(const int32_t* tok, const int32_t* len, const int32_t* host_len, int P, int ld, const asr_ngram_lm* lm, int has_eos, int eos,
+                       double* out_score, double* out_bias, int32_t* out_state, int32_t* out_ntok, void* stream);
+size_t asr_nbest_sweep_workspace_bytes(int U, int N, int K, int G);
+int asr_nbest_sweep(const double* feat, const int32_t* len, const int32_t* err, const double* grid, const double* host_feat,
+                    const int32_t* host_len, const double* host_grid, int U, int N, int K, int G, int32_t* out_pick, int64_t* out_tot,
+                    double* out_total, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
