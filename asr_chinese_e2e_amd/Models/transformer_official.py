@@ -21,6 +21,10 @@ Additions required by BASELINE.json's north_star (not in the reference):
   * config.ema_decay in [0, 1) / ema_warmup: an exponential moving average of the parameters kept beside them in the flat buffers and
     updated inside the fused Adam pass (include/asr_hip.h: asr_adam_ema_step); ema_state_dict() / save_ema() / load_ema() / ema_weights().
     0 (the default) allocates nothing and launches what was launched without it.
+  * config.mwer_weight > 0 (TransformerCTC only) / mwer_nbest / mwer_beam / mwer_frame_topk / mwer_blank_skip: MWER training - the step's
+    loss gains mwer_weight * the mean over the batch of the expected number of errors over the model's own n-best list (the device
+    prefix beam search on the step's logits; include/asr_hip.h: asr_ctc_mwer_lattice, engine.ctc_fwd_bwd), metrics gains `mwer`;
+    model.mwer_risk(pack) reports the same figures without a gradient.  0 (the default) launches what was launched without it.
 """
 import contextlib
 import math
@@ -36,6 +40,27 @@ from ..Utils import Pack
 SOS_ID, EOS_ID, PAD_ID = 2, 3, 0   # transformer_official.py:53-54, Utils/loss.py:5
 PE_MAXLEN = 5000                   # transformer_official.py:49, 65
 CLIP_NORM = 5.0                    # transformer_official.py:102
+
+
+def mwer_settings(weight, nbest, beam, frame_topk, blank_skip):
+    """The MWER keys as the engine takes them: (weight, dict(nbest, beam, frame_topk, thr)); ValueError for what the device search or the
+    lattice kernels would refuse - before anything is launched."""
+    try:
+        ok = not isinstance(weight, (bool, str)) and math.isfinite(float(weight)) and float(weight) >= 0.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"mwer_weight={weight!r}: a finite number >= 0 (0 = no MWER term)")
+    for name, v in (("mwer_nbest", nbest), ("mwer_beam", beam), ("mwer_frame_topk", frame_topk)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name}={v!r}: an integer")
+    nbest, beam, frame_topk = int(nbest), int(beam), int(frame_topk)
+    if beam < 2 or beam > K.MWER_MAX_N or not 2 <= nbest <= beam:
+        raise ValueError(f"mwer_nbest={nbest} must lie in [2, mwer_beam] and mwer_beam={beam} in [2, {K.MWER_MAX_N}]")
+    if frame_topk < 1 or beam * (frame_topk + 1) > 64:
+        raise ValueError(f"the device search ranks mwer_beam * (mwer_frame_topk + 1) <= 64 candidates per frame (beam {beam}, frame_topk {frame_topk})")
+    thr = None if blank_skip is None else K.blank_skip_threshold(blank_skip)
+    return float(weight), dict(nbest=nbest, beam=beam, frame_topk=frame_topk, thr=thr)
 
 
 def _set_nested(root, dotted, value, is_buffer=False):
@@ -93,6 +118,11 @@ class _SpeechTransformer(BaseModel):
         self._ema_step = 0           # steps counted here for optimizers that keep no _step of their own
         self._ema_active = False     # inside ema_weights(): p holds the average, ema the raw parameters
         self._ema_pending = None     # an average loaded (load_ema) before the flat buffers existed
+        self.mwer_weight, self._mwer = mwer_settings(getattr(c, "mwer_weight", 0.0), getattr(c, "mwer_nbest", 4), getattr(c, "mwer_beam", 4),
+                                                     getattr(c, "mwer_frame_topk", 7), getattr(c, "mwer_blank_skip", None))
+        self._mwer_mean = None       # the mean risk of the last training step (device scalar), None without the MWER term
+        if self.mwer_weight > 0.0 and self.use_decoder:
+            raise ValueError("mwer_weight > 0 needs the CTC-only model (TransformerCTC): MWER through the attention decoder is not implemented")
         d, H, dk, ff = c.d_model, c.num_head, c.hidden_size, c.ff_size
         d_in = c.n_mels * c.lfr_m
         V = vocab.vocab_size
@@ -223,6 +253,7 @@ class _SpeechTransformer(BaseModel):
             b.data = b.data.to(device)
         pe = self.encoder.positional_encoding.pe[0].to(device).contiguous()
         self._engine = E.Engine(f, self.config, self.V, self.use_decoder, self.use_ctc, pe)
+        self._engine.mwer = dict(self._mwer) if self.mwer_weight > 0.0 else None
         self._flat_device = device
         self._views_checked = True
         self._grads_checked = True
@@ -938,7 +969,10 @@ class _SpeechTransformer(BaseModel):
             # CTC-only model: the step's CER (the reference's trainer reads metrics.cer every step, Trainer/trainer11.py:73-75) is scored on the
             # greedy CTC path, which the loss kernels hand out (the gradient overwrites the logits in place)
             path = torch.empty(B, T, dtype=torch.int32, device=enc.device) if (self.cer_in_iterate and not self.use_decoder) else None
-            nll, d_enc = eng.ctc_fwd_bwd(enc, wave_len, labels32, lab_len, B, T, best_path=path, **ctc_scale)
+            mwer = {}
+            if self.mwer_weight > 0.0:      # scaled as the CTC term is: by the batch, or by the global batch on the device
+                mwer = dict(mwer_grad_scale=self.mwer_weight * loss_scale / (1.0 if batch_div is not None else float(B)))
+            nll, d_enc = eng.ctc_fwd_bwd(enc, wave_len, labels32, lab_len, B, T, best_path=path, **ctc_scale, **mwer)
             if path is not None:      # collapse the greedy path and score it against the label strings, as cal_metrics does for a CTC-only model
                 def score():
                     ids, lens = K.ctc_collapse(path, wave_len, PAD_ID)
@@ -952,7 +986,50 @@ class _SpeechTransformer(BaseModel):
                 pg = self._cer_beside_backward(eng, lambda: self._cer_ids(ids, ys_out), pg, inline=lambda: pg)      # inline: (ids, gold), scored by _cer_of
         eng.encoder_bwd(ecache, d_enc)
         loss = K.loss_combine(row_nll, n_valid, nll, (1.0 - lam) if self.use_ctc else 1.0, lam)
+        self._mwer_mean = None
+        if self.mwer_weight > 0.0 and self.use_ctc and not ctc_async:
+            # the MWER term beside the combined loss: mwer_weight * the mean risk of the batch (no device-to-host copy, no sync)
+            risk = eng.last_mwer[4]
+            self._mwer_mean = risk.sum() / (batch_div[0] if batch_div is not None else float(B))
+            loss = loss.clone()
+            loss[0] += self.mwer_weight * self._mwer_mean
         return loss, pg
+
+    def mwer_risk(self, input, nbest=None, beam_size=None, frame_topk=None, blank_skip=None):
+        """The figures MWER training lowers, without a gradient: per utterance {"risk": the expected number of errors over the n-best list
+        of the device prefix beam search, "errors": the entries' distances to the transcript, "posteriors": their share of the list's
+        probability (0 for an entry that does not take part), "nbest": the id lists}.  The defaults are the config's mwer_* keys.
+        Evaluation mode (no dropout); the definition is tests/mwer_ref.py on ctc_prefix_beam_search's lists."""
+        d = self._mwer
+        _, m = mwer_settings(0.0, d["nbest"] if nbest is None else nbest, d["beam"] if beam_size is None else beam_size,
+                             d["frame_topk"] if frame_topk is None else frame_topk, blank_skip)
+        if blank_skip is None:
+            m["thr"] = d["thr"]
+        if self.use_decoder or not self.use_ctc:
+            raise ValueError("mwer_risk needs the CTC-only model (TransformerCTC)")
+        eng = self._ensure_engine(input.wave.device)
+        was_training, eng.training = eng.training, False
+        try:
+            with torch.no_grad():
+                out = self.forward(input)
+        finally:
+            eng.training = was_training
+        logits = out.ctc_logits.contiguous()
+        B, T, V = logits.shape
+        wave_len = input.wave_len.to(torch.int32).contiguous()
+        prep = K.dec_preprocess(input.tgt_for_input.contiguous(), SOS_ID, EOS_ID)
+        labels32, lab_len = prep[2], prep[4]
+        vals, ids, blank_lp = K.ctc_frame_topk(logits.view(B * T, V), min(m["frame_topk"], V), PAD_ID)
+        search_len = wave_len
+        if m["thr"] is not None:
+            vals, ids, blank_lp, search_len, _ = K.ctc_blank_skip_compact(vals, ids, blank_lp, wave_len, m["thr"], B, T)
+        Lh = min(T, K.MWER_MAX_LEN, 2 * labels32.shape[1] + 8)
+        tok, ln, _ = K.ctc_prefix_beam(vals, ids, blank_lp, search_len, B, T, m["beam"], m["nbest"], PAD_ID, max_len=Lh)
+        res = K.ctc_mwer(logits, wave_len, tok, ln, labels32, lab_len, blank=PAD_ID, want_grad=False)
+        tok, ln, err, post, risk = (t.cpu().tolist() for t in (tok, ln, res["err"], res["post"], res["risk"]))
+        return [{"risk": risk[b], "errors": [err[b][r] for r in range(m["nbest"]) if ln[b][r] >= 0],
+                 "posteriors": [post[b][r] for r in range(m["nbest"]) if ln[b][r] >= 0],
+                 "nbest": [tok[b][r][:min(ln[b][r], Lh)] for r in range(m["nbest"]) if ln[b][r] >= 0]} for b in range(B)]
 
     def iterate(self, input, optimizer=None, is_train=True):
         """transformer_official.py:96-104: forward, metrics, and - when training - zero_grad,
@@ -986,6 +1063,8 @@ class _SpeechTransformer(BaseModel):
             metrics.add(ce=loss[1], ctc=loss[2])
         if pg is not None:
             metrics.add(cer=self._cer_of(pg))                 # no device-to-host copy, no sync
+        if getattr(self, "_mwer_mean", None) is not None:
+            metrics.add(mwer=self._mwer_mean)                 # the mean risk of the batch, in errors per utterance
         return metrics, None
 
     def greedy_search(self, input, decode_max_len=0):
@@ -1013,6 +1092,11 @@ class _SpeechTransformer(BaseModel):
             decoding_left_chunks = None     # None = left_chunks when the chunk is static, else -1
             ema_decay = 0.0                 # > 0: keep an exponential moving average of the parameters with this decay (0 = off, nothing allocated)
             ema_warmup = True               # the decay of step s is min(ema_decay, (1 + s) / (10 + s))
+            mwer_weight = 0.0               # > 0 (TransformerCTC): the loss gains mwer_weight * mean expected errors over the model's own n-best list
+            mwer_nbest = 4                  # entries of the list, in [2, mwer_beam]
+            mwer_beam = 4                   # beam of the device prefix beam search that makes the list
+            mwer_frame_topk = 7             # classes per frame the search looks at: mwer_beam * (mwer_frame_topk + 1) <= 64
+            mwer_blank_skip = None          # a probability in (0, 1]: blank-frame skipping in front of that search
 
         return ModelConfig
 

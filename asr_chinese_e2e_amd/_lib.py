@@ -35,6 +35,7 @@ EDIT_LDS_DIR_BYTES, EDIT_MAX_REF = 98304, 16384      # ASR_EDIT_*: direction mas
 EDIT_COR, EDIT_SUB, EDIT_DEL, EDIT_INS = 0, 1, 2, 3      # ASR_EDIT_COR .. ASR_EDIT_INS: the op codes of asr_edit_align
 NBEST_MAX_N, NBEST_MAX_LEN, NBEST_MAX_ALTS, NBEST_EPS = 64, 256, 8, -1      # ASR_NBEST_*: entries per list, tokens per entry, alternatives per slot, "no token"
 RESCORE_MAX_N, RESCORE_MAX_K, RESCORE_MAX_G, RESCORE_MAX_U = 64, 8, 65536, 1 << 20      # ASR_RESCORE_*: entries per list, feature columns, grid points, lists of asr_nbest_sweep
+MWER_MAX_N, MWER_MAX_LEN, MWER_ABSENT, MWER_LONG = 16, 255, 1, 2      # ASR_MWER_*: entries per list, tokens per entry / reference, the flags of asr_mwer_errors
 STREAM_OPEN = 0x3fffffff     # ASR_STREAM_OPEN: "length not known yet" in the streaming front end's parameter arrays
 
 P, I, F, Z, U = c_void_p, c_int, c_float, c_size_t, c_uint32
@@ -221,6 +222,10 @@ SIGNATURES = {
     "asr_lm_score_nbest": (I, [P, P, P, I, I, P, I, I, P, P, P, P, P]),
     "asr_nbest_sweep_workspace_bytes": (Z, [I, I, I, I]),
     "asr_nbest_sweep": (I, [P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, Z, P]),
+    "asr_ctc_mwer_workspace_bytes": (Z, [I, I, I, I]),
+    "asr_mwer_errors": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "asr_ctc_mwer_lattice": (I, [P] * 10 + [I] * 9 + [P, Z, I, P]),
+    "asr_ctc_mwer_grad": (I, [P, P, P, P, P] + [I] * 9 + [F, P, I, P, Z, I, P]),
 }
 
 

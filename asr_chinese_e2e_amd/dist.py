@@ -268,6 +268,8 @@ class DataParallel:
             metrics.add(loss=loss[0])
             if cer is not None:
                 metrics.add(cer=cer)
+            if getattr(model, "_mwer_mean", None) is not None:      # config.mwer_weight > 0: this rank's risks over the GLOBAL batch
+                metrics.add(mwer=model._mwer_mean)
             return metrics, None
         # CE was normalised by the GLOBAL token count (sum over ranks = global CE); the CTC term the kernel reports is
         # the mean over the LOCAL batch: weight it by local / global batch before the sum over ranks
@@ -283,4 +285,6 @@ class DataParallel:
         metrics.add(loss=total)
         if cer is not None:
             metrics.add(cer=cer)
+        if getattr(model, "_mwer_mean", None) is not None:      # rank-local, as above; the reduced loss is CE / CTC only (the MWER term is not summed over ranks)
+            metrics.add(mwer=model._mwer_mean)
         return metrics, None

@@ -578,6 +578,11 @@ class Engine:
         self.side = shared_stream(flat.device, "wgrad")      # first: the stream the step depends on most gets the first pick
         self.ctc_stream = shared_stream(flat.device, "aux")
         self.ws_ctc = K.Workspace(flat.device)
+        # the MWER stage of ctc_fwd_bwd: dict(nbest, beam, frame_topk, thr) while config.mwer_weight > 0 (the model validates the keys and
+        # sets it, Models/transformer_official.py), else None - and then ctc_fwd_bwd launches exactly what it launches without the feature
+        self.mwer = None
+        self.ws_mwer = K.Workspace(flat.device)
+        self.last_mwer = None       # (tok, len, err, post, risk) of the last MWER step, device tensors
         self._side_handle = self.side.cuda_stream
         # ---- environment switches of the engine (all read here, when the engine is built; the complete list is in README.md):
         # ASR_WGRAD_OVERLAP=0: ONE stream - weight gradients, the CTC branch and the cross-attention K|V work stay on the main stream
@@ -1040,19 +1045,40 @@ class Engine:
         self._keep += (enc, wave_len, labels32, lab_len, nll, d_enc)
         return nll, d_enc, done
 
-    def ctc_fwd_bwd(self, enc, wave_len, labels32, lab_len, B, T, grad_scale, want_grad=True, grad_scale_div=None, ws=None, best_path=None):
+    def ctc_fwd_bwd(self, enc, wave_len, labels32, lab_len, B, T, grad_scale, want_grad=True, grad_scale_div=None, ws=None, best_path=None,
+                    mwer_grad_scale=None):
         """Returns (nll (B,), d_enc contribution or None).  best_path: optional (B, T) int32 tensor for the frame-wise argmax of the
-        logits (the greedy path of the step's CER; the gradient overwrites the logits in place, so it is taken inside the loss kernels)."""
+        logits (the greedy path of the step's CER; the gradient overwrites the logits in place, so it is taken inside the loss kernels).
+        mwer_grad_scale (with self.mwer set and a gradient wanted): the MWER stage - the n-best list of the step's own logits from the
+        device search, its errors and lattices BEFORE the CTC kernels overwrite the logits, the sparse risk gradient added on top of the
+        CTC gradient AFTER them; scaled like grad_scale (divided by grad_scale_div when that is given).  self.last_mwer keeps the list."""
         buf = torch.empty(B * T, self.ld_v, dtype=enc.dtype, device=enc.device)      # rows padded to whole lines (see self.ld_v)
         ws = ws if ws is not None else self.ws
         logits = self.ctc_lo.fwd(enc, out=buf[:, :self.V])
         frames = buf.view(B, T, self.ld_v)[:, :, :self.V]
-        if want_grad:
-            self._arm()      # the head's weight gradient follows the loss kernels directly
+        mwer = self.mwer if (want_grad and mwer_grad_scale is not None) else None
+        if mwer is not None:
+            vals, ids, blank_lp = K.ctc_frame_topk(logits, mwer["frame_topk"], 0)
+            search_len = wave_len
+            if mwer["thr"] is not None:
+                vals, ids, blank_lp, search_len, _ = K.ctc_blank_skip_compact(vals, ids, blank_lp, wave_len, mwer["thr"], B, T)
+            Lh = min(T, K.MWER_MAX_LEN, 2 * labels32.shape[1] + 8)      # known on the host: the step never waits for the search
+            tok, ln, _ = K.ctc_prefix_beam(vals, ids, blank_lp, search_len, B, T, mwer["beam"], mwer["nbest"], 0, max_len=Lh)
+            err, _ = K.mwer_errors(tok, ln, labels32, lab_len)
+            lat = K.ctc_mwer_lattice(frames, wave_len, tok, ln, err, blank=0, ws=self.ws_mwer)
+            self.last_mwer = (tok, ln, err, lat["post"], lat["risk"])
+        elif want_grad:
+            # the head's weight gradient follows the loss kernels directly.  NOT in the MWER path: the arm would hand the gradient over to
+            # the weight-gradient stream on the CTC kernels' completion, before the risk gradient is added; the plain fork of _wgrad, behind
+            # the last MWER launch, is the correct hand-over there
+            self._arm()
         nll, dl = K.ctc_fwd_bwd(frames, wave_len, labels32, lab_len, ws, blank=0, grad_scale=grad_scale,
                                 dlogits=frames if want_grad else None, want_grad=want_grad, grad_scale_div=grad_scale_div, best_path=best_path)
         if not want_grad:
             return nll, None
+        if mwer is not None:
+            K.ctc_mwer_grad(frames, wave_len, tok, ln, lat["coef"], lat["ws"], blank=0, grad_scale=mwer_grad_scale, grad_scale_div=grad_scale_div,
+                            accumulate=True)
         dl = logits      # the gradient was written in place
         self._wgrad(self.ctc_lo, dl, enc, bias_from=dl)
         self.wait_transposes()      # this step's transposed copy of the head (made on the weight-gradient stream at the start of the step)

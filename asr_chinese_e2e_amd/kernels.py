@@ -1980,3 +1980,108 @@ def nbest_sweep(feat, ln, err, grid, host_feat, host_len, host_grid, totals=Fals
     check(lib.asr_nbest_sweep(_p(feat), _p(ln), _p(err), _p(grid), hf.ctypes.data, hl.ctypes.data, hg.ctypes.data, U_, N, K_, G, _p(out_pick), _p(out_tot),
                               _p(out_total), _p(w), w.numel(), _stream()), "asr_nbest_sweep")
     return out_pick, out_tot, out_total
+
+
+# --------------------------------------------------------------------------------- MWER training of the CTC head (csrc/mwer.hip)
+MWER_MAX_N, MWER_MAX_LEN, MWER_ABSENT, MWER_LONG = _lib.MWER_MAX_N, _lib.MWER_MAX_LEN, _lib.MWER_ABSENT, _lib.MWER_LONG
+
+
+def _mwer_list(name, hyp, hyp_len):
+    """(B, N, Lh, ldn, ldb) of an n-best list: hyp (B, N, Lh) int32 with unit stride along the tokens, hyp_len (B, N) int32 contiguous."""
+    if hyp.dtype != torch.int32 or hyp.dim() != 3 or hyp.stride(2) != 1 and hyp.shape[2] > 1:
+        raise ValueError(f"{name}: hyp is (B, N, Lh) int32 with unit stride along the tokens")
+    _chk_i32(hyp_len)
+    B, N, Lh = hyp.shape
+    if tuple(hyp_len.shape) != (B, N):
+        raise ValueError(f"{name}: hyp_len {tuple(hyp_len.shape)} for hyp {tuple(hyp.shape)}")
+    ldn = hyp.stride(1) if N > 1 else Lh
+    ldb = hyp.stride(0) if B > 1 else max((N - 1) * ldn + Lh, 1)
+    return B, N, Lh, ldn, ldb
+
+
+def ctc_mwer_workspace_bytes(B, N, T, Lh):
+    """Bytes of the workspace ctc_mwer_lattice fills and ctc_mwer_grad reads (asr_ctc_mwer_workspace_bytes); raises for a shape the
+    launchers would refuse."""
+    nbytes = int(lib.asr_ctc_mwer_workspace_bytes(int(B), int(N), int(T), int(Lh)))
+    if not nbytes:
+        raise ValueError(f"ctc_mwer: {_lib.last_error()}")
+    return nbytes
+
+
+def mwer_errors(hyp, hyp_len, ref, ref_len, err=None, flags=None):
+    """The Levenshtein distance of every entry of an n-best list to its utterance's reference (asr_mwer_errors), lengths read on the
+    device only.  hyp (B, N, Lh) int32, hyp_len (B, N) int32 (-1 = absent), ref (B, Lr) int32, ref_len (B) int32.
+    Returns (err (B, N) int32, flags (B, N) int32: 0, MWER_ABSENT or MWER_LONG; a flagged entry has err 0)."""
+    B, N, Lh, ldn, ldb = _mwer_list("mwer_errors", hyp, hyp_len)
+    _chk_i32(ref_len, err, flags)
+    if ref.dtype != torch.int32 or ref.dim() != 2 or ref.shape[0] != B or (ref.stride(1) != 1 and ref.shape[1] > 1) or ref_len.numel() != B:
+        raise ValueError("mwer_errors: ref is (B, Lr) int32 with unit stride along the tokens, ref_len (B) int32")
+    Lr = ref.shape[1]
+    ldr = ref.stride(0) if B > 1 else max(Lr, 1)
+    err = torch.empty(B, N, dtype=torch.int32, device=hyp.device) if err is None else err
+    flags = torch.empty(B, N, dtype=torch.int32, device=hyp.device) if flags is None else flags
+    assert err.numel() == B * N and flags.numel() == B * N
+    check(lib.asr_mwer_errors(_p(hyp), _p(hyp_len), _p(ref), _p(ref_len), _p(err), _p(flags), B, N, Lh, ldn, ldb, Lr, ldr, _stream()), "asr_mwer_errors")
+    return err, flags
+
+
+def ctc_mwer_lattice(logits, in_len, hyp, hyp_len, err, blank=0, ws=None):
+    """The CTC lattices of an n-best list (asr_ctc_mwer_lattice; the definition is tests/mwer_ref.py).  logits (B, T, V) f32 / bf16, dense
+    or rows padded as the engine lays them out (only read); in_len (B) int32; the list as mwer_errors takes it; err (B, N) int32.
+    Returns {"ll" (B, N) float64, "post", "coef" (B, N) float32, "risk" (B) float32, "present" (B, N) int32, "ws": the uint8 buffer
+    ctc_mwer_grad needs}.  ws: a Workspace to take the buffer from."""
+    B, T, V = logits.shape
+    ld = _frame_rows(logits)
+    Bh, N, Lh, ldn, ldb = _mwer_list("ctc_mwer_lattice", hyp, hyp_len)
+    _chk_i32(in_len, err)
+    if Bh != B or in_len.numel() != B or err.numel() != B * N:
+        raise ValueError(f"ctc_mwer_lattice: list {tuple(hyp.shape)}, in_len {tuple(in_len.shape)}, err {tuple(err.shape)} for logits {tuple(logits.shape)}")
+    dev = logits.device
+    nbytes = ctc_mwer_workspace_bytes(B, N, T, Lh)
+    w = ws.get(nbytes) if ws is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = dict(ll=torch.empty(B, N, dtype=torch.float64, device=dev), post=torch.empty(B, N, dtype=torch.float32, device=dev),
+               coef=torch.empty(B, N, dtype=torch.float32, device=dev), risk=torch.empty(B, dtype=torch.float32, device=dev),
+               present=torch.empty(B, N, dtype=torch.int32, device=dev), ws=w)
+    timed("ctc_mwer_lattice", 0.0, lambda: check(
+        lib.asr_ctc_mwer_lattice(_p(logits), _p(in_len), _p(hyp), _p(hyp_len), _p(err), _p(out["ll"]), _p(out["post"]), _p(out["coef"]), _p(out["risk"]),
+                                 _p(out["present"]), B, T, V, ld, N, Lh, ldn, ldb, int(blank), _p(w), w.numel(), _dt(logits), _stream()),
+        "asr_ctc_mwer_lattice"))
+    return out
+
+
+def ctc_mwer_grad(dlogits, in_len, hyp, hyp_len, coef, ws, blank=0, grad_scale=1.0, grad_scale_div=None, accumulate=False):
+    """The sparse MWER gradient (asr_ctc_mwer_grad): reads only the workspace ctc_mwer_lattice filled, the list, in_len and coef - never the
+    logits.  dlogits (B, T, V) f32 / bf16, dense or padded rows.  accumulate=False: the whole block is written (zeros where the gradient
+    is zero, columns past V untouched); accumulate=True: only the touched cells are read, added to and stored.  Returns dlogits."""
+    B, T, V = dlogits.shape
+    ld = _frame_rows(dlogits)
+    Bh, N, Lh, ldn, ldb = _mwer_list("ctc_mwer_grad", hyp, hyp_len)
+    _chk_i32(in_len)
+    _chk_f32(coef, grad_scale_div)
+    if Bh != B or in_len.numel() != B or coef.numel() != B * N:
+        raise ValueError(f"ctc_mwer_grad: list {tuple(hyp.shape)}, in_len {tuple(in_len.shape)}, coef {tuple(coef.shape)} for dlogits {tuple(dlogits.shape)}")
+    if ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise ValueError("ctc_mwer_grad: ws is the uint8 buffer of ctc_mwer_lattice")
+    timed("ctc_mwer_grad", 0.0, lambda: check(
+        lib.asr_ctc_mwer_grad(_p(dlogits), _p(in_len), _p(hyp), _p(hyp_len), _p(coef), B, T, V, ld, N, Lh, ldn, ldb, int(blank), float(grad_scale),
+                              _p(grad_scale_div), int(bool(accumulate)), _p(ws), ws.numel(), _dt(dlogits), _stream()),
+        "asr_ctc_mwer_grad"))
+    return dlogits
+
+
+def ctc_mwer(logits, in_len, hyp, hyp_len, ref, ref_len, blank=0, grad_scale=1.0, grad_scale_div=None, dlogits=None, accumulate=False,
+             want_grad=True, ws=None):
+    """MWER loss and gradient of an n-best list: mwer_errors, ctc_mwer_lattice and ctc_mwer_grad in order on the current stream.
+    Returns the dict of ctc_mwer_lattice plus "err", "flags" and "dlogits" (None with want_grad=False).  dlogits=None: a fresh tensor laid
+    out like the logits (accumulate must then be False).  The loss of the batch is grad_scale * risk.sum()."""
+    err, flags = mwer_errors(hyp, hyp_len, ref, ref_len)
+    out = ctc_mwer_lattice(logits, in_len, hyp, hyp_len, err, blank=blank, ws=ws)
+    out.update(err=err, flags=flags, dlogits=None)
+    if want_grad:
+        if dlogits is None:
+            if accumulate:
+                raise ValueError("ctc_mwer: accumulate=True needs the dlogits to add to")
+            dlogits = torch.empty_strided(logits.shape, logits.stride(), dtype=logits.dtype, device=logits.device)
+        out["dlogits"] = ctc_mwer_grad(dlogits, in_len, hyp, hyp_len, out["coef"], out["ws"], blank=blank, grad_scale=grad_scale,
+                                       grad_scale_div=grad_scale_div, accumulate=accumulate)
+    return out

@@ -1408,6 +1408,57 @@ int asr_nbest_sweep(const double* feat, const int32_t* len, const int32_t* err, 
                     const int32_t* host_len, const double* host_grid, int U, int N, int K, int G, int32_t* out_pick, int64_t* out_tot,
                     double* out_total, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * MWER training of the CTC head: the expected number of errors over an n-best list, and its gradient with respect to the logits
+ * (additive to ABI 10; csrc/mwer.hip, kernels.ctc_mwer, engine.ctc_fwd_bwd).
+ * Stands in for:  nothing in the reference.  The definition is tests/mwer_ref.py (float64, torch on the CPU).
+ *
+ * The list: hyp (B, N, Lh) int32 ids, entry rows ldn apart and utterances ldb apart, hyp_len (B, N) int32 with -1 = absent - the layout
+ * asr_ctc_prefix_beam writes.  Lengths are read ON THE DEVICE only (there are no host mirrors: the training step never waits for the
+ * search) and clamped to the shapes stated here.  Ids are compared, never used as indices, except as a column < V of the frames.
+ * An entry TAKES PART iff 0 <= len <= Lh (the search reports the true length of an entry it had to truncate: such an entry is dropped),
+ * every id is in [0, V) and differs from `blank`, len + adjacent repeats <= in_len[b], and in_len[b] > 0.
+ *
+ *   y_t = softmax(x_t);  ll_i = log p(h_i | x) (the CTC likelihood, as asr_ctc_fwd_bwd's -nll);  e_i = Levenshtein(h_i, r_b)
+ *   P_i = exp(ll_i - logsumexp over the entries taking part);  risk_b = sum_i P_i e_i;  c_i = P_i (e_i - risk_b)
+ *   G[b,t,v] = scale * sum_i c_i gamma_i(t, v),  gamma_i(t, v) = sum_{s: l'_s = v} alpha_t(s) beta_t(s) / (y_t(v) p(h_i | x))
+ * G is the gradient of scale * sum_b risk_b with respect to the logits: d ll_i / d x_t = gamma_i(t, .) - y_t and sum_i c_i = 0, so the
+ * dense softmax terms cancel and G is exactly 0 outside the blank column and the columns of the list's tokens, and on rows t >= in_len[b].
+ * An utterance with in_len = 0 or no entry taking part has risk 0, posteriors 0 and gradient 0.
+ *
+ * asr_mwer_errors: err (B, N) int32 = the distance of every entry to ref[b] (ref (B, Lr) int32 rows ldr apart, ref_len (B) int32 clamped
+ *   to [0, Lr]); one wave per pair.  flags (B, N) int32: 0, ASR_MWER_ABSENT (len < 0) or ASR_MWER_LONG (len > Lh); a flagged entry gets err 0.
+ * asr_ctc_mwer_lattice: logits (B, T, V) `dtype`, rows ld >= V apart, as asr_ctc_fwd_bwd takes them (only read).  Writes ll (B, N) fp64
+ *   (-inf for an entry that does not take part), post (B, N) f32 = P, coef (B, N) f32 = c, risk (B) f32, present (B, N) int32 (1 = takes
+ *   part), and leaves in ws (asr_ctc_mwer_workspace_bytes(B, N, T, Lh) bytes, 16-byte aligned) what the gradient needs: the state
+ *   posteriors of every entry (f32) and the chains that link equal tokens of a list.  The lattice runs in the log domain in fp64, so no
+ *   entry leaves the range: a long entry under blank-dominated posteriors never reads as infeasible.
+ * asr_ctc_mwer_grad: NEVER reads the logits - only ws, the list, in_len and coef.  dlogits (B, T, V) `dtype`, rows ld apart (it may be
+ *   the buffer asr_ctc_fwd_bwd wrote its gradient into: run the lattice before that call, this one after it).
+ *   scale = grad_scale, or grad_scale / *grad_scale_div (a DEVICE f32 scalar), as asr_ctc_fwd_bwd.
+ *   accumulate = 0: the whole (B, T, V) block is written, zeros where the gradient is zero; columns V .. ld are not touched.
+ *   accumulate = 1: only the touched cells (rows t < in_len[b]; the blank and the tokens of the entries taking part) are read, added to in
+ *   f32 and stored; every other byte stays.  No atomics; one summation order (entries ascending, states ascending) in f32: two runs
+ *   write the same bytes.
+ * Refused before any launch (ASR_EINVAL; ASR_EDTYPE; ASR_EWORKSPACE): null or misaligned pointers (fp64: 8 bytes, ws: 16), B outside
+ *   [1, 65535], N outside [1, ASR_MWER_MAX_N], Lh or Lr outside [1, ASR_MWER_MAX_LEN], ldn < Lh, ldb < (N - 1) ldn + Lh, ldr < Lr,
+ *   T <= 0, V <= 1, blank outside [0, V), ld < V, a dtype other than f32 / bf16, a workspace below the size query's answer (the query
+ *   itself returns 0 for a bad shape), a non-finite grad_scale, accumulate other than 0 / 1.
+ */
+#define ASR_MWER_MAX_N 16
+#define ASR_MWER_MAX_LEN 255
+#define ASR_MWER_ABSENT 1
+#define ASR_MWER_LONG 2
+size_t asr_ctc_mwer_workspace_bytes(int B, int N, int T, int Lh);
+int asr_mwer_errors(const int32_t* hyp, const int32_t* hyp_len, const int32_t* ref, const int32_t* ref_len, int32_t* err, int32_t* flags,
+                    int B, int N, int Lh, int ldn, int ldb, int Lr, int ldr, void* stream);
+int asr_ctc_mwer_lattice(const void* logits, const int32_t* in_len, const int32_t* hyp, const int32_t* hyp_len, const int32_t* err,
+                         double* ll, float* post, float* coef, float* risk, int32_t* present, int B, int T, int V, int ld, int N, int Lh,
+                         int ldn, int ldb, int blank, void* ws, size_t ws_bytes, int dtype, void* stream);
+int asr_ctc_mwer_grad(void* dlogits, const int32_t* in_len, const int32_t* hyp, const int32_t* hyp_len, const float* coef, int B, int T,
+                      int V, int ld, int N, int Lh, int ldn, int ldb, int blank, float grad_scale, const float* grad_scale_div,
+                      int accumulate, const void* ws, size_t ws_bytes, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

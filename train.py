@@ -36,6 +36,9 @@ Differences that come with the MI355X path:
     the warm-up `min(decay, (1 + s) / (10 + s))` off); both are model-config keys and reach the model like every other one.  The trainers
     then write e{E}_s{S}.ema.model beside every checkpoint and log dev/ema/loss, dev/ema/cer beside the raw figures; average.py takes the
     mean of the last or best N checkpoints afterwards;
+  * `--model_name=TransformerCTC --mwer_weight=0.5` fine-tunes on the expected number of errors over the model's own n-best list (MWER):
+    the loss gains mwer_weight * the mean risk of the batch and the log gains `mwer`; `--mwer_nbest=4 --mwer_beam=4 --mwer_frame_topk=7
+    --mwer_blank_skip=0.98` shape the device search that makes the list.  Model-config keys like ema_decay; 0 (the default) changes nothing;
   * `--synthetic=N` trains on N synthetic AISHELL-1-shaped utterances (no dataset ships with this repository);
   * `--trainer=BaseTrainer` selects the twin of Trainer/base_trainer.py instead of Trainer11.
 """
