@@ -25,6 +25,10 @@ Additions required by BASELINE.json's north_star (not in the reference):
     loss gains mwer_weight * the mean over the batch of the expected number of errors over the model's own n-best list (the device
     prefix beam search on the step's logits; include/asr_hip.h: asr_ctc_mwer_lattice, engine.ctc_fwd_bwd), metrics gains `mwer`;
     model.mwer_risk(pack) reports the same figures without a gradient.  0 (the default) launches what was launched without it.
+  * config.cr_ctc_weight > 0 (TransformerCTC only): CR-CTC training - the batch holds two views of every utterance (rows p and p + B/2,
+    data_handler.BucketedWaveLoader(views=2)) and the step's loss gains cr_ctc_weight * the mean over the pairs of the consistency term
+    between the two views' frame posteriors (include/asr_hip.h: asr_cr_ctc_fwd_bwd, engine.ctc_fwd_bwd), metrics gains `cr`.
+    0 (the default) launches what was launched without it.
 """
 import contextlib
 import math
@@ -61,6 +65,17 @@ def mwer_settings(weight, nbest, beam, frame_topk, blank_skip):
         raise ValueError(f"the device search ranks mwer_beam * (mwer_frame_topk + 1) <= 64 candidates per frame (beam {beam}, frame_topk {frame_topk})")
     thr = None if blank_skip is None else K.blank_skip_threshold(blank_skip)
     return float(weight), dict(nbest=nbest, beam=beam, frame_topk=frame_topk, thr=thr)
+
+
+def cr_ctc_setting(weight):
+    """config.cr_ctc_weight as a float; ValueError unless it is a finite number >= 0."""
+    try:
+        ok = not isinstance(weight, (bool, str)) and math.isfinite(float(weight)) and float(weight) >= 0.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"cr_ctc_weight={weight!r}: a finite number >= 0 (0 = no consistency term)")
+    return float(weight)
 
 
 def _set_nested(root, dotted, value, is_buffer=False):
@@ -123,6 +138,12 @@ class _SpeechTransformer(BaseModel):
         self._mwer_mean = None       # the mean risk of the last training step (device scalar), None without the MWER term
         if self.mwer_weight > 0.0 and self.use_decoder:
             raise ValueError("mwer_weight > 0 needs the CTC-only model (TransformerCTC): MWER through the attention decoder is not implemented")
+        self.cr_ctc_weight = cr_ctc_setting(getattr(c, "cr_ctc_weight", 0.0))
+        self._cr_mean = None         # the mean consistency term of the last training step's pairs (device scalar), None without the term
+        if self.cr_ctc_weight > 0.0 and self.use_decoder:
+            raise ValueError("cr_ctc_weight > 0 needs the CTC-only model (TransformerCTC): the consistency term is defined on the CTC head's posteriors")
+        if self.cr_ctc_weight > 0.0 and self.mwer_weight > 0.0:
+            raise ValueError("cr_ctc_weight > 0 together with mwer_weight > 0 is not implemented: both add a gradient on top of the CTC gradient")
         d, H, dk, ff = c.d_model, c.num_head, c.hidden_size, c.ff_size
         d_in = c.n_mels * c.lfr_m
         V = vocab.vocab_size
@@ -254,6 +275,7 @@ class _SpeechTransformer(BaseModel):
         pe = self.encoder.positional_encoding.pe[0].to(device).contiguous()
         self._engine = E.Engine(f, self.config, self.V, self.use_decoder, self.use_ctc, pe)
         self._engine.mwer = dict(self._mwer) if self.mwer_weight > 0.0 else None
+        self._engine.cr_ctc = self.cr_ctc_weight > 0.0
         self._flat_device = device
         self._views_checked = True
         self._grads_checked = True
@@ -934,6 +956,8 @@ class _SpeechTransformer(BaseModel):
         count_hook (data parallelism, dist.DataParallel): called as count_hook(n_valid, B) right after the label
         preprocessing; it starts the all-reduce of [non-pad token count, batch size] and returns an object whose wait()
         yields the two GLOBAL values as 1-element device tensors - the loss kernels then normalise by those."""
+        if self.cr_ctc_weight > 0.0 and int(input.wave.shape[0]) % 2:      # before anything is launched
+            raise ValueError(f"cr_ctc_weight > 0 takes the two views of every utterance, rows p and p + B/2: a batch of {int(input.wave.shape[0])} rows is odd")
         eng, x, wave_len, prep = self._prepare(input, training=self.training)
         B, T, _ = x.shape
         lam = self.ctc_weight
@@ -972,7 +996,10 @@ class _SpeechTransformer(BaseModel):
             mwer = {}
             if self.mwer_weight > 0.0:      # scaled as the CTC term is: by the batch, or by the global batch on the device
                 mwer = dict(mwer_grad_scale=self.mwer_weight * loss_scale / (1.0 if batch_div is not None else float(B)))
-            nll, d_enc = eng.ctc_fwd_bwd(enc, wave_len, labels32, lab_len, B, T, best_path=path, **ctc_scale, **mwer)
+            cr = {}
+            if self.cr_ctc_weight > 0.0:      # a mean over the pairs: cr_ctc_weight * loss_scale / (B / 2), or over the global pairs on the device
+                cr = dict(cr_grad_scale=2.0 * self.cr_ctc_weight * loss_scale / (1.0 if batch_div is not None else float(B)))
+            nll, d_enc = eng.ctc_fwd_bwd(enc, wave_len, labels32, lab_len, B, T, best_path=path, **ctc_scale, **mwer, **cr)
             if path is not None:      # collapse the greedy path and score it against the label strings, as cal_metrics does for a CTC-only model
                 def score():
                     ids, lens = K.ctc_collapse(path, wave_len, PAD_ID)
@@ -993,6 +1020,14 @@ class _SpeechTransformer(BaseModel):
             self._mwer_mean = risk.sum() / (batch_div[0] if batch_div is not None else float(B))
             loss = loss.clone()
             loss[0] += self.mwer_weight * self._mwer_mean
+        self._cr_mean = None
+        if self.cr_ctc_weight > 0.0 and self.use_ctc and not ctc_async:
+            # the consistency term beside the combined loss: cr_ctc_weight * the mean over the pairs (no device-to-host copy, no sync);
+            # metrics.cr is the mean over THIS batch's pairs, the loss under data parallelism this rank's share of the global mean
+            cr_sum = eng.last_cr[1].sum()
+            self._cr_mean = cr_sum / float(B // 2)
+            loss = loss.clone()
+            loss[0] += self.cr_ctc_weight * (2.0 * cr_sum / batch_div[0] if batch_div is not None else self._cr_mean)
         return loss, pg
 
     def mwer_risk(self, input, nbest=None, beam_size=None, frame_topk=None, blank_skip=None):
@@ -1065,6 +1100,8 @@ class _SpeechTransformer(BaseModel):
             metrics.add(cer=self._cer_of(pg))                 # no device-to-host copy, no sync
         if getattr(self, "_mwer_mean", None) is not None:
             metrics.add(mwer=self._mwer_mean)                 # the mean risk of the batch, in errors per utterance
+        if getattr(self, "_cr_mean", None) is not None:
+            metrics.add(cr=self._cr_mean)                     # the mean consistency term of the batch's pairs
         return metrics, None
 
     def greedy_search(self, input, decode_max_len=0):
@@ -1097,6 +1134,7 @@ class _SpeechTransformer(BaseModel):
             mwer_beam = 4                   # beam of the device prefix beam search that makes the list
             mwer_frame_topk = 7             # classes per frame the search looks at: mwer_beam * (mwer_frame_topk + 1) <= 64
             mwer_blank_skip = None          # a probability in (0, 1]: blank-frame skipping in front of that search
+            cr_ctc_weight = 0.0             # > 0 (TransformerCTC): batches hold two views per utterance; the loss gains cr_ctc_weight * mean consistency term
 
         return ModelConfig
 

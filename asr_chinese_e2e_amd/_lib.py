@@ -36,6 +36,7 @@ EDIT_COR, EDIT_SUB, EDIT_DEL, EDIT_INS = 0, 1, 2, 3      # ASR_EDIT_COR .. ASR_E
 NBEST_MAX_N, NBEST_MAX_LEN, NBEST_MAX_ALTS, NBEST_EPS = 64, 256, 8, -1      # ASR_NBEST_*: entries per list, tokens per entry, alternatives per slot, "no token"
 RESCORE_MAX_N, RESCORE_MAX_K, RESCORE_MAX_G, RESCORE_MAX_U = 64, 8, 65536, 1 << 20      # ASR_RESCORE_*: entries per list, feature columns, grid points, lists of asr_nbest_sweep
 MWER_MAX_N, MWER_MAX_LEN, MWER_ABSENT, MWER_LONG = 16, 255, 1, 2      # ASR_MWER_*: entries per list, tokens per entry / reference, the flags of asr_mwer_errors
+CR_CTC_RESIDENT_MAX_V = 6144      # ASR_CR_CTC_RESIDENT_MAX_V: the longest row asr_cr_ctc_fwd_bwd keeps in registers
 STREAM_OPEN = 0x3fffffff     # ASR_STREAM_OPEN: "length not known yet" in the streaming front end's parameter arrays
 
 P, I, F, Z, U = c_void_p, c_int, c_float, c_size_t, c_uint32
@@ -226,6 +227,7 @@ SIGNATURES = {
     "asr_mwer_errors": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "asr_ctc_mwer_lattice": (I, [P] * 10 + [I] * 9 + [P, Z, I, P]),
     "asr_ctc_mwer_grad": (I, [P, P, P, P, P] + [I] * 9 + [F, P, I, P, Z, I, P]),
+    "asr_cr_ctc_fwd_bwd": (I, [P, P, P, P, P, I, I, I, I, F, P, I, I, P]),
 }
 
 

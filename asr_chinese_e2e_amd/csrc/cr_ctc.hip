@@ -1,0 +1,239 @@
+// CR-CTC: the consistency term between the frame posteriors of two views of an utterance, and its gradient with respect to the logits
+// (include/asr_hip.h: asr_cr_ctc_fwd_bwd; the definition is tests/cr_ctc_ref.py).  An HBM-bound pass over (2P, T, V) logits.
+//
+// Two kernels on one stream:
+//   1. cr_ctc_kernel   : one workgroup of 256 threads per (pair, frame).  Loads the frame's row of BOTH views once (16 B per thread and
+//      load; element by element when V is no multiple of the vector), per row block_max and the block's sum of exp(x - max), then per
+//      element p = exp(x - max) / sum, lp = x - lse, J += (p_a - p_b) (lp_a - lp_b), g = scale/2 (p_a - p_b) -> row a, -g -> row b.
+//      The exponentials are f32 (expf); their sum, p, lp and J are carried in fp64 (see the note at block_sum_f64).  A row of up
+//      to CR_RESIDENT_MAX_V elements stays in registers from the load to the gradient store (CR_E values per thread and row); a longer one
+//      is read again for each of the three passes (it is L2-hot), with the same element-to-thread mapping, so that a thread adds the
+//      same terms in the same order on both paths.  Both rows go through one instruction sequence: identical views give exactly 0,
+//      swapped views swapped bytes.
+//   2. cr_ctc_pair_sum_kernel : one workgroup per pair adds frame_loss[p, :] in frame order (fp64 accumulator, one thread, rows staged
+//      through LDS).  No atomics anywhere: two runs write the same bytes.
+#include "asr_common.h"
+
+namespace {
+
+constexpr int CR_THREADS = 256;
+constexpr int CR_E = ASR_CR_CTC_RESIDENT_MAX_V / CR_THREADS;      // elements per thread and row in registers: 24 (V = 4232: 17 of them used)
+static_assert(CR_E * CR_THREADS == ASR_CR_CTC_RESIDENT_MAX_V && CR_E % 8 == 0, "the resident cap is whole 16-byte vectors per thread");
+ASR_FULL_WAVES(CR_THREADS);
+
+template <typename T> struct Vec {
+    static constexpr int N = 16 / sizeof(T);  // elements per 16-byte load
+};
+
+// N consecutive elements <-> fp32 (N = Vec<T>::N: one 16-byte access; N = 1: one element)
+template <typename T, int N>
+__device__ __forceinline__ void loadv(const T* p, float (&r)[N]) {
+    if constexpr (N == 1) {
+        r[0] = to_f32<T>(p[0]);
+    } else if constexpr (sizeof(T) == 2) {
+        load8<T>(p, r);
+    } else {
+        f32x4 v = *(const f32x4*)p;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = v[i];
+    }
+}
+template <typename T, int N>
+__device__ __forceinline__ void storev(T* p, const float (&r)[N]) {
+    if constexpr (N == 1) {
+        p[0] = from_f32<T>(r[0]);
+    } else if constexpr (sizeof(T) == 2) {
+        store8<T>(p, r);
+    } else {
+        f32x4 v = {r[0], r[1], r[2], r[3]};
+        *(f32x4*)p = v;
+    }
+}
+
+// Why fp64 behind the f32 exponentials: with peaked posteriors (logits spread over +-100) J is a sum of terms (p_a - p_b)(lp_a - lp_b) with
+// p ~ 1 and lp differences ~ 100, so a relative error of 6e-8 in a sum of exponentials (one f32 rounding) moves J by 6e-6 - more than the
+// f32 spacing of the result allows a kernel to be away from the definition.  Sums, p, lp and J in fp64 cost ~15 fp64 instructions per
+// pair of elements beside two expf and the memory traffic, and leave the f32 rounding of expf itself (p tiny wherever lp is large) and
+// of the results.  Fixed order (xor butterfly, then the waves in order): every lane gets the same bits, two runs the same bits.
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    double r = 0.0;
+#pragma unroll
+    for (int i = 0; i < CR_THREADS / 64; ++i) r += red[i];
+    return r;
+}
+
+// N: elements per access (Vec<T>::N, or 1 when V, ld or a base address is no multiple of the vector).  RES: the rows stay in registers.
+// Chunk c of a row = its elements [c N, c N + N); thread i owns the chunks i, i + 256, i + 512, ... on both paths.
+template <typename T, int N, bool RES>
+__global__ __launch_bounds__(CR_THREADS) void cr_ctc_kernel(const T* __restrict__ logits, T* __restrict__ grad, const int32_t* __restrict__ in_len,
+                                                            float* __restrict__ frame_loss, int P, int T_, int V, int ld, float grad_scale,
+                                                            const float* __restrict__ grad_scale_div, int accumulate) {
+    __shared__ float red[16];
+    __shared__ double red64[CR_THREADS / 64];
+    constexpr int KC = RES ? CR_E / N : 1;      // chunks per thread and row held in registers
+    const int t = blockIdx.x, p = blockIdx.y, tid = threadIdx.x;
+    const int n = min(max(min(in_len[p], in_len[p + P]), 0), T_);
+    const size_t oa = ((size_t)p * T_ + t) * ld, ob = ((size_t)(p + P) * T_ + t) * ld;
+    const int nch = V / N;      // N divides V on the vector path
+    if (t >= n) {      // the whole workgroup: no barrier below is reached by a part of it
+        if (tid == 0) frame_loss[(size_t)p * T_ + t] = 0.f;
+        if (grad && !accumulate) {
+            float z[N];
+#pragma unroll
+            for (int j = 0; j < N; ++j) z[j] = 0.f;
+            for (int c = tid; c < nch; c += CR_THREADS) {
+                storev<T, N>(grad + oa + (size_t)c * N, z);
+                storev<T, N>(grad + ob + (size_t)c * N, z);
+            }
+        }
+        return;
+    }
+    const T* xa_g = logits + oa;
+    const T* xb_g = logits + ob;
+    float xa[KC][N], xb[KC][N];
+    // f(k, c): called for every chunk c of this thread, k its register slot.  RES: slots 0 .. KC-1, unrolled; else slot 0 in a loop
+    auto each = [&](auto&& f) {
+        if constexpr (RES) {
+#pragma unroll
+            for (int k = 0; k < KC; ++k) {
+                const int c = tid + CR_THREADS * k;
+                if (c < nch) f(k, c);
+            }
+        } else {
+            for (int c = tid; c < nch; c += CR_THREADS) f(0, c);
+        }
+    };
+    auto fetch = [&](int k, int c) {      // the path that re-reads loads the chunk in front of every use
+        if constexpr (!RES) {
+            loadv<T, N>(xa_g + (size_t)c * N, xa[k]);
+            loadv<T, N>(xb_g + (size_t)c * N, xb[k]);
+        }
+    };
+    if constexpr (RES) {
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {      // all loads of both rows in flight at once
+            const int c = tid + CR_THREADS * k;
+            if (c < nch) {
+                loadv<T, N>(xa_g + (size_t)c * N, xa[k]);
+                loadv<T, N>(xb_g + (size_t)c * N, xb[k]);
+            }
+        }
+    }
+    float ma = -INFINITY, mb = -INFINITY;
+    each([&](int k, int c) {
+        fetch(k, c);
+#pragma unroll
+        for (int j = 0; j < N; ++j) { ma = fmaxf(ma, xa[k][j]); mb = fmaxf(mb, xb[k][j]); }
+    });
+    ma = block_max(ma, red);
+    mb = block_max(mb, red);
+    double sa = 0.0, sb = 0.0;
+    each([&](int k, int c) {
+        fetch(k, c);
+#pragma unroll
+        for (int j = 0; j < N; ++j) { sa += (double)expf(xa[k][j] - ma); sb += (double)expf(xb[k][j] - mb); }
+    });
+    sa = block_sum_f64(sa, red64);
+    sb = block_sum_f64(sb, red64);
+    const double ia = 1.0 / sa, ib = 1.0 / sb;
+    const double dlse = ((double)ma + log(sa)) - ((double)mb + log(sb));      // lse_a - lse_b
+    float h = 0.f;
+    if (grad) h = 0.5f * (grad_scale_div ? grad_scale / *grad_scale_div : grad_scale);
+    double js = 0.0;
+    each([&](int k, int c) {
+        // No contraction in this block (hipcc fuses a * b + c into one fma by default, across statements, and __dmul_rn / __fmul_rn are
+        // plain products to it): p_a - p_b must be the difference of two ROUNDED products - as one fused multiply-subtract equal rows
+        // gave 1e-20 instead of exactly 0 - and accumulate = 1 must add the rounded h * d that accumulate = 0 writes.
+#pragma clang fp contract(off)
+        fetch(k, c);
+        float ga[N], gb[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const double d = (double)expf(xa[k][j] - ma) * ia - (double)expf(xb[k][j] - mb) * ib;      // p_a - p_b
+            js += d * (((double)xa[k][j] - (double)xb[k][j]) - dlse);                                    // ... times lp_a - lp_b
+            ga[j] = h * (float)d;
+            gb[j] = -ga[j];
+        }
+        if (grad) {
+            T* da = grad + oa + (size_t)c * N;
+            T* db = grad + ob + (size_t)c * N;
+            if (accumulate) {      // read, add in fp32, round once
+                float qa[N], qb[N];
+                loadv<T, N>(da, qa);
+                loadv<T, N>(db, qb);
+#pragma unroll
+                for (int j = 0; j < N; ++j) { ga[j] += qa[j]; gb[j] += qb[j]; }
+            }
+            storev<T, N>(da, ga);
+            storev<T, N>(db, gb);
+        }
+    });
+    js = block_sum_f64(js, red64);
+    if (tid == 0) frame_loss[(size_t)p * T_ + t] = (float)(0.5 * js);
+}
+
+// pair_loss[p] = sum_t frame_loss[p, t] in frame order (frames t >= n hold zeros)
+__global__ __launch_bounds__(CR_THREADS) void cr_ctc_pair_sum_kernel(const float* __restrict__ frame_loss, float* __restrict__ pair_loss, int T_) {
+    __shared__ float row[4 * CR_THREADS];
+    const int p = blockIdx.x;
+    const float* f = frame_loss + (size_t)p * T_;
+    double acc = 0.0;
+    for (int t0 = 0; t0 < T_; t0 += 4 * CR_THREADS) {
+        const int m = min(4 * CR_THREADS, T_ - t0);
+        __syncthreads();      // the previous part has been added
+        for (int i = threadIdx.x; i < m; i += CR_THREADS) row[i] = f[t0 + i];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < m; ++i) acc += (double)row[i];
+    }
+    if (threadIdx.x == 0) pair_loss[p] = (float)acc;
+}
+
+template <typename T>
+void cr_ctc_launch(const void* logits, void* grad, const int32_t* in_len, float* frame_loss, int P, int T_, int V, int ld, float grad_scale,
+                   const float* grad_scale_div, int accumulate, hipStream_t st) {
+    constexpr int N = Vec<T>::N;
+    const bool vec = V % N == 0 && ld % N == 0 && (uintptr_t)logits % 16 == 0 && (uintptr_t)grad % 16 == 0;
+    const bool res = V <= ASR_CR_CTC_RESIDENT_MAX_V;
+    const dim3 grid(T_, P);
+#define CR_LAUNCH(N_, RES_) \
+    cr_ctc_kernel<T, N_, RES_><<<grid, CR_THREADS, 0, st>>>((const T*)logits, (T*)grad, in_len, frame_loss, P, T_, V, ld, grad_scale, grad_scale_div, accumulate)
+    if (vec && res) CR_LAUNCH(N, true);
+    else if (vec) CR_LAUNCH(N, false);
+    else if (res) CR_LAUNCH(1, true);
+    else CR_LAUNCH(1, false);
+#undef CR_LAUNCH
+}
+
+}  // namespace
+
+extern "C" int asr_cr_ctc_fwd_bwd(const void* logits, const int32_t* in_len, void* grad, float* frame_loss, float* pair_loss, int P, int T, int V,
+                                  int ld, float grad_scale, const float* grad_scale_div, int accumulate, int dtype, void* stream) {
+    const char* name = "asr_cr_ctc_fwd_bwd";
+    if (!logits || !in_len || !frame_loss || !pair_loss) ASR_FAIL(ASR_EINVAL, "%s: null pointer", name);
+    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "%s: dtype %d", name, dtype);
+    const size_t es = dtype == ASR_F32 ? 4 : 2;
+    if (((uintptr_t)in_len | (uintptr_t)frame_loss | (uintptr_t)pair_loss | (uintptr_t)grad_scale_div) % 4 || ((uintptr_t)logits | (uintptr_t)grad) % es)
+        ASR_FAIL(ASR_EINVAL, "%s: misaligned pointer", name);
+    if (P <= 0 || P > 65535 || T <= 0 || V < 2 || ld < V) ASR_FAIL(ASR_EINVAL, "%s: bad shape P=%d (1 .. 65535) T=%d V=%d ld=%d", name, P, T, V, ld);
+    if (accumulate != 0 && accumulate != 1) ASR_FAIL(ASR_EINVAL, "%s: accumulate=%d (0 or 1)", name, accumulate);
+    if (accumulate && !grad) ASR_FAIL(ASR_EINVAL, "%s: accumulate=1 needs the gradient block to add to", name);
+    if (!(grad_scale == grad_scale) || grad_scale - grad_scale != 0.f) ASR_FAIL(ASR_EINVAL, "%s: grad_scale is not finite", name);
+    if (grad) {      // both blocks span (2 P T - 1) ld + V elements
+        const size_t span = (((size_t)2 * P * T - 1) * ld + V) * es;
+        const uintptr_t a = (uintptr_t)logits, b = (uintptr_t)grad;
+        if (a < b + span && b < a + span) ASR_FAIL(ASR_EINVAL, "%s: the gradient block overlaps the logits (the logits are read after the first store)", name);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == ASR_F32) cr_ctc_launch<float>(logits, grad, in_len, frame_loss, P, T, V, ld, grad_scale, grad_scale_div, accumulate, st);
+    else cr_ctc_launch<bf16_t>(logits, grad, in_len, frame_loss, P, T, V, ld, grad_scale, grad_scale_div, accumulate, st);
+    cr_ctc_pair_sum_kernel<<<P, CR_THREADS, 0, st>>>(frame_loss, pair_loss, T);
+    ASR_CHECK_LAUNCH(name);
+    return ASR_OK;
+}

@@ -206,7 +206,7 @@ class MetaLayout:
     here and nowhere else, and field() slices the numpy view of the pinned buffer and its device copy alike.  A feature that is off
     contributes no words (all off: 2 B + B lmax words, the copy the first loader made)."""
 
-    def __init__(self, B, lmax, factor=False, rate=False, aug=False, spec=0):
+    def __init__(self, B, lmax, factor=False, rate=False, aug=False, spec=0, views=1):
         fields = [("n_samples", (B,)), ("tgt_len", (B,)), ("tgt", (B, lmax))]
         if factor:
             fields += [("factor", (B,))]                               # speed-factor index per utterance
@@ -216,6 +216,8 @@ class MetaLayout:
             fields += [("rir_idx", (B,)), ("noise_par", (B, 4))]       # {clip, offset, scale as float bits, 0}
         if spec:
             fields += [("spec", (B, int(spec)))]                       # SpecAugment policy rows, spec = the policy's width (specaug.resolve)
+            if views == 2:
+                fields += [("spec1", (B, int(spec)))]                  # ... of the second view of the same B utterances (views=2)
         self.B, self.lmax, self.at, self.size = B, lmax, {}, 0
         for name, shape in fields:
             words = B * (shape[1] if len(shape) > 1 else 1)
@@ -239,12 +241,13 @@ SpeedTables = collections.namedtuple("SpeedTables", "pq_host pq taps")
 BatchMeta = collections.namedtuple("BatchMeta", "len16 len_out smax16 smax_out any_rir any_noise")
 
 
-def pack_meta(lay, meta, sizes, tgt, fs=None, pq=None, rates=None, rate_table=None, aug=None, *, spec=None):
+def pack_meta(lay, meta, sizes, tgt, fs=None, pq=None, rates=None, rate_table=None, aug=None, *, spec=None, spec1=None):
     """The host half of a batch, no GPU: fills `meta` (numpy int32, lay.size words) field by field and decides what the batch launches.
     sizes: sample counts, tgt: label lists; fs, pq: the batch's speed-factor indices and the (p, q) list; rates, rate_table: the batch's
     source rates and a resample.RateTable (one built with device=None does); aug: noise.draw_augment's four lists, the batch's rows;
     spec: the batch's SpecAugment policy rows (B, width), or a function that makes them from the batch's final lengths (len_out, which are
-    decided here).  Each group is read only when `lay` has its fields.  -> BatchMeta."""
+    decided here); spec1: the same for the second view's rows (a layout built with views=2).  Each group is read only when `lay` has its
+    fields.  -> BatchMeta."""
     assert meta.shape == (lay.size,) and meta.dtype == np.int32 and len(sizes) == len(tgt) == lay.B
     lay.field(meta, "n_samples")[:] = sizes
     lay.field(meta, "tgt_len")[:] = [len(t) for t in tgt]
@@ -275,6 +278,8 @@ def pack_meta(lay, meta, sizes, tgt, fs=None, pq=None, rates=None, rate_table=No
         any_rir, any_noise = any(v >= 0 for v in ridx), any(v >= 0 for v in nidx)
     if "spec" in lay:
         lay.field(meta, "spec")[:] = spec(len_out) if callable(spec) else spec
+    if "spec1" in lay:
+        lay.field(meta, "spec1")[:] = spec1(len_out) if callable(spec1) else spec1
     return BatchMeta(len16, len_out, smax16, smax_out, any_rir, any_noise)
 
 
@@ -305,7 +310,7 @@ class BucketedWaveLoader:
 
     def __init__(self, dataset, batch_size, parser=None, augment=False, shuffle=True, drop_last=False, seed=0, bucket_size=None,
                  device="cuda", dtype=torch.bfloat16, rank=0, world=1, speed_perturb=None, noise=None, noise_prob=0.5, snr_db=(5, 20), rir=None,
-                 rir_prob=0.5, rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS, resample=False, spec_augment=None):
+                 rir_prob=0.5, rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS, resample=False, spec_augment=None, views=1):
         """rank / world: data-parallel sharding.  Every rank draws the SAME batch list (same seed), keeps only the full
         batches when world > 1 (dist.DataParallel normalises by world x local batch and every rank must take the same
         number of steps), drops the ragged tail of len(batches) % world and takes batches[rank::world].
@@ -328,7 +333,17 @@ class BucketedWaveLoader:
         with zero fill, time warp and substitution on the normalised frames (tests/specaug_ref.py), in place of - never together with -
         augment=True, the reference's one-mask variant.  Every epoch each utterance draws its numbers (specaug.draw: a function of seed,
         epoch and utterance index that leaves `rng` alone); the ranges are resolved on the host from the lengths pack_meta decides and
-        travel in the one meta buffer, so nothing is read back from the device.  None / empty: nothing of it is called."""
+        travel in the one meta buffer, so nothing is read back from the device.  None / empty: nothing of it is called.
+        views: 2 = two views of every utterance for CR-CTC training (config.cr_ctc_weight): a batch then has 2 * batch_size rows, [view 0
+        of the B utterances | view 1 of the same B], with the targets and lengths repeated.  The waveform chain (resample, speed,
+        reverberation, noise) runs once per utterance; only parse_batch, which applies the masks, runs per view - view 0 with the table of
+        a one-view loader (its rows are that loader's batch, bit for bit), view 1 with specaug.draw(..., view=1).  Without a policy the two
+        views are equal and differ by the model's dropout only.  Not with augment=True (masks from `rng`, not reproducible per view)."""
+        if isinstance(views, bool) or views not in (1, 2):
+            raise ValueError(f"views={views!r}: 1, or 2 (two views of every utterance, CR-CTC training)")
+        if views == 2 and augment:
+            raise ValueError("views=2 draws every view's masks per utterance (spec_augment=...): not with augment=True, whose masks come from the loader's rng")
+        self.views = views
         self.spec = specaug_mod.as_policy(spec_augment)
         if self.spec is not None and augment:
             raise ValueError("spec_augment replaces the reference's SpecAugment: pass it or augment=True, not both")
@@ -401,15 +416,15 @@ class BucketedWaveLoader:
             slots[k] = s
         return s
 
-    def _prepare(self, idx, k=0, fidx=None, aug=None, spec=None):
+    def _prepare(self, idx, k=0, fidx=None, aug=None, spec=None, spec1=None):
         """fidx: speed-factor index per utterance of the data set (BatchPlan.next_epoch), None = no perturbation.
         aug: noise.draw_augment's four lists for the data set, None = neither noise nor reverberation.
-        spec: specaug.draw's table for the data set, None = no SpecAugment policy.
+        spec: specaug.draw's table for the data set, None = no SpecAugment policy; spec1: the second view's table (views=2 with a policy).
         The integers of the batch travel in one buffer whose layout is MetaLayout; pack_meta fills it and decides what is launched."""
         tgt = [self.ds.ids(i) for i in idx]
         B = len(idx)
         lay = MetaLayout(B, max(1, max(len(t) for t in tgt)), factor=fidx is not None, rate=self.rates is not None, aug=aug is not None,
-                         spec=self.spec.width if spec is not None else 0)
+                         spec=self.spec.width if spec is not None else 0, views=2 if spec1 is not None else 1)
         into = getattr(self.ds, "wave_into", None)
         waves = None if into is not None else [self.ds.wave(i) for i in idx]
         smax = max(self.lengths[i] for i in idx) if waves is None else max(w.size for w in waves)
@@ -435,7 +450,8 @@ class BucketedWaveLoader:
         m = pack_meta(lay, slot["meta_np"][:lay.size], sizes, tgt, fs=take(fidx) if fidx is not None else None,
                       pq=self.speed.pq_host if self.speed else None, rates=take(self.rates) if self.rates is not None else None,
                       rate_table=self.rate_table, aug=[take(a) for a in aug] if aug is not None else None,
-                      spec=(lambda lens: self.parser.spec_ranges(self.spec, spec[idx], lens)) if spec is not None else None)
+                      spec=(lambda lens: self.parser.spec_ranges(self.spec, spec[idx], lens)) if spec is not None else None,
+                      spec1=(lambda lens: self.parser.spec_ranges(self.spec, spec1[idx], lens)) if spec1 is not None else None)
         from .. import kernels as K
         with torch.cuda.stream(self.stream):
             dev_wav = slot["wave"][:B * smax].view(B, smax).to(self.device, non_blocking=True)
@@ -469,9 +485,15 @@ class BucketedWaveLoader:
                 feat, feat_len = self.parser.parse_batch(wav, wav_len, self.dtype, spec_ranges=field("spec"), spec_policy=self.spec)
             else:
                 feat, feat_len = self.parser.parse_batch(wav, wav_len, self.dtype, augment=self.augment, rng=self.rng)
-            tgt_dev = field("tgt").long()
+            tgt_dev, tgt_len, feat_len = field("tgt").long(), field("tgt_len").long(), feat_len.long()
+            if self.views == 2:      # [view 0 of the B utterances | view 1 of the same B]: the same waveforms, targets and lengths
+                feat1 = feat
+                if spec1 is not None:
+                    feat1, _ = self.parser.parse_batch(wav, wav_len, self.dtype, spec_ranges=field("spec1"), spec_policy=self.spec)
+                feat = torch.cat([feat, feat1])
+                tgt_dev, tgt_len, feat_len = tgt_dev.repeat(2, 1), tgt_len.repeat(2), feat_len.repeat(2)
             pack = Pack()
-            pack.add(wave=feat, wave_len=feat_len.long(), tgt_for_input=tgt_dev, tgt_for_metric=tgt_dev.clone(), tgt_len=field("tgt_len").long())
+            pack.add(wave=feat, wave_len=feat_len, tgt_for_input=tgt_dev, tgt_for_metric=tgt_dev.clone(), tgt_len=tgt_len)
             done = torch.cuda.Event()
             done.record()
         slot["keep"] = tuple(keep) + (feat, feat_len) + tuple(v for v in pack.values() if torch.is_tensor(v))
@@ -491,6 +513,7 @@ class BucketedWaveLoader:
             aug = noise_mod.draw_augment(self.plan.seed, epoch, len(self.ds), self.noise_prob, len(self.noise) if self.noise else 0,
                                          self.noise.lens if self.noise else (), self.snr_db, self.rir_prob, len(self.rir) if self.rir else 0)
         spec = specaug_mod.draw(self.plan.seed, epoch, len(self.ds), self.spec) if self.spec is not None else None
+        spec1 = specaug_mod.draw(self.plan.seed, epoch, len(self.ds), self.spec, view=1) if (self.spec is not None and self.views == 2) else None
         q = queue.Queue(maxsize=self.PREFETCH)
         stop = threading.Event()
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()      # the consumer's device
@@ -510,7 +533,7 @@ class BucketedWaveLoader:
                 torch.cuda.set_device(dev_index)
                 for k, idx in enumerate(batches):
                     with self._gate:      # paused() (a hipGraph capture on the consumer thread) keeps this thread off the GPU runtime
-                        item = self._prepare(idx, k, fidx, aug, spec)
+                        item = self._prepare(idx, k, fidx, aug, spec, spec1)
                     if not hand_over(item):
                         return
                 hand_over(None)
@@ -552,7 +575,7 @@ def parser_norm(cmvn):
 def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=True, sample_rate=16000, window_size=400, n_mels=40,
                      augment=False, predump=False, use_old=False, lfr_m=4, lfr_n=3, dtype=torch.bfloat16, shuffle=None, seed=0,
                      rank=0, world=1, speed_perturb=None, cmvn=None, noise=None, noise_prob=0.5, snr_db=(5, 20), rir=None, rir_prob=0.5,
-                     rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS, resample=False, frontend="reference", spec_augment=None):
+                     rir_method="direct", rir_max_taps=noise_mod.MAX_TAPS, resample=False, frontend="reference", spec_augment=None, views=1):
     """build_dataloader of the reference (data/data_loader/ai_shell_1.py:91-104), same arguments: reads the manifest
     `<collector_path>_<part>.json` written by the reference's collector (one JSON object {"wave": path, "tgt": text}
     per line, data_collector/ai_shell_1.py:73-79) and returns an iterable of Packs.  The reference computes features
@@ -567,7 +590,8 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
     (WaveDataset / BucketedWaveLoader / noise banks, every part); False = they raise, as before.
     frontend: "reference" (the reference's log-mel) or "kaldi" (Kaldi fbank): AudioParser's.
     spec_augment: BucketedWaveLoader's SpecAugment policy (a specaug.SpecAugmentPolicy or its string), applied to part="train" only and never
-    together with augment=True; None / empty = off."""
+    together with augment=True; None / empty = off.
+    views: BucketedWaveLoader's, for part="train" only (2: two views of every utterance, CR-CTC training); every other part has one view."""
     import json
     spec = specaug_mod.as_policy(spec_augment)      # a malformed string, or both augmentations, is refused before anything is built
     if spec is not None:
@@ -587,6 +611,6 @@ def build_dataloader(collector_path, vocab, batch_size, part="test", use_cuda=Tr
     ds = WaveDataset(items, vocab, sample_rate=sample_rate, resample=resample)
     parser = AudioParser(sample_rate=sample_rate, n_mels=n_mels, lfr_m=lfr_m, lfr_n=lfr_n, device="cuda", frontend=frontend, **parser_norm(cmvn))
     wave_aug = dict(noise=noise, noise_prob=noise_prob, snr_db=snr_db, rir=rir, rir_prob=rir_prob, rir_method=rir_method,
-                    rir_max_taps=rir_max_taps, spec_augment=spec) if part == "train" else {}
+                    rir_max_taps=rir_max_taps, spec_augment=spec, views=views) if part == "train" else {}
     return BucketedWaveLoader(ds, batch_size, parser=parser, augment=augment, shuffle=(part == "train") if shuffle is None else shuffle,
                               drop_last=True, seed=seed, dtype=dtype, rank=rank, world=world, speed_perturb=speed_perturb, resample=resample, **wave_aug)

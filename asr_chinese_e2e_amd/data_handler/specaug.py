@@ -98,11 +98,15 @@ def as_policy(v):
     return v if isinstance(v, SpecAugmentPolicy) else SpecAugmentPolicy.from_string(v)
 
 
-def draw(seed, epoch, n, policy):
+def draw(seed, epoch, n, policy, view=0):
     """(n, policy.n_draws) uint32: the random numbers of every utterance 0 .. n-1 of the data set - a pure function of (seed, epoch,
     utterance index), like speed.draw_factors: one generator seeded from a string that names this augmentation, consumed in index order,
-    n_draws numbers per utterance whatever they decide.  It never touches the loader's rng, and every data-parallel rank draws the same."""
-    rng = random.Random(f"spec_augment/{int(seed)}/{int(epoch)}")
+    n_draws numbers per utterance whatever they decide.  It never touches the loader's rng, and every data-parallel rank draws the same.
+    view: 0 = the table of a one-view loader; 1 = the independent table of the second view of CR-CTC training (BucketedWaveLoader(views=2)),
+    from a generator whose string also names the view."""
+    if view not in (0, 1) or isinstance(view, bool):
+        raise ValueError(f"specaug.draw: view={view!r} (0 or 1)")
+    rng = random.Random(f"spec_augment/{int(seed)}/{int(epoch)}" + (f"/view{int(view)}" if view else ""))
     k = policy.n_draws
     bits = rng.getrandbits(32 * n * k) if n else 0      # the same words as n k calls of getrandbits(32): each takes one generator word
     return np.frombuffer(bits.to_bytes(4 * n * k, "little"), dtype="<u4").astype(np.uint32).reshape(n, k)

@@ -270,6 +270,8 @@ class DataParallel:
                 metrics.add(cer=cer)
             if getattr(model, "_mwer_mean", None) is not None:      # config.mwer_weight > 0: this rank's risks over the GLOBAL batch
                 metrics.add(mwer=model._mwer_mean)
+            if getattr(model, "_cr_mean", None) is not None:        # config.cr_ctc_weight > 0: the mean over this rank's pairs
+                metrics.add(cr=model._cr_mean)
             return metrics, None
         # CE was normalised by the GLOBAL token count (sum over ranks = global CE); the CTC term the kernel reports is
         # the mean over the LOCAL batch: weight it by local / global batch before the sum over ranks
@@ -287,4 +289,6 @@ class DataParallel:
             metrics.add(cer=cer)
         if getattr(model, "_mwer_mean", None) is not None:      # rank-local, as above; the reduced loss is CE / CTC only (the MWER term is not summed over ranks)
             metrics.add(mwer=model._mwer_mean)
+        if getattr(model, "_cr_mean", None) is not None:        # rank-local; the reduced loss is CE / CTC only, as with the MWER term
+            metrics.add(cr=model._cr_mean)
         return metrics, None

@@ -583,6 +583,10 @@ class Engine:
         self.mwer = None
         self.ws_mwer = K.Workspace(flat.device)
         self.last_mwer = None       # (tok, len, err, post, risk) of the last MWER step, device tensors
+        # the consistency stage of ctc_fwd_bwd (CR-CTC): True while config.cr_ctc_weight > 0 (set by the model), else False - and then
+        # ctc_fwd_bwd launches exactly what it launches without the feature
+        self.cr_ctc = False
+        self.last_cr = None         # (frame (P, T), cr (P)) of the last step with the consistency stage, device tensors
         self._side_handle = self.side.cuda_stream
         # ---- environment switches of the engine (all read here, when the engine is built; the complete list is in README.md):
         # ASR_WGRAD_OVERLAP=0: ONE stream - weight gradients, the CTC branch and the cross-attention K|V work stay on the main stream
@@ -1046,17 +1050,24 @@ class Engine:
         return nll, d_enc, done
 
     def ctc_fwd_bwd(self, enc, wave_len, labels32, lab_len, B, T, grad_scale, want_grad=True, grad_scale_div=None, ws=None, best_path=None,
-                    mwer_grad_scale=None):
+                    mwer_grad_scale=None, cr_grad_scale=None):
         """Returns (nll (B,), d_enc contribution or None).  best_path: optional (B, T) int32 tensor for the frame-wise argmax of the
         logits (the greedy path of the step's CER; the gradient overwrites the logits in place, so it is taken inside the loss kernels).
         mwer_grad_scale (with self.mwer set and a gradient wanted): the MWER stage - the n-best list of the step's own logits from the
         device search, its errors and lattices BEFORE the CTC kernels overwrite the logits, the sparse risk gradient added on top of the
-        CTC gradient AFTER them; scaled like grad_scale (divided by grad_scale_div when that is given).  self.last_mwer keeps the list."""
+        CTC gradient AFTER them; scaled like grad_scale (divided by grad_scale_div when that is given).  self.last_mwer keeps the list.
+        cr_grad_scale (with self.cr_ctc set and a gradient wanted; B even, rows b and b + B/2 the two views of an utterance): the
+        consistency stage - the CTC kernels write their gradient OUT OF PLACE into a second block laid out like the logits, so that the
+        logits stay intact, kernels.cr_ctc adds the consistency gradient onto that block, and the head's weight and input gradients read
+        it; scaled like grad_scale.  self.last_cr keeps (frame, cr)."""
         buf = torch.empty(B * T, self.ld_v, dtype=enc.dtype, device=enc.device)      # rows padded to whole lines (see self.ld_v)
         ws = ws if ws is not None else self.ws
         logits = self.ctc_lo.fwd(enc, out=buf[:, :self.V])
         frames = buf.view(B, T, self.ld_v)[:, :, :self.V]
         mwer = self.mwer if (want_grad and mwer_grad_scale is not None) else None
+        cr = bool(self.cr_ctc and want_grad and cr_grad_scale is not None)
+        if cr and (B % 2 or mwer is not None):
+            raise ValueError(f"the consistency stage takes an even number of rows (got {B}) and does not run together with the MWER stage")
         if mwer is not None:
             vals, ids, blank_lp = K.ctc_frame_topk(logits, mwer["frame_topk"], 0)
             search_len = wave_len
@@ -1067,19 +1078,27 @@ class Engine:
             err, _ = K.mwer_errors(tok, ln, labels32, lab_len)
             lat = K.ctc_mwer_lattice(frames, wave_len, tok, ln, err, blank=0, ws=self.ws_mwer)
             self.last_mwer = (tok, ln, err, lat["post"], lat["risk"])
-        elif want_grad:
-            # the head's weight gradient follows the loss kernels directly.  NOT in the MWER path: the arm would hand the gradient over to
-            # the weight-gradient stream on the CTC kernels' completion, before the risk gradient is added; the plain fork of _wgrad, behind
-            # the last MWER launch, is the correct hand-over there
+        elif want_grad and not cr:
+            # the head's weight gradient follows the loss kernels directly.  NOT in the MWER path, nor in the consistency path: the arm would
+            # hand the gradient over to the weight-gradient stream on the CTC kernels' completion, before the second gradient is added; the
+            # plain fork of _wgrad, behind the last launch of the stage, is the correct hand-over there
             self._arm()
+        gframes = frames      # in place: the gradient overwrites the logits
+        if cr:
+            gbuf = torch.empty_like(buf)
+            gframes = gbuf.view(B, T, self.ld_v)[:, :, :self.V]
         nll, dl = K.ctc_fwd_bwd(frames, wave_len, labels32, lab_len, ws, blank=0, grad_scale=grad_scale,
-                                dlogits=frames if want_grad else None, want_grad=want_grad, grad_scale_div=grad_scale_div, best_path=best_path)
+                                dlogits=gframes if want_grad else None, want_grad=want_grad, grad_scale_div=grad_scale_div, best_path=best_path)
         if not want_grad:
             return nll, None
         if mwer is not None:
             K.ctc_mwer_grad(frames, wave_len, tok, ln, lat["coef"], lat["ws"], blank=0, grad_scale=mwer_grad_scale, grad_scale_div=grad_scale_div,
                             accumulate=True)
         dl = logits      # the gradient was written in place
+        if cr:
+            out = K.cr_ctc(frames, wave_len, grad_scale=cr_grad_scale, grad_scale_div=grad_scale_div, dlogits=gframes, accumulate=True)
+            self.last_cr = (out["frame"], out["cr"])
+            dl = gbuf[:, :self.V]      # ... out of place: the logits are intact, the block beside them holds the sum of the two gradients
         self._wgrad(self.ctc_lo, dl, enc, bias_from=dl)
         self.wait_transposes()      # this step's transposed copy of the head (made on the weight-gradient stream at the start of the step)
         d_enc = self.ctc_lo.dgrad(dl)

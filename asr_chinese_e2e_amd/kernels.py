@@ -2085,3 +2085,46 @@ def ctc_mwer(logits, in_len, hyp, hyp_len, ref, ref_len, blank=0, grad_scale=1.0
         out["dlogits"] = ctc_mwer_grad(dlogits, in_len, hyp, hyp_len, out["coef"], out["ws"], blank=blank, grad_scale=grad_scale,
                                        grad_scale_div=grad_scale_div, accumulate=accumulate)
     return out
+
+
+# --------------------------------------------------------------------------------- CR-CTC: consistency between two views (csrc/cr_ctc.hip)
+CR_CTC_RESIDENT_MAX_V = _lib.CR_CTC_RESIDENT_MAX_V
+
+
+def cr_ctc(logits, in_len, grad_scale=1.0, grad_scale_div=None, dlogits=None, accumulate=False, want_grad=True):
+    """The consistency term between the two halves of a batch and its gradient (asr_cr_ctc_fwd_bwd; the definition is tests/cr_ctc_ref.py).
+    logits (2P, T, V) f32 / bf16, dense or rows padded as the engine lays them out (only read): rows p and p + P are the two views of
+    utterance p; in_len (2P) int32.  Returns {"cr" (P) f32: the term of every pair, "frame" (P, T) f32: its frames (0 past
+    min(in_len[p], in_len[p + P])), "dlogits": grad_scale * d cr.sum() / d logits, None with want_grad=False}.
+    dlogits: a block laid out like the logits that does not overlap them; None: a fresh one (accumulate must then be False).
+    accumulate=False: every cell is written, zeros past the pair's frames; accumulate=True: added to in f32, frames past them untouched.
+    grad_scale_div: optional 1-element f32 device tensor; the scale is then grad_scale / grad_scale_div[0]."""
+    if logits.dim() != 3 or logits.shape[0] < 2 or logits.shape[0] % 2:
+        raise ValueError(f"cr_ctc: logits {tuple(logits.shape)}: (2P, T, V), the two views of P utterances")
+    R, T, V = logits.shape
+    ld = _frame_rows(logits)
+    _chk_i32(in_len)
+    _chk_f32(grad_scale_div)
+    if in_len.numel() != R:
+        raise ValueError(f"cr_ctc: in_len {tuple(in_len.shape)} for logits {tuple(logits.shape)}")
+    if grad_scale_div is not None and grad_scale_div.numel() != 1:
+        raise ValueError("cr_ctc: grad_scale_div is a 1-element float32 device tensor")
+    if not want_grad:
+        if dlogits is not None or accumulate:
+            raise ValueError("cr_ctc: want_grad=False takes neither dlogits nor accumulate")
+    elif dlogits is None:
+        if accumulate:
+            raise ValueError("cr_ctc: accumulate=True needs the dlogits to add to")
+        dlogits = torch.empty_strided(logits.shape, logits.stride(), dtype=logits.dtype, device=logits.device)
+    elif dlogits.shape != logits.shape or dlogits.stride() != logits.stride() or dlogits.dtype != logits.dtype:
+        raise ValueError(f"cr_ctc: dlogits {tuple(dlogits.shape)} {dlogits.stride()} {dlogits.dtype} is not laid out like the logits "
+                         f"{tuple(logits.shape)} {logits.stride()} {logits.dtype}")
+    P_ = R // 2
+    frame = torch.empty(P_, T, dtype=torch.float32, device=logits.device)
+    cr = torch.empty(P_, dtype=torch.float32, device=logits.device)
+    e = logits.element_size()
+    timed("cr_ctc", 0.0, lambda: check(
+        lib.asr_cr_ctc_fwd_bwd(_p(logits), _p(in_len), _p(dlogits), _p(frame), _p(cr), P_, T, V, ld, float(grad_scale), _p(grad_scale_div),
+                               int(bool(accumulate)), _dt(logits), _stream()),
+        "asr_cr_ctc_fwd_bwd"), float(R) * T * V * e * (1.0 + (0.0 if dlogits is None else 2.0 if accumulate else 1.0)))
+    return {"cr": cr, "frame": frame, "dlogits": dlogits}

@@ -1459,6 +1459,36 @@ int asr_ctc_mwer_grad(void* dlogits, const int32_t* in_len, const int32_t* hyp, 
                       int V, int ld, int N, int Lh, int ldn, int ldb, int blank, float grad_scale, const float* grad_scale_div,
                       int accumulate, const void* ws, size_t ws_bytes, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * CR-CTC: consistency between the frame posteriors of two augmented views of an utterance, and its gradient with respect to the logits
+ * (additive to ABI 10; csrc/cr_ctc.hip, kernels.cr_ctc, engine.ctc_fwd_bwd).
+ * Stands in for:  nothing in the reference.  The definition is tests/cr_ctc_ref.py (float64, torch on the CPU).
+ *
+ * logits (2P, T, V) `dtype`, rows ld >= V apart (only read): rows p and p + P are the two views of utterance p.  in_len (2P) int32 ON
+ * THE DEVICE, clamped to [0, T]; n_p = min(in_len[p], in_len[p + P]).  For t < n_p, with y = softmax(x[., t]) of each view:
+ *   J[p, t] = 1/2 (KL(sg(y_b) || y_a) + KL(sg(y_a) || y_b)) = 1/2 sum_v (y_a - y_b)(log y_a - log y_b)     (sg: the target is a constant)
+ *   pair_loss[p] = sum_{t < n_p} J[p, t];   d pair_loss[p] / d x[p, t] = 1/2 (y_a - y_b),  d pair_loss[p] / d x[p + P, t] = 1/2 (y_b - y_a)
+ * frame_loss (P, T) f32 = J (0 for t >= n_p), pair_loss (P) f32 = its sum in frame order.  No atomics: two runs write the same bytes.
+ * Both rows go through one instruction sequence: identical views give exactly 0, swapped views swapped bytes, and an f32 gradient
+ * of view b is the exact negation of view a's.
+ * grad (optional; 2P, T, V, laid out like the logits, NOT overlapping them): scale = grad_scale, or grad_scale / *grad_scale_div (a
+ *   DEVICE f32 scalar), as asr_ctc_fwd_bwd.
+ *   accumulate = 0: every cell [.., :V] is written, zeros for frames t >= n_p.
+ *   accumulate = 1: the cells of frames t < n_p are read, added to in f32 and rounded once to `dtype`; frames t >= n_p are not touched.
+ *   Columns V .. ld are never touched.
+ * One workgroup per (pair, frame).  V <= ASR_CR_CTC_RESIDENT_MAX_V: both rows stay in registers from the load to the gradient store;
+ * above it they are read three times.  16-byte accesses when V and ld are multiples of 16 / sizeof(element) and both blocks are
+ * 16-byte aligned, element accesses otherwise.  The exponentials are f32; their sums, the probabilities and J are carried in fp64 and
+ * rounded once (with peaked posteriors one f32 rounding of a sum moves J by more than its f32 spacing).  A -inf logit is outside the
+ * contract.
+ * Refused before any launch (ASR_EINVAL; ASR_EDTYPE): null logits / in_len / frame_loss / pair_loss, pointers not aligned to their
+ *   element, P outside [1, 65535], T <= 0, V < 2, ld < V, a dtype other than f32 / bf16, a gradient block that overlaps the logits,
+ *   accumulate other than 0 / 1 or without a gradient block, a non-finite grad_scale.
+ */
+#define ASR_CR_CTC_RESIDENT_MAX_V 6144
+int asr_cr_ctc_fwd_bwd(const void* logits, const int32_t* in_len, void* grad, float* frame_loss, float* pair_loss, int P, int T, int V,
+                       int ld, float grad_scale, const float* grad_scale_div, int accumulate, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,10 @@ Differences that come with the MI355X path:
   * `--model_name=TransformerCTC --mwer_weight=0.5` fine-tunes on the expected number of errors over the model's own n-best list (MWER):
     the loss gains mwer_weight * the mean risk of the batch and the log gains `mwer`; `--mwer_nbest=4 --mwer_beam=4 --mwer_frame_topk=7
     --mwer_blank_skip=0.98` shape the device search that makes the list.  Model-config keys like ema_decay; 0 (the default) changes nothing;
+  * `--model_name=TransformerCTC --cr_ctc_weight=0.2` trains with consistency regularisation (CR-CTC): the training loader yields two
+    views of every utterance (views=2: 2 * batch_size rows, each view under its own draw of `--spec_aug`; the dev and test loaders stay
+    at one view), the loss gains cr_ctc_weight * the mean consistency term between the two views' frame posteriors and the log gains
+    `cr`.  A model-config key like mwer_weight, and not together with it; 0 (the default) changes nothing;
   * `--synthetic=N` trains on N synthetic AISHELL-1-shaped utterances (no dataset ships with this repository);
   * `--trainer=BaseTrainer` selects the twin of Trainer/base_trainer.py instead of Trainer11.
 """
@@ -153,11 +157,20 @@ def snr_range(v):
     return v[0], v[-1]
 
 
+def loader_views(cr_ctc_weight):
+    """--cr_ctc_weight > 0: the training loader yields two views of every utterance (the model checks the value itself)."""
+    try:
+        return 2 if float(cr_ctc_weight) > 0.0 else 1
+    except (TypeError, ValueError):
+        return 1
+
+
 class _SyntheticLoader:
     """len(data) synthetic batches with the reference's batch contract, sharded by rank like the real loader."""
 
-    def __init__(self, n_utt, batch, frames, feat, vocab, seed, rank, world):
+    def __init__(self, n_utt, batch, frames, feat, vocab, seed, rank, world, views=1):
         self.args = (batch, frames, feat, vocab)
+        self.views = views      # 2: every batch twice over, [the B utterances | the same B] (the views then differ by dropout only)
         n = n_utt // batch
         self.seeds = [seed + i for i in range(n // world * world)][rank::world] if world > 1 else [seed + i for i in range(n)]
 
@@ -167,7 +180,8 @@ class _SyntheticLoader:
     def __iter__(self):
         B, T, F, V = self.args
         for s in self.seeds:
-            yield synthetic_pack(B, T, F, V, seed=s, ragged=True, device="cuda", dtype=torch.bfloat16)
+            pack = synthetic_pack(B, T, F, V, seed=s, ragged=True, device="cuda", dtype=torch.bfloat16)
+            yield pack if self.views == 1 else type(pack)({k: torch.cat([v, v]) for k, v in pack.items()})
 
 
 def train(**kwargs):                        # main.py:55-98
@@ -188,11 +202,12 @@ def train(**kwargs):                        # main.py:55-98
         from asr_chinese_e2e_amd import dist as D
         D.init(os.environ.get("ASR_DIST_BACKEND", "nccl"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
+    views = loader_views(getattr(config, "cr_ctc_weight", 0.0))
     if config.synthetic:
         vocab = Vocab.synthetic(config.synthetic_vocab)
         F = config.n_mels * config.lfr_m
-        mk = lambda n, b, seed: _SyntheticLoader(n, b, config.synthetic_frames, F, vocab.vocab_size, seed, rank, world)
-        train_iter = mk(config.synthetic, config.batch_size, 1000)
+        mk = lambda n, b, seed, views=1: _SyntheticLoader(n, b, config.synthetic_frames, F, vocab.vocab_size, seed, rank, world, views)
+        train_iter = mk(config.synthetic, config.batch_size, 1000, views)
         test_iter = mk(max(config.synthetic // 8, config.eval_batch_size), config.eval_batch_size, 5000)
         dev_iter = mk(max(config.synthetic // 8, config.eval_batch_size), config.eval_batch_size, 7000)
     else:
@@ -203,7 +218,7 @@ def train(**kwargs):                        # main.py:55-98
         train_iter = build_dataloader(batch_size=config.batch_size, part="train", augment=config.augment, speed_perturb=speed_factors(config.speed_perturb),
                                       noise=path_list(config.noise_list), rir=path_list(config.rir_list), noise_prob=float(config.noise_prob),
                                       rir_prob=float(config.rir_prob), snr_db=snr_range(config.snr_db), rir_method=str(config.rir_method),
-                                      rir_max_taps=int(config.rir_max_taps), spec_augment=str(config.spec_aug or "") or None, **common)
+                                      rir_max_taps=int(config.rir_max_taps), spec_augment=str(config.spec_aug or "") or None, views=views, **common)
         test_iter = build_dataloader(batch_size=config.eval_batch_size, part="test", augment=False, **common)
         dev_iter = build_dataloader(batch_size=config.eval_batch_size, part="dev", augment=False, **common)
 
