@@ -29,6 +29,13 @@ Additions required by BASELINE.json's north_star (not in the reference):
     data_handler.BucketedWaveLoader(views=2)) and the step's loss gains cr_ctc_weight * the mean over the pairs of the consistency term
     between the two views' frame posteriors (include/asr_hip.h: asr_cr_ctc_fwd_bwd, engine.ctc_fwd_bwd), metrics gains `cr`.
     0 (the default) launches what was launched without it.
+  * config.interctc_weight = w in (0, 1) with config.interctc_layers (TransformerCTC only): intermediate CTC - the shared CTC head is
+    also applied to the output of the listed encoder layers and the loss becomes (1 - w) CTC + w * the mean of their CTC losses;
+    config.interctc_condition adds self-conditioning: the layers' frame posteriors, projected back to d_model by
+    encoder.conditioning_layer.weight (d_model, V; no bias), are added to the next layer's input - in training and in inference
+    (include/asr_hip.h: asr_softmax_rows, asr_softmax_bwd_add; engine.encoder_fwd / encoder_bwd; the definition is
+    tests/interctc_ref.py).  metrics gains `interctc`; model.interctc_losses(pack) reports the losses without a gradient.  The defaults
+    launch what was launched without them and add no parameter.
 """
 import contextlib
 import math
@@ -76,6 +83,44 @@ def cr_ctc_setting(weight):
     if not ok:
         raise ValueError(f"cr_ctc_weight={weight!r}: a finite number >= 0 (0 = no consistency term)")
     return float(weight)
+
+
+def interctc_settings(weight, layers, condition, layer_num):
+    """(w, layers, condition) of config.interctc_weight / interctc_layers / interctc_condition for an encoder of layer_num layers;
+    ValueError unless w is a finite number in [0, 1), the layers - a tuple or list of ints, or a string like "3" or "2,4" - are strictly
+    increasing 1-based encoder layers in [1, layer_num - 1], w > 0 exactly when layers are listed, and conditioning comes with layers."""
+    try:
+        ok = not isinstance(weight, (bool, str)) and math.isfinite(float(weight)) and 0.0 <= float(weight) < 1.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"interctc_weight={weight!r}: a finite number in [0, 1) (0 = no intermediate CTC)")
+    w = float(weight)
+    raw = layers
+    try:
+        if isinstance(layers, str):
+            layers = [int(t) for t in layers.split(",")] if layers.strip() else []
+        elif isinstance(layers, (tuple, list)):
+            if any(isinstance(l, bool) or not isinstance(l, (int, np.integer)) for l in layers):
+                raise ValueError
+            layers = [int(l) for l in layers]
+        elif isinstance(layers, (int, np.integer)) and not isinstance(layers, bool):      # --interctc_layers=3 parses as a number
+            layers = [int(layers)]
+        elif layers is None:
+            layers = []
+        else:
+            raise ValueError
+    except ValueError:
+        raise ValueError(f"interctc_layers={raw!r}: a tuple or list of encoder layers, or a string like '3' or '2,4'") from None
+    if any(l < 1 or l > layer_num - 1 for l in layers) or any(a >= b for a, b in zip(layers, layers[1:])):
+        raise ValueError(f"interctc_layers={raw!r}: strictly increasing 1-based encoder layers in [1, {layer_num - 1}] (layer_num = {layer_num})")
+    if not isinstance(condition, (bool, int, np.integer)) or condition not in (0, 1):
+        raise ValueError(f"interctc_condition={condition!r}: True or False")
+    if (w > 0.0) != bool(layers):
+        raise ValueError(f"interctc_weight={w} with interctc_layers={tuple(layers)}: a weight > 0 needs layers, and layers need a weight > 0")
+    if condition and not layers:
+        raise ValueError("interctc_condition needs interctc_layers")
+    return w, tuple(layers), bool(condition)
 
 
 def _set_nested(root, dotted, value, is_buffer=False):
@@ -144,6 +189,13 @@ class _SpeechTransformer(BaseModel):
             raise ValueError("cr_ctc_weight > 0 needs the CTC-only model (TransformerCTC): the consistency term is defined on the CTC head's posteriors")
         if self.cr_ctc_weight > 0.0 and self.mwer_weight > 0.0:
             raise ValueError("cr_ctc_weight > 0 together with mwer_weight > 0 is not implemented: both add a gradient on top of the CTC gradient")
+        self.interctc_weight, self.interctc_layers, self.interctc_condition = interctc_settings(
+            getattr(c, "interctc_weight", 0.0), getattr(c, "interctc_layers", ()), getattr(c, "interctc_condition", False), int(c.layer_num))
+        self._interctc_mean = None   # the mean intermediate CTC loss of the last training step (device scalar), None without the term
+        if self.interctc_layers and self.use_decoder:
+            raise ValueError("interctc_weight > 0 needs the CTC-only model (TransformerCTC): intermediate CTC for the joint model is not implemented")
+        if self.interctc_layers and (self.mwer_weight > 0.0 or self.cr_ctc_weight > 0.0):
+            raise ValueError("interctc_weight > 0 together with mwer_weight > 0 or cr_ctc_weight > 0 is not implemented")
         d, H, dk, ff = c.d_model, c.num_head, c.hidden_size, c.ff_size
         d_in = c.n_mels * c.lfr_m
         V = vocab.vocab_size
@@ -155,6 +207,8 @@ class _SpeechTransformer(BaseModel):
         for i in range(c.layer_num):
             blocks += E.mha_param_block(f"encoder.layer_stack.{i}.slf_attn.", H, dk, d)
             blocks += E.ffn_param_block(f"encoder.layer_stack.{i}.pos_ffn.", d, ff)
+        if self.interctc_condition:      # directly in front of the head: both become final at the same point of the backward pass
+            blocks += [[(E.COND_NAME, (d, V))]]
         if self.use_ctc:
             blocks += [[("ctc_lo.weight", (V, d))], [("ctc_lo.bias", (V,))]]
         if self.use_decoder:
@@ -197,6 +251,8 @@ class _SpeechTransformer(BaseModel):
                  "encoder.layer_norm_in.bias", "encoder.positional_encoding.pe"]
         for i in range(L):
             names += mha(f"encoder.layer_stack.{i}.slf_attn.") + ffn(f"encoder.layer_stack.{i}.pos_ffn.")
+        if self.interctc_condition:
+            names += [E.COND_NAME]
         if self.use_decoder:
             names += ["decoder.tgt_word_emb.weight", "decoder.positional_encoding.pe"]
             for i in range(L):
@@ -219,7 +275,7 @@ class _SpeechTransformer(BaseModel):
         if name.endswith(".weight"):
             if leaf in ("w_qs", "w_ks", "w_vs"):
                 return t.normal_(0.0, math.sqrt(2.0 / (d + dk)))
-            if leaf in ("fc", "linear_in", "ctc_lo"):
+            if leaf in ("fc", "linear_in", "ctc_lo", "conditioning_layer"):
                 return t.normal_(0.0, math.sqrt(2.0 / (fan_in + fan_out)))   # xavier_normal_
         bound = 1.0 / math.sqrt(fan_in)            # Linear / Conv1d default: U(+-1/sqrt(fan_in)), weights and biases
         return t.uniform_(-bound, bound)
@@ -276,6 +332,7 @@ class _SpeechTransformer(BaseModel):
         self._engine = E.Engine(f, self.config, self.V, self.use_decoder, self.use_ctc, pe)
         self._engine.mwer = dict(self._mwer) if self.mwer_weight > 0.0 else None
         self._engine.cr_ctc = self.cr_ctc_weight > 0.0
+        self._engine.interctc = (self.interctc_layers, self.interctc_weight, self.interctc_condition)
         self._flat_device = device
         self._views_checked = True
         self._grads_checked = True
@@ -476,16 +533,16 @@ class _SpeechTransformer(BaseModel):
             return (C, self.left_chunks) if C > 0 else (0, -1)
         return (self.decoding_chunk_size, self.decoding_left_chunks) if self.decoding_chunk_size > 0 else (0, -1)
 
-    def encode(self, eng, x, wave_len, training=False):
+    def encode(self, eng, x, wave_len, training=False, interctc=None):
         """Engine.encoder_fwd under encoder_mask(training): (enc (B*T, d), cache).  Inside given_encoder_output() the inference paths get
-        that output instead (cache None)."""
+        that output instead (cache None).  interctc: the labels and gradient scales of a step with intermediate CTC (Engine.encoder_fwd)."""
         if self._enc_given is not None and not training:
             enc, B, T = self._enc_given
             if x.shape[0] != B or x.shape[1] != T:
                 raise ValueError(f"the given encoder output is for (B, T) = ({B}, {T}), the batch has {tuple(x.shape[:2])}")
             return enc, None
         chunk, left = self.encoder_mask(training)
-        return eng.encoder_fwd(x, wave_len, self.attn_window, chunk, left)
+        return eng.encoder_fwd(x, wave_len, self.attn_window, chunk, left, interctc=interctc)
 
     def given_encoder_output(self, enc):
         """Context manager: the searches (forward, ctc_greedy_search, ctc_prefix_beam_search, beam_search, transcribe) use `enc`
@@ -526,6 +583,7 @@ class _SpeechTransformer(BaseModel):
         per utterance - after every push bit for bit ctc_prefix_beam_search(blank_skip=p) on the frames so far (sessions.py).
         keywords (a keywords.KeywordList; any search, not with blank_skip): keyword spotting with the audio - keyword_hits() lists per
         utterance the hits so far, as spot_keywords reports them."""
+        self._no_streamed_conditioning("stream")
         from ..stream import StreamingEncoder
         return StreamingEncoder(self, batch_size, parser=parser, source_rate=source_rate, search=search, beam_size=beam_size, frame_topk=frame_topk,
                                 context=context, context_ids=context_ids, lm=lm, timed=timed, confidence=confidence, beam_times=beam_times,
@@ -547,9 +605,14 @@ class _SpeechTransformer(BaseModel):
         counting every frame.
         keywords (a keywords.KeywordList; any search, not with blank_skip): one phrase list for all slots - keyword_hits(b) lists slot
         b's hits so far (final closes a match still open), a reopened slot starts an empty list."""
+        self._no_streamed_conditioning("sessions")
         from ..sessions import Sessions
         return Sessions(self, slots, parser=parser, search=search, beam_size=beam_size, frame_topk=frame_topk, endpoint=endpoint, source_rate=source_rate,
                         context=context, lm=lm, timed=timed, confidence=confidence, beam_times=beam_times, blank_skip=blank_skip, keywords=keywords)
+
+    def _no_streamed_conditioning(self, what):
+        if self.interctc_condition:      # the streaming tick runs its own encoder layers, without the conditioning between them
+            raise ValueError(f"model.{what}() with interctc_condition=True is not implemented: self-conditioning in the streaming encoder")
 
     def forward(self, input):
         """transformer_official.py:68-81 (inference-style forward; no gradients).  A batch without a transcript (only wave / wave_len)
@@ -965,15 +1028,25 @@ class _SpeechTransformer(BaseModel):
         pending = count_hook(n_valid, B) if count_hook is not None else None
         zero, self._zero_lazy = (self._flat.g if getattr(self, "_zero_lazy", False) else None), False
         eng.refresh_transposes(zero=zero)      # W^T copies for this step's input-gradient GEMMs (side stream, beside the forward pass)
-        enc, ecache = self.encode(eng, x, wave_len, training=True)
         batch_div = None
+        inter = None
+        w_inter = self.interctc_weight if (self.interctc_layers and self.use_ctc and not self.use_decoder) else 0.0
+        if w_inter > 0.0:
+            # the listed layers' CTC terms are scaled on the way up, so the global batch size is needed in front of the encoder here
+            if pending is not None:
+                n_valid, batch_div = pending.wait()
+                pending = None
+            share = w_inter / len(self.interctc_layers) * loss_scale
+            inter = dict(labels32=labels32, lab_len=lab_len, grad_scale=share if batch_div is not None else share / float(B), grad_scale_div=batch_div)
+        enc, ecache = self.encode(eng, x, wave_len, training=True, interctc=inter)
         if pending is not None:
             n_valid, batch_div = pending.wait()
         row_nll = nll = None
         d_enc = None
         pg = None
         ctc_done = None
-        ctc_scale = dict(grad_scale=lam * loss_scale, grad_scale_div=batch_div) if batch_div is not None else dict(grad_scale=lam * loss_scale / float(B))
+        lam_g = lam * (1.0 - w_inter)      # intermediate CTC: the final head carries 1 - w of the CTC term
+        ctc_scale = dict(grad_scale=lam_g * loss_scale, grad_scale_div=batch_div) if batch_div is not None else dict(grad_scale=lam_g * loss_scale / float(B))
         ctc_async = (self.use_decoder and self.use_ctc and eng._aux_active() and not eng.deterministic)
         if self.use_decoder:
             cross_len, Tk = self._cross(eng, input, wave_len, T)
@@ -1028,7 +1101,29 @@ class _SpeechTransformer(BaseModel):
             self._cr_mean = cr_sum / float(B // 2)
             loss = loss.clone()
             loss[0] += self.cr_ctc_weight * (2.0 * cr_sum / batch_div[0] if batch_div is not None else self._cr_mean)
+        self._interctc_mean = None
+        if w_inter > 0.0:
+            # (1 - w) CTC + w * the mean of the listed layers' CTC losses, combined on the device (no device-to-host copy, no sync); both
+            # terms are means over THIS batch, as the CTC term of loss_combine is
+            self._interctc_mean = eng.last_interctc.sum() / float(len(self.interctc_layers) * B)
+            loss = loss.clone()
+            loss[0] = (1.0 - w_inter) * loss[0] + w_inter * self._interctc_mean
         return loss, pg
+
+    def interctc_losses(self, input):
+        """The CTC loss of every utterance at the listed layers and at the top, in evaluation mode (no dropout) and without a gradient:
+        {"layers": the config's interctc_layers, "interctc": one list of B losses per listed layer, "ctc": the B final losses}.  With
+        interctc_condition the conditioning runs, as in every inference path.  The definition is tests/interctc_ref.py."""
+        if self.use_decoder or not self.use_ctc or not self.interctc_layers:
+            raise ValueError("interctc_losses needs the CTC-only model (TransformerCTC) with interctc_layers")
+        eng, x, wave_len, prep = self._prepare(input, training=False)
+        B, T, _ = x.shape
+        labels32, lab_len = prep[2], prep[4]
+        with torch.no_grad():
+            enc, cache = self.encode(eng, x, wave_len, interctc=dict(labels32=labels32, lab_len=lab_len, grad_scale=0.0, grad_scale_div=None,
+                                                                    want_grad=False))
+            nll, _ = eng.ctc_fwd_bwd(enc, wave_len, labels32, lab_len, B, T, 0.0, want_grad=False)
+        return {"layers": self.interctc_layers, "interctc": eng.last_interctc.cpu().tolist(), "ctc": nll.cpu().tolist()}
 
     def mwer_risk(self, input, nbest=None, beam_size=None, frame_topk=None, blank_skip=None):
         """The figures MWER training lowers, without a gradient: per utterance {"risk": the expected number of errors over the n-best list
@@ -1102,6 +1197,8 @@ class _SpeechTransformer(BaseModel):
             metrics.add(mwer=self._mwer_mean)                 # the mean risk of the batch, in errors per utterance
         if getattr(self, "_cr_mean", None) is not None:
             metrics.add(cr=self._cr_mean)                     # the mean consistency term of the batch's pairs
+        if getattr(self, "_interctc_mean", None) is not None:
+            metrics.add(interctc=self._interctc_mean)         # the mean CTC loss of the listed middle layers
         return metrics, None
 
     def greedy_search(self, input, decode_max_len=0):
@@ -1135,6 +1232,9 @@ class _SpeechTransformer(BaseModel):
             mwer_frame_topk = 7             # classes per frame the search looks at: mwer_beam * (mwer_frame_topk + 1) <= 64
             mwer_blank_skip = None          # a probability in (0, 1]: blank-frame skipping in front of that search
             cr_ctc_weight = 0.0             # > 0 (TransformerCTC): batches hold two views per utterance; the loss gains cr_ctc_weight * mean consistency term
+            interctc_weight = 0.0           # w in (0, 1) (TransformerCTC): the loss becomes (1 - w) CTC + w * the mean CTC loss of interctc_layers
+            interctc_layers = ()            # 1-based encoder layers in [1, layer_num - 1], strictly increasing; "3" / "2,4" from the command line
+            interctc_condition = False      # self-conditioning at those layers: adds encoder.conditioning_layer.weight (d_model, V)
 
         return ModelConfig
 

@@ -37,6 +37,7 @@ NBEST_MAX_N, NBEST_MAX_LEN, NBEST_MAX_ALTS, NBEST_EPS = 64, 256, 8, -1      # AS
 RESCORE_MAX_N, RESCORE_MAX_K, RESCORE_MAX_G, RESCORE_MAX_U = 64, 8, 65536, 1 << 20      # ASR_RESCORE_*: entries per list, feature columns, grid points, lists of asr_nbest_sweep
 MWER_MAX_N, MWER_MAX_LEN, MWER_ABSENT, MWER_LONG = 16, 255, 1, 2      # ASR_MWER_*: entries per list, tokens per entry / reference, the flags of asr_mwer_errors
 CR_CTC_RESIDENT_MAX_V = 6144      # ASR_CR_CTC_RESIDENT_MAX_V: the longest row asr_cr_ctc_fwd_bwd keeps in registers
+INTERCTC_RESIDENT_MAX_V = 6144      # ASR_INTERCTC_RESIDENT_MAX_V: the longest row asr_softmax_rows / asr_softmax_bwd_add keep in registers
 STREAM_OPEN = 0x3fffffff     # ASR_STREAM_OPEN: "length not known yet" in the streaming front end's parameter arrays
 
 P, I, F, Z, U = c_void_p, c_int, c_float, c_size_t, c_uint32
@@ -228,6 +229,8 @@ SIGNATURES = {
     "asr_ctc_mwer_lattice": (I, [P] * 10 + [I] * 9 + [P, Z, I, P]),
     "asr_ctc_mwer_grad": (I, [P, P, P, P, P] + [I] * 9 + [F, P, I, P, Z, I, P]),
     "asr_cr_ctc_fwd_bwd": (I, [P, P, P, P, P, I, I, I, I, F, P, I, I, P]),
+    "asr_softmax_rows": (I, [P, P, P, I, I, I, I, I, P]),
+    "asr_softmax_bwd_add": (I, [P, P, P, P, I, I, I, I, I, I, P]),
 }
 
 

@@ -272,6 +272,8 @@ class DataParallel:
                 metrics.add(mwer=model._mwer_mean)
             if getattr(model, "_cr_mean", None) is not None:        # config.cr_ctc_weight > 0: the mean over this rank's pairs
                 metrics.add(cr=model._cr_mean)
+            if getattr(model, "_interctc_mean", None) is not None:  # config.interctc_weight > 0: the middle layers' mean CTC loss on this rank's batch
+                metrics.add(interctc=model._interctc_mean)
             return metrics, None
         # CE was normalised by the GLOBAL token count (sum over ranks = global CE); the CTC term the kernel reports is
         # the mean over the LOCAL batch: weight it by local / global batch before the sum over ranks
@@ -291,4 +293,6 @@ class DataParallel:
             metrics.add(mwer=model._mwer_mean)
         if getattr(model, "_cr_mean", None) is not None:        # rank-local; the reduced loss is CE / CTC only, as with the MWER term
             metrics.add(cr=model._cr_mean)
+        if getattr(model, "_interctc_mean", None) is not None:  # rank-local; the reduced loss is the final head's CTC term only
+            metrics.add(interctc=model._interctc_mean)
         return metrics, None

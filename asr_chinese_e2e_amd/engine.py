@@ -26,6 +26,7 @@ from . import kernels as K
 from ._lib import ACT_NONE, ACT_RELU, ACT_RELU_MASK
 
 ALIGN = 64  # elements; keeps every block 256-byte (fp32) / 128-byte (bf16) aligned
+COND_NAME = "encoder.conditioning_layer.weight"      # (d_model, V): the self-conditioning projection of intermediate CTC, present only with config.interctc_condition
 
 
 def positional_encoding(max_len, d_model):
@@ -529,6 +530,8 @@ class Engine:
             self.kv_all.tag = "kv_all"
         if use_ctc:
             self.ctc_lo = Linear(flat, ["ctc_lo.weight"], ["ctc_lo.bias"], vocab_size, d)
+        # the self-conditioning projection of intermediate CTC (posteriors -> d_model, no bias: zero posterior rows give zero rows)
+        self.cond = Linear(flat, [COND_NAME], None, d, vocab_size) if COND_NAME in flat.index else None
         # row stride of the CTC head's logits / gradient rows in the training step: whole 128-byte lines (bf16: multiples of 64
         # elements; V = 4232 -> 4288).  With dense rows of 8464 B every row of a GEMM tile straddles one line more and shares
         # its first and last line with the neighbouring tiles: head GEMM 110 -> 94 us, its input gradient 87 -> 76 us
@@ -551,7 +554,9 @@ class Engine:
             cross_qkv = [self.kv_all] if self.dec else []
             # ... and the CTC head (reduction over V = 4232 columns: the kernel's last k-step is ragged)
             head = [self.ctc_lo] if use_ctc else []
-            lins = [l for l in lins + cross_qkv + head if l.N % 8 == 0 and l.K % 8 == 0]
+            # ... and the self-conditioning projection (its input gradient dp = e Wc is an NT product over all B*T frames)
+            cond = [self.cond] if self.cond is not None else []
+            lins = [l for l in lins + cross_qkv + cond + head if l.N % 8 == 0 and l.K % 8 == 0]
             # copies sit at the offsets of their matrices, rows N elements apart; the CTC head's (rows of V = 4232 elements = 8464 B:
             # every row starts 16 B further into a 128-byte line) goes behind them with rows padded to whole lines (self.ld_v)
             n_flat = (flat.lp.numel() + 63) // 64 * 64
@@ -587,6 +592,11 @@ class Engine:
         # ctc_fwd_bwd launches exactly what it launches without the feature
         self.cr_ctc = False
         self.last_cr = None         # (frame (P, T), cr (P)) of the last step with the consistency stage, device tensors
+        # intermediate CTC: (layers, w, condition) as the model validated them (Models/transformer_official.py: interctc_settings);
+        # without layers encoder_fwd / encoder_bwd launch exactly what they launch without the feature
+        self.interctc = ((), 0.0, False)
+        self.last_interctc = None   # (n_layers, B) f32: the listed layers' CTC loss of every utterance in the last training step
+        self._hold_marks = False    # conditioned step: no "gradient final" mark until the backward pass has issued the lowest listed layer's branch
         self._side_handle = self.side.cuda_stream
         # ---- environment switches of the engine (all read here, when the engine is built; the complete list is in README.md):
         # ASR_WGRAD_OVERLAP=0: ONE stream - weight gradients, the CTC branch and the cross-attention K|V work stay on the main stream
@@ -693,6 +703,11 @@ class Engine:
         self.flush_wgrads()
         if self.grad_ready is not None:
             self.flush_ln_reduce()
+            if self._hold_marks:
+                # self-conditioned intermediate CTC: the head and the conditioning projection sit ABOVE every encoder layer in the flat buffer
+                # and receive gradient until the backward pass has issued the lowest listed layer's branch (_interctc_bwd); a mark raised
+                # before that would send their bucket out incomplete.  Skipping a mark is safe: the next one covers it
+                return
             streams = [torch.cuda.current_stream()] + ([self.side] if self.overlap_wgrad else [])
             self.grad_ready(self.flat.index[name][0], streams)
 
@@ -987,9 +1002,12 @@ class Engine:
         return dx, dz
 
     # ------------------------------------------------------------------ encoder
-    def encoder_fwd(self, wave, wave_len, window=-1, chunk=0, left_chunks=-1):
+    def encoder_fwd(self, wave, wave_len, window=-1, chunk=0, left_chunks=-1, interctc=None):
         """wave (B,T,F) in the compute dtype, wave_len (B) int32.  transformer_official.py:158-189.
-        chunk > 0: chunk-masked self-attention (chunk frames, left_chunks chunks of left context, -1 = all; asr_hip.h)."""
+        chunk > 0: chunk-masked self-attention (chunk frames, left_chunks chunks of left context, -1 = all; asr_hip.h).
+        interctc (a training step with self.interctc layers): dict(labels32, lab_len, grad_scale, grad_scale_div) - the listed layers'
+        CTC loss and gradient are computed on the way up (_interctc_fwd); with want_grad=False in it only the losses
+        (self.last_interctc).  None: no loss; self-conditioning, being part of the model, still runs."""
         if chunk > 0 and window >= 0:
             raise ValueError("encoder_fwd: a chunk mask and an attention window are mutually exclusive")
         B, T, F = wave.shape
@@ -998,6 +1016,11 @@ class Engine:
         self._ln_pending.clear()     # its flush) must not be launched into this step's gradients
         self._disarm()               # ... nor may its arm skip this step's first hand-over (refresh_transposes clears it too)
         self._release_kept()
+        self._hold_marks = False
+        layers, _, condition = self.interctc
+        if interctc is not None and layers:
+            self.last_interctc = torch.empty(len(layers), B, dtype=torch.float32, device=wave.device)
+            self._hold_marks = condition and interctc.get("want_grad", True)
         x_in = wave.reshape(B * T, F)
         e0 = self.lin_in.fwd(x_in)
         p0, s0 = self._drop(1)             # dropout(LN(linear_in(x)) + PE)  (transformer_official.py:175-177)
@@ -1008,7 +1031,73 @@ class Engine:
             h1, c1 = self._attn_block_fwd(mha, h, h, B, T, T, wave_len, wave_len, mask, cross=False, site=10 + 4 * i)
             h, c2 = self._ffn_block_fwd(ffn, h1, B, T, wave_len, site=12 + 4 * i)
             cache["layers"].append((c1, c2))
+            if (i + 1) in layers and (interctc is not None or condition):
+                h, c3 = self._interctc_fwd(h, wave_len, B, T, layers.index(i + 1), interctc)
+                cache.setdefault("inter", {})[i] = c3
         return h, cache
+
+    # ------------------------------------------------------------------ intermediate CTC (config.interctc_*; the definition is tests/interctc_ref.py)
+    def _cond_fwd(self, p, h):
+        """h + p Wc^T, out of place (h is the layer's cached output)."""
+        c = self.cond
+        if h.dtype == torch.float32:
+            return K.gemm_f32(p, c.w32, h.clone(), trans_b=True, accumulate=True)
+        out = torch.empty_like(h)
+        if K.gemm_nt_supported(p.shape[0], c.N, c.K, p.stride(0), c.wlp.stride(0), out.stride(0)) and p.data_ptr() % 16 == 0:
+            return K.gemm_nt(p, c.wlp, None, out, res=h)      # the residual add in the NT kernel's store tail
+        # bf16 shapes the bf16 kernels refuse (an odd vocabulary): through the fp32 kernel, one rounding of the sum
+        acc = K.gemm_f32(p.float(), c.wlp.float(), h.float(), trans_b=True, accumulate=True)
+        out.copy_(acc)
+        return out
+
+    def _interctc_fwd(self, h, wave_len, B, T, j, ic):
+        """The branch at a listed layer, h (B*T, d) its output.  Returns (the next layer's input, cache for _interctc_bwd or None).
+        ic None: inference - only the conditioning.  Training: the shared head's logits in a padded block (self.ld_v), with
+        conditioning their softmax FIRST (the CTC gradient overwrites the logits in place), then the CTC kernels.  Without conditioning the
+        branch ends here: head weight / bias gradient, its input gradient kept for the backward pass, the big block released.  With
+        conditioning p, g and h stay alive until _interctc_bwd."""
+        _, _, condition = self.interctc
+        V, ld = self.V, self.ld_v
+        buf = torch.empty(B * T, ld, dtype=h.dtype, device=h.device)
+        logits = self.ctc_lo.fwd(h, out=buf[:, :V])
+        frames = buf.view(B, T, ld)[:, :, :V]
+        p = None
+        if condition:
+            pbuf = torch.empty_like(buf)
+            K.softmax_rows(frames, wave_len, out=pbuf.view(B, T, ld)[:, :, :V])
+            p = pbuf[:, :V]
+        if ic is None:
+            return self._cond_fwd(p, h), None
+        self._disarm()      # the hand-over of the head's weight gradient below is the plain fork
+        want_grad = ic.get("want_grad", True)
+        K.ctc_fwd_bwd(frames, wave_len, ic["labels32"], ic["lab_len"], self.ws, blank=0, grad_scale=ic["grad_scale"],
+                      dlogits=frames if want_grad else None, want_grad=want_grad, grad_scale_div=ic["grad_scale_div"], nll=self.last_interctc[j])
+        if not want_grad:      # the losses alone (model.interctc_losses)
+            return (self._cond_fwd(p, h) if condition else h), None
+        g = logits      # the gradient was written in place
+        if not condition:
+            self._wgrad(self.ctc_lo, g, h, bias_from=g)
+            self.wait_transposes()
+            return h, dict(d_inter=self.ctc_lo.dgrad(g))
+        return self._cond_fwd(p, h), dict(p=p, g=g, h=h)
+
+    def _interctc_bwd(self, c, dy, dy2, B, T, lens):
+        """The gradient pair at the boundary above a listed layer -> the pair that enters the layer's feed-forward block."""
+        self._disarm()
+        if "d_inter" in c:      # plain intermediate CTC: one add (both slots of the pair are taken below the top layer)
+            if dy2 is None:
+                return dy, c["d_inter"]
+            return K.rows_scatter_add(c["d_inter"], dy, B, T, T), dy2
+        # self-conditioning: e = dL/dh' reaches h through the identity, and through p = softmax(ctc_lo(h)) Wc^T
+        p, g, h = c["p"], c["g"], c["h"]
+        V, ld = self.V, self.ld_v
+        e = dy if dy2 is None else K.rows_scatter_add(dy2, dy, B, T, T)      # dy is the fresh output of the layer above's input-gradient GEMM
+        self._wgrad(self.cond, e, p)
+        dpbuf = torch.empty(B * T, ld, dtype=e.dtype, device=e.device)
+        self.cond.dgrad(e, out=dpbuf[:, :V])
+        K.softmax_bwd_add(p.view(B, T, V), dpbuf[:, :V].view(B, T, V), lens, g.view(B, T, V), accumulate=True)
+        self._wgrad(self.ctc_lo, g, h, bias_from=g)
+        return e, self.ctc_lo.dgrad(g)
 
     def encoder_bwd(self, cache, d_enc):
         B, T = cache["B"], cache["T"]
@@ -1017,6 +1106,11 @@ class Engine:
         for i in reversed(range(self.L)):
             mha, ffn = self.enc[i]
             c1, c2 = cache["layers"][i]
+            c3 = cache.get("inter", {}).get(i)
+            if c3 is not None:
+                dy, dy2 = self._interctc_bwd(c3, dy, dy2, B, T, c2["lens"])
+                if (i + 1) == self.interctc[0][0]:      # the lowest listed layer: the head's and the conditioning projection's gradients are all issued
+                    self._hold_marks = False
             dx, dz = self._ffn_block_bwd(ffn, c2, dy, dy2)
             if i == 0:      # finer mark inside the last layer: its feed-forward gradients can leave while attention runs
                 self._ready(self.tail_mark_name())

@@ -2128,3 +2128,55 @@ def cr_ctc(logits, in_len, grad_scale=1.0, grad_scale_div=None, dlogits=None, ac
                                int(bool(accumulate)), _dt(logits), _stream()),
         "asr_cr_ctc_fwd_bwd"), float(R) * T * V * e * (1.0 + (0.0 if dlogits is None else 2.0 if accumulate else 1.0)))
     return {"cr": cr, "frame": frame, "dlogits": dlogits}
+
+
+# --------------------------------------------------------------------------------- intermediate CTC: the conditioning's softmax (csrc/interctc.hip)
+INTERCTC_RESIDENT_MAX_V = _lib.INTERCTC_RESIDENT_MAX_V
+
+
+def _like_frames(name, what, t, logits):
+    if t.shape != logits.shape or t.stride() != logits.stride() or t.dtype != logits.dtype or t.device != logits.device:
+        raise ValueError(f"{name}: {what} {tuple(t.shape)} {t.stride()} {t.dtype} is not laid out like "
+                         f"{tuple(logits.shape)} {logits.stride()} {logits.dtype}")
+
+
+def softmax_rows(logits, in_len, out=None):
+    """Frame posteriors (asr_softmax_rows; the definition is tests/interctc_ref.py).  logits (B, T, V) f32 / bf16, dense or rows padded
+    as the engine lays them out (only read); in_len (B) int32.  Returns `out`, laid out like the logits: softmax over the V classes on
+    the frames t < in_len[b], zeros on the others; padding columns are not written.  out: a block laid out like the logits that does
+    not overlap them; None: a fresh one."""
+    if logits.dim() != 3:
+        raise ValueError(f"softmax_rows: logits {tuple(logits.shape)}: (B, T, V)")
+    B, T, V = logits.shape
+    ld = _frame_rows(logits)
+    _chk_i32(in_len)
+    if in_len.numel() != B:
+        raise ValueError(f"softmax_rows: in_len {tuple(in_len.shape)} for logits {tuple(logits.shape)}")
+    if out is None:
+        out = torch.empty_strided(logits.shape, logits.stride(), dtype=logits.dtype, device=logits.device)
+    else:
+        _like_frames("softmax_rows", "out", out, logits)
+    e = logits.element_size()
+    timed("softmax_rows", 0.0, lambda: check(
+        lib.asr_softmax_rows(_p(logits), _p(in_len), _p(out), B, T, V, ld, _dt(logits), _stream()), "asr_softmax_rows"), 2.0 * B * T * V * e)
+    return out
+
+
+def softmax_bwd_add(p, dp, in_len, grad, accumulate=True):
+    """Backward of softmax_rows (asr_softmax_bwd_add): grad[b, t] (+)= p (dp - sum_u p[u] dp[u]) on the frames t < in_len[b]; the other
+    frames are untouched under accumulate and zeroed otherwise.  p, dp, grad (B, T, V) f32 / bf16 laid out alike; grad overlaps
+    neither p nor dp.  Returns grad."""
+    if p.dim() != 3:
+        raise ValueError(f"softmax_bwd_add: p {tuple(p.shape)}: (B, T, V)")
+    B, T, V = p.shape
+    ld = _frame_rows(p)
+    _chk_i32(in_len)
+    if in_len.numel() != B:
+        raise ValueError(f"softmax_bwd_add: in_len {tuple(in_len.shape)} for p {tuple(p.shape)}")
+    _like_frames("softmax_bwd_add", "dp", dp, p)
+    _like_frames("softmax_bwd_add", "grad", grad, p)
+    e = p.element_size()
+    timed("softmax_bwd_add", 0.0, lambda: check(
+        lib.asr_softmax_bwd_add(_p(p), _p(dp), _p(in_len), _p(grad), B, T, V, ld, int(bool(accumulate)), _dt(p), _stream()),
+        "asr_softmax_bwd_add"), (4.0 if accumulate else 3.0) * B * T * V * e)
+    return grad

@@ -1489,6 +1489,30 @@ int asr_ctc_mwer_grad(void* dlogits, const int32_t* in_len, const int32_t* hyp, 
 int asr_cr_ctc_fwd_bwd(const void* logits, const int32_t* in_len, void* grad, float* frame_loss, float* pair_loss, int P, int T, int V,
                        int ld, float grad_scale, const float* grad_scale_div, int accumulate, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Intermediate CTC with self-conditioning: the frame posteriors of a middle layer and the backward pass of their softmax
+ * (additive to ABI 10; csrc/interctc.hip, kernels.softmax_rows / softmax_bwd_add, engine.encoder_fwd / encoder_bwd).
+ * Stands in for:  nothing in the reference.  The definition is tests/interctc_ref.py (float64, torch on the CPU).
+ *
+ * Both work on (B, T, V) frames of `dtype` in rows ld >= V elements apart, every block of a call laid out alike, and on in_len (B) int32
+ * ON THE DEVICE, clamped to [0, T].  One workgroup per frame; V <= ASR_INTERCTC_RESIDENT_MAX_V: the row (for the backward both rows)
+ * stays in registers from the load to the store, above it the rows are read once per pass.  16-byte accesses when V and ld are
+ * multiples of 16 / sizeof(element) and every block is 16-byte aligned, element accesses otherwise.  Exponentials and products are
+ * f32, the row sums fp64, one rounding to `dtype`.  No atomics: two runs write the same bytes.  Columns V .. ld are never touched.
+ *
+ * asr_softmax_rows:  out[b, t, :V] = softmax(logits[b, t, :V]) for t < in_len[b], zeros for t >= in_len[b].  A -inf logit gives
+ *   exactly 0; a row whose maximum is not finite gets zeros.  `out` must not overlap the logits.
+ * asr_softmax_bwd_add:  for t < in_len[b]:  grad[b, t, v] = (accumulate ? grad[b, t, v] : 0) + p[v] (dp[v] - sum_u p[u] dp[u]);
+ *   frames t >= in_len[b] are not touched under accumulate = 1 and get zeros under accumulate = 0.  Where p is 0 the term is exactly 0.
+ *   `grad` must overlap neither p nor dp.
+ * Refused before any launch (ASR_EINVAL; ASR_EDTYPE): a null pointer, pointers not aligned to their element, B outside [1, 65535],
+ *   T <= 0, V <= 0, ld < V, a dtype other than f32 / bf16, accumulate other than 0 / 1, overlapping blocks as stated.
+ */
+#define ASR_INTERCTC_RESIDENT_MAX_V 6144
+int asr_softmax_rows(const void* logits, const int32_t* in_len, void* out, int B, int T, int V, int ld, int dtype, void* stream);
+int asr_softmax_bwd_add(const void* p, const void* dp, const int32_t* in_len, void* grad, int B, int T, int V, int ld, int accumulate,
+                        int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,10 @@ Differences that come with the MI355X path:
     views of every utterance (views=2: 2 * batch_size rows, each view under its own draw of `--spec_aug`; the dev and test loaders stay
     at one view), the loss gains cr_ctc_weight * the mean consistency term between the two views' frame posteriors and the log gains
     `cr`.  A model-config key like mwer_weight, and not together with it; 0 (the default) changes nothing;
+  * `--model_name=TransformerCTC --interctc_weight=0.3 --interctc_layers=3 --interctc_condition=1` trains with intermediate CTC: the
+    shared CTC head is also applied to the output of the listed encoder layers (`--interctc_layers=2,4` lists two), the loss becomes
+    (1 - w) CTC + w * the mean of their CTC losses and the log gains `interctc`; `--interctc_condition=1` adds self-conditioning (one more
+    parameter, encoder.conditioning_layer.weight).  Model-config keys like mwer_weight, and not together with it or with cr_ctc_weight;
   * `--synthetic=N` trains on N synthetic AISHELL-1-shaped utterances (no dataset ships with this repository);
   * `--trainer=BaseTrainer` selects the twin of Trainer/base_trainer.py instead of Trainer11.
 """
