@@ -29,12 +29,6 @@ constexpr int AL_MAXL = ASR_ALIGN_LONG_MAX_LABELS;
 constexpr int AL_F = 128;         // frames per staged backtrace window
 constexpr int AL_WB = AL_F + 8;   // bytes per window row: AL_F + 1 columns, the start aligned down to 4, rounded up to 8
 
-__device__ __forceinline__ double al_shr1(double v) {   // lane i <- lane i-1 (two 32-bit DPP moves); lane 0 gets 0
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x138, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
 template <typename T> __device__ __forceinline__ float al_ld(const T* p) { return to_f32<T>(*p); }
 
 template <int P> struct al_code;
@@ -177,7 +171,7 @@ __global__ __launch_bounds__(al_threads(P)) void ctc_align_long_kernel(const T* 
             const int t = t0 + k;
             if (t >= Tn) break;      // uniform
             double up = -INFINITY;
-            if (active) up = al_shr1(lb[P - 1]);
+            if (active) up = wave_shr1(lb[P - 1]);
             if (NW > 1) {
                 if (active && lane == 63) s_x[t & 1][wave + 1] = lb[P - 1];
                 __syncthreads();

@@ -93,6 +93,39 @@ template <> __device__ __forceinline__ void store8<bf16_t>(bf16_t* p, const floa
     *(bf16x8*)p = v;
 }
 
+template <typename T> struct Vec {
+    static constexpr int N = 16 / sizeof(T);  // elements per 16-byte access
+};
+
+// N consecutive elements <-> fp32 (N = Vec<T>::N: one 16-byte access; N = 1: one element)
+template <typename T, int N>
+__device__ __forceinline__ void loadv(const T* p, float (&r)[N]) {
+    if constexpr (N == 1) {
+        r[0] = to_f32<T>(p[0]);
+    } else if constexpr (sizeof(T) == 2) {
+        load8<T>(p, r);
+    } else {
+        f32x4 v = *(const f32x4*)p;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = v[i];
+    }
+}
+template <typename T, int N>
+__device__ __forceinline__ void storev(T* p, const float (&r)[N]) {
+    if constexpr (N == 1) {
+        p[0] = from_f32<T>(r[0]);
+    } else if constexpr (sizeof(T) == 2) {
+        store8<T>(p, r);
+    } else {
+        f32x4 v = {r[0], r[1], r[2], r[3]};
+        *(f32x4*)p = v;
+    }
+}
+
+// the two bf16 halves of a 32-bit word of a packed row, as fp32
+__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
+__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
+
 // ---- wave-level reductions (64 lanes, DPP/shuffle, no LDS) ----------------------------------
 // Wave-wide reductions on the vector ALU's lane crossbar (DPP), result in every lane: four butterfly steps inside each row of
 // 16 lanes (quad swaps, half-row and row mirrors), two row broadcasts, one v_readlane.  As six __shfl_xor steps each of them was a
@@ -147,6 +180,41 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     float r = red[0];
     for (int i = 1; i < nw; ++i) r = fmaxf(r, red[i]);
     return r;
+}
+
+// block-wide fp64 sum for a block of THREADS threads; `red` is THREADS / 64 doubles of LDS.  Fixed order (xor butterfly, then the waves in
+// order): every lane gets the same bits, two runs the same bits.  Contains two barriers.
+template <int THREADS>
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+    ASR_FULL_WAVES(THREADS);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    double r = 0.0;
+#pragma unroll
+    for (int i = 0; i < THREADS / 64; ++i) r += red[i];
+    return r;
+}
+
+// (value, index) pair reduction over the wave: larger value wins, equal values -> smaller index (torch.argmax's tie rule)
+__device__ __forceinline__ void wave_argmax_first(float& v, int& i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float v2 = __shfl_xor(v, o, 64);
+        const int i2 = __shfl_xor(i, o, 64);
+        if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
+    }
+}
+
+// Whole-wave shift by one lane through DPP (no LDS round trip as ds_bpermute would need): lane i <- lane i-1 (two 32-bit DPP moves),
+// lane 0 gets 0.  The whole wave executes it.
+__device__ __forceinline__ double wave_shr1(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x138, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
 }
 
 __device__ __forceinline__ float log_add(float a, float b) {

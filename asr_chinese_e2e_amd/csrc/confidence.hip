@@ -9,19 +9,6 @@
 
 namespace {
 
-__device__ __forceinline__ float cbf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float cbf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-
-// (value, index) pair reduction over the wave, as session.hip's: larger value wins, equal values -> smaller index
-__device__ __forceinline__ void wave_argmax_first(float& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float v2 = __shfl_xor(v, o, 64);
-        const int i2 = __shfl_xor(i, o, 64);
-        if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-    }
-}
-
 // One wave per frame: frame_best_blank_kernel's two passes (its argmax pass, its order of the sum of exponentials - path and blank_lp have
 // that kernel's bits), the second pass also summing u = sum (x - m) e^(x - m): H = ln s - u / s.  A class whose exponential is 0 (a -inf
 // logit, an underflow) adds nothing to u: (-inf) * 0 is never formed.
@@ -49,7 +36,7 @@ __global__ __launch_bounds__(256) void frame_stats_kernel(const T* __restrict__ 
                 const u32x4 q = *(const u32x4*)(x + (size_t)k * 8);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float lo = cbf16_lo(q[j]), hi = cbf16_hi(q[j]);
+                    const float lo = bf16_lo(q[j]), hi = bf16_hi(q[j]);
                     if (lo > best) { best = lo; bi = k * 8 + 2 * j; }
                     if (hi > best) { best = hi; bi = k * 8 + 2 * j + 1; }
                 }

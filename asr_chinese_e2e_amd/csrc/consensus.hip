@@ -1,49 +1,31 @@
 // Consensus decoding of n-best lists (include/asr_hip.h: asr_nbest_consensus; the definition is tests/consensus_ref.py, and the kernels
 // agree with it integer for integer).  Three launches on one stream, no atomics, a fixed order everywhere: two runs write the same bytes.
 //
-// 1. nbest_pair_dist_kernel: one wave per (utterance, pair i < k).  The distance-only forward pass of score.hip: lanes own the columns
-//    of h_k, 64 at a time, the rows of h_i run serially, D[i][j] - j is the prefix minimum of t[k] - k (a wave min-scan on DPP) and the
-//    block's left boundary column, m + 1 ints of LDS, is the carry between column blocks.  Writes d[u][i][k] and d[u][k][i]; one more
-//    workgroup per utterance writes the diagonal.
+// 1. nbest_pair_dist_kernel: one wave per (utterance, pair i < k).  The distance-only forward pass of edit_wave.h, h_i on the row side
+//    and h_k on the column side.  Writes d[u][i][k] and d[u][k][i]; one more workgroup per utterance writes the diagonal.
 // 2. nbest_pivot_votes_kernel: one wave per (utterance, entry k).  Every wave recomputes the utterance's risks from d (lane i sums over k
 //    in index order, int64) and takes the pivot by a wave argmin on (risk, i), so no launch stands between the risks and their use.  It
-//    aligns h_k to the pivot (the pivot is the row side) with the two direction bits of a cell as ballot masks in LDS, 16 bytes per (row,
-//    column block): at most 256 * 4 * 16 = 16 KB.  Lane 0 walks back from (m, n) and writes h_k's votes into an LDS image of the 2 m + 1
+//    aligns h_k to the pivot (the pivot is the row side; edit_wave.h with its masks sink) with the two direction bits of a cell as ballot
+//    masks in LDS, 16 bytes per (row, column block): at most 256 * 4 * 16 = 16 KB.  Lane 0 walks back from (m, n) and writes h_k's votes into an LDS image of the 2 m + 1
 //    slots; the walk meets an insertion run last token first, so the LAST write into a gap's slot is the run's first token and every
 //    earlier one is an extra insertion.  The wave then copies the image out.
 // 3. nbest_slot_vote_kernel: one wave per (utterance, slot).  Lane k holds entry k's vote and weight.  A 64-step v_readlane sweep gives
 //    every lane its group's weight and leader (the lowest lane with the same vote); a second sweep ranks the leaders by (weight
 //    descending, lane ascending); the top A write (token, weight).
 //
-// The DPP helpers are copies of score.hip's (that file stays as it is).  PRECONDITION of all of them and of the v_readlane sweeps: the
-// whole wave executes them - every loop around them has wave-uniform bounds, and a wave that leaves early leaves as a whole.
+// PRECONDITION of the forward pass and of the v_readlane sweeps: the whole wave executes them - every loop around them has wave-uniform
+// bounds, and a wave that leaves early leaves as a whole.
 #include <limits.h>
 
 #include "asr_common.h"
+#include "edit_wave.h"
 
 namespace {
 
-constexpr int NBEST_BIG = 0x3fffffff;
 constexpr int NBEST_EPS = ASR_NBEST_EPS;
 constexpr int NBEST_NB = ASR_NBEST_MAX_LEN / 64;      // column blocks of the longest hypothesis
 
 __host__ __device__ __forceinline__ int nbest_len(int v, int L) { return v < 0 ? -1 : (v > L ? L : v); }      // -1: absent
-
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ int nbest_dpp_keep(int v) {      // a lane without a source, or in a masked row, keeps v
-    return __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ int nbest_scan_min(int v) {      // inclusive prefix minimum over the 64 lanes
-    v = min(v, nbest_dpp_keep<0x111>(v));            // row_shr:1
-    v = min(v, nbest_dpp_keep<0x112>(v));            // row_shr:2
-    v = min(v, nbest_dpp_keep<0x114>(v));            // row_shr:4
-    v = min(v, nbest_dpp_keep<0x118>(v));            // row_shr:8
-    v = min(v, nbest_dpp_keep<0x142, 0xA>(v));       // row_bcast15 into rows 1 and 3
-    v = min(v, nbest_dpp_keep<0x143, 0xC>(v));       // row_bcast31 into rows 2 and 3
-    return v;
-}
-// lane l takes v of lane l - 1, lane 0 takes `first` (wave_shr:1)
-__device__ __forceinline__ int nbest_shift_in(int v, int first) { return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xf, 0xf, false); }
 
 // Output layout, in int32 words from `out` (8-byte aligned; the risks come first because they are int64).  S = 2 L + 1.
 struct NbestLayout {
@@ -73,51 +55,6 @@ struct NbestArgs {
     int32_t* out;
 };
 
-// The forward pass of the definition for rows r[0..m) and columns h[0..n), m, n <= ASR_NBEST_MAX_LEN: returns D[m][n] in every lane.
-// carryD: m + 1 ints of LDS.  DIRS: the direction masks of cell (i, j), i, j >= 1, go to dir[(i - 1) * nb + (j - 1) / 64].
-template <bool DIRS>
-__device__ __forceinline__ int nbest_forward(const int32_t* __restrict__ r, int m, const int32_t* __restrict__ h, int n, int* carryD, ulonglong2* dir, int lane) {
-    const int nb = (n + 63) >> 6;
-    for (int i = lane; i <= m; i += 64) carryD[i] = i;
-    __syncthreads();
-    int Dfin = m;      // n == 0
-    for (int jb = 0; jb < nb; ++jb) {
-        const int c0 = jb << 6, j = c0 + lane + 1;
-        const bool valid = j <= n, more = jb + 1 < nb;
-        const int hj = valid ? h[j - 1] : 0;
-        int Dp = j;       // row 0: D = j
-        int dD = c0;      // the boundary column one row up
-        int rblk = 0;
-        int nextD = carryD[min(1, m)];      // the boundary column is read one row ahead of its use
-        for (int i = 1; i <= m; ++i) {
-            const int ii = (i - 1) & 63;
-            if (ii == 0) rblk = i - 1 + lane < m ? r[i - 1 + lane] : 0;
-            const int ri = __builtin_amdgcn_readlane(rblk, ii);
-            const int cinD = nextD;
-            nextD = carryD[min(i + 1, m)];      // row i + 1 is rewritten one iteration from now
-            const int Dd = nbest_shift_in(Dp, dD);
-            const int sub = ri != hj;
-            int v = valid ? min(Dp + 1, Dd + sub) - j : NBEST_BIG;
-            v = min(nbest_scan_min(v), cinD - c0);
-            const int Dc = v + j;
-            if (DIRS) {
-                const bool isDiag = Dd + sub == Dc, isUp = !isDiag && Dp + 1 == Dc;
-                const int code = isDiag ? sub : (isUp ? ASR_EDIT_DEL : ASR_EDIT_INS);
-                ulonglong2 mk;
-                mk.x = __ballot(valid && (code & 1));
-                mk.y = __ballot(valid && (code & 2));
-                if (lane == 0) dir[(i - 1) * nb + jb] = mk;
-            }
-            if (more && lane == 63) carryD[i] = Dc;
-            dD = cinD;
-            Dp = Dc;
-        }
-        __syncthreads();
-        if (!more) Dfin = __shfl(Dp, (n - 1) & 63, 64);
-    }
-    return Dfin;
-}
-
 __global__ __launch_bounds__(64) void nbest_pair_dist_kernel(NbestArgs a, size_t off_d) {
     __shared__ int carryD[ASR_NBEST_MAX_LEN + 1];
     const int u = blockIdx.y, lane = threadIdx.x, N = a.N;
@@ -138,7 +75,8 @@ __global__ __launch_bounds__(64) void nbest_pair_dist_kernel(NbestArgs a, size_t
     int dist = 0;      // a pair with an absent side
     if (m >= 0 && n >= 0) {
         const int32_t* row = a.tok + (size_t)u * a.ldu;
-        dist = nbest_forward<false>(row + (size_t)i * a.ldn, m, row + (size_t)k * a.ldn, n, carryD, nullptr, lane);
+        EditSinkNone none;
+        dist = edit_wave_forward(row + (size_t)i * a.ldn, m, row + (size_t)k * a.ldn, n, carryD, lane, none);
     }
     if (lane == 0) {
         d[i * N + k] = dist;
@@ -196,7 +134,8 @@ __global__ __launch_bounds__(64) void nbest_pivot_votes_kernel(NbestArgs a, Nbes
     const int32_t* h = row + (size_t)k * a.ldn;
     for (int j = lane; j < n; j += 64) hk[j] = h[j];
     for (int s = lane; s < S; s += 64) image[s] = NBEST_EPS;
-    (void)nbest_forward<true>(row + (size_t)pivot * a.ldn, m, h, n, carryD, dir, lane);
+    EditSinkMasks masks{dir};
+    (void)edit_wave_forward(row + (size_t)pivot * a.ldn, m, h, n, carryD, lane, masks);
     __syncthreads();
     if (lane == 0) {
         const int nb = (n + 63) >> 6;
@@ -205,11 +144,7 @@ __global__ __launch_bounds__(64) void nbest_pivot_votes_kernel(NbestArgs a, Nbes
             int code;
             if (i == 0) code = ASR_EDIT_INS;
             else if (j == 0) code = ASR_EDIT_DEL;
-            else {
-                const ulonglong2 mk = dir[(i - 1) * nb + ((j - 1) >> 6)];
-                const int bit = (j - 1) & 63;
-                code = (int)((mk.x >> bit) & 1ull) | ((int)((mk.y >> bit) & 1ull) << 1);
-            }
+            else code = edit_wave_code_at(dir[(i - 1) * nb + ((j - 1) >> 6)], j);
             if (code == ASR_EDIT_INS) {
                 extra += gap == i;
                 gap = i;

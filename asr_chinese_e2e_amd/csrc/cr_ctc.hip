@@ -5,7 +5,7 @@
 //   1. cr_ctc_kernel   : one workgroup of 256 threads per (pair, frame).  Loads the frame's row of BOTH views once (16 B per thread and
 //      load; element by element when V is no multiple of the vector), per row block_max and the block's sum of exp(x - max), then per
 //      element p = exp(x - max) / sum, lp = x - lse, J += (p_a - p_b) (lp_a - lp_b), g = scale/2 (p_a - p_b) -> row a, -g -> row b.
-//      The exponentials are f32 (expf); their sum, p, lp and J are carried in fp64 (see the note at block_sum_f64).  A row of up
+//      The exponentials are f32 (expf); their sum, p, lp and J are carried in fp64 (see the note below).  A row of up
 //      to CR_RESIDENT_MAX_V elements stays in registers from the load to the gradient store (CR_E values per thread and row); a longer one
 //      is read again for each of the three passes (it is L2-hot), with the same element-to-thread mapping, so that a thread adds the
 //      same terms in the same order on both paths.  Both rows go through one instruction sequence: identical views give exactly 0,
@@ -21,52 +21,11 @@ constexpr int CR_E = ASR_CR_CTC_RESIDENT_MAX_V / CR_THREADS;      // elements pe
 static_assert(CR_E * CR_THREADS == ASR_CR_CTC_RESIDENT_MAX_V && CR_E % 8 == 0, "the resident cap is whole 16-byte vectors per thread");
 ASR_FULL_WAVES(CR_THREADS);
 
-template <typename T> struct Vec {
-    static constexpr int N = 16 / sizeof(T);  // elements per 16-byte load
-};
-
-// N consecutive elements <-> fp32 (N = Vec<T>::N: one 16-byte access; N = 1: one element)
-template <typename T, int N>
-__device__ __forceinline__ void loadv(const T* p, float (&r)[N]) {
-    if constexpr (N == 1) {
-        r[0] = to_f32<T>(p[0]);
-    } else if constexpr (sizeof(T) == 2) {
-        load8<T>(p, r);
-    } else {
-        f32x4 v = *(const f32x4*)p;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = v[i];
-    }
-}
-template <typename T, int N>
-__device__ __forceinline__ void storev(T* p, const float (&r)[N]) {
-    if constexpr (N == 1) {
-        p[0] = from_f32<T>(r[0]);
-    } else if constexpr (sizeof(T) == 2) {
-        store8<T>(p, r);
-    } else {
-        f32x4 v = {r[0], r[1], r[2], r[3]};
-        *(f32x4*)p = v;
-    }
-}
-
 // Why fp64 behind the f32 exponentials: with peaked posteriors (logits spread over +-100) J is a sum of terms (p_a - p_b)(lp_a - lp_b) with
 // p ~ 1 and lp differences ~ 100, so a relative error of 6e-8 in a sum of exponentials (one f32 rounding) moves J by 6e-6 - more than the
 // f32 spacing of the result allows a kernel to be away from the definition.  Sums, p, lp and J in fp64 cost ~15 fp64 instructions per
 // pair of elements beside two expf and the memory traffic, and leave the f32 rounding of expf itself (p tiny wherever lp is large) and
-// of the results.  Fixed order (xor butterfly, then the waves in order): every lane gets the same bits, two runs the same bits.
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    double r = 0.0;
-#pragma unroll
-    for (int i = 0; i < CR_THREADS / 64; ++i) r += red[i];
-    return r;
-}
+// of the results.  block_sum_f64 adds in one fixed order.
 
 // N: elements per access (Vec<T>::N, or 1 when V, ld or a base address is no multiple of the vector).  RES: the rows stay in registers.
 // Chunk c of a row = its elements [c N, c N + N); thread i owns the chunks i, i + 256, i + 512, ... on both paths.
@@ -139,8 +98,8 @@ __global__ __launch_bounds__(CR_THREADS) void cr_ctc_kernel(const T* __restrict_
 #pragma unroll
         for (int j = 0; j < N; ++j) { sa += (double)expf(xa[k][j] - ma); sb += (double)expf(xb[k][j] - mb); }
     });
-    sa = block_sum_f64(sa, red64);
-    sb = block_sum_f64(sb, red64);
+    sa = block_sum_f64<CR_THREADS>(sa, red64);
+    sb = block_sum_f64<CR_THREADS>(sb, red64);
     const double ia = 1.0 / sa, ib = 1.0 / sb;
     const double dlse = ((double)ma + log(sa)) - ((double)mb + log(sb));      // lse_a - lse_b
     float h = 0.f;
@@ -174,7 +133,7 @@ __global__ __launch_bounds__(CR_THREADS) void cr_ctc_kernel(const T* __restrict_
             storev<T, N>(db, gb);
         }
     });
-    js = block_sum_f64(js, red64);
+    js = block_sum_f64<CR_THREADS>(js, red64);
     if (tid == 0) frame_loss[(size_t)p * T_ + t] = (float)(0.5 * js);
 }
 

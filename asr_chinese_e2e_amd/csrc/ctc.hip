@@ -26,30 +26,6 @@ namespace {
 constexpr float NEG_INF = -INFINITY;
 typedef __attribute__((ext_vector_type(2))) double f64x2;
 
-template <typename T> struct Vec {
-    static constexpr int N = 16 / sizeof(T);  // elements per 16-byte load
-};
-
-template <typename T>
-__device__ __forceinline__ void loadv(const T* p, float (&r)[Vec<T>::N]) {
-    if constexpr (sizeof(T) == 2) {
-        load8<T>(p, r);
-    } else {
-        f32x4 v = *(const f32x4*)p;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = v[i];
-    }
-}
-template <typename T>
-__device__ __forceinline__ void storev(T* p, const float (&r)[Vec<T>::N]) {
-    if constexpr (sizeof(T) == 2) {
-        store8<T>(p, r);
-    } else {
-        f32x4 v = {r[0], r[1], r[2], r[3]};
-        *(f32x4*)p = v;
-    }
-}
-
 // online (max, sum exp(x - max)) merge
 __device__ __forceinline__ void ms_merge(float& m, float& s, float m2, float s2) {
     const float mn = fmaxf(m, m2);
@@ -99,8 +75,6 @@ __device__ __forceinline__ float wave_row_lse(const T* __restrict__ x, int V, in
 
 // ---- bf16 fast path: a wave holds one whole row in registers (NV 16-byte vectors per lane)
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 
 template <int NV>
 __device__ __forceinline__ void wave_row_load(const bf16_t* __restrict__ x, int nvec, int lane, u32x4 (&xv)[NV]) {
@@ -283,12 +257,7 @@ __global__ __launch_bounds__(256) void ctc_lse_gather_rows_kernel(const bf16_t* 
 // log p(l|x) = ln2 * (sum of exponents taken out) + log of the final column; per-frame scale
 // factors cancel in the posterior (it is normalised over the states).
 // Whole-wave shifts by one lane through DPP (no LDS round trip as ds_bpermute would need): the
-// lane that has no source gets 0.
-__device__ __forceinline__ double wave_shr1(double v) {   // lane i <- lane i-1 (two 32-bit DPP moves)
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x138, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
+// lane that has no source gets 0.  wave_shr1 is asr_common.h's.
 __device__ __forceinline__ double wave_shl1(double v) {   // lane i <- lane i+1
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130, 0xf, 0xf, true);
     const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xf, 0xf, true);

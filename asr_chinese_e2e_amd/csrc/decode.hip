@@ -5,21 +5,9 @@
 //       loop transformer_official.py:331-434).  Semantics: argmax over the vocabulary per frame
 //       (first index wins ties, as torch.argmax), then the standard CTC collapse B(.) of Graves 2006.
 #include "asr_common.h"
+#include "edit_wave.h"
 
 namespace {
-
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-
-// (value, index) pair reduction over the wave: larger value wins, equal values -> smaller index
-__device__ __forceinline__ void wave_argmax(float& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float v2 = __shfl_xor(v, o, 64);
-        const int i2 = __shfl_xor(i, o, 64);
-        if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-    }
-}
 
 // one wave per frame; frames at or past in_len[b] get `blank`
 template <typename T>
@@ -48,7 +36,7 @@ __global__ __launch_bounds__(256) void frame_argmax_kernel(const T* __restrict__
                         if (hi > best) { best = hi; bi = k * 8 + 2 * j + 1; }
                     }
                 }
-                wave_argmax(best, bi);
+                wave_argmax_first(best, bi);
                 if (lane == 0) path[row] = bi;
                 continue;
             }
@@ -57,7 +45,7 @@ __global__ __launch_bounds__(256) void frame_argmax_kernel(const T* __restrict__
             const float v = to_f32<T>(x[i]);
             if (v > best) { best = v; bi = i; }
         }
-        wave_argmax(best, bi);
+        wave_argmax_first(best, bi);
         if (lane == 0) path[row] = bi;
     }
 }
@@ -355,7 +343,7 @@ extern "C" int asr_cache_gather(const void* src, void* dst, const int32_t* paren
 // data_handler/vocab.py:75-79): one wave per utterance.  The two strings are assembled in LDS as code points
 // (ids != pad, token strings joined by one space), then the Levenshtein rows are computed 64 columns at
 // a time: with t[j] = min(prev[j] + 1, prev[j-1] + (a_i != b_j)) the recurrence cur[j] = min(t[j], cur[j-1] + 1)
-// is cur[j] - j = prefix-min of (t[k] - k), a wave scan.
+// is cur[j] - j = prefix-min of (t[k] - k), a wave scan (edit_wave.h's, on DPP).
 namespace {
 
 __device__ __forceinline__ int wave_incl_scan_add(int v, int lane) {
@@ -363,14 +351,6 @@ __device__ __forceinline__ int wave_incl_scan_add(int v, int lane) {
     for (int o = 1; o < 64; o <<= 1) {
         const int u = __shfl_up(v, o, 64);
         if (lane >= o) v += u;
-    }
-    return v;
-}
-__device__ __forceinline__ int wave_incl_scan_min(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(v, o, 64);
-        if (lane >= o) v = min(v, u);
     }
     return v;
 }
@@ -429,7 +409,7 @@ __global__ __launch_bounds__(64) void cer_kernel(const int32_t* __restrict__ hyp
             const int j = j0 + lane;
             int v = 0x3fffffff;
             if (j <= m) v = min(prev[j] + 1, prev[j - 1] + (ca != bb[j - 1])) - j;
-            v = min(wave_incl_scan_min(v, lane), carry);
+            v = min(wave_prefix_min(v), carry);      // the j0 loop is wave-uniform (edit_wave.h: PRECONDITION)
             if (j <= m) cur[j] = v + j;
             carry = __shfl(v, 63, 64);
         }

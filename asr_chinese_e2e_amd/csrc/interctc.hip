@@ -20,49 +20,6 @@ constexpr int IC_E = ASR_INTERCTC_RESIDENT_MAX_V / IC_THREADS;      // elements 
 static_assert(IC_E * IC_THREADS == ASR_INTERCTC_RESIDENT_MAX_V && IC_E % 8 == 0, "the resident cap is whole 16-byte vectors per thread");
 ASR_FULL_WAVES(IC_THREADS);
 
-template <typename T> struct Vec {
-    static constexpr int N = 16 / sizeof(T);  // elements per 16-byte access
-};
-
-// N consecutive elements <-> fp32 (N = Vec<T>::N: one 16-byte access; N = 1: one element)
-template <typename T, int N>
-__device__ __forceinline__ void loadv(const T* p, float (&r)[N]) {
-    if constexpr (N == 1) {
-        r[0] = to_f32<T>(p[0]);
-    } else if constexpr (sizeof(T) == 2) {
-        load8<T>(p, r);
-    } else {
-        f32x4 v = *(const f32x4*)p;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = v[i];
-    }
-}
-template <typename T, int N>
-__device__ __forceinline__ void storev(T* p, const float (&r)[N]) {
-    if constexpr (N == 1) {
-        p[0] = from_f32<T>(r[0]);
-    } else if constexpr (sizeof(T) == 2) {
-        store8<T>(p, r);
-    } else {
-        f32x4 v = {r[0], r[1], r[2], r[3]};
-        *(f32x4*)p = v;
-    }
-}
-
-// Fixed order (xor butterfly, then the waves in order): every lane gets the same bits, two runs the same bits.
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    double r = 0.0;
-#pragma unroll
-    for (int i = 0; i < IC_THREADS / 64; ++i) r += red[i];
-    return r;
-}
-
 // columns [0, V) of one row <- 0 (the whole workgroup; chunk c = elements [c N, c N + N), N divides V on the vector path)
 template <typename T, int N>
 __device__ __forceinline__ void zero_row(T* row, int nch) {
@@ -135,7 +92,7 @@ __global__ __launch_bounds__(IC_THREADS) void softmax_rows_kernel(const T* __res
             s += (double)e;
         }
     });
-    s = block_sum_f64(s, red64);
+    s = block_sum_f64<IC_THREADS>(s, red64);
     const float inv = (float)(1.0 / s);      // s >= 1: the maximum's own term.  One rounding of the fp64 sum's reciprocal, then f32 products
     each_chunk<KC, RES>(nch, [&](int k, int c) {
         fetch(k, c);
@@ -184,7 +141,7 @@ __global__ __launch_bounds__(IC_THREADS) void softmax_bwd_add_kernel(const T* __
 #pragma unroll
         for (int j = 0; j < N; ++j) s += (double)(pr[k][j] * dr[k][j]);
     });
-    const float sf = (float)block_sum_f64(s, red64);
+    const float sf = (float)block_sum_f64<IC_THREADS>(s, red64);
     each_chunk<KC, RES>(nch, [&](int k, int c) {
         // no contraction: accumulate = 1 must add the rounded product that accumulate = 0 writes, and p = 0 gives a term of exactly 0
 #pragma clang fp contract(off)

@@ -7,7 +7,7 @@
 // sum_i c_i = 0, so the dense softmax terms cancel: per frame the gradient touches the blank and the tokens of the list, nothing else.
 //
 // 1. mwer_errors_kernel   one wave per (utterance, entry): the Levenshtein distance to the reference, lengths read on the device.
-//                         The distance-only forward pass of score.hip / consensus.hip (those files stay as they are: the helpers are copies).
+//                         The distance-only forward pass of edit_wave.h.
 // 2. mwer_lse_kernel      one wave per frame: the log-sum-exp of the row in fp64.  It is common to all entries and cancels in P.
 // 3. mwer_lattice_kernel  one workgroup per (utterance, entry), state s of the blank-augmented sequence on thread s.  The alpha recursion
 //                         forward in time, the beta recursion backward, both in the LOG domain in fp64: no value can leave the range, so a
@@ -24,30 +24,13 @@
 // Ids are compared, never used as indices, except as a column < V of the logits / dlogits: an entry with an id outside [0, V) or equal to
 // the blank takes part in nothing.  Every length read from the device is clamped to the shape the host stated.
 #include "asr_common.h"
+#include "edit_wave.h"
 
 namespace {
 
 constexpr int MWER_MAX_N = ASR_MWER_MAX_N;        // entries per list
 constexpr int MWER_MAX_LEN = ASR_MWER_MAX_LEN;    // tokens per entry and per reference
-constexpr int MWER_BIG = 0x3fffffff;
 constexpr double MWER_NEG_INF = -INFINITY;
-
-// ---- DPP helpers: copies of score.hip's.  PRECONDITION: the whole wave executes them.
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ int mwer_dpp_keep(int v) {      // a lane without a source, or in a masked row, keeps v
-    return __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ int mwer_scan_min(int v) {      // inclusive prefix minimum over the 64 lanes
-    v = min(v, mwer_dpp_keep<0x111>(v));            // row_shr:1
-    v = min(v, mwer_dpp_keep<0x112>(v));            // row_shr:2
-    v = min(v, mwer_dpp_keep<0x114>(v));            // row_shr:4
-    v = min(v, mwer_dpp_keep<0x118>(v));            // row_shr:8
-    v = min(v, mwer_dpp_keep<0x142, 0xA>(v));       // row_bcast15 into rows 1 and 3
-    v = min(v, mwer_dpp_keep<0x143, 0xC>(v));       // row_bcast31 into rows 2 and 3
-    return v;
-}
-// lane l takes v of lane l - 1, lane 0 takes `first` (wave_shr:1)
-__device__ __forceinline__ int mwer_shift_in(int v, int first) { return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xf, 0xf, false); }
 
 __device__ __forceinline__ int mwer_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -70,42 +53,6 @@ __host__ __device__ __forceinline__ MwerLayout mwer_layout(int B, int N, int T, 
 }
 
 // ---------------------------------------------------------------------------------- 1. errors
-// The distance of rows r[0..m) and columns h[0..n), m, n <= MWER_MAX_LEN: lanes own 64 columns at a time, the rows run serially,
-// D[i][j] - j is the prefix minimum of t[k] - k, and the block's left boundary column (m + 1 ints of LDS) carries between column blocks.
-__device__ __forceinline__ int mwer_distance(const int32_t* __restrict__ r, int m, const int32_t* __restrict__ h, int n, int* carryD, int lane) {
-    const int nb = (n + 63) >> 6;
-    for (int i = lane; i <= m; i += 64) carryD[i] = i;
-    __syncthreads();
-    int Dfin = m;      // n == 0
-    for (int jb = 0; jb < nb; ++jb) {
-        const int c0 = jb << 6, j = c0 + lane + 1;
-        const bool valid = j <= n, more = jb + 1 < nb;
-        const int hj = valid ? h[j - 1] : 0;
-        int Dp = j;       // row 0: D = j
-        int dD = c0;      // the boundary column one row up
-        int rblk = 0;
-        int nextD = carryD[min(1, m)];      // the boundary column is read one row ahead of its use
-        for (int i = 1; i <= m; ++i) {
-            const int ii = (i - 1) & 63;
-            if (ii == 0) rblk = i - 1 + lane < m ? r[i - 1 + lane] : 0;
-            const int ri = __builtin_amdgcn_readlane(rblk, ii);
-            const int cinD = nextD;
-            nextD = carryD[min(i + 1, m)];      // row i + 1 is rewritten one iteration from now
-            const int Dd = mwer_shift_in(Dp, dD);
-            const int sub = ri != hj;
-            int v = valid ? min(Dp + 1, Dd + sub) - j : MWER_BIG;
-            v = min(mwer_scan_min(v), cinD - c0);
-            const int Dc = v + j;
-            if (more && lane == 63) carryD[i] = Dc;
-            dD = cinD;
-            Dp = Dc;
-        }
-        __syncthreads();
-        if (!more) Dfin = __shfl(Dp, (n - 1) & 63, 64);
-    }
-    return Dfin;
-}
-
 __global__ __launch_bounds__(64) void mwer_errors_kernel(const int32_t* __restrict__ hyp, const int32_t* __restrict__ hyp_len,
                                                          const int32_t* __restrict__ ref, const int32_t* __restrict__ ref_len,
                                                          int32_t* __restrict__ err, int32_t* __restrict__ flags, int N, int Lh, int ldn, int ldb,
@@ -117,7 +64,8 @@ __global__ __launch_bounds__(64) void mwer_errors_kernel(const int32_t* __restri
     int dist = 0;
     if (!flag) {
         const int m = mwer_clamp(ref_len[b], 0, Lr);
-        dist = mwer_distance(ref + (size_t)b * ldr, m, hyp + (size_t)b * ldb + (size_t)i * ldn, n, carryD, lane);
+        EditSinkNone none;
+        dist = edit_wave_forward(ref + (size_t)b * ldr, m, hyp + (size_t)b * ldb + (size_t)i * ldn, n, carryD, lane, none);
     }
     if (lane == 0) {
         err[(size_t)b * N + i] = dist;

@@ -1,6 +1,7 @@
 // The CTC prefix beam search: offline and resumable, plain, hotword-biased (ctx), with an n-gram LM (lm) and with token times (timed).
 // One frame step, one offline kernel and one resumable kernel, each a template on <MODE, TIMES>; one validated host launcher per family.
 #include "asr_common.h"
+#include "ngram_walk.h"
 
 // ---------------------------------------------------------------------------------------------
 // CTC prefix beam search on the device (Hannun et al. 2014, algorithm 1 without a language model; the restatement the tests
@@ -82,20 +83,7 @@ __device__ __forceinline__ void pb_ctx_advance(const PbCtx& g, int root, int c, 
 // ---- n-gram LM shallow fusion (PB_LM instantiations only; the tables come from asr_chinese_e2e_amd/lm.py::NgramLM) -------------------------
 // A beam entry carries (LM state, bias): the state is the longest suffix of the prefix's last order - 1 tokens that the model knows as a
 // context, the bias the sum of the weighted LM log-probabilities of its tokens - both functions of the prefix alone, so merging and the
-// stable prefix hold as they do for hotwords.  Every table entry is an fp64 term, weights folded in on the host; the device only adds.
-struct PbLm {
-    const int32_t* __restrict__ st_off;      // (S + 1) arcs of state s = [st_off[s], st_off[s + 1]); state 0 (the empty history) has none
-    const int32_t* __restrict__ arc_tok;     // (A) ascending within a state
-    const int32_t* __restrict__ arc_next;    // (A) the state after the token; ~state when the n-gram itself is not listed (only longer ones are)
-    const double* __restrict__ arc_term;     // (A) the listed n-gram's term
-    const int32_t* __restrict__ st_back;     // (S) the state of the longest proper suffix that is a state
-    const double* __restrict__ st_bow;       // (S) the back-off term (0.0: none)
-    const double* __restrict__ uni_term;     // (V) the unigram's term, the unk term where there is none
-    const int32_t* __restrict__ uni_next;    // (V)
-    int S, A, V, order, start;
-    double ins;
-};
-
+// stable prefix hold as they do for hotwords.  The tables and the walk are ngram_walk.h's.
 // the beam's (LM state, bias) in rank order and one frame's slots, beside PbLds; apart from PbCtxLds, so that a later change can run both
 struct PbLmLds {
     double bias[PB_MAX_BEAM], nbias[64];
@@ -103,44 +91,11 @@ struct PbLmLds {
     int nnew[PB_MAX_BEAM], nold[PB_MAX_BEAM];      // per survivor: it got a new trie node; its parent's first child before this frame
 };
 
-// the index of the arc (st, c), or -1: binary search of st's arc range.  Every index is clamped to its table.
-__device__ __forceinline__ int pb_lm_find(const PbLm& g, int st, int c) {
-    int lo = min(max(g.st_off[st], 0), g.A);
-    const int end = min(max(g.st_off[st + 1], lo), g.A);
-    int hi = end;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (g.arc_tok[mid] < c) lo = mid + 1;
-        else hi = mid;
-    }
-    return (lo < end && g.arc_tok[lo] == c) ? lo : -1;
-}
-
-// (st, bias) of a prefix -> of the prefix + c (lm.py::NgramLM.advance, the same fp64 additions in the same order): down the back-off
-// chain from st, one term per back-off weight met, then the term of the n-gram found - at the latest the dense unigram level, one
-// indexed load that cannot miss -, then the insertion bonus.  The next state is that of the first arc met on the chain.
-__device__ __forceinline__ void pb_lm_advance(const PbLm& g, int c, int& st, double& bias) {
-    if ((unsigned)st >= (unsigned)g.S) st = 0;       // never from a state outside the table
-    int nx = -1;
-    bool hit = false;
-    for (int i = 1; i < g.order && st != 0; ++i) {   // a state spells at most order - 1 tokens, and st_back shortens it
-        const int a = pb_lm_find(g, st, c);
-        if (a >= 0) {
-            const int raw = g.arc_next[a];
-            if (nx < 0) nx = raw >= 0 ? raw : ~raw;
-            if (raw >= 0) { bias = bias + g.arc_term[a]; hit = true; break; }
-        }
-        bias = bias + g.st_bow[st];
-        const int bk = g.st_back[st];
-        st = (unsigned)bk < (unsigned)g.S ? bk : 0;
-    }
-    if (!hit) {
-        const int cc = min(max(c, 0), g.V - 1);
-        bias = bias + g.uni_term[cc];
-        if (nx < 0) nx = g.uni_next[cc];
-    }
+// (st, bias) of a prefix -> of the prefix + c (lm.py::NgramLM.advance, the same fp64 additions in the same order): the chain's terms,
+// then the insertion bonus.
+__device__ __forceinline__ void pb_lm_advance(const NgramLm& g, int c, int& st, double& bias) {
+    st = ngram_chain(g, c, st, bias);
     bias = bias + g.ins;
-    st = (unsigned)nx < (unsigned)g.S ? nx : 0;
 }
 
 // (state, bias) of the n best, beside pb_spell's outputs
@@ -200,7 +155,7 @@ template <> struct PbArgs<PB_CTX> {
     int32_t* out_state;       // (B, nbest) their context state (-1: no entry, or not biased)
 };
 template <> struct PbArgs<PB_LM> {
-    PbLm lm;
+    NgramLm lm;
     double* out_bias;         // (B, nbest) the entries' bias (the end-of-sentence term not yet added)
     int32_t* out_state;       // (B, nbest) their LM state (-1: no entry)
 };
@@ -241,7 +196,7 @@ __device__ __forceinline__ void pb_time_empty(PbTimesLds& ts, PbTimeTrie tt) {
 template <int MODE, bool TIMES = false>
 __device__ __forceinline__ void pb_frame_step(PbLds& s, const float* __restrict__ row_vals, const int32_t* __restrict__ row_ids, double lb, int k, int beam,
                                               int blank, int& nb, int& next_node, int32_t* npar, int32_t* ntok, PbCtxLds* cs = nullptr,
-                                              const PbCtx* g = nullptr, int root = -1, PbLmLds* ls = nullptr, const PbLm* lm = nullptr, int32_t* nfirst = nullptr,
+                                              const PbCtx* g = nullptr, int root = -1, PbLmLds* ls = nullptr, const NgramLm* lm = nullptr, int32_t* nfirst = nullptr,
                                               int32_t* nsib = nullptr, PbTimes* tm = nullptr) {
     constexpr bool CTX = MODE == PB_CTX, LM = MODE == PB_LM;
     const int lane = threadIdx.x, per = k + 1;
@@ -819,10 +774,6 @@ struct PbHost {
 };
 
 PbCtx pb_ctx_of(const asr_context_graph* ctx) { return ctx ? PbCtx{ctx->st_off, ctx->arc_tok, ctx->arc_next, ctx->st_held, ctx->S, ctx->A, ctx->w} : PbCtx{}; }
-PbLm pb_lm_of(const asr_ngram_lm* lm) {
-    if (!lm) return PbLm{};
-    return PbLm{lm->st_off, lm->arc_tok, lm->arc_next, lm->arc_term, lm->st_back, lm->st_bow, lm->uni_term, lm->uni_next, lm->S, lm->A, lm->V, lm->order, lm->start, lm->ins};
-}
 
 // a null graph / LM struct arrives as all-null tables
 const char* pb_ctx_check(const PbCtx& g) {
@@ -831,17 +782,6 @@ const char* pb_ctx_check(const PbCtx& g) {
     if ((((uintptr_t)g.st_off | (uintptr_t)g.arc_tok | (uintptr_t)g.arc_next) % 4) || ((uintptr_t)g.st_held % 8))
         return "misaligned context table (int32 tables: 4 bytes, st_held: 8)";
     if (!(g.w == g.w) || g.w - g.w != 0.0) return "the context score w must be finite";
-    return nullptr;
-}
-const char* pb_lm_check(const PbLm& lm) {
-    if (!lm.st_off || !lm.arc_tok || !lm.arc_next || !lm.arc_term || !lm.st_back || !lm.st_bow || !lm.uni_term || !lm.uni_next) return "null LM table";
-    if (lm.S < 1 || lm.A < 0 || lm.V < 1) return "an LM has S >= 1 states, A >= 0 arcs and V >= 1 tokens";
-    if (lm.order < 1 || lm.order > 5) return "LM orders 1 to 5";
-    if (lm.start < 0 || lm.start >= lm.S) return "the LM's start state is one of its states";
-    if ((((uintptr_t)lm.st_off | (uintptr_t)lm.arc_tok | (uintptr_t)lm.arc_next | (uintptr_t)lm.st_back | (uintptr_t)lm.uni_next) % 4) ||
-        (((uintptr_t)lm.arc_term | (uintptr_t)lm.st_bow | (uintptr_t)lm.uni_term) % 8))
-        return "misaligned LM table (int32 tables: 4 bytes, fp64 tables: 8)";
-    if (!(lm.ins == lm.ins) || lm.ins - lm.ins != 0.0) return "the LM's insertion bonus must be finite";
     return nullptr;
 }
 const char* pb_bias_out_check(const double* out_bias, const int32_t* out_state) {
@@ -857,7 +797,7 @@ const char* pb_args_check(const PbArgs<PB_CTX>& cx) {
     return why ? why : pb_bias_out_check(cx.out_bias, cx.out_state);
 }
 const char* pb_args_check(const PbArgs<PB_LM>& cx) {
-    const char* why = pb_lm_check(cx.lm);
+    const char* why = ngram_lm_check(cx.lm);
     return why ? why : pb_bias_out_check(cx.out_bias, cx.out_state);
 }
 // ... and the time outputs (the resumable search's out_final: pb_chunk_launch)
@@ -934,7 +874,7 @@ int pb_state_launch(const char* what, void* state, void* ws, const int32_t* flag
         if ((uintptr_t)cx.root % 4) ASR_FAIL(ASR_EINVAL, "%s: misaligned pointer (root: 4 bytes)", what);
     }
     if constexpr (MODE == PB_LM) {
-        if (const char* why = pb_lm_check(cx.lm)) ASR_FAIL(ASR_EINVAL, "%s: %s", what, why);
+        if (const char* why = ngram_lm_check(cx.lm)) ASR_FAIL(ASR_EINVAL, "%s: %s", what, why);
     }
     if (B <= 0 || beam <= 0 || beam > PB_MAX_BEAM || T_cap <= 0 || (size_t)T_cap * beam + 1 > (size_t)INT_MAX)
         ASR_FAIL(ASR_EINVAL, "%s: bad shape B=%d beam=%d (<= %d) T_cap=%d", what, B, beam, PB_MAX_BEAM, T_cap);
@@ -1016,16 +956,16 @@ extern "C" int asr_ctc_prefix_beam_lm(const float* vals, const int32_t* ids, con
                                       size_t ws_bytes, int32_t* out_tok, int32_t* out_len, float* out_score, double* out_bias, int32_t* out_state, int B,
                                       int T, int k, int beam, int nbest, int Lcap, int blank, void* stream) {
     return pb_search_launch<PB_LM, false>("asr_ctc_prefix_beam_lm", vals, ids, blank_lp, in_len, ws, ws_bytes, out_tok, out_len, out_score, B, T, k, beam, nbest, Lcap,
-                                          blank, stream, {pb_lm_of(lm), out_bias, out_state}, {});
+                                          blank, stream, {ngram_lm_of(lm), out_bias, out_state}, {});
 }
 
 extern "C" int asr_ctc_prefix_beam_lm_state_init(void* state, void* ws, const asr_ngram_lm* lm, int B, int beam, int T_cap, void* stream) {
-    return pb_state_launch<PB_LM, false>("asr_ctc_prefix_beam_lm_state_init", state, ws, nullptr, B, beam, T_cap, stream, {pb_lm_of(lm), nullptr, nullptr});
+    return pb_state_launch<PB_LM, false>("asr_ctc_prefix_beam_lm_state_init", state, ws, nullptr, B, beam, T_cap, stream, {ngram_lm_of(lm), nullptr, nullptr});
 }
 
 extern "C" int asr_ctc_prefix_beam_lm_state_reset(void* state, void* ws, const int32_t* flags, const asr_ngram_lm* lm, int B, int beam, int T_cap, void* stream) {
     if (!flags) ASR_FAIL(ASR_EINVAL, "asr_ctc_prefix_beam_lm_state_reset: null pointer");      // without flags it would be an init
-    return pb_state_launch<PB_LM, false>("asr_ctc_prefix_beam_lm_state_reset", state, ws, flags, B, beam, T_cap, stream, {pb_lm_of(lm), nullptr, nullptr});
+    return pb_state_launch<PB_LM, false>("asr_ctc_prefix_beam_lm_state_reset", state, ws, flags, B, beam, T_cap, stream, {ngram_lm_of(lm), nullptr, nullptr});
 }
 
 extern "C" int asr_ctc_prefix_beam_chunk_lm(const float* vals, const int32_t* ids, const float* blank_lp, const int32_t* n_valid, void* state, void* ws,
@@ -1033,7 +973,7 @@ extern "C" int asr_ctc_prefix_beam_chunk_lm(const float* vals, const int32_t* id
                                             int32_t* out_state, int32_t* out_stable, int B, int C, int k, int beam, int nbest, int Lcap, int T_cap, int blank,
                                             void* stream) {
     return pb_chunk_launch<PB_LM, false>("asr_ctc_prefix_beam_chunk_lm", vals, ids, blank_lp, n_valid, state, ws, ws_bytes, out_tok, out_len, out_score, out_stable, B, C,
-                                         k, beam, nbest, Lcap, T_cap, blank, stream, {pb_lm_of(lm), out_bias, out_state}, {});
+                                         k, beam, nbest, Lcap, T_cap, blank, stream, {ngram_lm_of(lm), out_bias, out_state}, {});
 }
 
 // ---- token times: the plain searches with the best single alignment of every prefix riding along (additive to ABI 10) ----------------------

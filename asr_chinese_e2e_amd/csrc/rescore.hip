@@ -1,9 +1,8 @@
 // Rescoring of n-best lists (include/asr_hip.h: asr_lm_score_nbest, asr_nbest_sweep; the definition is tests/rescore_ref.py on top of
 // lm.py::NgramLM's host methods, and the kernels agree with it in integers and float bits).
 //
-// 1. lm_score_nbest_kernel: one lane per hypothesis, workgroups of 64.  The lane walks its tokens from (lm.start, 0.0) with the statements
-//    of prefix_beam.hip's pb_lm_advance / pb_lm_find (copied here; that file stays as it is), then adds the end-of-sentence chain without
-//    the insertion bonus (NgramLM.final).  The device only adds fp64 table terms in the host's order, so score and bias equal
+// 1. lm_score_nbest_kernel: one lane per hypothesis, workgroups of 64.  The lane walks its tokens from (lm.start, 0.0) with ngram_walk.h's
+//    chain and the insertion bonus per token, as the beam search does, then adds the end-of-sentence chain without the bonus (NgramLM.final).  The device only adds fp64 table terms in the host's order, so score and bias equal
 //    NgramLM.score / NgramLM.walk bit for bit.
 // 2. nbest_sweep_kernel: one wave per (grid point, 64 utterances), lane = utterance.  The grid point's K weights are wave-uniform.  The
 //    features are (K, N, U) planes and the error counts (3, N, U), so the lanes of a load read consecutive addresses.  The lane forms
@@ -12,63 +11,11 @@
 // 3. nbest_sweep_sum_kernel: one wave per grid point sums the partials of its blocks.  Integers: any order gives the same bytes, and
 //    there is no atomic.
 #include "asr_common.h"
+#include "ngram_walk.h"
 
 namespace {
 
-// ---- the LM walk (copies of prefix_beam.hip's PbLm, pb_lm_find, pb_lm_advance; the chain is split off so that the end-of-sentence term
-// can take it without the insertion bonus) --------------------------------------------------------------------------------------------------
-struct RsLm {
-    const int32_t* __restrict__ st_off;
-    const int32_t* __restrict__ arc_tok;
-    const int32_t* __restrict__ arc_next;
-    const double* __restrict__ arc_term;
-    const int32_t* __restrict__ st_back;
-    const double* __restrict__ st_bow;
-    const double* __restrict__ uni_term;
-    const int32_t* __restrict__ uni_next;
-    int S, A, V, order, start;
-    double ins;
-};
-
-// the index of the arc (st, c), or -1: binary search of st's arc range.  Every index is clamped to its table.
-__device__ __forceinline__ int rs_lm_find(const RsLm& g, int st, int c) {
-    int lo = min(max(g.st_off[st], 0), g.A);
-    const int end = min(max(g.st_off[st + 1], lo), g.A);
-    int hi = end;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (g.arc_tok[mid] < c) lo = mid + 1;
-        else hi = mid;
-    }
-    return (lo < end && g.arc_tok[lo] == c) ? lo : -1;
-}
-
-// NgramLM._chain: down the back-off chain from st, one term per back-off weight met, then the term of the n-gram found - at the latest the
-// dense unigram level, where the token id is clamped as the host clamps it.  Returns the next state.
-__device__ __forceinline__ int rs_lm_chain(const RsLm& g, int c, int st, double& bias) {
-    if ((unsigned)st >= (unsigned)g.S) st = 0;
-    int nx = -1;
-    bool hit = false;
-    for (int i = 1; i < g.order && st != 0; ++i) {
-        const int a = rs_lm_find(g, st, c);
-        if (a >= 0) {
-            const int raw = g.arc_next[a];
-            if (nx < 0) nx = raw >= 0 ? raw : ~raw;
-            if (raw >= 0) { bias = bias + g.arc_term[a]; hit = true; break; }
-        }
-        bias = bias + g.st_bow[st];
-        const int bk = g.st_back[st];
-        st = (unsigned)bk < (unsigned)g.S ? bk : 0;
-    }
-    if (!hit) {
-        const int cc = min(max(c, 0), g.V - 1);
-        bias = bias + g.uni_term[cc];
-        if (nx < 0) nx = g.uni_next[cc];
-    }
-    return (unsigned)nx < (unsigned)g.S ? nx : 0;
-}
-
-__global__ __launch_bounds__(64) void lm_score_nbest_kernel(const int32_t* __restrict__ tok, const int32_t* __restrict__ len, int P, int ld, RsLm g,
+__global__ __launch_bounds__(64) void lm_score_nbest_kernel(const int32_t* __restrict__ tok, const int32_t* __restrict__ len, int P, int ld, NgramLm g,
                                                             int has_eos, int eos, double* __restrict__ out_score, double* __restrict__ out_bias,
                                                             int32_t* __restrict__ out_state, int32_t* __restrict__ out_ntok) {
     const int p = blockIdx.x * 64 + threadIdx.x;
@@ -85,11 +32,11 @@ __global__ __launch_bounds__(64) void lm_score_nbest_kernel(const int32_t* __res
     int st = g.start;
     double bias = 0.0;
     for (int j = 0; j < n; ++j) {
-        st = rs_lm_chain(g, row[j], st, bias);
+        st = ngram_chain(g, row[j], st, bias);
         bias = bias + g.ins;
     }
     double score = bias;
-    if (has_eos) (void)rs_lm_chain(g, eos, st, score);
+    if (has_eos) (void)ngram_chain(g, eos, st, score);
     out_score[p] = score;
     out_bias[p] = bias;
     out_state[p] = st;
@@ -193,20 +140,6 @@ const char* sweep_shape_check(int U, int N, int K, int G) {
     return nullptr;
 }
 
-// the LM struct's checks, as prefix_beam.hip's pb_lm_check makes them
-const char* rs_lm_check(const asr_ngram_lm* lm) {
-    if (!lm) return "null LM";
-    if (!lm->st_off || !lm->arc_tok || !lm->arc_next || !lm->arc_term || !lm->st_back || !lm->st_bow || !lm->uni_term || !lm->uni_next) return "null LM table";
-    if (lm->S < 1 || lm->A < 0 || lm->V < 1) return "an LM has S >= 1 states, A >= 0 arcs and V >= 1 tokens";
-    if (lm->order < 1 || lm->order > 5) return "LM orders 1 to 5";
-    if (lm->start < 0 || lm->start >= lm->S) return "the LM's start state is one of its states";
-    if ((((uintptr_t)lm->st_off | (uintptr_t)lm->arc_tok | (uintptr_t)lm->arc_next | (uintptr_t)lm->st_back | (uintptr_t)lm->uni_next) % 4) ||
-        (((uintptr_t)lm->arc_term | (uintptr_t)lm->st_bow | (uintptr_t)lm->uni_term) % 8))
-        return "misaligned LM table (int32 tables: 4 bytes, fp64 tables: 8)";
-    if (!(lm->ins == lm->ins) || lm->ins - lm->ins != 0.0) return "the LM's insertion bonus must be finite";
-    return nullptr;
-}
-
 }  // namespace
 
 extern "C" int asr_lm_score_nbest(const int32_t* tok, const int32_t* len, const int32_t* host_len, int P, int ld, const asr_ngram_lm* lm, int has_eos,
@@ -217,12 +150,12 @@ extern "C" int asr_lm_score_nbest(const int32_t* tok, const int32_t* len, const 
         ASR_FAIL(ASR_EINVAL, "%s: misaligned pointer (int32 arrays: 4 bytes, out_score / out_bias: 8)", name);
     if (P <= 0) ASR_FAIL(ASR_EINVAL, "%s: P=%d hypotheses", name, P);
     if (ld < 0) ASR_FAIL(ASR_EINVAL, "%s: ld=%d", name, ld);
-    if (const char* why = rs_lm_check(lm)) ASR_FAIL(ASR_EINVAL, "%s: %s", name, why);
+    const NgramLm g = ngram_lm_of(lm);
+    if (const char* why = lm ? ngram_lm_check(g) : "null LM") ASR_FAIL(ASR_EINVAL, "%s: %s", name, why);
     for (int p = 0; p < P; ++p) {
         if (host_len[p] < -1) ASR_FAIL(ASR_EINVAL, "%s: hypothesis %d has length %d (-1 = absent)", name, p, host_len[p]);
         if (host_len[p] > ld) ASR_FAIL(ASR_EINVAL, "%s: hypothesis %d has %d tokens, the rows are ld=%d apart", name, p, host_len[p], ld);
     }
-    const RsLm g{lm->st_off, lm->arc_tok, lm->arc_next, lm->arc_term, lm->st_back, lm->st_bow, lm->uni_term, lm->uni_next, lm->S, lm->A, lm->V, lm->order, lm->start, lm->ins};
     lm_score_nbest_kernel<<<dim3((P + 63) / 64), WAVE, 0, (hipStream_t)stream>>>(tok, len, P, ld, g, has_eos != 0, eos, out_score, out_bias, out_state, out_ntok);
     ASR_CHECK_LAUNCH(name);
     return ASR_OK;

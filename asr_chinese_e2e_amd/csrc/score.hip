@@ -1,17 +1,10 @@
 // Token-level scoring of hypotheses against references (include/asr_hip.h: asr_edit_align; the definition is tests/score_ref.py, and the
 // kernel agrees with it integer for integer).  One wave per (hypothesis, reference) pair.
 //
-// Forward pass.  Lanes own hypothesis columns, 64 at a time (a column block); inside a block the reference rows run serially, so a lane
-// keeps its column's id, its D[i-1][j] and (counts-only mode) its path counts in registers from row to row.  With
-// t[j] = min(D[i-1][j] + 1, D[i-1][j-1] + (r_i != h_j)) the recurrence D[i][j] = min(t[j], D[i][j-1] + 1) is D[i][j] - j = prefix-min of
-// (t[k] - k): a wave min-scan, with the block's left boundary column D[i][64 b] as the carry between blocks.  That column is the only
-// per-row state that has to leave the registers: m + 1 ints of LDS, rewritten in place by lane 63 for the next block.  The reference ids
-// never touch LDS: 64 of them are loaded at once, one per lane, and read back row by row with v_readlane.
+// Forward pass: edit_wave.h (lanes own hypothesis columns, the reference rows run serially), with one of two sinks of this file.
 //
-// Directions.  Once the row block's values are known every lane has what the three comparisons of the definition need: DIAG iff
-// D[i-1][j-1] + sub == D[i][j], else UP iff D[i-1][j] + 1 == D[i][j], else LEFT (the third comparison is implied: one of the three
-// candidates is the minimum).  The cell's code {COR, SUB, DEL, INS} is two bits, and the 64 cells leave the wave as two ballot masks,
-// 16 bytes per (row, block), stored by lane 0 into LDS (pairs of up to ASR_EDIT_LDS_DIR_BYTES) or into the caller's workspace.
+// Directions (ops mode).  The cell's code {COR, SUB, DEL, INS} is two bits, and the 64 cells leave the wave as two ballot masks, 16 bytes
+// per (row, block), stored by lane 0 into LDS (pairs of up to ASR_EDIT_LDS_DIR_BYTES) or into the caller's workspace.
 //
 // Counts-only mode (ops == NULL) keeps no masks.  The walk from a cell to (0, 0) is fixed by the directions, so its substitution and
 // deletion counts are a function of the cell: C[i][j] = C[predecessor] + the step.  They travel with D, packed in one int (sub | del << 16,
@@ -25,10 +18,10 @@
 #include <limits.h>
 
 #include "asr_common.h"
+#include "edit_wave.h"
 
 namespace {
 
-constexpr int EDIT_BIG = 0x3fffffff;
 constexpr int EDIT_LDS_MAX = 150 * 1024;      // what cer_kernel asks for
 
 __host__ __device__ __forceinline__ int edit_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
@@ -40,23 +33,57 @@ __host__ __device__ __forceinline__ unsigned long long edit_ws_need(int m, int n
     return db <= (unsigned long long)ASR_EDIT_LDS_DIR_BYTES && edit_carry_bytes(m) + db <= (unsigned long long)lds_bytes ? 0ull : db;
 }
 
-// Lane crossings on the vector ALU's DPP path, not through the LDS crossbar (six __shfl_up steps per scan were six ds_bpermute round trips
-// of ~100 cycles each: 350 ns per row step measured).  PRECONDITION: the whole wave executes these - the row loops are wave-uniform.
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ int edit_dpp_keep(int v) {      // a lane without a source, or in a masked row, keeps v
-    return __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ int edit_scan_min(int v) {      // inclusive prefix minimum over the 64 lanes
-    v = min(v, edit_dpp_keep<0x111>(v));            // row_shr:1
-    v = min(v, edit_dpp_keep<0x112>(v));            // row_shr:2
-    v = min(v, edit_dpp_keep<0x114>(v));            // row_shr:4
-    v = min(v, edit_dpp_keep<0x118>(v));            // row_shr:8: every row of 16 lanes holds its own prefix minimum
-    v = min(v, edit_dpp_keep<0x142, 0xA>(v));       // row_bcast15 into rows 1 and 3
-    v = min(v, edit_dpp_keep<0x143, 0xC>(v));       // row_bcast31 into rows 2 and 3
-    return v;
-}
-// lane l takes v of lane l - 1, lane 0 takes `first` (wave_shr:1)
-__device__ __forceinline__ int edit_shift_in(int v, int first) { return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xf, 0xf, false); }
+// The masks of a cell go to LDS, to the workspace, or nowhere (!have_dir: the distance alone).
+struct EditSinkDirs {
+    ulonglong2* ldir;      // the direction masks, (m, nb) pairs: in LDS ...
+    ulonglong2* gdir;      // ... or in the workspace
+    bool have_dir;
+    __device__ __forceinline__ ulonglong2 get(int i, int nb, int jb) const {
+        const size_t at = (size_t)(i - 1) * nb + jb;
+        return ldir ? ldir[at] : gdir[at];
+    }
+    __device__ __forceinline__ void block(int) {}
+    __device__ __forceinline__ void cell(int i, int jb, int nb, int lane, bool valid, bool, int sub, int Dp, int Dd, int Dc) {
+        if (!have_dir) return;
+        const ulonglong2 mk = edit_wave_masks(valid, edit_wave_code(sub, Dp, Dd, Dc));
+        if (lane == 0) {
+            const size_t at = (size_t)(i - 1) * nb + jb;
+            if (ldir) ldir[at] = mk;
+            else gdir[at] = mk;
+        }
+    }
+    __device__ __forceinline__ void finish(int) {}
+};
+
+// The packed counts C (sub | del << 16) travel with D; carryC (m + 1 ints of LDS) is their boundary column, read ahead like carryD.
+struct EditSinkCounts {
+    int* carryC;
+    int m, Cp, dC, nextC, Cfin;
+    __device__ __forceinline__ EditSinkCounts(int* c, int m_, int lane) : carryC(c), m(m_), Cp(0), dC(0), nextC(0), Cfin(m_ << 16) {      // Cfin: n == 0
+        for (int i = lane; i <= m; i += 64) carryC[i] = i << 16;      // column 0 is all UP: i deletions (the pass's first barrier follows)
+    }
+    __device__ __forceinline__ void block(int) {
+        Cp = 0;      // row 0: all LEFT
+        dC = 0;      // the boundary column one row up
+        nextC = carryC[min(1, m)];
+    }
+    __device__ __forceinline__ void cell(int i, int, int, int lane, bool valid, bool more, int sub, int Dp, int Dd, int Dc) {
+        const bool isDiag = Dd + sub == Dc, isUp = !isDiag && Dp + 1 == Dc;
+        const int Cd = wave_shift_in(Cp, dC);
+        const int cinC = nextC;
+        nextC = carryC[min(i + 1, m)];
+        const int Cb = isDiag ? Cd + sub : Cp + 0x10000;
+        const bool isLeft = valid && !isDiag && !isUp;
+        const unsigned long long below = __ballot(!isLeft) & ((1ull << lane) - 1ull);
+        const int src = below ? 63 - __clzll((long long)below) : 0;
+        const int Cs = __shfl(Cb, src, 64);
+        const int Cc = isLeft ? (below ? Cs : cinC) : Cb;
+        if (more && lane == 63) carryC[i] = Cc;
+        dC = cinC;
+        Cp = Cc;
+    }
+    __device__ __forceinline__ void finish(int n) { Cfin = __shfl(Cp, (n - 1) & 63, 64); }
+};
 
 struct EditShape { int n, m, rr; };
 __device__ __forceinline__ EditShape edit_shape(int p, const int32_t* __restrict__ hyp_len, const int32_t* __restrict__ ref_len, const int32_t* __restrict__ ref_of,
@@ -80,102 +107,38 @@ __global__ __launch_bounds__(64) void edit_align_kernel(const int32_t* __restric
     const EditShape sh = edit_shape(p, hyp_len, ref_len, ref_of, Lh, Lr, R, m_cap);
     const int n = sh.n, m = sh.m, nb = (n + 63) >> 6;
     int* carryD = (int*)edit_smem;      // D[i][64 b], i = 0 .. m
-    int* carryC = carryD + (m + 1);     // counts-only: the packed counts of that column
-    ulonglong2* ldir = nullptr;         // the direction masks, (m, nb) pairs: in LDS ...
-    ulonglong2* gdir = nullptr;         // ... or in the workspace
-    bool have_dir = false;
-    if (OPS) {
-        const unsigned long long need = edit_ws_need(m, n, lds_bytes);
-        if (need == 0) {
-            ldir = (ulonglong2*)(edit_smem + edit_carry_bytes(m));
-            have_dir = true;
-        } else if (ws) {      // the pair's slice begins behind those of the workspace pairs in front of it
-            unsigned long long off = 0;
-            for (int q = lane; q < p; q += 64) {
-                const EditShape o = edit_shape(q, hyp_len, ref_len, ref_of, Lh, Lr, R, m_cap);
-                off += edit_ws_need(o.m, o.n, lds_bytes);
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) off += __shfl_xor(off, o, 64);
-            if (off + need <= ws_bytes) {
-                gdir = (ulonglong2*)(ws + off);
-                have_dir = true;
-            }
-        }
-    }
-    for (int i = lane; i <= m; i += 64) {
-        carryD[i] = i;
-        if (!OPS) carryC[i] = i << 16;      // column 0 is all UP: i deletions
-    }
-    __syncthreads();
     const int32_t* h = hyp + (size_t)p * ldh;
     const int32_t* r = ref + (size_t)sh.rr * ldr;
-    int Dfin = m, Cfin = m << 16;      // n == 0
-    for (int jb = 0; jb < nb; ++jb) {
-        const int c0 = jb << 6, j = c0 + lane + 1;
-        const bool valid = j <= n, more = jb + 1 < nb;
-        const int hj = valid ? h[j - 1] : 0;
-        int Dp = j, Cp = 0;       // row 0: D = j, all LEFT
-        int dD = c0, dC = 0;      // the boundary column one row up
-        int rblk = 0;
-        int nextD = carryD[min(1, m)], nextC = OPS ? 0 : carryC[min(1, m)];      // the boundary column is read one row ahead of its use
-        for (int i = 1; i <= m; ++i) {
-            const int ii = (i - 1) & 63;
-            if (ii == 0) rblk = i - 1 + lane < m ? r[i - 1 + lane] : 0;
-            const int ri = __builtin_amdgcn_readlane(rblk, ii);
-            const int cinD = nextD;
-            nextD = carryD[min(i + 1, m)];      // row i + 1 is rewritten one iteration from now
-            const int Dd = edit_shift_in(Dp, dD);
-            const int sub = ri != hj;
-            int v = valid ? min(Dp + 1, Dd + sub) - j : EDIT_BIG;
-            v = min(edit_scan_min(v), cinD - c0);
-            const int Dc = v + j;
-            const bool isDiag = Dd + sub == Dc, isUp = !isDiag && Dp + 1 == Dc;
-            if (OPS) {
-                if (have_dir) {
-                    const int code = isDiag ? sub : (isUp ? ASR_EDIT_DEL : ASR_EDIT_INS);
-                    ulonglong2 mk;
-                    mk.x = __ballot(valid && (code & 1));
-                    mk.y = __ballot(valid && (code & 2));
-                    if (lane == 0) {
-                        const size_t at = (size_t)(i - 1) * nb + jb;
-                        if (ldir) ldir[at] = mk;
-                        else gdir[at] = mk;
-                    }
-                }
-            } else {
-                const int Cd = edit_shift_in(Cp, dC);
-                const int cinC = nextC;
-                nextC = carryC[min(i + 1, m)];
-                const int Cb = isDiag ? Cd + sub : Cp + 0x10000;
-                const bool isLeft = valid && !isDiag && !isUp;
-                const unsigned long long below = __ballot(!isLeft) & ((1ull << lane) - 1ull);
-                const int src = below ? 63 - __clzll((long long)below) : 0;
-                const int Cs = __shfl(Cb, src, 64);
-                const int Cc = isLeft ? (below ? Cs : cinC) : Cb;
-                if (more && lane == 63) carryC[i] = Cc;
-                dC = cinC;
-                Cp = Cc;
-            }
-            if (more && lane == 63) carryD[i] = Dc;
-            dD = cinD;
-            Dp = Dc;
-        }
-        __syncthreads();
-        if (!more) {
-            Dfin = __shfl(Dp, (n - 1) & 63, 64);
-            Cfin = __shfl(Cp, (n - 1) & 63, 64);
-        }
-    }
     int32_t* cnt = counts + (size_t)p * 5;
     if (!OPS) {
+        EditSinkCounts cs(carryD + (m + 1), m, lane);
+        const int Dfin = edit_wave_forward(r, m, h, n, carryD, lane, cs);
         if (lane == 0) {
-            const int s = Cfin & 0xffff, d = Cfin >> 16, c = m - s - d;
+            const int s = cs.Cfin & 0xffff, d = cs.Cfin >> 16, c = m - s - d;
             cnt[0] = Dfin; cnt[1] = c; cnt[2] = s; cnt[3] = d; cnt[4] = n - c - s;
         }
         return;
     }
-    if (!have_dir) {      // only when the device lengths are not the ones the caller sized the workspace by: the distance alone
+    EditSinkDirs ds{nullptr, nullptr, false};
+    const unsigned long long need = edit_ws_need(m, n, lds_bytes);
+    if (need == 0) {
+        ds.ldir = (ulonglong2*)(edit_smem + edit_carry_bytes(m));
+        ds.have_dir = true;
+    } else if (ws) {      // the pair's slice begins behind those of the workspace pairs in front of it
+        unsigned long long off = 0;
+        for (int q = lane; q < p; q += 64) {
+            const EditShape o = edit_shape(q, hyp_len, ref_len, ref_of, Lh, Lr, R, m_cap);
+            off += edit_ws_need(o.m, o.n, lds_bytes);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) off += __shfl_xor(off, o, 64);
+        if (off + need <= ws_bytes) {
+            ds.gdir = (ulonglong2*)(ws + off);
+            ds.have_dir = true;
+        }
+    }
+    const int Dfin = edit_wave_forward(r, m, h, n, carryD, lane, ds);
+    if (!ds.have_dir) {      // only when the device lengths are not the ones the caller sized the workspace by: the distance alone
         if (lane == 0) {
             cnt[0] = Dfin; cnt[1] = cnt[2] = cnt[3] = cnt[4] = -1;
             n_ops[p] = -1;
@@ -190,12 +153,7 @@ __global__ __launch_bounds__(64) void edit_align_kernel(const int32_t* __restric
             int code;
             if (i == 0) code = ASR_EDIT_INS;
             else if (j == 0) code = ASR_EDIT_DEL;
-            else {
-                const size_t at = (size_t)(i - 1) * nb + ((j - 1) >> 6);
-                const ulonglong2 mk = ldir ? ldir[at] : gdir[at];
-                const int bit = (j - 1) & 63;
-                code = (int)((mk.x >> bit) & 1ull) | ((int)((mk.y >> bit) & 1ull) << 1);
-            }
+            else code = edit_wave_code_at(ds.get(i, nb, (j - 1) >> 6), j);
             code_out[ldo - 1 - K] = code;
             ++K;
             ++tally[code];

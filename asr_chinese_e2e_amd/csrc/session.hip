@@ -36,19 +36,6 @@ __global__ __launch_bounds__(SR_WAVES* WAVE) void slot_rows_slide_kernel(const c
     for (int v = lane; v < vecs; v += 64) d[v] = s[v];
 }
 
-__device__ __forceinline__ float sbf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float sbf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-
-// (value, index) pair reduction over the wave, as decode.hip's: larger value wins, equal values -> smaller index
-__device__ __forceinline__ void wave_argmax_first(float& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float v2 = __shfl_xor(v, o, 64);
-        const int i2 = __shfl_xor(i, o, 64);
-        if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-    }
-}
-
 // One wave per frame.  The argmax pass is frame_argmax_kernel's (16-byte loads for bf16 rows that allow them); its maximum is the m of the
 // log-sum-exp, so the row is read from memory once and from cache a second time for the sum.  The sum keeps logsoftmax_topk_kernel's order
 // (lane l adds classes l, l + 64, ... and the lanes meet in wave_sum): blank_lp has that kernel's bits.
@@ -74,7 +61,7 @@ __global__ __launch_bounds__(256) void frame_best_blank_kernel(const T* __restri
                 const u32x4 q = *(const u32x4*)(x + (size_t)k * 8);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float lo = sbf16_lo(q[j]), hi = sbf16_hi(q[j]);
+                    const float lo = bf16_lo(q[j]), hi = bf16_hi(q[j]);
                     if (lo > best) { best = lo; bi = k * 8 + 2 * j; }
                     if (hi > best) { best = hi; bi = k * 8 + 2 * j + 1; }
                 }
