@@ -293,6 +293,7 @@ __device__ __forceinline__ int xcd_virtual_id(int id, int nwg) {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 // ---- armed launches (asr_stream_arm): the completion event of ONE kernel launch, without a marker packet in its queue ------------
 // hipEventRecord puts a barrier packet behind the kernel it follows: the next kernel of that queue then starts ~3.5 us later than it

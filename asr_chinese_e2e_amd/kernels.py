@@ -1277,17 +1277,29 @@ def logmel(wav, wav_len, window, melfb, Tmax, feat=None):
     return feat
 
 
-def utt_norm_lfr(feat, wav_len, m, n, Tlfr_max, dtype=torch.float32, masks=None):
-    """masks: optional (B, 4) int32 [t0, t1, f0, f1] SpecAugment ranges (see include/asr_hip.h)."""
-    _chk_f32(feat)
+def _norm_aug_lfr(entry, feat, wav_len, m, n, Tlfr_max, dtype, mean=None, istd=None, masks=None, policy=None):
+    """The body of the four normalise-augment-stack calls: checks, out (B, Tlfr_max, m n_mels) and out_len (B) int32, and the library
+    entry `entry`.  mean, istd: None under utterance normalisation, whose entries take none.  policy: None (the reference's masks, or
+    none) or (ranges, counts)."""
+    _chk_f32(feat, mean, istd)
     _chk_i32(wav_len, masks)
     B, Tmax, n_mels = feat.shape
-    assert masks is None or tuple(masks.shape) == (B, 4)
+    assert wav_len.numel() == B and (mean is None or (mean.numel() == n_mels and istd.numel() == n_mels))
+    if policy is None:
+        assert masks is None or tuple(masks.shape) == (B, 4)
+        aug = (_p(masks),)
+    else:
+        aug = _specaug_ranges(policy[0], B, policy[1])
     out = torch.empty(B, Tlfr_max, m * n_mels, dtype=dtype, device=feat.device)
     out_len = torch.empty(B, dtype=torch.int32, device=feat.device)
-    check(lib.asr_utt_norm_augment_lfr_fwd(_p(feat), _p(wav_len), _p(masks), _p(out), _p(out_len), B, Tmax, n_mels, m, n, Tlfr_max,
-                                           _dt(out), _stream()), "asr_utt_norm_augment_lfr_fwd")
+    stats = () if mean is None else (_p(mean), _p(istd))
+    check(getattr(lib, entry)(_p(feat), _p(wav_len), *aug, *stats, _p(out), _p(out_len), B, Tmax, n_mels, m, n, Tlfr_max, _dt(out), _stream()), entry)
     return out, out_len
+
+
+def utt_norm_lfr(feat, wav_len, m, n, Tlfr_max, dtype=torch.float32, masks=None):
+    """masks: optional (B, 4) int32 [t0, t1, f0, f1] SpecAugment ranges (see include/asr_hip.h)."""
+    return _norm_aug_lfr("asr_utt_norm_augment_lfr_fwd", feat, wav_len, m, n, Tlfr_max, dtype, masks=masks)
 
 
 SPEED_TILE = _lib.SPEED_TILE      # output samples per workgroup of the speed-perturbation kernel
@@ -1434,56 +1446,29 @@ def cmvn_accumulate(feat, wav_len, acc):
 
 def global_norm_lfr(feat, wav_len, mean, istd, m, n, Tlfr_max, dtype=torch.float32, masks=None):
     """utt_norm_lfr under global CMVN: (x - mean[bin]) * istd[bin]; mean, istd (n_mels) f32."""
-    _chk_f32(feat, mean, istd)
-    _chk_i32(wav_len, masks)
-    B, Tmax, n_mels = feat.shape
-    assert masks is None or tuple(masks.shape) == (B, 4)
-    assert mean.numel() == n_mels and istd.numel() == n_mels and wav_len.numel() == B
-    out = torch.empty(B, Tlfr_max, m * n_mels, dtype=dtype, device=feat.device)
-    out_len = torch.empty(B, dtype=torch.int32, device=feat.device)
-    check(lib.asr_global_norm_augment_lfr_fwd(_p(feat), _p(wav_len), _p(masks), _p(mean), _p(istd), _p(out), _p(out_len), B, Tmax, n_mels, m, n,
-                                              Tlfr_max, _dt(out), _stream()), "asr_global_norm_augment_lfr_fwd")
-    return out, out_len
+    return _norm_aug_lfr("asr_global_norm_augment_lfr_fwd", feat, wav_len, m, n, Tlfr_max, dtype, mean, istd, masks=masks)
 
 
 def _specaug_ranges(ranges, B, counts):
-    """(ranges, ld, n_t, n_f, n_s) of a specaug launch: ranges (B, >= width) int32 whose rows may lie ld >= width words apart."""
+    """(ranges pointer, ld, n_t, n_f, n_s) of a specaug launch: ranges (B, >= width) int32 whose rows may lie ld >= width words apart."""
     n_t, n_f, n_s = (int(v) for v in counts)
     width = 2 + 2 * n_t + 2 * n_f + 3 * n_s
     if ranges.dtype != torch.int32 or ranges.dim() != 2 or ranges.shape[0] != B or ranges.shape[1] < width or (ranges.shape[1] > 1 and ranges.stride(1) != 1):
         raise ValueError(f"ranges must be (B = {B}, >= {width}) int32 with unit column stride, got {tuple(ranges.shape)} {ranges.dtype}")
     if min(n_t, n_f, n_s) < 0 or max(n_t, n_f, n_s) > _lib.SPECAUG_MAX_RANGES:
         raise ValueError(f"n_t, n_f, n_s = {n_t}, {n_f}, {n_s}: each 0 .. {_lib.SPECAUG_MAX_RANGES}")
-    return ranges, (ranges.stride(0) if B > 1 else ranges.shape[1]), n_t, n_f, n_s
+    return _p(ranges), (ranges.stride(0) if B > 1 else ranges.shape[1]), n_t, n_f, n_s
 
 
 def utt_norm_specaug_lfr(feat, wav_len, ranges, counts, m, n, Tlfr_max, dtype=torch.float32):
     """utt_norm_lfr with a SpecAugment policy (include/asr_hip.h; tests/specaug_ref.py): ranges (B, width) int32 rows
     [wc, ww | (t0, t1) x n_t | (f0, f1) x n_f | (s, e, p) x n_s], counts = (n_t, n_f, n_s)."""
-    _chk_f32(feat)
-    _chk_i32(wav_len)
-    B, Tmax, n_mels = feat.shape
-    assert wav_len.numel() == B
-    ranges, ld, n_t, n_f, n_s = _specaug_ranges(ranges, B, counts)
-    out = torch.empty(B, Tlfr_max, m * n_mels, dtype=dtype, device=feat.device)
-    out_len = torch.empty(B, dtype=torch.int32, device=feat.device)
-    check(lib.asr_utt_norm_specaug_lfr_fwd(_p(feat), _p(wav_len), _p(ranges), ld, n_t, n_f, n_s, _p(out), _p(out_len), B, Tmax, n_mels, m, n, Tlfr_max,
-                                           _dt(out), _stream()), "asr_utt_norm_specaug_lfr_fwd")
-    return out, out_len
+    return _norm_aug_lfr("asr_utt_norm_specaug_lfr_fwd", feat, wav_len, m, n, Tlfr_max, dtype, policy=(ranges, counts))
 
 
 def global_norm_specaug_lfr(feat, wav_len, ranges, counts, mean, istd, m, n, Tlfr_max, dtype=torch.float32):
     """global_norm_lfr with a SpecAugment policy: utt_norm_specaug_lfr under global CMVN, on the tiled grid of the no-mask call."""
-    _chk_f32(feat, mean, istd)
-    _chk_i32(wav_len)
-    B, Tmax, n_mels = feat.shape
-    assert mean.numel() == n_mels and istd.numel() == n_mels and wav_len.numel() == B
-    ranges, ld, n_t, n_f, n_s = _specaug_ranges(ranges, B, counts)
-    out = torch.empty(B, Tlfr_max, m * n_mels, dtype=dtype, device=feat.device)
-    out_len = torch.empty(B, dtype=torch.int32, device=feat.device)
-    check(lib.asr_global_norm_specaug_lfr_fwd(_p(feat), _p(wav_len), _p(ranges), ld, n_t, n_f, n_s, _p(mean), _p(istd), _p(out), _p(out_len), B, Tmax,
-                                              n_mels, m, n, Tlfr_max, _dt(out), _stream()), "asr_global_norm_specaug_lfr_fwd")
-    return out, out_len
+    return _norm_aug_lfr("asr_global_norm_specaug_lfr_fwd", feat, wav_len, m, n, Tlfr_max, dtype, mean, istd, policy=(ranges, counts))
 
 
 def _pow2(v):

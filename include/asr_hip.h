@@ -800,6 +800,17 @@ int asr_decoder_layer_bwd(const asr_dec_layer_plan* plan, const void* dy, const 
  * melfb: (201, n_mels) f32 filterbank; window: (400) f32.
  * The normalisation entry points below are not given Smax: their frame count is min(1 + wav_len[b]/160, Tmax), 0 for
  * wav_len[b] <= 0, so they stay inside feat whatever the length says.
+ *
+ * One kernel and one tile.  asr_logmel_fwd, asr_fbank_fwd and their streaming forms run one frame tile (DFT, power,
+ * filterbank, log), instantiated per front end behind its own frame preparation.  The six normalise-augment-stack entry
+ * points - asr_utt_norm_lfr_fwd, asr_utt_norm_augment_lfr_fwd, asr_global_norm_augment_lfr_fwd, asr_utt_norm_specaug_lfr_fwd,
+ * asr_global_norm_specaug_lfr_fwd here and below - launch one kernel (utterance or global normalisation x reference masks or
+ * policy row x f32 or bf16) through one launcher, so they refuse the same things in the same order: ASR_EINVAL for a null
+ * pointer, then for a shape (B, Tmax, n_mels, m, n, Tlfr_max < 1, or B > 65535), then for Tlfr_max * m * n_mels > INT32_MAX,
+ * then for a policy's row arguments; ASR_EDTYPE for a dtype other than f32 / bf16; nothing is launched after a refusal.
+ * Two of these refusals are newer than ABI 10's first release, both of calls that could not work: the utterance entry
+ * points used to let Tlfr_max * m * n_mels overflow an int inside the kernel, and they did not refuse B > 65535 (utterances
+ * are now the grid's y dimension on every path).
  */
 int asr_logmel_fwd(const float* wav, const int32_t* wav_len, const float* window,
                    const float* melfb, float* feat, int B, int Smax, int Tmax, int n_mels,
@@ -973,9 +984,9 @@ int asr_global_norm_augment_lfr_fwd(const float* feat, const int32_t* wav_len, c
  *      max((2 o + 1) n_in - n_out, 0), den = 2 n_out, i0 = num / den, i1 = min(i0 + 1, n_in - 1), w = f32(num % den) / f32(den),
  *      value = v0 + w * (v1 - v0) with v = x[base + i][f]: one fp32 division, subtraction, multiplication and addition, each
  *      rounded on its own (never contracted).
- * Frame stacking, out and out_len as the siblings; an all-zero row gives the bits of the siblings without masks.  No
- * reduction runs for the augmentation: the global variant keeps the tiled grid of its sibling's no-mask path.
- * ASR_EINVAL before any launch: a null pointer, n_* outside 0 .. 8, ld too small, the shape checks of the siblings.
+ * Frame stacking, out and out_len as the augment entry points (the same kernel); an all-zero row gives the bits of the call
+ * without masks.  No reduction runs for the augmentation: the global variant keeps the tiled grid of the no-mask call.
+ * ASR_EINVAL before any launch: a null pointer, n_* outside 0 .. 8, ld too small, the shared shape checks (asr_logmel_fwd above).
  */
 #define ASR_SPECAUG_MAX_RANGES 8
 int asr_utt_norm_specaug_lfr_fwd(const float* feat, const int32_t* wav_len, const int32_t* ranges, int ld, int n_t, int n_f,
@@ -1000,7 +1011,8 @@ int asr_global_norm_specaug_lfr_fwd(const float* feat, const int32_t* wav_len, c
  *                      the end as offline), ASR_STREAM_OPEN otherwise; the ring must hold samples
  *                      max(0, 160 t_begin - 200) .. the last one the frames touch.
  * asr_stream_norm_lfr: par (B, 3) = {r_begin, n_rows, Tb}: LFR rows r_begin .. r_begin + n_rows - 1 (n_rows <= C) under
- *                      global CMVN, by the function asr_global_norm_augment_lfr_fwd uses, into out (B, C, m n_mels) f32 or
+ *                      global CMVN, by the source rule and the expression asr_global_norm_augment_lfr_fwd's kernel uses
+ *                      (neither is written twice), into out (B, C, m n_mels) f32 or
  *                      bf16; rows past n_rows are zero.  Tb = the frame count of a closed utterance (tail rows repeat
  *                      frame Tb - 1), ASR_STREAM_OPEN otherwise.
  */
@@ -1029,7 +1041,8 @@ int asr_stream_norm_lfr(const float* feat_ring, const int32_t* par, const float*
  * The normalisation entry points above count frames as 1 + wav_len / 160: hand them 160 (T_b - 1) + 1 (0 for T_b = 0).
  *
  * asr_stream_fbank: the streaming twin on the rings of the streaming front end above.  par (B, 2) = {t_begin, n_new}: frames
- * t_begin .. t_begin + n_new - 1 (n_new <= max_new <= fcap) by the same tile body - bit for bit the offline frames.  No
+ * t_begin .. t_begin + n_new - 1 (n_new <= max_new <= fcap) by the same tile body - bit for bit the offline frames - and
+ * behind the same host check as asr_stream_logmel.  No
  * length is passed: the ring must hold samples 160 t_begin .. 160 (t_begin + n_new - 1) + 399.  wav_ring (B, scap) f32 and
  * feat_ring (B, fcap, n_mels) f32 as above; refused with ASR_EINVAL unless scap is a power of two of at least 1024, fcap a
  * power of two, 1 <= max_new <= fcap, n_mels >= 1 and 1 <= B <= 65535.
