@@ -2,24 +2,19 @@
 // (include/asr_hip.h: asr_cr_ctc_fwd_bwd; the definition is tests/cr_ctc_ref.py).  An HBM-bound pass over (2P, T, V) logits.
 //
 // Two kernels on one stream:
-//   1. cr_ctc_kernel   : one workgroup of 256 threads per (pair, frame).  Loads the frame's row of BOTH views once (16 B per thread and
-//      load; element by element when V is no multiple of the vector), per row block_max and the block's sum of exp(x - max), then per
+//   1. cr_ctc_kernel   : one workgroup of 256 threads per (pair, frame), the dense row pass of dense_row.h over the frame's row of BOTH
+//      views (in registers up to ASR_CR_CTC_RESIDENT_MAX_V elements, else read again for each of the three passes): per row block_max
+//      and the block's sum of exp(x - max), then per
 //      element p = exp(x - max) / sum, lp = x - lse, J += (p_a - p_b) (lp_a - lp_b), g = scale/2 (p_a - p_b) -> row a, -g -> row b.
-//      The exponentials are f32 (expf); their sum, p, lp and J are carried in fp64 (see the note below).  A row of up
-//      to CR_RESIDENT_MAX_V elements stays in registers from the load to the gradient store (CR_E values per thread and row); a longer one
-//      is read again for each of the three passes (it is L2-hot), with the same element-to-thread mapping, so that a thread adds the
-//      same terms in the same order on both paths.  Both rows go through one instruction sequence: identical views give exactly 0,
-//      swapped views swapped bytes.
+//      The exponentials are f32 (expf); their sum, p, lp and J are carried in fp64 (see the note below).  Both rows go through one
+//      instruction sequence: identical views give exactly 0, swapped views swapped bytes.
 //   2. cr_ctc_pair_sum_kernel : one workgroup per pair adds frame_loss[p, :] in frame order (fp64 accumulator, one thread, rows staged
 //      through LDS).  No atomics anywhere: two runs write the same bytes.
-#include "asr_common.h"
+#include "dense_row.h"
 
 namespace {
 
-constexpr int CR_THREADS = 256;
-constexpr int CR_E = ASR_CR_CTC_RESIDENT_MAX_V / CR_THREADS;      // elements per thread and row in registers: 24 (V = 4232: 17 of them used)
-static_assert(CR_E * CR_THREADS == ASR_CR_CTC_RESIDENT_MAX_V && CR_E % 8 == 0, "the resident cap is whole 16-byte vectors per thread");
-ASR_FULL_WAVES(CR_THREADS);
+constexpr int CR_THREADS = 256;      // elements per thread and row in registers: 6144 / 256 = 24 (V = 4232: 17 of them used)
 
 // Why fp64 behind the f32 exponentials: with peaked posteriors (logits spread over +-100) J is a sum of terms (p_a - p_b)(lp_a - lp_b) with
 // p ~ 1 and lp differences ~ 100, so a relative error of 6e-8 in a sum of exponentials (one f32 rounding) moves J by 6e-6 - more than the
@@ -27,74 +22,38 @@ ASR_FULL_WAVES(CR_THREADS);
 // pair of elements beside two expf and the memory traffic, and leave the f32 rounding of expf itself (p tiny wherever lp is large) and
 // of the results.  block_sum_f64 adds in one fixed order.
 
-// N: elements per access (Vec<T>::N, or 1 when V, ld or a base address is no multiple of the vector).  RES: the rows stay in registers.
-// Chunk c of a row = its elements [c N, c N + N); thread i owns the chunks i, i + 256, i + 512, ... on both paths.
+// N, RES: dense_row.h.  xa, xb = r.x[0], r.x[1]: the frame's row of view a and of view b.
 template <typename T, int N, bool RES>
 __global__ __launch_bounds__(CR_THREADS) void cr_ctc_kernel(const T* __restrict__ logits, T* __restrict__ grad, const int32_t* __restrict__ in_len,
                                                             float* __restrict__ frame_loss, int P, int T_, int V, int ld, float grad_scale,
                                                             const float* __restrict__ grad_scale_div, int accumulate) {
     __shared__ float red[16];
     __shared__ double red64[CR_THREADS / 64];
-    constexpr int KC = RES ? CR_E / N : 1;      // chunks per thread and row held in registers
     const int t = blockIdx.x, p = blockIdx.y, tid = threadIdx.x;
     const int n = min(max(min(in_len[p], in_len[p + P]), 0), T_);
     const size_t oa = ((size_t)p * T_ + t) * ld, ob = ((size_t)(p + P) * T_ + t) * ld;
     const int nch = V / N;      // N divides V on the vector path
     if (t >= n) {      // the whole workgroup: no barrier below is reached by a part of it
         if (tid == 0) frame_loss[(size_t)p * T_ + t] = 0.f;
-        if (grad && !accumulate) {
-            float z[N];
-#pragma unroll
-            for (int j = 0; j < N; ++j) z[j] = 0.f;
-            for (int c = tid; c < nch; c += CR_THREADS) {
-                storev<T, N>(grad + oa + (size_t)c * N, z);
-                storev<T, N>(grad + ob + (size_t)c * N, z);
-            }
-        }
+        if (grad && !accumulate) zero_row<T, N, CR_THREADS>(nch, grad + oa, grad + ob);
         return;
     }
-    const T* xa_g = logits + oa;
-    const T* xb_g = logits + ob;
-    float xa[KC][N], xb[KC][N];
-    // f(k, c): called for every chunk c of this thread, k its register slot.  RES: slots 0 .. KC-1, unrolled; else slot 0 in a loop
-    auto each = [&](auto&& f) {
-        if constexpr (RES) {
-#pragma unroll
-            for (int k = 0; k < KC; ++k) {
-                const int c = tid + CR_THREADS * k;
-                if (c < nch) f(k, c);
-            }
-        } else {
-            for (int c = tid; c < nch; c += CR_THREADS) f(0, c);
-        }
-    };
-    auto fetch = [&](int k, int c) {      // the path that re-reads loads the chunk in front of every use
-        if constexpr (!RES) {
-            loadv<T, N>(xa_g + (size_t)c * N, xa[k]);
-            loadv<T, N>(xb_g + (size_t)c * N, xb[k]);
-        }
-    };
-    if constexpr (RES) {
-#pragma unroll
-        for (int k = 0; k < KC; ++k) {      // all loads of both rows in flight at once
-            const int c = tid + CR_THREADS * k;
-            if (c < nch) {
-                loadv<T, N>(xa_g + (size_t)c * N, xa[k]);
-                loadv<T, N>(xb_g + (size_t)c * N, xb[k]);
-            }
-        }
-    }
+    DenseRows<T, N, RES, CR_THREADS, ASR_CR_CTC_RESIDENT_MAX_V, 2> r;
+    r.g[0] = logits + oa;
+    r.g[1] = logits + ob;
+    r.nch = nch;
+    r.load();
+    auto& xa = r.x[0];
+    auto& xb = r.x[1];
     float ma = -INFINITY, mb = -INFINITY;
-    each([&](int k, int c) {
-        fetch(k, c);
+    r.each([&](int k, int c) {
 #pragma unroll
         for (int j = 0; j < N; ++j) { ma = fmaxf(ma, xa[k][j]); mb = fmaxf(mb, xb[k][j]); }
     });
     ma = block_max(ma, red);
     mb = block_max(mb, red);
     double sa = 0.0, sb = 0.0;
-    each([&](int k, int c) {
-        fetch(k, c);
+    r.each([&](int k, int c) {
 #pragma unroll
         for (int j = 0; j < N; ++j) { sa += (double)expf(xa[k][j] - ma); sb += (double)expf(xb[k][j] - mb); }
     });
@@ -105,12 +64,11 @@ __global__ __launch_bounds__(CR_THREADS) void cr_ctc_kernel(const T* __restrict_
     float h = 0.f;
     if (grad) h = 0.5f * (grad_scale_div ? grad_scale / *grad_scale_div : grad_scale);
     double js = 0.0;
-    each([&](int k, int c) {
+    r.each([&](int k, int c) {
         // No contraction in this block (hipcc fuses a * b + c into one fma by default, across statements, and __dmul_rn / __fmul_rn are
         // plain products to it): p_a - p_b must be the difference of two ROUNDED products - as one fused multiply-subtract equal rows
         // gave 1e-20 instead of exactly 0 - and accumulate = 1 must add the rounded h * d that accumulate = 0 writes.
 #pragma clang fp contract(off)
-        fetch(k, c);
         float ga[N], gb[N];
 #pragma unroll
         for (int j = 0; j < N; ++j) {
@@ -154,44 +112,27 @@ __global__ __launch_bounds__(CR_THREADS) void cr_ctc_pair_sum_kernel(const float
     if (threadIdx.x == 0) pair_loss[p] = (float)acc;
 }
 
-template <typename T>
-void cr_ctc_launch(const void* logits, void* grad, const int32_t* in_len, float* frame_loss, int P, int T_, int V, int ld, float grad_scale,
-                   const float* grad_scale_div, int accumulate, hipStream_t st) {
-    constexpr int N = Vec<T>::N;
-    const bool vec = V % N == 0 && ld % N == 0 && (uintptr_t)logits % 16 == 0 && (uintptr_t)grad % 16 == 0;
-    const bool res = V <= ASR_CR_CTC_RESIDENT_MAX_V;
-    const dim3 grid(T_, P);
-#define CR_LAUNCH(N_, RES_) \
-    cr_ctc_kernel<T, N_, RES_><<<grid, CR_THREADS, 0, st>>>((const T*)logits, (T*)grad, in_len, frame_loss, P, T_, V, ld, grad_scale, grad_scale_div, accumulate)
-    if (vec && res) CR_LAUNCH(N, true);
-    else if (vec) CR_LAUNCH(N, false);
-    else if (res) CR_LAUNCH(1, true);
-    else CR_LAUNCH(1, false);
-#undef CR_LAUNCH
-}
-
 }  // namespace
 
 extern "C" int asr_cr_ctc_fwd_bwd(const void* logits, const int32_t* in_len, void* grad, float* frame_loss, float* pair_loss, int P, int T, int V,
                                   int ld, float grad_scale, const float* grad_scale_div, int accumulate, int dtype, void* stream) {
     const char* name = "asr_cr_ctc_fwd_bwd";
     if (!logits || !in_len || !frame_loss || !pair_loss) ASR_FAIL(ASR_EINVAL, "%s: null pointer", name);
-    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "%s: dtype %d", name, dtype);
-    const size_t es = dtype == ASR_F32 ? 4 : 2;
+    size_t es;
+    if (int rc = dense_check_dtype(name, dtype, &es)) return rc;
     if (((uintptr_t)in_len | (uintptr_t)frame_loss | (uintptr_t)pair_loss | (uintptr_t)grad_scale_div) % 4 || ((uintptr_t)logits | (uintptr_t)grad) % es)
         ASR_FAIL(ASR_EINVAL, "%s: misaligned pointer", name);
     if (P <= 0 || P > 65535 || T <= 0 || V < 2 || ld < V) ASR_FAIL(ASR_EINVAL, "%s: bad shape P=%d (1 .. 65535) T=%d V=%d ld=%d", name, P, T, V, ld);
-    if (accumulate != 0 && accumulate != 1) ASR_FAIL(ASR_EINVAL, "%s: accumulate=%d (0 or 1)", name, accumulate);
+    if (int rc = dense_check_accumulate(name, accumulate)) return rc;
     if (accumulate && !grad) ASR_FAIL(ASR_EINVAL, "%s: accumulate=1 needs the gradient block to add to", name);
-    if (!(grad_scale == grad_scale) || grad_scale - grad_scale != 0.f) ASR_FAIL(ASR_EINVAL, "%s: grad_scale is not finite", name);
-    if (grad) {      // both blocks span (2 P T - 1) ld + V elements
-        const size_t span = (((size_t)2 * P * T - 1) * ld + V) * es;
-        const uintptr_t a = (uintptr_t)logits, b = (uintptr_t)grad;
-        if (a < b + span && b < a + span) ASR_FAIL(ASR_EINVAL, "%s: the gradient block overlaps the logits (the logits are read after the first store)", name);
-    }
+    if (int rc = dense_check_grad_scale(name, grad_scale)) return rc;
+    if (grad && dense_overlap(logits, grad, (size_t)2 * P * T, V, ld, es))
+        ASR_FAIL(ASR_EINVAL, "%s: the gradient block overlaps the logits (the logits are read after the first store)", name);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == ASR_F32) cr_ctc_launch<float>(logits, grad, in_len, frame_loss, P, T, V, ld, grad_scale, grad_scale_div, accumulate, st);
-    else cr_ctc_launch<bf16_t>(logits, grad, in_len, frame_loss, P, T, V, ld, grad_scale, grad_scale_div, accumulate, st);
+    dense_row_dispatch<ASR_CR_CTC_RESIDENT_MAX_V>(dtype, V, ld, (uintptr_t)logits | (uintptr_t)grad, [&](auto e, auto n, auto res) {
+        using E = decltype(e);
+        cr_ctc_kernel<E, n, res><<<dim3(T, P), CR_THREADS, 0, st>>>((const E*)logits, (E*)grad, in_len, frame_loss, P, T, V, ld, grad_scale, grad_scale_div, accumulate);
+    });
     cr_ctc_pair_sum_kernel<<<P, CR_THREADS, 0, st>>>(frame_loss, pair_loss, T);
     ASR_CHECK_LAUNCH(name);
     return ASR_OK;

@@ -8,8 +8,8 @@
 //   2. ctc_alpha_beta : one workgroup of two waves per utterance.  Wave 0 runs the alpha
 //      recursion forward in time, wave 1 the beta recursion backward, state s on lane s%64
 //      (register j = s/64), predecessors via DPP wave shifts (no LDS in the recursion), lattice
-//      inputs prefetched 2 x 8 timesteps ahead in registers so the serial chain never waits on
-//      memory.  Linear domain, rescaled by the column maximum every 2 steps (logs of the scales
+//      inputs prefetched in chunks of 8 timesteps in registers so the serial chain never waits on
+//      memory (lattice_row_walk, which the forced alignment's Viterbi recursion runs too).  Linear domain, rescaled by the column maximum every 2 steps (logs of the scales
 //      summed for the loss): 5 VALU per step instead of 3 exp + 1 log.
 //   3. ctc_grad       : one workgroup per frame.  Wave 0 forms the frame's state posteriors
 //      softmax_s(alpha+beta-lp) (exact: the sum over s is p(l|x) at every t) and scatters them into an LDS
@@ -19,6 +19,9 @@
 //      lattice (see LATTICE_TINY); such an utterance is redone in the log domain.
 // Algorithmic HBM bytes: logits read twice + dlogits written once = 3 * B*T*V*e;
 // the lattice (B*T*S*4 B * 3 arrays) stays in L2 / Infinity Cache.
+// Host side: asr_ctc_fwd_bwd and asr_ctc_align share ctc_check (validation) and ctc_lattice_inputs (the launch of kernel 1).
+#include <type_traits>
+
 #include "asr_common.h"
 
 namespace {
@@ -292,12 +295,73 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
 // marked (nll_raw = NaN) and ctc_rescue_kernel redoes it in the log domain; +inf is left to the utterances whose LENGTHS are infeasible.
 constexpr double LATTICE_TINY = 0x1p-600;
 
-// W = row half-width (compile time: 32, 64, 128, 256), NS = registers per lane per array (entry
-// i = lane + 64 j).  Every load and store of the steady-state loop is unconditional, at an
-// immediate offset from one running pointer, and the loop body is one basic block, so the
+// The lattice row walk of both recursions (ctc_recursion, ctc_viterbi_recursion): steps 1 .. nsteps over the rows of the lattice inputs,
+// DT doubles apart (+-2W: forward or backward in time), prefetched in chunks of CH steps into NB register buffers.  NS = registers per
+// lane per array (entry i = lane + 64 j); yp = this lane's pair of the row of step 0.
+//   one_step(yv, off, k): one recursion step on the row yv; k = its place in its chunk (the scaled recursion's phases), off = its place
+//                         among the steps since the last advance() - the step stores at off rows from its own running pointer;
+//   advance(n)          : n steps are done, the step's pointer moves n rows.
+// Every load and store of the steady-state loop is unconditional, at an
+// immediate offset from one running pointer per array, and the loop body is one basic block, so the
 // compiler counts outstanding memory operations (s_waitcnt vmcnt(N), N > 0) and the prefetched
 // chunk really overlaps the dependent chain.  (With predicated loads it fell back to vmcnt(0)
 // per chunk: ~1.5 us of exposed latency 60 times per utterance.)
+template <int NS, ptrdiff_t DT, typename Step, typename Advance>
+__device__ __forceinline__ void lattice_row_walk(const double* __restrict__ yp, int nsteps, Step&& one_step, Advance&& advance) {
+    constexpr int CH = 8;  // steps per prefetch chunk; chunk c covers steps 1 + c*CH .. c*CH + CH
+    // Prefetch depth.  The recursion is a dependent chain of ~25 ns per frame; a lattice row comes from memory (written by the kernel before
+    // this one) in ~0.7 us.  With two chunk buffers (round 1 - 4) the chunk after the current one was requested one chunk = 8 frames earlier
+    // and every chunk ended in a wait for memory: 88 ns per frame.  NB buffers = NB - 1 chunks in flight; memory instructions per chunk =
+    // CH loads + CH stores (16-byte accesses; byte stores in the Viterbi walk), so three chunks in flight stay inside the 6-bit vmcnt
+    // counter (stores count too on gfx950).
+    constexpr int NB = NS == 1 ? 4 : 2;
+    struct Chunk { f64x2 v[CH][NS]; };
+    Chunk q[NB];
+    auto fetch = [&](Chunk& d, const double* p) {   // p = row of the chunk's first step
+#pragma unroll
+        for (int k = 0; k < CH; ++k)
+#pragma unroll
+            for (int j = 0; j < NS; ++j) d.v[k][j] = *(const f64x2*)(p + k * DT + 128 * j);
+    };
+    auto fetch_clamped = [&](Chunk& d, int chunk) {   // rows past the last frame are clamped to it (never used)
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            const int step = min(1 + chunk * CH + k, nsteps);
+#pragma unroll
+            for (int j = 0; j < NS; ++j) d.v[k][j] = *(const f64x2*)(yp + (ptrdiff_t)step * DT + 128 * j);
+        }
+    };
+    const int nfull = nsteps / CH;
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < NB - 1; ++i) fetch_clamped(q[i], i);      // q[i] = chunk c + i for i < NB - 1
+    const double* yq = yp + DT;   // row of step 1 + c*CH
+    // steady state: the chunks requested in an iteration (c + NB - 1 .. c + 2 NB - 2) are full, every access unconditional
+    for (; c + 2 * NB - 1 <= nfull; c += NB) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            fetch(q[(i + NB - 1) % NB], yq + (i + NB - 1) * CH * DT);
+#pragma unroll
+            for (int k = 0; k < CH; ++k) one_step(q[i].v[k], i * CH + k, k);
+        }
+        yq += NB * CH * DT;
+        advance(NB * CH);
+    }
+    // the last chunks (fewer than 2 NB, the last one possibly partial); q[0 .. NB-2] hold chunks c .. c + NB - 2
+    for (; c * CH < nsteps; ++c) {
+        fetch_clamped(q[NB - 1], c + NB - 1);
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            if (1 + c * CH + k > nsteps) break;
+            one_step(q[0].v[k], k, k);
+        }
+        advance(CH);
+#pragma unroll
+        for (int i = 0; i + 1 < NB; ++i) q[i] = q[i + 1];
+    }
+}
+
+// W = row half-width (compile time: 32, 64, 128, 256), NS as in lattice_row_walk.
 // Returns ln of the scale taken out (true value = stored value * exp(ret)), or -inf once every
 // state has become 0 (infeasible alignment).
 template <int W, bool BWD>
@@ -331,32 +395,10 @@ __device__ __forceinline__ double ctc_recursion(const double* __restrict__ y, do
         const f64x2 o0 = {bk[j], lb[j]};
         *(f64x2*)(op + 128 * j) = o0;
     }
-    constexpr int CH = 8;  // steps per prefetch chunk; chunk c covers steps 1 + c*CH .. c*CH + CH
-    // Prefetch depth.  The recursion is a dependent chain of ~25 ns per frame; a lattice row comes from memory (written by the kernel before
-    // this one) in ~0.7 us.  With two chunk buffers (round 1 - 4) the chunk after the current one was requested one chunk = 8 frames earlier
-    // and every chunk ended in a wait for memory: 88 ns per frame.  NB buffers = NB - 1 chunks in flight; memory instructions per chunk =
-    // CH loads + CH stores (16-byte accesses), so three chunks in flight stay inside the 6-bit vmcnt counter (stores count too on gfx950).
-    constexpr int NB = NS == 1 ? 4 : 2;
-    const int nsteps = Tb - 1;            // recursion steps 1 .. Tb-1
-    struct Chunk { f64x2 v[CH][NS]; };
-    Chunk q[NB];
-    auto fetch = [&](Chunk& d, const double* p) {   // p = row of the chunk's first step
-#pragma unroll
-        for (int k = 0; k < CH; ++k)
-#pragma unroll
-            for (int j = 0; j < NS; ++j) d.v[k][j] = *(const f64x2*)(p + k * DT + 128 * j);
-    };
-    auto fetch_clamped = [&](Chunk& d, int chunk) {   // rows past the last frame are clamped to it (never used)
-#pragma unroll
-        for (int k = 0; k < CH; ++k) {
-            const int step = min(1 + chunk * CH + k, nsteps);
-#pragma unroll
-            for (int j = 0; j < NS; ++j) d.v[k][j] = *(const f64x2*)(yp + (ptrdiff_t)step * DT + 128 * j);
-        }
-    };
     double sc = 1.0;   // power-of-two scale waiting to be applied
     int e_pending = 0;
-    auto one_step = [&](const f64x2 (&yv)[NS], double* o, int k) {
+    double* oq = op + DT;   // output row of the first step since the last advance
+    auto one_step = [&](const f64x2 (&yv)[NS], int off, int k) {
         double yb[NS], yl[NS];
 #pragma unroll
         for (int j = 0; j < NS; ++j) { yb[j] = yv[j][0]; yl[j] = yv[j][1]; }
@@ -406,38 +448,10 @@ __device__ __forceinline__ double ctc_recursion(const double* __restrict__ y, do
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
             const f64x2 ov = {bk[j], lb[j]};
-            *(f64x2*)(o + 128 * j) = ov;
+            *(f64x2*)(oq + off * DT + 128 * j) = ov;
         }
     };
-    const int nfull = nsteps / CH;
-    int c = 0;
-#pragma unroll
-    for (int i = 0; i < NB - 1; ++i) fetch_clamped(q[i], i);      // q[i] = chunk c + i for i < NB - 1
-    const double* yq = yp + DT;   // row of step 1 + c*CH
-    double* oq = op + DT;
-    // steady state: the chunks requested in an iteration (c + NB - 1 .. c + 2 NB - 2) are full, every access unconditional
-    for (; c + 2 * NB - 1 <= nfull; c += NB) {
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            fetch(q[(i + NB - 1) % NB], yq + (i + NB - 1) * CH * DT);
-#pragma unroll
-            for (int k = 0; k < CH; ++k) one_step(q[i].v[k], oq + (i * CH + k) * DT, k);
-        }
-        yq += NB * CH * DT;
-        oq += NB * CH * DT;
-    }
-    // the last chunks (fewer than 2 NB, the last one possibly partial); q[0 .. NB-2] hold chunks c .. c + NB - 2
-    for (; c * CH < nsteps; ++c) {
-        fetch_clamped(q[NB - 1], c + NB - 1);
-#pragma unroll
-        for (int k = 0; k < CH; ++k) {
-            if (1 + c * CH + k > nsteps) break;
-            one_step(q[0].v[k], oq + k * DT, k);
-        }
-        oq += CH * DT;
-#pragma unroll
-        for (int i = 0; i + 1 < NB; ++i) q[i] = q[i + 1];
-    }
+    lattice_row_walk<NS, DT>(yp, Tb - 1, one_step, [&](int n) { oq += n * DT; });      // recursion steps 1 .. Tb-1
     return dead ? -INFINITY : (double)esum * 0.6931471805599453;
 }
 
@@ -830,26 +844,8 @@ __device__ __forceinline__ void ctc_viterbi_recursion(const double* __restrict__
         bk[j] = i == 0 ? y0[0] : -INFINITY;
         lb[j] = i == 0 ? y0[1] : -INFINITY;
     }
-    constexpr int CH = 8;
-    constexpr int NB = NS == 1 ? 4 : 2;   // chunk buffers, as ctc_recursion (CH loads + CH byte stores per chunk)
-    const int nsteps = Tb - 1;
-    struct Chunk { f64x2 v[CH][NS]; };
-    Chunk q[NB];
-    auto fetch = [&](Chunk& d, const double* p) {
-#pragma unroll
-        for (int k = 0; k < CH; ++k)
-#pragma unroll
-            for (int j = 0; j < NS; ++j) d.v[k][j] = *(const f64x2*)(p + k * RW + 128 * j);
-    };
-    auto fetch_clamped = [&](Chunk& d, int chunk) {
-#pragma unroll
-        for (int k = 0; k < CH; ++k) {
-            const int step = min(1 + chunk * CH + k, nsteps);
-#pragma unroll
-            for (int j = 0; j < NS; ++j) d.v[k][j] = *(const f64x2*)(yp + (ptrdiff_t)step * RW + 128 * j);
-        }
-    };
-    auto one_step = [&](const f64x2 (&yv)[NS], uint8_t* o) {
+    uint8_t* oq = op + W;               // back-pointer row of the first step since the last advance
+    auto one_step = [&](const f64x2 (&yv)[NS], int off, int) {
         double nb[NS], nl[NS];
         unsigned code[NS];
 #pragma unroll
@@ -868,35 +864,9 @@ __device__ __forceinline__ void ctc_viterbi_recursion(const double* __restrict__
 #pragma unroll
         for (int j = 0; j < NS; ++j) { bk[j] = nb[j]; lb[j] = nl[j]; }
 #pragma unroll
-        for (int j = 0; j < NS; ++j) o[64 * j] = (uint8_t)code[j];
+        for (int j = 0; j < NS; ++j) oq[off * W + 64 * j] = (uint8_t)code[j];
     };
-    const int nfull = nsteps / CH;
-    int c = 0;
-#pragma unroll
-    for (int i = 0; i < NB - 1; ++i) fetch_clamped(q[i], i);
-    const double* yq = yp + RW;
-    uint8_t* oq = op + W;
-    for (; c + 2 * NB - 1 <= nfull; c += NB) {
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            fetch(q[(i + NB - 1) % NB], yq + (i + NB - 1) * CH * RW);
-#pragma unroll
-            for (int k = 0; k < CH; ++k) one_step(q[i].v[k], oq + (i * CH + k) * W);
-        }
-        yq += NB * CH * RW;
-        oq += NB * CH * W;
-    }
-    for (; c * CH < nsteps; ++c) {
-        fetch_clamped(q[NB - 1], c + NB - 1);
-#pragma unroll
-        for (int k = 0; k < CH; ++k) {
-            if (1 + c * CH + k > nsteps) break;
-            one_step(q[0].v[k], oq + k * W);
-        }
-        oq += CH * W;
-#pragma unroll
-        for (int i = 0; i + 1 < NB; ++i) q[i] = q[i + 1];
-    }
+    lattice_row_walk<NS, RW>(yp, Tb - 1, one_step, [&](int n) { oq += n * W; });      // the prefetch of ctc_recursion
     fin_b = -INFINITY;
     fin_l = -INFINITY;
 #pragma unroll
@@ -1125,30 +1095,25 @@ __global__ __launch_bounds__(256) void xent_kernel(const T* __restrict__ logits,
 static inline int width_of(int Lmax) { return Lmax < 32 ? 32 : Lmax < 64 ? 64 : Lmax < 128 ? 128 : 256; }
 static inline int smax_of(int Lmax) { return 2 * width_of(Lmax); }
 
-}  // namespace
-
-extern "C" size_t asr_ctc_workspace_bytes(int B, int T, int Lmax) {
-    return (size_t)3 * B * T * smax_of(Lmax) * sizeof(double) + ((size_t)B * T + (size_t)B) * sizeof(float);
+// the checks asr_ctc_fwd_bwd and asr_ctc_align share (after their own null-pointer check); a workspace below ws_need fails with ws_code
+int ctc_check(const char* name, int B, int T, int V, int ld, int Lmax, int blank, size_t ws_bytes, size_t ws_need, int ws_code, int dtype) {
+    if (B <= 0 || T <= 0 || V <= 1 || Lmax <= 0 || blank < 0 || blank >= V) ASR_FAIL(ASR_EINVAL, "%s: bad shape B=%d T=%d V=%d Lmax=%d blank=%d", name, B, T, V, Lmax, blank);
+    if (ld < V || (ld != V && ld % 8)) ASR_FAIL(ASR_EINVAL, "%s: row stride ld=%d (V=%d): V, or a multiple of 8 above it", name, ld, V);
+    if (Lmax > 255) ASR_FAIL(ASR_EINVAL, "%s: Lmax = %d: label sequences longer than 255 are not supported", name, Lmax);
+    if (ws_bytes < ws_need) ASR_FAIL(ws_code, "%s: workspace %zu < %zu", name, ws_bytes, ws_need);
+    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "%s: dtype %d", name, dtype);
+    return ASR_OK;
 }
 
-extern "C" int asr_ctc_fwd_bwd(const void* logits, void* dlogits, const int32_t* in_len, const int32_t* labels, const int32_t* lab_len,
-                               float* nll, int B, int T, int V, int ld, int Lmax, int blank, float grad_scale, const float* grad_scale_div,
-                               int zero_infinity, int32_t* best_path, void* ws, size_t ws_bytes, int dtype, void* stream) {
-    if (!logits || !in_len || !labels || !lab_len || !nll || !ws) ASR_FAIL(ASR_EINVAL, "asr_ctc_fwd_bwd: null pointer");
-    if (B <= 0 || T <= 0 || V <= 1 || Lmax <= 0 || blank < 0 || blank >= V) ASR_FAIL(ASR_EINVAL, "asr_ctc_fwd_bwd: bad shape B=%d T=%d V=%d Lmax=%d blank=%d", B, T, V, Lmax, blank);
-    if (ld < V || (ld != V && ld % 8)) ASR_FAIL(ASR_EINVAL, "asr_ctc_fwd_bwd: row stride ld=%d (V=%d): V, or a multiple of 8 above it", ld, V);
-    if (Lmax > 255) ASR_FAIL(ASR_EINVAL, "asr_ctc_fwd_bwd: Lmax = %d: label sequences longer than 255 are not supported", Lmax);
-    if (ws_bytes < asr_ctc_workspace_bytes(B, T, Lmax)) ASR_FAIL(ASR_EWORKSPACE, "asr_ctc_fwd_bwd: workspace %zu < %zu", ws_bytes, asr_ctc_workspace_bytes(B, T, Lmax));
-    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "asr_ctc_fwd_bwd: dtype %d", dtype);
-    const size_t lds = (size_t)((V + 3) & ~3) * sizeof(float);
-    if (dlogits && lds > 160 * 1024 && !(dtype == ASR_BF16 && V % 8 == 0 && V <= 8192)) ASR_FAIL(ASR_EINVAL, "asr_ctc_fwd_bwd: V=%d does not fit the LDS posterior table", V);
-    hipStream_t st = (hipStream_t)stream;
-    const int W = width_of(Lmax), Smax = 2 * W;
-    double* lp = (double*)ws;
-    double* alpha = lp + (size_t)B * T * Smax;
-    double* beta = alpha + (size_t)B * T * Smax;
-    float* lse = (float*)(beta + (size_t)B * T * Smax);
-    float* nll_raw = lse + (size_t)B * T;
+template <int I> using int_c = std::integral_constant<int, I>;
+
+// Kernel 1 of both entry points: the lattice inputs lp and lse of every frame, LOGD for the forced alignment.  With dlogits the rows path
+// also writes scale * softmax, with best_path the greedy path (off the rows path: asr_ctc_frame_argmax, in front of the gradient kernel
+// that may overwrite the logits in place).  *g1 = the grid of the one-wave-per-frame kernels, *rows_path = the row-in-registers kernels ran.
+template <bool LOGD>
+int ctc_lattice_inputs(const void* logits, void* dlogits, int32_t* best_path, const int32_t* in_len, const int32_t* labels, const int32_t* lab_len,
+                       double* lp, float* lse, int B, int T, int V, int ld, int Lmax, int W, int blank, float grad_scale, const float* grad_scale_div,
+                       int dtype, hipStream_t st, int* g1_out, bool* rows_path_out) {
     const int rows = B * T;
     int g1 = ceil_div(rows, 4);
     if (g1 > 4096) g1 = 4096;
@@ -1159,41 +1124,71 @@ extern "C" int asr_ctc_fwd_bwd(const void* logits, void* dlogits, const int32_t*
     // bf16 rows of whole 16-byte vectors that fit a wave's registers take the row-in-registers kernels
     const int need = ceil_div(V / 8, 64);
     const bool rows_path = dtype == ASR_BF16 && V % 8 == 0 && ld % 8 == 0 && need <= 16 && ((uintptr_t)logits % 16) == 0 && (!dlogits || ((uintptr_t)dlogits % 16) == 0);
-#define ROWS_DISPATCH(CALL)           \
-    do {                              \
-        if (need <= 2) { CALL(2); }   \
-        else if (need <= 4) { CALL(4); }   \
-        else if (need <= 6) { CALL(6); }   \
-        else if (need <= 9) { CALL(9); }   \
-        else if (need <= 12) { CALL(12); } \
-        else { CALL(16); }            \
-    } while (0)
-    if (best_path && !rows_path) {      // fp32 / odd shapes: the decoding kernel, in front of the gradient kernel that may overwrite the logits in place
-        const int rc = asr_ctc_frame_argmax(logits, in_len, best_path, B, T, V, ld, blank, dtype, stream);
+    *g1_out = g1;
+    *rows_path_out = rows_path;
+    if (best_path && !rows_path) {      // fp32 / odd shapes: the decoding kernel
+        const int rc = asr_ctc_frame_argmax(logits, in_len, best_path, B, T, V, ld, blank, dtype, (void*)st);
         if (rc != ASR_OK) return rc;
     }
     if (rows_path) {
         // with a gradient: the softmax part of it is written by the same wave that reduces the row (one pass over the logits less than
         // with a separate row-in-registers gradient kernel: 110 vs 127 us; that kernel, ctc_grad_rows_kernel, is in the git history)
-        if (dlogits && best_path) {
-#define K1(NV) ctc_lse_gather_rows_kernel<NV, true, true><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank, (bf16_t*)dlogits, grad_scale, grad_scale_div, best_path)
-            ROWS_DISPATCH(K1);
-#undef K1
-        } else if (dlogits) {
-#define K1(NV) ctc_lse_gather_rows_kernel<NV, true, false><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank, (bf16_t*)dlogits, grad_scale, grad_scale_div, nullptr)
-            ROWS_DISPATCH(K1);
-#undef K1
-        } else if (best_path) {
-#define K1(NV) ctc_lse_gather_rows_kernel<NV, false, true><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank, nullptr, 0.f, nullptr, best_path)
-            ROWS_DISPATCH(K1);
-#undef K1
-        } else {
-#define K1(NV) ctc_lse_gather_rows_kernel<NV, false, false><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank, nullptr, 0.f, nullptr, nullptr)
-            ROWS_DISPATCH(K1);
-#undef K1
-        }
-    } else if (dtype == ASR_F32) ctc_lse_gather_kernel<float, false><<<g1, 256, 0, st>>>((const float*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
-    else ctc_lse_gather_kernel<bf16_t, false><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
+        auto launch = [&](auto write, auto path) {
+            constexpr bool WRITE = decltype(write)::value, PATH = decltype(path)::value;
+            auto k1 = [&](auto nv) {
+                ctc_lse_gather_rows_kernel<decltype(nv)::value, WRITE, PATH, LOGD><<<g1, 256, 0, st>>>(
+                    (const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank, WRITE ? (bf16_t*)dlogits : nullptr,
+                    WRITE ? grad_scale : 0.f, WRITE ? grad_scale_div : nullptr, PATH ? best_path : nullptr);
+            };
+            if (need <= 2) k1(int_c<2>());
+            else if (need <= 4) k1(int_c<4>());
+            else if (need <= 6) k1(int_c<6>());
+            else if (need <= 9) k1(int_c<9>());
+            else if (need <= 12) k1(int_c<12>());
+            else k1(int_c<16>());
+        };
+        if constexpr (LOGD) launch(std::false_type(), std::false_type());      // the alignment has neither
+        else if (dlogits && best_path) launch(std::true_type(), std::true_type());
+        else if (dlogits) launch(std::true_type(), std::false_type());
+        else if (best_path) launch(std::false_type(), std::true_type());
+        else launch(std::false_type(), std::false_type());
+    } else if (dtype == ASR_F32) ctc_lse_gather_kernel<float, LOGD><<<g1, 256, 0, st>>>((const float*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
+    else ctc_lse_gather_kernel<bf16_t, LOGD><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
+    return ASR_OK;
+}
+
+// one launch; arm: it may carry the stream's armed completion event (asr_launch_armed)
+template <typename... KArgs, typename... Args>
+void launch_maybe_armed(bool arm, void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t st, Args... args) {
+    if (arm) asr_launch_armed(kernel, grid, block, 0, st, args...);
+    else kernel<<<grid, block, 0, st>>>(static_cast<KArgs>(args)...);
+}
+
+}  // namespace
+
+extern "C" size_t asr_ctc_workspace_bytes(int B, int T, int Lmax) {
+    return (size_t)3 * B * T * smax_of(Lmax) * sizeof(double) + ((size_t)B * T + (size_t)B) * sizeof(float);
+}
+
+extern "C" int asr_ctc_fwd_bwd(const void* logits, void* dlogits, const int32_t* in_len, const int32_t* labels, const int32_t* lab_len,
+                               float* nll, int B, int T, int V, int ld, int Lmax, int blank, float grad_scale, const float* grad_scale_div,
+                               int zero_infinity, int32_t* best_path, void* ws, size_t ws_bytes, int dtype, void* stream) {
+    if (!logits || !in_len || !labels || !lab_len || !nll || !ws) ASR_FAIL(ASR_EINVAL, "asr_ctc_fwd_bwd: null pointer");
+    if (int rc = ctc_check("asr_ctc_fwd_bwd", B, T, V, ld, Lmax, blank, ws_bytes, asr_ctc_workspace_bytes(B, T, Lmax), ASR_EWORKSPACE, dtype)) return rc;
+    const size_t lds = (size_t)((V + 3) & ~3) * sizeof(float);
+    if (dlogits && lds > 160 * 1024 && !(dtype == ASR_BF16 && V % 8 == 0 && V <= 8192)) ASR_FAIL(ASR_EINVAL, "asr_ctc_fwd_bwd: V=%d does not fit the LDS posterior table", V);
+    hipStream_t st = (hipStream_t)stream;
+    const int W = width_of(Lmax), Smax = 2 * W;
+    double* lp = (double*)ws;
+    double* alpha = lp + (size_t)B * T * Smax;
+    double* beta = alpha + (size_t)B * T * Smax;
+    float* lse = (float*)(beta + (size_t)B * T * Smax);
+    float* nll_raw = lse + (size_t)B * T;
+    const int rows = B * T;
+    int g1;
+    bool rows_path;
+    if (int rc = ctc_lattice_inputs<false>(logits, dlogits, best_path, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank, grad_scale, grad_scale_div, dtype, st, &g1, &rows_path))
+        return rc;
 #define AB(N) ctc_alpha_beta_kernel<N><<<B, 128, 0, st>>>(lp, alpha, beta, in_len, labels, lab_len, nll, nll_raw, T, Lmax, blank, zero_infinity)
     if (W == 32) AB(32);
     else if (W == 64) AB(64);
@@ -1208,11 +1203,15 @@ extern "C" int asr_ctc_fwd_bwd(const void* logits, void* dlogits, const int32_t*
         else ctc_grad_kernel<bf16_t><<<g3, 256, lds, st>>>((const bf16_t*)logits, (bf16_t*)dlogits, lp, alpha, beta, lse, in_len, labels, lab_len, nll_raw, B, T, V, ld, Lmax, W, blank, grad_scale, asr_deterministic(), grad_scale_div);
     }
     if (!dlogits) ctc_frame_check_kernel<<<g1, 256, 0, st>>>(lp, alpha, beta, in_len, lab_len, nll_raw, B, T, W);
-    // utterances whose lattice left the fp64 range (marked by the kernels above): redone in the log domain; a workgroup of any other returns at once
-    if (rows_path && dlogits) {
-        asr_launch_armed(ctc_rescue_kernel<bf16_t>, dim3(B), dim3(256), 0, st, lp, alpha, in_len, labels, lab_len, nll, nll_raw, (bf16_t*)dlogits, T, V, ld, Lmax, W, blank, grad_scale, grad_scale_div, zero_infinity);      // last kernel: may carry an armed completion event
-    } else if (dtype == ASR_F32) ctc_rescue_kernel<float><<<B, 256, 0, st>>>(lp, alpha, in_len, labels, lab_len, nll, nll_raw, (float*)dlogits, T, V, ld, Lmax, W, blank, grad_scale, grad_scale_div, zero_infinity);
-    else ctc_rescue_kernel<bf16_t><<<B, 256, 0, st>>>(lp, alpha, in_len, labels, lab_len, nll, nll_raw, (bf16_t*)dlogits, T, V, ld, Lmax, W, blank, grad_scale, grad_scale_div, zero_infinity);
+    // utterances whose lattice left the fp64 range (marked by the kernels above): redone in the log domain; a workgroup of any other returns at once.
+    // The last kernel: on the bf16 rows path with a gradient it may carry an armed completion event
+    auto rescue = [&](auto e) {
+        using E = decltype(e);
+        launch_maybe_armed(rows_path && dlogits, ctc_rescue_kernel<E>, dim3(B), dim3(256), st, lp, alpha, in_len, labels, lab_len, nll, nll_raw, (E*)dlogits, T, V, ld, Lmax, W, blank,
+                           grad_scale, grad_scale_div, zero_infinity);
+    };
+    if (dtype == ASR_F32) rescue(0.f);
+    else rescue(bf16_t());
     ASR_CHECK_LAUNCH("asr_ctc_fwd_bwd");
     return ASR_OK;
 }
@@ -1243,32 +1242,16 @@ extern "C" int asr_ctc_align(const void* logits, const int32_t* in_len, const in
                              int32_t* spans, float* token_logp, float* score, int B, int T, int V, int ld, int Lmax, int blank, void* ws,
                              size_t ws_bytes, int dtype, void* stream) {
     if (!logits || !in_len || !labels || !lab_len || !path || !spans || !token_logp || !score || !ws) ASR_FAIL(ASR_EINVAL, "asr_ctc_align: null pointer");
-    if (B <= 0 || T <= 0 || V <= 1 || Lmax <= 0 || blank < 0 || blank >= V) ASR_FAIL(ASR_EINVAL, "asr_ctc_align: bad shape B=%d T=%d V=%d Lmax=%d blank=%d", B, T, V, Lmax, blank);
-    if (ld < V || (ld != V && ld % 8)) ASR_FAIL(ASR_EINVAL, "asr_ctc_align: row stride ld=%d (V=%d): V, or a multiple of 8 above it", ld, V);
-    if (Lmax > 255) ASR_FAIL(ASR_EINVAL, "asr_ctc_align: Lmax = %d: label sequences longer than 255 are not supported", Lmax);
-    const size_t need = asr_ctc_align_workspace_bytes(B, T, Lmax);
-    if (ws_bytes < need) ASR_FAIL(ASR_EINVAL, "asr_ctc_align: workspace %zu < %zu", ws_bytes, need);
-    if (dtype != ASR_F32 && dtype != ASR_BF16) ASR_FAIL(ASR_EDTYPE, "asr_ctc_align: dtype %d", dtype);
+    if (int rc = ctc_check("asr_ctc_align", B, T, V, ld, Lmax, blank, ws_bytes, asr_ctc_align_workspace_bytes(B, T, Lmax), ASR_EINVAL, dtype)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int W = width_of(Lmax);
     double* lp = (double*)ws;
     uint8_t* bp = (uint8_t*)(lp + (size_t)B * T * 2 * W);
     float* lse = (float*)(bp + (size_t)B * T * W);
-    const int rows = B * T;
-    int g1 = ceil_div(rows, 4);
-    if (g1 > 4096) g1 = 4096;
-    const int cu_lim = asr_option(ASR_OPT_CU_LIMIT);
-    if (cu_lim > 0 && g1 > 8 * cu_lim) g1 = 8 * cu_lim;
     // kernel 1 of asr_ctc_fwd_bwd without gradient or path: the logits are read once into the lattice, kept as log-probabilities
-    const int need_v = ceil_div(V / 8, 64);
-    const bool rows_path = dtype == ASR_BF16 && V % 8 == 0 && ld % 8 == 0 && need_v <= 16 && ((uintptr_t)logits % 16) == 0;
-    if (rows_path) {
-        const int need = need_v;
-#define K1(NV) ctc_lse_gather_rows_kernel<NV, false, false, true><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank, nullptr, 0.f, nullptr, nullptr)
-        ROWS_DISPATCH(K1);
-#undef K1
-    } else if (dtype == ASR_F32) ctc_lse_gather_kernel<float, true><<<g1, 256, 0, st>>>((const float*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
-    else ctc_lse_gather_kernel<bf16_t, true><<<g1, 256, 0, st>>>((const bf16_t*)logits, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank);
+    int g1;
+    bool rows_path;
+    (void)ctc_lattice_inputs<true>(logits, nullptr, nullptr, in_len, labels, lab_len, lp, lse, B, T, V, ld, Lmax, W, blank, 0.f, nullptr, dtype, st, &g1, &rows_path);
     const bool lds_bp = (size_t)T * W <= (size_t)VIT_LDS_BP;
     const size_t lds = lds_bp ? (size_t)T * W : (size_t)VIT_LDS_BP;
 #define VIT(N, M)                                                                                                                        \

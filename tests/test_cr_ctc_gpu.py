@@ -23,9 +23,20 @@ SENTINEL = 768.0      # exact in bf16
 CAP = 6144            # kernels.CR_CTC_RESIDENT_MAX_V (asserted below): the longest row the kernel keeps in registers
 LENS9 = {1: [12, 9], 3: [9, 0, 1, 8, 0, 1], 4: [9, 0, 1, 5, 9, 0, 1, 4]}      # a zero-length pair, a one-frame pair, views one frame apart; 12 > T is clamped
 # (P, T, V, ld or None): P in {1, 3}, T in {1, 9}, V in {2, 5, 64, 257} and 4232 in rows of 4288; the issue's four-pair lengths; the cap and
-# the cap plus one (the path that reads the rows again, with vectors and element by element), and a row of whole vectors above the cap
+# the cap plus one (the path that reads the rows again, with vectors and element by element), and a row of whole vectors above the cap;
+# whole vectors in V and ld behind a base address that is no multiple of 16 bytes (element by element for the address alone)
+
+
+class Shifted(int):
+    """A row stride whose blocks - the logits and every output block - begin one element into a 16-byte-aligned allocation."""
+
+    def __repr__(self):
+        return "%d+1" % int(self)
+
+
 SHAPES = ([(P, T, V, None) for P in (1, 3) for T in (1, 9) for V in (2, 5, 64, 257)] +
-          [(1, 1, 4232, 4288), (3, 9, 4232, 4288), (4, 9, 64, None), (1, 2, CAP, None), (1, 2, CAP + 1, None), (1, 2, CAP + 8, None)])
+          [(1, 1, 4232, 4288), (3, 9, 4232, 4288), (4, 9, 64, None), (1, 2, CAP, None), (1, 2, CAP + 1, None), (1, 2, CAP + 8, None),
+           (1, 2, 64, Shifted(72))])
 SPREADS = (1.0, 60.0)      # at 60 float32 probabilities underflow while the loss stays finite
 
 
@@ -55,7 +66,14 @@ def device_rows(x, ld, fill=SENTINEL):
     R, T, V = x.shape
     buf = torch.full((R, T, ld), fill, dtype=x.dtype)
     buf[:, :, :V] = x
-    buf = buf.to(DEV)
+    if isinstance(ld, Shifted):
+        flat = torch.empty(buf.numel() + 1, dtype=x.dtype, device=DEV)
+        assert flat.data_ptr() % 16 == 0
+        flat[1:] = buf.reshape(-1).to(DEV)
+        buf = flat[1:].view(R, T, ld)
+        assert buf.data_ptr() % 16 == x.element_size()
+    else:
+        buf = buf.to(DEV)
     return buf[:, :, :V], buf
 
 
@@ -113,7 +131,7 @@ def test_kernel_matches_the_definition(K, P, T, V, ld, spread, dtype, record_pro
         assert np.array_equal(raw[:P], -raw[P:])
 
 
-BYTES_SHAPES = [(3, 9, 257, None), (3, 9, 4232, 4288), (3, 9, 64, None), (1, 2, CAP + 8, None), (1, 2, CAP + 1, None)]
+BYTES_SHAPES = [(3, 9, 257, None), (3, 9, 4232, 4288), (3, 9, 64, None), (1, 2, CAP + 8, None), (1, 2, CAP + 1, None), (1, 2, 64, Shifted(72))]
 
 
 def _bytes(t):
@@ -129,25 +147,29 @@ def test_bytes(K, P, T, V, ld, dtype):
     xh = torch.from_numpy(logits).to(dtype)
     x, _ = device_rows(xh, ld)
     n_dev = _i32(in_len)
-    a = K.cr_ctc(x, n_dev, grad_scale=0.37)
-    b = K.cr_ctc(x, n_dev, grad_scale=0.37)
+
+    def out():      # a shifted case gets a shifted gradient block too; the others leave the block to the call
+        return dict(dlogits=device_rows(torch.zeros(2 * P, T, V, dtype=dtype), ld)[0]) if isinstance(ld, Shifted) else {}
+
+    a = K.cr_ctc(x, n_dev, grad_scale=0.37, **out())
+    b = K.cr_ctc(x, n_dev, grad_scale=0.37, **out())
     for k in ("cr", "frame", "dlogits"):
         assert torch.equal(_bytes(a[k]), _bytes(b[k])), k
     assert bool((a["dlogits"] != 0).any())
     # the scale through the device scalar: s = (2 s) / 2
-    c = K.cr_ctc(x, n_dev, grad_scale=0.74, grad_scale_div=torch.tensor([2.0], device=DEV))
+    c = K.cr_ctc(x, n_dev, grad_scale=0.74, grad_scale_div=torch.tensor([2.0], device=DEV), **out())
     assert torch.equal(_bytes(c["dlogits"]), _bytes(a["dlogits"])) and torch.equal(_bytes(c["cr"]), _bytes(a["cr"]))
     # no gradient wanted: the same values
     v = K.cr_ctc(x, n_dev, want_grad=False)
     assert v["dlogits"] is None and torch.equal(_bytes(v["cr"]), _bytes(a["cr"])) and torch.equal(_bytes(v["frame"]), _bytes(a["frame"]))
     # swapped halves: swapped gradient, the same cr and frame
     xs, _ = device_rows(torch.cat([xh[P:], xh[:P]]), ld)
-    s = K.cr_ctc(xs, _i32(np.concatenate([in_len[P:], in_len[:P]])), grad_scale=0.37)
+    s = K.cr_ctc(xs, _i32(np.concatenate([in_len[P:], in_len[:P]])), grad_scale=0.37, **out())
     assert torch.equal(_bytes(s["cr"]), _bytes(a["cr"])) and torch.equal(_bytes(s["frame"]), _bytes(a["frame"]))
     assert torch.equal(_bytes(s["dlogits"][:P]), _bytes(a["dlogits"][P:])) and torch.equal(_bytes(s["dlogits"][P:]), _bytes(a["dlogits"][:P]))
     # identical views: exactly zero
     xi, _ = device_rows(torch.cat([xh[:P], xh[:P]]), ld)
-    z = K.cr_ctc(xi, n_dev, grad_scale=0.37)
+    z = K.cr_ctc(xi, n_dev, grad_scale=0.37, **out())
     assert bool((z["frame"] == 0).all()) and bool((z["cr"] == 0).all()) and bool((z["dlogits"] == 0).all())
     # accumulate = 1 over a random prior
     n = np.minimum(np.clip(in_len[:P], 0, T), np.clip(in_len[P:], 0, T))
@@ -158,7 +180,7 @@ def test_bytes(K, P, T, V, ld, dtype):
     g = torch.Generator().manual_seed(3)
     width = ld if ld is not None else V
     prior_full = torch.randn(2 * P, T, width, generator=g).to(dtype)
-    buf = prior_full.to(DEV)
+    buf = device_rows(prior_full, ld)[1] if isinstance(ld, Shifted) else prior_full.to(DEV)
     K.cr_ctc(x, n_dev, grad_scale=0.37, dlogits=buf[:, :, :V], accumulate=True)
     got_full = buf.cpu()
     got, prior, added = got_full[:, :, :V], prior_full[:, :, :V], a["dlogits"].cpu()

@@ -29,9 +29,19 @@ CAP = 6144            # kernels.INTERCTC_RESIDENT_MAX_V (asserted below): the lo
 # one utterance of length 0, one of length 1 and one full (12 > T is clamped)
 LENS = {(1, 1): [1], (1, 9): [9], (3, 1): [0, 1, 1], (3, 9): [0, 1, 12], (1, 2): [2]}
 # (B, T, V, ld or None): B in {1, 3}, T in {1, 9}, V in {2, 5, 64, 257} and 4232 in rows of 4288; the cap, the cap plus one (the path that
-# reads the rows again, element by element) and a row of whole vectors above the cap
+# reads the rows again, element by element) and a row of whole vectors above the cap; whole vectors in V and ld behind a base address
+# that is no multiple of 16 bytes (element by element for the address alone)
+
+
+class Shifted(int):
+    """A row stride whose blocks - the inputs and every output block - begin one element into a 16-byte-aligned allocation."""
+
+    def __repr__(self):
+        return "%d+1" % int(self)
+
+
 SHAPES = ([(B, T, V, None) for B in (1, 3) for T in (1, 9) for V in (2, 5, 64, 257)] +
-          [(1, 1, 4232, 4288), (3, 9, 4232, 4288), (1, 2, CAP, None), (1, 2, CAP + 1, None), (1, 2, CAP + 8, None)])
+          [(1, 1, 4232, 4288), (3, 9, 4232, 4288), (1, 2, CAP, None), (1, 2, CAP + 1, None), (1, 2, CAP + 8, None), (1, 2, 64, Shifted(72))])
 SPREADS = (1.0, 60.0)
 
 
@@ -63,7 +73,14 @@ def device_rows(x, ld, fill=SENTINEL):
     B, T, V = x.shape
     buf = torch.full((B, T, ld), fill, dtype=x.dtype)
     buf[:, :, :V] = x
-    buf = buf.to(DEV)
+    if isinstance(ld, Shifted):
+        flat = torch.empty(buf.numel() + 1, dtype=x.dtype, device=DEV)
+        assert flat.data_ptr() % 16 == 0
+        flat[1:] = buf.reshape(-1).to(DEV)
+        buf = flat[1:].view(B, T, ld)
+        assert buf.data_ptr() % 16 == x.element_size()
+    else:
+        buf = buf.to(DEV)
     return buf[:, :, :V], buf
 
 
@@ -146,7 +163,7 @@ def test_kernels_match_the_definition(K, B, T, V, ld, spread, dtype, record_prop
     _keep_parity(row)
 
 
-BYTES_SHAPES = [(3, 9, 257, None), (3, 9, 4232, 4288), (3, 9, 64, None), (1, 2, CAP + 8, None), (1, 2, CAP + 1, None)]
+BYTES_SHAPES = [(3, 9, 257, None), (3, 9, 4232, 4288), (3, 9, 64, None), (1, 2, CAP + 8, None), (1, 2, CAP + 1, None), (1, 2, 64, Shifted(72))]
 
 
 def _bytes(t):
@@ -162,7 +179,11 @@ def test_bytes(K, B, T, V, ld, dtype):
     r = reference(B, T, V, 1.0, dtype)
     n_dev, n = _i32(r["in_len"]), np.clip(r["in_len"], 0, T)
     x, _ = device_rows(r["z"], ld)
-    a, b = K.softmax_rows(x, n_dev), K.softmax_rows(x, n_dev)
+
+    def out():      # a shifted case gets a shifted output block too; the others leave the block to the call
+        return dict(out=device_rows(torch.zeros(B, T, V, dtype=dtype), ld)[0]) if isinstance(ld, Shifted) else {}
+
+    a, b = K.softmax_rows(x, n_dev, **out()), K.softmax_rows(x, n_dev, **out())
     assert torch.equal(_bytes(a), _bytes(b)) and bool((a != 0).any())
     dp, _ = device_rows(r["dp"], ld)
     prior, _ = device_rows(r["prior"], ld)
@@ -181,7 +202,7 @@ def test_bytes(K, B, T, V, ld, dtype):
     if T > 2:
         z[full, 1, :] = float("-inf")
     xz, _ = device_rows(z, ld)
-    p = K.softmax_rows(xz, n_dev)
+    p = K.softmax_rows(xz, n_dev, **out())
     torch.cuda.synchronize()
     assert bool(torch.isfinite(p.float()).all())
     row0, last = p[full, 0].float().cpu(), p[full, T - 1].float().cpu()
